@@ -3,7 +3,7 @@
 the body of the reference's fd_forward loop, cuda_reference_RTM/src/fd-code.cu:259-267) on a synthetic
 grid, device resident.  One JSON line on rank 0.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--size 8192] [--ksteps 4] [--no-cpu-baseline]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--size 8192] [--ksteps 4] [--no-cpu-baseline] [--dump-outputs DIR]
 
 N = 1 : the whole grid on one MI355X.
 N > 1 : one rank per GPU; the SAME grid is split into x slabs with deep-halo exchange over RCCL inside
@@ -16,8 +16,13 @@ N > 1 : one rank per GPU; the SAME grid is split into x slabs with deep-halo exc
         switched off: 1 - t_stub / t).
 
 Metric: Gpoints/s = nxe*nze*K / wall (barrier + synchronize on both sides, max over ranks).
-Timing: the K-step window (barrier + synchronize on both sides) is repeated until 0.3 s have been measured; the MEDIAN window is
-reported, so --steps 20 and --steps 1000 give the same Gpoints/s.
+Timing: W untimed warm-up steps, then ONE window of exactly K steps (barrier + synchronize on both sides): --steps sets the number of
+timed steps and ms_per_step = window / K.  Before it, untimed repetitions of the window for 0.3 s bring the clocks up, and the fields
+are then put back to their state after the W warm-up steps.  --max-windows M > 1 repeats the K-step window until 0.3 s have been measured (at most M times)
+and reports the MEDIAN window instead.
+--dump-outputs DIR (forward workload, N = 1): after the timed window, the two fields a caller of the loop receives -- the reference's
+(d_p, d_pp) after its last step -- as DIR/p.npy and DIR/pp.npy (float32 [n][n]; on grids above 2048^2 the same seeded sample of
+DUMP_SAMPLE points of each, see dump_fields).  Inputs are seeded, so the same arguments give the same files on every run of one build.
 roofline: bound = HBM.  `achieved` = HBM-side bytes one launch moves / its duration (HIP events on the launch stream): the bytes are the
 rocprofv3 --pmc figure of profiles/traffic.json when that profile was taken on exactly this kernel build (source hash), otherwise the
 minimum one launch must move (12 B in + 8 B out per point for a multi-step pass).  SURVEY.md 8(d)'s 16 B/point/step model -- which a
@@ -108,7 +113,7 @@ MIN_BYTES_PER_POINT_PER_LAUNCH = 20.0   # what any launch of the forward kernels
 #                                         (the one-step kernel: 12 + 4 = the 16 B of the model above)
 HBM_PEAK_GBS = 8000.0         # MI355X HBM3E spec (MI355X_MICROARCH.md); ~6.3 TB/s is what a copy achieves
 ORDER, NB, FAC, DX, DT, FPEAK = 8, 64, 0.75, 10.0, 1.0e-3, 20.0
-MIN_TIMED_SECONDS = 0.3       # the K-step window is repeated until this much time has been measured; the median window is reported
+MIN_TIMED_SECONDS = 0.3       # --max-windows M > 1: the K-step window is repeated until this much time has been measured; the median is reported
 
 
 KERNEL_SOURCES = {      # the translation units behind each workload's dominant kernel (+ the shared device header and argument structs)
@@ -185,19 +190,34 @@ def reference_sibling_cpu(m, nti):
                       f"(dpct_gpu_rtm_domain_division/src, g++ -O3 as its Makefiles build them: oracle/_ref/libref_dd.so), single thread, {dt:.1f} s"}
 
 
-MAX_WINDOWS = [400]      # --max-windows: debugging aid (a short, fixed sequence of shots)
+MAX_WINDOWS = [1]        # --max-windows: repetitions of the K-step window (1: exactly --steps timed steps)
+DUMP_SAMPLE = 1 << 22    # --dump-outputs: points per field beyond which a fixed sample is written (2 x 16 MiB of float32 at most)
 
 
-def timed_windows(window, sync_all, world, dev, max_windows=None):
-    """Times `window()` (EXACTLY K steps, enqueue only) bracketed by barrier + synchronize on both sides, max over ranks; repeats the window
-    until MIN_TIMED_SECONDS have been measured and returns (median wall seconds, median device ms between HIP events, windows).  A 20-step
-    window at 8192^2 lasts 2.6 ms -- shorter than the clock ramp and than anything that samples the GPU; its median over ~100 windows equals
-    what a 1000-step window gives."""
+def dump_fields(dirname, fields, n):
+    """--dump-outputs: writes each [n][>= n] device field of `fields` ({name: tensor}) as dirname/<name>.npy, float32.  Up to DUMP_SAMPLE
+    points the whole [n][n] field; above, the values at the flat indices np.unique(default_rng(0).integers(0, n * n, DUMP_SAMPLE)) of the
+    [n][n] field in row-major order (the same points for every field and every run of the same --size)."""
+    os.makedirs(dirname, exist_ok=True)
+    idx = None
+    if n * n > DUMP_SAMPLE:
+        flat = np.unique(np.random.default_rng(0).integers(0, n * n, DUMP_SAMPLE, dtype=np.int64))
+        idx = [torch.from_numpy(a).to(next(iter(fields.values())).device) for a in (flat // n, flat % n)]
+    for name, f in fields.items():
+        a = f[:, :n] if idx is None else f[idx[0], idx[1]]
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(a.float().cpu().numpy(), dtype=np.float32))
+
+
+def timed_windows(window, sync_all, world, dev, max_windows=None, restore=None):
+    """Times `window()` (EXACTLY K steps, enqueue only) bracketed by barrier + synchronize on both sides, max over ranks.  By default once
+    (--max-windows 1: --steps is the number of timed steps), after untimed repetitions of the window for MIN_TIMED_SECONDS that bring the
+    clocks up (a window right after a short warm-up runs ~10 % slow) and `restore()`, which puts the fields back where they were before
+    them, so that the timed window continues from the W warm-up steps.  With --max-windows M > 1 the window is repeated until
+    MIN_TIMED_SECONDS have been measured or M windows have run.  Returns (median wall seconds, median device ms between HIP events, windows)."""
     import torch.distributed as dist
     max_windows = min(max_windows or MAX_WINDOWS[0], MAX_WINDOWS[0])
-    walls, devs = [], []
-    total = 0.0
-    while True:
+
+    def one():
         sync_all()
         t0 = time.perf_counter()
         dev_ms = window()
@@ -207,10 +227,20 @@ def timed_windows(window, sync_all, world, dev, max_windows=None):
             t = torch.tensor([wall], device=dev, dtype=torch.float64)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             wall = float(t.item())            # every rank sees the same number, so every rank stops after the same window
+        return wall, dev_ms
+
+    if max_windows == 1:
+        spent = 0.0
+        while spent < MIN_TIMED_SECONDS:
+            spent += one()[0]
+        if restore is not None:
+            restore()
+    walls, devs = [], []
+    while True:
+        wall, dev_ms = one()
         walls.append(wall)
         devs.append(dev_ms)
-        total += wall
-        if total >= MIN_TIMED_SECONDS or len(walls) >= max_windows:
+        if sum(walls) >= MIN_TIMED_SECONDS or len(walls) >= max_windows:
             break
     return float(np.median(walls)), float(np.median(devs)), len(walls)
 
@@ -716,7 +746,16 @@ def run_rtm_slab_workload(args):
         sync(me)
         return (time.perf_counter() - t0) * 1e3
 
-    wall, _, nwin = timed_windows(window, sync_all, world, dev)
+    snap = {"fld": [f_.clone() for f_ in me["fld"]], "img": me["img"].clone(), "ip": me["ip"], "ipp": me["ipp"]}
+
+    def restore():
+        for f_, s_ in zip(me["fld"], snap["fld"]):
+            f_.copy_(s_)
+        me["img"].copy_(snap["img"])
+        me["ip"], me["ipp"] = snap["ip"], snap["ipp"]
+
+    wall, _, nwin = timed_windows(window, sync_all, world, dev, restore=restore)
+    del snap
     g = me["g"]
     img_own = me["img"][g.g_lo:g.nxl - g.g_hi, :n]
     finite = bool(torch.isfinite(img_own).all().item())
@@ -889,7 +928,11 @@ def main():
                     help="exact (default, what `value` always reports in the default run): the reference's arithmetic operation for operation, bit-identical "
                          "to the oracle; fast: fdw_params.numerics = FDW_NUMERICS_FAST (symmetric sums + fused multiply-adds in the Laplacian, within "
                          "1e-5 of exact) for the whole run -- profiling and scaling runs of that mode; the default run prints it beside the headline")
-    ap.add_argument("--max-windows", type=int, default=400, help="cap on the repetitions of the timed window (debugging aid: a short, fixed sequence)")
+    ap.add_argument("--max-windows", type=int, default=1,
+                    help="repetitions of the K-step timed window (default 1: exactly --steps timed steps); M > 1: repeat until 0.3 s are measured, "
+                         "at most M times, and report the median window")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="forward workload, N = 1: write the fields the timed loop leaves after its last step (p, pp) as DIR/<name>.npy")
     ap.add_argument("--no-extra", action="store_true", help="forward workload, N = 1, default size: skip the extra 4096^2 / 1000-step line (BASELINE.json configs[1])")
     ap.add_argument("--no-fast-line", action="store_true", help="forward workload, N = 1: skip the extra measurement in FAST numerics")
     ap.add_argument("--init", choices=["noise", "rest"], default="noise",
@@ -902,6 +945,8 @@ def main():
             sys.exit("bench: no GPU visible (the product has no CPU path)")
         return rccl_rehearsal_main(args.rccl_rehearsal)
     MAX_WINDOWS[0] = max(1, args.max_windows)
+    if args.dump_outputs and args.workload != "forward":
+        sys.exit("bench: --dump-outputs is implemented for the forward workload")
     if os.environ.get("FDW_BENCH_POISON") == "1":
         poison_free_memory()
     if args.workload == "rtm-slab":
@@ -922,6 +967,8 @@ def main():
         if world == 1 and args.gpus > 1:
             sys.exit("bench.py --gpus N>1 must be launched with torch.distributed.run (one rank per GPU)")
         args.gpus = world
+    if args.dump_outputs and world > 1:
+        sys.exit("bench: --dump-outputs needs --gpus 1")
     if not torch.cuda.is_available():
         sys.exit("bench.py needs an MI355X: no GPU visible (the product has no CPU path)")
     if args.backend != "nccl" or os.environ.get("FDW_BENCH_SHARE_GPU") == "1":
@@ -1032,8 +1079,18 @@ def main():
             stream.synchronize()
             return e0.elapsed_time(e1)
 
-        wall, dev_ms, nwin = timed_windows(window, sync_all, world, dev)
+        snap, snap_roles = [b_.clone() for b_ in bufs], dict(roles)
+
+        def restore():
+            for b_, s_ in zip(bufs, snap):
+                b_.copy_(s_)
+            roles.update(snap_roles)
+
+        wall, dev_ms, nwin = timed_windows(window, sync_all, world, dev, restore=restore)
+        del snap
         newest = bufs[roles["ipp"]].clone()
+        if args.dump_outputs:           # before the extra lines below reuse the buffers
+            dump_fields(args.dump_outputs, {"p": bufs[roles["ip"]], "pp": bufs[roles["ipp"]]}, n)
         if args.init == "noise" and not args.no_rest_line:
             # BASELINE.md section 4's literal initial condition beside the headline: zero fields + the Ricker source at the grid centre, the
             # same K steps from time index 0.  It runs faster (a mostly-zero wavefield draws less power and the issue-bound kernel clocks
@@ -1137,8 +1194,18 @@ def main():
             slabs.synchronize()
             return (time.perf_counter() - t0) * 1e3
 
-        wall, dev_ms, nwin = timed_windows(window, sync_all, world, dev)
+        snap, snap_roles = [f_.clone() for f_ in fields], dict(roles)
+
+        def restore():
+            for f_, s_ in zip(fields, snap):
+                f_.copy_(s_)
+            roles.update(snap_roles)
+
+        wall, dev_ms, nwin = timed_windows(window, sync_all, world, dev, restore=restore)
+        del snap
         newest = fields[roles["ipp"]][geom.g_lo:geom.nxl - geom.g_hi]
+        if args.dump_outputs:
+            dump_fields(args.dump_outputs, {k: fields[roles[r]][geom.g_lo:geom.nxl - geom.g_hi] for k, r in (("p", "ip"), ("pp", "ipp"))}, n)
     finite = bool(torch.isfinite(newest).all().item()) and float(newest.abs().max().item()) > 0.0
     if world > 1:
         f = torch.tensor([1.0 if finite else 0.0])

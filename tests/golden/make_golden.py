@@ -24,6 +24,9 @@ oracle/Makefile from cuda_reference_RTM/lib/src/functions.c).  No reference sour
   psnr_reference_output.json  stdout (and the SHA-256 of ./dir.output) of the reference's own comparer models/marmousi/psnr -- an x86-64 ELF
                               shipped without source -- run here on pairs of the fixtures above: known answers of bin/psnr / fdw_image_compare
   dd_3lay_mod_dir_imalap.f32  output of the reference's laplace.f90 (built unmodified with flang: oracle/_ref/lapfilt) run on that dir.image
+  reference_function_outputs.npz  outputs of oracle/_ref (functions.c, and the sibling's fd.c / taper.c / ptsrc.c) on the inputs the
+                              tests of tests/test_oracle_golden.py draw, recorded by running those tests live: where oracle/_ref is
+                              not built they compare the oracle with these
 """
 import ctypes as C
 import os
@@ -119,6 +122,15 @@ def main():
     # the reference never seeds rand(): the first extendvel_linear call of a process sees seed 1
     out["extvel_new_mod_seed1"] = ref_extend(vk, 315, 195, 50, 50, 1)
     np.savez_compressed(os.path.join(HERE, "host_tables.npz"), **out)
+    # the live comparisons of tests/test_oracle_golden.py, recorded (they also compare the oracle with the live outputs while recording)
+    assert O.ref_dd_lib() is not None, "build oracle/_ref/libref_dd.so first (make -C oracle)"
+    sys.path.insert(0, os.path.dirname(HERE))
+    import test_oracle_golden as T
+    T._RECORD = {}
+    for test in (T.test_oracle_against_live_reference_library, T.test_modelling_passes_match_the_reference_functions,
+                 T.test_taper_apply2_matches_the_reference_function):
+        test()
+    np.savez_compressed(T.REF_OUTPUTS, **T._RECORD)
     print("golden fixtures written to", HERE)
 
 
