@@ -14,6 +14,7 @@
 #include <cstring>
 #include <mutex>
 #include <new>
+#include <type_traits>
 #include <vector>
 
 #include "fdw_internal.h"
@@ -36,13 +37,6 @@ int fdw_fail(int code, const char* fmt, ...)
     return code;
 }
 #define fail fdw_fail
-
-#define HIP_TRY(call)                                                                                     \
-    do {                                                                                                  \
-        hipError_t e_ = (call);                                                                           \
-        if (e_ != hipSuccess) return fail(FDW_EHIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), \
-                                          __FILE__, __LINE__);                                            \
-    } while (0)
 
 extern "C" const char* fdw_last_error(void) { return g_err; }
 extern "C" int fdw_version(void) { return FDW_VERSION; }
@@ -392,6 +386,91 @@ static void fill_geometry(const fdw_ctx* c, StepArgs& a, int rows, int batch = 1
     a.nper = (a.nblk + 7) / 8;
 }
 
+// ---- launch arguments: what the one-step, two-step and wave-pipeline kernels share ----------------------
+// inj_x of a launch without a point source.  It matches no row, also after a batch's shift inj_x + b * inj_dx (|b * inj_dx| < nxl), and lies
+// far outside the halo rows the multi-step kernels look at for a source (inj_x >= xa - H).
+constexpr int kNoRow = -1000000;
+
+// field pointers, geometry, numerics and the coefficient table (EXACT or FAST weights; taps beyond the order are 0)
+template <class A>
+static void fill_common(const fdw_ctx* c, A& a, const float* d_p, decltype(A::pp) d_pp, const float* d_v2, int pp_twice)
+{
+    a.p = d_p; a.pp = d_pp; a.v2 = d_v2;
+    a.taperz = c->d_taperz; a.txfac = c->d_txfac;
+    a.pitch = c->pitch; a.nxl = c->nxl;
+    a.lap_x0 = c->lap_x0; a.lap_x1 = c->lap_x1; a.lap_z0 = c->lap_z0; a.lap_z1 = c->lap_z1;
+    if constexpr (std::is_same_v<A, Step2Args>) a.upd_x1 = c->upd_x1;
+    a.upd_z1 = c->upd_z1;
+    a.ztap = c->ztap; a.tz_x1 = c->tz_x1; a.xt_lo = c->xt_lo; a.xt_hi = c->xt_hi;
+    a.pp_twice = pp_twice ? 1 : 0;
+    a.img_z1 = c->prm.nzb + std::min(c->nz, c->zlim);      // kernel_img: interior columns j < zlim && j < nz (R:133-144)
+    a.dt2 = c->dt2;
+    a.c0 = c->c0;
+    a.numerics = c->prm.numerics;
+    a.dx2inv = c->dx2inv; a.dz2inv = c->dz2inv;            // read by the instantiations of the sibling's dialects only
+    const bool fastw = c->prm.numerics == FDW_NUMERICS_FAST;      // (for the RTM dialect fcx / fcz are cx / cz)
+    for (int io = 0; io <= 2 * kMaxFastHalfOrder; io++) {
+        a.cx[io] = io <= c->prm.order ? (fastw ? c->fcx[io] : c->cx[io]) : 0.0f;
+        a.cz[io] = io <= c->prm.order ? (fastw ? c->fcz[io] : c->cz[io]) : 0.0f;
+    }
+}
+
+// the modelling dialect (mod_main): the weights of the 7x7 Gaussian source and this step's trace row, rec[r - rec_x0] = p(r, rec_z)
+template <class A>
+static int fill_mod(const fdw_ctx* c, A& a, const char* who, float* d_rec, int rec_z)
+{
+    if (d_rec && (rec_z < 0 || rec_z >= c->prm.nze)) return fail(FDW_EINVAL, "%s: receiver depth %d outside the grid", who, rec_z);
+    for (int i = 0; i < 4; i++)
+        for (int j = 0; j < 4; j++) a.gw[i][j] = expf(-(float)(i * i) - (float)(j * j));   // ptsrc.c:53 with exp(float) as g++ resolves it
+    a.rec = d_rec; a.rec_z = rec_z;
+    a.rec_x0 = c->prm.nxb - c->slab.x_off; a.rec_n = c->nx;
+    return FDW_OK;
+}
+
+// where a launch injects, in local rows: from row x (kNoRow: nowhere), n receiver rows (0 for a point source); the sample of row x sits at
+// `shift` in the caller's sample row
+struct Injection {
+    int x = kNoRow, n = 0;
+    ptrdiff_t shift = 0;
+};
+
+// The point source of a FWD / DD_FWD / MOD launch at global (sx, sz).  None without samples, nor at sx < 0 outside the modelling dialect
+// (the callers' "no source").  A row outside this slab matches no row of the launch.
+static int place_source(const fdw_ctx* c, const char* who, bool mod, const float* d_inj, int sx, int sz, Injection* in)
+{
+    if (!d_inj || (!mod && sx < 0)) return FDW_OK;
+    if (sz < 0 || sz >= c->prm.nze || sx < 0 || sx >= c->prm.nxe) return fail(FDW_EINVAL, "%s: source (%d,%d) outside the grid", who, sx, sz);
+    in->x = sx - c->slab.x_off;
+    if (in->x >= c->upd_x1 && in->x < c->nxl)
+        return fail(FDW_EINVAL, "%s: source row %d lies in rows the reference never time-steps (>= %d)", who, sx, c->xlim);
+    return FDW_OK;
+}
+
+// Receivers at depth gz on the interior rows off .. off+nx-1 (R:126-129: off = nxb) below xlim, clipped to this slab.  The sibling's rtm_main
+// offsets them by nzb instead (PP[ix+nzb][gz], rtm_main.cpp:203) -- the same thing only when both borders are equally wide; kept as is.
+static int place_receivers(const fdw_ctx* c, const char* who, int off, int gz, Injection* in)
+{
+    if (gz < 0 || gz >= c->prm.nze) return fail(FDW_EINVAL, "%s: receiver depth %d outside the grid", who, gz);
+    if (off + c->nx > c->prm.nxe) return fail(FDW_EINVAL, "%s: receiver rows [%d,%d) leave the grid", who, off, off + c->nx);
+    const int l0 = std::max(off - c->slab.x_off, 0), l1 = std::min(off + std::min(c->nx, c->xlim) - c->slab.x_off, c->nxl);
+    in->x = l0;
+    in->n = std::max(0, l1 - l0);
+    in->shift = l0 + c->slab.x_off - off;
+    return FDW_OK;
+}
+
+// Receiver rows [x, x+n) from upd_x1 up to r1 lie beyond the time-stepped rows (narrow x border + truncated extents): the reference still
+// injects into them and images them.  `samples` holds row x's sample.
+static int static_receiver_rows(fdw_ctx* c, int x, int n, int r1, float* field, const float* samples, const float* psrc, float* img, int gz,
+                                int img_z1, hipStream_t s)
+{
+    const int s0 = std::max(x, c->upd_x1), s1 = std::min(x + n, r1);
+    if (s1 <= s0) return FDW_OK;
+    hipError_t e = launch_static_rows(field, psrc, img, samples + (s0 - x), c->pitch, s0, s1 - s0, gz, c->prm.nzb, img_z1, s);
+    if (e != hipSuccess) return fail(FDW_EHIP, "static-row launch failed: %s", hipGetErrorString(e));
+    return FDW_OK;
+}
+
 static int step_impl(fdw_ctx* c, int mode, const float* d_p, float* d_pp, const float* d_v2, int r0, int r1,
                      int pp_twice, const float* d_inj, int inj_x_global, int inj_z, const float* d_psrc, float* d_img,
                      hipStream_t s, float* d_rec_row = nullptr, int rec_z = 0, float* d_fpp = nullptr, float* d_out = nullptr)
@@ -414,60 +493,22 @@ static int step_impl(fdw_ctx* c, int mode, const float* d_p, float* d_pp, const 
         return fail(FDW_EINVAL, "step: a separate output array is supported by the DD_FWD register-ring kernel only, and must not alias the inputs");
 
     StepArgs a{};
-    a.p = d_p; a.pp = d_pp; a.v2 = d_v2; a.psrc = d_psrc; a.img = d_img; a.fpp = d_fpp;
+    fill_common(c, a, d_p, d_pp, d_v2, pp_twice);
+    a.psrc = d_psrc; a.img = d_img; a.fpp = d_fpp;
     a.out = d_out;            // NULL: in place over pp
-    a.taperz = c->d_taperz; a.txfac = c->d_txfac; a.inj = d_inj; a.gcx = c->d_gcx; a.gcz = c->d_gcz;
-    a.pitch = c->pitch; a.nxl = c->nxl;
+    a.gcx = c->d_gcx; a.gcz = c->d_gcz;
     a.r0 = r0;
     a.r1 = lap ? r1 : std::min(r1, c->upd_x1);   // rows >= xlim are never time-stepped (R:83-87)
-    a.lap_x0 = lap ? c->slap_x0 : c->lap_x0; a.lap_x1 = lap ? c->slap_x1 : c->lap_x1;
-    a.lap_z0 = lap ? c->slap_z0 : c->lap_z0; a.lap_z1 = lap ? c->slap_z1 : c->lap_z1;
-    a.upd_z1 = c->upd_z1;
-    a.ztap = c->ztap; a.tz_x1 = c->tz_x1; a.xt_lo = c->xt_lo; a.xt_hi = c->xt_hi;
-    a.pp_twice = pp_twice ? 1 : 0;
-    a.img_z1 = c->prm.nzb + std::min(c->nz, c->zlim);      // kernel_img: interior columns j < zlim && j < nz (R:133-144)
-    a.inj_x = -1; a.inj_z = inj_z; a.inj_n = 0;
-    if (mode == FDW_MODE_DD_FWD || mode == FDW_MODE_DD_RECV) { a.dx2inv = c->dx2inv; a.dz2inv = c->dz2inv; }
-    if ((mode == FDW_MODE_FWD || mode == FDW_MODE_DD_FWD) && d_inj && inj_x_global >= 0) {
-        if (inj_z < 0 || inj_z >= c->prm.nze || inj_x_global >= c->prm.nxe)
-            return fail(FDW_EINVAL, "step: source (%d,%d) outside the grid", inj_x_global, inj_z);
-        a.inj_x = inj_x_global - c->slab.x_off;   // may fall outside this slab: then no row matches
-        if (a.inj_x >= c->upd_x1 && a.inj_x < c->nxl)
-            return fail(FDW_EINVAL, "step: source row %d lies in rows the reference never time-steps (>= %d)", inj_x_global, c->xlim);
-    } else if (mode == FDW_MODE_MOD) {
-        if (d_inj) {
-            if (inj_z < 0 || inj_z >= c->prm.nze || inj_x_global < 0 || inj_x_global >= c->prm.nxe)
-                return fail(FDW_EINVAL, "step: source (%d,%d) outside the grid", inj_x_global, inj_z);
-            a.inj_x = inj_x_global - c->slab.x_off;
-        } else {
-            a.inj_x = -1000000;
-        }
-        for (int i = 0; i < 4; i++)
-            for (int j = 0; j < 4; j++) a.gw[i][j] = expf(-(float)(i * i) - (float)(j * j));   // ptsrc.c:53 with exp(float) as g++ resolves it
-        a.dx2inv = c->dx2inv; a.dz2inv = c->dz2inv;
-        a.rec = d_rec_row; a.rec_z = rec_z;
-        a.rec_x0 = c->prm.nxb - c->slab.x_off; a.rec_n = c->nx;
-        if (d_rec_row && (rec_z < 0 || rec_z >= c->prm.nze)) return fail(FDW_EINVAL, "step: receiver depth %d outside the grid", rec_z);
-    } else if (mode == FDW_MODE_RECV || mode == FDW_MODE_DD_RECV || mode == FDW_MODE_BACK) {
-        if (inj_z < 0 || inj_z >= c->prm.nze) return fail(FDW_EINVAL, "step: receiver depth %d outside the grid", inj_z);
-        // receivers sit on interior columns nxb..nxb+nx-1 (R:126-129); clip to this slab.  The sibling's rtm_main offsets them by
-        // nzb instead (PP[ix+nzb][gz], rtm_main.cpp:203) -- the same thing only when both borders are equally wide; kept as is.
-        const int off = mode == FDW_MODE_DD_RECV ? c->prm.nzb : c->prm.nxb;
-        if (off + c->nx > c->prm.nxe) return fail(FDW_EINVAL, "step: receiver rows [%d,%d) leave the grid", off, off + c->nx);
-        const int g0 = off, g1 = off + std::min(c->nx, c->xlim);
-        const int l0 = std::max(g0 - c->slab.x_off, 0), l1 = std::min(g1 - c->slab.x_off, c->nxl);
-        a.inj_x = l0;
-        a.inj_n = std::max(0, l1 - l0);
-        a.inj = d_inj + (l0 + c->slab.x_off - g0);
+    if (lap) {                // the stencil program rounds its grid up to 32 (S:231-238): whole interior
+        a.lap_x0 = c->slap_x0; a.lap_x1 = c->slap_x1; a.lap_z0 = c->slap_z0; a.lap_z1 = c->slap_z1;
     }
-    a.dt2 = c->dt2;
-    a.c0 = c->c0;
-    a.numerics = c->prm.numerics;
-    const bool fastw = c->prm.numerics == FDW_NUMERICS_FAST;      // (for the RTM dialect fcx / fcz are cx / cz)
-    for (int io = 0; io <= 2 * kMaxFastHalfOrder; io++) {
-        a.cx[io] = io <= c->prm.order ? (fastw ? c->fcx[io] : c->cx[io]) : 0.0f;
-        a.cz[io] = io <= c->prm.order ? (fastw ? c->fcz[io] : c->cz[io]) : 0.0f;
-    }
+    Injection in;
+    if (mode == FDW_MODE_FWD || mode == FDW_MODE_DD_FWD || mode == FDW_MODE_MOD)
+        FDW_TRY(place_source(c, "step", mode == FDW_MODE_MOD, d_inj, inj_x_global, inj_z, &in));
+    else if (mode == FDW_MODE_RECV || mode == FDW_MODE_DD_RECV || mode == FDW_MODE_BACK)
+        FDW_TRY(place_receivers(c, "step", mode == FDW_MODE_DD_RECV ? c->prm.nzb : c->prm.nxb, inj_z, &in));
+    if (mode == FDW_MODE_MOD) FDW_TRY(fill_mod(c, a, "step", d_rec_row, rec_z));
+    a.inj = d_inj + in.shift; a.inj_x = in.x; a.inj_z = inj_z; a.inj_n = in.n;
     if (a.r1 <= a.r0) return FDW_OK;
     if (c->nbatch > 1) {      // fdw_shot_batch: shot b = these pointers + b fields, its own gather, its own source row
         a.nbatch = c->nbatch;
@@ -487,15 +528,9 @@ static int step_impl(fdw_ctx* c, int mode, const float* d_p, float* d_pp, const 
         e = launch_step_generic(a, c->h, mode, s);
     }
     if (e != hipSuccess) return fail(FDW_EHIP, "kernel launch failed: %s", hipGetErrorString(e));
-    if ((mode == FDW_MODE_RECV || mode == FDW_MODE_BACK) && r1 > c->upd_x1) {
-        // receiver rows beyond the time-stepped rows (narrow x border + truncated extents): the reference still injects and images them
-        const int s0 = std::max(a.inj_x, c->upd_x1), s1 = std::min(a.inj_x + a.inj_n, std::min(r1, c->nxl));
-        if (s1 > s0) {
-            e = launch_static_rows(d_pp, mode == FDW_MODE_BACK ? d_fpp : d_psrc, d_img, a.inj + (s0 - a.inj_x), c->pitch, s0, s1 - s0, inj_z,
-                                   c->prm.nzb, a.img_z1, s);
-            if (e != hipSuccess) return fail(FDW_EHIP, "static-row launch failed: %s", hipGetErrorString(e));
-        }
-    }
+    if ((mode == FDW_MODE_RECV || mode == FDW_MODE_BACK) && r1 > c->upd_x1)
+        return static_receiver_rows(c, a.inj_x, a.inj_n, std::min(r1, c->nxl), d_pp, a.inj, mode == FDW_MODE_BACK ? d_fpp : d_psrc, d_img, inj_z, a.img_z1,
+                                    s);
     return FDW_OK;
 }
 
@@ -509,40 +544,32 @@ extern "C" int fdw_dev_step(fdw_ctx* c, int mode, const float* d_p, float* d_pp,
 }
 
 // One iteration of fd_back's loop (R:302-339) on rows [r0, r1) of the slab, on caller-owned device arrays.
+static int back_iter(fdw_ctx* c, int step_source, const float* d_f1, float* d_f0, const float* d_pr, float* d_ppr, const float* d_v2, int r0, int r1,
+                     int pp_twice, const float* d_samples, int gz, float* d_img, hipStream_t s)
+{
+    if (!step_source)      // iterations 0 and 1: the source field is a snapshot as it stands (R:304-314)
+        return step_impl(c, FDW_MODE_RECV, d_pr, d_ppr, d_v2, r0, r1, pp_twice, d_samples, 0, gz, d_f1, d_img, s);
+    // the whole iteration in ONE pass: the source field is stepped in place (F_k overwrites F_{k-2}) in the same kernel that steps the
+    // receiver field, and meets the new receiver row in registers for the imaging condition
+    if (c->h <= kMaxFastHalfOrder && !c->use_generic && !c->no_fused_back)
+        return step_impl(c, FDW_MODE_BACK, d_pr, d_ppr, d_v2, r0, r1, pp_twice, d_samples, 0, gz, d_f1, d_img, s, nullptr, 0, d_f0);
+    FDW_TRY(step_impl(c, FDW_MODE_PLAIN, d_f1, d_f0, d_v2, r0, r1, 0, nullptr, -1, 0, nullptr, nullptr, s));      // F_k overwrites F_{k-2} (R:317-318)
+    return step_impl(c, FDW_MODE_RECV, d_pr, d_ppr, d_v2, r0, r1, pp_twice, d_samples, 0, gz, d_f0, d_img, s);
+}
+
 extern "C" int fdw_dev_back_iter(fdw_ctx* c, int step_source, const float* d_f1, float* d_f0, const float* d_pr, float* d_ppr, const float* d_v2,
                                  int r0, int r1, int pp_twice, const float* d_samples, int gz, float* d_img, void* stream)
 {
     if (!c) return fail(FDW_EINVAL, "ctx is NULL");
     if (c->prm.dialect != FDW_DIALECT_RTM) return fail(FDW_ESTATE, "fdw_dev_back_iter belongs to the RTM dialect");
     if (!d_f1 || !d_pr || !d_ppr || !d_v2 || !d_samples || !d_img || (step_source && !d_f0)) return fail(FDW_EINVAL, "back_iter: NULL buffer");
-    hipStream_t s = pick_stream(c, stream);
-    if (!step_source)      // iterations 0 and 1: the source field is a snapshot as it stands (R:304-314)
-        return step_impl(c, FDW_MODE_RECV, d_pr, d_ppr, d_v2, r0, r1, pp_twice, d_samples, 0, gz, d_f1, d_img, s);
-    if (c->h <= kMaxFastHalfOrder && !c->use_generic && !c->no_fused_back)
-        return step_impl(c, FDW_MODE_BACK, d_pr, d_ppr, d_v2, r0, r1, pp_twice, d_samples, 0, gz, d_f1, d_img, s, nullptr, 0, d_f0);
-    int rc = step_impl(c, FDW_MODE_PLAIN, d_f1, d_f0, d_v2, r0, r1, 0, nullptr, -1, 0, nullptr, nullptr, s);      // F_k overwrites F_{k-2} (R:317-318)
-    if (rc) return rc;
-    return step_impl(c, FDW_MODE_RECV, d_pr, d_ppr, d_v2, r0, r1, pp_twice, d_samples, 0, gz, d_f0, d_img, s);
+    return back_iter(c, step_source, d_f1, d_f0, d_pr, d_ppr, d_v2, r0, r1, pp_twice, d_samples, gz, d_img, pick_stream(c, stream));
 }
 
 extern "C" int fdw_dev_laplacian(fdw_ctx* c, const float* d_p, float* d_lap, void* stream)
 {
     if (!c) return fail(FDW_EINVAL, "ctx is NULL");
     return step_impl(c, FDW_MODE_LAP, d_p, d_lap, nullptr, 0, c->nxl, 0, nullptr, -1, 0, nullptr, nullptr, pick_stream(c, stream));
-}
-
-extern "C" int fdw_dev_steps(fdw_ctx* c, float* d_p, float* d_pp, const float* d_v2, const float* d_srce, int sx, int sz,
-                             int it0, int nsteps, int first_pp_twice, void* stream)
-{
-    if (!c) return fail(FDW_EINVAL, "ctx is NULL");
-    hipStream_t s = pick_stream(c, stream);
-    for (int k = 0; k < nsteps; k++) {
-        std::swap(d_p, d_pp);  // R:260-262
-        int rc = step_impl(c, FDW_MODE_FWD, d_p, d_pp, d_v2, 0, c->nxl, (k > 0) || first_pp_twice,
-                           d_srce ? d_srce + it0 + k : nullptr, d_srce ? sx : -1, sz, nullptr, nullptr, s);
-        if (rc) return rc;
-    }
-    return FDW_OK;
 }
 
 // ---- two time steps per pass (temporal blocking) --------------------------------------------------
@@ -556,6 +583,28 @@ static bool two_step_pays(const fdw_ctx* c)
     if (c->h != kMaxFastHalfOrder || c->use_generic || c->tb < 0 || c->prm.dialect != FDW_DIALECT_RTM) return false;
     if (c->tb > 0) return true;
     return (long)c->upd_x1 * ((c->pitch / 4 + 59) / 60) >= 200000;
+}
+
+// The end of a pass of an even number of steps (step2_impl, stepn_impl).  Rows the reference never time-steps (compat, nxe not a multiple
+// of 8) are static in both fields, which swap roles every step: out1 now carries pp's rows, out2 p's; so do the levels in between
+// (PLAIN_ALL: level 0 pp's, level 1 p's) and the receiver field of BACK4.  Receiver rows among them (two-step RECV): iteration it injects
+// into (and images) what is now out1, iteration it+1 what is now out2.
+static int even_steps_tail(fdw_ctx* c, int mode, const Step2Args& a, hipStream_t s)
+{
+    if (c->upd_x1 >= c->nxl) return FDW_OK;
+    const size_t off = (size_t)c->upd_x1 * c->pitch, n = (size_t)(c->nxl - c->upd_x1) * c->pitch * sizeof(float);
+    auto pair = [&](float* o1, float* o2, const float* p, const float* pp) -> int {
+        HIP_TRY(hipMemcpyAsync(o1 + off, pp + off, n, hipMemcpyDeviceToDevice, s));
+        HIP_TRY(hipMemcpyAsync(o2 + off, p + off, n, hipMemcpyDeviceToDevice, s));
+        return FDW_OK;
+    };
+    FDW_TRY(pair(a.out1, a.out2, a.p, a.pp));
+    if (mode == FDW_MODE_PLAIN_ALL) FDW_TRY(pair(a.lvl0, a.lvl1, a.p, a.pp));
+    if (mode == FDW_MODE_BACK4) FDW_TRY(pair(a.rout1, a.rout2, a.rp, a.rpp));
+    // (the pipeline's receiver passes, inj2 = NULL, run only where every receiver row is time-stepped: fdw_receivers_stepped)
+    if (mode != FDW_MODE_RECV || !a.inj2) return FDW_OK;
+    FDW_TRY(static_receiver_rows(c, a.inj_x, a.inj_n, c->nxl, a.out1, a.inj, a.psrc_a, a.img, a.inj_z, a.img_z1, s));
+    return static_receiver_rows(c, a.inj_x, a.inj_n, c->nxl, a.out2, a.inj2, a.psrc_b, a.img, a.inj_z, a.img_z1, s);
 }
 
 struct Step2Extra {          // what the receiver / imaging variant needs on top of the forward one
@@ -576,40 +625,18 @@ static int step2_impl(fdw_ctx* c, int mode, const float* d_p, const float* d_pp,
     if (d_out1 == d_p || d_out1 == d_pp || d_out2 == d_p || d_out2 == d_pp || d_out1 == d_out2)
         return fail(FDW_EINVAL, "step2: outputs must not alias the inputs (tiles re-read each other's input rows)");
     Step2Args a{};
-    a.p = d_p; a.pp = d_pp; a.v2 = d_v2; a.out1 = d_out1; a.out2 = d_out2;
-    a.taperz = c->d_taperz; a.txfac = c->d_txfac; a.inj = d_inj; a.inj2 = ex.inj2;
+    fill_common(c, a, d_p, d_pp, d_v2, pp_twice);
+    a.out1 = d_out1; a.out2 = d_out2;
     a.psrc_a = ex.psrc_a; a.psrc_b = ex.psrc_b; a.img = ex.img;
-    a.pitch = c->pitch; a.nxl = c->nxl;
     a.r0 = 0; a.r1 = c->upd_x1;
-    a.lap_x0 = c->lap_x0; a.lap_x1 = c->lap_x1; a.lap_z0 = c->lap_z0; a.lap_z1 = c->lap_z1;
-    a.upd_x1 = c->upd_x1; a.upd_z1 = c->upd_z1;
-    a.ztap = c->ztap; a.tz_x1 = c->tz_x1; a.xt_lo = c->xt_lo; a.xt_hi = c->xt_hi;
-    a.pp_twice = pp_twice ? 1 : 0;
-    a.img_z1 = c->prm.nzb + std::min(c->nz, c->zlim);
-    a.inj_x = -1000000; a.inj_z = inj_z; a.inj_n = 0;
-    if (mode == FDW_MODE_FWD && d_inj && inj_x_global >= 0) {
-        if (inj_z < 0 || inj_z >= c->prm.nze || inj_x_global >= c->prm.nxe) return fail(FDW_EINVAL, "step2: source (%d,%d) outside the grid", inj_x_global, inj_z);
-        a.inj_x = inj_x_global - c->slab.x_off;
-        if (a.inj_x >= c->upd_x1 && a.inj_x < c->nxl)
-            return fail(FDW_EINVAL, "step2: source row %d lies in rows the reference never time-steps (>= %d)", inj_x_global, c->xlim);
+    Injection in;
+    if (mode == FDW_MODE_FWD) {
+        FDW_TRY(place_source(c, "step2", false, d_inj, inj_x_global, inj_z, &in));
     } else if (mode == FDW_MODE_RECV) {
         if (!d_inj || !ex.inj2 || !ex.psrc_a || !ex.psrc_b || !ex.img) return fail(FDW_EINVAL, "step2: RECV needs both sample rows, both source fields and the image");
-        if (inj_z < 0 || inj_z >= c->prm.nze) return fail(FDW_EINVAL, "step2: receiver depth %d outside the grid", inj_z);
-        const int g0 = c->prm.nxb, g1 = c->prm.nxb + std::min(c->nx, c->xlim);       // receivers on interior columns (R:126-129)
-        const int l0 = std::max(g0 - c->slab.x_off, 0), l1 = std::min(g1 - c->slab.x_off, c->nxl);
-        a.inj_x = l0;
-        a.inj_n = std::max(0, l1 - l0);
-        a.inj = d_inj + (l0 + c->slab.x_off - g0);
-        a.inj2 = ex.inj2 + (l0 + c->slab.x_off - g0);
+        FDW_TRY(place_receivers(c, "step2", c->prm.nxb, inj_z, &in));
     }
-    a.dt2 = c->dt2;
-    a.c0 = c->c0;
-    a.numerics = c->prm.numerics;
-    for (int io = 0; io <= 2 * kMaxFastHalfOrder; io++) {
-        const bool fastw = c->prm.numerics == FDW_NUMERICS_FAST;
-        a.cx[io] = fastw ? c->fcx[io] : c->cx[io];
-        a.cz[io] = fastw ? c->fcz[io] : c->cz[io];
-    }
+    a.inj = d_inj + in.shift; a.inj2 = ex.inj2 + in.shift; a.inj_x = in.x; a.inj_z = inj_z; a.inj_n = in.n;
     const int ncells = c->pitch / 4;
     a.nstrip = (ncells + 59) / 60;
     a.nzblk = (a.nstrip + 3) / 4;
@@ -627,24 +654,7 @@ static int step2_impl(fdw_ctx* c, int mode, const float* d_p, const float* d_pp,
     a.nper = (a.nblk + 7) / 8;
     hipError_t e = launch_step2(a, c->h, mode, s);
     if (e != hipSuccess) return fail(FDW_EHIP, "step2 launch failed: %s", hipGetErrorString(e));
-    // rows the reference never time-steps (compat, nxe not a multiple of 8): both fields are static there and
-    // swap roles every step, so after two steps out1 carries pp's rows and out2 p's rows
-    if (c->upd_x1 < c->nxl) {
-        const size_t off = (size_t)c->upd_x1 * c->pitch, n = (size_t)(c->nxl - c->upd_x1) * c->pitch * sizeof(float);
-        HIP_TRY(hipMemcpyAsync(d_out1 + off, d_pp + off, n, hipMemcpyDeviceToDevice, s));
-        HIP_TRY(hipMemcpyAsync(d_out2 + off, d_p + off, n, hipMemcpyDeviceToDevice, s));
-        if (mode == FDW_MODE_RECV) {
-            // receiver rows among them: iteration it injects into (and images) what is now out1, iteration it+1 what is now out2
-            const int s0 = std::max(a.inj_x, c->upd_x1), s1 = std::min(a.inj_x + a.inj_n, c->nxl);
-            if (s1 > s0) {
-                hipError_t e2 = launch_static_rows(d_out1, ex.psrc_a, ex.img, a.inj + (s0 - a.inj_x), c->pitch, s0, s1 - s0, inj_z, c->prm.nzb, a.img_z1, s);
-                if (e2 == hipSuccess)
-                    e2 = launch_static_rows(d_out2, ex.psrc_b, ex.img, a.inj2 + (s0 - a.inj_x), c->pitch, s0, s1 - s0, inj_z, c->prm.nzb, a.img_z1, s);
-                if (e2 != hipSuccess) return fail(FDW_EHIP, "static-row launch failed: %s", hipGetErrorString(e2));
-            }
-        }
-    }
-    return FDW_OK;
+    return even_steps_tail(c, mode, a, s);
 }
 
 // ---- kPipeSteps time steps per pass (wave pipeline through LDS) -------------------------------------
@@ -692,30 +702,20 @@ static int stepn_impl(fdw_ctx* c, int mode, const float* d_p, const float* d_pp,
     if (d_out1 == d_p || d_out1 == d_pp || d_out2 == d_p || d_out2 == d_pp || d_out1 == d_out2)
         return fail(FDW_EINVAL, "stepn: outputs must not alias the inputs (tiles re-read each other's input rows)");
     Step2Args a{};
-    a.p = d_p; a.pp = d_pp; a.v2 = d_v2; a.out1 = d_out1; a.out2 = d_out2;
-    a.taperz = c->d_taperz; a.txfac = c->d_txfac; a.inj = d_inj;
-    a.pitch = c->pitch; a.nxl = c->nxl;
+    fill_common(c, a, d_p, d_pp, d_v2, pp_twice);
+    a.out1 = d_out1; a.out2 = d_out2;
     const bool whole = rr.r1 < 0;
     if (!whole && (rr.r0 < 0 || rr.r1 > c->nxl || rr.r0b < 0 || rr.r1b > c->nxl || (rr.r1b > rr.r0b && rr.r0b < rr.r1)))
         return fail(FDW_EINVAL, "stepn: row ranges [%d,%d) [%d,%d) outside the slab or overlapping", rr.r0, rr.r1, rr.r0b, rr.r1b);
     a.r0 = whole ? 0 : rr.r0; a.r1 = std::min(whole ? c->upd_x1 : rr.r1, c->upd_x1);
     a.r0b = whole ? 0 : rr.r0b; a.r1b = whole ? 0 : std::min(rr.r1b, c->upd_x1);
-    a.lap_x0 = c->lap_x0; a.lap_x1 = c->lap_x1; a.lap_z0 = c->lap_z0; a.lap_z1 = c->lap_z1;
-    a.upd_x1 = c->upd_x1; a.upd_z1 = c->upd_z1;
-    a.ztap = c->ztap; a.tz_x1 = c->tz_x1; a.xt_lo = c->xt_lo; a.xt_hi = c->xt_hi;
     {   // columns without a damping factor (taper_apply's table is 1.0f between the two strips; the RTM dialects damp the top strip only)
         const bool four_sided = c->prm.dialect == FDW_DIALECT_MOD;
         a.zt_lo = four_sided ? c->prm.nzb : c->ztap;
         a.zt_hi = four_sided ? c->prm.nze - c->prm.nzb : -1;
     }
-    a.pp_twice = pp_twice ? 1 : 0;
-    a.inj_x = -1000000; a.inj_z = inj_z; a.inj_n = 0;
-    if (mode == FDW_MODE_FWD && d_inj && inj_x_global >= 0) {
-        if (inj_z < 0 || inj_z >= c->prm.nze || inj_x_global >= c->prm.nxe) return fail(FDW_EINVAL, "stepn: source (%d,%d) outside the grid", inj_x_global, inj_z);
-        a.inj_x = inj_x_global - c->slab.x_off;
-        if (a.inj_x >= c->upd_x1 && a.inj_x < c->nxl)
-            return fail(FDW_EINVAL, "stepn: source row %d lies in rows the reference never time-steps (>= %d)", inj_x_global, c->xlim);
-    }
+    Injection in;
+    if (mode == FDW_MODE_FWD || mode == FDW_MODE_MOD) FDW_TRY(place_source(c, "stepn", mode == FDW_MODE_MOD, d_inj, inj_x_global, inj_z, &in));
     if (mode == FDW_MODE_PLAIN_ALL) {
         a.lvl0 = bk->lvl0; a.lvl1 = bk->lvl1;
         for (float* o : {d_out1, d_out2}) if (bk->lvl0 == o || bk->lvl1 == o || bk->lvl0 == bk->lvl1 || bk->lvl0 == d_p || bk->lvl0 == d_pp || bk->lvl1 == d_p || bk->lvl1 == d_pp)
@@ -725,36 +725,13 @@ static int stepn_impl(fdw_ctx* c, int mode, const float* d_p, const float* d_pp,
         a.rp = bk->rp; a.rpp = bk->rpp; a.rout1 = bk->rout1; a.rout2 = bk->rout2;
     }
     if (mode == FDW_MODE_RECV || mode == FDW_MODE_BACK4) {
-        if (inj_z < 0 || inj_z >= c->prm.nze) return fail(FDW_EINVAL, "stepn: receiver depth %d outside the grid", inj_z);
-        const int g0 = c->prm.nxb, g1 = c->prm.nxb + std::min(c->nx, c->xlim);       // receivers on interior rows (R:126-129)
-        const int l0 = std::max(g0 - c->slab.x_off, 0), l1 = std::min(g1 - c->slab.x_off, c->nxl);
-        a.inj_x = l0;
-        a.inj_n = std::max(0, l1 - l0);
-        a.inj = d_inj + (l0 + c->slab.x_off - g0);
+        FDW_TRY(place_receivers(c, "stepn", c->prm.nxb, inj_z, &in));
         a.inj_stride = bk->inj_stride;
         a.img = bk->img;
-        a.img_z1 = c->prm.nzb + std::min(c->nz, c->zlim);
         for (int i = 0; i < kPipeSteps; i++) a.plev[i] = bk->plev[i];
     }
-    if (mode == FDW_MODE_MOD) {
-        if (d_inj) {
-            if (inj_z < 0 || inj_z >= c->prm.nze || inj_x_global < 0 || inj_x_global >= c->prm.nxe)
-                return fail(FDW_EINVAL, "stepn: source (%d,%d) outside the grid", inj_x_global, inj_z);
-            a.inj_x = inj_x_global - c->slab.x_off;
-        }
-        for (int i = 0; i < 4; i++)
-            for (int j = 0; j < 4; j++) a.gw[i][j] = expf(-(float)(i * i) - (float)(j * j));
-        a.dx2inv = c->dx2inv; a.dz2inv = c->dz2inv;
-        a.rec = d_rec; a.rec_z = rec_z; a.rec_x0 = c->prm.nxb - c->slab.x_off; a.rec_n = c->nx;
-    }
-    a.dt2 = c->dt2;
-    a.c0 = c->c0;
-    a.numerics = c->prm.numerics;
-    for (int io = 0; io <= 2 * kMaxFastHalfOrder; io++) {
-        const bool fastw = c->prm.numerics == FDW_NUMERICS_FAST;
-        a.cx[io] = fastw ? c->fcx[io] : c->cx[io];
-        a.cz[io] = fastw ? c->fcz[io] : c->cz[io];
-    }
+    if (mode == FDW_MODE_MOD) FDW_TRY(fill_mod(c, a, "stepn", d_rec, rec_z));
+    a.inj = d_inj + in.shift; a.inj_x = in.x; a.inj_z = inj_z; a.inj_n = in.n;
     const int ncells = c->pitch / 4, own = 64 - 2 * kPipeSteps;
     a.nstrip = (ncells + own - 1) / own;
     a.nzblk = a.nstrip;
@@ -786,45 +763,28 @@ static int stepn_impl(fdw_ctx* c, int mode, const float* d_p, const float* d_pp,
     a.nper = (a.nblk + 7) / 8;
     hipError_t e = launch_stepn(a, c->h, mode, s);
     if (e != hipSuccess) return fail(FDW_EHIP, "stepn launch failed: %s", hipGetErrorString(e));
-    // rows the reference never time-steps swap roles every step: after an even number of steps out1 carries pp's rows, out2 p's
     static_assert(kPipeSteps % 2 == 0, "static-row bookkeeping assumes an even number of steps per pass");
-    if (c->upd_x1 < c->nxl && (whole || rr.r1 >= c->upd_x1 || rr.r1b >= c->upd_x1)) {
-        const size_t off = (size_t)c->upd_x1 * c->pitch, n = (size_t)(c->nxl - c->upd_x1) * c->pitch * sizeof(float);
-        HIP_TRY(hipMemcpyAsync(d_out1 + off, d_pp + off, n, hipMemcpyDeviceToDevice, s));
-        HIP_TRY(hipMemcpyAsync(d_out2 + off, d_p + off, n, hipMemcpyDeviceToDevice, s));
-        if (mode == FDW_MODE_PLAIN_ALL) {      // the levels in between alternate the same way: level 0 carries pp's rows, level 1 p's
-            HIP_TRY(hipMemcpyAsync(bk->lvl0 + off, d_pp + off, n, hipMemcpyDeviceToDevice, s));
-            HIP_TRY(hipMemcpyAsync(bk->lvl1 + off, d_p + off, n, hipMemcpyDeviceToDevice, s));
-        }
-        if (mode == FDW_MODE_BACK4) {          // and so do the receiver field's
-            HIP_TRY(hipMemcpyAsync(bk->rout1 + off, bk->rpp + off, n, hipMemcpyDeviceToDevice, s));
-            HIP_TRY(hipMemcpyAsync(bk->rout2 + off, bk->rp + off, n, hipMemcpyDeviceToDevice, s));
-        }
-    }
-    return FDW_OK;
+    return whole || rr.r1 >= c->upd_x1 || rr.r1b >= c->upd_x1 ? even_steps_tail(c, mode, a, s) : FDW_OK;
 }
 
-// FOUR iterations of fd_back's loop (R:317-329) as two passes of the wave-pipeline kernel on row ranges of the slab (see back_loop)
-extern "C" int fdw_dev_back4(fdw_ctx* c, const float* d_f1, const float* d_f0, float* d_fo1, float* d_fo2, float* d_lvl0, float* d_lvl1, const float* d_pr,
-                             const float* d_ppr, float* d_ro1, float* d_ro2, const float* d_v2, const float* d_samples, int sample_stride, int gz,
-                             float* d_img, int pp_twice, int r0, int r1, int r0b, int r1b, int xchunk, void* stream)
+int fdw_receivers_stepped(const fdw_ctx* c) { return c->prm.nxb + c->nx <= c->xlim; }
+
+// FOUR iterations of fd_back's loop (R:317-329) through the wave pipeline on row ranges of the slab: source field f1, f0 -> fo1, fo2, receiver
+// field pr, ppr -> ro1, ro2.  Fused (one pass of the eight-wave kernel, the levels in between never leave the chip) unless FDW_NO_BACK_FUSED:
+// then PLAIN_ALL reconstructs F_it .. F_{it+3} into lvl0, lvl1, fo1, fo2 and a RECV pass advances the receiver field four times, injects each
+// iteration's samples (rows sample_stride apart) and adds the four products F_{it+j} r^{it+j+1} to the image in iteration order.
+static int back4(fdw_ctx* c, const float* d_f1, const float* d_f0, float* d_fo1, float* d_fo2, float* d_lvl0, float* d_lvl1, const float* d_pr,
+                 const float* d_ppr, float* d_ro1, float* d_ro2, const float* d_v2, const float* d_samples, int sample_stride, int gz, float* d_img,
+                 int pp_twice, const RowRanges& rr, hipStream_t s)
 {
-    if (!c) return fail(FDW_EINVAL, "ctx is NULL");
-    if (c->prm.dialect != FDW_DIALECT_RTM || c->h != kMaxFastHalfOrder || (size_t)c->nxl * c->pitch * sizeof(float) >= (1ull << 31))
-        return fail(FDW_EINVAL, "back4: needs the RTM dialect, order 8 and fields below 2 GiB");
-    if (c->prm.nxb + c->nx > c->xlim) return fail(FDW_EINVAL, "back4: receiver rows beyond the time-stepped rows are not covered by the pipelined passes");
-    hipStream_t s = pick_stream(c, stream);
-    RowRanges rr;
-    rr.r0 = r0; rr.r1 = r1; rr.r0b = r0b; rr.r1b = r1b; rr.xchunk = xchunk;
-    if (!c->no_back_fused) {      // both fields in one pass of the eight-wave kernel: the levels in between never leave the chip
+    if (!c->no_back_fused) {
         StepnBack b4;
         b4.rp = d_pr; b4.rpp = d_ppr; b4.rout1 = d_ro1; b4.rout2 = d_ro2; b4.img = d_img; b4.inj_stride = sample_stride;
         return stepn_impl(c, FDW_MODE_BACK4, d_f1, d_f0, d_v2, d_fo1, d_fo2, pp_twice, d_samples, -1, gz, s, rr, nullptr, 0, &b4);
     }
     StepnBack fb;
     fb.lvl0 = d_lvl0; fb.lvl1 = d_lvl1;
-    int rc = stepn_impl(c, FDW_MODE_PLAIN_ALL, d_f1, d_f0, d_v2, d_fo1, d_fo2, 0, nullptr, -1, 0, s, rr, nullptr, 0, &fb);
-    if (rc) return rc;
+    FDW_TRY(stepn_impl(c, FDW_MODE_PLAIN_ALL, d_f1, d_f0, d_v2, d_fo1, d_fo2, 0, nullptr, -1, 0, s, rr, nullptr, 0, &fb));
     StepnBack rb;
     rb.plev[0] = d_lvl0; rb.plev[1] = d_lvl1; rb.plev[2] = d_fo1; rb.plev[3] = d_fo2;
     rb.img = d_img;
@@ -832,9 +792,24 @@ extern "C" int fdw_dev_back4(fdw_ctx* c, const float* d_f1, const float* d_f0, f
     return stepn_impl(c, FDW_MODE_RECV, d_pr, d_ppr, d_v2, d_ro1, d_ro2, pp_twice, d_samples, -1, gz, s, rr, nullptr, 0, &rb);
 }
 
+extern "C" int fdw_dev_back4(fdw_ctx* c, const float* d_f1, const float* d_f0, float* d_fo1, float* d_fo2, float* d_lvl0, float* d_lvl1, const float* d_pr,
+                             const float* d_ppr, float* d_ro1, float* d_ro2, const float* d_v2, const float* d_samples, int sample_stride, int gz,
+                             float* d_img, int pp_twice, int r0, int r1, int r0b, int r1b, int xchunk, void* stream)
+{
+    if (!c) return fail(FDW_EINVAL, "ctx is NULL");
+    if (c->prm.dialect != FDW_DIALECT_RTM || c->h != kMaxFastHalfOrder || (size_t)c->nxl * c->pitch * sizeof(float) >= (1ull << 31))
+        return fail(FDW_EINVAL, "back4: needs the RTM dialect, order 8 and fields below 2 GiB");
+    if (!fdw_receivers_stepped(c)) return fail(FDW_EINVAL, "back4: receiver rows beyond the time-stepped rows are not covered by the pipelined passes");
+    RowRanges rr;
+    rr.r0 = r0; rr.r1 = r1; rr.r0b = r0b; rr.r1b = r1b; rr.xchunk = xchunk;
+    return back4(c, d_f1, d_f0, d_fo1, d_fo2, d_lvl0, d_lvl1, d_pr, d_ppr, d_ro1, d_ro2, d_v2, d_samples, sample_stride, gz, d_img, pp_twice, rr,
+                 pick_stream(c, stream));
+}
+
+// the backward loop's tier (back_loop; fdw_slabs_create asks the same of every rank)
 extern "C" int fdw_back_pipe_active(const fdw_ctx* c)
 {
-    return c && pipe_pays(c) && c->prm.dialect == FDW_DIALECT_RTM && c->prm.nxb + c->nx <= c->xlim && !c->no_back_pipe ? 1 : 0;
+    return c && pipe_pays(c) && c->prm.dialect == FDW_DIALECT_RTM && fdw_receivers_stepped(c) && !c->no_back_pipe ? 1 : 0;
 }
 
 extern "C" int fdw_two_step_active(const fdw_ctx* c) { return c && two_step_pays(c) ? 1 : 0; }
@@ -871,30 +846,22 @@ extern "C" int fdw_dev_steps2(fdw_ctx* c, float* const* buf, const float* d_v2, 
     int k = 0;
     while (k < nsteps) {
         const int twice = (k > 0) || first_pp_twice;
+        const float* inj = d_srce ? d_srce + it0 + k : nullptr;
+        const int sxx = d_srce ? sx : -1;
+        int o1, o2;   // the two buffers not holding the current pair
+        spare_pair(*ip, *ipp, &o1, &o2);
         if (nsteps - k >= kPipeSteps && pipe_pays(c)) {
-            int o1 = 0, o2 = 0;
-            for (int i = 0, n = 0; i < 4; i++)
-                if (i != *ip && i != *ipp) { (n++ == 0 ? o1 : o2) = i; }
-            int rc = stepn_impl(c, FDW_MODE_FWD, buf[*ipp], buf[*ip], d_v2, buf[o1], buf[o2], twice, d_srce ? d_srce + it0 + k : nullptr,
-                                d_srce ? sx : -1, sz, s);
-            if (rc) return rc;
+            FDW_TRY(stepn_impl(c, FDW_MODE_FWD, buf[*ipp], buf[*ip], d_v2, buf[o1], buf[o2], twice, inj, sxx, sz, s));
             *ip = o1; *ipp = o2;   // d_p = u^{n+kPipeSteps-1}, d_pp = u^{n+kPipeSteps}
             k += kPipeSteps;
         } else if (nsteps - k >= 2 && two_step_pays(c)) {
-            int o1 = 0, o2 = 0;   // the two buffers not holding the current pair
-            for (int i = 0, n = 0; i < 4; i++)
-                if (i != *ip && i != *ipp) { (n++ == 0 ? o1 : o2) = i; }
             // after the swap the kernel's p is the old d_pp (newest field), its pp the old d_p
-            int rc = step2_impl(c, FDW_MODE_FWD, buf[*ipp], buf[*ip], d_v2, buf[o1], buf[o2], twice, d_srce ? d_srce + it0 + k : nullptr,
-                                d_srce ? sx : -1, sz, Step2Extra{}, s);
-            if (rc) return rc;
+            FDW_TRY(step2_impl(c, FDW_MODE_FWD, buf[*ipp], buf[*ip], d_v2, buf[o1], buf[o2], twice, inj, sxx, sz, Step2Extra{}, s));
             *ip = o1; *ipp = o2;   // d_p = u^{n+1}, d_pp = u^{n+2}
             k += 2;
         } else {
             std::swap(*ip, *ipp);
-            int rc = step_impl(c, FDW_MODE_FWD, buf[*ip], buf[*ipp], d_v2, 0, c->nxl, twice, d_srce ? d_srce + it0 + k : nullptr,
-                               d_srce ? sx : -1, sz, nullptr, nullptr, s);
-            if (rc) return rc;
+            FDW_TRY(step_impl(c, FDW_MODE_FWD, buf[*ip], buf[*ipp], d_v2, 0, c->nxl, twice, inj, sxx, sz, nullptr, nullptr, s));
             k += 1;
         }
     }
@@ -919,6 +886,12 @@ extern "C" int fdw_dev_steps_shrink(fdw_ctx* c, float* d_p, float* d_pp, const f
         if (rc) return rc;
     }
     return FDW_OK;
+}
+
+extern "C" int fdw_dev_steps(fdw_ctx* c, float* d_p, float* d_pp, const float* d_v2, const float* d_srce, int sx, int sz,
+                             int it0, int nsteps, int first_pp_twice, void* stream)
+{
+    return fdw_dev_steps_shrink(c, d_p, d_pp, d_v2, d_srce, sx, sz, it0, nsteps, first_pp_twice, 0, 0, 0, stream);
 }
 
 extern "C" int fdw_dev_taper_finalize(fdw_ctx* c, float* d_f, void* stream)
@@ -1099,9 +1072,10 @@ static int image_to_host(fdw_ctx* c, float* imloc)
 //          F_k = leap-frog(F_{k-1}, F_{k-2}) for k >= 2 (no taper, no source, R:317-318)
 //   r^k  = receiver field: r^{k+1} = damped leap-frog(r^k, r^{k-1}) + d_obs[.][nt-1-k] on row gz (R:325-328)
 //   img += F_k * r^{k+1}  (R:329)
-// Iterations are taken in PAIRS through the two-step kernel where it pays (one pass reconstructs F_k, F_{k+1}; one
-// pass advances the receiver field twice and applies both imaging conditions), singly through the one-step kernels
-// otherwise.  src[0..3] / rcv[0..3]: rotating buffers; on entry src[0] = snap0, src[1] = snap1, the receivers are zero.
+// Iterations go four at a time through the wave pipeline where it pays (back4), in PAIRS through the two-step kernel where that pays (one
+// pass reconstructs F_k, F_{k+1}; one pass advances the receiver field twice and applies both imaging conditions), singly through the
+// one-step kernels otherwise (back_iter).  src[0..3] / rcv[0..3]: rotating buffers; on entry src[0] = snap0, src[1] = snap1, the receivers
+// are zero.
 static int back_loop(fdw_ctx* c, float* const src[4], float* const rcv[4], int gz, int nsteps)
 {
     FDW_RANGE("fdw: backward loop + imaging (fd_back)");
@@ -1110,86 +1084,47 @@ static int back_loop(fdw_ctx* c, float* const src[4], float* const rcv[4], int g
     auto samples = [&](int it) { return c->d_dobs + (size_t)(nt - 1 - it) * nxs; };
     int f1 = 0, f0 = 1;          // indices into src of F_{k-1} (newer) and F_{k-2}: before iteration 2 these are snap0, snap1
     int rn = 0, ro = 1;          // indices into rcv of r^k (d_pr) and r^{k-1} (d_ppr)
-    int rc;
     int it = 0;
     const bool pairs = two_step_pays(c);
-    // Four iterations per pair of passes through the wave pipeline where it pays: pass 1 reconstructs F_it .. F_{it+3} (all four levels are
-    // kept: the imaging condition needs each of them), pass 2 advances the receiver field four times, injects each iteration's samples and
-    // adds the four products F_{it+j} r^{it+j+1} to the image in iteration order.  Not where receiver rows lie beyond the time-stepped rows.
-    const bool pipe = pipe_pays(c) && c->prm.dialect == FDW_DIALECT_RTM && c->nbatch <= 1 && c->prm.nxb + c->nx <= c->upd_x1 && !c->no_back_pipe;
+    const bool pipe = fdw_back_pipe_active(c) && c->nbatch <= 1;
     if (pipe && c->no_back_fused && nsteps >= 2 + kPipeSteps) {      // the two-pass form keeps two levels in memory
-        if ((rc = alloc_zero(&c->fld[8], field_elems(c))) || (rc = alloc_zero(&c->fld[9], field_elems(c)))) return rc;
+        FDW_TRY(alloc_zero(&c->fld[8], field_elems(c)));
+        FDW_TRY(alloc_zero(&c->fld[9], field_elems(c)));
     }
     while (it < nsteps) {
         if (pipe && it >= 2 && nsteps - it >= kPipeSteps) {
-            int o1 = -1, o2 = -1, q1 = -1, q2 = -1;
-            for (int i = 0; i < 4; i++) {
-                if (i != f1 && i != f0) { (o1 < 0 ? o1 : o2) = i; }
-                if (i != rn && i != ro) { (q1 < 0 ? q1 : q2) = i; }
-            }
-            if (!c->no_back_fused) {      // one pass of the eight-wave kernel for both fields
-                StepnBack b4;
-                b4.rp = rcv[rn]; b4.rpp = rcv[ro]; b4.rout1 = rcv[q1]; b4.rout2 = rcv[q2]; b4.img = c->d_img; b4.inj_stride = -(int)nxs;
-                if ((rc = stepn_impl(c, FDW_MODE_BACK4, src[f1], src[f0], c->d_v2, src[o1], src[o2], it > 0, samples(it), -1, gz, c->stream, RowRanges{}, nullptr, 0, &b4))) return rc;
-                f0 = o1; f1 = o2;
-                ro = q1; rn = q2;
-                it += kPipeSteps;
-                continue;
-            }
-            StepnBack fb;
-            fb.lvl0 = c->fld[8]; fb.lvl1 = c->fld[9];
-            if ((rc = stepn_impl(c, FDW_MODE_PLAIN_ALL, src[f1], src[f0], c->d_v2, src[o1], src[o2], 0, nullptr, -1, 0, c->stream, RowRanges{}, nullptr, 0, &fb))) return rc;
-            StepnBack rb;
-            rb.plev[0] = c->fld[8]; rb.plev[1] = c->fld[9]; rb.plev[2] = src[o1]; rb.plev[3] = src[o2];
-            rb.img = c->d_img;
-            rb.inj_stride = -(int)nxs;                       // iteration it+1 reads the sample row before (time-reversed traces, R:328)
-            if ((rc = stepn_impl(c, FDW_MODE_RECV, rcv[rn], rcv[ro], c->d_v2, rcv[q1], rcv[q2], it > 0, samples(it), -1, gz, c->stream, RowRanges{}, nullptr, 0, &rb))) return rc;
+            int o1, o2, q1, q2;
+            spare_pair(f1, f0, &o1, &o2);
+            spare_pair(rn, ro, &q1, &q2);
+            // iteration it+1 reads the sample row before (time-reversed traces, R:328)
+            FDW_TRY(back4(c, src[f1], src[f0], src[o1], src[o2], c->fld[8], c->fld[9], rcv[rn], rcv[ro], rcv[q1], rcv[q2], c->d_v2, samples(it),
+                          -(int)nxs, gz, c->d_img, it > 0, RowRanges{}, c->stream));
             f0 = o1; f1 = o2;
             ro = q1; rn = q2;
             it += kPipeSteps;
-            continue;
-        }
-        if (pairs && nsteps - it >= 2) {
+        } else if (pairs && nsteps - it >= 2) {
             const float *Fa, *Fb;   // source fields of iterations it, it+1
             if (it == 0) {
                 Fa = src[1]; Fb = src[0];                      // u^nt, u^{nt-1}
             } else {
-                int o1 = -1, o2 = -1;
-                for (int i = 0; i < 4; i++)
-                    if (i != f1 && i != f0) { (o1 < 0 ? o1 : o2) = i; }
-                if ((rc = step2_impl(c, FDW_MODE_PLAIN, src[f1], src[f0], c->d_v2, src[o1], src[o2], 0, nullptr, -1, 0, Step2Extra{}, c->stream))) return rc;
+                int o1, o2;
+                spare_pair(f1, f0, &o1, &o2);
+                FDW_TRY(step2_impl(c, FDW_MODE_PLAIN, src[f1], src[f0], c->d_v2, src[o1], src[o2], 0, nullptr, -1, 0, Step2Extra{}, c->stream));
                 Fa = src[o1]; Fb = src[o2];
                 f0 = o1; f1 = o2;
             }
-            int q1 = -1, q2 = -1;
-            for (int i = 0; i < 4; i++)
-                if (i != rn && i != ro) { (q1 < 0 ? q1 : q2) = i; }
+            int q1, q2;
+            spare_pair(rn, ro, &q1, &q2);
             Step2Extra ex;
             ex.inj2 = samples(it + 1); ex.psrc_a = Fa; ex.psrc_b = Fb; ex.img = c->d_img;
-            if ((rc = step2_impl(c, FDW_MODE_RECV, rcv[rn], rcv[ro], c->d_v2, rcv[q1], rcv[q2], it > 0, samples(it), -1, gz, ex, c->stream))) return rc;
+            FDW_TRY(step2_impl(c, FDW_MODE_RECV, rcv[rn], rcv[ro], c->d_v2, rcv[q1], rcv[q2], it > 0, samples(it), -1, gz, ex, c->stream));
             ro = q1; rn = q2;
             it += 2;
         } else {
-            const float* F;
-            if (it == 0) F = src[1];
-            else if (it == 1) F = src[0];
-            else if (c->h <= kMaxFastHalfOrder && !c->use_generic && !c->no_fused_back) {
-                // the whole iteration in ONE pass: the source field is stepped in place (F_k overwrites F_{k-2}) in the same kernel
-                // that steps the receiver field, and meets the new receiver row in registers for the imaging condition
-                if ((rc = step_impl(c, FDW_MODE_BACK, rcv[rn], rcv[ro], c->d_v2, 0, c->nxl, it > 0, samples(it), 0, gz, src[f1], c->d_img, c->stream,
-                                    nullptr, 0, src[f0])))
-                    return rc;
-                std::swap(f1, f0);
-                std::swap(rn, ro);
-                it += 1;
-                continue;
-            } else {
-                // one-step reconstruction in place: the new field overwrites F_{k-2}
-                if ((rc = step_impl(c, FDW_MODE_PLAIN, src[f1], src[f0], c->d_v2, 0, c->nxl, 0, nullptr, -1, 0, nullptr, nullptr, c->stream))) return rc;
-                std::swap(f1, f0);
-                F = src[f1];
-            }
-            if ((rc = step_impl(c, FDW_MODE_RECV, rcv[rn], rcv[ro], c->d_v2, 0, c->nxl, it > 0, samples(it), 0, gz, F, c->d_img, c->stream))) return rc;
+            // iteration 0 images u^nt, iteration 1 u^{nt-1}; from iteration 2 on F_k overwrites F_{k-2}
+            FDW_TRY(back_iter(c, it >= 2, it == 0 ? src[f0] : src[f1], src[f0], rcv[rn], rcv[ro], c->d_v2, 0, c->nxl, it > 0, samples(it), gz,
+                              c->d_img, c->stream));
+            if (it >= 2) std::swap(f1, f0);
             std::swap(rn, ro);
             it += 1;
         }
@@ -1201,6 +1136,15 @@ static int zero_fields(fdw_ctx* c, float* const f[], int n)
 {
     for (int i = 0; i < n; i++) HIP_TRY(hipMemsetAsync(f[i], 0, field_elems(c) * sizeof(float), c->stream));
     return FDW_OK;
+}
+
+// the backward loop's source-field buffers after the forward loop: the snapshots where it left them (fld[ip], fld[ipp]), then the other two
+// of the first four
+static void source_buffers(const fdw_ctx* c, int ip, int ipp, float* src[4])
+{
+    int o1, o2;
+    spare_pair(ip, ipp, &o1, &o2);
+    src[0] = c->fld[ip]; src[1] = c->fld[ipp]; src[2] = c->fld[o1]; src[3] = c->fld[o2];
 }
 
 extern "C" int fdw_back(fdw_ctx* c, const float* v2, const float* snap0, const float* snap1, const float* d_obs, int gz,
@@ -1216,10 +1160,8 @@ extern "C" int fdw_back(fdw_ctx* c, const float* v2, const float* snap0, const f
     if ((rc = upload_rows(c, c->d_v2, v2, c->stream)) || (rc = upload_gather(c, d_obs)) || (rc = image_to_device(c, imloc))) return rc;
     // the reference uploads the two snapshots into d_pp at it = 0 and 1 (R:304-314); having both on the device up front is the same
     if ((rc = upload_rows(c, c->fld[0], snap0, c->stream)) || (rc = upload_rows(c, c->fld[1], snap1, c->stream))) return rc;
-    float* const src[4] = {c->fld[0], c->fld[1], c->fld[2], c->fld[3]};
-    float* const rcv[4] = {c->fld[4], c->fld[5], c->fld[6], c->fld[7]};
-    if ((rc = zero_fields(c, rcv, 2))) return rc;                   // R:513-514
-    if ((rc = back_loop(c, src, rcv, gz, nsteps))) return rc;
+    if ((rc = zero_fields(c, c->fld + 4, 2))) return rc;             // R:513-514
+    if ((rc = back_loop(c, c->fld, c->fld + 4, gz, nsteps))) return rc;
     if ((rc = image_to_host(c, imloc))) return rc;
     HIP_TRY(hipStreamSynchronize(c->stream));
     return FDW_OK;
@@ -1243,16 +1185,12 @@ static int shot_impl(fdw_ctx* c, const float* v2, int sx, int sz, int gz, const 
         (rc = image_to_device(c, imloc)))
         return rc;
     if ((rc = forward_loop(c, &ip, &ipp, sx, sz, nt))) return rc;
-    float *d_p = c->fld[ip], *d_pp = c->fld[ipp];
-    if (P && (rc = download_rows(c, P, d_p, c->stream))) return rc;
-    if (PP && (rc = download_rows(c, PP, d_pp, c->stream))) return rc;
-    // the snapshots stay where the forward pass left them; the other two of the first four buffers are the spares
-    float* src[4] = {d_p, d_pp, nullptr, nullptr};
-    for (int i = 0, n = 2; i < 4; i++)
-        if (c->fld[i] != d_p && c->fld[i] != d_pp) src[n++] = c->fld[i];
-    float* const rcv[4] = {c->fld[4], c->fld[5], c->fld[6], c->fld[7]};
-    if ((rc = zero_fields(c, rcv, 2))) return rc;
-    if ((rc = back_loop(c, src, rcv, gz, nt))) return rc;
+    if (P && (rc = download_rows(c, P, c->fld[ip], c->stream))) return rc;
+    if (PP && (rc = download_rows(c, PP, c->fld[ipp], c->stream))) return rc;
+    float* src[4];
+    source_buffers(c, ip, ipp, src);
+    if ((rc = zero_fields(c, c->fld + 4, 2))) return rc;
+    if ((rc = back_loop(c, src, c->fld + 4, gz, nt))) return rc;
     if ((rc = image_to_host(c, imloc))) return rc;
     HIP_TRY(hipStreamSynchronize(c->stream));
     return FDW_OK;
@@ -1311,9 +1249,8 @@ extern "C" int fdw_dev_model_steps(fdw_ctx* c, float* d_p, float* d_pp, const fl
         float* B[4] = {d_p, d_pp, c->fld[2], c->fld[3]};
         int iP = 0, iPP = 1;
         for (; nsteps - k >= kPipeSteps; k += kPipeSteps) {
-            int o1 = -1, o2 = -1;
-            for (int i = 0; i < 4; i++)
-                if (i != iP && i != iPP) { (o1 < 0 ? o1 : o2) = i; }
+            int o1, o2;
+            spare_pair(iP, iPP, &o1, &o2);
             const int it = it0 + k;
             rc = stepn_impl(c, FDW_MODE_MOD, B[iP], B[iPP], d_v2, B[o1], B[o2], 1, d_srce ? d_srce + it : nullptr, sx, sz, s, RowRanges{},
                             d_rec ? d_rec + (size_t)it * c->nx : nullptr, gz);
@@ -1851,7 +1788,7 @@ static bool batch_ok(const fdw_ctx* c)
 {
     if (c->prm.dialect == FDW_DIALECT_MOD) return c->h <= kMaxFastHalfOrder && !c->use_generic && !pipe_pays(c);
     return c->prm.dialect == FDW_DIALECT_RTM && c->h <= kMaxFastHalfOrder && !c->use_generic && !c->no_fused_back && !two_step_pays(c) &&
-           !pipe_pays(c) && c->prm.nxb + c->nx <= c->upd_x1 /* no receiver rows outside the time-stepped extent */;
+           !pipe_pays(c) && fdw_receivers_stepped(c);
 }
 
 extern "C" int fdw_shot_batch_max(const fdw_ctx* c)
@@ -1926,28 +1863,21 @@ extern "C" int fdw_shot_batch(fdw_ctx* c, int nshots, const float* v2_all, unsig
     if (std::min(sx0, sx_last) < 0 || std::max(sx0, sx_last) >= c->prm.nxe || std::max(sx0, sx_last) >= c->upd_x1)
         return fail(FDW_EINVAL, "source rows %d..%d leave the rows the reference time-steps (< %d)", sx0, sx_last, c->upd_x1);
     HIP_TRY(hipSetDevice(c->device));
+    const long long draws = fdw_border_draws(c->nx, c->nz, c->prm.nxb, c->prm.nzb);
+    auto one_by_one = [&] {
+        for (int b = 0; b < nshots; b++) {
+            if (!v2_all) FDW_TRY(fdw_dev_extendvel_linear(c, draw_offset + (unsigned long long)b * draws, nullptr));
+            FDW_TRY(shot_impl(c, v2_all ? v2_all + b * ne : nullptr, sx0 + b * dsx, sz, gz, srce, d_obs + b * ng, imloc + b * ni, nullptr, nullptr));
+        }
+        return (int)FDW_OK;
+    };
+    if (nshots == 1 || !batch_ok(c)) return one_by_one();      // nothing to gain or a regime the batched launches do not cover
     int rc;
-    if (nshots == 1 || !batch_ok(c)) {      // nothing to gain or a regime the batched launches do not cover: the shots one after the other
-        for (int b = 0; b < nshots; b++) {
-            if (!v2_all && (rc = fdw_dev_extendvel_linear(c, draw_offset + (unsigned long long)b * fdw_border_draws(c->nx, c->nz, c->prm.nxb, c->prm.nzb), nullptr)))
-                return rc;
-            if ((rc = shot_impl(c, v2_all ? v2_all + b * ne : nullptr, sx0 + b * dsx, sz, gz, srce, d_obs + b * ng, imloc + b * ni, nullptr, nullptr))) return rc;
-        }
-        return FDW_OK;
-    }
     if ((rc = ensure_work_buffers(c, 8, true))) return rc;
-    if ((rc = ensure_batch_buffers(c, nshots, true)) == FDW_ENOMEM) {          // no room for the batch: the shots one after the other
-        for (int b = 0; b < nshots; b++) {
-            if (!v2_all && (rc = fdw_dev_extendvel_linear(c, draw_offset + (unsigned long long)b * fdw_border_draws(c->nx, c->nz, c->prm.nxb, c->prm.nzb), nullptr)))
-                return rc;
-            if ((rc = shot_impl(c, v2_all ? v2_all + b * ne : nullptr, sx0 + b * dsx, sz, gz, srce, d_obs + b * ng, imloc + b * ni, nullptr, nullptr))) return rc;
-        }
-        return FDW_OK;
-    }
+    if ((rc = ensure_batch_buffers(c, nshots, true)) == FDW_ENOMEM) return one_by_one();      // no room for the batch
     if (rc || (rc = upload_source(c, srce, nt))) return rc;
     hipStream_t s = c->stream;
     if ((rc = gathers_to_device(c, d_obs, c->b_dobs, nshots))) return rc;      // [shot][nx][nt] -> [shot][nt][nx]
-    const long long draws = fdw_border_draws(c->nx, c->nz, c->prm.nxb, c->prm.nzb);
     if (!v2_all) {      // the shots' draws are consecutive in the stream: one launch generates them all
         HIP_TRY(hipStreamSynchronize(s));                     // a larger draw buffer replaces one the stream may still be reading
         if ((rc = ensure_draws(c, draws * nshots))) return rc;
@@ -1975,12 +1905,9 @@ extern "C" int fdw_shot_batch(fdw_ctx* c, int nshots, const float* v2_all, unsig
         if ((rc = fdw_dev_steps2(c, c->fld, c->d_v2, c->d_srce, sx0, sz, 0, nt, 0, &ip, &ipp, s))) return rc;
         for (int b = 0; b < nshots && nt > 0; b++)
             if ((rc = fdw_dev_taper_finalize(c, c->fld[ip] + b * fe, s))) return rc;
-        float *d_p = c->fld[ip], *d_pp = c->fld[ipp];
-        float* src[4] = {d_p, d_pp, nullptr, nullptr};
-        for (int i = 0, n = 2; i < 4; i++)
-            if (c->fld[i] != d_p && c->fld[i] != d_pp) src[n++] = c->fld[i];
-        float* const rcv[4] = {c->fld[4], c->fld[5], c->fld[6], c->fld[7]};
-        if ((rc = back_loop(c, src, rcv, gz, nt))) return rc;
+        float* src[4];
+        source_buffers(c, ip, ipp, src);
+        if ((rc = back_loop(c, src, c->fld + 4, gz, nt))) return rc;
     }
     for (int b = 0; b < nshots; b++)
         HIP_TRY(hipMemcpy2DAsync(imloc + b * ni, (size_t)c->nz * sizeof(float), c->b_img + b * fe + (size_t)c->prm.nxb * c->pitch + c->prm.nzb,
@@ -2001,19 +1928,15 @@ extern "C" int fdw_model_shot_batch(fdw_ctx* c, int nshots, const float* vel2, i
     const int sx_last = sx0 + (nshots - 1) * dsx;
     if (std::min(sx0, sx_last) < 0 || std::max(sx0, sx_last) >= c->prm.nxe) return fail(FDW_EINVAL, "source rows %d..%d leave the grid", sx0, sx_last);
     const size_t nx = c->nx, ng = nx * (size_t)nt, fe = field_elems(c);
-    int rc;
-    if (nshots == 1 || nt == 0 || nt > c->prm.nt || !batch_ok(c)) {
-        for (int b = 0; b < nshots; b++)
-            if ((rc = fdw_model_shot(c, vel2, sx0 + b * dsx, sz, gz, srce, nt, data + b * ng))) return rc;
-        return FDW_OK;
-    }
+    auto one_by_one = [&] {
+        for (int b = 0; b < nshots; b++) FDW_TRY(fdw_model_shot(c, vel2, sx0 + b * dsx, sz, gz, srce, nt, data + b * ng));
+        return (int)FDW_OK;
+    };
+    if (nshots == 1 || nt == 0 || nt > c->prm.nt || !batch_ok(c)) return one_by_one();
     HIP_TRY(hipSetDevice(c->device));
+    int rc;
     if ((rc = ensure_work_buffers(c, 2, false))) return rc;
-    if ((rc = ensure_batch_buffers(c, nshots, false)) == FDW_ENOMEM) {         // no room for the batch: the shots one after the other
-        for (int b = 0; b < nshots; b++)
-            if ((rc = fdw_model_shot(c, vel2, sx0 + b * dsx, sz, gz, srce, nt, data + b * ng))) return rc;
-        return FDW_OK;
-    }
+    if ((rc = ensure_batch_buffers(c, nshots, false)) == FDW_ENOMEM) return one_by_one();      // no room for the batch: the shots one after the other
     if (rc || (rc = upload_source(c, srce, nt))) return rc;
     if ((rc = ensure_cap(&c->d_raw, &c->raw_cap, ng * nshots))) return rc;
     hipStream_t s = c->stream;

@@ -101,12 +101,6 @@ Rccl* rccl()
         ncclResult_t r_ = (call);                                                                                        \
         if (r_ != 0) return fdw_fail(FDW_ECOMM, "%s failed: %s", #call, rccl()->GetErrorString ? rccl()->GetErrorString(r_) : "?"); \
     } while (0)
-#define HIP_TRY(call)                                                                                            \
-    do {                                                                                                         \
-        hipError_t e_ = (call);                                                                                  \
-        if (e_ != hipSuccess) return fdw_fail(FDW_EHIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); \
-    } while (0)
-
 // A rank that dies (an error on one host thread) must not leave its neighbours waiting for ever
 constexpr std::chrono::seconds kRendezvousTimeout(120);
 

@@ -9,6 +9,30 @@
 // sets fdw_last_error() of the calling thread and returns `code`
 int fdw_fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
 
+// return FDW_EHIP (with the failing call in fdw_last_error()) / any other error code from the enclosing function
+#define HIP_TRY(call)                                                                                            \
+    do {                                                                                                         \
+        hipError_t e_ = (call);                                                                                  \
+        if (e_ != hipSuccess) return fdw_fail(FDW_EHIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); \
+    } while (0)
+#define FDW_TRY(call)              \
+    do {                           \
+        int rc_ = (call);          \
+        if (rc_ != FDW_OK) return rc_; \
+    } while (0)
+
+// the two of four rotating buffers that hold neither a nor b, in index order
+inline void spare_pair(int a, int b, int* o1, int* o2)
+{
+    int n = 0;
+    for (int i = 0; i < 4; i++)
+        if (i != a && i != b) (n++ == 0 ? *o1 : *o2) = i;
+}
+
+// every receiver row (interior rows nxb .. nxb+nx-1 of the global grid, R:126-129) lies below xlim, i.e. is time-stepped: the wave-pipeline
+// passes of the backward loop and the batched shots have no static-row epilogue for the others
+int fdw_receivers_stepped(const fdw_ctx* c);
+
 constexpr int FDW_COMM_MAX_FIELDS = 8;
 
 // Halo exchange of `nfields` fields with the two neighbouring ranks, enqueued on `stream` (fdw_comm.cpp)

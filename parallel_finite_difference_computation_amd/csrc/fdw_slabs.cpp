@@ -28,17 +28,6 @@
 #include "fdw_internal.h"
 #include "fdwave.h"
 
-#define HIP_TRY(call)                                                                                            \
-    do {                                                                                                         \
-        hipError_t e_ = (call);                                                                                  \
-        if (e_ != hipSuccess) return fdw_fail(FDW_EHIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); \
-    } while (0)
-#define FDW_TRY(call)              \
-    do {                           \
-        int rc_ = (call);          \
-        if (rc_ != FDW_OK) return rc_; \
-    } while (0)
-
 namespace {
 constexpr int kPipe = 4;      // time steps per pass of the wave-pipeline kernel (fdw_dev_step4)
 
@@ -182,7 +171,7 @@ extern "C" int fdw_slabs_create(const fdw_params* prm, fdw_comm* comm, int devic
     s->nbuf = (s->pipe || (s->world == 1 && fdw_steps_per_pass(s->ctx) > 1)) ? 4 : 2;
     // the same question for the backward loop (one more condition: no receiver rows beyond the time-stepped rows); world 1: whatever the grid asks for
     double no_bpipe = ((s->world == 1 ? fdw_steps_per_pass(s->ctx) == kPipe : s->pipe) && fdw_back_pipe_active(s->ctx)) ? 0.0 : 1.0;
-    if (const char* ev = getenv("FDW_SLAB_PIPE")) no_bpipe = (atoi(ev) && s->h == 4 && (s->world == 1 || s->ksteps % kPipe == 0) && s->prm.nxb + (s->prm.nxe - 2 * s->prm.nxb) <= (s->prm.compat ? 8 * (s->prm.nxe / 8) : s->prm.nxe)) ? 0.0 : 1.0;
+    if (const char* ev = getenv("FDW_SLAB_PIPE")) no_bpipe = (atoi(ev) && s->h == 4 && (s->world == 1 || s->ksteps % kPipe == 0) && fdw_receivers_stepped(s->ctx)) ? 0.0 : 1.0;
     if (comm && (rc = fdw_comm_allreduce(comm, &no_bpipe, 1)) != FDW_OK) {
         fdw_slabs_destroy(s);
         return rc;
@@ -274,9 +263,8 @@ extern "C" int fdw_slabs_dev_forward(fdw_slabs* s, float* const* buf, const floa
             const int passes = kk / kPipe;
             const bool split_last = s->overlap && s->world > 1 && more && (s->o1 - s->o0) >= 2 * G + 16;
             for (int j = 1; j <= passes; j++) {
-                int o1 = -1, o2 = -1;
-                for (int i = 0; i < 4; i++)
-                    if (i != *ip && i != *ipp) { (o1 < 0 ? o1 : o2) = i; }
+                int o1, o2;
+                spare_pair(*ip, *ipp, &o1, &o2);
                 const float *p_in = buf[*ipp], *pp_in = buf[*ip];      // the kernel's p is the newest field
                 const int lo = s->has_lo ? kPipe * h * j : 0, hi = nxl - (s->has_hi ? kPipe * h * j : 0);
                 if (j == passes && split_last) {
@@ -368,13 +356,6 @@ extern "C" int fdw_slabs_dev_back(fdw_slabs* s, float* const* f, float* const* r
     };
     // four iterations on rows [a, b) (+ [a2, b2)): F_it .. F_{it+3} into f[4], f[5], f[o1], f[o2]; r^{it+3}, r^{it+4} into r[q1], r[q2]
     int o1 = 0, o2 = 0, q1 = 0, q2 = 0;
-    auto pick_spares = [&] {
-        o1 = o2 = q1 = q2 = -1;
-        for (int i = 0; i < 4; i++) {
-            if (i != f1 && i != f0) { (o1 < 0 ? o1 : o2) = i; }
-            if (i != rn && i != ro) { (q1 < 0 ? q1 : q2) = i; }
-        }
-    };
     auto pass = [&](int a, int b, int a2, int b2, int xchunk, hipStream_t st) {
         if (a >= b && a2 >= b2) return (int)FDW_OK;
         return fdw_dev_back4(c, f[f1], f[f0], f[o1], f[o2], f[4], f[5], r[rn], r[ro], r[q1], r[q2], d_v2, d_samples + (size_t)it * nx, (int)nx, gz, d_img,
@@ -393,7 +374,10 @@ extern "C" int fdw_slabs_dev_back(fdw_slabs* s, float* const* f, float* const* r
             const int n = four_now ? kPipe : 1;
             const bool last = j + n - 1 == kk;
             const int r0 = s->has_lo ? h * (j + n - 1) : 0, r1 = nxl - (s->has_hi ? h * (j + n - 1) : 0);
-            if (four_now) pick_spares();
+            if (four_now) {
+                spare_pair(f1, f0, &o1, &o2);
+                spare_pair(rn, ro, &q1, &q2);
+            }
             if (split_last && last) {
                 const int lo_end = s->has_lo ? r0 + G : r0, hi_beg = s->has_hi ? r1 - G : r1;
                 float* nxt[4];
