@@ -51,14 +51,6 @@ namespace fdw {
 // ------------------------------------------------------------------------------------------------
 // small helpers
 // ------------------------------------------------------------------------------------------------
-// Timing experiments only (scripts/build_ablations.sh builds throw-away libraries with -DFDW_ABL_BITS=n; any bit
-// breaks the results): 1 fp32 update, 2 no strip-halo load, 4 no store, 8 no lane exchange, 16 trivial Laplacian,
-// 32 every row aliases row 0 (loads become cache hits: pure issue/VALU time), 64 pipeline kernel without its barriers;
-// pipeline kernel only: 128 no LDS hand-over, 256 trivial Laplacian, 512 fp32 update, 1024 no global loads/stores in the march, 2048 no lane exchange.
-#ifndef FDW_ABL_BITS
-#define FDW_ABL_BITS 0
-#endif
-
 struct f4 {
     float v[4];
 };
@@ -69,13 +61,10 @@ __device__ __forceinline__ f4 f4_zero()
     r.v[0] = r.v[1] = r.v[2] = r.v[3] = 0.0f;
     return r;
 }
-// Cache policy of the streams (FDW_NT bitmask; measured in scripts/ubench/rwmix.hip and on the kernel):
-//   1 pointwise inputs (pp, v2, psrc, img) are read once per step -> nontemporal loads
-//   2 the result is not read again in this launch               -> nontemporal store
-//   4 p rows (re-read by the neighbouring chunk as halo)        -> default policy unless set
-#ifndef FDW_NT
-#define FDW_NT 3
-#endif
+// Cache policy of the streams (measured in scripts/ubench/rwmix.hip and on the kernel):
+//   p rows (re-read by the neighbouring chunk as halo)        -> default policy            (f4_load, f4_load_arr(.., false))
+//   pointwise inputs (pp, v2, psrc, img) are read once per step -> nontemporal loads        (f4_load_stream, f4_load_arr(.., true))
+//   the result is not read again in this launch               -> nontemporal stores        (f4_store, f4_store_rsrc, f4_store_arr)
 typedef float v4f __attribute__((ext_vector_type(4)));
 
 // scalar (wave-uniform) row base + 32-bit per-lane byte offset: global_load saddr + voffset form
@@ -88,13 +77,13 @@ __device__ __forceinline__ f4 f4_load_t(const float* row, unsigned voff_bytes)
     r.v[0] = t.x; r.v[1] = t.y; r.v[2] = t.z; r.v[3] = t.w;
     return r;
 }
-__device__ __forceinline__ f4 f4_load(const float* row, unsigned voff_bytes) { return f4_load_t<(FDW_NT & 4) != 0>(row, voff_bytes); }
-__device__ __forceinline__ f4 f4_load_stream(const float* row, unsigned voff_bytes) { return f4_load_t<(FDW_NT & 1) != 0>(row, voff_bytes); }
+__device__ __forceinline__ f4 f4_load(const float* row, unsigned voff_bytes) { return f4_load_t<false>(row, voff_bytes); }
+__device__ __forceinline__ f4 f4_load_stream(const float* row, unsigned voff_bytes) { return f4_load_t<true>(row, voff_bytes); }
 __device__ __forceinline__ void f4_store(float* row, unsigned voff_bytes, const f4& a)
 {
     v4f* ptr = reinterpret_cast<v4f*>(reinterpret_cast<char*>(row) + voff_bytes);
     const v4f t = {a.v[0], a.v[1], a.v[2], a.v[3]};
-    if (FDW_NT & 2) __builtin_nontemporal_store(t, ptr); else *ptr = t;
+    __builtin_nontemporal_store(t, ptr);
 }
 
 template <int N, class F>
@@ -123,9 +112,6 @@ __device__ __forceinline__ float laplacian_pt(const float* W, int e, const float
                                               const float* cz)
 {
     float acmz = 0.0f, acmx = 0.0f;
-#if FDW_ABL_BITS & 16
-    return W[e] + W[8 + e] + col[0] + col[2 * H];   // keep every input alive, almost no arithmetic
-#endif
 #pragma unroll
     for (int io = 0; io <= 2 * H; ++io) {
         acmz = acmz + W[4 + e - H + io] * cz[io];
@@ -149,9 +135,6 @@ __device__ __forceinline__ float laplacian_dd_pt(const float* W, int e, const fl
 // the update once prod = (v2*dt2)*lap is formed (fp32, as the reference's float expression does; R:89)
 __device__ __forceinline__ float leapfrog_prod(float p, float pp, float prod)
 {
-#if FDW_ABL_BITS & 512
-    return (2.0f * p - pp) + prod;      // timing experiment: what the fp64 chain (3 cvt + fma + add + cvt per cell) costs
-#endif
     // 2.*p - pp: the product is exact in double, so the fused form rounds once exactly like the reference's two operations
     const double d = __builtin_fma(2.0, (double)p, -(double)pp) + (double)prod;
     float r = (float)d;
@@ -163,9 +146,6 @@ __device__ __forceinline__ float leapfrog_prod(float p, float pp, float prod)
 __device__ __forceinline__ float leapfrog_pt(float p, float pp, float v2, float dt2, float lap)
 {
     const float prod = (v2 * dt2) * lap;
-#if FDW_ABL_BITS & 1
-    return (2.0f * p - pp) + prod;
-#endif
     const double d = 2.0 * (double)p - (double)pp + (double)prod;
     return (float)d;
 }
@@ -178,25 +158,8 @@ __device__ __forceinline__ float lane_shift(float x)
     // bound_ctrl: the lane without a source reads 0, so the builtin's "old" operand is dead and costs no initialising v_mov
     return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), CTRL, 0xf, 0xf, true));
 }
-#ifndef FDW_DPP
-#define FDW_DPP 1          // 0: __shfl_up / __shfl_down (timing experiments)
-#endif
-__device__ __forceinline__ float lane_up(float x)
-{
-#if FDW_DPP
-    return lane_shift<0x138>(x);        // wave_shr:1 -- lane i takes lane i-1's
-#else
-    return __shfl_up(x, 1, 64);
-#endif
-}
-__device__ __forceinline__ float lane_down(float x)
-{
-#if FDW_DPP
-    return lane_shift<0x130>(x);        // wave_shl:1
-#else
-    return __shfl_down(x, 1, 64);
-#endif
-}
+__device__ __forceinline__ float lane_up(float x) { return lane_shift<0x138>(x); }       // wave_shr:1 -- lane i takes lane i-1's
+__device__ __forceinline__ float lane_down(float x) { return lane_shift<0x130>(x); }     // wave_shl:1
 
 // ---- packed fp32 (v_pk_mul_f32 / v_pk_add_f32: two IEEE fp32 operations per lane and instruction) --------------
 // The two-step kernel is VALU-issue bound (SQ counters: ~48 VALU instructions per point and step, 85 % VALU busy at
@@ -271,14 +234,6 @@ template <int H, class Row>
 __device__ __forceinline__ void laplacian_quad(const ZPairs& z, Row&& row, const CoefPairs<H>& c, v2f& lap01, v2f& lap23)
 {
     v2f az0 = {0.0f, 0.0f}, ax0 = {0.0f, 0.0f}, az1 = {0.0f, 0.0f}, ax1 = {0.0f, 0.0f};
-#if FDW_ABL_BITS & 256
-    {      // timing experiment: every input kept alive, almost no arithmetic
-        const f4 r0 = row(std::integral_constant<int, 0>{}), r8 = row(std::integral_constant<int, 2 * H>{});
-        lap01 = z.E[0] + z.E[5] + v2f{r0.v[0], r0.v[1]} + v2f{r8.v[0], r8.v[1]};
-        lap23 = z.O[0] + z.O[4] + v2f{r0.v[2], r0.v[3]} + v2f{r8.v[2], r8.v[3]};
-        return;
-    }
-#endif
     static_for<2 * H + 1>([&](auto IO) {
         constexpr int io = decltype(IO)::value;
         constexpr int k0 = 4 - H + io, k1 = 6 - H + io;
@@ -347,14 +302,6 @@ __device__ __forceinline__ void laplacian_fast_quad(const ZPairs& z, Row&& row, 
         constexpr int k = decltype(KK)::value;
         return (k & 1) ? z.O[k >> 1] : z.E[k >> 1];
     };
-#if FDW_ABL_BITS & 256
-    {      // timing experiment: every input kept alive, almost no arithmetic
-        const f4 r0 = row(std::integral_constant<int, 0>{}), r8 = row(std::integral_constant<int, 2 * H>{});
-        lap01 = z.E[0] + z.E[5] + v2f{r0.v[0], r0.v[1]} + v2f{r8.v[0], r8.v[1]};
-        lap23 = z.O[0] + z.O[4] + v2f{r0.v[2], r0.v[3]} + v2f{r8.v[2], r8.v[3]};
-        return;
-    }
-#endif
     const f4 rc = row(std::integral_constant<int, H>{});
     v2f a0 = pk_mul_sel<0>(v2f{rc.v[0], rc.v[1]}, c0), a1 = pk_mul_sel<0>(v2f{rc.v[2], rc.v[3]}, c0);
     static_for<H>([&](auto KK) {
@@ -431,7 +378,7 @@ __device__ __forceinline__ void f4_store_rsrc(float* row, unsigned row_bytes, un
 {
     const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(row, 0, row_bytes, 0x00020000);
     const v4f t = {a.v[0], a.v[1], a.v[2], a.v[3]};
-    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4u, t), rs, voff_bytes, 0, (FDW_NT & 2) ? 2 : 0);
+    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4u, t), rs, voff_bytes, 0, 2);
 }
 
 __device__ __forceinline__ f4 f4_load_rsrc(const float* row, unsigned row_bytes, unsigned voff_bytes, bool nt)
@@ -468,10 +415,8 @@ __device__ __forceinline__ f4 f4_load_arr(__amdgpu_buffer_rsrc_t rs, unsigned vo
 __device__ __forceinline__ void f4_store_arr(__amdgpu_buffer_rsrc_t rs, unsigned voff_bytes, unsigned row_off_bytes, const f4& a)
 {
     const v4f t = {a.v[0], a.v[1], a.v[2], a.v[3]};
-    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4u, t), rs, voff_bytes, row_off_bytes, (FDW_NT & 2) ? 2 : 0);
-#ifndef FDW_NO_STORE_PAD       // (defined only to show that tests/test_slabs_gpu.py::test_full_size_shot_is_reproducible... catches the hazard)
+    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4u, t), rs, voff_bytes, row_off_bytes, 2);
     asm volatile("s_nop 1" : : "v"(t) : "memory");
-#endif
 }
 
 }  // namespace fdw

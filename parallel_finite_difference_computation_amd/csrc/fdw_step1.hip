@@ -57,11 +57,7 @@ __device__ __forceinline__ void march(const StepArgs& a, const ShotView& sv, con
     // condition instead of travelling through memory.
     using G = RingGeom<H, PF>;
     constexpr int R = G::R, LOOK = G::LOOK;
-#if FDW_ABL_BITS & 32
-    const size_t pitch = 0;   // every row aliases row 0: loads become L1 hits -> pure issue/VALU time
-#else
     const size_t pitch = (size_t)a.pitch;
-#endif
     const int z0 = zs + lane * 4;
     const bool partial = (zs + 256 > a.pitch);              // wave-uniform: last strip of a ragged row
     const bool act = z0 < a.pitch;                          // pitch % 4 == 0: a float4 never straddles a row end
@@ -125,12 +121,7 @@ __device__ __forceinline__ void march(const StepArgs& a, const ShotView& sv, con
 
     // ---- loaders: unconditional, clamped --------------------------------------------------------
     auto load_p = [&](int row) -> f4 { return f4_load(sv.p + (size_t)min(max(row, 0), rowmax) * pitch, voff); };
-    auto load_halo = [&](int row) -> f4 {
-#if FDW_ABL_BITS & 2
-        return f4_zero();
-#endif
-        return f4_load(sv.p + (size_t)row * pitch, hoff);
-    };
+    auto load_halo = [&](int row) -> f4 { return f4_load(sv.p + (size_t)row * pitch, hoff); };
     auto load_plain = [&](const float* base, int row) -> f4 { return f4_load_stream(base + (size_t)row * pitch, voff); };
     auto load_f = [&](int row) -> f4 { return f4_load(sv.psrc + (size_t)min(max(row, 0), rowmax) * pitch, voff); };
     auto load_fhalo = [&](int row) -> f4 { return f4_load(sv.psrc + (size_t)row * pitch, hoff); };
@@ -199,19 +190,14 @@ __device__ __forceinline__ void march(const StepArgs& a, const ShotView& sv, con
                     if (a.pp_twice) taper_row(ppt, tzc, znc, r);
                 }
             }
-            // ---- z neighbours from the adjacent lanes (ds_bpermute), strip halo at the ends ----
+            // ---- z neighbours from the adjacent lanes (DPP lane shifts), strip halo at the ends ----
             const f4 c = ring[(U + H) % R];
             f4 lft, rgt;
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-#if FDW_ABL_BITS & 8
-                lft.v[e] = c.v[e] + hal.v[e];
-                rgt.v[e] = c.v[e] - hal.v[e];
-#else
                 const float up = lane_up(c.v[e]), dn = lane_down(c.v[e]);
                 lft.v[e] = lane_first ? hal.v[e] : up;
                 rgt.v[e] = lane_last ? hal.v[e] : dn;
-#endif
             }
             const bool rowok = (r >= a.lap_x0) && (r < a.lap_x1);
             f4 res, imr;
@@ -317,9 +303,6 @@ __device__ __forceinline__ void march(const StepArgs& a, const ShotView& sv, con
                     for (int e = 0; e < 4; ++e) imr.v[e] = (z0 + e < a.img_z1) ? imr.v[e] : qim[Q].v[e];
                 }
             }
-#if FDW_ABL_BITS & (4 | 32)
-            if (res.v[0] == 123.456f)
-#endif
             if (!partial) {
                 f4_store(sv.out + (size_t)r * pitch, voff, res);
                 if constexpr (IMG) f4_store(sv.img + (size_t)r * pitch, voff, imr);

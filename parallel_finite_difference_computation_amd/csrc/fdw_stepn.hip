@@ -25,28 +25,9 @@ namespace fdw {
 // k-1); in z every step costs H = one lane per side, so NS lanes per side of a wave are halo and 64-2NS owned.
 // Per point and step the arithmetic is the one-step kernel's (packed pairs as in the two-step kernel).
 // ------------------------------------------------------------------------------------------------
-#ifndef FDW_PIPE_PF
-#define FDW_PIPE_PF 2      // rows of global look-ahead of wave 0
-#endif
-#ifndef FDW_DD_WG
-#define FDW_DD_WG 4
-#endif
-#ifndef FDW_PIPE_WG
-#define FDW_PIPE_WG 5      // workgroups per CU the forward kernels are held to by their launch bounds (5 x 4 waves: 96 VGPRs)
-#endif
-#ifndef FDW_PIPE_OPT
-#define FDW_PIPE_OPT 993   // 1: waves skip the march steps outside their useful window; 4: the frame masks only in workgroups that touch the frame;
-                           // 32: workgroups away from the frame, the damped strip and the sources run the lean body (pipe_lean);
-                           // 64: neighbouring lanes' values through DPP (v_mov_b32_dpp wave_shr / wave_shl) instead of ds_bpermute_b32;
-                           // 128 / 256 / 512: the lean body compiled once for wave 0 and once for the other waves (forward kernel / source-field role / receiver
-                           // role of the fused backward kernel)
-#endif                     //    (bit 4 measured slower: 581 vs 590 Gpoints/s at 8192^2; bit 16: idle-step skipping for the modelling dialect, 5 % slower)
-#ifndef FDW_PIPE_ROWS
-#define FDW_PIPE_ROWS 1    // march steps between two workgroup barriers of the pipeline kernel (1 or 2)
-#endif
-// v2 FIFO depth: the last wave reads row m - (NS-1)(H+ROWS) while wave 0 writes rows m .. m+ROWS-1
+// v2 FIFO depth: the last wave reads row m - (NS-1)(H+1) while wave 0 writes row m, so (NS-1)(H+1)+1 rows, rounded up to 8 or 16
 constexpr int kFusedFifoRows = 20;      // fused backward kernel: a v2 row is 1 + 3 (H + 1) = 16 march steps under way from the first wave to the last
-constexpr int pipe_fifo_rows(int ns, int h, int rows) { return rows == 1 ? ((ns - 1) * (h + 1) + 1 <= 8 ? 8 : 16) : (ns - 1) * (h + rows) + rows; }
+constexpr int pipe_fifo_rows(int ns, int h) { return (ns - 1) * (h + 1) + 1 <= 8 ? 8 : 16; }
 template <int FD>
 __device__ __forceinline__ int pipe_fifo_slot(int m)
 {
@@ -64,37 +45,28 @@ __device__ __forceinline__ int pipe_fifo_slot(int m)
 // nor the source (instantiate with TAPER = false, INJ = 0): the kernel picks it per workgroup (pipe_lean)
 // WK: 0 = the wave finds out at run time whether it is wave 0 (full body); 1 / 2 = compiled for wave 0 / for the other waves (lean body)
 // NUM: 0 = the reference's exact arithmetic, 1 = FAST numerics (symmetric sums + fused multiply-adds, fdw_device.h)
-template <int H, int NS, bool TAPER, int INJ, int PF, bool DD = false, int BK = 0, int ROWS = FDW_PIPE_ROWS, bool LEAN = false, int WK = 0, int NUM = 0>
+template <int H, int NS, bool TAPER, int INJ, int PF, bool DD = false, int BK = 0, bool LEAN = false, int WK = 0, int NUM = 0>
 __device__ __forceinline__ void marchn(const Step2Args& a, const int lane, const int k, const int cs, const int xa, const int xe,
-                                       f4 (*link)[2][2][ROWS][64], f4 (*fifo)[64], f4 (*imf)[64] = nullptr, f4 (*linkx)[2][2][ROWS][64] = nullptr)
+                                       f4 (*link)[2][2][64], f4 (*fifo)[64], f4 (*imf)[64] = nullptr, f4 (*linkx)[2][2][64] = nullptr)
 {
     static_assert(!LEAN || (!TAPER && INJ == 0), "the lean body has no damping, no injection (and records no trace)");
     constexpr bool IMG = (BK == 2 || BK == 4);
     constexpr int D = (BK == 4) ? 1 : 0;                      // this role runs D march steps behind
     constexpr int DL = (BK >= 3) ? 1 : 0;                     // ... so both roles of the fused kernel loop one step longer
-    // ROWS march steps between two workgroup barriers (1 or 2): a wave consumes what its predecessor produced during the previous
-    // ROWS steps, so consecutive waves work H + ROWS rows apart and a wave's first good row comes ROWS later per stage.
+    // one march step per workgroup barrier (two measured slower: DESIGN.md section 3c): a wave consumes what its predecessor produced
+    // during the previous step, so consecutive waves work H + 1 rows apart
     constexpr int R = ((2 * H + PF + PF - 1) / PF) * PF;
     constexpr int LOOK = R - 2 * H;
-    constexpr int SK = H + ROWS;
-    constexpr int FD = BK >= 3 ? kFusedFifoRows : pipe_fifo_rows(NS, H, ROWS);
-    static_assert(ROWS == 1 || (ROWS == 2 && R % 2 == 0), "one or two rows per barrier");
-    static_assert(BK < 3 || ROWS == 1, "the fused backward kernel assumes one row per barrier");
+    constexpr int SK = H + 1;
+    constexpr int FD = BK >= 3 ? kFusedFifoRows : pipe_fifo_rows(NS, H);
+    static_assert((NS - 1) * SK + 1 <= FD, "the v2 FIFO holds every row from wave 0's to the last wave's");
     const bool first = WK == 1 ? true : (WK == 2 ? false : (k == 0));      // WK 1 / 2: the body compiled for wave 0 / for the other waves
     const int cell = cs + lane;
     const int z0 = cell * 4;
     const unsigned voff = (unsigned)min(max(z0, 0), a.pitch - 4) * 4u;
     const bool own = (lane >= NS) && (lane <= 63 - NS) && (z0 >= 0) && (z0 < a.pitch);
-#if FDW_ABL_BITS & 8192          // timing experiment: no global stores
-    const unsigned soff = kLaneOff;
-#else
     const unsigned soff = (own && (BK == 1 || k >= NS - 2)) ? voff : kLaneOff;      // only the last two waves store (BK 1: all four levels are kept)
-#endif
-#if FDW_ABL_BITS & 16384         // timing experiment: no global loads
-    const unsigned loff = kLaneOff;
-#else
     const unsigned loff = first ? voff : kLaneOff;                        // only wave 0 loads
-#endif
     const unsigned row_bytes = (unsigned)a.pitch * 4u;
     const int rowmax = a.nxl - 1;
     const unsigned arr_bytes = (unsigned)a.nxl * row_bytes;               // < 2 GiB (checked by the host)
@@ -147,18 +119,14 @@ __device__ __forceinline__ void marchn(const Step2Args& a, const int lane, const
         }
     };
     auto rowoff = [&](int row) -> unsigned { return LEAN ? (unsigned)row * row_bytes : (unsigned)min(max(row, 0), rowmax) * row_bytes; };
-#if FDW_ABL_BITS & 4096          // timing experiment: every load of the march reads the chunk's first rows again (cache hits: the cost of the instructions without the memory behind them)
-    auto lrow = [&](int row) -> unsigned { return (unsigned)(max(xa, 0) + (row & 3)) * row_bytes; };
-#else
-    auto lrow = [&](int row) -> unsigned { return rowoff(row); };
-#endif
-    auto load_p = [&](int row) -> f4 { return f4_load_arr(rs_p, loff, lrow(row), (FDW_NT & 4) != 0); };
-    auto load_pw = [&](__amdgpu_buffer_rsrc_t rs, int row) -> f4 { return f4_load_arr(rs, loff, lrow(row), (FDW_NT & 1) != 0); };
+    // cache policy (fdw_device.h): p rows are re-read by the neighbouring chunk, the pointwise streams are read once
+    auto load_p = [&](int row) -> f4 { return f4_load_arr(rs_p, loff, rowoff(row), false); };
+    auto load_pw = [&](__amdgpu_buffer_rsrc_t rs, int row) -> f4 { return f4_load_arr(rs, loff, rowoff(row), true); };
 
     // rows: wave 0's centre row at march step m is s0 + m (what the global loads follow); this wave's is rk + m
     const int s0 = xa - (NS - 1) * H - D, b0 = s0 - H;
     const int rk = s0 - k * SK;
-    const int M = (xe - xa) + (NS - 1) * (2 * H + ROWS) + DL;
+    const int M = (xe - xa) + (NS - 1) * (2 * H + 1) + DL;
     const int kp = max(k - 1, 0);
     f4 ring[R];
     f4 qpp[PF], qv2[PF];
@@ -180,8 +148,8 @@ __device__ __forceinline__ void marchn(const Step2Args& a, const int lane, const
             constexpr int mm = j + PF;
             qpp[mm] = load_pw(rs_pp, s0 + mm);
             if constexpr (BK != 4) qv2[mm] = load_pw(rs_v2, s0 + mm);
-            if constexpr (BK == 2) qlv[mm] = f4_load_arr(rs_lev, ioff, rowoff(rk + mm), (FDW_NT & 1) != 0);
-            if constexpr (IMG) qim[mm] = f4_load_arr(rs_img, imoff, rowoff(rk + mm), (FDW_NT & 1) != 0);
+            if constexpr (BK == 2) qlv[mm] = f4_load_arr(rs_lev, ioff, rowoff(rk + mm), true);
+            if constexpr (IMG) qim[mm] = f4_load_arr(rs_img, imoff, rowoff(rk + mm), true);
         }
         __builtin_amdgcn_sched_barrier(0);
     });
@@ -192,16 +160,13 @@ __device__ __forceinline__ void marchn(const Step2Args& a, const int lane, const
         });
     }
 
-    // A wave has nothing useful to compute before its window holds good rows of its predecessor (march steps < k (2H + ROWS); during the
+    // A wave has nothing useful to compute before its window holds good rows of its predecessor (march steps < k (2H + 1); during the
     // last 2H of them it only collects the rows entering its window) nor after the last row a later level needs from it: outside
     // [m_lo, m_hi) it keeps the barriers and its memory instructions, which are predicated off through the buffer descriptor so that
     // the s_waitcnt counting stays exact.  That frees a fifth of the issue slots of a 43-row chunk (7 % at 173 rows) for the other
-    // workgroups of the CU.
-    const int m_lo = k * (2 * H + ROWS) + D, m_hi = (xe - xa) + 2 * (NS - 1) * H + k * ROWS + D;
-    // The frame of the grid (rows / columns where the Laplacian or the update is masked) only concerns the workgroups that touch it;
-    // all others take the wave-uniform branch around the mask selects.
-    const bool edge = !LEAN && (!(FDW_PIPE_OPT & 4) || (cs * 4 < a.lap_z0) || (cs * 4 + 256 > min(a.lap_z1, a.upd_z1)) || (xa - (NS - 1) * H - NS * SK < max(a.lap_x0, 0)) ||
-                      (xe + (NS - 1) * H + NS * SK > min(a.lap_x1, a.upd_x1)));
+    // workgroups of the CU.  The modelling dialect (DD) runs every step: skipping measured 5 % slower there, its scalar Laplacian
+    // leaves no slack.
+    const int m_lo = k * (2 * H + 1) + D, m_hi = (xe - xa) + 2 * (NS - 1) * H + k + D;
 
     auto row_step = [&](const int mb, auto UU) {
         constexpr int U = decltype(UU)::value;
@@ -209,16 +174,12 @@ __device__ __forceinline__ void marchn(const Step2Args& a, const int lane, const
         constexpr int E = (U + 2 * H) % R;                      // slot of the row entering the window this step
         const int m = mb + U;
         const int r = rk + m;
-        constexpr int SLOT = U % ROWS;                          // which of the ROWS rows between two barriers
-        const int par = (m / ROWS) & 1;                          // link buffers alternate per barrier interval
-        constexpr bool SKIP = (FDW_PIPE_OPT & 1) && (!DD || (FDW_PIPE_OPT & 16));   // (the modelling dialect measured 5 % slower with it: its scalar Laplacian leaves no slack)
-        const bool act = !SKIP || ((m >= m_lo) && (m < m_hi));
-        const bool fill = !SKIP || ((m >= m_lo - 2 * H) && (m < m_hi));                   // collecting the rows that enter the window
+        const int par = m & 1;                                   // link buffers alternate per march step
+        const bool act = DD || ((m >= m_lo) && (m < m_hi));
+        const bool fill = DD || ((m >= m_lo - 2 * H) && (m < m_hi));                   // collecting the rows that enter the window
         // ---- what the previous wave handed over during march step m-1: the row entering this wave's window ----
         if (fill) {
-#if !(FDW_ABL_BITS & 128)
-            if (!first) ring[E] = link[kp][par ^ 1][0][SLOT][lane];
-#endif
+            if (!first) ring[E] = link[kp][par ^ 1][0][lane];
             if (wave_tap) taper_row(ring[E], r + H);            // damped once as "p" of this step
         }
         f4 u;
@@ -235,17 +196,11 @@ __device__ __forceinline__ void marchn(const Step2Args& a, const int lane, const
                 // v2 dt2 (R:89's first product) is formed once, here, and travels through the FIFO in place of v2
                 const v2f w01 = v2f{qv2[Q].v[0], qv2[Q].v[1]} * a.dt2, w23 = v2f{qv2[Q].v[2], qv2[Q].v[3]} * a.dt2;
                 qv2[Q].v[0] = w01.x; qv2[Q].v[1] = w01.y; qv2[Q].v[2] = w23.x; qv2[Q].v[3] = w23.y;
-#if !(FDW_ABL_BITS & 128)
                 fifo[pipe_fifo_slot<FD>(m)][lane] = qv2[Q];
-#endif
             }
         } else {
-#if FDW_ABL_BITS & 128
-            ppt = ring[(U + 1) % R]; v2t = ring[(U + 2) % R];
-#else
-            ppt = link[kp][par ^ 1][1][SLOT][lane];
+            ppt = link[kp][par ^ 1][1][lane];
             v2t = fifo[pipe_fifo_slot<FD>(m - D - k * SK)][lane];
-#endif
         }
         if (wave_tap) {
             taper_row(ppt, r);                                  // "pp": from memory once (+ once owed), from LDS once more
@@ -255,15 +210,8 @@ __device__ __forceinline__ void marchn(const Step2Args& a, const int lane, const
         f4 lft, rgt;
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-#if FDW_ABL_BITS & 2048
-            lft.v[e] = c1.v[(e + 1) & 3]; rgt.v[e] = c1.v[(e + 2) & 3];
-#elif FDW_PIPE_OPT & 64
-            lft.v[e] = lane_shift<0x138>(c1.v[e]);              // wave_shr:1 -- lane i takes lane i-1's
-            rgt.v[e] = lane_shift<0x130>(c1.v[e]);              // wave_shl:1
-#else
-            lft.v[e] = __shfl_up(c1.v[e], 1, 64);
-            rgt.v[e] = __shfl_down(c1.v[e], 1, 64);
-#endif
+            lft.v[e] = lane_up(c1.v[e]);
+            rgt.v[e] = lane_down(c1.v[e]);
         }
         const bool rowok = LEAN || ((r >= a.lap_x0) && (r < a.lap_x1));
         const bool rowupd = LEAN || ((r >= 0) && (r < a.upd_x1));
@@ -274,41 +222,26 @@ __device__ __forceinline__ void marchn(const Step2Args& a, const int lane, const
                 for (int e = 0; e < 4; ++e)
                     if (z0 + e == a.rec_z) a.rec[k * a.rec_n + (r - a.rec_x0)] = c1.v[e];
             }
-            // the sibling's single-accumulator Laplacian, two cells per instruction (laplacian_dd_quad)
-            const ZPairs zp = zpairs(lft, c1, rgt);
-            v2f lapq[2];
-            if constexpr (NUM == 0) laplacian_dd_quad<H>(zp, [&](auto IO) -> const f4& { return ring[(U + decltype(IO)::value) % R]; }, cpk, ddinv, lapq[0], lapq[1]);
-            else lap_quad<1, H>(zp, [&](auto IO) -> const f4& { return ring[(U + decltype(IO)::value) % R]; }, cpk, c0p, lapq[0], lapq[1]);      // FAST: weights carry their spacing
-            static_for<2>([&](auto PP) {
-                constexpr int P = decltype(PP)::value;
-                v2f lap2 = lapq[P];
-                if constexpr (!LEAN) lap2 = v2f{(rowok && mlap[2 * P]) ? lap2.x : 0.0f, (rowok && mlap[2 * P + 1]) ? lap2.y : 0.0f};
-                const v2f prod2 = f4_pair(v2t, P) * lap2;          // v2t holds v2 dt2 (see above)
-#pragma unroll
-                for (int q = 0; q < 2; ++q) {
-                    const int e = 2 * P + q;
-                    const float upd = leapfrog_prod(c1.v[e], ppt.v[e], q ? prod2.y : prod2.x);
-                    u.v[e] = (LEAN || (rowupd && mupd[e])) ? upd : ppt.v[e];
-                }
-            });
-        } else {
-            const ZPairs zp = zpairs(lft, c1, rgt);
-            v2f lapq[2];
-            lap_quad<NUM, H>(zp, [&](auto IO) -> const f4& { return ring[(U + decltype(IO)::value) % R]; }, cpk, c0p, lapq[0], lapq[1]);
-            static_for<2>([&](auto PP) {
-                constexpr int P = decltype(PP)::value;
-                v2f lap2 = lapq[P];
-                if constexpr (!LEAN)
-                    if (edge) lap2 = v2f{(rowok && mlap[2 * P]) ? lap2.x : 0.0f, (rowok && mlap[2 * P + 1]) ? lap2.y : 0.0f};
-                const v2f prod2 = f4_pair(v2t, P) * lap2;          // v2t holds v2 dt2 (see above)
-#pragma unroll
-                for (int q = 0; q < 2; ++q) {
-                    const int e = 2 * P + q;
-                    const float upd = leapfrog_prod(c1.v[e], ppt.v[e], q ? prod2.y : prod2.x);
-                    u.v[e] = (LEAN || !edge || (rowupd && mupd[e])) ? upd : ppt.v[e];
-                }
-            });
         }
+        const ZPairs zp = zpairs(lft, c1, rgt);
+        auto row = [&](auto IO) -> const f4& { return ring[(U + decltype(IO)::value) % R]; };
+        v2f lapq[2];
+        // DD exact: the sibling's single-accumulator Laplacian, two cells per instruction; DD FAST: the weights carry their spacing
+        if constexpr (DD && NUM == 0) laplacian_dd_quad<H>(zp, row, cpk, ddinv, lapq[0], lapq[1]);
+        else lap_quad<NUM, H>(zp, row, cpk, c0p, lapq[0], lapq[1]);
+        // (the masks behind a per-workgroup branch, taken only where a tile touches the frame, measured 1.5 % slower: DESIGN.md section 3c)
+        static_for<2>([&](auto PP) {
+            constexpr int P = decltype(PP)::value;
+            v2f lap2 = lapq[P];
+            if constexpr (!LEAN) lap2 = v2f{(rowok && mlap[2 * P]) ? lap2.x : 0.0f, (rowok && mlap[2 * P + 1]) ? lap2.y : 0.0f};
+            const v2f prod2 = f4_pair(v2t, P) * lap2;          // v2t holds v2 dt2 (see above)
+#pragma unroll
+            for (int q = 0; q < 2; ++q) {
+                const int e = 2 * P + q;
+                const float upd = leapfrog_prod(c1.v[e], ppt.v[e], q ? prod2.y : prod2.x);
+                u.v[e] = (LEAN || (rowupd && mupd[e])) ? upd : ppt.v[e];
+            }
+        });
         if constexpr (INJ == 1) {
             if (inj_here && r == a.inj_x) {
 #pragma unroll
@@ -330,7 +263,7 @@ __device__ __forceinline__ void marchn(const Step2Args& a, const int lane, const
             else im = imf[r & 15][lane];
             if (r >= xa && r < xe) {
                 f4 lv;
-                if constexpr (BK == 4) lv = linkx[k][par ^ 1][0][SLOT][lane];      // F_{it+k}(r): the source-field wave of this level formed it one step ago
+                if constexpr (BK == 4) lv = linkx[k][par ^ 1][0][lane];      // F_{it+k}(r): the source-field wave of this level formed it one step ago
                 else lv = qlv[Q];
 #pragma unroll
                 for (int e = 0; e < 4; ++e) im.v[e] = zim[e] ? im.v[e] + lv.v[e] * u.v[e] : im.v[e];
@@ -351,18 +284,13 @@ __device__ __forceinline__ void marchn(const Step2Args& a, const int lane, const
             }
         }
         // ---- hand over to the next wave: the new row (raw) and the row leaving this window (damped once) ----
-#if !(FDW_ABL_BITS & 128)
-        link[k][par][0][SLOT][lane] = u;
-        link[k][par][1][SLOT][lane] = ring[U];
-#endif
+        link[k][par][0][lane] = u;
+        link[k][par][1][lane] = ring[U];
         } else {
 #pragma unroll
             for (int e = 0; e < 4; ++e) asm volatile("" : "=v"(u.v[e]));      // defined (no instruction) on the path that skips the row
         }
         const unsigned so = (act && (r >= xa) && (r < xe) && (m < M)) ? soff : kLaneOff;
-#if FDW_ABL_BITS & 1024
-        ring[U] = u;
-#else
         f4_store_arr(rs_out, so, rowoff(r), u);
         if constexpr (IMG) {
             const unsigned sim = (k == NS - 1 && act && (r >= xa) && (r < xe)) ? ioff : kLaneOff;
@@ -374,12 +302,9 @@ __device__ __forceinline__ void marchn(const Step2Args& a, const int lane, const
         if constexpr (WK != 2) ring[U] = load_p(b0 + m + R);
         qpp[Q] = load_pw(rs_pp, s0 + m + PF);
         if constexpr (BK != 4) qv2[Q] = load_pw(rs_v2, s0 + m + PF);
-        if constexpr (BK == 2) qlv[Q] = f4_load_arr(rs_lev, ioff, rowoff(r + PF), (FDW_NT & 1) != 0);
-        if constexpr (IMG) qim[Q] = f4_load_arr(rs_img, imoff, rowoff(r + PF), (FDW_NT & 1) != 0);
-#endif
-#if !(FDW_ABL_BITS & 64)
-        if constexpr (SLOT == ROWS - 1) __syncthreads();
-#endif
+        if constexpr (BK == 2) qlv[Q] = f4_load_arr(rs_lev, ioff, rowoff(r + PF), true);
+        if constexpr (IMG) qim[Q] = f4_load_arr(rs_img, imoff, rowoff(r + PF), true);
+        __syncthreads();
     };
 
     for (int mb = 0; mb < M; mb += R)
@@ -392,7 +317,7 @@ __device__ __forceinline__ void marchn(const Step2Args& a, const int lane, const
 template <int H, int NS, bool TAPER, int INJ, bool DD = false>
 __device__ __forceinline__ bool pipe_lean(const Step2Args& a, int cs, int xa, int xe)
 {
-    const int lo = xa - (NS - 1) * H - H - NS * (H + FDW_PIPE_ROWS), hi = xe + (NS - 1) * (2 * H + FDW_PIPE_ROWS) + 2 * H + 16;
+    const int lo = xa - (NS - 1) * H - H - NS * (H + 1), hi = xe + (NS - 1) * (2 * H + 1) + 2 * H + 16;
     const int c0 = cs * 4, c1 = cs * 4 + 256;
     bool ok = (c0 >= a.lap_z0) && (c1 <= min(a.lap_z1, a.upd_z1)) && (lo >= max(a.lap_x0, 0)) && (hi <= min(min(a.lap_x1, a.upd_x1), a.nxl));
     if (TAPER) {
@@ -406,8 +331,13 @@ __device__ __forceinline__ bool pipe_lean(const Step2Args& a, int cs, int xa, in
     return ok;
 }
 
+// workgroups per CU the launch bounds hold the kernels to: 5 x 4 waves = 96 VGPRs (forward, source field); 4 for the modelling dialect;
+// 3 for the receiver field (BK 2)
+constexpr int kPipeWG = 5;
+constexpr int kDDWG = 4;
+
 template <int H, int NS, bool TAPER, int INJ, int PF, bool DD = false, int BK = 0, int NUM = 0>
-__global__ __launch_bounds__(64 * NS, (FDW_PIPE_ROWS != 1 || BK == 2) ? 3 : (DD ? FDW_DD_WG : FDW_PIPE_WG)) void fdw_stepn_kernel(const Step2Args a)
+__global__ __launch_bounds__(64 * NS, BK == 2 ? 3 : (DD ? kDDWG : kPipeWG)) void fdw_stepn_kernel(const Step2Args a)
 {
     const int lane = threadIdx.x & 63;
     const int k = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -420,26 +350,26 @@ __global__ __launch_bounds__(64 * NS, (FDW_PIPE_ROWS != 1 || BK == 2) ? 3 : (DD 
     const int xa = second ? a.r0b + (xb - a.chunks_a) * a.xchunk : a.r0 + xb * a.xchunk;
     const int xe = min(xa + a.xchunk, second ? a.r1b : a.r1);
     if (xa >= xe) return;
-    __shared__ f4 link[NS][2][2][FDW_PIPE_ROWS][64];       // [producer wave][parity][0 new row | 1 row leaving the window][row of the interval][lane]
-    __shared__ f4 fifo[pipe_fifo_rows(NS, H, FDW_PIPE_ROWS)][64];
+    __shared__ f4 link[NS][2][2][64];                      // [producer wave][parity][0 new row | 1 row leaving the window][lane]
+    __shared__ f4 fifo[pipe_fifo_rows(NS, H)][64];
     if constexpr (BK == 2) {
-        static_assert(FDW_PIPE_ROWS == 1, "the image FIFO assumes one row per barrier");
         __shared__ f4 imf[16][64];                         // image rows on their way from wave to wave (a row is 3 (H + 1) = 15 steps under way)
-        marchn<H, NS, TAPER, INJ, PF, DD, BK, FDW_PIPE_ROWS, false, 0, NUM>(a, lane, k, zb * (64 - 2 * NS) - NS, xa, xe, link, fifo, imf);
-    } else if constexpr (BK == 0 && (FDW_PIPE_OPT & 32)) {
-        // nine workgroups in ten of a large grid touch neither the frame, nor the damped strip, nor the source: they take the lean body
+        marchn<H, NS, TAPER, INJ, PF, DD, BK, false, 0, NUM>(a, lane, k, zb * (64 - 2 * NS) - NS, xa, xe, link, fifo, imf);
+    } else if constexpr (BK == 0) {
+        // nine workgroups in ten of a large grid touch neither the frame, nor the damped strip, nor the source: they take the lean body,
+        // compiled once for wave 0 and once for the other waves (the modelling dialect: one body for all four)
         const int cs = zb * (64 - 2 * NS) - NS;
         if (pipe_lean<H, NS, TAPER, INJ, DD>(a, cs, xa, xe)) {
-            if constexpr ((FDW_PIPE_OPT & 128) != 0 && !DD) {
-                if (k == 0) marchn<H, NS, false, 0, PF, DD, 0, FDW_PIPE_ROWS, true, 1, NUM>(a, lane, k, cs, xa, xe, link, fifo);
-                else marchn<H, NS, false, 0, PF, DD, 0, FDW_PIPE_ROWS, true, 2, NUM>(a, lane, k, cs, xa, xe, link, fifo);
+            if constexpr (!DD) {
+                if (k == 0) marchn<H, NS, false, 0, PF, DD, 0, true, 1, NUM>(a, lane, k, cs, xa, xe, link, fifo);
+                else marchn<H, NS, false, 0, PF, DD, 0, true, 2, NUM>(a, lane, k, cs, xa, xe, link, fifo);
             } else {
-                marchn<H, NS, false, 0, PF, DD, 0, FDW_PIPE_ROWS, true, 0, NUM>(a, lane, k, cs, xa, xe, link, fifo);
+                marchn<H, NS, false, 0, PF, DD, 0, true, 0, NUM>(a, lane, k, cs, xa, xe, link, fifo);
             }
         }
-        else marchn<H, NS, TAPER, INJ, PF, DD, BK, FDW_PIPE_ROWS, false, 0, NUM>(a, lane, k, cs, xa, xe, link, fifo);
+        else marchn<H, NS, TAPER, INJ, PF, DD, BK, false, 0, NUM>(a, lane, k, cs, xa, xe, link, fifo);
     } else {
-        marchn<H, NS, TAPER, INJ, PF, DD, BK, FDW_PIPE_ROWS, false, 0, NUM>(a, lane, k, zb * (64 - 2 * NS) - NS, xa, xe, link, fifo);
+        marchn<H, NS, TAPER, INJ, PF, DD, BK, false, 0, NUM>(a, lane, k, zb * (64 - 2 * NS) - NS, xa, xe, link, fifo);
     }
 }
 
@@ -461,38 +391,31 @@ __global__ __launch_bounds__(128 * NS, 2) void fdw_back4_kernel(const Step2Args 
     const int xa = second ? a.r0b + (xb - a.chunks_a) * a.xchunk : a.r0 + xb * a.xchunk;
     const int xe = min(xa + a.xchunk, second ? a.r1b : a.r1);
     if (xa >= xe) return;
-    static_assert(FDW_PIPE_ROWS == 1, "one row per barrier");
-    __shared__ f4 linkF[NS][2][2][1][64];
-    __shared__ f4 linkR[NS][2][2][1][64];
+    __shared__ f4 linkF[NS][2][2][64];
+    __shared__ f4 linkR[NS][2][2][64];
     __shared__ f4 fifo[kFusedFifoRows][64];
     __shared__ f4 imf[16][64];
     const int cs = zb * (64 - 2 * NS) - NS;
-    constexpr bool kLean = (FDW_PIPE_OPT & 32) != 0, kSplit = (FDW_PIPE_OPT & 256) != 0, kSplitR = (FDW_PIPE_OPT & 512) != 0;
+    // each role runs the lean body (compiled once for its wave 0 and once for its other waves) where its tile allows
     if (k8 < NS) {
-        if (kLean && pipe_lean<H, NS, false, 0>(a, cs, xa, xe)) {
-            if constexpr (kSplit) {
-                if (k8 == 0) marchn<H, NS, false, 0, PF, false, 3, 1, true, 1, NUM>(a, lane, k8, cs, xa, xe, linkF, fifo);
-                else marchn<H, NS, false, 0, PF, false, 3, 1, true, 2, NUM>(a, lane, k8, cs, xa, xe, linkF, fifo);
-            } else {
-                marchn<H, NS, false, 0, PF, false, 3, 1, true, 0, NUM>(a, lane, k8, cs, xa, xe, linkF, fifo);
-            }
+        if (pipe_lean<H, NS, false, 0>(a, cs, xa, xe)) {
+            if (k8 == 0) marchn<H, NS, false, 0, PF, false, 3, true, 1, NUM>(a, lane, k8, cs, xa, xe, linkF, fifo);
+            else marchn<H, NS, false, 0, PF, false, 3, true, 2, NUM>(a, lane, k8, cs, xa, xe, linkF, fifo);
         } else {
-            marchn<H, NS, false, 0, PF, false, 3, 1, false, 0, NUM>(a, lane, k8, cs, xa, xe, linkF, fifo);
+            marchn<H, NS, false, 0, PF, false, 3, false, 0, NUM>(a, lane, k8, cs, xa, xe, linkF, fifo);
         }
     } else {
         // receiver role: lean where the tile holds neither the damped strip nor the receiver line
-        if (kLean && pipe_lean<H, NS, true, 2>(a, cs, xa, xe)) {
-            if constexpr (kSplitR) {
-                if (k8 == NS) marchn<H, NS, false, 0, PF, false, 4, 1, true, 1, NUM>(a, lane, 0, cs, xa, xe, linkR, fifo, imf, linkF);
-                else marchn<H, NS, false, 0, PF, false, 4, 1, true, 2, NUM>(a, lane, k8 - NS, cs, xa, xe, linkR, fifo, imf, linkF);
-            } else {
-                marchn<H, NS, false, 0, PF, false, 4, 1, true, 0, NUM>(a, lane, k8 - NS, cs, xa, xe, linkR, fifo, imf, linkF);
-            }
+        if (pipe_lean<H, NS, true, 2>(a, cs, xa, xe)) {
+            if (k8 == NS) marchn<H, NS, false, 0, PF, false, 4, true, 1, NUM>(a, lane, 0, cs, xa, xe, linkR, fifo, imf, linkF);
+            else marchn<H, NS, false, 0, PF, false, 4, true, 2, NUM>(a, lane, k8 - NS, cs, xa, xe, linkR, fifo, imf, linkF);
         } else {
-            marchn<H, NS, true, 2, PF, false, 4, 1, false, 0, NUM>(a, lane, k8 - NS, cs, xa, xe, linkR, fifo, imf, linkF);
+            marchn<H, NS, true, 2, PF, false, 4, false, 0, NUM>(a, lane, k8 - NS, cs, xa, xe, linkR, fifo, imf, linkF);
         }
     }
 }
+
+constexpr int kPipePF = 2;      // rows of global look-ahead of wave 0
 
 hipError_t launch_stepn(const Step2Args& a, int h, int mode, hipStream_t s)
 {
@@ -501,23 +424,23 @@ hipError_t launch_stepn(const Step2Args& a, int h, int mode, hipStream_t s)
     const dim3 grid(8 * a.nper), block(64 * kPipeSteps);
     if (a.numerics) {      // FAST numerics (fdw_device.h): the same kernels with NUM = 1
         switch (mode) {
-        case FDW_MODE_FWD:   hipLaunchKernelGGL((fdw_stepn_kernel<4, kPipeSteps, true, 1, FDW_PIPE_PF, false, 0, 1>), grid, block, 0, s, a); break;
-        case FDW_MODE_PLAIN: hipLaunchKernelGGL((fdw_stepn_kernel<4, kPipeSteps, false, 0, FDW_PIPE_PF, false, 0, 1>), grid, block, 0, s, a); break;
-        case FDW_MODE_MOD:   hipLaunchKernelGGL((fdw_stepn_kernel<4, kPipeSteps, true, 3, FDW_PIPE_PF, true, 0, 1>), grid, block, 0, s, a); break;
-        case FDW_MODE_PLAIN_ALL: hipLaunchKernelGGL((fdw_stepn_kernel<4, kPipeSteps, false, 0, FDW_PIPE_PF, false, 1, 1>), grid, block, 0, s, a); break;
-        case FDW_MODE_RECV:  hipLaunchKernelGGL((fdw_stepn_kernel<4, kPipeSteps, true, 2, FDW_PIPE_PF, false, 2, 1>), grid, block, 0, s, a); break;
-        case FDW_MODE_BACK4: hipLaunchKernelGGL((fdw_back4_kernel<4, kPipeSteps, FDW_PIPE_PF, 1>), grid, dim3(128 * kPipeSteps), 0, s, a); break;
+        case FDW_MODE_FWD:   hipLaunchKernelGGL((fdw_stepn_kernel<4, kPipeSteps, true, 1, kPipePF, false, 0, 1>), grid, block, 0, s, a); break;
+        case FDW_MODE_PLAIN: hipLaunchKernelGGL((fdw_stepn_kernel<4, kPipeSteps, false, 0, kPipePF, false, 0, 1>), grid, block, 0, s, a); break;
+        case FDW_MODE_MOD:   hipLaunchKernelGGL((fdw_stepn_kernel<4, kPipeSteps, true, 3, kPipePF, true, 0, 1>), grid, block, 0, s, a); break;
+        case FDW_MODE_PLAIN_ALL: hipLaunchKernelGGL((fdw_stepn_kernel<4, kPipeSteps, false, 0, kPipePF, false, 1, 1>), grid, block, 0, s, a); break;
+        case FDW_MODE_RECV:  hipLaunchKernelGGL((fdw_stepn_kernel<4, kPipeSteps, true, 2, kPipePF, false, 2, 1>), grid, block, 0, s, a); break;
+        case FDW_MODE_BACK4: hipLaunchKernelGGL((fdw_back4_kernel<4, kPipeSteps, kPipePF, 1>), grid, dim3(128 * kPipeSteps), 0, s, a); break;
         default: return hipErrorInvalidValue;
         }
         return hipGetLastError();
     }
     switch (mode) {
-    case FDW_MODE_FWD:   hipLaunchKernelGGL((fdw_stepn_kernel<4, kPipeSteps, true, 1, FDW_PIPE_PF>), grid, block, 0, s, a); break;
-    case FDW_MODE_PLAIN: hipLaunchKernelGGL((fdw_stepn_kernel<4, kPipeSteps, false, 0, FDW_PIPE_PF>), grid, block, 0, s, a); break;
-    case FDW_MODE_MOD:   hipLaunchKernelGGL((fdw_stepn_kernel<4, kPipeSteps, true, 3, FDW_PIPE_PF, true>), grid, block, 0, s, a); break;
-    case FDW_MODE_PLAIN_ALL: hipLaunchKernelGGL((fdw_stepn_kernel<4, kPipeSteps, false, 0, FDW_PIPE_PF, false, 1>), grid, block, 0, s, a); break;
-    case FDW_MODE_RECV:  hipLaunchKernelGGL((fdw_stepn_kernel<4, kPipeSteps, true, 2, FDW_PIPE_PF, false, 2>), grid, block, 0, s, a); break;
-    case FDW_MODE_BACK4: hipLaunchKernelGGL((fdw_back4_kernel<4, kPipeSteps, FDW_PIPE_PF>), grid, dim3(128 * kPipeSteps), 0, s, a); break;
+    case FDW_MODE_FWD:   hipLaunchKernelGGL((fdw_stepn_kernel<4, kPipeSteps, true, 1, kPipePF>), grid, block, 0, s, a); break;
+    case FDW_MODE_PLAIN: hipLaunchKernelGGL((fdw_stepn_kernel<4, kPipeSteps, false, 0, kPipePF>), grid, block, 0, s, a); break;
+    case FDW_MODE_MOD:   hipLaunchKernelGGL((fdw_stepn_kernel<4, kPipeSteps, true, 3, kPipePF, true>), grid, block, 0, s, a); break;
+    case FDW_MODE_PLAIN_ALL: hipLaunchKernelGGL((fdw_stepn_kernel<4, kPipeSteps, false, 0, kPipePF, false, 1>), grid, block, 0, s, a); break;
+    case FDW_MODE_RECV:  hipLaunchKernelGGL((fdw_stepn_kernel<4, kPipeSteps, true, 2, kPipePF, false, 2>), grid, block, 0, s, a); break;
+    case FDW_MODE_BACK4: hipLaunchKernelGGL((fdw_back4_kernel<4, kPipeSteps, kPipePF>), grid, dim3(128 * kPipeSteps), 0, s, a); break;
     default: return hipErrorInvalidValue;
     }
     return hipGetLastError();
