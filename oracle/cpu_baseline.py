@@ -59,7 +59,7 @@ def rtm_main():
     out = {"value": round(g1, 4), "unit": "Gpoints/s", "cores": 1, "kind": "port",
            "sample": f"one RTM shot on a {m}x{m} fp32 grid cut to {s1} forward + {s1} backward iterations with imaging (oracle/fdw_oracle.c orc_fd_forward + "
                      f"orc_fd_back: one pass per reference kernel, gcc -O2 -ffp-contract=off), single thread, {t1:.1f} s"}
-    if os.path.exists(os.path.join(os.path.dirname(os.path.abspath(__file__)), "liborc_omp.so")) and host_threads() > 1:
+    if os.path.exists(os.path.join(os.path.dirname(os.path.abspath(__file__)), O.SO_OMP)) and host_threads() > 1:
         gm, sm, tm = leg(True, 2000)
         out = {"value": round(gm, 4), "unit": "Gpoints/s", "cores": host_threads(), "kind": "port",
                "sample": f"one RTM shot on a {m}x{m} fp32 grid cut to {sm} forward + {sm} backward iterations with imaging (oracle/fdw_oracle.c orc_fd_forward + "
@@ -102,7 +102,7 @@ def main():
     g1, s1, t1 = leg(L, 40)
     out = {"value": round(g1, 4), "unit": "Gpoints/s", "cores": 1, "kind": "port",
            "sample": f"{n}x{n} fp32 grid, {s1} fused steps (oracle/fdw_oracle.c orc_fused_steps, gcc -O2 -ffp-contract=off), single thread, {t1:.1f} s"}
-    omp = os.path.join(os.path.dirname(os.path.abspath(__file__)), "liborc_omp.so")
+    omp = os.path.join(os.path.dirname(os.path.abspath(__file__)), O.SO_OMP)
     if os.path.exists(omp):
         M = C.CDLL(omp)
         M.orc_fused_steps.argtypes = L.orc_fused_steps.argtypes

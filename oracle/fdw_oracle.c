@@ -23,15 +23,18 @@
  * Build: gcc -O2 -ffp-contract=off (no FMA contraction: the reference is built with
  * --fmad=false, S Makefile:4) -- see oracle/Makefile.
  *
- * FAST numerics (orc_set_numerics(s, 1)): NOT the reference's arithmetic but the product's documented tolerance mode (include/fdwave.h
- * fdw_params.numerics, csrc/fdw_device.h): the Laplacian as ONE chain of symmetric sums and fused multiply-adds, everything else as
- * above.  Restated here (orc_lap_fast, explicit fmaf calls) so that the FAST kernels are checked bit for bit against a CPU statement of
- * their own formula -- masks, extents, taper and injection included -- and not only to a tolerance against the exact arithmetic.
+ * FAST numerics (numerics = 1, an argument of orc_init and orc_stencil): NOT the reference's arithmetic but the product's documented
+ * tolerance mode (include/fdwave.h fdw_params.numerics, csrc/fdw_device.h): the Laplacian as ONE chain of symmetric sums and fused
+ * multiply-adds, everything else as above.  Restated here (orc_lap_fast in fdw_oracle.h, explicit fmaf calls) so that the FAST kernels
+ * are checked bit for bit against a CPU statement of their own formula -- masks, extents, taper and injection included -- and not only
+ * to a tolerance against the exact arithmetic.  Every Laplacian of this file goes through orc_lap_exact or orc_lap_fast.
  */
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+
+#include "fdw_oracle.h"
 
 #define ORC_PI (3.141592653589793) /* F header: functions.h:7 */
 #define ORC_BLOCK_RTM 8            /* functions.h:6 sizeblock */
@@ -207,65 +210,44 @@ void orc_extents(int nxe, int nze, int nzb, int compat, int *xlim, int *zlim, in
 
 /* ------------------------------------------------------------------ kernels (one pass each) */
 
+/* R:53-78 == S:110-135: one sum per axis over the taps in order, z and x added last.  p points at the centre, sx = floats between rows. */
+static inline float orc_lap_exact(const float *p, size_t sx, int order, const float *coefsx, const float *coefsz)
+{
+    float acmx = 0, acmz = 0;
+    int io;
+    for (io = 0; io <= order; io++) {
+        long aux = io - order / 2;
+        acmz += p[aux] * coefsz[io];
+        acmx += p[aux * (long)sx] * coefsx[io];
+    }
+    return acmz + acmx;
+}
+
+/* lap[j] = the Laplacian at p[j] for j in [j0, j1) of one row (p, lap point at the row's first element); numerics 1 = FAST */
+static void orc_lap_row(int numerics, int order, const float *p, size_t sx, int j0, int j1, const float *coefsx, const float *coefsz,
+                        float *lap)
+{
+    int j;
+    if (numerics)
+        for (j = j0; j < j1; j++) lap[j] = orc_lap_fast(p + j, sx, order / 2, coefsx, coefsz);
+    else
+        for (j = j0; j < j1; j++) lap[j] = orc_lap_exact(p + j, sx, order, coefsx, coefsz);
+}
+
 /* R:53-78 == S:110-135.  gx,gz = number of threads launched per axis (grid*block). */
 void orc_kernel_lap(int order, int nx, int nz, int gx, int gz, const float *p, float *lap,
-                    const float *coefsx, const float *coefsz)
+                    const float *coefsx, const float *coefsz, int numerics)
 {
     /* thread (ti, tj) works on i = h + ti, j = h + tj and returns unless i < nx - h, j < nz - h (R:56-64) */
-    int half_order = order / 2, ti, tj, io;
+    int half_order = order / 2, ti;
     int nti = gx < nx - 2 * half_order ? gx : nx - 2 * half_order;
     int ntj = gz < nz - 2 * half_order ? gz : nz - 2 * half_order;
 #ifdef _OPENMP
-#pragma omp parallel for private(tj, io) schedule(static)   /* rows are independent; per-point arithmetic unchanged */
+#pragma omp parallel for schedule(static)   /* rows are independent; per-point arithmetic unchanged */
 #endif
     for (ti = 0; ti < nti; ti++) {
-        int i = half_order + ti;
-        for (tj = 0; tj < ntj; tj++) {
-            int j = half_order + tj;
-            size_t mult = (size_t)i * nz;
-            float acmx = 0, acmz = 0;
-            for (io = 0; io <= order; io++) {
-                int aux = io - half_order;
-                acmz += p[mult + j + aux] * coefsz[io];
-                acmx += p[(size_t)(i + aux) * nz + j] * coefsx[io];
-            }
-            lap[mult + j] = acmz + acmx;
-        }
-    }
-}
-
-/* FAST numerics (see the header): lap = c0 p + sum_k [cz_k (p(j-k) + p(j+k)) + cx_k (p(i-k) + p(i+k))], c0 = cz_0 + cx_0 in fp32, one chain:
- * acc = c0 * p; per k = 1..h: acc = fma(z sum, cz_k, acc); acc = fma(x sum, cx_k, acc).  p points at the centre, sx = floats between rows. */
-static float orc_lap_fast(const float *p, size_t sx, int h, const float *coefsx, const float *coefsz)
-{
-    float c0 = coefsz[h] + coefsx[h];
-    float acc = c0 * p[0];
-    int k;
-    for (k = 1; k <= h; k++) {
-        float sz = p[-k] + p[k];
-        float sxs = p[-(long)(k * sx)] + p[k * sx];
-        acc = fmaf(sz, coefsz[h - k], acc);
-        acc = fmaf(sxs, coefsx[h - k], acc);
-    }
-    return acc;
-}
-
-/* kernel_lap's extents with the FAST Laplacian */
-void orc_kernel_lap_fast(int order, int nx, int nz, int gx, int gz, const float *p, float *lap,
-                         const float *coefsx, const float *coefsz)
-{
-    int half_order = order / 2, ti, tj;
-    int nti = gx < nx - 2 * half_order ? gx : nx - 2 * half_order;
-    int ntj = gz < nz - 2 * half_order ? gz : nz - 2 * half_order;
-#ifdef _OPENMP
-#pragma omp parallel for private(tj) schedule(static)
-#endif
-    for (ti = 0; ti < nti; ti++) {
-        int i = half_order + ti;
-        for (tj = 0; tj < ntj; tj++) {
-            int j = half_order + tj;
-            lap[(size_t)i * nz + j] = orc_lap_fast(p + (size_t)i * nz + j, (size_t)nz, half_order, coefsx, coefsz);
-        }
+        size_t row = (size_t)(half_order + ti) * nz;
+        orc_lap_row(numerics, order, p + row, (size_t)nz, half_order, half_order + ntj, coefsx, coefsz, lap + row);
     }
 }
 
@@ -347,19 +329,18 @@ typedef struct {
     int numerics;     /* 0: the reference's arithmetic; 1: FAST (orc_lap_fast) */
 } orc_state;
 
-void orc_set_numerics(orc_state *s, int numerics) { s->numerics = numerics; }
 static void orc_lap_pass(const orc_state *s, const float *p, float *lap)
 {
-    if (s->numerics) orc_kernel_lap_fast(s->order, s->nxe, s->nze, s->xlim, s->zlim, p, lap, s->coefs_x, s->coefs_z);
-    else orc_kernel_lap(s->order, s->nxe, s->nze, s->xlim, s->zlim, p, lap, s->coefs_x, s->coefs_z);
+    orc_kernel_lap(s->order, s->nxe, s->nze, s->xlim, s->zlim, p, lap, s->coefs_x, s->coefs_z, s->numerics);
 }
 
 orc_state *orc_init(int order, int nxe, int nze, int nxb, int nzb, int nt, float fac, float dx,
-                    float dz, float dt, int compat)
+                    float dz, float dt, int compat, int numerics)
 {
     orc_state *s = (orc_state *)calloc(1, sizeof(orc_state));
     if (order < 2 || order > 64 || (order & 1)) { free(s); return NULL; }
     s->order = order; s->nxe = nxe; s->nze = nze; s->nxb = nxb; s->nzb = nzb; s->nt = nt;
+    s->numerics = numerics;
     s->dt2 = dt * dt; /* R:205 */
     orc_scaled_coefs(order, dx, dz, 0, s->coefs_x, s->coefs_z);
     s->taper_x = (float *)calloc(nxb > 0 ? nxb : 1, sizeof(float));
@@ -436,42 +417,27 @@ void orc_fd_back(orc_state *s, const float *v2, const float *snap0, const float 
 }
 
 /* S:241-262 + S:325: the stencil program's single launch.  Grid rounds up to 32 (S:231-238) so the
- * whole interior is covered; border cells of the output stay zero (S:153 memset + golden). */
-void orc_stencil(int order, int nxe, int nze, float dx, float dz, const float *in, float *out)
+ * whole interior is covered; border cells of the output stay zero (S:153 memset + golden).
+ * numerics 1: the same launch with the FAST Laplacian (fdw_dev_laplacian on a numerics = 1 context). */
+void orc_stencil(int order, int nxe, int nze, float dx, float dz, const float *in, float *out, int numerics)
 {
     float cx[65], cz[65];
     int gx = ((nxe - 1) / 32 + 1) * 32, gz = ((nze - 1) / 32 + 1) * 32;
     orc_scaled_coefs(order, dx, dz, 1, cx, cz);
     memset(out, 0, (size_t)nxe * nze * sizeof(float));
-    orc_kernel_lap(order, nxe, nze, gx, gz, in, out, cx, cz);
+    orc_kernel_lap(order, nxe, nze, gx, gz, in, out, cx, cz, numerics);
 }
 
-/* One forward iteration (R:260-267 without the pointer swap) on an x-slab of a decomposed grid: the
- * local arrays hold global rows [x_off, x_off+nxl); rows [r0,r1) (local) are updated, rows
- * [r0-h, r1+h) are damped in place first (they are exactly the rows this step reads).  The reference
- * has no decomposition; this is the per-slab restatement used by the CPU (gloo) tests of the halo
- * exchange logic -- with x_off=0, nxl=nxe, r0=t0=0, r1=t1=nxe it is orc_forward_step. */
-/* the same launch with the FAST Laplacian (fdw_dev_laplacian on a numerics = 1 context) */
-void orc_stencil_fast(int order, int nxe, int nze, float dx, float dz, const float *in, float *out)
-{
-    float cx[65], cz[65];
-    int gx = ((nxe - 1) / 32 + 1) * 32, gz = ((nze - 1) / 32 + 1) * 32;
-    orc_scaled_coefs(order, dx, dz, 1, cx, cz);
-    memset(out, 0, (size_t)nxe * nze * sizeof(float));
-    orc_kernel_lap_fast(order, nxe, nze, gx, gz, in, out, cx, cz);
-}
+/* ------------------------------------------------------------------ per-slab restatements (decomposed grids, tests only) */
 
-void orc_slab_step(const orc_state *s, int x_off, int nxl, float *p, float *pp, const float *v2, int r0, int r1,
-                   int t0, int t1, int sx_global, int sz, float srce_it)
+/* kernel_tapper with its thread extents, in global coordinates (pass 1 taperz, pass 2 taperx), on the local rows [t0,t1) of a slab
+ * whose first local row is global row x_off */
+static void orc_slab_taper(const orc_state *s, int x_off, int t0, int t1, float *p, float *pp)
 {
-    /* [t0,t1): rows damped in place by this call.  A caller that splits one time step into several
-     * row ranges damps every row it will read exactly once (first call), t0>=t1 on the others. */
-    const int h = s->order / 2, nze = s->nze, nxe = s->nxe;
-    int l, j, io;
-    float *lap = (float *)calloc((size_t)nxl * nze, sizeof(float));
-    /* kernel_tapper with its thread extents, in global coordinates (pass 1 taperz, pass 2 taperx) */
+    const int nze = s->nze;
+    int l, j;
     for (l = t0; l < t1; l++) {
-        int g = x_off + l, gm = nxe - 1 - g;
+        int g = x_off + l, gm = s->nxe - 1 - g;
         for (j = 0; j < s->ztap && j < s->nzb; j++) {
             size_t k = (size_t)l * nze + j;
             if (g < s->xlim) { p[k] *= s->taper_z[j]; pp[k] *= s->taper_z[j]; }
@@ -482,21 +448,19 @@ void orc_slab_step(const orc_state *s, int x_off, int nxl, float *p, float *pp, 
             else if (gm < s->nxb && gm < s->xlim) { p[k] *= s->taper_x[gm]; pp[k] *= s->taper_x[gm]; }
         }
     }
+}
+
+/* kernel_lap + kernel_time on the local rows [r0,r1) of a slab of nxl rows: pp = leap-frog(p, pp), each pass with its thread extents in
+ * global coordinates; the Laplacian also needs h rows of p on each side inside the slab */
+static void orc_slab_lap_time(const orc_state *s, int x_off, int nxl, const float *p, float *pp, const float *v2, int r0, int r1)
+{
+    const int h = s->order / 2, nze = s->nze, j1 = nze - h < h + s->zlim ? nze - h : h + s->zlim;
+    int l, j;
+    float *lap = (float *)calloc((size_t)nxl * nze, sizeof(float));
     for (l = r0; l < r1; l++) {
         int g = x_off + l;
-        if (g < h || g >= nxe - h || g >= h + s->xlim || l < h || l >= nxl - h) continue;
-        for (j = h; j < nze - h && j < h + s->zlim; j++) {
-            float acmx = 0, acmz = 0;
-            if (s->numerics) {
-                lap[(size_t)l * nze + j] = orc_lap_fast(p + (size_t)l * nze + j, (size_t)nze, h, s->coefs_x, s->coefs_z);
-                continue;
-            }
-            for (io = 0; io <= s->order; io++) {
-                acmz += p[(size_t)l * nze + j + io - h] * s->coefs_z[io];
-                acmx += p[(size_t)(l + io - h) * nze + j] * s->coefs_x[io];
-            }
-            lap[(size_t)l * nze + j] = acmz + acmx;
-        }
+        if (g < h || g >= s->nxe - h || g >= h + s->xlim || l < h || l >= nxl - h) continue;
+        orc_lap_row(s->numerics, s->order, p + (size_t)l * nze, (size_t)nze, h, j1, s->coefs_x, s->coefs_z, lap + (size_t)l * nze);
     }
     for (l = r0; l < r1; l++) {
         if (x_off + l >= s->xlim) continue;
@@ -505,9 +469,23 @@ void orc_slab_step(const orc_state *s, int x_off, int nxl, float *p, float *pp, 
             pp[k] = 2. * p[k] - pp[k] + v2[k] * s->dt2 * lap[k];
         }
     }
-    l = sx_global - x_off;
-    if (sx_global >= 0 && l >= r0 && l < r1) pp[(size_t)l * nze + sz] += srce_it;
     free(lap);
+}
+
+/* One forward iteration (R:260-267 without the pointer swap) on an x-slab of a decomposed grid: the
+ * local arrays hold global rows [x_off, x_off+nxl); rows [r0,r1) (local) are updated, rows
+ * [r0-h, r1+h) are damped in place first (they are exactly the rows this step reads).  The reference
+ * has no decomposition; this is the per-slab restatement used by the CPU (gloo) tests of the halo
+ * exchange logic -- with x_off=0, nxl=nxe, r0=t0=0, r1=t1=nxe it is orc_forward_step. */
+void orc_slab_step(const orc_state *s, int x_off, int nxl, float *p, float *pp, const float *v2, int r0, int r1,
+                   int t0, int t1, int sx_global, int sz, float srce_it)
+{
+    /* [t0,t1): rows damped in place by this call.  A caller that splits one time step into several
+     * row ranges damps every row it will read exactly once (first call), t0>=t1 on the others. */
+    int l = sx_global - x_off;
+    orc_slab_taper(s, x_off, t0, t1, p, pp);
+    orc_slab_lap_time(s, x_off, nxl, p, pp, v2, r0, r1);
+    if (sx_global >= 0 && l >= r0 && l < r1) pp[(size_t)l * s->nze + sz] += srce_it;
 }
 
 /* One iteration of fd_back's loop (R:302-339) on rows [r0,r1) of an x-slab, the per-slab restatement behind the CPU (gloo) tests of
@@ -521,50 +499,12 @@ void orc_slab_step(const orc_state *s, int x_off, int nxl, float *p, float *pp, 
 void orc_slab_back_iter(const orc_state *s, int x_off, int nxl, int step_source, float *f1, float *f0, float *pr, float *ppr,
                         const float *v2, int r0, int r1, int t0, int t1, const float *samples, int gz_, float *img)
 {
-    const int h = s->order / 2, nze = s->nze, nxe = s->nxe, nx = nxe - 2 * s->nxb, nz = nze - 2 * s->nzb;
-    int l, j, io, pass;
-    float *lap = (float *)calloc((size_t)nxl * nze, sizeof(float));
+    const int nze = s->nze, nx = s->nxe - 2 * s->nxb, nz = nze - 2 * s->nzb;
     const float *F = step_source ? f0 : f1;
-    for (l = t0; l < t1; l++) {
-        int g = x_off + l, gm = nxe - 1 - g;
-        for (j = 0; j < s->ztap && j < s->nzb; j++) {
-            size_t k = (size_t)l * nze + j;
-            if (g < s->xlim) { pr[k] *= s->taper_z[j]; ppr[k] *= s->taper_z[j]; }
-        }
-        for (j = 0; j < s->ztap && j < s->nzb; j++) {
-            size_t k = (size_t)l * nze + j;
-            if (g < s->nxb && g < s->xlim) { pr[k] *= s->taper_x[g]; ppr[k] *= s->taper_x[g]; }
-            else if (gm < s->nxb && gm < s->xlim) { pr[k] *= s->taper_x[gm]; ppr[k] *= s->taper_x[gm]; }
-        }
-    }
-    for (pass = step_source ? 0 : 1; pass < 2; pass++) {      /* pass 0: the source pair, pass 1: the receiver pair */
-        const float *p = pass == 0 ? f1 : pr;
-        float *pp = pass == 0 ? f0 : ppr;
-        memset(lap, 0, (size_t)nxl * nze * sizeof(float));
-        for (l = r0; l < r1; l++) {
-            int g = x_off + l;
-            if (g < h || g >= nxe - h || g >= h + s->xlim || l < h || l >= nxl - h) continue;
-            for (j = h; j < nze - h && j < h + s->zlim; j++) {
-                float acmx = 0, acmz = 0;
-                if (s->numerics) {
-                    lap[(size_t)l * nze + j] = orc_lap_fast(p + (size_t)l * nze + j, (size_t)nze, h, s->coefs_x, s->coefs_z);
-                    continue;
-                }
-                for (io = 0; io <= s->order; io++) {
-                    acmz += p[(size_t)l * nze + j + io - h] * s->coefs_z[io];
-                    acmx += p[(size_t)(l + io - h) * nze + j] * s->coefs_x[io];
-                }
-                lap[(size_t)l * nze + j] = acmz + acmx;
-            }
-        }
-        for (l = r0; l < r1; l++) {
-            if (x_off + l >= s->xlim) continue;
-            for (j = 0; j < s->zlim; j++) {
-                size_t k = (size_t)l * nze + j;
-                pp[k] = 2. * p[k] - pp[k] + v2[k] * s->dt2 * lap[k];
-            }
-        }
-    }
+    int l, j;
+    orc_slab_taper(s, x_off, t0, t1, pr, ppr);
+    if (step_source) orc_slab_lap_time(s, x_off, nxl, f1, f0, v2, r0, r1);
+    orc_slab_lap_time(s, x_off, nxl, pr, ppr, v2, r0, r1);
     for (l = r0; l < r1; l++) {
         int i = x_off + l - s->nxb;                            /* interior row index of kernel_sism / kernel_img */
         if (i < 0 || i >= nx || i >= s->xlim) continue;
@@ -574,7 +514,6 @@ void orc_slab_back_iter(const orc_state *s, int x_off, int nxl, int step_source,
             img[k] += F[k] * ppr[k];
         }
     }
-    free(lap);
 }
 
 int orc_max_threads(void);
@@ -584,27 +523,19 @@ int orc_max_threads(void);
 void orc_fused_steps(int order, int nxe, int nze, float *p, float *pp, const float *v2,
                      const float *cx, const float *cz, float dt2, int nsteps)
 {
-    int h = order / 2, it, i, j, io;
+    int h = order / 2, it, i, j;
     for (it = 0; it < nsteps; it++) {
         float *t;
-        /* rows are independent within a step: the OpenMP build (liborc_native.so, oracle/Makefile) shares them out; the arithmetic
+        /* rows are independent within a step: the OpenMP build (liborc_v2_omp.so, oracle/Makefile) shares them out; the arithmetic
          * per point is unchanged, so the threaded result equals the serial one bit for bit */
 #ifdef _OPENMP
-#pragma omp parallel for private(j, io) schedule(dynamic, 8)
+#pragma omp parallel for private(j) schedule(dynamic, 8)
 #endif
         for (i = 0; i < nxe; i++)
             for (j = 0; j < nze; j++) {
                 size_t k = (size_t)i * nze + j;
                 float lap = 0.0f;
-                if (i >= h && i < nxe - h && j >= h && j < nze - h) {
-                    float acmx = 0, acmz = 0;
-                    for (io = 0; io <= order; io++) {
-                        long a = io - h;
-                        acmz += p[(long)k + a] * cz[io];
-                        acmx += p[(long)k + a * nze] * cx[io];
-                    }
-                    lap = acmz + acmx;
-                }
+                if (i >= h && i < nxe - h && j >= h && j < nze - h) lap = orc_lap_exact(p + k, (size_t)nze, order, cx, cz);
                 pp[k] = 2. * p[k] - pp[k] + v2[k] * dt2 * lap;
             }
         t = p; p = pp; pp = t;

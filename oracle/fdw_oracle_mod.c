@@ -20,11 +20,12 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include "fdw_oracle.h"
+
 #define MOD_PI (3.141592653589793) /* cwp.h PI */
 
-/* FD:54-92 calc_coefs: table orders 2..8 are the same rationals as the CUDA path's; other orders (makeo2 as C++:
- * cos(float) and pow(float,float) are the float overloads) are not needed by any deck and are left to orc_calc_coefs(cxx=1). */
-void orc_calc_coefs(int order, int cxx, float *coef);
+/* FD:54-92 calc_coefs is orc_calc_coefs(cxx=1): table orders 2..8 are the same rationals as the CUDA path's; other orders (makeo2 as C++:
+ * cos(float) and pow(float,float) are the float overloads) are not needed by any deck. */
 
 /* T:26-44: taper[i] = exp(-pow(F*(nb-i), 2)); F*(nb-i) is a float product, pow(float,int) promotes to double in C++11 */
 void orc_mod_taper_tables(int nxb, int nzb, float F, float *taperx, float *taperz)
@@ -92,37 +93,24 @@ void orc_mod_taper_apply(float *pp, int nx, int nz, int nxb, int nzb, const floa
     }
 }
 
-/* FAST numerics of the product for these dialects (include/fdwave.h fdw_params.numerics = 1; NOT the sibling's arithmetic, see the header of
- * fdw_oracle.c): the weights carry their spacing (czf_k = c_k * dz2inv, cxf_k = c_k * dx2inv, c0 = czf_0 + cxf_0, all fp32) and the Laplacian is
- * one chain of symmetric sums and fused multiply-adds, exactly the RTM dialect's FAST formula.  orc_mod_set_numerics(1) switches every loop
- * of this file to it. */
-static int orc_mod_numerics = 0;
-void orc_mod_set_numerics(int numerics) { orc_mod_numerics = numerics; }
-
 /* FD:24-46 fd_step: ONE accumulator, z term then x term per tap, weights scaled per term; Laplacian only inside the
- * order/2 frame (zero elsewhere, FD:19); update on the whole grid */
+ * order/2 frame (zero elsewhere, FD:19); update on the whole grid.
+ * numerics 1: the product's FAST numerics for these dialects (include/fdwave.h fdw_params.numerics = 1; NOT the sibling's arithmetic, see
+ * the header of fdw_oracle.c): the weights carry their spacing (czf_k = c_k * dz2inv, cxf_k = c_k * dx2inv, all fp32) and the Laplacian is
+ * the RTM dialect's FAST formula, orc_lap_fast. */
 void orc_mod_fd_step(int order, const float *coefs, float dx2inv, float dz2inv, float dt2, const float *p, float *pp, const float *v2,
-                     float *laplace, int nze, int nxe)
+                     float *laplace, int nze, int nxe, int numerics)
 {
     const int h = order / 2;
     float acm = 0;
-    if (orc_mod_numerics) {
+    if (numerics) {
         float czf[65], cxf[65];
         for (int io = 0; io <= order; io++) {
             czf[io] = coefs[io] * dz2inv;
             cxf[io] = coefs[io] * dx2inv;
         }
-        const float c0 = czf[h] + cxf[h];
         for (int ix = h; ix < nxe - h; ix++)
-            for (int iz = h; iz < nze - h; iz++) {
-                const float *q = p + (size_t)ix * nze + iz;
-                float acc = c0 * q[0];
-                for (int k = 1; k <= h; k++) {
-                    acc = fmaf(q[-k] + q[k], czf[h - k], acc);
-                    acc = fmaf(q[-(long)k * nze] + q[(long)k * nze], cxf[h - k], acc);
-                }
-                laplace[ix * nze + iz] = acc;
-            }
+            for (int iz = h; iz < nze - h; iz++) laplace[ix * nze + iz] = orc_lap_fast(p + (size_t)ix * nze + iz, (size_t)nze, h, cxf, czf);
     } else
     for (int ix = h; ix < nxe - h; ix++)
         for (int iz = h; iz < nze - h; iz++) {
@@ -158,7 +146,7 @@ void orc_mod_ptsrc(int xs, int zs, int nx, int nz, float ts, float *s)
 
 /* M:140-174: one shot of the modelling loop.  v2 is the extended squared velocity, data is [nx][nt]. */
 void orc_mod_shot(int order, int nx, int nz, int nxb, int nzb, int nt, float dx, float dz, float dt, float fac, const float *v2, int sx, int sz,
-                  int gz, const float *srce, float *data)
+                  int gz, const float *srce, float *data, int numerics)
 {
     const int nxe = nx + 2 * nxb, nze = nz + 2 * nzb;
     const size_t ne = (size_t)nxe * nze;
@@ -169,7 +157,7 @@ void orc_mod_shot(int order, int nx, int nz, int nxb, int nzb, int nt, float dx,
     orc_mod_taper_tables(nxb, nzb, fac, taperx, taperz);
     float *P = (float *)calloc(ne, sizeof(float)), *PP = (float *)calloc(ne, sizeof(float)), *lap = (float *)calloc(ne, sizeof(float));
     for (int it = 0; it < nt; it++) {
-        orc_mod_fd_step(order, coefs, dx2inv, dz2inv, dt2, P, PP, v2, lap, nze, nxe);
+        orc_mod_fd_step(order, coefs, dx2inv, dz2inv, dt2, P, PP, v2, lap, nze, nxe, numerics);
         orc_mod_ptsrc(sx, sz, nxe, nze, srce[it], PP);
         orc_mod_taper_apply(PP, nx, nz, nxb, nzb, taperx, taperz);
         orc_mod_taper_apply(P, nx, nz, nxb, nzb, taperx, taperz);
@@ -206,7 +194,7 @@ void orc_mod_taper_apply2(float *pp, int nx, int nz, int nxb, int nzb, const flo
  * trace of the last shot, one float past the allocation (taken as 0 here).  It also offsets the receiver rows by nzb, not nxb
  * (RM:203), which is kept.  imloc[nx][nz] is overwritten (RM:189). */
 void orc_rtm_stored_shot(int order, int nx, int nz, int nxb, int nzb, int nt, float dx, float dz, float dt, float fac, const float *v2, int sx,
-                         int sz, int gz, const float *srce, const float *dobs_flat, size_t n_flat, int is, float *imloc)
+                         int sz, int gz, const float *srce, const float *dobs_flat, size_t n_flat, int is, float *imloc, int numerics)
 {
     const int nxe = nx + 2 * nxb, nze = nz + 2 * nzb;
     const size_t ne = (size_t)nxe * nze, ni = (size_t)nx * nz;
@@ -218,7 +206,7 @@ void orc_rtm_stored_shot(int order, int nx, int nz, int nxb, int nzb, int nt, fl
     float *P = (float *)calloc(ne, sizeof(float)), *PP = (float *)calloc(ne, sizeof(float)), *lap = (float *)calloc(ne, sizeof(float));
     float *swf = (float *)calloc(ni * (size_t)nt, sizeof(float)), *rwf = (float *)calloc(ni * (size_t)nt, sizeof(float));
     for (int it = 0; it < nt; it++) {
-        orc_mod_fd_step(order, coefs, dx2inv, dz2inv, dt2, P, PP, v2, lap, nze, nxe);
+        orc_mod_fd_step(order, coefs, dx2inv, dz2inv, dt2, P, PP, v2, lap, nze, nxe, numerics);
         PP[(size_t)sx * nze + sz] += srce[it];
         orc_mod_taper_apply2(PP, nx, nz, nxb, nzb, taperx, taperz);
         orc_mod_taper_apply2(P, nx, nz, nxb, nzb, taperx, taperz);
@@ -230,7 +218,7 @@ void orc_rtm_stored_shot(int order, int nx, int nz, int nxb, int nzb, int nt, fl
     memset(PP, 0, ne * sizeof(float));
     memset(imloc, 0, ni * sizeof(float));
     for (int it = 0; it < nt; it++) {
-        orc_mod_fd_step(order, coefs, dx2inv, dz2inv, dt2, P, PP, v2, lap, nze, nxe);
+        orc_mod_fd_step(order, coefs, dx2inv, dz2inv, dt2, P, PP, v2, lap, nze, nxe, numerics);
         for (int ix = 0; ix < nx; ix++) {
             const size_t k = ((size_t)is * nx + ix) * nt + (size_t)(nt - it);
             PP[(size_t)(ix + nzb) * nze + gz] += k < n_flat ? dobs_flat[k] : 0.0f;

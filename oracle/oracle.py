@@ -1,7 +1,7 @@
 """ctypes front end of the CPU oracle (oracle/fdw_oracle.c) -- TEST INFRASTRUCTURE ONLY.
 
 Imported by tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg; never by the
-product package.  Builds liborc.so on first use (gcc -O2 -ffp-contract=off, oracle/Makefile).
+product package.  Builds liborc_v2.so on first use (gcc -O2 -ffp-contract=off, oracle/Makefile).
 """
 import ctypes as C
 import os
@@ -10,6 +10,8 @@ import subprocess
 import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
+_SOURCES = ("fdw_oracle.c", "fdw_oracle_mod.c", "fdw_oracle.h", "Makefile")      # what either library is rebuilt from (oracle/Makefile)
+SO, SO_OMP = "liborc_v2.so", "liborc_v2_omp.so"      # versioned with the C interface declared in _declare (oracle/Makefile)
 _LIB = None
 _OMP = None
 f32p = np.ctypeslib.ndpointer(dtype=np.float32, flags="C_CONTIGUOUS")
@@ -32,24 +34,24 @@ def host_threads():
     return max(1, min(n, int(os.environ.get("FDW_CPU_THREADS", "16"))))
 
 
+def _load(name):
+    so = os.path.join(_HERE, name)
+    if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(os.path.join(_HERE, f)) for f in _SOURCES):
+        build()
+    return _declare(C.CDLL(so))
+
+
 def lib(omp=False):
-    """liborc.so; omp=True: the OpenMP build of the same file (rows of the lap / time / img passes shared out over the host threads,
+    """The serial library; omp=True: the OpenMP build of the same file (rows of the lap / time / img passes shared out over the host threads,
     per-point arithmetic unchanged -- for the full-size parity tests, where one thread would take minutes)."""
     global _LIB, _OMP
     if omp:
         if _OMP is None:
             os.environ.setdefault("OMP_NUM_THREADS", str(host_threads()))      # read by libgomp when the library is loaded
-            so = os.path.join(_HERE, "liborc_omp.so")
-            if not os.path.exists(so) or os.path.getmtime(so) < os.path.getmtime(os.path.join(_HERE, "fdw_oracle.c")):
-                build()
-            _OMP = _declare(C.CDLL(so))
+            _OMP = _load(SO_OMP)
         return _OMP
     if _LIB is None:
-        so = os.path.join(_HERE, "liborc.so")
-        src = os.path.join(_HERE, "fdw_oracle.c")
-        if not os.path.exists(so) or os.path.getmtime(so) < os.path.getmtime(src):
-            build()
-        _LIB = _declare(C.CDLL(so))
+        _LIB = _load(SO)
     return _LIB
 
 
@@ -62,28 +64,25 @@ def _declare(L):
     L.orc_srand.argtypes = [C.c_uint]
     L.orc_extents.argtypes = [C.c_int] * 4 + [C.POINTER(C.c_int)] * 3
     L.orc_init.restype = C.c_void_p
-    L.orc_init.argtypes = [C.c_int] * 6 + [C.c_float] * 4 + [C.c_int]
+    L.orc_init.argtypes = [C.c_int] * 6 + [C.c_float] * 4 + [C.c_int, C.c_int]
     L.orc_free.argtypes = [C.c_void_p]
-    L.orc_set_numerics.argtypes = [C.c_void_p, C.c_int]
-    L.orc_stencil_fast.argtypes = [C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, f32p, f32p]
     L.orc_fd_forward.argtypes = [C.c_void_p, f32p, f32p, f32p, C.c_int, C.c_int, f32p, C.c_int]
     L.orc_fd_back.argtypes = [C.c_void_p, f32p, f32p, f32p, f32p, C.c_int, f32p, C.c_int]
     L.orc_slab_step.argtypes = [C.c_void_p, C.c_int, C.c_int, f32p, f32p, f32p] + [C.c_int] * 6 + [C.c_float]
     L.orc_slab_back_iter.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, f32p, f32p, f32p, f32p, f32p] + [C.c_int] * 4 + [f32p, C.c_int, f32p]
-    L.orc_stencil.argtypes = [C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, f32p, f32p]
+    L.orc_stencil.argtypes = [C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, f32p, f32p, C.c_int]
     L.orc_fused_steps.argtypes = [C.c_int, C.c_int, C.c_int, f32p, f32p, f32p, f32p, f32p, C.c_float, C.c_int]
-    L.orc_mod_set_numerics.argtypes = [C.c_int]
     L.orc_mod_taper_tables.argtypes = [C.c_int, C.c_int, C.c_float, f32p, f32p]
     L.orc_mod_extendvel.argtypes = [C.c_int] * 4 + [f32p]
     L.orc_mod_ricker_wavelet.argtypes = [C.c_int, C.c_float, C.c_float, f32p]
     L.orc_mod_taper_apply.argtypes = [f32p] + [C.c_int] * 4 + [f32p, f32p]
-    L.orc_mod_fd_step.argtypes = [C.c_int, f32p, C.c_float, C.c_float, C.c_float, f32p, f32p, f32p, f32p, C.c_int, C.c_int]
+    L.orc_mod_fd_step.argtypes = [C.c_int, f32p, C.c_float, C.c_float, C.c_float, f32p, f32p, f32p, f32p, C.c_int, C.c_int, C.c_int]
     L.orc_mod_ptsrc.argtypes = [C.c_int] * 4 + [C.c_float, f32p]
-    L.orc_mod_shot.argtypes = [C.c_int] * 6 + [C.c_float] * 4 + [f32p, C.c_int, C.c_int, C.c_int, f32p, f32p]
+    L.orc_mod_shot.argtypes = [C.c_int] * 6 + [C.c_float] * 4 + [f32p, C.c_int, C.c_int, C.c_int, f32p, f32p, C.c_int]
     L.orc_mod_taper_apply2.argtypes = [f32p] + [C.c_int] * 4 + [f32p, f32p]
     L.orc_image_laplacian.argtypes = [f32p, C.c_int, C.c_int, C.c_float, C.c_float, f32p]
     L.orc_image_compare.argtypes = [f32p, f32p, C.c_size_t, C.c_void_p, C.POINTER(C.c_double)]
-    L.orc_rtm_stored_shot.argtypes = [C.c_int] * 6 + [C.c_float] * 4 + [f32p, C.c_int, C.c_int, C.c_int, f32p, f32p, C.c_size_t, C.c_int, f32p]
+    L.orc_rtm_stored_shot.argtypes = [C.c_int] * 6 + [C.c_float] * 4 + [f32p, C.c_int, C.c_int, C.c_int, f32p, f32p, C.c_size_t, C.c_int, f32p, C.c_int]
     return L
 
 
@@ -143,8 +142,7 @@ def extents(nxe, nze, nzb, compat):
 
 def stencil(order, nxe, nze, dx, dz, field, numerics=0):
     out = np.zeros((nxe, nze), np.float32)
-    fn = lib().orc_stencil_fast if numerics else lib().orc_stencil
-    fn(order, nxe, nze, dx, dz, np.ascontiguousarray(field, np.float32).reshape(nxe, nze), out)
+    lib().orc_stencil(order, nxe, nze, dx, dz, np.ascontiguousarray(field, np.float32).reshape(nxe, nze), out, int(numerics))
     return out
 
 
@@ -157,11 +155,9 @@ class Oracle:
         self.shape = (nxe, nze)
         self.nx, self.nz, self.nt = nxe - 2 * nxb, nze - 2 * nzb, nt
         self._lib = lib(omp)
-        self._h = self._lib.orc_init(order, nxe, nze, nxb, nzb, nt, fac, dx, dz, dt, int(compat))
+        self._h = self._lib.orc_init(order, nxe, nze, nxb, nzb, nt, fac, dx, dz, dt, int(compat), int(numerics))
         if not self._h:
             raise ValueError("orc_init rejected the parameters")
-        if numerics:
-            self._lib.orc_set_numerics(self._h, int(numerics))
 
     def __del__(self):
         if getattr(self, "_h", None):
@@ -221,25 +217,18 @@ def mod_ricker_wavelet(nt, dt, fpeak):
     return s
 
 
-def mod_numerics(numerics):
-    """Switch the sibling-dialect loops of the oracle (mod_shot, mod_steps, rtm_stored_shot) to the product's FAST formula (1) or back to
-    the sibling's own arithmetic (0, what every parity pin refers to).  Module-level state: tests reset it."""
-    lib().orc_mod_set_numerics(int(numerics))
-
-
+# numerics (mod_shot, mod_steps, rtm_stored_shot): 0 = the sibling's own arithmetic (what every parity pin refers to), 1 = the product's
+# FAST formula on these loops
 def mod_shot(order, nx, nz, nxb, nzb, dx, dz, dt, fac, vel2, sx, sz, gz, srce, numerics=0):
     """mod_main's loop for one shot (mod_main.cpp:140-174): data[nx][nt]."""
     srce = np.ascontiguousarray(srce, np.float32)
     data = np.zeros((nx, srce.size), np.float32)
-    mod_numerics(numerics)
-    try:
-        lib().orc_mod_shot(order, nx, nz, nxb, nzb, srce.size, dx, dz, dt, fac, np.ascontiguousarray(vel2, np.float32), sx, sz, gz, srce, data)
-    finally:
-        mod_numerics(0)
+    lib().orc_mod_shot(order, nx, nz, nxb, nzb, srce.size, dx, dz, dt, fac, np.ascontiguousarray(vel2, np.float32), sx, sz, gz, srce, data,
+                       int(numerics))
     return data
 
 
-def mod_steps(order, nx, nz, nxb, nzb, dx, dz, dt, fac, vel2, sx, sz, gz, srce, P, PP):
+def mod_steps(order, nx, nz, nxb, nzb, dx, dz, dt, fac, vel2, sx, sz, gz, srce, P, PP, numerics=0):
     """nsteps = len(srce) iterations of mod_main's loop (mod_main.cpp:147-164) from the given P / PP (as the loop holds them on entry):
     returns (P, PP, data[nx][nsteps]) as the loop holds them after the last swap."""
     L = lib()
@@ -255,7 +244,7 @@ def mod_steps(order, nx, nz, nxb, nzb, dx, dz, dt, fac, vel2, sx, sz, gz, srce, 
     lap = np.zeros((nxe, nze), np.float32)
     data = np.zeros((nx, srce.size), np.float32)
     for it in range(srce.size):
-        L.orc_mod_fd_step(order, coefs, dx2inv, dz2inv, dt2, P, PP, vel2, lap, nze, nxe)
+        L.orc_mod_fd_step(order, coefs, dx2inv, dz2inv, dt2, P, PP, vel2, lap, nze, nxe, int(numerics))
         L.orc_mod_ptsrc(sx, sz, nxe, nze, srce[it], PP)
         L.orc_mod_taper_apply(PP, nx, nz, nxb, nzb, tx, tz)
         L.orc_mod_taper_apply(P, nx, nz, nxb, nzb, tx, tz)
@@ -279,12 +268,8 @@ def rtm_stored_shot(order, nx, nz, nxb, nzb, dx, dz, dt, fac, vel2, sx, sz, gz, 
     srce = np.ascontiguousarray(srce, np.float32)
     dobs = np.ascontiguousarray(dobs, np.float32).ravel()
     imloc = np.zeros((nx, nz), np.float32)
-    mod_numerics(numerics)
-    try:
-        lib().orc_rtm_stored_shot(order, nx, nz, nxb, nzb, srce.size, dx, dz, dt, fac, np.ascontiguousarray(vel2, np.float32), sx, sz, gz, srce,
-                                  dobs, dobs.size, shot, imloc)
-    finally:
-        mod_numerics(0)
+    lib().orc_rtm_stored_shot(order, nx, nz, nxb, nzb, srce.size, dx, dz, dt, fac, np.ascontiguousarray(vel2, np.float32), sx, sz, gz, srce,
+                              dobs, dobs.size, shot, imloc, int(numerics))
     return imloc
 
 

@@ -22,13 +22,11 @@
 
 /* oracle/fdw_oracle.c, oracle/fdw_oracle_mod.c */
 typedef struct orc_state orc_state;
-orc_state *orc_init(int order, int nxe, int nze, int nxb, int nzb, int nt, float fac, float dx, float dz, float dt, int compat);
-void orc_set_numerics(orc_state *s, int numerics);
+orc_state *orc_init(int order, int nxe, int nze, int nxb, int nzb, int nt, float fac, float dx, float dz, float dt, int compat, int numerics);
 void orc_free(orc_state *s);
 void orc_fd_forward(orc_state *s, float *p, float *pp, const float *v2, int sx, int sz, const float *srce, int nsteps);
 void orc_fd_back(orc_state *s, const float *v2, const float *snap0, const float *snap1, const float *d_obs, int gz_, float *imloc, int nsteps);
-void orc_stencil(int order, int nxe, int nze, float dx, float dz, const float *in, float *out);
-void orc_stencil_fast(int order, int nxe, int nze, float dx, float dz, const float *in, float *out);
+void orc_stencil(int order, int nxe, int nze, float dx, float dz, const float *in, float *out, int numerics);
 void orc_slab_step(const orc_state *s, int x_off, int nxl, float *p, float *pp, const float *v2, int r0, int r1, int t0, int t1, int sx_global, int sz, float srce_it);
 void orc_slab_back_iter(const orc_state *s, int x_off, int nxl, int step_source, float *f1, float *f0, float *pr, float *ppr, const float *v2, int r0, int r1, int t0,
                         int t1, const float *samples, int gz_, float *img);
@@ -40,11 +38,10 @@ void orc_srand(unsigned seed);
 void orc_fused_steps(int order, int nxe, int nze, float *p, float *pp, const float *v2, const float *cx, const float *cz, float dt2, int nsteps);
 void orc_scaled_coefs(int order, float dx, float dz, int cxx, float *coefs_x, float *coefs_z);
 void orc_mod_shot(int order, int nx, int nz, int nxb, int nzb, int nt, float dx, float dz, float dt, float fac, const float *v2, int sx, int sz, int gz,
-                  const float *srce, float *data);
+                  const float *srce, float *data, int numerics);
 void orc_rtm_stored_shot(int order, int nx, int nz, int nxb, int nzb, int nt, float dx, float dz, float dt, float fac, const float *v2, int sx, int sz, int gz,
-                         const float *srce, const float *dobs_flat, size_t n_flat, int is, float *imloc);
+                         const float *srce, const float *dobs_flat, size_t n_flat, int is, float *imloc, int numerics);
 void orc_mod_ricker_wavelet(int nt, float dt, float peak, float *s);
-void orc_mod_set_numerics(int numerics);
 void orc_mod_extendvel(int nx, int nz, int nxb, int nzb, float *vel);
 void orc_image_laplacian(const float *img, int nx, int nz, float dx, float dz, float *out);
 void orc_image_compare(const float *f1, const float *f2, size_t n, float *diff, double *stats);
@@ -195,9 +192,8 @@ static void oracle_loops(void)
                 const int nxe = cases[c][0], nze = cases[c][1], nxb = cases[c][2], nzb = cases[c][3], nt = cases[c][4], order = cases[c][5];
                 const int nx = nxe - 2 * nxb, nz = nze - 2 * nzb;
                 const size_t ne = (size_t)nxe * nze;
-                orc_state *s = orc_init(order, nxe, nze, nxb, nzb, nt, 0.75f, 10.0f, 12.5f, 0.001f, compat);
+                orc_state *s = orc_init(order, nxe, nze, nxb, nzb, nt, 0.75f, 10.0f, 12.5f, 0.001f, compat, numerics);
                 if (!s) abort();
-                orc_set_numerics(s, numerics);
                 float *v2 = randf(ne, 1500.0f * 1500.0f, 3000.0f * 3000.0f), *srce = randf((size_t)nt, -1, 1);
                 float *P = (float *)calloc(ne, sizeof(float)), *PP = (float *)calloc(ne, sizeof(float));
                 float *dobs = randf((size_t)nx * nt, -1, 1), *img = (float *)calloc((size_t)nx * nz + 1, sizeof(float));
@@ -228,7 +224,7 @@ static void oracle_loops(void)
                 }
                 float *lap = (float *)calloc(ne, sizeof(float));
                 if (!lap) abort();
-                (numerics ? orc_stencil_fast : orc_stencil)(order, nxe, nze, 10.0f, 12.5f, v2, lap);
+                orc_stencil(order, nxe, nze, 10.0f, 12.5f, v2, lap, numerics);
                 eat(lap, ne);
                 float cx[65], cz[65];
                 orc_scaled_coefs(order, 10.0f, 12.5f, 0, cx, cz);
@@ -244,14 +240,13 @@ static void oracle_loops(void)
         float *img = (float *)calloc((size_t)nx * nz, sizeof(float)), *out = (float *)calloc((size_t)nx * nz, sizeof(float));
         if (!data || !img || !out) abort();
         for (int order = 2; order <= 8; order += 2) {
-            orc_mod_set_numerics((order / 2) & 1);      /* both numerics modes of these loops */
-            orc_mod_shot(order, nx, nz, nxb, nzb, nt, 10.0f, 8.0f, 0.001f, 0.01f, v2, nxb + 3, nzb + 2, nzb + 1, srce, data);
+            const int numerics = (order / 2) & 1;      /* both numerics modes of these loops */
+            orc_mod_shot(order, nx, nz, nxb, nzb, nt, 10.0f, 8.0f, 0.001f, 0.01f, v2, nxb + 3, nzb + 2, nzb + 1, srce, data, numerics);
             eat(data, (size_t)nx * nt);
             /* the gather as rtm_main indexes it: one sample past the last trace of the last shot reads as 0 (n_flat bounds it) */
-            orc_rtm_stored_shot(order, nx, nz, nxb, nzb, nt, 10.0f, 8.0f, 0.001f, 0.01f, v2, nxb + 3, nzb + 2, nzb + 1, srce, data, (size_t)nx * nt, 0, img);
+            orc_rtm_stored_shot(order, nx, nz, nxb, nzb, nt, 10.0f, 8.0f, 0.001f, 0.01f, v2, nxb + 3, nzb + 2, nzb + 1, srce, data, (size_t)nx * nt, 0, img, numerics);
             eat(img, (size_t)nx * nz);
         }
-        orc_mod_set_numerics(0);
         orc_image_laplacian(img, nx, nz, 10.0f, 8.0f, out);
         eat(out, (size_t)nx * nz);
         double st[4];

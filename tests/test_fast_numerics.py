@@ -308,7 +308,7 @@ from test_gpu_parity import MOD_CASES  # noqa: E402
 @pytest.mark.parametrize("case", MOD_CASES, ids=lambda c: "x".join(map(str, c[:6])))
 def test_fast_model_shot_vs_fast_oracle_bit_exact(case):
     """mod_main's loop in FAST numerics (one-step kernel, and the wave pipeline where it exists) against the oracle's FAST restatement of
-    fd_step (fdw_oracle_mod.c orc_mod_set_numerics), bit for bit: four-sided damping, Gaussian source, trace recording, orders 2..8,
+    fd_step (fdw_oracle_mod.c orc_mod_fd_step, numerics = 1), bit for bit: four-sided damping, Gaussian source, trace recording, orders 2..8,
     dx != dz; and within 1e-5 (max norm) of the sibling's own arithmetic."""
     nx, nz, nxb, nzb, nt, order, dx, dz, fac, (sx0, sz0, gz0) = case
     nxe, nze = nx + 2 * nxb, nz + 2 * nzb

@@ -723,12 +723,8 @@ def test_full_size_modelling_steps_vs_oracle(n):
         torch.cuda.synchronize()
         ctx.dev_model_steps(p.data_ptr(), pp.data_ptr(), dv2.data_ptr(), dsr.data_ptr(), sx, sz, gz, rec.data_ptr(), 0, nsteps)
         torch.cuda.synchronize()
-        O.mod_numerics(numerics)
-        try:
-            wP, wPP, wdata = O.mod_steps(8, nx, nz, nxb, nzb, 10.0, 10.0, 0.001, fac, v2, sx, sz, gz, srce,
-                                         O.mod_taper_apply(P0, nx, nz, nxb, nzb, fac, 1), O.mod_taper_apply(PP0, nx, nz, nxb, nzb, fac, 2))
-        finally:
-            O.mod_numerics(0)
+        wP, wPP, wdata = O.mod_steps(8, nx, nz, nxb, nzb, 10.0, 10.0, 0.001, fac, v2, sx, sz, gz, srce,
+                                     O.mod_taper_apply(P0, nx, nz, nxb, nzb, fac, 1), O.mod_taper_apply(PP0, nx, nz, nxb, nzb, fac, 2), numerics=numerics)
         assert_bit_equal(rec.cpu().numpy().T, wdata, f"gather at {n}^2, numerics={numerics}")
         assert_bit_equal(O.mod_taper_apply(p[:, :n].cpu().numpy(), nx, nz, nxb, nzb, fac, 1), wP, f"P at {n}^2, numerics={numerics}")
         assert_bit_equal(O.mod_taper_apply(pp[:, :n].cpu().numpy(), nx, nz, nxb, nzb, fac, 2), wPP, f"PP at {n}^2, numerics={numerics}")

@@ -234,7 +234,7 @@ def test_modelling_passes_match_the_reference_functions():
         lap = np.zeros((nxe, nze), np.float32)
         dx2inv = np.float32((1. / 10.0) * (1. / 10.0))
         dz2inv = np.float32((1. / 12.5) * (1. / 12.5))
-        O.lib().orc_mod_fd_step(order, np.ascontiguousarray(coefs), dx2inv, dz2inv, np.float32(0.001) * np.float32(0.001), p, pp, v2, lap, nze, nxe)
+        O.lib().orc_mod_fd_step(order, np.ascontiguousarray(coefs), dx2inv, dz2inv, np.float32(0.001) * np.float32(0.001), p, pp, v2, lap, nze, nxe, 0)
         assert_bit_equal(pp, pp_ref, f"fd_step order {order}")
         if R:
             R._Z10fd_destroyv()
@@ -249,6 +249,30 @@ def test_stored_wavefield_rtm_known_answer_bit_exact():
     srce = O.mod_ricker_wavelet(d["nt"], d["dt"], d["fpeak"])
     img = O.rtm_stored_shot(d["order"], d["nx"], d["nz"], d["nxb"], d["nzb"], d["dx"], d["dz"], d["dt"], d["fac"], v2, d["sx"], d["sz"], d["gz"], srce, d["dobs"])
     assert_bit_equal(img, golden_field("dd_3lay_mod_dir_image.f32", (d["nx"], d["nz"])), "oracle rtm_main loop vs build/3lay_mod/dir.image")
+
+
+def test_sibling_loops_take_numerics_per_call_under_threads():
+    """numerics is an argument of each sibling-dialect oracle call, not process state: EXACT and FAST calls of mod_shot and rtm_stored_shot
+    running side by side in threads (ctypes releases the GIL) each return the serial result of their own numerics, and the two differ."""
+    import concurrent.futures
+    nx, nz, nxb, nzb, nt = 64, 48, 12, 10, 120
+    rng = np.random.default_rng(11)
+    v2 = ((1500 + 2500 * rng.random((nx + 2 * nxb, nz + 2 * nzb))) ** 2).astype(np.float32)
+    srce = O.mod_ricker_wavelet(nt, 0.001, 25.0)
+    dobs = (1e-2 * rng.standard_normal((1, nx, nt))).astype(np.float32)
+    deck = (8, nx, nz, nxb, nzb, 10.0, 12.5, 0.001, 0.02, v2, nxb + nx // 2, nzb + 3, nzb + 2, srce)
+    run = {"mod_shot": lambda numerics: O.mod_shot(*deck, numerics=numerics),
+           "rtm_stored_shot": lambda numerics: O.rtm_stored_shot(*deck, dobs, numerics=numerics)}
+    serial = {(name, numerics): fn(numerics) for name, fn in run.items() for numerics in (0, 1)}
+    for name in run:
+        assert (serial[(name, 0)] != serial[(name, 1)]).any() and np.abs(serial[(name, 0)]).max() > 0, name
+    jobs = [(name, numerics) for _ in range(4) for name in run for numerics in (0, 1)]
+    with concurrent.futures.ThreadPoolExecutor(max_workers=8) as pool:
+        results = list(pool.map(lambda job: run[job[0]](job[1]), jobs))
+    for job, got in zip(jobs, results):
+        assert_bit_equal(got, serial[job], f"{job[0]} numerics={job[1]} in a thread")
+    for setter in ("orc_mod_set_numerics", "orc_set_numerics"):
+        assert not hasattr(O.lib(), setter), setter
 
 
 def test_taper_apply2_matches_the_reference_function():
