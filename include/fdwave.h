@@ -69,7 +69,10 @@ typedef struct fdw_params {
                        Results agree with EXACT to rounding: <= 1e-5 max-norm-relative over the 1 700 steps of the reference's new_mod
                        deck (tests), the size of the reference's own FMA / no-FMA difference.  Dialects 1 and 2 take the same formula
                        with the spacings folded into the weights (c_k * d?2inv once instead of inside every term): the sibling's committed
-                       3lay_mod gather is met to 2.2e-6 in the max norm (1.3e-5 in the L2 norm) over its 1 001 steps. */
+                       3lay_mod gather is met to 2.2e-6 in the max norm (1.3e-5 in the L2 norm) over its 1 001 steps.
+                       Against the float64 statement of the RTM loop (tests/rtm_restatement.py) the FAST image of a whole shot is
+                       within 1.9e-6 max-norm-relative on two decks but 1.23e-5 on a third (70 x 53, dx = 8, dz = 12.5, order 8,
+                       400 steps), where EXACT is within 1.6e-6: FAST is held to 2e-5 there (tests/test_backward_pins.py). */
 } fdw_params;
 enum { FDW_NUMERICS_EXACT = 0, FDW_NUMERICS_FAST = 1 };
 enum { FDW_DIALECT_RTM = 0, FDW_DIALECT_MOD = 1, FDW_DIALECT_RTM_STORED = 2 };

@@ -15,10 +15,15 @@
  *   - orc_fd_forward      <=1e-5 max-norm-rel vs cuda_reference_stencil_computation/input.bin
  *                         (shot 5 of models/new_mod, P after 1700 steps, real-hardware output)
  *   - host tables         bit-exact vs oracle/_ref (F compiled unmodified by gcc)
- *   - orc_fd_back         PARITY UNPINNED: the reference ships no usable image golden
+ *   - orc_fd_back         no reference output: the reference ships no usable image golden
  *                         (output/dir.image is all zeros, dobs.6 is missing) and the .cu cannot
- *                         be built here (needs nvcc / cuda.h).  fd_back reuses the pinned
- *                         lap/time/taper passes; injection + imaging are restated from R:124-144.
+ *                         be built here (needs nvcc / cuda.h).  Pinned instead to an independent
+ *                         NumPy statement of R:290-341 (tests/rtm_restatement.py): bit for bit at
+ *                         v2 = 0, where the loop has a closed form in fp32, and within 1e-5 of a
+ *                         float64 statement with propagation (tests/test_backward_pins.py, which
+ *                         also shows that eleven named misreadings fail those pins).  NOT
+ *                         pinned: the two race resolutions below (orc_kernel_tapper,
+ *                         orc_kernel_sism), which that statement takes by the same convention.
  *
  * Build: gcc -O2 -ffp-contract=off (no FMA contraction: the reference is built with
  * --fmad=false, S Makefile:4) -- see oracle/Makefile.
