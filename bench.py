@@ -3,7 +3,16 @@
 the body of the reference's fd_forward loop, cuda_reference_RTM/src/fd-code.cu:259-267) on a synthetic
 grid, device resident.  One JSON line on rank 0.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--size 8192] [--ksteps 4] [--no-cpu-baseline] [--dump-outputs DIR]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--size 8192] [--ksteps 4] [--full] [--no-cpu-baseline] [--dump-outputs DIR]
+
+A plain run does only what its headline figure needs: set-up, the W warm-up steps, the timed K steps, --dump-outputs, the line.
+--full adds everything measured or checked beside the headline, each still switched off by its own --no-... option:
+  forward, N = 1: the zero-initial-field line (--no-rest-line), the FAST-numerics line (--no-fast-line), BASELINE.json's 4096^2 line
+                  at --size 8192 (--no-extra), the CPU baselines (--no-cpu-baseline);
+  N > 1:          the bitwise comparison with a single-domain run (--no-check; --check asks for it in a plain run too), the re-timing
+                  with the transfers switched off (--no-exposed);
+  rtm-slab, N = 1: the launch time of the fused backward pass (timed by extra backward loops) as the roofline;
+  model / stencil / rtm: the CPU baseline.
 
 N = 1 : the whole grid on one MI355X.
 N > 1 : one rank per GPU; the SAME grid is split into x slabs with deep-halo exchange over RCCL inside
@@ -27,7 +36,7 @@ roofline: bound = HBM.  `achieved` = HBM-side bytes one launch moves / its durat
 rocprofv3 --pmc figure of profiles/traffic.json when that profile was taken on exactly this kernel build (source hash), otherwise the
 minimum one launch must move (12 B in + 8 B out per point for a multi-step pass).  SURVEY.md 8(d)'s 16 B/point/step model -- which a
 temporally blocked kernel beats by construction -- is reported beside it as `algorithmic_16B_model`, never as the fraction.
-cpu_baseline: the oracle's fused C loop (same arithmetic), 1 thread, bounded sample, rank 0, N = 1.
+cpu_baseline (--full): the oracle's fused C loop (same arithmetic), 1 thread, bounded sample, rank 0, N = 1.
 """
 import argparse
 import json
@@ -808,9 +817,9 @@ def run_rtm_slab_workload(args):
                    "ms_per_step_transfers_off": round(wall_stub * 1e3 / K, 6),
                    "method": "median window re-timed with fdw_slabs_set_stub(1): exchanges enqueue nothing, everything else unchanged"}
     # N = 1 through the C driver: the dominant kernel is the fused backward pass (four iterations per launch); its launch time is measured
-    # here, on the slab's stream, as the difference of two backward loops that differ by 32 passes
+    # here (--full), on the slab's stream, as the difference of two backward loops that differ by 32 passes
     back_launch_s = None
-    if world == 1 and c_driver and me["sl"].back_buffers() == (6, 4) and nt >= 2 + 4 * 40:
+    if args.full and world == 1 and c_driver and me["sl"].back_buffers() == (6, 4) and nt >= 2 + 4 * 40:
         sl, fld, rcv = me["sl"], me["fld"], me["fld"][me["nsrc"]:]
         ext = torch.cuda.ExternalStream(sl.stream)
         scratch_img = torch.zeros_like(me["img"])
@@ -915,26 +924,30 @@ def main():
     ap.add_argument("--workload", choices=("forward", "model", "rtm", "stencil", "rtm-slab"), default="forward",
                     help="forward: the headline fused forward step of rtm_code (default); model: the forward-modelling producer; "
                          "rtm: whole RTM shots on the reference's new_mod deck size (both N = 1 only)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-rest-line", action="store_true", help="forward workload, N = 1: skip the extra measurement from BASELINE.md's zero initial fields")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline (CPU baselines, the other lines, the N > 1 comparison and "
+                         "re-timing, per-kernel launch times); a plain run sets up, warms up, times the K steps, dumps and prints the line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines")
+    ap.add_argument("--no-rest-line", action="store_true", help="--full, forward workload, N = 1: skip the extra measurement from BASELINE.md's zero initial fields")
     ap.add_argument("--no-overlap", action="store_true")
     ap.add_argument("--backend", default="nccl", choices=("nccl", "shm"),
                     help="N > 1: nccl = halo exchange over RCCL inside libfdwave.so, one rank per GPU (default); shm = the same C drivers over the "
                          "library's process transport (shared-memory staging), ranks may share one GPU (rehearsals on a one-GPU box)")
-    ap.add_argument("--check", action="store_true", help="N > 1: compare the decomposed result with a single-domain run on rank 0, bitwise (always on; kept for old command lines)")
+    ap.add_argument("--check", action="store_true", help="N > 1: compare the decomposed result with a single-domain run on rank 0, bitwise (on with --full; "
+                                                          "this asks for it in a plain run)")
     ap.add_argument("--no-check", action="store_true", help="N > 1: skip that comparison")
-    ap.add_argument("--no-exposed", action="store_true", help="N > 1, --backend nccl: skip the re-timing with the transfers off (exposed_comm_fraction)")
+    ap.add_argument("--no-exposed", action="store_true", help="--full, N > 1: skip the re-timing with the transfers off (exposed_comm_fraction)")
     ap.add_argument("--numerics", choices=["exact", "fast"], default="exact",
                     help="exact (default, what `value` always reports in the default run): the reference's arithmetic operation for operation, bit-identical "
                          "to the oracle; fast: fdw_params.numerics = FDW_NUMERICS_FAST (symmetric sums + fused multiply-adds in the Laplacian, within "
-                         "1e-5 of exact) for the whole run -- profiling and scaling runs of that mode; the default run prints it beside the headline")
+                         "1e-5 of exact) for the whole run -- profiling and scaling runs of that mode; a --full run prints it beside the headline")
     ap.add_argument("--max-windows", type=int, default=1,
                     help="repetitions of the K-step timed window (default 1: exactly --steps timed steps); M > 1: repeat until 0.3 s are measured, "
                          "at most M times, and report the median window")
     ap.add_argument("--dump-outputs", default=None, metavar="DIR",
                     help="forward workload, N = 1: write the fields the timed loop leaves after its last step (p, pp) as DIR/<name>.npy")
-    ap.add_argument("--no-extra", action="store_true", help="forward workload, N = 1, default size: skip the extra 4096^2 / 1000-step line (BASELINE.json configs[1])")
-    ap.add_argument("--no-fast-line", action="store_true", help="forward workload, N = 1: skip the extra measurement in FAST numerics")
+    ap.add_argument("--no-extra", action="store_true", help="--full, forward workload, N = 1, default size: skip the extra 4096^2 / 1000-step line (BASELINE.json configs[1])")
+    ap.add_argument("--no-fast-line", action="store_true", help="--full, forward workload, N = 1: skip the extra measurement in FAST numerics")
     ap.add_argument("--init", choices=["noise", "rest"], default="noise",
                     help="initial wavefield: seeded noise (default; every cache line carries real data) or at rest (zeros + source)")
     ap.add_argument("--rccl-rehearsal", default=None, metavar="UNIQUE_ID_HEX",
@@ -945,6 +958,9 @@ def main():
             sys.exit("bench: no GPU visible (the product has no CPU path)")
         return rccl_rehearsal_main(args.rccl_rehearsal)
     MAX_WINDOWS[0] = max(1, args.max_windows)
+    if not args.full:             # a plain run: nothing beside the headline (the module docstring lists what --full adds)
+        args.no_cpu_baseline = args.no_rest_line = args.no_fast_line = args.no_extra = args.no_exposed = True
+        args.no_check = args.no_check or not args.check
     if args.dump_outputs and args.workload != "forward":
         sys.exit("bench: --dump-outputs is implemented for the forward workload")
     if os.environ.get("FDW_BENCH_POISON") == "1":

@@ -475,7 +475,7 @@ def test_bench_starts_its_own_ranks(workload, backend, tmp_path):
     import sys
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "LOCAL_WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", backend, "--size", "1024", "--steps", "24", "--warmup", "6",
-           "--check", "--no-cpu-baseline", "--workload", workload]
+           "--full", "--no-cpu-baseline", "--workload", workload]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=tmp_path, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     last = [ln for ln in r.stdout.splitlines() if ln.strip()][-1]
@@ -545,6 +545,26 @@ def test_bench_multi_gpu_code_path_on_one_rank(tmp_path):
 
 
 @pytest.mark.gpu
+def test_bench_plain_run_leaves_the_rest_to_full(tmp_path):
+    """`bench.py --gpus 1` without --full prints the headline line and nothing measured beside it; with --full the same command adds the
+    zero-initial-field and FAST-numerics lines (the CPU baselines, --full's slowest part, are left out here with --no-cpu-baseline)."""
+    import json
+    import sys
+    base = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--size", "1024", "--steps", "24", "--warmup", "6"]
+    lines = []
+    for opts in ([], ["--full", "--no-cpu-baseline"]):
+        r = subprocess.run(base + opts, capture_output=True, text=True, timeout=600, cwd=tmp_path)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines.append(json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]))
+    plain, full = lines
+    for d in (plain, full):
+        assert d["n_gpus"] == 1 and d["steps"] == 24 and d["warmup"] == 6 and d["result_finite_nonzero"] and d["value"] > 0 and d["ms_per_step"] > 0
+        assert d["numerics"] == "exact" and d["roofline"]["bound"] == "hbm"
+    assert not {"cpu_baseline", "fast_numerics", "baseline_md_initial_condition", "extra"} & set(plain)
+    assert full["fast_numerics"]["result_finite_nonzero"] and full["fast_numerics"]["value"] > 0 and full["baseline_md_initial_condition"]["value"] > 0
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("ranks,opts", [(1, []), (2, ["--backend", "shm", "--ksteps", "4"]), (3, ["--backend", "shm", "--ksteps", "3", "--steps", "11"])],
                          ids=["1rank-c-driver", "2ranks-shm-k4", "3ranks-shm-k3-leftover"])
 def test_bench_rtm_slab_workload(ranks, opts, tmp_path):
@@ -553,7 +573,8 @@ def test_bench_rtm_slab_workload(ranks, opts, tmp_path):
     compared bitwise with a single-domain run of the same shots."""
     import json
     import sys
-    base = [os.path.join(ROOT, "bench.py"), "--workload", "rtm-slab", "--gpus", str(ranks), "--size", "1024", "--steps", "12", "--warmup", "4", "--no-cpu-baseline"] + opts
+    base = [os.path.join(ROOT, "bench.py"), "--workload", "rtm-slab", "--gpus", str(ranks), "--size", "1024", "--steps", "12", "--warmup", "4", "--full",
+            "--no-cpu-baseline"] + opts
     if ranks == 1:
         cmd = [sys.executable] + base
     else:
