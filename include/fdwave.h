@@ -297,6 +297,29 @@ int fdw_shot_batch_max(const fdw_ctx *ctx);
 int fdw_model_shot_batch(fdw_ctx *ctx, int nshots, const float *vel2, int sx0, int dsx, int sz, int gz, const float *srce, int nt, float *data);
 int fdw_model_resident(fdw_ctx *ctx, const float *vp);
 int fdw_dev_extendvel_linear(fdw_ctx *ctx, unsigned long long draw_offset, float *vel_out);
+
+/* ---- recorded shot gathers of the RTM dialect (the data rtm_code migrates, R:420-424) ------------------------------------------
+ * Definition: data[ix][it] (ix < nx, it < nt) is what the reference's d_pp holds at row nxb + ix, column gz at the END of iteration it of
+ * fd_forward's loop (R:259-267), i.e. after kernel_src (R:267): the new field u^{it+1}, undamped (the taper of R:264 reaches it only at
+ * the start of the next iteration), a source on the receiver cell included.  Backward iteration k of fd_back injects sample nt-1-k
+ * (R:328) into r^{k+1} and images it against F_k = u^{nt-k}, so sample j meets u^{j+1}, the level it was recorded from: migrating such a
+ * gather correlates equal time levels.  (The sibling's mod_main records the CURRENT field instead, mod_main.cpp:155-157.)  Receiver
+ * rows the loop never time-steps (compat extents: rows >= xlim) record what d_pp holds there; gz must lie in [0, zlim), the columns the
+ * loop time-steps (fdw_get_extents), else FDW_EINVAL.  RTM dialect only (FDW_ESTATE otherwise); EXACT and FAST numerics alike.
+ * fdw_dev_record_steps   fdw_dev_steps2 (R:259-267, same buffers, indices and kernel family per pass, bit-identical fields) that also writes
+ *                        the samples of iteration it to d_rec + it * nx (d_rec [>= it0+nsteps][nx] on the device, absolute row it, as
+ *                        fdw_dev_model_steps does)
+ * fdw_record_shot        one shot from rest (R:496-497, nt = the context's steps) on v2[nxe][nze]: data[nx][nt]; P / PP (may be NULL) are
+ *                        fdw_forward's, P damped as R:285 downloads it.  Full-grid contexts.
+ * fdw_record_shot_batch  `nshots` of them with source rows sx0 + b dsx (R:405-407) and models as fdw_shot_batch takes them (v2_all
+ *                        [nshots][nxe][nze], or NULL: the border models of draws [draw_offset + b T, ...) on the resident model): one launch
+ *                        per time step for the whole batch where fdw_shot_batch batches, the shots one by one otherwise; data
+ *                        [nshots][nx][nt] equals fdw_record_shot shot by shot, bit for bit. */
+int fdw_dev_record_steps(fdw_ctx *ctx, float *const *d_buf, const float *d_v2, const float *d_srce, int sx, int sz, int gz, float *d_rec,
+                         int it0, int nsteps, int first_pp_twice, int *ip, int *ipp, void *stream);
+int fdw_record_shot(fdw_ctx *ctx, const float *v2, int sx, int sz, int gz, const float *srce, float *data, float *P, float *PP);
+int fdw_record_shot_batch(fdw_ctx *ctx, int nshots, const float *v2_all, unsigned long long draw_offset, int sx0, int dsx, int sz, int gz,
+                          const float *srce, float *data);
 int fdw_shot_resident(fdw_ctx *ctx, int sx, int sz, int gz, const float *srce, const float *d_obs, float *imloc, float *P, float *PP);
 int fdw_rand_stream(fdw_ctx *ctx, unsigned long long draw_offset, long long n, int *out);
 

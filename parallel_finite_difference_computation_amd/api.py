@@ -237,6 +237,24 @@ class FDWave:
                                    _f32(d_obs, (nshots, self.nx, self.nt)), imloc))
         return imloc
 
+    def record_shot(self, v2, sx, sz, gz, srce, want_fields=False):
+        """fd_forward from rest (fd-code.cu:496-497, 259-267) recording the gather data[nx][nt]: data[ix][it] = d_pp(nxb + ix, gz) at the end
+        of iteration it (fdwave.h, fdw_record_shot), the layout rtm_code's datfile holds per shot.  want_fields: also (P, PP) as forward()."""
+        shape = (self.nxe, self.nze)
+        data = np.zeros((self.nx, self.nt), np.float32)
+        P = np.zeros(shape, np.float32) if want_fields else None
+        PP = np.zeros(shape, np.float32) if want_fields else None
+        check(lib().fdw_record_shot(self._h, _f32(v2, shape), sx, sz, gz, _f32(srce, (self.nt,)), data,
+                                    P.ctypes.data if want_fields else None, PP.ctypes.data if want_fields else None))
+        return (data, P, PP) if want_fields else data
+
+    def record_shot_batch(self, nshots, sx0, dsx, sz, gz, srce, v2_all=None, draw_offset=0):
+        """`nshots` recorded gathers, source rows sx0 + b dsx, models as shot_batch takes them: data[nshots][nx][nt]."""
+        data = np.zeros((nshots, self.nx, self.nt), np.float32)
+        v2p = None if v2_all is None else _f32(v2_all, (nshots, self.nxe, self.nze)).ctypes.data
+        check(lib().fdw_record_shot_batch(self._h, nshots, v2p, int(draw_offset), sx0, dsx, sz, gz, _f32(srce, (self.nt,)), data))
+        return data
+
     def shot_batch_max(self):
         return int(lib().fdw_shot_batch_max(self._h))
 
@@ -321,6 +339,14 @@ class FDWave:
         arr = (C.c_void_p * 4)(*bufs)
         a, b = C.c_int(ip), C.c_int(ipp)
         check(lib().fdw_dev_steps2(self._h, arr, d_v2, d_srce, sx, sz, it0, nsteps, int(first_pp_twice), C.byref(a), C.byref(b), stream))
+        return a.value, b.value
+
+    def dev_record_steps(self, bufs, d_v2, d_srce, sx, sz, gz, d_rec, it0, nsteps, first_pp_twice=False, ip=0, ipp=1, stream=None):
+        """dev_steps2 that also writes the trace samples of iteration it to d_rec + it * nx (device [it][nx]; fdwave.h).
+        Returns (ip, ipp) as dev_steps2 does."""
+        arr = (C.c_void_p * 4)(*bufs)
+        a, b = C.c_int(ip), C.c_int(ipp)
+        check(lib().fdw_dev_record_steps(self._h, arr, d_v2, d_srce, sx, sz, gz, d_rec, it0, nsteps, int(first_pp_twice), C.byref(a), C.byref(b), stream))
         return a.value, b.value
 
     def dev_taper_finalize(self, d_f, stream=None):

@@ -415,6 +415,14 @@ static void fill_common(const fdw_ctx* c, A& a, const float* d_p, decltype(A::pp
     }
 }
 
+// this step's trace row on the receiver line (interior rows nxb .. nxb+nx-1, R:126-129): rec[r - rec_x0] = a field at (r, rec_z)
+template <class A>
+static void fill_rec(const fdw_ctx* c, A& a, float* d_rec, int rec_z)
+{
+    a.rec = d_rec; a.rec_z = rec_z;
+    a.rec_x0 = c->prm.nxb - c->slab.x_off; a.rec_n = c->nx;
+}
+
 // the modelling dialect (mod_main): the weights of the 7x7 Gaussian source and this step's trace row, rec[r - rec_x0] = p(r, rec_z)
 template <class A>
 static int fill_mod(const fdw_ctx* c, A& a, const char* who, float* d_rec, int rec_z)
@@ -422,8 +430,7 @@ static int fill_mod(const fdw_ctx* c, A& a, const char* who, float* d_rec, int r
     if (d_rec && (rec_z < 0 || rec_z >= c->prm.nze)) return fail(FDW_EINVAL, "%s: receiver depth %d outside the grid", who, rec_z);
     for (int i = 0; i < 4; i++)
         for (int j = 0; j < 4; j++) a.gw[i][j] = expf(-(float)(i * i) - (float)(j * j));   // ptsrc.c:53 with exp(float) as g++ resolves it
-    a.rec = d_rec; a.rec_z = rec_z;
-    a.rec_x0 = c->prm.nxb - c->slab.x_off; a.rec_n = c->nx;
+    fill_rec(c, a, d_rec, rec_z);
     return FDW_OK;
 }
 
@@ -508,6 +515,8 @@ static int step_impl(fdw_ctx* c, int mode, const float* d_p, float* d_pp, const 
     else if (mode == FDW_MODE_RECV || mode == FDW_MODE_DD_RECV || mode == FDW_MODE_BACK)
         FDW_TRY(place_receivers(c, "step", mode == FDW_MODE_DD_RECV ? c->prm.nzb : c->prm.nxb, inj_z, &in));
     if (mode == FDW_MODE_MOD) FDW_TRY(fill_mod(c, a, "step", d_rec_row, rec_z));
+    const int kmode = (mode == FDW_MODE_FWD && d_rec_row) ? FDW_MODE_FWD_REC : mode;      // the RTM forward step that records its trace row
+    if (kmode == FDW_MODE_FWD_REC) fill_rec(c, a, d_rec_row, rec_z);
     a.inj = d_inj + in.shift; a.inj_x = in.x; a.inj_z = inj_z; a.inj_n = in.n;
     if (a.r1 <= a.r0) return FDW_OK;
     if (c->nbatch > 1) {      // fdw_shot_batch: shot b = these pointers + b fields, its own gather, its own source row
@@ -522,10 +531,10 @@ static int step_impl(fdw_ctx* c, int mode, const float* d_p, float* d_pp, const 
     hipError_t e;
     if (c->h <= kMaxFastHalfOrder && !c->use_generic) {
         fill_geometry(c, a, a.r1 - a.r0, std::max(c->nbatch, 1));
-        e = launch_step_fast(a, c->h, mode, effective_prefetch(c), s);
+        e = launch_step_fast(a, c->h, kmode, effective_prefetch(c), s);
     } else {
         if (mode >= FDW_MODE_MOD) return fail(FDW_EINVAL, "step: mode %d has no generic-order kernel", mode);
-        e = launch_step_generic(a, c->h, mode, s);
+        e = launch_step_generic(a, c->h, kmode, s);
     }
     if (e != hipSuccess) return fail(FDW_EHIP, "kernel launch failed: %s", hipGetErrorString(e));
     if ((mode == FDW_MODE_RECV || mode == FDW_MODE_BACK) && r1 > c->upd_x1)
@@ -617,8 +626,9 @@ struct Step2Extra {          // what the receiver / imaging variant needs on top
 // mode FWD: d_inj -> {srce[it], srce[it+1]}, inj_x_global / inj_z = source position (inj_x_global < 0: none)
 // mode PLAIN: no taper, no injection
 // mode RECV: d_inj / ex.inj2 -> receiver samples of iterations it / it+1 (nx each), inj_z = gz, imaging with ex.psrc_a/b
+// d_rec (mode FWD only): the trace rows of both steps, rec and rec + nx (FDW_MODE_FWD_REC)
 static int step2_impl(fdw_ctx* c, int mode, const float* d_p, const float* d_pp, const float* d_v2, float* d_out1, float* d_out2, int pp_twice,
-                      const float* d_inj, int inj_x_global, int inj_z, const Step2Extra& ex, hipStream_t s)
+                      const float* d_inj, int inj_x_global, int inj_z, const Step2Extra& ex, hipStream_t s, float* d_rec = nullptr, int rec_z = 0)
 {
     if (c->h != kMaxFastHalfOrder) return fail(FDW_EINVAL, "step2: the two-step kernel is built for order 8 only");
     if (!d_p || !d_pp || !d_v2 || !d_out1 || !d_out2) return fail(FDW_EINVAL, "step2: NULL buffer");
@@ -652,7 +662,9 @@ static int step2_impl(fdw_ctx* c, int mode, const float* d_p, const float* d_pp,
     const int chunks = (rows + xchunk - 1) / xchunk;
     a.nblk = a.nzblk * chunks;
     a.nper = (a.nblk + 7) / 8;
-    hipError_t e = launch_step2(a, c->h, mode, s);
+    const int kmode = (mode == FDW_MODE_FWD && d_rec) ? FDW_MODE_FWD_REC : mode;
+    if (kmode == FDW_MODE_FWD_REC) fill_rec(c, a, d_rec, rec_z);
+    hipError_t e = launch_step2(a, c->h, kmode, s);
     if (e != hipSuccess) return fail(FDW_EHIP, "step2 launch failed: %s", hipGetErrorString(e));
     return even_steps_tail(c, mode, a, s);
 }
@@ -731,6 +743,8 @@ static int stepn_impl(fdw_ctx* c, int mode, const float* d_p, const float* d_pp,
         for (int i = 0; i < kPipeSteps; i++) a.plev[i] = bk->plev[i];
     }
     if (mode == FDW_MODE_MOD) FDW_TRY(fill_mod(c, a, "stepn", d_rec, rec_z));
+    const int kmode = (mode == FDW_MODE_FWD && d_rec) ? FDW_MODE_FWD_REC : mode;      // FWD with d_rec: the trace rows of the pass's four steps
+    if (kmode == FDW_MODE_FWD_REC) fill_rec(c, a, d_rec, rec_z);
     a.inj = d_inj + in.shift; a.inj_x = in.x; a.inj_z = inj_z; a.inj_n = in.n;
     const int ncells = c->pitch / 4, own = 64 - 2 * kPipeSteps;
     a.nstrip = (ncells + own - 1) / own;
@@ -761,7 +775,7 @@ static int stepn_impl(fdw_ctx* c, int mode, const float* d_p, const float* d_pp,
     const int chunks = a.chunks_a + (rows_b + xchunk - 1) / xchunk;
     a.nblk = a.nstrip * chunks;
     a.nper = (a.nblk + 7) / 8;
-    hipError_t e = launch_stepn(a, c->h, mode, s);
+    hipError_t e = launch_stepn(a, c->h, kmode, s);
     if (e != hipSuccess) return fail(FDW_EHIP, "stepn launch failed: %s", hipGetErrorString(e));
     static_assert(kPipeSteps % 2 == 0, "static-row bookkeeping assumes an even number of steps per pass");
     return whole || rr.r1 >= c->upd_x1 || rr.r1b >= c->upd_x1 ? even_steps_tail(c, mode, a, s) : FDW_OK;
@@ -834,38 +848,72 @@ extern "C" int fdw_dev_step4(fdw_ctx* c, const float* d_p, const float* d_pp, co
     return stepn_impl(c, FDW_MODE_FWD, d_p, d_pp, d_v2, d_out1, d_out2, pp_twice, d_srce_it, d_srce_it ? sx : -1, sz, pick_stream(c, stream), rr);
 }
 
-// nsteps reference iterations (R:259-267) over four rotating buffers: pairs of steps through the two-step
-// kernel, an odd last step through the one-step kernel.  On entry buf[*ip], buf[*ipp] are the reference's
-// (d_p, d_pp) BEFORE the first swap; on return they index (d_p, d_pp) after the loop.
-extern "C" int fdw_dev_steps2(fdw_ctx* c, float* const* buf, const float* d_v2, const float* d_srce, int sx, int sz, int it0, int nsteps,
-                              int first_pp_twice, int* ip, int* ipp, void* stream)
+// nsteps reference iterations (R:259-267) over four rotating buffers: kPipeSteps per pass through the wave pipeline, pairs of steps through
+// the two-step kernel, single steps through the one-step kernel, whichever pays.  On entry buf[*ip], buf[*ipp] are the reference's (d_p, d_pp)
+// BEFORE the first swap; on return they index (d_p, d_pp) after the loop.  d_rec: NULL, or the trace rows [it][nx] (fdw_dev_record_steps):
+// the same passes, each through its kernel's recording variant.
+static int steps_loop(fdw_ctx* c, float* const* buf, const float* d_v2, const float* d_srce, int sx, int sz, int gz, float* d_rec, int it0, int nsteps,
+                      int first_pp_twice, int* ip, int* ipp, hipStream_t s)
 {
     if (!c || !buf || !ip || !ipp) return fail(FDW_EINVAL, "NULL argument");
     if (*ip < 0 || *ip > 3 || *ipp < 0 || *ipp > 3 || *ip == *ipp) return fail(FDW_EINVAL, "steps2: bad buffer indices");
-    hipStream_t s = pick_stream(c, stream);
+    const size_t nxs = (size_t)c->nx;
+    if (d_rec && nsteps > 0) {
+        // receiver rows the loop never time-steps (rows >= xlim of this slab): what the reference's d_pp holds there, from the entry fields
+        const int rec_x0 = c->prm.nxb - c->slab.x_off, r0 = std::max({rec_x0, c->upd_x1, 0}), r1 = std::min(rec_x0 + c->nx, c->nxl);
+        const long long rec_bstride = c->nbatch > 1 ? (long long)nxs * c->batch_nt : 0;
+        hipError_t e = launch_record_static(buf[*ip], buf[*ipp], d_rec + (size_t)it0 * nxs, c->pitch, r0, r1 - r0, gz, rec_x0, c->nx, nsteps, c->nbatch,
+                                            (long long)field_elems(c), rec_bstride, s);
+        if (e != hipSuccess) return fail(FDW_EHIP, "static receiver rows: launch failed: %s", hipGetErrorString(e));
+    }
     int k = 0;
     while (k < nsteps) {
         const int twice = (k > 0) || first_pp_twice;
         const float* inj = d_srce ? d_srce + it0 + k : nullptr;
         const int sxx = d_srce ? sx : -1;
+        float* rec = d_rec ? d_rec + (size_t)(it0 + k) * nxs : nullptr;
         int o1, o2;   // the two buffers not holding the current pair
         spare_pair(*ip, *ipp, &o1, &o2);
         if (nsteps - k >= kPipeSteps && pipe_pays(c)) {
-            FDW_TRY(stepn_impl(c, FDW_MODE_FWD, buf[*ipp], buf[*ip], d_v2, buf[o1], buf[o2], twice, inj, sxx, sz, s));
+            FDW_TRY(stepn_impl(c, FDW_MODE_FWD, buf[*ipp], buf[*ip], d_v2, buf[o1], buf[o2], twice, inj, sxx, sz, s, RowRanges{}, rec, gz));
             *ip = o1; *ipp = o2;   // d_p = u^{n+kPipeSteps-1}, d_pp = u^{n+kPipeSteps}
             k += kPipeSteps;
         } else if (nsteps - k >= 2 && two_step_pays(c)) {
             // after the swap the kernel's p is the old d_pp (newest field), its pp the old d_p
-            FDW_TRY(step2_impl(c, FDW_MODE_FWD, buf[*ipp], buf[*ip], d_v2, buf[o1], buf[o2], twice, inj, sxx, sz, Step2Extra{}, s));
+            FDW_TRY(step2_impl(c, FDW_MODE_FWD, buf[*ipp], buf[*ip], d_v2, buf[o1], buf[o2], twice, inj, sxx, sz, Step2Extra{}, s, rec, gz));
             *ip = o1; *ipp = o2;   // d_p = u^{n+1}, d_pp = u^{n+2}
             k += 2;
         } else {
             std::swap(*ip, *ipp);
-            FDW_TRY(step_impl(c, FDW_MODE_FWD, buf[*ip], buf[*ipp], d_v2, 0, c->nxl, twice, inj, sxx, sz, nullptr, nullptr, s));
+            FDW_TRY(step_impl(c, FDW_MODE_FWD, buf[*ip], buf[*ipp], d_v2, 0, c->nxl, twice, inj, sxx, sz, nullptr, nullptr, s, rec, gz));
             k += 1;
         }
     }
     return FDW_OK;
+}
+
+extern "C" int fdw_dev_steps2(fdw_ctx* c, float* const* buf, const float* d_v2, const float* d_srce, int sx, int sz, int it0, int nsteps,
+                              int first_pp_twice, int* ip, int* ipp, void* stream)
+{
+    if (!c) return fail(FDW_EINVAL, "NULL argument");
+    return steps_loop(c, buf, d_v2, d_srce, sx, sz, 0, nullptr, it0, nsteps, first_pp_twice, ip, ipp, pick_stream(c, stream));
+}
+
+// the receiver column of a recorded gather: one the forward loop time-steps (R:83-87: j < zlim)
+static int check_record_depth(const fdw_ctx* c, int gz)
+{
+    if (c->prm.dialect != FDW_DIALECT_RTM) return fail(FDW_ESTATE, "trace recording belongs to the RTM dialect (the sibling's has fdw_model_shot)");
+    if (gz < 0 || gz >= c->zlim) return fail(FDW_EINVAL, "receiver depth %d outside the time-stepped columns [0,%d)", gz, c->zlim);
+    return FDW_OK;
+}
+
+extern "C" int fdw_dev_record_steps(fdw_ctx* c, float* const* d_buf, const float* d_v2, const float* d_srce, int sx, int sz, int gz, float* d_rec,
+                                    int it0, int nsteps, int first_pp_twice, int* ip, int* ipp, void* stream)
+{
+    if (!c || !d_rec) return fail(FDW_EINVAL, "NULL argument");
+    if (it0 < 0) return fail(FDW_EINVAL, "it0=%d", it0);
+    FDW_TRY(check_record_depth(c, gz));
+    return steps_loop(c, d_buf, d_v2, d_srce, sx, sz, gz, d_rec, it0, nsteps, first_pp_twice, ip, ipp, pick_stream(c, stream));
 }
 
 // ksteps-cycle of the slab decomposition in one call: step j (1-based, j = j0 .. j0+nsteps-1) updates the
@@ -1004,11 +1052,11 @@ static int upload_source(fdw_ctx* c, const float* srce, int n)
 }
 
 // fd_forward's loop body R:259-267 for nsteps iterations over the context's four field buffers (pairs of steps go
-// through the two-step kernel where it pays); *ip / *ipp index (d_p, d_pp) before the loop and after it.
-static int forward_loop(fdw_ctx* c, int* ip, int* ipp, int sx, int sz, int nsteps)
+// through the two-step kernel where it pays); *ip / *ipp index (d_p, d_pp) before the loop and after it.  d_rec: trace rows [nt][nx] at gz.
+static int forward_loop(fdw_ctx* c, int* ip, int* ipp, int sx, int sz, int nsteps, int gz = 0, float* d_rec = nullptr)
 {
     FDW_RANGE("fdw: forward loop (fd_forward)");
-    int rc = fdw_dev_steps2(c, c->fld, c->d_v2, c->d_srce, sx, sz, 0, nsteps, 0, ip, ipp, c->stream);
+    int rc = steps_loop(c, c->fld, c->d_v2, c->d_srce, sx, sz, gz, d_rec, 0, nsteps, 0, ip, ipp, c->stream);
     if (rc) return rc;
     if (nsteps > 0) return fdw_dev_taper_finalize(c, c->fld[*ip], c->stream);   // the T() d_p still owes (R:285 downloads the damped d_p)
     return FDW_OK;
@@ -1202,6 +1250,53 @@ extern "C" int fdw_shot(fdw_ctx* c, const float* v2, int sx, int sz, int gz, con
     if (!v2) return fail(FDW_EINVAL, "NULL argument");
     if (c) c->v2_resident = false;
     return shot_impl(c, v2, sx, sz, gz, srce, d_obs, imloc, P, PP);
+}
+
+// ------------------------------------------------------------------------------------------------
+// recorded shot gathers of the RTM dialect (the data rtm_code migrates, R:420-424)
+// ------------------------------------------------------------------------------------------------
+// d_rec [nshots][nt][nx] -> data [nshots][nx][nt] (the layout of rtm_code's datfile; fd_back reads d_obs[ix][nt-1-it], R:328)
+static int gathers_to_host(fdw_ctx* c, const float* d_rec, int nshots, float* data)
+{
+    const size_t n = (size_t)c->nx * c->prm.nt * nshots;
+    if (n == 0) return FDW_OK;
+    FDW_TRY(ensure_cap(&c->d_raw, &c->raw_cap, n));
+    hipError_t e = launch_gather_transpose(d_rec, c->d_raw, c->prm.nt, c->nx, nshots, c->stream);
+    if (e != hipSuccess) return fail(FDW_EHIP, "gather transposition launch failed: %s", hipGetErrorString(e));
+    HIP_TRY(hipMemcpyAsync(data, c->d_raw, n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    return FDW_OK;
+}
+
+// fd_forward from rest (R:496-497, R:259-267) recording data[ix][it] = d_pp(nxb + ix, gz) at the end of iteration it.  v2 == nullptr: the
+// squared model already resident in c->d_v2 (fdw_dev_extendvel_linear).
+static int record_impl(fdw_ctx* c, const float* v2, int sx, int sz, int gz, const float* srce, float* data, float* P, float* PP)
+{
+    if (!c || !srce || !data) return fail(FDW_EINVAL, "NULL argument");
+    FDW_TRY(check_record_depth(c, gz));
+    if (!is_full_grid(c)) return fail(FDW_EINVAL, "fdw_record_shot needs a full-grid context");
+    if (c->nx <= 0) return fail(FDW_EINVAL, "no receiver rows");
+    HIP_TRY(hipSetDevice(c->device));
+    const int nt = c->prm.nt;
+    FDW_TRY(ensure_work_buffers(c, 4, false));
+    FDW_TRY(ensure_cap(&c->d_rec, &c->rec_cap, (size_t)c->nx * nt));
+    HIP_TRY(hipMemsetAsync(c->fld[0], 0, field_elems(c) * sizeof(float), c->stream));
+    HIP_TRY(hipMemsetAsync(c->fld[1], 0, field_elems(c) * sizeof(float), c->stream));
+    if (v2) FDW_TRY(upload_rows(c, c->d_v2, v2, c->stream));
+    FDW_TRY(upload_source(c, srce, nt));
+    int ip = 0, ipp = 1;
+    FDW_TRY(forward_loop(c, &ip, &ipp, sx, sz, nt, gz, c->d_rec));
+    FDW_TRY(gathers_to_host(c, c->d_rec, 1, data));
+    if (P) FDW_TRY(download_rows(c, P, c->fld[ip], c->stream));
+    if (PP) FDW_TRY(download_rows(c, PP, c->fld[ipp], c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return FDW_OK;
+}
+
+extern "C" int fdw_record_shot(fdw_ctx* c, const float* v2, int sx, int sz, int gz, const float* srce, float* data, float* P, float* PP)
+{
+    if (!v2) return fail(FDW_EINVAL, "NULL argument");
+    if (c) c->v2_resident = false;
+    return record_impl(c, v2, sx, sz, gz, srce, data, P, PP);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1849,6 +1944,32 @@ struct BatchScope {      // the context's single-shot buffers step aside for the
 };
 }  // namespace
 
+// the batch's squared models into b_v2: host-given (v2_all [nshots][nxe][nze]) or the border models of draws [draw_offset + b T, ...) on the
+// resident interior model (the shots' draws are consecutive in the stream: one launch generates them all)
+static int batch_models(fdw_ctx* c, int nshots, const float* v2_all, unsigned long long draw_offset)
+{
+    hipStream_t s = c->stream;
+    const long long draws = fdw_border_draws(c->nx, c->nz, c->prm.nxb, c->prm.nzb);
+    const size_t ne = (size_t)c->prm.nxe * c->prm.nze, fe = field_elems(c);
+    if (!v2_all) {
+        HIP_TRY(hipStreamSynchronize(s));                     // a larger draw buffer replaces one the stream may still be reading
+        FDW_TRY(ensure_draws(c, draws * nshots));
+        hipError_t e = launch_rand_stream(base_at(kGlibcDiscard + draw_offset), c->d_jump, draws * nshots, c->d_draws, s);
+        if (e != hipSuccess) return fail(FDW_EHIP, "rand_stream launch failed: %s", hipGetErrorString(e));
+    }
+    for (int b = 0; b < nshots; b++) {
+        if (v2_all) {
+            HIP_TRY(hipMemcpy2DAsync(c->b_v2 + b * fe, (size_t)c->pitch * sizeof(float), v2_all + b * ne, (size_t)c->prm.nze * sizeof(float),
+                                     (size_t)c->prm.nze * sizeof(float), c->nxl, hipMemcpyHostToDevice, s));
+        } else {
+            BorderArgs ba{c->d_vp, c->d_draws + (size_t)b * draws, nullptr, c->b_v2 + b * fe, c->nx, c->nz, c->prm.nxb, c->prm.nzb, c->pitch};
+            hipError_t e = launch_extendvel(ba, s);
+            if (e != hipSuccess) return fail(FDW_EHIP, "border model launch failed: %s", hipGetErrorString(e));
+        }
+    }
+    return FDW_OK;
+}
+
 extern "C" int fdw_shot_batch(fdw_ctx* c, int nshots, const float* v2_all, unsigned long long draw_offset, int sx0, int dsx, int sz, int gz,
                               const float* srce, const float* d_obs, float* imloc)
 {
@@ -1878,22 +1999,7 @@ extern "C" int fdw_shot_batch(fdw_ctx* c, int nshots, const float* v2_all, unsig
     if (rc || (rc = upload_source(c, srce, nt))) return rc;
     hipStream_t s = c->stream;
     if ((rc = gathers_to_device(c, d_obs, c->b_dobs, nshots))) return rc;      // [shot][nx][nt] -> [shot][nt][nx]
-    if (!v2_all) {      // the shots' draws are consecutive in the stream: one launch generates them all
-        HIP_TRY(hipStreamSynchronize(s));                     // a larger draw buffer replaces one the stream may still be reading
-        if ((rc = ensure_draws(c, draws * nshots))) return rc;
-        hipError_t e = launch_rand_stream(base_at(kGlibcDiscard + draw_offset), c->d_jump, draws * nshots, c->d_draws, s);
-        if (e != hipSuccess) return fail(FDW_EHIP, "rand_stream launch failed: %s", hipGetErrorString(e));
-    }
-    for (int b = 0; b < nshots; b++) {
-        if (v2_all) {
-            HIP_TRY(hipMemcpy2DAsync(c->b_v2 + b * fe, (size_t)c->pitch * sizeof(float), v2_all + b * ne, (size_t)c->prm.nze * sizeof(float),
-                                     (size_t)c->prm.nze * sizeof(float), c->nxl, hipMemcpyHostToDevice, s));
-        } else {
-            BorderArgs ba{c->d_vp, c->d_draws + (size_t)b * draws, nullptr, c->b_v2 + b * fe, c->nx, c->nz, c->prm.nxb, c->prm.nzb, c->pitch};
-            hipError_t e = launch_extendvel(ba, s);
-            if (e != hipSuccess) return fail(FDW_EHIP, "border model launch failed: %s", hipGetErrorString(e));
-        }
-    }
+    if ((rc = batch_models(c, nshots, v2_all, draw_offset))) return rc;
     for (int i = 0; i < 8; i++) HIP_TRY(hipMemsetAsync(c->bfld[i], 0, fe * nshots * sizeof(float), s));    // R:496-497, R:511-514
     HIP_TRY(hipMemsetAsync(c->b_img, 0, fe * nshots * sizeof(float), s));
     for (int b = 0; b < nshots; b++)
@@ -1912,6 +2018,47 @@ extern "C" int fdw_shot_batch(fdw_ctx* c, int nshots, const float* v2_all, unsig
     for (int b = 0; b < nshots; b++)
         HIP_TRY(hipMemcpy2DAsync(imloc + b * ni, (size_t)c->nz * sizeof(float), c->b_img + b * fe + (size_t)c->prm.nxb * c->pitch + c->prm.nzb,
                                  (size_t)c->pitch * sizeof(float), (size_t)c->nz * sizeof(float), c->nx, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return FDW_OK;
+}
+
+// `nshots` recorded gathers (fdw_record_shot) through one launch per time step for the whole batch where batch_ok holds, one shot after the
+// other otherwise; models as fdw_shot_batch takes them.  data [nshots][nx][nt].
+extern "C" int fdw_record_shot_batch(fdw_ctx* c, int nshots, const float* v2_all, unsigned long long draw_offset, int sx0, int dsx, int sz, int gz,
+                                     const float* srce, float* data)
+{
+    if (!c || !srce || !data) return fail(FDW_EINVAL, "NULL argument");
+    if (nshots < 1) return fail(FDW_EINVAL, "nshots=%d", nshots);
+    FDW_TRY(check_record_depth(c, gz));
+    if (!is_full_grid(c)) return fail(FDW_EINVAL, "fdw_record_shot_batch needs a full-grid context");
+    if (c->nx <= 0) return fail(FDW_EINVAL, "no receiver rows");
+    if (!v2_all && !c->model_resident) return fail(FDW_ESTATE, "no model: pass v2_all or call fdw_model_resident first");
+    const int nt = c->prm.nt;
+    const size_t ne = (size_t)c->prm.nxe * c->prm.nze, ng = (size_t)c->nx * nt, fe = field_elems(c);
+    const int sx_last = sx0 + (nshots - 1) * dsx;
+    if (std::min(sx0, sx_last) < 0 || std::max(sx0, sx_last) >= c->prm.nxe || std::max(sx0, sx_last) >= c->upd_x1)
+        return fail(FDW_EINVAL, "source rows %d..%d leave the rows the reference time-steps (< %d)", sx0, sx_last, c->upd_x1);
+    HIP_TRY(hipSetDevice(c->device));
+    const long long draws = fdw_border_draws(c->nx, c->nz, c->prm.nxb, c->prm.nzb);
+    auto one_by_one = [&] {
+        for (int b = 0; b < nshots; b++) {
+            if (!v2_all) FDW_TRY(fdw_dev_extendvel_linear(c, draw_offset + (unsigned long long)b * draws, nullptr));
+            FDW_TRY(record_impl(c, v2_all ? v2_all + b * ne : nullptr, sx0 + b * dsx, sz, gz, srce, data + b * ng, nullptr, nullptr));
+        }
+        return (int)FDW_OK;
+    };
+    if (nshots == 1 || !batch_ok(c)) return one_by_one();
+    int rc;
+    if ((rc = ensure_batch_buffers(c, nshots, true)) == FDW_ENOMEM) return one_by_one();
+    if (rc || (rc = upload_source(c, srce, nt)) || (rc = batch_models(c, nshots, v2_all, draw_offset))) return rc;
+    hipStream_t s = c->stream;
+    for (int i = 0; i < 2; i++) HIP_TRY(hipMemsetAsync(c->bfld[i], 0, fe * nshots * sizeof(float), s));    // R:496-497
+    {
+        BatchScope scope(c, nshots, dsx);
+        int ip = 0, ipp = 1;
+        if ((rc = steps_loop(c, c->fld, c->d_v2, c->d_srce, sx0, sz, gz, c->d_dobs, 0, nt, 0, &ip, &ipp, s))) return rc;      // d_dobs: the batch's [shot][nt][nx]
+    }
+    if ((rc = gathers_to_host(c, c->b_dobs, nshots, data))) return rc;
     HIP_TRY(hipStreamSynchronize(s));
     return FDW_OK;
 }

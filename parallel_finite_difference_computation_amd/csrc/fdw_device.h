@@ -419,4 +419,26 @@ __device__ __forceinline__ void f4_store_arr(__amdgpu_buffer_rsrc_t rs, unsigned
     asm volatile("s_nop 1" : : "v"(t) : "memory");
 }
 
+// ---- trace recording of the RTM dialect's forward loop (fdw_dev_record_steps) ----------------------------------------------------
+// One sample per receiver row and step, rec[r - rec_x0] = the new field at (r, rec_z), stored by the one lane that owns column rec_z.  The
+// store is unconditional in the march: lanes and rows that record nothing pass kLaneOff and the descriptor's range check drops them (a
+// 32-bit store: the data hazard of f4_store_arr concerns 96- and 128-bit stores only).
+__device__ __forceinline__ unsigned rec_offset(bool lane_rec, int r, int rec_x0, int rec_n)
+{
+    const unsigned rr = (unsigned)(r - rec_x0);
+    return (lane_rec && rr < (unsigned)rec_n) ? rr * 4u : kLaneOff;
+}
+// element e (wave-uniform) of a lane's float4, as selects between values: a select between the ADDRESSES of the elements would keep the
+// float4 in scratch memory
+__device__ __forceinline__ float f4_pick(const f4& a, int e)
+{
+    const float x0 = a.v[0], x1 = a.v[1], x2 = a.v[2], x3 = a.v[3];
+    const float lo = (e & 1) ? x1 : x0, hi = (e & 1) ? x3 : x2;
+    return (e & 2) ? hi : lo;
+}
+__device__ __forceinline__ void f1_store_arr(__amdgpu_buffer_rsrc_t rs, unsigned voff_bytes, float v)
+{
+    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), rs, voff_bytes, 0, 2);
+}
+
 }  // namespace fdw

@@ -14,6 +14,7 @@ enum {
     FDW_MODE_BACK = 7,   // one whole backward iteration of fd_back in a single pass: source-field step + receiver step + imaging (R:317-329)
     FDW_MODE_BACK4 = 9,  // wave-pipeline kernel only: four whole iterations of fd_back in one pass of an eight-wave workgroup (source + receiver fields)
     FDW_MODE_PLAIN_ALL = 8, // wave-pipeline kernel only: PLAIN with all four time levels stored (source field of the backward loop)
+    FDW_MODE_FWD_REC = 10, // launchers only: FWD + the trace sample of every step on the receiver line (fdw_dev_record_steps; StepArgs / Step2Args rec*)
     FDW_MODE_DD_RECV = 6 // its receiver pass (rtm_main.cpp:197-220) + img += stored source field * CURRENT receiver field (rtm_main.cpp:224-230)
 };
 
@@ -53,7 +54,7 @@ struct StepArgs {
     // FDW_MODE_MOD only: cz holds the UNSCALED weights, the spacings come separately (fd.c:24-36 scales per term)
     float dx2inv, dz2inv;
     float gw[4][4];        // expf(-(i*i + j*j)): the 7x7 Gaussian point source of ptsrc.c:49-55
-    float* rec;            // this step's trace samples [rec_n]: rec[r - rec_x0] = p(r, rec_z)   (mod_main.cpp:155-157)
+    float* rec;            // this step's trace samples [rec_n]: rec[r - rec_x0] = p(r, rec_z)   (mod_main.cpp:155-157); FWD_REC: the NEW field
     int rec_z, rec_x0, rec_n;
     // batch of independent shots on one geometry (gridDim.y = shots; 0 / 1 = a single shot): shot b works on field pointers + b * bstride,
     // samples inj + b * inj_bstride, source row inj_x + b * inj_dx
@@ -94,7 +95,7 @@ struct Step2Args {
     // pipeline kernel in FDW_MODE_MOD only (see StepArgs): unscaled weights in cz, spacings, Gaussian source weights, trace samples
     float dx2inv, dz2inv;
     float gw[4][4];
-    float* rec;            // [steps of the pass][rec_n]: wave k writes row k
+    float* rec;            // [steps of the pass][rec_n]: wave k writes row k (MOD: its p field; FWD_REC, also the two-step kernel: its new row)
     int rec_z, rec_x0, rec_n;
     // pipeline kernel, backward loop (fd_back, R:302-339), two passes per kPipeSteps iterations:
     //   FDW_MODE_PLAIN_ALL  the source field: like PLAIN, but EVERY wave stores its time level (wave 0 -> lvl0, wave 1 -> lvl1, then out1, out2),
@@ -124,6 +125,9 @@ hipError_t launch_taper_finalize(float* f, const float* taperz, const float* txf
                                  int tz_x1, hipStream_t s);
 hipError_t launch_selftest(const float* src, float* out, hipStream_t s);
 // receiver rows the reference injects and images but never time-steps (truncated launch extents with a narrow x border): see fdw_static_rows_kernel
+// trace samples of receiver rows the loop never time-steps: see fdw_record_static_kernel
+hipError_t launch_record_static(const float* p0, const float* pp0, float* rec, int pitch, int row0, int nrows, int gz, int rec_x0, int rec_n, int nsteps,
+                               int nbatch, long long bstride, long long rec_bstride, hipStream_t s);
 hipError_t launch_static_rows(float* pp, const float* psrc, float* img, const float* samples, int pitch, int row0, int nrows, int gz,
                               int img_z0, int img_z1, hipStream_t s);
 hipError_t launch_image_laplacian(const float* d_img, float* d_out, int nx, int nz, float dx, float dz, hipStream_t s);

@@ -24,6 +24,7 @@ namespace fdw {
 //   LAPONLY store the Laplacian itself into a.pp (stencil_code path, S:110-135); no update
 //   DD      arithmetic of the CPU-serial sibling's fd_step (single accumulator, per-term scaling) + one trace sample per row
 //   PF      software prefetch distance in rows
+//   REC     trace recording of the RTM dialect's forward loop: the new field at column rec_z of every receiver row (fdw_step_rec_kernel)
 // block = 256 threads = 4 independent waves (no LDS, no barrier).
 //
 // ONE code path for every tile.  Every global load of the march is unconditional (addresses are
@@ -48,7 +49,7 @@ struct ShotView {
     float* rec;
 };
 
-template <int H, bool TAPER, int INJ, bool IMG, bool LAPONLY, int PF, bool DD = false, bool BACK = false, int NUM = 0>
+template <int H, bool TAPER, int INJ, bool IMG, bool LAPONLY, int PF, bool DD = false, bool BACK = false, int NUM = 0, bool REC = false>
 __device__ __forceinline__ void march(const StepArgs& a, const ShotView& sv, const int lane, const int zs, const int xa, const int xe)
 {
     // BACK: one whole backward iteration of fd_back (R:317-329) in a single pass: the source field is reconstructed in a second
@@ -81,6 +82,8 @@ __device__ __forceinline__ void march(const StepArgs& a, const ShotView& sv, con
     const bool rec_here = DD && (a.rec != nullptr) && (a.rec_z >= zs) && (a.rec_z < zs + 256);
     const CoefPairs<H> cpk = coef_pairs<H>(a.cx, a.cz);
     const v2f c0p = v2f{a.c0, a.c0};                          // FAST numerics: weight of the centre point
+    // REC: the lane whose float4 holds column rec_z records element rec_z & 3 of its new row (strips do not overlap: one lane in the grid)
+    const bool rec_lane = REC && (z0 >> 2) == (a.rec_z >> 2);
 
     // per-lane column masks and damping factors
     bool mlap[4], mupd[4], znc[4], znh[4], ihit[4];
@@ -312,6 +315,7 @@ __device__ __forceinline__ void march(const StepArgs& a, const ShotView& sv, con
                 if constexpr (IMG) f4_store(sv.img + (size_t)r * pitch, voff, imr);
                 if constexpr (BACK) f4_store(sv.fpp + (size_t)r * pitch, voff, fres);
             }
+            if constexpr (REC) f1_store_arr(array_rsrc(sv.rec, (unsigned)a.rec_n * 4u), rec_offset(rec_lane, r, a.rec_x0, a.rec_n), f4_pick(res, a.rec_z & 3));
 
             // ---- refill the slots this row just freed (look-ahead loads) ----------------------
             ring[U] = load_p(r - H + R);
@@ -378,6 +382,35 @@ __global__ __launch_bounds__(256) void fdw_step_kernel(const StepArgs a)
     march<H, TAPER, INJ, IMG, LAPONLY, PF, DD, BACK, NUM>(a, sv, lane, zs, xa, xe);
 }
 
+// the forward step (FDW_MODE_FWD) that also records its trace samples (FDW_MODE_FWD_REC; batched like the others: rec + shot * rec_bstride).
+// Its own copy of fdw_step_kernel's tile placement: routing both kernels through one inlined function changes the register allocation
+// of the existing instantiations.
+template <int H, int PF, int NUM>
+__global__ __launch_bounds__(256) void fdw_step_rec_kernel(const StepArgs a)
+{
+    const int shot = blockIdx.y;
+    const long long o = shot * a.bstride;
+    const ShotView sv{a.p + o, a.pp + o, (a.out ? a.out : a.pp) + o, a.v2 + shot * a.v2_bstride, a.psrc + o, a.fpp + o, a.img + o, a.inj + shot * a.inj_bstride,
+                      a.inj_x + shot * a.inj_dx, a.rec + shot * a.rec_bstride};
+    const int lane = threadIdx.x & 63;
+    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+
+    const int bid = blockIdx.x;
+    const int L = (bid & 7) * a.nper + (bid >> 3);
+    if (L >= a.nblk) return;
+    const int zb = L % a.nzblk;
+    const int xb = L / a.nzblk;
+    const int wz = a.wz;
+    const int strip = zb * wz + (w & (wz - 1));
+    const int chunk = xb * (4 / wz) + (w / wz);
+    const int zs = strip * 256;
+    if (zs >= a.pitch) return;
+    const int xa = a.r0 + chunk * a.xchunk;
+    const int xe = min(xa + a.xchunk, a.r1);
+    if (xa >= xe) return;
+    march<H, true, 1, false, false, PF, false, false, NUM, true>(a, sv, lane, zs, xa, xe);
+}
+
 #if FDW_TU == 0
 // ------------------------------------------------------------------------------------------------
 // generic-order kernel: any even order up to FDW_MAX_ORDER, one thread per point, every tap from
@@ -391,8 +424,8 @@ __device__ __forceinline__ float generic_p(const StepArgs& a, int row, int z, bo
     return v;
 }
 
-__global__ __launch_bounds__(256) void fdw_generic_kernel(const StepArgs a, int h, int taper, int injmode,
-                                                          int img, int laponly)
+template <bool REC>
+__device__ __forceinline__ void generic_point(const StepArgs& a, int h, int taper, int injmode, int img, int laponly)
 {
     const int z = blockIdx.x * 256 + threadIdx.x;
     const int r = a.r0 + blockIdx.y;
@@ -435,7 +468,19 @@ __global__ __launch_bounds__(256) void fdw_generic_kernel(const StepArgs a, int 
         }
     }
     a.pp[k] = out;
+    if (REC && z == a.rec_z && (unsigned)(r - a.rec_x0) < (unsigned)a.rec_n) a.rec[r - a.rec_x0] = out;      // this step's trace sample
     if (img) a.img[k] = a.img[k] + a.psrc[k] * out;
+}
+
+__global__ __launch_bounds__(256) void fdw_generic_kernel(const StepArgs a, int h, int taper, int injmode,
+                                                          int img, int laponly)
+{
+    generic_point<false>(a, h, taper, injmode, img, laponly);
+}
+// FDW_MODE_FWD_REC: the forward step and its trace sample (one thread per point: no march loop to keep free of branches)
+__global__ __launch_bounds__(256) void fdw_generic_rec_kernel(const StepArgs a, int h)
+{
+    generic_point<true>(a, h, 1, 1, 0, 0);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -491,6 +536,19 @@ __global__ __launch_bounds__(256) void fdw_static_rows_kernel(float* pp, const f
     if (z >= img_z0 && z < img_z1) img[k] = img[k] + psrc[k] * v;
 }
 
+// Trace samples of receiver rows the loop never time-steps (compat extents, rows >= xlim): the reference's d_pp there holds, at the end of
+// iteration it0 + k, what its d_p held before the loop for even k and what its d_pp held for odd k (the pointers swap every iteration,
+// R:260-262, and no kernel writes those rows).  rec -> the row of iteration it0; blockIdx.y = shot of a batch.
+__global__ __launch_bounds__(256) void fdw_record_static_kernel(const float* p0, const float* pp0, float* rec, int pitch, int row0, int nrows, int gz,
+                                                                int rec_x0, int rec_n, int nsteps, long long bstride, long long rec_bstride)
+{
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= nrows * nsteps) return;
+    const int k = t / nrows, row = row0 + t % nrows;
+    const long long b = blockIdx.y;
+    rec[b * rec_bstride + (long long)k * rec_n + (row - rec_x0)] = ((k & 1) ? pp0 : p0)[b * bstride + (long long)row * pitch + gz];
+}
+
 __global__ void fdw_selftest_kernel(const float* src, float* out)
 {
     const int t = threadIdx.x;
@@ -521,6 +579,7 @@ static hipError_t launch_fast_hp(const StepArgs& a, int mode, hipStream_t s)
     case FDW_MODE_RECV:  hipLaunchKernelGGL((fdw_step_kernel<H, true, 2, true, false, PF>), grid, block, 0, s, a); break;
     case FDW_MODE_LAP:   hipLaunchKernelGGL((fdw_step_kernel<H, false, 0, false, true, PF>), grid, block, 0, s, a); break;
     case FDW_MODE_BACK:  hipLaunchKernelGGL((fdw_step_kernel<H, true, 2, true, false, PF, false, true>), grid, block, 0, s, a); break;
+    case FDW_MODE_FWD_REC: hipLaunchKernelGGL((fdw_step_rec_kernel<H, PF, 0>), grid, block, 0, s, a); break;
     default: return hipErrorInvalidValue;
     }
     return hipGetLastError();
@@ -608,6 +667,7 @@ static hipError_t launch_fastnum_h(const StepArgs& a, int mode, hipStream_t s)
     case FDW_MODE_RECV:  hipLaunchKernelGGL((fdw_step_kernel<H, true, 2, true, false, 2, false, false, 1>), grid, block, 0, s, a); break;
     case FDW_MODE_LAP:   hipLaunchKernelGGL((fdw_step_kernel<H, false, 0, false, true, 2, false, false, 1>), grid, block, 0, s, a); break;
     case FDW_MODE_BACK:  hipLaunchKernelGGL((fdw_step_kernel<H, true, 2, true, false, 2, false, true, 1>), grid, block, 0, s, a); break;
+    case FDW_MODE_FWD_REC: hipLaunchKernelGGL((fdw_step_rec_kernel<H, 2, 1>), grid, block, 0, s, a); break;
     default: return hipErrorInvalidValue;
     }
     return hipGetLastError();
@@ -629,6 +689,10 @@ hipError_t launch_step_generic(const StepArgs& a, int h, int mode, hipStream_t s
 {
     if (a.r1 <= a.r0) return hipSuccess;
     const dim3 grid((a.pitch + 255) / 256, a.r1 - a.r0), block(256);
+    if (mode == FDW_MODE_FWD_REC) {
+        hipLaunchKernelGGL(fdw_generic_rec_kernel, grid, block, 0, s, a, h);
+        return hipGetLastError();
+    }
     const int taper = (mode == FDW_MODE_FWD || mode == FDW_MODE_RECV);
     const int inj = (mode == FDW_MODE_FWD) ? 1 : (mode == FDW_MODE_RECV ? 2 : 0);
     hipLaunchKernelGGL(fdw_generic_kernel, grid, block, 0, s, a, h, taper, inj, mode == FDW_MODE_RECV ? 1 : 0,
@@ -732,6 +796,15 @@ hipError_t launch_static_rows(float* pp, const float* psrc, float* img, const fl
 {
     if (nrows <= 0) return hipSuccess;
     hipLaunchKernelGGL(fdw_static_rows_kernel, dim3((pitch + 255) / 256, nrows), dim3(256), 0, s, pp, psrc, img, samples, pitch, row0, gz, img_z0, img_z1);
+    return hipGetLastError();
+}
+
+hipError_t launch_record_static(const float* p0, const float* pp0, float* rec, int pitch, int row0, int nrows, int gz, int rec_x0, int rec_n, int nsteps,
+                               int nbatch, long long bstride, long long rec_bstride, hipStream_t s)
+{
+    if (nrows <= 0 || nsteps <= 0) return hipSuccess;
+    hipLaunchKernelGGL(fdw_record_static_kernel, dim3((nrows * nsteps + 255) / 256, nbatch > 1 ? nbatch : 1), dim3(256), 0, s, p0, pp0, rec, pitch, row0, nrows,
+                       gz, rec_x0, rec_n, nsteps, bstride, rec_bstride);
     return hipGetLastError();
 }
 

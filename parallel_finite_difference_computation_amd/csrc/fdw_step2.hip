@@ -20,8 +20,10 @@ namespace fdw {
 // u^{n+2} -> out2 (four field buffers rotate).  Non-owned lanes are predicated off by the buffer
 // descriptor's range check (per-row SRSRC, offset 0xFFFFFFF0), so the stores are unconditional too.
 // Arithmetic per point and per step is exactly the one-step kernel's (same helpers), hence bit-identical.
+// REC (FDW_MODE_FWD_REC): the two new rows' samples at column rec_z go to rec (step 1) and rec + rec_n (step 2), from owned lanes and the
+// tile's own rows only -- the same conditions as the field stores, so every sample is written once.
 // ------------------------------------------------------------------------------------------------
-template <int H, bool TAPER, int INJ, bool IMG, int PF, int NUM = 0>
+template <int H, bool TAPER, int INJ, bool IMG, int PF, int NUM = 0, bool REC = false>
 __device__ __forceinline__ void march2(const Step2Args& a, const int lane, const int cs, const int xa, const int xe, f4* stash)
 {
     constexpr int R = ((2 * H + PF + PF - 1) / PF) * PF;   // ring turns == unroll factor (10 for H=4, PF=2)
@@ -47,6 +49,8 @@ __device__ __forceinline__ void march2(const Step2Args& a, const int lane, const
     if (INJ == 2) inj_here = inj_cols && (a.inj_x < xe + H) && (a.inj_x + a.inj_n > xa - H);
     const float inj0 = (INJ == 1 && inj_here) ? sload(a.inj, 0) : 0.0f;
     const float inj1 = (INJ == 1 && inj_here) ? sload(a.inj, 1) : 0.0f;
+    const bool rec_lane = REC && own && (cell == (a.rec_z >> 2));
+    auto rs_rec = [&] { return array_rsrc(a.rec, 2u * (unsigned)a.rec_n * 4u); };       // step 1's row, then step 2's
 
     bool mlap[4], mupd[4], znc[4], ihit[4];
     float tzc[4];
@@ -168,6 +172,7 @@ __device__ __forceinline__ void march2(const Step2Args& a, const int lane, const
                 }
             }
             f4_store_rsrc(a.out1 + rowoff(s), row_bytes, soff1, u1);
+            if constexpr (REC) f1_store_arr(rs_rec(), rec_offset(rec_lane && live && (s >= xa) && (s < xe), s, a.rec_x0, a.rec_n), f4_pick(u1, a.rec_z & 3));
             if (wave_tap) taper_row(u1, s);                              // as "p" of step 2 it is damped once
             ring2[U] = u1;                                               // row s of u^{n+1}
             stash[((m & 7) << 6) + lane] = qv2[Q];                       // v2(s) is needed again H rows later: park it in LDS
@@ -210,6 +215,8 @@ __device__ __forceinline__ void march2(const Step2Args& a, const int lane, const
                     }
                 }
                 f4_store_rsrc(a.out2 + rowoff(r), row_bytes, soff2, u2);
+                if constexpr (REC)
+                    f1_store_arr(rs_rec(), rec_offset(rec_lane && live && (r >= xa), r, a.rec_x0, a.rec_n) + (unsigned)a.rec_n * 4u, f4_pick(u2, a.rec_z & 3));
                 if constexpr (IMG) {
                     // imaging condition of BOTH iterations at row r (kernel_img, R:133-144):  img += psrc_a * u^{n+1}, then
                     // img += psrc_b * u^{n+2}.  u^{n+1}(r) is ring2's centre row; where the image is extracted (interior) no
@@ -241,8 +248,8 @@ __device__ __forceinline__ void march2(const Step2Args& a, const int lane, const
         static_for<R>([&](auto UU) { row_step(mb, UU); });
 }
 
-template <int H, bool TAPER, int INJ, bool IMG, int PF, int NUM = 0>
-__global__ __launch_bounds__(256, IMG ? 3 : (TAPER ? 4 : 2)) void fdw_step2_kernel(const Step2Args a)
+template <int H, bool TAPER, int INJ, bool IMG, int PF, int NUM, bool REC>
+__device__ __forceinline__ void step2_tile(const Step2Args& a)
 {
     const int lane = threadIdx.x & 63;
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -258,7 +265,20 @@ __global__ __launch_bounds__(256, IMG ? 3 : (TAPER ? 4 : 2)) void fdw_step2_kern
     if (xa >= xe) return;
     // per-wave LDS slab: 8 rows x 64 lanes x 16 B for the v2 rows waiting between step 1 (row s) and step 2 (row s-H)
     __shared__ f4 v2_stash[4][8 * 64];
-    march2<H, TAPER, INJ, IMG, PF, NUM>(a, lane, strip * 60 - 2, xa, xe, v2_stash[w]);
+    march2<H, TAPER, INJ, IMG, PF, NUM, REC>(a, lane, strip * 60 - 2, xa, xe, v2_stash[w]);
+}
+
+template <int H, bool TAPER, int INJ, bool IMG, int PF, int NUM = 0>
+__global__ __launch_bounds__(256, IMG ? 3 : (TAPER ? 4 : 2)) void fdw_step2_kernel(const Step2Args a)
+{
+    step2_tile<H, TAPER, INJ, IMG, PF, NUM, false>(a);
+}
+
+// FDW_MODE_FWD_REC: the forward pass that also records both steps' trace samples
+template <int NUM>
+__global__ __launch_bounds__(256, 4) void fdw_step2_rec_kernel(const Step2Args a)
+{
+    step2_tile<4, true, 1, false, 2, NUM, true>(a);
 }
 
 hipError_t launch_step2(const Step2Args& a, int h, int mode, hipStream_t s)
@@ -271,6 +291,7 @@ hipError_t launch_step2(const Step2Args& a, int h, int mode, hipStream_t s)
         case FDW_MODE_FWD:   hipLaunchKernelGGL((fdw_step2_kernel<4, true, 1, false, 2, 1>), grid, block, 0, s, a); break;
         case FDW_MODE_PLAIN: hipLaunchKernelGGL((fdw_step2_kernel<4, false, 0, false, 2, 1>), grid, block, 0, s, a); break;
         case FDW_MODE_RECV:  hipLaunchKernelGGL((fdw_step2_kernel<4, true, 2, true, 2, 1>), grid, block, 0, s, a); break;
+        case FDW_MODE_FWD_REC: hipLaunchKernelGGL((fdw_step2_rec_kernel<1>), grid, block, 0, s, a); break;
         default: return hipErrorInvalidValue;
         }
         return hipGetLastError();
@@ -279,6 +300,7 @@ hipError_t launch_step2(const Step2Args& a, int h, int mode, hipStream_t s)
     case FDW_MODE_FWD:   hipLaunchKernelGGL((fdw_step2_kernel<4, true, 1, false, 2>), grid, block, 0, s, a); break;
     case FDW_MODE_PLAIN: hipLaunchKernelGGL((fdw_step2_kernel<4, false, 0, false, 2>), grid, block, 0, s, a); break;
     case FDW_MODE_RECV:  hipLaunchKernelGGL((fdw_step2_kernel<4, true, 2, true, 2>), grid, block, 0, s, a); break;
+    case FDW_MODE_FWD_REC: hipLaunchKernelGGL((fdw_step2_rec_kernel<0>), grid, block, 0, s, a); break;
     default: return hipErrorInvalidValue;
     }
     return hipGetLastError();

@@ -45,7 +45,9 @@ __device__ __forceinline__ int pipe_fifo_slot(int m)
 // nor the source (instantiate with TAPER = false, INJ = 0): the kernel picks it per workgroup (pipe_lean)
 // WK: 0 = the wave finds out at run time whether it is wave 0 (full body); 1 / 2 = compiled for wave 0 / for the other waves (lean body)
 // NUM: 0 = the reference's exact arithmetic, 1 = FAST numerics (symmetric sums + fused multiply-adds, fdw_device.h)
-template <int H, int NS, bool TAPER, int INJ, int PF, bool DD = false, int BK = 0, bool LEAN = false, int WK = 0, int NUM = 0>
+// REC: forward loop with trace recording (FDW_MODE_FWD_REC): wave k records its new row u^{n+k+1} at column rec_z into rec + k rec_n, from owned
+// lanes and the tile's own rows [xa, xe) only (the conditions of the field stores), so every sample is written once
+template <int H, int NS, bool TAPER, int INJ, int PF, bool DD = false, int BK = 0, bool LEAN = false, int WK = 0, int NUM = 0, bool REC = false>
 __device__ __forceinline__ void marchn(const Step2Args& a, const int lane, const int k, const int cs, const int xa, const int xe,
                                        f4 (*link)[2][2][64], f4 (*fifo)[64], f4 (*imf)[64] = nullptr, f4 (*linkx)[2][2][64] = nullptr)
 {
@@ -89,6 +91,8 @@ __device__ __forceinline__ void marchn(const Step2Args& a, const int lane, const
     const float injv = (INJ != 2 && inj_here) ? sload(a.inj, k) : 0.0f;    // source sample of this wave's time step (R:119-122)
     const float* injk = a.inj + (INJ == 2 ? k * a.inj_stride : 0);        // INJ 2: the trace samples of iteration it + k (R:124-131)
     const bool rec_here = DD && !LEAN && (a.rec != nullptr) && (a.rec_z >= cs * 4) && (a.rec_z < cs * 4 + 256);
+    static_assert(!REC || (!LEAN && !DD && BK == 0), "trace recording belongs to the full body of the RTM dialect's forward pass");
+    const bool rec_lane = REC && own && (cell == (a.rec_z >> 2));
 
     bool mlap[4], mupd[4], znc[4], ihit[4];
     float tzc[4];
@@ -292,6 +296,9 @@ __device__ __forceinline__ void marchn(const Step2Args& a, const int lane, const
         }
         const unsigned so = (act && (r >= xa) && (r < xe) && (m < M)) ? soff : kLaneOff;
         f4_store_arr(rs_out, so, rowoff(r), u);
+        if constexpr (REC)
+            f1_store_arr(array_rsrc(a.rec + (size_t)k * a.rec_n, (unsigned)a.rec_n * 4u),
+                         rec_offset(rec_lane && act && (r >= xa) && (r < xe) && (m < M), r, a.rec_x0, a.rec_n), f4_pick(u, a.rec_z & 3));
         if constexpr (IMG) {
             const unsigned sim = (k == NS - 1 && act && (r >= xa) && (r < xe)) ? ioff : kLaneOff;
             f4 im;
@@ -313,8 +320,8 @@ __device__ __forceinline__ void marchn(const Step2Args& a, const int lane, const
 
 // Workgroup-uniform: may this tile run the lean body?  Every row it touches -- stencil taps, look-ahead loads (PF + ring rows beyond the
 // chunk) -- lies inside the rows where the Laplacian and the update are unmasked, its columns likewise, it is outside the damped strip, and
-// neither a source nor (modelling) the receiver line is in it.
-template <int H, int NS, bool TAPER, int INJ, bool DD = false>
+// neither a source nor (modelling, REC) the receiver line is in it.
+template <int H, int NS, bool TAPER, int INJ, bool DD = false, bool REC = false>
 __device__ __forceinline__ bool pipe_lean(const Step2Args& a, int cs, int xa, int xe)
 {
     const int lo = xa - (NS - 1) * H - H - NS * (H + 1), hi = xe + (NS - 1) * (2 * H + 1) + 2 * H + 16;
@@ -328,6 +335,7 @@ __device__ __forceinline__ bool pipe_lean(const Step2Args& a, int cs, int xa, in
     if (INJ == 2) ok = ok && !((a.inj_z >= c0) && (a.inj_z < c1) && (a.inj_x < xe + NS * H) && (a.inj_x + a.inj_n > xa - NS * H));
     if (INJ == 1) ok = ok && !((a.inj_z >= c0) && (a.inj_z < c1) && (a.inj_x >= xa - NS * H) && (a.inj_x < xe + NS * H));
     if (DD) ok = ok && !((a.rec != nullptr) && (a.rec_z >= c0) && (a.rec_z < c1));                  // trace recording
+    if (REC) ok = ok && !((a.rec_z >= c0 + 4 * NS) && (a.rec_z < c1 - 4 * NS));                      // ... the strip whose owned lanes record it
     return ok;
 }
 
@@ -335,6 +343,7 @@ __device__ __forceinline__ bool pipe_lean(const Step2Args& a, int cs, int xa, in
 // 3 for the receiver field (BK 2)
 constexpr int kPipeWG = 5;
 constexpr int kDDWG = 4;
+constexpr int kPipePF = 2;      // rows of global look-ahead of wave 0
 
 template <int H, int NS, bool TAPER, int INJ, int PF, bool DD = false, int BK = 0, int NUM = 0>
 __global__ __launch_bounds__(64 * NS, BK == 2 ? 3 : (DD ? kDDWG : kPipeWG)) void fdw_stepn_kernel(const Step2Args a)
@@ -371,6 +380,35 @@ __global__ __launch_bounds__(64 * NS, BK == 2 ? 3 : (DD ? kDDWG : kPipeWG)) void
     } else {
         marchn<H, NS, TAPER, INJ, PF, DD, BK, false, 0, NUM>(a, lane, k, zb * (64 - 2 * NS) - NS, xa, xe, link, fifo);
     }
+}
+
+// FDW_MODE_FWD_REC: the forward pass that also records the trace samples of its kPipeSteps steps.  The tiles whose owned lanes hold the
+// receiver column run the full body with recording, the others fdw_stepn_kernel's lean bodies.  (Its own copy of the tile placement: routing
+// both kernels through one inlined function changes the register allocation of the existing instantiations.)  Four workgroups per CU, not
+// kPipeWG: at 96 VGPRs the recording full body spills one VGPR to scratch (its SGPRs, at the limit of 106, spill into VGPR lanes); DESIGN.md 6f.
+template <int NUM>
+__global__ __launch_bounds__(64 * kPipeSteps, kDDWG) void fdw_stepn_rec_kernel(const Step2Args a)
+{
+    constexpr int H = 4, NS = kPipeSteps, PF = kPipePF;
+    const int lane = threadIdx.x & 63;
+    const int k = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int bid = blockIdx.x;
+    const int L = (bid & 7) * a.nper + (bid >> 3);
+    if (L >= a.nblk) return;
+    const int zb = L % a.nstrip;
+    const int xb = L / a.nstrip;
+    const bool second = xb >= a.chunks_a;
+    const int xa = second ? a.r0b + (xb - a.chunks_a) * a.xchunk : a.r0 + xb * a.xchunk;
+    const int xe = min(xa + a.xchunk, second ? a.r1b : a.r1);
+    if (xa >= xe) return;
+    __shared__ f4 link[NS][2][2][64];
+    __shared__ f4 fifo[pipe_fifo_rows(NS, H)][64];
+    const int cs = zb * (64 - 2 * NS) - NS;
+    if (pipe_lean<H, NS, true, 1, false, true>(a, cs, xa, xe)) {
+        if (k == 0) marchn<H, NS, false, 0, PF, false, 0, true, 1, NUM>(a, lane, k, cs, xa, xe, link, fifo);
+        else marchn<H, NS, false, 0, PF, false, 0, true, 2, NUM>(a, lane, k, cs, xa, xe, link, fifo);
+    }
+    else marchn<H, NS, true, 1, PF, false, 0, false, 0, NUM, true>(a, lane, k, cs, xa, xe, link, fifo);
 }
 
 // Four iterations of the backward loop in ONE pass: a workgroup of eight waves, waves 0-3 the pipeline of the source field (role 3), waves 4-7
@@ -415,8 +453,6 @@ __global__ __launch_bounds__(128 * NS, 2) void fdw_back4_kernel(const Step2Args 
     }
 }
 
-constexpr int kPipePF = 2;      // rows of global look-ahead of wave 0
-
 hipError_t launch_stepn(const Step2Args& a, int h, int mode, hipStream_t s)
 {
     if (a.nper <= 0) return hipSuccess;
@@ -425,6 +461,7 @@ hipError_t launch_stepn(const Step2Args& a, int h, int mode, hipStream_t s)
     if (a.numerics) {      // FAST numerics (fdw_device.h): the same kernels with NUM = 1
         switch (mode) {
         case FDW_MODE_FWD:   hipLaunchKernelGGL((fdw_stepn_kernel<4, kPipeSteps, true, 1, kPipePF, false, 0, 1>), grid, block, 0, s, a); break;
+        case FDW_MODE_FWD_REC: hipLaunchKernelGGL((fdw_stepn_rec_kernel<1>), grid, block, 0, s, a); break;
         case FDW_MODE_PLAIN: hipLaunchKernelGGL((fdw_stepn_kernel<4, kPipeSteps, false, 0, kPipePF, false, 0, 1>), grid, block, 0, s, a); break;
         case FDW_MODE_MOD:   hipLaunchKernelGGL((fdw_stepn_kernel<4, kPipeSteps, true, 3, kPipePF, true, 0, 1>), grid, block, 0, s, a); break;
         case FDW_MODE_PLAIN_ALL: hipLaunchKernelGGL((fdw_stepn_kernel<4, kPipeSteps, false, 0, kPipePF, false, 1, 1>), grid, block, 0, s, a); break;
@@ -436,6 +473,7 @@ hipError_t launch_stepn(const Step2Args& a, int h, int mode, hipStream_t s)
     }
     switch (mode) {
     case FDW_MODE_FWD:   hipLaunchKernelGGL((fdw_stepn_kernel<4, kPipeSteps, true, 1, kPipePF>), grid, block, 0, s, a); break;
+    case FDW_MODE_FWD_REC: hipLaunchKernelGGL((fdw_stepn_rec_kernel<0>), grid, block, 0, s, a); break;
     case FDW_MODE_PLAIN: hipLaunchKernelGGL((fdw_stepn_kernel<4, kPipeSteps, false, 0, kPipePF>), grid, block, 0, s, a); break;
     case FDW_MODE_MOD:   hipLaunchKernelGGL((fdw_stepn_kernel<4, kPipeSteps, true, 3, kPipePF, true>), grid, block, 0, s, a); break;
     case FDW_MODE_PLAIN_ALL: hipLaunchKernelGGL((fdw_stepn_kernel<4, kPipeSteps, false, 0, kPipePF, false, 1>), grid, block, 0, s, a); break;

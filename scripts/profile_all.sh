@@ -1,7 +1,7 @@
 #!/bin/bash
 # GPU box: the profile set of a round (kernel trace + one counter group per pass each; scripts/profile_bench.py), in two or three calls:
 #   scripts/profile_all.sh a | b | c | d        outputs under gpurun_out/prof_<tag>/ ; scripts/collect_profiles.py copies what is judged into profiles/
-set -x
+set -ex      # the first tag that fails ends the set
 P="python3 scripts/profile_bench.py"
 case "$1" in
 a) $P fwd8192 -- --steps 200 --warmup 20

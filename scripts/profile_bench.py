@@ -22,6 +22,7 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
+PASS_TIMEOUT_S = 300      # one rocprofv3 process (a bench.py run of a few hundred steps)
 PMC_PASSES = [
     "FETCH_SIZE TCC_EA0_RDREQ",
     "WRITE_SIZE TCC_EA0_WRREQ",
@@ -44,9 +45,13 @@ def main():
     env = dict(os.environ, TMPDIR="/tmp")
 
     def run(name, args):
+        # each pass under its own time limit; a pass that fails (a fault, an abort, the limit) ends the profile: nothing more is started on the GPU
         log = open(os.path.join(out, name + ".log"), "w")
-        r = subprocess.run(["rocprofv3"] + args + ["-d", os.path.join(out, name), "--output-format", "csv"] + cmd_tail, stdout=log, stderr=subprocess.STDOUT, cwd="/tmp", env=env)
+        r = subprocess.run(["timeout", "-k", "10", str(PASS_TIMEOUT_S), "rocprofv3"] + args + ["-d", os.path.join(out, name), "--output-format", "csv"] + cmd_tail,
+                           stdout=log, stderr=subprocess.STDOUT, cwd="/tmp", env=env)
         print(f"[profile_bench] {name}: rc {r.returncode}", flush=True)
+        if r.returncode != 0:
+            sys.exit(f"[profile_bench] {name} failed (rc {r.returncode}): see {log.name}")
         return r.returncode
 
     run("trace", ["--kernel-trace", "--stats"])
