@@ -11,7 +11,8 @@
 //   * a wave marches along x over `xchunk` rows keeping the rows of p it needs in a REGISTER ring
 //     (2H+1 stencil rows + look-ahead rows that are still in flight), so x taps never touch memory
 //     twice inside a chunk and HBM latency is covered by explicit software prefetch, not occupancy;
-//   * z taps come from the two neighbouring lanes (DPP wave shifts, lane_up / lane_down below; the LDS crossbar that
+//   * z taps come from the two neighbouring lanes (DPP wave shifts, lane_up / lane_down below -- the EXACT four-step Laplacian shifts
+//     products and partial sums instead of values, laplacian_quad; the LDS crossbar that
 //     __shfl_up / __shfl_down compile to cost the pipeline kernel 4 %); the 4+4 halo columns of a strip come from ONE
 //     extra load issued by all lanes (lane 0 the left piece, every other lane the right piece);
 //   * taper, Laplacian, leap-frog update, point-source / receiver injection and the imaging
@@ -228,29 +229,89 @@ __device__ __forceinline__ v2f laplacian_pair(const ZPairs& z, Col&& col, const 
     return acmz + acmx;
 }
 __device__ __forceinline__ v2f f4_pair(const f4& a, int P) { return v2f{a.v[2 * P], a.v[2 * P + 1]}; }
-// Both pairs of a lane at once: the four accumulator chains (z and x of each pair) advance tap by tap side by side, which gives a
-// lone wave four independent dependency chains to issue from instead of two (same operations, same order within each chain).
-template <int H, class Row>
-__device__ __forceinline__ void laplacian_quad(const ZPairs& z, Row&& row, const CoefPairs<H>& c, v2f& lap01, v2f& lap23)
+// product j = 0..9 of group g of laplacian_quad: (element i, weight index ic) with i + ic = g mod 2, element-major
+constexpr int zgroup_prod(int g, int j, bool want_ic)
 {
-    v2f az0 = {0.0f, 0.0f}, ax0 = {0.0f, 0.0f}, az1 = {0.0f, 0.0f}, ax1 = {0.0f, 0.0f};
-    static_for<2 * H + 1>([&](auto IO) {
-        constexpr int io = decltype(IO)::value;
-        constexpr int k0 = 4 - H + io, k1 = 6 - H + io;
-        constexpr int ic = io <= H ? io : 2 * H - io;
-        const f4 r = row(IO);
-        az0 = az0 + pk_mul_sel<ic & 1>((k0 & 1) ? z.O[k0 >> 1] : z.E[k0 >> 1], c.z[ic >> 1]);
-        ax0 = ax0 + pk_mul_sel<ic & 1>(v2f{r.v[0], r.v[1]}, c.x[ic >> 1]);
-        az1 = az1 + pk_mul_sel<ic & 1>((k1 & 1) ? z.O[k1 >> 1] : z.E[k1 >> 1], c.z[ic >> 1]);
-        ax1 = ax1 + pk_mul_sel<ic & 1>(v2f{r.v[2], r.v[3]}, c.x[ic >> 1]);
+    int n = 0;
+    for (int i = 0; i < 4; ++i)
+        for (int ic = 0; ic <= 4; ++ic)
+            if ((i + ic) % 2 == g) {
+                if (n == j) return want_ic ? ic : i;
+                ++n;
+            }
+    return -1;
+}
+// The lane's four cells at once (the four-step kernel, EXACT).  x half: two packed chains, as laplacian_pair.  z half: the products are
+// SHARED between lanes.  Tap d of cell j is W[j + d] * cz[H - |d|], the same rounded fp32 product that cell j + 2d forms for its tap -d, so
+// a lane multiplies only its OWN four values by the H + 1 distinct weights: 20 products, no window of neighbour values.  Cell e's chain,
+// 0 + term 0 + ... + term 8 in io order with every add rounded (bit-identical to laplacian_pt), runs in three parts:
+//   * terms 0 .. 3-e are the LEFT lane's products: that lane sums them, from 0, for its right neighbour (the prefix sums pa, pb);
+//   * that partial sum enters as the DPP operand of the add of this lane's first term (v_add_f32_dpp wave_shr:1);
+//   * terms 8-e .. 8 are the RIGHT lane's products, each the DPP operand of its add (wave_shl:1).
+// lane_up / lane_down feeding an add fold into v_add_f32_dpp: no lane moves.  Lanes 0 / 63 read 0 for the missing neighbour (halo lanes).
+// Product (i, ic) serves the chains of cells (i + ic) mod 4 and (i - ic) mod 4, both of the parity of i + ic, so the z half runs as two
+// groups, cells {g, g + 2}, each on its own 10 products: half of them are live at a time (all 20 at once, or packed pairs, which straddle
+// the groups, spill the full body of the forward kernel).  The products are scalar multiplies, not pk_mul_sel: the hazard recogniser
+// counts an asm statement as no wait state, so asm products read by DPP drew s_nop padding.  The x taps, the group's products and the two
+// chains are written interleaved, so that independent work separates each asm multiply from its add and each prefix sum from its shift.
+template <int H, class Row>
+__device__ __forceinline__ void laplacian_quad(const f4& c, Row&& row, const CoefPairs<H>& cf, v2f& lap01, v2f& lap23)
+{
+    static_assert(H == 4, "a lane's four cells reach exactly one float4 to each side");
+    auto cz = [&](int ic) { return cf.z[ic >> 1][ic & 1]; };
+    v2f ax0 = {0.0f, 0.0f}, ax1 = {0.0f, 0.0f};
+    float qz[4][H + 1];                                         // qz[i][ic] = c.v[i] * cz[ic], formed for the group that uses it
+    float az[4];
+    static_for<2>([&](auto G) {
+        constexpr int g = decltype(G)::value;
+        // x taps 5g .. 5g + 4 (g = 1: 5 .. 8): the group's products j = 2t, 2t + 1 (the last tap: the rest) between multiplies and adds
+        static_for<5 - g>([&](auto T) {
+            constexpr int t = decltype(T)::value, io = 5 * g + t, icx = io <= H ? io : 2 * H - io;
+            const f4 r = row(std::integral_constant<int, io>{});
+            const v2f m0 = pk_mul_sel<icx & 1>(v2f{r.v[0], r.v[1]}, cf.x[icx >> 1]);
+            const v2f m1 = pk_mul_sel<icx & 1>(v2f{r.v[2], r.v[3]}, cf.x[icx >> 1]);
+            static_for<10>([&](auto J) {
+                constexpr int j = decltype(J)::value;
+                if constexpr ((j / 2 < 4 - g ? j / 2 : 4 - g) == t) {
+                    constexpr int i = zgroup_prod(g, j, false), ic = zgroup_prod(g, j, true);
+                    qz[i][ic] = c.v[i] * cz(ic);
+                }
+            });
+            ax0 = ax0 + m0;
+            ax1 = ax1 + m1;
+        });
+        constexpr int a = g, b = g + 2;                         // prefix sums: terms io = 0 .. 3-e of the right neighbour's cell e
+        float pa = 0.0f, pb = 0.0f;
+        static_for<4 - a>([&](auto S) {
+            constexpr int s = decltype(S)::value;
+            pa = pa + qz[a + s][s];
+            if constexpr (s < 4 - b) pb = pb + qz[b + s][s];
+        });
+        // the chains: op 0 joins the left lane's partial sum to this lane's value 0 (io = 4-e), ops 1-3 this lane's values 1-3,
+        // ops 4 .. 4+e the right lane's values 0 .. e (io = 8-e .. 8); chain b leads by two ops so that pa is complete
+        auto op = [&](auto OP, auto E, float& acc, float p) {
+            constexpr int o = decltype(OP)::value, e = decltype(E)::value;
+            if constexpr (o == 0) acc = lane_up(p) + qz[0][4 - e];
+            else if constexpr (o < 4) { constexpr int io = 4 - e + o; acc = acc + qz[o][io <= H ? io : 2 * H - io]; }
+            else if constexpr (o <= 4 + e) { constexpr int io = 4 + o - e; acc = lane_down(qz[o - 4][2 * H - io]) + acc; }
+        };
+        float acca, accb;
+        static_for<5 + b>([&](auto S) {
+            constexpr int s = decltype(S)::value;
+            op(std::integral_constant<int, s>{}, std::integral_constant<int, b>{}, accb, pb);
+            if constexpr (s >= 2) op(std::integral_constant<int, s - 2>{}, std::integral_constant<int, a>{}, acca, pa);
+        });
+        az[a] = acca;
+        az[b] = accb;
     });
-    lap01 = az0 + ax0;
-    lap23 = az1 + ax1;
+    lap01 = v2f{az[0], az[1]} + ax0;
+    lap23 = v2f{az[2], az[3]} + ax1;
 }
 
 // ---- FAST numerics (fdw_params.numerics = FDW_NUMERICS_FAST; include/fdwave.h) ---------------------------------------------------
 // The EXACT Laplacian above is the reference's arithmetic operation for operation (nvcc --fmad=false): 17 products and 17 sums per axis pair,
-// every one rounded -- 72 packed instructions per lane and row, which is what binds the pipeline kernel (VALU issue).  The
+// every one rounded -- 72 packed instructions per lane and row in laplacian_pair (laplacian_quad: 38 packed and 56 scalar ones, its z
+// products shared between lanes), which is what binds the pipeline kernel (VALU issue).  The
 // north star asks for 1e-5, not for bits, and the reference's own FMA / no-FMA builds differ by 4e-6 over 1 700 steps.  FAST
 // uses the symmetry of the weights and fused multiply-adds:
 //     lap = c0 p(i,j) + sum_{k=1..H} [ cz_k (p(i,j-k) + p(i,j+k)) + cx_k (p(i-k,j) + p(i+k,j)) ],   c0 = cz_0 + cx_0 (formed on the host in fp32)
@@ -326,11 +387,23 @@ __device__ __forceinline__ v2f lap_pair(const ZPairs& z, Col&& col, const CoefPa
     if constexpr (NUM == 0) return laplacian_pair<H, P>(z, col, c);
     else return laplacian_fast_pair<H, P>(z, col, c, c0);
 }
-template <int NUM, int H, class Row>
-__device__ __forceinline__ void lap_quad(const ZPairs& z, Row&& row, const CoefPairs<H>& c, v2f c0, v2f& lap01, v2f& lap23)
+// the lane's window of 12 z values (its float4 between both neighbours') as pairs, for the Laplacians that read their neighbours' VALUES
+__device__ __forceinline__ ZPairs lane_window(const f4& c)
 {
-    if constexpr (NUM == 0) laplacian_quad<H>(z, row, c, lap01, lap23);
-    else laplacian_fast_quad<H>(z, row, c, c0, lap01, lap23);
+    f4 lft, rgt;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        lft.v[e] = lane_up(c.v[e]);
+        rgt.v[e] = lane_down(c.v[e]);
+    }
+    return zpairs(lft, c, rgt);
+}
+// c = the lane's float4 of the centre row
+template <int NUM, int H, class Row>
+__device__ __forceinline__ void lap_quad(const f4& c, Row&& row, const CoefPairs<H>& cf, v2f c0, v2f& lap01, v2f& lap23)
+{
+    if constexpr (NUM == 0) laplacian_quad<H>(c, row, cf, lap01, lap23);
+    else laplacian_fast_quad<H>(lane_window(c), row, cf, c0, lap01, lap23);
 }
 
 // The CPU-serial sibling's Laplacian (laplacian_dd_pt above; fd.c:28-36) for the lane's two pairs: one accumulator chain per pair, per

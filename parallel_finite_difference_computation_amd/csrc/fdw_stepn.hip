@@ -211,12 +211,6 @@ __device__ __forceinline__ void marchn(const Step2Args& a, const int lane, const
             if (first && a.pp_twice) taper_row(ppt, r);
         }
         const f4 c1 = ring[(U + H) % R];
-        f4 lft, rgt;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            lft.v[e] = lane_up(c1.v[e]);
-            rgt.v[e] = lane_down(c1.v[e]);
-        }
         const bool rowok = LEAN || ((r >= a.lap_x0) && (r < a.lap_x1));
         const bool rowupd = LEAN || ((r >= 0) && (r < a.upd_x1));
         if constexpr (DD) {
@@ -227,12 +221,11 @@ __device__ __forceinline__ void marchn(const Step2Args& a, const int lane, const
                     if (z0 + e == a.rec_z) a.rec[k * a.rec_n + (r - a.rec_x0)] = c1.v[e];
             }
         }
-        const ZPairs zp = zpairs(lft, c1, rgt);
         auto row = [&](auto IO) -> const f4& { return ring[(U + decltype(IO)::value) % R]; };
         v2f lapq[2];
         // DD exact: the sibling's single-accumulator Laplacian, two cells per instruction; DD FAST: the weights carry their spacing
-        if constexpr (DD && NUM == 0) laplacian_dd_quad<H>(zp, row, cpk, ddinv, lapq[0], lapq[1]);
-        else lap_quad<NUM, H>(zp, row, cpk, c0p, lapq[0], lapq[1]);
+        if constexpr (DD && NUM == 0) laplacian_dd_quad<H>(lane_window(c1), row, cpk, ddinv, lapq[0], lapq[1]);
+        else lap_quad<NUM, H>(c1, row, cpk, c0p, lapq[0], lapq[1]);
         // (the masks behind a per-workgroup branch, taken only where a tile touches the frame, measured 1.5 % slower: DESIGN.md section 3c)
         static_for<2>([&](auto PP) {
             constexpr int P = decltype(PP)::value;

@@ -12,6 +12,7 @@ __global__ __launch_bounds__(256) void k(float* out, int iters, float c0, float 
     double d[8];
     for (int i = 0; i < 16; i++) a[i] = (float)threadIdx.x * 0.001f + i;
     for (int i = 0; i < 8; i++) d[i] = (double)a[i];
+    if (MODE >= 12) asm volatile("s_nop 4");      // a DPP read of a VGPR wants two wait states after the VALU write (asm is not padded)
     for (int it = 0; it < iters; it++) {
 #pragma unroll
         for (int r = 0; r < 4; r++) {
@@ -29,6 +30,9 @@ __global__ __launch_bounds__(256) void k(float* out, int iters, float c0, float 
                 if (MODE == 9) asm volatile("v_cndmask_b32 %0, %0, %1, vcc" : "+v"(a[i]) : "v"(c0));
                 if (MODE == 10) asm volatile("v_mov_b32 %0, %1" : "=v"(a[i]) : "v"(a[(i + 1) & 15]));
                 if (MODE == 11) asm volatile("ds_bpermute_b32 %0, %1, %0\n s_waitcnt lgkmcnt(0)" : "+v"(a[i]) : "v"((int)(threadIdx.x & 63) * 4));
+                // the neighbouring lane's operand through DPP (the EXACT four-step Laplacian's z adds; lane moves of the other Laplacians)
+                if (MODE == 12) asm volatile("v_add_f32_dpp %0, %0, %1 wave_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:1" : "+v"(a[i]) : "v"(c1));
+                if (MODE == 13) asm volatile("v_mov_b32_dpp %0, %1 wave_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:1" : "=v"(a[i]) : "v"(a[(i + 1) & 15]));
             }
         }
     }
@@ -62,6 +66,6 @@ int main()
 {
     run<0>("v_mul_f32", 16); run<1>("v_add_f32", 16); run<2>("v_fma_f32", 16); run<3>("v_pk_mul_f32", 8); run<4>("v_pk_add_f32", 8);
     run<5>("v_fma_f64", 8); run<6>("v_add_f64", 8); run<7>("v_cvt_f64_f32", 8); run<8>("v_cvt_f32_f64", 8); run<9>("v_cndmask_b32", 16);
-    run<10>("v_mov_b32", 16); run<11>("ds_bpermute_b32", 16);
+    run<10>("v_mov_b32", 16); run<11>("ds_bpermute_b32", 16); run<12>("v_add_f32_dpp", 16); run<13>("v_mov_b32_dpp", 16);
     return 0;
 }
