@@ -323,6 +323,33 @@ int fdw_record_shot_batch(fdw_ctx *ctx, int nshots, const float *v2_all, unsigne
 int fdw_shot_resident(fdw_ctx *ctx, int sx, int sz, int gz, const float *srce, const float *d_obs, float *imloc, float *P, float *PP);
 int fdw_rand_stream(fdw_ctx *ctx, unsigned long long draw_offset, long long n, int *out);
 
+/* ---- source illumination of the forward loop; illumination-compensated image ------------------------------------------------
+ * Definition.  RTM dialect, full-grid contexts.  For every extended-grid cell (x, z) with x < xlim, z < zlim (fdw_get_extents)
+ *     for it = 0 .. nsteps-1 (increasing):   I(x,z) = I(x,z) (+) ( u(x,z) (*) u(x,z) )
+ * with u = what the reference's d_pp holds at the END of iteration it of fd_forward's loop (R:259-267, after kernel_src): the value the
+ * kernels store as the new field, source sample included, undamped -- the level the recording definition above samples.  (*) and (+)
+ * are fp32 round-to-nearest operations rounded separately (no fused multiply-add), in EXACT and in FAST numerics alike (FAST changes the
+ * Laplacian only).  Cells outside the update extents keep their value; I is read-modify-write and starts from what the caller put there.
+ * Dividing the cross-correlation image sum_t F_t R_t by I = sum_t F_t^2 takes out the strong shallow energy around each shot.  The
+ * accumulation rides the forward loop's own passes (the four-step pipeline stores only two of its four levels, so no caller can form I
+ * from outside without giving up temporal blocking): +8 B/point per pass.  Slab contexts and the sibling's dialects: FDW_ESTATE.
+ * fdw_dev_illum_steps      fdw_dev_steps2 (same buffers, indices and kernel family per pass, bit-identical fields) that also accumulates
+ *                          into d_illum [nxl][pitch] (a field-sized device array; its padding columns stay as they are).  d_illum == NULL:
+ *                          FDW_EINVAL.  Orders above 8 and forced generic: the generic step followed by a plain add kernel.
+ * fdw_shot_illum           fdw_shot whose forward loop goes through the illumination kernels: illum[nx][nz] (interior, like imloc) is
+ *                          accumulated into; imloc, P, PP equal fdw_shot's bit for bit.  The accumulator field is allocated on first use.
+ * fdw_shot_resident_illum  the same on the resident vel2 (fdw_shot_resident).
+ * fdw_image_compensate     pure host C, usable without a device:  m = max_i illum[i] (from 0.0f with '>' comparisons, so a NaN never
+ *                          wins), s = eps (*) m, d_i = illum[i] (+) s, out_i = d_i > 0 ? img[i] (/) d_i : 0.0f (IEEE fp32 division; out may
+ *                          alias img).  eps finite and >= 0, else FDW_EINVAL.  O(n) once per job. */
+int fdw_dev_illum_steps(fdw_ctx *ctx, float *const *d_buf, const float *d_v2, const float *d_srce, int sx, int sz, float *d_illum, int it0,
+                        int nsteps, int first_pp_twice, int *ip, int *ipp, void *stream);
+int fdw_shot_illum(fdw_ctx *ctx, const float *v2, int sx, int sz, int gz, const float *srce, const float *d_obs, float *imloc, float *illum,
+                   float *P, float *PP);
+int fdw_shot_resident_illum(fdw_ctx *ctx, int sx, int sz, int gz, const float *srce, const float *d_obs, float *imloc, float *illum,
+                            float *P, float *PP);
+int fdw_image_compensate(const float *img, const float *illum, size_t n, float eps, float *out);
+
 /* ---- multi-GPU: communicators and the slab-decomposed loops (csrc/fdw_comm.cpp, csrc/fdw_slabs.cpp) ------------------------
  * The reference has no multi-GPU path.  The grid is decomposed along x, the slow axis, into one band of rows per
  * rank; a rank is one GPU, driven by one process (RCCL backend) or by one host thread of a process (RCCL or local backend).

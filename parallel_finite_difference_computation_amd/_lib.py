@@ -73,6 +73,10 @@ SIGNATURES = [
     ("fdw_dev_record_steps", C.c_int, [vp, C.POINTER(vp), vp, vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), vp]),
     ("fdw_record_shot", C.c_int, [vp, f32p, C.c_int, C.c_int, C.c_int, f32p, f32p, vp, vp]),
     ("fdw_record_shot_batch", C.c_int, [vp, C.c_int, vp, C.c_ulonglong, C.c_int, C.c_int, C.c_int, C.c_int, f32p, f32p]),
+    ("fdw_dev_illum_steps", C.c_int, [vp, C.POINTER(vp), vp, vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), vp]),
+    ("fdw_shot_illum", C.c_int, [vp, f32p, C.c_int, C.c_int, C.c_int, f32p, f32p, f32p, f32p, vp, vp]),
+    ("fdw_shot_resident_illum", C.c_int, [vp, C.c_int, C.c_int, C.c_int, f32p, f32p, f32p, f32p, vp, vp]),
+    ("fdw_image_compensate", C.c_int, [vp, vp, C.c_size_t, C.c_float, vp]),
     ("fdw_rand_stream", C.c_int, [vp, C.c_ulonglong, C.c_longlong, vp]),
     ("fdw_dev_model_steps", C.c_int, [vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, vp]),
     ("fdw_mod_extendvel", None, [C.c_int] * 4 + [f32p]),

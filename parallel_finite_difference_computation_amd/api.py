@@ -97,6 +97,16 @@ def image_compare(a, b, device=0, want_diff=False, exact_sums=False):
     return (out, diff) if want_diff else out
 
 
+def image_compensate(img, illum, eps=1e-3):
+    """The image divided by the source illumination (fdwave.h, fdw_image_compensate): img / (illum + eps * max illum) in fp32, 0 where the
+    denominator is not positive.  Host arithmetic; eps is a parameter of the method (finite, >= 0)."""
+    img = np.ascontiguousarray(img, np.float32)
+    illum = _f32(illum, img.shape)
+    out = np.empty_like(img)
+    check(lib().fdw_image_compensate(img.ctypes.data, illum.ctypes.data, img.size, eps, out.ctypes.data))
+    return out
+
+
 class FDWave:
     """One fd_init (fd-code.cu:200-224 / fd-source-code.cu:241-262) worth of state on one MI355X."""
 
@@ -190,15 +200,21 @@ class FDWave:
                              _f32(d_obs, (self.nx, self.nt)), gz, imloc, nsteps))
         return imloc
 
-    def shot(self, v2, sx, sz, gz, srce, d_obs, imloc=None, want_fields=False):
-        """One shot of rtm_code's loop (fd-code.cu:496-518), device resident."""
+    def shot(self, v2, sx, sz, gz, srce, d_obs, imloc=None, want_fields=False, want_illum=False, illum=None):
+        """One shot of rtm_code's loop (fd-code.cu:496-518), device resident.  want_illum: the forward loop also accumulates the source
+        illumination illum[nx][nz] (from zero, or into `illum`; fdwave.h), appended to what is returned."""
         shape = (self.nxe, self.nze)
         imloc = np.zeros((self.nx, self.nz), np.float32) if imloc is None else np.array(imloc, np.float32, order="C")
         P = np.zeros(shape, np.float32) if want_fields else None
         PP = np.zeros(shape, np.float32) if want_fields else None
+        fields = (P.ctypes.data if want_fields else None, PP.ctypes.data if want_fields else None)
+        if want_illum:
+            illum = np.zeros((self.nx, self.nz), np.float32) if illum is None else np.array(_f32(illum, (self.nx, self.nz)), order="C")
+            check(lib().fdw_shot_illum(self._h, _f32(v2, shape), sx, sz, gz, _f32(srce, (self.nt,)), _f32(d_obs, (self.nx, self.nt)), imloc, illum,
+                                       *fields))
+            return (imloc, P, PP, illum) if want_fields else (imloc, illum)
         check(lib().fdw_shot(self._h, _f32(v2, shape), sx, sz, gz, _f32(srce, (self.nt,)),
-                             _f32(d_obs, (self.nx, self.nt)), imloc,
-                             P.ctypes.data if want_fields else None, PP.ctypes.data if want_fields else None))
+                             _f32(d_obs, (self.nx, self.nt)), imloc, *fields))
         return (imloc, P, PP) if want_fields else imloc
 
     # ---- random-border model generated on the device (SURVEY.md section 8 row f4) ----
@@ -217,12 +233,17 @@ class FDWave:
         check(lib().fdw_dev_extendvel_linear(self._h, int(draw_offset), vel.ctypes.data if want_vel else None))
         return vel
 
-    def shot_resident(self, sx, sz, gz, srce, d_obs, imloc=None, want_fields=False):
+    def shot_resident(self, sx, sz, gz, srce, d_obs, imloc=None, want_fields=False, want_illum=False, illum=None):
         """shot() on the squared model dev_extendvel_linear left in HBM."""
         shape = (self.nxe, self.nze)
         imloc = np.zeros((self.nx, self.nz), np.float32) if imloc is None else np.array(imloc, np.float32, order="C")
         P = np.zeros(shape, np.float32) if want_fields else None
         PP = np.zeros(shape, np.float32) if want_fields else None
+        if want_illum:
+            illum = np.zeros((self.nx, self.nz), np.float32) if illum is None else np.array(_f32(illum, (self.nx, self.nz)), order="C")
+            check(lib().fdw_shot_resident_illum(self._h, sx, sz, gz, _f32(srce, (self.nt,)), _f32(d_obs, (self.nx, self.nt)), imloc, illum,
+                                                P.ctypes.data if want_fields else None, PP.ctypes.data if want_fields else None))
+            return (imloc, P, PP, illum) if want_fields else (imloc, illum)
         check(lib().fdw_shot_resident(self._h, sx, sz, gz, _f32(srce, (self.nt,)), _f32(d_obs, (self.nx, self.nt)), imloc,
                                       P.ctypes.data if want_fields else None, PP.ctypes.data if want_fields else None))
         return (imloc, P, PP) if want_fields else imloc
@@ -347,6 +368,14 @@ class FDWave:
         arr = (C.c_void_p * 4)(*bufs)
         a, b = C.c_int(ip), C.c_int(ipp)
         check(lib().fdw_dev_record_steps(self._h, arr, d_v2, d_srce, sx, sz, gz, d_rec, it0, nsteps, int(first_pp_twice), C.byref(a), C.byref(b), stream))
+        return a.value, b.value
+
+    def dev_illum_steps(self, bufs, d_v2, d_srce, sx, sz, d_illum, it0, nsteps, first_pp_twice=False, ip=0, ipp=1, stream=None):
+        """dev_steps2 that also adds the square of every step's new field to d_illum (device [nxl][pitch]; fdwave.h).
+        Returns (ip, ipp) as dev_steps2 does."""
+        arr = (C.c_void_p * 4)(*bufs)
+        a, b = C.c_int(ip), C.c_int(ipp)
+        check(lib().fdw_dev_illum_steps(self._h, arr, d_v2, d_srce, sx, sz, d_illum, it0, nsteps, int(first_pp_twice), C.byref(a), C.byref(b), stream))
         return a.value, b.value
 
     def dev_taper_finalize(self, d_f, stream=None):

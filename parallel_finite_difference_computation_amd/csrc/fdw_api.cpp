@@ -68,6 +68,7 @@ struct fdw_ctx {
     // lazily allocated work buffers of the host-array API
     float* fld[10] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};      // 8, 9: source-field levels of a backward pipeline pass
     float *d_v2 = nullptr, *d_img = nullptr, *d_srce = nullptr, *d_dobs = nullptr;
+    float* d_illum = nullptr;   // source illumination of one shot on the extended grid (fdw_shot_illum); allocated on first use
     size_t srce_cap = 0, dobs_cap = 0;
     // tuning
     int xchunk = 0, wz = 0, use_generic = 0, prefetch = 0, force_edge = 0, xchunk2 = 0;
@@ -339,7 +340,7 @@ extern "C" void fdw_destroy(fdw_ctx* c)
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     float* bufs[] = {c->d_taperz, c->d_txfac, c->d_gcx, c->d_gcz, c->fld[0], c->fld[1], c->fld[2], c->fld[3],
-                     c->fld[4], c->fld[5], c->fld[6], c->fld[7], c->fld[8], c->fld[9], c->d_v2, c->d_img, c->d_srce, c->d_dobs, c->d_rec,
+                     c->fld[4], c->fld[5], c->fld[6], c->fld[7], c->fld[8], c->fld[9], c->d_v2, c->d_img, c->d_illum, c->d_srce, c->d_dobs, c->d_rec,
                      c->d_vp, c->d_vpe, (float*)c->d_draws, (float*)c->d_jump, c->bfld[0], c->bfld[1], c->bfld[2], c->bfld[3],
                      c->bfld[4], c->bfld[5], c->bfld[6], c->bfld[7], c->b_v2, c->b_img, c->b_dobs, c->d_raw};
     for (float* b : bufs)
@@ -480,7 +481,7 @@ static int static_receiver_rows(fdw_ctx* c, int x, int n, int r1, float* field, 
 
 static int step_impl(fdw_ctx* c, int mode, const float* d_p, float* d_pp, const float* d_v2, int r0, int r1,
                      int pp_twice, const float* d_inj, int inj_x_global, int inj_z, const float* d_psrc, float* d_img,
-                     hipStream_t s, float* d_rec_row = nullptr, int rec_z = 0, float* d_fpp = nullptr, float* d_out = nullptr)
+                     hipStream_t s, float* d_rec_row = nullptr, int rec_z = 0, float* d_fpp = nullptr, float* d_out = nullptr, float* d_illum = nullptr)
 {
     const bool lap = (mode == FDW_MODE_LAP);
     if (!d_p || !d_pp) return fail(FDW_EINVAL, "step: field pointer is NULL");
@@ -515,8 +516,11 @@ static int step_impl(fdw_ctx* c, int mode, const float* d_p, float* d_pp, const 
     else if (mode == FDW_MODE_RECV || mode == FDW_MODE_DD_RECV || mode == FDW_MODE_BACK)
         FDW_TRY(place_receivers(c, "step", mode == FDW_MODE_DD_RECV ? c->prm.nzb : c->prm.nxb, inj_z, &in));
     if (mode == FDW_MODE_MOD) FDW_TRY(fill_mod(c, a, "step", d_rec_row, rec_z));
-    const int kmode = (mode == FDW_MODE_FWD && d_rec_row) ? FDW_MODE_FWD_REC : mode;      // the RTM forward step that records its trace row
+    if (d_illum && (mode != FDW_MODE_FWD || d_rec_row || c->nbatch > 1)) return fail(FDW_EINVAL, "step: illumination belongs to a plain forward step of one shot");
+    // the RTM forward step that records its trace row, or that accumulates the source illumination (the accumulator travels in `img`)
+    const int kmode = (mode == FDW_MODE_FWD && d_rec_row) ? FDW_MODE_FWD_REC : ((mode == FDW_MODE_FWD && d_illum) ? FDW_MODE_FWD_ILLUM : mode);
     if (kmode == FDW_MODE_FWD_REC) fill_rec(c, a, d_rec_row, rec_z);
+    if (kmode == FDW_MODE_FWD_ILLUM) a.img = d_illum;
     a.inj = d_inj + in.shift; a.inj_x = in.x; a.inj_z = inj_z; a.inj_n = in.n;
     if (a.r1 <= a.r0) return FDW_OK;
     if (c->nbatch > 1) {      // fdw_shot_batch: shot b = these pointers + b fields, its own gather, its own source row
@@ -534,7 +538,9 @@ static int step_impl(fdw_ctx* c, int mode, const float* d_p, float* d_pp, const 
         e = launch_step_fast(a, c->h, kmode, effective_prefetch(c), s);
     } else {
         if (mode >= FDW_MODE_MOD) return fail(FDW_EINVAL, "step: mode %d has no generic-order kernel", mode);
-        e = launch_step_generic(a, c->h, kmode, s);
+        // no generic-order illumination kernel: the plain step, then illum += pp (*) pp over the cells it updated
+        e = launch_step_generic(a, c->h, kmode == FDW_MODE_FWD_ILLUM ? FDW_MODE_FWD : kmode, s);
+        if (e == hipSuccess && kmode == FDW_MODE_FWD_ILLUM) e = launch_illum_add(d_pp, d_illum, c->pitch, a.r0, a.r1, c->upd_z1, s);
     }
     if (e != hipSuccess) return fail(FDW_EHIP, "kernel launch failed: %s", hipGetErrorString(e));
     if ((mode == FDW_MODE_RECV || mode == FDW_MODE_BACK) && r1 > c->upd_x1)
@@ -628,7 +634,8 @@ struct Step2Extra {          // what the receiver / imaging variant needs on top
 // mode RECV: d_inj / ex.inj2 -> receiver samples of iterations it / it+1 (nx each), inj_z = gz, imaging with ex.psrc_a/b
 // d_rec (mode FWD only): the trace rows of both steps, rec and rec + nx (FDW_MODE_FWD_REC)
 static int step2_impl(fdw_ctx* c, int mode, const float* d_p, const float* d_pp, const float* d_v2, float* d_out1, float* d_out2, int pp_twice,
-                      const float* d_inj, int inj_x_global, int inj_z, const Step2Extra& ex, hipStream_t s, float* d_rec = nullptr, int rec_z = 0)
+                      const float* d_inj, int inj_x_global, int inj_z, const Step2Extra& ex, hipStream_t s, float* d_rec = nullptr, int rec_z = 0,
+                      float* d_illum = nullptr)
 {
     if (c->h != kMaxFastHalfOrder) return fail(FDW_EINVAL, "step2: the two-step kernel is built for order 8 only");
     if (!d_p || !d_pp || !d_v2 || !d_out1 || !d_out2) return fail(FDW_EINVAL, "step2: NULL buffer");
@@ -662,8 +669,10 @@ static int step2_impl(fdw_ctx* c, int mode, const float* d_p, const float* d_pp,
     const int chunks = (rows + xchunk - 1) / xchunk;
     a.nblk = a.nzblk * chunks;
     a.nper = (a.nblk + 7) / 8;
-    const int kmode = (mode == FDW_MODE_FWD && d_rec) ? FDW_MODE_FWD_REC : mode;
+    if (d_illum && (mode != FDW_MODE_FWD || d_rec)) return fail(FDW_EINVAL, "step2: illumination belongs to a plain forward pass");
+    const int kmode = (mode == FDW_MODE_FWD && d_rec) ? FDW_MODE_FWD_REC : ((mode == FDW_MODE_FWD && d_illum) ? FDW_MODE_FWD_ILLUM : mode);
     if (kmode == FDW_MODE_FWD_REC) fill_rec(c, a, d_rec, rec_z);
+    if (kmode == FDW_MODE_FWD_ILLUM) a.img = d_illum;
     hipError_t e = launch_step2(a, c->h, kmode, s);
     if (e != hipSuccess) return fail(FDW_EHIP, "step2 launch failed: %s", hipGetErrorString(e));
     return even_steps_tail(c, mode, a, s);
@@ -694,7 +703,7 @@ struct RowRanges {      // rows the pass produces: [r0, r1) and optionally [r0b,
 };
 static int stepn_impl(fdw_ctx* c, int mode, const float* d_p, const float* d_pp, const float* d_v2, float* d_out1, float* d_out2, int pp_twice,
                       const float* d_inj, int inj_x_global, int inj_z, hipStream_t s, const RowRanges& rr = RowRanges{}, float* d_rec = nullptr,
-                      int rec_z = 0, const StepnBack* bk = nullptr)
+                      int rec_z = 0, const StepnBack* bk = nullptr, float* d_illum = nullptr)
 {
     if (c->h != kMaxFastHalfOrder) return fail(FDW_EINVAL, "stepn: the pipelined kernel is built for order 8 only");
     if (mode != FDW_MODE_FWD && mode != FDW_MODE_PLAIN && mode != FDW_MODE_MOD && mode != FDW_MODE_PLAIN_ALL && mode != FDW_MODE_RECV && mode != FDW_MODE_BACK4)
@@ -743,8 +752,11 @@ static int stepn_impl(fdw_ctx* c, int mode, const float* d_p, const float* d_pp,
         for (int i = 0; i < kPipeSteps; i++) a.plev[i] = bk->plev[i];
     }
     if (mode == FDW_MODE_MOD) FDW_TRY(fill_mod(c, a, "stepn", d_rec, rec_z));
-    const int kmode = (mode == FDW_MODE_FWD && d_rec) ? FDW_MODE_FWD_REC : mode;      // FWD with d_rec: the trace rows of the pass's four steps
+    if (d_illum && (mode != FDW_MODE_FWD || d_rec)) return fail(FDW_EINVAL, "stepn: illumination belongs to a plain forward pass");
+    // FWD with d_rec: the trace rows of the pass's four steps; with d_illum: their squares added to the illumination
+    const int kmode = (mode == FDW_MODE_FWD && d_rec) ? FDW_MODE_FWD_REC : ((mode == FDW_MODE_FWD && d_illum) ? FDW_MODE_FWD_ILLUM : mode);
     if (kmode == FDW_MODE_FWD_REC) fill_rec(c, a, d_rec, rec_z);
+    if (kmode == FDW_MODE_FWD_ILLUM) a.img = d_illum;
     a.inj = d_inj + in.shift; a.inj_x = in.x; a.inj_z = inj_z; a.inj_n = in.n;
     const int ncells = c->pitch / 4, own = 64 - 2 * kPipeSteps;
     a.nstrip = (ncells + own - 1) / own;
@@ -851,9 +863,10 @@ extern "C" int fdw_dev_step4(fdw_ctx* c, const float* d_p, const float* d_pp, co
 // nsteps reference iterations (R:259-267) over four rotating buffers: kPipeSteps per pass through the wave pipeline, pairs of steps through
 // the two-step kernel, single steps through the one-step kernel, whichever pays.  On entry buf[*ip], buf[*ipp] are the reference's (d_p, d_pp)
 // BEFORE the first swap; on return they index (d_p, d_pp) after the loop.  d_rec: NULL, or the trace rows [it][nx] (fdw_dev_record_steps):
-// the same passes, each through its kernel's recording variant.
+// the same passes, each through its kernel's recording variant.  d_illum: NULL, or the source illumination (fdw_dev_illum_steps): the same
+// passes, each through its kernel's illumination variant (not together with d_rec).
 static int steps_loop(fdw_ctx* c, float* const* buf, const float* d_v2, const float* d_srce, int sx, int sz, int gz, float* d_rec, int it0, int nsteps,
-                      int first_pp_twice, int* ip, int* ipp, hipStream_t s)
+                      int first_pp_twice, int* ip, int* ipp, hipStream_t s, float* d_illum = nullptr)
 {
     if (!c || !buf || !ip || !ipp) return fail(FDW_EINVAL, "NULL argument");
     if (*ip < 0 || *ip > 3 || *ipp < 0 || *ipp > 3 || *ip == *ipp) return fail(FDW_EINVAL, "steps2: bad buffer indices");
@@ -875,17 +888,19 @@ static int steps_loop(fdw_ctx* c, float* const* buf, const float* d_v2, const fl
         int o1, o2;   // the two buffers not holding the current pair
         spare_pair(*ip, *ipp, &o1, &o2);
         if (nsteps - k >= kPipeSteps && pipe_pays(c)) {
-            FDW_TRY(stepn_impl(c, FDW_MODE_FWD, buf[*ipp], buf[*ip], d_v2, buf[o1], buf[o2], twice, inj, sxx, sz, s, RowRanges{}, rec, gz));
+            FDW_TRY(stepn_impl(c, FDW_MODE_FWD, buf[*ipp], buf[*ip], d_v2, buf[o1], buf[o2], twice, inj, sxx, sz, s, RowRanges{}, rec, gz, nullptr,
+                                d_illum));
             *ip = o1; *ipp = o2;   // d_p = u^{n+kPipeSteps-1}, d_pp = u^{n+kPipeSteps}
             k += kPipeSteps;
         } else if (nsteps - k >= 2 && two_step_pays(c)) {
             // after the swap the kernel's p is the old d_pp (newest field), its pp the old d_p
-            FDW_TRY(step2_impl(c, FDW_MODE_FWD, buf[*ipp], buf[*ip], d_v2, buf[o1], buf[o2], twice, inj, sxx, sz, Step2Extra{}, s, rec, gz));
+            FDW_TRY(step2_impl(c, FDW_MODE_FWD, buf[*ipp], buf[*ip], d_v2, buf[o1], buf[o2], twice, inj, sxx, sz, Step2Extra{}, s, rec, gz, d_illum));
             *ip = o1; *ipp = o2;   // d_p = u^{n+1}, d_pp = u^{n+2}
             k += 2;
         } else {
             std::swap(*ip, *ipp);
-            FDW_TRY(step_impl(c, FDW_MODE_FWD, buf[*ip], buf[*ipp], d_v2, 0, c->nxl, twice, inj, sxx, sz, nullptr, nullptr, s, rec, gz));
+            FDW_TRY(step_impl(c, FDW_MODE_FWD, buf[*ip], buf[*ipp], d_v2, 0, c->nxl, twice, inj, sxx, sz, nullptr, nullptr, s, rec, gz, nullptr, nullptr,
+                               d_illum));
             k += 1;
         }
     }
@@ -914,6 +929,24 @@ extern "C" int fdw_dev_record_steps(fdw_ctx* c, float* const* d_buf, const float
     if (it0 < 0) return fail(FDW_EINVAL, "it0=%d", it0);
     FDW_TRY(check_record_depth(c, gz));
     return steps_loop(c, d_buf, d_v2, d_srce, sx, sz, gz, d_rec, it0, nsteps, first_pp_twice, ip, ipp, pick_stream(c, stream));
+}
+
+// the forward loop with source illumination: the RTM dialect on the whole grid
+static int check_illum_ctx(const fdw_ctx* c, const char* who)
+{
+    if (c->prm.dialect != FDW_DIALECT_RTM) return fail(FDW_ESTATE, "%s: source illumination belongs to the RTM dialect", who);
+    if (!is_full_grid(c)) return fail(FDW_ESTATE, "%s: source illumination needs a full-grid context (slab-decomposed shots are not covered)", who);
+    if (c->nbatch > 1) return fail(FDW_ESTATE, "%s: not inside a batch of shots", who);
+    return FDW_OK;
+}
+
+extern "C" int fdw_dev_illum_steps(fdw_ctx* c, float* const* d_buf, const float* d_v2, const float* d_srce, int sx, int sz, float* d_illum, int it0,
+                                   int nsteps, int first_pp_twice, int* ip, int* ipp, void* stream)
+{
+    if (!c || !d_illum) return fail(FDW_EINVAL, "NULL argument");
+    if (it0 < 0) return fail(FDW_EINVAL, "it0=%d", it0);
+    FDW_TRY(check_illum_ctx(c, "fdw_dev_illum_steps"));
+    return steps_loop(c, d_buf, d_v2, d_srce, sx, sz, 0, nullptr, it0, nsteps, first_pp_twice, ip, ipp, pick_stream(c, stream), d_illum);
 }
 
 // ksteps-cycle of the slab decomposition in one call: step j (1-based, j = j0 .. j0+nsteps-1) updates the
@@ -1053,10 +1086,10 @@ static int upload_source(fdw_ctx* c, const float* srce, int n)
 
 // fd_forward's loop body R:259-267 for nsteps iterations over the context's four field buffers (pairs of steps go
 // through the two-step kernel where it pays); *ip / *ipp index (d_p, d_pp) before the loop and after it.  d_rec: trace rows [nt][nx] at gz.
-static int forward_loop(fdw_ctx* c, int* ip, int* ipp, int sx, int sz, int nsteps, int gz = 0, float* d_rec = nullptr)
+static int forward_loop(fdw_ctx* c, int* ip, int* ipp, int sx, int sz, int nsteps, int gz = 0, float* d_rec = nullptr, float* d_illum = nullptr)
 {
     FDW_RANGE("fdw: forward loop (fd_forward)");
-    int rc = steps_loop(c, c->fld, c->d_v2, c->d_srce, sx, sz, gz, d_rec, 0, nsteps, 0, ip, ipp, c->stream);
+    int rc = steps_loop(c, c->fld, c->d_v2, c->d_srce, sx, sz, gz, d_rec, 0, nsteps, 0, ip, ipp, c->stream, d_illum);
     if (rc) return rc;
     if (nsteps > 0) return fdw_dev_taper_finalize(c, c->fld[*ip], c->stream);   // the T() d_p still owes (R:285 downloads the damped d_p)
     return FDW_OK;
@@ -1099,17 +1132,18 @@ static int upload_gather(fdw_ctx* c, const float* d_obs)
     return gathers_to_device(c, d_obs, c->d_dobs, 1);
 }
 
-static int image_to_device(fdw_ctx* c, const float* imloc)
+static int image_to_device(fdw_ctx* c, const float* imloc, float* d_dst = nullptr)
 {
-    HIP_TRY(hipMemsetAsync(c->d_img, 0, field_elems(c) * sizeof(float), c->stream));
-    float* dst = c->d_img + (size_t)c->prm.nxb * c->pitch + c->prm.nzb;
+    if (!d_dst) d_dst = c->d_img;
+    HIP_TRY(hipMemsetAsync(d_dst, 0, field_elems(c) * sizeof(float), c->stream));
+    float* dst = d_dst + (size_t)c->prm.nxb * c->pitch + c->prm.nzb;
     HIP_TRY(hipMemcpy2DAsync(dst, (size_t)c->pitch * sizeof(float), imloc, (size_t)c->nz * sizeof(float),
                              (size_t)c->nz * sizeof(float), c->nx, hipMemcpyHostToDevice, c->stream));
     return FDW_OK;
 }
-static int image_to_host(fdw_ctx* c, float* imloc)
+static int image_to_host(fdw_ctx* c, float* imloc, const float* d_src = nullptr)
 {
-    const float* src = c->d_img + (size_t)c->prm.nxb * c->pitch + c->prm.nzb;
+    const float* src = (d_src ? d_src : c->d_img) + (size_t)c->prm.nxb * c->pitch + c->prm.nzb;
     HIP_TRY(hipMemcpy2DAsync(imloc, (size_t)c->nz * sizeof(float), src, (size_t)c->pitch * sizeof(float),
                              (size_t)c->nz * sizeof(float), c->nx, hipMemcpyDeviceToHost, c->stream));
     return FDW_OK;
@@ -1216,7 +1250,9 @@ extern "C" int fdw_back(fdw_ctx* c, const float* v2, const float* snap0, const f
 }
 
 // v2 == nullptr: the squared model already resident in c->d_v2 (fdw_dev_extendvel_linear)
-static int shot_impl(fdw_ctx* c, const float* v2, int sx, int sz, int gz, const float* srce, const float* d_obs, float* imloc, float* P, float* PP)
+// illum: NULL, or the interior illumination [nx][nz] the forward loop accumulates into (fdw_shot_illum)
+static int shot_impl(fdw_ctx* c, const float* v2, int sx, int sz, int gz, const float* srce, const float* d_obs, float* imloc, float* P, float* PP,
+                     float* illum = nullptr)
 {
     if (!c || !srce || !d_obs || !imloc) return fail(FDW_EINVAL, "NULL argument");
     FDW_RANGE("fdw: shot (uploads, forward, backward, image download)");
@@ -1232,7 +1268,9 @@ static int shot_impl(fdw_ctx* c, const float* v2, int sx, int sz, int gz, const 
     if ((v2 && (rc = upload_rows(c, c->d_v2, v2, c->stream))) || (rc = upload_source(c, srce, nt)) || (rc = upload_gather(c, d_obs)) ||
         (rc = image_to_device(c, imloc)))
         return rc;
-    if ((rc = forward_loop(c, &ip, &ipp, sx, sz, nt))) return rc;
+    if (illum && ((rc = alloc_zero(&c->d_illum, field_elems(c))) || (rc = image_to_device(c, illum, c->d_illum)))) return rc;
+    if ((rc = forward_loop(c, &ip, &ipp, sx, sz, nt, 0, nullptr, illum ? c->d_illum : nullptr))) return rc;
+    if (illum && (rc = image_to_host(c, illum, c->d_illum))) return rc;
     if (P && (rc = download_rows(c, P, c->fld[ip], c->stream))) return rc;
     if (PP && (rc = download_rows(c, PP, c->fld[ipp], c->stream))) return rc;
     float* src[4];
@@ -1250,6 +1288,15 @@ extern "C" int fdw_shot(fdw_ctx* c, const float* v2, int sx, int sz, int gz, con
     if (!v2) return fail(FDW_EINVAL, "NULL argument");
     if (c) c->v2_resident = false;
     return shot_impl(c, v2, sx, sz, gz, srce, d_obs, imloc, P, PP);
+}
+
+extern "C" int fdw_shot_illum(fdw_ctx* c, const float* v2, int sx, int sz, int gz, const float* srce, const float* d_obs, float* imloc,
+                              float* illum, float* P, float* PP)
+{
+    if (!c || !v2 || !illum) return fail(FDW_EINVAL, "NULL argument");
+    FDW_TRY(check_illum_ctx(c, "fdw_shot_illum"));
+    c->v2_resident = false;
+    return shot_impl(c, v2, sx, sz, gz, srce, d_obs, imloc, P, PP, illum);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1870,6 +1917,15 @@ extern "C" int fdw_shot_resident(fdw_ctx* c, int sx, int sz, int gz, const float
     if (!c) return fail(FDW_EINVAL, "ctx is NULL");
     if (!c->v2_resident) return fail(FDW_ESTATE, "no resident squared model: call fdw_dev_extendvel_linear first");
     return shot_impl(c, nullptr, sx, sz, gz, srce, d_obs, imloc, P, PP);
+}
+
+extern "C" int fdw_shot_resident_illum(fdw_ctx* c, int sx, int sz, int gz, const float* srce, const float* d_obs, float* imloc, float* illum,
+                                       float* P, float* PP)
+{
+    if (!c || !illum) return fail(FDW_EINVAL, "NULL argument");
+    FDW_TRY(check_illum_ctx(c, "fdw_shot_resident_illum"));
+    if (!c->v2_resident) return fail(FDW_ESTATE, "no resident squared model: call fdw_dev_extendvel_linear first");
+    return shot_impl(c, nullptr, sx, sz, gz, srce, d_obs, imloc, P, PP, illum);
 }
 
 // ------------------------------------------------------------------------------------------------

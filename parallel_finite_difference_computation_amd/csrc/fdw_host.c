@@ -186,6 +186,23 @@ void fdw_extendvel_linear(int nx, int nz, int nxb, int nzb, float *vel)
 #undef AT
 }
 
+/* ---- source-illumination compensation of an RTM image (fdwave.h) -----------------------------------------------------
+ * m = max illum (from 0.0f, '>' comparisons: a NaN never wins), s = eps * m, d = illum + s, out = d > 0 ? img / d : 0.0f; every
+ * operation an individually rounded fp32 one (the file is built with -ffp-contract=off).  out may alias img. */
+int fdw_image_compensate(const float *img, const float *illum, size_t n, float eps, float *out)
+{
+    if (!img || !illum || !out || !(eps >= 0.0f) || isinf(eps)) return FDW_EINVAL;
+    float m = 0.0f;
+    for (size_t i = 0; i < n; i++)
+        if (illum[i] > m) m = illum[i];
+    const float s = eps * m;
+    for (size_t i = 0; i < n; i++) {
+        const float d = illum[i] + s;
+        out[i] = d > 0.0f ? img[i] / d : 0.0f;
+    }
+    return FDW_OK;
+}
+
 /* ---- forward-modelling producer of the CPU-serial sibling (DD = dpct_gpu_rtm_domain_division/src) --------------------
  * DD builds its .c files with g++ (every Makefile there sets CC = g++ -fpermissive), so exp(float) is the float overload. */
 

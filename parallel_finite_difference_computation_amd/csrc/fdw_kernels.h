@@ -15,6 +15,7 @@ enum {
     FDW_MODE_BACK4 = 9,  // wave-pipeline kernel only: four whole iterations of fd_back in one pass of an eight-wave workgroup (source + receiver fields)
     FDW_MODE_PLAIN_ALL = 8, // wave-pipeline kernel only: PLAIN with all four time levels stored (source field of the backward loop)
     FDW_MODE_FWD_REC = 10, // launchers only: FWD + the trace sample of every step on the receiver line (fdw_dev_record_steps; StepArgs / Step2Args rec*)
+    FDW_MODE_FWD_ILLUM = 11, // launchers only: FWD + the source illumination, illum += new field (*) new field over the update extents (fdw_dev_illum_steps; the accumulator travels in `img`)
     FDW_MODE_DD_RECV = 6 // its receiver pass (rtm_main.cpp:197-220) + img += stored source field * CURRENT receiver field (rtm_main.cpp:224-230)
 };
 
@@ -31,7 +32,7 @@ struct StepArgs {
     const float* psrc;     // IMG: source wavefield to correlate with; BACK: F_{k-1}, the newer source field (read only)
     float* fpp;            // BACK: F_{k-2}, overwritten with the reconstructed F_k
     int img_z1;            // IMG: columns >= img_z1 lie outside kernel_img's launch extent (R:133-144) and keep their image value
-    float* img;            // IMG: image accumulator on the extended grid
+    float* img;            // IMG: image accumulator on the extended grid; FWD_ILLUM: the illumination accumulator
     const float* taperz;   // [ztap] z damping factors
     const float* txfac;    // [nxl] per-row x damping factor (1.0f where none applies)
     const float* inj;      // INJ=1: one source sample; INJ=2: inj_n receiver samples of this step
@@ -76,7 +77,7 @@ struct Step2Args {
     const float* inj2;     // RECV: receiver samples of iteration it+1 (step 2)
     const float* psrc_a;   // RECV: source wavefield of iteration it   (imaged against u^{n+1})
     const float* psrc_b;   // RECV: source wavefield of iteration it+1 (imaged against u^{n+2})
-    float* img;            // RECV: image accumulator on the extended grid (in place, owned cells only)
+    float* img;            // RECV: image accumulator on the extended grid (in place, owned cells only); FWD_ILLUM: the illumination accumulator
     int img_z1;            // RECV: columns >= img_z1 lie outside kernel_img's launch extent and keep their image value
     int pitch, nxl;
     int r0, r1;            // rows whose u^{n+1}, u^{n+2} this launch produces
@@ -123,6 +124,8 @@ hipError_t launch_step_fast(const StepArgs& a, int half_order, int mode, int pre
 hipError_t launch_step_generic(const StepArgs& a, int half_order, int mode, hipStream_t s);
 hipError_t launch_taper_finalize(float* f, const float* taperz, const float* txfac, int pitch, int nxl, int ztap,
                                  int tz_x1, hipStream_t s);
+// source illumination of the orders without a register-ring kernel: illum += f (*) f on rows [r0, r1), columns < z1 (fdw_illum_add_kernel)
+hipError_t launch_illum_add(const float* f, float* illum, int pitch, int r0, int r1, int z1, hipStream_t s);
 hipError_t launch_selftest(const float* src, float* out, hipStream_t s);
 // receiver rows the reference injects and images but never time-steps (truncated launch extents with a narrow x border): see fdw_static_rows_kernel
 // trace samples of receiver rows the loop never time-steps: see fdw_record_static_kernel

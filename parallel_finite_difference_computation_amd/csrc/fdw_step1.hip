@@ -25,6 +25,8 @@ namespace fdw {
 //   DD      arithmetic of the CPU-serial sibling's fd_step (single accumulator, per-term scaling) + one trace sample per row
 //   PF      software prefetch distance in rows
 //   REC     trace recording of the RTM dialect's forward loop: the new field at column rec_z of every receiver row (fdw_step_rec_kernel)
+//   ILL     source illumination of the forward loop: sv.img += new field (*) new field on the updated cells, product and sum rounded
+//           separately (fdw_step_illum_kernel); the row of the accumulator rides the image queue
 // block = 256 threads = 4 independent waves (no LDS, no barrier).
 //
 // ONE code path for every tile.  Every global load of the march is unconditional (addresses are
@@ -49,7 +51,7 @@ struct ShotView {
     float* rec;
 };
 
-template <int H, bool TAPER, int INJ, bool IMG, bool LAPONLY, int PF, bool DD = false, bool BACK = false, int NUM = 0, bool REC = false>
+template <int H, bool TAPER, int INJ, bool IMG, bool LAPONLY, int PF, bool DD = false, bool BACK = false, int NUM = 0, bool REC = false, bool ILL = false>
 __device__ __forceinline__ void march(const StepArgs& a, const ShotView& sv, const int lane, const int zs, const int xa, const int xe)
 {
     // BACK: one whole backward iteration of fd_back (R:317-329) in a single pass: the source field is reconstructed in a second
@@ -161,6 +163,7 @@ __device__ __forceinline__ void march(const StepArgs& a, const ShotView& sv, con
                 if constexpr (!BACK) qps[m] = load_plain(sv.psrc, row);
                 qim[m] = load_plain(sv.img, row);
             }
+            if constexpr (ILL) qim[m] = load_plain(sv.img, row);
             if constexpr (BACK) {
                 fqhal[m] = load_fhalo(row);
                 fqpp[m] = load_plain(sv.fpp, row);
@@ -270,6 +273,15 @@ __device__ __forceinline__ void march(const StepArgs& a, const ShotView& sv, con
                     }
                 }
             }
+            if constexpr (ILL) {
+                // the value squared is the one stored below, source sample included and undamped; cells outside the update extents keep theirs
+#pragma unroll
+                for (int e = 0; e < 4; ++e) imr.v[e] = qim[Q].v[e] + res.v[e] * res.v[e];
+                if (zedge) {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) imr.v[e] = mupd[e] ? imr.v[e] : qim[Q].v[e];
+                }
+            }
             f4 fres;
             if constexpr (BACK) {
                 // ---- the source field's own step on the same row: kernel_lap + kernel_time, no damping, no injection (R:317-318) ----
@@ -309,10 +321,12 @@ __device__ __forceinline__ void march(const StepArgs& a, const ShotView& sv, con
             if (!partial) {
                 f4_store(sv.out + (size_t)r * pitch, voff, res);
                 if constexpr (IMG) f4_store(sv.img + (size_t)r * pitch, voff, imr);
+                if constexpr (ILL) f4_store(sv.img + (size_t)r * pitch, voff, imr);
                 if constexpr (BACK) f4_store(sv.fpp + (size_t)r * pitch, voff, fres);
             } else if (act) {
                 f4_store(sv.out + (size_t)r * pitch, voff, res);
                 if constexpr (IMG) f4_store(sv.img + (size_t)r * pitch, voff, imr);
+                if constexpr (ILL) f4_store(sv.img + (size_t)r * pitch, voff, imr);
                 if constexpr (BACK) f4_store(sv.fpp + (size_t)r * pitch, voff, fres);
             }
             if constexpr (REC) f1_store_arr(array_rsrc(sv.rec, (unsigned)a.rec_n * 4u), rec_offset(rec_lane, r, a.rec_x0, a.rec_n), f4_pick(res, a.rec_z & 3));
@@ -330,6 +344,7 @@ __device__ __forceinline__ void march(const StepArgs& a, const ShotView& sv, con
                     if constexpr (!BACK) qps[Q] = load_plain(sv.psrc, nr);
                     qim[Q] = load_plain(sv.img, nr);
                 }
+                if constexpr (ILL) qim[Q] = load_plain(sv.img, nr);
                 if constexpr (BACK) {
                     fqhal[Q] = load_fhalo(nr);
                     fqpp[Q] = load_plain(sv.fpp, nr);
@@ -411,6 +426,34 @@ __global__ __launch_bounds__(256) void fdw_step_rec_kernel(const StepArgs a)
     march<H, true, 1, false, false, PF, false, false, NUM, true>(a, sv, lane, zs, xa, xe);
 }
 
+// the forward step (FDW_MODE_FWD) that also accumulates the source illumination (FDW_MODE_FWD_ILLUM: a.img is the accumulator, +8 B/point/step).
+// Its own copy of the tile placement, like fdw_step_rec_kernel's.
+template <int H, int PF, int NUM>
+__global__ __launch_bounds__(256) void fdw_step_illum_kernel(const StepArgs a)
+{
+    const int shot = blockIdx.y;
+    const long long o = shot * a.bstride;
+    const ShotView sv{a.p + o, a.pp + o, (a.out ? a.out : a.pp) + o, a.v2 + shot * a.v2_bstride, a.psrc + o, a.fpp + o, a.img + o, a.inj + shot * a.inj_bstride,
+                      a.inj_x + shot * a.inj_dx, a.rec + shot * a.rec_bstride};
+    const int lane = threadIdx.x & 63;
+    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+
+    const int bid = blockIdx.x;
+    const int L = (bid & 7) * a.nper + (bid >> 3);
+    if (L >= a.nblk) return;
+    const int zb = L % a.nzblk;
+    const int xb = L / a.nzblk;
+    const int wz = a.wz;
+    const int strip = zb * wz + (w & (wz - 1));
+    const int chunk = xb * (4 / wz) + (w / wz);
+    const int zs = strip * 256;
+    if (zs >= a.pitch) return;
+    const int xa = a.r0 + chunk * a.xchunk;
+    const int xe = min(xa + a.xchunk, a.r1);
+    if (xa >= xe) return;
+    march<H, true, 1, false, false, PF, false, false, NUM, false, true>(a, sv, lane, zs, xa, xe);
+}
+
 #if FDW_TU == 0
 // ------------------------------------------------------------------------------------------------
 // generic-order kernel: any even order up to FDW_MAX_ORDER, one thread per point, every tap from
@@ -481,6 +524,17 @@ __global__ __launch_bounds__(256) void fdw_generic_kernel(const StepArgs a, int 
 __global__ __launch_bounds__(256) void fdw_generic_rec_kernel(const StepArgs a, int h)
 {
     generic_point<true>(a, h, 1, 1, 0, 0);
+}
+
+// Source illumination behind the generic-order kernel (orders above 8, forced generic): illum += f (*) f with f the field the step just
+// stored, on the cells the step updated.  Product and sum are rounded separately (the file is built with -ffp-contract=off).
+__global__ __launch_bounds__(256) void fdw_illum_add_kernel(const float* f, float* illum, int pitch, int r0, int z1)
+{
+    const int z = blockIdx.x * 256 + threadIdx.x;
+    if (z >= z1) return;
+    const size_t k = (size_t)(r0 + blockIdx.y) * pitch + z;
+    const float u = f[k];
+    illum[k] = illum[k] + u * u;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -580,6 +634,7 @@ static hipError_t launch_fast_hp(const StepArgs& a, int mode, hipStream_t s)
     case FDW_MODE_LAP:   hipLaunchKernelGGL((fdw_step_kernel<H, false, 0, false, true, PF>), grid, block, 0, s, a); break;
     case FDW_MODE_BACK:  hipLaunchKernelGGL((fdw_step_kernel<H, true, 2, true, false, PF, false, true>), grid, block, 0, s, a); break;
     case FDW_MODE_FWD_REC: hipLaunchKernelGGL((fdw_step_rec_kernel<H, PF, 0>), grid, block, 0, s, a); break;
+    case FDW_MODE_FWD_ILLUM: hipLaunchKernelGGL((fdw_step_illum_kernel<H, PF, 0>), grid, block, 0, s, a); break;
     default: return hipErrorInvalidValue;
     }
     return hipGetLastError();
@@ -668,6 +723,7 @@ static hipError_t launch_fastnum_h(const StepArgs& a, int mode, hipStream_t s)
     case FDW_MODE_LAP:   hipLaunchKernelGGL((fdw_step_kernel<H, false, 0, false, true, 2, false, false, 1>), grid, block, 0, s, a); break;
     case FDW_MODE_BACK:  hipLaunchKernelGGL((fdw_step_kernel<H, true, 2, true, false, 2, false, true, 1>), grid, block, 0, s, a); break;
     case FDW_MODE_FWD_REC: hipLaunchKernelGGL((fdw_step_rec_kernel<H, 2, 1>), grid, block, 0, s, a); break;
+    case FDW_MODE_FWD_ILLUM: hipLaunchKernelGGL((fdw_step_illum_kernel<H, 2, 1>), grid, block, 0, s, a); break;
     default: return hipErrorInvalidValue;
     }
     return hipGetLastError();
@@ -697,6 +753,14 @@ hipError_t launch_step_generic(const StepArgs& a, int h, int mode, hipStream_t s
     const int inj = (mode == FDW_MODE_FWD) ? 1 : (mode == FDW_MODE_RECV ? 2 : 0);
     hipLaunchKernelGGL(fdw_generic_kernel, grid, block, 0, s, a, h, taper, inj, mode == FDW_MODE_RECV ? 1 : 0,
                        mode == FDW_MODE_LAP ? 1 : 0);
+    return hipGetLastError();
+}
+
+hipError_t launch_illum_add(const float* f, float* illum, int pitch, int r0, int r1, int z1, hipStream_t s)
+{
+    const int zc = z1 < pitch ? z1 : pitch;
+    if (r1 <= r0 || zc <= 0) return hipSuccess;
+    hipLaunchKernelGGL(fdw_illum_add_kernel, dim3((zc + 255) / 256, r1 - r0), dim3(256), 0, s, f, illum, pitch, r0, zc);
     return hipGetLastError();
 }
 

@@ -22,9 +22,12 @@ namespace fdw {
 // Arithmetic per point and per step is exactly the one-step kernel's (same helpers), hence bit-identical.
 // REC (FDW_MODE_FWD_REC): the two new rows' samples at column rec_z go to rec (step 1) and rec + rec_n (step 2), from owned lanes and the
 // tile's own rows only -- the same conditions as the field stores, so every sample is written once.
+// ILL (FDW_MODE_FWD_ILLUM): a.img += u^{n+1} (*) u^{n+1}, then += u^{n+2} (*) u^{n+2}, on the updated cells.  The accumulator row s is read
+// when u^{n+1}(s) is formed (raw: ring2 holds it damped inside the strip), takes the first square, waits H march steps in LDS next to the
+// parked v2 row (ill_stash), takes the second square and is stored with u^{n+2}: one load and one store per owned row and pass.
 // ------------------------------------------------------------------------------------------------
-template <int H, bool TAPER, int INJ, bool IMG, int PF, int NUM = 0, bool REC = false>
-__device__ __forceinline__ void march2(const Step2Args& a, const int lane, const int cs, const int xa, const int xe, f4* stash)
+template <int H, bool TAPER, int INJ, bool IMG, int PF, int NUM = 0, bool REC = false, bool ILL = false>
+__device__ __forceinline__ void march2(const Step2Args& a, const int lane, const int cs, const int xa, const int xe, f4* stash, f4* ill_stash = nullptr)
 {
     constexpr int R = ((2 * H + PF + PF - 1) / PF) * PF;   // ring turns == unroll factor (10 for H=4, PF=2)
     constexpr int LOOK = R - 2 * H;
@@ -108,6 +111,7 @@ __device__ __forceinline__ void march2(const Step2Args& a, const int lane, const
                 qsb[m] = load_pw(a.psrc_b, s0 + m - H);
                 qim[m] = load_pw(a.img, s0 + m - H);
             }
+            if constexpr (ILL) qim[m] = load_pw(a.img, s0 + m);
         }
         __builtin_amdgcn_sched_barrier(0);
     });
@@ -172,6 +176,12 @@ __device__ __forceinline__ void march2(const Step2Args& a, const int lane, const
                 }
             }
             f4_store_rsrc(a.out1 + rowoff(s), row_bytes, soff1, u1);
+            if constexpr (ILL) {
+                f4 il = qim[Q];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) il.v[e] = (rowupd1 && mupd[e]) ? il.v[e] + u1.v[e] * u1.v[e] : il.v[e];
+                ill_stash[((m & 7) << 6) + lane] = il;
+            }
             if constexpr (REC) f1_store_arr(rs_rec(), rec_offset(rec_lane && live && (s >= xa) && (s < xe), s, a.rec_x0, a.rec_n), f4_pick(u1, a.rec_z & 3));
             if (wave_tap) taper_row(u1, s);                              // as "p" of step 2 it is damped once
             ring2[U] = u1;                                               // row s of u^{n+1}
@@ -215,6 +225,12 @@ __device__ __forceinline__ void march2(const Step2Args& a, const int lane, const
                     }
                 }
                 f4_store_rsrc(a.out2 + rowoff(r), row_bytes, soff2, u2);
+                if constexpr (ILL) {
+                    f4 il = ill_stash[(((m - H) & 7) << 6) + lane];
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) il.v[e] = mupd[e] ? il.v[e] + u2.v[e] * u2.v[e] : il.v[e];
+                    f4_store_rsrc(a.img + rowoff(r), row_bytes, soff2, il);
+                }
                 if constexpr (REC)
                     f1_store_arr(rs_rec(), rec_offset(rec_lane && live && (r >= xa), r, a.rec_x0, a.rec_n) + (unsigned)a.rec_n * 4u, f4_pick(u2, a.rec_z & 3));
                 if constexpr (IMG) {
@@ -240,6 +256,7 @@ __device__ __forceinline__ void march2(const Step2Args& a, const int lane, const
                 qsb[Q] = load_pw(a.psrc_b, r + PF);
                 qim[Q] = load_pw(a.img, r + PF);
             }
+            if constexpr (ILL) qim[Q] = load_pw(a.img, s + PF);
         }
         __builtin_amdgcn_sched_barrier(0);
     };
@@ -281,6 +298,28 @@ __global__ __launch_bounds__(256, 4) void fdw_step2_rec_kernel(const Step2Args a
     step2_tile<4, true, 1, false, 2, NUM, true>(a);
 }
 
+// FDW_MODE_FWD_ILLUM: the forward pass that also accumulates the source illumination of both steps.  Its own tile placement (see
+// fdw_stepn_rec_kernel); 64 KiB of LDS per workgroup (the v2 rows and the accumulator rows in waiting), two workgroups per CU.
+template <int NUM>
+__global__ __launch_bounds__(256, 2) void fdw_step2_illum_kernel(const Step2Args a)
+{
+    const int lane = threadIdx.x & 63;
+    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int bid = blockIdx.x;
+    const int L = (bid & 7) * a.nper + (bid >> 3);
+    if (L >= a.nblk) return;
+    const int zb = L % a.nzblk;
+    const int xb = L / a.nzblk;
+    const int strip = zb * 4 + w;
+    if (strip >= a.nstrip) return;
+    const int xa = a.r0 + xb * a.xchunk;
+    const int xe = min(xa + a.xchunk, a.r1);
+    if (xa >= xe) return;
+    __shared__ f4 v2_stash[4][8 * 64];
+    __shared__ f4 ill_stash[4][8 * 64];
+    march2<4, true, 1, false, 2, NUM, false, true>(a, lane, strip * 60 - 2, xa, xe, v2_stash[w], ill_stash[w]);
+}
+
 hipError_t launch_step2(const Step2Args& a, int h, int mode, hipStream_t s)
 {
     if (a.nper <= 0) return hipSuccess;
@@ -292,6 +331,7 @@ hipError_t launch_step2(const Step2Args& a, int h, int mode, hipStream_t s)
         case FDW_MODE_PLAIN: hipLaunchKernelGGL((fdw_step2_kernel<4, false, 0, false, 2, 1>), grid, block, 0, s, a); break;
         case FDW_MODE_RECV:  hipLaunchKernelGGL((fdw_step2_kernel<4, true, 2, true, 2, 1>), grid, block, 0, s, a); break;
         case FDW_MODE_FWD_REC: hipLaunchKernelGGL((fdw_step2_rec_kernel<1>), grid, block, 0, s, a); break;
+        case FDW_MODE_FWD_ILLUM: hipLaunchKernelGGL((fdw_step2_illum_kernel<1>), grid, block, 0, s, a); break;
         default: return hipErrorInvalidValue;
         }
         return hipGetLastError();
@@ -301,6 +341,7 @@ hipError_t launch_step2(const Step2Args& a, int h, int mode, hipStream_t s)
     case FDW_MODE_PLAIN: hipLaunchKernelGGL((fdw_step2_kernel<4, false, 0, false, 2>), grid, block, 0, s, a); break;
     case FDW_MODE_RECV:  hipLaunchKernelGGL((fdw_step2_kernel<4, true, 2, true, 2>), grid, block, 0, s, a); break;
     case FDW_MODE_FWD_REC: hipLaunchKernelGGL((fdw_step2_rec_kernel<0>), grid, block, 0, s, a); break;
+    case FDW_MODE_FWD_ILLUM: hipLaunchKernelGGL((fdw_step2_illum_kernel<0>), grid, block, 0, s, a); break;
     default: return hipErrorInvalidValue;
     }
     return hipGetLastError();

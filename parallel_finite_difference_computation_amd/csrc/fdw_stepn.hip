@@ -47,12 +47,17 @@ __device__ __forceinline__ int pipe_fifo_slot(int m)
 // NUM: 0 = the reference's exact arithmetic, 1 = FAST numerics (symmetric sums + fused multiply-adds, fdw_device.h)
 // REC: forward loop with trace recording (FDW_MODE_FWD_REC): wave k records its new row u^{n+k+1} at column rec_z into rec + k rec_n, from owned
 // lanes and the tile's own rows [xa, xe) only (the conditions of the field stores), so every sample is written once
-template <int H, int NS, bool TAPER, int INJ, int PF, bool DD = false, int BK = 0, bool LEAN = false, int WK = 0, int NUM = 0, bool REC = false>
+// ILL: forward loop with source illumination (FDW_MODE_FWD_ILLUM): a.img += u^{n+k+1} (*) u^{n+k+1} for k = 0 .. NS-1 in that order on the updated
+// cells.  The accumulator row travels like the image row of BK 2: in at wave 0 from memory, through the imf FIFO from wave to wave, each wave
+// adding the square of the row it has just formed (raw, source sample included), out from the last wave -- owned lanes, the tile's own rows
+template <int H, int NS, bool TAPER, int INJ, int PF, bool DD = false, int BK = 0, bool LEAN = false, int WK = 0, int NUM = 0, bool REC = false, bool ILL = false>
 __device__ __forceinline__ void marchn(const Step2Args& a, const int lane, const int k, const int cs, const int xa, const int xe,
                                        f4 (*link)[2][2][64], f4 (*fifo)[64], f4 (*imf)[64] = nullptr, f4 (*linkx)[2][2][64] = nullptr)
 {
     static_assert(!LEAN || (!TAPER && INJ == 0), "the lean body has no damping, no injection (and records no trace)");
     constexpr bool IMG = (BK == 2 || BK == 4);
+    constexpr bool ACC = IMG || ILL;                          // a row of an accumulator (image, illumination) rides along
+    static_assert(!ILL || (BK == 0 && !DD && !REC), "illumination belongs to the RTM dialect's plain forward pass");
     constexpr int D = (BK == 4) ? 1 : 0;                      // this role runs D march steps behind
     constexpr int DL = (BK >= 3) ? 1 : 0;                     // ... so both roles of the fused kernel loop one step longer
     // one march step per workgroup barrier (two measured slower: DESIGN.md section 3c): a wave consumes what its predecessor produced
@@ -77,8 +82,8 @@ __device__ __forceinline__ void marchn(const Step2Args& a, const int lane, const
     const __amdgpu_buffer_rsrc_t rs_p = array_rsrc(gp, arr_bytes), rs_pp = array_rsrc(gpp, arr_bytes), rs_v2 = array_rsrc(a.v2, arr_bytes);
     const __amdgpu_buffer_rsrc_t rs_out = array_rsrc((k == NS - 1) ? go2 : ((BK == 1 && k < NS - 2) ? (k == 0 ? a.lvl0 : a.lvl1) : go1), arr_bytes);
     // BK 2: this wave's source-field level and, for wave 0 / the last wave, the image
-    const __amdgpu_buffer_rsrc_t rs_lev = array_rsrc(BK == 2 ? a.plev[k] : gp, arr_bytes), rs_img = array_rsrc(IMG ? a.img : go1, arr_bytes);
-    const unsigned ioff = (IMG && own) ? voff : kLaneOff;                 // imaging: owned lanes only
+    const __amdgpu_buffer_rsrc_t rs_lev = array_rsrc(BK == 2 ? a.plev[k] : gp, arr_bytes), rs_img = array_rsrc(ACC ? a.img : go1, arr_bytes);
+    const unsigned ioff = (ACC && own) ? voff : kLaneOff;                 // imaging: owned lanes only
 
     const bool wave_tap = TAPER && (cs * 4 < a.ztap);
     const bool xtap = wave_tap && ((xa - NS * H < a.xt_lo) || (xe + NS * H > a.xt_hi));
@@ -134,8 +139,8 @@ __device__ __forceinline__ void marchn(const Step2Args& a, const int lane, const
     const int kp = max(k - 1, 0);
     f4 ring[R];
     f4 qpp[PF], qv2[PF];
-    f4 qlv[BK == 2 ? PF : 1], qim[IMG ? PF : 1];                        // BK 2: this wave's source-field rows; BK 2, 4: (wave 0) the image rows, PF steps ahead
-    const unsigned imoff = (IMG && first) ? ioff : kLaneOff;              // only wave 0 reads the image
+    f4 qlv[BK == 2 ? PF : 1], qim[ACC ? PF : 1];                        // BK 2: this wave's source-field rows; BK 2, 4: (wave 0) the image rows, PF steps ahead
+    const unsigned imoff = (ACC && first) ? ioff : kLaneOff;              // only wave 0 reads the image
     bool zim[4];
 #pragma unroll
     for (int e = 0; e < 4; ++e) zim[e] = (z0 + e >= 0) && (z0 + e < a.img_z1);
@@ -154,6 +159,7 @@ __device__ __forceinline__ void marchn(const Step2Args& a, const int lane, const
             if constexpr (BK != 4) qv2[mm] = load_pw(rs_v2, s0 + mm);
             if constexpr (BK == 2) qlv[mm] = f4_load_arr(rs_lev, ioff, rowoff(rk + mm), true);
             if constexpr (IMG) qim[mm] = f4_load_arr(rs_img, imoff, rowoff(rk + mm), true);
+            if constexpr (ILL && WK != 2) qim[mm] = f4_load_arr(rs_img, imoff, rowoff(rk + mm), true);
         }
         __builtin_amdgcn_sched_barrier(0);
     });
@@ -188,7 +194,7 @@ __device__ __forceinline__ void marchn(const Step2Args& a, const int lane, const
         }
         f4 u;
         float im0, im1, im2, im3;                               // the image row (BK 2, 4), as scalars: defined on every path without an instruction
-        if constexpr (IMG) asm volatile("" : "=v"(im0), "=v"(im1), "=v"(im2), "=v"(im3));
+        if constexpr (ACC) asm volatile("" : "=v"(im0), "=v"(im1), "=v"(im2), "=v"(im3));
         if (act) {
         // pp and v2 of this row live in the look-ahead queue's registers: wave 0 finds them there (loaded PF steps ago), the other waves
         // read theirs from LDS into the same registers (their own look-ahead loads are switched off and return nothing they need)
@@ -268,6 +274,19 @@ __device__ __forceinline__ void marchn(const Step2Args& a, const int lane, const
             if (k < NS - 1) imf[r & 15][lane] = im;
             im0 = im.v[0]; im1 = im.v[1]; im2 = im.v[2]; im3 = im.v[3];
         }
+        if constexpr (ILL) {
+            // the square of the row as it is stored and handed on (the window rows are damped copies); product and sum rounded separately
+            f4 il;
+            if (first) il = qim[Q];
+            else il = imf[r & 15][lane];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const float sq = u.v[e] * u.v[e];
+                il.v[e] = (LEAN || (rowupd && mupd[e])) ? il.v[e] + sq : il.v[e];
+            }
+            if (k < NS - 1) imf[r & 15][lane] = il;
+            im0 = il.v[0]; im1 = il.v[1]; im2 = il.v[2]; im3 = il.v[3];
+        }
         if constexpr (INJ == 3) {
             if (inj_here && r >= a.inj_x - 3 && r <= a.inj_x + 3) {
                 const int dxa = r > a.inj_x ? r - a.inj_x : a.inj_x - r;
@@ -292,7 +311,7 @@ __device__ __forceinline__ void marchn(const Step2Args& a, const int lane, const
         if constexpr (REC)
             f1_store_arr(array_rsrc(a.rec + (size_t)k * a.rec_n, (unsigned)a.rec_n * 4u),
                          rec_offset(rec_lane && act && (r >= xa) && (r < xe) && (m < M), r, a.rec_x0, a.rec_n), f4_pick(u, a.rec_z & 3));
-        if constexpr (IMG) {
+        if constexpr (ACC) {
             const unsigned sim = (k == NS - 1 && act && (r >= xa) && (r < xe)) ? ioff : kLaneOff;
             f4 im;
             im.v[0] = im0; im.v[1] = im1; im.v[2] = im2; im.v[3] = im3;
@@ -304,6 +323,7 @@ __device__ __forceinline__ void marchn(const Step2Args& a, const int lane, const
         if constexpr (BK != 4) qv2[Q] = load_pw(rs_v2, s0 + m + PF);
         if constexpr (BK == 2) qlv[Q] = f4_load_arr(rs_lev, ioff, rowoff(r + PF), true);
         if constexpr (IMG) qim[Q] = f4_load_arr(rs_img, imoff, rowoff(r + PF), true);
+        if constexpr (ILL && WK != 2) qim[Q] = f4_load_arr(rs_img, imoff, rowoff(r + PF), true);
         __syncthreads();
     };
 
@@ -404,6 +424,36 @@ __global__ __launch_bounds__(64 * kPipeSteps, kDDWG) void fdw_stepn_rec_kernel(c
     else marchn<H, NS, true, 1, PF, false, 0, false, 0, NUM, true>(a, lane, k, cs, xa, xe, link, fifo);
 }
 
+// FDW_MODE_FWD_ILLUM: the forward pass that also accumulates the source illumination of its kPipeSteps steps (a.img).  Every tile carries the
+// accumulator row: the lean tiles add the squares without masks, the tiles on the frame, the damped strip or the source with the update masks
+// of the full body.  16 KiB of LDS more than fdw_stepn_kernel (48 KiB): three workgroups per CU, so up to 168 VGPRs.  Its own tile placement
+// (see fdw_stepn_rec_kernel).
+template <int NUM>
+__global__ __launch_bounds__(64 * kPipeSteps, 3) void fdw_stepn_illum_kernel(const Step2Args a)
+{
+    constexpr int H = 4, NS = kPipeSteps, PF = kPipePF;
+    const int lane = threadIdx.x & 63;
+    const int k = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int bid = blockIdx.x;
+    const int L = (bid & 7) * a.nper + (bid >> 3);
+    if (L >= a.nblk) return;
+    const int zb = L % a.nstrip;
+    const int xb = L / a.nstrip;
+    const bool second = xb >= a.chunks_a;
+    const int xa = second ? a.r0b + (xb - a.chunks_a) * a.xchunk : a.r0 + xb * a.xchunk;
+    const int xe = min(xa + a.xchunk, second ? a.r1b : a.r1);
+    if (xa >= xe) return;
+    __shared__ f4 link[NS][2][2][64];
+    __shared__ f4 fifo[pipe_fifo_rows(NS, H)][64];
+    __shared__ f4 ilf[16][64];                             // accumulator rows on their way from wave to wave (3 (H + 1) = 15 steps under way)
+    const int cs = zb * (64 - 2 * NS) - NS;
+    if (pipe_lean<H, NS, true, 1>(a, cs, xa, xe)) {
+        if (k == 0) marchn<H, NS, false, 0, PF, false, 0, true, 1, NUM, false, true>(a, lane, k, cs, xa, xe, link, fifo, ilf);
+        else marchn<H, NS, false, 0, PF, false, 0, true, 2, NUM, false, true>(a, lane, k, cs, xa, xe, link, fifo, ilf);
+    }
+    else marchn<H, NS, true, 1, PF, false, 0, false, 0, NUM, false, true>(a, lane, k, cs, xa, xe, link, fifo, ilf);
+}
+
 // Four iterations of the backward loop in ONE pass: a workgroup of eight waves, waves 0-3 the pipeline of the source field (role 3), waves 4-7
 // the pipeline of the receiver field one march step behind (role 4).  The source-field levels never leave the chip: the receiver wave of
 // level k reads F_{it+k}(row) from the link buffer the source-field wave k wrote it to for its own successor.  6 fields in + 5 out per
@@ -455,6 +505,7 @@ hipError_t launch_stepn(const Step2Args& a, int h, int mode, hipStream_t s)
         switch (mode) {
         case FDW_MODE_FWD:   hipLaunchKernelGGL((fdw_stepn_kernel<4, kPipeSteps, true, 1, kPipePF, false, 0, 1>), grid, block, 0, s, a); break;
         case FDW_MODE_FWD_REC: hipLaunchKernelGGL((fdw_stepn_rec_kernel<1>), grid, block, 0, s, a); break;
+        case FDW_MODE_FWD_ILLUM: hipLaunchKernelGGL((fdw_stepn_illum_kernel<1>), grid, block, 0, s, a); break;
         case FDW_MODE_PLAIN: hipLaunchKernelGGL((fdw_stepn_kernel<4, kPipeSteps, false, 0, kPipePF, false, 0, 1>), grid, block, 0, s, a); break;
         case FDW_MODE_MOD:   hipLaunchKernelGGL((fdw_stepn_kernel<4, kPipeSteps, true, 3, kPipePF, true, 0, 1>), grid, block, 0, s, a); break;
         case FDW_MODE_PLAIN_ALL: hipLaunchKernelGGL((fdw_stepn_kernel<4, kPipeSteps, false, 0, kPipePF, false, 1, 1>), grid, block, 0, s, a); break;
@@ -467,6 +518,7 @@ hipError_t launch_stepn(const Step2Args& a, int h, int mode, hipStream_t s)
     switch (mode) {
     case FDW_MODE_FWD:   hipLaunchKernelGGL((fdw_stepn_kernel<4, kPipeSteps, true, 1, kPipePF>), grid, block, 0, s, a); break;
     case FDW_MODE_FWD_REC: hipLaunchKernelGGL((fdw_stepn_rec_kernel<0>), grid, block, 0, s, a); break;
+    case FDW_MODE_FWD_ILLUM: hipLaunchKernelGGL((fdw_stepn_illum_kernel<0>), grid, block, 0, s, a); break;
     case FDW_MODE_PLAIN: hipLaunchKernelGGL((fdw_stepn_kernel<4, kPipeSteps, false, 0, kPipePF>), grid, block, 0, s, a); break;
     case FDW_MODE_MOD:   hipLaunchKernelGGL((fdw_stepn_kernel<4, kPipeSteps, true, 3, kPipePF, true>), grid, block, 0, s, a); break;
     case FDW_MODE_PLAIN_ALL: hipLaunchKernelGGL((fdw_stepn_kernel<4, kPipeSteps, false, 0, kPipePF, false, 1>), grid, block, 0, s, a); break;

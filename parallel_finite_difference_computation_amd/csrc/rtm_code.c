@@ -12,7 +12,13 @@
  * Several GPUs (no counterpart in the reference, which drives one): the deck key `slabs=N` (or FDW_SLABS=N in the environment) runs every
  * shot on N GPUs, the grid cut into N bands of rows with halo exchange over RCCL / xGMI inside libfdwave.so (fdw_slabs_shot), one host
  * thread per GPU; FDW_SLABS_LOCAL=1 keeps all N ranks on GPU 0 with device copies instead of RCCL (tests on a one-GPU box).  `gpus=N` (or
- * FDW_GPUS=N) deals whole shots to N GPUs instead.  Every output file is byte for byte the one-GPU program's. */
+ * FDW_GPUS=N) deals whole shots to N GPUs instead.  Every output file is byte for byte the one-GPU program's.
+ *
+ * Source illumination (no counterpart in the reference): the deck key `illum=1` makes every shot's forward loop accumulate sum_t F_t^2
+ * (fdw_shot_illum; per shot from zero, stacked on the host in shot order like the image) and adds two outputs, <tmpdir>/dir.illum (the
+ * stack, [nx][nz]) and <tmpdir>/dir.image_illum = fdw_image_compensate(image, illumination, illum_eps), `illum_eps` defaulting to 1e-3.
+ * dir.image, dir.image_lap and image.num are what they are without the key.  Shots then go one by one per worker (no fdw_shot_batch);
+ * together with slabs > 1 the key is refused. */
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -55,6 +61,7 @@ typedef struct {
     long long draws;      /* rand() calls one extendvel_linear consumes */
     int dev_border;
     float *imloc_all;
+    float *illoc_all;     /* illum=1: the shots' source illumination [nb][nx][nz], else NULL */
     size_t ne, ni;
     int gpus;             /* workers are dealt to GPUs 0 .. gpus-1 */
     volatile int failed;
@@ -82,11 +89,15 @@ static void *shot_worker(void *p)
         const int is = j->is0 + b;
         const float *d_obs = j->d_obs + (size_t)is * j->nx * j->nt;
         float *imloc = j->imloc_all + (size_t)b * j->ni;
+        float *illoc = j->illoc_all ? j->illoc_all + (size_t)b * j->ni : NULL;
         int rc;
         if (j->dev_border) {
             /* R:486-494 in HBM: shot `is` of the serial program consumes draws [is T, (is + 1) T) of the unseeded rand() stream */
             rc = fdw_dev_extendvel_linear(ctx, (unsigned long long)is * (unsigned long long)j->draws, NULL);
-            if (rc == FDW_OK) rc = fdw_shot_resident(ctx, j->sx[is], j->sz, j->gz, j->srce, d_obs, imloc, NULL, NULL);
+            if (rc == FDW_OK && illoc) rc = fdw_shot_resident_illum(ctx, j->sx[is], j->sz, j->gz, j->srce, d_obs, imloc, illoc, NULL, NULL);
+            else if (rc == FDW_OK) rc = fdw_shot_resident(ctx, j->sx[is], j->sz, j->gz, j->srce, d_obs, imloc, NULL, NULL);
+        } else if (illoc) {
+            rc = fdw_shot_illum(ctx, j->vel2_all + (size_t)b * j->ne, j->sx[is], j->sz, j->gz, j->srce, d_obs, imloc, illoc, NULL, NULL);
         } else {
             rc = fdw_shot(ctx, j->vel2_all + (size_t)b * j->ne, j->sx[is], j->sz, j->gz, j->srce, d_obs, imloc, NULL, NULL);
         }
@@ -212,6 +223,23 @@ int main(int argc, char **argv)
     if (nxb == -1) nxb = 40;
     if (fac == -1.0f) fac = 0.7f;
     (void)iss;
+    /* our extension (absent or 0: nothing changes): source illumination and the compensated image.  Slab-decomposed shots do not
+     * accumulate it: refused here, before any file, thread, communicator or device is touched */
+    const int illum = fdw_deck_int(deck, "illum") == 1;
+    float illum_eps = fdw_deck_float(deck, "illum_eps");
+    if (illum_eps == -1.0f) illum_eps = 1.0e-3f;
+    if (illum) {
+        int sl = fdw_deck_int(deck, "slabs");
+        if (getenv("FDW_SLABS")) sl = atoi(getenv("FDW_SLABS"));
+        if (sl > 1) {
+            fprintf(stderr, "illum=1 cannot be combined with slabs=%d: slab-decomposed shots do not accumulate the source illumination\n", sl);
+            return EXIT_FAILURE;
+        }
+        if (!(illum_eps >= 0.0f) || illum_eps > 3.0e38f) {
+            fprintf(stderr, "illum_eps=%g: must be finite and >= 0\n", (double)illum_eps);
+            return EXIT_FAILURE;
+        }
+    }
 
     printf("## vp = %s, d_obs = %s, vel_ext_file = %s, vel_ext_flag = %d \n", vpfile, datfile, vel_ext_file, vel_ext_flag);
     printf("## nz = %d, nx = %d, nt = %d \n", nz, nx, nt);
@@ -342,7 +370,7 @@ int main(int argc, char **argv)
      * the chip for this geometry, 1 = the grid is big enough by itself).  FDW_NO_SHOT_BATCH=1 keeps one shot per launch sequence. */
     fdw_ctx *bctx = NULL;
     int bmax = 1;
-    if (ns > 1 && !getenv("FDW_NO_SHOT_BATCH") && gpus <= 1) {      /* (shots dealt to several GPUs go one context per worker instead) */
+    if (ns > 1 && !getenv("FDW_NO_SHOT_BATCH") && gpus <= 1 && !illum) {      /* (shots dealt to several GPUs go one context per worker instead) */
         if (fdw_create(&prm, 0, &bctx) != FDW_OK) {
             fprintf(stderr, "fdw_create: %s\n", fdw_last_error());
             return EXIT_FAILURE;
@@ -360,13 +388,14 @@ int main(int argc, char **argv)
     }
     const int batch = bctx ? bmax : (nworkers > 1 ? ns : 1);      /* shots whose model and image are held at once */
     float *vel2_all = (float *)malloc((size_t)batch * ne * sizeof(float)), *imloc_all = (float *)calloc((size_t)batch * ni, sizeof(float));
-    if (!vel2_all || !imloc_all) {
+    float *illoc_all = illum ? (float *)calloc((size_t)batch * ni, sizeof(float)) : NULL, *ill = illum ? (float *)calloc(ni, sizeof(float)) : NULL;
+    if (!vel2_all || !imloc_all || (illum && (!illoc_all || !ill))) {
         fprintf(stderr, "out of host memory\n");
         return EXIT_FAILURE;
     }
     shot_job job;
     job.prm = &prm; job.ns = ns; job.nworkers = nworkers; job.sx = sx; job.sz = sz; job.gz = gz; job.srce = srce; job.d_obs = d_obs;
-    job.nx = nx; job.nt = nt; job.ne = ne; job.ni = ni; job.vel2_all = vel2_all; job.imloc_all = imloc_all; job.failed = 0;
+    job.nx = nx; job.nt = nt; job.ne = ne; job.ni = ni; job.vel2_all = vel2_all; job.imloc_all = imloc_all; job.illoc_all = illoc_all; job.failed = 0;
     job.vp = vp; job.draws = fdw_border_draws(nx, nz, nxb, nzb); job.dev_border = dev_border; job.gpus = gpus;
 
     for (int is0 = 0; is0 < ns; is0 += batch) {
@@ -384,6 +413,7 @@ int main(int argc, char **argv)
         const double t0 = now_s();
         job.is0 = is0; job.nb = nb;
         memset(imloc_all, 0, (size_t)nb * ni * sizeof(float));                                 /* R:515 */
+        if (illum) memset(illoc_all, 0, (size_t)nb * ni * sizeof(float));                      /* per shot from zero */
         if (bctx) {
             /* shots is0 .. is0 + nb - 1: source rows sx[is0] + b ds (R:405-407), border models from draws [(is0 + b) T, ...) of the stream */
             /* models: drawn on the device, or the host-built ones of this batch (vel_ext_file decks, FDW_HOST_BORDER=1) */
@@ -422,12 +452,33 @@ int main(int argc, char **argv)
                     img[(size_t)ix * nz + iz] += imloc[(size_t)ix * nz + iz];
                     fprintf(fnum, " %f \n", img[(size_t)ix * nz + iz]);
                 }
+            if (illum) {                             /* stacked like the image, in shot order: independent of the number of workers */
+                const float *illoc = illoc_all + (size_t)b * ni;
+                for (int iz = 0; iz < nz; iz++)
+                    for (int ix = 0; ix < nx; ix++) ill[(size_t)ix * nz + iz] += illoc[(size_t)ix * nz + iz];
+            }
         }
         t_stack += now_s() - t1;
     }
     if (bctx) fdw_destroy(bctx);
     free(vel2_all);
     free(imloc_all);
+    if (illum) {      /* dir.illum and dir.image_illum, next to the outputs the key leaves untouched */
+        float *comp = (float *)malloc((ni ? ni : 1) * sizeof(float));
+        FILE *fill = open_out(tmpdir, "dir.illum"), *fcomp = open_out(tmpdir, "dir.image_illum");
+        if (!comp || !fill || !fcomp) return EXIT_FAILURE;
+        if (fdw_image_compensate(img, ill, ni, illum_eps, comp) != FDW_OK) {
+            fprintf(stderr, "fdw_image_compensate refused illum_eps=%g\n", (double)illum_eps);
+            return EXIT_FAILURE;
+        }
+        fwrite(ill, sizeof(float), ni, fill);
+        fwrite(comp, sizeof(float), ni, fcomp);
+        fclose(fill);
+        fclose(fcomp);
+        free(comp);
+        free(illoc_all);
+        free(ill);
+    }
 outputs:
     if (timing)
         fprintf(stderr, "[timing] total %.3f s: shots (contexts, border models, propagation) %.3f s, stacking + image.num %.3f s, rest (deck, inputs) %.3f s\n",
