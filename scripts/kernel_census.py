@@ -1,0 +1,202 @@
+#!/usr/bin/env python3
+"""Census of the compiled kernels: which GPU test module launches which kernel of libfdwave.so, and how often.
+
+    python3 scripts/kernel_census.py [--out DIR] [--modules a,b,...] [--assemble-only] [--csv FILE]
+
+The kernel list comes from the BUILT library: the `.kd` symbols of the embedded gfx950 code objects (extracted as the `isa` fixture of
+tests/test_stepn_isa_budget.py extracts them), demangled by the ROCm LLVM demangler (`llvm-readelf --demangle`; the ROCm install ships no
+llvm-cxxfilt).  The launch counts come from the profiler: each test module runs as its own child process
+
+    timeout -k 10 <s> rocprofv3 --kernel-trace --stats --mangled-kernels --output-format csv -d <dir> -- python -m pytest tests/<module>.py -q -m gpu
+
+(kernel tracing only; no counters, no other tracing), one after another.  The kernel-stats files of every process of the run -- pytest
+itself and the programs and rank workers its tests start -- are summed into the module's counts.  A module that exits non-zero (a failing
+test, a fault, an abort, the time limit) ends the census there: nothing more is started on the GPU and nothing is retried.  Per module the
+tool keeps <out>/<module>/counts.json (and the merged raw stats), so a census can be taken in several sittings (--modules) and put together
+with --assemble-only.
+
+The join between the profiler's names and the library's kernels is exact: by mangled symbol, or -- for a profiler that prints demangled
+names -- by the LLVM demangler's form ("void fdw::fdw_step_kernel<4, true, ...>(fdw::StepArgs)").  A traced name of the library's namespace that
+matches no kernel of the library is an error, not an uncovered kernel.  Kernels of torch and of the runtime are not recorded.
+
+Output: profiles/kernel_census.csv -- one row per kernel of the library (symbol, demangled name, launches per module), sorted by symbol.
+tests/test_programs.py::test_every_compiled_kernel_runs_in_a_parity_module reads it.  This is a development tool, not part of the suite."""
+import argparse
+import collections
+import csv
+import glob
+import json
+import os
+import shutil
+import subprocess
+import sys
+import tempfile
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+LIB = os.path.join(ROOT, "parallel_finite_difference_computation_amd", "libfdwave.so")
+LLVM = "/opt/rocm/lib/llvm/bin"
+CSV = os.path.join(ROOT, "profiles", "kernel_census.csv")
+
+# module -> time limit in seconds of its traced run.  Measured on one MI355X, traced: test_programs 145 s, test_gpu_parity 125 s,
+# test_fast_numerics 30 s, the others 6 - 19 s each: 366 s in all, against 276 s for the whole GPU suite plain in one process -- the limits
+# leave a factor of four and never go below three minutes
+MODULES = collections.OrderedDict([
+    ("test_gpu_parity", 600), ("test_value_domain", 180), ("test_illum", 180), ("test_record", 180), ("test_backward_pins", 180),
+    ("test_slabs_gpu", 180), ("test_fast_numerics", 180), ("test_programs", 600), ("test_kernel_census", 180),
+])
+# modules whose GPU tests compare device output with the oracle or a restatement of it (test_programs runs the programs end to end)
+PARITY_MODULES = tuple(m for m in MODULES if m != "test_programs")
+OURS = ("fdw::", "_ZN3fdw")          # every kernel of the library lives in namespace fdw
+
+
+def library_kernels(lib=LIB):
+    """{mangled symbol: demangled name} of every kernel descriptor in the gfx950 code objects embedded in the library."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    try:
+        import test_stepn_isa_budget as isa_mod
+    finally:
+        sys.path.pop(0)
+    kernels = {}
+    with tempfile.TemporaryDirectory() as td:
+        old = isa_mod.LIB
+        isa_mod.LIB = lib
+        try:
+            for co in isa_mod._code_objects(td):
+                # the symbol tables twice, as they are and through the LLVM demangler: the same lines in the same order
+                raw, dem = (subprocess.run([f"{LLVM}/llvm-readelf", "-sW"] + flag + [co], capture_output=True, text=True, check=True).stdout.splitlines()
+                            for flag in ([], ["--demangle"]))
+                assert len(raw) == len(dem), co
+                for a, b in zip(raw, dem):
+                    f = a.split()
+                    if len(f) == 8 and f[3] == "OBJECT" and f[7].endswith(".kd"):
+                        g = b.split(None, 7)
+                        assert g[:7] == f[:7] and g[7].endswith(" (.kd)"), (a, b)
+                        name = g[7][:-len(" (.kd)")]
+                        assert kernels.setdefault(f[7][:-3], name) == name
+        finally:
+            isa_mod.LIB = old
+    if not kernels:
+        raise RuntimeError(f"{lib}: no kernel descriptor found")
+    foreign = [s for s in kernels if not s.startswith(OURS[1])]
+    if foreign:
+        raise RuntimeError(f"kernels outside namespace fdw (the census tells ours from torch's by it): {foreign}")
+    return dict(sorted(kernels.items()))
+
+
+def merged_stats(trace_dir):
+    """{profiler's kernel name: calls} summed over every *kernel_stats.csv below trace_dir (one per traced process)."""
+    calls = collections.Counter()
+    files = sorted(glob.glob(os.path.join(trace_dir, "**", "*kernel_stats.csv"), recursive=True))
+    for f in files:
+        for row in csv.DictReader(open(f, newline="")):
+            calls[row["Name"]] += int(row["Calls"])
+    return calls, len(files)
+
+
+def join(calls, kernels):
+    """{symbol: calls} for the library's kernels; names of other libraries are dropped, a name of ours that matches nothing is an error."""
+    by_name = {}
+    for s, d in kernels.items():
+        if d in by_name:
+            sys.exit(f"two kernels demangle to the same name: {s} and {by_name[d]}")
+        by_name[d] = s
+    out, lost = collections.Counter(), []
+    for name, n in calls.items():
+        key = name[:-3] if name.endswith(".kd") else name
+        if key in kernels:
+            out[key] += n
+        elif key in by_name:
+            out[by_name[key]] += n
+        elif any(tag in key for tag in OURS):
+            lost.append(name)
+    if lost:
+        sys.exit("traced kernel names of the library that match no kernel of the built library (is it the library that ran?):\n  " + "\n  ".join(sorted(lost)))
+    return out
+
+
+def run_module(module, limit, out):
+    """One traced pytest run of tests/<module>.py; returns its exit status (0 = every GPU test passed)."""
+    mdir = os.path.join(out, module)
+    shutil.rmtree(mdir, ignore_errors=True)
+    os.makedirs(mdir)
+    trace = tempfile.mkdtemp(prefix=f"census_{module}_")          # the per-dispatch trace files are large: only the stats are kept
+    cmd = ["timeout", "-k", "10", str(limit), "rocprofv3", "--kernel-trace", "--stats", "--mangled-kernels", "--output-format", "csv", "-d", trace,
+           "--", sys.executable, "-m", "pytest", os.path.join("tests", module + ".py"), "-q", "-m", "gpu", "-p", "no:cacheprovider"]
+    print(f"[kernel_census] {module}: limit {limit} s", flush=True)
+    t0 = time.time()
+    with open(os.path.join(mdir, "run.log"), "w") as log:
+        rc = subprocess.run(cmd, cwd=ROOT, stdout=log, stderr=subprocess.STDOUT).returncode
+    wall = time.time() - t0
+    tail = open(os.path.join(mdir, "run.log"), errors="replace").read().strip().splitlines()[-1:]
+    print(f"[kernel_census] {module}: rc {rc} after {wall:.1f} s   {tail[0] if tail else ''}", flush=True)
+    if rc == 0:
+        calls, nfiles = merged_stats(trace)
+        if not nfiles:
+            rc = 1
+            print(f"[kernel_census] {module}: the profiler wrote no kernel_stats.csv", flush=True)
+        else:
+            with open(os.path.join(mdir, "merged_kernel_stats.csv"), "w", newline="") as fo:
+                w = csv.writer(fo)
+                w.writerow(["Name", "Calls"])
+                w.writerows(sorted(calls.items()))
+            json.dump(dict(module=module, wall_s=round(wall, 1), processes=nfiles, calls=dict(calls)), open(os.path.join(mdir, "counts.json"), "w"), indent=0)
+    shutil.rmtree(trace, ignore_errors=True)
+    return rc
+
+
+def read_census(path=CSV):
+    """(modules, {symbol: (demangled name, {module: launches})}) of a committed census."""
+    rows = list(csv.reader(open(path, newline="")))
+    head = rows[0]
+    assert head[:2] == ["symbol", "kernel"], head
+    modules = head[2:]
+    return modules, {r[0]: (r[1], dict(zip(modules, map(int, r[2:])))) for r in rows[1:]}
+
+
+def assemble(out, modules, path):
+    kernels = library_kernels()
+    per = {}
+    for m in modules:
+        f = os.path.join(out, m, "counts.json")
+        if not os.path.exists(f):
+            sys.exit(f"[kernel_census] no counts for {m} under {out}: run it first (--modules {m})")
+        per[m] = join(collections.Counter(json.load(open(f))["calls"]), kernels)
+    with open(path, "w", newline="") as fo:
+        w = csv.writer(fo, lineterminator="\n")
+        w.writerow(["symbol", "kernel"] + list(modules))
+        for s in sorted(kernels):
+            w.writerow([s, kernels[s]] + [per[m][s] for m in modules])
+    parity = [m for m in modules if m in PARITY_MODULES]
+    bare = [s for s in sorted(kernels) if not any(per[m][s] for m in parity)]
+    print(f"[kernel_census] {len(kernels)} kernels, {len(bare)} without a launch in a parity module -> {os.path.relpath(path, ROOT)}")
+    for s in bare:
+        print(f"    {kernels[s]}   ({s}; test_programs: {per['test_programs'][s] if 'test_programs' in per else '-'})")
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
+    ap.add_argument("--out", default=os.path.join(ROOT, "build", "census"), help="where the per-module counts are kept (build/ is ignored by git)")
+    ap.add_argument("--modules", default=",".join(MODULES), help="modules to run now (default: all)")
+    ap.add_argument("--columns", default=None, help="modules of the CSV (default: all; they must have been run)")
+    ap.add_argument("--assemble-only", action="store_true", help="run nothing: write the CSV from the counts under --out")
+    ap.add_argument("--no-assemble", action="store_true", help="run the modules and stop (a census taken in several sittings)")
+    ap.add_argument("--csv", default=CSV)
+    args = ap.parse_args()
+    todo = [m for m in args.modules.split(",") if m]
+    for m in todo:
+        if m not in MODULES:
+            sys.exit(f"unknown module {m}; known: {', '.join(MODULES)}")
+    if not args.assemble_only:
+        t0 = time.time()
+        for m in todo:
+            rc = run_module(m, MODULES[m], args.out)
+            if rc != 0:      # a failing test, a fault, an abort or the limit: nothing more is started on the GPU
+                sys.exit(f"[kernel_census] {m} failed (rc {rc}): see {os.path.join(args.out, m, 'run.log')}; the census stops here")
+        print(f"[kernel_census] traced {len(todo)} modules in {time.time() - t0:.0f} s", flush=True)
+    if not args.no_assemble:
+        assemble(args.out, args.columns.split(",") if args.columns else list(MODULES), args.csv)
+
+
+if __name__ == "__main__":
+    main()

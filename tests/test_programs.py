@@ -829,3 +829,55 @@ def test_built_library_has_no_store_followed_by_a_write_of_its_data():
         assert mod.check("x")[0] == []
     finally:
         mod.disassemble = orig
+
+
+# kernels of the census with no launch in a parity module, by symbol, with the reason: for kernels without numerical output to compare only
+CENSUS_EXEMPT = {
+}
+# step kernels no entry point of the ABI reaches (dead code: DESIGN.md lists each of them for a follow-up), by symbol
+CENSUS_UNREACHABLE = {
+    "_ZN3fdw16fdw_stepn_kernelILi4ELi4ELb0ELi0ELi2ELb0ELi0ELi0EEEvNS_9Step2ArgsE": "FDW_MODE_PLAIN of the wave pipeline, EXACT: launch_stepn has the case, no host code passes the mode",
+    "_ZN3fdw16fdw_stepn_kernelILi4ELi4ELb0ELi0ELi2ELb0ELi0ELi1EEEvNS_9Step2ArgsE": "the same in FAST numerics",
+}
+STEP_FAMILIES = ("fdw_step", "fdw_stepn", "fdw_step2", "fdw_back4", "fdw_generic")
+
+
+def test_every_compiled_kernel_runs_in_a_parity_module():
+    """profiles/kernel_census.csv (scripts/kernel_census.py: the GPU test modules traced with the profiler, launches per kernel and module)
+    lists exactly the kernels of the built libfdwave.so, and every one of them was launched by a module whose GPU tests compare device
+    output with the oracle or a restatement -- every module but test_programs, which runs the programs end to end.  A kernel added,
+    removed or re-parameterised without a new census, or one that only the programs (or nothing) launch, fails here.  Needs the ROCm LLVM
+    tools but no GPU."""
+    import importlib.util
+    lib = os.path.join(ROOT, "parallel_finite_difference_computation_amd", "libfdwave.so")
+    if not (os.path.exists(lib) and os.path.exists("/opt/rocm/lib/llvm/bin/llvm-readelf")):
+        pytest.skip("needs the built library and the ROCm LLVM tools")
+    spec = importlib.util.spec_from_file_location("kernel_census", os.path.join(ROOT, "scripts", "kernel_census.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    built = mod.library_kernels(lib)
+    modules, census = mod.read_census(os.path.join(ROOT, "profiles", "kernel_census.csv"))
+    retake = "take the census again on an MI355X: python3 scripts/kernel_census.py"
+    assert len(built) > 100
+    missing, stale = sorted(set(built) - set(census)), sorted(set(census) - set(built))
+    assert not missing and not stale, (f"profiles/kernel_census.csv does not describe the built library: {len(missing)} kernels of the library are not in it "
+                                       f"{missing}, {len(stale)} of its kernels are not in the library {stale}; {retake}")
+    assert list(census) == sorted(census), "profiles/kernel_census.csv is not sorted by symbol"
+    for s in built:
+        assert census[s][0] == built[s], (s, census[s][0], built[s])
+    assert set(modules) == set(mod.MODULES) and "test_programs" in modules and set(mod.PARITY_MODULES) == set(modules) - {"test_programs"}
+    # the lists: explicit symbols of the library, a reason each, no step kernel among the exempt, the unreachable documented
+    design = open(os.path.join(ROOT, "DESIGN.md")).read()
+    for s, why in list(CENSUS_EXEMPT.items()) + list(CENSUS_UNREACHABLE.items()):
+        assert s in built and why.strip(), s
+    for s in CENSUS_EXEMPT:
+        assert not any(f"::{fam}" in built[s] for fam in STEP_FAMILIES), f"{built[s]} is a step kernel: it cannot be exempt"
+    for s in CENSUS_UNREACHABLE:
+        assert s not in CENSUS_EXEMPT and built[s].split("(")[0].replace("void ", "") in design, f"{built[s]} is not documented in DESIGN.md as dead code"
+    bare = [s for s in built if not any(census[s][1][m] for m in mod.PARITY_MODULES)]
+    uncovered = [s for s in bare if s not in CENSUS_EXEMPT and s not in CENSUS_UNREACHABLE]
+    assert not uncovered, ("kernels no parity module launches (launches in test_programs: "
+                           + ", ".join(f"{built[s]} {census[s][1]['test_programs']}" for s in uncovered)
+                           + f"): add a bit-exact comparison that launches them to tests/test_kernel_census.py, then {retake}")
+    idle = [s for s in list(CENSUS_EXEMPT) + list(CENSUS_UNREACHABLE) if s not in bare]
+    assert not idle, f"listed as exempt or unreachable, but a parity module launches them: {idle}"
