@@ -339,6 +339,13 @@ int fdw_rand_stream(fdw_ctx *ctx, unsigned long long draw_offset, long long n, i
  * fdw_shot_illum           fdw_shot whose forward loop goes through the illumination kernels: illum[nx][nz] (interior, like imloc) is
  *                          accumulated into; imloc, P, PP equal fdw_shot's bit for bit.  The accumulator field is allocated on first use.
  * fdw_shot_resident_illum  the same on the resident vel2 (fdw_shot_resident).
+ * fdw_shot_batch_illum     fdw_shot_batch (same arguments, same batched launches where it batches) whose forward loop also accumulates
+ *                          every shot's illumination: illum[nshots][nx][nz] is accumulated into per shot, through a per-shot accumulator
+ *                          field on the device (one more batch buffer of [nshots] fields).  imloc equals fdw_shot_batch's bit for bit, illum
+ *                          equals `nshots` calls of fdw_shot_illum / fdw_shot_resident_illum bit for bit.  Contexts whose regime the
+ *                          batched launches do not cover, or a device without room for the accumulators, run the shots one by one --
+ *                          the same bytes.  fdw_shot_batch_max counts the eleven fields per shot of fdw_shot_batch; a larger batch than
+ *                          twelve fields per shot allow in the same budget is split into parts of that size inside the call.
  * fdw_image_compensate     pure host C, usable without a device:  m = max_i illum[i] (from 0.0f with '>' comparisons, so a NaN never
  *                          wins), s = eps (*) m, d_i = illum[i] (+) s, out_i = d_i > 0 ? img[i] (/) d_i : 0.0f (IEEE fp32 division; out may
  *                          alias img).  eps finite and >= 0, else FDW_EINVAL.  O(n) once per job. */
@@ -348,6 +355,8 @@ int fdw_shot_illum(fdw_ctx *ctx, const float *v2, int sx, int sz, int gz, const 
                    float *P, float *PP);
 int fdw_shot_resident_illum(fdw_ctx *ctx, int sx, int sz, int gz, const float *srce, const float *d_obs, float *imloc, float *illum,
                             float *P, float *PP);
+int fdw_shot_batch_illum(fdw_ctx *ctx, int nshots, const float *v2_all, unsigned long long draw_offset, int sx0, int dsx, int sz, int gz,
+                         const float *srce, const float *d_obs, float *imloc, float *illum);
 int fdw_image_compensate(const float *img, const float *illum, size_t n, float eps, float *out);
 
 /* ---- multi-GPU: communicators and the slab-decomposed loops (csrc/fdw_comm.cpp, csrc/fdw_slabs.cpp) ------------------------
@@ -390,6 +399,20 @@ int fdw_image_compensate(const float *img, const float *illum, size_t n, float e
  * fdw_slabs_shot          one shot of rtm_code's loop (R:496-520) on host arrays: every rank passes the GLOBAL v2[nxe][nze], srce[nt],
  *                         d_obs[nx][nt]; imloc[nx][nz] (global; accumulated into) and the optional P, PP [nxe][nze] receive this rank's
  *                         OWNED rows only.  Bit-identical to fdw_shot on the whole grid.
+ * fdw_slabs_dev_record_forward
+ *                         fdw_slabs_dev_forward (same fields, buffer indices, launches and exchanges) that also writes the trace samples
+ *                         of iteration it (fdw_dev_record_steps' definition, receiver column gz) to d_rec + it * nx.  d_rec is THIS RANK'S OWN
+ *                         device array [>= it0+nsteps][nx], indexed by the GLOBAL receiver (interior row) number.  On return (after
+ *                         fdw_slabs_synchronize) the entries of the rank's OWNED interior rows are defined; entries of its ghost rows may
+ *                         hold valid duplicates of a neighbour's samples or what they held before, entries of other rows are untouched:
+ *                         neither is to be reported.  Receiver rows the loop never time-steps (compat extents, rows >= xlim) are written
+ *                         once per call from the entry fields by the rank that owns them.  gz outside [0, zlim): FDW_EINVAL on every
+ *                         rank alike, before anything is enqueued.
+ * fdw_slabs_record_shot   fdw_record_shot on the decomposed grid: one shot from rest, every rank passes the GLOBAL v2[nxe][nze] and srce[nt];
+ *                         data[nx][nt] (global) and the optional P, PP [nxe][nze] receive this rank's OWNED (interior) rows only, as imloc
+ *                         does in fdw_slabs_shot.  Assembled over the ranks the gather is bit-identical to fdw_record_shot on the whole
+ *                         grid, in EXACT and FAST numerics.  Refusals (receiver depth, dialect) as fdw_record_shot's, taken by every rank
+ *                         alike before anything is enqueued.
  * fdw_slabs_set_stub      on = 1: this rank's halo exchanges move nothing from now on (the cycles keep their launches and stream hand-overs).
  *                         MEASUREMENT ONLY: bench.py times the same window with and without the transfers to report the exposed
  *                         communication fraction; results computed while it is on are wrong.  Every rank must switch together. */
@@ -419,6 +442,9 @@ void *fdw_slabs_stream(fdw_slabs *s);
 int fdw_slabs_synchronize(fdw_slabs *s);
 int fdw_slabs_dev_forward(fdw_slabs *s, float *const *buf, const float *d_v2, const float *d_srce, int sx, int sz, int it0, int nsteps,
                           int first_pp_twice, int *ip, int *ipp);
+int fdw_slabs_dev_record_forward(fdw_slabs *s, float *const *buf, const float *d_v2, const float *d_srce, int sx, int sz, int gz, float *d_rec,
+                                 int it0, int nsteps, int first_pp_twice, int *ip, int *ipp);
+int fdw_slabs_record_shot(fdw_slabs *s, const float *v2, int sx, int sz, int gz, const float *srce, float *data, float *P, float *PP);
 int fdw_slabs_back_buffers(const fdw_slabs *s, int *nfb, int *nrb);
 int fdw_slabs_dev_back(fdw_slabs *s, float *const *f, float *const *r, const float *d_v2, const float *d_samples, int gz, float *d_img, int it0,
                        int nsteps, int role[4]);

@@ -76,6 +76,7 @@ SIGNATURES = [
     ("fdw_dev_illum_steps", C.c_int, [vp, C.POINTER(vp), vp, vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), vp]),
     ("fdw_shot_illum", C.c_int, [vp, f32p, C.c_int, C.c_int, C.c_int, f32p, f32p, f32p, f32p, vp, vp]),
     ("fdw_shot_resident_illum", C.c_int, [vp, C.c_int, C.c_int, C.c_int, f32p, f32p, f32p, f32p, vp, vp]),
+    ("fdw_shot_batch_illum", C.c_int, [vp, C.c_int, vp, C.c_ulonglong, C.c_int, C.c_int, C.c_int, C.c_int, f32p, f32p, f32p, f32p]),
     ("fdw_image_compensate", C.c_int, [vp, vp, C.c_size_t, C.c_float, vp]),
     ("fdw_rand_stream", C.c_int, [vp, C.c_ulonglong, C.c_longlong, vp]),
     ("fdw_dev_model_steps", C.c_int, [vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, vp]),
@@ -106,6 +107,8 @@ SIGNATURES = [
     ("fdw_slabs_stream", vp, [vp]),
     ("fdw_slabs_synchronize", C.c_int, [vp]),
     ("fdw_slabs_dev_forward", C.c_int, [vp, C.POINTER(vp), vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    ("fdw_slabs_dev_record_forward", C.c_int, [vp, C.POINTER(vp), vp, vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    ("fdw_slabs_record_shot", C.c_int, [vp, f32p, C.c_int, C.c_int, C.c_int, f32p, f32p, vp, vp]),
     ("fdw_slabs_back_buffers", C.c_int, [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     ("fdw_slabs_dev_back", C.c_int, [vp, C.POINTER(vp), C.POINTER(vp), vp, vp, C.c_int, vp, C.c_int, C.c_int, C.POINTER(C.c_int)]),
     ("fdw_slabs_shot", C.c_int, [vp, f32p, C.c_int, C.c_int, C.c_int, f32p, f32p, f32p, vp, vp]),

@@ -248,12 +248,19 @@ class FDWave:
                                       P.ctypes.data if want_fields else None, PP.ctypes.data if want_fields else None))
         return (imloc, P, PP) if want_fields else imloc
 
-    def shot_batch(self, nshots, sx0, dsx, sz, gz, srce, d_obs, v2_all=None, draw_offset=0, imloc=None):
+    def shot_batch(self, nshots, sx0, dsx, sz, gz, srce, d_obs, v2_all=None, draw_offset=0, imloc=None, want_illum=False, illum=None):
         """`nshots` consecutive shots of rtm_code's loop (fd-code.cu:480-520) through one launch per time step.  d_obs[nshots][nx][nt];
         v2_all[nshots][nxe][nze], or None = border models drawn on the device from the resident interior model at draws
-        draw_offset + b * border_draws().  Returns imloc[nshots][nx][nz]."""
+        draw_offset + b * border_draws().  Returns imloc[nshots][nx][nz].  want_illum: the forward loop also accumulates every shot's
+        source illumination illum[nshots][nx][nz] (from zero, or into `illum`); returns (imloc, illum)."""
         imloc = np.zeros((nshots, self.nx, self.nz), np.float32) if imloc is None else np.array(imloc, np.float32, order="C")
         v2p = None if v2_all is None else _f32(v2_all, (nshots, self.nxe, self.nze)).ctypes.data
+        if want_illum:
+            shape = (nshots, self.nx, self.nz)
+            illum = np.zeros(shape, np.float32) if illum is None else np.array(_f32(illum, shape), order="C")
+            check(lib().fdw_shot_batch_illum(self._h, nshots, v2p, int(draw_offset), sx0, dsx, sz, gz, _f32(srce, (self.nt,)),
+                                             _f32(d_obs, (nshots, self.nx, self.nt)), imloc, illum))
+            return imloc, illum
         check(lib().fdw_shot_batch(self._h, nshots, v2p, int(draw_offset), sx0, dsx, sz, gz, _f32(srce, (self.nt,)),
                                    _f32(d_obs, (nshots, self.nx, self.nt)), imloc))
         return imloc

@@ -85,6 +85,9 @@ struct fdw_ctx {
     bool batch_all = false;      // the batch buffers hold the RTM loop's full set (else: the modelling loop's two fields + gathers)
     float* bfld[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     float *b_v2 = nullptr, *b_img = nullptr, *b_dobs = nullptr;
+    float* b_illum = nullptr;    // the shots' source illuminations, [shots] fields (fdw_shot_batch_illum); allocated on first use
+    int b_illum_cap = 0;         // ... shots it holds
+    bool batch_illum = false;    // inside fdw_shot_batch_illum's forward loop: the one place a batched launch accumulates illumination
     float* d_raw = nullptr;      // gathers as the caller holds them ([shot][nx][nt]) before the transposition on the device
     size_t raw_cap = 0;
     int no_fused_back = 0;   // experiments / tests: backward iterations as two launches (source step, receiver step) -- FDW_NO_FUSED_BACK=1
@@ -342,7 +345,7 @@ extern "C" void fdw_destroy(fdw_ctx* c)
     float* bufs[] = {c->d_taperz, c->d_txfac, c->d_gcx, c->d_gcz, c->fld[0], c->fld[1], c->fld[2], c->fld[3],
                      c->fld[4], c->fld[5], c->fld[6], c->fld[7], c->fld[8], c->fld[9], c->d_v2, c->d_img, c->d_illum, c->d_srce, c->d_dobs, c->d_rec,
                      c->d_vp, c->d_vpe, (float*)c->d_draws, (float*)c->d_jump, c->bfld[0], c->bfld[1], c->bfld[2], c->bfld[3],
-                     c->bfld[4], c->bfld[5], c->bfld[6], c->bfld[7], c->b_v2, c->b_img, c->b_dobs, c->d_raw};
+                     c->bfld[4], c->bfld[5], c->bfld[6], c->bfld[7], c->b_v2, c->b_img, c->b_dobs, c->b_illum, c->d_raw};
     for (float* b : bufs)
         if (b) (void)hipFree(b);
     if (c->stream) (void)hipStreamDestroy(c->stream);
@@ -516,7 +519,9 @@ static int step_impl(fdw_ctx* c, int mode, const float* d_p, float* d_pp, const 
     else if (mode == FDW_MODE_RECV || mode == FDW_MODE_DD_RECV || mode == FDW_MODE_BACK)
         FDW_TRY(place_receivers(c, "step", mode == FDW_MODE_DD_RECV ? c->prm.nzb : c->prm.nxb, inj_z, &in));
     if (mode == FDW_MODE_MOD) FDW_TRY(fill_mod(c, a, "step", d_rec_row, rec_z));
-    if (d_illum && (mode != FDW_MODE_FWD || d_rec_row || c->nbatch > 1)) return fail(FDW_EINVAL, "step: illumination belongs to a plain forward step of one shot");
+    // (a batch accumulates per shot, illum + shot * field, inside fdw_shot_batch_illum only)
+    if (d_illum && (mode != FDW_MODE_FWD || d_rec_row || (c->nbatch > 1 && !c->batch_illum)))
+        return fail(FDW_EINVAL, "step: illumination belongs to a plain forward step of one shot");
     // the RTM forward step that records its trace row, or that accumulates the source illumination (the accumulator travels in `img`)
     const int kmode = (mode == FDW_MODE_FWD && d_rec_row) ? FDW_MODE_FWD_REC : ((mode == FDW_MODE_FWD && d_illum) ? FDW_MODE_FWD_ILLUM : mode);
     if (kmode == FDW_MODE_FWD_REC) fill_rec(c, a, d_rec_row, rec_z);
@@ -865,20 +870,27 @@ extern "C" int fdw_dev_step4(fdw_ctx* c, const float* d_p, const float* d_pp, co
 // BEFORE the first swap; on return they index (d_p, d_pp) after the loop.  d_rec: NULL, or the trace rows [it][nx] (fdw_dev_record_steps):
 // the same passes, each through its kernel's recording variant.  d_illum: NULL, or the source illumination (fdw_dev_illum_steps): the same
 // passes, each through its kernel's illumination variant (not together with d_rec).
+// Trace samples of iterations it0 .. it0+nsteps-1 on the receiver rows the loop never time-steps (rows >= xlim of this slab): what the
+// reference's d_pp holds there, from the fields (d_p, d_pp) before the first swap
+static int record_static(fdw_ctx* c, const float* d_p, const float* d_pp, int gz, float* d_rec, int it0, int nsteps, hipStream_t s)
+{
+    if (nsteps <= 0) return FDW_OK;
+    const size_t nxs = (size_t)c->nx;
+    const int rec_x0 = c->prm.nxb - c->slab.x_off, r0 = std::max({rec_x0, c->upd_x1, 0}), r1 = std::min(rec_x0 + c->nx, c->nxl);
+    const long long rec_bstride = c->nbatch > 1 ? (long long)nxs * c->batch_nt : 0;
+    hipError_t e = launch_record_static(d_p, d_pp, d_rec + (size_t)it0 * nxs, c->pitch, r0, r1 - r0, gz, rec_x0, c->nx, nsteps, c->nbatch,
+                                        (long long)field_elems(c), rec_bstride, s);
+    if (e != hipSuccess) return fail(FDW_EHIP, "static receiver rows: launch failed: %s", hipGetErrorString(e));
+    return FDW_OK;
+}
+
 static int steps_loop(fdw_ctx* c, float* const* buf, const float* d_v2, const float* d_srce, int sx, int sz, int gz, float* d_rec, int it0, int nsteps,
                       int first_pp_twice, int* ip, int* ipp, hipStream_t s, float* d_illum = nullptr)
 {
     if (!c || !buf || !ip || !ipp) return fail(FDW_EINVAL, "NULL argument");
     if (*ip < 0 || *ip > 3 || *ipp < 0 || *ipp > 3 || *ip == *ipp) return fail(FDW_EINVAL, "steps2: bad buffer indices");
     const size_t nxs = (size_t)c->nx;
-    if (d_rec && nsteps > 0) {
-        // receiver rows the loop never time-steps (rows >= xlim of this slab): what the reference's d_pp holds there, from the entry fields
-        const int rec_x0 = c->prm.nxb - c->slab.x_off, r0 = std::max({rec_x0, c->upd_x1, 0}), r1 = std::min(rec_x0 + c->nx, c->nxl);
-        const long long rec_bstride = c->nbatch > 1 ? (long long)nxs * c->batch_nt : 0;
-        hipError_t e = launch_record_static(buf[*ip], buf[*ipp], d_rec + (size_t)it0 * nxs, c->pitch, r0, r1 - r0, gz, rec_x0, c->nx, nsteps, c->nbatch,
-                                            (long long)field_elems(c), rec_bstride, s);
-        if (e != hipSuccess) return fail(FDW_EHIP, "static receiver rows: launch failed: %s", hipGetErrorString(e));
-    }
+    if (d_rec) FDW_TRY(record_static(c, buf[*ip], buf[*ipp], gz, d_rec, it0, nsteps, s));
     int k = 0;
     while (k < nsteps) {
         const int twice = (k > 0) || first_pp_twice;
@@ -929,6 +941,35 @@ extern "C" int fdw_dev_record_steps(fdw_ctx* c, float* const* d_buf, const float
     if (it0 < 0) return fail(FDW_EINVAL, "it0=%d", it0);
     FDW_TRY(check_record_depth(c, gz));
     return steps_loop(c, d_buf, d_v2, d_srce, sx, sz, gz, d_rec, it0, nsteps, first_pp_twice, ip, ipp, pick_stream(c, stream));
+}
+
+// ---- what the slab driver's recording loop (fdw_slabs_dev_record_forward) launches: fdw_dev_step / fdw_dev_step4 on row ranges of the slab
+// that also write their trace rows (d_rec_row: this step's [nx]; d_rec: the pass's four), and the static receiver rows of a whole call.
+// d_rec* == NULL: exactly the plain launch.
+int fdw_check_record_depth(const fdw_ctx* c, int gz) { return c ? check_record_depth(c, gz) : fail(FDW_EINVAL, "ctx is NULL"); }
+
+int fdw_dev_step_rec(fdw_ctx* c, const float* d_p, float* d_pp, const float* d_v2, int r0, int r1, int pp_twice, const float* d_srce_it, int sx, int sz,
+                     float* d_rec_row, int gz, hipStream_t s)
+{
+    if (!c) return fail(FDW_EINVAL, "ctx is NULL");
+    return step_impl(c, FDW_MODE_FWD, d_p, d_pp, d_v2, r0, r1, pp_twice, d_srce_it, d_srce_it ? sx : -1, sz, nullptr, nullptr, pick_stream(c, s), d_rec_row, gz);
+}
+
+int fdw_dev_step4_rec(fdw_ctx* c, const float* d_p, const float* d_pp, const float* d_v2, float* d_out1, float* d_out2, int pp_twice, const float* d_srce_it,
+                      int sx, int sz, int r0, int r1, int r0b, int r1b, int xchunk, float* d_rec, int gz, hipStream_t s)
+{
+    if (!c) return fail(FDW_EINVAL, "ctx is NULL");
+    if (c->h != kMaxFastHalfOrder || (size_t)c->nxl * c->pitch * sizeof(float) >= (1ull << 31))
+        return fail(FDW_EINVAL, "step4: needs order 8 and fields below 2 GiB");
+    RowRanges rr;
+    rr.r0 = r0; rr.r1 = r1; rr.r0b = r0b; rr.r1b = r1b; rr.xchunk = xchunk;
+    return stepn_impl(c, FDW_MODE_FWD, d_p, d_pp, d_v2, d_out1, d_out2, pp_twice, d_srce_it, d_srce_it ? sx : -1, sz, pick_stream(c, s), rr, d_rec, gz);
+}
+
+int fdw_dev_record_static(fdw_ctx* c, const float* d_p, const float* d_pp, int gz, float* d_rec, int it0, int nsteps, hipStream_t s)
+{
+    if (!c || !d_p || !d_pp || !d_rec) return fail(FDW_EINVAL, "NULL argument");
+    return record_static(c, d_p, d_pp, gz, d_rec, it0, nsteps, pick_stream(c, s));
 }
 
 // the forward loop with source illumination: the RTM dialect on the whole grid
@@ -1988,8 +2029,12 @@ static int ensure_batch_buffers(fdw_ctx* c, int n, bool need_all)
 namespace {
 struct BatchScope {      // the context's single-shot buffers step aside for the batch ones while a batch runs
     fdw_ctx* c;
-    explicit BatchScope(fdw_ctx* ctx, int n, int dsx) : c(ctx) { swap(); c->nbatch = n; c->batch_dsx = dsx; c->batch_nt = c->prm.nt; }
-    ~BatchScope() { swap(); c->nbatch = 1; c->batch_dsx = 0; }
+    explicit BatchScope(fdw_ctx* ctx, int n, int dsx, bool illum = false) : c(ctx)
+    {
+        swap();
+        c->nbatch = n; c->batch_dsx = dsx; c->batch_nt = c->prm.nt; c->batch_illum = illum;
+    }
+    ~BatchScope() { swap(); c->nbatch = 1; c->batch_dsx = 0; c->batch_illum = false; }
     void swap()
     {
         for (int i = 0; i < 8; i++) std::swap(c->fld[i], c->bfld[i]);
@@ -2026,12 +2071,51 @@ static int batch_models(fdw_ctx* c, int nshots, const float* v2_all, unsigned lo
     return FDW_OK;
 }
 
-extern "C" int fdw_shot_batch(fdw_ctx* c, int nshots, const float* v2_all, unsigned long long draw_offset, int sx0, int dsx, int sz, int gz,
-                              const float* srce, const float* d_obs, float* imloc)
+// the per-shot accumulator fields of a batch with illumination: one more batch buffer, kept apart from the others so that fdw_shot_batch's
+// own allocation stays what it is
+static int ensure_batch_illum(fdw_ctx* c, int n)
+{
+    if (c->b_illum && c->b_illum_cap >= n) return FDW_OK;
+    if (c->b_illum) (void)hipFree(c->b_illum);
+    c->b_illum = nullptr;
+    c->b_illum_cap = 0;
+    const size_t bytes = field_elems(c) * (size_t)n * sizeof(float);
+    hipError_t e = hipMalloc((void**)&c->b_illum, bytes);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        c->b_illum = nullptr;
+        return fail(FDW_ENOMEM, "batch of %d shots: hipMalloc(%zu bytes) for the illumination failed: %s", n, bytes, hipGetErrorString(e));
+    }
+    c->b_illum_cap = n;
+    return FDW_OK;
+}
+
+// the interiors of `nshots` host arrays [nx][nz] into / out of the batch's fields (b_img, b_illum)
+static int batch_interiors_to_device(fdw_ctx* c, float* d_dst, const float* h_src, int nshots)
+{
+    const size_t ni = (size_t)c->nx * c->nz, fe = field_elems(c);
+    HIP_TRY(hipMemsetAsync(d_dst, 0, fe * nshots * sizeof(float), c->stream));
+    for (int b = 0; b < nshots; b++)
+        HIP_TRY(hipMemcpy2DAsync(d_dst + b * fe + (size_t)c->prm.nxb * c->pitch + c->prm.nzb, (size_t)c->pitch * sizeof(float), h_src + b * ni,
+                                 (size_t)c->nz * sizeof(float), (size_t)c->nz * sizeof(float), c->nx, hipMemcpyHostToDevice, c->stream));
+    return FDW_OK;
+}
+static int batch_interiors_to_host(fdw_ctx* c, float* h_dst, const float* d_src, int nshots)
+{
+    const size_t ni = (size_t)c->nx * c->nz, fe = field_elems(c);
+    for (int b = 0; b < nshots; b++)
+        HIP_TRY(hipMemcpy2DAsync(h_dst + b * ni, (size_t)c->nz * sizeof(float), d_src + b * fe + (size_t)c->prm.nxb * c->pitch + c->prm.nzb,
+                                 (size_t)c->pitch * sizeof(float), (size_t)c->nz * sizeof(float), c->nx, hipMemcpyDeviceToHost, c->stream));
+    return FDW_OK;
+}
+
+// fdw_shot_batch (illum == NULL) and fdw_shot_batch_illum: illum [nshots][nx][nz] is accumulated into per shot by the forward loop
+static int shot_batch_impl(fdw_ctx* c, const char* who, int nshots, const float* v2_all, unsigned long long draw_offset, int sx0, int dsx, int sz, int gz,
+                           const float* srce, const float* d_obs, float* imloc, float* illum)
 {
     if (!c || !srce || !d_obs || !imloc) return fail(FDW_EINVAL, "NULL argument");
     if (nshots < 1) return fail(FDW_EINVAL, "nshots=%d", nshots);
-    if (!is_full_grid(c)) return fail(FDW_EINVAL, "fdw_shot_batch needs a full-grid context");
+    if (!is_full_grid(c)) return fail(FDW_EINVAL, "%s needs a full-grid context", who);
     if (c->nx <= 0 || c->nz <= 0) return fail(FDW_EINVAL, "no interior to image");
     if (!v2_all && !c->model_resident) return fail(FDW_ESTATE, "no model: pass v2_all or call fdw_model_resident first");
     const int nt = c->prm.nt;
@@ -2044,7 +2128,8 @@ extern "C" int fdw_shot_batch(fdw_ctx* c, int nshots, const float* v2_all, unsig
     auto one_by_one = [&] {
         for (int b = 0; b < nshots; b++) {
             if (!v2_all) FDW_TRY(fdw_dev_extendvel_linear(c, draw_offset + (unsigned long long)b * draws, nullptr));
-            FDW_TRY(shot_impl(c, v2_all ? v2_all + b * ne : nullptr, sx0 + b * dsx, sz, gz, srce, d_obs + b * ng, imloc + b * ni, nullptr, nullptr));
+            FDW_TRY(shot_impl(c, v2_all ? v2_all + b * ne : nullptr, sx0 + b * dsx, sz, gz, srce, d_obs + b * ng, imloc + b * ni, nullptr, nullptr,
+                              illum ? illum + b * ni : nullptr));
         }
         return (int)FDW_OK;
     };
@@ -2052,29 +2137,54 @@ extern "C" int fdw_shot_batch(fdw_ctx* c, int nshots, const float* v2_all, unsig
     int rc;
     if ((rc = ensure_work_buffers(c, 8, true))) return rc;
     if ((rc = ensure_batch_buffers(c, nshots, true)) == FDW_ENOMEM) return one_by_one();      // no room for the batch
+    if (!rc && illum && (rc = ensure_batch_illum(c, nshots)) == FDW_ENOMEM) return one_by_one();      // ... or for its accumulators
     if (rc || (rc = upload_source(c, srce, nt))) return rc;
     hipStream_t s = c->stream;
     if ((rc = gathers_to_device(c, d_obs, c->b_dobs, nshots))) return rc;      // [shot][nx][nt] -> [shot][nt][nx]
     if ((rc = batch_models(c, nshots, v2_all, draw_offset))) return rc;
     for (int i = 0; i < 8; i++) HIP_TRY(hipMemsetAsync(c->bfld[i], 0, fe * nshots * sizeof(float), s));    // R:496-497, R:511-514
-    HIP_TRY(hipMemsetAsync(c->b_img, 0, fe * nshots * sizeof(float), s));
-    for (int b = 0; b < nshots; b++)
-        HIP_TRY(hipMemcpy2DAsync(c->b_img + b * fe + (size_t)c->prm.nxb * c->pitch + c->prm.nzb, (size_t)c->pitch * sizeof(float), imloc + b * ni,
-                                 (size_t)c->nz * sizeof(float), (size_t)c->nz * sizeof(float), c->nx, hipMemcpyHostToDevice, s));
+    if ((rc = batch_interiors_to_device(c, c->b_img, imloc, nshots))) return rc;
+    if (illum && (rc = batch_interiors_to_device(c, c->b_illum, illum, nshots))) return rc;
     {
-        BatchScope scope(c, nshots, dsx);
+        BatchScope scope(c, nshots, dsx, illum != nullptr);
         int ip = 0, ipp = 1;
-        if ((rc = fdw_dev_steps2(c, c->fld, c->d_v2, c->d_srce, sx0, sz, 0, nt, 0, &ip, &ipp, s))) return rc;
+        if ((rc = steps_loop(c, c->fld, c->d_v2, c->d_srce, sx0, sz, 0, nullptr, 0, nt, 0, &ip, &ipp, s, illum ? c->b_illum : nullptr))) return rc;
         for (int b = 0; b < nshots && nt > 0; b++)
             if ((rc = fdw_dev_taper_finalize(c, c->fld[ip] + b * fe, s))) return rc;
         float* src[4];
         source_buffers(c, ip, ipp, src);
         if ((rc = back_loop(c, src, c->fld + 4, gz, nt))) return rc;
     }
-    for (int b = 0; b < nshots; b++)
-        HIP_TRY(hipMemcpy2DAsync(imloc + b * ni, (size_t)c->nz * sizeof(float), c->b_img + b * fe + (size_t)c->prm.nxb * c->pitch + c->prm.nzb,
-                                 (size_t)c->pitch * sizeof(float), (size_t)c->nz * sizeof(float), c->nx, hipMemcpyDeviceToHost, s));
+    if (illum && (rc = batch_interiors_to_host(c, illum, c->b_illum, nshots))) return rc;
+    if ((rc = batch_interiors_to_host(c, imloc, c->b_img, nshots))) return rc;
     HIP_TRY(hipStreamSynchronize(s));
+    return FDW_OK;
+}
+
+extern "C" int fdw_shot_batch(fdw_ctx* c, int nshots, const float* v2_all, unsigned long long draw_offset, int sx0, int dsx, int sz, int gz,
+                              const float* srce, const float* d_obs, float* imloc)
+{
+    return shot_batch_impl(c, "fdw_shot_batch", nshots, v2_all, draw_offset, sx0, dsx, sz, gz, srce, d_obs, imloc, nullptr);
+}
+
+// fdw_shot_batch whose forward loop also accumulates every shot's source illumination.  The batch holds one field more per shot than
+// fdw_shot_batch_max counts (11), so a batch larger than twelve fields per shot allow within the same budget goes through in parts of that
+// size: the parts are independent, the bytes the same.
+extern "C" int fdw_shot_batch_illum(fdw_ctx* c, int nshots, const float* v2_all, unsigned long long draw_offset, int sx0, int dsx, int sz, int gz,
+                                    const float* srce, const float* d_obs, float* imloc, float* illum)
+{
+    if (!c || !illum) return fail(FDW_EINVAL, "NULL argument");
+    FDW_TRY(check_illum_ctx(c, "fdw_shot_batch_illum"));
+    if (nshots < 1) return fail(FDW_EINVAL, "nshots=%d", nshots);
+    const long by_mem = (long)(((size_t)6 << 30) / (12 * field_elems(c) * sizeof(float)));
+    const int part = (int)std::max<long>(1, std::min<long>(by_mem, nshots));
+    const size_t ni = (size_t)c->nx * c->nz, ne = (size_t)c->prm.nxe * c->prm.nze, ng = (size_t)c->nx * c->prm.nt;
+    const unsigned long long draws = (unsigned long long)fdw_border_draws(c->nx, c->nz, c->prm.nxb, c->prm.nzb);
+    for (int b0 = 0; b0 < nshots; b0 += part) {
+        const int nb = std::min(part, nshots - b0);
+        FDW_TRY(shot_batch_impl(c, "fdw_shot_batch_illum", nb, v2_all ? v2_all + b0 * ne : nullptr, draw_offset + b0 * draws, sx0 + b0 * dsx, dsx, sz, gz,
+                                srce, d_obs ? d_obs + b0 * ng : nullptr, imloc ? imloc + b0 * ni : nullptr, illum + b0 * ni));
+    }
     return FDW_OK;
 }
 

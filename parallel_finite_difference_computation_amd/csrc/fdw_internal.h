@@ -33,6 +33,17 @@ inline void spare_pair(int a, int b, int* o1, int* o2)
 // passes of the backward loop and the batched shots have no static-row epilogue for the others
 int fdw_receivers_stepped(const fdw_ctx* c);
 
+// The launches of the slab driver's recording forward loop (fdw_api.cpp): fdw_dev_step (mode FWD) and fdw_dev_step4 on row ranges of a slab
+// that also write their trace rows -- d_rec_row: this step's samples [nx], d_rec: the four rows of the pass, indexed by GLOBAL receiver
+// (rec[g - nxb] for global row g); NULL: the plain launch --, the samples of receiver rows the loop never time-steps for a whole call
+// (from the fields before the first swap), and fdw_record_shot's check of the receiver depth and the dialect.
+int fdw_dev_step_rec(fdw_ctx* c, const float* d_p, float* d_pp, const float* d_v2, int r0, int r1, int pp_twice, const float* d_srce_it, int sx, int sz,
+                     float* d_rec_row, int gz, hipStream_t s);
+int fdw_dev_step4_rec(fdw_ctx* c, const float* d_p, const float* d_pp, const float* d_v2, float* d_out1, float* d_out2, int pp_twice, const float* d_srce_it,
+                      int sx, int sz, int r0, int r1, int r0b, int r1b, int xchunk, float* d_rec, int gz, hipStream_t s);
+int fdw_dev_record_static(fdw_ctx* c, const float* d_p, const float* d_pp, int gz, float* d_rec, int it0, int nsteps, hipStream_t s);
+int fdw_check_record_depth(const fdw_ctx* c, int gz);
+
 constexpr int FDW_COMM_MAX_FIELDS = 8;
 
 // Halo exchange of `nfields` fields with the two neighbouring ranks, enqueued on `stream` (fdw_comm.cpp)

@@ -61,7 +61,8 @@ struct fdw_slabs {
     // work arrays of the host-array entry points
     float* fld[10] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     float *d_v2 = nullptr, *d_img = nullptr, *d_srce = nullptr, *d_samples = nullptr;
-    size_t srce_cap = 0, samples_cap = 0;
+    float* d_rec = nullptr;               // fdw_slabs_record_shot: this rank's trace rows [nt][nx]
+    size_t srce_cap = 0, samples_cap = 0, rec_cap = 0;
 
     size_t row(int r) const { return (size_t)r * (size_t)pitch; }
     int wait(hipStream_t waiter, hipStream_t on)
@@ -191,7 +192,7 @@ extern "C" void fdw_slabs_destroy(fdw_slabs* s)
             (void)hipStreamDestroy(st);
         }
     if (s->ev) (void)hipEventDestroy(s->ev);
-    for (float* f : {s->fld[0], s->fld[1], s->fld[2], s->fld[3], s->fld[4], s->fld[5], s->fld[6], s->fld[7], s->fld[8], s->fld[9], s->d_v2, s->d_img, s->d_srce, s->d_samples})
+    for (float* f : {s->fld[0], s->fld[1], s->fld[2], s->fld[3], s->fld[4], s->fld[5], s->fld[6], s->fld[7], s->fld[8], s->fld[9], s->d_v2, s->d_img, s->d_srce, s->d_samples, s->d_rec})
         if (f) (void)hipFree(f);
     if (s->ctx) fdw_destroy(s->ctx);
     delete s;
@@ -235,9 +236,14 @@ extern "C" int fdw_slabs_synchronize(fdw_slabs* s)
 // fd_forward's loop (R:259-267) on the slab.  buf[*ip], buf[*ipp] = the reference's (d_p, d_pp) BEFORE its first swap (d_pp is the
 // newest field); on return they index the pair after the loop.  Four buffers when the slab runs four steps per pass (fdw_slabs_geometry
 // says so), two suffice otherwise.
+// d_rec: NULL, or this rank's trace rows [>= it0+nsteps][nx] (fdw_slabs_dev_record_forward): the same launches, each through its kernel's
+// recording variant, which writes the samples of the receiver rows among the rows it produces.  Every launch of a cycle covers the owned
+// rows, so their samples are complete; ghost rows are recorded while the shrinking ranges still hold them (valid duplicates of the
+// neighbour's samples) and keep what they held afterwards.  The boundary strips (side stream) and the interior (compute stream) of a split
+// pass write disjoint receiver rows of the same trace rows.
 // ------------------------------------------------------------------------------------------------
-extern "C" int fdw_slabs_dev_forward(fdw_slabs* s, float* const* buf, const float* d_v2, const float* d_srce, int sx, int sz, int it0, int nsteps,
-                                     int first_pp_twice, int* ip, int* ipp)
+static int slabs_forward(fdw_slabs* s, float* const* buf, const float* d_v2, const float* d_srce, int sx, int sz, int gz, float* d_rec, int it0, int nsteps,
+                         int first_pp_twice, int* ip, int* ipp)
 {
     if (!s || !buf || !d_v2 || !ip || !ipp) return fdw_fail(FDW_EINVAL, "slabs forward: NULL argument");
     FDW_RANGE("fdw: slab forward loop (enqueue)");
@@ -245,12 +251,18 @@ extern "C" int fdw_slabs_dev_forward(fdw_slabs* s, float* const* buf, const floa
     if (*ip < 0 || *ip >= nb || *ipp < 0 || *ipp >= nb || *ip == *ipp) return fdw_fail(FDW_EINVAL, "slabs forward: bad buffer indices %d, %d", *ip, *ipp);
     HIP_TRY(hipSetDevice(s->device));
     fdw_ctx* c = s->ctx;
-    if (s->world == 1)      // nothing to exchange: the library's own forward loop (four / two / one steps per pass as the grid size decides)
+    if (s->world == 1) {    // nothing to exchange: the library's own forward loop (four / two / one steps per pass as the grid size decides)
+        if (d_rec) return fdw_dev_record_steps(c, buf, d_v2, d_srce, sx, sz, gz, d_rec, it0, nsteps, first_pp_twice, ip, ipp, s->compute);
         return fdw_dev_steps2(c, buf, d_v2, d_srce, sx, sz, it0, nsteps, first_pp_twice, ip, ipp, s->compute);
+    }
     const int h = s->h, G = s->G, nxl = s->nxl;
+    const size_t nxs = (size_t)(s->prm.nxe - 2 * s->prm.nxb);
     int it = it0, done = 0;
     bool twice = first_pp_twice != 0;
     auto srce_at = [&](int i) { return d_srce ? d_srce + i : nullptr; };
+    auto rec_at = [&](int i) { return d_rec ? d_rec + (size_t)i * nxs : nullptr; };
+    // receiver rows the loop never time-steps (compat extents: rows >= xlim, owned by the last rank): once per call, from the entry fields
+    if (d_rec) FDW_TRY(fdw_dev_record_static(c, buf[*ip], buf[*ipp], gz, d_rec, it0, nsteps, s->compute));
     const int sxx = d_srce ? sx : -1;
     while (done < nsteps) {
         const int kk = std::min(s->ksteps, nsteps - done);
@@ -274,14 +286,14 @@ extern "C" int fdw_slabs_dev_forward(fdw_slabs* s, float* const* buf, const floa
                     if (!s->has_lo) { ra0 = rb0; ra1 = rb1; rb0 = rb1 = 0; }
                     // the strips the neighbours need: a short latency chain on a stream of its own, beside the interior launch
                     FDW_TRY(s->wait(s->side, s->compute));
-                    FDW_TRY(fdw_dev_step4(c, p_in, pp_in, d_v2, buf[o1], buf[o2], twice, srce_at(it), sxx, sz, ra0, ra1, rb0, rb1, 23, s->side));
+                    FDW_TRY(fdw_dev_step4_rec(c, p_in, pp_in, d_v2, buf[o1], buf[o2], twice, srce_at(it), sxx, sz, ra0, ra1, rb0, rb1, 23, rec_at(it), gz, s->side));
                     s->send_after = s->side;
                     float* nxt[2] = {buf[o1], buf[o2]};
                     FDW_TRY(s->exchange(2, nxt));                      // the next cycle's ghosts, beside the interior rows of this pass
-                    FDW_TRY(fdw_dev_step4(c, p_in, pp_in, d_v2, buf[o1], buf[o2], twice, srce_at(it), sxx, sz, s->has_lo ? lo + G : lo,
-                                          s->has_hi ? hi - G : hi, 0, 0, 0, s->compute));
+                    FDW_TRY(fdw_dev_step4_rec(c, p_in, pp_in, d_v2, buf[o1], buf[o2], twice, srce_at(it), sxx, sz, s->has_lo ? lo + G : lo,
+                                              s->has_hi ? hi - G : hi, 0, 0, 0, rec_at(it), gz, s->compute));
                 } else {
-                    FDW_TRY(fdw_dev_step4(c, p_in, pp_in, d_v2, buf[o1], buf[o2], twice, srce_at(it), sxx, sz, lo, hi, 0, 0, 0, s->compute));
+                    FDW_TRY(fdw_dev_step4_rec(c, p_in, pp_in, d_v2, buf[o1], buf[o2], twice, srce_at(it), sxx, sz, lo, hi, 0, 0, 0, rec_at(it), gz, s->compute));
                 }
                 *ip = o1; *ipp = o2;
                 it += kPipe;
@@ -295,7 +307,7 @@ extern "C" int fdw_slabs_dev_forward(fdw_slabs* s, float* const* buf, const floa
                 float *d_p = buf[*ip], *d_pp = buf[*ipp];
                 const int r0 = s->has_lo ? h * j : 0, r1 = nxl - (s->has_hi ? h * j : 0);
                 auto step = [&](int a, int b, hipStream_t st) {
-                    return a < b ? fdw_dev_step(c, 0 /* FWD */, d_p, d_pp, d_v2, a, b, twice, srce_at(it), sxx, sz, nullptr, nullptr, st) : FDW_OK;
+                    return a < b ? fdw_dev_step_rec(c, d_p, d_pp, d_v2, a, b, twice, srce_at(it), sxx, sz, rec_at(it), gz, st) : FDW_OK;
                 };
                 if (split_last && j == kk) {
                     const int lo_end = s->has_lo ? r0 + G : r0, hi_beg = s->has_hi ? r1 - G : r1;
@@ -314,6 +326,21 @@ extern "C" int fdw_slabs_dev_forward(fdw_slabs* s, float* const* buf, const floa
         done += kk;
     }
     return FDW_OK;
+}
+
+extern "C" int fdw_slabs_dev_forward(fdw_slabs* s, float* const* buf, const float* d_v2, const float* d_srce, int sx, int sz, int it0, int nsteps,
+                                     int first_pp_twice, int* ip, int* ipp)
+{
+    return slabs_forward(s, buf, d_v2, d_srce, sx, sz, 0, nullptr, it0, nsteps, first_pp_twice, ip, ipp);
+}
+
+extern "C" int fdw_slabs_dev_record_forward(fdw_slabs* s, float* const* buf, const float* d_v2, const float* d_srce, int sx, int sz, int gz, float* d_rec,
+                                            int it0, int nsteps, int first_pp_twice, int* ip, int* ipp)
+{
+    if (!s || !d_rec) return fdw_fail(FDW_EINVAL, "slabs record forward: NULL argument");
+    if (it0 < 0) return fdw_fail(FDW_EINVAL, "it0=%d", it0);
+    FDW_TRY(fdw_check_record_depth(s->ctx, gz));      // the same decision on every rank (global extents), before anything is enqueued
+    return slabs_forward(s, buf, d_v2, d_srce, sx, sz, gz, d_rec, it0, nsteps, first_pp_twice, ip, ipp);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -498,4 +525,60 @@ extern "C" int fdw_slabs_shot(fdw_slabs* s, const float* v2, int sx, int sz, int
         HIP_TRY(hipMemcpy2DAsync(imloc + (size_t)(w0 - p.nxb) * nz, (size_t)nz * sizeof(float), s->d_img + s->row(w0 - s->x_off) + p.nzb,
                                  (size_t)s->pitch * sizeof(float), (size_t)nz * sizeof(float), w1 - w0, hipMemcpyDeviceToHost, st));
     return fdw_slabs_synchronize(s);
+}
+
+// ------------------------------------------------------------------------------------------------
+// host-array entry point: one recorded shot from rest (fdw_record_shot, R:496-497 + R:259-267) on the decomposed grid
+// ------------------------------------------------------------------------------------------------
+extern "C" int fdw_slabs_record_shot(fdw_slabs* s, const float* v2, int sx, int sz, int gz, const float* srce, float* data, float* P, float* PP)
+{
+    if (!s || !v2 || !srce || !data) return fdw_fail(FDW_EINVAL, "slabs record shot: NULL argument");
+    const fdw_params& p = s->prm;
+    const int nt = p.nt, nx = p.nxe - 2 * p.nxb, nze = p.nze;
+    // refusals first, from global quantities only: every rank takes the same decision before anything is enqueued
+    FDW_TRY(fdw_check_record_depth(s->ctx, gz));
+    if (nx <= 0) return fdw_fail(FDW_EINVAL, "no receiver rows");
+    HIP_TRY(hipSetDevice(s->device));
+    const size_t fe = (size_t)s->nxl * s->pitch, nrec = (size_t)nt * nx;
+    for (int i = 0; i < s->nbuf; i++) FDW_TRY(ensure(&s->fld[i], fe));
+    FDW_TRY(ensure(&s->d_v2, fe));
+    if (s->srce_cap < (size_t)nt) {
+        if (s->d_srce) (void)hipFree(s->d_srce);
+        s->d_srce = nullptr;
+        FDW_TRY(ensure(&s->d_srce, (size_t)nt));
+        s->srce_cap = (size_t)nt;
+    }
+    if (s->rec_cap < nrec) {
+        if (s->d_rec) (void)hipFree(s->d_rec);
+        s->d_rec = nullptr;
+        FDW_TRY(ensure(&s->d_rec, nrec));
+        s->rec_cap = nrec;
+    }
+    hipStream_t st = s->compute;
+    HIP_TRY(hipMemsetAsync(s->d_v2, 0, fe * sizeof(float), st));
+    HIP_TRY(hipMemcpy2DAsync(s->d_v2, (size_t)s->pitch * sizeof(float), v2 + (size_t)s->x_off * nze, (size_t)nze * sizeof(float), (size_t)nze * sizeof(float),
+                             s->nxl, hipMemcpyHostToDevice, st));
+    for (int i = 0; i < s->nbuf; i++) HIP_TRY(hipMemsetAsync(s->fld[i], 0, fe * sizeof(float), st));      // R:496-497
+    HIP_TRY(hipMemsetAsync(s->d_rec, 0, std::max<size_t>(nrec, 1) * sizeof(float), st));
+    HIP_TRY(hipMemcpyAsync(s->d_srce, srce, (size_t)nt * sizeof(float), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipStreamSynchronize(st));      // the other streams start from a settled state
+    s->fresh = false;
+    int ip = 0, ipp = 1;
+    FDW_TRY(slabs_forward(s, s->fld, s->d_v2, s->d_srce, sx, sz, gz, s->d_rec, 0, nt, 0, &ip, &ipp));
+    if (nt > 0 && P) FDW_TRY(fdw_dev_taper_finalize(s->ctx, s->fld[ip], s->compute));      // the T() d_p still owes (R:285 downloads the damped d_p)
+    FDW_TRY(fdw_slabs_synchronize(s));      // the boundary strips' samples come from the side stream
+    auto download_owned = [&](float* dst, const float* src) {
+        return hipMemcpy2DAsync(dst + (size_t)s->o0 * nze, (size_t)nze * sizeof(float), src + s->row(s->g_lo), (size_t)s->pitch * sizeof(float),
+                                (size_t)nze * sizeof(float), s->o1 - s->o0, hipMemcpyDeviceToHost, st);
+    };
+    if (P) HIP_TRY(download_owned(P, s->fld[ip]));
+    if (PP) HIP_TRY(download_owned(PP, s->fld[ipp]));
+    // device [it][ix] -> data[ix][it], the owned interior rows only
+    std::vector<float> t(std::max<size_t>(nrec, 1));
+    HIP_TRY(hipMemcpyAsync(t.data(), s->d_rec, nrec * sizeof(float), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    const int w0 = std::max(s->o0, p.nxb), w1 = std::min(s->o1, p.nxb + nx);
+    for (int g = w0; g < w1; g++)
+        for (int it = 0; it < nt; it++) data[(size_t)(g - p.nxb) * nt + it] = t[(size_t)it * nx + (g - p.nxb)];
+    return FDW_OK;
 }

@@ -17,8 +17,8 @@
  * Source illumination (no counterpart in the reference): the deck key `illum=1` makes every shot's forward loop accumulate sum_t F_t^2
  * (fdw_shot_illum; per shot from zero, stacked on the host in shot order like the image) and adds two outputs, <tmpdir>/dir.illum (the
  * stack, [nx][nz]) and <tmpdir>/dir.image_illum = fdw_image_compensate(image, illumination, illum_eps), `illum_eps` defaulting to 1e-3.
- * dir.image, dir.image_lap and image.num are what they are without the key.  Shots then go one by one per worker (no fdw_shot_batch);
- * together with slabs > 1 the key is refused. */
+ * dir.image, dir.image_lap and image.num are what they are without the key.  Small decks still advance a batch of shots through one
+ * launch per time step (fdw_shot_batch_illum: one accumulator field per shot); together with slabs > 1 the key is refused. */
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -303,6 +303,7 @@ int main(int argc, char **argv)
         fprintf(stderr, "slabs / gpus: at most 64\n");
         return EXIT_FAILURE;
     }
+    int shots_per_launch = 1;      /* FDW_TIMING: how many shots advance through one launch per time step */
     if (slabs > 1) {
         /* ---- every shot on `slabs` GPUs: bands of rows, halo exchange inside the library ---- */
         slab_job sj;
@@ -370,7 +371,7 @@ int main(int argc, char **argv)
      * the chip for this geometry, 1 = the grid is big enough by itself).  FDW_NO_SHOT_BATCH=1 keeps one shot per launch sequence. */
     fdw_ctx *bctx = NULL;
     int bmax = 1;
-    if (ns > 1 && !getenv("FDW_NO_SHOT_BATCH") && gpus <= 1 && !illum) {      /* (shots dealt to several GPUs go one context per worker instead) */
+    if (ns > 1 && !getenv("FDW_NO_SHOT_BATCH") && gpus <= 1) {      /* (shots dealt to several GPUs go one context per worker instead) */
         if (fdw_create(&prm, 0, &bctx) != FDW_OK) {
             fprintf(stderr, "fdw_create: %s\n", fdw_last_error());
             return EXIT_FAILURE;
@@ -387,6 +388,7 @@ int main(int argc, char **argv)
         }
     }
     const int batch = bctx ? bmax : (nworkers > 1 ? ns : 1);      /* shots whose model and image are held at once */
+    if (bctx) shots_per_launch = bmax;
     float *vel2_all = (float *)malloc((size_t)batch * ne * sizeof(float)), *imloc_all = (float *)calloc((size_t)batch * ni, sizeof(float));
     float *illoc_all = illum ? (float *)calloc((size_t)batch * ni, sizeof(float)) : NULL, *ill = illum ? (float *)calloc(ni, sizeof(float)) : NULL;
     if (!vel2_all || !imloc_all || (illum && (!illoc_all || !ill))) {
@@ -417,8 +419,10 @@ int main(int argc, char **argv)
         if (bctx) {
             /* shots is0 .. is0 + nb - 1: source rows sx[is0] + b ds (R:405-407), border models from draws [(is0 + b) T, ...) of the stream */
             /* models: drawn on the device, or the host-built ones of this batch (vel_ext_file decks, FDW_HOST_BORDER=1) */
-            if (fdw_shot_batch(bctx, nb, dev_border ? NULL : vel2_all, (unsigned long long)is0 * (unsigned long long)job.draws, sx[is0], ds, sz, gz, srce,
-                               d_obs + (size_t)is0 * nx * nt, imloc_all) != FDW_OK) {
+            const unsigned long long draw0 = (unsigned long long)is0 * (unsigned long long)job.draws;
+            const float *models = dev_border ? NULL : vel2_all, *gathers = d_obs + (size_t)is0 * nx * nt;
+            if ((illum ? fdw_shot_batch_illum(bctx, nb, models, draw0, sx[is0], ds, sz, gz, srce, gathers, imloc_all, illoc_all)
+                       : fdw_shot_batch(bctx, nb, models, draw0, sx[is0], ds, sz, gz, srce, gathers, imloc_all)) != FDW_OK) {
                 fprintf(stderr, "fdw_shot_batch: %s\n", fdw_last_error());
                 return EXIT_FAILURE;
             }
@@ -480,6 +484,9 @@ int main(int argc, char **argv)
         free(ill);
     }
 outputs:
+    if (timing)
+        fprintf(stderr, "[timing] shots per launch sequence: up to %d (%s)\n", shots_per_launch,
+                shots_per_launch > 1 ? (illum ? "fdw_shot_batch_illum" : "fdw_shot_batch") : "one by one");
     if (timing)
         fprintf(stderr, "[timing] total %.3f s: shots (contexts, border models, propagation) %.3f s, stacking + image.num %.3f s, rest (deck, inputs) %.3f s\n",
                 now_s() - t_begin, t_shots, t_stack, now_s() - t_begin - t_shots - t_stack);

@@ -103,8 +103,8 @@ class Comm:
 class Slabs:
     """This rank's share of an x-slab decomposition (fdw_slabs_create).  Collective: every rank of `comm` constructs one."""
 
-    def __init__(self, order, nxe, nze, nxb, nzb, nt, fac, dx, dz, dt, comm=None, compat=True, device=0, ksteps=0, numerics=0):
-        self.params = Params(order, nxe, nze, nxb, nzb, nt, dx, dz, dt, fac, int(compat), 0, 0, int(numerics))
+    def __init__(self, order, nxe, nze, nxb, nzb, nt, fac, dx, dz, dt, comm=None, compat=True, device=0, ksteps=0, numerics=0, dialect=0):
+        self.params = Params(order, nxe, nze, nxb, nzb, nt, dx, dz, dt, fac, int(compat), 0, int(dialect), int(numerics))
         self._h = C.c_void_p()
         self.comm = comm
         check(lib().fdw_slabs_create(C.byref(self.params), comm._h if comm is not None else None, device, ksteps, C.byref(self._h)))
@@ -127,6 +127,15 @@ class Slabs:
         arr = (C.c_void_p * len(bufs))(*bufs)
         a, b = C.c_int(ip), C.c_int(ipp)
         check(lib().fdw_slabs_dev_forward(self._h, arr, d_v2, d_srce, sx, sz, it0, nsteps, int(first_pp_twice), C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def dev_record_forward(self, bufs, d_v2, d_srce, sx, sz, gz, d_rec, it0, nsteps, first_pp_twice=False, ip=0, ipp=1):
+        """dev_forward that also writes the trace samples of iteration it to d_rec + it * nx (this rank's own device array [>= it0+nsteps][nx],
+        global receiver index; the entries of the rank's owned interior rows are defined on return, fdwave.h)."""
+        arr = (C.c_void_p * len(bufs))(*bufs)
+        a, b = C.c_int(ip), C.c_int(ipp)
+        check(lib().fdw_slabs_dev_record_forward(self._h, arr, d_v2, d_srce, sx, sz, gz, d_rec, it0, nsteps, int(first_pp_twice), C.byref(a),
+                                                 C.byref(b)))
         return a.value, b.value
 
     def back_buffers(self):
@@ -161,6 +170,17 @@ class Slabs:
         check(lib().fdw_slabs_shot(self._h, _f32(v2, shape), sx, sz, gz, _f32(srce, (self.nt,)), _f32(d_obs, (self.nx, self.nt)), imloc,
                                    P.ctypes.data if want_fields else None, PP.ctypes.data if want_fields else None))
         return (imloc, P, PP) if want_fields else imloc
+
+    def record_shot(self, v2, sx, sz, gz, srce, want_fields=False):
+        """FDWave.record_shot on the decomposed grid (global host arrays in; this rank's OWNED interior rows of data[nx][nt] and owned rows of
+        P / PP out)."""
+        shape = (self.nxe, self.nze)
+        data = np.zeros((self.nx, self.nt), np.float32)
+        P = np.zeros(shape, np.float32) if want_fields else None
+        PP = np.zeros(shape, np.float32) if want_fields else None
+        check(lib().fdw_slabs_record_shot(self._h, _f32(v2, shape), sx, sz, gz, _f32(srce, (self.nt,)), data,
+                                          P.ctypes.data if want_fields else None, PP.ctypes.data if want_fields else None))
+        return (data, P, PP) if want_fields else data
 
     def owned_interior_rows(self):
         """Rows [a, b) of the image imloc[nx][nz] this rank produces."""
