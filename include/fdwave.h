@@ -359,6 +359,41 @@ int fdw_shot_batch_illum(fdw_ctx *ctx, int nshots, const float *v2_all, unsigned
                          const float *srce, const float *d_obs, float *imloc, float *illum);
 int fdw_image_compensate(const float *img, const float *illum, size_t n, float eps, float *out);
 
+/* ---- wavefield snapshots from both loops of a shot (rtm_code's dir.snaps, dir.snaps_rec, dir.snapr) --------------------------------
+ * The reference opens the three files and leaves them empty (R:465-470; its deck key iss, "save snaps of this source", R:368, is read and
+ * dropped).  Definitions, for the parameters every = K >= 1 and dec = D >= 1, RTM dialect, full-grid contexts, EXACT and FAST numerics alike:
+ *   levels     frames are taken at the time levels L = K, 2K, ... <= nt: nframes = nt / K (integer division, may be 0); frame j is level
+ *              (j+1) K in all three sets, in ascending time.
+ *   snaps      u^L: what d_pp holds at the end of forward iteration it = L-1, after kernel_src (R:267) -- the level the recorded gathers
+ *              and the illumination sample: raw, undamped, source sample included.
+ *   snaps_rec  F_k with k = nt - L: the source field backward iteration k images (d_p after the swap of R:321-323).  k = 0 is u^nt, k = 1
+ *              the handed-over P, damped once (R:285); k >= 2 are reconstructed by the undamped leap-frog of R:317-318.
+ *   snapr      r^{k+1} of the same iteration: d_ppr after kernel_sism (R:328), the field multiplied into the image at R:329.
+ *   frame      the interior cells (nxb + a D, nzb + b D): nxs = ceil(nx / D) by nzs = ceil(nz / D) floats laid out [nxs][nzs], z fastest,
+ *              like dir.image.  Cells the loops never time-step (compat extents) carry what the device arrays hold, as the reference's do.
+ * So imloc = sum over k of snaps_rec(level nt-k) (*) snapr(level nt-k) on the cells kernel_img covers, added in iteration order, and
+ * snaps_rec against snaps measures how well the reconstruction from the last two fields reproduces the forward run.
+ * Frames stay in a device store per requested set ([nframes][nxs][nzs]) and each set is downloaded once at the end of the shot.  The forward
+ * loop runs in segments that end on the levels; in the backward loop no pass of several iterations reaches across iteration nt - L, so a K
+ * that is no multiple of four (two) leaves single iterations around every stop where the loop would otherwise run four (two) per pass:
+ * measured on one MI355X at 8192^2, 500 steps, D = 8: K = 100 adds 1.8 % to the plain shot's 180 ms, K = 50 adds 5.8 % -- visibly more: prefer a multiple of four.
+ * Every family of passes equals the one-step iteration bit for bit: imloc, P, PP and illum are fdw_shot's / fdw_shot_illum's.
+ * fdw_snap_dims     the frame count and shape for a geometry; needs no device.  every < 1 or dec < 1: FDW_EINVAL.
+ * fdw_dev_snapshot  one frame of the caller-owned device field d_field [nxl][pitch] into d_frame [nxs][nzs] (device), asynchronous on `stream`:
+ *                   a crop-and-decimate copy without arithmetic (NaN payloads, -0 and subnormals survive).  Slab contexts: FDW_ESTATE.
+ * fdw_shot_snaps    fdw_shot (v2 == NULL: fdw_shot_resident on the resident model) with an optional illum (NULL, or as fdw_shot_illum) that
+ *                   also fills the host arrays of `snaps` ([nframes][nxs][nzs] each; any may be NULL, all three NULL: FDW_EINVAL).  Slab
+ *                   contexts, the sibling's dialects, a context inside a batch: FDW_ESTATE, as for fdw_shot_illum.  Frame stores that do not
+ *                   fit on the device: FDW_ENOMEM with the byte counts, before anything is enqueued. */
+typedef struct fdw_snaps {
+    int every, dec;                      /* K, D */
+    float *snaps, *snaps_rec, *snapr;    /* host, [nframes][nxs][nzs]; NULL = not wanted */
+} fdw_snaps;
+int fdw_snap_dims(int nx, int nz, int nt, int every, int dec, int *nframes, int *nxs, int *nzs);
+int fdw_dev_snapshot(fdw_ctx *ctx, const float *d_field, int dec, float *d_frame, void *stream);
+int fdw_shot_snaps(fdw_ctx *ctx, const float *v2, int sx, int sz, int gz, const float *srce, const float *d_obs, float *imloc, float *illum,
+                   float *P, float *PP, const fdw_snaps *snaps);
+
 /* ---- multi-GPU: communicators and the slab-decomposed loops (csrc/fdw_comm.cpp, csrc/fdw_slabs.cpp) ------------------------
  * The reference has no multi-GPU path.  The grid is decomposed along x, the slow axis, into one band of rows per
  * rank; a rank is one GPU, driven by one process (RCCL backend) or by one host thread of a process (RCCL or local backend).

@@ -31,6 +31,11 @@ class Slab(C.Structure):
     _fields_ = [("x_off", C.c_int), ("nxl", C.c_int)]
 
 
+class Snaps(C.Structure):
+    """struct fdw_snaps (fdwave.h): every, dec and the three host frame sets (NULL = not wanted)."""
+    _fields_ = [("every", C.c_int), ("dec", C.c_int), ("snaps", vp), ("snaps_rec", vp), ("snapr", vp)]
+
+
 # every symbol fdwave.h declares: (name, restype, argtypes)
 SIGNATURES = [
     ("fdw_last_error", C.c_char_p, []),
@@ -78,6 +83,9 @@ SIGNATURES = [
     ("fdw_shot_resident_illum", C.c_int, [vp, C.c_int, C.c_int, C.c_int, f32p, f32p, f32p, f32p, vp, vp]),
     ("fdw_shot_batch_illum", C.c_int, [vp, C.c_int, vp, C.c_ulonglong, C.c_int, C.c_int, C.c_int, C.c_int, f32p, f32p, f32p, f32p]),
     ("fdw_image_compensate", C.c_int, [vp, vp, C.c_size_t, C.c_float, vp]),
+    ("fdw_snap_dims", C.c_int, [C.c_int] * 5 + [C.POINTER(C.c_int)] * 3),
+    ("fdw_dev_snapshot", C.c_int, [vp, vp, C.c_int, vp, vp]),
+    ("fdw_shot_snaps", C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, f32p, f32p, f32p, vp, vp, vp, C.POINTER(Snaps)]),
     ("fdw_rand_stream", C.c_int, [vp, C.c_ulonglong, C.c_longlong, vp]),
     ("fdw_dev_model_steps", C.c_int, [vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, vp]),
     ("fdw_mod_extendvel", None, [C.c_int] * 4 + [f32p]),

@@ -11,7 +11,7 @@ import sys
 import numpy as np
 
 from . import _lib
-from ._lib import Params, Slab, check, lib
+from ._lib import Params, Slab, Snaps, check, lib
 
 
 def _f32(a, shape=None):
@@ -105,6 +105,13 @@ def image_compensate(img, illum, eps=1e-3):
     out = np.empty_like(img)
     check(lib().fdw_image_compensate(img.ctypes.data, illum.ctypes.data, img.size, eps, out.ctypes.data))
     return out
+
+
+def snap_dims(nx, nz, nt, every, dec=1):
+    """fdw_snap_dims: (nframes, nxs, nzs) = (nt // every, ceil(nx / dec), ceil(nz / dec)); every < 1 or dec < 1 is refused.  No device."""
+    a, b, c = C.c_int(), C.c_int(), C.c_int()
+    check(lib().fdw_snap_dims(nx, nz, nt, int(every), int(dec), C.byref(a), C.byref(b), C.byref(c)))
+    return a.value, b.value, c.value
 
 
 class FDWave:
@@ -216,6 +223,41 @@ class FDWave:
         check(lib().fdw_shot(self._h, _f32(v2, shape), sx, sz, gz, _f32(srce, (self.nt,)),
                              _f32(d_obs, (self.nx, self.nt)), imloc, *fields))
         return (imloc, P, PP) if want_fields else imloc
+
+    # ---- wavefield snapshots (fdwave.h: dir.snaps, dir.snaps_rec, dir.snapr) ----
+    def snap_dims(self, every, dec=1):
+        """(nframes, nxs, nzs) of this geometry's snapshots every `every` time levels, decimated by `dec`: frames at levels every, 2 every, ...
+        <= nt of ceil(nx / dec) x ceil(nz / dec) interior cells.  Needs no device."""
+        return snap_dims(self.nx, self.nz, self.nt, every, dec)
+
+    def dev_snapshot(self, d_field, dec, d_frame, stream=None):
+        """One frame of the device field d_field [nxl][pitch] into the device array d_frame [nxs][nzs]: a bit-exact crop-and-decimate copy."""
+        check(lib().fdw_dev_snapshot(self._h, d_field, int(dec), d_frame, stream))
+
+    def shot_snaps(self, v2, sx, sz, gz, srce, d_obs, every, dec=1, sets=("snaps", "snaps_rec", "snapr"), imloc=None, want_fields=False,
+                   want_illum=False, illum=None):
+        """shot() (v2=None: shot_resident()) that also takes wavefield frames at the levels every, 2 every, ... (fdwave.h): `snaps` the forward
+        field u^L, `snaps_rec` the source field the backward loop images at that level, `snapr` the receiver field it is multiplied with.
+        Returns a dict: image, the requested sets as [nframes][nxs][nzs], and P, PP / illum if asked."""
+        nframes, nxs, nzs = self.snap_dims(every, dec)
+        unknown = set(sets) - {"snaps", "snaps_rec", "snapr"}
+        if unknown:
+            raise ValueError(f"unknown frame sets {sorted(unknown)}")
+        shape = (self.nxe, self.nze)
+        out = {name: np.zeros((nframes, nxs, nzs), np.float32) for name in sets}
+        out["image"] = np.zeros((self.nx, self.nz), np.float32) if imloc is None else np.array(imloc, np.float32, order="C")
+        if want_fields:
+            out["P"], out["PP"] = np.zeros(shape, np.float32), np.zeros(shape, np.float32)
+        if want_illum:
+            out["illum"] = np.zeros((self.nx, self.nz), np.float32) if illum is None else np.array(_f32(illum, (self.nx, self.nz)), order="C")
+
+        def ptr(name):
+            return out[name].ctypes.data if name in out else None
+
+        sn = Snaps(int(every), int(dec), ptr("snaps"), ptr("snaps_rec"), ptr("snapr"))
+        check(lib().fdw_shot_snaps(self._h, None if v2 is None else _f32(v2, shape).ctypes.data, sx, sz, gz, _f32(srce, (self.nt,)),
+                                   _f32(d_obs, (self.nx, self.nt)), out["image"], ptr("illum"), ptr("P"), ptr("PP"), C.byref(sn)))
+        return out
 
     # ---- random-border model generated on the device (SURVEY.md section 8 row f4) ----
     def border_draws(self):

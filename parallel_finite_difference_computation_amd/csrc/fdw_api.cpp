@@ -69,6 +69,8 @@ struct fdw_ctx {
     float* fld[10] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};      // 8, 9: source-field levels of a backward pipeline pass
     float *d_v2 = nullptr, *d_img = nullptr, *d_srce = nullptr, *d_dobs = nullptr;
     float* d_illum = nullptr;   // source illumination of one shot on the extended grid (fdw_shot_illum); allocated on first use
+    float* d_snap[3] = {nullptr, nullptr, nullptr};   // frame stores of fdw_shot_snaps (snaps, snaps_rec, snapr): [nframes][nxs][nzs] each
+    size_t snap_cap[3] = {0, 0, 0};
     size_t srce_cap = 0, dobs_cap = 0;
     // tuning
     int xchunk = 0, wz = 0, use_generic = 0, prefetch = 0, force_edge = 0, xchunk2 = 0;
@@ -345,7 +347,7 @@ extern "C" void fdw_destroy(fdw_ctx* c)
     float* bufs[] = {c->d_taperz, c->d_txfac, c->d_gcx, c->d_gcz, c->fld[0], c->fld[1], c->fld[2], c->fld[3],
                      c->fld[4], c->fld[5], c->fld[6], c->fld[7], c->fld[8], c->fld[9], c->d_v2, c->d_img, c->d_illum, c->d_srce, c->d_dobs, c->d_rec,
                      c->d_vp, c->d_vpe, (float*)c->d_draws, (float*)c->d_jump, c->bfld[0], c->bfld[1], c->bfld[2], c->bfld[3],
-                     c->bfld[4], c->bfld[5], c->bfld[6], c->bfld[7], c->b_v2, c->b_img, c->b_dobs, c->b_illum, c->d_raw};
+                     c->bfld[4], c->bfld[5], c->bfld[6], c->bfld[7], c->b_v2, c->b_img, c->b_dobs, c->b_illum, c->d_raw, c->d_snap[0], c->d_snap[1], c->d_snap[2]};
     for (float* b : bufs)
         if (b) (void)hipFree(b);
     if (c->stream) (void)hipStreamDestroy(c->stream);
@@ -1117,6 +1119,23 @@ extern "C" int fdw_laplacian(fdw_ctx* c, const float* p, float* lap)
     return FDW_OK;
 }
 
+// ---- wavefield snapshots (fdw_snap_dims, fdw_dev_snapshot, fdw_shot_snaps; definitions in fdwave.h) ----
+static int snap_extent(int n, int dec) { return (n + dec - 1) / dec; }
+
+struct SnapPlan {        // one shot's snapshots: the frame geometry and the device frame stores of the requested sets
+    int every = 1, dec = 1, nframes = 0, nxs = 0, nzs = 0;
+    float* store[3] = {nullptr, nullptr, nullptr};      // snaps, snaps_rec, snapr: [nframes][nxs][nzs]; NULL = not requested
+    size_t frame_elems() const { return (size_t)nxs * (size_t)nzs; }
+};
+
+// the interior cells (nxb + a dec, nzb + b dec) of one field as one dense frame [ceil(nx/dec)][ceil(nz/dec)]
+static int snapshot(fdw_ctx* c, const float* d_field, int dec, float* d_frame, hipStream_t s)
+{
+    hipError_t e = launch_snapshot(d_field, d_frame, c->pitch, c->prm.nxb, c->prm.nzb, dec, snap_extent(c->nx, dec), snap_extent(c->nz, dec), s);
+    if (e != hipSuccess) return fail(FDW_EHIP, "snapshot launch failed: %s", hipGetErrorString(e));
+    return FDW_OK;
+}
+
 static int upload_source(fdw_ctx* c, const float* srce, int n)
 {
     int rc = ensure_cap(&c->d_srce, &c->srce_cap, (size_t)std::max(n, 1));
@@ -1127,10 +1146,20 @@ static int upload_source(fdw_ctx* c, const float* srce, int n)
 
 // fd_forward's loop body R:259-267 for nsteps iterations over the context's four field buffers (pairs of steps go
 // through the two-step kernel where it pays); *ip / *ipp index (d_p, d_pp) before the loop and after it.  d_rec: trace rows [nt][nx] at gz.
-static int forward_loop(fdw_ctx* c, int* ip, int* ipp, int sx, int sz, int nsteps, int gz = 0, float* d_rec = nullptr, float* d_illum = nullptr)
+// sn (fdw_shot_snaps): the loop runs in segments that end on the snapshot levels L = every, 2 every, ... (a loop cut at any iteration equals the
+// uncut one bit for bit: it0 and the owed-taper flag carry over), and after each the frame of d_pp = u^L goes into the frame store.
+static int forward_loop(fdw_ctx* c, int* ip, int* ipp, int sx, int sz, int nsteps, int gz = 0, float* d_rec = nullptr, float* d_illum = nullptr,
+                        const SnapPlan* sn = nullptr)
 {
     FDW_RANGE("fdw: forward loop (fd_forward)");
-    int rc = steps_loop(c, c->fld, c->d_v2, c->d_srce, sx, sz, gz, d_rec, 0, nsteps, 0, ip, ipp, c->stream, d_illum);
+    int it = 0;
+    for (int j = 0; sn && sn->store[0] && j < sn->nframes; j++) {
+        const int level = (j + 1) * sn->every;
+        FDW_TRY(steps_loop(c, c->fld, c->d_v2, c->d_srce, sx, sz, gz, d_rec, it, level - it, it > 0, ip, ipp, c->stream, d_illum));
+        FDW_TRY(snapshot(c, c->fld[*ipp], sn->dec, sn->store[0] + (size_t)j * sn->frame_elems(), c->stream));
+        it = level;
+    }
+    int rc = steps_loop(c, c->fld, c->d_v2, c->d_srce, sx, sz, gz, d_rec, it, nsteps - it, it > 0, ip, ipp, c->stream, d_illum);
     if (rc) return rc;
     if (nsteps > 0) return fdw_dev_taper_finalize(c, c->fld[*ip], c->stream);   // the T() d_p still owes (R:285 downloads the damped d_p)
     return FDW_OK;
@@ -1199,7 +1228,10 @@ static int image_to_host(fdw_ctx* c, float* imloc, const float* d_src = nullptr)
 // pass reconstructs F_k, F_{k+1}; one pass advances the receiver field twice and applies both imaging conditions), singly through the
 // one-step kernels otherwise (back_iter).  src[0..3] / rcv[0..3]: rotating buffers; on entry src[0] = snap0, src[1] = snap1, the receivers
 // are zero.
-static int back_loop(fdw_ctx* c, float* const src[4], float* const rcv[4], int gz, int nsteps)
+// sn (fdw_shot_snaps): iterations k = nt - L of the snapshot levels L are STOPS: no pass of several iterations reaches across one (the
+// family is chosen by the iterations left until the next stop; every family equals the one-step iteration bit for bit, so the image
+// does not change), and after iteration k the frames of F_k and r^{k+1} go into the frame stores at index L / every - 1.
+static int back_loop(fdw_ctx* c, float* const src[4], float* const rcv[4], int gz, int nsteps, const SnapPlan* sn = nullptr)
 {
     FDW_RANGE("fdw: backward loop + imaging (fd_back)");
     const int nt = c->prm.nt;
@@ -1210,12 +1242,18 @@ static int back_loop(fdw_ctx* c, float* const src[4], float* const rcv[4], int g
     int it = 0;
     const bool pairs = two_step_pays(c);
     const bool pipe = fdw_back_pipe_active(c) && c->nbatch <= 1;
+    std::vector<int> stops;      // ascending iterations after which frames are taken
+    if (sn && (sn->store[1] || sn->store[2]))
+        for (int j = sn->nframes - 1; j >= 0; j--)
+            if (nt - (j + 1) * sn->every < nsteps) stops.push_back(nt - (j + 1) * sn->every);
+    size_t next = 0;             // stops[next] = the first stop not yet passed
     if (pipe && c->no_back_fused && nsteps >= 2 + kPipeSteps) {      // the two-pass form keeps two levels in memory
         FDW_TRY(alloc_zero(&c->fld[8], field_elems(c)));
         FDW_TRY(alloc_zero(&c->fld[9], field_elems(c)));
     }
     while (it < nsteps) {
-        if (pipe && it >= 2 && nsteps - it >= kPipeSteps) {
+        const int left = (next < stops.size() ? stops[next] + 1 : nsteps) - it;      // iterations until the next stop (or the end)
+        if (pipe && it >= 2 && left >= kPipeSteps) {
             int o1, o2, q1, q2;
             spare_pair(f1, f0, &o1, &o2);
             spare_pair(rn, ro, &q1, &q2);
@@ -1225,7 +1263,7 @@ static int back_loop(fdw_ctx* c, float* const src[4], float* const rcv[4], int g
             f0 = o1; f1 = o2;
             ro = q1; rn = q2;
             it += kPipeSteps;
-        } else if (pairs && nsteps - it >= 2) {
+        } else if (pairs && left >= 2 && it != 1) {      // (it = 1 only after a stop at iteration 0: F_1 is still a snapshot, a pair would reconstruct it)
             const float *Fa, *Fb;   // source fields of iterations it, it+1
             if (it == 0) {
                 Fa = src[1]; Fb = src[0];                      // u^nt, u^{nt-1}
@@ -1250,6 +1288,13 @@ static int back_loop(fdw_ctx* c, float* const src[4], float* const rcv[4], int g
             if (it >= 2) std::swap(f1, f0);
             std::swap(rn, ro);
             it += 1;
+        }
+        if (next < stops.size() && it == stops[next] + 1) {
+            // F_k: u^nt (src[1]) at k = 0, then the newer of the source pair (k = 1: the handed-over P in src[0]); r^{k+1}: the newer receiver field
+            const int k = stops[next++];
+            const size_t off = (size_t)((nt - k) / sn->every - 1) * sn->frame_elems();
+            if (sn->store[1]) FDW_TRY(snapshot(c, k == 0 ? src[1] : src[f1], sn->dec, sn->store[1] + off, c->stream));
+            if (sn->store[2]) FDW_TRY(snapshot(c, rcv[rn], sn->dec, sn->store[2] + off, c->stream));
         }
     }
     return FDW_OK;
@@ -1292,8 +1337,9 @@ extern "C" int fdw_back(fdw_ctx* c, const float* v2, const float* snap0, const f
 
 // v2 == nullptr: the squared model already resident in c->d_v2 (fdw_dev_extendvel_linear)
 // illum: NULL, or the interior illumination [nx][nz] the forward loop accumulates into (fdw_shot_illum)
+// sn: NULL, or the snapshot plan of fdw_shot_snaps (frame stores already allocated)
 static int shot_impl(fdw_ctx* c, const float* v2, int sx, int sz, int gz, const float* srce, const float* d_obs, float* imloc, float* P, float* PP,
-                     float* illum = nullptr)
+                     float* illum = nullptr, const SnapPlan* sn = nullptr)
 {
     if (!c || !srce || !d_obs || !imloc) return fail(FDW_EINVAL, "NULL argument");
     FDW_RANGE("fdw: shot (uploads, forward, backward, image download)");
@@ -1310,14 +1356,14 @@ static int shot_impl(fdw_ctx* c, const float* v2, int sx, int sz, int gz, const 
         (rc = image_to_device(c, imloc)))
         return rc;
     if (illum && ((rc = alloc_zero(&c->d_illum, field_elems(c))) || (rc = image_to_device(c, illum, c->d_illum)))) return rc;
-    if ((rc = forward_loop(c, &ip, &ipp, sx, sz, nt, 0, nullptr, illum ? c->d_illum : nullptr))) return rc;
+    if ((rc = forward_loop(c, &ip, &ipp, sx, sz, nt, 0, nullptr, illum ? c->d_illum : nullptr, sn))) return rc;
     if (illum && (rc = image_to_host(c, illum, c->d_illum))) return rc;
     if (P && (rc = download_rows(c, P, c->fld[ip], c->stream))) return rc;
     if (PP && (rc = download_rows(c, PP, c->fld[ipp], c->stream))) return rc;
     float* src[4];
     source_buffers(c, ip, ipp, src);
     if ((rc = zero_fields(c, c->fld + 4, 2))) return rc;
-    if ((rc = back_loop(c, src, c->fld + 4, gz, nt))) return rc;
+    if ((rc = back_loop(c, src, c->fld + 4, gz, nt, sn))) return rc;
     if ((rc = image_to_host(c, imloc))) return rc;
     HIP_TRY(hipStreamSynchronize(c->stream));
     return FDW_OK;
@@ -1338,6 +1384,72 @@ extern "C" int fdw_shot_illum(fdw_ctx* c, const float* v2, int sx, int sz, int g
     FDW_TRY(check_illum_ctx(c, "fdw_shot_illum"));
     c->v2_resident = false;
     return shot_impl(c, v2, sx, sz, gz, srce, d_obs, imloc, P, PP, illum);
+}
+
+// ---- wavefield snapshots ----
+extern "C" int fdw_snap_dims(int nx, int nz, int nt, int every, int dec, int* nframes, int* nxs, int* nzs)
+{
+    if (every < 1 || dec < 1) return fail(FDW_EINVAL, "snapshots: every=%d and dec=%d must both be >= 1", every, dec);
+    if (nx < 0 || nz < 0 || nt < 0) return fail(FDW_EINVAL, "snapshots: nx=%d nz=%d nt=%d", nx, nz, nt);
+    if (nframes) *nframes = nt / every;
+    if (nxs) *nxs = snap_extent(nx, dec);
+    if (nzs) *nzs = snap_extent(nz, dec);
+    return FDW_OK;
+}
+
+static int check_snaps_ctx(const fdw_ctx* c, const char* who)
+{
+    if (c->prm.dialect != FDW_DIALECT_RTM) return fail(FDW_ESTATE, "%s: wavefield snapshots belong to the RTM dialect", who);
+    if (!is_full_grid(c)) return fail(FDW_ESTATE, "%s: wavefield snapshots need a full-grid context (slab-decomposed shots are not covered)", who);
+    if (c->nbatch > 1) return fail(FDW_ESTATE, "%s: not inside a batch of shots", who);
+    return FDW_OK;
+}
+
+extern "C" int fdw_dev_snapshot(fdw_ctx* c, const float* d_field, int dec, float* d_frame, void* stream)
+{
+    if (!c || !d_field || !d_frame) return fail(FDW_EINVAL, "NULL argument");
+    if (dec < 1) return fail(FDW_EINVAL, "snapshot: dec=%d must be >= 1", dec);
+    FDW_TRY(check_snaps_ctx(c, "fdw_dev_snapshot"));
+    if (c->nx <= 0 || c->nz <= 0) return fail(FDW_EINVAL, "no interior to take a frame of");
+    return snapshot(c, d_field, dec, d_frame, pick_stream(c, stream));
+}
+
+extern "C" int fdw_shot_snaps(fdw_ctx* c, const float* v2, int sx, int sz, int gz, const float* srce, const float* d_obs, float* imloc, float* illum,
+                              float* P, float* PP, const fdw_snaps* snaps)
+{
+    if (!c || !snaps) return fail(FDW_EINVAL, "NULL argument");
+    float* const host[3] = {snaps->snaps, snaps->snaps_rec, snaps->snapr};
+    if (!host[0] && !host[1] && !host[2]) return fail(FDW_EINVAL, "fdw_shot_snaps: none of snaps, snaps_rec, snapr is requested");
+    SnapPlan plan;
+    plan.every = snaps->every; plan.dec = snaps->dec;
+    FDW_TRY(fdw_snap_dims(c->nx, c->nz, c->prm.nt, snaps->every, snaps->dec, &plan.nframes, &plan.nxs, &plan.nzs));
+    FDW_TRY(check_snaps_ctx(c, "fdw_shot_snaps"));
+    if (!v2 && !c->v2_resident) return fail(FDW_ESTATE, "no resident squared model: call fdw_dev_extendvel_linear first");
+    if (!srce || !d_obs || !imloc) return fail(FDW_EINVAL, "NULL argument");
+    if (c->nx <= 0 || c->nz <= 0) return fail(FDW_EINVAL, "no interior to image");
+    HIP_TRY(hipSetDevice(c->device));
+    // the frame stores, before anything is enqueued
+    const size_t set_elems = (size_t)plan.nframes * plan.frame_elems();
+    int nsets = 0;
+    for (int i = 0; i < 3; i++) nsets += host[i] != nullptr;
+    FDW_TRY(ensure_work_buffers(c, 8, true));
+    for (int i = 0; i < 3 && set_elems > 0; i++) {
+        if (!host[i]) continue;
+        if (ensure_cap(&c->d_snap[i], &c->snap_cap[i], set_elems) != FDW_OK) {
+            size_t free_b = 0, total_b = 0;
+            (void)hipMemGetInfo(&free_b, &total_b);
+            return fail(FDW_ENOMEM, "fdw_shot_snaps: the frame stores do not fit: %d sets x %d frames x %zu bytes = %zu bytes, %zu bytes free on the device",
+                        nsets, plan.nframes, plan.frame_elems() * sizeof(float), (size_t)nsets * set_elems * sizeof(float), free_b);
+        }
+        plan.store[i] = c->d_snap[i];
+    }
+    if (v2) c->v2_resident = false;
+    FDW_TRY(shot_impl(c, v2, sx, sz, gz, srce, d_obs, imloc, P, PP, illum, &plan));
+    // one download per set (shot_impl has synchronised: the copies below are the only work left on the stream)
+    for (int i = 0; i < 3; i++)
+        if (plan.store[i]) HIP_TRY(hipMemcpyAsync(host[i], plan.store[i], set_elems * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return FDW_OK;
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -127,6 +127,8 @@ hipError_t launch_taper_finalize(float* f, const float* taperz, const float* txf
 // source illumination of the orders without a register-ring kernel: illum += f (*) f on rows [r0, r1), columns < z1 (fdw_illum_add_kernel)
 hipError_t launch_illum_add(const float* f, float* illum, int pitch, int r0, int r1, int z1, hipStream_t s);
 hipError_t launch_selftest(const float* src, float* out, hipStream_t s);
+// one field [.][pitch] cropped to the cells (x0 + a dec, z0 + b dec), a < nxs, b < nzs, as one dense frame [nxs][nzs] (fdw_snapshot_kernel)
+hipError_t launch_snapshot(const float* f, float* frame, int pitch, int x0, int z0, int dec, int nxs, int nzs, hipStream_t s);
 // receiver rows the reference injects and images but never time-steps (truncated launch extents with a narrow x border): see fdw_static_rows_kernel
 // trace samples of receiver rows the loop never time-steps: see fdw_record_static_kernel
 hipError_t launch_record_static(const float* p0, const float* pp0, float* rec, int pitch, int row0, int nrows, int gz, int rec_x0, int rec_n, int nsteps,

@@ -603,6 +603,21 @@ __global__ __launch_bounds__(256) void fdw_record_static_kernel(const float* p0,
     rec[b * rec_bstride + (long long)k * rec_n + (row - rec_x0)] = ((k & 1) ? pp0 : p0)[b * bstride + (long long)row * pitch + gz];
 }
 
+// Wavefield snapshot (fdw_dev_snapshot, fdw_shot_snaps): frame[a][b] = f(x0 + a dec, z0 + b dec) for a < nxs, b < nzs -- the interior of one
+// field cropped and decimated into one dense frame, z fastest like dir.image.  Lanes run along z: the stores are coalesced, the loads too
+// when dec = 1.  No arithmetic: the values travel as 32-bit words, so NaN payloads, -0 and subnormals arrive as they are.  blockIdx.y strides
+// over the frame rows (a grid holds 65 535 of them at most).
+__global__ __launch_bounds__(256) void fdw_snapshot_kernel(const float* f, float* frame, int pitch, int x0, int z0, int dec, int nxs, int nzs)
+{
+    const int b = blockIdx.x * 256 + threadIdx.x;
+    if (b >= nzs) return;
+    const unsigned* src = reinterpret_cast<const unsigned*>(f);
+    unsigned* dst = reinterpret_cast<unsigned*>(frame);
+    const size_t col = (size_t)z0 + (size_t)b * (size_t)dec;
+    for (int a = blockIdx.y; a < nxs; a += gridDim.y)
+        dst[(size_t)a * (size_t)nzs + (size_t)b] = src[((size_t)x0 + (size_t)a * (size_t)dec) * (size_t)pitch + col];
+}
+
 __global__ void fdw_selftest_kernel(const float* src, float* out)
 {
     const int t = threadIdx.x;
@@ -869,6 +884,13 @@ hipError_t launch_record_static(const float* p0, const float* pp0, float* rec, i
     if (nrows <= 0 || nsteps <= 0) return hipSuccess;
     hipLaunchKernelGGL(fdw_record_static_kernel, dim3((nrows * nsteps + 255) / 256, nbatch > 1 ? nbatch : 1), dim3(256), 0, s, p0, pp0, rec, pitch, row0, nrows,
                        gz, rec_x0, rec_n, nsteps, bstride, rec_bstride);
+    return hipGetLastError();
+}
+
+hipError_t launch_snapshot(const float* f, float* frame, int pitch, int x0, int z0, int dec, int nxs, int nzs, hipStream_t s)
+{
+    if (nxs <= 0 || nzs <= 0) return hipSuccess;
+    hipLaunchKernelGGL(fdw_snapshot_kernel, dim3((nzs + 255) / 256, nxs < 65535 ? nxs : 65535), dim3(256), 0, s, f, frame, pitch, x0, z0, dec, nxs, nzs);
     return hipGetLastError();
 }
 

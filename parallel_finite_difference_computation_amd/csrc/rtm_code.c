@@ -3,7 +3,7 @@
  * Same deck keys and defaults (R:343-378), same input binaries (vpfile [nx][nz], datfile
  * [ns][nx][nt], optional vel_ext_file [ns][nxe][nze]), same outputs: <tmpdir>/dir.image (stacked image
  * [nx][nz]), <tmpdir>/dir.image_lap (zeros, R:477,542), empty dir.snaps / dir.snaps_rec / dir.snapr
- * (R:465-470), ./image.num text dump (R:522-528), and the stdout banners.  The per-shot propagation
+ * (R:465-470; filled by the key `snap`, below), ./image.num text dump (R:522-528), and the stdout banners.  The per-shot propagation
  * (fd_forward + fd_back, R:499-518) is one device-resident fdw_shot() call; launch extents are the
  * reference's (compat = 1), so the image equals the reference's.  Shots run side by side on up to FDW_SHOT_WORKERS (default 4) host
  * threads / streams; models are drawn and images stacked in shot order, so every output is what the serial loop writes.
@@ -18,7 +18,16 @@
  * (fdw_shot_illum; per shot from zero, stacked on the host in shot order like the image) and adds two outputs, <tmpdir>/dir.illum (the
  * stack, [nx][nz]) and <tmpdir>/dir.image_illum = fdw_image_compensate(image, illumination, illum_eps), `illum_eps` defaulting to 1e-3.
  * dir.image, dir.image_lap and image.num are what they are without the key.  Small decks still advance a batch of shots through one
- * launch per time step (fdw_shot_batch_illum: one accumulator field per shot); together with slabs > 1 the key is refused. */
+ * launch per time step (fdw_shot_batch_illum: one accumulator field per shot); together with slabs > 1 the key is refused.
+ *
+ * Wavefield snapshots (the reference opens the three files, reads the deck key `iss` -- "save snaps of this source", R:368 -- and writes
+ * nothing): the deck key `snap=K` (absent, -1 or 0: the three files stay empty, every byte of every output as before) runs shot `iss`
+ * through fdw_shot_snaps and writes its frames at the time levels K, 2K, ... <= nt (fdwave.h): dir.snaps the forward field, dir.snaps_rec
+ * the source field the backward loop images at that level, dir.snapr the receiver field it is multiplied with -- each
+ * [nt / K][ceil(nx / D)][ceil(nz / D)] floats, D = `snap_dec` (default 1) the decimation along both axes.  On decks that batch their shots,
+ * shot `iss` leaves its batch and runs alone; among workers (and GPUs) the one that owns the shot takes the frames.  dir.image,
+ * dir.image_lap, image.num and dir.illum* stay byte for byte what they are without the key.  iss >= ns, snap_dec < 1 and snap > 0 together
+ * with slabs > 1 are refused before anything is opened. */
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -62,6 +71,8 @@ typedef struct {
     int dev_border;
     float *imloc_all;
     float *illoc_all;     /* illum=1: the shots' source illumination [nb][nx][nz], else NULL */
+    int snap_is;          /* snap=K: the shot whose wavefield frames are taken, else -1 */
+    const fdw_snaps *snaps;
     size_t ne, ni;
     int gpus;             /* workers are dealt to GPUs 0 .. gpus-1 */
     volatile int failed;
@@ -91,7 +102,12 @@ static void *shot_worker(void *p)
         float *imloc = j->imloc_all + (size_t)b * j->ni;
         float *illoc = j->illoc_all ? j->illoc_all + (size_t)b * j->ni : NULL;
         int rc;
-        if (j->dev_border) {
+        if (is == j->snap_is) {      /* the worker that owns shot iss takes its frames (illoc may be NULL) */
+            rc = j->dev_border ? fdw_dev_extendvel_linear(ctx, (unsigned long long)is * (unsigned long long)j->draws, NULL) : FDW_OK;
+            if (rc == FDW_OK)
+                rc = fdw_shot_snaps(ctx, j->dev_border ? NULL : j->vel2_all + (size_t)b * j->ne, j->sx[is], j->sz, j->gz, j->srce, d_obs, imloc, illoc,
+                                    NULL, NULL, j->snaps);
+        } else if (j->dev_border) {
             /* R:486-494 in HBM: shot `is` of the serial program consumes draws [is T, (is + 1) T) of the unseeded rand() stream */
             rc = fdw_dev_extendvel_linear(ctx, (unsigned long long)is * (unsigned long long)j->draws, NULL);
             if (rc == FDW_OK && illoc) rc = fdw_shot_resident_illum(ctx, j->sx[is], j->sz, j->gz, j->srce, d_obs, imloc, illoc, NULL, NULL);
@@ -222,7 +238,26 @@ int main(int argc, char **argv)
     if (nzb == -1) nzb = 40;
     if (nxb == -1) nxb = 40;
     if (fac == -1.0f) fac = 0.7f;
-    (void)iss;
+    /* our extension (absent, -1 or 0: nothing changes): wavefield frames of shot iss every `snap` time levels, decimated by `snap_dec`.
+     * Refused here, before any file, thread, communicator or device is touched */
+    const int snap = fdw_deck_int(deck, "snap") > 0 ? fdw_deck_int(deck, "snap") : 0;
+    const int snap_dec = fdw_deck_has(deck, "snap_dec") ? fdw_deck_int(deck, "snap_dec") : 1;
+    if (snap_dec < 1) {
+        fprintf(stderr, "snap_dec=%d: the decimation must be >= 1\n", snap_dec);
+        return EXIT_FAILURE;
+    }
+    if (snap > 0) {
+        int sl = fdw_deck_int(deck, "slabs");
+        if (getenv("FDW_SLABS")) sl = atoi(getenv("FDW_SLABS"));
+        if (sl > 1) {
+            fprintf(stderr, "snap=%d cannot be combined with slabs=%d: slab-decomposed shots take no wavefield snapshots\n", snap, sl);
+            return EXIT_FAILURE;
+        }
+        if (iss < 0 || iss >= ns) {
+            fprintf(stderr, "snap=%d: iss=%d is not one of the %d shots\n", snap, iss, ns);
+            return EXIT_FAILURE;
+        }
+    }
     /* our extension (absent or 0: nothing changes): source illumination and the compensated image.  Slab-decomposed shots do not
      * accumulate it: refused here, before any file, thread, communicator or device is touched */
     const int illum = fdw_deck_int(deck, "illum") == 1;
@@ -246,6 +281,12 @@ int main(int argc, char **argv)
     printf("## dz = %f, dx = %f, dt = %f \n", dz, dx, dt);
     printf("## ns = %d, sz = %d, fsx = %d, ds = %d, gz = %d \n", ns, sz, fsx, ds, gz);
     printf("## order = %d, nzb = %d, nxb = %d, F = %f, rnd = %d \n", order, nzb, nxb, fac, rnd);
+    int snap_nf = 0, snap_nxs = 0, snap_nzs = 0;
+    if (snap > 0) {
+        fdw_snap_dims(nx > 0 ? nx : 0, nz > 0 ? nz : 0, nt > 0 ? nt : 0, snap, snap_dec, &snap_nf, &snap_nxs, &snap_nzs);
+        printf("## snap = %d, snap_dec = %d, iss = %d: %d frames of %d x %d in dir.snaps, dir.snaps_rec, dir.snapr \n", snap, snap_dec, iss, snap_nf,
+               snap_nxs, snap_nzs);
+    }
     if (nz <= 0 || nx <= 0 || nt <= 0 || !tmpdir || !vpfile || !datfile) {
         fprintf(stderr, "input deck is missing one of tmpdir/vpfile/datfile/nz/nx/nt\n");
         return EXIT_FAILURE;
@@ -399,6 +440,28 @@ int main(int argc, char **argv)
     job.prm = &prm; job.ns = ns; job.nworkers = nworkers; job.sx = sx; job.sz = sz; job.gz = gz; job.srce = srce; job.d_obs = d_obs;
     job.nx = nx; job.nt = nt; job.ne = ne; job.ni = ni; job.vel2_all = vel2_all; job.imloc_all = imloc_all; job.illoc_all = illoc_all; job.failed = 0;
     job.vp = vp; job.draws = fdw_border_draws(nx, nz, nxb, nzb); job.dev_border = dev_border; job.gpus = gpus;
+    if (gpus > 1) {      /* more GPUs asked for than visible: the workers share the visible ones, as in rtm_model (the bytes do not depend on where a shot runs) */
+        const int ndev = fdw_device_count();
+        if (ndev >= 1 && gpus > ndev) {
+            fprintf(stderr, "gpus=%d: %d visible; the %d workers share %s\n", gpus, ndev, nworkers, ndev == 1 ? "it" : "them");
+            job.gpus = ndev;
+        }
+    }
+    /* snap=K: the three frame sets of shot iss, on the host until they are written */
+    const size_t snap_n = (size_t)snap_nf * snap_nxs * snap_nzs;
+    fdw_snaps sn;
+    memset(&sn, 0, sizeof sn);
+    sn.every = snap; sn.dec = snap_dec;
+    if (snap > 0) {
+        sn.snaps = (float *)calloc(snap_n ? snap_n : 1, sizeof(float));
+        sn.snaps_rec = (float *)calloc(snap_n ? snap_n : 1, sizeof(float));
+        sn.snapr = (float *)calloc(snap_n ? snap_n : 1, sizeof(float));
+        if (!sn.snaps || !sn.snaps_rec || !sn.snapr) {
+            fprintf(stderr, "out of host memory\n");
+            return EXIT_FAILURE;
+        }
+    }
+    job.snap_is = snap > 0 ? iss : -1; job.snaps = &sn;
 
     for (int is0 = 0; is0 < ns; is0 += batch) {
         const int nb = is0 + batch <= ns ? batch : ns - is0;
@@ -419,12 +482,26 @@ int main(int argc, char **argv)
         if (bctx) {
             /* shots is0 .. is0 + nb - 1: source rows sx[is0] + b ds (R:405-407), border models from draws [(is0 + b) T, ...) of the stream */
             /* models: drawn on the device, or the host-built ones of this batch (vel_ext_file decks, FDW_HOST_BORDER=1) */
-            const unsigned long long draw0 = (unsigned long long)is0 * (unsigned long long)job.draws;
-            const float *models = dev_border ? NULL : vel2_all, *gathers = d_obs + (size_t)is0 * nx * nt;
-            if ((illum ? fdw_shot_batch_illum(bctx, nb, models, draw0, sx[is0], ds, sz, gz, srce, gathers, imloc_all, illoc_all)
-                       : fdw_shot_batch(bctx, nb, models, draw0, sx[is0], ds, sz, gz, srce, gathers, imloc_all)) != FDW_OK) {
-                fprintf(stderr, "fdw_shot_batch: %s\n", fdw_last_error());
-                return EXIT_FAILURE;
+            /* snap=K: shot iss leaves the batch and runs alone through fdw_shot_snaps; the shots before and after it batch as they did */
+            for (int b0 = 0; b0 < nb;) {
+                const int isb = is0 + b0;
+                const int n = isb == job.snap_is ? 1 : (job.snap_is > isb && job.snap_is < is0 + nb ? job.snap_is - isb : nb - b0);
+                const unsigned long long draw0 = (unsigned long long)isb * (unsigned long long)job.draws;
+                const float *models = dev_border ? NULL : vel2_all + (size_t)b0 * ne, *gathers = d_obs + (size_t)isb * nx * nt;
+                float *im = imloc_all + (size_t)b0 * ni, *il = illum ? illoc_all + (size_t)b0 * ni : NULL;
+                int rc;
+                if (isb == job.snap_is) {
+                    rc = dev_border ? fdw_dev_extendvel_linear(bctx, draw0, NULL) : FDW_OK;
+                    if (rc == FDW_OK) rc = fdw_shot_snaps(bctx, models, sx[isb], sz, gz, srce, gathers, im, il, NULL, NULL, &sn);
+                } else {
+                    rc = illum ? fdw_shot_batch_illum(bctx, n, models, draw0, sx[isb], ds, sz, gz, srce, gathers, im, il)
+                               : fdw_shot_batch(bctx, n, models, draw0, sx[isb], ds, sz, gz, srce, gathers, im);
+                }
+                if (rc != FDW_OK) {
+                    fprintf(stderr, "fdw_shot_batch: %s\n", fdw_last_error());
+                    return EXIT_FAILURE;
+                }
+                b0 += n;
             }
         } else {
             const int nw = nb < nworkers ? nb : nworkers;
@@ -482,6 +559,13 @@ int main(int argc, char **argv)
         free(comp);
         free(illoc_all);
         free(ill);
+    }
+    if (snap > 0) {      /* dir.snaps, dir.snaps_rec, dir.snapr: shot iss, [frames][ceil(nx / D)][ceil(nz / D)] each */
+        if (!fsns || !fsns2 || !fsnr) return EXIT_FAILURE;
+        fwrite(sn.snaps, sizeof(float), snap_n, fsns);
+        fwrite(sn.snaps_rec, sizeof(float), snap_n, fsns2);
+        fwrite(sn.snapr, sizeof(float), snap_n, fsnr);
+        free(sn.snaps); free(sn.snaps_rec); free(sn.snapr);
     }
 outputs:
     if (timing)
