@@ -359,6 +359,46 @@ int fdw_shot_batch_illum(fdw_ctx *ctx, int nshots, const float *v2_all, unsigned
                          const float *srce, const float *d_obs, float *imloc, float *illum);
 int fdw_image_compensate(const float *img, const float *illum, size_t n, float eps, float *out);
 
+/* ---- residual migration: image d_obs minus the gather the forward loop itself models --------------------------------------------
+ * Definitions.  RTM dialect, full-grid contexts, EXACT and FAST numerics alike.
+ *   d_mod[ix][it]   what fdw_record_shot returns for the same context, model, source, sz and gz (the recording definition above), bit for bit:
+ *                   the recording kernels write it inside the forward loop the shot runs anyway.
+ *   resid[ix][it]   d_obs[ix][it] (-) d_mod[ix][it]: one fp32 subtraction, round to nearest even, subnormals kept, nothing fused.
+ *   sign            with d_obs from the true model and a reflector-free migration model the residual is the reflection data.
+ *   image           the one fdw_shot forms when handed `resid` as its d_obs, bit for bit; P and PP are fdw_shot's.  With an accumulator,
+ *                   illum is fdw_shot_illum's, bit for bit (the forward loop then records and accumulates in one launch per pass).
+ *   gz              must lie in [0, zlim) as for recording, else FDW_EINVAL before anything is enqueued.
+ *   consequence     a gather modelled by fdw_record_shot / rtm_model in the model it is migrated with gives a residual whose every word is
+ *                   0x00000000, and the image then equals its entry values.
+ *   misfit          0.5 * sum_i resid[i]^2 on the host: each square and the sum carried in double, the squares added one after the other in
+ *                   memory order (a defined, bit-checkable number; O(nx nt) per shot).
+ * The same difference is the data residual of full-waveform inversion: its migrated image is the gradient, and that image divided by the
+ * illumination the gradient with the pseudo-Hessian preconditioner.  No weighting or time differentiation is applied.
+ * Slab contexts and the sibling's dialects: FDW_ESTATE.
+ * fdw_dev_gather_residual     d_out[i] = d_a[i] (-) d_b[i] for i < n on device arrays, asynchronous on `stream`; d_out may be d_a.
+ * fdw_dev_record_illum_steps  fdw_dev_steps2 (same buffers and indices, bit-identical fields) that writes the trace rows of
+ *                             fdw_dev_record_steps AND accumulates as fdw_dev_illum_steps does, each pass one launch (orders above 8 and
+ *                             forced generic: the generic recording step followed by the add kernel; where fdw_dev_steps2 runs a pair of
+ *                             steps through the two-step kernel: two single steps that land in the same buffers).  The refusals of both; d_rec or
+ *                             d_illum NULL: FDW_EINVAL (the existing entry points are the ones to call).
+ * fdw_shot_residual           fdw_shot (v2 == NULL: on the resident squared model) whose forward loop records d_mod on the device, then
+ *                             d_obs (-) d_mod in place on the device, then the backward loop on the difference.  illum: NULL, or accumulated
+ *                             into as by fdw_shot_illum.  resid: NULL, or [nx][nt], the residual as the backward loop read it.
+ * fdw_shot_batch_residual     `nshots` of them as fdw_shot_batch takes shots and models: one launch per time step for the whole batch where
+ *                             fdw_shot_batch batches, one residual launch over the batch; the shots one by one otherwise -- the same bytes.
+ *                             imloc [nshots][nx][nz]; illum (NULL ok) [nshots][nx][nz]; resid (NULL ok) [nshots][nx][nt].  One more batch
+ *                             buffer of [nshots][nt][nx] floats (and, with illum, fdw_shot_batch_illum's accumulators); batches larger
+ *                             than the memory budget allows go through in parts.
+ * fdw_gather_misfit           *misfit = 0.5 * sum resid[i]^2 as defined above; pure host C.  n == 0: 0.0.  A NaN propagates. */
+int fdw_dev_gather_residual(fdw_ctx *ctx, const float *d_a, const float *d_b, float *d_out, size_t n, void *stream);
+int fdw_dev_record_illum_steps(fdw_ctx *ctx, float *const *d_buf, const float *d_v2, const float *d_srce, int sx, int sz, int gz, float *d_rec,
+                               float *d_illum, int it0, int nsteps, int first_pp_twice, int *ip, int *ipp, void *stream);
+int fdw_shot_residual(fdw_ctx *ctx, const float *v2, int sx, int sz, int gz, const float *srce, const float *d_obs, float *imloc, float *illum,
+                      float *resid, float *P, float *PP);
+int fdw_shot_batch_residual(fdw_ctx *ctx, int nshots, const float *v2_all, unsigned long long draw_offset, int sx0, int dsx, int sz, int gz,
+                            const float *srce, const float *d_obs, float *imloc, float *illum, float *resid);
+int fdw_gather_misfit(const float *resid, size_t n, double *misfit);
+
 /* ---- wavefield snapshots from both loops of a shot (rtm_code's dir.snaps, dir.snaps_rec, dir.snapr) --------------------------------
  * The reference opens the three files and leaves them empty (R:465-470; its deck key iss, "save snaps of this source", R:368, is read and
  * dropped).  Definitions, for the parameters every = K >= 1 and dec = D >= 1, RTM dialect, full-grid contexts, EXACT and FAST numerics alike:

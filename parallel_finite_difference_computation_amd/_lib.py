@@ -83,6 +83,11 @@ SIGNATURES = [
     ("fdw_shot_resident_illum", C.c_int, [vp, C.c_int, C.c_int, C.c_int, f32p, f32p, f32p, f32p, vp, vp]),
     ("fdw_shot_batch_illum", C.c_int, [vp, C.c_int, vp, C.c_ulonglong, C.c_int, C.c_int, C.c_int, C.c_int, f32p, f32p, f32p, f32p]),
     ("fdw_image_compensate", C.c_int, [vp, vp, C.c_size_t, C.c_float, vp]),
+    ("fdw_dev_gather_residual", C.c_int, [vp, vp, vp, vp, C.c_size_t, vp]),
+    ("fdw_dev_record_illum_steps", C.c_int, [vp, C.POINTER(vp), vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), vp]),
+    ("fdw_shot_residual", C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, f32p, f32p, f32p, vp, vp, vp, vp]),
+    ("fdw_shot_batch_residual", C.c_int, [vp, C.c_int, vp, C.c_ulonglong, C.c_int, C.c_int, C.c_int, C.c_int, f32p, f32p, f32p, vp, vp]),
+    ("fdw_gather_misfit", C.c_int, [vp, C.c_size_t, C.POINTER(C.c_double)]),
     ("fdw_snap_dims", C.c_int, [C.c_int] * 5 + [C.POINTER(C.c_int)] * 3),
     ("fdw_dev_snapshot", C.c_int, [vp, vp, C.c_int, vp, vp]),
     ("fdw_shot_snaps", C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, f32p, f32p, f32p, vp, vp, vp, C.POINTER(Snaps)]),

@@ -107,6 +107,15 @@ def image_compensate(img, illum, eps=1e-3):
     return out
 
 
+def gather_misfit(resid):
+    """0.5 * sum resid^2 of a data residual (fdwave.h, fdw_gather_misfit): each square and the sum carried in double, added one after the
+    other in memory order.  Host arithmetic."""
+    resid = np.ascontiguousarray(resid, np.float32)
+    m = C.c_double()
+    check(lib().fdw_gather_misfit(resid.ctypes.data if resid.size else None, resid.size, C.byref(m)))
+    return m.value
+
+
 def snap_dims(nx, nz, nt, every, dec=1):
     """fdw_snap_dims: (nframes, nxs, nzs) = (nt // every, ceil(nx / dec), ceil(nz / dec)); every < 1 or dec < 1 is refused.  No device."""
     a, b, c = C.c_int(), C.c_int(), C.c_int()
@@ -307,6 +316,42 @@ class FDWave:
                                    _f32(d_obs, (nshots, self.nx, self.nt)), imloc))
         return imloc
 
+    def shot_residual(self, v2, sx, sz, gz, srce, d_obs, imloc=None, want_resid=True, want_fields=False, want_illum=False, illum=None):
+        """Residual migration of one shot (fdwave.h, fdw_shot_residual): shot() (v2=None: shot_resident()) whose forward loop also models the
+        gather d_mod of the migration model at gz, and whose backward loop migrates d_obs - d_mod instead of d_obs.  Returns a dict: image,
+        and resid [nx][nt] / illum / P, PP as asked."""
+        shape = (self.nxe, self.nze)
+        out = {"image": np.zeros((self.nx, self.nz), np.float32) if imloc is None else np.array(imloc, np.float32, order="C")}
+        if want_resid:
+            out["resid"] = np.zeros((self.nx, self.nt), np.float32)
+        if want_fields:
+            out["P"], out["PP"] = np.zeros(shape, np.float32), np.zeros(shape, np.float32)
+        if want_illum:
+            out["illum"] = np.zeros((self.nx, self.nz), np.float32) if illum is None else np.array(_f32(illum, (self.nx, self.nz)), order="C")
+
+        def ptr(name):
+            return out[name].ctypes.data if name in out else None
+
+        check(lib().fdw_shot_residual(self._h, None if v2 is None else _f32(v2, shape).ctypes.data, sx, sz, gz, _f32(srce, (self.nt,)),
+                                      _f32(d_obs, (self.nx, self.nt)), out["image"], ptr("illum"), ptr("resid"), ptr("P"), ptr("PP")))
+        return out
+
+    def shot_batch_residual(self, nshots, sx0, dsx, sz, gz, srce, d_obs, v2_all=None, draw_offset=0, imloc=None, want_resid=True,
+                            want_illum=False, illum=None):
+        """`nshots` residual migrations, shots and models as shot_batch takes them (one launch per time step where shot_batch batches).
+        Returns a dict: image [nshots][nx][nz], and resid [nshots][nx][nt] / illum [nshots][nx][nz] as asked."""
+        out = {"image": np.zeros((nshots, self.nx, self.nz), np.float32) if imloc is None else np.array(imloc, np.float32, order="C")}
+        if want_resid:
+            out["resid"] = np.zeros((nshots, self.nx, self.nt), np.float32)
+        if want_illum:
+            shape = (nshots, self.nx, self.nz)
+            out["illum"] = np.zeros(shape, np.float32) if illum is None else np.array(_f32(illum, shape), order="C")
+        v2p = None if v2_all is None else _f32(v2_all, (nshots, self.nxe, self.nze)).ctypes.data
+        check(lib().fdw_shot_batch_residual(self._h, nshots, v2p, int(draw_offset), sx0, dsx, sz, gz, _f32(srce, (self.nt,)),
+                                            _f32(d_obs, (nshots, self.nx, self.nt)), out["image"],
+                                            out["illum"].ctypes.data if want_illum else None, out["resid"].ctypes.data if want_resid else None))
+        return out
+
     def record_shot(self, v2, sx, sz, gz, srce, want_fields=False):
         """fd_forward from rest (fd-code.cu:496-497, 259-267) recording the gather data[nx][nt]: data[ix][it] = d_pp(nxb + ix, gz) at the end
         of iteration it (fdwave.h, fdw_record_shot), the layout rtm_code's datfile holds per shot.  want_fields: also (P, PP) as forward()."""
@@ -426,6 +471,19 @@ class FDWave:
         a, b = C.c_int(ip), C.c_int(ipp)
         check(lib().fdw_dev_illum_steps(self._h, arr, d_v2, d_srce, sx, sz, d_illum, it0, nsteps, int(first_pp_twice), C.byref(a), C.byref(b), stream))
         return a.value, b.value
+
+    def dev_record_illum_steps(self, bufs, d_v2, d_srce, sx, sz, gz, d_rec, d_illum, it0, nsteps, first_pp_twice=False, ip=0, ipp=1, stream=None):
+        """dev_steps2 that writes the trace rows of dev_record_steps and accumulates as dev_illum_steps does, one launch per pass (fdwave.h).
+        Returns (ip, ipp) as dev_steps2 does."""
+        arr = (C.c_void_p * 4)(*bufs)
+        a, b = C.c_int(ip), C.c_int(ipp)
+        check(lib().fdw_dev_record_illum_steps(self._h, arr, d_v2, d_srce, sx, sz, gz, d_rec, d_illum, it0, nsteps, int(first_pp_twice), C.byref(a),
+                                               C.byref(b), stream))
+        return a.value, b.value
+
+    def dev_gather_residual(self, d_a, d_b, d_out, n, stream=None):
+        """d_out[i] = d_a[i] - d_b[i] for i < n on device arrays of floats (one fp32 subtraction each); d_out may be d_a."""
+        check(lib().fdw_dev_gather_residual(self._h, d_a, d_b, d_out, int(n), stream))
 
     def dev_taper_finalize(self, d_f, stream=None):
         check(lib().fdw_dev_taper_finalize(self._h, d_f, stream))

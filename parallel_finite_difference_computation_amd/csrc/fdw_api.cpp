@@ -90,6 +90,8 @@ struct fdw_ctx {
     float* b_illum = nullptr;    // the shots' source illuminations, [shots] fields (fdw_shot_batch_illum); allocated on first use
     int b_illum_cap = 0;         // ... shots it holds
     bool batch_illum = false;    // inside fdw_shot_batch_illum's forward loop: the one place a batched launch accumulates illumination
+    float* b_rec = nullptr;      // the shots' modelled gathers [shots][nt][nx] (fdw_shot_batch_residual); allocated on first use
+    size_t b_rec_cap = 0;
     float* d_raw = nullptr;      // gathers as the caller holds them ([shot][nx][nt]) before the transposition on the device
     size_t raw_cap = 0;
     int no_fused_back = 0;   // experiments / tests: backward iterations as two launches (source step, receiver step) -- FDW_NO_FUSED_BACK=1
@@ -347,7 +349,7 @@ extern "C" void fdw_destroy(fdw_ctx* c)
     float* bufs[] = {c->d_taperz, c->d_txfac, c->d_gcx, c->d_gcz, c->fld[0], c->fld[1], c->fld[2], c->fld[3],
                      c->fld[4], c->fld[5], c->fld[6], c->fld[7], c->fld[8], c->fld[9], c->d_v2, c->d_img, c->d_illum, c->d_srce, c->d_dobs, c->d_rec,
                      c->d_vp, c->d_vpe, (float*)c->d_draws, (float*)c->d_jump, c->bfld[0], c->bfld[1], c->bfld[2], c->bfld[3],
-                     c->bfld[4], c->bfld[5], c->bfld[6], c->bfld[7], c->b_v2, c->b_img, c->b_dobs, c->b_illum, c->d_raw, c->d_snap[0], c->d_snap[1], c->d_snap[2]};
+                     c->bfld[4], c->bfld[5], c->bfld[6], c->bfld[7], c->b_v2, c->b_img, c->b_dobs, c->b_illum, c->b_rec, c->d_raw, c->d_snap[0], c->d_snap[1], c->d_snap[2]};
     for (float* b : bufs)
         if (b) (void)hipFree(b);
     if (c->stream) (void)hipStreamDestroy(c->stream);
@@ -522,12 +524,13 @@ static int step_impl(fdw_ctx* c, int mode, const float* d_p, float* d_pp, const 
         FDW_TRY(place_receivers(c, "step", mode == FDW_MODE_DD_RECV ? c->prm.nzb : c->prm.nxb, inj_z, &in));
     if (mode == FDW_MODE_MOD) FDW_TRY(fill_mod(c, a, "step", d_rec_row, rec_z));
     // (a batch accumulates per shot, illum + shot * field, inside fdw_shot_batch_illum only)
-    if (d_illum && (mode != FDW_MODE_FWD || d_rec_row || (c->nbatch > 1 && !c->batch_illum)))
-        return fail(FDW_EINVAL, "step: illumination belongs to a plain forward step of one shot");
-    // the RTM forward step that records its trace row, or that accumulates the source illumination (the accumulator travels in `img`)
-    const int kmode = (mode == FDW_MODE_FWD && d_rec_row) ? FDW_MODE_FWD_REC : ((mode == FDW_MODE_FWD && d_illum) ? FDW_MODE_FWD_ILLUM : mode);
-    if (kmode == FDW_MODE_FWD_REC) fill_rec(c, a, d_rec_row, rec_z);
-    if (kmode == FDW_MODE_FWD_ILLUM) a.img = d_illum;
+    if (d_illum && (mode != FDW_MODE_FWD || (c->nbatch > 1 && !c->batch_illum)))
+        return fail(FDW_EINVAL, "step: illumination belongs to a forward step of one shot");
+    // the RTM forward step that records its trace row, that accumulates the source illumination (the accumulator travels in `img`), or both
+    const bool fwd = mode == FDW_MODE_FWD;
+    const int kmode = (fwd && d_rec_row && d_illum) ? FDW_MODE_FWD_REC_ILLUM : ((fwd && d_rec_row) ? FDW_MODE_FWD_REC : ((fwd && d_illum) ? FDW_MODE_FWD_ILLUM : mode));
+    if (kmode == FDW_MODE_FWD_REC || kmode == FDW_MODE_FWD_REC_ILLUM) fill_rec(c, a, d_rec_row, rec_z);
+    if (kmode == FDW_MODE_FWD_ILLUM || kmode == FDW_MODE_FWD_REC_ILLUM) a.img = d_illum;
     a.inj = d_inj + in.shift; a.inj_x = in.x; a.inj_z = inj_z; a.inj_n = in.n;
     if (a.r1 <= a.r0) return FDW_OK;
     if (c->nbatch > 1) {      // fdw_shot_batch: shot b = these pointers + b fields, its own gather, its own source row
@@ -546,8 +549,10 @@ static int step_impl(fdw_ctx* c, int mode, const float* d_p, float* d_pp, const 
     } else {
         if (mode >= FDW_MODE_MOD) return fail(FDW_EINVAL, "step: mode %d has no generic-order kernel", mode);
         // no generic-order illumination kernel: the plain step, then illum += pp (*) pp over the cells it updated
-        e = launch_step_generic(a, c->h, kmode == FDW_MODE_FWD_ILLUM ? FDW_MODE_FWD : kmode, s);
-        if (e == hipSuccess && kmode == FDW_MODE_FWD_ILLUM) e = launch_illum_add(d_pp, d_illum, c->pitch, a.r0, a.r1, c->upd_z1, s);
+        // (recording too: the generic recording step, then the same add)
+        const bool add = kmode == FDW_MODE_FWD_ILLUM || kmode == FDW_MODE_FWD_REC_ILLUM;
+        e = launch_step_generic(a, c->h, kmode == FDW_MODE_FWD_ILLUM ? FDW_MODE_FWD : (kmode == FDW_MODE_FWD_REC_ILLUM ? FDW_MODE_FWD_REC : kmode), s);
+        if (e == hipSuccess && add) e = launch_illum_add(d_pp, d_illum, c->pitch, a.r0, a.r1, c->upd_z1, s);
     }
     if (e != hipSuccess) return fail(FDW_EHIP, "kernel launch failed: %s", hipGetErrorString(e));
     if ((mode == FDW_MODE_RECV || mode == FDW_MODE_BACK) && r1 > c->upd_x1)
@@ -759,11 +764,12 @@ static int stepn_impl(fdw_ctx* c, int mode, const float* d_p, const float* d_pp,
         for (int i = 0; i < kPipeSteps; i++) a.plev[i] = bk->plev[i];
     }
     if (mode == FDW_MODE_MOD) FDW_TRY(fill_mod(c, a, "stepn", d_rec, rec_z));
-    if (d_illum && (mode != FDW_MODE_FWD || d_rec)) return fail(FDW_EINVAL, "stepn: illumination belongs to a plain forward pass");
-    // FWD with d_rec: the trace rows of the pass's four steps; with d_illum: their squares added to the illumination
-    const int kmode = (mode == FDW_MODE_FWD && d_rec) ? FDW_MODE_FWD_REC : ((mode == FDW_MODE_FWD && d_illum) ? FDW_MODE_FWD_ILLUM : mode);
-    if (kmode == FDW_MODE_FWD_REC) fill_rec(c, a, d_rec, rec_z);
-    if (kmode == FDW_MODE_FWD_ILLUM) a.img = d_illum;
+    if (d_illum && mode != FDW_MODE_FWD) return fail(FDW_EINVAL, "stepn: illumination belongs to a forward pass");
+    // FWD with d_rec: the trace rows of the pass's four steps; with d_illum: their squares added to the illumination; with both: both
+    const bool fwd = mode == FDW_MODE_FWD;
+    const int kmode = (fwd && d_rec && d_illum) ? FDW_MODE_FWD_REC_ILLUM : ((fwd && d_rec) ? FDW_MODE_FWD_REC : ((fwd && d_illum) ? FDW_MODE_FWD_ILLUM : mode));
+    if (kmode == FDW_MODE_FWD_REC || kmode == FDW_MODE_FWD_REC_ILLUM) fill_rec(c, a, d_rec, rec_z);
+    if (kmode == FDW_MODE_FWD_ILLUM || kmode == FDW_MODE_FWD_REC_ILLUM) a.img = d_illum;
     a.inj = d_inj + in.shift; a.inj_x = in.x; a.inj_z = inj_z; a.inj_n = in.n;
     const int ncells = c->pitch / 4, own = 64 - 2 * kPipeSteps;
     a.nstrip = (ncells + own - 1) / own;
@@ -871,7 +877,9 @@ extern "C" int fdw_dev_step4(fdw_ctx* c, const float* d_p, const float* d_pp, co
 // the two-step kernel, single steps through the one-step kernel, whichever pays.  On entry buf[*ip], buf[*ipp] are the reference's (d_p, d_pp)
 // BEFORE the first swap; on return they index (d_p, d_pp) after the loop.  d_rec: NULL, or the trace rows [it][nx] (fdw_dev_record_steps):
 // the same passes, each through its kernel's recording variant.  d_illum: NULL, or the source illumination (fdw_dev_illum_steps): the same
-// passes, each through its kernel's illumination variant (not together with d_rec).
+// passes, each through its kernel's illumination variant.  Both (fdw_dev_record_illum_steps): pipeline passes and single steps through the
+// combined kernels; there is no combined two-step kernel (a pair becomes two single steps), and every family equals the one-step iteration
+// bit for bit.
 // Trace samples of iterations it0 .. it0+nsteps-1 on the receiver rows the loop never time-steps (rows >= xlim of this slab): what the
 // reference's d_pp holds there, from the fields (d_p, d_pp) before the first swap
 static int record_static(fdw_ctx* c, const float* d_p, const float* d_pp, int gz, float* d_rec, int it0, int nsteps, hipStream_t s)
@@ -906,6 +914,20 @@ static int steps_loop(fdw_ctx* c, float* const* buf, const float* d_v2, const fl
                                 d_illum));
             *ip = o1; *ipp = o2;   // d_p = u^{n+kPipeSteps-1}, d_pp = u^{n+kPipeSteps}
             k += kPipeSteps;
+        } else if (nsteps - k >= 2 && two_step_pays(c) && d_rec && d_illum) {
+            // no combined two-step kernel: two single steps that land where the pair's pass would -- u^{n+1} in buf[o1], u^{n+2} in buf[o2],
+            // the current pair left as it is --, each on a copy of the field it overwrites; the same fields, indices and static rows
+            const size_t bytes = field_elems(c) * sizeof(float) * (size_t)std::max(c->nbatch, 1);
+            const float* newest = buf[*ipp];
+            for (int j = 0; j < 2; j++) {
+                float* dst = buf[j == 0 ? o1 : o2];
+                HIP_TRY(hipMemcpyAsync(dst, buf[j == 0 ? *ip : *ipp], bytes, hipMemcpyDeviceToDevice, s));
+                FDW_TRY(step_impl(c, FDW_MODE_FWD, newest, dst, d_v2, 0, c->nxl, twice || j > 0, inj ? inj + j : nullptr, sxx, sz, nullptr, nullptr, s,
+                                   rec + (size_t)j * nxs, gz, nullptr, nullptr, d_illum));
+                newest = dst;
+            }
+            *ip = o1; *ipp = o2;
+            k += 2;
         } else if (nsteps - k >= 2 && two_step_pays(c)) {
             // after the swap the kernel's p is the old d_pp (newest field), its pp the old d_p
             FDW_TRY(step2_impl(c, FDW_MODE_FWD, buf[*ipp], buf[*ip], d_v2, buf[o1], buf[o2], twice, inj, sxx, sz, Step2Extra{}, s, rec, gz, d_illum));
@@ -990,6 +1012,33 @@ extern "C" int fdw_dev_illum_steps(fdw_ctx* c, float* const* d_buf, const float*
     if (it0 < 0) return fail(FDW_EINVAL, "it0=%d", it0);
     FDW_TRY(check_illum_ctx(c, "fdw_dev_illum_steps"));
     return steps_loop(c, d_buf, d_v2, d_srce, sx, sz, 0, nullptr, it0, nsteps, first_pp_twice, ip, ipp, pick_stream(c, stream), d_illum);
+}
+
+// the forward loop that records and accumulates in one launch per pass (the forward loop of fdw_shot_residual with an accumulator)
+extern "C" int fdw_dev_record_illum_steps(fdw_ctx* c, float* const* d_buf, const float* d_v2, const float* d_srce, int sx, int sz, int gz, float* d_rec,
+                                          float* d_illum, int it0, int nsteps, int first_pp_twice, int* ip, int* ipp, void* stream)
+{
+    if (!c) return fail(FDW_EINVAL, "NULL argument");
+    if (!d_rec || !d_illum)
+        return fail(FDW_EINVAL, "fdw_dev_record_illum_steps needs both d_rec and d_illum (one alone: fdw_dev_record_steps / fdw_dev_illum_steps)");
+    if (it0 < 0) return fail(FDW_EINVAL, "it0=%d", it0);
+    FDW_TRY(check_illum_ctx(c, "fdw_dev_record_illum_steps"));
+    FDW_TRY(check_record_depth(c, gz));
+    return steps_loop(c, d_buf, d_v2, d_srce, sx, sz, gz, d_rec, it0, nsteps, first_pp_twice, ip, ipp, pick_stream(c, stream), d_illum);
+}
+
+// d_out[i] = d_a[i] - d_b[i] (fdw_gather_residual_kernel); d_out may be d_a
+static int gather_residual(const float* d_a, const float* d_b, float* d_out, size_t n, hipStream_t s)
+{
+    hipError_t e = launch_gather_residual(d_a, d_b, d_out, n, s);
+    if (e != hipSuccess) return fail(FDW_EHIP, "gather residual launch failed: %s", hipGetErrorString(e));
+    return FDW_OK;
+}
+
+extern "C" int fdw_dev_gather_residual(fdw_ctx* c, const float* d_a, const float* d_b, float* d_out, size_t n, void* stream)
+{
+    if (!c || (n > 0 && (!d_a || !d_b || !d_out))) return fail(FDW_EINVAL, "NULL argument");
+    return gather_residual(d_a, d_b, d_out, n, pick_stream(c, stream));
 }
 
 // ksteps-cycle of the slab decomposition in one call: step j (1-based, j = j0 .. j0+nsteps-1) updates the
@@ -1335,13 +1384,18 @@ extern "C" int fdw_back(fdw_ctx* c, const float* v2, const float* snap0, const f
     return FDW_OK;
 }
 
+static int gathers_to_host(fdw_ctx* c, const float* d_rec, int nshots, float* data);
+
 // v2 == nullptr: the squared model already resident in c->d_v2 (fdw_dev_extendvel_linear)
 // illum: NULL, or the interior illumination [nx][nz] the forward loop accumulates into (fdw_shot_illum)
 // sn: NULL, or the snapshot plan of fdw_shot_snaps (frame stores already allocated)
+// residual (fdw_shot_residual): the forward loop records the modelled gather into c->d_rec, c->d_dobs becomes d_obs - d_mod in place before the
+// backward loop reads it; resid: NULL, or [nx][nt] that difference
 static int shot_impl(fdw_ctx* c, const float* v2, int sx, int sz, int gz, const float* srce, const float* d_obs, float* imloc, float* P, float* PP,
-                     float* illum = nullptr, const SnapPlan* sn = nullptr)
+                     float* illum = nullptr, const SnapPlan* sn = nullptr, bool residual = false, float* resid = nullptr)
 {
     if (!c || !srce || !d_obs || !imloc) return fail(FDW_EINVAL, "NULL argument");
+    if (residual) FDW_TRY(check_record_depth(c, gz));
     FDW_RANGE("fdw: shot (uploads, forward, backward, image download)");
     if (!is_full_grid(c)) return fail(FDW_EINVAL, "fdw_shot needs a full-grid context");
     if (c->nx <= 0 || c->nz <= 0) return fail(FDW_EINVAL, "no interior to image");
@@ -1356,7 +1410,12 @@ static int shot_impl(fdw_ctx* c, const float* v2, int sx, int sz, int gz, const 
         (rc = image_to_device(c, imloc)))
         return rc;
     if (illum && ((rc = alloc_zero(&c->d_illum, field_elems(c))) || (rc = image_to_device(c, illum, c->d_illum)))) return rc;
-    if ((rc = forward_loop(c, &ip, &ipp, sx, sz, nt, 0, nullptr, illum ? c->d_illum : nullptr, sn))) return rc;
+    if (residual && (rc = ensure_cap(&c->d_rec, &c->rec_cap, (size_t)c->nx * nt))) return rc;
+    if ((rc = forward_loop(c, &ip, &ipp, sx, sz, nt, residual ? gz : 0, residual ? c->d_rec : nullptr, illum ? c->d_illum : nullptr, sn))) return rc;
+    if (residual) {      // both [nt][nx] in forward time: the backward loop's sample indexing stays as it is
+        if ((rc = gather_residual(c->d_dobs, c->d_rec, c->d_dobs, (size_t)c->nx * nt, c->stream))) return rc;
+        if (resid && (rc = gathers_to_host(c, c->d_dobs, 1, resid))) return rc;
+    }
     if (illum && (rc = image_to_host(c, illum, c->d_illum))) return rc;
     if (P && (rc = download_rows(c, P, c->fld[ip], c->stream))) return rc;
     if (PP && (rc = download_rows(c, PP, c->fld[ipp], c->stream))) return rc;
@@ -2081,6 +2140,25 @@ extern "C" int fdw_shot_resident_illum(fdw_ctx* c, int sx, int sz, int gz, const
     return shot_impl(c, nullptr, sx, sz, gz, srce, d_obs, imloc, P, PP, illum);
 }
 
+// ---- residual migration (definitions in fdwave.h) ----
+static int check_residual_ctx(const fdw_ctx* c, const char* who)
+{
+    if (c->prm.dialect != FDW_DIALECT_RTM) return fail(FDW_ESTATE, "%s: residual migration belongs to the RTM dialect", who);
+    if (!is_full_grid(c)) return fail(FDW_ESTATE, "%s: residual migration needs a full-grid context (slab-decomposed shots are not covered)", who);
+    if (c->nbatch > 1) return fail(FDW_ESTATE, "%s: not inside a batch of shots", who);
+    return FDW_OK;
+}
+
+extern "C" int fdw_shot_residual(fdw_ctx* c, const float* v2, int sx, int sz, int gz, const float* srce, const float* d_obs, float* imloc, float* illum,
+                                 float* resid, float* P, float* PP)
+{
+    if (!c) return fail(FDW_EINVAL, "ctx is NULL");
+    FDW_TRY(check_residual_ctx(c, "fdw_shot_residual"));
+    if (!v2 && !c->v2_resident) return fail(FDW_ESTATE, "no resident squared model: call fdw_dev_extendvel_linear first");
+    if (v2) c->v2_resident = false;
+    return shot_impl(c, v2, sx, sz, gz, srce, d_obs, imloc, P, PP, illum, nullptr, true, resid);
+}
+
 // ------------------------------------------------------------------------------------------------
 // a batch of shots through ONE launch per time step
 // ------------------------------------------------------------------------------------------------
@@ -2222,8 +2300,10 @@ static int batch_interiors_to_host(fdw_ctx* c, float* h_dst, const float* d_src,
 }
 
 // fdw_shot_batch (illum == NULL) and fdw_shot_batch_illum: illum [nshots][nx][nz] is accumulated into per shot by the forward loop
+// residual (fdw_shot_batch_residual): the forward loop records every shot's modelled gather into b_rec [shot][nt][nx], one launch turns the
+// batch's gathers into d_obs - d_mod in place before the backward loop; resid: NULL, or [nshots][nx][nt] that difference
 static int shot_batch_impl(fdw_ctx* c, const char* who, int nshots, const float* v2_all, unsigned long long draw_offset, int sx0, int dsx, int sz, int gz,
-                           const float* srce, const float* d_obs, float* imloc, float* illum)
+                           const float* srce, const float* d_obs, float* imloc, float* illum, bool residual = false, float* resid = nullptr)
 {
     if (!c || !srce || !d_obs || !imloc) return fail(FDW_EINVAL, "NULL argument");
     if (nshots < 1) return fail(FDW_EINVAL, "nshots=%d", nshots);
@@ -2241,7 +2321,7 @@ static int shot_batch_impl(fdw_ctx* c, const char* who, int nshots, const float*
         for (int b = 0; b < nshots; b++) {
             if (!v2_all) FDW_TRY(fdw_dev_extendvel_linear(c, draw_offset + (unsigned long long)b * draws, nullptr));
             FDW_TRY(shot_impl(c, v2_all ? v2_all + b * ne : nullptr, sx0 + b * dsx, sz, gz, srce, d_obs + b * ng, imloc + b * ni, nullptr, nullptr,
-                              illum ? illum + b * ni : nullptr));
+                              illum ? illum + b * ni : nullptr, nullptr, residual, resid ? resid + b * ng : nullptr));
         }
         return (int)FDW_OK;
     };
@@ -2250,6 +2330,7 @@ static int shot_batch_impl(fdw_ctx* c, const char* who, int nshots, const float*
     if ((rc = ensure_work_buffers(c, 8, true))) return rc;
     if ((rc = ensure_batch_buffers(c, nshots, true)) == FDW_ENOMEM) return one_by_one();      // no room for the batch
     if (!rc && illum && (rc = ensure_batch_illum(c, nshots)) == FDW_ENOMEM) return one_by_one();      // ... or for its accumulators
+    if (!rc && residual && (rc = ensure_cap(&c->b_rec, &c->b_rec_cap, ng * nshots)) == FDW_ENOMEM) return one_by_one();      // ... or its modelled gathers
     if (rc || (rc = upload_source(c, srce, nt))) return rc;
     hipStream_t s = c->stream;
     if ((rc = gathers_to_device(c, d_obs, c->b_dobs, nshots))) return rc;      // [shot][nx][nt] -> [shot][nt][nx]
@@ -2260,13 +2341,17 @@ static int shot_batch_impl(fdw_ctx* c, const char* who, int nshots, const float*
     {
         BatchScope scope(c, nshots, dsx, illum != nullptr);
         int ip = 0, ipp = 1;
-        if ((rc = steps_loop(c, c->fld, c->d_v2, c->d_srce, sx0, sz, 0, nullptr, 0, nt, 0, &ip, &ipp, s, illum ? c->b_illum : nullptr))) return rc;
+        if ((rc = steps_loop(c, c->fld, c->d_v2, c->d_srce, sx0, sz, residual ? gz : 0, residual ? c->b_rec : nullptr, 0, nt, 0, &ip, &ipp, s,
+                             illum ? c->b_illum : nullptr)))
+            return rc;
+        if (residual && (rc = gather_residual(c->d_dobs, c->b_rec, c->d_dobs, ng * nshots, s))) return rc;      // d_dobs: the batch's [shot][nt][nx]
         for (int b = 0; b < nshots && nt > 0; b++)
             if ((rc = fdw_dev_taper_finalize(c, c->fld[ip] + b * fe, s))) return rc;
         float* src[4];
         source_buffers(c, ip, ipp, src);
         if ((rc = back_loop(c, src, c->fld + 4, gz, nt))) return rc;
     }
+    if (resid && (rc = gathers_to_host(c, c->b_dobs, nshots, resid))) return rc;
     if (illum && (rc = batch_interiors_to_host(c, illum, c->b_illum, nshots))) return rc;
     if ((rc = batch_interiors_to_host(c, imloc, c->b_img, nshots))) return rc;
     HIP_TRY(hipStreamSynchronize(s));
@@ -2296,6 +2381,29 @@ extern "C" int fdw_shot_batch_illum(fdw_ctx* c, int nshots, const float* v2_all,
         const int nb = std::min(part, nshots - b0);
         FDW_TRY(shot_batch_impl(c, "fdw_shot_batch_illum", nb, v2_all ? v2_all + b0 * ne : nullptr, draw_offset + b0 * draws, sx0 + b0 * dsx, dsx, sz, gz,
                                 srce, d_obs ? d_obs + b0 * ng : nullptr, imloc ? imloc + b0 * ni : nullptr, illum + b0 * ni));
+    }
+    return FDW_OK;
+}
+
+// fdw_shot_batch whose forward loop also records every shot's modelled gather (and, with illum, accumulates its illumination in the same
+// launch), migrating d_obs - d_mod.  The batch holds the modelled gathers and, with illum, one field more per shot than fdw_shot_batch_max
+// counts: a batch larger than the same budget allows goes through in parts -- independent, the bytes the same.
+extern "C" int fdw_shot_batch_residual(fdw_ctx* c, int nshots, const float* v2_all, unsigned long long draw_offset, int sx0, int dsx, int sz, int gz,
+                                       const float* srce, const float* d_obs, float* imloc, float* illum, float* resid)
+{
+    if (!c) return fail(FDW_EINVAL, "ctx is NULL");
+    FDW_TRY(check_residual_ctx(c, "fdw_shot_batch_residual"));
+    FDW_TRY(check_record_depth(c, gz));
+    if (nshots < 1) return fail(FDW_EINVAL, "nshots=%d", nshots);
+    const size_t ni = (size_t)c->nx * c->nz, ne = (size_t)c->prm.nxe * c->prm.nze, ng = (size_t)c->nx * c->prm.nt;
+    const long by_mem = (long)(((size_t)6 << 30) / (((illum ? 12 : 11) * field_elems(c) + ng) * sizeof(float)));
+    const int part = (int)std::max<long>(1, std::min<long>(by_mem, nshots));
+    const unsigned long long draws = (unsigned long long)fdw_border_draws(c->nx, c->nz, c->prm.nxb, c->prm.nzb);
+    for (int b0 = 0; b0 < nshots; b0 += part) {
+        const int nb = std::min(part, nshots - b0);
+        FDW_TRY(shot_batch_impl(c, "fdw_shot_batch_residual", nb, v2_all ? v2_all + b0 * ne : nullptr, draw_offset + b0 * draws, sx0 + b0 * dsx, dsx, sz,
+                                gz, srce, d_obs ? d_obs + b0 * ng : nullptr, imloc ? imloc + b0 * ni : nullptr, illum ? illum + b0 * ni : nullptr, true,
+                                resid ? resid + b0 * ng : nullptr));
     }
     return FDW_OK;
 }

@@ -11,6 +11,7 @@
 //     coordinates (the phases below), so the fill is one thread per cell with no ordering between cells.
 #include <hip/hip_runtime.h>
 
+#include <cstdint>
 #include <type_traits>
 
 #include "fdw_kernels.h"
@@ -137,7 +138,37 @@ __global__ __launch_bounds__(256) void fdw_gather_transpose_kernel(const float* 
         if (c0 + j < cols && r0 + tx < rows) out[shot + (size_t)(c0 + j) * rows + r0 + tx] = tile[tx][j];
 }
 
+// The data residual of a migrated gather (fdw_shot_residual): out[i] = a[i] - b[i], one fp32 subtraction each (round to nearest even,
+// subnormals kept: the file is built with -ffp-contract=off and the kernel has no other arithmetic).  `out` may alias `a` (no __restrict__):
+// every element is read before it is written, by the thread that writes it.  16-byte pieces where all three arrays are 16-byte aligned,
+// single floats for the tail and for arrays that are not; size_t indices, so [nshots][nt][nx] of any size goes through one launch.
+__global__ __launch_bounds__(256) void fdw_gather_residual_kernel(const float* a, const float* b, float* out, size_t n, int vec)
+{
+    const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x, stride = (size_t)gridDim.x * 256;
+    const size_t n4 = vec ? n / 4 : 0;
+    const float4* a4 = reinterpret_cast<const float4*>(a);
+    const float4* b4 = reinterpret_cast<const float4*>(b);
+    float4* o4 = reinterpret_cast<float4*>(out);
+    for (size_t i = t; i < n4; i += stride) {
+        const float4 x = a4[i], y = b4[i];
+        float4 r;
+        r.x = x.x - y.x; r.y = x.y - y.y; r.z = x.z - y.z; r.w = x.w - y.w;
+        o4[i] = r;
+    }
+    for (size_t i = n4 * 4 + t; i < n; i += stride) out[i] = a[i] - b[i];
+}
+
 }  // namespace
+
+hipError_t launch_gather_residual(const float* d_a, const float* d_b, float* d_out, size_t n, hipStream_t s)
+{
+    if (n == 0) return hipSuccess;
+    const int vec = (((uintptr_t)d_a | (uintptr_t)d_b | (uintptr_t)d_out) & 15u) == 0;
+    const size_t work = vec ? n / 4 + 3 : n;      // threads that find something to do
+    const size_t blocks = (work + 255) / 256;
+    hipLaunchKernelGGL(fdw_gather_residual_kernel, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(256), 0, s, d_a, d_b, d_out, n, vec);
+    return hipGetLastError();
+}
 
 hipError_t launch_gather_transpose(const float* d_in, float* d_out, int nx, int nt, int nshots, hipStream_t s)
 {

@@ -203,6 +203,19 @@ int fdw_image_compensate(const float *img, const float *illum, size_t n, float e
     return FDW_OK;
 }
 
+/* ---- misfit of a data residual (fdwave.h): 0.5 * sum resid^2, each square and the sum in double, added in memory order -------------- */
+int fdw_gather_misfit(const float *resid, size_t n, double *misfit)
+{
+    if (!misfit || (!resid && n > 0)) return FDW_EINVAL;
+    double sum = 0.0;
+    for (size_t i = 0; i < n; i++) {
+        const double r = (double)resid[i];
+        sum = sum + r * r;
+    }
+    *misfit = 0.5 * sum;
+    return FDW_OK;
+}
+
 /* ---- forward-modelling producer of the CPU-serial sibling (DD = dpct_gpu_rtm_domain_division/src) --------------------
  * DD builds its .c files with g++ (every Makefile there sets CC = g++ -fpermissive), so exp(float) is the float overload. */
 

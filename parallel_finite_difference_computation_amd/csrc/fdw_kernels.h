@@ -16,6 +16,7 @@ enum {
     FDW_MODE_PLAIN_ALL = 8, // wave-pipeline kernel only: PLAIN with all four time levels stored (source field of the backward loop)
     FDW_MODE_FWD_REC = 10, // launchers only: FWD + the trace sample of every step on the receiver line (fdw_dev_record_steps; StepArgs / Step2Args rec*)
     FDW_MODE_FWD_ILLUM = 11, // launchers only: FWD + the source illumination, illum += new field (*) new field over the update extents (fdw_dev_illum_steps; the accumulator travels in `img`)
+    FDW_MODE_FWD_REC_ILLUM = 12, // launchers only: FWD + the trace samples + the source illumination in one launch (fdw_dev_record_illum_steps, fdw_shot_residual)
     FDW_MODE_DD_RECV = 6 // its receiver pass (rtm_main.cpp:197-220) + img += stored source field * CURRENT receiver field (rtm_main.cpp:224-230)
 };
 
@@ -161,5 +162,7 @@ hipError_t launch_rand_stream(const RandBase& base, const unsigned* d_tab, long 
 hipError_t launch_extendvel(const BorderArgs& a, hipStream_t s);
 // d_in [nshots][nx][nt] -> d_out [nshots][nt][nx]
 hipError_t launch_gather_transpose(const float* d_in, float* d_out, int nx, int nt, int nshots, hipStream_t s);
+// d_out[i] = d_a[i] - d_b[i] for i < n, one fp32 subtraction each; d_out may be d_a (fdw_gather_residual_kernel)
+hipError_t launch_gather_residual(const float* d_a, const float* d_b, float* d_out, size_t n, hipStream_t s);
 
 }  // namespace fdw

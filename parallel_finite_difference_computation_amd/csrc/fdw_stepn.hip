@@ -57,7 +57,7 @@ __device__ __forceinline__ void marchn(const Step2Args& a, const int lane, const
     static_assert(!LEAN || (!TAPER && INJ == 0), "the lean body has no damping, no injection (and records no trace)");
     constexpr bool IMG = (BK == 2 || BK == 4);
     constexpr bool ACC = IMG || ILL;                          // a row of an accumulator (image, illumination) rides along
-    static_assert(!ILL || (BK == 0 && !DD && !REC), "illumination belongs to the RTM dialect's plain forward pass");
+    static_assert(!ILL || (BK == 0 && !DD), "illumination belongs to the RTM dialect's forward pass");
     constexpr int D = (BK == 4) ? 1 : 0;                      // this role runs D march steps behind
     constexpr int DL = (BK >= 3) ? 1 : 0;                     // ... so both roles of the fused kernel loop one step longer
     // one march step per workgroup barrier (two measured slower: DESIGN.md section 3c): a wave consumes what its predecessor produced
@@ -454,6 +454,37 @@ __global__ __launch_bounds__(64 * kPipeSteps, 3) void fdw_stepn_illum_kernel(con
     else marchn<H, NS, true, 1, PF, false, 0, false, 0, NUM, false, true>(a, lane, k, cs, xa, xe, link, fifo, ilf);
 }
 
+// FDW_MODE_FWD_REC_ILLUM: the forward pass that records the trace samples of its kPipeSteps steps AND accumulates their source illumination
+// (the forward loop of fdw_shot_residual with an accumulator).  Every tile carries the accumulator row through the 16-slot LDS FIFO as in
+// fdw_stepn_illum_kernel (48 KiB of LDS, three workgroups per CU, the square taken before the hand-over); the tiles whose owned lanes hold the
+// receiver column run the full body, in which wave k also records row k of the pass as in fdw_stepn_rec_kernel; all others run
+// fdw_stepn_illum_kernel's bodies, lean where the tile allows.  Its own tile placement (see fdw_stepn_rec_kernel).
+template <int NUM>
+__global__ __launch_bounds__(64 * kPipeSteps, 3) void fdw_stepn_rec_illum_kernel(const Step2Args a)
+{
+    constexpr int H = 4, NS = kPipeSteps, PF = kPipePF;
+    const int lane = threadIdx.x & 63;
+    const int k = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int bid = blockIdx.x;
+    const int L = (bid & 7) * a.nper + (bid >> 3);
+    if (L >= a.nblk) return;
+    const int zb = L % a.nstrip;
+    const int xb = L / a.nstrip;
+    const bool second = xb >= a.chunks_a;
+    const int xa = second ? a.r0b + (xb - a.chunks_a) * a.xchunk : a.r0 + xb * a.xchunk;
+    const int xe = min(xa + a.xchunk, second ? a.r1b : a.r1);
+    if (xa >= xe) return;
+    __shared__ f4 link[NS][2][2][64];
+    __shared__ f4 fifo[pipe_fifo_rows(NS, H)][64];
+    __shared__ f4 ilf[16][64];
+    const int cs = zb * (64 - 2 * NS) - NS;
+    if (pipe_lean<H, NS, true, 1, false, true>(a, cs, xa, xe)) {
+        if (k == 0) marchn<H, NS, false, 0, PF, false, 0, true, 1, NUM, false, true>(a, lane, k, cs, xa, xe, link, fifo, ilf);
+        else marchn<H, NS, false, 0, PF, false, 0, true, 2, NUM, false, true>(a, lane, k, cs, xa, xe, link, fifo, ilf);
+    }
+    else marchn<H, NS, true, 1, PF, false, 0, false, 0, NUM, true, true>(a, lane, k, cs, xa, xe, link, fifo, ilf);
+}
+
 // Four iterations of the backward loop in ONE pass: a workgroup of eight waves, waves 0-3 the pipeline of the source field (role 3), waves 4-7
 // the pipeline of the receiver field one march step behind (role 4).  The source-field levels never leave the chip: the receiver wave of
 // level k reads F_{it+k}(row) from the link buffer the source-field wave k wrote it to for its own successor.  6 fields in + 5 out per
@@ -506,6 +537,7 @@ hipError_t launch_stepn(const Step2Args& a, int h, int mode, hipStream_t s)
         case FDW_MODE_FWD:   hipLaunchKernelGGL((fdw_stepn_kernel<4, kPipeSteps, true, 1, kPipePF, false, 0, 1>), grid, block, 0, s, a); break;
         case FDW_MODE_FWD_REC: hipLaunchKernelGGL((fdw_stepn_rec_kernel<1>), grid, block, 0, s, a); break;
         case FDW_MODE_FWD_ILLUM: hipLaunchKernelGGL((fdw_stepn_illum_kernel<1>), grid, block, 0, s, a); break;
+        case FDW_MODE_FWD_REC_ILLUM: hipLaunchKernelGGL((fdw_stepn_rec_illum_kernel<1>), grid, block, 0, s, a); break;
         case FDW_MODE_PLAIN: hipLaunchKernelGGL((fdw_stepn_kernel<4, kPipeSteps, false, 0, kPipePF, false, 0, 1>), grid, block, 0, s, a); break;
         case FDW_MODE_MOD:   hipLaunchKernelGGL((fdw_stepn_kernel<4, kPipeSteps, true, 3, kPipePF, true, 0, 1>), grid, block, 0, s, a); break;
         case FDW_MODE_PLAIN_ALL: hipLaunchKernelGGL((fdw_stepn_kernel<4, kPipeSteps, false, 0, kPipePF, false, 1, 1>), grid, block, 0, s, a); break;
@@ -519,6 +551,7 @@ hipError_t launch_stepn(const Step2Args& a, int h, int mode, hipStream_t s)
     case FDW_MODE_FWD:   hipLaunchKernelGGL((fdw_stepn_kernel<4, kPipeSteps, true, 1, kPipePF>), grid, block, 0, s, a); break;
     case FDW_MODE_FWD_REC: hipLaunchKernelGGL((fdw_stepn_rec_kernel<0>), grid, block, 0, s, a); break;
     case FDW_MODE_FWD_ILLUM: hipLaunchKernelGGL((fdw_stepn_illum_kernel<0>), grid, block, 0, s, a); break;
+    case FDW_MODE_FWD_REC_ILLUM: hipLaunchKernelGGL((fdw_stepn_rec_illum_kernel<0>), grid, block, 0, s, a); break;
     case FDW_MODE_PLAIN: hipLaunchKernelGGL((fdw_stepn_kernel<4, kPipeSteps, false, 0, kPipePF>), grid, block, 0, s, a); break;
     case FDW_MODE_MOD:   hipLaunchKernelGGL((fdw_stepn_kernel<4, kPipeSteps, true, 3, kPipePF, true>), grid, block, 0, s, a); break;
     case FDW_MODE_PLAIN_ALL: hipLaunchKernelGGL((fdw_stepn_kernel<4, kPipeSteps, false, 0, kPipePF, false, 1>), grid, block, 0, s, a); break;

@@ -27,7 +27,16 @@
  * [nt / K][ceil(nx / D)][ceil(nz / D)] floats, D = `snap_dec` (default 1) the decimation along both axes.  On decks that batch their shots,
  * shot `iss` leaves its batch and runs alone; among workers (and GPUs) the one that owns the shot takes the frames.  dir.image,
  * dir.image_lap, image.num and dir.illum* stay byte for byte what they are without the key.  iss >= ns, snap_dec < 1 and snap > 0 together
- * with slabs > 1 are refused before anything is opened. */
+ * with slabs > 1 are refused before anything is opened.
+ *
+ * Residual migration (no counterpart in the reference): the deck key `resid=1` (absent or 0: the same files and the same bytes as without
+ * it) sends every shot through fdw_shot_residual / fdw_shot_batch_residual: the forward loop models the shot's gather in the migration
+ * model, and the backward loop migrates datfile's gather minus that one (fdwave.h) -- the direct arrival leaves the data on the device, and
+ * the image is the gradient of the least-squares misfit.  Shots batch where the program batches, `gpus=N` workers take their own shots,
+ * the host stacks in shot order as always.  With `illum=1` too, dir.illum and dir.image_illum are written as before and now describe the
+ * residual image.  Two more outputs: <tmpdir>/dir.resid ([ns][nx][nt] floats, the layout of datfile, each shot at its offset) and
+ * <tmpdir>/dir.misfit (ns doubles, 0.5 sum resid^2 per shot, fdw_gather_misfit); the total is printed after the shots.  resid=1 together
+ * with slabs > 1 or with snap > 0 is refused before anything is opened. */
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -71,6 +80,8 @@ typedef struct {
     int dev_border;
     float *imloc_all;
     float *illoc_all;     /* illum=1: the shots' source illumination [nb][nx][nz], else NULL */
+    int resid;            /* resid=1: every shot through fdw_shot_residual */
+    float *resloc_all;    /* ... the shots' residual gathers [nb][nx][nt] */
     int snap_is;          /* snap=K: the shot whose wavefield frames are taken, else -1 */
     const fdw_snaps *snaps;
     size_t ne, ni;
@@ -102,7 +113,12 @@ static void *shot_worker(void *p)
         float *imloc = j->imloc_all + (size_t)b * j->ni;
         float *illoc = j->illoc_all ? j->illoc_all + (size_t)b * j->ni : NULL;
         int rc;
-        if (is == j->snap_is) {      /* the worker that owns shot iss takes its frames (illoc may be NULL) */
+        if (j->resid) {              /* d_obs minus the gather the forward loop models (illoc may be NULL; never together with snap) */
+            rc = j->dev_border ? fdw_dev_extendvel_linear(ctx, (unsigned long long)is * (unsigned long long)j->draws, NULL) : FDW_OK;
+            if (rc == FDW_OK)
+                rc = fdw_shot_residual(ctx, j->dev_border ? NULL : j->vel2_all + (size_t)b * j->ne, j->sx[is], j->sz, j->gz, j->srce, d_obs, imloc, illoc,
+                                       j->resloc_all + (size_t)b * j->nx * j->nt, NULL, NULL);
+        } else if (is == j->snap_is) {      /* the worker that owns shot iss takes its frames (illoc may be NULL) */
             rc = j->dev_border ? fdw_dev_extendvel_linear(ctx, (unsigned long long)is * (unsigned long long)j->draws, NULL) : FDW_OK;
             if (rc == FDW_OK)
                 rc = fdw_shot_snaps(ctx, j->dev_border ? NULL : j->vel2_all + (size_t)b * j->ne, j->sx[is], j->sz, j->gz, j->srce, d_obs, imloc, illoc,
@@ -276,6 +292,22 @@ int main(int argc, char **argv)
         }
     }
 
+    /* our extension (absent or 0: nothing changes): residual migration.  Slab-decomposed shots and the snapshot path do not cover it:
+     * refused here, before any file, thread, communicator or device is touched */
+    const int resid = fdw_deck_int(deck, "resid") == 1;
+    if (resid) {
+        int sl = fdw_deck_int(deck, "slabs");
+        if (getenv("FDW_SLABS")) sl = atoi(getenv("FDW_SLABS"));
+        if (sl > 1) {
+            fprintf(stderr, "resid=1 cannot be combined with slabs=%d: slab-decomposed shots do not migrate data residuals\n", sl);
+            return EXIT_FAILURE;
+        }
+        if (snap > 0) {
+            fprintf(stderr, "resid=1 cannot be combined with snap=%d: the snapshot shot does not migrate a data residual\n", snap);
+            return EXIT_FAILURE;
+        }
+    }
+
     printf("## vp = %s, d_obs = %s, vel_ext_file = %s, vel_ext_flag = %d \n", vpfile, datfile, vel_ext_file, vel_ext_flag);
     printf("## nz = %d, nx = %d, nt = %d \n", nz, nx, nt);
     printf("## dz = %f, dx = %f, dt = %f \n", dz, dx, dt);
@@ -287,6 +319,7 @@ int main(int argc, char **argv)
         printf("## snap = %d, snap_dec = %d, iss = %d: %d frames of %d x %d in dir.snaps, dir.snaps_rec, dir.snapr \n", snap, snap_dec, iss, snap_nf,
                snap_nxs, snap_nzs);
     }
+    if (resid) printf("## resid = 1: every shot migrates d_obs minus the gather modelled in the migration model; dir.resid, dir.misfit \n");
     if (nz <= 0 || nx <= 0 || nt <= 0 || !tmpdir || !vpfile || !datfile) {
         fprintf(stderr, "input deck is missing one of tmpdir/vpfile/datfile/nz/nx/nt\n");
         return EXIT_FAILURE;
@@ -329,6 +362,9 @@ int main(int argc, char **argv)
     FILE *fimg = open_out(tmpdir, "dir.image"), *fimg_lap = open_out(tmpdir, "dir.image_lap"); /* R:464-474 */
     FILE *fnum = fopen("image.num", "w");                                                       /* R:478-479 */
     if (!fimg || !fimg_lap || !fnum) return EXIT_FAILURE;
+    FILE *fres = resid ? open_out(tmpdir, "dir.resid") : NULL, *fmis = resid ? open_out(tmpdir, "dir.misfit") : NULL;
+    double *misfit = resid ? (double *)calloc((size_t)ns, sizeof(double)) : NULL;
+    if (resid && (!fres || !fmis || !misfit)) return EXIT_FAILURE;
 
     /* Shots are independent (R:480-529 only couples them through the running image sum), and a shot of a deck this size fills a
      * few percent of an MI355X: up to FDW_SHOT_WORKERS (default 4) host threads, each with its own context and stream, propagate
@@ -432,13 +468,16 @@ int main(int argc, char **argv)
     if (bctx) shots_per_launch = bmax;
     float *vel2_all = (float *)malloc((size_t)batch * ne * sizeof(float)), *imloc_all = (float *)calloc((size_t)batch * ni, sizeof(float));
     float *illoc_all = illum ? (float *)calloc((size_t)batch * ni, sizeof(float)) : NULL, *ill = illum ? (float *)calloc(ni, sizeof(float)) : NULL;
-    if (!vel2_all || !imloc_all || (illum && (!illoc_all || !ill))) {
+    const size_t ng = (size_t)nx * nt;
+    float *resloc_all = resid ? (float *)calloc((size_t)batch * ng, sizeof(float)) : NULL;
+    if (!vel2_all || !imloc_all || (illum && (!illoc_all || !ill)) || (resid && !resloc_all)) {
         fprintf(stderr, "out of host memory\n");
         return EXIT_FAILURE;
     }
     shot_job job;
     job.prm = &prm; job.ns = ns; job.nworkers = nworkers; job.sx = sx; job.sz = sz; job.gz = gz; job.srce = srce; job.d_obs = d_obs;
     job.nx = nx; job.nt = nt; job.ne = ne; job.ni = ni; job.vel2_all = vel2_all; job.imloc_all = imloc_all; job.illoc_all = illoc_all; job.failed = 0;
+    job.resid = resid; job.resloc_all = resloc_all;
     job.vp = vp; job.draws = fdw_border_draws(nx, nz, nxb, nzb); job.dev_border = dev_border; job.gpus = gpus;
     if (gpus > 1) {      /* more GPUs asked for than visible: the workers share the visible ones, as in rtm_model (the bytes do not depend on where a shot runs) */
         const int ndev = fdw_device_count();
@@ -490,7 +529,9 @@ int main(int argc, char **argv)
                 const float *models = dev_border ? NULL : vel2_all + (size_t)b0 * ne, *gathers = d_obs + (size_t)isb * nx * nt;
                 float *im = imloc_all + (size_t)b0 * ni, *il = illum ? illoc_all + (size_t)b0 * ni : NULL;
                 int rc;
-                if (isb == job.snap_is) {
+                if (resid) {
+                    rc = fdw_shot_batch_residual(bctx, n, models, draw0, sx[isb], ds, sz, gz, srce, gathers, im, il, resloc_all + (size_t)b0 * ng);
+                } else if (isb == job.snap_is) {
                     rc = dev_border ? fdw_dev_extendvel_linear(bctx, draw0, NULL) : FDW_OK;
                     if (rc == FDW_OK) rc = fdw_shot_snaps(bctx, models, sx[isb], sz, gz, srce, gathers, im, il, NULL, NULL, &sn);
                 } else {
@@ -533,6 +574,13 @@ int main(int argc, char **argv)
                     img[(size_t)ix * nz + iz] += imloc[(size_t)ix * nz + iz];
                     fprintf(fnum, " %f \n", img[(size_t)ix * nz + iz]);
                 }
+            if (resid) {                             /* dir.resid in shot order: every shot at its offset; its misfit */
+                const float *resloc = resloc_all + (size_t)b * ng;
+                if (fwrite(resloc, sizeof(float), ng, fres) != ng || fdw_gather_misfit(resloc, ng, &misfit[is]) != FDW_OK) {
+                    fprintf(stderr, "cannot write dir.resid\n");
+                    return EXIT_FAILURE;
+                }
+            }
             if (illum) {                             /* stacked like the image, in shot order: independent of the number of workers */
                 const float *illoc = illoc_all + (size_t)b * ni;
                 for (int iz = 0; iz < nz; iz++)
@@ -560,6 +608,16 @@ int main(int argc, char **argv)
         free(illoc_all);
         free(ill);
     }
+    if (resid) {      /* dir.misfit: ns doubles; the total added in shot order */
+        double total = 0.0;
+        for (int is = 0; is < ns; is++) total = total + misfit[is];
+        fwrite(misfit, sizeof(double), (size_t)ns, fmis);
+        fclose(fres);
+        fclose(fmis);
+        printf("## misfit = %.9e (0.5 sum resid^2 over %d shots) \n", total, ns);
+        free(misfit);
+        free(resloc_all);
+    }
     if (snap > 0) {      /* dir.snaps, dir.snaps_rec, dir.snapr: shot iss, [frames][ceil(nx / D)][ceil(nz / D)] each */
         if (!fsns || !fsns2 || !fsnr) return EXIT_FAILURE;
         fwrite(sn.snaps, sizeof(float), snap_n, fsns);
@@ -570,7 +628,8 @@ int main(int argc, char **argv)
 outputs:
     if (timing)
         fprintf(stderr, "[timing] shots per launch sequence: up to %d (%s)\n", shots_per_launch,
-                shots_per_launch > 1 ? (illum ? "fdw_shot_batch_illum" : "fdw_shot_batch") : "one by one");
+                shots_per_launch > 1 ? (resid ? "fdw_shot_batch_residual" : (illum ? "fdw_shot_batch_illum" : "fdw_shot_batch"))
+                                     : (resid ? "one by one, fdw_shot_residual" : "one by one"));
     if (timing)
         fprintf(stderr, "[timing] total %.3f s: shots (contexts, border models, propagation) %.3f s, stacking + image.num %.3f s, rest (deck, inputs) %.3f s\n",
                 now_s() - t_begin, t_shots, t_stack, now_s() - t_begin - t_shots - t_stack);

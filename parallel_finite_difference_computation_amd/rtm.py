@@ -46,11 +46,13 @@ def read_deck(path):
         d = dict(tmpdir=s("tmpdir"), vpfile=s("vpfile"), datfile=s("datfile"), vel_ext_file=s("vel_ext_file"),
                  nz=i("nz"), nx=i("nx"), nt=i("nt"), ns=i("ns"), sz=i("sz"), fsx=i("fsx"), ds=i("ds"), gz=i("gz"),
                  order=i("order"), nzb=i("nzb"), nxb=i("nxb"), dz=f("dz"), dx=f("dx"), dt=f("dt"), fpeak=f("fpeak"), fac=f("fac"),
-                 numerics=i("numerics"), illum=i("illum"), snap=i("snap"))
+                 numerics=i("numerics"), illum=i("illum"), snap=i("snap"), resid=i("resid"))
     finally:
         L.fdw_deck_free(h)
     if d["illum"] == 1:      # rtm_code's key: this driver would silently write neither dir.illum nor dir.image_illum
         raise ValueError("the deck sets illum=1: the shot-parallel Python driver does not accumulate the source illumination; run bin/rtm_code")
+    if d["resid"] == 1:      # rtm_code's key: this driver would silently migrate the gathers as they are and write neither dir.resid nor dir.misfit
+        raise ValueError("the deck sets resid=1: the shot-parallel Python driver does not migrate data residuals; run bin/rtm_code")
     if d["snap"] > 0:       # rtm_code's key: this driver would silently leave dir.snaps, dir.snaps_rec and dir.snapr empty
         raise ValueError(f"the deck sets snap={d['snap']}: the shot-parallel Python driver takes no wavefield snapshots; run bin/rtm_code")
     for key, default in (("ns", 1), ("sz", 0), ("fsx", 0), ("ds", 1), ("gz", 0), ("order", 8), ("nzb", 40), ("nxb", 40)):
