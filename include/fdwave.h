@@ -541,6 +541,13 @@ int fdw_slabs_set_stub(fdw_slabs *s, int on);
 int fdw_set_tuning(fdw_ctx *ctx, int xchunk, int wz, int use_generic, int prefetch, int two_step);
 int fdw_get_tables(const fdw_ctx *ctx, float *coefs_x, float *coefs_z, float *taper_x, float *taper_z);
 int fdw_get_extents(const fdw_ctx *ctx, int *xlim, int *zlim, int *ztap);
+/* Tests and probes (nothing is launched).
+ * fdw_debug_step4_plan  what fdw_dev_step4 would launch on these row ranges (forward = 1: FWD with the source at (sx, sz), sx < 0 none;
+ *                       0: the PLAIN pass): tiles, strips and, for tile L = chunk row * nstrip + strip, cls[L] = 0 if it runs the lean body
+ *                       (no masks, clamps, damping or source code), 1 if the full body; at most cls_cap entries are written (cls may be NULL).
+ */
+int fdw_debug_step4_plan(fdw_ctx *ctx, int forward, int sx, int sz, int r0, int r1, int r0b, int r1b, int xchunk, int *nblk, int *nstrip,
+                         unsigned char *cls, int cls_cap);
 int fdw_two_step_active(const fdw_ctx *ctx); /* 1 if the forward loops of this context use the two-step kernel */
 int fdw_steps_per_pass(const fdw_ctx *ctx);  /* time steps one launch of the forward loops advances: 4 (wave pipeline), 2 or 1 */
 int fdw_selftest(fdw_ctx *ctx);

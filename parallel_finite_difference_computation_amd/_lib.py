@@ -129,6 +129,7 @@ SIGNATURES = [
     ("fdw_set_tuning", C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     ("fdw_get_tables", C.c_int, [vp, vp, vp, vp, vp]),
     ("fdw_get_extents", C.c_int, [vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    ("fdw_debug_step4_plan", C.c_int, [vp] + [C.c_int] * 8 + [C.POINTER(C.c_int)] * 2 + [vp, C.c_int]),
     ("fdw_two_step_active", C.c_int, [vp]),
     ("fdw_steps_per_pass", C.c_int, [vp]),
     ("fdw_selftest", C.c_int, [vp]),

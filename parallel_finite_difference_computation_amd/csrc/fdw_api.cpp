@@ -713,6 +713,29 @@ struct StepnBack {      // the passes of the backward loop (Step2Args: lvl0, lvl
 struct RowRanges {      // rows the pass produces: [r0, r1) and optionally [r0b, r1b); r1 < 0 = all rows the reference time-steps
     int r0 = 0, r1 = -1, r0b = 0, r1b = 0, xchunk = 0;
 };
+// cls[L] of every tile of a FWD / PLAIN launch of fdw_stepn_kernel, in the tile order L = chunk row * nstrip + strip: 0 = it runs the lean body,
+// 1 = the full body, by the predicate the kernel picks the body with (pipe_tile_lean, fdw_kernels.h)
+static void tile_classes(const Step2Args& a, int kmode, std::vector<unsigned char>& cls)
+{
+    constexpr int H = kMaxFastHalfOrder, NS = kPipeSteps;
+    cls.resize((size_t)a.nblk);
+    for (int L = 0; L < a.nblk; L++) {
+        const int zb = L % a.nstrip, xb = L / a.nstrip;
+        const bool second = xb >= a.chunks_a;
+        const int xa = second ? a.r0b + (xb - a.chunks_a) * a.xchunk : a.r0 + xb * a.xchunk;
+        const int xe = std::min(xa + a.xchunk, second ? a.r1b : a.r1);
+        const int cs = zb * (64 - 2 * NS) - NS;
+        const bool lean = kmode == FDW_MODE_PLAIN ? pipe_tile_lean<H, NS, false, 0>(a, cs, xa, xe) : pipe_tile_lean<H, NS, true, 1>(a, cs, xa, xe);
+        cls[(size_t)L] = lean ? 0 : 1;
+    }
+}
+
+struct StepnPlan {
+    int nblk = 0, nstrip = 0;
+    std::vector<unsigned char> cls;
+};
+static thread_local StepnPlan* g_plan = nullptr;
+
 static int stepn_impl(fdw_ctx* c, int mode, const float* d_p, const float* d_pp, const float* d_v2, float* d_out1, float* d_out2, int pp_twice,
                       const float* d_inj, int inj_x_global, int inj_z, hipStream_t s, const RowRanges& rr = RowRanges{}, float* d_rec = nullptr,
                       int rec_z = 0, const StepnBack* bk = nullptr, float* d_illum = nullptr)
@@ -800,6 +823,11 @@ static int stepn_impl(fdw_ctx* c, int mode, const float* d_p, const float* d_pp,
     const int chunks = a.chunks_a + (rows_b + xchunk - 1) / xchunk;
     a.nblk = a.nstrip * chunks;
     a.nper = (a.nblk + 7) / 8;
+    if (g_plan) {      // fdw_debug_step4_plan: the tiles of this launch and which of them run the lean body; nothing launched
+        g_plan->nblk = a.nblk; g_plan->nstrip = a.nstrip;
+        tile_classes(a, kmode, g_plan->cls);
+        return FDW_OK;
+    }
     hipError_t e = launch_stepn(a, c->h, kmode, s);
     if (e != hipSuccess) return fail(FDW_EHIP, "stepn launch failed: %s", hipGetErrorString(e));
     static_assert(kPipeSteps % 2 == 0, "static-row bookkeeping assumes an even number of steps per pass");
@@ -871,6 +899,27 @@ extern "C" int fdw_dev_step4(fdw_ctx* c, const float* d_p, const float* d_pp, co
     RowRanges rr;
     rr.r0 = r0; rr.r1 = r1; rr.r0b = r0b; rr.r1b = r1b; rr.xchunk = xchunk;
     return stepn_impl(c, FDW_MODE_FWD, d_p, d_pp, d_v2, d_out1, d_out2, pp_twice, d_srce_it, d_srce_it ? sx : -1, sz, pick_stream(c, stream), rr);
+}
+
+// Tests and probes: what fdw_dev_step4 (forward = 1: FWD with the source at (sx, sz), sx < 0 none; 0: PLAIN) would launch on these row ranges --
+// tiles, strips and, per tile of the order L = chunk row * nstrip + strip, its class (0 lean, 1 full).  Launches nothing.
+extern "C" int fdw_debug_step4_plan(fdw_ctx* c, int forward, int sx, int sz, int r0, int r1, int r0b, int r1b, int xchunk, int* nblk, int* nstrip,
+                                    unsigned char* cls, int cls_cap)
+{
+    if (!c || !nblk || !nstrip) return fail(FDW_EINVAL, "NULL argument");
+    if (c->h != kMaxFastHalfOrder) return fail(FDW_EINVAL, "step4: needs order 8");
+    RowRanges rr;
+    rr.r0 = r0; rr.r1 = r1; rr.r0b = r0b; rr.r1b = r1b; rr.xchunk = xchunk;
+    StepnPlan plan;
+    float* const fake = reinterpret_cast<float*>(uintptr_t(1) << 20);      // never dereferenced: the plan hook returns before the launch
+    g_plan = &plan;
+    const int rc = stepn_impl(c, forward ? FDW_MODE_FWD : FDW_MODE_PLAIN, fake, fake + 1, fake + 2, fake + 3, fake + 4, 1, forward && sx >= 0 ? fake + 5 : nullptr,
+                              forward ? sx : -1, sz, nullptr, rr);
+    g_plan = nullptr;
+    if (rc != FDW_OK) return rc;
+    *nblk = plan.nblk; *nstrip = plan.nstrip;
+    if (cls) std::copy(plan.cls.begin(), plan.cls.begin() + std::min<size_t>(plan.cls.size(), (size_t)std::max(cls_cap, 0)), cls);
+    return FDW_OK;
 }
 
 // nsteps reference iterations (R:259-267) over four rotating buffers: kPipeSteps per pass through the wave pipeline, pairs of steps through

@@ -121,6 +121,28 @@ hipError_t launch_step2(const Step2Args& a, int half_order, int mode, hipStream_
 constexpr int kPipeSteps = 4;
 hipError_t launch_stepn(const Step2Args& a, int half_order, int mode, hipStream_t s);
 
+// May a tile (strip of cells from cs, rows [xa, xe)) of a pipeline pass run the lean body?  Every row it touches -- stencil taps, look-ahead
+// loads (PF + ring rows beyond the chunk) -- lies inside the rows where the Laplacian and the update are unmasked, its columns likewise, it is
+// outside the damped strip, and neither a source nor (modelling, REC) the receiver line is in it.  By the template values of the instantiation
+// that runs the tile; stated once for the kernels (workgroup-uniform, fdw_stepn.hip) and the host (fdw_debug_step4_plan: tile counts).
+template <int H, int NS, bool TAPER, int INJ, bool DD = false, bool REC = false>
+__host__ __device__ __forceinline__ bool pipe_tile_lean(const Step2Args& a, int cs, int xa, int xe)
+{
+    const int lo = xa - (NS - 1) * H - H - NS * (H + 1), hi = xe + (NS - 1) * (2 * H + 1) + 2 * H + 16;
+    const int c0 = cs * 4, c1 = cs * 4 + 256;
+    bool ok = (c0 >= a.lap_z0) && (c1 <= min(a.lap_z1, a.upd_z1)) && (lo >= max(a.lap_x0, 0)) && (hi <= min(min(a.lap_x1, a.upd_x1), a.nxl));
+    if (TAPER) {
+        ok = ok && (c0 >= a.zt_lo);
+        if (a.zt_hi >= 0) ok = ok && (c1 <= a.zt_hi) && (lo >= a.xt_lo) && (hi <= a.xt_hi);      // four-sided damping (taper_apply)
+    }
+    if (INJ == 3) ok = ok && !((a.inj_z + 3 >= c0) && (a.inj_z - 3 < c1) && (a.inj_x + 3 >= xa - NS * H) && (a.inj_x - 3 < xe + NS * H));
+    if (INJ == 2) ok = ok && !((a.inj_z >= c0) && (a.inj_z < c1) && (a.inj_x < xe + NS * H) && (a.inj_x + a.inj_n > xa - NS * H));
+    if (INJ == 1) ok = ok && !((a.inj_z >= c0) && (a.inj_z < c1) && (a.inj_x >= xa - NS * H) && (a.inj_x < xe + NS * H));
+    if (DD) ok = ok && !((a.rec != nullptr) && (a.rec_z >= c0) && (a.rec_z < c1));                  // trace recording
+    if (REC) ok = ok && !((a.rec_z >= c0 + 4 * NS) && (a.rec_z < c1 - 4 * NS));                      // ... the strip whose owned lanes record it
+    return ok;
+}
+
 hipError_t launch_step_fast(const StepArgs& a, int half_order, int mode, int prefetch, hipStream_t s);
 hipError_t launch_step_generic(const StepArgs& a, int half_order, int mode, hipStream_t s);
 hipError_t launch_taper_finalize(float* f, const float* taperz, const float* txfac, int pitch, int nxl, int ztap,

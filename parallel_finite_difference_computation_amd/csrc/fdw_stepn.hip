@@ -43,7 +43,7 @@ __device__ __forceinline__ int pipe_fifo_slot(int m)
 // written to the link buffers during the step before; v2 for all four waves from the FIFO; image as in BK 2)
 // LEAN: the body for workgroups that touch neither the frame of the grid (no Laplacian / update masks, no row clamps), nor the damped strip,
 // nor the source (instantiate with TAPER = false, INJ = 0): the kernel picks it per workgroup (pipe_lean)
-// WK: 0 = the wave finds out at run time whether it is wave 0 (full body); 1 / 2 = compiled for wave 0 / for the other waves (lean body)
+// WK: 0 = the wave finds out at run time whether it is wave 0; 1 / 2 = compiled for wave 0 / for the other waves (both bodies of the forward kernel)
 // NUM: 0 = the reference's exact arithmetic, 1 = FAST numerics (symmetric sums + fused multiply-adds, fdw_device.h)
 // REC: forward loop with trace recording (FDW_MODE_FWD_REC): wave k records its new row u^{n+k+1} at column rec_z into rec + k rec_n, from owned
 // lanes and the tile's own rows [xa, xe) only (the conditions of the field stores), so every sample is written once
@@ -331,25 +331,11 @@ __device__ __forceinline__ void marchn(const Step2Args& a, const int lane, const
         static_for<R>([&](auto UU) { row_step(mb, UU); });
 }
 
-// Workgroup-uniform: may this tile run the lean body?  Every row it touches -- stencil taps, look-ahead loads (PF + ring rows beyond the
-// chunk) -- lies inside the rows where the Laplacian and the update are unmasked, its columns likewise, it is outside the damped strip, and
-// neither a source nor (modelling, REC) the receiver line is in it.
+// Workgroup-uniform: may this tile run the lean body?  (pipe_tile_lean, fdw_kernels.h: the host counts the tiles by the same predicate)
 template <int H, int NS, bool TAPER, int INJ, bool DD = false, bool REC = false>
 __device__ __forceinline__ bool pipe_lean(const Step2Args& a, int cs, int xa, int xe)
 {
-    const int lo = xa - (NS - 1) * H - H - NS * (H + 1), hi = xe + (NS - 1) * (2 * H + 1) + 2 * H + 16;
-    const int c0 = cs * 4, c1 = cs * 4 + 256;
-    bool ok = (c0 >= a.lap_z0) && (c1 <= min(a.lap_z1, a.upd_z1)) && (lo >= max(a.lap_x0, 0)) && (hi <= min(min(a.lap_x1, a.upd_x1), a.nxl));
-    if (TAPER) {
-        ok = ok && (c0 >= a.zt_lo);
-        if (a.zt_hi >= 0) ok = ok && (c1 <= a.zt_hi) && (lo >= a.xt_lo) && (hi <= a.xt_hi);      // four-sided damping (taper_apply)
-    }
-    if (INJ == 3) ok = ok && !((a.inj_z + 3 >= c0) && (a.inj_z - 3 < c1) && (a.inj_x + 3 >= xa - NS * H) && (a.inj_x - 3 < xe + NS * H));
-    if (INJ == 2) ok = ok && !((a.inj_z >= c0) && (a.inj_z < c1) && (a.inj_x < xe + NS * H) && (a.inj_x + a.inj_n > xa - NS * H));
-    if (INJ == 1) ok = ok && !((a.inj_z >= c0) && (a.inj_z < c1) && (a.inj_x >= xa - NS * H) && (a.inj_x < xe + NS * H));
-    if (DD) ok = ok && !((a.rec != nullptr) && (a.rec_z >= c0) && (a.rec_z < c1));                  // trace recording
-    if (REC) ok = ok && !((a.rec_z >= c0 + 4 * NS) && (a.rec_z < c1 - 4 * NS));                      // ... the strip whose owned lanes record it
-    return ok;
+    return pipe_tile_lean<H, NS, TAPER, INJ, DD, REC>(a, cs, xa, xe);
 }
 
 // workgroups per CU the launch bounds hold the kernels to: 5 x 4 waves = 96 VGPRs (forward, source field); 4 for the modelling dialect;
@@ -389,7 +375,13 @@ __global__ __launch_bounds__(64 * NS, BK == 2 ? 3 : (DD ? kDDWG : kPipeWG)) void
                 marchn<H, NS, false, 0, PF, DD, 0, true, 0, NUM>(a, lane, k, cs, xa, xe, link, fifo);
             }
         }
-        else marchn<H, NS, TAPER, INJ, PF, DD, BK, false, 0, NUM>(a, lane, k, cs, xa, xe, link, fifo);
+        // ... and so is the full body of the others (not the modelling dialect): no selects between "from memory" and "from LDS", no switched-off
+        // look-ahead loads with their waits in waves 1 .. NS-1
+        else if constexpr (DD) marchn<H, NS, TAPER, INJ, PF, DD, BK, false, 0, NUM>(a, lane, k, cs, xa, xe, link, fifo);
+        else {
+            if (k == 0) marchn<H, NS, TAPER, INJ, PF, false, 0, false, 1, NUM>(a, lane, k, cs, xa, xe, link, fifo);
+            else marchn<H, NS, TAPER, INJ, PF, false, 0, false, 2, NUM>(a, lane, k, cs, xa, xe, link, fifo);
+        }
     } else {
         marchn<H, NS, TAPER, INJ, PF, DD, BK, false, 0, NUM>(a, lane, k, zb * (64 - 2 * NS) - NS, xa, xe, link, fifo);
     }
