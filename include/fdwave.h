@@ -526,6 +526,44 @@ int fdw_slabs_dev_back(fdw_slabs *s, float *const *f, float *const *r, const flo
 int fdw_slabs_shot(fdw_slabs *s, const float *v2, int sx, int sz, int gz, const float *srce, const float *d_obs, float *imloc, float *P, float *PP);
 int fdw_slabs_set_stub(fdw_slabs *s, int on);
 
+/* ---- line sources in the forward loop: plane-wave and encoded-shot migration -------------------------
+ * The RTM dialect on full-grid contexts, EXACT and FAST numerics alike.  Slab contexts, the sibling's dialects and a context inside a
+ * batch of shots return FDW_ESTATE.
+ *
+ * Line source.  nsrc = min(nx, xlim - nxb): the interior rows the loop time-steps (fdw_get_extents).  Iteration it of fd_forward's loop
+ * (R:259-267) runs unchanged except that kernel_src (R:267) is replaced: for ix = 0 .. nsrc-1, d_pp[nxb+ix][sz] = d_pp[nxb+ix][sz] (+) w[it][ix],
+ * one fp32 add per row applied after the leap-frog, exactly as kernel_sism (R:124-131) adds its samples.  Samples of rows ix >= nsrc are
+ * ignored: the line ends before the rows the reference never time-steps (a point source there is refused, a full-width line is not).
+ * sz outside [0, zlim): FDW_EINVAL before anything is enqueued.  Recording, illumination, P / PP and the backward loop keep their
+ * definitions: the recorded and the squared value is the stored new field, line samples included; the backward loop is fd_back as it
+ * stands and reconstructs the source field from (P, PP) without a source (R:317-318), as it does for a point source.  Recording and
+ * illumination together are not built for a line source: both pointers non-NULL is FDW_EINVAL.
+ *
+ * fdw_dev_line_steps    fdw_dev_steps2 / fdw_dev_record_steps / fdw_dev_illum_steps driven by the line: d_wav [>= it0+nsteps][nx] on the
+ *                       device (row it = the samples of iteration it), d_rec (NULL ok) the trace rows [it][nx] at gz, d_illum (NULL ok) the
+ *                       accumulator [nxl][pitch].  The same kernel family per pass, buffer rotation and static-row recording.
+ * fdw_shot_line         fdw_shot (v2 == NULL: fdw_shot_resident) whose forward loop is driven by wav[nx][nt] (the gather layout: wav[ix][it])
+ *                       at depth sz; illum (NULL ok) as fdw_shot_illum.
+ * fdw_record_shot_line  fdw_record_shot driven by wav[nx][nt].
+ * fdw_debug_step4_plan_line  fdw_debug_step4_plan for a four-step pass of fdw_dev_line_steps (plain) with the line at depth sz.
+ *
+ * Encoding.  All arithmetic fp32, round to nearest, nothing fused; sums run in ascending shot order from +0.0f.
+ * fdw_planewave_lags      in double, l_s = lround(p * (src_ix[s] - src_ix[0]) * dx / dt); lag[s] = l_s - min l_s >= 0.  p: ray parameter, s/m.
+ * fdw_encode_line_source  wav[nx][nt] starts at zero; for s ascending and it >= lag[s]: wav[src_ix[s]][it] (+)= weight[s] (*) srce[it - lag[s]].
+ *                         A src_ix outside [0, nx) or a negative lag: FDW_EINVAL.  Pure host C.
+ * fdw_encode_gathers      out[ix][it] = the fold, over the s with 0 <= it - lag[s] < nt, of acc (+) weight[s] (*) d_obs_all[s][ix][it - lag[s]];
+ *                         runs on `device` (fdw_encode_gathers_kernel). */
+int fdw_dev_line_steps(fdw_ctx *ctx, float *const *d_buf /* [4] */, const float *d_v2, const float *d_wav, int sz, int gz, float *d_rec,
+                       float *d_illum, int it0, int nsteps, int first_pp_twice, int *ip, int *ipp, void *stream);
+int fdw_shot_line(fdw_ctx *ctx, const float *v2, int sz, int gz, const float *wav, const float *d_obs, float *imloc, float *illum, float *P,
+                  float *PP);
+int fdw_record_shot_line(fdw_ctx *ctx, const float *v2, int sz, int gz, const float *wav, float *data, float *P, float *PP);
+int fdw_debug_step4_plan_line(fdw_ctx *ctx, int sz, int r0, int r1, int r0b, int r1b, int xchunk, int *nblk, int *nstrip, unsigned char *cls,
+                              int cls_cap);
+int fdw_planewave_lags(int nshots, const int *src_ix, float dx, float dt, double p, int *lag);
+int fdw_encode_line_source(int nshots, const int *src_ix, const int *lag, const float *weight, const float *srce, int nt, int nx, float *wav);
+int fdw_encode_gathers(int device, int nshots, const int *lag, const float *weight, const float *d_obs_all, int nx, int nt, float *out);
+
 /* ---- tuning / introspection --------------------------------------------------------------------
  * fdw_set_tuning  xchunk = rows marched per wave (0 = auto), wz = waves of a block laid along z
  *                 (1,2,4; 0 = auto), use_generic = force the generic-order kernel (tests),

@@ -130,6 +130,13 @@ SIGNATURES = [
     ("fdw_get_tables", C.c_int, [vp, vp, vp, vp, vp]),
     ("fdw_get_extents", C.c_int, [vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     ("fdw_debug_step4_plan", C.c_int, [vp] + [C.c_int] * 8 + [C.POINTER(C.c_int)] * 2 + [vp, C.c_int]),
+    ("fdw_debug_step4_plan_line", C.c_int, [vp] + [C.c_int] * 6 + [C.POINTER(C.c_int)] * 2 + [vp, C.c_int]),
+    ("fdw_dev_line_steps", C.c_int, [vp, C.POINTER(vp), vp, vp, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), vp]),
+    ("fdw_shot_line", C.c_int, [vp, vp, C.c_int, C.c_int, f32p, f32p, f32p, vp, vp, vp]),
+    ("fdw_record_shot_line", C.c_int, [vp, vp, C.c_int, C.c_int, f32p, f32p, vp, vp]),
+    ("fdw_planewave_lags", C.c_int, [C.c_int, vp, C.c_float, C.c_float, C.c_double, vp]),
+    ("fdw_encode_line_source", C.c_int, [C.c_int, vp, vp, vp, vp, C.c_int, C.c_int, vp]),
+    ("fdw_encode_gathers", C.c_int, [C.c_int, C.c_int, vp, vp, vp, C.c_int, C.c_int, vp]),
     ("fdw_two_step_active", C.c_int, [vp]),
     ("fdw_steps_per_pass", C.c_int, [vp]),
     ("fdw_selftest", C.c_int, [vp]),

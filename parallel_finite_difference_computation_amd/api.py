@@ -123,6 +123,42 @@ def snap_dims(nx, nz, nt, every, dec=1):
     return a.value, b.value, c.value
 
 
+def _i32(a):
+    return np.ascontiguousarray(a, dtype=np.int32).reshape(-1)
+
+
+def planewave_lags(src_ix, dx, dt, p):
+    """fdw_planewave_lags (fdwave.h): lag[s] = lround(p (src_ix[s] - src_ix[0]) dx / dt) - the smallest of them, in double; p in s/m."""
+    src_ix = _i32(src_ix)
+    lag = np.zeros(src_ix.size, np.int32)
+    check(lib().fdw_planewave_lags(src_ix.size, src_ix.ctypes.data, dx, dt, float(p), lag.ctypes.data))
+    return lag
+
+
+def encode_line_source(src_ix, lag, weight, srce, nx):
+    """fdw_encode_line_source (fdwave.h): wav[nx][nt], wav[src_ix[s]][it] += weight[s] * srce[it - lag[s]] for s ascending.  Host arithmetic."""
+    src_ix, lag, weight, srce = _i32(src_ix), _i32(lag), _f32(weight).reshape(-1), _f32(srce).reshape(-1)
+    if not (src_ix.size == lag.size == weight.size):
+        raise ValueError("src_ix, lag and weight must have one entry per shot")
+    wav = np.zeros((nx, srce.size), np.float32)
+    check(lib().fdw_encode_line_source(src_ix.size, src_ix.ctypes.data, lag.ctypes.data, weight.ctypes.data, srce.ctypes.data, srce.size, nx,
+                                       wav.ctypes.data))
+    return wav
+
+
+def encode_gathers(lag, weight, d_obs_all, device=0):
+    """fdw_encode_gathers (fdwave.h): out[ix][it] = sum over s ascending, 0 <= it - lag[s] < nt, of weight[s] * d_obs_all[s][ix][it - lag[s]],
+    every element folded in shot order on the GPU."""
+    lag, weight = _i32(lag), _f32(weight).reshape(-1)
+    d_obs_all = np.ascontiguousarray(d_obs_all, np.float32)
+    if d_obs_all.ndim != 3 or not (d_obs_all.shape[0] == lag.size == weight.size):
+        raise ValueError("d_obs_all must be [nshots][nx][nt] with one lag and one weight per shot")
+    _, nx, nt = d_obs_all.shape
+    out = np.zeros((nx, nt), np.float32)
+    check(lib().fdw_encode_gathers(device, lag.size, lag.ctypes.data, weight.ctypes.data, d_obs_all.ctypes.data, nx, nt, out.ctypes.data))
+    return out
+
+
 class FDWave:
     """One fd_init (fd-code.cu:200-224 / fd-source-code.cu:241-262) worth of state on one MI355X."""
 
@@ -362,6 +398,50 @@ class FDWave:
         check(lib().fdw_record_shot(self._h, _f32(v2, shape), sx, sz, gz, _f32(srce, (self.nt,)), data,
                                     P.ctypes.data if want_fields else None, PP.ctypes.data if want_fields else None))
         return (data, P, PP) if want_fields else data
+
+    # ---- line sources (fdwave.h: plane-wave and encoded-shot migration) ----
+    def shot_line(self, v2, sz, gz, wav, d_obs, imloc=None, want_fields=False, want_illum=False, illum=None):
+        """shot() (v2=None: shot_resident()) whose forward loop is driven by the line source wav[nx][nt] at depth sz instead of a point source
+        (fdwave.h, fdw_shot_line).  Returns what shot() returns."""
+        shape = (self.nxe, self.nze)
+        imloc = np.zeros((self.nx, self.nz), np.float32) if imloc is None else np.array(imloc, np.float32, order="C")
+        P = np.zeros(shape, np.float32) if want_fields else None
+        PP = np.zeros(shape, np.float32) if want_fields else None
+        if want_illum:
+            illum = np.zeros((self.nx, self.nz), np.float32) if illum is None else np.array(_f32(illum, (self.nx, self.nz)), order="C")
+        check(lib().fdw_shot_line(self._h, None if v2 is None else _f32(v2, shape).ctypes.data, sz, gz, _f32(wav, (self.nx, self.nt)),
+                                  _f32(d_obs, (self.nx, self.nt)), imloc, illum.ctypes.data if want_illum else None,
+                                  P.ctypes.data if want_fields else None, PP.ctypes.data if want_fields else None))
+        out = (imloc, P, PP) if want_fields else (imloc,)
+        out = out + (illum,) if want_illum else out
+        return out if len(out) > 1 else imloc
+
+    def record_shot_line(self, v2, sz, gz, wav, want_fields=False):
+        """record_shot() driven by the line source wav[nx][nt] at depth sz (fdwave.h, fdw_record_shot_line); v2=None: the resident model."""
+        shape = (self.nxe, self.nze)
+        data = np.zeros((self.nx, self.nt), np.float32)
+        P = np.zeros(shape, np.float32) if want_fields else None
+        PP = np.zeros(shape, np.float32) if want_fields else None
+        check(lib().fdw_record_shot_line(self._h, None if v2 is None else _f32(v2, shape).ctypes.data, sz, gz, _f32(wav, (self.nx, self.nt)), data,
+                                         P.ctypes.data if want_fields else None, PP.ctypes.data if want_fields else None))
+        return (data, P, PP) if want_fields else data
+
+    def dev_line_steps(self, bufs, d_v2, d_wav, sz, it0, nsteps, gz=0, d_rec=None, d_illum=None, first_pp_twice=False, ip=0, ipp=1, stream=None):
+        """dev_steps2 / dev_record_steps / dev_illum_steps driven by the line source d_wav (device [it][nx]) at depth sz (fdwave.h).
+        Returns (ip, ipp) as dev_steps2 does."""
+        arr = (C.c_void_p * 4)(*bufs)
+        a, b = C.c_int(ip), C.c_int(ipp)
+        check(lib().fdw_dev_line_steps(self._h, arr, d_v2, d_wav, sz, gz, d_rec, d_illum, it0, nsteps, int(first_pp_twice), C.byref(a), C.byref(b),
+                                       stream))
+        return a.value, b.value
+
+    def debug_step4_plan_line(self, sz, r0=0, r1=-1, r0b=0, r1b=0, xchunk=0):
+        """(nblk, nstrip, cls) of a four-step pass of dev_line_steps with the line at depth sz: cls[chunk row * nstrip + strip] = 0 lean, 1 full."""
+        nblk, nstrip = C.c_int(), C.c_int()
+        check(lib().fdw_debug_step4_plan_line(self._h, sz, r0, r1, r0b, r1b, xchunk, C.byref(nblk), C.byref(nstrip), None, 0))
+        cls = np.zeros(nblk.value, np.uint8)
+        check(lib().fdw_debug_step4_plan_line(self._h, sz, r0, r1, r0b, r1b, xchunk, C.byref(nblk), C.byref(nstrip), cls.ctypes.data, cls.size))
+        return nblk.value, nstrip.value, cls
 
     def record_shot_batch(self, nshots, sx0, dsx, sz, gz, srce, v2_all=None, draw_offset=0):
         """`nshots` recorded gathers, source rows sx0 + b dsx, models as shot_batch takes them: data[nshots][nx][nt]."""

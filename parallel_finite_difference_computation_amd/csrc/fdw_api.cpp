@@ -92,6 +92,8 @@ struct fdw_ctx {
     bool batch_illum = false;    // inside fdw_shot_batch_illum's forward loop: the one place a batched launch accumulates illumination
     float* b_rec = nullptr;      // the shots' modelled gathers [shots][nt][nx] (fdw_shot_batch_residual); allocated on first use
     size_t b_rec_cap = 0;
+    float* d_wav = nullptr;      // the line-source gather of fdw_shot_line / fdw_record_shot_line, [nt][nx] (one step's samples contiguous)
+    size_t wav_cap = 0;
     float* d_raw = nullptr;      // gathers as the caller holds them ([shot][nx][nt]) before the transposition on the device
     size_t raw_cap = 0;
     int no_fused_back = 0;   // experiments / tests: backward iterations as two launches (source step, receiver step) -- FDW_NO_FUSED_BACK=1
@@ -349,7 +351,7 @@ extern "C" void fdw_destroy(fdw_ctx* c)
     float* bufs[] = {c->d_taperz, c->d_txfac, c->d_gcx, c->d_gcz, c->fld[0], c->fld[1], c->fld[2], c->fld[3],
                      c->fld[4], c->fld[5], c->fld[6], c->fld[7], c->fld[8], c->fld[9], c->d_v2, c->d_img, c->d_illum, c->d_srce, c->d_dobs, c->d_rec,
                      c->d_vp, c->d_vpe, (float*)c->d_draws, (float*)c->d_jump, c->bfld[0], c->bfld[1], c->bfld[2], c->bfld[3],
-                     c->bfld[4], c->bfld[5], c->bfld[6], c->bfld[7], c->b_v2, c->b_img, c->b_dobs, c->b_illum, c->b_rec, c->d_raw, c->d_snap[0], c->d_snap[1], c->d_snap[2]};
+                     c->bfld[4], c->bfld[5], c->bfld[6], c->bfld[7], c->b_v2, c->b_img, c->b_dobs, c->b_illum, c->b_rec, c->d_raw, c->d_wav, c->d_snap[0], c->d_snap[1], c->d_snap[2]};
     for (float* b : bufs)
         if (b) (void)hipFree(b);
     if (c->stream) (void)hipStreamDestroy(c->stream);
@@ -474,6 +476,18 @@ static int place_receivers(const fdw_ctx* c, const char* who, int off, int gz, I
     return FDW_OK;
 }
 
+// The line source of a forward launch (fdwave.h, "line sources"): one sample per interior row the loop time-steps, rows nxb .. nxb+nsrc-1 with
+// nsrc = min(nx, xlim - nxb), on column sz.  Full-grid contexts only (the callers check): local rows are global rows.
+static int place_line(const fdw_ctx* c, const char* who, int sz, Injection* in)
+{
+    if (sz < 0 || sz >= c->zlim) return fail(FDW_EINVAL, "%s: line-source depth %d outside the time-stepped columns [0,%d)", who, sz, c->zlim);
+    in->x = c->prm.nxb;
+    in->n = std::max(0, std::min(c->nx, c->xlim - c->prm.nxb));
+    return FDW_OK;
+}
+// launcher mode of a forward launch with a line source
+static int line_kmode(const float* d_rec, const float* d_illum) { return d_rec ? FDW_MODE_FWD_LINE_REC : (d_illum ? FDW_MODE_FWD_LINE_ILLUM : FDW_MODE_FWD_LINE); }
+
 // Receiver rows [x, x+n) from upd_x1 up to r1 lie beyond the time-stepped rows (narrow x border + truncated extents): the reference still
 // injects into them and images them.  `samples` holds row x's sample.
 static int static_receiver_rows(fdw_ctx* c, int x, int n, int r1, float* field, const float* samples, const float* psrc, float* img, int gz,
@@ -488,7 +502,8 @@ static int static_receiver_rows(fdw_ctx* c, int x, int n, int r1, float* field, 
 
 static int step_impl(fdw_ctx* c, int mode, const float* d_p, float* d_pp, const float* d_v2, int r0, int r1,
                      int pp_twice, const float* d_inj, int inj_x_global, int inj_z, const float* d_psrc, float* d_img,
-                     hipStream_t s, float* d_rec_row = nullptr, int rec_z = 0, float* d_fpp = nullptr, float* d_out = nullptr, float* d_illum = nullptr)
+                     hipStream_t s, float* d_rec_row = nullptr, int rec_z = 0, float* d_fpp = nullptr, float* d_out = nullptr, float* d_illum = nullptr,
+                     bool line = false)
 {
     const bool lap = (mode == FDW_MODE_LAP);
     if (!d_p || !d_pp) return fail(FDW_EINVAL, "step: field pointer is NULL");
@@ -518,7 +533,10 @@ static int step_impl(fdw_ctx* c, int mode, const float* d_p, float* d_pp, const 
         a.lap_x0 = c->slap_x0; a.lap_x1 = c->slap_x1; a.lap_z0 = c->slap_z0; a.lap_z1 = c->slap_z1;
     }
     Injection in;
-    if (mode == FDW_MODE_FWD || mode == FDW_MODE_DD_FWD || mode == FDW_MODE_MOD)
+    if (line) {               // FWD with d_inj -> this step's line samples [nx], inj_z = their depth
+        if (mode != FDW_MODE_FWD || !d_inj || (d_rec_row && d_illum)) return fail(FDW_EINVAL, "step: a line source drives a forward step, plain, recording or accumulating");
+        FDW_TRY(place_line(c, "step", inj_z, &in));
+    } else if (mode == FDW_MODE_FWD || mode == FDW_MODE_DD_FWD || mode == FDW_MODE_MOD)
         FDW_TRY(place_source(c, "step", mode == FDW_MODE_MOD, d_inj, inj_x_global, inj_z, &in));
     else if (mode == FDW_MODE_RECV || mode == FDW_MODE_DD_RECV || mode == FDW_MODE_BACK)
         FDW_TRY(place_receivers(c, "step", mode == FDW_MODE_DD_RECV ? c->prm.nzb : c->prm.nxb, inj_z, &in));
@@ -528,9 +546,10 @@ static int step_impl(fdw_ctx* c, int mode, const float* d_p, float* d_pp, const 
         return fail(FDW_EINVAL, "step: illumination belongs to a forward step of one shot");
     // the RTM forward step that records its trace row, that accumulates the source illumination (the accumulator travels in `img`), or both
     const bool fwd = mode == FDW_MODE_FWD;
-    const int kmode = (fwd && d_rec_row && d_illum) ? FDW_MODE_FWD_REC_ILLUM : ((fwd && d_rec_row) ? FDW_MODE_FWD_REC : ((fwd && d_illum) ? FDW_MODE_FWD_ILLUM : mode));
-    if (kmode == FDW_MODE_FWD_REC || kmode == FDW_MODE_FWD_REC_ILLUM) fill_rec(c, a, d_rec_row, rec_z);
-    if (kmode == FDW_MODE_FWD_ILLUM || kmode == FDW_MODE_FWD_REC_ILLUM) a.img = d_illum;
+    const int kmode = line ? line_kmode(d_rec_row, d_illum)
+                           : ((fwd && d_rec_row && d_illum) ? FDW_MODE_FWD_REC_ILLUM : ((fwd && d_rec_row) ? FDW_MODE_FWD_REC : ((fwd && d_illum) ? FDW_MODE_FWD_ILLUM : mode)));
+    if (kmode == FDW_MODE_FWD_REC || kmode == FDW_MODE_FWD_REC_ILLUM || kmode == FDW_MODE_FWD_LINE_REC) fill_rec(c, a, d_rec_row, rec_z);
+    if (kmode == FDW_MODE_FWD_ILLUM || kmode == FDW_MODE_FWD_REC_ILLUM || kmode == FDW_MODE_FWD_LINE_ILLUM) a.img = d_illum;
     a.inj = d_inj + in.shift; a.inj_x = in.x; a.inj_z = inj_z; a.inj_n = in.n;
     if (a.r1 <= a.r0) return FDW_OK;
     if (c->nbatch > 1) {      // fdw_shot_batch: shot b = these pointers + b fields, its own gather, its own source row
@@ -550,8 +569,8 @@ static int step_impl(fdw_ctx* c, int mode, const float* d_p, float* d_pp, const 
         if (mode >= FDW_MODE_MOD) return fail(FDW_EINVAL, "step: mode %d has no generic-order kernel", mode);
         // no generic-order illumination kernel: the plain step, then illum += pp (*) pp over the cells it updated
         // (recording too: the generic recording step, then the same add)
-        const bool add = kmode == FDW_MODE_FWD_ILLUM || kmode == FDW_MODE_FWD_REC_ILLUM;
-        e = launch_step_generic(a, c->h, kmode == FDW_MODE_FWD_ILLUM ? FDW_MODE_FWD : (kmode == FDW_MODE_FWD_REC_ILLUM ? FDW_MODE_FWD_REC : kmode), s);
+        const bool add = kmode == FDW_MODE_FWD_ILLUM || kmode == FDW_MODE_FWD_REC_ILLUM || kmode == FDW_MODE_FWD_LINE_ILLUM;
+        e = launch_step_generic(a, c->h, kmode == FDW_MODE_FWD_ILLUM ? FDW_MODE_FWD : (kmode == FDW_MODE_FWD_REC_ILLUM ? FDW_MODE_FWD_REC : (kmode == FDW_MODE_FWD_LINE_ILLUM ? FDW_MODE_FWD_LINE : kmode)), s);
         if (e == hipSuccess && add) e = launch_illum_add(d_pp, d_illum, c->pitch, a.r0, a.r1, c->upd_z1, s);
     }
     if (e != hipSuccess) return fail(FDW_EHIP, "kernel launch failed: %s", hipGetErrorString(e));
@@ -647,7 +666,7 @@ struct Step2Extra {          // what the receiver / imaging variant needs on top
 // d_rec (mode FWD only): the trace rows of both steps, rec and rec + nx (FDW_MODE_FWD_REC)
 static int step2_impl(fdw_ctx* c, int mode, const float* d_p, const float* d_pp, const float* d_v2, float* d_out1, float* d_out2, int pp_twice,
                       const float* d_inj, int inj_x_global, int inj_z, const Step2Extra& ex, hipStream_t s, float* d_rec = nullptr, int rec_z = 0,
-                      float* d_illum = nullptr)
+                      float* d_illum = nullptr, bool line = false)
 {
     if (c->h != kMaxFastHalfOrder) return fail(FDW_EINVAL, "step2: the two-step kernel is built for order 8 only");
     if (!d_p || !d_pp || !d_v2 || !d_out1 || !d_out2) return fail(FDW_EINVAL, "step2: NULL buffer");
@@ -659,13 +678,16 @@ static int step2_impl(fdw_ctx* c, int mode, const float* d_p, const float* d_pp,
     a.psrc_a = ex.psrc_a; a.psrc_b = ex.psrc_b; a.img = ex.img;
     a.r0 = 0; a.r1 = c->upd_x1;
     Injection in;
-    if (mode == FDW_MODE_FWD) {
+    if (line) {               // FWD with d_inj -> the line samples of both steps, [2][nx]
+        if (mode != FDW_MODE_FWD || !d_inj) return fail(FDW_EINVAL, "step2: a line source drives a forward pass");
+        FDW_TRY(place_line(c, "step2", inj_z, &in));
+    } else if (mode == FDW_MODE_FWD) {
         FDW_TRY(place_source(c, "step2", false, d_inj, inj_x_global, inj_z, &in));
     } else if (mode == FDW_MODE_RECV) {
         if (!d_inj || !ex.inj2 || !ex.psrc_a || !ex.psrc_b || !ex.img) return fail(FDW_EINVAL, "step2: RECV needs both sample rows, both source fields and the image");
         FDW_TRY(place_receivers(c, "step2", c->prm.nxb, inj_z, &in));
     }
-    a.inj = d_inj + in.shift; a.inj2 = ex.inj2 + in.shift; a.inj_x = in.x; a.inj_z = inj_z; a.inj_n = in.n;
+    a.inj = d_inj + in.shift; a.inj2 = line ? d_inj + c->nx : ex.inj2 + in.shift; a.inj_x = in.x; a.inj_z = inj_z; a.inj_n = in.n;
     const int ncells = c->pitch / 4;
     a.nstrip = (ncells + 59) / 60;
     a.nzblk = (a.nstrip + 3) / 4;
@@ -682,9 +704,9 @@ static int step2_impl(fdw_ctx* c, int mode, const float* d_p, const float* d_pp,
     a.nblk = a.nzblk * chunks;
     a.nper = (a.nblk + 7) / 8;
     if (d_illum && (mode != FDW_MODE_FWD || d_rec)) return fail(FDW_EINVAL, "step2: illumination belongs to a plain forward pass");
-    const int kmode = (mode == FDW_MODE_FWD && d_rec) ? FDW_MODE_FWD_REC : ((mode == FDW_MODE_FWD && d_illum) ? FDW_MODE_FWD_ILLUM : mode);
-    if (kmode == FDW_MODE_FWD_REC) fill_rec(c, a, d_rec, rec_z);
-    if (kmode == FDW_MODE_FWD_ILLUM) a.img = d_illum;
+    const int kmode = line ? line_kmode(d_rec, d_illum) : ((mode == FDW_MODE_FWD && d_rec) ? FDW_MODE_FWD_REC : ((mode == FDW_MODE_FWD && d_illum) ? FDW_MODE_FWD_ILLUM : mode));
+    if (kmode == FDW_MODE_FWD_REC || kmode == FDW_MODE_FWD_LINE_REC) fill_rec(c, a, d_rec, rec_z);
+    if (kmode == FDW_MODE_FWD_ILLUM || kmode == FDW_MODE_FWD_LINE_ILLUM) a.img = d_illum;
     hipError_t e = launch_step2(a, c->h, kmode, s);
     if (e != hipSuccess) return fail(FDW_EHIP, "step2 launch failed: %s", hipGetErrorString(e));
     return even_steps_tail(c, mode, a, s);
@@ -725,7 +747,10 @@ static void tile_classes(const Step2Args& a, int kmode, std::vector<unsigned cha
         const int xa = second ? a.r0b + (xb - a.chunks_a) * a.xchunk : a.r0 + xb * a.xchunk;
         const int xe = std::min(xa + a.xchunk, second ? a.r1b : a.r1);
         const int cs = zb * (64 - 2 * NS) - NS;
-        const bool lean = kmode == FDW_MODE_PLAIN ? pipe_tile_lean<H, NS, false, 0>(a, cs, xa, xe) : pipe_tile_lean<H, NS, true, 1>(a, cs, xa, xe);
+        const bool lean = kmode == FDW_MODE_PLAIN      ? pipe_tile_lean<H, NS, false, 0>(a, cs, xa, xe)
+                          : kmode == FDW_MODE_FWD_LINE_REC ? pipe_tile_lean<H, NS, true, 2, false, true>(a, cs, xa, xe)
+                          : (kmode == FDW_MODE_FWD_LINE || kmode == FDW_MODE_FWD_LINE_ILLUM) ? pipe_tile_lean<H, NS, true, 2>(a, cs, xa, xe)
+                                                           : pipe_tile_lean<H, NS, true, 1>(a, cs, xa, xe);
         cls[(size_t)L] = lean ? 0 : 1;
     }
 }
@@ -738,7 +763,7 @@ static thread_local StepnPlan* g_plan = nullptr;
 
 static int stepn_impl(fdw_ctx* c, int mode, const float* d_p, const float* d_pp, const float* d_v2, float* d_out1, float* d_out2, int pp_twice,
                       const float* d_inj, int inj_x_global, int inj_z, hipStream_t s, const RowRanges& rr = RowRanges{}, float* d_rec = nullptr,
-                      int rec_z = 0, const StepnBack* bk = nullptr, float* d_illum = nullptr)
+                      int rec_z = 0, const StepnBack* bk = nullptr, float* d_illum = nullptr, bool line = false)
 {
     if (c->h != kMaxFastHalfOrder) return fail(FDW_EINVAL, "stepn: the pipelined kernel is built for order 8 only");
     if (mode != FDW_MODE_FWD && mode != FDW_MODE_PLAIN && mode != FDW_MODE_MOD && mode != FDW_MODE_PLAIN_ALL && mode != FDW_MODE_RECV && mode != FDW_MODE_BACK4)
@@ -771,7 +796,11 @@ static int stepn_impl(fdw_ctx* c, int mode, const float* d_p, const float* d_pp,
         a.zt_hi = four_sided ? c->prm.nze - c->prm.nzb : -1;
     }
     Injection in;
-    if (mode == FDW_MODE_FWD || mode == FDW_MODE_MOD) FDW_TRY(place_source(c, "stepn", mode == FDW_MODE_MOD, d_inj, inj_x_global, inj_z, &in));
+    if (line) {               // FWD with d_inj -> the line samples of the pass's steps, [kPipeSteps][nx]
+        if (mode != FDW_MODE_FWD || !d_inj || (d_rec && d_illum)) return fail(FDW_EINVAL, "stepn: a line source drives a forward pass, plain, recording or accumulating");
+        FDW_TRY(place_line(c, "stepn", inj_z, &in));
+        a.inj_stride = c->nx;
+    } else if (mode == FDW_MODE_FWD || mode == FDW_MODE_MOD) FDW_TRY(place_source(c, "stepn", mode == FDW_MODE_MOD, d_inj, inj_x_global, inj_z, &in));
     if (mode == FDW_MODE_PLAIN_ALL) {
         a.lvl0 = bk->lvl0; a.lvl1 = bk->lvl1;
         for (float* o : {d_out1, d_out2}) if (bk->lvl0 == o || bk->lvl1 == o || bk->lvl0 == bk->lvl1 || bk->lvl0 == d_p || bk->lvl0 == d_pp || bk->lvl1 == d_p || bk->lvl1 == d_pp)
@@ -790,9 +819,10 @@ static int stepn_impl(fdw_ctx* c, int mode, const float* d_p, const float* d_pp,
     if (d_illum && mode != FDW_MODE_FWD) return fail(FDW_EINVAL, "stepn: illumination belongs to a forward pass");
     // FWD with d_rec: the trace rows of the pass's four steps; with d_illum: their squares added to the illumination; with both: both
     const bool fwd = mode == FDW_MODE_FWD;
-    const int kmode = (fwd && d_rec && d_illum) ? FDW_MODE_FWD_REC_ILLUM : ((fwd && d_rec) ? FDW_MODE_FWD_REC : ((fwd && d_illum) ? FDW_MODE_FWD_ILLUM : mode));
-    if (kmode == FDW_MODE_FWD_REC || kmode == FDW_MODE_FWD_REC_ILLUM) fill_rec(c, a, d_rec, rec_z);
-    if (kmode == FDW_MODE_FWD_ILLUM || kmode == FDW_MODE_FWD_REC_ILLUM) a.img = d_illum;
+    const int kmode = line ? line_kmode(d_rec, d_illum)
+                           : ((fwd && d_rec && d_illum) ? FDW_MODE_FWD_REC_ILLUM : ((fwd && d_rec) ? FDW_MODE_FWD_REC : ((fwd && d_illum) ? FDW_MODE_FWD_ILLUM : mode)));
+    if (kmode == FDW_MODE_FWD_REC || kmode == FDW_MODE_FWD_REC_ILLUM || kmode == FDW_MODE_FWD_LINE_REC) fill_rec(c, a, d_rec, rec_z);
+    if (kmode == FDW_MODE_FWD_ILLUM || kmode == FDW_MODE_FWD_REC_ILLUM || kmode == FDW_MODE_FWD_LINE_ILLUM) a.img = d_illum;
     a.inj = d_inj + in.shift; a.inj_x = in.x; a.inj_z = inj_z; a.inj_n = in.n;
     const int ncells = c->pitch / 4, own = 64 - 2 * kPipeSteps;
     a.nstrip = (ncells + own - 1) / own;
@@ -922,13 +952,34 @@ extern "C" int fdw_debug_step4_plan(fdw_ctx* c, int forward, int sx, int sz, int
     return FDW_OK;
 }
 
+// The same for a pass of fdw_dev_line_steps (plain) with the line at depth sz: the tiles of the strip that holds the line run the full body.
+extern "C" int fdw_debug_step4_plan_line(fdw_ctx* c, int sz, int r0, int r1, int r0b, int r1b, int xchunk, int* nblk, int* nstrip, unsigned char* cls,
+                                         int cls_cap)
+{
+    if (!c || !nblk || !nstrip) return fail(FDW_EINVAL, "NULL argument");
+    if (c->prm.dialect != FDW_DIALECT_RTM || !is_full_grid(c)) return fail(FDW_ESTATE, "step4 plan: line sources need a full-grid context of the RTM dialect");
+    if (c->h != kMaxFastHalfOrder) return fail(FDW_EINVAL, "step4: needs order 8");
+    RowRanges rr;
+    rr.r0 = r0; rr.r1 = r1; rr.r0b = r0b; rr.r1b = r1b; rr.xchunk = xchunk;
+    StepnPlan plan;
+    float* const fake = reinterpret_cast<float*>(uintptr_t(1) << 20);      // never dereferenced: the plan hook returns before the launch
+    g_plan = &plan;
+    const int rc = stepn_impl(c, FDW_MODE_FWD, fake, fake + 1, fake + 2, fake + 3, fake + 4, 1, fake + 5, -1, sz, nullptr, rr, nullptr, 0, nullptr, nullptr, true);
+    g_plan = nullptr;
+    if (rc != FDW_OK) return rc;
+    *nblk = plan.nblk; *nstrip = plan.nstrip;
+    if (cls) std::copy(plan.cls.begin(), plan.cls.begin() + std::min<size_t>(plan.cls.size(), (size_t)std::max(cls_cap, 0)), cls);
+    return FDW_OK;
+}
+
 // nsteps reference iterations (R:259-267) over four rotating buffers: kPipeSteps per pass through the wave pipeline, pairs of steps through
 // the two-step kernel, single steps through the one-step kernel, whichever pays.  On entry buf[*ip], buf[*ipp] are the reference's (d_p, d_pp)
 // BEFORE the first swap; on return they index (d_p, d_pp) after the loop.  d_rec: NULL, or the trace rows [it][nx] (fdw_dev_record_steps):
 // the same passes, each through its kernel's recording variant.  d_illum: NULL, or the source illumination (fdw_dev_illum_steps): the same
 // passes, each through its kernel's illumination variant.  Both (fdw_dev_record_illum_steps): pipeline passes and single steps through the
 // combined kernels; there is no combined two-step kernel (a pair becomes two single steps), and every family equals the one-step iteration
-// bit for bit.
+// bit for bit.  line (fdw_dev_line_steps): d_srce holds the line-source gather [it][nx] instead of the wavelet, sx is unused; the same family
+// per pass, the same rotation, the same static rows, each pass through its kernel's line-source variant.
 // Trace samples of iterations it0 .. it0+nsteps-1 on the receiver rows the loop never time-steps (rows >= xlim of this slab): what the
 // reference's d_pp holds there, from the fields (d_p, d_pp) before the first swap
 static int record_static(fdw_ctx* c, const float* d_p, const float* d_pp, int gz, float* d_rec, int it0, int nsteps, hipStream_t s)
@@ -944,7 +995,7 @@ static int record_static(fdw_ctx* c, const float* d_p, const float* d_pp, int gz
 }
 
 static int steps_loop(fdw_ctx* c, float* const* buf, const float* d_v2, const float* d_srce, int sx, int sz, int gz, float* d_rec, int it0, int nsteps,
-                      int first_pp_twice, int* ip, int* ipp, hipStream_t s, float* d_illum = nullptr)
+                      int first_pp_twice, int* ip, int* ipp, hipStream_t s, float* d_illum = nullptr, bool line = false)
 {
     if (!c || !buf || !ip || !ipp) return fail(FDW_EINVAL, "NULL argument");
     if (*ip < 0 || *ip > 3 || *ipp < 0 || *ipp > 3 || *ip == *ipp) return fail(FDW_EINVAL, "steps2: bad buffer indices");
@@ -953,14 +1004,14 @@ static int steps_loop(fdw_ctx* c, float* const* buf, const float* d_v2, const fl
     int k = 0;
     while (k < nsteps) {
         const int twice = (k > 0) || first_pp_twice;
-        const float* inj = d_srce ? d_srce + it0 + k : nullptr;
+        const float* inj = d_srce ? d_srce + (size_t)(it0 + k) * (line ? nxs : 1) : nullptr;
         const int sxx = d_srce ? sx : -1;
         float* rec = d_rec ? d_rec + (size_t)(it0 + k) * nxs : nullptr;
         int o1, o2;   // the two buffers not holding the current pair
         spare_pair(*ip, *ipp, &o1, &o2);
         if (nsteps - k >= kPipeSteps && pipe_pays(c)) {
             FDW_TRY(stepn_impl(c, FDW_MODE_FWD, buf[*ipp], buf[*ip], d_v2, buf[o1], buf[o2], twice, inj, sxx, sz, s, RowRanges{}, rec, gz, nullptr,
-                                d_illum));
+                                d_illum, line));
             *ip = o1; *ipp = o2;   // d_p = u^{n+kPipeSteps-1}, d_pp = u^{n+kPipeSteps}
             k += kPipeSteps;
         } else if (nsteps - k >= 2 && two_step_pays(c) && d_rec && d_illum) {
@@ -979,13 +1030,13 @@ static int steps_loop(fdw_ctx* c, float* const* buf, const float* d_v2, const fl
             k += 2;
         } else if (nsteps - k >= 2 && two_step_pays(c)) {
             // after the swap the kernel's p is the old d_pp (newest field), its pp the old d_p
-            FDW_TRY(step2_impl(c, FDW_MODE_FWD, buf[*ipp], buf[*ip], d_v2, buf[o1], buf[o2], twice, inj, sxx, sz, Step2Extra{}, s, rec, gz, d_illum));
+            FDW_TRY(step2_impl(c, FDW_MODE_FWD, buf[*ipp], buf[*ip], d_v2, buf[o1], buf[o2], twice, inj, sxx, sz, Step2Extra{}, s, rec, gz, d_illum, line));
             *ip = o1; *ipp = o2;   // d_p = u^{n+1}, d_pp = u^{n+2}
             k += 2;
         } else {
             std::swap(*ip, *ipp);
             FDW_TRY(step_impl(c, FDW_MODE_FWD, buf[*ip], buf[*ipp], d_v2, 0, c->nxl, twice, inj, sxx, sz, nullptr, nullptr, s, rec, gz, nullptr, nullptr,
-                               d_illum));
+                               d_illum, line));
             k += 1;
         }
     }
@@ -1074,6 +1125,33 @@ extern "C" int fdw_dev_record_illum_steps(fdw_ctx* c, float* const* d_buf, const
     FDW_TRY(check_illum_ctx(c, "fdw_dev_record_illum_steps"));
     FDW_TRY(check_record_depth(c, gz));
     return steps_loop(c, d_buf, d_v2, d_srce, sx, sz, gz, d_rec, it0, nsteps, first_pp_twice, ip, ipp, pick_stream(c, stream), d_illum);
+}
+
+// ---- line sources (definitions in fdwave.h) ----
+// the RTM dialect on the whole grid, one shot at a time; then the depth of the line, and at most one of recording and illumination
+static int check_line_ctx(const fdw_ctx* c, const char* who)
+{
+    if (c->prm.dialect != FDW_DIALECT_RTM) return fail(FDW_ESTATE, "%s: line sources belong to the RTM dialect", who);
+    if (!is_full_grid(c)) return fail(FDW_ESTATE, "%s: line sources need a full-grid context (slab-decomposed shots are not covered)", who);
+    if (c->nbatch > 1) return fail(FDW_ESTATE, "%s: not inside a batch of shots", who);
+    return FDW_OK;
+}
+static int check_line_args(const fdw_ctx* c, const char* who, int sz, int gz, bool rec, bool illum)
+{
+    if (rec && illum) return fail(FDW_EINVAL, "%s: trace recording and illumination together are not built for a line source", who);
+    if (sz < 0 || sz >= c->zlim) return fail(FDW_EINVAL, "%s: line-source depth %d outside the time-stepped columns [0,%d)", who, sz, c->zlim);
+    if (rec) FDW_TRY(check_record_depth(c, gz));
+    return FDW_OK;
+}
+
+extern "C" int fdw_dev_line_steps(fdw_ctx* c, float* const* d_buf, const float* d_v2, const float* d_wav, int sz, int gz, float* d_rec, float* d_illum,
+                                  int it0, int nsteps, int first_pp_twice, int* ip, int* ipp, void* stream)
+{
+    if (!c || !d_wav) return fail(FDW_EINVAL, "NULL argument");
+    FDW_TRY(check_line_ctx(c, "fdw_dev_line_steps"));
+    if (it0 < 0) return fail(FDW_EINVAL, "it0=%d", it0);
+    FDW_TRY(check_line_args(c, "fdw_dev_line_steps", sz, gz, d_rec != nullptr, d_illum != nullptr));
+    return steps_loop(c, d_buf, d_v2, d_wav, -1, sz, d_rec ? gz : 0, d_rec, it0, nsteps, first_pp_twice, ip, ipp, pick_stream(c, stream), d_illum, true);
 }
 
 // d_out[i] = d_a[i] - d_b[i] (fdw_gather_residual_kernel); d_out may be d_a
@@ -1247,17 +1325,18 @@ static int upload_source(fdw_ctx* c, const float* srce, int n)
 // sn (fdw_shot_snaps): the loop runs in segments that end on the snapshot levels L = every, 2 every, ... (a loop cut at any iteration equals the
 // uncut one bit for bit: it0 and the owed-taper flag carry over), and after each the frame of d_pp = u^L goes into the frame store.
 static int forward_loop(fdw_ctx* c, int* ip, int* ipp, int sx, int sz, int nsteps, int gz = 0, float* d_rec = nullptr, float* d_illum = nullptr,
-                        const SnapPlan* sn = nullptr)
+                        const SnapPlan* sn = nullptr, bool line = false)
 {
+    const float* d_samples = line ? c->d_wav : c->d_srce;      // line: the gather fdw_shot_line uploaded, [nt][nx]
     FDW_RANGE("fdw: forward loop (fd_forward)");
     int it = 0;
     for (int j = 0; sn && sn->store[0] && j < sn->nframes; j++) {
         const int level = (j + 1) * sn->every;
-        FDW_TRY(steps_loop(c, c->fld, c->d_v2, c->d_srce, sx, sz, gz, d_rec, it, level - it, it > 0, ip, ipp, c->stream, d_illum));
+        FDW_TRY(steps_loop(c, c->fld, c->d_v2, d_samples, sx, sz, gz, d_rec, it, level - it, it > 0, ip, ipp, c->stream, d_illum, line));
         FDW_TRY(snapshot(c, c->fld[*ipp], sn->dec, sn->store[0] + (size_t)j * sn->frame_elems(), c->stream));
         it = level;
     }
-    int rc = steps_loop(c, c->fld, c->d_v2, c->d_srce, sx, sz, gz, d_rec, it, nsteps - it, it > 0, ip, ipp, c->stream, d_illum);
+    int rc = steps_loop(c, c->fld, c->d_v2, d_samples, sx, sz, gz, d_rec, it, nsteps - it, it > 0, ip, ipp, c->stream, d_illum, line);
     if (rc) return rc;
     if (nsteps > 0) return fdw_dev_taper_finalize(c, c->fld[*ip], c->stream);   // the T() d_p still owes (R:285 downloads the damped d_p)
     return FDW_OK;
@@ -1298,6 +1377,14 @@ static int upload_gather(fdw_ctx* c, const float* d_obs)
     int rc = ensure_cap(&c->d_dobs, &c->dobs_cap, (size_t)c->nx * c->prm.nt);
     if (rc) return rc;
     return gathers_to_device(c, d_obs, c->d_dobs, 1);
+}
+
+// the line-source gather wav [nx][nt] -> c->d_wav [nt][nx] (transposed on the device, like a data gather)
+static int upload_line_source(fdw_ctx* c, const float* wav)
+{
+    int rc = ensure_cap(&c->d_wav, &c->wav_cap, (size_t)c->nx * c->prm.nt);
+    if (rc) return rc;
+    return gathers_to_device(c, wav, c->d_wav, 1);
 }
 
 static int image_to_device(fdw_ctx* c, const float* imloc, float* d_dst = nullptr)
@@ -1440,10 +1527,11 @@ static int gathers_to_host(fdw_ctx* c, const float* d_rec, int nshots, float* da
 // sn: NULL, or the snapshot plan of fdw_shot_snaps (frame stores already allocated)
 // residual (fdw_shot_residual): the forward loop records the modelled gather into c->d_rec, c->d_dobs becomes d_obs - d_mod in place before the
 // backward loop reads it; resid: NULL, or [nx][nt] that difference
+// wav (fdw_shot_line): NULL, or the line-source gather [nx][nt] that drives the forward loop in place of (sx, srce)
 static int shot_impl(fdw_ctx* c, const float* v2, int sx, int sz, int gz, const float* srce, const float* d_obs, float* imloc, float* P, float* PP,
-                     float* illum = nullptr, const SnapPlan* sn = nullptr, bool residual = false, float* resid = nullptr)
+                     float* illum = nullptr, const SnapPlan* sn = nullptr, bool residual = false, float* resid = nullptr, const float* wav = nullptr)
 {
-    if (!c || !srce || !d_obs || !imloc) return fail(FDW_EINVAL, "NULL argument");
+    if (!c || (!srce && !wav) || !d_obs || !imloc) return fail(FDW_EINVAL, "NULL argument");
     if (residual) FDW_TRY(check_record_depth(c, gz));
     FDW_RANGE("fdw: shot (uploads, forward, backward, image download)");
     if (!is_full_grid(c)) return fail(FDW_EINVAL, "fdw_shot needs a full-grid context");
@@ -1455,12 +1543,13 @@ static int shot_impl(fdw_ctx* c, const float* v2, int sx, int sz, int gz, const 
     int ip = 0, ipp = 1;
     HIP_TRY(hipMemsetAsync(c->fld[0], 0, field_elems(c) * sizeof(float), c->stream));    // R:496-497
     HIP_TRY(hipMemsetAsync(c->fld[1], 0, field_elems(c) * sizeof(float), c->stream));
-    if ((v2 && (rc = upload_rows(c, c->d_v2, v2, c->stream))) || (rc = upload_source(c, srce, nt)) || (rc = upload_gather(c, d_obs)) ||
-        (rc = image_to_device(c, imloc)))
+    if ((v2 && (rc = upload_rows(c, c->d_v2, v2, c->stream))) || (rc = wav ? upload_line_source(c, wav) : upload_source(c, srce, nt)) ||
+        (rc = upload_gather(c, d_obs)) || (rc = image_to_device(c, imloc)))
         return rc;
     if (illum && ((rc = alloc_zero(&c->d_illum, field_elems(c))) || (rc = image_to_device(c, illum, c->d_illum)))) return rc;
     if (residual && (rc = ensure_cap(&c->d_rec, &c->rec_cap, (size_t)c->nx * nt))) return rc;
-    if ((rc = forward_loop(c, &ip, &ipp, sx, sz, nt, residual ? gz : 0, residual ? c->d_rec : nullptr, illum ? c->d_illum : nullptr, sn))) return rc;
+    if ((rc = forward_loop(c, &ip, &ipp, sx, sz, nt, residual ? gz : 0, residual ? c->d_rec : nullptr, illum ? c->d_illum : nullptr, sn, wav != nullptr)))
+        return rc;
     if (residual) {      // both [nt][nx] in forward time: the backward loop's sample indexing stays as it is
         if ((rc = gather_residual(c->d_dobs, c->d_rec, c->d_dobs, (size_t)c->nx * nt, c->stream))) return rc;
         if (resid && (rc = gathers_to_host(c, c->d_dobs, 1, resid))) return rc;
@@ -1577,9 +1666,9 @@ static int gathers_to_host(fdw_ctx* c, const float* d_rec, int nshots, float* da
 
 // fd_forward from rest (R:496-497, R:259-267) recording data[ix][it] = d_pp(nxb + ix, gz) at the end of iteration it.  v2 == nullptr: the
 // squared model already resident in c->d_v2 (fdw_dev_extendvel_linear).
-static int record_impl(fdw_ctx* c, const float* v2, int sx, int sz, int gz, const float* srce, float* data, float* P, float* PP)
+static int record_impl(fdw_ctx* c, const float* v2, int sx, int sz, int gz, const float* srce, float* data, float* P, float* PP, const float* wav = nullptr)
 {
-    if (!c || !srce || !data) return fail(FDW_EINVAL, "NULL argument");
+    if (!c || (!srce && !wav) || !data) return fail(FDW_EINVAL, "NULL argument");
     FDW_TRY(check_record_depth(c, gz));
     if (!is_full_grid(c)) return fail(FDW_EINVAL, "fdw_record_shot needs a full-grid context");
     if (c->nx <= 0) return fail(FDW_EINVAL, "no receiver rows");
@@ -1590,9 +1679,9 @@ static int record_impl(fdw_ctx* c, const float* v2, int sx, int sz, int gz, cons
     HIP_TRY(hipMemsetAsync(c->fld[0], 0, field_elems(c) * sizeof(float), c->stream));
     HIP_TRY(hipMemsetAsync(c->fld[1], 0, field_elems(c) * sizeof(float), c->stream));
     if (v2) FDW_TRY(upload_rows(c, c->d_v2, v2, c->stream));
-    FDW_TRY(upload_source(c, srce, nt));
+    FDW_TRY(wav ? upload_line_source(c, wav) : upload_source(c, srce, nt));
     int ip = 0, ipp = 1;
-    FDW_TRY(forward_loop(c, &ip, &ipp, sx, sz, nt, gz, c->d_rec));
+    FDW_TRY(forward_loop(c, &ip, &ipp, sx, sz, nt, gz, c->d_rec, nullptr, nullptr, wav != nullptr));
     FDW_TRY(gathers_to_host(c, c->d_rec, 1, data));
     if (P) FDW_TRY(download_rows(c, P, c->fld[ip], c->stream));
     if (PP) FDW_TRY(download_rows(c, PP, c->fld[ipp], c->stream));
@@ -1605,6 +1694,55 @@ extern "C" int fdw_record_shot(fdw_ctx* c, const float* v2, int sx, int sz, int 
     if (!v2) return fail(FDW_EINVAL, "NULL argument");
     if (c) c->v2_resident = false;
     return record_impl(c, v2, sx, sz, gz, srce, data, P, PP);
+}
+
+// ---- shots driven by a line source (definitions in fdwave.h) ----
+extern "C" int fdw_shot_line(fdw_ctx* c, const float* v2, int sz, int gz, const float* wav, const float* d_obs, float* imloc, float* illum, float* P,
+                             float* PP)
+{
+    if (!c || !wav) return fail(FDW_EINVAL, "NULL argument");
+    FDW_TRY(check_line_ctx(c, "fdw_shot_line"));
+    if (!v2 && !c->v2_resident) return fail(FDW_ESTATE, "no resident squared model: call fdw_dev_extendvel_linear first");
+    FDW_TRY(check_line_args(c, "fdw_shot_line", sz, gz, false, illum != nullptr));
+    if (v2) c->v2_resident = false;
+    return shot_impl(c, v2, -1, sz, gz, nullptr, d_obs, imloc, P, PP, illum, nullptr, false, nullptr, wav);
+}
+
+extern "C" int fdw_record_shot_line(fdw_ctx* c, const float* v2, int sz, int gz, const float* wav, float* data, float* P, float* PP)
+{
+    if (!c || !wav) return fail(FDW_EINVAL, "NULL argument");
+    FDW_TRY(check_line_ctx(c, "fdw_record_shot_line"));
+    if (!v2 && !c->v2_resident) return fail(FDW_ESTATE, "no resident squared model: call fdw_dev_extendvel_linear first");
+    FDW_TRY(check_line_args(c, "fdw_record_shot_line", sz, gz, true, false));
+    if (v2) c->v2_resident = false;
+    return record_impl(c, v2, -1, sz, gz, nullptr, data, P, PP, wav);
+}
+
+// The encoded data gather on the device (fdw_encode_gathers_kernel): every output element folds its shots in ascending order.
+extern "C" int fdw_encode_gathers(int device, int nshots, const int* lag, const float* weight, const float* d_obs_all, int nx, int nt, float* out)
+{
+    if (nshots < 0 || nx < 1 || nt < 1 || nx > 65535 || !out || (nshots > 0 && (!lag || !weight || !d_obs_all))) return fail(FDW_EINVAL, "encode_gathers: bad argument");
+    for (int s = 0; s < nshots; s++)
+        if (lag[s] < 0) return fail(FDW_EINVAL, "encode_gathers: lag[%d]=%d is negative", s, lag[s]);
+    int ndev = 0;
+    hipError_t e = hipGetDeviceCount(&ndev);
+    if (e != hipSuccess || device < 0 || device >= ndev)
+        return fail(FDW_ENODEVICE, "encode_gathers: no HIP device %d (%s); libfdwave has no CPU path", device, e != hipSuccess ? hipGetErrorString(e) : "out of range");
+    HIP_TRY(hipSetDevice(device));
+    const size_t gather = (size_t)nx * nt * sizeof(float), all = gather * (size_t)std::max(nshots, 1), tab = (size_t)std::max(nshots, 1) * sizeof(int);
+    float *d_in = nullptr, *d_out = nullptr, *d_w = nullptr;
+    int* d_lag = nullptr;
+    int rc = FDW_OK;
+    if (hipMalloc((void**)&d_in, all) != hipSuccess || hipMalloc((void**)&d_out, gather) != hipSuccess || hipMalloc((void**)&d_w, tab) != hipSuccess ||
+        hipMalloc((void**)&d_lag, tab) != hipSuccess)
+        rc = fail(FDW_ENOMEM, "encode_gathers: hipMalloc(%zu) failed", all + gather);
+    else if ((nshots > 0 && ((e = hipMemcpy(d_in, d_obs_all, all, hipMemcpyHostToDevice)) != hipSuccess || (e = hipMemcpy(d_w, weight, tab, hipMemcpyHostToDevice)) != hipSuccess ||
+                             (e = hipMemcpy(d_lag, lag, tab, hipMemcpyHostToDevice)) != hipSuccess)) ||
+             (e = launch_encode_gathers(d_in, d_lag, d_w, d_out, nshots, nx, nt, nullptr)) != hipSuccess || (e = hipMemcpy(out, d_out, gather, hipMemcpyDeviceToHost)) != hipSuccess)
+        rc = fail(FDW_EHIP, "encode_gathers: %s", hipGetErrorString(e));
+    for (void* b : {(void*)d_in, (void*)d_out, (void*)d_w, (void*)d_lag})
+        if (b) (void)hipFree(b);
+    return rc;
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -160,6 +160,30 @@ __global__ __launch_bounds__(256) void fdw_gather_residual_kernel(const float* a
 
 }  // namespace
 
+// The encoded data gather of a line-source migration (fdw_encode_gathers): out[ix][it] = sum over the shots s, in ascending order from +0.0f,
+// of w[s] * in[s][ix][it - lag[s]] where 0 <= it - lag[s] < nt.  One thread per output element does its own in-order fold (no atomics); lanes
+// run along it, so every shot's reads and the store are contiguous.  Product and sum are rounded separately (round to nearest even).
+__global__ __launch_bounds__(256) void fdw_encode_gathers_kernel(const float* __restrict__ in, const int* __restrict__ lag, const float* __restrict__ w,
+                                                                 float* __restrict__ out, int nshots, int nx, int nt)
+{
+    const int it = blockIdx.x * 256 + threadIdx.x, ix = blockIdx.y;
+    if (it >= nt) return;
+    const size_t row = (size_t)ix * nt, shot = (size_t)nx * nt;
+    float acc = 0.0f;
+    for (int s = 0; s < nshots; s++) {
+        const long long src = (long long)it - lag[s];
+        if (src >= 0 && src < nt) acc = __fadd_rn(acc, __fmul_rn(w[s], in[(size_t)s * shot + row + (size_t)src]));
+    }
+    out[row + it] = acc;
+}
+
+hipError_t launch_encode_gathers(const float* d_in, const int* d_lag, const float* d_w, float* d_out, int nshots, int nx, int nt, hipStream_t s)
+{
+    if (nx <= 0 || nt <= 0) return hipSuccess;
+    hipLaunchKernelGGL(fdw_encode_gathers_kernel, dim3((nt + 255) / 256, nx), dim3(256), 0, s, d_in, d_lag, d_w, d_out, nshots, nx, nt);
+    return hipGetLastError();
+}
+
 hipError_t launch_gather_residual(const float* d_a, const float* d_b, float* d_out, size_t n, hipStream_t s)
 {
     if (n == 0) return hipSuccess;

@@ -255,3 +255,36 @@ void fdw_mod_ricker_wavelet(int nt, float dt, float fpeak, float *s)
         }
     }
 }
+
+/* Plane-wave lags (fdwave.h, "line sources"): in double, l_s = lround(p (src_ix[s] - src_ix[0]) dx / dt), shifted so that the smallest is 0. */
+int fdw_planewave_lags(int nshots, const int *src_ix, float dx, float dt, double p, int *lag)
+{
+    if (nshots < 0 || (nshots > 0 && (!src_ix || !lag)) || !(dt > 0.0f) || !isfinite(p) || !isfinite(dx)) return FDW_EINVAL;
+    long lmin = 0;
+    for (int s = 0; s < nshots; s++) {
+        const double l = p * (double)(src_ix[s] - src_ix[0]) * (double)dx / (double)dt;
+        if (!(fabs(l) < 1e9)) return FDW_EINVAL;
+        const long ls = lround(l);
+        lag[s] = (int)ls;
+        if (s == 0 || ls < lmin) lmin = ls;
+    }
+    for (int s = 0; s < nshots; s++) lag[s] -= (int)lmin;
+    return FDW_OK;
+}
+
+/* The encoded source gather wav[nx][nt]: shots in ascending order, product and sum rounded separately (the file is built with contraction off). */
+int fdw_encode_line_source(int nshots, const int *src_ix, const int *lag, const float *weight, const float *srce, int nt, int nx, float *wav)
+{
+    if (nshots < 0 || nt < 0 || nx < 0 || !wav || (nshots > 0 && (!src_ix || !lag || !weight || (!srce && nt > 0)))) return FDW_EINVAL;
+    for (int s = 0; s < nshots; s++)
+        if (src_ix[s] < 0 || src_ix[s] >= nx || lag[s] < 0) return FDW_EINVAL;
+    for (size_t i = 0; i < (size_t)nx * (size_t)nt; i++) wav[i] = 0.0f;
+    for (int s = 0; s < nshots; s++) {
+        float *row = wav + (size_t)src_ix[s] * (size_t)nt;
+        for (int it = lag[s]; it < nt; it++) {
+            const float prod = weight[s] * srce[it - lag[s]];
+            row[it] = row[it] + prod;
+        }
+    }
+    return FDW_OK;
+}

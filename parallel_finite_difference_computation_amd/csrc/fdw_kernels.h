@@ -17,6 +17,10 @@ enum {
     FDW_MODE_FWD_REC = 10, // launchers only: FWD + the trace sample of every step on the receiver line (fdw_dev_record_steps; StepArgs / Step2Args rec*)
     FDW_MODE_FWD_ILLUM = 11, // launchers only: FWD + the source illumination, illum += new field (*) new field over the update extents (fdw_dev_illum_steps; the accumulator travels in `img`)
     FDW_MODE_FWD_REC_ILLUM = 12, // launchers only: FWD + the trace samples + the source illumination in one launch (fdw_dev_record_illum_steps, fdw_shot_residual)
+    FDW_MODE_FWD_LINE = 13, // launchers only: FWD with a LINE source in place of the point source: inj_n samples on column inj_z of rows [inj_x, inj_x+inj_n)
+                            // (fdw_dev_line_steps; multi-step kernels: level k takes inj + k * inj_stride)
+    FDW_MODE_FWD_LINE_REC = 14,   // ... + the trace samples, written after the injection
+    FDW_MODE_FWD_LINE_ILLUM = 15, // ... + the source illumination, accumulated after the injection
     FDW_MODE_DD_RECV = 6 // its receiver pass (rtm_main.cpp:197-220) + img += stored source field * CURRENT receiver field (rtm_main.cpp:224-230)
 };
 
@@ -186,5 +190,7 @@ hipError_t launch_extendvel(const BorderArgs& a, hipStream_t s);
 hipError_t launch_gather_transpose(const float* d_in, float* d_out, int nx, int nt, int nshots, hipStream_t s);
 // d_out[i] = d_a[i] - d_b[i] for i < n, one fp32 subtraction each; d_out may be d_a (fdw_gather_residual_kernel)
 hipError_t launch_gather_residual(const float* d_a, const float* d_b, float* d_out, size_t n, hipStream_t s);
+// encoded data gather (fdw_encode_gathers_kernel): d_out[ix][it] = the fold over s ascending, 0 <= it - lag[s] < nt, of acc + w[s] * d_in[s][ix][it - lag[s]]
+hipError_t launch_encode_gathers(const float* d_in, const int* d_lag, const float* d_w, float* d_out, int nshots, int nx, int nt, hipStream_t s);
 
 }  // namespace fdw

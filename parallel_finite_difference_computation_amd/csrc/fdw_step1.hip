@@ -483,6 +483,36 @@ __global__ __launch_bounds__(256) void fdw_step_rec_illum_kernel(const StepArgs 
     march<H, true, 1, false, false, PF, false, false, NUM, true, true>(a, sv, lane, zs, xa, xe);
 }
 
+// the forward step driven by a LINE source instead of the point source (FDW_MODE_FWD_LINE*: fdw_dev_line_steps): TAPER + INJ = 2 without imaging,
+// one sample per row of [inj_x, inj_x + inj_n) added on column inj_z after the leap-frog, exactly as the receiver pass adds its trace samples.
+// REC: the trace row of the new field, line sample included; ILL: its square into the accumulator (a.img).  Its own copy of the tile
+// placement, like fdw_step_rec_kernel's.
+template <int H, int PF, bool REC, bool ILL, int NUM>
+__global__ __launch_bounds__(256) void fdw_step_line_kernel(const StepArgs a)
+{
+    const int shot = blockIdx.y;
+    const long long o = shot * a.bstride;
+    const ShotView sv{a.p + o, a.pp + o, (a.out ? a.out : a.pp) + o, a.v2 + shot * a.v2_bstride, a.psrc + o, a.fpp + o, a.img + o, a.inj + shot * a.inj_bstride,
+                      a.inj_x + shot * a.inj_dx, a.rec + shot * a.rec_bstride};
+    const int lane = threadIdx.x & 63;
+    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+
+    const int bid = blockIdx.x;
+    const int L = (bid & 7) * a.nper + (bid >> 3);
+    if (L >= a.nblk) return;
+    const int zb = L % a.nzblk;
+    const int xb = L / a.nzblk;
+    const int wz = a.wz;
+    const int strip = zb * wz + (w & (wz - 1));
+    const int chunk = xb * (4 / wz) + (w / wz);
+    const int zs = strip * 256;
+    if (zs >= a.pitch) return;
+    const int xa = a.r0 + chunk * a.xchunk;
+    const int xe = min(xa + a.xchunk, a.r1);
+    if (xa >= xe) return;
+    march<H, true, 2, false, false, PF, false, false, NUM, REC, ILL>(a, sv, lane, zs, xa, xe);
+}
+
 #if FDW_TU == 0
 // ------------------------------------------------------------------------------------------------
 // generic-order kernel: any even order up to FDW_MAX_ORDER, one thread per point, every tap from
@@ -549,10 +579,11 @@ __global__ __launch_bounds__(256) void fdw_generic_kernel(const StepArgs a, int 
 {
     generic_point<false>(a, h, taper, injmode, img, laponly);
 }
-// FDW_MODE_FWD_REC: the forward step and its trace sample (one thread per point: no march loop to keep free of branches)
-__global__ __launch_bounds__(256) void fdw_generic_rec_kernel(const StepArgs a, int h)
+// FDW_MODE_FWD_REC / FWD_LINE_REC: the forward step (injmode 1 point source, 2 line source) and its trace sample (one thread per point: no
+// march loop to keep free of branches)
+__global__ __launch_bounds__(256) void fdw_generic_rec_kernel(const StepArgs a, int h, int injmode)
 {
-    generic_point<true>(a, h, 1, 1, 0, 0);
+    generic_point<true>(a, h, 1, injmode, 0, 0);
 }
 
 // Source illumination behind the generic-order kernel (orders above 8, forced generic): illum += f (*) f with f the field the step just
@@ -680,6 +711,9 @@ static hipError_t launch_fast_hp(const StepArgs& a, int mode, hipStream_t s)
     case FDW_MODE_FWD_REC: hipLaunchKernelGGL((fdw_step_rec_kernel<H, PF, 0>), grid, block, 0, s, a); break;
     case FDW_MODE_FWD_ILLUM: hipLaunchKernelGGL((fdw_step_illum_kernel<H, PF, 0>), grid, block, 0, s, a); break;
     case FDW_MODE_FWD_REC_ILLUM: hipLaunchKernelGGL((fdw_step_rec_illum_kernel<H, PF, 0>), grid, block, 0, s, a); break;
+    case FDW_MODE_FWD_LINE: hipLaunchKernelGGL((fdw_step_line_kernel<H, PF, false, false, 0>), grid, block, 0, s, a); break;
+    case FDW_MODE_FWD_LINE_REC: hipLaunchKernelGGL((fdw_step_line_kernel<H, PF, true, false, 0>), grid, block, 0, s, a); break;
+    case FDW_MODE_FWD_LINE_ILLUM: hipLaunchKernelGGL((fdw_step_line_kernel<H, PF, false, true, 0>), grid, block, 0, s, a); break;
     default: return hipErrorInvalidValue;
     }
     return hipGetLastError();
@@ -770,6 +804,9 @@ static hipError_t launch_fastnum_h(const StepArgs& a, int mode, hipStream_t s)
     case FDW_MODE_FWD_REC: hipLaunchKernelGGL((fdw_step_rec_kernel<H, 2, 1>), grid, block, 0, s, a); break;
     case FDW_MODE_FWD_ILLUM: hipLaunchKernelGGL((fdw_step_illum_kernel<H, 2, 1>), grid, block, 0, s, a); break;
     case FDW_MODE_FWD_REC_ILLUM: hipLaunchKernelGGL((fdw_step_rec_illum_kernel<H, 2, 1>), grid, block, 0, s, a); break;
+    case FDW_MODE_FWD_LINE: hipLaunchKernelGGL((fdw_step_line_kernel<H, 2, false, false, 1>), grid, block, 0, s, a); break;
+    case FDW_MODE_FWD_LINE_REC: hipLaunchKernelGGL((fdw_step_line_kernel<H, 2, true, false, 1>), grid, block, 0, s, a); break;
+    case FDW_MODE_FWD_LINE_ILLUM: hipLaunchKernelGGL((fdw_step_line_kernel<H, 2, false, true, 1>), grid, block, 0, s, a); break;
     default: return hipErrorInvalidValue;
     }
     return hipGetLastError();
@@ -791,12 +828,12 @@ hipError_t launch_step_generic(const StepArgs& a, int h, int mode, hipStream_t s
 {
     if (a.r1 <= a.r0) return hipSuccess;
     const dim3 grid((a.pitch + 255) / 256, a.r1 - a.r0), block(256);
-    if (mode == FDW_MODE_FWD_REC) {
-        hipLaunchKernelGGL(fdw_generic_rec_kernel, grid, block, 0, s, a, h);
+    if (mode == FDW_MODE_FWD_REC || mode == FDW_MODE_FWD_LINE_REC) {
+        hipLaunchKernelGGL(fdw_generic_rec_kernel, grid, block, 0, s, a, h, mode == FDW_MODE_FWD_REC ? 1 : 2);
         return hipGetLastError();
     }
-    const int taper = (mode == FDW_MODE_FWD || mode == FDW_MODE_RECV);
-    const int inj = (mode == FDW_MODE_FWD) ? 1 : (mode == FDW_MODE_RECV ? 2 : 0);
+    const int taper = (mode == FDW_MODE_FWD || mode == FDW_MODE_RECV || mode == FDW_MODE_FWD_LINE);
+    const int inj = (mode == FDW_MODE_FWD) ? 1 : ((mode == FDW_MODE_RECV || mode == FDW_MODE_FWD_LINE) ? 2 : 0);
     hipLaunchKernelGGL(fdw_generic_kernel, grid, block, 0, s, a, h, taper, inj, mode == FDW_MODE_RECV ? 1 : 0,
                        mode == FDW_MODE_LAP ? 1 : 0);
     return hipGetLastError();

@@ -320,6 +320,34 @@ __global__ __launch_bounds__(256, 2) void fdw_step2_illum_kernel(const Step2Args
     march2<4, true, 1, false, 2, NUM, false, true>(a, lane, strip * 60 - 2, xa, xe, v2_stash[w], ill_stash[w]);
 }
 
+// FDW_MODE_FWD_LINE*: the forward pass driven by a line source (INJ = 2 without imaging: inj -> u^{n+1}, inj2 -> u^{n+2}), plain, with the
+// trace samples of both steps or with their illumination.  Its own tile placement (see fdw_stepn_rec_kernel); ILL: the second LDS slab and two
+// workgroups per CU as in fdw_step2_illum_kernel.  Otherwise three workgroups per CU like the receiver pass, not the point source's four: at
+// 128 VGPRs the FAST plain body spills one VGPR to scratch (the per-row sample loads of both steps keep more scalars alive).
+template <bool REC, bool ILL, int NUM>
+__global__ __launch_bounds__(256, ILL ? 2 : 3) void fdw_step2_line_kernel(const Step2Args a)
+{
+    const int lane = threadIdx.x & 63;
+    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int bid = blockIdx.x;
+    const int L = (bid & 7) * a.nper + (bid >> 3);
+    if (L >= a.nblk) return;
+    const int zb = L % a.nzblk;
+    const int xb = L / a.nzblk;
+    const int strip = zb * 4 + w;
+    if (strip >= a.nstrip) return;
+    const int xa = a.r0 + xb * a.xchunk;
+    const int xe = min(xa + a.xchunk, a.r1);
+    if (xa >= xe) return;
+    __shared__ f4 v2_stash[4][8 * 64];
+    if constexpr (ILL) {
+        __shared__ f4 ill_stash[4][8 * 64];
+        march2<4, true, 2, false, 2, NUM, REC, true>(a, lane, strip * 60 - 2, xa, xe, v2_stash[w], ill_stash[w]);
+    } else {
+        march2<4, true, 2, false, 2, NUM, REC, false>(a, lane, strip * 60 - 2, xa, xe, v2_stash[w]);
+    }
+}
+
 hipError_t launch_step2(const Step2Args& a, int h, int mode, hipStream_t s)
 {
     if (a.nper <= 0) return hipSuccess;
@@ -332,6 +360,9 @@ hipError_t launch_step2(const Step2Args& a, int h, int mode, hipStream_t s)
         case FDW_MODE_RECV:  hipLaunchKernelGGL((fdw_step2_kernel<4, true, 2, true, 2, 1>), grid, block, 0, s, a); break;
         case FDW_MODE_FWD_REC: hipLaunchKernelGGL((fdw_step2_rec_kernel<1>), grid, block, 0, s, a); break;
         case FDW_MODE_FWD_ILLUM: hipLaunchKernelGGL((fdw_step2_illum_kernel<1>), grid, block, 0, s, a); break;
+        case FDW_MODE_FWD_LINE: hipLaunchKernelGGL((fdw_step2_line_kernel<false, false, 1>), grid, block, 0, s, a); break;
+        case FDW_MODE_FWD_LINE_REC: hipLaunchKernelGGL((fdw_step2_line_kernel<true, false, 1>), grid, block, 0, s, a); break;
+        case FDW_MODE_FWD_LINE_ILLUM: hipLaunchKernelGGL((fdw_step2_line_kernel<false, true, 1>), grid, block, 0, s, a); break;
         default: return hipErrorInvalidValue;
         }
         return hipGetLastError();
@@ -342,6 +373,9 @@ hipError_t launch_step2(const Step2Args& a, int h, int mode, hipStream_t s)
     case FDW_MODE_RECV:  hipLaunchKernelGGL((fdw_step2_kernel<4, true, 2, true, 2>), grid, block, 0, s, a); break;
     case FDW_MODE_FWD_REC: hipLaunchKernelGGL((fdw_step2_rec_kernel<0>), grid, block, 0, s, a); break;
     case FDW_MODE_FWD_ILLUM: hipLaunchKernelGGL((fdw_step2_illum_kernel<0>), grid, block, 0, s, a); break;
+    case FDW_MODE_FWD_LINE: hipLaunchKernelGGL((fdw_step2_line_kernel<false, false, 0>), grid, block, 0, s, a); break;
+    case FDW_MODE_FWD_LINE_REC: hipLaunchKernelGGL((fdw_step2_line_kernel<true, false, 0>), grid, block, 0, s, a); break;
+    case FDW_MODE_FWD_LINE_ILLUM: hipLaunchKernelGGL((fdw_step2_line_kernel<false, true, 0>), grid, block, 0, s, a); break;
     default: return hipErrorInvalidValue;
     }
     return hipGetLastError();

@@ -477,6 +477,52 @@ __global__ __launch_bounds__(64 * kPipeSteps, 3) void fdw_stepn_rec_illum_kernel
     else marchn<H, NS, true, 1, PF, false, 0, false, 0, NUM, true, true>(a, lane, k, cs, xa, xe, link, fifo, ilf);
 }
 
+// FDW_MODE_FWD_LINE*: the forward pass driven by a LINE source (fdw_dev_line_steps): wave k adds the samples inj + k inj_stride on column inj_z
+// of rows [inj_x, inj_x + inj_n) to its new row, as the receiver pass of the backward loop does (INJ = 2), here without imaging.  Only the
+// tiles of the strip that holds the line (and those on the frame and in the damped strip) run the full body; the others keep the lean bodies
+// of fdw_stepn_kernel (plain, REC) or of fdw_stepn_illum_kernel (ILL).  REC: wave k records row k of the pass after the injection, full body
+// where the owned lanes hold the receiver column; ILL: the accumulator row rides the 16-slot LDS FIFO, the square taken after the injection.
+// Workgroups per CU as the point-source kernels of the same variant.  Its own tile placement (see fdw_stepn_rec_kernel).
+template <bool REC, bool ILL, int NUM>
+__global__ __launch_bounds__(64 * kPipeSteps, ILL ? 3 : (REC ? kDDWG : kPipeWG)) void fdw_stepn_line_kernel(const Step2Args a)
+{
+    static_assert(!(REC && ILL), "recording and illumination together are not built for the line source");
+    constexpr int H = 4, NS = kPipeSteps, PF = kPipePF;
+    const int lane = threadIdx.x & 63;
+    const int k = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int bid = blockIdx.x;
+    const int L = (bid & 7) * a.nper + (bid >> 3);
+    if (L >= a.nblk) return;
+    const int zb = L % a.nstrip;
+    const int xb = L / a.nstrip;
+    const bool second = xb >= a.chunks_a;
+    const int xa = second ? a.r0b + (xb - a.chunks_a) * a.xchunk : a.r0 + xb * a.xchunk;
+    const int xe = min(xa + a.xchunk, second ? a.r1b : a.r1);
+    if (xa >= xe) return;
+    __shared__ f4 link[NS][2][2][64];
+    __shared__ f4 fifo[pipe_fifo_rows(NS, H)][64];
+    const int cs = zb * (64 - 2 * NS) - NS;
+    const bool lean = pipe_lean<H, NS, true, 2, false, REC>(a, cs, xa, xe);
+    if constexpr (ILL) {
+        __shared__ f4 ilf[16][64];
+        if (lean) {
+            if (k == 0) marchn<H, NS, false, 0, PF, false, 0, true, 1, NUM, false, true>(a, lane, k, cs, xa, xe, link, fifo, ilf);
+            else marchn<H, NS, false, 0, PF, false, 0, true, 2, NUM, false, true>(a, lane, k, cs, xa, xe, link, fifo, ilf);
+        }
+        else marchn<H, NS, true, 2, PF, false, 0, false, 0, NUM, false, true>(a, lane, k, cs, xa, xe, link, fifo, ilf);
+    } else {
+        if (lean) {
+            if (k == 0) marchn<H, NS, false, 0, PF, false, 0, true, 1, NUM>(a, lane, k, cs, xa, xe, link, fifo);
+            else marchn<H, NS, false, 0, PF, false, 0, true, 2, NUM>(a, lane, k, cs, xa, xe, link, fifo);
+        }
+        else if constexpr (REC) marchn<H, NS, true, 2, PF, false, 0, false, 0, NUM, true>(a, lane, k, cs, xa, xe, link, fifo);
+        else {
+            if (k == 0) marchn<H, NS, true, 2, PF, false, 0, false, 1, NUM>(a, lane, k, cs, xa, xe, link, fifo);
+            else marchn<H, NS, true, 2, PF, false, 0, false, 2, NUM>(a, lane, k, cs, xa, xe, link, fifo);
+        }
+    }
+}
+
 // Four iterations of the backward loop in ONE pass: a workgroup of eight waves, waves 0-3 the pipeline of the source field (role 3), waves 4-7
 // the pipeline of the receiver field one march step behind (role 4).  The source-field levels never leave the chip: the receiver wave of
 // level k reads F_{it+k}(row) from the link buffer the source-field wave k wrote it to for its own successor.  6 fields in + 5 out per
@@ -530,6 +576,9 @@ hipError_t launch_stepn(const Step2Args& a, int h, int mode, hipStream_t s)
         case FDW_MODE_FWD_REC: hipLaunchKernelGGL((fdw_stepn_rec_kernel<1>), grid, block, 0, s, a); break;
         case FDW_MODE_FWD_ILLUM: hipLaunchKernelGGL((fdw_stepn_illum_kernel<1>), grid, block, 0, s, a); break;
         case FDW_MODE_FWD_REC_ILLUM: hipLaunchKernelGGL((fdw_stepn_rec_illum_kernel<1>), grid, block, 0, s, a); break;
+        case FDW_MODE_FWD_LINE: hipLaunchKernelGGL((fdw_stepn_line_kernel<false, false, 1>), grid, block, 0, s, a); break;
+        case FDW_MODE_FWD_LINE_REC: hipLaunchKernelGGL((fdw_stepn_line_kernel<true, false, 1>), grid, block, 0, s, a); break;
+        case FDW_MODE_FWD_LINE_ILLUM: hipLaunchKernelGGL((fdw_stepn_line_kernel<false, true, 1>), grid, block, 0, s, a); break;
         case FDW_MODE_PLAIN: hipLaunchKernelGGL((fdw_stepn_kernel<4, kPipeSteps, false, 0, kPipePF, false, 0, 1>), grid, block, 0, s, a); break;
         case FDW_MODE_MOD:   hipLaunchKernelGGL((fdw_stepn_kernel<4, kPipeSteps, true, 3, kPipePF, true, 0, 1>), grid, block, 0, s, a); break;
         case FDW_MODE_PLAIN_ALL: hipLaunchKernelGGL((fdw_stepn_kernel<4, kPipeSteps, false, 0, kPipePF, false, 1, 1>), grid, block, 0, s, a); break;
@@ -544,6 +593,9 @@ hipError_t launch_stepn(const Step2Args& a, int h, int mode, hipStream_t s)
     case FDW_MODE_FWD_REC: hipLaunchKernelGGL((fdw_stepn_rec_kernel<0>), grid, block, 0, s, a); break;
     case FDW_MODE_FWD_ILLUM: hipLaunchKernelGGL((fdw_stepn_illum_kernel<0>), grid, block, 0, s, a); break;
     case FDW_MODE_FWD_REC_ILLUM: hipLaunchKernelGGL((fdw_stepn_rec_illum_kernel<0>), grid, block, 0, s, a); break;
+    case FDW_MODE_FWD_LINE: hipLaunchKernelGGL((fdw_stepn_line_kernel<false, false, 0>), grid, block, 0, s, a); break;
+    case FDW_MODE_FWD_LINE_REC: hipLaunchKernelGGL((fdw_stepn_line_kernel<true, false, 0>), grid, block, 0, s, a); break;
+    case FDW_MODE_FWD_LINE_ILLUM: hipLaunchKernelGGL((fdw_stepn_line_kernel<false, true, 0>), grid, block, 0, s, a); break;
     case FDW_MODE_PLAIN: hipLaunchKernelGGL((fdw_stepn_kernel<4, kPipeSteps, false, 0, kPipePF>), grid, block, 0, s, a); break;
     case FDW_MODE_MOD:   hipLaunchKernelGGL((fdw_stepn_kernel<4, kPipeSteps, true, 3, kPipePF, true>), grid, block, 0, s, a); break;
     case FDW_MODE_PLAIN_ALL: hipLaunchKernelGGL((fdw_stepn_kernel<4, kPipeSteps, false, 0, kPipePF, false, 1>), grid, block, 0, s, a); break;

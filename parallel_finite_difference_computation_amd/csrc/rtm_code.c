@@ -36,7 +36,15 @@
  * the host stacks in shot order as always.  With `illum=1` too, dir.illum and dir.image_illum are written as before and now describe the
  * residual image.  Two more outputs: <tmpdir>/dir.resid ([ns][nx][nt] floats, the layout of datfile, each shot at its offset) and
  * <tmpdir>/dir.misfit (ns doubles, 0.5 sum resid^2 per shot, fdw_gather_misfit); the total is printed after the shots.  resid=1 together
- * with slabs > 1 or with snap > 0 is refused before anything is opened. */
+ * with slabs > 1 or with snap > 0 is refused before anything is opened.
+ *
+ * Plane-wave migration (no counterpart in the reference): the deck key `pw=NP` (>= 1; absent: nothing changes) migrates NP plane-wave
+ * gathers instead of the ns shots.  Plane wave j has the ray parameter p_j = NP == 1 ? 0 : -P + 2 P j / (NP - 1) s/m, P = `pw_pmax`
+ * (>= 0; absent or 0: NP must be 1).  Its lags come from the deck's shot rows fsx + is ds (fdw_planewave_lags), its source gather from the
+ * Ricker wavelet with weights of 1 (fdw_encode_line_source), its data gather from the ns gathers of datfile (fdw_encode_gathers); the
+ * model is the next draw of the border stream (R:486) or vel_ext_file's model j mod ns (R:484); fdw_shot_line migrates it.  The images
+ * are stacked in the order j into dir.image, image.num has one section per plane wave, illum=1 and image_lap=1 work as for shots.  One
+ * plane wave after the other; pw together with slabs > 1, gpus > 1, resid=1 or snap > 0 is refused before anything is opened. */
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -211,6 +219,24 @@ static void *slab_rank_thread(void *p)      /* ranks 1 .. N-1; rank 0 is the mai
     return NULL;
 }
 
+/* illum=1: dir.illum (the stacked illumination) and dir.image_illum (the compensated image) next to the outputs the key leaves untouched */
+static int write_illum_outputs(const char *tmpdir, const float *img, const float *ill, size_t ni, float illum_eps)
+{
+    float *comp = (float *)malloc((ni ? ni : 1) * sizeof(float));
+    FILE *fill = open_out(tmpdir, "dir.illum"), *fcomp = open_out(tmpdir, "dir.image_illum");
+    if (!comp || !fill || !fcomp) return -1;
+    if (fdw_image_compensate(img, ill, ni, illum_eps, comp) != FDW_OK) {
+        fprintf(stderr, "fdw_image_compensate refused illum_eps=%g\n", (double)illum_eps);
+        return -1;
+    }
+    fwrite(ill, sizeof(float), ni, fill);
+    fwrite(comp, sizeof(float), ni, fcomp);
+    fclose(fill);
+    fclose(fcomp);
+    free(comp);
+    return 0;
+}
+
 static double now_s(void)
 {
     struct timeval t;
@@ -308,6 +334,45 @@ int main(int argc, char **argv)
         }
     }
 
+    /* our extension (absent: nothing changes): pw=NP plane-wave gathers migrated with a line source each instead of the ns shots.  One
+     * context, one plane wave after the other: refused with the keys that deal shots out or change what a shot is, before any file, thread,
+     * communicator or device is touched */
+    const int pw = fdw_deck_has(deck, "pw") ? fdw_deck_int(deck, "pw") : 0;
+    const float pw_pmax = fdw_deck_has(deck, "pw_pmax") ? fdw_deck_float(deck, "pw_pmax") : 0.0f;
+    if (fdw_deck_has(deck, "pw")) {
+        int sl = fdw_deck_int(deck, "slabs"), gp = fdw_deck_int(deck, "gpus");
+        if (getenv("FDW_SLABS")) sl = atoi(getenv("FDW_SLABS"));
+        if (getenv("FDW_GPUS")) gp = atoi(getenv("FDW_GPUS"));
+        if (pw < 1) {
+            fprintf(stderr, "pw=%d: the number of plane waves must be >= 1\n", pw);
+            return EXIT_FAILURE;
+        }
+        if (!(pw_pmax >= 0.0f) || pw_pmax > 3.0e38f) {
+            fprintf(stderr, "pw_pmax=%g: the largest ray parameter (s/m) must be finite and >= 0\n", (double)pw_pmax);
+            return EXIT_FAILURE;
+        }
+        if (pw > 1 && pw_pmax == 0.0f) {
+            fprintf(stderr, "pw=%d needs pw_pmax > 0: without it there is one plane wave (p = 0) only\n", pw);
+            return EXIT_FAILURE;
+        }
+        if (sl > 1) {
+            fprintf(stderr, "pw=%d cannot be combined with slabs=%d: slab-decomposed shots take no line source\n", pw, sl);
+            return EXIT_FAILURE;
+        }
+        if (gp > 1) {
+            fprintf(stderr, "pw=%d cannot be combined with gpus=%d: plane waves run one after another on one GPU\n", pw, gp);
+            return EXIT_FAILURE;
+        }
+        if (resid) {
+            fprintf(stderr, "pw=%d cannot be combined with resid=1: residual migration with a line source is not built\n", pw);
+            return EXIT_FAILURE;
+        }
+        if (snap > 0) {
+            fprintf(stderr, "pw=%d cannot be combined with snap=%d: the snapshot shot takes a point source\n", pw, snap);
+            return EXIT_FAILURE;
+        }
+    }
+
     printf("## vp = %s, d_obs = %s, vel_ext_file = %s, vel_ext_flag = %d \n", vpfile, datfile, vel_ext_file, vel_ext_flag);
     printf("## nz = %d, nx = %d, nt = %d \n", nz, nx, nt);
     printf("## dz = %f, dx = %f, dt = %f \n", dz, dx, dt);
@@ -381,6 +446,69 @@ int main(int argc, char **argv)
         return EXIT_FAILURE;
     }
     int shots_per_launch = 1;      /* FDW_TIMING: how many shots advance through one launch per time step */
+    if (pw > 0) {
+        /* ---- pw=NP: NP encoded gathers, each migrated with a delayed line of sources (fdw_shot_line) ---- */
+        const int dev_models = !vel_ext_flag && !getenv("FDW_HOST_BORDER") && nxb != 1 && nzb != 1 && nzb <= nxe;      /* as dev_border below */
+        const long long draws = fdw_border_draws(nx, nz, nxb, nzb);
+        const size_t ng = (size_t)nx * nt;
+        fdw_ctx *ctx = NULL;
+        int *src_ix = (int *)malloc((size_t)ns * sizeof(int)), *lag = (int *)malloc((size_t)ns * sizeof(int));
+        float *weight = (float *)malloc((size_t)ns * sizeof(float)), *wav = (float *)malloc(ng * sizeof(float)), *enc = (float *)malloc(ng * sizeof(float));
+        float *v2 = (float *)malloc(ne * sizeof(float)), *imloc = (float *)malloc(ni * sizeof(float));
+        float *illoc = illum ? (float *)malloc(ni * sizeof(float)) : NULL, *ill = illum ? (float *)calloc(ni, sizeof(float)) : NULL;
+        if (!src_ix || !lag || !weight || !wav || !enc || !v2 || !imloc || (illum && (!illoc || !ill))) {
+            fprintf(stderr, "out of host memory\n");
+            return EXIT_FAILURE;
+        }
+        for (int is = 0; is < ns; is++) {
+            src_ix[is] = fsx + is * ds;
+            weight[is] = 1.0f;
+        }
+        if (fdw_create(&prm, 0, &ctx) != FDW_OK || (dev_models && fdw_model_resident(ctx, vp) != FDW_OK)) {
+            fprintf(stderr, "fdw_create: %s\n", fdw_last_error());
+            return EXIT_FAILURE;
+        }
+        const double t0 = now_s();
+        for (int j = 0; j < pw; j++) {
+            const double p = pw == 1 ? 0.0 : -(double)pw_pmax + 2.0 * (double)pw_pmax * (double)j / (double)(pw - 1);
+            if (fdw_planewave_lags(ns, src_ix, dx, dt, p, lag) != FDW_OK || fdw_encode_line_source(ns, src_ix, lag, weight, srce, nt, nx, wav) != FDW_OK) {
+                fprintf(stderr, "plane wave %d (p = %g s/m): the shot rows fsx + is ds must lie in [0, nx) and the lags p (row - first row) dx / dt must be finite\n",
+                        j + 1, p);
+                return EXIT_FAILURE;
+            }
+            int rc = fdw_encode_gathers(0, ns, lag, weight, d_obs, nx, nt, enc);
+            const float *model = NULL;      /* NULL: the squared model drawn in HBM */
+            if (rc == FDW_OK && dev_models) {
+                rc = fdw_dev_extendvel_linear(ctx, (unsigned long long)j * (unsigned long long)draws, NULL);      /* R:486: the next draw of the stream */
+            } else if (rc == FDW_OK) {
+                const float *v = vpe;
+                if (vel_ext_flag) v = vel_ext_rnd + (size_t)(j % ns) * ne;      /* R:484 */
+                else fdw_extendvel_linear(nx, nz, nxb, nzb, vpe);               /* R:486 */
+                for (size_t k = 0; k < ne; k++) v2[k] = v[k] * v[k];             /* R:490-494 */
+                model = v2;
+            }
+            memset(imloc, 0, ni * sizeof(float));                                /* R:515 */
+            if (illum) memset(illoc, 0, ni * sizeof(float));
+            if (rc == FDW_OK) rc = fdw_shot_line(ctx, model, sz, gz, wav, enc, imloc, illoc, NULL, NULL);
+            if (rc != FDW_OK) {
+                fprintf(stderr, "plane wave %d: %s\n", j + 1, fdw_last_error());
+                return EXIT_FAILURE;
+            }
+            fprintf(stdout, "** plane wave %d, p = %g s/m, depth %d \n\n** backward propagation %d \n\n", j + 1, p, sz - nzb, j + 1);
+            fprintf(fnum, "======== %i ========\n", j);
+            for (int iz = 0; iz < nz; iz++)
+                for (int ix = 0; ix < nx; ix++) {
+                    img[(size_t)ix * nz + iz] += imloc[(size_t)ix * nz + iz];
+                    fprintf(fnum, " %f \n", img[(size_t)ix * nz + iz]);
+                    if (illum) ill[(size_t)ix * nz + iz] += illoc[(size_t)ix * nz + iz];
+                }
+        }
+        t_shots = now_s() - t0;
+        fdw_destroy(ctx);
+        if (illum && write_illum_outputs(tmpdir, img, ill, ni, illum_eps) != 0) return EXIT_FAILURE;
+        free(src_ix); free(lag); free(weight); free(wav); free(enc); free(v2); free(imloc); free(illoc); free(ill);
+        goto outputs;
+    }
     if (slabs > 1) {
         /* ---- every shot on `slabs` GPUs: bands of rows, halo exchange inside the library ---- */
         slab_job sj;
@@ -593,18 +721,7 @@ int main(int argc, char **argv)
     free(vel2_all);
     free(imloc_all);
     if (illum) {      /* dir.illum and dir.image_illum, next to the outputs the key leaves untouched */
-        float *comp = (float *)malloc((ni ? ni : 1) * sizeof(float));
-        FILE *fill = open_out(tmpdir, "dir.illum"), *fcomp = open_out(tmpdir, "dir.image_illum");
-        if (!comp || !fill || !fcomp) return EXIT_FAILURE;
-        if (fdw_image_compensate(img, ill, ni, illum_eps, comp) != FDW_OK) {
-            fprintf(stderr, "fdw_image_compensate refused illum_eps=%g\n", (double)illum_eps);
-            return EXIT_FAILURE;
-        }
-        fwrite(ill, sizeof(float), ni, fill);
-        fwrite(comp, sizeof(float), ni, fcomp);
-        fclose(fill);
-        fclose(fcomp);
-        free(comp);
+        if (write_illum_outputs(tmpdir, img, ill, ni, illum_eps) != 0) return EXIT_FAILURE;
         free(illoc_all);
         free(ill);
     }
