@@ -536,8 +536,8 @@ int fdw_slabs_set_stub(fdw_slabs *s, int on);
  * ignored: the line ends before the rows the reference never time-steps (a point source there is refused, a full-width line is not).
  * sz outside [0, zlim): FDW_EINVAL before anything is enqueued.  Recording, illumination, P / PP and the backward loop keep their
  * definitions: the recorded and the squared value is the stored new field, line samples included; the backward loop is fd_back as it
- * stands and reconstructs the source field from (P, PP) without a source (R:317-318), as it does for a point source.  Recording and
- * illumination together are not built for a line source: both pointers non-NULL is FDW_EINVAL.
+ * stands and reconstructs the source field from (P, PP) without a source (R:317-318), as it does for a point source.  fdw_dev_line_steps takes
+ * at most one of d_rec and d_illum (both non-NULL is FDW_EINVAL); both together go through fdw_dev_line_record_illum_steps.
  *
  * fdw_dev_line_steps    fdw_dev_steps2 / fdw_dev_record_steps / fdw_dev_illum_steps driven by the line: d_wav [>= it0+nsteps][nx] on the
  *                       device (row it = the samples of iteration it), d_rec (NULL ok) the trace rows [it][nx] at gz, d_illum (NULL ok) the
@@ -563,6 +563,44 @@ int fdw_debug_step4_plan_line(fdw_ctx *ctx, int sz, int r0, int r1, int r0b, int
 int fdw_planewave_lags(int nshots, const int *src_ix, float dx, float dt, double p, int *lag);
 int fdw_encode_line_source(int nshots, const int *src_ix, const int *lag, const float *weight, const float *srce, int nt, int nx, float *wav);
 int fdw_encode_gathers(int device, int nshots, const int *lag, const float *weight, const float *d_obs_all, int nx, int nt, float *out);
+
+/* ---- line sources: recording with illumination, residual migration, batches, one-pass encoding -----
+ * Same contexts and refusals as above (FDW_ESTATE elsewhere; sz, and gz where traces are recorded, outside [0, zlim): FDW_EINVAL before
+ * anything is enqueued).  Every result is defined by single calls of the entry points above and equals them bit for bit.
+ *
+ * fdw_dev_line_record_illum_steps  fdw_dev_line_steps that writes the trace rows AND accumulates, every pass one launch of its family's
+ *                                  combined line-source kernel (orders above 8 and the forced generic kernel: the generic recording step, then
+ *                                  the accumulation).  d_rec or d_illum NULL: FDW_EINVAL.  Fields, trace rows and accumulator equal two runs
+ *                                  of fdw_dev_line_steps, one with d_rec, one with d_illum.
+ * fdw_shot_line_residual           fdw_shot_line that migrates resid = d_obs (-) d_mod (one fp32 subtraction per sample, fdw_dev_gather_residual),
+ *                                  d_mod the gather its own forward loop records: fdw_record_shot_line's for the same context, model, wav, sz,
+ *                                  gz.  imloc is fdw_shot_line's handed resid as d_obs; illum, P, PP are fdw_shot_line's.  resid (NULL ok)
+ *                                  [nx][nt].  Data modelled by fdw_record_shot_line in the migration model: resid is all-zero words and imloc
+ *                                  keeps its entry values.
+ * fdw_shot_line_batch              `nshots` calls of fdw_shot_line, shot b with wav_all[b], d_obs[b] (both [nshots][nx][nt]), imloc[b] and
+ *                                  illum[b] (NULL ok; [nshots][nx][nz]) and the model v2_all[b], or with v2_all == NULL the border model of
+ *                                  draws draw_offset + b T on the resident interior model (T = fdw_border_draws), as fdw_shot_batch takes them.
+ *                                  Where fdw_shot_batch batches, the whole batch advances through one launch per time step (one more batch
+ *                                  buffer, [nshots][nt][nx], holds the line gathers); otherwise, and on a device without room for the
+ *                                  buffers, the shots run one by one.  Batches larger than the budget of fdw_shot_batch_max allows with these
+ *                                  buffers counted go through in parts.  The bytes are the same in every case.
+ * fdw_shot_line_batch_residual     the same for fdw_shot_line_residual; resid (NULL ok) [nshots][nx][nt].
+ * fdw_record_shot_line_batch       the same for fdw_record_shot_line; data [nshots][nx][nt].
+ * fdw_encode_gathers_multi         `nplanes` calls of fdw_encode_gathers on one data set: lag, weight [nplanes][nshots], out [nplanes][nx][nt].
+ *                                  One upload of d_obs_all, one launch (fdw_encode_gathers_multi_kernel), one download.  nplanes outside
+ *                                  [1, 65535], a negative lag or a NULL argument: FDW_EINVAL before a device is opened. */
+int fdw_dev_line_record_illum_steps(fdw_ctx *ctx, float *const *d_buf /* [4] */, const float *d_v2, const float *d_wav, int sz, int gz, float *d_rec,
+                                    float *d_illum, int it0, int nsteps, int first_pp_twice, int *ip, int *ipp, void *stream);
+int fdw_shot_line_residual(fdw_ctx *ctx, const float *v2, int sz, int gz, const float *wav, const float *d_obs, float *imloc, float *illum,
+                           float *resid, float *P, float *PP);
+int fdw_shot_line_batch(fdw_ctx *ctx, int nshots, const float *v2_all, unsigned long long draw_offset, int sz, int gz, const float *wav_all,
+                        const float *d_obs, float *imloc, float *illum);
+int fdw_shot_line_batch_residual(fdw_ctx *ctx, int nshots, const float *v2_all, unsigned long long draw_offset, int sz, int gz, const float *wav_all,
+                                 const float *d_obs, float *imloc, float *illum, float *resid);
+int fdw_record_shot_line_batch(fdw_ctx *ctx, int nshots, const float *v2_all, unsigned long long draw_offset, int sz, int gz, const float *wav_all,
+                               float *data);
+int fdw_encode_gathers_multi(int device, int nshots, int nplanes, const int *lag, const float *weight, const float *d_obs_all, int nx, int nt,
+                             float *out);
 
 /* ---- tuning / introspection --------------------------------------------------------------------
  * fdw_set_tuning  xchunk = rows marched per wave (0 = auto), wz = waves of a block laid along z

@@ -137,6 +137,12 @@ SIGNATURES = [
     ("fdw_planewave_lags", C.c_int, [C.c_int, vp, C.c_float, C.c_float, C.c_double, vp]),
     ("fdw_encode_line_source", C.c_int, [C.c_int, vp, vp, vp, vp, C.c_int, C.c_int, vp]),
     ("fdw_encode_gathers", C.c_int, [C.c_int, C.c_int, vp, vp, vp, C.c_int, C.c_int, vp]),
+    ("fdw_dev_line_record_illum_steps", C.c_int, [vp, C.POINTER(vp), vp, vp, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), vp]),
+    ("fdw_shot_line_residual", C.c_int, [vp, vp, C.c_int, C.c_int, f32p, f32p, f32p, vp, vp, vp, vp]),
+    ("fdw_shot_line_batch", C.c_int, [vp, C.c_int, vp, C.c_ulonglong, C.c_int, C.c_int, f32p, f32p, f32p, vp]),
+    ("fdw_shot_line_batch_residual", C.c_int, [vp, C.c_int, vp, C.c_ulonglong, C.c_int, C.c_int, f32p, f32p, f32p, vp, vp]),
+    ("fdw_record_shot_line_batch", C.c_int, [vp, C.c_int, vp, C.c_ulonglong, C.c_int, C.c_int, f32p, f32p]),
+    ("fdw_encode_gathers_multi", C.c_int, [C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_int, C.c_int, vp]),
     ("fdw_two_step_active", C.c_int, [vp]),
     ("fdw_steps_per_pass", C.c_int, [vp]),
     ("fdw_selftest", C.c_int, [vp]),

@@ -159,6 +159,20 @@ def encode_gathers(lag, weight, d_obs_all, device=0):
     return out
 
 
+def encode_gathers_multi(lag, weight, d_obs_all, device=0):
+    """fdw_encode_gathers_multi (fdwave.h): encode_gathers for `nplanes` encodings of one data set in one upload and one launch.
+    lag, weight [nplanes][nshots]; returns out[nplanes][nx][nt], plane j equal to encode_gathers(lag[j], weight[j], d_obs_all) bit for bit."""
+    lag, weight = np.ascontiguousarray(lag, np.int32), _f32(weight)
+    d_obs_all = np.ascontiguousarray(d_obs_all, np.float32)
+    if d_obs_all.ndim != 3 or lag.ndim != 2 or lag.shape != weight.shape or lag.shape[1] != d_obs_all.shape[0]:
+        raise ValueError("d_obs_all must be [nshots][nx][nt], lag and weight [nplanes][nshots]")
+    _, nx, nt = d_obs_all.shape
+    out = np.zeros((lag.shape[0], nx, nt), np.float32)
+    check(lib().fdw_encode_gathers_multi(device, lag.shape[1], lag.shape[0], lag.ctypes.data, weight.ctypes.data, d_obs_all.ctypes.data, nx, nt,
+                                         out.ctypes.data))
+    return out
+
+
 class FDWave:
     """One fd_init (fd-code.cu:200-224 / fd-source-code.cu:241-262) worth of state on one MI355X."""
 
@@ -434,6 +448,68 @@ class FDWave:
         check(lib().fdw_dev_line_steps(self._h, arr, d_v2, d_wav, sz, gz, d_rec, d_illum, it0, nsteps, int(first_pp_twice), C.byref(a), C.byref(b),
                                        stream))
         return a.value, b.value
+
+    def dev_line_record_illum_steps(self, bufs, d_v2, d_wav, sz, gz, d_rec, d_illum, it0, nsteps, first_pp_twice=False, ip=0, ipp=1, stream=None):
+        """dev_line_steps that writes the trace rows AND accumulates the illumination, one launch per pass (fdwave.h).  Returns (ip, ipp)."""
+        arr = (C.c_void_p * 4)(*bufs)
+        a, b = C.c_int(ip), C.c_int(ipp)
+        check(lib().fdw_dev_line_record_illum_steps(self._h, arr, d_v2, d_wav, sz, gz, d_rec, d_illum, it0, nsteps, int(first_pp_twice), C.byref(a),
+                                                    C.byref(b), stream))
+        return a.value, b.value
+
+    def shot_line_residual(self, v2, sz, gz, wav, d_obs, imloc=None, want_resid=True, want_fields=False, want_illum=False, illum=None):
+        """Residual migration with a line source (fdwave.h, fdw_shot_line_residual): shot_line() whose forward loop also models the gather d_mod
+        of record_shot_line() and whose backward loop migrates d_obs - d_mod.  Returns a dict as shot_residual() does."""
+        shape = (self.nxe, self.nze)
+        out = {"image": np.zeros((self.nx, self.nz), np.float32) if imloc is None else np.array(imloc, np.float32, order="C")}
+        if want_resid:
+            out["resid"] = np.zeros((self.nx, self.nt), np.float32)
+        if want_fields:
+            out["P"], out["PP"] = np.zeros(shape, np.float32), np.zeros(shape, np.float32)
+        if want_illum:
+            out["illum"] = np.zeros((self.nx, self.nz), np.float32) if illum is None else np.array(_f32(illum, (self.nx, self.nz)), order="C")
+
+        def ptr(name):
+            return out[name].ctypes.data if name in out else None
+
+        check(lib().fdw_shot_line_residual(self._h, None if v2 is None else _f32(v2, shape).ctypes.data, sz, gz, _f32(wav, (self.nx, self.nt)),
+                                           _f32(d_obs, (self.nx, self.nt)), out["image"], ptr("illum"), ptr("resid"), ptr("P"), ptr("PP")))
+        return out
+
+    def shot_line_batch(self, nshots, sz, gz, wav_all, d_obs, v2_all=None, draw_offset=0, imloc=None, want_illum=False, illum=None):
+        """`nshots` line-source shots (shot_line) through one launch per time step where shot_batch batches: wav_all, d_obs [nshots][nx][nt],
+        models as shot_batch takes them.  Returns imloc[nshots][nx][nz], or (imloc, illum) with want_illum."""
+        shape = (nshots, self.nx, self.nz)
+        imloc = np.zeros(shape, np.float32) if imloc is None else np.array(_f32(imloc, shape), order="C")
+        v2p = None if v2_all is None else _f32(v2_all, (nshots, self.nxe, self.nze)).ctypes.data
+        if want_illum:
+            illum = np.zeros(shape, np.float32) if illum is None else np.array(_f32(illum, shape), order="C")
+        check(lib().fdw_shot_line_batch(self._h, nshots, v2p, int(draw_offset), sz, gz, _f32(wav_all, (nshots, self.nx, self.nt)),
+                                        _f32(d_obs, (nshots, self.nx, self.nt)), imloc, illum.ctypes.data if want_illum else None))
+        return (imloc, illum) if want_illum else imloc
+
+    def shot_line_batch_residual(self, nshots, sz, gz, wav_all, d_obs, v2_all=None, draw_offset=0, imloc=None, want_resid=True, want_illum=False,
+                                 illum=None):
+        """`nshots` residual migrations with line sources (shot_line_residual), batched as shot_line_batch.  Returns a dict: image
+        [nshots][nx][nz], and resid [nshots][nx][nt] / illum [nshots][nx][nz] as asked."""
+        shape = (nshots, self.nx, self.nz)
+        out = {"image": np.zeros(shape, np.float32) if imloc is None else np.array(_f32(imloc, shape), order="C")}
+        if want_resid:
+            out["resid"] = np.zeros((nshots, self.nx, self.nt), np.float32)
+        if want_illum:
+            out["illum"] = np.zeros(shape, np.float32) if illum is None else np.array(_f32(illum, shape), order="C")
+        v2p = None if v2_all is None else _f32(v2_all, (nshots, self.nxe, self.nze)).ctypes.data
+        check(lib().fdw_shot_line_batch_residual(self._h, nshots, v2p, int(draw_offset), sz, gz, _f32(wav_all, (nshots, self.nx, self.nt)),
+                                                 _f32(d_obs, (nshots, self.nx, self.nt)), out["image"],
+                                                 out["illum"].ctypes.data if want_illum else None, out["resid"].ctypes.data if want_resid else None))
+        return out
+
+    def record_shot_line_batch(self, nshots, sz, gz, wav_all, v2_all=None, draw_offset=0):
+        """`nshots` gathers recorded with line sources (record_shot_line), batched as shot_line_batch: data[nshots][nx][nt]."""
+        data = np.zeros((nshots, self.nx, self.nt), np.float32)
+        v2p = None if v2_all is None else _f32(v2_all, (nshots, self.nxe, self.nze)).ctypes.data
+        check(lib().fdw_record_shot_line_batch(self._h, nshots, v2p, int(draw_offset), sz, gz, _f32(wav_all, (nshots, self.nx, self.nt)), data))
+        return data
 
     def debug_step4_plan_line(self, sz, r0=0, r1=-1, r0b=0, r1b=0, xchunk=0):
         """(nblk, nstrip, cls) of a four-step pass of dev_line_steps with the line at depth sz: cls[chunk row * nstrip + strip] = 0 lean, 1 full."""

@@ -94,6 +94,8 @@ struct fdw_ctx {
     size_t b_rec_cap = 0;
     float* d_wav = nullptr;      // the line-source gather of fdw_shot_line / fdw_record_shot_line, [nt][nx] (one step's samples contiguous)
     size_t wav_cap = 0;
+    float* b_wav = nullptr;      // the shots' line-source gathers [shots][nt][nx] (fdw_shot_line_batch and its kin); allocated on first use
+    size_t b_wav_cap = 0;
     float* d_raw = nullptr;      // gathers as the caller holds them ([shot][nx][nt]) before the transposition on the device
     size_t raw_cap = 0;
     int no_fused_back = 0;   // experiments / tests: backward iterations as two launches (source step, receiver step) -- FDW_NO_FUSED_BACK=1
@@ -351,7 +353,7 @@ extern "C" void fdw_destroy(fdw_ctx* c)
     float* bufs[] = {c->d_taperz, c->d_txfac, c->d_gcx, c->d_gcz, c->fld[0], c->fld[1], c->fld[2], c->fld[3],
                      c->fld[4], c->fld[5], c->fld[6], c->fld[7], c->fld[8], c->fld[9], c->d_v2, c->d_img, c->d_illum, c->d_srce, c->d_dobs, c->d_rec,
                      c->d_vp, c->d_vpe, (float*)c->d_draws, (float*)c->d_jump, c->bfld[0], c->bfld[1], c->bfld[2], c->bfld[3],
-                     c->bfld[4], c->bfld[5], c->bfld[6], c->bfld[7], c->b_v2, c->b_img, c->b_dobs, c->b_illum, c->b_rec, c->d_raw, c->d_wav, c->d_snap[0], c->d_snap[1], c->d_snap[2]};
+                     c->bfld[4], c->bfld[5], c->bfld[6], c->bfld[7], c->b_v2, c->b_img, c->b_dobs, c->b_illum, c->b_rec, c->b_wav, c->d_raw, c->d_wav, c->d_snap[0], c->d_snap[1], c->d_snap[2]};
     for (float* b : bufs)
         if (b) (void)hipFree(b);
     if (c->stream) (void)hipStreamDestroy(c->stream);
@@ -486,7 +488,11 @@ static int place_line(const fdw_ctx* c, const char* who, int sz, Injection* in)
     return FDW_OK;
 }
 // launcher mode of a forward launch with a line source
-static int line_kmode(const float* d_rec, const float* d_illum) { return d_rec ? FDW_MODE_FWD_LINE_REC : (d_illum ? FDW_MODE_FWD_LINE_ILLUM : FDW_MODE_FWD_LINE); }
+static int line_kmode(const float* d_rec, const float* d_illum)
+{
+    if (d_rec && d_illum) return FDW_MODE_FWD_LINE_REC_ILLUM;
+    return d_rec ? FDW_MODE_FWD_LINE_REC : (d_illum ? FDW_MODE_FWD_LINE_ILLUM : FDW_MODE_FWD_LINE);
+}
 
 // Receiver rows [x, x+n) from upd_x1 up to r1 lie beyond the time-stepped rows (narrow x border + truncated extents): the reference still
 // injects into them and images them.  `samples` holds row x's sample.
@@ -534,7 +540,7 @@ static int step_impl(fdw_ctx* c, int mode, const float* d_p, float* d_pp, const 
     }
     Injection in;
     if (line) {               // FWD with d_inj -> this step's line samples [nx], inj_z = their depth
-        if (mode != FDW_MODE_FWD || !d_inj || (d_rec_row && d_illum)) return fail(FDW_EINVAL, "step: a line source drives a forward step, plain, recording or accumulating");
+        if (mode != FDW_MODE_FWD || !d_inj) return fail(FDW_EINVAL, "step: a line source drives a forward step");
         FDW_TRY(place_line(c, "step", inj_z, &in));
     } else if (mode == FDW_MODE_FWD || mode == FDW_MODE_DD_FWD || mode == FDW_MODE_MOD)
         FDW_TRY(place_source(c, "step", mode == FDW_MODE_MOD, d_inj, inj_x_global, inj_z, &in));
@@ -548,15 +554,17 @@ static int step_impl(fdw_ctx* c, int mode, const float* d_p, float* d_pp, const 
     const bool fwd = mode == FDW_MODE_FWD;
     const int kmode = line ? line_kmode(d_rec_row, d_illum)
                            : ((fwd && d_rec_row && d_illum) ? FDW_MODE_FWD_REC_ILLUM : ((fwd && d_rec_row) ? FDW_MODE_FWD_REC : ((fwd && d_illum) ? FDW_MODE_FWD_ILLUM : mode)));
-    if (kmode == FDW_MODE_FWD_REC || kmode == FDW_MODE_FWD_REC_ILLUM || kmode == FDW_MODE_FWD_LINE_REC) fill_rec(c, a, d_rec_row, rec_z);
-    if (kmode == FDW_MODE_FWD_ILLUM || kmode == FDW_MODE_FWD_REC_ILLUM || kmode == FDW_MODE_FWD_LINE_ILLUM) a.img = d_illum;
+    if (kmode == FDW_MODE_FWD_REC || kmode == FDW_MODE_FWD_REC_ILLUM || kmode == FDW_MODE_FWD_LINE_REC || kmode == FDW_MODE_FWD_LINE_REC_ILLUM)
+        fill_rec(c, a, d_rec_row, rec_z);
+    if (kmode == FDW_MODE_FWD_ILLUM || kmode == FDW_MODE_FWD_REC_ILLUM || kmode == FDW_MODE_FWD_LINE_ILLUM || kmode == FDW_MODE_FWD_LINE_REC_ILLUM) a.img = d_illum;
     a.inj = d_inj + in.shift; a.inj_x = in.x; a.inj_z = inj_z; a.inj_n = in.n;
     if (a.r1 <= a.r0) return FDW_OK;
     if (c->nbatch > 1) {      // fdw_shot_batch: shot b = these pointers + b fields, its own gather, its own source row
         a.nbatch = c->nbatch;
         a.bstride = (long long)field_elems(c);
-        const bool one_source = mode == FDW_MODE_FWD || mode == FDW_MODE_MOD;     // the wavelet is shared, its row moves; receivers: a gather each
-        a.inj_bstride = one_source ? 0 : (long long)c->nx * c->prm.nt;
+        // the wavelet is shared, its row moves; receivers and line sources (fdw_shot_line_batch): a gather each, the rows the same
+        const bool one_source = (mode == FDW_MODE_FWD && !line) || mode == FDW_MODE_MOD;
+        a.inj_bstride = one_source ? 0 : (long long)c->nx * (line ? c->batch_nt : c->prm.nt);
         a.inj_dx = one_source ? c->batch_dsx : 0;
         a.v2_bstride = mode == FDW_MODE_MOD ? 0 : a.bstride;                       // mod_main models every shot on one velocity model (M:140-174)
         a.rec_bstride = (long long)c->nx * c->batch_nt;
@@ -569,8 +577,11 @@ static int step_impl(fdw_ctx* c, int mode, const float* d_p, float* d_pp, const 
         if (mode >= FDW_MODE_MOD) return fail(FDW_EINVAL, "step: mode %d has no generic-order kernel", mode);
         // no generic-order illumination kernel: the plain step, then illum += pp (*) pp over the cells it updated
         // (recording too: the generic recording step, then the same add)
-        const bool add = kmode == FDW_MODE_FWD_ILLUM || kmode == FDW_MODE_FWD_REC_ILLUM || kmode == FDW_MODE_FWD_LINE_ILLUM;
-        e = launch_step_generic(a, c->h, kmode == FDW_MODE_FWD_ILLUM ? FDW_MODE_FWD : (kmode == FDW_MODE_FWD_REC_ILLUM ? FDW_MODE_FWD_REC : (kmode == FDW_MODE_FWD_LINE_ILLUM ? FDW_MODE_FWD_LINE : kmode)), s);
+        const bool add = kmode == FDW_MODE_FWD_ILLUM || kmode == FDW_MODE_FWD_REC_ILLUM || kmode == FDW_MODE_FWD_LINE_ILLUM || kmode == FDW_MODE_FWD_LINE_REC_ILLUM;
+        const int gmode = kmode == FDW_MODE_FWD_ILLUM ? FDW_MODE_FWD
+                          : (kmode == FDW_MODE_FWD_REC_ILLUM ? FDW_MODE_FWD_REC
+                             : (kmode == FDW_MODE_FWD_LINE_ILLUM ? FDW_MODE_FWD_LINE : (kmode == FDW_MODE_FWD_LINE_REC_ILLUM ? FDW_MODE_FWD_LINE_REC : kmode)));
+        e = launch_step_generic(a, c->h, gmode, s);
         if (e == hipSuccess && add) e = launch_illum_add(d_pp, d_illum, c->pitch, a.r0, a.r1, c->upd_z1, s);
     }
     if (e != hipSuccess) return fail(FDW_EHIP, "kernel launch failed: %s", hipGetErrorString(e));
@@ -703,10 +714,10 @@ static int step2_impl(fdw_ctx* c, int mode, const float* d_p, const float* d_pp,
     const int chunks = (rows + xchunk - 1) / xchunk;
     a.nblk = a.nzblk * chunks;
     a.nper = (a.nblk + 7) / 8;
-    if (d_illum && (mode != FDW_MODE_FWD || d_rec)) return fail(FDW_EINVAL, "step2: illumination belongs to a plain forward pass");
+    if (d_illum && (mode != FDW_MODE_FWD || (d_rec && !line))) return fail(FDW_EINVAL, "step2: illumination belongs to a plain forward pass");
     const int kmode = line ? line_kmode(d_rec, d_illum) : ((mode == FDW_MODE_FWD && d_rec) ? FDW_MODE_FWD_REC : ((mode == FDW_MODE_FWD && d_illum) ? FDW_MODE_FWD_ILLUM : mode));
-    if (kmode == FDW_MODE_FWD_REC || kmode == FDW_MODE_FWD_LINE_REC) fill_rec(c, a, d_rec, rec_z);
-    if (kmode == FDW_MODE_FWD_ILLUM || kmode == FDW_MODE_FWD_LINE_ILLUM) a.img = d_illum;
+    if (kmode == FDW_MODE_FWD_REC || kmode == FDW_MODE_FWD_LINE_REC || kmode == FDW_MODE_FWD_LINE_REC_ILLUM) fill_rec(c, a, d_rec, rec_z);
+    if (kmode == FDW_MODE_FWD_ILLUM || kmode == FDW_MODE_FWD_LINE_ILLUM || kmode == FDW_MODE_FWD_LINE_REC_ILLUM) a.img = d_illum;
     hipError_t e = launch_step2(a, c->h, kmode, s);
     if (e != hipSuccess) return fail(FDW_EHIP, "step2 launch failed: %s", hipGetErrorString(e));
     return even_steps_tail(c, mode, a, s);
@@ -748,7 +759,7 @@ static void tile_classes(const Step2Args& a, int kmode, std::vector<unsigned cha
         const int xe = std::min(xa + a.xchunk, second ? a.r1b : a.r1);
         const int cs = zb * (64 - 2 * NS) - NS;
         const bool lean = kmode == FDW_MODE_PLAIN      ? pipe_tile_lean<H, NS, false, 0>(a, cs, xa, xe)
-                          : kmode == FDW_MODE_FWD_LINE_REC ? pipe_tile_lean<H, NS, true, 2, false, true>(a, cs, xa, xe)
+                          : (kmode == FDW_MODE_FWD_LINE_REC || kmode == FDW_MODE_FWD_LINE_REC_ILLUM) ? pipe_tile_lean<H, NS, true, 2, false, true>(a, cs, xa, xe)
                           : (kmode == FDW_MODE_FWD_LINE || kmode == FDW_MODE_FWD_LINE_ILLUM) ? pipe_tile_lean<H, NS, true, 2>(a, cs, xa, xe)
                                                            : pipe_tile_lean<H, NS, true, 1>(a, cs, xa, xe);
         cls[(size_t)L] = lean ? 0 : 1;
@@ -797,7 +808,7 @@ static int stepn_impl(fdw_ctx* c, int mode, const float* d_p, const float* d_pp,
     }
     Injection in;
     if (line) {               // FWD with d_inj -> the line samples of the pass's steps, [kPipeSteps][nx]
-        if (mode != FDW_MODE_FWD || !d_inj || (d_rec && d_illum)) return fail(FDW_EINVAL, "stepn: a line source drives a forward pass, plain, recording or accumulating");
+        if (mode != FDW_MODE_FWD || !d_inj) return fail(FDW_EINVAL, "stepn: a line source drives a forward pass");
         FDW_TRY(place_line(c, "stepn", inj_z, &in));
         a.inj_stride = c->nx;
     } else if (mode == FDW_MODE_FWD || mode == FDW_MODE_MOD) FDW_TRY(place_source(c, "stepn", mode == FDW_MODE_MOD, d_inj, inj_x_global, inj_z, &in));
@@ -821,8 +832,9 @@ static int stepn_impl(fdw_ctx* c, int mode, const float* d_p, const float* d_pp,
     const bool fwd = mode == FDW_MODE_FWD;
     const int kmode = line ? line_kmode(d_rec, d_illum)
                            : ((fwd && d_rec && d_illum) ? FDW_MODE_FWD_REC_ILLUM : ((fwd && d_rec) ? FDW_MODE_FWD_REC : ((fwd && d_illum) ? FDW_MODE_FWD_ILLUM : mode)));
-    if (kmode == FDW_MODE_FWD_REC || kmode == FDW_MODE_FWD_REC_ILLUM || kmode == FDW_MODE_FWD_LINE_REC) fill_rec(c, a, d_rec, rec_z);
-    if (kmode == FDW_MODE_FWD_ILLUM || kmode == FDW_MODE_FWD_REC_ILLUM || kmode == FDW_MODE_FWD_LINE_ILLUM) a.img = d_illum;
+    if (kmode == FDW_MODE_FWD_REC || kmode == FDW_MODE_FWD_REC_ILLUM || kmode == FDW_MODE_FWD_LINE_REC || kmode == FDW_MODE_FWD_LINE_REC_ILLUM)
+        fill_rec(c, a, d_rec, rec_z);
+    if (kmode == FDW_MODE_FWD_ILLUM || kmode == FDW_MODE_FWD_REC_ILLUM || kmode == FDW_MODE_FWD_LINE_ILLUM || kmode == FDW_MODE_FWD_LINE_REC_ILLUM) a.img = d_illum;
     a.inj = d_inj + in.shift; a.inj_x = in.x; a.inj_z = inj_z; a.inj_n = in.n;
     const int ncells = c->pitch / 4, own = 64 - 2 * kPipeSteps;
     a.nstrip = (ncells + own - 1) / own;
@@ -979,7 +991,9 @@ extern "C" int fdw_debug_step4_plan_line(fdw_ctx* c, int sz, int r0, int r1, int
 // passes, each through its kernel's illumination variant.  Both (fdw_dev_record_illum_steps): pipeline passes and single steps through the
 // combined kernels; there is no combined two-step kernel (a pair becomes two single steps), and every family equals the one-step iteration
 // bit for bit.  line (fdw_dev_line_steps): d_srce holds the line-source gather [it][nx] instead of the wavelet, sx is unused; the same family
-// per pass, the same rotation, the same static rows, each pass through its kernel's line-source variant.
+// per pass, the same rotation, the same static rows, each pass through its kernel's line-source variant.  line with both d_rec and d_illum
+// (fdw_dev_line_record_illum_steps): every family has its combined kernel, the two-step one included, so every pass is one launch.  Inside a
+// batch (c->nbatch > 1, one-step passes only) d_srce is the batch's [shot][nt][nx] and step_impl strides it per shot.
 // Trace samples of iterations it0 .. it0+nsteps-1 on the receiver rows the loop never time-steps (rows >= xlim of this slab): what the
 // reference's d_pp holds there, from the fields (d_p, d_pp) before the first swap
 static int record_static(fdw_ctx* c, const float* d_p, const float* d_pp, int gz, float* d_rec, int it0, int nsteps, hipStream_t s)
@@ -1014,7 +1028,7 @@ static int steps_loop(fdw_ctx* c, float* const* buf, const float* d_v2, const fl
                                 d_illum, line));
             *ip = o1; *ipp = o2;   // d_p = u^{n+kPipeSteps-1}, d_pp = u^{n+kPipeSteps}
             k += kPipeSteps;
-        } else if (nsteps - k >= 2 && two_step_pays(c) && d_rec && d_illum) {
+        } else if (nsteps - k >= 2 && two_step_pays(c) && d_rec && d_illum && !line) {
             // no combined two-step kernel: two single steps that land where the pair's pass would -- u^{n+1} in buf[o1], u^{n+2} in buf[o2],
             // the current pair left as it is --, each on a copy of the field it overwrites; the same fields, indices and static rows
             const size_t bytes = field_elems(c) * sizeof(float) * (size_t)std::max(c->nbatch, 1);
@@ -1136,9 +1150,9 @@ static int check_line_ctx(const fdw_ctx* c, const char* who)
     if (c->nbatch > 1) return fail(FDW_ESTATE, "%s: not inside a batch of shots", who);
     return FDW_OK;
 }
-static int check_line_args(const fdw_ctx* c, const char* who, int sz, int gz, bool rec, bool illum)
+static int check_line_args(const fdw_ctx* c, const char* who, int sz, int gz, bool rec, bool illum, bool both_built = false)
 {
-    if (rec && illum) return fail(FDW_EINVAL, "%s: trace recording and illumination together are not built for a line source", who);
+    if (rec && illum && !both_built) return fail(FDW_EINVAL, "%s: trace recording and illumination together are not built for a line source", who);
     if (sz < 0 || sz >= c->zlim) return fail(FDW_EINVAL, "%s: line-source depth %d outside the time-stepped columns [0,%d)", who, sz, c->zlim);
     if (rec) FDW_TRY(check_record_depth(c, gz));
     return FDW_OK;
@@ -1152,6 +1166,19 @@ extern "C" int fdw_dev_line_steps(fdw_ctx* c, float* const* d_buf, const float* 
     if (it0 < 0) return fail(FDW_EINVAL, "it0=%d", it0);
     FDW_TRY(check_line_args(c, "fdw_dev_line_steps", sz, gz, d_rec != nullptr, d_illum != nullptr));
     return steps_loop(c, d_buf, d_v2, d_wav, -1, sz, d_rec ? gz : 0, d_rec, it0, nsteps, first_pp_twice, ip, ipp, pick_stream(c, stream), d_illum, true);
+}
+
+// fdw_dev_line_steps that writes the trace rows and accumulates, one launch per pass: every family's combined line-source kernel
+extern "C" int fdw_dev_line_record_illum_steps(fdw_ctx* c, float* const* d_buf, const float* d_v2, const float* d_wav, int sz, int gz, float* d_rec,
+                                               float* d_illum, int it0, int nsteps, int first_pp_twice, int* ip, int* ipp, void* stream)
+{
+    if (!c || !d_wav) return fail(FDW_EINVAL, "NULL argument");
+    if (!d_rec || !d_illum)
+        return fail(FDW_EINVAL, "fdw_dev_line_record_illum_steps needs both d_rec and d_illum (one alone or neither: fdw_dev_line_steps)");
+    FDW_TRY(check_line_ctx(c, "fdw_dev_line_record_illum_steps"));
+    if (it0 < 0) return fail(FDW_EINVAL, "it0=%d", it0);
+    FDW_TRY(check_line_args(c, "fdw_dev_line_record_illum_steps", sz, gz, true, true, true));
+    return steps_loop(c, d_buf, d_v2, d_wav, -1, sz, gz, d_rec, it0, nsteps, first_pp_twice, ip, ipp, pick_stream(c, stream), d_illum, true);
 }
 
 // d_out[i] = d_a[i] - d_b[i] (fdw_gather_residual_kernel); d_out may be d_a
@@ -1718,6 +1745,19 @@ extern "C" int fdw_record_shot_line(fdw_ctx* c, const float* v2, int sz, int gz,
     return record_impl(c, v2, -1, sz, gz, nullptr, data, P, PP, wav);
 }
 
+// fdw_shot_line that migrates d_obs - d_mod, d_mod the gather its own forward loop records (fdw_record_shot_line's, bit for bit); with illum
+// the forward loop runs the combined line-source kernels
+extern "C" int fdw_shot_line_residual(fdw_ctx* c, const float* v2, int sz, int gz, const float* wav, const float* d_obs, float* imloc, float* illum,
+                                      float* resid, float* P, float* PP)
+{
+    if (!c || !wav) return fail(FDW_EINVAL, "NULL argument");
+    FDW_TRY(check_line_ctx(c, "fdw_shot_line_residual"));
+    if (!v2 && !c->v2_resident) return fail(FDW_ESTATE, "no resident squared model: call fdw_dev_extendvel_linear first");
+    FDW_TRY(check_line_args(c, "fdw_shot_line_residual", sz, gz, true, illum != nullptr, true));
+    if (v2) c->v2_resident = false;
+    return shot_impl(c, v2, -1, sz, gz, nullptr, d_obs, imloc, P, PP, illum, nullptr, true, resid, wav);
+}
+
 // The encoded data gather on the device (fdw_encode_gathers_kernel): every output element folds its shots in ascending order.
 extern "C" int fdw_encode_gathers(int device, int nshots, const int* lag, const float* weight, const float* d_obs_all, int nx, int nt, float* out)
 {
@@ -1740,6 +1780,39 @@ extern "C" int fdw_encode_gathers(int device, int nshots, const int* lag, const 
                              (e = hipMemcpy(d_lag, lag, tab, hipMemcpyHostToDevice)) != hipSuccess)) ||
              (e = launch_encode_gathers(d_in, d_lag, d_w, d_out, nshots, nx, nt, nullptr)) != hipSuccess || (e = hipMemcpy(out, d_out, gather, hipMemcpyDeviceToHost)) != hipSuccess)
         rc = fail(FDW_EHIP, "encode_gathers: %s", hipGetErrorString(e));
+    for (void* b : {(void*)d_in, (void*)d_out, (void*)d_w, (void*)d_lag})
+        if (b) (void)hipFree(b);
+    return rc;
+}
+
+// nplanes encodings of one data set: one upload of d_obs_all, one launch (fdw_encode_gathers_multi_kernel, blockIdx.y = the plane wave), one
+// download.  Every refusal comes before a device is opened.
+extern "C" int fdw_encode_gathers_multi(int device, int nshots, int nplanes, const int* lag, const float* weight, const float* d_obs_all, int nx, int nt,
+                                        float* out)
+{
+    if (nshots < 0 || nplanes < 1 || nplanes > 65535 || nx < 1 || nt < 1 || nx > 65535 || !out || (nshots > 0 && (!lag || !weight || !d_obs_all)))
+        return fail(FDW_EINVAL, "encode_gathers_multi: bad argument");
+    for (size_t i = 0; i < (size_t)nplanes * (size_t)nshots; i++)
+        if (lag[i] < 0) return fail(FDW_EINVAL, "encode_gathers_multi: lag[%zu][%zu]=%d is negative", i / (size_t)nshots, i % (size_t)nshots, lag[i]);
+    int ndev = 0;
+    hipError_t e = hipGetDeviceCount(&ndev);
+    if (e != hipSuccess || device < 0 || device >= ndev)
+        return fail(FDW_ENODEVICE, "encode_gathers_multi: no HIP device %d (%s); libfdwave has no CPU path", device,
+                    e != hipSuccess ? hipGetErrorString(e) : "out of range");
+    HIP_TRY(hipSetDevice(device));
+    const size_t gather = (size_t)nx * nt * sizeof(float), all = gather * (size_t)std::max(nshots, 1), outb = gather * (size_t)nplanes;
+    const size_t tab = (size_t)nplanes * (size_t)std::max(nshots, 1) * sizeof(int), used = (size_t)nplanes * (size_t)nshots * sizeof(int);
+    float *d_in = nullptr, *d_out = nullptr, *d_w = nullptr;
+    int* d_lag = nullptr;
+    int rc = FDW_OK;
+    if (hipMalloc((void**)&d_in, all) != hipSuccess || hipMalloc((void**)&d_out, outb) != hipSuccess || hipMalloc((void**)&d_w, tab) != hipSuccess ||
+        hipMalloc((void**)&d_lag, tab) != hipSuccess)
+        rc = fail(FDW_ENOMEM, "encode_gathers_multi: hipMalloc(%zu) failed", all + outb);
+    else if ((nshots > 0 && ((e = hipMemcpy(d_in, d_obs_all, all, hipMemcpyHostToDevice)) != hipSuccess || (e = hipMemcpy(d_w, weight, used, hipMemcpyHostToDevice)) != hipSuccess ||
+                             (e = hipMemcpy(d_lag, lag, used, hipMemcpyHostToDevice)) != hipSuccess)) ||
+             (e = launch_encode_gathers_multi(d_in, d_lag, d_w, d_out, nshots, nplanes, nx, nt, nullptr)) != hipSuccess ||
+             (e = hipMemcpy(out, d_out, outb, hipMemcpyDeviceToHost)) != hipSuccess)
+        rc = fail(FDW_EHIP, "encode_gathers_multi: %s", hipGetErrorString(e));
     for (void* b : {(void*)d_in, (void*)d_out, (void*)d_w, (void*)d_lag})
         if (b) (void)hipFree(b);
     return rc;
@@ -2489,10 +2562,14 @@ static int batch_interiors_to_host(fdw_ctx* c, float* h_dst, const float* d_src,
 // fdw_shot_batch (illum == NULL) and fdw_shot_batch_illum: illum [nshots][nx][nz] is accumulated into per shot by the forward loop
 // residual (fdw_shot_batch_residual): the forward loop records every shot's modelled gather into b_rec [shot][nt][nx], one launch turns the
 // batch's gathers into d_obs - d_mod in place before the backward loop; resid: NULL, or [nshots][nx][nt] that difference
+// wav_all (fdw_shot_line_batch and its kin): NULL, or the shots' line-source gathers [nshots][nx][nt] that drive the forward loop in place of
+// (sx0, dsx, srce): one more batch buffer, b_wav [shot][nt][nx], from which every forward launch takes a row per shot
 static int shot_batch_impl(fdw_ctx* c, const char* who, int nshots, const float* v2_all, unsigned long long draw_offset, int sx0, int dsx, int sz, int gz,
-                           const float* srce, const float* d_obs, float* imloc, float* illum, bool residual = false, float* resid = nullptr)
+                           const float* srce, const float* d_obs, float* imloc, float* illum, bool residual = false, float* resid = nullptr,
+                           const float* wav_all = nullptr)
 {
-    if (!c || !srce || !d_obs || !imloc) return fail(FDW_EINVAL, "NULL argument");
+    if (!c || (!srce && !wav_all) || !d_obs || !imloc) return fail(FDW_EINVAL, "NULL argument");
+    const bool line = wav_all != nullptr;
     if (nshots < 1) return fail(FDW_EINVAL, "nshots=%d", nshots);
     if (!is_full_grid(c)) return fail(FDW_EINVAL, "%s needs a full-grid context", who);
     if (c->nx <= 0 || c->nz <= 0) return fail(FDW_EINVAL, "no interior to image");
@@ -2500,15 +2577,15 @@ static int shot_batch_impl(fdw_ctx* c, const char* who, int nshots, const float*
     const int nt = c->prm.nt;
     const size_t ni = (size_t)c->nx * c->nz, ne = (size_t)c->prm.nxe * c->prm.nze, ng = (size_t)c->nx * nt, fe = field_elems(c);
     const int sx_last = sx0 + (nshots - 1) * dsx;
-    if (std::min(sx0, sx_last) < 0 || std::max(sx0, sx_last) >= c->prm.nxe || std::max(sx0, sx_last) >= c->upd_x1)
+    if (!line && (std::min(sx0, sx_last) < 0 || std::max(sx0, sx_last) >= c->prm.nxe || std::max(sx0, sx_last) >= c->upd_x1))
         return fail(FDW_EINVAL, "source rows %d..%d leave the rows the reference time-steps (< %d)", sx0, sx_last, c->upd_x1);
     HIP_TRY(hipSetDevice(c->device));
     const long long draws = fdw_border_draws(c->nx, c->nz, c->prm.nxb, c->prm.nzb);
     auto one_by_one = [&] {
         for (int b = 0; b < nshots; b++) {
             if (!v2_all) FDW_TRY(fdw_dev_extendvel_linear(c, draw_offset + (unsigned long long)b * draws, nullptr));
-            FDW_TRY(shot_impl(c, v2_all ? v2_all + b * ne : nullptr, sx0 + b * dsx, sz, gz, srce, d_obs + b * ng, imloc + b * ni, nullptr, nullptr,
-                              illum ? illum + b * ni : nullptr, nullptr, residual, resid ? resid + b * ng : nullptr));
+            FDW_TRY(shot_impl(c, v2_all ? v2_all + b * ne : nullptr, line ? -1 : sx0 + b * dsx, sz, gz, srce, d_obs + b * ng, imloc + b * ni, nullptr, nullptr,
+                              illum ? illum + b * ni : nullptr, nullptr, residual, resid ? resid + b * ng : nullptr, line ? wav_all + b * ng : nullptr));
         }
         return (int)FDW_OK;
     };
@@ -2518,7 +2595,8 @@ static int shot_batch_impl(fdw_ctx* c, const char* who, int nshots, const float*
     if ((rc = ensure_batch_buffers(c, nshots, true)) == FDW_ENOMEM) return one_by_one();      // no room for the batch
     if (!rc && illum && (rc = ensure_batch_illum(c, nshots)) == FDW_ENOMEM) return one_by_one();      // ... or for its accumulators
     if (!rc && residual && (rc = ensure_cap(&c->b_rec, &c->b_rec_cap, ng * nshots)) == FDW_ENOMEM) return one_by_one();      // ... or its modelled gathers
-    if (rc || (rc = upload_source(c, srce, nt))) return rc;
+    if (!rc && line && (rc = ensure_cap(&c->b_wav, &c->b_wav_cap, ng * nshots)) == FDW_ENOMEM) return one_by_one();      // ... or its line-source gathers
+    if (rc || (rc = line ? gathers_to_device(c, wav_all, c->b_wav, nshots) : upload_source(c, srce, nt))) return rc;
     hipStream_t s = c->stream;
     if ((rc = gathers_to_device(c, d_obs, c->b_dobs, nshots))) return rc;      // [shot][nx][nt] -> [shot][nt][nx]
     if ((rc = batch_models(c, nshots, v2_all, draw_offset))) return rc;
@@ -2526,10 +2604,10 @@ static int shot_batch_impl(fdw_ctx* c, const char* who, int nshots, const float*
     if ((rc = batch_interiors_to_device(c, c->b_img, imloc, nshots))) return rc;
     if (illum && (rc = batch_interiors_to_device(c, c->b_illum, illum, nshots))) return rc;
     {
-        BatchScope scope(c, nshots, dsx, illum != nullptr);
+        BatchScope scope(c, nshots, line ? 0 : dsx, illum != nullptr);
         int ip = 0, ipp = 1;
-        if ((rc = steps_loop(c, c->fld, c->d_v2, c->d_srce, sx0, sz, residual ? gz : 0, residual ? c->b_rec : nullptr, 0, nt, 0, &ip, &ipp, s,
-                             illum ? c->b_illum : nullptr)))
+        if ((rc = steps_loop(c, c->fld, c->d_v2, line ? c->b_wav : c->d_srce, line ? -1 : sx0, sz, residual ? gz : 0, residual ? c->b_rec : nullptr, 0, nt, 0,
+                             &ip, &ipp, s, illum ? c->b_illum : nullptr, line)))
             return rc;
         if (residual && (rc = gather_residual(c->d_dobs, c->b_rec, c->d_dobs, ng * nshots, s))) return rc;      // d_dobs: the batch's [shot][nt][nx]
         for (int b = 0; b < nshots && nt > 0; b++)
@@ -2551,6 +2629,15 @@ extern "C" int fdw_shot_batch(fdw_ctx* c, int nshots, const float* v2_all, unsig
     return shot_batch_impl(c, "fdw_shot_batch", nshots, v2_all, draw_offset, sx0, dsx, sz, gz, srce, d_obs, imloc, nullptr);
 }
 
+// How many shots of a batch go through at once: what the budget fdw_shot_batch_max counts with (6 GiB) holds of `fields` fields and `gathers`
+// gathers [nt][nx] per shot.  A larger batch goes through in parts of that size: the parts are independent, the bytes the same.
+static int batch_part(const fdw_ctx* c, int nshots, int fields, int gathers)
+{
+    const size_t ng = (size_t)c->nx * c->prm.nt;
+    const long by_mem = (long)(((size_t)6 << 30) / (((size_t)fields * field_elems(c) + (size_t)gathers * ng) * sizeof(float)));
+    return (int)std::max<long>(1, std::min<long>(by_mem, nshots));
+}
+
 // fdw_shot_batch whose forward loop also accumulates every shot's source illumination.  The batch holds one field more per shot than
 // fdw_shot_batch_max counts (11), so a batch larger than twelve fields per shot allow within the same budget goes through in parts of that
 // size: the parts are independent, the bytes the same.
@@ -2560,8 +2647,7 @@ extern "C" int fdw_shot_batch_illum(fdw_ctx* c, int nshots, const float* v2_all,
     if (!c || !illum) return fail(FDW_EINVAL, "NULL argument");
     FDW_TRY(check_illum_ctx(c, "fdw_shot_batch_illum"));
     if (nshots < 1) return fail(FDW_EINVAL, "nshots=%d", nshots);
-    const long by_mem = (long)(((size_t)6 << 30) / (12 * field_elems(c) * sizeof(float)));
-    const int part = (int)std::max<long>(1, std::min<long>(by_mem, nshots));
+    const int part = batch_part(c, nshots, 12, 0);
     const size_t ni = (size_t)c->nx * c->nz, ne = (size_t)c->prm.nxe * c->prm.nze, ng = (size_t)c->nx * c->prm.nt;
     const unsigned long long draws = (unsigned long long)fdw_border_draws(c->nx, c->nz, c->prm.nxb, c->prm.nzb);
     for (int b0 = 0; b0 < nshots; b0 += part) {
@@ -2583,8 +2669,7 @@ extern "C" int fdw_shot_batch_residual(fdw_ctx* c, int nshots, const float* v2_a
     FDW_TRY(check_record_depth(c, gz));
     if (nshots < 1) return fail(FDW_EINVAL, "nshots=%d", nshots);
     const size_t ni = (size_t)c->nx * c->nz, ne = (size_t)c->prm.nxe * c->prm.nze, ng = (size_t)c->nx * c->prm.nt;
-    const long by_mem = (long)(((size_t)6 << 30) / (((illum ? 12 : 11) * field_elems(c) + ng) * sizeof(float)));
-    const int part = (int)std::max<long>(1, std::min<long>(by_mem, nshots));
+    const int part = batch_part(c, nshots, illum ? 12 : 11, 1);
     const unsigned long long draws = (unsigned long long)fdw_border_draws(c->nx, c->nz, c->prm.nxb, c->prm.nzb);
     for (int b0 = 0; b0 < nshots; b0 += part) {
         const int nb = std::min(part, nshots - b0);
@@ -2595,12 +2680,49 @@ extern "C" int fdw_shot_batch_residual(fdw_ctx* c, int nshots, const float* v2_a
     return FDW_OK;
 }
 
+// ---- batches of line-source shots (definitions in fdwave.h) ----
+// fdw_shot_line (illum == NULL or not) / fdw_shot_line_residual for `nshots` shots: shot_batch_impl with the shots' line gathers in place of the
+// moving point source.  On top of fdw_shot_batch's eleven fields per shot the batch holds the line gathers, with illum the accumulators and
+// with residual the modelled gathers: parts by batch_part.
+static int shot_line_batch(fdw_ctx* c, const char* who, int nshots, const float* v2_all, unsigned long long draw_offset, int sz, int gz,
+                           const float* wav_all, const float* d_obs, float* imloc, float* illum, bool residual, float* resid)
+{
+    if (!c || !wav_all) return fail(FDW_EINVAL, "NULL argument");
+    FDW_TRY(check_line_ctx(c, who));
+    FDW_TRY(check_line_args(c, who, sz, gz, residual, illum != nullptr, true));
+    if (nshots < 1) return fail(FDW_EINVAL, "nshots=%d", nshots);
+    const size_t ni = (size_t)c->nx * c->nz, ne = (size_t)c->prm.nxe * c->prm.nze, ng = (size_t)c->nx * c->prm.nt;
+    const int part = batch_part(c, nshots, illum ? 12 : 11, residual ? 2 : 1);
+    const unsigned long long draws = (unsigned long long)fdw_border_draws(c->nx, c->nz, c->prm.nxb, c->prm.nzb);
+    for (int b0 = 0; b0 < nshots; b0 += part) {
+        const int nb = std::min(part, nshots - b0);
+        FDW_TRY(shot_batch_impl(c, who, nb, v2_all ? v2_all + b0 * ne : nullptr, draw_offset + b0 * draws, 0, 0, sz, gz, nullptr,
+                                d_obs ? d_obs + b0 * ng : nullptr, imloc ? imloc + b0 * ni : nullptr, illum ? illum + b0 * ni : nullptr, residual,
+                                resid ? resid + b0 * ng : nullptr, wav_all + b0 * ng));
+    }
+    return FDW_OK;
+}
+
+extern "C" int fdw_shot_line_batch(fdw_ctx* c, int nshots, const float* v2_all, unsigned long long draw_offset, int sz, int gz, const float* wav_all,
+                                   const float* d_obs, float* imloc, float* illum)
+{
+    return shot_line_batch(c, "fdw_shot_line_batch", nshots, v2_all, draw_offset, sz, gz, wav_all, d_obs, imloc, illum, false, nullptr);
+}
+
+extern "C" int fdw_shot_line_batch_residual(fdw_ctx* c, int nshots, const float* v2_all, unsigned long long draw_offset, int sz, int gz,
+                                            const float* wav_all, const float* d_obs, float* imloc, float* illum, float* resid)
+{
+    return shot_line_batch(c, "fdw_shot_line_batch_residual", nshots, v2_all, draw_offset, sz, gz, wav_all, d_obs, imloc, illum, true, resid);
+}
+
 // `nshots` recorded gathers (fdw_record_shot) through one launch per time step for the whole batch where batch_ok holds, one shot after the
 // other otherwise; models as fdw_shot_batch takes them.  data [nshots][nx][nt].
-extern "C" int fdw_record_shot_batch(fdw_ctx* c, int nshots, const float* v2_all, unsigned long long draw_offset, int sx0, int dsx, int sz, int gz,
-                                     const float* srce, float* data)
+// wav_all (fdw_record_shot_line_batch): NULL, or the shots' line-source gathers [nshots][nx][nt] in place of (sx0, dsx, srce)
+static int record_batch_impl(fdw_ctx* c, int nshots, const float* v2_all, unsigned long long draw_offset, int sx0, int dsx, int sz, int gz,
+                             const float* srce, float* data, const float* wav_all = nullptr)
 {
-    if (!c || !srce || !data) return fail(FDW_EINVAL, "NULL argument");
+    if (!c || (!srce && !wav_all) || !data) return fail(FDW_EINVAL, "NULL argument");
+    const bool line = wav_all != nullptr;
     if (nshots < 1) return fail(FDW_EINVAL, "nshots=%d", nshots);
     FDW_TRY(check_record_depth(c, gz));
     if (!is_full_grid(c)) return fail(FDW_EINVAL, "fdw_record_shot_batch needs a full-grid context");
@@ -2609,31 +2731,51 @@ extern "C" int fdw_record_shot_batch(fdw_ctx* c, int nshots, const float* v2_all
     const int nt = c->prm.nt;
     const size_t ne = (size_t)c->prm.nxe * c->prm.nze, ng = (size_t)c->nx * nt, fe = field_elems(c);
     const int sx_last = sx0 + (nshots - 1) * dsx;
-    if (std::min(sx0, sx_last) < 0 || std::max(sx0, sx_last) >= c->prm.nxe || std::max(sx0, sx_last) >= c->upd_x1)
+    if (!line && (std::min(sx0, sx_last) < 0 || std::max(sx0, sx_last) >= c->prm.nxe || std::max(sx0, sx_last) >= c->upd_x1))
         return fail(FDW_EINVAL, "source rows %d..%d leave the rows the reference time-steps (< %d)", sx0, sx_last, c->upd_x1);
     HIP_TRY(hipSetDevice(c->device));
     const long long draws = fdw_border_draws(c->nx, c->nz, c->prm.nxb, c->prm.nzb);
     auto one_by_one = [&] {
         for (int b = 0; b < nshots; b++) {
             if (!v2_all) FDW_TRY(fdw_dev_extendvel_linear(c, draw_offset + (unsigned long long)b * draws, nullptr));
-            FDW_TRY(record_impl(c, v2_all ? v2_all + b * ne : nullptr, sx0 + b * dsx, sz, gz, srce, data + b * ng, nullptr, nullptr));
+            FDW_TRY(record_impl(c, v2_all ? v2_all + b * ne : nullptr, line ? -1 : sx0 + b * dsx, sz, gz, srce, data + b * ng, nullptr, nullptr,
+                                line ? wav_all + b * ng : nullptr));
         }
         return (int)FDW_OK;
     };
     if (nshots == 1 || !batch_ok(c)) return one_by_one();
     int rc;
     if ((rc = ensure_batch_buffers(c, nshots, true)) == FDW_ENOMEM) return one_by_one();
-    if (rc || (rc = upload_source(c, srce, nt)) || (rc = batch_models(c, nshots, v2_all, draw_offset))) return rc;
+    if (!rc && line && (rc = ensure_cap(&c->b_wav, &c->b_wav_cap, ng * nshots)) == FDW_ENOMEM) return one_by_one();
+    if (rc || (rc = line ? gathers_to_device(c, wav_all, c->b_wav, nshots) : upload_source(c, srce, nt)) || (rc = batch_models(c, nshots, v2_all, draw_offset)))
+        return rc;
     hipStream_t s = c->stream;
     for (int i = 0; i < 2; i++) HIP_TRY(hipMemsetAsync(c->bfld[i], 0, fe * nshots * sizeof(float), s));    // R:496-497
     {
-        BatchScope scope(c, nshots, dsx);
+        BatchScope scope(c, nshots, line ? 0 : dsx);
         int ip = 0, ipp = 1;
-        if ((rc = steps_loop(c, c->fld, c->d_v2, c->d_srce, sx0, sz, gz, c->d_dobs, 0, nt, 0, &ip, &ipp, s))) return rc;      // d_dobs: the batch's [shot][nt][nx]
+        // d_dobs: the batch's [shot][nt][nx]
+        if ((rc = steps_loop(c, c->fld, c->d_v2, line ? c->b_wav : c->d_srce, line ? -1 : sx0, sz, gz, c->d_dobs, 0, nt, 0, &ip, &ipp, s, nullptr, line))) return rc;
     }
     if ((rc = gathers_to_host(c, c->b_dobs, nshots, data))) return rc;
     HIP_TRY(hipStreamSynchronize(s));
     return FDW_OK;
+}
+
+extern "C" int fdw_record_shot_batch(fdw_ctx* c, int nshots, const float* v2_all, unsigned long long draw_offset, int sx0, int dsx, int sz, int gz,
+                                     const float* srce, float* data)
+{
+    if (!srce) return fail(FDW_EINVAL, "NULL argument");
+    return record_batch_impl(c, nshots, v2_all, draw_offset, sx0, dsx, sz, gz, srce, data);
+}
+
+extern "C" int fdw_record_shot_line_batch(fdw_ctx* c, int nshots, const float* v2_all, unsigned long long draw_offset, int sz, int gz, const float* wav_all,
+                                          float* data)
+{
+    if (!c || !wav_all) return fail(FDW_EINVAL, "NULL argument");
+    FDW_TRY(check_line_ctx(c, "fdw_record_shot_line_batch"));
+    FDW_TRY(check_line_args(c, "fdw_record_shot_line_batch", sz, gz, true, false));
+    return record_batch_impl(c, nshots, v2_all, draw_offset, 0, 0, sz, gz, nullptr, data, wav_all);
 }
 
 // mod_main's shot loop (M:140-174) for `nshots` consecutive shots on its one velocity model, one launch per time step for all of them

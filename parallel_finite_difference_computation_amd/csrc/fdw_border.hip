@@ -184,6 +184,33 @@ hipError_t launch_encode_gathers(const float* d_in, const int* d_lag, const floa
     return hipGetLastError();
 }
 
+// fdw_encode_gathers_kernel for `nplanes` encodings of ONE resident data set (fdw_encode_gathers_multi): blockIdx.y is the plane wave, with its
+// own row of lags and weights [plane][nshots] and its own output gather [plane][nx][nt]; blockIdx.z is the receiver row.  Per output element the
+// same fold: ascending shot order from +0.0f, product and sum rounded separately, no atomics.
+__global__ __launch_bounds__(256) void fdw_encode_gathers_multi_kernel(const float* __restrict__ in, const int* __restrict__ lag, const float* __restrict__ w,
+                                                                       float* __restrict__ out, int nshots, int nx, int nt)
+{
+    const int it = blockIdx.x * 256 + threadIdx.x, plane = blockIdx.y, ix = blockIdx.z;
+    if (it >= nt) return;
+    const size_t row = (size_t)ix * nt, shot = (size_t)nx * nt;
+    const int* pl = lag + (size_t)plane * nshots;
+    const float* pw = w + (size_t)plane * nshots;
+    float acc = 0.0f;
+    for (int s = 0; s < nshots; s++) {
+        const long long src = (long long)it - pl[s];
+        if (src >= 0 && src < nt) acc = __fadd_rn(acc, __fmul_rn(pw[s], in[(size_t)s * shot + row + (size_t)src]));
+    }
+    out[(size_t)plane * shot + row + it] = acc;
+}
+
+hipError_t launch_encode_gathers_multi(const float* d_in, const int* d_lag, const float* d_w, float* d_out, int nshots, int nplanes, int nx, int nt,
+                                       hipStream_t s)
+{
+    if (nx <= 0 || nt <= 0 || nplanes <= 0) return hipSuccess;
+    hipLaunchKernelGGL(fdw_encode_gathers_multi_kernel, dim3((nt + 255) / 256, nplanes, nx), dim3(256), 0, s, d_in, d_lag, d_w, d_out, nshots, nx, nt);
+    return hipGetLastError();
+}
+
 hipError_t launch_gather_residual(const float* d_a, const float* d_b, float* d_out, size_t n, hipStream_t s)
 {
     if (n == 0) return hipSuccess;

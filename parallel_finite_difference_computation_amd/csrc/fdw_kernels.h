@@ -21,6 +21,7 @@ enum {
                             // (fdw_dev_line_steps; multi-step kernels: level k takes inj + k * inj_stride)
     FDW_MODE_FWD_LINE_REC = 14,   // ... + the trace samples, written after the injection
     FDW_MODE_FWD_LINE_ILLUM = 15, // ... + the source illumination, accumulated after the injection
+    FDW_MODE_FWD_LINE_REC_ILLUM = 16, // ... + both in one launch (fdw_dev_line_record_illum_steps, fdw_shot_line_residual with an accumulator)
     FDW_MODE_DD_RECV = 6 // its receiver pass (rtm_main.cpp:197-220) + img += stored source field * CURRENT receiver field (rtm_main.cpp:224-230)
 };
 
@@ -192,5 +193,8 @@ hipError_t launch_gather_transpose(const float* d_in, float* d_out, int nx, int 
 hipError_t launch_gather_residual(const float* d_a, const float* d_b, float* d_out, size_t n, hipStream_t s);
 // encoded data gather (fdw_encode_gathers_kernel): d_out[ix][it] = the fold over s ascending, 0 <= it - lag[s] < nt, of acc + w[s] * d_in[s][ix][it - lag[s]]
 hipError_t launch_encode_gathers(const float* d_in, const int* d_lag, const float* d_w, float* d_out, int nshots, int nx, int nt, hipStream_t s);
+// the same fold for nplanes encodings of one resident data set (fdw_encode_gathers_multi_kernel): d_lag, d_w [nplanes][nshots], d_out [nplanes][nx][nt]
+hipError_t launch_encode_gathers_multi(const float* d_in, const int* d_lag, const float* d_w, float* d_out, int nshots, int nplanes, int nx, int nt,
+                                       hipStream_t s);
 
 }  // namespace fdw

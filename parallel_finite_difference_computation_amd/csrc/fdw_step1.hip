@@ -513,6 +513,36 @@ __global__ __launch_bounds__(256) void fdw_step_line_kernel(const StepArgs a)
     march<H, true, 2, false, false, PF, false, false, NUM, REC, ILL>(a, sv, lane, zs, xa, xe);
 }
 
+// the line-source step that records its trace samples AND accumulates the source illumination (FDW_MODE_FWD_LINE_REC_ILLUM: the forward loop of
+// fdw_shot_line_residual with an accumulator, fdw_dev_line_record_illum_steps): fdw_step_rec_illum_kernel with INJ = 2 -- sample and square are
+// the stored new field, line sample included.  A kernel of its own name, as the point source's combined kernel is, with its own copy of the
+// tile placement.
+template <int H, int PF, int NUM>
+__global__ __launch_bounds__(256) void fdw_step_line_rec_illum_kernel(const StepArgs a)
+{
+    const int shot = blockIdx.y;
+    const long long o = shot * a.bstride;
+    const ShotView sv{a.p + o, a.pp + o, (a.out ? a.out : a.pp) + o, a.v2 + shot * a.v2_bstride, a.psrc + o, a.fpp + o, a.img + o, a.inj + shot * a.inj_bstride,
+                      a.inj_x + shot * a.inj_dx, a.rec + shot * a.rec_bstride};
+    const int lane = threadIdx.x & 63;
+    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+
+    const int bid = blockIdx.x;
+    const int L = (bid & 7) * a.nper + (bid >> 3);
+    if (L >= a.nblk) return;
+    const int zb = L % a.nzblk;
+    const int xb = L / a.nzblk;
+    const int wz = a.wz;
+    const int strip = zb * wz + (w & (wz - 1));
+    const int chunk = xb * (4 / wz) + (w / wz);
+    const int zs = strip * 256;
+    if (zs >= a.pitch) return;
+    const int xa = a.r0 + chunk * a.xchunk;
+    const int xe = min(xa + a.xchunk, a.r1);
+    if (xa >= xe) return;
+    march<H, true, 2, false, false, PF, false, false, NUM, true, true>(a, sv, lane, zs, xa, xe);
+}
+
 #if FDW_TU == 0
 // ------------------------------------------------------------------------------------------------
 // generic-order kernel: any even order up to FDW_MAX_ORDER, one thread per point, every tap from
@@ -714,6 +744,7 @@ static hipError_t launch_fast_hp(const StepArgs& a, int mode, hipStream_t s)
     case FDW_MODE_FWD_LINE: hipLaunchKernelGGL((fdw_step_line_kernel<H, PF, false, false, 0>), grid, block, 0, s, a); break;
     case FDW_MODE_FWD_LINE_REC: hipLaunchKernelGGL((fdw_step_line_kernel<H, PF, true, false, 0>), grid, block, 0, s, a); break;
     case FDW_MODE_FWD_LINE_ILLUM: hipLaunchKernelGGL((fdw_step_line_kernel<H, PF, false, true, 0>), grid, block, 0, s, a); break;
+    case FDW_MODE_FWD_LINE_REC_ILLUM: hipLaunchKernelGGL((fdw_step_line_rec_illum_kernel<H, PF, 0>), grid, block, 0, s, a); break;
     default: return hipErrorInvalidValue;
     }
     return hipGetLastError();
@@ -807,6 +838,7 @@ static hipError_t launch_fastnum_h(const StepArgs& a, int mode, hipStream_t s)
     case FDW_MODE_FWD_LINE: hipLaunchKernelGGL((fdw_step_line_kernel<H, 2, false, false, 1>), grid, block, 0, s, a); break;
     case FDW_MODE_FWD_LINE_REC: hipLaunchKernelGGL((fdw_step_line_kernel<H, 2, true, false, 1>), grid, block, 0, s, a); break;
     case FDW_MODE_FWD_LINE_ILLUM: hipLaunchKernelGGL((fdw_step_line_kernel<H, 2, false, true, 1>), grid, block, 0, s, a); break;
+    case FDW_MODE_FWD_LINE_REC_ILLUM: hipLaunchKernelGGL((fdw_step_line_rec_illum_kernel<H, 2, 1>), grid, block, 0, s, a); break;
     default: return hipErrorInvalidValue;
     }
     return hipGetLastError();

@@ -348,6 +348,29 @@ __global__ __launch_bounds__(256, ILL ? 2 : 3) void fdw_step2_line_kernel(const 
     }
 }
 
+// FDW_MODE_FWD_LINE_REC_ILLUM: the line-source pass that records the trace samples of both steps AND accumulates their illumination
+// (fdw_dev_line_record_illum_steps, fdw_shot_line_residual with an accumulator).  The LDS slabs and the two workgroups per CU of
+// fdw_step2_illum_kernel, which leave the body 256 VGPRs; its own tile placement and its own name, as the point source's combined kernels have.
+template <int NUM>
+__global__ __launch_bounds__(256, 2) void fdw_step2_line_rec_illum_kernel(const Step2Args a)
+{
+    const int lane = threadIdx.x & 63;
+    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int bid = blockIdx.x;
+    const int L = (bid & 7) * a.nper + (bid >> 3);
+    if (L >= a.nblk) return;
+    const int zb = L % a.nzblk;
+    const int xb = L / a.nzblk;
+    const int strip = zb * 4 + w;
+    if (strip >= a.nstrip) return;
+    const int xa = a.r0 + xb * a.xchunk;
+    const int xe = min(xa + a.xchunk, a.r1);
+    if (xa >= xe) return;
+    __shared__ f4 v2_stash[4][8 * 64];
+    __shared__ f4 ill_stash[4][8 * 64];
+    march2<4, true, 2, false, 2, NUM, true, true>(a, lane, strip * 60 - 2, xa, xe, v2_stash[w], ill_stash[w]);
+}
+
 hipError_t launch_step2(const Step2Args& a, int h, int mode, hipStream_t s)
 {
     if (a.nper <= 0) return hipSuccess;
@@ -363,6 +386,7 @@ hipError_t launch_step2(const Step2Args& a, int h, int mode, hipStream_t s)
         case FDW_MODE_FWD_LINE: hipLaunchKernelGGL((fdw_step2_line_kernel<false, false, 1>), grid, block, 0, s, a); break;
         case FDW_MODE_FWD_LINE_REC: hipLaunchKernelGGL((fdw_step2_line_kernel<true, false, 1>), grid, block, 0, s, a); break;
         case FDW_MODE_FWD_LINE_ILLUM: hipLaunchKernelGGL((fdw_step2_line_kernel<false, true, 1>), grid, block, 0, s, a); break;
+        case FDW_MODE_FWD_LINE_REC_ILLUM: hipLaunchKernelGGL((fdw_step2_line_rec_illum_kernel<1>), grid, block, 0, s, a); break;
         default: return hipErrorInvalidValue;
         }
         return hipGetLastError();
@@ -376,6 +400,7 @@ hipError_t launch_step2(const Step2Args& a, int h, int mode, hipStream_t s)
     case FDW_MODE_FWD_LINE: hipLaunchKernelGGL((fdw_step2_line_kernel<false, false, 0>), grid, block, 0, s, a); break;
     case FDW_MODE_FWD_LINE_REC: hipLaunchKernelGGL((fdw_step2_line_kernel<true, false, 0>), grid, block, 0, s, a); break;
     case FDW_MODE_FWD_LINE_ILLUM: hipLaunchKernelGGL((fdw_step2_line_kernel<false, true, 0>), grid, block, 0, s, a); break;
+    case FDW_MODE_FWD_LINE_REC_ILLUM: hipLaunchKernelGGL((fdw_step2_line_rec_illum_kernel<0>), grid, block, 0, s, a); break;
     default: return hipErrorInvalidValue;
     }
     return hipGetLastError();

@@ -523,6 +523,37 @@ __global__ __launch_bounds__(64 * kPipeSteps, ILL ? 3 : (REC ? kDDWG : kPipeWG))
     }
 }
 
+// FDW_MODE_FWD_LINE_REC_ILLUM: the line-source pass that records the trace samples of its kPipeSteps steps AND accumulates their illumination
+// (fdw_dev_line_record_illum_steps, fdw_shot_line_residual with an accumulator): fdw_stepn_rec_illum_kernel with INJ = 2.  The tiles of the
+// strip that holds the line, of the strip whose owned lanes hold the receiver column, on the frame and in the damped strip run the full body,
+// in which wave k injects, records row k of the pass and squares, in that order; all others run fdw_stepn_illum_kernel's lean bodies.  48 KiB
+// of LDS, three workgroups per CU.  Its own tile placement and its own name (see fdw_stepn_rec_kernel).
+template <int NUM>
+__global__ __launch_bounds__(64 * kPipeSteps, 3) void fdw_stepn_line_rec_illum_kernel(const Step2Args a)
+{
+    constexpr int H = 4, NS = kPipeSteps, PF = kPipePF;
+    const int lane = threadIdx.x & 63;
+    const int k = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int bid = blockIdx.x;
+    const int L = (bid & 7) * a.nper + (bid >> 3);
+    if (L >= a.nblk) return;
+    const int zb = L % a.nstrip;
+    const int xb = L / a.nstrip;
+    const bool second = xb >= a.chunks_a;
+    const int xa = second ? a.r0b + (xb - a.chunks_a) * a.xchunk : a.r0 + xb * a.xchunk;
+    const int xe = min(xa + a.xchunk, second ? a.r1b : a.r1);
+    if (xa >= xe) return;
+    __shared__ f4 link[NS][2][2][64];
+    __shared__ f4 fifo[pipe_fifo_rows(NS, H)][64];
+    __shared__ f4 ilf[16][64];
+    const int cs = zb * (64 - 2 * NS) - NS;
+    if (pipe_lean<H, NS, true, 2, false, true>(a, cs, xa, xe)) {
+        if (k == 0) marchn<H, NS, false, 0, PF, false, 0, true, 1, NUM, false, true>(a, lane, k, cs, xa, xe, link, fifo, ilf);
+        else marchn<H, NS, false, 0, PF, false, 0, true, 2, NUM, false, true>(a, lane, k, cs, xa, xe, link, fifo, ilf);
+    }
+    else marchn<H, NS, true, 2, PF, false, 0, false, 0, NUM, true, true>(a, lane, k, cs, xa, xe, link, fifo, ilf);
+}
+
 // Four iterations of the backward loop in ONE pass: a workgroup of eight waves, waves 0-3 the pipeline of the source field (role 3), waves 4-7
 // the pipeline of the receiver field one march step behind (role 4).  The source-field levels never leave the chip: the receiver wave of
 // level k reads F_{it+k}(row) from the link buffer the source-field wave k wrote it to for its own successor.  6 fields in + 5 out per
@@ -579,6 +610,7 @@ hipError_t launch_stepn(const Step2Args& a, int h, int mode, hipStream_t s)
         case FDW_MODE_FWD_LINE: hipLaunchKernelGGL((fdw_stepn_line_kernel<false, false, 1>), grid, block, 0, s, a); break;
         case FDW_MODE_FWD_LINE_REC: hipLaunchKernelGGL((fdw_stepn_line_kernel<true, false, 1>), grid, block, 0, s, a); break;
         case FDW_MODE_FWD_LINE_ILLUM: hipLaunchKernelGGL((fdw_stepn_line_kernel<false, true, 1>), grid, block, 0, s, a); break;
+        case FDW_MODE_FWD_LINE_REC_ILLUM: hipLaunchKernelGGL((fdw_stepn_line_rec_illum_kernel<1>), grid, block, 0, s, a); break;
         case FDW_MODE_PLAIN: hipLaunchKernelGGL((fdw_stepn_kernel<4, kPipeSteps, false, 0, kPipePF, false, 0, 1>), grid, block, 0, s, a); break;
         case FDW_MODE_MOD:   hipLaunchKernelGGL((fdw_stepn_kernel<4, kPipeSteps, true, 3, kPipePF, true, 0, 1>), grid, block, 0, s, a); break;
         case FDW_MODE_PLAIN_ALL: hipLaunchKernelGGL((fdw_stepn_kernel<4, kPipeSteps, false, 0, kPipePF, false, 1, 1>), grid, block, 0, s, a); break;
@@ -596,6 +628,7 @@ hipError_t launch_stepn(const Step2Args& a, int h, int mode, hipStream_t s)
     case FDW_MODE_FWD_LINE: hipLaunchKernelGGL((fdw_stepn_line_kernel<false, false, 0>), grid, block, 0, s, a); break;
     case FDW_MODE_FWD_LINE_REC: hipLaunchKernelGGL((fdw_stepn_line_kernel<true, false, 0>), grid, block, 0, s, a); break;
     case FDW_MODE_FWD_LINE_ILLUM: hipLaunchKernelGGL((fdw_stepn_line_kernel<false, true, 0>), grid, block, 0, s, a); break;
+    case FDW_MODE_FWD_LINE_REC_ILLUM: hipLaunchKernelGGL((fdw_stepn_line_rec_illum_kernel<0>), grid, block, 0, s, a); break;
     case FDW_MODE_PLAIN: hipLaunchKernelGGL((fdw_stepn_kernel<4, kPipeSteps, false, 0, kPipePF>), grid, block, 0, s, a); break;
     case FDW_MODE_MOD:   hipLaunchKernelGGL((fdw_stepn_kernel<4, kPipeSteps, true, 3, kPipePF, true>), grid, block, 0, s, a); break;
     case FDW_MODE_PLAIN_ALL: hipLaunchKernelGGL((fdw_stepn_kernel<4, kPipeSteps, false, 0, kPipePF, false, 1>), grid, block, 0, s, a); break;

@@ -237,6 +237,23 @@ static int write_illum_outputs(const char *tmpdir, const float *img, const float
     return 0;
 }
 
+/* pw=NP: the ray parameter of plane wave j, and its image stacked into img (and ill) and printed, exactly as the shot loop does per shot */
+static double pw_ray(int pw, float pw_pmax, int j)
+{
+    return pw == 1 ? 0.0 : -(double)pw_pmax + 2.0 * (double)pw_pmax * (double)j / (double)(pw - 1);
+}
+static void pw_stack(FILE *fnum, int j, double p, int depth, int nx, int nz, float *img, const float *imloc, float *ill, const float *illoc)
+{
+    fprintf(stdout, "** plane wave %d, p = %g s/m, depth %d \n\n** backward propagation %d \n\n", j + 1, p, depth, j + 1);
+    fprintf(fnum, "======== %i ========\n", j);
+    for (int iz = 0; iz < nz; iz++)
+        for (int ix = 0; ix < nx; ix++) {
+            img[(size_t)ix * nz + iz] += imloc[(size_t)ix * nz + iz];
+            fprintf(fnum, " %f \n", img[(size_t)ix * nz + iz]);
+            if (ill) ill[(size_t)ix * nz + iz] += illoc[(size_t)ix * nz + iz];
+        }
+}
+
 static double now_s(void)
 {
     struct timeval t;
@@ -447,46 +464,61 @@ int main(int argc, char **argv)
     }
     int shots_per_launch = 1;      /* FDW_TIMING: how many shots advance through one launch per time step */
     if (pw > 0) {
-        /* ---- pw=NP: NP encoded gathers, each migrated with a delayed line of sources (fdw_shot_line) ---- */
+        /* ---- pw=NP: NP encoded gathers, each migrated with a delayed line of sources (fdw_shot_line).  On decks where shots batch
+         * (fdw_shot_batch_max > 1) the plane waves do too: all data gathers encoded in one pass (fdw_encode_gathers_multi), the line gathers
+         * and the models built in the order j, then fdw_shot_batch_max plane waves per launch sequence (fdw_shot_line_batch); stacked
+         * and printed in the order j either way.  FDW_NO_SHOT_BATCH=1 keeps one plane wave after the other. ---- */
         const int dev_models = !vel_ext_flag && !getenv("FDW_HOST_BORDER") && nxb != 1 && nzb != 1 && nzb <= nxe;      /* as dev_border below */
         const long long draws = fdw_border_draws(nx, nz, nxb, nzb);
         const size_t ng = (size_t)nx * nt;
         fdw_ctx *ctx = NULL;
-        int *src_ix = (int *)malloc((size_t)ns * sizeof(int)), *lag = (int *)malloc((size_t)ns * sizeof(int));
-        float *weight = (float *)malloc((size_t)ns * sizeof(float)), *wav = (float *)malloc(ng * sizeof(float)), *enc = (float *)malloc(ng * sizeof(float));
-        float *v2 = (float *)malloc(ne * sizeof(float)), *imloc = (float *)malloc(ni * sizeof(float));
-        float *illoc = illum ? (float *)malloc(ni * sizeof(float)) : NULL, *ill = illum ? (float *)calloc(ni, sizeof(float)) : NULL;
-        if (!src_ix || !lag || !weight || !wav || !enc || !v2 || !imloc || (illum && (!illoc || !ill))) {
+        int *src_ix = (int *)malloc((size_t)ns * sizeof(int));
+        float *ill = illum ? (float *)calloc(ni, sizeof(float)) : NULL;
+        if (!src_ix || (illum && !ill)) {
             fprintf(stderr, "out of host memory\n");
             return EXIT_FAILURE;
         }
-        for (int is = 0; is < ns; is++) {
-            src_ix[is] = fsx + is * ds;
-            weight[is] = 1.0f;
-        }
+        for (int is = 0; is < ns; is++) src_ix[is] = fsx + is * ds;
         if (fdw_create(&prm, 0, &ctx) != FDW_OK || (dev_models && fdw_model_resident(ctx, vp) != FDW_OK)) {
             fprintf(stderr, "fdw_create: %s\n", fdw_last_error());
             return EXIT_FAILURE;
         }
+        int pw_bmax = (pw > 1 && !getenv("FDW_NO_SHOT_BATCH")) ? fdw_shot_batch_max(ctx) : 1;
+        if (pw_bmax > pw) pw_bmax = pw;
+        shots_per_launch = pw_bmax;
+        const int nb = pw_bmax > 1 ? pw : 1;      /* plane waves held on the host at a time */
+        int *lag = (int *)malloc((size_t)nb * ns * sizeof(int));
+        float *weight = (float *)malloc((size_t)nb * ns * sizeof(float)), *wav = (float *)malloc((size_t)nb * ng * sizeof(float));
+        float *enc = (float *)malloc((size_t)nb * ng * sizeof(float)), *imloc = (float *)calloc((size_t)nb * ni, sizeof(float));
+        float *v2 = (float *)malloc((dev_models ? 1 : (size_t)nb) * ne * sizeof(float)), *illoc = illum ? (float *)calloc((size_t)nb * ni, sizeof(float)) : NULL;
+        if (!lag || !weight || !wav || !enc || !v2 || !imloc || (illum && !illoc)) {
+            fprintf(stderr, "out of host memory\n");
+            return EXIT_FAILURE;
+        }
+        for (size_t k = 0; k < (size_t)nb * ns; k++) weight[k] = 1.0f;
         const double t0 = now_s();
         for (int j = 0; j < pw; j++) {
-            const double p = pw == 1 ? 0.0 : -(double)pw_pmax + 2.0 * (double)pw_pmax * (double)j / (double)(pw - 1);
-            if (fdw_planewave_lags(ns, src_ix, dx, dt, p, lag) != FDW_OK || fdw_encode_line_source(ns, src_ix, lag, weight, srce, nt, nx, wav) != FDW_OK) {
+            const int slot = pw_bmax > 1 ? j : 0;
+            const double p = pw_ray(pw, pw_pmax, j);
+            if (fdw_planewave_lags(ns, src_ix, dx, dt, p, lag + (size_t)slot * ns) != FDW_OK ||
+                fdw_encode_line_source(ns, src_ix, lag + (size_t)slot * ns, weight, srce, nt, nx, wav + (size_t)slot * ng) != FDW_OK) {
                 fprintf(stderr, "plane wave %d (p = %g s/m): the shot rows fsx + is ds must lie in [0, nx) and the lags p (row - first row) dx / dt must be finite\n",
                         j + 1, p);
                 return EXIT_FAILURE;
             }
-            int rc = fdw_encode_gathers(0, ns, lag, weight, d_obs, nx, nt, enc);
             const float *model = NULL;      /* NULL: the squared model drawn in HBM */
-            if (rc == FDW_OK && dev_models) {
-                rc = fdw_dev_extendvel_linear(ctx, (unsigned long long)j * (unsigned long long)draws, NULL);      /* R:486: the next draw of the stream */
-            } else if (rc == FDW_OK) {
+            if (!dev_models) {
                 const float *v = vpe;
+                float *dst = v2 + (size_t)slot * ne;
                 if (vel_ext_flag) v = vel_ext_rnd + (size_t)(j % ns) * ne;      /* R:484 */
-                else fdw_extendvel_linear(nx, nz, nxb, nzb, vpe);               /* R:486 */
-                for (size_t k = 0; k < ne; k++) v2[k] = v[k] * v[k];             /* R:490-494 */
-                model = v2;
+                else fdw_extendvel_linear(nx, nz, nxb, nzb, vpe);               /* R:486: the next draws of the one stream, in the order j */
+                for (size_t k = 0; k < ne; k++) dst[k] = v[k] * v[k];            /* R:490-494 */
+                model = dst;
             }
+            if (pw_bmax > 1) continue;      /* batched: migrated below */
+            int rc = fdw_encode_gathers(0, ns, lag, weight, d_obs, nx, nt, enc);
+            if (rc == FDW_OK && dev_models)
+                rc = fdw_dev_extendvel_linear(ctx, (unsigned long long)j * (unsigned long long)draws, NULL);      /* R:486: the next draw of the stream */
             memset(imloc, 0, ni * sizeof(float));                                /* R:515 */
             if (illum) memset(illoc, 0, ni * sizeof(float));
             if (rc == FDW_OK) rc = fdw_shot_line(ctx, model, sz, gz, wav, enc, imloc, illoc, NULL, NULL);
@@ -494,14 +526,21 @@ int main(int argc, char **argv)
                 fprintf(stderr, "plane wave %d: %s\n", j + 1, fdw_last_error());
                 return EXIT_FAILURE;
             }
-            fprintf(stdout, "** plane wave %d, p = %g s/m, depth %d \n\n** backward propagation %d \n\n", j + 1, p, sz - nzb, j + 1);
-            fprintf(fnum, "======== %i ========\n", j);
-            for (int iz = 0; iz < nz; iz++)
-                for (int ix = 0; ix < nx; ix++) {
-                    img[(size_t)ix * nz + iz] += imloc[(size_t)ix * nz + iz];
-                    fprintf(fnum, " %f \n", img[(size_t)ix * nz + iz]);
-                    if (illum) ill[(size_t)ix * nz + iz] += illoc[(size_t)ix * nz + iz];
-                }
+            pw_stack(fnum, j, p, sz - nzb, nx, nz, img, imloc, ill, illoc);
+        }
+        if (pw_bmax > 1) {
+            int rc = fdw_encode_gathers_multi(0, ns, pw, lag, weight, d_obs, nx, nt, enc);
+            for (int j0 = 0; rc == FDW_OK && j0 < pw; j0 += pw_bmax) {
+                const int n = pw - j0 < pw_bmax ? pw - j0 : pw_bmax;
+                rc = fdw_shot_line_batch(ctx, n, dev_models ? NULL : v2 + (size_t)j0 * ne, (unsigned long long)j0 * (unsigned long long)draws, sz, gz,
+                                         wav + (size_t)j0 * ng, enc + (size_t)j0 * ng, imloc + (size_t)j0 * ni, illum ? illoc + (size_t)j0 * ni : NULL);
+            }
+            if (rc != FDW_OK) {
+                fprintf(stderr, "fdw_shot_line_batch: %s\n", fdw_last_error());
+                return EXIT_FAILURE;
+            }
+            for (int j = 0; j < pw; j++)
+                pw_stack(fnum, j, pw_ray(pw, pw_pmax, j), sz - nzb, nx, nz, img, imloc + (size_t)j * ni, ill, illum ? illoc + (size_t)j * ni : NULL);
         }
         t_shots = now_s() - t0;
         fdw_destroy(ctx);
@@ -745,7 +784,7 @@ int main(int argc, char **argv)
 outputs:
     if (timing)
         fprintf(stderr, "[timing] shots per launch sequence: up to %d (%s)\n", shots_per_launch,
-                shots_per_launch > 1 ? (resid ? "fdw_shot_batch_residual" : (illum ? "fdw_shot_batch_illum" : "fdw_shot_batch"))
+                shots_per_launch > 1 ? (pw > 0 ? "fdw_shot_line_batch" : (resid ? "fdw_shot_batch_residual" : (illum ? "fdw_shot_batch_illum" : "fdw_shot_batch")))
                                      : (resid ? "one by one, fdw_shot_residual" : "one by one"));
     if (timing)
         fprintf(stderr, "[timing] total %.3f s: shots (contexts, border models, propagation) %.3f s, stacking + image.num %.3f s, rest (deck, inputs) %.3f s\n",
