@@ -132,6 +132,19 @@ int fdw_shot(fdw_ctx *ctx, const float *v2, int sx, int sz, int gz, const float 
 /* ---- device-array entry points (benchmarks, multi-GPU drivers; asynchronous on `stream`) -------
  * Buffers are caller-owned device memory laid out [nxl][fdw_pitch()] (e.g. a torch tensor).
  *
+ * THE STREAM CONTRACT of every entry point that takes a `stream` (pinned by tests/test_stream_contract.py):
+ *   stream == NULL  the context's own stream, created with hipStreamNonBlocking.  It has NO implicit ordering against any stream of the
+ *                   caller's, the legacy default stream included: what filled the buffers must have COMPLETED before the call (the caller
+ *                   synchronised, or waited for an event on the host), and the results are complete only once the device (or, for the
+ *                   host-array entry points, the call itself) has synchronised.  A fill queued on a torch stream and not waited for races
+ *                   with the kernels here.
+ *   stream != NULL  a hipStream_t of the caller's.  EVERY kernel launch, device copy and memset of the call is issued on that stream, in
+ *                   order, and the call returns without synchronising: it sees whatever was queued on the stream before it -- a producer that
+ *                   has not run yet included -- and work queued on the stream after it sees its results.  Nothing is issued on the context's
+ *                   own stream, and no other stream or event is involved.  Chained calls on one stream need no host synchronisation in between.
+ *                   The ONE exception is fdw_dev_check_field, which issues its check on the stream and then synchronises it to return the count.
+ *   Host arguments (pointers to ip / ipp, role[], scalars) are read and written before the call returns.
+ *
  * PRECONDITION of every entry point that takes wavefields (host or device) on a context with compat = 1 and nxe not a multiple of 8:
  * inside the damped strip (columns < 8*floor(nzb/8)) the rows the reference never time-steps (>= 8*floor(nxe/8)) must be ZERO.  The
  * reference damps those rows with taperx every step although nothing ever rewrites them (R:94-117 with the grids of R:185-195); the kernels
@@ -176,7 +189,9 @@ int fdw_shot(fdw_ctx *ctx, const float *v2, int sx, int sz, int gz, const float 
  *                 source fields are the two snapshots, R:304-314) d_f1 is used as it stands and d_f0 is ignored.  Then the receiver
  *                 step (taper + Laplacian + leap-frog, d_pr read, d_ppr overwritten, R:325-327), the injection of d_samples[0..nx)
  *                 = d_obs[.][nt-1-it] on column gz of the interior rows (R:328) and img += F_k * new receiver field (R:329), where
- *                 d_img is [nxl][pitch] on the extended grid.  The caller swaps (d_f1, d_f0) when step_source and (d_pr, d_ppr) always.
+ *                 d_img is [nxl][pitch] on the extended grid; its INTERIOR cells are what kernel_img defines (R:133-144) -- the imaging
+ *                 epilogues also accumulate in border cells inside their launch extents, which no entry point reports.
+ *                 The caller swaps (d_f1, d_f0) when step_source and (d_pr, d_ppr) always.
  *                 Rows of different calls of one iteration must be disjoint; pp_twice as for fdw_dev_step.  One launch where the fused
  *                 backward kernel exists (order <= 8), two otherwise.
  * fdw_dev_back4   FOUR iterations of that loop (no snapshot iterations among them) as two passes of the wave-pipeline kernel (order 8, fields
@@ -186,10 +201,12 @@ int fdw_shot(fdw_ctx *ctx, const float *v2, int sx, int sz, int gz, const float 
  *                 d_samples + j * sample_stride at iteration it + j, and adds the four imaging products to d_img in iteration order.  Local
  *                 rows [r0, r1) and [r0b, r1b) (r1 < 0: all); rows within 16 of a range end are read from the inputs, so a slab driver
  *                 shrinks the range by 16 rows per call between two halo exchanges.  No buffer may alias another.  Bit-identical to four
- *                 fdw_dev_back_iter calls.
+ *                 fdw_dev_back_iter calls.  d_lvl0 / d_lvl1 receive F_it / F_{it+1} only in the two-pass form (FDW_NO_BACK_FUSED); the fused
+ *                 pass keeps those two levels on the chip and leaves the two buffers untouched (they must still be valid memory).
  * fdw_dev_steps   nsteps FWD steps with internal role swapping; *d_srce is srce[] on the device
- *                 (may be NULL = no source).  After an odd number of steps the newest field is in
- *                 the buffer passed as d_pp, after an even number in d_p (as in the reference loop).
+ *                 (may be NULL = no source).  Every step swaps the two roles first and then writes the new field
+ *                 over d_pp (R:260-267): after an odd number of steps the newest field is in the buffer passed
+ *                 as d_p, after an even number in the one passed as d_pp (as in the reference loop).
  */
 int fdw_pitch(const fdw_ctx *ctx);           /* floats per row of a device array */
 size_t fdw_field_bytes(const fdw_ctx *ctx);  /* nxl * pitch * 4 */
@@ -466,6 +483,18 @@ int fdw_shot_snaps(fdw_ctx *ctx, const float *v2, int sx, int sz, int gz, const 
  *                         are the reference's (d_p, d_pp) before its first swap on entry and after the loop on return.  Halo exchanges
  *                         included, overlapped with the interior rows; asynchronous (fdw_slabs_synchronize; fdw_slabs_stream is the
  *                         compute stream, for events).
+ *                         STREAMS of fdw_slabs_dev_forward, fdw_slabs_dev_record_forward and fdw_slabs_dev_back (they take no stream argument):
+ *                         each rank owns three hipStreamNonBlocking streams -- compute (fdw_slabs_stream), communication and side -- none of
+ *                         them ordered against the caller's streams.  Inputs: what fills the buffers must be ordered BEFORE the call on
+ *                         fdw_slabs_stream -- an event recorded behind the producer that fdw_slabs_stream waits for
+ *                         (hipStreamWaitEvent), or a completed fill; the communication and side streams start every piece of their work
+ *                         behind the compute stream, so behind that event too, and neighbouring ranks whose inputs arrive at different times
+ *                         are ordered by the communicator's own events.  Outputs: when a call returns, every launch and transfer it issued on
+ *                         the communication and side streams has already been joined into the compute stream (the last cycle of a call never
+ *                         splits, and every cycle begins by waiting for the exchange before it), so a consumer needs to wait on
+ *                         fdw_slabs_stream ALONE -- an event recorded on it after the call -- to read the owned rows, the owned receivers'
+ *                         trace rows and the image; calls chain on it without a host synchronisation.  fdw_slabs_synchronize (all three
+ *                         streams) is what a caller uses who reads on the host or is about to free the buffers.
  * fdw_slabs_dev_back      fd_back's loop (R:302-339) on caller-owned device arrays: f[role[0]], f[role[1]] = (F_{k-1}, F_{k-2}) -- before iteration 2
  *                         the (P, PP) of the forward pass, P damped (fdw_dev_taper_finalize) --, r[role[2]], r[role[3]] = (r^k, r^{k-1}), zero
  *                         before iteration 0; role[] is updated on return.  f holds nfb buffers and r nrb (fdw_slabs_back_buffers: 6 and 4

@@ -290,7 +290,9 @@ class FDWave:
         return snap_dims(self.nx, self.nz, self.nt, every, dec)
 
     def dev_snapshot(self, d_field, dec, d_frame, stream=None):
-        """One frame of the device field d_field [nxl][pitch] into the device array d_frame [nxs][nzs]: a bit-exact crop-and-decimate copy."""
+        """One frame of the device field d_field [nxl][pitch] into the device array d_frame [nxs][nzs]: a bit-exact crop-and-decimate copy.
+        stream=None: the context's own non-blocking stream, unordered against the caller's streams (the legacy default stream included); a caller's
+        stream: every launch, copy and memset of the call is issued on it and the call does not synchronise (fdwave.h)."""
         check(lib().fdw_dev_snapshot(self._h, d_field, int(dec), d_frame, stream))
 
     def shot_snaps(self, v2, sx, sz, gz, srce, d_obs, every, dec=1, sets=("snaps", "snaps_rec", "snapr"), imloc=None, want_fields=False,
@@ -442,7 +444,9 @@ class FDWave:
 
     def dev_line_steps(self, bufs, d_v2, d_wav, sz, it0, nsteps, gz=0, d_rec=None, d_illum=None, first_pp_twice=False, ip=0, ipp=1, stream=None):
         """dev_steps2 / dev_record_steps / dev_illum_steps driven by the line source d_wav (device [it][nx]) at depth sz (fdwave.h).
-        Returns (ip, ipp) as dev_steps2 does."""
+        Returns (ip, ipp) as dev_steps2 does.
+        stream=None: the context's own non-blocking stream, unordered against the caller's streams (the legacy default stream included); a caller's
+        stream: every launch, copy and memset of the call is issued on it and the call does not synchronise (fdwave.h)."""
         arr = (C.c_void_p * 4)(*bufs)
         a, b = C.c_int(ip), C.c_int(ipp)
         check(lib().fdw_dev_line_steps(self._h, arr, d_v2, d_wav, sz, gz, d_rec, d_illum, it0, nsteps, int(first_pp_twice), C.byref(a), C.byref(b),
@@ -450,7 +454,9 @@ class FDWave:
         return a.value, b.value
 
     def dev_line_record_illum_steps(self, bufs, d_v2, d_wav, sz, gz, d_rec, d_illum, it0, nsteps, first_pp_twice=False, ip=0, ipp=1, stream=None):
-        """dev_line_steps that writes the trace rows AND accumulates the illumination, one launch per pass (fdwave.h).  Returns (ip, ipp)."""
+        """dev_line_steps that writes the trace rows AND accumulates the illumination, one launch per pass (fdwave.h).  Returns (ip, ipp).
+        stream=None: the context's own non-blocking stream, unordered against the caller's streams (the legacy default stream included); a caller's
+        stream: every launch, copy and memset of the call is issued on it and the call does not synchronise (fdwave.h)."""
         arr = (C.c_void_p * 4)(*bufs)
         a, b = C.c_int(ip), C.c_int(ipp)
         check(lib().fdw_dev_line_record_illum_steps(self._h, arr, d_v2, d_wav, sz, gz, d_rec, d_illum, it0, nsteps, int(first_pp_twice), C.byref(a),
@@ -560,7 +566,9 @@ class FDWave:
 
     def dev_check_field(self, d_f, stream=None):
         """The precondition of the lazy damping checked on a DEVICE array (compat extents: the damped strip must be zero on the rows the
-        reference never time-steps; fdwave.h).  Raises FdwError if it is violated; synchronises the stream."""
+        reference never time-steps; fdwave.h).  Raises FdwError if it is violated; synchronises the stream.
+        stream=None: the context's own non-blocking stream, unordered against the caller's streams (the legacy default stream included); a caller's
+        stream: the check is issued on it -- and, the one exception among the dev_* methods, this call SYNCHRONISES it (fdwave.h)."""
         check(lib().fdw_dev_check_field(self._h, d_f, stream))
 
     def set_store_budget(self, nbytes):
@@ -576,37 +584,69 @@ class FDWave:
         return int(lib().fdw_field_bytes(self._h))
 
     def dev_model_steps(self, d_p, d_pp, d_v2, d_srce, sx, sz, gz, d_rec, it0, nsteps, stream=None):
+        """stream=None: the context's own non-blocking stream, unordered against the caller's streams (the legacy default stream included); a caller's
+        stream: every launch, copy and memset of the call is issued on it and the call does not synchronise (fdwave.h)."""
         check(lib().fdw_dev_model_steps(self._h, d_p, d_pp, d_v2, d_srce, sx, sz, gz, d_rec, it0, nsteps, stream))
 
     # ---- device-array API (raw pointers; see device.py for torch helpers) -----------------------
+    # THE STREAM CONTRACT of every dev_* method (fdwave.h, pinned by tests/test_stream_contract.py):
+    #   stream=None   the context's own hipStreamNonBlocking stream.  It has NO implicit ordering against the caller's streams, the legacy
+    #                 default stream included: whatever filled the buffers must have completed (torch.cuda.synchronize(), or an event the
+    #                 caller has waited for on the host) before the call, and the results are ready only after the device was synchronised.
+    #   stream=S      (a hipStream_t as an int, e.g. torch.cuda.Stream().cuda_stream) every launch, copy and memset of the call is issued on
+    #                 S and the call returns without synchronising: work queued on S before the call is seen by it, work queued on S after
+    #                 it sees its results.  The one exception is dev_check_field, which synchronises S to return its count.
     def dev_step(self, mode, d_p, d_pp, d_v2, r0=0, r1=None, pp_twice=True, d_inj=None, inj_x=-1, inj_z=0,
                  d_psrc=None, d_img=None, stream=None):
+        """One fused time step (fdwave.h, fdw_dev_step; mode 3 is dev_laplacian's).  stream: the contract above -- None is the context's own
+        non-blocking stream, unordered against the caller's; a caller's stream carries every launch of the call."""
         r1 = self.nxl if r1 is None else r1
         check(lib().fdw_dev_step(self._h, mode, d_p, d_pp, d_v2, r0, r1, int(pp_twice), d_inj, inj_x, inj_z,
                                  d_psrc, d_img, stream))
 
     def dev_back_iter(self, step_source, d_f1, d_f0, d_pr, d_ppr, d_v2, r0, r1, pp_twice, d_samples, gz, d_img, stream=None):
-        """One iteration of fd_back's loop (fd-code.cu:302-339) on local rows [r0, r1): see fdwave.h."""
+        """One iteration of fd_back's loop (fd-code.cu:302-339) on local rows [r0, r1): see fdwave.h.
+        stream=None: the context's own non-blocking stream, unordered against the caller's streams (the legacy default stream included); a caller's
+        stream: every launch, copy and memset of the call is issued on it and the call does not synchronise (fdwave.h)."""
         check(lib().fdw_dev_back_iter(self._h, int(step_source), d_f1, d_f0, d_pr, d_ppr, d_v2, r0, r1, int(pp_twice), d_samples, gz, d_img, stream))
 
+    def dev_back4(self, d_f1, d_f0, d_fo1, d_fo2, d_lvl0, d_lvl1, d_pr, d_ppr, d_ro1, d_ro2, d_v2, d_samples, sample_stride, gz, d_img, pp_twice=True,
+                  r0=0, r1=-1, r0b=0, r1b=0, xchunk=0, stream=None):
+        """Four iterations of fd_back's loop as two passes of the wave pipeline on local rows [r0, r1) (+ [r0b, r1b)); r1 < 0 = all rows: see
+        fdwave.h.  stream: the contract above -- None is the context's own non-blocking stream, unordered against the caller's; a caller's
+        stream carries every launch and copy of the call, which does not synchronise."""
+        check(lib().fdw_dev_back4(self._h, d_f1, d_f0, d_fo1, d_fo2, d_lvl0, d_lvl1, d_pr, d_ppr, d_ro1, d_ro2, d_v2, d_samples, int(sample_stride), gz,
+                                  d_img, int(pp_twice), r0, r1, r0b, r1b, xchunk, stream))
+
     def dev_steps(self, d_p, d_pp, d_v2, d_srce, sx, sz, it0, nsteps, first_pp_twice=False, stream=None):
+        """nsteps forward iterations on two buffers (one-step kernel; fdwave.h, fdw_dev_steps).
+        stream=None: the context's own non-blocking stream, unordered against the caller's streams (the legacy default stream included); a caller's
+        stream: every launch, copy and memset of the call is issued on it and the call does not synchronise (fdwave.h)."""
         check(lib().fdw_dev_steps(self._h, d_p, d_pp, d_v2, d_srce, sx, sz, it0, nsteps, int(first_pp_twice), stream))
 
     def dev_steps_shrink(self, d_p, d_pp, d_v2, d_srce, sx, sz, it0, nsteps, first_pp_twice, j0, shrink_lo, shrink_hi, stream=None):
+        """stream=None: the context's own non-blocking stream, unordered against the caller's streams (the legacy default stream included); a caller's
+        stream: every launch, copy and memset of the call is issued on it and the call does not synchronise (fdwave.h)."""
         check(lib().fdw_dev_steps_shrink(self._h, d_p, d_pp, d_v2, d_srce, sx, sz, it0, nsteps, int(first_pp_twice), j0,
                                          int(shrink_lo), int(shrink_hi), stream))
 
     def dev_step2(self, d_p, d_pp, d_v2, d_out1, d_out2, pp_twice=True, d_srce_it=None, sx=-1, sz=0, stream=None):
-        """Two forward iterations in one pass (temporal blocking); d_p is the NEWEST field."""
+        """Two forward iterations in one pass (temporal blocking); d_p is the NEWEST field.
+        stream=None: the context's own non-blocking stream, unordered against the caller's streams (the legacy default stream included); a caller's
+        stream: every launch, copy and memset of the call is issued on it and the call does not synchronise (fdwave.h)."""
         check(lib().fdw_dev_step2(self._h, d_p, d_pp, d_v2, d_out1, d_out2, int(pp_twice), d_srce_it, sx, sz, stream))
 
     def dev_step4(self, d_p, d_pp, d_v2, d_out1, d_out2, pp_twice=True, d_srce_it=None, sx=-1, sz=0, r0=0, r1=-1, r0b=0, r1b=0, xchunk=0, stream=None):
-        """Four forward iterations in one pass (wave pipeline) on local rows [r0, r1) (+ [r0b, r1b)); r1 < 0 = all rows."""
+        """Four forward iterations in one pass (wave pipeline) on local rows [r0, r1) (+ [r0b, r1b)); r1 < 0 = all rows.
+        stream=None: the context's own non-blocking stream, unordered against the caller's streams (the legacy default stream included); a caller's
+        stream: every launch, copy and memset of the call is issued on it and the call does not synchronise (fdwave.h)."""
         check(lib().fdw_dev_step4(self._h, d_p, d_pp, d_v2, d_out1, d_out2, int(pp_twice), d_srce_it, sx, sz, r0, r1, r0b, r1b, xchunk, stream))
 
     def dev_steps2(self, bufs, d_v2, d_srce, sx, sz, it0, nsteps, first_pp_twice=False, ip=0, ipp=1, stream=None):
         """nsteps iterations over four rotating device buffers (pairs via the two-step kernel).
-        Returns the indices (ip, ipp) of the reference's (d_p, d_pp) after the loop."""
+        Returns the indices (ip, ipp) of the reference's (d_p, d_pp) after the loop.
+        stream=None: the context's own non-blocking stream, unordered against the caller's streams (the legacy default stream included); a caller's
+        stream: every launch, copy and memset of the call is issued on it and the call does not synchronise (fdwave.h)."""
         arr = (C.c_void_p * 4)(*bufs)
         a, b = C.c_int(ip), C.c_int(ipp)
         check(lib().fdw_dev_steps2(self._h, arr, d_v2, d_srce, sx, sz, it0, nsteps, int(first_pp_twice), C.byref(a), C.byref(b), stream))
@@ -614,7 +654,9 @@ class FDWave:
 
     def dev_record_steps(self, bufs, d_v2, d_srce, sx, sz, gz, d_rec, it0, nsteps, first_pp_twice=False, ip=0, ipp=1, stream=None):
         """dev_steps2 that also writes the trace samples of iteration it to d_rec + it * nx (device [it][nx]; fdwave.h).
-        Returns (ip, ipp) as dev_steps2 does."""
+        Returns (ip, ipp) as dev_steps2 does.
+        stream=None: the context's own non-blocking stream, unordered against the caller's streams (the legacy default stream included); a caller's
+        stream: every launch, copy and memset of the call is issued on it and the call does not synchronise (fdwave.h)."""
         arr = (C.c_void_p * 4)(*bufs)
         a, b = C.c_int(ip), C.c_int(ipp)
         check(lib().fdw_dev_record_steps(self._h, arr, d_v2, d_srce, sx, sz, gz, d_rec, it0, nsteps, int(first_pp_twice), C.byref(a), C.byref(b), stream))
@@ -622,7 +664,9 @@ class FDWave:
 
     def dev_illum_steps(self, bufs, d_v2, d_srce, sx, sz, d_illum, it0, nsteps, first_pp_twice=False, ip=0, ipp=1, stream=None):
         """dev_steps2 that also adds the square of every step's new field to d_illum (device [nxl][pitch]; fdwave.h).
-        Returns (ip, ipp) as dev_steps2 does."""
+        Returns (ip, ipp) as dev_steps2 does.
+        stream=None: the context's own non-blocking stream, unordered against the caller's streams (the legacy default stream included); a caller's
+        stream: every launch, copy and memset of the call is issued on it and the call does not synchronise (fdwave.h)."""
         arr = (C.c_void_p * 4)(*bufs)
         a, b = C.c_int(ip), C.c_int(ipp)
         check(lib().fdw_dev_illum_steps(self._h, arr, d_v2, d_srce, sx, sz, d_illum, it0, nsteps, int(first_pp_twice), C.byref(a), C.byref(b), stream))
@@ -630,7 +674,9 @@ class FDWave:
 
     def dev_record_illum_steps(self, bufs, d_v2, d_srce, sx, sz, gz, d_rec, d_illum, it0, nsteps, first_pp_twice=False, ip=0, ipp=1, stream=None):
         """dev_steps2 that writes the trace rows of dev_record_steps and accumulates as dev_illum_steps does, one launch per pass (fdwave.h).
-        Returns (ip, ipp) as dev_steps2 does."""
+        Returns (ip, ipp) as dev_steps2 does.
+        stream=None: the context's own non-blocking stream, unordered against the caller's streams (the legacy default stream included); a caller's
+        stream: every launch, copy and memset of the call is issued on it and the call does not synchronise (fdwave.h)."""
         arr = (C.c_void_p * 4)(*bufs)
         a, b = C.c_int(ip), C.c_int(ipp)
         check(lib().fdw_dev_record_illum_steps(self._h, arr, d_v2, d_srce, sx, sz, gz, d_rec, d_illum, it0, nsteps, int(first_pp_twice), C.byref(a),
@@ -638,13 +684,19 @@ class FDWave:
         return a.value, b.value
 
     def dev_gather_residual(self, d_a, d_b, d_out, n, stream=None):
-        """d_out[i] = d_a[i] - d_b[i] for i < n on device arrays of floats (one fp32 subtraction each); d_out may be d_a."""
+        """d_out[i] = d_a[i] - d_b[i] for i < n on device arrays of floats (one fp32 subtraction each); d_out may be d_a.
+        stream=None: the context's own non-blocking stream, unordered against the caller's streams (the legacy default stream included); a caller's
+        stream: every launch, copy and memset of the call is issued on it and the call does not synchronise (fdwave.h)."""
         check(lib().fdw_dev_gather_residual(self._h, d_a, d_b, d_out, int(n), stream))
 
     def dev_taper_finalize(self, d_f, stream=None):
+        """stream=None: the context's own non-blocking stream, unordered against the caller's streams (the legacy default stream included); a caller's
+        stream: every launch, copy and memset of the call is issued on it and the call does not synchronise (fdwave.h)."""
         check(lib().fdw_dev_taper_finalize(self._h, d_f, stream))
 
     def dev_laplacian(self, d_p, d_lap, stream=None):
+        """stream=None: the context's own non-blocking stream, unordered against the caller's streams (the legacy default stream included); a caller's
+        stream: every launch, copy and memset of the call is issued on it and the call does not synchronise (fdwave.h)."""
         check(lib().fdw_dev_laplacian(self._h, d_p, d_lap, stream))
 
     def upload(self, d_dst, h_src):

@@ -117,6 +117,12 @@ class Slabs:
         self.ctx._h = None
         self._ctx_h = C.c_void_p(lib().fdw_slabs_ctx(self._h))
         self.pitch = lib().fdw_pitch(self._ctx_h)
+        # stream: the rank's compute stream (fdw_slabs_stream, a hipStream_t as an int; torch.cuda.ExternalStream(s.stream)), created with
+        # hipStreamNonBlocking: it has no implicit ordering against the caller's streams, the legacy default stream included.  dev_forward,
+        # dev_record_forward and dev_back take no stream: order what fills their buffers before the call on THIS stream (an event it waits
+        # for, or a completed fill) -- the rank's communication and side streams start behind it --, and wait on THIS stream alone for the
+        # results (an event recorded on it after the call): everything the other two streams did has been joined into it when a call
+        # returns (fdwave.h; tests/test_stream_contract.py).  Calls chain without a host synchronisation; synchronize() waits for all three.
         self.stream = lib().fdw_slabs_stream(self._h)
 
     def ctx_call(self, name, *args):

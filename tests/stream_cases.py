@@ -1,0 +1,562 @@
+"""TEST HELPER (not a conftest) of tests/test_stream_contract.py: the stream-taking entry points of fdwave.h as CASES -- for each one the
+device buffers it works on with two valid argument sets (the TRUE inputs and the DECOYS: another model, other fields, another wavelet, another
+gather, another entry image and illumination), the call itself, and the CPU oracle's answer to either set -- and the late-producer machinery
+that runs a case: a delay on the caller's stream, then the true inputs copied over the decoys, then the entry point, then the outputs copied
+out, all on that one stream and with no synchronisation before the end.
+
+The answers come from the restatements the other modules already pin: tests/test_line_source.py's line_restatement (the forward chain with
+a point or a line source, its trace rows and its illumination; with a point source it is Oracle.forward bit for bit, pinned there on the
+CPU), Oracle.slab_step / slab_back_iter (one forward / backward iteration on row ranges), O.mod_steps, tests/context_reuse_cases.py's
+oracle_laplacian, and numpy slicing / fp32 subtraction for the two copy-like kernels."""
+import functools
+import os
+import time
+
+import numpy as np
+
+from conftest import make_deck, random_fields
+from context_reuse_cases import oracle_laplacian
+from oracle import oracle as O
+from test_line_source import args_of, extents_of, line_restatement
+
+NT = 9                                    # a four-step pass, a two-step pass and an odd tail; 5 + 4 when chained
+SENTINELS = (7.0, -7.0, 9.0)              # what pure outputs hold before the call; no oracle answer holds any of them (checked on the CPU)
+EINVAL = -1
+MOD_FAC = 0.05
+
+# name: geometry (nxe, nze, nxb, nzb), compat, spacings, (sx, sz, gz), tuning every context on it gets on top of its family
+DECKS = {
+    # the ragged compat grid of tests/context_reuse_cases.py: rows 64..68 never time-stepped, receiver rows 64, 65 among them (record_static,
+    # static_receiver_rows and even_steps_tail all have work), zlim 296, ztap 8, pitch 320 > nze
+    "ragged": dict(geom=(69, 301, 3, 10), compat=True, dx=10.0, dz=12.5, place=(26, 258, 255), tuning={}),
+    # the same grid with every receiver row time-stepped: what fdw_dev_back4 needs
+    "stepped": dict(geom=(69, 301, 8, 10), compat=True, dx=10.0, dz=12.5, place=(26, 258, 255), tuning={}),
+    # the deck of tests/test_tile_classes.py: 14 chunk rows x 3 strips at 13-row chunks, lean and full tiles in one launch
+    "tiles": dict(geom=(180, 500, 12, 14), compat=False, dx=10.0, dz=10.0, place=(84, 300, 310), tuning=dict(xchunk=13)),
+}
+FAMILIES = {"one-step": -1, "two-step": 1, "pipeline": 4}
+
+
+def _freeze(d):
+    for a in d.values():
+        if isinstance(a, np.ndarray):
+            a.setflags(write=False)
+    return d
+
+
+@functools.lru_cache(maxsize=None)
+def inputs(deck, v):
+    """Argument set v ("true" or "decoy") on a deck: everything an entry point reads from device memory."""
+    D = DECKS[deck]
+    nxe, nze, nxb, nzb = D["geom"]
+    nx = nxe - 2 * nxb
+    seed = 3 if v == "true" else 11
+    d = make_deck(nxe, nze, nxb, nzb, NT, seed=seed, compat=D["compat"], dx=D["dx"], dz=D["dz"])
+    rng = np.random.default_rng(500 + seed)
+    f = np.float32
+    p0, pp0 = random_fields(d, seed + 1, amp=0.1)
+    f1, f0 = random_fields(d, seed + 2, amp=0.1)
+    pr, ppr = random_fields(d, seed + 3, amp=0.1)
+    m0, m1 = random_fields(d, seed + 4, amp=1e-3)
+    base = O.ricker_wavelet(NT, d["dt"], 30.0)
+    srce = (base * 1000.0 + 0.5).astype(f) if v == "true" else (base * 700.0 + 3.0).astype(f)
+    clean = np.array(p0)
+    planted = np.array(clean)
+    xlim, _, ztap = extents_of(d)
+    if D["compat"] and xlim < nxe and ztap > 0:
+        planted[xlim, 0], planted[nxe - 1, ztap - 1], planted[xlim + 1, 3] = 1e-30, -4.0, 2.5
+    return _freeze(dict(d=d, v2=d["v2"], p0=p0, pp0=pp0, f1=f1, f0=f0, pr=pr, ppr=ppr, m0=m0, m1=m1, srce=srce,
+                        msrce=(1e-2 * rng.standard_normal(NT)).astype(f), w=rng.standard_normal((NT, nx)).astype(f),
+                        il0=(0.5 + rng.random((nxe, nze))).astype(f), img0=rng.standard_normal((nxe, nze)).astype(f),
+                        samples=rng.standard_normal((4, nx)).astype(f), ga=rng.standard_normal((NT, nx)).astype(f),
+                        gb=rng.standard_normal((NT, nx)).astype(f), lap_in=rng.standard_normal((nxe, nze)).astype(f), clean=clean, planted=planted))
+
+
+@functools.lru_cache(maxsize=None)
+def oracle(deck, numerics):
+    D = DECKS[deck]
+    return O.Oracle(*args_of(inputs(deck, "true")["d"]), compat=D["compat"], numerics=numerics)
+
+
+@functools.lru_cache(maxsize=None)
+def chain(deck, numerics, v, line, nsteps=NT):
+    """P (damped once, as fdw_dev_taper_finalize leaves it), PP, data[nx][nsteps] and illum after nsteps forward iterations from (p0, pp0, il0)."""
+    i = inputs(deck, v)
+    sx, sz, gz = DECKS[deck]["place"]
+    return _freeze(line_restatement(oracle(deck, numerics), i["d"], i["v2"], i["w"][:nsteps] if line else None, sz, gz=gz, p0=i["p0"], pp0=i["pp0"],
+                                    il0=i["il0"], point=None if line else (sx, i["srce"][:nsteps])))
+
+
+@functools.lru_cache(maxsize=None)
+def back_chain(deck, numerics, v, n, step_source):
+    """n iterations of fd_back's loop body (Oracle.slab_back_iter on the whole grid) from (f1, f0, pr, ppr, img0) with the sample rows
+    samples[0..n): F = the reconstructed source fields, r_new / r_old = the receiver pair after the last swap (r_old damped as the next
+    iteration would read it: fdw_dev_taper_finalize), img."""
+    i = inputs(deck, v)
+    nxe = i["d"]["nxe"]
+    gz = DECKS[deck]["place"][2]
+    f1, f0, pr, ppr, img = (np.array(i[k], np.float32, order="C") for k in ("f1", "f0", "pr", "ppr", "img0"))
+    F = []
+    for j in range(n):
+        oracle(deck, numerics).slab_back_iter(0, step_source, f1, f0, pr, ppr, i["v2"], 0, nxe, i["samples"][j], gz, img)
+        if step_source:
+            F.append(f0.copy())
+            f1, f0 = f0, f1
+        pr, ppr = ppr, pr
+    out = dict(r_new=pr, r_old=ppr, img=img)
+    out.update({f"F{j}": a for j, a in enumerate(F)})
+    return _freeze(out)
+
+
+@functools.lru_cache(maxsize=None)
+def shrink_chain(deck, numerics, v, nsteps):
+    """nsteps cycle steps j = 1.. of a slab with neighbours on both sides: step j updates rows [4 j, nxe - 4 j) (fdw_dev_steps_shrink)."""
+    i = inputs(deck, v)
+    sx, sz, _ = DECKS[deck]["place"]
+    nxe = i["d"]["nxe"]
+    P, PP = np.array(i["p0"], np.float32, order="C"), np.array(i["pp0"], np.float32, order="C")
+    for k in range(nsteps):
+        P, PP = PP, P
+        oracle(deck, numerics).slab_step(0, P, PP, i["v2"], 4 * (k + 1), nxe - 4 * (k + 1), sx, sz, float(i["srce"][k]))
+    return _freeze(dict(P=P, PP=PP))
+
+
+@functools.lru_cache(maxsize=None)
+def mod_chain(deck, numerics, v):
+    i = inputs(deck, v)
+    nxe, nze, nxb, nzb = DECKS[deck]["geom"]
+    nx, nz = nxe - 2 * nxb, nze - 2 * nzb
+    D = DECKS[deck]
+    sx, sz, gz = D["place"]
+    P, PP, data = O.mod_steps(8, nx, nz, nxb, nzb, D["dx"], D["dz"], 0.001, MOD_FAC, i["v2"], sx, sz, gz, i["msrce"],
+                              O.mod_taper_apply(i["m0"], nx, nz, nxb, nzb, MOD_FAC, 1), O.mod_taper_apply(i["m1"], nx, nz, nxb, nzb, MOD_FAC, 2),
+                              numerics=numerics)
+    return _freeze(dict(P=P, PP=PP, rec=np.ascontiguousarray(data.T)))
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------
+# cases
+# ---------------------------------------------------------------------------------------------------------------------------------------
+class Case:
+    """name; deck; numerics; two_step (None: the context's default); dialect.
+    ins(i) -> {buffer: (kind, array)} for an argument set i; kind "field" = [nxe][pitch] on the device, "flat" = dense.
+    outs   -> {buffer: (kind, shape, sentinel)}: pure outputs.
+    call(ctx, ptr, stream) -> [(label, buffer, post or None, rows or None)]: makes the call(s) and says where each answer lies.
+    want(v) -> {label: array}."""
+
+    def __init__(self, name, deck, numerics, two_step, ins, outs, call, want, dialect=0, env=None):
+        self.name, self.deck, self.numerics, self.two_step, self.dialect, self.env = name, deck, numerics, two_step, dialect, env or {}
+        self.ins, self.outs, self.call, self.want = ins, outs, call, want
+
+    def make_ctx(self):
+        """The context of the case; self.env holds switches the library reads when a context is created."""
+        old = {k: os.environ.get(k) for k in self.env}
+        os.environ.update(self.env)
+        try:
+            return self._make_ctx()
+        finally:
+            for k, v in old.items():
+                os.environ.pop(k, None)
+                if v is not None:
+                    os.environ[k] = v
+
+    def _make_ctx(self):
+        import parallel_finite_difference_computation_amd as F
+        D = DECKS[self.deck]
+        d = inputs(self.deck, "true")["d"]
+        if self.dialect == 1:
+            ctx = F.FDWave(8, d["nxe"], d["nze"], d["nxb"], d["nzb"], NT, MOD_FAC, D["dx"], D["dz"], 0.001, device=0, dialect=1, numerics=self.numerics)
+        else:
+            ctx = F.FDWave(*args_of(d), compat=D["compat"], device=0, numerics=self.numerics)
+        if self.two_step is not None:
+            ctx.set_tuning(two_step=self.two_step, **D["tuning"])
+            assert ctx.steps_per_pass() == {-1: 1, 1: 2 if self.dialect == 0 else 1, 4: 4}[self.two_step]
+        return ctx
+
+    def __repr__(self):
+        return self.name
+
+
+CASES = []
+
+
+def _add(name, deck, numerics, two_step, ins, outs, call, want, **kw):
+    tag = f"{name}-{deck}" + ("" if two_step is None else "-" + {v: k for k, v in FAMILIES.items()}[two_step]) + ("-fast" if numerics else "")
+    CASES.append(Case(tag, deck, numerics, two_step, ins, outs, call, want, **kw))
+
+
+def _dims(deck):
+    nxe, nze, nxb, nzb = DECKS[deck]["geom"]
+    return nxe, nze, nxb, nzb, nxe - 2 * nxb, nze - 2 * nzb
+
+
+def _loop_case(kind, deck, numerics, two_step, split=((0, NT),)):
+    """The forward loops over four rotating buffers: kind = steps2 | record | illum | record_illum | line | line_rec | line_ill | line_rec_ill."""
+    nxe, nze, nxb, nzb, nx, nz = _dims(deck)
+    sx, sz, gz = DECKS[deck]["place"]
+    line = kind.startswith("line")
+    rec = kind in ("record", "record_illum", "line_rec", "line_rec_ill")
+    ill = kind in ("illum", "record_illum", "line_ill", "line_rec_ill")
+
+    def ins(i):
+        b = dict(b0=("field", i["p0"]), b1=("field", i["pp0"]), v2=("field", i["v2"]), src=("flat", i["w"] if line else i["srce"]))
+        if ill:
+            b["il"] = ("field", i["il0"])
+        return b
+
+    outs = dict(b2=("field", (nxe, nze), 7.0), b3=("field", (nxe, nze), -7.0))
+    if rec:
+        outs["rec"] = ("flat", (NT, nx), 9.0)
+
+    def call(ctx, p, stream):
+        bufs = [p["b0"], p["b1"], p["b2"], p["b3"]]
+        ip, ipp = 0, 1
+        for k, (it0, n) in enumerate(split):
+            a = dict(first_pp_twice=k > 0, ip=ip, ipp=ipp, stream=stream)
+            if kind == "steps2":
+                ip, ipp = ctx.dev_steps2(bufs, p["v2"], p["src"], sx, sz, it0, n, **a)
+            elif kind == "record":
+                ip, ipp = ctx.dev_record_steps(bufs, p["v2"], p["src"], sx, sz, gz, p["rec"], it0, n, **a)
+            elif kind == "illum":
+                ip, ipp = ctx.dev_illum_steps(bufs, p["v2"], p["src"], sx, sz, p["il"], it0, n, **a)
+            elif kind == "record_illum":
+                ip, ipp = ctx.dev_record_illum_steps(bufs, p["v2"], p["src"], sx, sz, gz, p["rec"], p["il"], it0, n, **a)
+            elif kind == "line_rec_ill":
+                ip, ipp = ctx.dev_line_record_illum_steps(bufs, p["v2"], p["src"], sz, gz, p["rec"], p["il"], it0, n, **a)
+            else:
+                ip, ipp = ctx.dev_line_steps(bufs, p["v2"], p["src"], sz, it0, n, gz=gz, d_rec=p["rec"] if rec else None, d_illum=p["il"] if ill else None, **a)
+        ctx.dev_taper_finalize(bufs[ip], stream=stream)
+        out = [("PP", f"b{ipp}", None, None), ("P", f"b{ip}", None, None)]
+        if rec:
+            out.append(("rec", "rec", None, None))
+        if ill:
+            out.append(("illum", "il", None, None))
+        return out
+
+    def want(v):
+        c = chain(deck, numerics, v, line)
+        out = dict(PP=c["PP"], P=c["P"])
+        if rec:
+            out["rec"] = np.ascontiguousarray(c["data"].T)
+        if ill:
+            out["illum"] = c["illum"]
+        return out
+
+    _add(kind + ("" if len(split) == 1 else "-chained"), deck, numerics, two_step, ins, outs, call, want)
+
+
+LOOP_KINDS = ("steps2", "record", "illum", "record_illum", "line", "line_rec", "line_ill", "line_rec_ill")
+for _num in (0, 1):
+    for _kind in LOOP_KINDS:
+        for _fam, _deck in ((-1, "ragged"), (1, "ragged"), (4, "stepped")):
+            _loop_case(_kind, _deck, _num, _fam)
+    _loop_case("record", "ragged", _num, 4)               # the pipeline's trace rows with static receiver rows beside them
+for _kind in ("steps2", "record", "line"):                 # 5 + 4 steps, no host synchronisation in between
+    for _fam, _deck in ((-1, "ragged"), (1, "ragged"), (4, "stepped")):
+        _loop_case(_kind, _deck, 0, _fam, split=((0, 5), (5, 4)))
+for _kind in ("steps2", "record", "illum", "record_illum", "line", "line_rec_ill"):      # lean and full tiles behind the late producer
+    _loop_case(_kind, "tiles", 0, 4)
+_loop_case("steps2", "tiles", 1, 4)
+
+
+def _two_buffer_case(kind, deck, numerics):
+    """fdw_dev_steps (9 steps) and fdw_dev_steps_shrink (3 cycle steps, both sides shrinking) on two buffers: always the one-step kernel."""
+    nxe, nze, nxb, nzb, nx, nz = _dims(deck)
+    sx, sz, gz = DECKS[deck]["place"]
+    n = NT if kind == "steps" else 3
+    rows = None if kind == "steps" else slice(4 * n, nxe - 4 * n)
+
+    def ins(i):
+        return dict(A=("field", i["p0"]), B=("field", i["pp0"]), v2=("field", i["v2"]), src=("flat", i["srce"]))
+
+    def call(ctx, p, stream):
+        if kind == "steps":
+            ctx.dev_steps(p["A"], p["B"], p["v2"], p["src"], sx, sz, 0, n, False, stream=stream)
+        else:
+            ctx.dev_steps_shrink(p["A"], p["B"], p["v2"], p["src"], sx, sz, 0, n, False, 1, 1, 1, stream=stream)
+        ctx.dev_taper_finalize(p["B"], stream=stream)      # n is odd: the newest field lies in the buffer passed as d_p
+        return [("PP", "A", None, rows), ("P", "B", None, rows)]
+
+    def want(v):
+        c = chain(deck, numerics, v, False) if kind == "steps" else shrink_chain(deck, numerics, v, n)
+        return dict(PP=c["PP"] if rows is None else c["PP"][rows], P=c["P"] if rows is None else c["P"][rows])
+
+    _add(kind, deck, numerics, None, ins, {}, call, want)
+
+
+def _pass_case(kind, deck, numerics, ranges=None):
+    """One pass of fdw_dev_step (FWD), fdw_dev_step2 or fdw_dev_step4 from (p0, pp0); step4 optionally on two row ranges."""
+    nxe, nze, nxb, nzb, nx, nz = _dims(deck)
+    sx, sz, gz = DECKS[deck]["place"]
+    n = dict(step_fwd=1, step2=2, step4=4)[kind]
+    rows = None
+    if ranges:
+        rows = np.zeros(nxe, bool)
+        rows[ranges["r0"]:ranges["r1"]] = True
+        rows[ranges["r0b"]:ranges["r1b"]] = True
+
+    def ins(i):      # forward()'s convention: the kernel's p (newest) is pp0
+        return dict(NEW=("field", i["pp0"]), OLD=("field", i["p0"]), v2=("field", i["v2"]), src=("flat", i["srce"]))
+
+    outs = {} if kind == "step_fwd" else dict(O1=("field", (nxe, nze), 7.0), O2=("field", (nxe, nze), -7.0))
+
+    def call(ctx, p, stream):
+        from parallel_finite_difference_computation_amd._lib import MODE_FWD
+        if kind == "step_fwd":
+            ctx.dev_step(MODE_FWD, p["NEW"], p["OLD"], p["v2"], 0, nxe, pp_twice=False, d_inj=p["src"], inj_x=sx, inj_z=sz, stream=stream)
+            ctx.dev_taper_finalize(p["NEW"], stream=stream)
+            return [("PP", "OLD", None, None), ("P", "NEW", None, None)]
+        if kind == "step2":
+            ctx.dev_step2(p["NEW"], p["OLD"], p["v2"], p["O1"], p["O2"], pp_twice=False, d_srce_it=p["src"], sx=sx, sz=sz, stream=stream)
+        else:
+            ctx.dev_step4(p["NEW"], p["OLD"], p["v2"], p["O1"], p["O2"], pp_twice=False, d_srce_it=p["src"], sx=sx, sz=sz,
+                          xchunk=DECKS[deck]["tuning"].get("xchunk", 0), stream=stream, **(ranges or {}))
+        ctx.dev_taper_finalize(p["O1"], stream=stream)
+        return [("PP", "O2", None, rows), ("P", "O1", None, rows)]
+
+    def want(v):
+        c = chain(deck, numerics, v, False, n)
+        return dict(PP=c["PP"] if rows is None else c["PP"][rows], P=c["P"] if rows is None else c["P"][rows])
+
+    _add(kind + ("-two-ranges" if ranges else ""), deck, numerics, None, ins, outs, call, want)
+
+
+def _back_case(kind, deck, numerics, two_pass=False):
+    """fdw_dev_step PLAIN / RECV, fdw_dev_back_iter (step_source 0 / 1) and fdw_dev_back4 from noise-filled source and receiver fields.
+    The image is compared on the interior cells: d_img lies on the extended grid, the kernels also accumulate in its border cells inside
+    their launch extents, and only the interior is what fd_back's kernel_img defines (and what the host entry points return).
+    two_pass (FDW_NO_BACK_FUSED): fdw_dev_back4 as a PLAIN_ALL and a RECV pass, which also leaves F_it, F_it+1 in d_lvl0, d_lvl1 -- the fused
+    pass keeps those two levels on the chip and does not touch the two buffers."""
+    nxe, nze, nxb, nzb, nx, nz = _dims(deck)
+    gz = DECKS[deck]["place"][2]
+
+    def crop(a):
+        return np.ascontiguousarray(a[nxb:nxb + nx, nzb:nzb + nz])
+
+    def ins(i):
+        return dict(F1=("field", i["f1"]), F0=("field", i["f0"]), PR=("field", i["pr"]), PPR=("field", i["ppr"]), v2=("field", i["v2"]),
+                    IMG=("field", i["img0"]), SAMP=("flat", i["samples"]))
+
+    outs = {}
+    if kind == "back4":
+        outs = {k: ("field", (nxe, nze), s) for k, s in (("FO1", 7.0), ("FO2", -7.0), ("L0", 7.0), ("L1", -7.0), ("RO1", 9.0), ("RO2", -7.0))}
+
+    def call(ctx, p, stream):
+        from parallel_finite_difference_computation_amd._lib import MODE_PLAIN, MODE_RECV
+        if kind == "step_plain":
+            ctx.dev_step(MODE_PLAIN, p["F1"], p["F0"], p["v2"], 0, nxe, pp_twice=False, stream=stream)
+            return [("F0", "F0", None, None)]
+        if kind == "step_recv":
+            ctx.dev_step(MODE_RECV, p["PR"], p["PPR"], p["v2"], 0, nxe, pp_twice=False, d_inj=p["SAMP"], inj_x=0, inj_z=gz, d_psrc=p["F1"], d_img=p["IMG"],
+                         stream=stream)
+            return [("r_new", "PPR", None, None), ("img", "IMG", crop, None)]
+        if kind in ("back_iter0", "back_iter1"):
+            ss = int(kind[-1])
+            ctx.dev_back_iter(ss, p["F1"], p["F0"], p["PR"], p["PPR"], p["v2"], 0, nxe, False, p["SAMP"], gz, p["IMG"], stream=stream)
+            return [("r_new", "PPR", None, None), ("img", "IMG", crop, None)] + ([("F0", "F0", None, None)] if ss else [])
+        ctx.dev_back4(p["F1"], p["F0"], p["FO1"], p["FO2"], p["L0"], p["L1"], p["PR"], p["PPR"], p["RO1"], p["RO2"], p["v2"], p["SAMP"], nx, gz, p["IMG"],
+                      pp_twice=False, xchunk=DECKS[deck]["tuning"].get("xchunk", 0), stream=stream)
+        ctx.dev_taper_finalize(p["RO1"], stream=stream)
+        levels = [("F0", "L0", None, None), ("F1", "L1", None, None)] if two_pass else []
+        return levels + [("F2", "FO1", None, None), ("F3", "FO2", None, None), ("r_new", "RO2", None, None), ("r_old", "RO1", None, None),
+                         ("img", "IMG", crop, None)]
+
+    def want(v):
+        c = dict(back_chain(deck, numerics, v, 4 if kind == "back4" else 1, 0 if kind in ("step_recv", "back_iter0") else 1))
+        c["img"] = crop(c["img"])
+        if kind == "back4":
+            return {k: a for k, a in c.items() if two_pass or k not in ("F0", "F1")}
+        if kind == "step_plain":
+            return dict(F0=c["F0"])
+        return {k: c[k] for k in ("r_new", "img") + (("F0",) if kind == "back_iter1" else ())}
+
+    _add(kind + ("-two-pass" if two_pass else ""), deck, numerics, None, ins, outs, call, want, env={"FDW_NO_BACK_FUSED": "1"} if two_pass else None)
+
+
+def _model_case(deck, numerics, two_step):
+    nxe, nze, nxb, nzb, nx, nz = _dims(deck)
+    sx, sz, gz = DECKS[deck]["place"]
+
+    def ins(i):
+        return dict(A=("field", i["m0"]), B=("field", i["m1"]), v2=("field", i["v2"]), src=("flat", i["msrce"]))
+
+    def call(ctx, p, stream):
+        ctx.dev_model_steps(p["A"], p["B"], p["v2"], p["src"], sx, sz, gz, p["rec"], 0, NT, stream=stream)
+        # the device arrays hold the fields before the damping the loop still owes them (P one pass short, PP two); NT is odd: they swapped
+        return [("rec", "rec", None, None), ("P", "B", lambda a: O.mod_taper_apply(a, nx, nz, nxb, nzb, MOD_FAC, 1), None),
+                ("PP", "A", lambda a: O.mod_taper_apply(a, nx, nz, nxb, nzb, MOD_FAC, 2), None)]
+
+    _add("model_steps", deck, numerics, two_step, ins, dict(rec=("flat", (NT, nx), 9.0)), call, lambda v: dict(mod_chain(deck, numerics, v)), dialect=1)
+
+
+def _small_case(kind, deck, numerics=0):
+    nxe, nze, nxb, nzb, nx, nz = _dims(deck)
+    D = DECKS[deck]
+    DEC = 3
+
+    if kind == "taper_finalize":
+        ins = lambda i: dict(FLD=("field", i["p0"]))                                                                           # noqa: E731
+        outs = {}
+        call = lambda ctx, p, s: (ctx.dev_taper_finalize(p["FLD"], stream=s), [("field", "FLD", None, None)])[1]             # noqa: E731
+
+        def want(v):
+            i = inputs(deck, v)
+            f = np.array(i["p0"], np.float32, order="C")
+            oracle(deck, numerics).slab_step(0, f, np.array(i["pp0"], np.float32, order="C"), i["v2"], 0, 0, -1, 0, 0.0)      # one damping pass, no row stepped
+            return dict(field=f)
+    elif kind == "laplacian":
+        ins = lambda i: dict(IN=("field", i["lap_in"]))                                                                        # noqa: E731
+        outs = dict(LAP=("field", (nxe, nze), 7.0))
+        call = lambda ctx, p, s: (ctx.dev_laplacian(p["IN"], p["LAP"], stream=s), [("lap", "LAP", None, None)])[1]            # noqa: E731
+        want = lambda v: dict(lap=oracle_laplacian(8, nxe, nze, D["dx"], D["dz"], inputs(deck, v)["lap_in"], numerics))       # noqa: E731
+    elif kind in ("gather_residual", "gather_residual-in-place"):
+        inplace = kind.endswith("in-place")
+        ins = lambda i: dict(GA=("flat", i["ga"]), GB=("flat", i["gb"]))                                                       # noqa: E731
+        outs = {} if inplace else dict(OUT=("flat", (NT, nx), 9.0))
+        call = lambda ctx, p, s: (ctx.dev_gather_residual(p["GA"], p["GB"], p["GA" if inplace else "OUT"], NT * nx, stream=s),   # noqa: E731
+                                  [("resid", "GA" if inplace else "OUT", None, None)])[1]
+        want = lambda v: dict(resid=(inputs(deck, v)["ga"] - inputs(deck, v)["gb"]).astype(np.float32))                       # noqa: E731
+    else:
+        assert kind == "snapshot"
+        ins = lambda i: dict(FLD=("field", i["p0"]))                                                                           # noqa: E731
+        outs = dict(FRAME=("flat", (-(-nx // DEC), -(-nz // DEC)), 9.0))
+        call = lambda ctx, p, s: (ctx.dev_snapshot(p["FLD"], DEC, p["FRAME"], stream=s), [("frame", "FRAME", None, None)])[1]  # noqa: E731
+        want = lambda v: dict(frame=np.ascontiguousarray(inputs(deck, v)["p0"][nxb:nxb + nx:DEC, nzb:nzb + nz:DEC]))          # noqa: E731
+    _add(kind, deck, numerics, None, ins, outs, call, want)
+
+
+for _num in (0, 1):
+    _two_buffer_case("steps", "ragged", _num)
+    _two_buffer_case("steps_shrink", "ragged", _num)
+    for _kind in ("step_fwd", "step2"):
+        _pass_case(_kind, "ragged", _num)
+    _pass_case("step4", "stepped", _num)
+    for _kind in ("step_plain", "step_recv", "back_iter0", "back_iter1"):
+        _back_case(_kind, "ragged", _num)
+    _back_case("back4", "stepped", _num)
+    _model_case("ragged", _num, -1)
+    _small_case("laplacian", "ragged", _num)
+_pass_case("step4", "tiles", 0, ranges=dict(r0=16, r1=50, r0b=120, r1b=164))
+_pass_case("step4", "stepped", 0, ranges=dict(r0=0, r1=30, r0b=36, r1b=64))
+_back_case("back4", "tiles", 0)
+_back_case("back4", "stepped", 0, two_pass=True)
+_model_case("stepped", 0, 4)
+_model_case("tiles", 0, 4)
+for _kind in ("taper_finalize", "gather_residual", "gather_residual-in-place", "snapshot"):
+    _small_case(_kind, "ragged")
+
+BY_NAME = {c.name: c for c in CASES}
+assert len(BY_NAME) == len(CASES)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------
+# the late producer
+# ---------------------------------------------------------------------------------------------------------------------------------------
+class Delay:
+    """A kernel that keeps a stream busy for a given time: torch.cuda._sleep(cycles), calibrated once with two events; where that does not
+    hold a stream (it returned within a fifth of the time asked for), element-wise passes over a 256 MiB tensor calibrated the same way."""
+
+    def __init__(self, torch):
+        self.torch = torch
+        self.scratch = None
+        n = 20_000_000
+        torch.cuda._sleep(1000)
+        self.per_ms = n / self._time(lambda: torch.cuda._sleep(n))
+        if not 0.2 * 25.0 < self._time(lambda: torch.cuda._sleep(int(25.0 * self.per_ms))) < 5 * 25.0:
+            self.scratch = torch.zeros(64 << 20, device="cuda:0")
+            self.scratch.add_(1.0)
+            self.per_ms = 8 / self._time(lambda: [self.scratch.add_(1.0) for _ in range(8)])
+
+    def _time(self, fn):
+        torch = self.torch
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        return a.elapsed_time(b)
+
+    def __call__(self, ms):
+        """Enqueue ms milliseconds of delay on the current stream."""
+        k = max(1, int(ms * self.per_ms))
+        if self.scratch is None:
+            self.torch.cuda._sleep(k)
+        else:
+            for _ in range(k):
+                self.scratch.add_(1.0)
+
+
+WALLS = {}            # case name -> host milliseconds from the first enqueue on the stream to the return of the entry point
+
+
+class Run:
+    """One case behind a late producer.  Construction allocates and fills everything (decoys in the inputs, sentinels in the outputs, the true
+    inputs in staging tensors), makes the call once on the context's own stream so that no code object is loaded and nothing is allocated
+    inside the timed part, and puts the decoys and sentinels back; the caller then synchronises the device ONCE.  enqueue() issues delay,
+    producer copies, entry point and output copies on one stream; finish() synchronises that stream and compares with the oracle."""
+
+    def __init__(self, case, torch, ctx=None):
+        self.case, self.torch = case, torch
+        self.ctx = ctx or case.make_ctx()
+        self.nze = DECKS[case.deck]["geom"][1]
+        true, decoy = case.ins(inputs(case.deck, "true")), case.ins(inputs(case.deck, "decoy"))
+        self.dev, self.stage = {}, {}
+        for name, (kind, arr) in decoy.items():
+            self.dev[name] = self._up(kind, arr)
+            self.stage[name] = self._up(kind, true[name][1])
+        self.kinds = {name: kind for name, (kind, _) in decoy.items()}
+        for name, (kind, shape, val) in case.outs.items():
+            self.dev[name] = self._up(kind, np.full(shape, val, np.float32))
+            self.kinds[name] = kind
+        self.first = {name: t.clone() for name, t in self.dev.items()}
+        self.res = {name: torch.empty_like(t) for name, t in self.dev.items()}
+        self.ptr = {name: t.data_ptr() for name, t in self.dev.items()}
+        self.warm_labels = case.call(self.ctx, self.ptr, None)
+        torch.cuda.synchronize()
+        for name, t in self.dev.items():
+            t.copy_(self.first[name])
+
+    def _up(self, kind, arr):
+        torch = self.torch
+        a = torch.from_numpy(np.array(arr, np.float32, order="C")).to("cuda:0")
+        if kind == "flat":
+            return a
+        t = torch.zeros((a.shape[0], self.ctx.pitch), device="cuda:0")      # padding columns [nze, pitch) stay zero
+        t[:, :a.shape[1]] = a
+        return t
+
+    def enqueue(self, S, delay, ms, entry=None, collect=True):
+        """entry: the stream handed to the entry point (default S, the producer's own)."""
+        torch = self.torch
+        t0 = time.perf_counter()
+        with torch.cuda.stream(S):
+            delay(ms)
+            for name, t in self.stage.items():
+                self.dev[name].copy_(t, non_blocking=True)
+            self.labels = self.case.call(self.ctx, self.ptr, (entry or S).cuda_stream)
+            self.wall_ms = 1e3 * (time.perf_counter() - t0)
+            self.busy = not S.query()
+            if collect:
+                self.collect(S)
+        WALLS[self.case.name] = max(WALLS.get(self.case.name, 0.0), self.wall_ms)
+
+    def collect(self, S):
+        with self.torch.cuda.stream(S):
+            for name, t in self.dev.items():
+                self.res[name].copy_(t, non_blocking=True)
+
+    def results(self):
+        """{label: host array} of what the stream left, after the caller synchronised it."""
+        out = {}
+        for label, name, post, rows in self.labels:
+            a = self.res[name].cpu().numpy()
+            if self.kinds[name] == "field":
+                a = np.ascontiguousarray(a[:, :self.nze])
+            if post is not None:
+                a = post(a)
+            out[label] = a if rows is None else a[rows]
+        return out
+
+    def close(self):
+        self.ctx.close()
