@@ -244,8 +244,9 @@ constexpr int zgroup_prod(int g, int j, bool want_ic)
 // The lane's four cells at once (the four-step kernel, EXACT).  x half: two packed chains, as laplacian_pair.  z half: the products are
 // SHARED between lanes.  Tap d of cell j is W[j + d] * cz[H - |d|], the same rounded fp32 product that cell j + 2d forms for its tap -d, so
 // a lane multiplies only its OWN four values by the H + 1 distinct weights: 20 products, no window of neighbour values.  Cell e's chain,
-// 0 + term 0 + ... + term 8 in io order with every add rounded (bit-identical to laplacian_pt), runs in three parts:
-//   * terms 0 .. 3-e are the LEFT lane's products: that lane sums them, from 0, for its right neighbour (the prefix sums pa, pb);
+// term 0 + ... + term 8 in io order with every add rounded (bit-identical to laplacian_pt's 0 + term 0 + ... once the halves are added: see
+// the prefix sums below), runs in three parts:
+//   * terms 0 .. 3-e are the LEFT lane's products: that lane sums them for its right neighbour (the prefix sums pa, pb);
 //   * that partial sum enters as the DPP operand of the add of this lane's first term (v_add_f32_dpp wave_shr:1);
 //   * terms 8-e .. 8 are the RIGHT lane's products, each the DPP operand of its add (wave_shl:1).
 // lane_up / lane_down feeding an add fold into v_add_f32_dpp: no lane moves.  Lanes 0 / 63 read 0 for the missing neighbour (halo lanes).
@@ -281,9 +282,15 @@ __device__ __forceinline__ void laplacian_quad(const f4& c, Row&& row, const Coe
             ax1 = ax1 + m1;
         });
         constexpr int a = g, b = g + 2;                         // prefix sums: terms io = 0 .. 3-e of the right neighbour's cell e
-        float pa = 0.0f, pb = 0.0f;
-        static_for<4 - a>([&](auto S) {
-            constexpr int s = decltype(S)::value;
+        // They start from term 0, not from 0 + term 0 as the reference's chain does.  The leading zero only turns -0 into +0: a chain that
+        // starts from +0 is never -0 (+0 + -0 = +0 and an exact cancellation gives +0 in round-to-nearest), and the chain without it has the
+        // same bits unless all nine terms are -0, where it is -0 instead of +0.  The z half meets the x half in one add, az + ax, and the x
+        // half KEEPS its zero (ax0, ax1 above), so ax is never -0 and ax + (-0) == ax + (+0) bit for bit for every ax it can be (+0, NaN and
+        // +-inf included).  Dropping the zero from both halves would be wrong: over an all-(-0) neighbourhood the Laplacian would be -0.
+        // (Dropped here and not there: four v_add_f32 per row against two v_pk_add_f32.)
+        float pa = qz[a][0], pb = qz[b][0];
+        static_for<3 - a>([&](auto S) {
+            constexpr int s = decltype(S)::value + 1;
             pa = pa + qz[a + s][s];
             if constexpr (s < 4 - b) pb = pb + qz[b + s][s];
         });

@@ -16,11 +16,14 @@ namespace fdw {
 // produced during step m-1 (its result row r_{k-1}(m-1) = r_k(m)+H, which enters wave k's window, and the
 // row its own window dropped, r_{k-1}(m-1)-H = r_k(m), which is wave k's "pp") is consumed during step m;
 // one workgroup barrier per march step separates producer and consumer, link buffers alternate by the parity
-// of m.  v2 dt2 rows (formed once, by wave 0) ride a 16-row LDS FIFO.  In the FULL body all waves run identical code: the global loads of
-// waves k > 0 are sent out of range through the buffer descriptor (no memory request, zeros returned) and the stores of waves < NS-2
-// likewise, so the s_waitcnt counting stays exact and nothing diverges.  Workgroups away from the frame of the grid, the damped strip and
-// the sources -- nine in ten on a large grid -- run the LEAN body instead (pipe_lean: no masks, clamps, damping or injection code), which
-// is compiled once for wave 0 and once for the other waves (WK: no selects between "from memory" and "from LDS", no switched-off loads).
+// of m.  v2 dt2 rows (formed once, by wave 0) ride a 16-row LDS FIFO.  Where all waves run ONE body (WK 0: the modelling dialect, the receiver
+// field, the recording and illumination full bodies) the global loads of waves k > 0 are sent out of range through the buffer descriptor
+// (no memory request, zeros returned) and the stores of waves < NS-2 likewise, so the s_waitcnt counting stays exact and nothing diverges.
+// Workgroups away from the frame of the grid, the damped strip and the sources -- nine in ten on a large grid -- run the LEAN body instead
+// (pipe_lean: no masks, clamps, damping or injection code).  The lean body and the forward kernel's full body are compiled once for wave 0
+// and once for the other waves (WK 1 / 2: no selects between "from memory" and "from LDS", no switched-off loads); there the forward kernels
+// issue no switched-off store either: wave 0's body holds none, and in the other waves' body, which issues no global loads whose count a
+// branch could split, the store sits behind a scalar branch on k that wave 1 skips.
 // Validity: wave k's rows are good from march step k(2H+1) on (its window then holds only good rows of wave
 // k-1); in z every step costs H = one lane per side, so NS lanes per side of a wave are halo and 64-2NS owned.
 // Per point and step the arithmetic is the one-step kernel's (packed pairs as in the two-step kernel).
@@ -306,8 +309,15 @@ __device__ __forceinline__ void marchn(const Step2Args& a, const int lane, const
 #pragma unroll
             for (int e = 0; e < 4; ++e) asm volatile("" : "=v"(u.v[e]));      // defined (no instruction) on the path that skips the row
         }
-        const unsigned so = (act && (r >= xa) && (r < xe) && (m < M)) ? soff : kLaneOff;
-        f4_store_arr(rs_out, so, rowoff(r), u);
+        // The field store.  Forward kernels (BK 0) keep the last two levels only: the body compiled for wave 0 holds no store at all, the
+        // body of the other waves holds it behind a scalar branch that wave 1 skips (k is wave-uniform; this body issues no global loads,
+        // so no load count crosses the branch).  Everywhere else every wave issues it and switches its lanes off through the offset.
+        if constexpr (!(BK == 0 && WK == 1 && NS > 2)) {
+            if (!(BK == 0 && WK == 2) || k >= NS - 2) {
+                const unsigned so = (act && (r >= xa) && (r < xe) && (m < M)) ? soff : kLaneOff;
+                f4_store_arr(rs_out, so, rowoff(r), u);
+            }
+        }
         if constexpr (REC)
             f1_store_arr(array_rsrc(a.rec + (size_t)k * a.rec_n, (unsigned)a.rec_n * 4u),
                          rec_offset(rec_lane && act && (r >= xa) && (r < xe) && (m < M), r, a.rec_x0, a.rec_n), f4_pick(u, a.rec_z & 3));
