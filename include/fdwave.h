@@ -303,12 +303,27 @@ int fdw_download_field(fdw_ctx *ctx, float *h_dst, const float *d_src);
  *                           [draw_offset + b T, ...) drawn on the device.  Results are those of the shots run one by one, bit for bit;
  *                           contexts whose regime the batched launches do not cover (large grids, orders above 8, receiver rows
  *                           outside the truncated extents) run them one by one.
- * fdw_shot_batch_max        batch size that fills the chip for this geometry (1: batching gains nothing)
+ * fdw_shot_batch_max        batch size that fills the chip for this geometry (1: batching gains nothing), at most what the batch budget
+ *                           holds of fdw_shot_batch's eleven fields per shot
+ * fdw_set_batch_budget      bytes the buffers of a batch may take; 0 = the default.  The budget in force is, in this order: the value set
+ *                           here if non-zero, else the environment variable FDW_BATCH_BUDGET_BYTES (a decimal byte count, read at every
+ *                           call; unset, empty, zero or unparsable: ignored), else 6 GiB.  So the call wins over the environment (unlike
+ *                           FDW_STORE_BUDGET_MB, which overrides fdw_set_store_budget).  Only this call writes the context's value.
+ *                           NULL context: FDW_EINVAL.  It bounds fdw_shot_batch_max and the parts below; results never depend on it.
+ * fdw_batch_parts           how many batched launch sequences the last batched call on this context went through: 0 = its shots ran one
+ *                           by one (nshots == 1, a regime the batched launches do not cover, or no room on the device), 1 = the whole
+ *                           batch at once, k = k parts (a last part of a single shot counts).  Written by every batched call.
+ * Who splits.  fdw_shot_batch_illum, fdw_shot_batch_residual, fdw_shot_line_batch and fdw_shot_line_batch_residual hold more per shot than
+ * the eleven fields fdw_shot_batch_max counts and cut a batch that exceeds the budget into parts themselves.  fdw_shot_batch,
+ * fdw_record_shot_batch, fdw_record_shot_line_batch and fdw_model_shot_batch have NO part loop: they take `nshots` whole, whatever the
+ * budget says (fdw_batch_parts 1 or 0); their callers walk the shots in groups of at most fdw_shot_batch_max.
  */
 long long fdw_border_draws(int nx, int nz, int nxb, int nzb);
 int fdw_shot_batch(fdw_ctx *ctx, int nshots, const float *v2_all, unsigned long long draw_offset, int sx0, int dsx, int sz, int gz,
                    const float *srce, const float *d_obs, float *imloc);
 int fdw_shot_batch_max(const fdw_ctx *ctx);
+int fdw_set_batch_budget(fdw_ctx *ctx, size_t bytes);
+int fdw_batch_parts(const fdw_ctx *ctx);
 /* mod_main's shot loop (mod_main.cpp:140-174) for `nshots` consecutive shots (source rows sx0 + b dsx, M:99-101) on its one velocity
  * model, one launch per time step for all of them; data[nshots][nx][nt].  Same results as fdw_model_shot per shot, bit for bit. */
 int fdw_model_shot_batch(fdw_ctx *ctx, int nshots, const float *vel2, int sx0, int dsx, int sz, int gz, const float *srce, int nt, float *data);

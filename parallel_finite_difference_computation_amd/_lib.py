@@ -74,6 +74,8 @@ SIGNATURES = [
     ("fdw_shot_resident", C.c_int, [vp, C.c_int, C.c_int, C.c_int, f32p, f32p, f32p, vp, vp]),
     ("fdw_shot_batch", C.c_int, [vp, C.c_int, vp, C.c_ulonglong, C.c_int, C.c_int, C.c_int, C.c_int, f32p, f32p, f32p]),
     ("fdw_shot_batch_max", C.c_int, [vp]),
+    ("fdw_set_batch_budget", C.c_int, [vp, C.c_size_t]),
+    ("fdw_batch_parts", C.c_int, [vp]),
     ("fdw_model_shot_batch", C.c_int, [vp, C.c_int, f32p, C.c_int, C.c_int, C.c_int, C.c_int, f32p, C.c_int, f32p]),
     ("fdw_dev_record_steps", C.c_int, [vp, C.POINTER(vp), vp, vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), vp]),
     ("fdw_record_shot", C.c_int, [vp, f32p, C.c_int, C.c_int, C.c_int, f32p, f32p, vp, vp]),

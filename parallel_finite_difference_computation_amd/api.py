@@ -580,6 +580,15 @@ class FDWave:
         """Segments the last rtm_stored_shot was cut into (1: every field was kept)."""
         return int(lib().fdw_store_segments(self._h))
 
+    def set_batch_budget(self, nbytes):
+        """Bytes the buffers of a batch of shots may take (0: FDW_BATCH_BUDGET_BYTES if set, else 6 GiB; a non-zero value wins over the
+        environment).  It bounds shot_batch_max() and the parts the batched calls cut a batch into (fdwave.h); results never depend on it."""
+        check(lib().fdw_set_batch_budget(self._h, int(nbytes)))
+
+    def batch_parts(self):
+        """Batched launch sequences of the last batched call (0: its shots ran one by one, 1: the whole batch at once, k: k parts)."""
+        return int(lib().fdw_batch_parts(self._h))
+
     def field_bytes(self):
         return int(lib().fdw_field_bytes(self._h))
 

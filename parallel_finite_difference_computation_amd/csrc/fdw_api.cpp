@@ -103,6 +103,9 @@ struct fdw_ctx {
     int no_back_fused = 0;   // experiments / tests: the backward pipeline as two passes (source field, receiver field) instead of the fused kernel -- FDW_NO_BACK_FUSED=1
     size_t store_budget = 0; // fdw_rtm_stored_shot: bytes the stored source fields may take (0: whatever the device grants); fdw_set_store_budget
     int store_segments = 0;  // ... segments the last such shot was cut into (1: every field kept)
+    size_t batch_budget = 0; // bytes a batch of shots may take (0: FDW_BATCH_BUDGET_BYTES, else 6 GiB); written by fdw_set_batch_budget alone
+    int batch_parts = 0;     // batched launch sequences of the last batched call (0: its shots ran one by one); fdw_batch_parts
+    bool batch_single = false;      // inside a batched call: a part of more than one shot ran its shots one by one
 };
 
 static size_t field_elems(const fdw_ctx* c) { return (size_t)c->nxl * (size_t)c->pitch; }
@@ -1829,6 +1832,39 @@ extern "C" int fdw_set_store_budget(fdw_ctx* c, size_t bytes)
 }
 extern "C" int fdw_store_segments(const fdw_ctx* c) { return c ? c->store_segments : 0; }
 
+extern "C" int fdw_set_batch_budget(fdw_ctx* c, size_t bytes)
+{
+    if (!c) return fail(FDW_EINVAL, "ctx is NULL");
+    c->batch_budget = bytes;
+    return FDW_OK;
+}
+extern "C" int fdw_batch_parts(const fdw_ctx* c) { return c ? c->batch_parts : 0; }
+
+// The bytes a batch of shots may take: the context's own value (fdw_set_batch_budget) if non-zero, else FDW_BATCH_BUDGET_BYTES (a decimal
+// byte count read at every call; empty, zero or anything else counts as unset), else 6 GiB.
+static size_t batch_budget(const fdw_ctx* c)
+{
+    if (c->batch_budget) return c->batch_budget;
+    if (const char* e = getenv("FDW_BATCH_BUDGET_BYTES")) {
+        char* end = nullptr;
+        const unsigned long long v = strtoull(e, &end, 10);
+        if (*e >= '0' && *e <= '9' && *end == '\0' && v > 0) return (size_t)v;
+    }
+    return (size_t)6 << 30;
+}
+
+// fdw_batch_parts' bookkeeping.  Every batched entry point brackets its parts with batch_begin / batch_end; every part says how it ran
+// (batch_part_ran): a part that could not go through the batched launches although it holds more than one shot (!batch_ok, no room)
+// makes the call count as "one by one".  A part of a single shot inside a larger batch is a launch sequence like any other.
+static void batch_begin(fdw_ctx* c) { c->batch_parts = 0; c->batch_single = false; }
+static void batch_part_ran(fdw_ctx* c, bool batched_path) { c->batch_parts++; c->batch_single = c->batch_single || !batched_path; }
+static int batch_end(fdw_ctx* c, int nshots, int rc)
+{
+    if (nshots <= 1 || c->batch_single) c->batch_parts = 0;
+    c->batch_single = false;
+    return rc;
+}
+
 extern "C" int fdw_set_tuning(fdw_ctx* c, int xchunk, int wz, int use_generic, int prefetch, int two_step)
 {
     if (!c) return fail(FDW_EINVAL, "ctx is NULL");
@@ -2438,7 +2474,7 @@ extern "C" int fdw_shot_batch_max(const fdw_ctx* c)
     if (!c || !is_full_grid(c) || !batch_ok(c)) return 1;
     const long waves = (long)c->nxl * ((c->pitch + 255) / 256);        // one-row-per-wave regime: waves one shot launches
     const long by_fill = 32768 / std::max<long>(waves, 1);            // measured on new_mod-sized shots: 18.6 ms per shot alone, 5.6 at 8, 4.4 at 16, 3.7 at 32
-    const long by_mem = (long)(((size_t)6 << 30) / (11 * field_elems(c) * sizeof(float)));
+    const long by_mem = (long)(batch_budget(c) / (11 * field_elems(c) * sizeof(float)));
     return (int)std::max<long>(1, std::min<long>({by_fill, by_mem, 64}));
 }
 
@@ -2589,13 +2625,16 @@ static int shot_batch_impl(fdw_ctx* c, const char* who, int nshots, const float*
         }
         return (int)FDW_OK;
     };
-    if (nshots == 1 || !batch_ok(c)) return one_by_one();      // nothing to gain or a regime the batched launches do not cover
+    auto fallback = [&] { batch_part_ran(c, false); return one_by_one(); };
+    if (!batch_ok(c)) return fallback();      // a regime the batched launches do not cover
+    if (nshots == 1) { batch_part_ran(c, true); return one_by_one(); }      // nothing to gain
     int rc;
     if ((rc = ensure_work_buffers(c, 8, true))) return rc;
-    if ((rc = ensure_batch_buffers(c, nshots, true)) == FDW_ENOMEM) return one_by_one();      // no room for the batch
-    if (!rc && illum && (rc = ensure_batch_illum(c, nshots)) == FDW_ENOMEM) return one_by_one();      // ... or for its accumulators
-    if (!rc && residual && (rc = ensure_cap(&c->b_rec, &c->b_rec_cap, ng * nshots)) == FDW_ENOMEM) return one_by_one();      // ... or its modelled gathers
-    if (!rc && line && (rc = ensure_cap(&c->b_wav, &c->b_wav_cap, ng * nshots)) == FDW_ENOMEM) return one_by_one();      // ... or its line-source gathers
+    if ((rc = ensure_batch_buffers(c, nshots, true)) == FDW_ENOMEM) return fallback();      // no room for the batch
+    if (!rc && illum && (rc = ensure_batch_illum(c, nshots)) == FDW_ENOMEM) return fallback();      // ... or for its accumulators
+    if (!rc && residual && (rc = ensure_cap(&c->b_rec, &c->b_rec_cap, ng * nshots)) == FDW_ENOMEM) return fallback();      // ... or its modelled gathers
+    if (!rc && line && (rc = ensure_cap(&c->b_wav, &c->b_wav_cap, ng * nshots)) == FDW_ENOMEM) return fallback();      // ... or its line-source gathers
+    if (!rc) batch_part_ran(c, true);
     if (rc || (rc = line ? gathers_to_device(c, wav_all, c->b_wav, nshots) : upload_source(c, srce, nt))) return rc;
     hipStream_t s = c->stream;
     if ((rc = gathers_to_device(c, d_obs, c->b_dobs, nshots))) return rc;      // [shot][nx][nt] -> [shot][nt][nx]
@@ -2626,15 +2665,17 @@ static int shot_batch_impl(fdw_ctx* c, const char* who, int nshots, const float*
 extern "C" int fdw_shot_batch(fdw_ctx* c, int nshots, const float* v2_all, unsigned long long draw_offset, int sx0, int dsx, int sz, int gz,
                               const float* srce, const float* d_obs, float* imloc)
 {
-    return shot_batch_impl(c, "fdw_shot_batch", nshots, v2_all, draw_offset, sx0, dsx, sz, gz, srce, d_obs, imloc, nullptr);
+    if (!c) return fail(FDW_EINVAL, "NULL argument");
+    batch_begin(c);
+    return batch_end(c, nshots, shot_batch_impl(c, "fdw_shot_batch", nshots, v2_all, draw_offset, sx0, dsx, sz, gz, srce, d_obs, imloc, nullptr));
 }
 
-// How many shots of a batch go through at once: what the budget fdw_shot_batch_max counts with (6 GiB) holds of `fields` fields and `gathers`
+// How many shots of a batch go through at once: what the budget fdw_shot_batch_max counts with (batch_budget) holds of `fields` fields and `gathers`
 // gathers [nt][nx] per shot.  A larger batch goes through in parts of that size: the parts are independent, the bytes the same.
 static int batch_part(const fdw_ctx* c, int nshots, int fields, int gathers)
 {
     const size_t ng = (size_t)c->nx * c->prm.nt;
-    const long by_mem = (long)(((size_t)6 << 30) / (((size_t)fields * field_elems(c) + (size_t)gathers * ng) * sizeof(float)));
+    const long by_mem = (long)(batch_budget(c) / (((size_t)fields * field_elems(c) + (size_t)gathers * ng) * sizeof(float)));
     return (int)std::max<long>(1, std::min<long>(by_mem, nshots));
 }
 
@@ -2650,12 +2691,13 @@ extern "C" int fdw_shot_batch_illum(fdw_ctx* c, int nshots, const float* v2_all,
     const int part = batch_part(c, nshots, 12, 0);
     const size_t ni = (size_t)c->nx * c->nz, ne = (size_t)c->prm.nxe * c->prm.nze, ng = (size_t)c->nx * c->prm.nt;
     const unsigned long long draws = (unsigned long long)fdw_border_draws(c->nx, c->nz, c->prm.nxb, c->prm.nzb);
+    batch_begin(c);
     for (int b0 = 0; b0 < nshots; b0 += part) {
         const int nb = std::min(part, nshots - b0);
         FDW_TRY(shot_batch_impl(c, "fdw_shot_batch_illum", nb, v2_all ? v2_all + b0 * ne : nullptr, draw_offset + b0 * draws, sx0 + b0 * dsx, dsx, sz, gz,
                                 srce, d_obs ? d_obs + b0 * ng : nullptr, imloc ? imloc + b0 * ni : nullptr, illum + b0 * ni));
     }
-    return FDW_OK;
+    return batch_end(c, nshots, FDW_OK);
 }
 
 // fdw_shot_batch whose forward loop also records every shot's modelled gather (and, with illum, accumulates its illumination in the same
@@ -2671,13 +2713,14 @@ extern "C" int fdw_shot_batch_residual(fdw_ctx* c, int nshots, const float* v2_a
     const size_t ni = (size_t)c->nx * c->nz, ne = (size_t)c->prm.nxe * c->prm.nze, ng = (size_t)c->nx * c->prm.nt;
     const int part = batch_part(c, nshots, illum ? 12 : 11, 1);
     const unsigned long long draws = (unsigned long long)fdw_border_draws(c->nx, c->nz, c->prm.nxb, c->prm.nzb);
+    batch_begin(c);
     for (int b0 = 0; b0 < nshots; b0 += part) {
         const int nb = std::min(part, nshots - b0);
         FDW_TRY(shot_batch_impl(c, "fdw_shot_batch_residual", nb, v2_all ? v2_all + b0 * ne : nullptr, draw_offset + b0 * draws, sx0 + b0 * dsx, dsx, sz,
                                 gz, srce, d_obs ? d_obs + b0 * ng : nullptr, imloc ? imloc + b0 * ni : nullptr, illum ? illum + b0 * ni : nullptr, true,
                                 resid ? resid + b0 * ng : nullptr));
     }
-    return FDW_OK;
+    return batch_end(c, nshots, FDW_OK);
 }
 
 // ---- batches of line-source shots (definitions in fdwave.h) ----
@@ -2694,13 +2737,14 @@ static int shot_line_batch(fdw_ctx* c, const char* who, int nshots, const float*
     const size_t ni = (size_t)c->nx * c->nz, ne = (size_t)c->prm.nxe * c->prm.nze, ng = (size_t)c->nx * c->prm.nt;
     const int part = batch_part(c, nshots, illum ? 12 : 11, residual ? 2 : 1);
     const unsigned long long draws = (unsigned long long)fdw_border_draws(c->nx, c->nz, c->prm.nxb, c->prm.nzb);
+    batch_begin(c);
     for (int b0 = 0; b0 < nshots; b0 += part) {
         const int nb = std::min(part, nshots - b0);
         FDW_TRY(shot_batch_impl(c, who, nb, v2_all ? v2_all + b0 * ne : nullptr, draw_offset + b0 * draws, 0, 0, sz, gz, nullptr,
                                 d_obs ? d_obs + b0 * ng : nullptr, imloc ? imloc + b0 * ni : nullptr, illum ? illum + b0 * ni : nullptr, residual,
                                 resid ? resid + b0 * ng : nullptr, wav_all + b0 * ng));
     }
-    return FDW_OK;
+    return batch_end(c, nshots, FDW_OK);
 }
 
 extern "C" int fdw_shot_line_batch(fdw_ctx* c, int nshots, const float* v2_all, unsigned long long draw_offset, int sz, int gz, const float* wav_all,
@@ -2743,10 +2787,12 @@ static int record_batch_impl(fdw_ctx* c, int nshots, const float* v2_all, unsign
         }
         return (int)FDW_OK;
     };
+    batch_begin(c);
     if (nshots == 1 || !batch_ok(c)) return one_by_one();
     int rc;
     if ((rc = ensure_batch_buffers(c, nshots, true)) == FDW_ENOMEM) return one_by_one();
     if (!rc && line && (rc = ensure_cap(&c->b_wav, &c->b_wav_cap, ng * nshots)) == FDW_ENOMEM) return one_by_one();
+    if (!rc) batch_part_ran(c, true);      // no part loop here: the whole batch or, above, the shots one by one (fdw_batch_parts 1 or 0)
     if (rc || (rc = line ? gathers_to_device(c, wav_all, c->b_wav, nshots) : upload_source(c, srce, nt)) || (rc = batch_models(c, nshots, v2_all, draw_offset)))
         return rc;
     hipStream_t s = c->stream;
@@ -2794,11 +2840,13 @@ extern "C" int fdw_model_shot_batch(fdw_ctx* c, int nshots, const float* vel2, i
         for (int b = 0; b < nshots; b++) FDW_TRY(fdw_model_shot(c, vel2, sx0 + b * dsx, sz, gz, srce, nt, data + b * ng));
         return (int)FDW_OK;
     };
+    batch_begin(c);
     if (nshots == 1 || nt == 0 || nt > c->prm.nt || !batch_ok(c)) return one_by_one();
     HIP_TRY(hipSetDevice(c->device));
     int rc;
     if ((rc = ensure_work_buffers(c, 2, false))) return rc;
     if ((rc = ensure_batch_buffers(c, nshots, false)) == FDW_ENOMEM) return one_by_one();      // no room for the batch: the shots one after the other
+    if (!rc) batch_part_ran(c, true);      // no part loop here either
     if (rc || (rc = upload_source(c, srce, nt))) return rc;
     if ((rc = ensure_cap(&c->d_raw, &c->raw_cap, ng * nshots))) return rc;
     hipStream_t s = c->stream;

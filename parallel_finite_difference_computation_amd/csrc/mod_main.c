@@ -99,6 +99,9 @@ int main(int argc, char **argv)
     /* small decks: a batch of shots per launch (fdw_shot_batch_max says how many fill the chip; 1 = the grid is big enough alone) */
     int bmax = getenv("FDW_NO_SHOT_BATCH") ? 1 : fdw_shot_batch_max(ctx);
     if (bmax < 1) bmax = 1;
+    if (getenv("FDW_TIMING"))      /* as rtm_code says it: how many shots advance through one launch per time step */
+        fprintf(stderr, "[timing] shots per launch sequence: up to %d (%s)\n", bmax < ns ? bmax : ns,
+                bmax > 1 && ns > 1 ? "fdw_model_shot_batch" : "one by one");
     for (int is0 = 0; is0 < ns; is0 += bmax) {
         const int nb = is0 + bmax <= ns ? bmax : ns - is0;
         for (int is = is0; is < is0 + nb; is++) printf("** source %d, at (%d,%d) \n", is + 1, fsx + is * ds, sz - nzb); /* M:99-101 */

@@ -377,6 +377,8 @@ int main(int argc, char **argv)
         }
         int batch = ok ? fdw_shot_batch_max(ctx) : 1;
         if (batch > ns) batch = ns;
+        if (ok && getenv("FDW_TIMING"))      /* as rtm_code says it: how many shots advance through one launch per time step */
+            fprintf(stderr, "[timing] shots per launch sequence: up to %d (%s)\n", batch, batch > 1 ? "fdw_record_shot_batch" : "one by one");
         float *data = (float *)malloc((size_t)batch * ng * sizeof(float));
         float *v2_all = dev_border ? NULL : (float *)malloc((size_t)batch * ne * sizeof(float));
         if (ok && (!data || (!dev_border && !v2_all))) {

@@ -54,7 +54,12 @@ def _one_by_one(ctx, ns, dsx, srce, d_obs, im0, il0, v2_all=None, draw_offset=0)
 
 
 def test_shot_batch_illum_is_exported():
-    assert hasattr(F.lib(), "fdw_shot_batch_illum")
+    import ctypes as C
+    L = F.lib()
+    assert hasattr(L, "fdw_shot_batch_illum")
+    # the batch budget and the part count (tests/test_batch_parts.py), with their signatures
+    assert L.fdw_set_batch_budget.argtypes == [C.c_void_p, C.c_size_t] and L.fdw_set_batch_budget.restype is C.c_int
+    assert L.fdw_batch_parts.argtypes == [C.c_void_p] and L.fdw_batch_parts.restype is C.c_int
 
 
 @pytest.mark.gpu

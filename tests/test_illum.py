@@ -595,3 +595,26 @@ def test_rtm_code_illum_key(tmp_path):
     again, _ = _run_rtm_code(tmp_path / "on", {"FDW_SHOT_WORKERS": "1"})
     for name in ("dir.image", "dir.illum", "dir.image_illum"):
         assert again[name] == on[name], name
+
+
+@pytest.mark.gpu
+def test_rtm_code_illum_in_groups_of_two_shots(tmp_path):
+    """illum=1 under a batch budget that lets fdw_shot_batch_max be 2 (groups {0, 1}, {2, 3}, {4} through fdw_shot_batch_illum): dir.image,
+    dir.illum and dir.image_illum against the oracle's shot loop stacked in shot order, every file against the run one shot at a time."""
+    import batch_groups as G
+    nx, nz, nxb, nzb, nt, ns, vp, d_obs, _ = G.five_shot_case(tmp_path / "grouped", extra="illum=1\n")
+    G.five_shot_case(tmp_path / "single", extra="illum=1\n")
+    grouped, r = G.run_program("rtm_code", tmp_path / "grouped", G.group_env(nx + 2 * nxb, nz + 2 * nzb, nxb, nzb, nt))
+    G.assert_grouped(r.stderr, "fdw_shot_batch_illum")
+    want = G.five_shot_oracle()
+    img, ill = G.stack(want["image"]), G.stack(want["illum"])
+    assert_bit_equal(np.frombuffer(grouped["dir.image"], np.float32).reshape(nx, nz), img, "dir.image")
+    assert_bit_equal(np.frombuffer(grouped["dir.illum"], np.float32).reshape(nx, nz), ill, "dir.illum")
+    assert_bit_equal(np.frombuffer(grouped["dir.image_illum"], np.float32), compensate_formula(img.ravel(), ill.ravel(), 1e-3), "dir.image_illum")
+    assert ill.max() > 0 and all((want["illum"][s] != want["illum"][t]).any() for s in range(ns) for t in range(s))
+    single, r1 = G.run_program("rtm_code", tmp_path / "single", {"FDW_NO_SHOT_BATCH": "1", "FDW_TIMING": "1"})
+    G.assert_grouped(r1.stderr, "one by one", 1)
+    assert sorted(grouped) == sorted(single)
+    for name in single:
+        assert grouped[name] == single[name], name
+    assert (tmp_path / "grouped" / "image.num").read_bytes() == (tmp_path / "single" / "image.num").read_bytes()

@@ -630,14 +630,10 @@ def test_python_driver_refuses_a_pw_deck(tmp_path):
         rtm.read_deck(str(tmp_path / "input.dat"))
 
 
-@pytest.mark.gpu
-@pytest.mark.parametrize("with_vel_ext,npw", [(False, 3), (True, 4)], ids=["border-stream-pw3", "vel-ext-pw4"])
-def test_rtm_code_plane_waves_equal_the_python_composition(tmp_path, with_vel_ext, npw):
-    """dir.image (and, with illum=1, dir.illum / dir.image_illum) of a pw= deck against the same composition through the Python API: lags,
-    source gather, data gather, the model of plane wave j (the next draw of the border stream / vel_ext model j mod ns), shot_line, stacked
-    in the order j."""
-    nx, nz, nxb, nzb, nt, ns, vp, d_obs, vel_ext = _pw_deck(tmp_path, f"pw={npw}\npw_pmax={PW_PMAX}\n", with_vel_ext)
+def pw_composition(nx, nz, nxb, nzb, nt, ns, vp, d_obs, vel_ext, npw):
+    """(dir.image, dir.illum) of a pw= deck of _pw_deck through the Python API, one plane wave after the other, stacked in the order j."""
     nxe, nze = nx + 2 * nxb, nz + 2 * nzb
+    with_vel_ext = vel_ext is not None
     ctx = F.FDWave(8, nxe, nze, nxb, nzb, nt, 0.75, 10.0, 10.0, 0.001, compat=True, device=0)
     srce = F.ricker_wavelet(nt, 0.001, 25.0)
     src_ix = 5 + 20 * np.arange(ns)
@@ -660,6 +656,18 @@ def test_rtm_code_plane_waves_equal_the_python_composition(tmp_path, with_vel_ex
         im, il = ctx.shot_line(v2, 1 + nzb, 2 + nzb, wav, enc, want_illum=True)
         img, ill = img + im, ill + il
     assert len(seen) >= 3 and np.abs(img).max() > 0
+    ctx.close()
+    return img, ill
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("with_vel_ext,npw", [(False, 3), (True, 4)], ids=["border-stream-pw3", "vel-ext-pw4"])
+def test_rtm_code_plane_waves_equal_the_python_composition(tmp_path, with_vel_ext, npw):
+    """dir.image (and, with illum=1, dir.illum / dir.image_illum) of a pw= deck against the same composition through the Python API: lags,
+    source gather, data gather, the model of plane wave j (the next draw of the border stream / vel_ext model j mod ns), shot_line, stacked
+    in the order j."""
+    nx, nz, nxb, nzb, nt, ns, vp, d_obs, vel_ext = _pw_deck(tmp_path, f"pw={npw}\npw_pmax={PW_PMAX}\n", with_vel_ext)
+    img, ill = pw_composition(nx, nz, nxb, nzb, nt, ns, vp, d_obs, vel_ext, npw)
     r = _run_rtm_code(tmp_path)
     assert r.returncode == 0, r.stderr + r.stdout
     assert f"** plane wave {npw}" in r.stdout and "> Exec time" in r.stdout
@@ -679,3 +687,30 @@ def test_rtm_code_plane_waves_equal_the_python_composition(tmp_path, with_vel_ex
         r = _run_rtm_code(tmp_path, {"FDW_HOST_BORDER": "1"})
         assert r.returncode == 0, r.stderr
         assert_bit_equal(np.fromfile(tmp_path / "output" / "dir.image", np.float32).reshape(nx, nz), img, "dir.image with FDW_HOST_BORDER=1")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("with_vel_ext", [False, True], ids=["border-stream", "vel-ext"])
+def test_rtm_code_takes_five_plane_waves_in_groups_of_two(tmp_path, with_vel_ext):
+    """pw=5 under a batch budget that lets fdw_shot_batch_max be 2: fdw_shot_line_batch takes plane waves {0, 1}, {2, 3}, {4}, each group its
+    own line gathers, encoded data, models (draws from j0 T on) and image slots.  dir.image, dir.illum and dir.image_illum against the
+    composition plane wave by plane wave, every file and stdout against the run with FDW_NO_SHOT_BATCH=1."""
+    import batch_groups as G
+    keys = f"pw=5\npw_pmax={PW_PMAX}\nillum=1\n"
+    (tmp_path / "grouped").mkdir()
+    (tmp_path / "single").mkdir()
+    nx, nz, nxb, nzb, nt, ns, vp, d_obs, vel_ext = _pw_deck(tmp_path / "grouped", keys, with_vel_ext)
+    _pw_deck(tmp_path / "single", keys, with_vel_ext)
+    img, ill = pw_composition(nx, nz, nxb, nzb, nt, ns, vp, d_obs, vel_ext, 5)
+    grouped, r = G.run_program("rtm_code", tmp_path / "grouped", G.group_env(nx + 2 * nxb, nz + 2 * nzb, nxb, nzb, nt))
+    G.assert_grouped(r.stderr, "fdw_shot_line_batch")
+    assert_bit_equal(np.frombuffer(grouped["dir.image"], np.float32).reshape(nx, nz), img, "dir.image")
+    assert_bit_equal(np.frombuffer(grouped["dir.illum"], np.float32).reshape(nx, nz), ill, "dir.illum")
+    assert_bit_equal(np.frombuffer(grouped["dir.image_illum"], np.float32).reshape(nx, nz), F.image_compensate(img, ill, 1e-3), "dir.image_illum")
+    single, r1 = G.run_program("rtm_code", tmp_path / "single", {"FDW_NO_SHOT_BATCH": "1", "FDW_TIMING": "1"})
+    G.assert_grouped(r1.stderr, "one by one", 1)
+    assert sorted(grouped) == sorted(single)
+    for name in single:
+        assert grouped[name] == single[name], name
+    assert (tmp_path / "grouped" / "image.num").read_bytes() == (tmp_path / "single" / "image.num").read_bytes()
+    assert G.without_exec_time(r.stdout) == G.without_exec_time(r1.stdout)

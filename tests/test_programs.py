@@ -174,6 +174,33 @@ def test_rtm_code_program_vs_oracle_pipeline(tmp_path, with_vel_ext):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("mode", ["device-border", "vel-ext", "host-border"])
+def test_rtm_code_takes_five_shots_in_groups_of_two(tmp_path, mode):
+    """A batch budget that lets fdw_shot_batch_max be 2: the shot loop runs three times, groups {0, 1}, {2, 3}, {4}.  dir.image against the
+    oracle's shot loop (the border models in the order of the one rand() stream; with FDW_HOST_BORDER=1 the host rebuilds them group by
+    group), image.num and stdout against the program run one shot at a time."""
+    import batch_groups as G
+    with_vel_ext = mode == "vel-ext"
+    nx, nz, nxb, nzb, nt, ns, vp, d_obs, vel_ext = G.five_shot_case(tmp_path / "grouped", with_vel_ext)
+    G.five_shot_case(tmp_path / "single", with_vel_ext)
+    env = G.group_env(nx + 2 * nxb, nz + 2 * nzb, nxb, nzb, nt)
+    if mode == "host-border":
+        env["FDW_HOST_BORDER"] = "1"
+    grouped, r = G.run_program("rtm_code", tmp_path / "grouped", env)
+    G.assert_grouped(r.stderr, "fdw_shot_batch")
+    want = G.stack(G.five_shot_oracle(with_vel_ext)["image"])
+    assert_bit_equal(np.frombuffer(grouped["dir.image"], np.float32).reshape(nx, nz), want, "dir.image of the grouped run vs the oracle")
+    assert np.abs(want).max() > 0 and "** source 5, at (49,1) " in r.stdout
+    single, r1 = G.run_program("rtm_code", tmp_path / "single", {"FDW_NO_SHOT_BATCH": "1", "FDW_TIMING": "1"})
+    G.assert_grouped(r1.stderr, "one by one", 1)
+    assert sorted(grouped) == sorted(single)
+    for name in single:
+        assert grouped[name] == single[name], name
+    assert (tmp_path / "grouped" / "image.num").read_bytes() == (tmp_path / "single" / "image.num").read_bytes()
+    assert G.without_exec_time(r.stdout) == G.without_exec_time(r1.stdout)
+
+
+@pytest.mark.gpu
 def test_rtm_code_program_on_a_large_deck(tmp_path):
     """./rtm_code where one shot fills the chip (2 980 x 2 484 extended grid, extents that are no multiples of 8: the reference's truncated
     kernel ranges at scale): the border model drawn on the device from the rand() stream (two shots, 0.85 M draws each), the resident-model
@@ -653,6 +680,37 @@ def test_mod_main_program_reproduces_the_reference_gather(tmp_path):
     assert r.returncode == 0, r.stderr + r.stdout
     assert "## nz = 151, nx = 151, nt = 1001 " in r.stdout and "** source 1, at (0,0) " in r.stdout and "F = 0.010000" in r.stdout
     assert (tmp_path / "dobs.bin").read_bytes() == open(os.path.join(GOLDEN, "dd_3lay_mod_dobs.f32"), "rb").read()
+
+
+@pytest.mark.gpu
+def test_mod_main_takes_five_shots_in_groups_of_two(tmp_path):
+    """mod_main under a batch budget that lets fdw_shot_batch_max be 2: dobs of the groups {0, 1}, {2, 3}, {4} is the ungrouped program's byte
+    for byte, and O.mod_shot's shot by shot."""
+    import batch_groups as G
+    nx, nz, nb, nt, ns, fsx, ds = 61, 47, 20, 60, 5, 4, 12
+    rng = np.random.default_rng(5)
+    vp = (2000 + 1000 * rng.random((nx, nz))).astype(np.float32)
+    vp.tofile(tmp_path / "vp.bin")
+    (tmp_path / "output").mkdir()
+    (tmp_path / "mod.dat").write_text(f"tmpdir=./output\nvpfile=vp.bin\ndatfile=dobs.bin\nnz={nz}\nnx={nx}\nnt={nt}\ndz=10\ndx=10\ndt=0.001\n"
+                                      f"fpeak=30.\nns={ns}\nsz=1\nfsx={fsx}\nds={ds}\ngz=2\nnxb={nb}\nnzb={nb}\nfac=0.02\norder=8\n")
+    _, r1 = G.run_program("mod_main", tmp_path, {"FDW_TIMING": "1"}, "par=mod.dat")
+    whole = (tmp_path / "dobs.bin").read_bytes()
+    assert f"up to {ns} (fdw_model_shot_batch)" in r1.stderr, r1.stderr
+    (tmp_path / "dobs.bin").unlink()
+    _, r = G.run_program("mod_main", tmp_path, G.group_env(nx + 2 * nb, nz + 2 * nb, nb, nb, nt, fac=0.02, dialect=1), "par=mod.dat")
+    G.assert_grouped(r.stderr, "fdw_model_shot_batch")
+    assert (tmp_path / "dobs.bin").read_bytes() == whole
+    assert G.without_exec_time(r.stdout) == G.without_exec_time(r1.stdout)
+    got = np.frombuffer(whole, np.float32).reshape(ns, nx, nt)
+    v2 = np.zeros((nx + 2 * nb, nz + 2 * nb), np.float32)
+    v2[nb:nb + nx, nb:nb + nz] = vp * vp
+    v2 = O.mod_extendvel(v2, nx, nz, nb, nb)
+    srce = O.mod_ricker_wavelet(nt, 0.001, 30.0)
+    for s in range(ns):
+        want = O.mod_shot(8, nx, nz, nb, nb, 10.0, 10.0, 0.001, 0.02, v2, fsx + s * ds + nb, 1 + nb, 2 + nb, srce)
+        assert np.count_nonzero(want) > nx
+        assert_bit_equal(got[s], want, f"dobs of shot {s} vs the oracle")
 
 
 @pytest.mark.gpu

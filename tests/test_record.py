@@ -338,3 +338,23 @@ def test_migrating_recorded_reflections_images_the_interface():
         img = img + ctx.shot(h2, sx, sz, gz, srce, refl)
     lap = F.image_laplacian(img, 10.0, 10.0)
     assert interface_hits(lap, nz, nb, iface) >= 0.9
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("with_vel_ext", [False, True], ids=["device-border", "vel-ext"])
+def test_rtm_model_takes_five_shots_in_groups_of_two(tmp_path, with_vel_ext):
+    """rtm_model under a batch budget that lets fdw_shot_batch_max be 2 (groups {0, 1}, {2, 3}, {4} through fdw_record_shot_batch): the
+    datfile is the one of the run without the budget byte for byte, and the oracle's gathers shot by shot."""
+    import batch_groups as G
+    nx, nz, nxb, nzb, nt, ns, vp, d_obs, vel_ext = G.five_shot_case(tmp_path, with_vel_ext)
+    datfile = tmp_path / "models" / "dobs.bin"
+    _, r1 = G.run_program("rtm_model", tmp_path, {"FDW_TIMING": "1"})
+    G.assert_grouped(r1.stderr, "fdw_record_shot_batch", ns)
+    whole = datfile.read_bytes()
+    datfile.write_bytes(b"stale")
+    _, r = G.run_program("rtm_model", tmp_path, G.group_env(nx + 2 * nxb, nz + 2 * nzb, nxb, nzb, nt))
+    G.assert_grouped(r.stderr, "fdw_record_shot_batch")
+    assert datfile.read_bytes() == whole and r.stdout == r1.stdout
+    want = G.five_shot_oracle(with_vel_ext)["data"]
+    assert_bit_equal(np.frombuffer(whole, np.float32).reshape(ns, nx, nt), want, "datfile vs the oracle's gathers")
+    assert all(np.count_nonzero(want[s]) > nx for s in range(ns))

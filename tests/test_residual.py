@@ -634,3 +634,34 @@ def test_rtm_model_then_rtm_code_resid(tmp_path):
     for f in plain_files:
         assert nokey[f] == runs["off"][f], f
     assert nokey["dir.image"] != img.tobytes()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("illum", [False, True], ids=["resid", "resid-illum"])
+def test_rtm_code_resid_in_groups_of_two_shots(tmp_path, illum):
+    """resid=1 under a batch budget that lets fdw_shot_batch_max be 2 (groups {0, 1}, {2, 3}, {4} through fdw_shot_batch_residual): dir.resid
+    and dir.misfit in shot order and dir.image (with illum=1 also dir.illum, dir.image_illum) against the oracle's shot loop, every file
+    against the run one shot at a time."""
+    import batch_groups as G
+    extra = "resid=1\n" + ("illum=1\n" if illum else "")
+    nx, nz, nxb, nzb, nt, ns, vp, d_obs, _ = G.five_shot_case(tmp_path / "grouped", extra=extra)
+    G.five_shot_case(tmp_path / "single", extra=extra)
+    grouped, r = G.run_program("rtm_code", tmp_path / "grouped", G.group_env(nx + 2 * nxb, nz + 2 * nzb, nxb, nzb, nt))
+    G.assert_grouped(r.stderr, "fdw_shot_batch_residual")
+    want = G.five_shot_oracle()
+    img = G.stack(want["r_image"])
+    assert_bit_equal(np.frombuffer(grouped["dir.resid"], np.float32).reshape(ns, nx, nt), want["resid"], "dir.resid, shot order")
+    misfit = np.array([misfit_formula(want["resid"][s]) for s in range(ns)], np.float64)
+    assert grouped["dir.misfit"] == misfit.tobytes() and len(set(misfit)) == ns and (misfit > 0).all()
+    assert_bit_equal(np.frombuffer(grouped["dir.image"], np.float32).reshape(nx, nz), img, "dir.image")
+    assert np.count_nonzero(want["resid"] != d_obs) > ns * nx
+    if illum:
+        ill = G.stack(want["illum"])
+        assert_bit_equal(np.frombuffer(grouped["dir.illum"], np.float32).reshape(nx, nz), ill, "dir.illum")
+        assert grouped["dir.image_illum"] == F.image_compensate(img, ill, 1e-3).tobytes()
+    single, r1 = G.run_program("rtm_code", tmp_path / "single", {"FDW_NO_SHOT_BATCH": "1", "FDW_TIMING": "1"})
+    G.assert_grouped(r1.stderr, "one by one, fdw_shot_residual", 1)
+    assert sorted(grouped) == sorted(single) and ("dir.illum" in single) == illum
+    for name in single:
+        assert grouped[name] == single[name], name
+    assert G.without_exec_time(r.stdout) == G.without_exec_time(r1.stdout)

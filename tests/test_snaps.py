@@ -497,3 +497,37 @@ def test_rtm_code_snap_key_leaves_the_illumination_files_alone(tmp_path):
         assert on[name] == off[name], name
     assert num_on == num_off
     assert len(on["dir.snaps"]) == 4 * 11 * 50 * 37 and off["dir.snaps"] == b""
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("iss", [3, 2], ids=["second-of-its-group", "first-of-its-group"])
+def test_rtm_code_snap_key_in_groups_of_two_shots(tmp_path, iss):
+    """snap=K under a batch budget that lets fdw_shot_batch_max be 2 (groups {0, 1}, {2, 3}, {4}): shot iss leaves ITS group and runs alone
+    on the border model of its own draws; the other shot of that group runs before (iss = 3) or after it (iss = 2).  The three frame files
+    against the oracle's levels of that shot, dir.image against the oracle's shot loop, every file against the run one shot at a time."""
+    import batch_groups as G
+    K, D = 10, 2
+    extra = f"snap={K}\nsnap_dec={D}\niss={iss}\n"
+    nx, nz, nxb, nzb, nt, ns, vp, d_obs, _ = G.five_shot_case(tmp_path / "grouped", extra=extra)
+    G.five_shot_case(tmp_path / "single", extra=extra)
+    nxe, nze = nx + 2 * nxb, nz + 2 * nzb
+    grouped, r = G.run_program("rtm_code", tmp_path / "grouped", G.group_env(nxe, nze, nxb, nzb, nt))
+    G.assert_grouped(r.stderr, "fdw_shot_batch")
+    want = G.five_shot_oracle()
+    orc = O.Oracle(8, nxe, nze, nxb, nzb, nt, 0.75, 10.0, 10.0, 0.001, compat=True)
+    d = dict(nxe=nxe, nze=nze, nxb=nxb, nzb=nzb, v2=want["v2"][iss])
+    lv = oracle_levels(orc, d, G.FSX + iss * G.DS + nxb, G.SZ + nzb, G.GZ + nzb, O.ricker_wavelet(nt, 0.001, 25.0), d_obs=d_obs[iss], keep=K)
+    assert_bit_equal(lv["image"], want["image"][iss], "the levels' image is the shot's")
+    nf, nxs, nzs = F.snap_dims(nx, nz, nt, K, D)
+    assert nf == 9
+    for file, key in (("dir.snaps", "snaps"), ("dir.snaps_rec", "snaps_rec"), ("dir.snapr", "snapr")):
+        frames = expected_set(lv[key], nt, K, D, (nxs, nzs))
+        assert np.count_nonzero(frames) > 100
+        assert_bit_equal(np.frombuffer(grouped[file], np.float32).reshape(nf, nxs, nzs), frames, f"{file}, iss {iss}")
+    assert_bit_equal(np.frombuffer(grouped["dir.image"], np.float32).reshape(nx, nz), G.stack(want["image"]), "dir.image")
+    single, r1 = G.run_program("rtm_code", tmp_path / "single", {"FDW_NO_SHOT_BATCH": "1", "FDW_TIMING": "1"})
+    G.assert_grouped(r1.stderr, "one by one", 1)
+    assert sorted(grouped) == sorted(single)
+    for name in single:
+        assert grouped[name] == single[name], name
+    assert (tmp_path / "grouped" / "image.num").read_bytes() == (tmp_path / "single" / "image.num").read_bytes()
