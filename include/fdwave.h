@@ -143,6 +143,9 @@ int fdw_shot(fdw_ctx *ctx, const float *v2, int sx, int sz, int gz, const float 
  *                   has not run yet included -- and work queued on the stream after it sees its results.  Nothing is issued on the context's
  *                   own stream, and no other stream or event is involved.  Chained calls on one stream need no host synchronisation in between.
  *                   The ONE exception is fdw_dev_check_field, which issues its check on the stream and then synchronises it to return the count.
+ *                   ONE amendment: fdw_dev_steps2 with a pass-band depth above 1 (fdw_set_pass_bands, below) forks part of its passes onto side
+ *                   streams of the context behind an event of the caller's stream and joins them into it before it returns; towards the
+ *                   caller the ordering above holds unchanged.
  *   Host arguments (pointers to ip / ipp, role[], scalars) are read and written before the call returns.
  *
  * PRECONDITION of every entry point that takes wavefields (host or device) on a context with compat = 1 and nxe not a multiple of 8:
@@ -674,6 +677,55 @@ int fdw_selftest(fdw_ctx *ctx);
 /* 1 if the host loops emit roctx ranges (forward loop, backward loop, halo exchange, shot): they do when a marker library
  * (librocprofiler-sdk-roctx / libroctx64) is already in the process -- rocprofv3 --marker-trace -- or FDW_ROCTX=1 asks for it. */
 int fdw_trace_active(void);
+
+/* ---- consecutive four-step forward passes as row bands on side streams -------------------------
+ * Two launches in one stream never overlap, so every pass of fdw_dev_steps2 fills and drains the chip on its own.  A pass cut into G
+ * bands of whole chunk rows can overlap the next one: pass n+1 on a band needs pass n on that band and its two neighbours only.  The
+ * tiles are the same tiles (bands are cut on chunk boundaries with the pass's own chunk length), so every result is unchanged bit for bit.
+ *
+ * fdw_plan_pass_bands  the schedule; pure host C, no context, no device.  nxl rows, of which [0, upd_x1) are time-stepped; xchunk = the
+ *                      pass's chunk length; bands / depth = the wanted G / D (depth 1..FDW_PASS_DEPTH_MAX); npasses >= 1.
+ *                      Launch units are numbered pass-major, band-minor: unit i = n * G + g is pass n on band g.  Bands are whole chunk
+ *                      rows counted from row 0, as equal as possible (the first ones take the extra chunk row); the last band ends at
+ *                      nxl: it owns the static rows [upd_x1, nxl) that every pass copies.  Unit i runs on stream i mod D (stream 0 is the
+ *                      caller's) and first waits for the events of units i-D-1 .. i-2D+1 (D-1 of them; those below 0 do not exist).  With
+ *                      stream order (unit i-D) every unit up to i-D is then complete, and unit i overlaps at most the D-1 units before
+ *                      it.  That is safe if and only if every band holds at least 16 time-stepped rows (four steps of half order 4: a
+ *                      pass on a band then reads rows of the adjacent bands only, and overwrites only what pass n-1 read there) and
+ *                      G >= D+1 (the adjacent bands of pass n-1 lie at or below i-D).  A request that is not -- or G = 1 -- comes back
+ *                      as ONE band [0, nxl) of depth 1: the plain loop.  *bands_out / *depth_out = what the plan uses; units (may be
+ *                      NULL) receives min(cap, G * npasses) entries.  Returns G * npasses, or FDW_EINVAL.
+ * fdw_set_pass_bands   the policy of fdw_dev_steps2 on this context: bands = depth = 0 automatic (below); depth 1: the bands run one after
+ *                      the other on the caller's stream, no event involved.  bands < 0, depth outside [0, FDW_PASS_DEPTH_MAX] or only one of
+ *                      the two zero: FDW_EINVAL.  While the policy is automatic the environment variable FDW_PASS_BANDS="G,D" (read
+ *                      at every call; experiments) takes its place.
+ * fdw_pass_bands       what the last fdw_dev_steps2 call on this context used (1, 1: the plain loop; 0, 0 before the first call).
+ *
+ * Where the schedule is used: fdw_dev_steps2 only (not inside a batch), for the passes of the four-step kernel; the steps left over
+ * (nsteps mod 4) and every other entry point -- the recording, illumination and line-source loops, fdw_forward and the shots, the slab
+ * drivers -- run as before.  Automatic policy, from the measurement on one MI355X: 3 bands, depth 2
+ * where a pass has at least 1776 tiles (8192^2 and larger: +3.2 % at 8192^2, +3.1 % at 12288^2, +1.7 % at 16384^2 in EXACT numerics,
+ * +7.6 % at 8192^2 and +4.2 % at 16384^2 in FAST) and the call holds at least 8 passes; one band otherwise (4096^2: -16 %; 6144^2: not
+ * separable from one band; a call of one pass only pays for the cut).  THE GAIN NEEDS A HARDWARE QUEUE FOR THE SIDE STREAM: a process has four, and where more streams than that are alive two
+ * streams may share one; a side stream that shares the caller's queue runs behind it and the schedule costs up to a quarter of the
+ * loop's time.  A process with many streams of its own sets one band (fdw_set_pass_bands(ctx, 1, 1)), as fdw_slabs_create does.
+ * STREAMS (the one amendment to the stream contract above): with depth D > 1 the units of streams 1 .. D-1 run on side streams the context
+ * owns (hipStreamNonBlocking, created on first use).  Every side stream first waits for an event recorded on the caller's stream at
+ * entry, so a producer queued there is respected; the caller's stream waits for the last unit of every side stream before the left-over
+ * steps and before the call returns -- also when a launch fails part-way.  The call stays asynchronous and ordered on the stream it was
+ * given: what is queued behind it sees its results.  At most FDW_PASS_DEPTH_MAX = 3 streams, the caller's included. */
+#define FDW_PASS_DEPTH_MAX 3
+typedef struct fdw_band_unit {
+    int pass, band;     /* n, g */
+    int r0, r1;         /* rows the unit produces (r1 = nxl for the last band: its launch ends at upd_x1 and copies the static rows) */
+    int stream;         /* i mod D */
+    int nwait;          /* 0 .. FDW_PASS_DEPTH_MAX - 1 */
+    int wait[FDW_PASS_DEPTH_MAX - 1];   /* unit numbers, descending */
+} fdw_band_unit;
+int fdw_plan_pass_bands(int nxl, int upd_x1, int xchunk, int bands, int depth, int npasses, int *bands_out, int *depth_out,
+                        fdw_band_unit *units, int cap);
+int fdw_set_pass_bands(fdw_ctx *ctx, int bands, int depth);
+int fdw_pass_bands(const fdw_ctx *ctx, int *bands, int *depth);
 
 /* ---- host formulas of libsource.a restated (pure C, usable without a device) --------------------
  * fdw_calc_coefs        calc_coefs + makeo2, F:113-192 / S:137-216 (cxx selects the float variant)

@@ -36,6 +36,15 @@ class Snaps(C.Structure):
     _fields_ = [("every", C.c_int), ("dec", C.c_int), ("snaps", vp), ("snaps_rec", vp), ("snapr", vp)]
 
 
+PASS_DEPTH_MAX = 3
+
+
+class BandUnit(C.Structure):
+    """struct fdw_band_unit (fdwave.h): one launch unit of fdw_plan_pass_bands."""
+    _fields_ = [("pass_", C.c_int), ("band", C.c_int), ("r0", C.c_int), ("r1", C.c_int), ("stream", C.c_int), ("nwait", C.c_int),
+                ("wait", C.c_int * (PASS_DEPTH_MAX - 1))]
+
+
 # every symbol fdwave.h declares: (name, restype, argtypes)
 SIGNATURES = [
     ("fdw_last_error", C.c_char_p, []),
@@ -149,6 +158,9 @@ SIGNATURES = [
     ("fdw_steps_per_pass", C.c_int, [vp]),
     ("fdw_selftest", C.c_int, [vp]),
     ("fdw_trace_active", C.c_int, []),
+    ("fdw_plan_pass_bands", C.c_int, [C.c_int] * 6 + [C.POINTER(C.c_int)] * 2 + [vp, C.c_int]),
+    ("fdw_set_pass_bands", C.c_int, [vp, C.c_int, C.c_int]),
+    ("fdw_pass_bands", C.c_int, [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     ("fdw_calc_coefs", C.c_int, [C.c_int, C.c_int, f32p]),
     ("fdw_ricker_wavelet", None, [C.c_int, C.c_float, C.c_float, f32p]),
     ("fdw_taper_tables", None, [C.c_int, C.c_int, C.c_float, vp, vp]),

@@ -127,6 +127,18 @@ def _i32(a):
     return np.ascontiguousarray(a, dtype=np.int32).reshape(-1)
 
 
+def plan_pass_bands(nxl, upd_x1, xchunk, bands, depth, npasses):
+    """fdw_plan_pass_bands (fdwave.h): (bands, depth, units) of the schedule dev_steps2 follows; units[i] = dict(pass_, band, r0, r1, stream,
+    wait).  A request the planner finds unsafe comes back as one band of depth 1.  No device."""
+    g, d = C.c_int(), C.c_int()
+    n = lib().fdw_plan_pass_bands(nxl, upd_x1, xchunk, bands, depth, npasses, C.byref(g), C.byref(d), None, 0)
+    check(min(n, 0))
+    units = (_lib.BandUnit * n)()
+    check(min(lib().fdw_plan_pass_bands(nxl, upd_x1, xchunk, bands, depth, npasses, C.byref(g), C.byref(d), units, n), 0))
+    return g.value, d.value, [dict(pass_=u.pass_, band=u.band, r0=u.r0, r1=u.r1, stream=u.stream, wait=[u.wait[k] for k in range(u.nwait)])
+                              for u in units]
+
+
 def planewave_lags(src_ix, dx, dt, p):
     """fdw_planewave_lags (fdwave.h): lag[s] = lround(p (src_ix[s] - src_ix[0]) dx / dt) - the smallest of them, in double; p in s/m."""
     src_ix = _i32(src_ix)
@@ -233,6 +245,18 @@ class FDWave:
     def steps_per_pass(self):
         """Time steps one launch of the forward loops advances on this grid: 4 (wave pipeline), 2 (two-step kernel) or 1."""
         return int(lib().fdw_steps_per_pass(self._h))
+
+    def set_pass_bands(self, bands=0, depth=0):
+        """How dev_steps2 issues the passes of the four-step kernel (fdwave.h): `bands` row bands per pass, units `depth` deep on the caller's
+        stream and depth - 1 side streams.  0, 0: automatic; depth 1: the bands one after the other on the caller's stream.  Results never
+        depend on it."""
+        check(lib().fdw_set_pass_bands(self._h, int(bands), int(depth)))
+
+    def pass_bands(self):
+        """(bands, depth) the last dev_steps2 call used; (1, 1) is the plain loop."""
+        a, b = C.c_int(), C.c_int()
+        check(lib().fdw_pass_bands(self._h, C.byref(a), C.byref(b)))
+        return a.value, b.value
 
     def selftest(self):
         check(lib().fdw_selftest(self._h))
@@ -655,7 +679,9 @@ class FDWave:
         """nsteps iterations over four rotating device buffers (pairs via the two-step kernel).
         Returns the indices (ip, ipp) of the reference's (d_p, d_pp) after the loop.
         stream=None: the context's own non-blocking stream, unordered against the caller's streams (the legacy default stream included); a caller's
-        stream: every launch, copy and memset of the call is issued on it and the call does not synchronise (fdwave.h)."""
+        stream: every launch, copy and memset of the call is issued on it and the call does not synchronise (fdwave.h).  On large grids the
+        four-step passes run as row bands, part of them on a side stream of the context that starts behind `stream` and is joined into it
+        before the call returns (set_pass_bands; fdwave.h): towards the caller the ordering is the same."""
         arr = (C.c_void_p * 4)(*bufs)
         a, b = C.c_int(ip), C.c_int(ipp)
         check(lib().fdw_dev_steps2(self._h, arr, d_v2, d_srce, sx, sz, it0, nsteps, int(first_pp_twice), C.byref(a), C.byref(b), stream))

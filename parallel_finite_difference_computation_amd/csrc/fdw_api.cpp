@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <climits>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -44,6 +45,11 @@ extern "C" int fdw_version(void) { return FDW_VERSION; }
 // ------------------------------------------------------------------------------------------------
 // context
 // ------------------------------------------------------------------------------------------------
+// events of the launch units of band_passes: unit i records slot i % kBandRing, and the last unit that waits for it (i + 2D - 1) is
+// issued before unit i + kBandRing records the slot again
+constexpr int kBandRing = 8;
+static_assert(kBandRing >= 2 * FDW_PASS_DEPTH_MAX, "a slot must not be recorded again before its last waiter is issued");
+
 struct fdw_ctx {
     fdw_params prm{};
     fdw_slab slab{};
@@ -106,6 +112,11 @@ struct fdw_ctx {
     size_t batch_budget = 0; // bytes a batch of shots may take (0: FDW_BATCH_BUDGET_BYTES, else 6 GiB); written by fdw_set_batch_budget alone
     int batch_parts = 0;     // batched launch sequences of the last batched call (0: its shots ran one by one); fdw_batch_parts
     bool batch_single = false;      // inside a batched call: a part of more than one shot ran its shots one by one
+    // consecutive four-step forward passes as row bands on side streams (fdw_set_pass_bands; band_passes)
+    int pb_bands = 0, pb_depth = 0;             // the policy; 0, 0: automatic
+    int pb_used_bands = 0, pb_used_depth = 0;   // what the last forward loop used (fdw_pass_bands)
+    hipStream_t pb_side[FDW_PASS_DEPTH_MAX - 1] = {};      // created on first use
+    hipEvent_t pb_fork = nullptr, pb_join[FDW_PASS_DEPTH_MAX - 1] = {}, pb_ring[kBandRing] = {};
 };
 
 static size_t field_elems(const fdw_ctx* c) { return (size_t)c->nxl * (size_t)c->pitch; }
@@ -353,6 +364,16 @@ extern "C" void fdw_destroy(fdw_ctx* c)
     if (!c) return;
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
+    for (hipStream_t side : c->pb_side)
+        if (side) {
+            (void)hipStreamSynchronize(side);
+            (void)hipStreamDestroy(side);
+        }
+    for (hipEvent_t e : c->pb_join)
+        if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : c->pb_ring)
+        if (e) (void)hipEventDestroy(e);
+    if (c->pb_fork) (void)hipEventDestroy(c->pb_fork);
     float* bufs[] = {c->d_taperz, c->d_txfac, c->d_gcx, c->d_gcz, c->fld[0], c->fld[1], c->fld[2], c->fld[3],
                      c->fld[4], c->fld[5], c->fld[6], c->fld[7], c->fld[8], c->fld[9], c->d_v2, c->d_img, c->d_illum, c->d_srce, c->d_dobs, c->d_rec,
                      c->d_vp, c->d_vpe, (float*)c->d_draws, (float*)c->d_jump, c->bfld[0], c->bfld[1], c->bfld[2], c->bfld[3],
@@ -769,6 +790,19 @@ static void tile_classes(const Step2Args& a, int kmode, std::vector<unsigned cha
     }
 }
 
+// strips of a pipeline pass (each owns 64 - 2 kPipeSteps columns of 4 cells) and the chunk length of its forward passes on `strip_rows` =
+// rows x strips (the measurements are in stepn_impl)
+static int pipe_strips(const fdw_ctx* c)
+{
+    const int ncells = c->pitch / 4, own = 64 - 2 * kPipeSteps;
+    return (ncells + own - 1) / own;
+}
+static int pipe_fwd_xchunk(const fdw_ctx* c, long strip_rows)
+{
+    const bool fastnum = c->prm.numerics == FDW_NUMERICS_FAST;
+    return c->xchunk2 > 0 ? c->xchunk2 : (strip_rows >= 1000000 ? 253 : (strip_rows >= 250000 ? 173 : (strip_rows >= 120000 ? (fastnum ? 173 : 143) : (strip_rows >= 60000 ? 83 : 43))));
+}
+
 struct StepnPlan {
     int nblk = 0, nstrip = 0;
     std::vector<unsigned char> cls;
@@ -851,8 +885,7 @@ static int stepn_impl(fdw_ctx* c, int mode, const float* d_p, const float* d_pp,
     // end of round 2 (scripts/probe_pipe.py, PIPE_SHAPE): 4128x8192 (half of the bench grid) 584 at 83, 592 at 123, 609 at 143, 601 at 173;
     // 2144x8192 538 at 83 (499 at 53, 521 at 103)
     // end of round 3 (same probe, FAST numerics): 4128x8192 677 at 143, 710 at 173, 700 at 83 -- the memory-bound FAST kernel prefers the longer chunk there
-    const bool fastnum = c->prm.numerics == FDW_NUMERICS_FAST;
-    int xchunk = c->xchunk2 > 0 ? c->xchunk2 : (strip_rows >= 1000000 ? 253 : (strip_rows >= 250000 ? 173 : (strip_rows >= 120000 ? (fastnum ? 173 : 143) : (strip_rows >= 60000 ? 83 : 43))));
+    int xchunk = pipe_fwd_xchunk(c, strip_rows);
     if (mode == FDW_MODE_BACK4 && c->xchunk2 <= 0) {
         // the eight-wave kernel holds two workgroups per CU (512 at a time): longer chunks than the forward kernel's at the same grid size
         // (scripts/probe_slabs_c.py, us per iteration by chunk length 43 / 83 / 123 / 173: 8192 rows 363 / 309 / 289 / 277; 4160 rows 192 / 172 / 157 / 162;
@@ -1011,14 +1044,168 @@ static int record_static(fdw_ctx* c, const float* d_p, const float* d_pp, int gz
     return FDW_OK;
 }
 
+// ---- consecutive pipeline passes as row bands on side streams (fdwave.h: fdw_plan_pass_bands) -----------------------------------------
+// The schedule.  Pure host arithmetic: no context, no HIP call.
+extern "C" int fdw_plan_pass_bands(int nxl, int upd_x1, int xchunk, int bands, int depth, int npasses, int* bands_out, int* depth_out,
+                                   fdw_band_unit* units, int cap)
+{
+    if (nxl <= 0 || upd_x1 < 0 || upd_x1 > nxl || xchunk <= 0 || bands < 1 || depth < 1 || depth > FDW_PASS_DEPTH_MAX || npasses < 1 || (units && cap < 0))
+        return fail(FDW_EINVAL, "pass bands: nxl=%d upd_x1=%d xchunk=%d bands=%d depth=%d (1..%d) npasses=%d", nxl, upd_x1, xchunk, bands, depth,
+                    FDW_PASS_DEPTH_MAX, npasses);
+    constexpr int reach = kPipeSteps * kMaxFastHalfOrder;      // rows beyond its own that a pass reads on either side
+    const int nchunks = (upd_x1 + xchunk - 1) / xchunk;
+    int G = bands, D = depth;
+    // the first nchunks % G bands hold one chunk row more than the others; the thinnest band is the last (it also has the ragged chunk)
+    const int base = nchunks / G, extra = nchunks % G;
+    auto first_chunk = [&](int g) { return g * base + std::min(g, extra); };
+    const bool safe = G >= 2 && G >= D + 1 && base >= 1 && (long)base * xchunk >= reach && upd_x1 - first_chunk(G - 1) * xchunk >= reach;
+    if (!safe) G = D = 1;
+    if (npasses > INT_MAX / G) return fail(FDW_EINVAL, "pass bands: %d passes of %d bands", npasses, G);
+    if (bands_out) *bands_out = G;
+    if (depth_out) *depth_out = D;
+    const int total = G * npasses;
+    for (int i = 0; units && i < std::min(cap, total); i++) {
+        fdw_band_unit& u = units[i];
+        u.pass = i / G; u.band = i % G;
+        u.r0 = G == 1 ? 0 : first_chunk(u.band) * xchunk;
+        u.r1 = u.band == G - 1 ? nxl : first_chunk(u.band + 1) * xchunk;
+        u.stream = i % D;
+        u.nwait = 0;
+        for (int k = 0; k < FDW_PASS_DEPTH_MAX - 1; k++) u.wait[k] = -1;
+        for (int j = i - D - 1; j >= i - 2 * D + 1 && j >= 0; j--) u.wait[u.nwait++] = j;
+    }
+    return total;
+}
+
+extern "C" int fdw_set_pass_bands(fdw_ctx* c, int bands, int depth)
+{
+    if (!c) return fail(FDW_EINVAL, "ctx is NULL");
+    if (bands < 0 || depth < 0 || depth > FDW_PASS_DEPTH_MAX || (bands == 0) != (depth == 0))
+        return fail(FDW_EINVAL, "pass bands: bands=%d depth=%d (0, 0 = automatic; depth 1..%d)", bands, depth, FDW_PASS_DEPTH_MAX);
+    c->pb_bands = bands; c->pb_depth = depth;
+    return FDW_OK;
+}
+
+extern "C" int fdw_pass_bands(const fdw_ctx* c, int* bands, int* depth)
+{
+    if (!c || !bands || !depth) return fail(FDW_EINVAL, "NULL argument");
+    *bands = c->pb_used_bands; *depth = c->pb_used_depth;
+    return FDW_OK;
+}
+
+// The wanted bands / depth of the forward loop's pipeline passes of `tiles` tiles each: the knob, else FDW_PASS_BANDS="G,D" (experiments),
+// else the automatic policy, which is the measurement on one MI355X and nothing else (DESIGN.md section 3c, round 13;
+// profiles/r13_band_probe.txt, python bench.py against the parent commit, Gpoints/s):
+//   tiles   grid            3/2      other settings
+//    950    4096^2          -16 %    (4/2 -30 %)
+//   1204    6144^2          +1.6 % in one session, +0.9 % with overlapping ranges in the next; FAST -0.2 %: not separable
+//   1776    8192^2          +3.4 %   (4/2 -4 %, every D = 3 -25 % and worse, 3/1 -24 %: cutting alone costs);  FAST numerics +7.6 %
+//   3960    12288^2         +3.1 %   (4/2 +3.0 %, 6/2 +0.4 %)
+//   4810    16384^2         +1.8 %   (4/2, 5/2 +1.7 %, 6/2 +1.2 %, 7/2 -0.2 %, 8/2 -1.4 %, 9/2 -2.8 %);  FAST numerics +4.2 %
+// Three bands two deep wherever it was measured to gain: the fewest bands the schedule allows, so the price of cutting is least and two
+// resident units together are the largest.  All of these are calls of 100 passes and more.  The units overlap only inside one call (it
+// joins before it returns), so a call of a single pass pays for the cut and gets nothing back: below kBandAutoPasses the automatic policy
+// stays at one band (a bound from that reasoning, not from a measurement).
+// The gain needs the side stream on a hardware queue of its own.  A process holds four; where more streams are alive than that the
+// runtime lets streams share a queue, and a side stream that shares the caller's runs behind it: the schedule then costs what 3/1 costs.
+// Seen on the slab driver's context (one rank, three more streams: a whole 8192^2 shot 586 against 650 Gpoints/s), which therefore sets
+// one band for its context (fdw_slabs_create), and on every depth-3 setting above (two of the three streams on one queue,
+// profiles/r13_band_probe.txt).  A caller with many streams of its own does the same: fdw_set_pass_bands(ctx, 1, 1).
+constexpr int kBandAutoTiles = 1776, kBandAutoPasses = 8;      // 1776: the smallest pass measured to gain, every run above the parent's
+static void wanted_pass_bands(const fdw_ctx* c, long tiles, int npasses, int* bands, int* depth)
+{
+    *bands = *depth = 1;
+    if (c->pb_bands > 0) {
+        *bands = c->pb_bands; *depth = c->pb_depth;
+    } else if (const char* e = getenv("FDW_PASS_BANDS")) {
+        int g = 0, d = 0;
+        if (sscanf(e, "%d,%d", &g, &d) == 2 && g >= 1 && d >= 1 && d <= FDW_PASS_DEPTH_MAX) { *bands = g; *depth = d; }
+    } else if (tiles >= kBandAutoTiles && npasses >= kBandAutoPasses) {
+        *bands = 3; *depth = 2;
+    }
+}
+
+static int ensure_band_streams(fdw_ctx* c, int depth)
+{
+    if (!c->pb_fork) HIP_TRY(hipEventCreateWithFlags(&c->pb_fork, hipEventDisableTiming));
+    for (hipEvent_t& e : c->pb_ring)
+        if (!e) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    for (int j = 0; j < depth - 1; j++) {
+        if (!c->pb_side[j]) HIP_TRY(hipStreamCreateWithFlags(&c->pb_side[j], hipStreamNonBlocking));
+        if (!c->pb_join[j]) HIP_TRY(hipEventCreateWithFlags(&c->pb_join[j], hipEventDisableTiming));
+    }
+    return FDW_OK;
+}
+
+// `npasses` plain forward passes of the pipeline kernel (what steps_loop's first branch issues one after the other on s) as the launch units
+// of fdw_plan_pass_bands: unit i on stream i mod D behind the events of the units the plan names.  Fork: every side stream starts behind
+// an event recorded on s here.  Join: s waits for the last unit of every side stream, whatever happened in between.  *ip, *ipp advance
+// over the passes issued.
+static int band_passes(fdw_ctx* c, float* const* buf, const float* d_v2, const float* d_srce, int sx, int sz, int it0, int npasses, int first_pp_twice,
+                       int* ip, int* ipp, hipStream_t s, int G, int D, int xchunk)
+{
+    std::vector<fdw_band_unit> units((size_t)G * npasses);
+    int g_ = 0, d_ = 0;
+    const int total = fdw_plan_pass_bands(c->nxl, c->upd_x1, xchunk, G, D, npasses, &g_, &d_, units.data(), (int)units.size());
+    if (total < 0) return total;
+    if (g_ != G || d_ != D || total != (int)units.size()) return fail(FDW_ESTATE, "pass bands: the plan changed between two calls");
+    hipStream_t st[FDW_PASS_DEPTH_MAX] = {s};
+    if (D > 1) {
+        FDW_TRY(ensure_band_streams(c, D));
+        HIP_TRY(hipEventRecord(c->pb_fork, s));
+        for (int j = 1; j < D; j++) {
+            st[j] = c->pb_side[j - 1];
+            HIP_TRY(hipStreamWaitEvent(st[j], c->pb_fork, 0));
+        }
+    }
+    auto issue = [&]() -> int {
+        int o1 = 0, o2 = 0;
+        for (int i = 0; i < total; i++) {
+            const fdw_band_unit& u = units[(size_t)i];
+            if (u.band == 0) spare_pair(*ip, *ipp, &o1, &o2);
+            const int k = u.pass * kPipeSteps;
+            for (int w = 0; w < u.nwait; w++) HIP_TRY(hipStreamWaitEvent(st[u.stream], c->pb_ring[u.wait[w] % kBandRing], 0));
+            FDW_TRY(stepn_impl(c, FDW_MODE_FWD, buf[*ipp], buf[*ip], d_v2, buf[o1], buf[o2], (k > 0) || first_pp_twice,
+                                d_srce ? d_srce + (size_t)(it0 + k) : nullptr, d_srce ? sx : -1, sz, st[u.stream], RowRanges{u.r0, u.r1, 0, 0, xchunk}));
+            if (D > 1 && i + D + 1 < total) HIP_TRY(hipEventRecord(c->pb_ring[i % kBandRing], st[u.stream]));      // someone will wait for it
+            if (u.band == G - 1) { *ip = o1; *ipp = o2; }      // d_p = u^{n+kPipeSteps-1}, d_pp = u^{n+kPipeSteps}
+        }
+        return FDW_OK;
+    };
+    const int rc = issue();
+    char msg[sizeof g_err];
+    if (rc != FDW_OK) memcpy(msg, g_err, sizeof msg);
+    int jrc = FDW_OK;
+    for (int j = 1; j < D; j++) {
+        hipError_t e = hipEventRecord(c->pb_join[j - 1], st[j]);
+        if (e == hipSuccess) e = hipStreamWaitEvent(s, c->pb_join[j - 1], 0);
+        if (e != hipSuccess && jrc == FDW_OK) jrc = fail(FDW_EHIP, "pass bands: joining side stream %d failed: %s", j, hipGetErrorString(e));
+    }
+    if (rc != FDW_OK) memcpy(g_err, msg, sizeof msg);      // the first error is the one to report
+    return rc != FDW_OK ? rc : jrc;
+}
+
 static int steps_loop(fdw_ctx* c, float* const* buf, const float* d_v2, const float* d_srce, int sx, int sz, int gz, float* d_rec, int it0, int nsteps,
-                      int first_pp_twice, int* ip, int* ipp, hipStream_t s, float* d_illum = nullptr, bool line = false)
+                      int first_pp_twice, int* ip, int* ipp, hipStream_t s, float* d_illum = nullptr, bool line = false, bool may_band = false)
 {
     if (!c || !buf || !ip || !ipp) return fail(FDW_EINVAL, "NULL argument");
     if (*ip < 0 || *ip > 3 || *ipp < 0 || *ipp > 3 || *ip == *ipp) return fail(FDW_EINVAL, "steps2: bad buffer indices");
     const size_t nxs = (size_t)c->nx;
     if (d_rec) FDW_TRY(record_static(c, buf[*ip], buf[*ipp], gz, d_rec, it0, nsteps, s));
     int k = 0;
+    c->pb_used_bands = c->pb_used_depth = 1;
+    if (may_band && !d_rec && !d_illum && !line && c->nbatch <= 1 && nsteps >= kPipeSteps && pipe_pays(c)) {
+        // fdw_dev_steps2, the plain forward loop on caller-owned buffers: its pipeline passes may run as row bands (whole chunk rows of the pass's own chunk length: the same tiles)
+        const int nstrip = pipe_strips(c), xchunk = pipe_fwd_xchunk(c, (long)c->upd_x1 * nstrip), npasses = nsteps / kPipeSteps;
+        int G, D;
+        wanted_pass_bands(c, (long)nstrip * ((c->upd_x1 + xchunk - 1) / xchunk), npasses, &G, &D);
+        if (G > 1 && fdw_plan_pass_bands(c->nxl, c->upd_x1, xchunk, G, D, npasses, &G, &D, nullptr, 0) < 0) return FDW_EINVAL;
+        if (G > 1) {
+            c->pb_used_bands = G; c->pb_used_depth = D;
+            FDW_TRY(band_passes(c, buf, d_v2, d_srce, sx, sz, it0, npasses, first_pp_twice, ip, ipp, s, G, D, xchunk));
+            k = npasses * kPipeSteps;
+        }
+    }
     while (k < nsteps) {
         const int twice = (k > 0) || first_pp_twice;
         const float* inj = d_srce ? d_srce + (size_t)(it0 + k) * (line ? nxs : 1) : nullptr;
@@ -1064,7 +1251,7 @@ extern "C" int fdw_dev_steps2(fdw_ctx* c, float* const* buf, const float* d_v2, 
                               int first_pp_twice, int* ip, int* ipp, void* stream)
 {
     if (!c) return fail(FDW_EINVAL, "NULL argument");
-    return steps_loop(c, buf, d_v2, d_srce, sx, sz, 0, nullptr, it0, nsteps, first_pp_twice, ip, ipp, pick_stream(c, stream));
+    return steps_loop(c, buf, d_v2, d_srce, sx, sz, 0, nullptr, it0, nsteps, first_pp_twice, ip, ipp, pick_stream(c, stream), nullptr, false, true);
 }
 
 // the receiver column of a recorded gather: one the forward loop time-steps (R:83-87: j < zlim)

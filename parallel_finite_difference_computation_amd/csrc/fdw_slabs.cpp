@@ -148,6 +148,10 @@ extern "C" int fdw_slabs_create(const fdw_params* prm, fdw_comm* comm, int devic
         return rc;
     }
     s->pitch = fdw_pitch(s->ctx);
+    // One rank runs the library's own forward loop (slabs_forward).  Its passes stay whole: the three streams below, the context's and the
+    // caller's already outnumber the process's hardware queues, and a side stream of fdw_dev_steps2's band schedule (fdwave.h:
+    // fdw_set_pass_bands) that shares the compute stream's queue only pays for the cut -- measured, DESIGN.md section 3c, round 13.
+    (void)fdw_set_pass_bands(s->ctx, 1, 1);
     // Three streams of equal priority.  Giving the boundary strips and the halo exchange the device's highest stream priority (FDW_SLAB_PRIORITY=1)
     // was measured and costs far more than a late exchange could: with the links stubbed, 8192^2, us per step at N = 2 / 4 / 8: forward
     // 57.4 / 34.2 / 21.4 flat against 69.4 / 47.9 / 37.2 with priorities, backward 129.6 / 76.8 / 47.9 against 138.9 / 89.5 / 60.6 (round 3).
