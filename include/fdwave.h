@@ -182,7 +182,10 @@ int fdw_shot(fdw_ctx *ctx, const float *v2, int sx, int sz, int gz, const float 
  *                 d_pp = u^{n-1} -> d_out1 = u^{n+3}, d_out2 = u^{n+4} on local rows [r0, r1) and, optionally, [r0b, r1b)
  *                 (r1 < 0: every row the reference time-steps); rows within 16 of a range end are read from d_p / d_pp, so
  *                 a slab driver shrinks the range by 16 rows per pass between two halo exchanges (decomp.py).
- *                 d_srce_it -> srce[it .. it+3]; xchunk 0 = automatic.  Bit-identical to four fdw_dev_step calls.
+ *                 d_srce_it -> srce[it .. it+3]; xchunk 0 = automatic.  Bit-identical to four fdw_dev_step calls.  Rows of a range that
+ *                 the reference never time-steps (compat extents, rows >= xlim; with r1 < 0 all of them) receive the inputs' rows, which
+ *                 are static -- also where a range holds such rows only and nothing is launched for it; no row outside the ranges is
+ *                 written, the rows of a gap between the two ranges included (tests/test_dev_footprint.py) -- fdw_dev_back4 alike.
  * fdw_dev_steps_shrink  like fdw_dev_steps for one slab of a decomposed grid between two halo exchanges:
  *                 step j = j0.. of the cycle updates rows [h*j, nxl - h*j) on the sides that have a
  *                 neighbour (shrink_lo / shrink_hi), see decomp.py.

@@ -670,18 +670,24 @@ static bool two_step_pays(const fdw_ctx* c)
 // of 8) are static in both fields, which swap roles every step: out1 now carries pp's rows, out2 p's; so do the levels in between
 // (PLAIN_ALL: level 0 pp's, level 1 p's) and the receiver field of BACK4.  Receiver rows among them (two-step RECV): iteration it injects
 // into (and images) what is now out1, iteration it+1 what is now out2.
-static int even_steps_tail(fdw_ctx* c, int mode, const Step2Args& a, hipStream_t s)
+// [sa0, sa1) and [sb0, sb1): the rows the call was asked for (default: all).  A pass on row ranges copies the static rows AMONG them and no
+// others -- none of a gap between the two ranges, and those of a range that holds no time-stepped row at all.
+static int even_steps_tail(fdw_ctx* c, int mode, const Step2Args& a, hipStream_t s, int sa0 = 0, int sa1 = INT_MAX, int sb0 = 0, int sb1 = 0)
 {
-    if (c->upd_x1 >= c->nxl) return FDW_OK;
-    const size_t off = (size_t)c->upd_x1 * c->pitch, n = (size_t)(c->nxl - c->upd_x1) * c->pitch * sizeof(float);
-    auto pair = [&](float* o1, float* o2, const float* p, const float* pp) -> int {
-        HIP_TRY(hipMemcpyAsync(o1 + off, pp + off, n, hipMemcpyDeviceToDevice, s));
-        HIP_TRY(hipMemcpyAsync(o2 + off, p + off, n, hipMemcpyDeviceToDevice, s));
-        return FDW_OK;
-    };
-    FDW_TRY(pair(a.out1, a.out2, a.p, a.pp));
-    if (mode == FDW_MODE_PLAIN_ALL) FDW_TRY(pair(a.lvl0, a.lvl1, a.p, a.pp));
-    if (mode == FDW_MODE_BACK4) FDW_TRY(pair(a.rout1, a.rout2, a.rp, a.rpp));
+    const int span[2][2] = {{sa0, sa1}, {sb0, sb1}};
+    for (const auto& sp : span) {
+        const int x0 = std::max(sp[0], c->upd_x1), x1 = std::min(sp[1], c->nxl);
+        if (x1 <= x0) continue;
+        const size_t off = (size_t)x0 * c->pitch, n = (size_t)(x1 - x0) * c->pitch * sizeof(float);
+        auto pair = [&](float* o1, float* o2, const float* p, const float* pp) -> int {
+            HIP_TRY(hipMemcpyAsync(o1 + off, pp + off, n, hipMemcpyDeviceToDevice, s));
+            HIP_TRY(hipMemcpyAsync(o2 + off, p + off, n, hipMemcpyDeviceToDevice, s));
+            return FDW_OK;
+        };
+        FDW_TRY(pair(a.out1, a.out2, a.p, a.pp));
+        if (mode == FDW_MODE_PLAIN_ALL) FDW_TRY(pair(a.lvl0, a.lvl1, a.p, a.pp));
+        if (mode == FDW_MODE_BACK4) FDW_TRY(pair(a.rout1, a.rout2, a.rp, a.rpp));
+    }
     // (the pipeline's receiver passes, inj2 = NULL, run only where every receiver row is time-stepped: fdw_receivers_stepped)
     if (mode != FDW_MODE_RECV || !a.inj2) return FDW_OK;
     FDW_TRY(static_receiver_rows(c, a.inj_x, a.inj_n, c->nxl, a.out1, a.inj, a.psrc_a, a.img, a.inj_z, a.img_z1, s));
@@ -877,7 +883,11 @@ static int stepn_impl(fdw_ctx* c, int mode, const float* d_p, const float* d_pp,
     a.nstrip = (ncells + own - 1) / own;
     a.nzblk = a.nstrip;
     const int rows_a = std::max(a.r1 - a.r0, 0), rows_b = std::max(a.r1b - a.r0b, 0), rows = rows_a + rows_b;
-    if (rows <= 0) return FDW_OK;
+    static_assert(kPipeSteps % 2 == 0, "static-row bookkeeping assumes an even number of steps per pass");
+    auto static_rows = [&]() -> int {      // the static rows among the rows asked for
+        return whole ? even_steps_tail(c, mode, a, s) : even_steps_tail(c, mode, a, s, rr.r0, rr.r1, rr.r0b, rr.r1b);
+    };
+    if (rows <= 0) return g_plan ? FDW_OK : static_rows();      // no time-stepped row among them: nothing to launch
     // whole ring turns: xchunk + (NS-1)(2H+1) = 10k  ->  xchunk = 10k - 27 (13, 23, ... 83, 93, ...)
     const long strip_rows = (long)rows * a.nstrip;
     // measured: 16384^2 579 Gpt/s at 253 (560 at 173); 8192^2 566 at 173 (509 at 83, 553 at 253); 4096^2 452 at 83 (382 at 43, 388 at 173);
@@ -908,8 +918,7 @@ static int stepn_impl(fdw_ctx* c, int mode, const float* d_p, const float* d_pp,
     }
     hipError_t e = launch_stepn(a, c->h, kmode, s);
     if (e != hipSuccess) return fail(FDW_EHIP, "stepn launch failed: %s", hipGetErrorString(e));
-    static_assert(kPipeSteps % 2 == 0, "static-row bookkeeping assumes an even number of steps per pass");
-    return whole || rr.r1 >= c->upd_x1 || rr.r1b >= c->upd_x1 ? even_steps_tail(c, mode, a, s) : FDW_OK;
+    return static_rows();
 }
 
 int fdw_receivers_stepped(const fdw_ctx* c) { return c->prm.nxb + c->nx <= c->xlim; }

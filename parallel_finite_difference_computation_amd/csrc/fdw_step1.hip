@@ -211,7 +211,12 @@ __device__ __forceinline__ void march(const StepArgs& a, const ShotView& sv, con
                 if (rec_here && r >= a.rec_x0 && r < a.rec_x0 + a.rec_n) {      // the trace sample of this step: the current field at depth rec_z
 #pragma unroll
                     for (int e = 0; e < 4; ++e)
-                        if (z0 + e == a.rec_z) sv.rec[r - a.rec_x0] = c.v[e];      // interior point: its damping factors are 1.0f
+                        // mod_main's iteration is fd_step, ptsrc, taper_apply(PP), taper_apply(P), and only then data = P (mod_main.cpp:147-157): the
+                        // sample is P after this iteration's taper_apply.  The device array holds P one pass short of the field fd_step reads; the
+                        // window row c got that pass on load, so it is fd_step's P, and this iteration's own pass -- which the array will only
+                        // see on the next load -- is applied here: the column's z factor (1.0f, exact, between the strips; receiver rows are
+                        // interior rows and carry no x factor).  Two passes from the array, as two taper_apply calls lie between it and the sample.
+                        if (z0 + e == a.rec_z) sv.rec[r - a.rec_x0] = c.v[e] * tzc[e];
                 }
             }
             if constexpr (DD && NUM == 0) {
@@ -269,7 +274,7 @@ __device__ __forceinline__ void march(const StepArgs& a, const ShotView& sv, con
                     for (int e = 0; e < 4; ++e) {
                         const int dz = z0 + e - a.inj_z, dza = dz < 0 ? -dz : dz;
                         const float g = dza == 0 ? g0 : (dza == 1 ? g1 : (dza == 2 ? g2 : g3));
-                        if (dza <= 3) res.v[e] = res.v[e] + inj_src * g;
+                        if (dza <= 3 && mupd[e]) res.v[e] = res.v[e] + inj_src * g;      // ptsrc.c leaves out the cells beyond the grid edge: none lands in a padding column
                     }
                 }
             }

@@ -227,7 +227,7 @@ __device__ __forceinline__ void marchn(const Step2Args& a, const int lane, const
             if (rec_here && own && r >= xa && r < xe && r >= a.rec_x0 && r < a.rec_x0 + a.rec_n) {
 #pragma unroll
                 for (int e = 0; e < 4; ++e)
-                    if (z0 + e == a.rec_z) a.rec[k * a.rec_n + (r - a.rec_x0)] = c1.v[e];
+                    if (z0 + e == a.rec_z) a.rec[k * a.rec_n + (r - a.rec_x0)] = c1.v[e] * tzc[e];      // after this step's taper_apply, as the one-step kernel
             }
         }
         auto row = [&](auto IO) -> const f4& { return ring[(U + decltype(IO)::value) % R]; };
@@ -298,7 +298,7 @@ __device__ __forceinline__ void marchn(const Step2Args& a, const int lane, const
                 for (int e = 0; e < 4; ++e) {
                     const int dz = z0 + e - a.inj_z, dza = dz < 0 ? -dz : dz;
                     const float g = dza == 0 ? g0 : (dza == 1 ? g1 : (dza == 2 ? g2 : g3));
-                    if (dza <= 3) u.v[e] = u.v[e] + injv * g;
+                    if (dza <= 3 && mupd[e]) u.v[e] = u.v[e] + injv * g;      // ptsrc.c leaves out the cells beyond the grid edge: none lands in a padding column
                 }
             }
         }

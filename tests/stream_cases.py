@@ -33,7 +33,20 @@ DECKS = {
     "stepped": dict(geom=(69, 301, 8, 10), compat=True, dx=10.0, dz=12.5, place=(26, 258, 255), tuning={}),
     # the deck of tests/test_tile_classes.py: 14 chunk rows x 3 strips at 13-row chunks, lean and full tiles in one launch
     "tiles": dict(geom=(180, 500, 12, 14), compat=False, dx=10.0, dz=10.0, place=(84, 300, 310), tuning=dict(xchunk=13)),
+    # ---- the edge decks of tests/test_dev_footprint.py (FOOTPRINT_CASES only) ----
+    # pitch == nze == 320: no padding column absorbs a stray store; the second pipeline strip (columns 224..447) and the second 256-column
+    # strip of the one-step kernels run 128 / 192 columns past the row end, into the next row.  Rows 64..68 static, every receiver row
+    # (8..60) time-stepped, so fdw_dev_back4 runs.  xlim 64, zlim 320, ztap 8.  Every placement is accepted as the table gives it.
+    "flush": dict(geom=(69, 320, 8, 10), compat=True, dx=10.0, dz=12.5, place=(26, 258, 255), tuning={}),
+    # 449 = 2 x 224 + 1: the third pipeline strip owns ONE column (448), which is the receiver column; the source sits in the last owned
+    # columns of strip 1 (sz = 446, so the 7 x 7 source of the modelling dialect is cut off by the grid edge at column 448); pitch 512,
+    # 63 padding columns.  Whole-grid update: xlim 69, zlim 449.  Every placement is accepted as given.
+    "onecol": dict(geom=(69, 449, 8, 10), compat=False, dx=10.0, dz=10.0, place=(26, 446, 448), tuning={}),
+    # one partial strip (61 columns, pitch 64) and 41 rows: shorter than the shortest automatic chunk of the pipeline (43) and hardly longer
+    # than its 27-step prologue, so every wave spends most of its march outside the grid.  xlim 40, zlim 56, ztap 8.  Placements as given.
+    "narrow": dict(geom=(41, 61, 6, 9), compat=True, dx=10.0, dz=12.5, place=(20, 40, 38), tuning={}),
 }
+EDGE_DECKS = ("flush", "onecol", "narrow")
 FAMILIES = {"one-step": -1, "two-step": 1, "pipeline": 4}
 
 
@@ -64,7 +77,7 @@ def inputs(deck, v):
     planted = np.array(clean)
     xlim, _, ztap = extents_of(d)
     if D["compat"] and xlim < nxe and ztap > 0:
-        planted[xlim, 0], planted[nxe - 1, ztap - 1], planted[xlim + 1, 3] = 1e-30, -4.0, 2.5
+        planted[xlim, 0], planted[nxe - 1, ztap - 1], planted[min(xlim + 1, nxe - 1), 3] = 1e-30, -4.0, 2.5
     return _freeze(dict(d=d, v2=d["v2"], p0=p0, pp0=pp0, f1=f1, f0=f0, pr=pr, ppr=ppr, m0=m0, m1=m1, srce=srce,
                         msrce=(1e-2 * rng.standard_normal(NT)).astype(f), w=rng.standard_normal((NT, nx)).astype(f),
                         il0=(0.5 + rng.random((nxe, nze))).astype(f), img0=rng.standard_normal((nxe, nze)).astype(f),
@@ -76,6 +89,13 @@ def inputs(deck, v):
 def oracle(deck, numerics):
     D = DECKS[deck]
     return O.Oracle(*args_of(inputs(deck, "true")["d"]), compat=D["compat"], numerics=numerics)
+
+
+def damped_once(deck, field):
+    """The field after the one damping pass fdw_dev_taper_finalize applies to it (Oracle.slab_step with no row to step)."""
+    f = np.array(field, np.float32, order="C")
+    oracle(deck, 0).slab_step(0, f, np.zeros_like(f), np.ascontiguousarray(inputs(deck, "true")["v2"]), 0, 0, -1, 0, 0.0)
+    return f
 
 
 @functools.lru_cache(maxsize=None)
@@ -142,11 +162,20 @@ class Case:
     ins(i) -> {buffer: (kind, array)} for an argument set i; kind "field" = [nxe][pitch] on the device, "flat" = dense.
     outs   -> {buffer: (kind, shape, sentinel)}: pure outputs.
     call(ctx, ptr, stream) -> [(label, buffer, post or None, rows or None)]: makes the call(s) and says where each answer lies.
-    want(v) -> {label: array}."""
+    want(v) -> {label: array}.
+    What tests/test_dev_footprint.py reads on top (fdwave.h's words about who writes what, not what the code does):
+    scratch       buffers the call may overwrite although no label names them (the rotating buffers of a loop);
+    written_rows  {buffer: rows} where the rows a call may write are not the rows of the buffer's label (an image compared on its
+                  interior; fdw_dev_steps_shrink, whose rows between the valid ones hold intermediate values);
+    finalized     buffers the case itself hands to fdw_dev_taper_finalize after the call: their rows outside the rows asked for come back
+                  damped once (damped_once), not as uploaded;
+    tuning        set_tuning arguments of this case alone, on top of the deck's."""
 
-    def __init__(self, name, deck, numerics, two_step, ins, outs, call, want, dialect=0, env=None):
+    def __init__(self, name, deck, numerics, two_step, ins, outs, call, want, dialect=0, env=None, scratch=(), written_rows=None, tuning=None,
+                 finalized=()):
         self.name, self.deck, self.numerics, self.two_step, self.dialect, self.env = name, deck, numerics, two_step, dialect, env or {}
         self.ins, self.outs, self.call, self.want = ins, outs, call, want
+        self.scratch, self.written_rows, self.tuning, self.finalized = tuple(scratch), dict(written_rows or {}), dict(tuning or {}), tuple(finalized)
 
     def make_ctx(self):
         """The context of the case; self.env holds switches the library reads when a context is created."""
@@ -168,21 +197,24 @@ class Case:
             ctx = F.FDWave(8, d["nxe"], d["nze"], d["nxb"], d["nzb"], NT, MOD_FAC, D["dx"], D["dz"], 0.001, device=0, dialect=1, numerics=self.numerics)
         else:
             ctx = F.FDWave(*args_of(d), compat=D["compat"], device=0, numerics=self.numerics)
-        if self.two_step is not None:
-            ctx.set_tuning(two_step=self.two_step, **D["tuning"])
+        if self.two_step is not None:      # (one set_tuning call: it sets every knob, the ones left out to their defaults)
+            ctx.set_tuning(two_step=self.two_step, **dict(D["tuning"], **self.tuning))
             assert ctx.steps_per_pass() == {-1: 1, 1: 2 if self.dialect == 0 else 1, 4: 4}[self.two_step]
+        elif self.tuning:
+            ctx.set_tuning(**self.tuning)
         return ctx
 
     def __repr__(self):
         return self.name
 
 
-CASES = []
+CASES = []                # what tests/test_stream_contract.py runs: 100 cases, names and order pinned by tests/test_dev_footprint.py
+FOOTPRINT_CASES = []      # the same builders on the edge decks, and the row-range cases: tests/test_dev_footprint.py only
 
 
-def _add(name, deck, numerics, two_step, ins, outs, call, want, **kw):
+def _add(name, deck, numerics, two_step, ins, outs, call, want, to=None, **kw):
     tag = f"{name}-{deck}" + ("" if two_step is None else "-" + {v: k for k, v in FAMILIES.items()}[two_step]) + ("-fast" if numerics else "")
-    CASES.append(Case(tag, deck, numerics, two_step, ins, outs, call, want, **kw))
+    (CASES if to is None else to).append(Case(tag, deck, numerics, two_step, ins, outs, call, want, **kw))
 
 
 def _dims(deck):
@@ -190,7 +222,7 @@ def _dims(deck):
     return nxe, nze, nxb, nzb, nxe - 2 * nxb, nze - 2 * nzb
 
 
-def _loop_case(kind, deck, numerics, two_step, split=((0, NT),)):
+def _loop_case(kind, deck, numerics, two_step, split=((0, NT),), to=None):
     """The forward loops over four rotating buffers: kind = steps2 | record | illum | record_illum | line | line_rec | line_ill | line_rec_ill."""
     nxe, nze, nxb, nzb, nx, nz = _dims(deck)
     sx, sz, gz = DECKS[deck]["place"]
@@ -242,7 +274,7 @@ def _loop_case(kind, deck, numerics, two_step, split=((0, NT),)):
             out["illum"] = c["illum"]
         return out
 
-    _add(kind + ("" if len(split) == 1 else "-chained"), deck, numerics, two_step, ins, outs, call, want)
+    _add(kind + ("" if len(split) == 1 else "-chained"), deck, numerics, two_step, ins, outs, call, want, to=to, scratch=("b0", "b1", "b2", "b3"))
 
 
 LOOP_KINDS = ("steps2", "record", "illum", "record_illum", "line", "line_rec", "line_ill", "line_rec_ill")
@@ -259,7 +291,7 @@ for _kind in ("steps2", "record", "illum", "record_illum", "line", "line_rec_ill
 _loop_case("steps2", "tiles", 1, 4)
 
 
-def _two_buffer_case(kind, deck, numerics):
+def _two_buffer_case(kind, deck, numerics, to=None):
     """fdw_dev_steps (9 steps) and fdw_dev_steps_shrink (3 cycle steps, both sides shrinking) on two buffers: always the one-step kernel."""
     nxe, nze, nxb, nzb, nx, nz = _dims(deck)
     sx, sz, gz = DECKS[deck]["place"]
@@ -281,10 +313,12 @@ def _two_buffer_case(kind, deck, numerics):
         c = chain(deck, numerics, v, False) if kind == "steps" else shrink_chain(deck, numerics, v, n)
         return dict(PP=c["PP"] if rows is None else c["PP"][rows], P=c["P"] if rows is None else c["P"][rows])
 
-    _add(kind, deck, numerics, None, ins, {}, call, want)
+    # fdw_dev_steps_shrink: the rows between the outermost four on either side and the valid ones hold intermediate values
+    _add(kind, deck, numerics, None, ins, {}, call, want, to=to, scratch=("A", "B"),
+         written_rows=None if rows is None else dict(A=slice(4, nxe - 4), B=slice(4, nxe - 4)), finalized=() if rows is None else ("B",))
 
 
-def _pass_case(kind, deck, numerics, ranges=None):
+def _pass_case(kind, deck, numerics, ranges=None, to=None, tag="-two-ranges"):
     """One pass of fdw_dev_step (FWD), fdw_dev_step2 or fdw_dev_step4 from (p0, pp0); step4 optionally on two row ranges."""
     nxe, nze, nxb, nzb, nx, nz = _dims(deck)
     sx, sz, gz = DECKS[deck]["place"]
@@ -318,10 +352,10 @@ def _pass_case(kind, deck, numerics, ranges=None):
         c = chain(deck, numerics, v, False, n)
         return dict(PP=c["PP"] if rows is None else c["PP"][rows], P=c["P"] if rows is None else c["P"][rows])
 
-    _add(kind + ("-two-ranges" if ranges else ""), deck, numerics, None, ins, outs, call, want)
+    _add(kind + (tag if ranges else ""), deck, numerics, None, ins, outs, call, want, to=to, finalized=("O1",) if ranges else ())
 
 
-def _back_case(kind, deck, numerics, two_pass=False):
+def _back_case(kind, deck, numerics, two_pass=False, to=None):
     """fdw_dev_step PLAIN / RECV, fdw_dev_back_iter (step_source 0 / 1) and fdw_dev_back4 from noise-filled source and receiver fields.
     The image is compared on the interior cells: d_img lies on the extended grid, the kernels also accumulate in its border cells inside
     their launch extents, and only the interior is what fd_back's kernel_img defines (and what the host entry points return).
@@ -370,10 +404,10 @@ def _back_case(kind, deck, numerics, two_pass=False):
             return dict(F0=c["F0"])
         return {k: c[k] for k in ("r_new", "img") + (("F0",) if kind == "back_iter1" else ())}
 
-    _add(kind + ("-two-pass" if two_pass else ""), deck, numerics, None, ins, outs, call, want, env={"FDW_NO_BACK_FUSED": "1"} if two_pass else None)
+    _add(kind + ("-two-pass" if two_pass else ""), deck, numerics, None, ins, outs, call, want, to=to, env={"FDW_NO_BACK_FUSED": "1"} if two_pass else None)
 
 
-def _model_case(deck, numerics, two_step):
+def _model_case(deck, numerics, two_step, to=None):
     nxe, nze, nxb, nzb, nx, nz = _dims(deck)
     sx, sz, gz = DECKS[deck]["place"]
 
@@ -386,10 +420,11 @@ def _model_case(deck, numerics, two_step):
         return [("rec", "rec", None, None), ("P", "B", lambda a: O.mod_taper_apply(a, nx, nz, nxb, nzb, MOD_FAC, 1), None),
                 ("PP", "A", lambda a: O.mod_taper_apply(a, nx, nz, nxb, nzb, MOD_FAC, 2), None)]
 
-    _add("model_steps", deck, numerics, two_step, ins, dict(rec=("flat", (NT, nx), 9.0)), call, lambda v: dict(mod_chain(deck, numerics, v)), dialect=1)
+    _add("model_steps", deck, numerics, two_step, ins, dict(rec=("flat", (NT, nx), 9.0)), call, lambda v: dict(mod_chain(deck, numerics, v)), to=to, dialect=1,
+         scratch=("A", "B"))
 
 
-def _small_case(kind, deck, numerics=0):
+def _small_case(kind, deck, numerics=0, to=None):
     nxe, nze, nxb, nzb, nx, nz = _dims(deck)
     D = DECKS[deck]
     DEC = 3
@@ -422,7 +457,7 @@ def _small_case(kind, deck, numerics=0):
         outs = dict(FRAME=("flat", (-(-nx // DEC), -(-nz // DEC)), 9.0))
         call = lambda ctx, p, s: (ctx.dev_snapshot(p["FLD"], DEC, p["FRAME"], stream=s), [("frame", "FRAME", None, None)])[1]  # noqa: E731
         want = lambda v: dict(frame=np.ascontiguousarray(inputs(deck, v)["p0"][nxb:nxb + nx:DEC, nzb:nzb + nz:DEC]))          # noqa: E731
-    _add(kind, deck, numerics, None, ins, outs, call, want)
+    _add(kind, deck, numerics, None, ins, outs, call, want, to=to)
 
 
 for _num in (0, 1):
@@ -447,6 +482,110 @@ for _kind in ("taper_finalize", "gather_residual", "gather_residual-in-place", "
 
 BY_NAME = {c.name: c for c in CASES}
 assert len(BY_NAME) == len(CASES)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------
+# FOOTPRINT_CASES (tests/test_dev_footprint.py): calls on row ranges, and the catalogue on the edge decks
+# ---------------------------------------------------------------------------------------------------------------------------------------
+def _rows_case(kind, deck, r0, r1, tuning=None, to=None):
+    """fdw_dev_step FWD / PLAIN / RECV and fdw_dev_back_iter(step_source = 1) on local rows [r0, r1) only, from fresh fields (pp_twice = 0),
+    against Oracle.slab_step / slab_back_iter on the same rows.  The field read as d_p is not finalized afterwards: it is `const` and must
+    come back as it went in.  The image is compared on its interior; the rows the call may write in it are [r0, r1)."""
+    nxe, nze, nxb, nzb, nx, nz = _dims(deck)
+    sx, sz, gz = DECKS[deck]["place"]
+    rows = slice(r0, r1)
+    irows = slice(max(r0, nxb) - nxb, max(min(r1, nxb + nx), nxb) - nxb)      # the interior rows among them, as rows of the cropped image
+
+    def crop(a):
+        return np.ascontiguousarray(a[nxb:nxb + nx, nzb:nzb + nz])
+
+    if kind == "step_fwd":
+        ins = lambda i: dict(NEW=("field", i["pp0"]), OLD=("field", i["p0"]), v2=("field", i["v2"]), src=("flat", i["srce"]))      # noqa: E731
+    else:
+        ins = lambda i: dict(F1=("field", i["f1"]), F0=("field", i["f0"]), PR=("field", i["pr"]), PPR=("field", i["ppr"]), v2=("field", i["v2"]),      # noqa: E731
+                             IMG=("field", i["img0"]), SAMP=("flat", i["samples"]))
+
+    def call(ctx, p, stream):
+        from parallel_finite_difference_computation_amd._lib import MODE_FWD, MODE_PLAIN, MODE_RECV
+        if kind == "step_fwd":
+            ctx.dev_step(MODE_FWD, p["NEW"], p["OLD"], p["v2"], r0, r1, pp_twice=False, d_inj=p["src"], inj_x=sx, inj_z=sz, stream=stream)
+            return [("PP", "OLD", None, rows)]
+        if kind == "step_plain":
+            ctx.dev_step(MODE_PLAIN, p["F1"], p["F0"], p["v2"], r0, r1, pp_twice=False, stream=stream)
+            return [("F0", "F0", None, rows)]
+        if kind == "step_recv":
+            ctx.dev_step(MODE_RECV, p["PR"], p["PPR"], p["v2"], r0, r1, pp_twice=False, d_inj=p["SAMP"], inj_x=0, inj_z=gz, d_psrc=p["F1"], d_img=p["IMG"],
+                         stream=stream)
+            return [("r_new", "PPR", None, rows), ("img", "IMG", crop, irows)]
+        ctx.dev_back_iter(1, p["F1"], p["F0"], p["PR"], p["PPR"], p["v2"], r0, r1, False, p["SAMP"], gz, p["IMG"], stream=stream)
+        return [("r_new", "PPR", None, rows), ("img", "IMG", crop, irows), ("F0", "F0", None, rows)]
+
+    @functools.lru_cache(maxsize=None)
+    def answers(v):
+        i = inputs(deck, v)
+        orc = oracle(deck, 0)
+        if kind == "step_fwd":
+            P, PP = np.array(i["pp0"], np.float32, order="C"), np.array(i["p0"], np.float32, order="C")
+            orc.slab_step(0, P, PP, i["v2"], r0, r1, sx, sz, float(i["srce"][0]))
+            return _freeze(dict(PP=PP[rows]))
+        f1, f0, pr, ppr, img = (np.array(i[k], np.float32, order="C") for k in ("f1", "f0", "pr", "ppr", "img0"))
+        if kind == "step_plain":      # F_k = leap-frog(f1, f0) over f0: no taper, no source (R:317-318) -- the source half of slab_back_iter
+            orc.slab_back_iter(0, 1, f1, f0, pr, ppr, i["v2"], r0, r1, i["samples"][0], gz, img)
+            return _freeze(dict(F0=f0[rows]))
+        ss = 0 if kind == "step_recv" else 1
+        orc.slab_back_iter(0, ss, f1, f0, pr, ppr, i["v2"], r0, r1, i["samples"][0], gz, img)
+        out = dict(r_new=ppr[rows], img=crop(img)[irows])
+        if ss:
+            out["F0"] = f0[rows]
+        return _freeze(out)
+
+    _add(f"{kind}-rows{r0}-{r1}", deck, 0, None, ins, {}, call, lambda v: dict(answers(v)), to=to, tuning=tuning,
+         written_rows={} if kind in ("step_fwd", "step_plain") else dict(IMG=rows))
+
+
+def _footprint_cases():
+    to = FOOTPRINT_CASES
+    def limits(deck):      # nxe, xlim as fdw_get_extents gives it (pinned per deck by tests/test_dev_footprint.py)
+        nxe = DECKS[deck]["geom"][0]
+        return nxe, 8 * (nxe // 8) if DECKS[deck]["compat"] else nxe
+
+    for deck in ("ragged",) + EDGE_DECKS:
+        nxe, xlim = limits(deck)
+        for kind in ("step_fwd", "step_plain", "step_recv", "back_iter1"):
+            _rows_case(kind, deck, 0, 9, to=to)
+            # the shortest chunk: fill_geometry (csrc/fdw_api.cpp) takes the context's xchunk for the one-step kernels as it stands, so
+            # every wave marches one row -- thirteen chunk borders inside the range; the answer does not depend on it, the footprint could
+            _rows_case(kind, deck, 17, 30, tuning=dict(xchunk=1), to=to)
+            _rows_case(kind, deck, xlim - 9, nxe, to=to)
+    for deck in EDGE_DECKS:
+        nxe, xlim = limits(deck)
+        for kind in LOOP_KINDS:
+            for fam in (-1, 1, 4):
+                _loop_case(kind, deck, 0, fam, to=to)
+        for fam in (-1, 1, 4):      # FAST kernels are separate instantiations: one loop per family
+            _loop_case("steps2", deck, 1, fam, to=to)
+        _two_buffer_case("steps", deck, 0, to=to)
+        _two_buffer_case("steps_shrink", deck, 0, to=to)
+        for kind in ("step_fwd", "step2", "step4"):
+            _pass_case(kind, deck, 0, to=to)
+        # two row ranges that touch row 0 and the last time-stepped row, six rows apart
+        _pass_case("step4", deck, 0, ranges=dict(r0=0, r1=(xlim - 6) // 2, r0b=(xlim - 6) // 2 + 6, r1b=xlim), to=to)
+        if xlim + 4 < nxe:      # static rows (flush: 64..68) among the rows asked for: copied from the inputs, they and no others
+            # a range that ends inside them, a gap of two static rows, a second range that holds static rows only
+            _pass_case("step4", deck, 0, ranges=dict(r0=0, r1=xlim + 1, r0b=xlim + 3, r1b=nxe), to=to, tag="-static-gap")
+            # no time-stepped row asked for at all: nothing is launched, two static rows are copied
+            _pass_case("step4", deck, 0, ranges=dict(r0=xlim, r1=xlim + 2, r0b=0, r1b=0), to=to, tag="-static-only")
+        for kind in ("step_plain", "step_recv", "back_iter0", "back_iter1", "back4"):
+            _back_case(kind, deck, 0, to=to)
+        _back_case("back4", deck, 0, two_pass=True, to=to)
+        _model_case(deck, 0, -1, to=to)
+        _model_case(deck, 0, 4, to=to)
+        for kind in ("laplacian", "taper_finalize", "snapshot", "gather_residual", "gather_residual-in-place"):
+            _small_case(kind, deck, to=to)
+
+
+_footprint_cases()
+assert len({c.name for c in CASES + FOOTPRINT_CASES}) == len(CASES) + len(FOOTPRINT_CASES)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------------
