@@ -652,6 +652,64 @@ int fdw_record_shot_line_batch(fdw_ctx *ctx, int nshots, const float *v2_all, un
 int fdw_encode_gathers_multi(int device, int nshots, int nplanes, const int *lag, const float *weight, const float *d_obs_all, int nx, int nt,
                              float *out);
 
+/* ---- excitation-amplitude imaging: a receiver-only backward loop ---------------------------------------------------------------
+ * The other standard RTM imaging condition.  The forward loop remembers, per cell, the peak of the source field and the time level at which
+ * it occurred (the excitation time); the backward loop propagates the receiver field ALONE, and every cell takes one sample of it, at its
+ * excitation time, divided by the peak.  No source field is reconstructed, no product is accumulated, and the image is source-normalised as
+ * it comes.  The RTM dialect on full-grid contexts, EXACT and FAST numerics alike (FAST changes the Laplacian only).  Slab contexts, the
+ * sibling's dialects and a context inside a batch: FDW_ESTATE.  A NULL required pointer, it0 < 0, a depth outside [0, zlim) (as for line
+ * sources), a source row the loop never time-steps: FDW_EINVAL.  Every refusal happens before anything is enqueued.
+ *
+ * Excitation maps.  Two field-shaped device arrays [nxl][pitch], d_amp (float) and d_texc (int32).  Over every extended-grid cell with
+ * x < xlim, z < zlim (fdw_get_extents), for it = it0 .. it0+nsteps-1 in ascending order, with u the value stored as the new field at the end
+ * of iteration it -- after kernel_src, raw and undamped, the level recording, illumination and snapshots sample:
+ *         if (fabsf(u) > fabsf(amp)) { amp = u; texc = it + 1; }
+ * The compare is strict (the first of equal peaks wins), a NaN u never wins and a NaN already in amp stays, +-0 never replaces anything, an
+ * infinity wins once, amp keeps the SIGNED winner.  Both arrays are read-modify-write and start from what the caller put there (a fresh shot:
+ * all-zero words).  Cells outside the extents and the padding columns keep their words.  No arithmetic is involved: the maps are exact.
+ *
+ * Excitation pick.  The line-source loop of fdw_dev_line_steps (d_wav [>= it0+nsteps][nx], row it = the samples of iteration it at depth sz,
+ * rows >= nsrc ignored, same damping, same static rows) with one epilogue: after the injection of iteration it, over the same cells,
+ *         if (texc == top - it) exc = r;        r: the stored new field, injected sample included, raw
+ * d_texc is only read.  d_exc (float [nxl][pitch]) changes only where a pick happens; every other word keeps its entry value, padding columns
+ * and cells outside the extents included.  The test is int32 equality: a cell whose texc is not in (top - it0 - nsteps, top - it0] is never
+ * picked.
+ *
+ * fdw_dev_excite_steps      fdw_dev_steps2's loop with the maps.  The same buffers, indices and fields, bit for bit; everything on the
+ *                           caller's stream, nothing synchronised, no pass bands.  d_srce NULL or sx < 0: no source.
+ * fdw_dev_line_pick_steps   fdw_dev_line_steps' plain loop with the pick; the same contract.
+ *   Kernels: the one-step register-ring family (orders 2-8, prefetch 1 / 2 / 3) and the four-step wave pipeline have fused kernels for both,
+ *   EXACT and FAST; orders above 8 and the forced generic kernel run the generic step followed by a small compare-and-select / pick
+ *   kernel.  In the pipeline the amp (exc) row rides the 16-slot LDS FIFO as the illumination accumulator does, with a dword of 4-bit
+ *   tags per lane and row beside it that says which level of the pass won (picks) each cell: 52 KiB of LDS, three workgroups per CU.  The
+ *   two-step family has NO excitation kernel: on a context whose plain loop runs pairs, a pair becomes two single steps that land in the
+ *   buffers the pair would have used (each on a copy of the field it overwrites), so fields, indices and static rows still equal the
+ *   plain loop's.  Traffic: +16 B/point per forward pass (amp and texc, in and out), +12 B/point per pick pass (texc and exc in, exc out).
+ *   Measured on one MI355X at 8192^2, order 8 (profiles/excitation.json): the forward loop with the maps 142.5 us
+ *   per step against 96.6 plain and 123.1 with illumination (FAST 135.8 / 86.8 / 115.4); the line loop with the pick 129.8 against 97.0
+ *   (FAST 123.8 / 86.6).  A whole fdw_shot_excitation of 500 steps takes 266.8 ms against fdw_shot's 187.2 ms (FAST 257.4 / 174.1): the
+ *   device loops are 0.85 of fdw_shot's, but three interior arrays come back instead of one and the image is formed on the host, so the
+ *   shot is 1.43x SLOWER, not cheaper; on a 415 x 295 deck (nt 1700) the two are level (19.8 against 19.5 ms).
+ * fdw_shot_excitation       One shot from rest: the forward loop of fdw_shot for nt steps with the maps; the receiver fields zeroed; nt
+ *                           iterations of the pick loop with top = nt, row k of the line gather = d_obs[.][nt-1-k], at depth gz.  Iteration
+ *                           k meets the cells whose excitation level is nt - k: sample j pairs with level u^{j+1}, as in the recording
+ *                           section.  Receiver rows the loop never time-steps (ix >= nsrc) are NOT injected -- the line-source rule, which
+ *                           differs from fd_back on ragged compat grids.  v2 NULL: the resident model.  P / PP: fdw_shot's.  exc, amp,
+ *                           texc: the interiors [nx][nz]; imloc is then updated by fdw_image_excitation.  Each of the four may be NULL,
+ *                           all four NULL is FDW_EINVAL.  The work arrays are allocated on first use.
+ * fdw_image_excitation      Pure host C, no device.  m = max_i fabsf(amp[i]) taken from 0.0f with > (a NaN never wins); s = eps * m; for each
+ *                           i with fabsf(amp[i]) > s: img[i] = img[i] + exc[i] / amp[i], one fp32 division and one fp32 add.  Every other
+ *                           img[i] is left untouched (no + 0.0f: -0.0 survives).  eps not finite or < 0: FDW_EINVAL.  Shots stack by calling
+ *                           it per shot into one img.
+ * Out of scope: batches, slabs, maps under a line source, a combined recording + maps kernel, a two-step excitation kernel. */
+int fdw_dev_excite_steps(fdw_ctx *ctx, float *const *d_buf /* [4] */, const float *d_v2, const float *d_srce, int sx, int sz, float *d_amp,
+                         int *d_texc, int it0, int nsteps, int first_pp_twice, int *ip, int *ipp, void *stream);
+int fdw_dev_line_pick_steps(fdw_ctx *ctx, float *const *d_buf /* [4] */, const float *d_v2, const float *d_wav, int sz, const int *d_texc, int top,
+                            float *d_exc, int it0, int nsteps, int first_pp_twice, int *ip, int *ipp, void *stream);
+int fdw_shot_excitation(fdw_ctx *ctx, const float *v2 /* NULL: the resident model */, int sx, int sz, int gz, const float *srce, const float *d_obs,
+                        float eps, float *imloc, float *exc, float *amp, int *texc, float *P, float *PP);
+int fdw_image_excitation(const float *exc, const float *amp, size_t n, float eps, float *img);
+
 /* ---- tuning / introspection --------------------------------------------------------------------
  * fdw_set_tuning  xchunk = rows marched per wave (0 = auto), wz = waves of a block laid along z
  *                 (1,2,4; 0 = auto), use_generic = force the generic-order kernel (tests),

@@ -107,6 +107,17 @@ def image_compensate(img, illum, eps=1e-3):
     return out
 
 
+def image_excitation(exc, amp, eps=1e-3, img=None):
+    """The excitation-amplitude image of one shot added to img (fdwave.h, fdw_image_excitation): img += exc / amp in fp32 where
+    |amp| > eps * max |amp|, every other cell left as it is.  img=None starts from zeros; shots stack by passing the same img again.  Host
+    arithmetic; eps is a parameter of the method (finite, >= 0).  Returns img (a copy of the one passed in)."""
+    exc = np.ascontiguousarray(exc, np.float32)
+    amp = _f32(amp, exc.shape)
+    img = np.zeros(exc.shape, np.float32) if img is None else np.array(_f32(img, exc.shape), order="C")
+    check(lib().fdw_image_excitation(exc.ctypes.data, amp.ctypes.data, exc.size, eps, img.ctypes.data))
+    return img
+
+
 def gather_misfit(resid):
     """0.5 * sum resid^2 of a data residual (fdwave.h, fdw_gather_misfit): each square and the sum carried in double, added one after the
     other in memory order.  Host arithmetic."""
@@ -486,6 +497,46 @@ class FDWave:
         check(lib().fdw_dev_line_record_illum_steps(self._h, arr, d_v2, d_wav, sz, gz, d_rec, d_illum, it0, nsteps, int(first_pp_twice), C.byref(a),
                                                     C.byref(b), stream))
         return a.value, b.value
+
+    # ---- excitation-amplitude imaging (fdwave.h: a receiver-only backward loop) ----
+    def dev_excite_steps(self, bufs, d_v2, d_srce, sx, sz, d_amp, d_texc, it0, nsteps, first_pp_twice=False, ip=0, ipp=1, stream=None):
+        """dev_steps2 that also keeps the excitation maps d_amp (float) / d_texc (int32), device [nxl][pitch] (fdwave.h).  Returns (ip, ipp).
+        stream=None: the context's own non-blocking stream, unordered against the caller's streams (the legacy default stream included); a caller's
+        stream: every launch, copy and memset of the call is issued on it and the call does not synchronise (fdwave.h)."""
+        arr = (C.c_void_p * 4)(*bufs)
+        a, b = C.c_int(ip), C.c_int(ipp)
+        check(lib().fdw_dev_excite_steps(self._h, arr, d_v2, d_srce, sx, sz, d_amp, d_texc, it0, nsteps, int(first_pp_twice), C.byref(a), C.byref(b),
+                                         stream))
+        return a.value, b.value
+
+    def dev_line_pick_steps(self, bufs, d_v2, d_wav, sz, d_texc, top, d_exc, it0, nsteps, first_pp_twice=False, ip=0, ipp=1, stream=None):
+        """dev_line_steps (plain) that also takes the excitation pick: d_exc = the new field where d_texc == top - it (fdwave.h).  Returns
+        (ip, ipp).
+        stream=None: the context's own non-blocking stream, unordered against the caller's streams (the legacy default stream included); a caller's
+        stream: every launch, copy and memset of the call is issued on it and the call does not synchronise (fdwave.h)."""
+        arr = (C.c_void_p * 4)(*bufs)
+        a, b = C.c_int(ip), C.c_int(ipp)
+        check(lib().fdw_dev_line_pick_steps(self._h, arr, d_v2, d_wav, sz, d_texc, top, d_exc, it0, nsteps, int(first_pp_twice), C.byref(a),
+                                            C.byref(b), stream))
+        return a.value, b.value
+
+    def shot_excitation(self, v2, sx, sz, gz, srce, d_obs, eps=1e-3, imloc=None, want_fields=False):
+        """One shot under the excitation-amplitude imaging condition (fdwave.h, fdw_shot_excitation); v2=None: the resident model.  Returns
+        (imloc, exc, amp, texc), the interiors [nx][nz] (texc int32), and with want_fields also P, PP as shot() returns them.  imloc (a copy of
+        the one passed in, zeros if None) has the shot's image added to it."""
+        shape = (self.nxe, self.nze)
+        inner = (self.nx, self.nz)
+        imloc = np.zeros(inner, np.float32) if imloc is None else np.array(_f32(imloc, inner), order="C")
+        exc, amp, texc = np.zeros(inner, np.float32), np.zeros(inner, np.float32), np.zeros(inner, np.int32)
+        P = np.zeros(shape, np.float32) if want_fields else None
+        PP = np.zeros(shape, np.float32) if want_fields else None
+        srce = _f32(srce, (self.nt,))
+        d_obs = _f32(d_obs, inner[:1] + (self.nt,))
+        check(lib().fdw_shot_excitation(self._h, None if v2 is None else _f32(v2, shape).ctypes.data, sx, sz, gz, srce.ctypes.data, d_obs.ctypes.data,
+                                        eps, imloc.ctypes.data, exc.ctypes.data, amp.ctypes.data, texc.ctypes.data,
+                                        P.ctypes.data if want_fields else None, PP.ctypes.data if want_fields else None))
+        out = (imloc, exc, amp, texc)
+        return out + (P, PP) if want_fields else out
 
     def shot_line_residual(self, v2, sz, gz, wav, d_obs, imloc=None, want_resid=True, want_fields=False, want_illum=False, illum=None):
         """Residual migration with a line source (fdwave.h, fdw_shot_line_residual): shot_line() whose forward loop also models the gather d_mod

@@ -75,6 +75,9 @@ struct fdw_ctx {
     float* fld[10] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};      // 8, 9: source-field levels of a backward pipeline pass
     float *d_v2 = nullptr, *d_img = nullptr, *d_srce = nullptr, *d_dobs = nullptr;
     float* d_illum = nullptr;   // source illumination of one shot on the extended grid (fdw_shot_illum); allocated on first use
+    float* d_amp = nullptr;     // excitation maps and picked samples of one shot on the extended grid (fdw_shot_excitation); allocated on first use
+    int* d_texc = nullptr;
+    float* d_exc = nullptr;
     float* d_snap[3] = {nullptr, nullptr, nullptr};   // frame stores of fdw_shot_snaps (snaps, snaps_rec, snapr): [nframes][nxs][nzs] each
     size_t snap_cap[3] = {0, 0, 0};
     size_t srce_cap = 0, dobs_cap = 0;
@@ -377,7 +380,7 @@ extern "C" void fdw_destroy(fdw_ctx* c)
     float* bufs[] = {c->d_taperz, c->d_txfac, c->d_gcx, c->d_gcz, c->fld[0], c->fld[1], c->fld[2], c->fld[3],
                      c->fld[4], c->fld[5], c->fld[6], c->fld[7], c->fld[8], c->fld[9], c->d_v2, c->d_img, c->d_illum, c->d_srce, c->d_dobs, c->d_rec,
                      c->d_vp, c->d_vpe, (float*)c->d_draws, (float*)c->d_jump, c->bfld[0], c->bfld[1], c->bfld[2], c->bfld[3],
-                     c->bfld[4], c->bfld[5], c->bfld[6], c->bfld[7], c->b_v2, c->b_img, c->b_dobs, c->b_illum, c->b_rec, c->b_wav, c->d_raw, c->d_wav, c->d_snap[0], c->d_snap[1], c->d_snap[2]};
+                     c->bfld[4], c->bfld[5], c->bfld[6], c->bfld[7], c->b_v2, c->b_img, c->b_dobs, c->b_illum, c->b_rec, c->b_wav, c->d_raw, c->d_wav, c->d_snap[0], c->d_snap[1], c->d_snap[2], c->d_amp, (float*)c->d_texc, c->d_exc};
     for (float* b : bufs)
         if (b) (void)hipFree(b);
     if (c->stream) (void)hipStreamDestroy(c->stream);
@@ -530,10 +533,20 @@ static int static_receiver_rows(fdw_ctx* c, int x, int n, int r1, float* field, 
     return FDW_OK;
 }
 
+// excitation-amplitude imaging (fdwave.h): what one forward step does on top of its update.  Maps (pick = false): arr = amp, where the new
+// field beats it strictly in magnitude amp takes it and texc takes key (= it + 1).  Pick: arr = exc, which takes the new field where texc == key
+// (= top - it); texc is only read.
+struct ExcStep {
+    float* arr;
+    int* texc;
+    int key;
+    bool pick;
+};
+
 static int step_impl(fdw_ctx* c, int mode, const float* d_p, float* d_pp, const float* d_v2, int r0, int r1,
                      int pp_twice, const float* d_inj, int inj_x_global, int inj_z, const float* d_psrc, float* d_img,
                      hipStream_t s, float* d_rec_row = nullptr, int rec_z = 0, float* d_fpp = nullptr, float* d_out = nullptr, float* d_illum = nullptr,
-                     bool line = false)
+                     bool line = false, const ExcStep* xs = nullptr)
 {
     const bool lap = (mode == FDW_MODE_LAP);
     if (!d_p || !d_pp) return fail(FDW_EINVAL, "step: field pointer is NULL");
@@ -574,10 +587,17 @@ static int step_impl(fdw_ctx* c, int mode, const float* d_p, float* d_pp, const 
     // (a batch accumulates per shot, illum + shot * field, inside fdw_shot_batch_illum only)
     if (d_illum && (mode != FDW_MODE_FWD || (c->nbatch > 1 && !c->batch_illum)))
         return fail(FDW_EINVAL, "step: illumination belongs to a forward step of one shot");
+    // the maps ride a point-source step, the pick a line-source step; neither is built together with recording or illumination, nor batched
+    if (xs && (mode != FDW_MODE_FWD || xs->pick != line || d_rec_row || d_illum || c->nbatch > 1 || !xs->arr || !xs->texc))
+        return fail(FDW_EINVAL, "step: the excitation maps belong to a plain forward step of one shot, the pick to a plain line-source step");
     // the RTM forward step that records its trace row, that accumulates the source illumination (the accumulator travels in `img`), or both
     const bool fwd = mode == FDW_MODE_FWD;
-    const int kmode = line ? line_kmode(d_rec_row, d_illum)
+    const int kmode = xs ? (xs->pick ? FDW_MODE_FWD_LINE_PICK : FDW_MODE_FWD_EXC)
+                      : line ? line_kmode(d_rec_row, d_illum)
                            : ((fwd && d_rec_row && d_illum) ? FDW_MODE_FWD_REC_ILLUM : ((fwd && d_rec_row) ? FDW_MODE_FWD_REC : ((fwd && d_illum) ? FDW_MODE_FWD_ILLUM : mode)));
+    if (xs) {
+        a.img = xs->arr; a.texc = xs->texc; a.exc_key = xs->key;
+    }
     if (kmode == FDW_MODE_FWD_REC || kmode == FDW_MODE_FWD_REC_ILLUM || kmode == FDW_MODE_FWD_LINE_REC || kmode == FDW_MODE_FWD_LINE_REC_ILLUM)
         fill_rec(c, a, d_rec_row, rec_z);
     if (kmode == FDW_MODE_FWD_ILLUM || kmode == FDW_MODE_FWD_REC_ILLUM || kmode == FDW_MODE_FWD_LINE_ILLUM || kmode == FDW_MODE_FWD_LINE_REC_ILLUM) a.img = d_illum;
@@ -604,9 +624,15 @@ static int step_impl(fdw_ctx* c, int mode, const float* d_p, float* d_pp, const 
         const bool add = kmode == FDW_MODE_FWD_ILLUM || kmode == FDW_MODE_FWD_REC_ILLUM || kmode == FDW_MODE_FWD_LINE_ILLUM || kmode == FDW_MODE_FWD_LINE_REC_ILLUM;
         const int gmode = kmode == FDW_MODE_FWD_ILLUM ? FDW_MODE_FWD
                           : (kmode == FDW_MODE_FWD_REC_ILLUM ? FDW_MODE_FWD_REC
-                             : (kmode == FDW_MODE_FWD_LINE_ILLUM ? FDW_MODE_FWD_LINE : (kmode == FDW_MODE_FWD_LINE_REC_ILLUM ? FDW_MODE_FWD_LINE_REC : kmode)));
+                             : (kmode == FDW_MODE_FWD_LINE_ILLUM ? FDW_MODE_FWD_LINE
+                                : (kmode == FDW_MODE_FWD_LINE_REC_ILLUM ? FDW_MODE_FWD_LINE_REC
+                                   : (kmode == FDW_MODE_FWD_EXC ? FDW_MODE_FWD : (kmode == FDW_MODE_FWD_LINE_PICK ? FDW_MODE_FWD_LINE : kmode)))));
         e = launch_step_generic(a, c->h, gmode, s);
         if (e == hipSuccess && add) e = launch_illum_add(d_pp, d_illum, c->pitch, a.r0, a.r1, c->upd_z1, s);
+        // no generic-order excitation kernel either: the plain step, then the compare-and-select / the pick over the cells it updated
+        if (e == hipSuccess && xs)
+            e = xs->pick ? launch_exc_pick(d_pp, xs->texc, xs->arr, c->pitch, a.r0, a.r1, c->upd_z1, xs->key, s)
+                         : launch_exc_select(d_pp, xs->arr, xs->texc, c->pitch, a.r0, a.r1, c->upd_z1, xs->key, s);
     }
     if (e != hipSuccess) return fail(FDW_EHIP, "kernel launch failed: %s", hipGetErrorString(e));
     if ((mode == FDW_MODE_RECV || mode == FDW_MODE_BACK) && r1 > c->upd_x1)
@@ -790,7 +816,7 @@ static void tile_classes(const Step2Args& a, int kmode, std::vector<unsigned cha
         const int cs = zb * (64 - 2 * NS) - NS;
         const bool lean = kmode == FDW_MODE_PLAIN      ? pipe_tile_lean<H, NS, false, 0>(a, cs, xa, xe)
                           : (kmode == FDW_MODE_FWD_LINE_REC || kmode == FDW_MODE_FWD_LINE_REC_ILLUM) ? pipe_tile_lean<H, NS, true, 2, false, true>(a, cs, xa, xe)
-                          : (kmode == FDW_MODE_FWD_LINE || kmode == FDW_MODE_FWD_LINE_ILLUM) ? pipe_tile_lean<H, NS, true, 2>(a, cs, xa, xe)
+                          : (kmode == FDW_MODE_FWD_LINE || kmode == FDW_MODE_FWD_LINE_ILLUM || kmode == FDW_MODE_FWD_LINE_PICK) ? pipe_tile_lean<H, NS, true, 2>(a, cs, xa, xe)
                                                            : pipe_tile_lean<H, NS, true, 1>(a, cs, xa, xe);
         cls[(size_t)L] = lean ? 0 : 1;
     }
@@ -817,7 +843,7 @@ static thread_local StepnPlan* g_plan = nullptr;
 
 static int stepn_impl(fdw_ctx* c, int mode, const float* d_p, const float* d_pp, const float* d_v2, float* d_out1, float* d_out2, int pp_twice,
                       const float* d_inj, int inj_x_global, int inj_z, hipStream_t s, const RowRanges& rr = RowRanges{}, float* d_rec = nullptr,
-                      int rec_z = 0, const StepnBack* bk = nullptr, float* d_illum = nullptr, bool line = false)
+                      int rec_z = 0, const StepnBack* bk = nullptr, float* d_illum = nullptr, bool line = false, const ExcStep* xs = nullptr)
 {
     if (c->h != kMaxFastHalfOrder) return fail(FDW_EINVAL, "stepn: the pipelined kernel is built for order 8 only");
     if (mode != FDW_MODE_FWD && mode != FDW_MODE_PLAIN && mode != FDW_MODE_MOD && mode != FDW_MODE_PLAIN_ALL && mode != FDW_MODE_RECV && mode != FDW_MODE_BACK4)
@@ -871,9 +897,16 @@ static int stepn_impl(fdw_ctx* c, int mode, const float* d_p, const float* d_pp,
     }
     if (mode == FDW_MODE_MOD) FDW_TRY(fill_mod(c, a, "stepn", d_rec, rec_z));
     if (d_illum && mode != FDW_MODE_FWD) return fail(FDW_EINVAL, "stepn: illumination belongs to a forward pass");
+    // xs: the excitation maps of a point-source pass / the pick of a line-source pass; xs->key belongs to the pass's first step
+    if (xs && (mode != FDW_MODE_FWD || xs->pick != line || d_rec || d_illum || !xs->arr || !xs->texc))
+        return fail(FDW_EINVAL, "stepn: the excitation maps belong to a plain forward pass, the pick to a plain line-source pass");
+    if (xs) {
+        a.img = xs->arr; a.texc = xs->texc; a.exc_key = xs->key;
+    }
     // FWD with d_rec: the trace rows of the pass's four steps; with d_illum: their squares added to the illumination; with both: both
     const bool fwd = mode == FDW_MODE_FWD;
-    const int kmode = line ? line_kmode(d_rec, d_illum)
+    const int kmode = xs ? (xs->pick ? FDW_MODE_FWD_LINE_PICK : FDW_MODE_FWD_EXC)
+                      : line ? line_kmode(d_rec, d_illum)
                            : ((fwd && d_rec && d_illum) ? FDW_MODE_FWD_REC_ILLUM : ((fwd && d_rec) ? FDW_MODE_FWD_REC : ((fwd && d_illum) ? FDW_MODE_FWD_ILLUM : mode)));
     if (kmode == FDW_MODE_FWD_REC || kmode == FDW_MODE_FWD_REC_ILLUM || kmode == FDW_MODE_FWD_LINE_REC || kmode == FDW_MODE_FWD_LINE_REC_ILLUM)
         fill_rec(c, a, d_rec, rec_z);
@@ -1194,8 +1227,20 @@ static int band_passes(fdw_ctx* c, float* const* buf, const float* d_v2, const f
     return rc != FDW_OK ? rc : jrc;
 }
 
+// xl (fdw_dev_excite_steps: the maps; fdw_dev_line_pick_steps, with line: the pick): the same family per pass as the plain loop, each pass
+// through its kernel's excitation variant -- except that there is no two-step excitation kernel: a pair becomes two single steps that land
+// where the pair's pass would (u^{n+1} in buf[o1], u^{n+2} in buf[o2], the current pair left as it is, each on a copy of the field it
+// overwrites): the same fields in all four buffers, the same indices and static rows as the plain loop.
+struct ExcLoop {
+    float* arr;      // amp (maps) or exc (pick)
+    int* texc;
+    int top;         // pick: iteration it takes the cells with texc == top - it
+    bool pick;
+};
+
 static int steps_loop(fdw_ctx* c, float* const* buf, const float* d_v2, const float* d_srce, int sx, int sz, int gz, float* d_rec, int it0, int nsteps,
-                      int first_pp_twice, int* ip, int* ipp, hipStream_t s, float* d_illum = nullptr, bool line = false, bool may_band = false)
+                      int first_pp_twice, int* ip, int* ipp, hipStream_t s, float* d_illum = nullptr, bool line = false, bool may_band = false,
+                      const ExcLoop* xl = nullptr)
 {
     if (!c || !buf || !ip || !ipp) return fail(FDW_EINVAL, "NULL argument");
     if (*ip < 0 || *ip > 3 || *ipp < 0 || *ipp > 3 || *ip == *ipp) return fail(FDW_EINVAL, "steps2: bad buffer indices");
@@ -1222,7 +1267,34 @@ static int steps_loop(fdw_ctx* c, float* const* buf, const float* d_v2, const fl
         float* rec = d_rec ? d_rec + (size_t)(it0 + k) * nxs : nullptr;
         int o1, o2;   // the two buffers not holding the current pair
         spare_pair(*ip, *ipp, &o1, &o2);
-        if (nsteps - k >= kPipeSteps && pipe_pays(c)) {
+        if (xl) {
+            const int m = (nsteps - k >= kPipeSteps && pipe_pays(c)) ? kPipeSteps : ((nsteps - k >= 2 && two_step_pays(c)) ? 2 : 1);
+            auto exc_step = [&](int j) { return ExcStep{xl->arr, xl->texc, xl->pick ? xl->top - (it0 + k + j) : it0 + k + j + 1, xl->pick}; };
+            if (m == kPipeSteps) {
+                const ExcStep xs = exc_step(0);
+                FDW_TRY(stepn_impl(c, FDW_MODE_FWD, buf[*ipp], buf[*ip], d_v2, buf[o1], buf[o2], twice, inj, sxx, sz, s, RowRanges{}, nullptr, 0, nullptr,
+                                    nullptr, line, &xs));
+                *ip = o1; *ipp = o2;
+            } else if (m == 1) {
+                std::swap(*ip, *ipp);
+                const ExcStep xs = exc_step(0);
+                FDW_TRY(step_impl(c, FDW_MODE_FWD, buf[*ip], buf[*ipp], d_v2, 0, c->nxl, twice, inj, sxx, sz, nullptr, nullptr, s, nullptr, 0, nullptr, nullptr,
+                                   nullptr, line, &xs));
+            } else {
+                const size_t bytes = field_elems(c) * sizeof(float);
+                const float* newest = buf[*ipp];
+                for (int j = 0; j < m; j++) {
+                    float* dst = buf[(j & 1) ? o2 : o1];
+                    if (j < 2) HIP_TRY(hipMemcpyAsync(dst, buf[j == 0 ? *ip : *ipp], bytes, hipMemcpyDeviceToDevice, s));
+                    const ExcStep xs = exc_step(j);
+                    FDW_TRY(step_impl(c, FDW_MODE_FWD, newest, dst, d_v2, 0, c->nxl, twice || j > 0, inj ? inj + (size_t)j * (line ? nxs : 1) : nullptr, sxx, sz,
+                                       nullptr, nullptr, s, nullptr, 0, nullptr, nullptr, nullptr, line, &xs));
+                    newest = dst;
+                }
+                *ip = o1; *ipp = o2;
+            }
+            k += m;
+        } else if (nsteps - k >= kPipeSteps && pipe_pays(c)) {
             FDW_TRY(stepn_impl(c, FDW_MODE_FWD, buf[*ipp], buf[*ip], d_v2, buf[o1], buf[o2], twice, inj, sxx, sz, s, RowRanges{}, rec, gz, nullptr,
                                 d_illum, line));
             *ip = o1; *ipp = o2;   // d_p = u^{n+kPipeSteps-1}, d_pp = u^{n+kPipeSteps}
@@ -1378,6 +1450,47 @@ extern "C" int fdw_dev_line_record_illum_steps(fdw_ctx* c, float* const* d_buf, 
     if (it0 < 0) return fail(FDW_EINVAL, "it0=%d", it0);
     FDW_TRY(check_line_args(c, "fdw_dev_line_record_illum_steps", sz, gz, true, true, true));
     return steps_loop(c, d_buf, d_v2, d_wav, -1, sz, gz, d_rec, it0, nsteps, first_pp_twice, ip, ipp, pick_stream(c, stream), d_illum, true);
+}
+
+// ---- excitation-amplitude imaging (definitions in fdwave.h) ----
+// the RTM dialect on the whole grid, one shot at a time
+static int check_exc_ctx(const fdw_ctx* c, const char* who)
+{
+    if (c->prm.dialect != FDW_DIALECT_RTM) return fail(FDW_ESTATE, "%s: excitation-amplitude imaging belongs to the RTM dialect", who);
+    if (!is_full_grid(c)) return fail(FDW_ESTATE, "%s: excitation-amplitude imaging needs a full-grid context (slab-decomposed shots are not covered)", who);
+    if (c->nbatch > 1) return fail(FDW_ESTATE, "%s: not inside a batch of shots", who);
+    return FDW_OK;
+}
+// a point source the maps' forward loop can inject: a cell the loop time-steps
+static int check_exc_source(const fdw_ctx* c, const char* who, int sx, int sz)
+{
+    if (sz < 0 || sz >= c->zlim) return fail(FDW_EINVAL, "%s: source depth %d outside the time-stepped columns [0,%d)", who, sz, c->zlim);
+    if (sx >= c->upd_x1) return fail(FDW_EINVAL, "%s: source row %d outside the time-stepped rows [0,%d)", who, sx, c->upd_x1);
+    return FDW_OK;
+}
+
+extern "C" int fdw_dev_excite_steps(fdw_ctx* c, float* const* d_buf, const float* d_v2, const float* d_srce, int sx, int sz, float* d_amp, int* d_texc,
+                                    int it0, int nsteps, int first_pp_twice, int* ip, int* ipp, void* stream)
+{
+    if (!c) return fail(FDW_EINVAL, "NULL argument");
+    FDW_TRY(check_exc_ctx(c, "fdw_dev_excite_steps"));
+    if (!d_buf || !d_buf[0] || !d_buf[1] || !d_buf[2] || !d_buf[3] || !d_v2 || !d_amp || !d_texc || !ip || !ipp) return fail(FDW_EINVAL, "NULL argument");
+    if (it0 < 0) return fail(FDW_EINVAL, "it0=%d", it0);
+    if (d_srce && sx >= 0) FDW_TRY(check_exc_source(c, "fdw_dev_excite_steps", sx, sz));
+    const ExcLoop xl{d_amp, d_texc, 0, false};
+    return steps_loop(c, d_buf, d_v2, d_srce, sx, sz, 0, nullptr, it0, nsteps, first_pp_twice, ip, ipp, pick_stream(c, stream), nullptr, false, false, &xl);
+}
+
+extern "C" int fdw_dev_line_pick_steps(fdw_ctx* c, float* const* d_buf, const float* d_v2, const float* d_wav, int sz, const int* d_texc, int top,
+                                       float* d_exc, int it0, int nsteps, int first_pp_twice, int* ip, int* ipp, void* stream)
+{
+    if (!c) return fail(FDW_EINVAL, "NULL argument");
+    FDW_TRY(check_exc_ctx(c, "fdw_dev_line_pick_steps"));
+    if (!d_buf || !d_buf[0] || !d_buf[1] || !d_buf[2] || !d_buf[3] || !d_v2 || !d_wav || !d_texc || !d_exc || !ip || !ipp) return fail(FDW_EINVAL, "NULL argument");
+    if (it0 < 0) return fail(FDW_EINVAL, "it0=%d", it0);
+    FDW_TRY(check_line_args(c, "fdw_dev_line_pick_steps", sz, 0, false, false));
+    const ExcLoop xl{d_exc, const_cast<int*>(d_texc), top, true};      // the pick only reads the map
+    return steps_loop(c, d_buf, d_v2, d_wav, -1, sz, 0, nullptr, it0, nsteps, first_pp_twice, ip, ipp, pick_stream(c, stream), nullptr, true, false, &xl);
 }
 
 // d_out[i] = d_a[i] - d_b[i] (fdw_gather_residual_kernel); d_out may be d_a
@@ -2630,6 +2743,72 @@ extern "C" int fdw_shot_resident_illum(fdw_ctx* c, int sx, int sz, int gz, const
     FDW_TRY(check_illum_ctx(c, "fdw_shot_resident_illum"));
     if (!c->v2_resident) return fail(FDW_ESTATE, "no resident squared model: call fdw_dev_extendvel_linear first");
     return shot_impl(c, nullptr, sx, sz, gz, srce, d_obs, imloc, P, PP, illum);
+}
+
+// ---- the excitation-amplitude shot (definitions in fdwave.h) ----
+extern "C" int fdw_image_excitation(const float* exc, const float* amp, size_t n, float eps, float* img)
+{
+    if (!(eps >= 0.0f) || std::isinf(eps)) return fail(FDW_EINVAL, "fdw_image_excitation: eps must be finite and >= 0");
+    if (n > 0 && (!exc || !amp || !img)) return fail(FDW_EINVAL, "NULL argument");
+    float m = 0.0f;
+    for (size_t i = 0; i < n; i++) {
+        const float a = fabsf(amp[i]);
+        if (a > m) m = a;
+    }
+    const float s = eps * m;
+    for (size_t i = 0; i < n; i++)
+        if (fabsf(amp[i]) > s) img[i] = img[i] + exc[i] / amp[i];
+    return FDW_OK;
+}
+
+extern "C" int fdw_shot_excitation(fdw_ctx* c, const float* v2, int sx, int sz, int gz, const float* srce, const float* d_obs, float eps, float* imloc,
+                                   float* exc, float* amp, int* texc, float* P, float* PP)
+{
+    if (!c) return fail(FDW_EINVAL, "NULL argument");
+    FDW_TRY(check_exc_ctx(c, "fdw_shot_excitation"));
+    if (!srce || !d_obs || (!imloc && !exc && !amp && !texc)) return fail(FDW_EINVAL, "NULL argument");
+    if (!(eps >= 0.0f) || std::isinf(eps)) return fail(FDW_EINVAL, "fdw_shot_excitation: eps must be finite and >= 0");
+    if (!v2 && !c->v2_resident) return fail(FDW_ESTATE, "no resident squared model: call fdw_dev_extendvel_linear first");
+    if (sx < 0) return fail(FDW_EINVAL, "fdw_shot_excitation: source row %d", sx);
+    FDW_TRY(check_exc_source(c, "fdw_shot_excitation", sx, sz));
+    FDW_TRY(check_line_args(c, "fdw_shot_excitation", gz, 0, false, false));
+    if (c->nx <= 0 || c->nz <= 0) return fail(FDW_EINVAL, "no interior to image");
+    FDW_RANGE("fdw: excitation-amplitude shot (uploads, forward + maps, receiver loop + pick, downloads)");
+    HIP_TRY(hipSetDevice(c->device));
+    int rc;
+    const int nt = c->prm.nt, nx = c->nx;
+    const size_t fe = field_elems(c), ni = (size_t)nx * c->nz;
+    if ((rc = ensure_work_buffers(c, 8, false)) || (rc = alloc_zero(&c->d_amp, fe)) || (rc = alloc_zero((float**)&c->d_texc, fe)) ||
+        (rc = alloc_zero(&c->d_exc, fe)) || (rc = ensure_cap(&c->d_wav, &c->wav_cap, (size_t)nx * nt)))
+        return rc;
+    // row k of the pick loop's line gather: d_obs[.][nt-1-k]
+    std::vector<float> wav((size_t)nx * nt);
+    for (int k = 0; k < nt; k++)
+        for (int ix = 0; ix < nx; ix++) wav[(size_t)k * nx + ix] = d_obs[(size_t)ix * nt + (nt - 1 - k)];
+    std::vector<float> h_exc, h_amp;      // the image needs both, whether the caller wants them or not
+    if (imloc && !exc) { h_exc.resize(ni); exc = h_exc.data(); }
+    if (imloc && !amp) { h_amp.resize(ni); amp = h_amp.data(); }
+    float* const maps[3] = {c->d_amp, (float*)c->d_texc, c->d_exc};
+    if ((rc = zero_fields(c, c->fld, 2)) || (rc = zero_fields(c, maps, 3))) return rc;
+    if (v2) c->v2_resident = false;
+    if ((v2 && (rc = upload_rows(c, c->d_v2, v2, c->stream))) || (rc = upload_source(c, srce, nt))) return rc;
+    if (nt > 0) HIP_TRY(hipMemcpyAsync(c->d_wav, wav.data(), wav.size() * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    int ip = 0, ipp = 1;
+    const ExcLoop fwd{c->d_amp, c->d_texc, 0, false};
+    if ((rc = steps_loop(c, c->fld, c->d_v2, c->d_srce, sx, sz, 0, nullptr, 0, nt, 0, &ip, &ipp, c->stream, nullptr, false, false, &fwd))) return rc;
+    if (nt > 0 && (rc = fdw_dev_taper_finalize(c, c->fld[ip], c->stream))) return rc;      // as fdw_shot's forward loop leaves d_p
+    if (P && (rc = download_rows(c, P, c->fld[ip], c->stream))) return rc;
+    if (PP && (rc = download_rows(c, PP, c->fld[ipp], c->stream))) return rc;
+    if ((rc = zero_fields(c, c->fld + 4, 2))) return rc;
+    int rp = 0, rpp = 1;
+    const ExcLoop bwd{c->d_exc, c->d_texc, nt, true};
+    if ((rc = steps_loop(c, c->fld + 4, c->d_v2, c->d_wav, -1, gz, 0, nullptr, 0, nt, 0, &rp, &rpp, c->stream, nullptr, true, false, &bwd))) return rc;
+    if (exc && (rc = image_to_host(c, exc, c->d_exc))) return rc;
+    if (amp && (rc = image_to_host(c, amp, c->d_amp))) return rc;
+    if (texc && (rc = image_to_host(c, (float*)texc, (const float*)c->d_texc))) return rc;
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (imloc) return fdw_image_excitation(exc, amp, ni, eps, imloc);
+    return FDW_OK;
 }
 
 // ---- residual migration (definitions in fdwave.h) ----

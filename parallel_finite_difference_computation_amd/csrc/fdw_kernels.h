@@ -22,6 +22,8 @@ enum {
     FDW_MODE_FWD_LINE_REC = 14,   // ... + the trace samples, written after the injection
     FDW_MODE_FWD_LINE_ILLUM = 15, // ... + the source illumination, accumulated after the injection
     FDW_MODE_FWD_LINE_REC_ILLUM = 16, // ... + both in one launch (fdw_dev_line_record_illum_steps, fdw_shot_line_residual with an accumulator)
+    FDW_MODE_FWD_EXC = 17,       // launchers only: FWD + the excitation maps (fdw_dev_excite_steps): amp travels in `img`, the time map in `texc`, exc_key = it + 1
+    FDW_MODE_FWD_LINE_PICK = 18, // launchers only: FWD_LINE + the excitation pick (fdw_dev_line_pick_steps): exc travels in `img`, exc_key = top - it
     FDW_MODE_DD_RECV = 6 // its receiver pass (rtm_main.cpp:197-220) + img += stored source field * CURRENT receiver field (rtm_main.cpp:224-230)
 };
 
@@ -68,6 +70,9 @@ struct StepArgs {
     // (v2 + b * v2_bstride: one model per shot in the RTM loop, one for all in the modelling loop; rec + b * rec_bstride)
     long long bstride, inj_bstride, v2_bstride, rec_bstride;
     int inj_dx, nbatch;
+    // FDW_MODE_FWD_EXC / FWD_LINE_PICK (one shot, no batch stride): the excitation-time map [nxl][pitch] and the level this launch writes / picks
+    int* texc;
+    int exc_key;
 };
 
 // Two-steps-per-pass kernel (temporal blocking, order 8, forward mode): see fdw_step2_kernel.
@@ -116,6 +121,9 @@ struct Step2Args {
     //   FDW_MODE_BACK4      both in one pass (fdw_back4_kernel): p / pp / out1 / out2 are the source field's, these the receiver field's
     const float *rp, *rpp;
     float *rout1, *rout2;
+    // pipeline kernel, FDW_MODE_FWD_EXC / FWD_LINE_PICK: the excitation-time map and the key of the pass's FIRST step (it + 1 / top - it); amp / exc in img
+    int* texc;
+    int exc_key;
 };
 hipError_t launch_step2(const Step2Args& a, int half_order, int mode, hipStream_t s);
 
@@ -154,6 +162,10 @@ hipError_t launch_taper_finalize(float* f, const float* taperz, const float* txf
                                  int tz_x1, hipStream_t s);
 // source illumination of the orders without a register-ring kernel: illum += f (*) f on rows [r0, r1), columns < z1 (fdw_illum_add_kernel)
 hipError_t launch_illum_add(const float* f, float* illum, int pitch, int r0, int r1, int z1, hipStream_t s);
+// excitation maps / pick of the orders without a register-ring kernel, on rows [r0, r1), columns < z1 of the field f the step just stored
+// (fdw_exc_select_kernel, fdw_exc_pick_kernel)
+hipError_t launch_exc_select(const float* f, float* amp, int* texc, int pitch, int r0, int r1, int z1, int key, hipStream_t s);
+hipError_t launch_exc_pick(const float* f, const int* texc, float* exc, int pitch, int r0, int r1, int z1, int key, hipStream_t s);
 hipError_t launch_selftest(const float* src, float* out, hipStream_t s);
 // one field [.][pitch] cropped to the cells (x0 + a dec, z0 + b dec), a < nxs, b < nzs, as one dense frame [nxs][nzs] (fdw_snapshot_kernel)
 hipError_t launch_snapshot(const float* f, float* frame, int pitch, int x0, int z0, int dec, int nxs, int nzs, hipStream_t s);

@@ -27,6 +27,12 @@ namespace fdw {
 //   REC     trace recording of the RTM dialect's forward loop: the new field at column rec_z of every receiver row (fdw_step_rec_kernel)
 //   ILL     source illumination of the forward loop: sv.img += new field (*) new field on the updated cells, product and sum rounded
 //           separately (fdw_step_illum_kernel); the row of the accumulator rides the image queue
+//   EXC     excitation-amplitude imaging (fdwave.h, "excitation amplitude"), the RTM dialect's forward loops, one shot (no batch):
+//           1  the excitation maps: where |new field| > |amp| strictly, amp = the new field (signed) and texc = a.exc_key (= it + 1);
+//              the amp row rides the image queue (a.img), the texc row a queue of its own (fdw_step_exc_kernel)
+//           2  the excitation pick: where texc == a.exc_key (= top - it), exc = the new field; texc is only read, the exc row (a.img) is
+//              stored back whole, unpicked words with the bits they came with (fdw_step_line_pick_kernel)
+//           Compares and selects only: texc travels as 32-bit words in float registers and meets no arithmetic.
 // block = 256 threads = 4 independent waves (no LDS, no barrier).
 //
 // ONE code path for every tile.  Every global load of the march is unconditional (addresses are
@@ -51,7 +57,8 @@ struct ShotView {
     float* rec;
 };
 
-template <int H, bool TAPER, int INJ, bool IMG, bool LAPONLY, int PF, bool DD = false, bool BACK = false, int NUM = 0, bool REC = false, bool ILL = false>
+template <int H, bool TAPER, int INJ, bool IMG, bool LAPONLY, int PF, bool DD = false, bool BACK = false, int NUM = 0, bool REC = false, bool ILL = false,
+          int EXC = 0>
 __device__ __forceinline__ void march(const StepArgs& a, const ShotView& sv, const int lane, const int zs, const int xa, const int xe)
 {
     // BACK: one whole backward iteration of fd_back (R:317-329) in a single pass: the source field is reconstructed in a second
@@ -137,6 +144,7 @@ __device__ __forceinline__ void march(const StepArgs& a, const ShotView& sv, con
     // ("virtual steps" -LOOK..-1) makes the two states agree, so no turn starts with a pipeline drain.
     f4 ring[R];
     f4 qhal[PF], qpp[PF], qv2[PF], qps[PF], qim[PF];
+    f4 qtx[EXC ? PF : 1];                                   // EXC: the texc row, as words
     f4 fring[BACK ? R : 1], fqhal[BACK ? PF : 1], fqpp[BACK ? PF : 1];      // the source field's ring and pointwise queues
     constexpr int NV = LOOK > PF ? LOOK : PF;
     static_for<2 * H>([&](auto K) {
@@ -164,6 +172,10 @@ __device__ __forceinline__ void march(const StepArgs& a, const ShotView& sv, con
                 qim[m] = load_plain(sv.img, row);
             }
             if constexpr (ILL) qim[m] = load_plain(sv.img, row);
+            if constexpr (EXC != 0) {
+                qim[m] = load_plain(sv.img, row);
+                qtx[m] = load_plain(reinterpret_cast<const float*>(a.texc), row);
+            }
             if constexpr (BACK) {
                 fqhal[m] = load_fhalo(row);
                 fqpp[m] = load_plain(sv.fpp, row);
@@ -287,6 +299,25 @@ __device__ __forceinline__ void march(const StepArgs& a, const ShotView& sv, con
                     for (int e = 0; e < 4; ++e) imr.v[e] = mupd[e] ? imr.v[e] : qim[Q].v[e];
                 }
             }
+            f4 txr;
+            if constexpr (EXC == 1) {
+                // the value compared and kept is the one stored below, source sample included and undamped; a NaN on either side compares
+                // false, so it never wins and is never replaced; cells outside the update extents keep both words
+                const float key = __int_as_float(a.exc_key);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const bool win = (__builtin_fabsf(res.v[e]) > __builtin_fabsf(qim[Q].v[e])) && (!zedge || mupd[e]);
+                    imr.v[e] = win ? res.v[e] : qim[Q].v[e];
+                    txr.v[e] = win ? key : qtx[Q].v[e];
+                }
+            }
+            if constexpr (EXC == 2) {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const bool pick = (__float_as_int(qtx[Q].v[e]) == a.exc_key) && (!zedge || mupd[e]);
+                    imr.v[e] = pick ? res.v[e] : qim[Q].v[e];
+                }
+            }
             f4 fres;
             if constexpr (BACK) {
                 // ---- the source field's own step on the same row: kernel_lap + kernel_time, no damping, no injection (R:317-318) ----
@@ -327,11 +358,15 @@ __device__ __forceinline__ void march(const StepArgs& a, const ShotView& sv, con
                 f4_store(sv.out + (size_t)r * pitch, voff, res);
                 if constexpr (IMG) f4_store(sv.img + (size_t)r * pitch, voff, imr);
                 if constexpr (ILL) f4_store(sv.img + (size_t)r * pitch, voff, imr);
+                if constexpr (EXC != 0) f4_store(sv.img + (size_t)r * pitch, voff, imr);
+                if constexpr (EXC == 1) f4_store(reinterpret_cast<float*>(a.texc) + (size_t)r * pitch, voff, txr);
                 if constexpr (BACK) f4_store(sv.fpp + (size_t)r * pitch, voff, fres);
             } else if (act) {
                 f4_store(sv.out + (size_t)r * pitch, voff, res);
                 if constexpr (IMG) f4_store(sv.img + (size_t)r * pitch, voff, imr);
                 if constexpr (ILL) f4_store(sv.img + (size_t)r * pitch, voff, imr);
+                if constexpr (EXC != 0) f4_store(sv.img + (size_t)r * pitch, voff, imr);
+                if constexpr (EXC == 1) f4_store(reinterpret_cast<float*>(a.texc) + (size_t)r * pitch, voff, txr);
                 if constexpr (BACK) f4_store(sv.fpp + (size_t)r * pitch, voff, fres);
             }
             if constexpr (REC) f1_store_arr(array_rsrc(sv.rec, (unsigned)a.rec_n * 4u), rec_offset(rec_lane, r, a.rec_x0, a.rec_n), f4_pick(res, a.rec_z & 3));
@@ -350,6 +385,10 @@ __device__ __forceinline__ void march(const StepArgs& a, const ShotView& sv, con
                     qim[Q] = load_plain(sv.img, nr);
                 }
                 if constexpr (ILL) qim[Q] = load_plain(sv.img, nr);
+                if constexpr (EXC != 0) {
+                    qim[Q] = load_plain(sv.img, nr);
+                    qtx[Q] = load_plain(reinterpret_cast<const float*>(a.texc), nr);
+                }
                 if constexpr (BACK) {
                     fqhal[Q] = load_fhalo(nr);
                     fqpp[Q] = load_plain(sv.fpp, nr);
@@ -548,6 +587,63 @@ __global__ __launch_bounds__(256) void fdw_step_line_rec_illum_kernel(const Step
     march<H, true, 2, false, false, PF, false, false, NUM, true, true>(a, sv, lane, zs, xa, xe);
 }
 
+// the forward step (FDW_MODE_FWD) that also keeps the excitation maps (FDW_MODE_FWD_EXC, fdw_dev_excite_steps): a.img is amp, a.texc the time
+// map, both read and written once per cell, +16 B/point/step.  One shot only (the callers refuse a batch: a.texc carries no shot stride).
+// Its own copy of the tile placement, like fdw_step_rec_kernel's.
+template <int H, int PF, int NUM>
+__global__ __launch_bounds__(256) void fdw_step_exc_kernel(const StepArgs a)
+{
+    const int shot = blockIdx.y;
+    const long long o = shot * a.bstride;
+    const ShotView sv{a.p + o, a.pp + o, (a.out ? a.out : a.pp) + o, a.v2 + shot * a.v2_bstride, a.psrc + o, a.fpp + o, a.img + o, a.inj + shot * a.inj_bstride,
+                      a.inj_x + shot * a.inj_dx, a.rec + shot * a.rec_bstride};
+    const int lane = threadIdx.x & 63;
+    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+
+    const int bid = blockIdx.x;
+    const int L = (bid & 7) * a.nper + (bid >> 3);
+    if (L >= a.nblk) return;
+    const int zb = L % a.nzblk;
+    const int xb = L / a.nzblk;
+    const int wz = a.wz;
+    const int strip = zb * wz + (w & (wz - 1));
+    const int chunk = xb * (4 / wz) + (w / wz);
+    const int zs = strip * 256;
+    if (zs >= a.pitch) return;
+    const int xa = a.r0 + chunk * a.xchunk;
+    const int xe = min(xa + a.xchunk, a.r1);
+    if (xa >= xe) return;
+    march<H, true, 1, false, false, PF, false, false, NUM, false, false, 1>(a, sv, lane, zs, xa, xe);
+}
+
+// the line-source step that also takes the excitation pick (FDW_MODE_FWD_LINE_PICK, fdw_dev_line_pick_steps): fdw_step_line_kernel's step, then
+// exc = the new field, line sample included, where texc equals a.exc_key.  a.img is exc.  Its own copy of the tile placement.
+template <int H, int PF, int NUM>
+__global__ __launch_bounds__(256) void fdw_step_line_pick_kernel(const StepArgs a)
+{
+    const int shot = blockIdx.y;
+    const long long o = shot * a.bstride;
+    const ShotView sv{a.p + o, a.pp + o, (a.out ? a.out : a.pp) + o, a.v2 + shot * a.v2_bstride, a.psrc + o, a.fpp + o, a.img + o, a.inj + shot * a.inj_bstride,
+                      a.inj_x + shot * a.inj_dx, a.rec + shot * a.rec_bstride};
+    const int lane = threadIdx.x & 63;
+    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+
+    const int bid = blockIdx.x;
+    const int L = (bid & 7) * a.nper + (bid >> 3);
+    if (L >= a.nblk) return;
+    const int zb = L % a.nzblk;
+    const int xb = L / a.nzblk;
+    const int wz = a.wz;
+    const int strip = zb * wz + (w & (wz - 1));
+    const int chunk = xb * (4 / wz) + (w / wz);
+    const int zs = strip * 256;
+    if (zs >= a.pitch) return;
+    const int xa = a.r0 + chunk * a.xchunk;
+    const int xe = min(xa + a.xchunk, a.r1);
+    if (xa >= xe) return;
+    march<H, true, 2, false, false, PF, false, false, NUM, false, false, 2>(a, sv, lane, zs, xa, xe);
+}
+
 #if FDW_TU == 0
 // ------------------------------------------------------------------------------------------------
 // generic-order kernel: any even order up to FDW_MAX_ORDER, one thread per point, every tap from
@@ -630,6 +726,29 @@ __global__ __launch_bounds__(256) void fdw_illum_add_kernel(const float* f, floa
     const size_t k = (size_t)(r0 + blockIdx.y) * pitch + z;
     const float u = f[k];
     illum[k] = illum[k] + u * u;
+}
+
+// The excitation maps behind the generic-order kernel: f is the field the step just stored; where |f| > |amp| strictly, amp = f and
+// texc = key (= it + 1), on the cells the step updated.  A NaN on either side compares false.
+__global__ __launch_bounds__(256) void fdw_exc_select_kernel(const float* f, float* amp, int* texc, int pitch, int r0, int z1, int key)
+{
+    const int z = blockIdx.x * 256 + threadIdx.x;
+    if (z >= z1) return;
+    const size_t k = (size_t)(r0 + blockIdx.y) * pitch + z;
+    const float u = f[k];
+    if (__builtin_fabsf(u) > __builtin_fabsf(amp[k])) {
+        amp[k] = u;
+        texc[k] = key;
+    }
+}
+
+// The excitation pick behind the generic-order kernel: exc = f where texc == key (= top - it), on the cells the step updated.
+__global__ __launch_bounds__(256) void fdw_exc_pick_kernel(const float* f, const int* texc, float* exc, int pitch, int r0, int z1, int key)
+{
+    const int z = blockIdx.x * 256 + threadIdx.x;
+    if (z >= z1) return;
+    const size_t k = (size_t)(r0 + blockIdx.y) * pitch + z;
+    if (texc[k] == key) reinterpret_cast<unsigned*>(exc)[k] = reinterpret_cast<const unsigned*>(f)[k];
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -750,6 +869,8 @@ static hipError_t launch_fast_hp(const StepArgs& a, int mode, hipStream_t s)
     case FDW_MODE_FWD_LINE_REC: hipLaunchKernelGGL((fdw_step_line_kernel<H, PF, true, false, 0>), grid, block, 0, s, a); break;
     case FDW_MODE_FWD_LINE_ILLUM: hipLaunchKernelGGL((fdw_step_line_kernel<H, PF, false, true, 0>), grid, block, 0, s, a); break;
     case FDW_MODE_FWD_LINE_REC_ILLUM: hipLaunchKernelGGL((fdw_step_line_rec_illum_kernel<H, PF, 0>), grid, block, 0, s, a); break;
+    case FDW_MODE_FWD_EXC: hipLaunchKernelGGL((fdw_step_exc_kernel<H, PF, 0>), grid, block, 0, s, a); break;
+    case FDW_MODE_FWD_LINE_PICK: hipLaunchKernelGGL((fdw_step_line_pick_kernel<H, PF, 0>), grid, block, 0, s, a); break;
     default: return hipErrorInvalidValue;
     }
     return hipGetLastError();
@@ -844,6 +965,8 @@ static hipError_t launch_fastnum_h(const StepArgs& a, int mode, hipStream_t s)
     case FDW_MODE_FWD_LINE_REC: hipLaunchKernelGGL((fdw_step_line_kernel<H, 2, true, false, 1>), grid, block, 0, s, a); break;
     case FDW_MODE_FWD_LINE_ILLUM: hipLaunchKernelGGL((fdw_step_line_kernel<H, 2, false, true, 1>), grid, block, 0, s, a); break;
     case FDW_MODE_FWD_LINE_REC_ILLUM: hipLaunchKernelGGL((fdw_step_line_rec_illum_kernel<H, 2, 1>), grid, block, 0, s, a); break;
+    case FDW_MODE_FWD_EXC: hipLaunchKernelGGL((fdw_step_exc_kernel<H, 2, 1>), grid, block, 0, s, a); break;
+    case FDW_MODE_FWD_LINE_PICK: hipLaunchKernelGGL((fdw_step_line_pick_kernel<H, 2, 1>), grid, block, 0, s, a); break;
     default: return hipErrorInvalidValue;
     }
     return hipGetLastError();
@@ -881,6 +1004,22 @@ hipError_t launch_illum_add(const float* f, float* illum, int pitch, int r0, int
     const int zc = z1 < pitch ? z1 : pitch;
     if (r1 <= r0 || zc <= 0) return hipSuccess;
     hipLaunchKernelGGL(fdw_illum_add_kernel, dim3((zc + 255) / 256, r1 - r0), dim3(256), 0, s, f, illum, pitch, r0, zc);
+    return hipGetLastError();
+}
+
+hipError_t launch_exc_select(const float* f, float* amp, int* texc, int pitch, int r0, int r1, int z1, int key, hipStream_t s)
+{
+    const int zc = z1 < pitch ? z1 : pitch;
+    if (r1 <= r0 || zc <= 0) return hipSuccess;
+    hipLaunchKernelGGL(fdw_exc_select_kernel, dim3((zc + 255) / 256, r1 - r0), dim3(256), 0, s, f, amp, texc, pitch, r0, zc, key);
+    return hipGetLastError();
+}
+
+hipError_t launch_exc_pick(const float* f, const int* texc, float* exc, int pitch, int r0, int r1, int z1, int key, hipStream_t s)
+{
+    const int zc = z1 < pitch ? z1 : pitch;
+    if (r1 <= r0 || zc <= 0) return hipSuccess;
+    hipLaunchKernelGGL(fdw_exc_pick_kernel, dim3((zc + 255) / 256, r1 - r0), dim3(256), 0, s, f, texc, exc, pitch, r0, zc, key);
     return hipGetLastError();
 }
 

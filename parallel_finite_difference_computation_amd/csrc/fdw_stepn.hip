@@ -53,13 +53,25 @@ __device__ __forceinline__ int pipe_fifo_slot(int m)
 // ILL: forward loop with source illumination (FDW_MODE_FWD_ILLUM): a.img += u^{n+k+1} (*) u^{n+k+1} for k = 0 .. NS-1 in that order on the updated
 // cells.  The accumulator row travels like the image row of BK 2: in at wave 0 from memory, through the imf FIFO from wave to wave, each wave
 // adding the square of the row it has just formed (raw, source sample included), out from the last wave -- owned lanes, the tile's own rows
-template <int H, int NS, bool TAPER, int INJ, int PF, bool DD = false, int BK = 0, bool LEAN = false, int WK = 0, int NUM = 0, bool REC = false, bool ILL = false>
+// EXC: excitation-amplitude imaging (fdwave.h), the RTM dialect's forward passes.  Two arrays per epilogue, ONE f4 row in the imf FIFO: beside it
+// travels a dword per lane and row (tgf, 4 KiB) with a 4-bit tag per cell.
+//   1  the maps (FDW_MODE_FWD_EXC): the amp row (a.img) goes in at wave 0, wave k keeps u^{n+k+1} where it beats the row strictly in magnitude and
+//      tags the cell k + 1, the last wave stores amp and turns the tags into a.exc_key + tag - 1 (= it + 1 of the winning level) over the texc row,
+//      which it alone loads (its own rows, owned lanes, PF steps ahead); untagged cells keep their word
+//   2  the pick (FDW_MODE_FWD_LINE_PICK): wave 0 loads the texc row and forms the tags once, tag d + 1 where texc == a.exc_key - d (= top - it
+//      of level d) for d < NS; the exc row (a.img) goes in at wave 0, wave k puts u^{n+k+1} (sample included) into the cells tagged k + 1, the last
+//      wave stores it; no other wave loads anything
+// Compares, selects and integer adds only: texc meets no float arithmetic.  Masks as ILL: none in the lean body, the update masks in the full one.
+template <int H, int NS, bool TAPER, int INJ, int PF, bool DD = false, int BK = 0, bool LEAN = false, int WK = 0, int NUM = 0, bool REC = false, bool ILL = false,
+          int EXC = 0>
 __device__ __forceinline__ void marchn(const Step2Args& a, const int lane, const int k, const int cs, const int xa, const int xe,
-                                       f4 (*link)[2][2][64], f4 (*fifo)[64], f4 (*imf)[64] = nullptr, f4 (*linkx)[2][2][64] = nullptr)
+                                       f4 (*link)[2][2][64], f4 (*fifo)[64], f4 (*imf)[64] = nullptr, f4 (*linkx)[2][2][64] = nullptr,
+                                       unsigned (*tgf)[64] = nullptr)
 {
     static_assert(!LEAN || (!TAPER && INJ == 0), "the lean body has no damping, no injection (and records no trace)");
     constexpr bool IMG = (BK == 2 || BK == 4);
-    constexpr bool ACC = IMG || ILL;                          // a row of an accumulator (image, illumination) rides along
+    constexpr bool ACC = IMG || ILL || (EXC != 0);            // a row of an accumulator (image, illumination, amp, exc) rides along
+    static_assert(EXC == 0 || (BK == 0 && !DD && !ILL && !REC), "the excitation epilogues belong to the RTM dialect's plain forward passes");
     static_assert(!ILL || (BK == 0 && !DD), "illumination belongs to the RTM dialect's forward pass");
     constexpr int D = (BK == 4) ? 1 : 0;                      // this role runs D march steps behind
     constexpr int DL = (BK >= 3) ? 1 : 0;                     // ... so both roles of the fused kernel loop one step longer
@@ -147,6 +159,10 @@ __device__ __forceinline__ void marchn(const Step2Args& a, const int lane, const
     bool zim[4];
 #pragma unroll
     for (int e = 0; e < 4; ++e) zim[e] = (z0 + e >= 0) && (z0 + e < a.img_z1);
+    // EXC: the time map.  1: read and written by the last wave; 2: read by wave 0
+    const __amdgpu_buffer_rsrc_t rs_tx = array_rsrc(EXC != 0 ? reinterpret_cast<const float*>(a.texc) : gp, arr_bytes);
+    const unsigned txoff = EXC == 1 ? ((own && k == NS - 1) ? voff : kLaneOff) : imoff;
+    f4 qtx[EXC != 0 ? PF : 1];
     constexpr int NV = LOOK > PF ? LOOK : PF;
     static_for<2 * H>([&](auto K) {
         constexpr int kk = decltype(K)::value;
@@ -163,6 +179,8 @@ __device__ __forceinline__ void marchn(const Step2Args& a, const int lane, const
             if constexpr (BK == 2) qlv[mm] = f4_load_arr(rs_lev, ioff, rowoff(rk + mm), true);
             if constexpr (IMG) qim[mm] = f4_load_arr(rs_img, imoff, rowoff(rk + mm), true);
             if constexpr (ILL && WK != 2) qim[mm] = f4_load_arr(rs_img, imoff, rowoff(rk + mm), true);
+            if constexpr (EXC != 0 && WK != 2) qim[mm] = f4_load_arr(rs_img, imoff, rowoff(rk + mm), true);
+            if constexpr ((EXC == 1 && WK != 1) || (EXC == 2 && WK != 2)) qtx[mm] = f4_load_arr(rs_tx, txoff, rowoff(rk + mm), true);
         }
         __builtin_amdgcn_sched_barrier(0);
     });
@@ -198,6 +216,8 @@ __device__ __forceinline__ void marchn(const Step2Args& a, const int lane, const
         f4 u;
         float im0, im1, im2, im3;                               // the image row (BK 2, 4), as scalars: defined on every path without an instruction
         if constexpr (ACC) asm volatile("" : "=v"(im0), "=v"(im1), "=v"(im2), "=v"(im3));
+        unsigned tgv;                                           // EXC: the row's tags
+        if constexpr (EXC != 0) asm volatile("" : "=v"(tgv));
         if (act) {
         // pp and v2 of this row live in the look-ahead queue's registers: wave 0 finds them there (loaded PF steps ago), the other waves
         // read theirs from LDS into the same registers (their own look-ahead loads are switched off and return nothing they need)
@@ -290,6 +310,42 @@ __device__ __forceinline__ void marchn(const Step2Args& a, const int lane, const
             if (k < NS - 1) imf[r & 15][lane] = il;
             im0 = il.v[0]; im1 = il.v[1]; im2 = il.v[2]; im3 = il.v[3];
         }
+        if constexpr (EXC == 1) {
+            // the row compared and kept is the one stored and handed on (raw, source sample included); a NaN on either side compares false
+            f4 am;
+            unsigned tg;
+            if (first) { am = qim[Q]; tg = 0u; }
+            else { am = imf[r & 15][lane]; tg = tgf[r & 15][lane]; }
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const bool win = (__builtin_fabsf(u.v[e]) > __builtin_fabsf(am.v[e])) && (LEAN || (rowupd && mupd[e]));
+                am.v[e] = win ? u.v[e] : am.v[e];
+                tg = win ? ((tg & ~(15u << (4 * e))) | ((unsigned)(k + 1) << (4 * e))) : tg;
+            }
+            if (k < NS - 1) { imf[r & 15][lane] = am; tgf[r & 15][lane] = tg; }
+            im0 = am.v[0]; im1 = am.v[1]; im2 = am.v[2]; im3 = am.v[3];
+            tgv = tg;
+        }
+        if constexpr (EXC == 2) {
+            f4 ex;
+            unsigned tg;
+            if (first) {
+                ex = qim[Q];
+                tg = 0u;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const unsigned d = (unsigned)a.exc_key - (unsigned)__float_as_int(qtx[Q].v[e]);      // level d of the pass picks this cell
+                    tg |= (d < (unsigned)NS ? d + 1u : 0u) << (4 * e);
+                }
+            } else { ex = imf[r & 15][lane]; tg = tgf[r & 15][lane]; }
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const bool pick = (((tg >> (4 * e)) & 15u) == (unsigned)(k + 1)) && (LEAN || (rowupd && mupd[e]));
+                ex.v[e] = pick ? u.v[e] : ex.v[e];
+            }
+            if (k < NS - 1) { imf[r & 15][lane] = ex; tgf[r & 15][lane] = tg; }
+            im0 = ex.v[0]; im1 = ex.v[1]; im2 = ex.v[2]; im3 = ex.v[3];
+        }
         if constexpr (INJ == 3) {
             if (inj_here && r >= a.inj_x - 3 && r <= a.inj_x + 3) {
                 const int dxa = r > a.inj_x ? r - a.inj_x : a.inj_x - r;
@@ -326,6 +382,15 @@ __device__ __forceinline__ void marchn(const Step2Args& a, const int lane, const
             f4 im;
             im.v[0] = im0; im.v[1] = im1; im.v[2] = im2; im.v[3] = im3;
             f4_store_arr(rs_img, sim, rowoff(r), im);
+            if constexpr (EXC == 1 && WK != 1) {      // the time map of the last wave's row: the winning level's it + 1 where a level of this pass won
+                f4 tx;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const unsigned w = (tgv >> (4 * e)) & 15u;
+                    tx.v[e] = w ? __int_as_float(a.exc_key + (int)w - 1) : qtx[Q].v[e];
+                }
+                f4_store_arr(rs_tx, sim, rowoff(r), tx);
+            }
         }
         // ---- look-ahead loads of wave 0 into the slots this step freed ----
         if constexpr (WK != 2) ring[U] = load_p(b0 + m + R);
@@ -334,6 +399,8 @@ __device__ __forceinline__ void marchn(const Step2Args& a, const int lane, const
         if constexpr (BK == 2) qlv[Q] = f4_load_arr(rs_lev, ioff, rowoff(r + PF), true);
         if constexpr (IMG) qim[Q] = f4_load_arr(rs_img, imoff, rowoff(r + PF), true);
         if constexpr (ILL && WK != 2) qim[Q] = f4_load_arr(rs_img, imoff, rowoff(r + PF), true);
+        if constexpr (EXC != 0 && WK != 2) qim[Q] = f4_load_arr(rs_img, imoff, rowoff(r + PF), true);
+        if constexpr ((EXC == 1 && WK != 1) || (EXC == 2 && WK != 2)) qtx[Q] = f4_load_arr(rs_tx, txoff, rowoff(r + PF), true);
         __syncthreads();
     };
 
@@ -564,6 +631,71 @@ __global__ __launch_bounds__(64 * kPipeSteps, 3) void fdw_stepn_line_rec_illum_k
     else marchn<H, NS, true, 2, PF, false, 0, false, 0, NUM, true, true>(a, lane, k, cs, xa, xe, link, fifo, ilf);
 }
 
+// FDW_MODE_FWD_EXC: the forward pass that also keeps the excitation maps of its kPipeSteps steps (a.img = amp, a.texc; marchn, EXC 1).  Every
+// tile carries the amp row through the 16-slot LDS FIFO as fdw_stepn_illum_kernel carries its accumulator, and beside it a dword of tags per
+// lane and row: 16 + 16 + 16 + 4 = 52 KiB of LDS, three workgroups per CU (156 of the CU's 160 KiB).  Lean tiles compare without masks, the
+// tiles on the frame, the damped strip or the source with the update masks of the full body.  Its own tile placement (see fdw_stepn_rec_kernel).
+template <int NUM>
+__global__ __launch_bounds__(64 * kPipeSteps, 3) void fdw_stepn_exc_kernel(const Step2Args a)
+{
+    constexpr int H = 4, NS = kPipeSteps, PF = kPipePF;
+    const int lane = threadIdx.x & 63;
+    const int k = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int bid = blockIdx.x;
+    const int L = (bid & 7) * a.nper + (bid >> 3);
+    if (L >= a.nblk) return;
+    const int zb = L % a.nstrip;
+    const int xb = L / a.nstrip;
+    const bool second = xb >= a.chunks_a;
+    const int xa = second ? a.r0b + (xb - a.chunks_a) * a.xchunk : a.r0 + xb * a.xchunk;
+    const int xe = min(xa + a.xchunk, second ? a.r1b : a.r1);
+    if (xa >= xe) return;
+    __shared__ f4 link[NS][2][2][64];
+    __shared__ f4 fifo[pipe_fifo_rows(NS, H)][64];
+    __shared__ f4 amf[16][64];                             // amp rows on their way from wave to wave (3 (H + 1) = 15 steps under way)
+    __shared__ unsigned tgf[16][64];                       // ... and their tags
+    const int cs = zb * (64 - 2 * NS) - NS;
+    if (pipe_lean<H, NS, true, 1>(a, cs, xa, xe)) {
+        if (k == 0) marchn<H, NS, false, 0, PF, false, 0, true, 1, NUM, false, false, 1>(a, lane, k, cs, xa, xe, link, fifo, amf, nullptr, tgf);
+        else marchn<H, NS, false, 0, PF, false, 0, true, 2, NUM, false, false, 1>(a, lane, k, cs, xa, xe, link, fifo, amf, nullptr, tgf);
+    }
+    // the full body too is compiled once for wave 0 and once for the other waves, as the plain forward kernel's: with one body for all four waves
+    // the compiler keeps the amp look-ahead queue in scratch memory
+    else if (k == 0) marchn<H, NS, true, 1, PF, false, 0, false, 1, NUM, false, false, 1>(a, lane, k, cs, xa, xe, link, fifo, amf, nullptr, tgf);
+    else marchn<H, NS, true, 1, PF, false, 0, false, 2, NUM, false, false, 1>(a, lane, k, cs, xa, xe, link, fifo, amf, nullptr, tgf);
+}
+
+// FDW_MODE_FWD_LINE_PICK: the line-source pass that also takes the excitation pick of its kPipeSteps steps (a.img = exc, a.texc read only;
+// marchn, EXC 2): fdw_stepn_line_kernel's tiles (full body in the strip that holds the line, on the frame and in the damped strip, lean
+// elsewhere), every tile carrying the exc row and the tags wave 0 formed.  52 KiB of LDS, three workgroups per CU.  Its own tile placement.
+template <int NUM>
+__global__ __launch_bounds__(64 * kPipeSteps, 3) void fdw_stepn_line_pick_kernel(const Step2Args a)
+{
+    constexpr int H = 4, NS = kPipeSteps, PF = kPipePF;
+    const int lane = threadIdx.x & 63;
+    const int k = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int bid = blockIdx.x;
+    const int L = (bid & 7) * a.nper + (bid >> 3);
+    if (L >= a.nblk) return;
+    const int zb = L % a.nstrip;
+    const int xb = L / a.nstrip;
+    const bool second = xb >= a.chunks_a;
+    const int xa = second ? a.r0b + (xb - a.chunks_a) * a.xchunk : a.r0 + xb * a.xchunk;
+    const int xe = min(xa + a.xchunk, second ? a.r1b : a.r1);
+    if (xa >= xe) return;
+    __shared__ f4 link[NS][2][2][64];
+    __shared__ f4 fifo[pipe_fifo_rows(NS, H)][64];
+    __shared__ f4 exf[16][64];
+    __shared__ unsigned tgf[16][64];
+    const int cs = zb * (64 - 2 * NS) - NS;
+    if (pipe_lean<H, NS, true, 2>(a, cs, xa, xe)) {
+        if (k == 0) marchn<H, NS, false, 0, PF, false, 0, true, 1, NUM, false, false, 2>(a, lane, k, cs, xa, xe, link, fifo, exf, nullptr, tgf);
+        else marchn<H, NS, false, 0, PF, false, 0, true, 2, NUM, false, false, 2>(a, lane, k, cs, xa, xe, link, fifo, exf, nullptr, tgf);
+    }
+    else if (k == 0) marchn<H, NS, true, 2, PF, false, 0, false, 1, NUM, false, false, 2>(a, lane, k, cs, xa, xe, link, fifo, exf, nullptr, tgf);
+    else marchn<H, NS, true, 2, PF, false, 0, false, 2, NUM, false, false, 2>(a, lane, k, cs, xa, xe, link, fifo, exf, nullptr, tgf);
+}
+
 // Four iterations of the backward loop in ONE pass: a workgroup of eight waves, waves 0-3 the pipeline of the source field (role 3), waves 4-7
 // the pipeline of the receiver field one march step behind (role 4).  The source-field levels never leave the chip: the receiver wave of
 // level k reads F_{it+k}(row) from the link buffer the source-field wave k wrote it to for its own successor.  6 fields in + 5 out per
@@ -621,6 +753,8 @@ hipError_t launch_stepn(const Step2Args& a, int h, int mode, hipStream_t s)
         case FDW_MODE_FWD_LINE_REC: hipLaunchKernelGGL((fdw_stepn_line_kernel<true, false, 1>), grid, block, 0, s, a); break;
         case FDW_MODE_FWD_LINE_ILLUM: hipLaunchKernelGGL((fdw_stepn_line_kernel<false, true, 1>), grid, block, 0, s, a); break;
         case FDW_MODE_FWD_LINE_REC_ILLUM: hipLaunchKernelGGL((fdw_stepn_line_rec_illum_kernel<1>), grid, block, 0, s, a); break;
+        case FDW_MODE_FWD_EXC: hipLaunchKernelGGL((fdw_stepn_exc_kernel<1>), grid, block, 0, s, a); break;
+        case FDW_MODE_FWD_LINE_PICK: hipLaunchKernelGGL((fdw_stepn_line_pick_kernel<1>), grid, block, 0, s, a); break;
         case FDW_MODE_PLAIN: hipLaunchKernelGGL((fdw_stepn_kernel<4, kPipeSteps, false, 0, kPipePF, false, 0, 1>), grid, block, 0, s, a); break;
         case FDW_MODE_MOD:   hipLaunchKernelGGL((fdw_stepn_kernel<4, kPipeSteps, true, 3, kPipePF, true, 0, 1>), grid, block, 0, s, a); break;
         case FDW_MODE_PLAIN_ALL: hipLaunchKernelGGL((fdw_stepn_kernel<4, kPipeSteps, false, 0, kPipePF, false, 1, 1>), grid, block, 0, s, a); break;
@@ -639,6 +773,8 @@ hipError_t launch_stepn(const Step2Args& a, int h, int mode, hipStream_t s)
     case FDW_MODE_FWD_LINE_REC: hipLaunchKernelGGL((fdw_stepn_line_kernel<true, false, 0>), grid, block, 0, s, a); break;
     case FDW_MODE_FWD_LINE_ILLUM: hipLaunchKernelGGL((fdw_stepn_line_kernel<false, true, 0>), grid, block, 0, s, a); break;
     case FDW_MODE_FWD_LINE_REC_ILLUM: hipLaunchKernelGGL((fdw_stepn_line_rec_illum_kernel<0>), grid, block, 0, s, a); break;
+    case FDW_MODE_FWD_EXC: hipLaunchKernelGGL((fdw_stepn_exc_kernel<0>), grid, block, 0, s, a); break;
+    case FDW_MODE_FWD_LINE_PICK: hipLaunchKernelGGL((fdw_stepn_line_pick_kernel<0>), grid, block, 0, s, a); break;
     case FDW_MODE_PLAIN: hipLaunchKernelGGL((fdw_stepn_kernel<4, kPipeSteps, false, 0, kPipePF>), grid, block, 0, s, a); break;
     case FDW_MODE_MOD:   hipLaunchKernelGGL((fdw_stepn_kernel<4, kPipeSteps, true, 3, kPipePF, true>), grid, block, 0, s, a); break;
     case FDW_MODE_PLAIN_ALL: hipLaunchKernelGGL((fdw_stepn_kernel<4, kPipeSteps, false, 0, kPipePF, false, 1>), grid, block, 0, s, a); break;

@@ -44,7 +44,13 @@
  * Ricker wavelet with weights of 1 (fdw_encode_line_source), its data gather from the ns gathers of datfile (fdw_encode_gathers); the
  * model is the next draw of the border stream (R:486) or vel_ext_file's model j mod ns (R:484); fdw_shot_line migrates it.  The images
  * are stacked in the order j into dir.image, image.num has one section per plane wave, illum=1 and image_lap=1 work as for shots.  One
- * plane wave after the other; pw together with slabs > 1, gpus > 1, resid=1 or snap > 0 is refused before anything is opened. */
+ * plane wave after the other; pw together with slabs > 1, gpus > 1, resid=1 or snap > 0 is refused before anything is opened.
+ *
+ * Excitation-amplitude imaging (no counterpart in the reference): the deck key `exc=1` (absent or 0: nothing changes) sends every shot, one
+ * by one, through fdw_shot_excitation: the forward loop keeps the peak of the source field and its time level per cell, the backward loop
+ * propagates the receiver field alone and every cell takes its sample at that level.  dir.image is the stack in shot order of exc / amp
+ * where |amp| > exc_eps max |amp| (fdw_image_excitation; `exc_eps` defaults to 1e-3), image.num has one section per shot.  exc together
+ * with illum=1, resid=1, pw, snap > 0, slabs > 1 or gpus > 1 (deck or environment) is refused before anything is opened. */
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -390,6 +396,26 @@ int main(int argc, char **argv)
         }
     }
 
+    /* our extension (absent or 0: nothing changes): the excitation-amplitude imaging condition.  Every shot through fdw_shot_excitation, one
+     * after the other on one context: refused with every key that deals shots out or changes what a shot is, before any file, thread,
+     * communicator or device is touched */
+    const int exc = fdw_deck_int(deck, "exc") == 1;
+    float exc_eps = fdw_deck_has(deck, "exc_eps") ? fdw_deck_float(deck, "exc_eps") : 1.0e-3f;
+    if (exc) {
+        int sl = fdw_deck_int(deck, "slabs"), gp = fdw_deck_int(deck, "gpus");
+        if (getenv("FDW_SLABS")) sl = atoi(getenv("FDW_SLABS"));
+        if (getenv("FDW_GPUS")) gp = atoi(getenv("FDW_GPUS"));
+        const char *with = illum ? "illum=1" : (resid ? "resid=1" : (pw > 0 ? "pw" : (snap > 0 ? "snap" : (sl > 1 ? "slabs" : (gp > 1 ? "gpus" : NULL)))));
+        if (with) {
+            fprintf(stderr, "exc=1 cannot be combined with %s: the excitation-amplitude shot is a single point-source shot on one full-grid context\n", with);
+            return EXIT_FAILURE;
+        }
+        if (!(exc_eps >= 0.0f) || exc_eps > 3.0e38f) {
+            fprintf(stderr, "exc_eps=%g: must be finite and >= 0\n", (double)exc_eps);
+            return EXIT_FAILURE;
+        }
+    }
+
     printf("## vp = %s, d_obs = %s, vel_ext_file = %s, vel_ext_flag = %d \n", vpfile, datfile, vel_ext_file, vel_ext_flag);
     printf("## nz = %d, nx = %d, nt = %d \n", nz, nx, nt);
     printf("## dz = %f, dx = %f, dt = %f \n", dz, dx, dt);
@@ -546,6 +572,52 @@ int main(int argc, char **argv)
         fdw_destroy(ctx);
         if (illum && write_illum_outputs(tmpdir, img, ill, ni, illum_eps) != 0) return EXIT_FAILURE;
         free(src_ix); free(lag); free(weight); free(wav); free(enc); free(v2); free(imloc); free(illoc); free(ill);
+        goto outputs;
+    }
+    if (exc) {
+        /* ---- exc=1: every shot through fdw_shot_excitation, one by one on one context; the image of each is added to the stack in shot
+         * order by fdw_image_excitation (img is the running sum the call updates), image.num has one section per shot as always ---- */
+        const int dev_models = !vel_ext_flag && !getenv("FDW_HOST_BORDER") && nxb != 1 && nzb != 1 && nzb <= nxe;      /* as dev_border below */
+        const long long draws = fdw_border_draws(nx, nz, nxb, nzb);
+        fdw_ctx *ctx = NULL;
+        float *v2 = (float *)malloc(ne * sizeof(float));
+        if (!v2) {
+            fprintf(stderr, "out of host memory\n");
+            return EXIT_FAILURE;
+        }
+        if (fdw_create(&prm, 0, &ctx) != FDW_OK || (dev_models && fdw_model_resident(ctx, vp) != FDW_OK)) {
+            fprintf(stderr, "fdw_create: %s\n", fdw_last_error());
+            return EXIT_FAILURE;
+        }
+        printf("## exc = 1, exc_eps = %g: excitation-amplitude imaging, image += exc / amp per shot \n", (double)exc_eps);
+        const double t0 = now_s();
+        for (int is = 0; is < ns; is++) {
+            const float *model = NULL;      /* NULL: the squared model drawn in HBM */
+            int rc = FDW_OK;
+            if (!dev_models) {
+                const float *v = vpe;
+                if (vel_ext_flag) v = vel_ext_rnd + (size_t)is * ne;             /* R:484 */
+                else fdw_extendvel_linear(nx, nz, nxb, nzb, vpe);               /* R:486: the next draws of the one stream, in shot order */
+                for (size_t k = 0; k < ne; k++) v2[k] = v[k] * v[k];             /* R:490-494 */
+                model = v2;
+            } else {
+                rc = fdw_dev_extendvel_linear(ctx, (unsigned long long)is * (unsigned long long)draws, NULL);
+            }
+            if (rc == FDW_OK)
+                rc = fdw_shot_excitation(ctx, model, sx[is], sz, gz, srce, d_obs + (size_t)is * nx * nt, exc_eps, img, NULL, NULL, NULL, NULL, NULL);
+            if (rc != FDW_OK) {
+                fprintf(stderr, "shot %d: %s\n", is + 1, fdw_last_error());
+                return EXIT_FAILURE;
+            }
+            fprintf(stdout, "** source %d, at (%d,%d) \n\n** backward propagation %d, at (%d,%d) \n\n", is + 1, sx[is] - nxb, sz - nzb, is + 1, sx[is] - nxb,
+                    sz - nzb);
+            fprintf(fnum, "======== %i ========\n", is);
+            for (int iz = 0; iz < nz; iz++)
+                for (int ix = 0; ix < nx; ix++) fprintf(fnum, " %f \n", img[(size_t)ix * nz + iz]);
+        }
+        t_shots = now_s() - t0;
+        fdw_destroy(ctx);
+        free(v2);
         goto outputs;
     }
     if (slabs > 1) {
