@@ -514,11 +514,109 @@ static int place_line(const fdw_ctx* c, const char* who, int sz, Injection* in)
     in->n = std::max(0, std::min(c->nx, c->xlim - c->prm.nxb));
     return FDW_OK;
 }
-// launcher mode of a forward launch with a line source
-static int line_kmode(const float* d_rec, const float* d_illum)
+
+// ---- what a forward pass does besides stepping ------------------------------------------------------------------------------------------
+// excitation-amplitude imaging (fdwave.h): what one forward step does on top of its update.  Maps: exc_arr = amp, where the new field beats
+// it strictly in magnitude amp takes it and texc takes the key (= it + 1).  Pick: exc_arr = exc, which takes the new field where
+// texc == key (= top - it); texc is only read.
+enum class Exc { none, maps, pick };
+
+// The description of a forward loop, filled where the loop is asked for: its arrays hold all iterations.  The launch builders take a
+// FwdView, which only view_at() makes: the launch whose first step is iteration `it`.
+struct Forward {
+    const float* samples = nullptr;   // the wavelet [nt] of a point source at (sx, sz) -- NULL, or sx < 0 outside the modelling dialect: none --
+    int sx = -1, sz = 0;
+    bool line = false;                // ... or the line-source gather [nt][nx] on column sz (sx unused)
+    float* rec = nullptr;             // recording: the trace rows [nt][nx] at depth gz
+    int gz = 0;
+    float* illum = nullptr;           // the source illumination accumulator
+    Exc exc = Exc::none;              // the excitation maps of a point-source pass / the pick of a line-source pass
+    float* exc_arr = nullptr;         // amp (maps) or exc (pick)
+    int* texc = nullptr;
+    int top = 0;                      // pick: iteration it takes the cells with texc == top - it
+    bool may_band = false;            // fdw_dev_steps2: the loop's pipeline passes may run as row bands (steps_loop)
+    Forward recording(float* d_rec, int rec_z) const { Forward v = *this; v.rec = d_rec; v.gz = rec_z; return v; }      // (NULL: none)
+    Forward illuminating(float* d_illum) const { Forward v = *this; v.illum = d_illum; return v; }
+    Forward exciting(Exc what, float* arr, int* map, int pick_top) const { Forward v = *this; v.exc = what; v.exc_arr = arr; v.texc = map; v.top = pick_top; return v; }
+};
+struct FwdView : Forward {
+    int exc_key = 0;                  // the excitation key of the launch's first step
+    float* out = nullptr;             // DD_FWD: the new field goes here instead of over pp
+};
+// The strides, stated once: a line source advances nx samples per step and a point source one, a trace row is nx samples, the maps' key
+// is it + 1 and the pick's top - it.
+static FwdView view_at(const Forward& f, int it, int nx)
 {
-    if (d_rec && d_illum) return FDW_MODE_FWD_LINE_REC_ILLUM;
-    return d_rec ? FDW_MODE_FWD_LINE_REC : (d_illum ? FDW_MODE_FWD_LINE_ILLUM : FDW_MODE_FWD_LINE);
+    FwdView v;
+    static_cast<Forward&>(v) = f;
+    if (f.samples) v.samples = f.samples + (size_t)it * (f.line ? (size_t)nx : 1);
+    if (f.rec) v.rec = f.rec + (size_t)it * (size_t)nx;
+    v.exc_key = f.exc == Exc::pick ? f.top - it : it + 1;
+    return v;
+}
+// a point source at (sx, sz) with the samples d_srce (NULL: no source) / a line source on column sz with the gather d_wav
+static Forward point_source(const float* d_srce, int sx, int sz) { Forward f; f.samples = d_srce; f.sx = d_srce ? sx : -1; f.sz = sz; return f; }
+static Forward line_source(const float* d_wav, int sz) { Forward f; f.samples = d_wav; f.sz = sz; f.line = true; return f; }
+// what a backward launch injects: its first iteration's receiver samples [nx], at depth gz
+static FwdView receiver_samples(const float* d_samples, int gz) { return view_at(point_source(d_samples, -1, gz), 0, 0); }
+
+// The forward variants the launchers are built for: (line?, records?, illuminates?, excitation) <-> launcher mode, and what each kernel
+// family does with it.  The one-step ring family and the pipeline have a kernel for every row.  two_step: the two-step family has one (a
+// pair of such steps is two single steps on copies otherwise).  generic: what the generic-order family launches for it; where that is
+// another mode, the illumination / excitation follows the plain step as an add kernel.  A new variant is one row here.
+static const struct FwdVariant {
+    int kmode;
+    bool line, rec, illum;
+    Exc exc;
+    bool two_step;
+    int generic;
+} kFwdVariants[] = {
+    // kmode, line, rec, illum, exc, two_step, generic
+    {FDW_MODE_FWD, false, false, false, Exc::none, true, FDW_MODE_FWD},
+    {FDW_MODE_FWD_REC, false, true, false, Exc::none, true, FDW_MODE_FWD_REC},
+    {FDW_MODE_FWD_ILLUM, false, false, true, Exc::none, true, FDW_MODE_FWD},
+    {FDW_MODE_FWD_REC_ILLUM, false, true, true, Exc::none, false, FDW_MODE_FWD_REC},
+    {FDW_MODE_FWD_LINE, true, false, false, Exc::none, true, FDW_MODE_FWD_LINE},
+    {FDW_MODE_FWD_LINE_REC, true, true, false, Exc::none, true, FDW_MODE_FWD_LINE_REC},
+    {FDW_MODE_FWD_LINE_ILLUM, true, false, true, Exc::none, true, FDW_MODE_FWD_LINE},
+    {FDW_MODE_FWD_LINE_REC_ILLUM, true, true, true, Exc::none, true, FDW_MODE_FWD_LINE_REC},
+    {FDW_MODE_FWD_EXC, false, false, false, Exc::maps, false, FDW_MODE_FWD},
+    {FDW_MODE_FWD_LINE_PICK, true, false, false, Exc::pick, false, FDW_MODE_FWD_LINE},
+};
+// The row of a launch of base mode `mode` with these extras.  Only FWD has variants: the other modes (PLAIN, RECV, MOD ...) are served as
+// they are by every family that takes them.  kmode -1: no kernel is built for the combination.
+static FwdVariant fwd_variant(int mode, const Forward& f)
+{
+    for (const FwdVariant& v : kFwdVariants)
+        if (mode == FDW_MODE_FWD && v.line == f.line && v.rec == (f.rec != nullptr) && v.illum == (f.illum != nullptr) && v.exc == f.exc) return v;
+    return FwdVariant{mode == FDW_MODE_FWD ? -1 : mode, false, false, false, Exc::none, true, mode};
+}
+// whether the family of `steps` steps per pass (1: ring or generic order, 2: two-step, kPipeSteps: pipeline) serves it in one pass
+static bool family_serves(int steps, const FwdVariant& v) { return steps != 2 || v.two_step; }
+
+// rec*, img, texc and exc_key of a forward launch from its view
+template <class A>
+static void fill_forward(const fdw_ctx* c, A& a, const FwdVariant& v, const FwdView& f)
+{
+    if (v.rec) fill_rec(c, a, f.rec, f.gz);
+    if (v.illum) a.img = f.illum;      // the accumulator travels in `img`
+    if (f.exc != Exc::none) {
+        a.img = f.exc_arr; a.texc = f.texc; a.exc_key = f.exc_key;
+    }
+}
+
+// Where a launch of `mode` injects f.samples: the line or the point of a forward launch (a line's samples: [steps][nx] at depth f.sz), or
+// the receiver rows of a backward launch (receiver_samples).
+static int place_injection(const fdw_ctx* c, const char* who, int mode, const FwdView& f, Injection* in)
+{
+    if (f.line) {
+        if (mode != FDW_MODE_FWD || !f.samples) return fail(FDW_EINVAL, "%s: a line source drives a forward launch", who);
+        return place_line(c, who, f.sz, in);
+    }
+    if (mode == FDW_MODE_FWD || mode == FDW_MODE_DD_FWD || mode == FDW_MODE_MOD) return place_source(c, who, mode == FDW_MODE_MOD, f.samples, f.sx, f.sz, in);
+    if (mode == FDW_MODE_RECV || mode == FDW_MODE_DD_RECV || mode == FDW_MODE_BACK || mode == FDW_MODE_BACK4)
+        return place_receivers(c, who, mode == FDW_MODE_DD_RECV ? c->prm.nzb : c->prm.nxb, f.sz, in);
+    return FDW_OK;
 }
 
 // Receiver rows [x, x+n) from upd_x1 up to r1 lie beyond the time-stepped rows (narrow x border + truncated extents): the reference still
@@ -533,42 +631,40 @@ static int static_receiver_rows(fdw_ctx* c, int x, int n, int r1, float* field, 
     return FDW_OK;
 }
 
-// excitation-amplitude imaging (fdwave.h): what one forward step does on top of its update.  Maps (pick = false): arr = amp, where the new
-// field beats it strictly in magnitude amp takes it and texc takes key (= it + 1).  Pick: arr = exc, which takes the new field where texc == key
-// (= top - it); texc is only read.
-struct ExcStep {
-    float* arr;
-    int* texc;
-    int key;
-    bool pick;
+struct BackExtra {           // what the receiver / imaging variants of the one-step and two-step kernels need on top of the forward ones
+    const float* inj2 = nullptr;      // two-step: the receiver samples of iteration it+1
+    const float* psrc_a = nullptr;    // the source field the new receiver field is imaged against (two-step: iteration it's)
+    const float* psrc_b = nullptr;    // two-step: iteration it+1's
+    float* img = nullptr;
+    float* fpp = nullptr;             // BACK: the older source field, stepped in place by the same launch
 };
 
-static int step_impl(fdw_ctx* c, int mode, const float* d_p, float* d_pp, const float* d_v2, int r0, int r1,
-                     int pp_twice, const float* d_inj, int inj_x_global, int inj_z, const float* d_psrc, float* d_img,
-                     hipStream_t s, float* d_rec_row = nullptr, int rec_z = 0, float* d_fpp = nullptr, float* d_out = nullptr, float* d_illum = nullptr,
-                     bool line = false, const ExcStep* xs = nullptr)
+// One launch of the one-step kernels on rows [r0, r1).  f (a view): the source, trace row and accumulators of a FWD / DD_FWD / MOD step, the
+// receiver samples of a RECV / DD_RECV / BACK step; bk: the source field and image of the latter.
+static int step_impl(fdw_ctx* c, int mode, const float* d_p, float* d_pp, const float* d_v2, int r0, int r1, int pp_twice, const FwdView& f,
+                     const BackExtra& bk, hipStream_t s)
 {
     const bool lap = (mode == FDW_MODE_LAP);
     if (!d_p || !d_pp) return fail(FDW_EINVAL, "step: field pointer is NULL");
     if (!lap && !d_v2) return fail(FDW_EINVAL, "step: v2 is NULL");
-    if ((mode == FDW_MODE_RECV || mode == FDW_MODE_DD_RECV || mode == FDW_MODE_BACK) && (!d_psrc || !d_img || !d_inj)) return fail(FDW_EINVAL, "step: RECV needs d_inj, d_psrc and d_img");
-    if (mode == FDW_MODE_BACK && (!d_fpp || d_fpp == d_pp || d_fpp == d_p || d_psrc == d_pp || c->h > kMaxFastHalfOrder || c->use_generic))
+    if ((mode == FDW_MODE_RECV || mode == FDW_MODE_DD_RECV || mode == FDW_MODE_BACK) && (!bk.psrc_a || !bk.img || !f.samples)) return fail(FDW_EINVAL, "step: RECV needs d_inj, d_psrc and d_img");
+    if (mode == FDW_MODE_BACK && (!bk.fpp || bk.fpp == d_pp || bk.fpp == d_p || bk.psrc_a == d_pp || c->h > kMaxFastHalfOrder || c->use_generic))
         return fail(FDW_EINVAL, "step: BACK needs the older source field as a fourth, distinct buffer and an order <= 8");
     if (mode < FDW_MODE_FWD || mode > FDW_MODE_BACK) return fail(FDW_EINVAL, "step: unknown mode %d", mode);
     const int mode_dialect = mode == FDW_MODE_MOD ? FDW_DIALECT_MOD : ((mode == FDW_MODE_DD_FWD || mode == FDW_MODE_DD_RECV) ? FDW_DIALECT_RTM_STORED : FDW_DIALECT_RTM);
     if (mode_dialect != c->prm.dialect)
         return fail(FDW_ESTATE, "step: mode %d does not belong to this context's dialect %d", mode, c->prm.dialect);
     if (r0 < 0 || r1 > c->nxl || r0 > r1) return fail(FDW_EINVAL, "step: rows [%d,%d) outside the slab (%d rows)", r0, r1, c->nxl);
-    // d_out (the new field stored somewhere else than over pp) is honoured by the register-ring kernel's DD_FWD instantiation only -- the one
+    // f.out (the new field stored somewhere else than over pp) is honoured by the register-ring kernel's DD_FWD instantiation only -- the one
     // caller, fdw_rtm_stored_shot, whose store slots are zero-filled so that cells the kernel never stores equal what an in-place update
     // would have left there.  Anything else would silently update in place: refuse.
-    if (d_out && (mode != FDW_MODE_DD_FWD || c->h > kMaxFastHalfOrder || c->use_generic || d_out == d_p || d_out == d_pp))
+    if (f.out && (mode != FDW_MODE_DD_FWD || c->h > kMaxFastHalfOrder || c->use_generic || f.out == d_p || f.out == d_pp))
         return fail(FDW_EINVAL, "step: a separate output array is supported by the DD_FWD register-ring kernel only, and must not alias the inputs");
 
     StepArgs a{};
     fill_common(c, a, d_p, d_pp, d_v2, pp_twice);
-    a.psrc = d_psrc; a.img = d_img; a.fpp = d_fpp;
-    a.out = d_out;            // NULL: in place over pp
+    a.psrc = bk.psrc_a; a.img = bk.img; a.fpp = bk.fpp;
+    a.out = f.out;            // NULL: in place over pp
     a.gcx = c->d_gcx; a.gcz = c->d_gcz;
     a.r0 = r0;
     a.r1 = lap ? r1 : std::min(r1, c->upd_x1);   // rows >= xlim are never time-stepped (R:83-87)
@@ -576,39 +672,25 @@ static int step_impl(fdw_ctx* c, int mode, const float* d_p, float* d_pp, const 
         a.lap_x0 = c->slap_x0; a.lap_x1 = c->slap_x1; a.lap_z0 = c->slap_z0; a.lap_z1 = c->slap_z1;
     }
     Injection in;
-    if (line) {               // FWD with d_inj -> this step's line samples [nx], inj_z = their depth
-        if (mode != FDW_MODE_FWD || !d_inj) return fail(FDW_EINVAL, "step: a line source drives a forward step");
-        FDW_TRY(place_line(c, "step", inj_z, &in));
-    } else if (mode == FDW_MODE_FWD || mode == FDW_MODE_DD_FWD || mode == FDW_MODE_MOD)
-        FDW_TRY(place_source(c, "step", mode == FDW_MODE_MOD, d_inj, inj_x_global, inj_z, &in));
-    else if (mode == FDW_MODE_RECV || mode == FDW_MODE_DD_RECV || mode == FDW_MODE_BACK)
-        FDW_TRY(place_receivers(c, "step", mode == FDW_MODE_DD_RECV ? c->prm.nzb : c->prm.nxb, inj_z, &in));
-    if (mode == FDW_MODE_MOD) FDW_TRY(fill_mod(c, a, "step", d_rec_row, rec_z));
+    FDW_TRY(place_injection(c, "step", mode, f, &in));
+    if (mode == FDW_MODE_MOD) FDW_TRY(fill_mod(c, a, "step", f.rec, f.gz));
     // (a batch accumulates per shot, illum + shot * field, inside fdw_shot_batch_illum only)
-    if (d_illum && (mode != FDW_MODE_FWD || (c->nbatch > 1 && !c->batch_illum)))
+    if (f.illum && (mode != FDW_MODE_FWD || (c->nbatch > 1 && !c->batch_illum)))
         return fail(FDW_EINVAL, "step: illumination belongs to a forward step of one shot");
     // the maps ride a point-source step, the pick a line-source step; neither is built together with recording or illumination, nor batched
-    if (xs && (mode != FDW_MODE_FWD || xs->pick != line || d_rec_row || d_illum || c->nbatch > 1 || !xs->arr || !xs->texc))
+    const FwdVariant v = fwd_variant(mode, f);
+    if (f.exc != Exc::none && (v.kmode < 0 || mode != FDW_MODE_FWD || c->nbatch > 1 || !f.exc_arr || !f.texc))
         return fail(FDW_EINVAL, "step: the excitation maps belong to a plain forward step of one shot, the pick to a plain line-source step");
-    // the RTM forward step that records its trace row, that accumulates the source illumination (the accumulator travels in `img`), or both
-    const bool fwd = mode == FDW_MODE_FWD;
-    const int kmode = xs ? (xs->pick ? FDW_MODE_FWD_LINE_PICK : FDW_MODE_FWD_EXC)
-                      : line ? line_kmode(d_rec_row, d_illum)
-                           : ((fwd && d_rec_row && d_illum) ? FDW_MODE_FWD_REC_ILLUM : ((fwd && d_rec_row) ? FDW_MODE_FWD_REC : ((fwd && d_illum) ? FDW_MODE_FWD_ILLUM : mode)));
-    if (xs) {
-        a.img = xs->arr; a.texc = xs->texc; a.exc_key = xs->key;
-    }
-    if (kmode == FDW_MODE_FWD_REC || kmode == FDW_MODE_FWD_REC_ILLUM || kmode == FDW_MODE_FWD_LINE_REC || kmode == FDW_MODE_FWD_LINE_REC_ILLUM)
-        fill_rec(c, a, d_rec_row, rec_z);
-    if (kmode == FDW_MODE_FWD_ILLUM || kmode == FDW_MODE_FWD_REC_ILLUM || kmode == FDW_MODE_FWD_LINE_ILLUM || kmode == FDW_MODE_FWD_LINE_REC_ILLUM) a.img = d_illum;
-    a.inj = d_inj + in.shift; a.inj_x = in.x; a.inj_z = inj_z; a.inj_n = in.n;
+    // the RTM forward step that records its trace row, that accumulates the source illumination, or both
+    fill_forward(c, a, v, f);
+    a.inj = f.samples + in.shift; a.inj_x = in.x; a.inj_z = f.sz; a.inj_n = in.n;
     if (a.r1 <= a.r0) return FDW_OK;
     if (c->nbatch > 1) {      // fdw_shot_batch: shot b = these pointers + b fields, its own gather, its own source row
         a.nbatch = c->nbatch;
         a.bstride = (long long)field_elems(c);
         // the wavelet is shared, its row moves; receivers and line sources (fdw_shot_line_batch): a gather each, the rows the same
-        const bool one_source = (mode == FDW_MODE_FWD && !line) || mode == FDW_MODE_MOD;
-        a.inj_bstride = one_source ? 0 : (long long)c->nx * (line ? c->batch_nt : c->prm.nt);
+        const bool one_source = (mode == FDW_MODE_FWD && !f.line) || mode == FDW_MODE_MOD;
+        a.inj_bstride = one_source ? 0 : (long long)c->nx * (f.line ? c->batch_nt : c->prm.nt);
         a.inj_dx = one_source ? c->batch_dsx : 0;
         a.v2_bstride = mode == FDW_MODE_MOD ? 0 : a.bstride;                       // mod_main models every shot on one velocity model (M:140-174)
         a.rec_bstride = (long long)c->nx * c->batch_nt;
@@ -616,27 +698,21 @@ static int step_impl(fdw_ctx* c, int mode, const float* d_p, float* d_pp, const 
     hipError_t e;
     if (c->h <= kMaxFastHalfOrder && !c->use_generic) {
         fill_geometry(c, a, a.r1 - a.r0, std::max(c->nbatch, 1));
-        e = launch_step_fast(a, c->h, kmode, effective_prefetch(c), s);
+        e = launch_step_fast(a, c->h, v.kmode, effective_prefetch(c), s);
     } else {
         if (mode >= FDW_MODE_MOD) return fail(FDW_EINVAL, "step: mode %d has no generic-order kernel", mode);
         // no generic-order illumination kernel: the plain step, then illum += pp (*) pp over the cells it updated
         // (recording too: the generic recording step, then the same add)
-        const bool add = kmode == FDW_MODE_FWD_ILLUM || kmode == FDW_MODE_FWD_REC_ILLUM || kmode == FDW_MODE_FWD_LINE_ILLUM || kmode == FDW_MODE_FWD_LINE_REC_ILLUM;
-        const int gmode = kmode == FDW_MODE_FWD_ILLUM ? FDW_MODE_FWD
-                          : (kmode == FDW_MODE_FWD_REC_ILLUM ? FDW_MODE_FWD_REC
-                             : (kmode == FDW_MODE_FWD_LINE_ILLUM ? FDW_MODE_FWD_LINE
-                                : (kmode == FDW_MODE_FWD_LINE_REC_ILLUM ? FDW_MODE_FWD_LINE_REC
-                                   : (kmode == FDW_MODE_FWD_EXC ? FDW_MODE_FWD : (kmode == FDW_MODE_FWD_LINE_PICK ? FDW_MODE_FWD_LINE : kmode)))));
-        e = launch_step_generic(a, c->h, gmode, s);
-        if (e == hipSuccess && add) e = launch_illum_add(d_pp, d_illum, c->pitch, a.r0, a.r1, c->upd_z1, s);
+        e = launch_step_generic(a, c->h, v.generic, s);
+        if (e == hipSuccess && v.illum) e = launch_illum_add(d_pp, f.illum, c->pitch, a.r0, a.r1, c->upd_z1, s);
         // no generic-order excitation kernel either: the plain step, then the compare-and-select / the pick over the cells it updated
-        if (e == hipSuccess && xs)
-            e = xs->pick ? launch_exc_pick(d_pp, xs->texc, xs->arr, c->pitch, a.r0, a.r1, c->upd_z1, xs->key, s)
-                         : launch_exc_select(d_pp, xs->arr, xs->texc, c->pitch, a.r0, a.r1, c->upd_z1, xs->key, s);
+        if (e == hipSuccess && f.exc != Exc::none)
+            e = f.exc == Exc::pick ? launch_exc_pick(d_pp, f.texc, f.exc_arr, c->pitch, a.r0, a.r1, c->upd_z1, f.exc_key, s)
+                                   : launch_exc_select(d_pp, f.exc_arr, f.texc, c->pitch, a.r0, a.r1, c->upd_z1, f.exc_key, s);
     }
     if (e != hipSuccess) return fail(FDW_EHIP, "kernel launch failed: %s", hipGetErrorString(e));
     if ((mode == FDW_MODE_RECV || mode == FDW_MODE_BACK) && r1 > c->upd_x1)
-        return static_receiver_rows(c, a.inj_x, a.inj_n, std::min(r1, c->nxl), d_pp, a.inj, mode == FDW_MODE_BACK ? d_fpp : d_psrc, d_img, inj_z, a.img_z1,
+        return static_receiver_rows(c, a.inj_x, a.inj_n, std::min(r1, c->nxl), d_pp, a.inj, mode == FDW_MODE_BACK ? bk.fpp : bk.psrc_a, bk.img, f.sz, a.img_z1,
                                     s);
     return FDW_OK;
 }
@@ -647,21 +723,30 @@ extern "C" int fdw_dev_step(fdw_ctx* c, int mode, const float* d_p, float* d_pp,
 {
     if (!c) return fail(FDW_EINVAL, "ctx is NULL");
     if (mode == FDW_MODE_LAP) return fail(FDW_EINVAL, "use fdw_dev_laplacian for mode 3");
-    return step_impl(c, mode, d_p, d_pp, d_v2, r0, r1, pp_twice, d_inj, inj_x, inj_z, d_psrc, d_img, pick_stream(c, stream));
+    const Forward f = point_source(d_inj, inj_x, inj_z);      // d_inj is the source's sample in the forward modes, the receivers' in the others
+    BackExtra bk;
+    bk.psrc_a = d_psrc; bk.img = d_img;
+    return step_impl(c, mode, d_p, d_pp, d_v2, r0, r1, pp_twice, view_at(f, 0, c->nx), bk, pick_stream(c, stream));
 }
 
 // One iteration of fd_back's loop (R:302-339) on rows [r0, r1) of the slab, on caller-owned device arrays.
 static int back_iter(fdw_ctx* c, int step_source, const float* d_f1, float* d_f0, const float* d_pr, float* d_ppr, const float* d_v2, int r0, int r1,
                      int pp_twice, const float* d_samples, int gz, float* d_img, hipStream_t s)
 {
+    const FwdView rs = receiver_samples(d_samples, gz);
+    BackExtra bk;
+    bk.psrc_a = d_f1; bk.img = d_img;
     if (!step_source)      // iterations 0 and 1: the source field is a snapshot as it stands (R:304-314)
-        return step_impl(c, FDW_MODE_RECV, d_pr, d_ppr, d_v2, r0, r1, pp_twice, d_samples, 0, gz, d_f1, d_img, s);
+        return step_impl(c, FDW_MODE_RECV, d_pr, d_ppr, d_v2, r0, r1, pp_twice, rs, bk, s);
     // the whole iteration in ONE pass: the source field is stepped in place (F_k overwrites F_{k-2}) in the same kernel that steps the
     // receiver field, and meets the new receiver row in registers for the imaging condition
-    if (c->h <= kMaxFastHalfOrder && !c->use_generic && !c->no_fused_back)
-        return step_impl(c, FDW_MODE_BACK, d_pr, d_ppr, d_v2, r0, r1, pp_twice, d_samples, 0, gz, d_f1, d_img, s, nullptr, 0, d_f0);
-    FDW_TRY(step_impl(c, FDW_MODE_PLAIN, d_f1, d_f0, d_v2, r0, r1, 0, nullptr, -1, 0, nullptr, nullptr, s));      // F_k overwrites F_{k-2} (R:317-318)
-    return step_impl(c, FDW_MODE_RECV, d_pr, d_ppr, d_v2, r0, r1, pp_twice, d_samples, 0, gz, d_f0, d_img, s);
+    if (c->h <= kMaxFastHalfOrder && !c->use_generic && !c->no_fused_back) {
+        bk.fpp = d_f0;
+        return step_impl(c, FDW_MODE_BACK, d_pr, d_ppr, d_v2, r0, r1, pp_twice, rs, bk, s);
+    }
+    FDW_TRY(step_impl(c, FDW_MODE_PLAIN, d_f1, d_f0, d_v2, r0, r1, 0, FwdView{}, BackExtra{}, s));      // F_k overwrites F_{k-2} (R:317-318)
+    bk.psrc_a = d_f0;
+    return step_impl(c, FDW_MODE_RECV, d_pr, d_ppr, d_v2, r0, r1, pp_twice, rs, bk, s);
 }
 
 extern "C" int fdw_dev_back_iter(fdw_ctx* c, int step_source, const float* d_f1, float* d_f0, const float* d_pr, float* d_ppr, const float* d_v2,
@@ -676,7 +761,7 @@ extern "C" int fdw_dev_back_iter(fdw_ctx* c, int step_source, const float* d_f1,
 extern "C" int fdw_dev_laplacian(fdw_ctx* c, const float* d_p, float* d_lap, void* stream)
 {
     if (!c) return fail(FDW_EINVAL, "ctx is NULL");
-    return step_impl(c, FDW_MODE_LAP, d_p, d_lap, nullptr, 0, c->nxl, 0, nullptr, -1, 0, nullptr, nullptr, pick_stream(c, stream));
+    return step_impl(c, FDW_MODE_LAP, d_p, d_lap, nullptr, 0, c->nxl, 0, FwdView{}, BackExtra{}, pick_stream(c, stream));
 }
 
 // ---- two time steps per pass (temporal blocking) --------------------------------------------------
@@ -696,11 +781,15 @@ static bool two_step_pays(const fdw_ctx* c)
 // of 8) are static in both fields, which swap roles every step: out1 now carries pp's rows, out2 p's; so do the levels in between
 // (PLAIN_ALL: level 0 pp's, level 1 p's) and the receiver field of BACK4.  Receiver rows among them (two-step RECV): iteration it injects
 // into (and images) what is now out1, iteration it+1 what is now out2.
-// [sa0, sa1) and [sb0, sb1): the rows the call was asked for (default: all).  A pass on row ranges copies the static rows AMONG them and no
-// others -- none of a gap between the two ranges, and those of a range that holds no time-stepped row at all.
-static int even_steps_tail(fdw_ctx* c, int mode, const Step2Args& a, hipStream_t s, int sa0 = 0, int sa1 = INT_MAX, int sb0 = 0, int sb1 = 0)
+// rr: the rows the call was asked for.  A pass on row ranges copies the static rows AMONG them and no others -- none of a gap between the
+// two ranges, and those of a range that holds no time-stepped row at all.
+struct RowRanges {      // rows the pass produces: [r0, r1) and optionally [r0b, r1b); r1 < 0 = all rows the reference time-steps
+    int r0 = 0, r1 = -1, r0b = 0, r1b = 0, xchunk = 0;
+};
+static int even_steps_tail(fdw_ctx* c, int mode, const Step2Args& a, const RowRanges& rr, hipStream_t s)
 {
-    const int span[2][2] = {{sa0, sa1}, {sb0, sb1}};
+    const bool whole = rr.r1 < 0;
+    const int span[2][2] = {{whole ? 0 : rr.r0, whole ? INT_MAX : rr.r1}, {whole ? 0 : rr.r0b, whole ? 0 : rr.r1b}};
     for (const auto& sp : span) {
         const int x0 = std::max(sp[0], c->upd_x1), x1 = std::min(sp[1], c->nxl);
         if (x1 <= x0) continue;
@@ -720,20 +809,13 @@ static int even_steps_tail(fdw_ctx* c, int mode, const Step2Args& a, hipStream_t
     return static_receiver_rows(c, a.inj_x, a.inj_n, c->nxl, a.out2, a.inj2, a.psrc_b, a.img, a.inj_z, a.img_z1, s);
 }
 
-struct Step2Extra {          // what the receiver / imaging variant needs on top of the forward one
-    const float* inj2 = nullptr;
-    const float* psrc_a = nullptr;
-    const float* psrc_b = nullptr;
-    float* img = nullptr;
-};
 
-// mode FWD: d_inj -> {srce[it], srce[it+1]}, inj_x_global / inj_z = source position (inj_x_global < 0: none)
+// mode FWD: f (a view) -> f.samples = {srce[it], srce[it+1]} at (f.sx, f.sz) (f.sx < 0: none), or the line samples of both steps; f.rec: the
+//   trace rows of both steps, rec and rec + nx; f.illum: their squares added to the illumination
 // mode PLAIN: no taper, no injection
-// mode RECV: d_inj / ex.inj2 -> receiver samples of iterations it / it+1 (nx each), inj_z = gz, imaging with ex.psrc_a/b
-// d_rec (mode FWD only): the trace rows of both steps, rec and rec + nx (FDW_MODE_FWD_REC)
+// mode RECV: f.samples / ex.inj2 -> receiver samples of iterations it / it+1 (nx each), f.sz = gz, imaging with ex.psrc_a/b
 static int step2_impl(fdw_ctx* c, int mode, const float* d_p, const float* d_pp, const float* d_v2, float* d_out1, float* d_out2, int pp_twice,
-                      const float* d_inj, int inj_x_global, int inj_z, const Step2Extra& ex, hipStream_t s, float* d_rec = nullptr, int rec_z = 0,
-                      float* d_illum = nullptr, bool line = false)
+                      const FwdView& f, const BackExtra& ex, hipStream_t s)
 {
     if (c->h != kMaxFastHalfOrder) return fail(FDW_EINVAL, "step2: the two-step kernel is built for order 8 only");
     if (!d_p || !d_pp || !d_v2 || !d_out1 || !d_out2) return fail(FDW_EINVAL, "step2: NULL buffer");
@@ -744,17 +826,11 @@ static int step2_impl(fdw_ctx* c, int mode, const float* d_p, const float* d_pp,
     a.out1 = d_out1; a.out2 = d_out2;
     a.psrc_a = ex.psrc_a; a.psrc_b = ex.psrc_b; a.img = ex.img;
     a.r0 = 0; a.r1 = c->upd_x1;
+    if (mode == FDW_MODE_RECV && (!f.samples || !ex.inj2 || !ex.psrc_a || !ex.psrc_b || !ex.img))
+        return fail(FDW_EINVAL, "step2: RECV needs both sample rows, both source fields and the image");
     Injection in;
-    if (line) {               // FWD with d_inj -> the line samples of both steps, [2][nx]
-        if (mode != FDW_MODE_FWD || !d_inj) return fail(FDW_EINVAL, "step2: a line source drives a forward pass");
-        FDW_TRY(place_line(c, "step2", inj_z, &in));
-    } else if (mode == FDW_MODE_FWD) {
-        FDW_TRY(place_source(c, "step2", false, d_inj, inj_x_global, inj_z, &in));
-    } else if (mode == FDW_MODE_RECV) {
-        if (!d_inj || !ex.inj2 || !ex.psrc_a || !ex.psrc_b || !ex.img) return fail(FDW_EINVAL, "step2: RECV needs both sample rows, both source fields and the image");
-        FDW_TRY(place_receivers(c, "step2", c->prm.nxb, inj_z, &in));
-    }
-    a.inj = d_inj + in.shift; a.inj2 = line ? d_inj + c->nx : ex.inj2 + in.shift; a.inj_x = in.x; a.inj_z = inj_z; a.inj_n = in.n;
+    FDW_TRY(place_injection(c, "step2", mode, f, &in));
+    a.inj = f.samples + in.shift; a.inj2 = f.line ? f.samples + c->nx : ex.inj2 + in.shift; a.inj_x = in.x; a.inj_z = f.sz; a.inj_n = in.n;
     const int ncells = c->pitch / 4;
     a.nstrip = (ncells + 59) / 60;
     a.nzblk = (a.nstrip + 3) / 4;
@@ -770,13 +846,13 @@ static int step2_impl(fdw_ctx* c, int mode, const float* d_p, const float* d_pp,
     const int chunks = (rows + xchunk - 1) / xchunk;
     a.nblk = a.nzblk * chunks;
     a.nper = (a.nblk + 7) / 8;
-    if (d_illum && (mode != FDW_MODE_FWD || (d_rec && !line))) return fail(FDW_EINVAL, "step2: illumination belongs to a plain forward pass");
-    const int kmode = line ? line_kmode(d_rec, d_illum) : ((mode == FDW_MODE_FWD && d_rec) ? FDW_MODE_FWD_REC : ((mode == FDW_MODE_FWD && d_illum) ? FDW_MODE_FWD_ILLUM : mode));
-    if (kmode == FDW_MODE_FWD_REC || kmode == FDW_MODE_FWD_LINE_REC || kmode == FDW_MODE_FWD_LINE_REC_ILLUM) fill_rec(c, a, d_rec, rec_z);
-    if (kmode == FDW_MODE_FWD_ILLUM || kmode == FDW_MODE_FWD_LINE_ILLUM || kmode == FDW_MODE_FWD_LINE_REC_ILLUM) a.img = d_illum;
-    hipError_t e = launch_step2(a, c->h, kmode, s);
+    const FwdVariant v = fwd_variant(mode, f);
+    if ((f.illum && mode != FDW_MODE_FWD) || v.kmode < 0 || !family_serves(2, v))
+        return fail(FDW_EINVAL, "step2: illumination belongs to a forward pass, and no two-step kernel is built for this combination of extras");
+    fill_forward(c, a, v, f);
+    hipError_t e = launch_step2(a, c->h, v.kmode, s);
     if (e != hipSuccess) return fail(FDW_EHIP, "step2 launch failed: %s", hipGetErrorString(e));
-    return even_steps_tail(c, mode, a, s);
+    return even_steps_tail(c, mode, a, RowRanges{}, s);
 }
 
 // ---- kPipeSteps time steps per pass (wave pipeline through LDS) -------------------------------------
@@ -789,7 +865,7 @@ static bool pipe_pays(const fdw_ctx* c)
     return (long)c->upd_x1 * ((c->pitch / 4 + 55) / 56) >= kPipeAutoStripRows;
 }
 
-// FWD: d_inj -> kPipeSteps source samples srce[it .. it+kPipeSteps-1]; PLAIN: no taper, no injection.
+// FWD: f.samples -> kPipeSteps source samples srce[it .. it+kPipeSteps-1]; PLAIN: no taper, no injection.
 // d_out1 = u^{n+kPipeSteps-1}, d_out2 = u^{n+kPipeSteps}.
 struct StepnBack {      // the passes of the backward loop (Step2Args: lvl0, lvl1, plev, img, inj_stride, rp ...)
     float *lvl0 = nullptr, *lvl1 = nullptr;       // PLAIN_ALL: where waves 0 and 1 store their levels
@@ -799,12 +875,9 @@ struct StepnBack {      // the passes of the backward loop (Step2Args: lvl0, lvl
     const float *rp = nullptr, *rpp = nullptr;    // BACK4: the receiver pair (the positional arguments are the source field's)
     float *rout1 = nullptr, *rout2 = nullptr;
 };
-struct RowRanges {      // rows the pass produces: [r0, r1) and optionally [r0b, r1b); r1 < 0 = all rows the reference time-steps
-    int r0 = 0, r1 = -1, r0b = 0, r1b = 0, xchunk = 0;
-};
 // cls[L] of every tile of a FWD / PLAIN launch of fdw_stepn_kernel, in the tile order L = chunk row * nstrip + strip: 0 = it runs the lean body,
 // 1 = the full body, by the predicate the kernel picks the body with (pipe_tile_lean, fdw_kernels.h)
-static void tile_classes(const Step2Args& a, int kmode, std::vector<unsigned char>& cls)
+static void tile_classes(const Step2Args& a, const FwdVariant& v, std::vector<unsigned char>& cls)
 {
     constexpr int H = kMaxFastHalfOrder, NS = kPipeSteps;
     cls.resize((size_t)a.nblk);
@@ -814,10 +887,10 @@ static void tile_classes(const Step2Args& a, int kmode, std::vector<unsigned cha
         const int xa = second ? a.r0b + (xb - a.chunks_a) * a.xchunk : a.r0 + xb * a.xchunk;
         const int xe = std::min(xa + a.xchunk, second ? a.r1b : a.r1);
         const int cs = zb * (64 - 2 * NS) - NS;
-        const bool lean = kmode == FDW_MODE_PLAIN      ? pipe_tile_lean<H, NS, false, 0>(a, cs, xa, xe)
-                          : (kmode == FDW_MODE_FWD_LINE_REC || kmode == FDW_MODE_FWD_LINE_REC_ILLUM) ? pipe_tile_lean<H, NS, true, 2, false, true>(a, cs, xa, xe)
-                          : (kmode == FDW_MODE_FWD_LINE || kmode == FDW_MODE_FWD_LINE_ILLUM || kmode == FDW_MODE_FWD_LINE_PICK) ? pipe_tile_lean<H, NS, true, 2>(a, cs, xa, xe)
-                                                           : pipe_tile_lean<H, NS, true, 1>(a, cs, xa, xe);
+        const bool lean = v.kmode == FDW_MODE_PLAIN ? pipe_tile_lean<H, NS, false, 0>(a, cs, xa, xe)
+                          : (v.line && v.rec)       ? pipe_tile_lean<H, NS, true, 2, false, true>(a, cs, xa, xe)
+                          : v.line                  ? pipe_tile_lean<H, NS, true, 2>(a, cs, xa, xe)
+                                                    : pipe_tile_lean<H, NS, true, 1>(a, cs, xa, xe);
         cls[(size_t)L] = lean ? 0 : 1;
     }
 }
@@ -842,21 +915,21 @@ struct StepnPlan {
 static thread_local StepnPlan* g_plan = nullptr;
 
 static int stepn_impl(fdw_ctx* c, int mode, const float* d_p, const float* d_pp, const float* d_v2, float* d_out1, float* d_out2, int pp_twice,
-                      const float* d_inj, int inj_x_global, int inj_z, hipStream_t s, const RowRanges& rr = RowRanges{}, float* d_rec = nullptr,
-                      int rec_z = 0, const StepnBack* bk = nullptr, float* d_illum = nullptr, bool line = false, const ExcStep* xs = nullptr)
+                      const FwdView& f, const StepnBack& bk, const RowRanges& rr, hipStream_t s)
 {
+    const bool recv = mode == FDW_MODE_RECV || mode == FDW_MODE_BACK4;
     if (c->h != kMaxFastHalfOrder) return fail(FDW_EINVAL, "stepn: the pipelined kernel is built for order 8 only");
     if (mode != FDW_MODE_FWD && mode != FDW_MODE_PLAIN && mode != FDW_MODE_MOD && mode != FDW_MODE_PLAIN_ALL && mode != FDW_MODE_RECV && mode != FDW_MODE_BACK4)
         return fail(FDW_EINVAL, "stepn: FWD, PLAIN, PLAIN_ALL, RECV, BACK4 or MOD only");
     if (mode == FDW_MODE_BACK4) {
-        if (!bk || !bk->img || !d_inj || !bk->rp || !bk->rpp || !bk->rout1 || !bk->rout2) return fail(FDW_EINVAL, "stepn: BACK4 needs the receiver pair, its outputs, samples and image");
-        const float* all[8] = {d_p, d_pp, d_out1, d_out2, bk->rp, bk->rpp, bk->rout1, bk->rout2};
+        if (!bk.img || !f.samples || !bk.rp || !bk.rpp || !bk.rout1 || !bk.rout2) return fail(FDW_EINVAL, "stepn: BACK4 needs the receiver pair, its outputs, samples and image");
+        const float* all[8] = {d_p, d_pp, d_out1, d_out2, bk.rp, bk.rpp, bk.rout1, bk.rout2};
         for (int i = 0; i < 8; i++)
             for (int j = i + 1; j < 8; j++)
                 if (all[i] == all[j]) return fail(FDW_EINVAL, "stepn: BACK4 buffers must not alias");
     }
-    if ((mode == FDW_MODE_PLAIN_ALL && (!bk || !bk->lvl0 || !bk->lvl1)) ||
-        (mode == FDW_MODE_RECV && (!bk || !bk->img || !d_inj || !bk->plev[0] || !bk->plev[1] || !bk->plev[2] || !bk->plev[3])))
+    if ((mode == FDW_MODE_PLAIN_ALL && (!bk.lvl0 || !bk.lvl1)) ||
+        (mode == FDW_MODE_RECV && (!bk.img || !f.samples || !bk.plev[0] || !bk.plev[1] || !bk.plev[2] || !bk.plev[3])))
         return fail(FDW_EINVAL, "stepn: the backward passes need their level buffers / source fields, samples and image");
     if ((mode == FDW_MODE_MOD) != (c->prm.dialect == FDW_DIALECT_MOD)) return fail(FDW_ESTATE, "stepn: mode %d does not belong to dialect %d", mode, c->prm.dialect);
     if (!d_p || !d_pp || !d_v2 || !d_out1 || !d_out2) return fail(FDW_EINVAL, "stepn: NULL buffer");
@@ -876,51 +949,37 @@ static int stepn_impl(fdw_ctx* c, int mode, const float* d_p, const float* d_pp,
         a.zt_hi = four_sided ? c->prm.nze - c->prm.nzb : -1;
     }
     Injection in;
-    if (line) {               // FWD with d_inj -> the line samples of the pass's steps, [kPipeSteps][nx]
-        if (mode != FDW_MODE_FWD || !d_inj) return fail(FDW_EINVAL, "stepn: a line source drives a forward pass");
-        FDW_TRY(place_line(c, "stepn", inj_z, &in));
-        a.inj_stride = c->nx;
-    } else if (mode == FDW_MODE_FWD || mode == FDW_MODE_MOD) FDW_TRY(place_source(c, "stepn", mode == FDW_MODE_MOD, d_inj, inj_x_global, inj_z, &in));
+    FDW_TRY(place_injection(c, "stepn", mode, f, &in));
+    if (f.line) a.inj_stride = c->nx;
     if (mode == FDW_MODE_PLAIN_ALL) {
-        a.lvl0 = bk->lvl0; a.lvl1 = bk->lvl1;
-        for (float* o : {d_out1, d_out2}) if (bk->lvl0 == o || bk->lvl1 == o || bk->lvl0 == bk->lvl1 || bk->lvl0 == d_p || bk->lvl0 == d_pp || bk->lvl1 == d_p || bk->lvl1 == d_pp)
+        a.lvl0 = bk.lvl0; a.lvl1 = bk.lvl1;
+        for (float* o : {d_out1, d_out2}) if (bk.lvl0 == o || bk.lvl1 == o || bk.lvl0 == bk.lvl1 || bk.lvl0 == d_p || bk.lvl0 == d_pp || bk.lvl1 == d_p || bk.lvl1 == d_pp)
             return fail(FDW_EINVAL, "stepn: level buffers must not alias the inputs or outputs");
     }
     if (mode == FDW_MODE_BACK4) {
-        a.rp = bk->rp; a.rpp = bk->rpp; a.rout1 = bk->rout1; a.rout2 = bk->rout2;
+        a.rp = bk.rp; a.rpp = bk.rpp; a.rout1 = bk.rout1; a.rout2 = bk.rout2;
     }
-    if (mode == FDW_MODE_RECV || mode == FDW_MODE_BACK4) {
-        FDW_TRY(place_receivers(c, "stepn", c->prm.nxb, inj_z, &in));
-        a.inj_stride = bk->inj_stride;
-        a.img = bk->img;
-        for (int i = 0; i < kPipeSteps; i++) a.plev[i] = bk->plev[i];
+    if (recv) {
+        a.inj_stride = bk.inj_stride;
+        a.img = bk.img;
+        for (int i = 0; i < kPipeSteps; i++) a.plev[i] = bk.plev[i];
     }
-    if (mode == FDW_MODE_MOD) FDW_TRY(fill_mod(c, a, "stepn", d_rec, rec_z));
-    if (d_illum && mode != FDW_MODE_FWD) return fail(FDW_EINVAL, "stepn: illumination belongs to a forward pass");
-    // xs: the excitation maps of a point-source pass / the pick of a line-source pass; xs->key belongs to the pass's first step
-    if (xs && (mode != FDW_MODE_FWD || xs->pick != line || d_rec || d_illum || !xs->arr || !xs->texc))
+    if (mode == FDW_MODE_MOD) FDW_TRY(fill_mod(c, a, "stepn", f.rec, f.gz));
+    if (f.illum && mode != FDW_MODE_FWD) return fail(FDW_EINVAL, "stepn: illumination belongs to a forward pass");
+    // the excitation maps of a point-source pass / the pick of a line-source pass; f.exc_key belongs to the pass's first step
+    const FwdVariant v = fwd_variant(mode, f);
+    if (f.exc != Exc::none && (v.kmode < 0 || mode != FDW_MODE_FWD || !f.exc_arr || !f.texc))
         return fail(FDW_EINVAL, "stepn: the excitation maps belong to a plain forward pass, the pick to a plain line-source pass");
-    if (xs) {
-        a.img = xs->arr; a.texc = xs->texc; a.exc_key = xs->key;
-    }
-    // FWD with d_rec: the trace rows of the pass's four steps; with d_illum: their squares added to the illumination; with both: both
-    const bool fwd = mode == FDW_MODE_FWD;
-    const int kmode = xs ? (xs->pick ? FDW_MODE_FWD_LINE_PICK : FDW_MODE_FWD_EXC)
-                      : line ? line_kmode(d_rec, d_illum)
-                           : ((fwd && d_rec && d_illum) ? FDW_MODE_FWD_REC_ILLUM : ((fwd && d_rec) ? FDW_MODE_FWD_REC : ((fwd && d_illum) ? FDW_MODE_FWD_ILLUM : mode)));
-    if (kmode == FDW_MODE_FWD_REC || kmode == FDW_MODE_FWD_REC_ILLUM || kmode == FDW_MODE_FWD_LINE_REC || kmode == FDW_MODE_FWD_LINE_REC_ILLUM)
-        fill_rec(c, a, d_rec, rec_z);
-    if (kmode == FDW_MODE_FWD_ILLUM || kmode == FDW_MODE_FWD_REC_ILLUM || kmode == FDW_MODE_FWD_LINE_ILLUM || kmode == FDW_MODE_FWD_LINE_REC_ILLUM) a.img = d_illum;
-    a.inj = d_inj + in.shift; a.inj_x = in.x; a.inj_z = inj_z; a.inj_n = in.n;
+    // FWD with f.rec: the trace rows of the pass's four steps; with f.illum: their squares added to the illumination; with both: both
+    fill_forward(c, a, v, f);
+    a.inj = f.samples + in.shift; a.inj_x = in.x; a.inj_z = f.sz; a.inj_n = in.n;
     const int ncells = c->pitch / 4, own = 64 - 2 * kPipeSteps;
     a.nstrip = (ncells + own - 1) / own;
     a.nzblk = a.nstrip;
     const int rows_a = std::max(a.r1 - a.r0, 0), rows_b = std::max(a.r1b - a.r0b, 0), rows = rows_a + rows_b;
     static_assert(kPipeSteps % 2 == 0, "static-row bookkeeping assumes an even number of steps per pass");
-    auto static_rows = [&]() -> int {      // the static rows among the rows asked for
-        return whole ? even_steps_tail(c, mode, a, s) : even_steps_tail(c, mode, a, s, rr.r0, rr.r1, rr.r0b, rr.r1b);
-    };
-    if (rows <= 0) return g_plan ? FDW_OK : static_rows();      // no time-stepped row among them: nothing to launch
+    // (even_steps_tail: the static rows among the rows asked for)
+    if (rows <= 0) return g_plan ? FDW_OK : even_steps_tail(c, mode, a, rr, s);      // no time-stepped row among them: nothing to launch
     // whole ring turns: xchunk + (NS-1)(2H+1) = 10k  ->  xchunk = 10k - 27 (13, 23, ... 83, 93, ...)
     const long strip_rows = (long)rows * a.nstrip;
     // measured: 16384^2 579 Gpt/s at 253 (560 at 173); 8192^2 566 at 173 (509 at 83, 553 at 253); 4096^2 452 at 83 (382 at 43, 388 at 173);
@@ -946,12 +1005,12 @@ static int stepn_impl(fdw_ctx* c, int mode, const float* d_p, const float* d_pp,
     a.nper = (a.nblk + 7) / 8;
     if (g_plan) {      // fdw_debug_step4_plan: the tiles of this launch and which of them run the lean body; nothing launched
         g_plan->nblk = a.nblk; g_plan->nstrip = a.nstrip;
-        tile_classes(a, kmode, g_plan->cls);
+        tile_classes(a, v, g_plan->cls);
         return FDW_OK;
     }
-    hipError_t e = launch_stepn(a, c->h, kmode, s);
+    hipError_t e = launch_stepn(a, c->h, v.kmode, s);
     if (e != hipSuccess) return fail(FDW_EHIP, "stepn launch failed: %s", hipGetErrorString(e));
-    return static_rows();
+    return even_steps_tail(c, mode, a, rr, s);
 }
 
 int fdw_receivers_stepped(const fdw_ctx* c) { return c->prm.nxb + c->nx <= c->xlim; }
@@ -966,17 +1025,18 @@ static int back4(fdw_ctx* c, const float* d_f1, const float* d_f0, float* d_fo1,
 {
     if (!c->no_back_fused) {
         StepnBack b4;
-        b4.rp = d_pr; b4.rpp = d_ppr; b4.rout1 = d_ro1; b4.rout2 = d_ro2; b4.img = d_img; b4.inj_stride = sample_stride;
-        return stepn_impl(c, FDW_MODE_BACK4, d_f1, d_f0, d_v2, d_fo1, d_fo2, pp_twice, d_samples, -1, gz, s, rr, nullptr, 0, &b4);
+        b4.rp = d_pr; b4.rpp = d_ppr; b4.rout1 = d_ro1; b4.rout2 = d_ro2; b4.img = d_img;
+        b4.inj_stride = sample_stride;
+        return stepn_impl(c, FDW_MODE_BACK4, d_f1, d_f0, d_v2, d_fo1, d_fo2, pp_twice, receiver_samples(d_samples, gz), b4, rr, s);
     }
     StepnBack fb;
     fb.lvl0 = d_lvl0; fb.lvl1 = d_lvl1;
-    FDW_TRY(stepn_impl(c, FDW_MODE_PLAIN_ALL, d_f1, d_f0, d_v2, d_fo1, d_fo2, 0, nullptr, -1, 0, s, rr, nullptr, 0, &fb));
+    FDW_TRY(stepn_impl(c, FDW_MODE_PLAIN_ALL, d_f1, d_f0, d_v2, d_fo1, d_fo2, 0, FwdView{}, fb, rr, s));
     StepnBack rb;
     rb.plev[0] = d_lvl0; rb.plev[1] = d_lvl1; rb.plev[2] = d_fo1; rb.plev[3] = d_fo2;
     rb.img = d_img;
     rb.inj_stride = sample_stride;
-    return stepn_impl(c, FDW_MODE_RECV, d_pr, d_ppr, d_v2, d_ro1, d_ro2, pp_twice, d_samples, -1, gz, s, rr, nullptr, 0, &rb);
+    return stepn_impl(c, FDW_MODE_RECV, d_pr, d_ppr, d_v2, d_ro1, d_ro2, pp_twice, receiver_samples(d_samples, gz), rb, rr, s);
 }
 
 extern "C" int fdw_dev_back4(fdw_ctx* c, const float* d_f1, const float* d_f0, float* d_fo1, float* d_fo2, float* d_lvl0, float* d_lvl1, const float* d_pr,
@@ -987,10 +1047,8 @@ extern "C" int fdw_dev_back4(fdw_ctx* c, const float* d_f1, const float* d_f0, f
     if (c->prm.dialect != FDW_DIALECT_RTM || c->h != kMaxFastHalfOrder || (size_t)c->nxl * c->pitch * sizeof(float) >= (1ull << 31))
         return fail(FDW_EINVAL, "back4: needs the RTM dialect, order 8 and fields below 2 GiB");
     if (!fdw_receivers_stepped(c)) return fail(FDW_EINVAL, "back4: receiver rows beyond the time-stepped rows are not covered by the pipelined passes");
-    RowRanges rr;
-    rr.r0 = r0; rr.r1 = r1; rr.r0b = r0b; rr.r1b = r1b; rr.xchunk = xchunk;
-    return back4(c, d_f1, d_f0, d_fo1, d_fo2, d_lvl0, d_lvl1, d_pr, d_ppr, d_ro1, d_ro2, d_v2, d_samples, sample_stride, gz, d_img, pp_twice, rr,
-                 pick_stream(c, stream));
+    return back4(c, d_f1, d_f0, d_fo1, d_fo2, d_lvl0, d_lvl1, d_pr, d_ppr, d_ro1, d_ro2, d_v2, d_samples, sample_stride, gz, d_img, pp_twice,
+                 RowRanges{r0, r1, r0b, r1b, xchunk}, pick_stream(c, stream));
 }
 
 // the backward loop's tier (back_loop; fdw_slabs_create asks the same of every rank)
@@ -1006,19 +1064,29 @@ extern "C" int fdw_dev_step2(fdw_ctx* c, const float* d_p, const float* d_pp, co
                              const float* d_srce_it, int sx, int sz, void* stream)
 {
     if (!c) return fail(FDW_EINVAL, "ctx is NULL");
-    return step2_impl(c, FDW_MODE_FWD, d_p, d_pp, d_v2, d_out1, d_out2, pp_twice, d_srce_it, d_srce_it ? sx : -1, sz, Step2Extra{}, pick_stream(c, stream));
+    return step2_impl(c, FDW_MODE_FWD, d_p, d_pp, d_v2, d_out1, d_out2, pp_twice, view_at(point_source(d_srce_it, sx, sz), 0, c->nx), BackExtra{}, pick_stream(c, stream));
 }
 
 // kPipeSteps (4) forward iterations in one pass of the wave-pipeline kernel on the given row ranges of a slab
 extern "C" int fdw_dev_step4(fdw_ctx* c, const float* d_p, const float* d_pp, const float* d_v2, float* d_out1, float* d_out2, int pp_twice,
                              const float* d_srce_it, int sx, int sz, int r0, int r1, int r0b, int r1b, int xchunk, void* stream)
 {
-    if (!c) return fail(FDW_EINVAL, "ctx is NULL");
-    if (c->h != kMaxFastHalfOrder || (size_t)c->nxl * c->pitch * sizeof(float) >= (1ull << 31))
-        return fail(FDW_EINVAL, "step4: needs order 8 and fields below 2 GiB");
-    RowRanges rr;
-    rr.r0 = r0; rr.r1 = r1; rr.r0b = r0b; rr.r1b = r1b; rr.xchunk = xchunk;
-    return stepn_impl(c, FDW_MODE_FWD, d_p, d_pp, d_v2, d_out1, d_out2, pp_twice, d_srce_it, d_srce_it ? sx : -1, sz, pick_stream(c, stream), rr);
+    // (fdw_dev_step4_rec without a gather is exactly this launch)
+    return fdw_dev_step4_rec(c, d_p, d_pp, d_v2, d_out1, d_out2, pp_twice, d_srce_it, sx, sz, r0, r1, r0b, r1b, xchunk, nullptr, 0, (hipStream_t)stream);
+}
+
+// The tiles a pipeline pass on the rows rr would launch and their classes, through stepn_impl's plan hook.  Nothing is launched.
+static float* const kPlanFake = reinterpret_cast<float*>(uintptr_t(1) << 20);      // never dereferenced: the plan hook returns before the launch
+static int step4_plan(fdw_ctx* c, int mode, const Forward& f, const RowRanges& rr, int* nblk, int* nstrip, unsigned char* cls, int cls_cap)
+{
+    StepnPlan plan;
+    g_plan = &plan;
+    const int rc = stepn_impl(c, mode, kPlanFake, kPlanFake + 1, kPlanFake + 2, kPlanFake + 3, kPlanFake + 4, 1, view_at(f, 0, c->nx), StepnBack{}, rr, nullptr);
+    g_plan = nullptr;
+    if (rc != FDW_OK) return rc;
+    *nblk = plan.nblk; *nstrip = plan.nstrip;
+    if (cls) std::copy(plan.cls.begin(), plan.cls.begin() + std::min<size_t>(plan.cls.size(), (size_t)std::max(cls_cap, 0)), cls);
+    return FDW_OK;
 }
 
 // Tests and probes: what fdw_dev_step4 (forward = 1: FWD with the source at (sx, sz), sx < 0 none; 0: PLAIN) would launch on these row ranges --
@@ -1028,18 +1096,8 @@ extern "C" int fdw_debug_step4_plan(fdw_ctx* c, int forward, int sx, int sz, int
 {
     if (!c || !nblk || !nstrip) return fail(FDW_EINVAL, "NULL argument");
     if (c->h != kMaxFastHalfOrder) return fail(FDW_EINVAL, "step4: needs order 8");
-    RowRanges rr;
-    rr.r0 = r0; rr.r1 = r1; rr.r0b = r0b; rr.r1b = r1b; rr.xchunk = xchunk;
-    StepnPlan plan;
-    float* const fake = reinterpret_cast<float*>(uintptr_t(1) << 20);      // never dereferenced: the plan hook returns before the launch
-    g_plan = &plan;
-    const int rc = stepn_impl(c, forward ? FDW_MODE_FWD : FDW_MODE_PLAIN, fake, fake + 1, fake + 2, fake + 3, fake + 4, 1, forward && sx >= 0 ? fake + 5 : nullptr,
-                              forward ? sx : -1, sz, nullptr, rr);
-    g_plan = nullptr;
-    if (rc != FDW_OK) return rc;
-    *nblk = plan.nblk; *nstrip = plan.nstrip;
-    if (cls) std::copy(plan.cls.begin(), plan.cls.begin() + std::min<size_t>(plan.cls.size(), (size_t)std::max(cls_cap, 0)), cls);
-    return FDW_OK;
+    const Forward f = point_source(forward && sx >= 0 ? kPlanFake + 5 : nullptr, sx, sz);      // (no samples: no source)
+    return step4_plan(c, forward ? FDW_MODE_FWD : FDW_MODE_PLAIN, f, RowRanges{r0, r1, r0b, r1b, xchunk}, nblk, nstrip, cls, cls_cap);
 }
 
 // The same for a pass of fdw_dev_line_steps (plain) with the line at depth sz: the tiles of the strip that holds the line run the full body.
@@ -1049,29 +1107,9 @@ extern "C" int fdw_debug_step4_plan_line(fdw_ctx* c, int sz, int r0, int r1, int
     if (!c || !nblk || !nstrip) return fail(FDW_EINVAL, "NULL argument");
     if (c->prm.dialect != FDW_DIALECT_RTM || !is_full_grid(c)) return fail(FDW_ESTATE, "step4 plan: line sources need a full-grid context of the RTM dialect");
     if (c->h != kMaxFastHalfOrder) return fail(FDW_EINVAL, "step4: needs order 8");
-    RowRanges rr;
-    rr.r0 = r0; rr.r1 = r1; rr.r0b = r0b; rr.r1b = r1b; rr.xchunk = xchunk;
-    StepnPlan plan;
-    float* const fake = reinterpret_cast<float*>(uintptr_t(1) << 20);      // never dereferenced: the plan hook returns before the launch
-    g_plan = &plan;
-    const int rc = stepn_impl(c, FDW_MODE_FWD, fake, fake + 1, fake + 2, fake + 3, fake + 4, 1, fake + 5, -1, sz, nullptr, rr, nullptr, 0, nullptr, nullptr, true);
-    g_plan = nullptr;
-    if (rc != FDW_OK) return rc;
-    *nblk = plan.nblk; *nstrip = plan.nstrip;
-    if (cls) std::copy(plan.cls.begin(), plan.cls.begin() + std::min<size_t>(plan.cls.size(), (size_t)std::max(cls_cap, 0)), cls);
-    return FDW_OK;
+    return step4_plan(c, FDW_MODE_FWD, line_source(kPlanFake + 5, sz), RowRanges{r0, r1, r0b, r1b, xchunk}, nblk, nstrip, cls, cls_cap);
 }
 
-// nsteps reference iterations (R:259-267) over four rotating buffers: kPipeSteps per pass through the wave pipeline, pairs of steps through
-// the two-step kernel, single steps through the one-step kernel, whichever pays.  On entry buf[*ip], buf[*ipp] are the reference's (d_p, d_pp)
-// BEFORE the first swap; on return they index (d_p, d_pp) after the loop.  d_rec: NULL, or the trace rows [it][nx] (fdw_dev_record_steps):
-// the same passes, each through its kernel's recording variant.  d_illum: NULL, or the source illumination (fdw_dev_illum_steps): the same
-// passes, each through its kernel's illumination variant.  Both (fdw_dev_record_illum_steps): pipeline passes and single steps through the
-// combined kernels; there is no combined two-step kernel (a pair becomes two single steps), and every family equals the one-step iteration
-// bit for bit.  line (fdw_dev_line_steps): d_srce holds the line-source gather [it][nx] instead of the wavelet, sx is unused; the same family
-// per pass, the same rotation, the same static rows, each pass through its kernel's line-source variant.  line with both d_rec and d_illum
-// (fdw_dev_line_record_illum_steps): every family has its combined kernel, the two-step one included, so every pass is one launch.  Inside a
-// batch (c->nbatch > 1, one-step passes only) d_srce is the batch's [shot][nt][nx] and step_impl strides it per shot.
 // Trace samples of iterations it0 .. it0+nsteps-1 on the receiver rows the loop never time-steps (rows >= xlim of this slab): what the
 // reference's d_pp holds there, from the fields (d_p, d_pp) before the first swap
 static int record_static(fdw_ctx* c, const float* d_p, const float* d_pp, int gz, float* d_rec, int it0, int nsteps, hipStream_t s)
@@ -1183,8 +1221,8 @@ static int ensure_band_streams(fdw_ctx* c, int depth)
 // of fdw_plan_pass_bands: unit i on stream i mod D behind the events of the units the plan names.  Fork: every side stream starts behind
 // an event recorded on s here.  Join: s waits for the last unit of every side stream, whatever happened in between.  *ip, *ipp advance
 // over the passes issued.
-static int band_passes(fdw_ctx* c, float* const* buf, const float* d_v2, const float* d_srce, int sx, int sz, int it0, int npasses, int first_pp_twice,
-                       int* ip, int* ipp, hipStream_t s, int G, int D, int xchunk)
+static int band_passes(fdw_ctx* c, float* const* buf, const float* d_v2, const Forward& f, int it0, int npasses, int first_pp_twice, int* ip, int* ipp,
+                       hipStream_t s, int G, int D, int xchunk)
 {
     std::vector<fdw_band_unit> units((size_t)G * npasses);
     int g_ = 0, d_ = 0;
@@ -1207,8 +1245,8 @@ static int band_passes(fdw_ctx* c, float* const* buf, const float* d_v2, const f
             if (u.band == 0) spare_pair(*ip, *ipp, &o1, &o2);
             const int k = u.pass * kPipeSteps;
             for (int w = 0; w < u.nwait; w++) HIP_TRY(hipStreamWaitEvent(st[u.stream], c->pb_ring[u.wait[w] % kBandRing], 0));
-            FDW_TRY(stepn_impl(c, FDW_MODE_FWD, buf[*ipp], buf[*ip], d_v2, buf[o1], buf[o2], (k > 0) || first_pp_twice,
-                                d_srce ? d_srce + (size_t)(it0 + k) : nullptr, d_srce ? sx : -1, sz, st[u.stream], RowRanges{u.r0, u.r1, 0, 0, xchunk}));
+            FDW_TRY(stepn_impl(c, FDW_MODE_FWD, buf[*ipp], buf[*ip], d_v2, buf[o1], buf[o2], (k > 0) || first_pp_twice, view_at(f, it0 + k, c->nx), StepnBack{},
+                                RowRanges{u.r0, u.r1, 0, 0, xchunk}, st[u.stream]));
             if (D > 1 && i + D + 1 < total) HIP_TRY(hipEventRecord(c->pb_ring[i % kBandRing], st[u.stream]));      // someone will wait for it
             if (u.band == G - 1) { *ip = o1; *ipp = o2; }      // d_p = u^{n+kPipeSteps-1}, d_pp = u^{n+kPipeSteps}
         }
@@ -1227,28 +1265,41 @@ static int band_passes(fdw_ctx* c, float* const* buf, const float* d_v2, const f
     return rc != FDW_OK ? rc : jrc;
 }
 
-// xl (fdw_dev_excite_steps: the maps; fdw_dev_line_pick_steps, with line: the pick): the same family per pass as the plain loop, each pass
-// through its kernel's excitation variant -- except that there is no two-step excitation kernel: a pair becomes two single steps that land
-// where the pair's pass would (u^{n+1} in buf[o1], u^{n+2} in buf[o2], the current pair left as it is, each on a copy of the field it
-// overwrites): the same fields in all four buffers, the same indices and static rows as the plain loop.
-struct ExcLoop {
-    float* arr;      // amp (maps) or exc (pick)
-    int* texc;
-    int top;         // pick: iteration it takes the cells with texc == top - it
-    bool pick;
-};
+// A pass of m steps whose family has no kernel for the loop's extras (the two-step family: point-source recording + illumination, the
+// excitation maps and the pick) becomes m single steps that land where the pass would: u^{n+1} in buf[o1], u^{n+2} in buf[o2], the current
+// pair left as it is, each on a copy of the field it overwrites -- the same fields in all four buffers, the same indices and static rows
+// as the plain loop.  `it`: the iteration of the first step.
+static int single_steps_on_copies(fdw_ctx* c, float* const* buf, const float* d_v2, const Forward& f, int it, int m, int twice, int ip, int ipp, int o1,
+                                  int o2, hipStream_t s)
+{
+    const size_t bytes = field_elems(c) * sizeof(float) * (size_t)std::max(c->nbatch, 1);
+    const float* newest = buf[ipp];
+    for (int j = 0; j < m; j++) {
+        float* dst = buf[(j & 1) ? o2 : o1];
+        if (j < 2) HIP_TRY(hipMemcpyAsync(dst, buf[j == 0 ? ip : ipp], bytes, hipMemcpyDeviceToDevice, s));
+        FDW_TRY(step_impl(c, FDW_MODE_FWD, newest, dst, d_v2, 0, c->nxl, twice || j > 0, view_at(f, it + j, c->nx), BackExtra{}, s));
+        newest = dst;
+    }
+    return FDW_OK;
+}
 
-static int steps_loop(fdw_ctx* c, float* const* buf, const float* d_v2, const float* d_srce, int sx, int sz, int gz, float* d_rec, int it0, int nsteps,
-                      int first_pp_twice, int* ip, int* ipp, hipStream_t s, float* d_illum = nullptr, bool line = false, bool may_band = false,
-                      const ExcLoop* xl = nullptr)
+// nsteps reference iterations (R:259-267) over four rotating buffers: kPipeSteps per pass through the wave pipeline, pairs of steps through
+// the two-step kernel, single steps through the one-step kernel, whichever pays.  On entry buf[*ip], buf[*ipp] are the reference's (d_p, d_pp)
+// BEFORE the first swap; on return they index (d_p, d_pp) after the loop.  Whatever the loop does besides stepping (Forward: recording,
+// illumination, a line source, the excitation maps or pick): the same family per pass, the same rotation, the same static rows, each pass
+// through its kernel's variant (kFwdVariants), and every family equals the one-step iteration bit for bit.  Inside a batch (c->nbatch > 1,
+// one-step passes only) a line source's samples are the batch's [shot][nt][nx] and step_impl strides them per shot.
+static int steps_loop(fdw_ctx* c, float* const* buf, const float* d_v2, const Forward& f, int it0, int nsteps, int first_pp_twice, int* ip, int* ipp,
+                      hipStream_t s)
 {
     if (!c || !buf || !ip || !ipp) return fail(FDW_EINVAL, "NULL argument");
     if (*ip < 0 || *ip > 3 || *ipp < 0 || *ipp > 3 || *ip == *ipp) return fail(FDW_EINVAL, "steps2: bad buffer indices");
-    const size_t nxs = (size_t)c->nx;
-    if (d_rec) FDW_TRY(record_static(c, buf[*ip], buf[*ipp], gz, d_rec, it0, nsteps, s));
+    const FwdVariant var = fwd_variant(FDW_MODE_FWD, f);
+    if (var.kmode < 0) return fail(FDW_EINVAL, "steps: no kernel is built for this combination of a line source, recording, illumination and excitation");
+    if (f.rec) FDW_TRY(record_static(c, buf[*ip], buf[*ipp], f.gz, f.rec, it0, nsteps, s));
     int k = 0;
     c->pb_used_bands = c->pb_used_depth = 1;
-    if (may_band && !d_rec && !d_illum && !line && c->nbatch <= 1 && nsteps >= kPipeSteps && pipe_pays(c)) {
+    if (f.may_band && var.kmode == FDW_MODE_FWD && c->nbatch <= 1 && nsteps >= kPipeSteps && pipe_pays(c)) {
         // fdw_dev_steps2, the plain forward loop on caller-owned buffers: its pipeline passes may run as row bands (whole chunk rows of the pass's own chunk length: the same tiles)
         const int nstrip = pipe_strips(c), xchunk = pipe_fwd_xchunk(c, (long)c->upd_x1 * nstrip), npasses = nsteps / kPipeSteps;
         int G, D;
@@ -1256,74 +1307,32 @@ static int steps_loop(fdw_ctx* c, float* const* buf, const float* d_v2, const fl
         if (G > 1 && fdw_plan_pass_bands(c->nxl, c->upd_x1, xchunk, G, D, npasses, &G, &D, nullptr, 0) < 0) return FDW_EINVAL;
         if (G > 1) {
             c->pb_used_bands = G; c->pb_used_depth = D;
-            FDW_TRY(band_passes(c, buf, d_v2, d_srce, sx, sz, it0, npasses, first_pp_twice, ip, ipp, s, G, D, xchunk));
+            FDW_TRY(band_passes(c, buf, d_v2, f, it0, npasses, first_pp_twice, ip, ipp, s, G, D, xchunk));
             k = npasses * kPipeSteps;
         }
     }
     while (k < nsteps) {
         const int twice = (k > 0) || first_pp_twice;
-        const float* inj = d_srce ? d_srce + (size_t)(it0 + k) * (line ? nxs : 1) : nullptr;
-        const int sxx = d_srce ? sx : -1;
-        float* rec = d_rec ? d_rec + (size_t)(it0 + k) * nxs : nullptr;
+        const FwdView v = view_at(f, it0 + k, c->nx);
+        // the steps of this pass: the family that pays among those the steps left allow
+        const int m = (nsteps - k >= kPipeSteps && pipe_pays(c)) ? kPipeSteps : ((nsteps - k >= 2 && two_step_pays(c)) ? 2 : 1);
+        if (m == 1) {
+            std::swap(*ip, *ipp);
+            FDW_TRY(step_impl(c, FDW_MODE_FWD, buf[*ip], buf[*ipp], d_v2, 0, c->nxl, twice, v, BackExtra{}, s));
+            k += 1;
+            continue;
+        }
         int o1, o2;   // the two buffers not holding the current pair
         spare_pair(*ip, *ipp, &o1, &o2);
-        if (xl) {
-            const int m = (nsteps - k >= kPipeSteps && pipe_pays(c)) ? kPipeSteps : ((nsteps - k >= 2 && two_step_pays(c)) ? 2 : 1);
-            auto exc_step = [&](int j) { return ExcStep{xl->arr, xl->texc, xl->pick ? xl->top - (it0 + k + j) : it0 + k + j + 1, xl->pick}; };
-            if (m == kPipeSteps) {
-                const ExcStep xs = exc_step(0);
-                FDW_TRY(stepn_impl(c, FDW_MODE_FWD, buf[*ipp], buf[*ip], d_v2, buf[o1], buf[o2], twice, inj, sxx, sz, s, RowRanges{}, nullptr, 0, nullptr,
-                                    nullptr, line, &xs));
-                *ip = o1; *ipp = o2;
-            } else if (m == 1) {
-                std::swap(*ip, *ipp);
-                const ExcStep xs = exc_step(0);
-                FDW_TRY(step_impl(c, FDW_MODE_FWD, buf[*ip], buf[*ipp], d_v2, 0, c->nxl, twice, inj, sxx, sz, nullptr, nullptr, s, nullptr, 0, nullptr, nullptr,
-                                   nullptr, line, &xs));
-            } else {
-                const size_t bytes = field_elems(c) * sizeof(float);
-                const float* newest = buf[*ipp];
-                for (int j = 0; j < m; j++) {
-                    float* dst = buf[(j & 1) ? o2 : o1];
-                    if (j < 2) HIP_TRY(hipMemcpyAsync(dst, buf[j == 0 ? *ip : *ipp], bytes, hipMemcpyDeviceToDevice, s));
-                    const ExcStep xs = exc_step(j);
-                    FDW_TRY(step_impl(c, FDW_MODE_FWD, newest, dst, d_v2, 0, c->nxl, twice || j > 0, inj ? inj + (size_t)j * (line ? nxs : 1) : nullptr, sxx, sz,
-                                       nullptr, nullptr, s, nullptr, 0, nullptr, nullptr, nullptr, line, &xs));
-                    newest = dst;
-                }
-                *ip = o1; *ipp = o2;
-            }
-            k += m;
-        } else if (nsteps - k >= kPipeSteps && pipe_pays(c)) {
-            FDW_TRY(stepn_impl(c, FDW_MODE_FWD, buf[*ipp], buf[*ip], d_v2, buf[o1], buf[o2], twice, inj, sxx, sz, s, RowRanges{}, rec, gz, nullptr,
-                                d_illum, line));
-            *ip = o1; *ipp = o2;   // d_p = u^{n+kPipeSteps-1}, d_pp = u^{n+kPipeSteps}
-            k += kPipeSteps;
-        } else if (nsteps - k >= 2 && two_step_pays(c) && d_rec && d_illum && !line) {
-            // no combined two-step kernel: two single steps that land where the pair's pass would -- u^{n+1} in buf[o1], u^{n+2} in buf[o2],
-            // the current pair left as it is --, each on a copy of the field it overwrites; the same fields, indices and static rows
-            const size_t bytes = field_elems(c) * sizeof(float) * (size_t)std::max(c->nbatch, 1);
-            const float* newest = buf[*ipp];
-            for (int j = 0; j < 2; j++) {
-                float* dst = buf[j == 0 ? o1 : o2];
-                HIP_TRY(hipMemcpyAsync(dst, buf[j == 0 ? *ip : *ipp], bytes, hipMemcpyDeviceToDevice, s));
-                FDW_TRY(step_impl(c, FDW_MODE_FWD, newest, dst, d_v2, 0, c->nxl, twice || j > 0, inj ? inj + j : nullptr, sxx, sz, nullptr, nullptr, s,
-                                   rec + (size_t)j * nxs, gz, nullptr, nullptr, d_illum));
-                newest = dst;
-            }
-            *ip = o1; *ipp = o2;
-            k += 2;
-        } else if (nsteps - k >= 2 && two_step_pays(c)) {
-            // after the swap the kernel's p is the old d_pp (newest field), its pp the old d_p
-            FDW_TRY(step2_impl(c, FDW_MODE_FWD, buf[*ipp], buf[*ip], d_v2, buf[o1], buf[o2], twice, inj, sxx, sz, Step2Extra{}, s, rec, gz, d_illum, line));
-            *ip = o1; *ipp = o2;   // d_p = u^{n+1}, d_pp = u^{n+2}
-            k += 2;
-        } else {
-            std::swap(*ip, *ipp);
-            FDW_TRY(step_impl(c, FDW_MODE_FWD, buf[*ip], buf[*ipp], d_v2, 0, c->nxl, twice, inj, sxx, sz, nullptr, nullptr, s, rec, gz, nullptr, nullptr,
-                               d_illum, line));
-            k += 1;
-        }
+        // after the swap the kernel's p is the old d_pp (newest field), its pp the old d_p
+        if (!family_serves(m, var))
+            FDW_TRY(single_steps_on_copies(c, buf, d_v2, f, it0 + k, m, twice, *ip, *ipp, o1, o2, s));
+        else if (m == kPipeSteps)
+            FDW_TRY(stepn_impl(c, FDW_MODE_FWD, buf[*ipp], buf[*ip], d_v2, buf[o1], buf[o2], twice, v, StepnBack{}, RowRanges{}, s));
+        else
+            FDW_TRY(step2_impl(c, FDW_MODE_FWD, buf[*ipp], buf[*ip], d_v2, buf[o1], buf[o2], twice, v, BackExtra{}, s));
+        *ip = o1; *ipp = o2;   // d_p = u^{n+m-1}, d_pp = u^{n+m}
+        k += m;
     }
     return FDW_OK;
 }
@@ -1332,7 +1341,9 @@ extern "C" int fdw_dev_steps2(fdw_ctx* c, float* const* buf, const float* d_v2, 
                               int first_pp_twice, int* ip, int* ipp, void* stream)
 {
     if (!c) return fail(FDW_EINVAL, "NULL argument");
-    return steps_loop(c, buf, d_v2, d_srce, sx, sz, 0, nullptr, it0, nsteps, first_pp_twice, ip, ipp, pick_stream(c, stream), nullptr, false, true);
+    Forward f = point_source(d_srce, sx, sz);
+    f.may_band = true;
+    return steps_loop(c, buf, d_v2, f, it0, nsteps, first_pp_twice, ip, ipp, pick_stream(c, stream));
 }
 
 // the receiver column of a recorded gather: one the forward loop time-steps (R:83-87: j < zlim)
@@ -1349,7 +1360,8 @@ extern "C" int fdw_dev_record_steps(fdw_ctx* c, float* const* d_buf, const float
     if (!c || !d_rec) return fail(FDW_EINVAL, "NULL argument");
     if (it0 < 0) return fail(FDW_EINVAL, "it0=%d", it0);
     FDW_TRY(check_record_depth(c, gz));
-    return steps_loop(c, d_buf, d_v2, d_srce, sx, sz, gz, d_rec, it0, nsteps, first_pp_twice, ip, ipp, pick_stream(c, stream));
+    const Forward f = point_source(d_srce, sx, sz).recording(d_rec, gz);
+    return steps_loop(c, d_buf, d_v2, f, it0, nsteps, first_pp_twice, ip, ipp, pick_stream(c, stream));
 }
 
 // ---- what the slab driver's recording loop (fdw_slabs_dev_record_forward) launches: fdw_dev_step / fdw_dev_step4 on row ranges of the slab
@@ -1361,7 +1373,8 @@ int fdw_dev_step_rec(fdw_ctx* c, const float* d_p, float* d_pp, const float* d_v
                      float* d_rec_row, int gz, hipStream_t s)
 {
     if (!c) return fail(FDW_EINVAL, "ctx is NULL");
-    return step_impl(c, FDW_MODE_FWD, d_p, d_pp, d_v2, r0, r1, pp_twice, d_srce_it, d_srce_it ? sx : -1, sz, nullptr, nullptr, pick_stream(c, s), d_rec_row, gz);
+    return step_impl(c, FDW_MODE_FWD, d_p, d_pp, d_v2, r0, r1, pp_twice, view_at(point_source(d_srce_it, sx, sz).recording(d_rec_row, gz), 0, c->nx), BackExtra{},
+                     pick_stream(c, s));
 }
 
 int fdw_dev_step4_rec(fdw_ctx* c, const float* d_p, const float* d_pp, const float* d_v2, float* d_out1, float* d_out2, int pp_twice, const float* d_srce_it,
@@ -1370,9 +1383,8 @@ int fdw_dev_step4_rec(fdw_ctx* c, const float* d_p, const float* d_pp, const flo
     if (!c) return fail(FDW_EINVAL, "ctx is NULL");
     if (c->h != kMaxFastHalfOrder || (size_t)c->nxl * c->pitch * sizeof(float) >= (1ull << 31))
         return fail(FDW_EINVAL, "step4: needs order 8 and fields below 2 GiB");
-    RowRanges rr;
-    rr.r0 = r0; rr.r1 = r1; rr.r0b = r0b; rr.r1b = r1b; rr.xchunk = xchunk;
-    return stepn_impl(c, FDW_MODE_FWD, d_p, d_pp, d_v2, d_out1, d_out2, pp_twice, d_srce_it, d_srce_it ? sx : -1, sz, pick_stream(c, s), rr, d_rec, gz);
+    return stepn_impl(c, FDW_MODE_FWD, d_p, d_pp, d_v2, d_out1, d_out2, pp_twice, view_at(point_source(d_srce_it, sx, sz).recording(d_rec, gz), 0, c->nx), StepnBack{},
+                      RowRanges{r0, r1, r0b, r1b, xchunk}, pick_stream(c, s));
 }
 
 int fdw_dev_record_static(fdw_ctx* c, const float* d_p, const float* d_pp, int gz, float* d_rec, int it0, int nsteps, hipStream_t s)
@@ -1381,11 +1393,12 @@ int fdw_dev_record_static(fdw_ctx* c, const float* d_p, const float* d_pp, int g
     return record_static(c, d_p, d_pp, gz, d_rec, it0, nsteps, pick_stream(c, s));
 }
 
-// the forward loop with source illumination: the RTM dialect on the whole grid
-static int check_illum_ctx(const fdw_ctx* c, const char* who)
+// What source illumination, line sources, excitation-amplitude imaging, wavefield snapshots and residual migration (`what`) ask of the
+// context: the RTM dialect on the whole grid, one shot at a time
+static int check_single_shot_ctx(const fdw_ctx* c, const char* what, const char* who)
 {
-    if (c->prm.dialect != FDW_DIALECT_RTM) return fail(FDW_ESTATE, "%s: source illumination belongs to the RTM dialect", who);
-    if (!is_full_grid(c)) return fail(FDW_ESTATE, "%s: source illumination needs a full-grid context (slab-decomposed shots are not covered)", who);
+    if (c->prm.dialect != FDW_DIALECT_RTM) return fail(FDW_ESTATE, "%s: %s: RTM dialect only", who, what);
+    if (!is_full_grid(c)) return fail(FDW_ESTATE, "%s: %s: full-grid contexts only (slab-decomposed shots are not covered)", who, what);
     if (c->nbatch > 1) return fail(FDW_ESTATE, "%s: not inside a batch of shots", who);
     return FDW_OK;
 }
@@ -1395,8 +1408,9 @@ extern "C" int fdw_dev_illum_steps(fdw_ctx* c, float* const* d_buf, const float*
 {
     if (!c || !d_illum) return fail(FDW_EINVAL, "NULL argument");
     if (it0 < 0) return fail(FDW_EINVAL, "it0=%d", it0);
-    FDW_TRY(check_illum_ctx(c, "fdw_dev_illum_steps"));
-    return steps_loop(c, d_buf, d_v2, d_srce, sx, sz, 0, nullptr, it0, nsteps, first_pp_twice, ip, ipp, pick_stream(c, stream), d_illum);
+    FDW_TRY(check_single_shot_ctx(c, "source illumination", "fdw_dev_illum_steps"));
+    const Forward f = point_source(d_srce, sx, sz).illuminating(d_illum);
+    return steps_loop(c, d_buf, d_v2, f, it0, nsteps, first_pp_twice, ip, ipp, pick_stream(c, stream));
 }
 
 // the forward loop that records and accumulates in one launch per pass (the forward loop of fdw_shot_residual with an accumulator)
@@ -1407,20 +1421,14 @@ extern "C" int fdw_dev_record_illum_steps(fdw_ctx* c, float* const* d_buf, const
     if (!d_rec || !d_illum)
         return fail(FDW_EINVAL, "fdw_dev_record_illum_steps needs both d_rec and d_illum (one alone: fdw_dev_record_steps / fdw_dev_illum_steps)");
     if (it0 < 0) return fail(FDW_EINVAL, "it0=%d", it0);
-    FDW_TRY(check_illum_ctx(c, "fdw_dev_record_illum_steps"));
+    FDW_TRY(check_single_shot_ctx(c, "source illumination", "fdw_dev_record_illum_steps"));
     FDW_TRY(check_record_depth(c, gz));
-    return steps_loop(c, d_buf, d_v2, d_srce, sx, sz, gz, d_rec, it0, nsteps, first_pp_twice, ip, ipp, pick_stream(c, stream), d_illum);
+    const Forward f = point_source(d_srce, sx, sz).recording(d_rec, gz).illuminating(d_illum);
+    return steps_loop(c, d_buf, d_v2, f, it0, nsteps, first_pp_twice, ip, ipp, pick_stream(c, stream));
 }
 
 // ---- line sources (definitions in fdwave.h) ----
-// the RTM dialect on the whole grid, one shot at a time; then the depth of the line, and at most one of recording and illumination
-static int check_line_ctx(const fdw_ctx* c, const char* who)
-{
-    if (c->prm.dialect != FDW_DIALECT_RTM) return fail(FDW_ESTATE, "%s: line sources belong to the RTM dialect", who);
-    if (!is_full_grid(c)) return fail(FDW_ESTATE, "%s: line sources need a full-grid context (slab-decomposed shots are not covered)", who);
-    if (c->nbatch > 1) return fail(FDW_ESTATE, "%s: not inside a batch of shots", who);
-    return FDW_OK;
-}
+// the depth of the line, and recording and illumination together only where the caller runs the combined kernels
 static int check_line_args(const fdw_ctx* c, const char* who, int sz, int gz, bool rec, bool illum, bool both_built = false)
 {
     if (rec && illum && !both_built) return fail(FDW_EINVAL, "%s: trace recording and illumination together are not built for a line source", who);
@@ -1433,10 +1441,11 @@ extern "C" int fdw_dev_line_steps(fdw_ctx* c, float* const* d_buf, const float* 
                                   int it0, int nsteps, int first_pp_twice, int* ip, int* ipp, void* stream)
 {
     if (!c || !d_wav) return fail(FDW_EINVAL, "NULL argument");
-    FDW_TRY(check_line_ctx(c, "fdw_dev_line_steps"));
+    FDW_TRY(check_single_shot_ctx(c, "line sources", "fdw_dev_line_steps"));
     if (it0 < 0) return fail(FDW_EINVAL, "it0=%d", it0);
     FDW_TRY(check_line_args(c, "fdw_dev_line_steps", sz, gz, d_rec != nullptr, d_illum != nullptr));
-    return steps_loop(c, d_buf, d_v2, d_wav, -1, sz, d_rec ? gz : 0, d_rec, it0, nsteps, first_pp_twice, ip, ipp, pick_stream(c, stream), d_illum, true);
+    const Forward f = line_source(d_wav, sz).recording(d_rec, gz).illuminating(d_illum);
+    return steps_loop(c, d_buf, d_v2, f, it0, nsteps, first_pp_twice, ip, ipp, pick_stream(c, stream));
 }
 
 // fdw_dev_line_steps that writes the trace rows and accumulates, one launch per pass: every family's combined line-source kernel
@@ -1446,21 +1455,14 @@ extern "C" int fdw_dev_line_record_illum_steps(fdw_ctx* c, float* const* d_buf, 
     if (!c || !d_wav) return fail(FDW_EINVAL, "NULL argument");
     if (!d_rec || !d_illum)
         return fail(FDW_EINVAL, "fdw_dev_line_record_illum_steps needs both d_rec and d_illum (one alone or neither: fdw_dev_line_steps)");
-    FDW_TRY(check_line_ctx(c, "fdw_dev_line_record_illum_steps"));
+    FDW_TRY(check_single_shot_ctx(c, "line sources", "fdw_dev_line_record_illum_steps"));
     if (it0 < 0) return fail(FDW_EINVAL, "it0=%d", it0);
     FDW_TRY(check_line_args(c, "fdw_dev_line_record_illum_steps", sz, gz, true, true, true));
-    return steps_loop(c, d_buf, d_v2, d_wav, -1, sz, gz, d_rec, it0, nsteps, first_pp_twice, ip, ipp, pick_stream(c, stream), d_illum, true);
+    const Forward f = line_source(d_wav, sz).recording(d_rec, gz).illuminating(d_illum);
+    return steps_loop(c, d_buf, d_v2, f, it0, nsteps, first_pp_twice, ip, ipp, pick_stream(c, stream));
 }
 
 // ---- excitation-amplitude imaging (definitions in fdwave.h) ----
-// the RTM dialect on the whole grid, one shot at a time
-static int check_exc_ctx(const fdw_ctx* c, const char* who)
-{
-    if (c->prm.dialect != FDW_DIALECT_RTM) return fail(FDW_ESTATE, "%s: excitation-amplitude imaging belongs to the RTM dialect", who);
-    if (!is_full_grid(c)) return fail(FDW_ESTATE, "%s: excitation-amplitude imaging needs a full-grid context (slab-decomposed shots are not covered)", who);
-    if (c->nbatch > 1) return fail(FDW_ESTATE, "%s: not inside a batch of shots", who);
-    return FDW_OK;
-}
 // a point source the maps' forward loop can inject: a cell the loop time-steps
 static int check_exc_source(const fdw_ctx* c, const char* who, int sx, int sz)
 {
@@ -1473,24 +1475,24 @@ extern "C" int fdw_dev_excite_steps(fdw_ctx* c, float* const* d_buf, const float
                                     int it0, int nsteps, int first_pp_twice, int* ip, int* ipp, void* stream)
 {
     if (!c) return fail(FDW_EINVAL, "NULL argument");
-    FDW_TRY(check_exc_ctx(c, "fdw_dev_excite_steps"));
+    FDW_TRY(check_single_shot_ctx(c, "excitation-amplitude imaging", "fdw_dev_excite_steps"));
     if (!d_buf || !d_buf[0] || !d_buf[1] || !d_buf[2] || !d_buf[3] || !d_v2 || !d_amp || !d_texc || !ip || !ipp) return fail(FDW_EINVAL, "NULL argument");
     if (it0 < 0) return fail(FDW_EINVAL, "it0=%d", it0);
     if (d_srce && sx >= 0) FDW_TRY(check_exc_source(c, "fdw_dev_excite_steps", sx, sz));
-    const ExcLoop xl{d_amp, d_texc, 0, false};
-    return steps_loop(c, d_buf, d_v2, d_srce, sx, sz, 0, nullptr, it0, nsteps, first_pp_twice, ip, ipp, pick_stream(c, stream), nullptr, false, false, &xl);
+    const Forward f = point_source(d_srce, sx, sz).exciting(Exc::maps, d_amp, d_texc, 0);
+    return steps_loop(c, d_buf, d_v2, f, it0, nsteps, first_pp_twice, ip, ipp, pick_stream(c, stream));
 }
 
 extern "C" int fdw_dev_line_pick_steps(fdw_ctx* c, float* const* d_buf, const float* d_v2, const float* d_wav, int sz, const int* d_texc, int top,
                                        float* d_exc, int it0, int nsteps, int first_pp_twice, int* ip, int* ipp, void* stream)
 {
     if (!c) return fail(FDW_EINVAL, "NULL argument");
-    FDW_TRY(check_exc_ctx(c, "fdw_dev_line_pick_steps"));
+    FDW_TRY(check_single_shot_ctx(c, "excitation-amplitude imaging", "fdw_dev_line_pick_steps"));
     if (!d_buf || !d_buf[0] || !d_buf[1] || !d_buf[2] || !d_buf[3] || !d_v2 || !d_wav || !d_texc || !d_exc || !ip || !ipp) return fail(FDW_EINVAL, "NULL argument");
     if (it0 < 0) return fail(FDW_EINVAL, "it0=%d", it0);
     FDW_TRY(check_line_args(c, "fdw_dev_line_pick_steps", sz, 0, false, false));
-    const ExcLoop xl{d_exc, const_cast<int*>(d_texc), top, true};      // the pick only reads the map
-    return steps_loop(c, d_buf, d_v2, d_wav, -1, sz, 0, nullptr, it0, nsteps, first_pp_twice, ip, ipp, pick_stream(c, stream), nullptr, true, false, &xl);
+    const Forward f = line_source(d_wav, sz).exciting(Exc::pick, d_exc, const_cast<int*>(d_texc), top);      // the pick only reads the map
+    return steps_loop(c, d_buf, d_v2, f, it0, nsteps, first_pp_twice, ip, ipp, pick_stream(c, stream));
 }
 
 // d_out[i] = d_a[i] - d_b[i] (fdw_gather_residual_kernel); d_out may be d_a
@@ -1514,14 +1516,14 @@ extern "C" int fdw_dev_steps_shrink(fdw_ctx* c, float* d_p, float* d_pp, const f
 {
     if (!c) return fail(FDW_EINVAL, "ctx is NULL");
     hipStream_t s = pick_stream(c, stream);
+    const Forward f = point_source(d_srce, sx, sz);
     for (int k = 0; k < nsteps; k++) {
         std::swap(d_p, d_pp);  // R:260-262
         const int j = j0 + k;
         const int r0 = shrink_lo ? c->h * j : 0;
         const int r1 = c->nxl - (shrink_hi ? c->h * j : 0);
         if (r1 <= r0) return fail(FDW_EINVAL, "steps_shrink: slab exhausted at cycle step %d", j);
-        int rc = step_impl(c, FDW_MODE_FWD, d_p, d_pp, d_v2, r0, r1, (k > 0) || first_pp_twice, d_srce ? d_srce + it0 + k : nullptr,
-                           d_srce ? sx : -1, sz, nullptr, nullptr, s);
+        int rc = step_impl(c, FDW_MODE_FWD, d_p, d_pp, d_v2, r0, r1, (k > 0) || first_pp_twice, view_at(f, it0 + k, c->nx), BackExtra{}, s);
         if (rc) return rc;
     }
     return FDW_OK;
@@ -1628,7 +1630,7 @@ extern "C" int fdw_laplacian(fdw_ctx* c, const float* p, float* lap)
     int rc = ensure_work_buffers(c, 2, false);
     if (rc) return rc;
     if ((rc = upload_rows(c, c->fld[0], p, c->stream))) return rc;
-    if ((rc = step_impl(c, FDW_MODE_LAP, c->fld[0], c->fld[1], nullptr, 0, c->nxl, 0, nullptr, -1, 0, nullptr, nullptr, c->stream))) return rc;
+    if ((rc = step_impl(c, FDW_MODE_LAP, c->fld[0], c->fld[1], nullptr, 0, c->nxl, 0, FwdView{}, BackExtra{}, c->stream))) return rc;
     if ((rc = download_rows(c, lap, c->fld[1], c->stream))) return rc;
     HIP_TRY(hipStreamSynchronize(c->stream));
     return FDW_OK;
@@ -1659,23 +1661,21 @@ static int upload_source(fdw_ctx* c, const float* srce, int n)
     return FDW_OK;
 }
 
-// fd_forward's loop body R:259-267 for nsteps iterations over the context's four field buffers (pairs of steps go
-// through the two-step kernel where it pays); *ip / *ipp index (d_p, d_pp) before the loop and after it.  d_rec: trace rows [nt][nx] at gz.
-// sn (fdw_shot_snaps): the loop runs in segments that end on the snapshot levels L = every, 2 every, ... (a loop cut at any iteration equals the
+// fd_forward's loop body R:259-267 for nsteps iterations over the context's four field buffers (pairs of steps go through the two-step kernel
+// where it pays); *ip / *ipp index (d_p, d_pp) before the loop and after it.  f: the loop's source and extras.  sn (fdw_shot_snaps;
+// SnapPlan{}: none): the loop runs in segments that end on the snapshot levels L = every, 2 every, ... (a loop cut at any iteration equals the
 // uncut one bit for bit: it0 and the owed-taper flag carry over), and after each the frame of d_pp = u^L goes into the frame store.
-static int forward_loop(fdw_ctx* c, int* ip, int* ipp, int sx, int sz, int nsteps, int gz = 0, float* d_rec = nullptr, float* d_illum = nullptr,
-                        const SnapPlan* sn = nullptr, bool line = false)
+static int forward_loop(fdw_ctx* c, int* ip, int* ipp, const Forward& f, int nsteps, const SnapPlan& sn)
 {
-    const float* d_samples = line ? c->d_wav : c->d_srce;      // line: the gather fdw_shot_line uploaded, [nt][nx]
     FDW_RANGE("fdw: forward loop (fd_forward)");
     int it = 0;
-    for (int j = 0; sn && sn->store[0] && j < sn->nframes; j++) {
-        const int level = (j + 1) * sn->every;
-        FDW_TRY(steps_loop(c, c->fld, c->d_v2, d_samples, sx, sz, gz, d_rec, it, level - it, it > 0, ip, ipp, c->stream, d_illum, line));
-        FDW_TRY(snapshot(c, c->fld[*ipp], sn->dec, sn->store[0] + (size_t)j * sn->frame_elems(), c->stream));
+    for (int j = 0; sn.store[0] && j < sn.nframes; j++) {
+        const int level = (j + 1) * sn.every;
+        FDW_TRY(steps_loop(c, c->fld, c->d_v2, f, it, level - it, it > 0, ip, ipp, c->stream));
+        FDW_TRY(snapshot(c, c->fld[*ipp], sn.dec, sn.store[0] + (size_t)j * sn.frame_elems(), c->stream));
         it = level;
     }
-    int rc = steps_loop(c, c->fld, c->d_v2, d_samples, sx, sz, gz, d_rec, it, nsteps - it, it > 0, ip, ipp, c->stream, d_illum, line);
+    int rc = steps_loop(c, c->fld, c->d_v2, f, it, nsteps - it, it > 0, ip, ipp, c->stream);
     if (rc) return rc;
     if (nsteps > 0) return fdw_dev_taper_finalize(c, c->fld[*ip], c->stream);   // the T() d_p still owes (R:285 downloads the damped d_p)
     return FDW_OK;
@@ -1694,7 +1694,7 @@ extern "C" int fdw_forward(fdw_ctx* c, float* p, float* pp, const float* v2, int
     if ((rc = upload_rows(c, c->fld[0], p, c->stream)) || (rc = upload_rows(c, c->fld[1], pp, c->stream)) ||
         (rc = upload_rows(c, c->d_v2, v2, c->stream)) || (rc = upload_source(c, srce, nsteps)))
         return rc;
-    if ((rc = forward_loop(c, &ip, &ipp, sx, sz, nsteps))) return rc;
+    if ((rc = forward_loop(c, &ip, &ipp, point_source(c->d_srce, sx, sz), nsteps, SnapPlan{}))) return rc;
     if ((rc = download_rows(c, p, c->fld[ip], c->stream)) || (rc = download_rows(c, pp, c->fld[ipp], c->stream))) return rc;
     HIP_TRY(hipStreamSynchronize(c->stream));
     return FDW_OK;
@@ -1726,18 +1726,17 @@ static int upload_line_source(fdw_ctx* c, const float* wav)
     return gathers_to_device(c, wav, c->d_wav, 1);
 }
 
-static int image_to_device(fdw_ctx* c, const float* imloc, float* d_dst = nullptr)
+static int image_to_device(fdw_ctx* c, const float* imloc, float* d_dst)
 {
-    if (!d_dst) d_dst = c->d_img;
     HIP_TRY(hipMemsetAsync(d_dst, 0, field_elems(c) * sizeof(float), c->stream));
     float* dst = d_dst + (size_t)c->prm.nxb * c->pitch + c->prm.nzb;
     HIP_TRY(hipMemcpy2DAsync(dst, (size_t)c->pitch * sizeof(float), imloc, (size_t)c->nz * sizeof(float),
                              (size_t)c->nz * sizeof(float), c->nx, hipMemcpyHostToDevice, c->stream));
     return FDW_OK;
 }
-static int image_to_host(fdw_ctx* c, float* imloc, const float* d_src = nullptr)
+static int image_to_host(fdw_ctx* c, float* imloc, const float* d_src)
 {
-    const float* src = (d_src ? d_src : c->d_img) + (size_t)c->prm.nxb * c->pitch + c->prm.nzb;
+    const float* src = d_src + (size_t)c->prm.nxb * c->pitch + c->prm.nzb;
     HIP_TRY(hipMemcpy2DAsync(imloc, (size_t)c->nz * sizeof(float), src, (size_t)c->pitch * sizeof(float),
                              (size_t)c->nz * sizeof(float), c->nx, hipMemcpyDeviceToHost, c->stream));
     return FDW_OK;
@@ -1752,10 +1751,10 @@ static int image_to_host(fdw_ctx* c, float* imloc, const float* d_src = nullptr)
 // pass reconstructs F_k, F_{k+1}; one pass advances the receiver field twice and applies both imaging conditions), singly through the
 // one-step kernels otherwise (back_iter).  src[0..3] / rcv[0..3]: rotating buffers; on entry src[0] = snap0, src[1] = snap1, the receivers
 // are zero.
-// sn (fdw_shot_snaps): iterations k = nt - L of the snapshot levels L are STOPS: no pass of several iterations reaches across one (the
+// sn (fdw_shot_snaps; SnapPlan{}: none): iterations k = nt - L of the snapshot levels L are STOPS: no pass of several iterations reaches across one (the
 // family is chosen by the iterations left until the next stop; every family equals the one-step iteration bit for bit, so the image
 // does not change), and after iteration k the frames of F_k and r^{k+1} go into the frame stores at index L / every - 1.
-static int back_loop(fdw_ctx* c, float* const src[4], float* const rcv[4], int gz, int nsteps, const SnapPlan* sn = nullptr)
+static int back_loop(fdw_ctx* c, float* const src[4], float* const rcv[4], int gz, int nsteps, const SnapPlan& sn)
 {
     FDW_RANGE("fdw: backward loop + imaging (fd_back)");
     const int nt = c->prm.nt;
@@ -1767,9 +1766,9 @@ static int back_loop(fdw_ctx* c, float* const src[4], float* const rcv[4], int g
     const bool pairs = two_step_pays(c);
     const bool pipe = fdw_back_pipe_active(c) && c->nbatch <= 1;
     std::vector<int> stops;      // ascending iterations after which frames are taken
-    if (sn && (sn->store[1] || sn->store[2]))
-        for (int j = sn->nframes - 1; j >= 0; j--)
-            if (nt - (j + 1) * sn->every < nsteps) stops.push_back(nt - (j + 1) * sn->every);
+    if (sn.store[1] || sn.store[2])
+        for (int j = sn.nframes - 1; j >= 0; j--)
+            if (nt - (j + 1) * sn.every < nsteps) stops.push_back(nt - (j + 1) * sn.every);
     size_t next = 0;             // stops[next] = the first stop not yet passed
     if (pipe && c->no_back_fused && nsteps >= 2 + kPipeSteps) {      // the two-pass form keeps two levels in memory
         FDW_TRY(alloc_zero(&c->fld[8], field_elems(c)));
@@ -1794,15 +1793,15 @@ static int back_loop(fdw_ctx* c, float* const src[4], float* const rcv[4], int g
             } else {
                 int o1, o2;
                 spare_pair(f1, f0, &o1, &o2);
-                FDW_TRY(step2_impl(c, FDW_MODE_PLAIN, src[f1], src[f0], c->d_v2, src[o1], src[o2], 0, nullptr, -1, 0, Step2Extra{}, c->stream));
+                FDW_TRY(step2_impl(c, FDW_MODE_PLAIN, src[f1], src[f0], c->d_v2, src[o1], src[o2], 0, FwdView{}, BackExtra{}, c->stream));
                 Fa = src[o1]; Fb = src[o2];
                 f0 = o1; f1 = o2;
             }
             int q1, q2;
             spare_pair(rn, ro, &q1, &q2);
-            Step2Extra ex;
+            BackExtra ex;
             ex.inj2 = samples(it + 1); ex.psrc_a = Fa; ex.psrc_b = Fb; ex.img = c->d_img;
-            FDW_TRY(step2_impl(c, FDW_MODE_RECV, rcv[rn], rcv[ro], c->d_v2, rcv[q1], rcv[q2], it > 0, samples(it), -1, gz, ex, c->stream));
+            FDW_TRY(step2_impl(c, FDW_MODE_RECV, rcv[rn], rcv[ro], c->d_v2, rcv[q1], rcv[q2], it > 0, receiver_samples(samples(it), gz), ex, c->stream));
             ro = q1; rn = q2;
             it += 2;
         } else {
@@ -1816,9 +1815,9 @@ static int back_loop(fdw_ctx* c, float* const src[4], float* const rcv[4], int g
         if (next < stops.size() && it == stops[next] + 1) {
             // F_k: u^nt (src[1]) at k = 0, then the newer of the source pair (k = 1: the handed-over P in src[0]); r^{k+1}: the newer receiver field
             const int k = stops[next++];
-            const size_t off = (size_t)((nt - k) / sn->every - 1) * sn->frame_elems();
-            if (sn->store[1]) FDW_TRY(snapshot(c, k == 0 ? src[1] : src[f1], sn->dec, sn->store[1] + off, c->stream));
-            if (sn->store[2]) FDW_TRY(snapshot(c, rcv[rn], sn->dec, sn->store[2] + off, c->stream));
+            const size_t off = (size_t)((nt - k) / sn.every - 1) * sn.frame_elems();
+            if (sn.store[1]) FDW_TRY(snapshot(c, k == 0 ? src[1] : src[f1], sn.dec, sn.store[1] + off, c->stream));
+            if (sn.store[2]) FDW_TRY(snapshot(c, rcv[rn], sn.dec, sn.store[2] + off, c->stream));
         }
     }
     return FDW_OK;
@@ -1849,29 +1848,40 @@ extern "C" int fdw_back(fdw_ctx* c, const float* v2, const float* snap0, const f
     HIP_TRY(hipSetDevice(c->device));
     int rc;
     if ((rc = ensure_work_buffers(c, 8, true))) return rc;
-    if ((rc = upload_rows(c, c->d_v2, v2, c->stream)) || (rc = upload_gather(c, d_obs)) || (rc = image_to_device(c, imloc))) return rc;
+    if ((rc = upload_rows(c, c->d_v2, v2, c->stream)) || (rc = upload_gather(c, d_obs)) || (rc = image_to_device(c, imloc, c->d_img))) return rc;
     // the reference uploads the two snapshots into d_pp at it = 0 and 1 (R:304-314); having both on the device up front is the same
     if ((rc = upload_rows(c, c->fld[0], snap0, c->stream)) || (rc = upload_rows(c, c->fld[1], snap1, c->stream))) return rc;
     if ((rc = zero_fields(c, c->fld + 4, 2))) return rc;             // R:513-514
-    if ((rc = back_loop(c, c->fld, c->fld + 4, gz, nsteps))) return rc;
-    if ((rc = image_to_host(c, imloc))) return rc;
+    if ((rc = back_loop(c, c->fld, c->fld + 4, gz, nsteps, SnapPlan{}))) return rc;
+    if ((rc = image_to_host(c, imloc, c->d_img))) return rc;
     HIP_TRY(hipStreamSynchronize(c->stream));
     return FDW_OK;
 }
 
 static int gathers_to_host(fdw_ctx* c, const float* d_rec, int nshots, float* data);
 
-// v2 == nullptr: the squared model already resident in c->d_v2 (fdw_dev_extendvel_linear)
-// illum: NULL, or the interior illumination [nx][nz] the forward loop accumulates into (fdw_shot_illum)
-// sn: NULL, or the snapshot plan of fdw_shot_snaps (frame stores already allocated)
-// residual (fdw_shot_residual): the forward loop records the modelled gather into c->d_rec, c->d_dobs becomes d_obs - d_mod in place before the
-// backward loop reads it; resid: NULL, or [nx][nt] that difference
-// wav (fdw_shot_line): NULL, or the line-source gather [nx][nt] that drives the forward loop in place of (sx, srce)
-static int shot_impl(fdw_ctx* c, const float* v2, int sx, int sz, int gz, const float* srce, const float* d_obs, float* imloc, float* P, float* PP,
-                     float* illum = nullptr, const SnapPlan* sn = nullptr, bool residual = false, float* resid = nullptr, const float* wav = nullptr)
+// The squared model of a call is the caller's v2 or (v2 == NULL) the resident one (fdw_dev_extendvel_linear); a caller's v2 ends the residency
+// once the entry point has accepted its arguments.
+static int has_model(const fdw_ctx* c, const float* v2) { return v2 || c->v2_resident ? FDW_OK : fail(FDW_ESTATE, "no resident squared model: call fdw_dev_extendvel_linear first"); }
+static void end_residency(fdw_ctx* c, const float* v2) { if (v2) c->v2_resident = false; }
+
+struct ShotExtras {      // what a shot does beyond fdw_shot's; of a batch every array is [nshots][...]
+    bool line = false;         // fdw_shot_line: `samples` is the line-source gather [nx][nt] on column sz in place of the wavelet [nt]; sx is unused
+    float* illum = nullptr;    // the interior illumination [nx][nz] the forward loop accumulates into (fdw_shot_illum)
+    SnapPlan snaps;            // one shot: the snapshot plan of fdw_shot_snaps (frame stores already allocated)
+    bool residual = false;     // fdw_shot_residual: the forward loop records the modelled gather (c->d_rec; a batch: b_rec [shot][nt][nx]), which turns
+    float* resid = nullptr;    // the data gather into d_obs - d_mod in place before the backward loop reads it; resid: NULL, or [nx][nt] that difference
+    ShotExtras of_shot(size_t b, size_t ni, size_t ng) const { ShotExtras x = *this; if (illum) x.illum += b * ni; if (resid) x.resid += b * ng; return x; }
+};
+// the uploaded source as the forward loop takes it: the wavelet in c->d_srce, or (line) the gathers transposed to [shot][nt][nx] in d_wav
+static Forward device_source(const fdw_ctx* c, bool line, int sx, int sz, const float* d_wav) { return line ? line_source(d_wav, sz) : point_source(c->d_srce, sx, sz); }
+
+// v2 == nullptr: the squared model already resident in c->d_v2
+static int shot_impl(fdw_ctx* c, const float* v2, int sx, int sz, int gz, const float* samples, const float* d_obs, float* imloc, float* P, float* PP,
+                     const ShotExtras& x)
 {
-    if (!c || (!srce && !wav) || !d_obs || !imloc) return fail(FDW_EINVAL, "NULL argument");
-    if (residual) FDW_TRY(check_record_depth(c, gz));
+    if (!c || !samples || !d_obs || !imloc) return fail(FDW_EINVAL, "NULL argument");
+    if (x.residual) FDW_TRY(check_record_depth(c, gz));
     FDW_RANGE("fdw: shot (uploads, forward, backward, image download)");
     if (!is_full_grid(c)) return fail(FDW_EINVAL, "fdw_shot needs a full-grid context");
     if (c->nx <= 0 || c->nz <= 0) return fail(FDW_EINVAL, "no interior to image");
@@ -1882,25 +1892,25 @@ static int shot_impl(fdw_ctx* c, const float* v2, int sx, int sz, int gz, const 
     int ip = 0, ipp = 1;
     HIP_TRY(hipMemsetAsync(c->fld[0], 0, field_elems(c) * sizeof(float), c->stream));    // R:496-497
     HIP_TRY(hipMemsetAsync(c->fld[1], 0, field_elems(c) * sizeof(float), c->stream));
-    if ((v2 && (rc = upload_rows(c, c->d_v2, v2, c->stream))) || (rc = wav ? upload_line_source(c, wav) : upload_source(c, srce, nt)) ||
-        (rc = upload_gather(c, d_obs)) || (rc = image_to_device(c, imloc)))
+    if ((v2 && (rc = upload_rows(c, c->d_v2, v2, c->stream))) || (rc = x.line ? upload_line_source(c, samples) : upload_source(c, samples, nt)) ||
+        (rc = upload_gather(c, d_obs)) || (rc = image_to_device(c, imloc, c->d_img)))
         return rc;
-    if (illum && ((rc = alloc_zero(&c->d_illum, field_elems(c))) || (rc = image_to_device(c, illum, c->d_illum)))) return rc;
-    if (residual && (rc = ensure_cap(&c->d_rec, &c->rec_cap, (size_t)c->nx * nt))) return rc;
-    if ((rc = forward_loop(c, &ip, &ipp, sx, sz, nt, residual ? gz : 0, residual ? c->d_rec : nullptr, illum ? c->d_illum : nullptr, sn, wav != nullptr)))
-        return rc;
-    if (residual) {      // both [nt][nx] in forward time: the backward loop's sample indexing stays as it is
+    if (x.illum && ((rc = alloc_zero(&c->d_illum, field_elems(c))) || (rc = image_to_device(c, x.illum, c->d_illum)))) return rc;
+    if (x.residual && (rc = ensure_cap(&c->d_rec, &c->rec_cap, (size_t)c->nx * nt))) return rc;
+    const Forward f = device_source(c, x.line, sx, sz, c->d_wav).recording(x.residual ? c->d_rec : nullptr, gz).illuminating(x.illum ? c->d_illum : nullptr);
+    if ((rc = forward_loop(c, &ip, &ipp, f, nt, x.snaps))) return rc;
+    if (x.residual) {      // both [nt][nx] in forward time: the backward loop's sample indexing stays as it is
         if ((rc = gather_residual(c->d_dobs, c->d_rec, c->d_dobs, (size_t)c->nx * nt, c->stream))) return rc;
-        if (resid && (rc = gathers_to_host(c, c->d_dobs, 1, resid))) return rc;
+        if (x.resid && (rc = gathers_to_host(c, c->d_dobs, 1, x.resid))) return rc;
     }
-    if (illum && (rc = image_to_host(c, illum, c->d_illum))) return rc;
+    if (x.illum && (rc = image_to_host(c, x.illum, c->d_illum))) return rc;
     if (P && (rc = download_rows(c, P, c->fld[ip], c->stream))) return rc;
     if (PP && (rc = download_rows(c, PP, c->fld[ipp], c->stream))) return rc;
     float* src[4];
     source_buffers(c, ip, ipp, src);
     if ((rc = zero_fields(c, c->fld + 4, 2))) return rc;
-    if ((rc = back_loop(c, src, c->fld + 4, gz, nt, sn))) return rc;
-    if ((rc = image_to_host(c, imloc))) return rc;
+    if ((rc = back_loop(c, src, c->fld + 4, gz, nt, x.snaps))) return rc;
+    if ((rc = image_to_host(c, imloc, c->d_img))) return rc;
     HIP_TRY(hipStreamSynchronize(c->stream));
     return FDW_OK;
 }
@@ -1910,16 +1920,18 @@ extern "C" int fdw_shot(fdw_ctx* c, const float* v2, int sx, int sz, int gz, con
 {
     if (!v2) return fail(FDW_EINVAL, "NULL argument");
     if (c) c->v2_resident = false;
-    return shot_impl(c, v2, sx, sz, gz, srce, d_obs, imloc, P, PP);
+    return shot_impl(c, v2, sx, sz, gz, srce, d_obs, imloc, P, PP, ShotExtras{});
 }
 
 extern "C" int fdw_shot_illum(fdw_ctx* c, const float* v2, int sx, int sz, int gz, const float* srce, const float* d_obs, float* imloc,
                               float* illum, float* P, float* PP)
 {
     if (!c || !v2 || !illum) return fail(FDW_EINVAL, "NULL argument");
-    FDW_TRY(check_illum_ctx(c, "fdw_shot_illum"));
+    FDW_TRY(check_single_shot_ctx(c, "source illumination", "fdw_shot_illum"));
     c->v2_resident = false;
-    return shot_impl(c, v2, sx, sz, gz, srce, d_obs, imloc, P, PP, illum);
+    ShotExtras x;
+    x.illum = illum;
+    return shot_impl(c, v2, sx, sz, gz, srce, d_obs, imloc, P, PP, x);
 }
 
 // ---- wavefield snapshots ----
@@ -1933,19 +1945,11 @@ extern "C" int fdw_snap_dims(int nx, int nz, int nt, int every, int dec, int* nf
     return FDW_OK;
 }
 
-static int check_snaps_ctx(const fdw_ctx* c, const char* who)
-{
-    if (c->prm.dialect != FDW_DIALECT_RTM) return fail(FDW_ESTATE, "%s: wavefield snapshots belong to the RTM dialect", who);
-    if (!is_full_grid(c)) return fail(FDW_ESTATE, "%s: wavefield snapshots need a full-grid context (slab-decomposed shots are not covered)", who);
-    if (c->nbatch > 1) return fail(FDW_ESTATE, "%s: not inside a batch of shots", who);
-    return FDW_OK;
-}
-
 extern "C" int fdw_dev_snapshot(fdw_ctx* c, const float* d_field, int dec, float* d_frame, void* stream)
 {
     if (!c || !d_field || !d_frame) return fail(FDW_EINVAL, "NULL argument");
     if (dec < 1) return fail(FDW_EINVAL, "snapshot: dec=%d must be >= 1", dec);
-    FDW_TRY(check_snaps_ctx(c, "fdw_dev_snapshot"));
+    FDW_TRY(check_single_shot_ctx(c, "wavefield snapshots", "fdw_dev_snapshot"));
     if (c->nx <= 0 || c->nz <= 0) return fail(FDW_EINVAL, "no interior to take a frame of");
     return snapshot(c, d_field, dec, d_frame, pick_stream(c, stream));
 }
@@ -1959,8 +1963,8 @@ extern "C" int fdw_shot_snaps(fdw_ctx* c, const float* v2, int sx, int sz, int g
     SnapPlan plan;
     plan.every = snaps->every; plan.dec = snaps->dec;
     FDW_TRY(fdw_snap_dims(c->nx, c->nz, c->prm.nt, snaps->every, snaps->dec, &plan.nframes, &plan.nxs, &plan.nzs));
-    FDW_TRY(check_snaps_ctx(c, "fdw_shot_snaps"));
-    if (!v2 && !c->v2_resident) return fail(FDW_ESTATE, "no resident squared model: call fdw_dev_extendvel_linear first");
+    FDW_TRY(check_single_shot_ctx(c, "wavefield snapshots", "fdw_shot_snaps"));
+    FDW_TRY(has_model(c, v2));
     if (!srce || !d_obs || !imloc) return fail(FDW_EINVAL, "NULL argument");
     if (c->nx <= 0 || c->nz <= 0) return fail(FDW_EINVAL, "no interior to image");
     HIP_TRY(hipSetDevice(c->device));
@@ -1979,8 +1983,10 @@ extern "C" int fdw_shot_snaps(fdw_ctx* c, const float* v2, int sx, int sz, int g
         }
         plan.store[i] = c->d_snap[i];
     }
-    if (v2) c->v2_resident = false;
-    FDW_TRY(shot_impl(c, v2, sx, sz, gz, srce, d_obs, imloc, P, PP, illum, &plan));
+    end_residency(c, v2);
+    ShotExtras x;
+    x.illum = illum; x.snaps = plan;
+    FDW_TRY(shot_impl(c, v2, sx, sz, gz, srce, d_obs, imloc, P, PP, x));
     // one download per set (shot_impl has synchronised: the copies below are the only work left on the stream)
     for (int i = 0; i < 3; i++)
         if (plan.store[i]) HIP_TRY(hipMemcpyAsync(host[i], plan.store[i], set_elems * sizeof(float), hipMemcpyDeviceToHost, c->stream));
@@ -2005,9 +2011,9 @@ static int gathers_to_host(fdw_ctx* c, const float* d_rec, int nshots, float* da
 
 // fd_forward from rest (R:496-497, R:259-267) recording data[ix][it] = d_pp(nxb + ix, gz) at the end of iteration it.  v2 == nullptr: the
 // squared model already resident in c->d_v2 (fdw_dev_extendvel_linear).
-static int record_impl(fdw_ctx* c, const float* v2, int sx, int sz, int gz, const float* srce, float* data, float* P, float* PP, const float* wav = nullptr)
+static int record_impl(fdw_ctx* c, const float* v2, int sx, int sz, int gz, const float* samples, float* data, float* P, float* PP, bool line)
 {
-    if (!c || (!srce && !wav) || !data) return fail(FDW_EINVAL, "NULL argument");
+    if (!c || !samples || !data) return fail(FDW_EINVAL, "NULL argument");
     FDW_TRY(check_record_depth(c, gz));
     if (!is_full_grid(c)) return fail(FDW_EINVAL, "fdw_record_shot needs a full-grid context");
     if (c->nx <= 0) return fail(FDW_EINVAL, "no receiver rows");
@@ -2018,9 +2024,9 @@ static int record_impl(fdw_ctx* c, const float* v2, int sx, int sz, int gz, cons
     HIP_TRY(hipMemsetAsync(c->fld[0], 0, field_elems(c) * sizeof(float), c->stream));
     HIP_TRY(hipMemsetAsync(c->fld[1], 0, field_elems(c) * sizeof(float), c->stream));
     if (v2) FDW_TRY(upload_rows(c, c->d_v2, v2, c->stream));
-    FDW_TRY(wav ? upload_line_source(c, wav) : upload_source(c, srce, nt));
+    FDW_TRY(line ? upload_line_source(c, samples) : upload_source(c, samples, nt));
     int ip = 0, ipp = 1;
-    FDW_TRY(forward_loop(c, &ip, &ipp, sx, sz, nt, gz, c->d_rec, nullptr, nullptr, wav != nullptr));
+    FDW_TRY(forward_loop(c, &ip, &ipp, device_source(c, line, sx, sz, c->d_wav).recording(c->d_rec, gz), nt, SnapPlan{}));
     FDW_TRY(gathers_to_host(c, c->d_rec, 1, data));
     if (P) FDW_TRY(download_rows(c, P, c->fld[ip], c->stream));
     if (PP) FDW_TRY(download_rows(c, PP, c->fld[ipp], c->stream));
@@ -2032,7 +2038,7 @@ extern "C" int fdw_record_shot(fdw_ctx* c, const float* v2, int sx, int sz, int 
 {
     if (!v2) return fail(FDW_EINVAL, "NULL argument");
     if (c) c->v2_resident = false;
-    return record_impl(c, v2, sx, sz, gz, srce, data, P, PP);
+    return record_impl(c, v2, sx, sz, gz, srce, data, P, PP, false);
 }
 
 // ---- shots driven by a line source (definitions in fdwave.h) ----
@@ -2040,21 +2046,23 @@ extern "C" int fdw_shot_line(fdw_ctx* c, const float* v2, int sz, int gz, const 
                              float* PP)
 {
     if (!c || !wav) return fail(FDW_EINVAL, "NULL argument");
-    FDW_TRY(check_line_ctx(c, "fdw_shot_line"));
-    if (!v2 && !c->v2_resident) return fail(FDW_ESTATE, "no resident squared model: call fdw_dev_extendvel_linear first");
+    FDW_TRY(check_single_shot_ctx(c, "line sources", "fdw_shot_line"));
+    FDW_TRY(has_model(c, v2));
     FDW_TRY(check_line_args(c, "fdw_shot_line", sz, gz, false, illum != nullptr));
-    if (v2) c->v2_resident = false;
-    return shot_impl(c, v2, -1, sz, gz, nullptr, d_obs, imloc, P, PP, illum, nullptr, false, nullptr, wav);
+    end_residency(c, v2);
+    ShotExtras x;
+    x.line = true; x.illum = illum;
+    return shot_impl(c, v2, -1, sz, gz, wav, d_obs, imloc, P, PP, x);
 }
 
 extern "C" int fdw_record_shot_line(fdw_ctx* c, const float* v2, int sz, int gz, const float* wav, float* data, float* P, float* PP)
 {
     if (!c || !wav) return fail(FDW_EINVAL, "NULL argument");
-    FDW_TRY(check_line_ctx(c, "fdw_record_shot_line"));
-    if (!v2 && !c->v2_resident) return fail(FDW_ESTATE, "no resident squared model: call fdw_dev_extendvel_linear first");
+    FDW_TRY(check_single_shot_ctx(c, "line sources", "fdw_record_shot_line"));
+    FDW_TRY(has_model(c, v2));
     FDW_TRY(check_line_args(c, "fdw_record_shot_line", sz, gz, true, false));
-    if (v2) c->v2_resident = false;
-    return record_impl(c, v2, -1, sz, gz, nullptr, data, P, PP, wav);
+    end_residency(c, v2);
+    return record_impl(c, v2, -1, sz, gz, wav, data, P, PP, true);
 }
 
 // fdw_shot_line that migrates d_obs - d_mod, d_mod the gather its own forward loop records (fdw_record_shot_line's, bit for bit); with illum
@@ -2063,11 +2071,13 @@ extern "C" int fdw_shot_line_residual(fdw_ctx* c, const float* v2, int sz, int g
                                       float* resid, float* P, float* PP)
 {
     if (!c || !wav) return fail(FDW_EINVAL, "NULL argument");
-    FDW_TRY(check_line_ctx(c, "fdw_shot_line_residual"));
-    if (!v2 && !c->v2_resident) return fail(FDW_ESTATE, "no resident squared model: call fdw_dev_extendvel_linear first");
+    FDW_TRY(check_single_shot_ctx(c, "line sources", "fdw_shot_line_residual"));
+    FDW_TRY(has_model(c, v2));
     FDW_TRY(check_line_args(c, "fdw_shot_line_residual", sz, gz, true, illum != nullptr, true));
-    if (v2) c->v2_resident = false;
-    return shot_impl(c, v2, -1, sz, gz, nullptr, d_obs, imloc, P, PP, illum, nullptr, true, resid, wav);
+    end_residency(c, v2);
+    ShotExtras x;
+    x.line = true; x.illum = illum; x.residual = true; x.resid = resid;
+    return shot_impl(c, v2, -1, sz, gz, wav, d_obs, imloc, P, PP, x);
 }
 
 // The encoded data gather on the device (fdw_encode_gathers_kernel): every output element folds its shots in ascending order.
@@ -2199,6 +2209,7 @@ extern "C" int fdw_dev_model_steps(fdw_ctx* c, float* d_p, float* d_pp, const fl
     if (!c) return fail(FDW_EINVAL, "ctx is NULL");
     if (c->prm.dialect != FDW_DIALECT_MOD) return fail(FDW_ESTATE, "fdw_dev_model_steps needs a context created with dialect = FDW_DIALECT_MOD");
     hipStream_t s = pick_stream(c, stream);
+    const Forward f = point_source(d_srce, sx, sz).recording(d_rec, gz);
     int k = 0;
     if (pipe_pays(c) && nsteps >= kPipeSteps) {
         // four steps per pass, out of place: the caller's two buffers plus two of the context's rotate.  In M's convention P is
@@ -2210,9 +2221,7 @@ extern "C" int fdw_dev_model_steps(fdw_ctx* c, float* d_p, float* d_pp, const fl
         for (; nsteps - k >= kPipeSteps; k += kPipeSteps) {
             int o1, o2;
             spare_pair(iP, iPP, &o1, &o2);
-            const int it = it0 + k;
-            rc = stepn_impl(c, FDW_MODE_MOD, B[iP], B[iPP], d_v2, B[o1], B[o2], 1, d_srce ? d_srce + it : nullptr, sx, sz, s, RowRanges{},
-                            d_rec ? d_rec + (size_t)it * c->nx : nullptr, gz);
+            rc = stepn_impl(c, FDW_MODE_MOD, B[iP], B[iPP], d_v2, B[o1], B[o2], 1, view_at(f, it0 + k, c->nx), StepnBack{}, RowRanges{}, s);
             if (rc) return rc;
             iPP = o1; iP = o2;
         }
@@ -2230,9 +2239,7 @@ extern "C" int fdw_dev_model_steps(fdw_ctx* c, float* d_p, float* d_pp, const fl
         }
     }
     for (; k < nsteps; k++) {
-        const int it = it0 + k;
-        int rc = step_impl(c, FDW_MODE_MOD, d_p, d_pp, d_v2, 0, c->nxl, 1, d_srce ? d_srce + it : nullptr, sx, sz, nullptr, nullptr, s,
-                           d_rec ? d_rec + (size_t)it * c->nx : nullptr, gz);
+        int rc = step_impl(c, FDW_MODE_MOD, d_p, d_pp, d_v2, 0, c->nxl, 1, view_at(f, it0 + k, c->nx), BackExtra{}, s);
         if (rc) return rc;
         std::swap(d_p, d_pp);
     }
@@ -2342,7 +2349,9 @@ extern "C" int fdw_rtm_stored_shot(fdw_ctx* c, const float* vel2, int sx, int sz
         for (int j = 0; j < len; j++) {
             const int it = s0 + j;
             float* pp_in = j > 0 ? seg(j - 1) : const_cast<float*>(prev);                  // only read (out is given)
-            int r = step_impl(c, FDW_MODE_DD_FWD, seg(j), pp_in, c->d_v2, 0, c->nxl, 1, c->d_srce + it, sx, sz, nullptr, nullptr, c->stream, nullptr, 0, nullptr, seg(j + 1));
+            FwdView f = view_at(point_source(c->d_srce, sx, sz), it, c->nx);
+            f.out = seg(j + 1);
+            int r = step_impl(c, FDW_MODE_DD_FWD, seg(j), pp_in, c->d_v2, 0, c->nxl, 1, f, BackExtra{}, c->stream);
             if (r) return r;
         }
         return FDW_OK;
@@ -2378,12 +2387,14 @@ extern "C" int fdw_rtm_stored_shot(fdw_ctx* c, const float* vel2, int sx, int sz
             if ((rc = run_segment(s0, len, s > 0 ? ck(s, 0) : d_zero))) return rc;
         }
         for (int j = len - 1; j >= 0; j--, it++) {          // receiver iteration `it` images against swf[nt - it - 1] = swf[s0 + j]
-            rc = step_impl(c, FDW_MODE_DD_RECV, d_p, d_pp, c->d_v2, 0, c->nxl, 1, c->d_dobs + (size_t)it * nx, -1, gz, seg(j), c->d_img, c->stream);
+            BackExtra bk;
+            bk.psrc_a = seg(j); bk.img = c->d_img;
+            rc = step_impl(c, FDW_MODE_DD_RECV, d_p, d_pp, c->d_v2, 0, c->nxl, 1, receiver_samples(c->d_dobs + (size_t)it * nx, gz), bk, c->stream);
             if (rc) return rc;
             std::swap(d_p, d_pp);
         }
     }
-    if ((rc = image_to_host(c, imloc))) return rc;
+    if ((rc = image_to_host(c, imloc, c->d_img))) return rc;
     HIP_TRY(hipStreamSynchronize(c->stream));
     return FDW_OK;
 }
@@ -2732,17 +2743,19 @@ extern "C" int fdw_dev_extendvel_linear(fdw_ctx* c, unsigned long long draw_offs
 extern "C" int fdw_shot_resident(fdw_ctx* c, int sx, int sz, int gz, const float* srce, const float* d_obs, float* imloc, float* P, float* PP)
 {
     if (!c) return fail(FDW_EINVAL, "ctx is NULL");
-    if (!c->v2_resident) return fail(FDW_ESTATE, "no resident squared model: call fdw_dev_extendvel_linear first");
-    return shot_impl(c, nullptr, sx, sz, gz, srce, d_obs, imloc, P, PP);
+    FDW_TRY(has_model(c, nullptr));
+    return shot_impl(c, nullptr, sx, sz, gz, srce, d_obs, imloc, P, PP, ShotExtras{});
 }
 
 extern "C" int fdw_shot_resident_illum(fdw_ctx* c, int sx, int sz, int gz, const float* srce, const float* d_obs, float* imloc, float* illum,
                                        float* P, float* PP)
 {
     if (!c || !illum) return fail(FDW_EINVAL, "NULL argument");
-    FDW_TRY(check_illum_ctx(c, "fdw_shot_resident_illum"));
-    if (!c->v2_resident) return fail(FDW_ESTATE, "no resident squared model: call fdw_dev_extendvel_linear first");
-    return shot_impl(c, nullptr, sx, sz, gz, srce, d_obs, imloc, P, PP, illum);
+    FDW_TRY(check_single_shot_ctx(c, "source illumination", "fdw_shot_resident_illum"));
+    FDW_TRY(has_model(c, nullptr));
+    ShotExtras x;
+    x.illum = illum;
+    return shot_impl(c, nullptr, sx, sz, gz, srce, d_obs, imloc, P, PP, x);
 }
 
 // ---- the excitation-amplitude shot (definitions in fdwave.h) ----
@@ -2765,10 +2778,10 @@ extern "C" int fdw_shot_excitation(fdw_ctx* c, const float* v2, int sx, int sz, 
                                    float* exc, float* amp, int* texc, float* P, float* PP)
 {
     if (!c) return fail(FDW_EINVAL, "NULL argument");
-    FDW_TRY(check_exc_ctx(c, "fdw_shot_excitation"));
+    FDW_TRY(check_single_shot_ctx(c, "excitation-amplitude imaging", "fdw_shot_excitation"));
     if (!srce || !d_obs || (!imloc && !exc && !amp && !texc)) return fail(FDW_EINVAL, "NULL argument");
     if (!(eps >= 0.0f) || std::isinf(eps)) return fail(FDW_EINVAL, "fdw_shot_excitation: eps must be finite and >= 0");
-    if (!v2 && !c->v2_resident) return fail(FDW_ESTATE, "no resident squared model: call fdw_dev_extendvel_linear first");
+    FDW_TRY(has_model(c, v2));
     if (sx < 0) return fail(FDW_EINVAL, "fdw_shot_excitation: source row %d", sx);
     FDW_TRY(check_exc_source(c, "fdw_shot_excitation", sx, sz));
     FDW_TRY(check_line_args(c, "fdw_shot_excitation", gz, 0, false, false));
@@ -2790,19 +2803,19 @@ extern "C" int fdw_shot_excitation(fdw_ctx* c, const float* v2, int sx, int sz, 
     if (imloc && !amp) { h_amp.resize(ni); amp = h_amp.data(); }
     float* const maps[3] = {c->d_amp, (float*)c->d_texc, c->d_exc};
     if ((rc = zero_fields(c, c->fld, 2)) || (rc = zero_fields(c, maps, 3))) return rc;
-    if (v2) c->v2_resident = false;
+    end_residency(c, v2);
     if ((v2 && (rc = upload_rows(c, c->d_v2, v2, c->stream))) || (rc = upload_source(c, srce, nt))) return rc;
     if (nt > 0) HIP_TRY(hipMemcpyAsync(c->d_wav, wav.data(), wav.size() * sizeof(float), hipMemcpyHostToDevice, c->stream));
     int ip = 0, ipp = 1;
-    const ExcLoop fwd{c->d_amp, c->d_texc, 0, false};
-    if ((rc = steps_loop(c, c->fld, c->d_v2, c->d_srce, sx, sz, 0, nullptr, 0, nt, 0, &ip, &ipp, c->stream, nullptr, false, false, &fwd))) return rc;
+    const Forward fwd = point_source(c->d_srce, sx, sz).exciting(Exc::maps, c->d_amp, c->d_texc, 0);
+    if ((rc = steps_loop(c, c->fld, c->d_v2, fwd, 0, nt, 0, &ip, &ipp, c->stream))) return rc;
     if (nt > 0 && (rc = fdw_dev_taper_finalize(c, c->fld[ip], c->stream))) return rc;      // as fdw_shot's forward loop leaves d_p
     if (P && (rc = download_rows(c, P, c->fld[ip], c->stream))) return rc;
     if (PP && (rc = download_rows(c, PP, c->fld[ipp], c->stream))) return rc;
     if ((rc = zero_fields(c, c->fld + 4, 2))) return rc;
     int rp = 0, rpp = 1;
-    const ExcLoop bwd{c->d_exc, c->d_texc, nt, true};
-    if ((rc = steps_loop(c, c->fld + 4, c->d_v2, c->d_wav, -1, gz, 0, nullptr, 0, nt, 0, &rp, &rpp, c->stream, nullptr, true, false, &bwd))) return rc;
+    const Forward bwd = line_source(c->d_wav, gz).exciting(Exc::pick, c->d_exc, c->d_texc, nt);
+    if ((rc = steps_loop(c, c->fld + 4, c->d_v2, bwd, 0, nt, 0, &rp, &rpp, c->stream))) return rc;
     if (exc && (rc = image_to_host(c, exc, c->d_exc))) return rc;
     if (amp && (rc = image_to_host(c, amp, c->d_amp))) return rc;
     if (texc && (rc = image_to_host(c, (float*)texc, (const float*)c->d_texc))) return rc;
@@ -2812,22 +2825,16 @@ extern "C" int fdw_shot_excitation(fdw_ctx* c, const float* v2, int sx, int sz, 
 }
 
 // ---- residual migration (definitions in fdwave.h) ----
-static int check_residual_ctx(const fdw_ctx* c, const char* who)
-{
-    if (c->prm.dialect != FDW_DIALECT_RTM) return fail(FDW_ESTATE, "%s: residual migration belongs to the RTM dialect", who);
-    if (!is_full_grid(c)) return fail(FDW_ESTATE, "%s: residual migration needs a full-grid context (slab-decomposed shots are not covered)", who);
-    if (c->nbatch > 1) return fail(FDW_ESTATE, "%s: not inside a batch of shots", who);
-    return FDW_OK;
-}
-
 extern "C" int fdw_shot_residual(fdw_ctx* c, const float* v2, int sx, int sz, int gz, const float* srce, const float* d_obs, float* imloc, float* illum,
                                  float* resid, float* P, float* PP)
 {
     if (!c) return fail(FDW_EINVAL, "ctx is NULL");
-    FDW_TRY(check_residual_ctx(c, "fdw_shot_residual"));
-    if (!v2 && !c->v2_resident) return fail(FDW_ESTATE, "no resident squared model: call fdw_dev_extendvel_linear first");
-    if (v2) c->v2_resident = false;
-    return shot_impl(c, v2, sx, sz, gz, srce, d_obs, imloc, P, PP, illum, nullptr, true, resid);
+    FDW_TRY(check_single_shot_ctx(c, "residual migration", "fdw_shot_residual"));
+    FDW_TRY(has_model(c, v2));
+    end_residency(c, v2);
+    ShotExtras x;
+    x.illum = illum; x.residual = true; x.resid = resid;
+    return shot_impl(c, v2, sx, sz, gz, srce, d_obs, imloc, P, PP, x);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2890,7 +2897,7 @@ static int ensure_batch_buffers(fdw_ctx* c, int n, bool need_all)
 namespace {
 struct BatchScope {      // the context's single-shot buffers step aside for the batch ones while a batch runs
     fdw_ctx* c;
-    explicit BatchScope(fdw_ctx* ctx, int n, int dsx, bool illum = false) : c(ctx)
+    BatchScope(fdw_ctx* ctx, int n, int dsx, bool illum) : c(ctx)
     {
         swap();
         c->nbatch = n; c->batch_dsx = dsx; c->batch_nt = c->prm.nt; c->batch_illum = illum;
@@ -2970,33 +2977,36 @@ static int batch_interiors_to_host(fdw_ctx* c, float* h_dst, const float* d_src,
     return FDW_OK;
 }
 
-// fdw_shot_batch (illum == NULL) and fdw_shot_batch_illum: illum [nshots][nx][nz] is accumulated into per shot by the forward loop
-// residual (fdw_shot_batch_residual): the forward loop records every shot's modelled gather into b_rec [shot][nt][nx], one launch turns the
-// batch's gathers into d_obs - d_mod in place before the backward loop; resid: NULL, or [nshots][nx][nt] that difference
-// wav_all (fdw_shot_line_batch and its kin): NULL, or the shots' line-source gathers [nshots][nx][nt] that drive the forward loop in place of
-// (sx0, dsx, srce): one more batch buffer, b_wav [shot][nt][nx], from which every forward launch takes a row per shot
-static int shot_batch_impl(fdw_ctx* c, const char* who, int nshots, const float* v2_all, unsigned long long draw_offset, int sx0, int dsx, int sz, int gz,
-                           const float* srce, const float* d_obs, float* imloc, float* illum, bool residual = false, float* resid = nullptr,
-                           const float* wav_all = nullptr)
+// the source rows of a batch of point-source shots: rows the forward loop time-steps
+static int check_batch_source_rows(const fdw_ctx* c, int nshots, int sx0, int dsx)
 {
-    if (!c || (!srce && !wav_all) || !d_obs || !imloc) return fail(FDW_EINVAL, "NULL argument");
-    const bool line = wav_all != nullptr;
+    const int sx_last = sx0 + (nshots - 1) * dsx;
+    if (std::min(sx0, sx_last) < 0 || std::max(sx0, sx_last) >= c->prm.nxe || std::max(sx0, sx_last) >= c->upd_x1)
+        return fail(FDW_EINVAL, "source rows %d..%d leave the rows the reference time-steps (< %d)", sx0, sx_last, c->upd_x1);
+    return FDW_OK;
+}
+
+// fdw_shot_batch, with x.illum fdw_shot_batch_illum, with x.residual fdw_shot_batch_residual.  x.line (fdw_shot_line_batch and its kin):
+// `samples` holds the shots' line-source gathers [nshots][nx][nt] in place of the wavelet and (sx0, dsx): one more batch buffer, b_wav
+// [shot][nt][nx], from which every forward launch takes a row per shot.
+static int shot_batch_impl(fdw_ctx* c, const char* who, int nshots, const float* v2_all, unsigned long long draw_offset, int sx0, int dsx, int sz, int gz,
+                           const float* samples, const float* d_obs, float* imloc, const ShotExtras& x)
+{
+    if (!c || !samples || !d_obs || !imloc) return fail(FDW_EINVAL, "NULL argument");
     if (nshots < 1) return fail(FDW_EINVAL, "nshots=%d", nshots);
     if (!is_full_grid(c)) return fail(FDW_EINVAL, "%s needs a full-grid context", who);
     if (c->nx <= 0 || c->nz <= 0) return fail(FDW_EINVAL, "no interior to image");
     if (!v2_all && !c->model_resident) return fail(FDW_ESTATE, "no model: pass v2_all or call fdw_model_resident first");
     const int nt = c->prm.nt;
     const size_t ni = (size_t)c->nx * c->nz, ne = (size_t)c->prm.nxe * c->prm.nze, ng = (size_t)c->nx * nt, fe = field_elems(c);
-    const int sx_last = sx0 + (nshots - 1) * dsx;
-    if (!line && (std::min(sx0, sx_last) < 0 || std::max(sx0, sx_last) >= c->prm.nxe || std::max(sx0, sx_last) >= c->upd_x1))
-        return fail(FDW_EINVAL, "source rows %d..%d leave the rows the reference time-steps (< %d)", sx0, sx_last, c->upd_x1);
+    if (!x.line) FDW_TRY(check_batch_source_rows(c, nshots, sx0, dsx));
     HIP_TRY(hipSetDevice(c->device));
     const long long draws = fdw_border_draws(c->nx, c->nz, c->prm.nxb, c->prm.nzb);
     auto one_by_one = [&] {
         for (int b = 0; b < nshots; b++) {
             if (!v2_all) FDW_TRY(fdw_dev_extendvel_linear(c, draw_offset + (unsigned long long)b * draws, nullptr));
-            FDW_TRY(shot_impl(c, v2_all ? v2_all + b * ne : nullptr, line ? -1 : sx0 + b * dsx, sz, gz, srce, d_obs + b * ng, imloc + b * ni, nullptr, nullptr,
-                              illum ? illum + b * ni : nullptr, nullptr, residual, resid ? resid + b * ng : nullptr, line ? wav_all + b * ng : nullptr));
+            FDW_TRY(shot_impl(c, v2_all ? v2_all + b * ne : nullptr, sx0 + b * dsx, sz, gz, x.line ? samples + b * ng : samples, d_obs + b * ng, imloc + b * ni,
+                              nullptr, nullptr, x.of_shot(b, ni, ng)));
         }
         return (int)FDW_OK;
     };
@@ -3006,32 +3016,31 @@ static int shot_batch_impl(fdw_ctx* c, const char* who, int nshots, const float*
     int rc;
     if ((rc = ensure_work_buffers(c, 8, true))) return rc;
     if ((rc = ensure_batch_buffers(c, nshots, true)) == FDW_ENOMEM) return fallback();      // no room for the batch
-    if (!rc && illum && (rc = ensure_batch_illum(c, nshots)) == FDW_ENOMEM) return fallback();      // ... or for its accumulators
-    if (!rc && residual && (rc = ensure_cap(&c->b_rec, &c->b_rec_cap, ng * nshots)) == FDW_ENOMEM) return fallback();      // ... or its modelled gathers
-    if (!rc && line && (rc = ensure_cap(&c->b_wav, &c->b_wav_cap, ng * nshots)) == FDW_ENOMEM) return fallback();      // ... or its line-source gathers
+    if (!rc && x.illum && (rc = ensure_batch_illum(c, nshots)) == FDW_ENOMEM) return fallback();      // ... or for its accumulators
+    if (!rc && x.residual && (rc = ensure_cap(&c->b_rec, &c->b_rec_cap, ng * nshots)) == FDW_ENOMEM) return fallback();      // ... or its modelled gathers
+    if (!rc && x.line && (rc = ensure_cap(&c->b_wav, &c->b_wav_cap, ng * nshots)) == FDW_ENOMEM) return fallback();      // ... or its line-source gathers
     if (!rc) batch_part_ran(c, true);
-    if (rc || (rc = line ? gathers_to_device(c, wav_all, c->b_wav, nshots) : upload_source(c, srce, nt))) return rc;
+    if (rc || (rc = x.line ? gathers_to_device(c, samples, c->b_wav, nshots) : upload_source(c, samples, nt))) return rc;
     hipStream_t s = c->stream;
     if ((rc = gathers_to_device(c, d_obs, c->b_dobs, nshots))) return rc;      // [shot][nx][nt] -> [shot][nt][nx]
     if ((rc = batch_models(c, nshots, v2_all, draw_offset))) return rc;
     for (int i = 0; i < 8; i++) HIP_TRY(hipMemsetAsync(c->bfld[i], 0, fe * nshots * sizeof(float), s));    // R:496-497, R:511-514
     if ((rc = batch_interiors_to_device(c, c->b_img, imloc, nshots))) return rc;
-    if (illum && (rc = batch_interiors_to_device(c, c->b_illum, illum, nshots))) return rc;
+    if (x.illum && (rc = batch_interiors_to_device(c, c->b_illum, x.illum, nshots))) return rc;
     {
-        BatchScope scope(c, nshots, line ? 0 : dsx, illum != nullptr);
+        BatchScope scope(c, nshots, dsx, x.illum != nullptr);
         int ip = 0, ipp = 1;
-        if ((rc = steps_loop(c, c->fld, c->d_v2, line ? c->b_wav : c->d_srce, line ? -1 : sx0, sz, residual ? gz : 0, residual ? c->b_rec : nullptr, 0, nt, 0,
-                             &ip, &ipp, s, illum ? c->b_illum : nullptr, line)))
-            return rc;
-        if (residual && (rc = gather_residual(c->d_dobs, c->b_rec, c->d_dobs, ng * nshots, s))) return rc;      // d_dobs: the batch's [shot][nt][nx]
+        const Forward f = device_source(c, x.line, sx0, sz, c->b_wav).recording(x.residual ? c->b_rec : nullptr, gz).illuminating(x.illum ? c->b_illum : nullptr);
+        if ((rc = steps_loop(c, c->fld, c->d_v2, f, 0, nt, 0, &ip, &ipp, s))) return rc;
+        if (x.residual && (rc = gather_residual(c->d_dobs, c->b_rec, c->d_dobs, ng * nshots, s))) return rc;      // d_dobs: the batch's [shot][nt][nx]
         for (int b = 0; b < nshots && nt > 0; b++)
             if ((rc = fdw_dev_taper_finalize(c, c->fld[ip] + b * fe, s))) return rc;
         float* src[4];
         source_buffers(c, ip, ipp, src);
-        if ((rc = back_loop(c, src, c->fld + 4, gz, nt))) return rc;
+        if ((rc = back_loop(c, src, c->fld + 4, gz, nt, SnapPlan{}))) return rc;
     }
-    if (resid && (rc = gathers_to_host(c, c->b_dobs, nshots, resid))) return rc;
-    if (illum && (rc = batch_interiors_to_host(c, illum, c->b_illum, nshots))) return rc;
+    if (x.resid && (rc = gathers_to_host(c, c->b_dobs, nshots, x.resid))) return rc;
+    if (x.illum && (rc = batch_interiors_to_host(c, x.illum, c->b_illum, nshots))) return rc;
     if ((rc = batch_interiors_to_host(c, imloc, c->b_img, nshots))) return rc;
     HIP_TRY(hipStreamSynchronize(s));
     return FDW_OK;
@@ -3042,7 +3051,7 @@ extern "C" int fdw_shot_batch(fdw_ctx* c, int nshots, const float* v2_all, unsig
 {
     if (!c) return fail(FDW_EINVAL, "NULL argument");
     batch_begin(c);
-    return batch_end(c, nshots, shot_batch_impl(c, "fdw_shot_batch", nshots, v2_all, draw_offset, sx0, dsx, sz, gz, srce, d_obs, imloc, nullptr));
+    return batch_end(c, nshots, shot_batch_impl(c, "fdw_shot_batch", nshots, v2_all, draw_offset, sx0, dsx, sz, gz, srce, d_obs, imloc, ShotExtras{}));
 }
 
 // How many shots of a batch go through at once: what the budget fdw_shot_batch_max counts with (batch_budget) holds of `fields` fields and `gathers`
@@ -3053,6 +3062,22 @@ static int batch_part(const fdw_ctx* c, int nshots, int fields, int gathers)
     const long by_mem = (long)(batch_budget(c) / (((size_t)fields * field_elems(c) + (size_t)gathers * ng) * sizeof(float)));
     return (int)std::max<long>(1, std::min<long>(by_mem, nshots));
 }
+// shot_batch_impl in parts of what batch_part allows for `fields` fields and `gathers` gathers per shot
+static int shot_batch_in_parts(fdw_ctx* c, const char* who, int nshots, const float* v2_all, unsigned long long draw_offset, int sx0, int dsx, int sz, int gz,
+                               const float* samples, const float* d_obs, float* imloc, const ShotExtras& x, int fields, int gathers)
+{
+    const int part = batch_part(c, nshots, fields, gathers);
+    const size_t ni = (size_t)c->nx * c->nz, ne = (size_t)c->prm.nxe * c->prm.nze, ng = (size_t)c->nx * c->prm.nt;
+    const unsigned long long draws = (unsigned long long)fdw_border_draws(c->nx, c->nz, c->prm.nxb, c->prm.nzb);
+    batch_begin(c);
+    for (int b0 = 0; b0 < nshots; b0 += part) {
+        const int nb = std::min(part, nshots - b0);
+        FDW_TRY(shot_batch_impl(c, who, nb, v2_all ? v2_all + b0 * ne : nullptr, draw_offset + b0 * draws, sx0 + b0 * dsx, dsx, sz, gz,
+                                x.line && samples ? samples + b0 * ng : samples, d_obs ? d_obs + b0 * ng : nullptr, imloc ? imloc + b0 * ni : nullptr,
+                                x.of_shot(b0, ni, ng)));
+    }
+    return batch_end(c, nshots, FDW_OK);
+}
 
 // fdw_shot_batch whose forward loop also accumulates every shot's source illumination.  The batch holds one field more per shot than
 // fdw_shot_batch_max counts (11), so a batch larger than twelve fields per shot allow within the same budget goes through in parts of that
@@ -3061,18 +3086,11 @@ extern "C" int fdw_shot_batch_illum(fdw_ctx* c, int nshots, const float* v2_all,
                                     const float* srce, const float* d_obs, float* imloc, float* illum)
 {
     if (!c || !illum) return fail(FDW_EINVAL, "NULL argument");
-    FDW_TRY(check_illum_ctx(c, "fdw_shot_batch_illum"));
+    FDW_TRY(check_single_shot_ctx(c, "source illumination", "fdw_shot_batch_illum"));
     if (nshots < 1) return fail(FDW_EINVAL, "nshots=%d", nshots);
-    const int part = batch_part(c, nshots, 12, 0);
-    const size_t ni = (size_t)c->nx * c->nz, ne = (size_t)c->prm.nxe * c->prm.nze, ng = (size_t)c->nx * c->prm.nt;
-    const unsigned long long draws = (unsigned long long)fdw_border_draws(c->nx, c->nz, c->prm.nxb, c->prm.nzb);
-    batch_begin(c);
-    for (int b0 = 0; b0 < nshots; b0 += part) {
-        const int nb = std::min(part, nshots - b0);
-        FDW_TRY(shot_batch_impl(c, "fdw_shot_batch_illum", nb, v2_all ? v2_all + b0 * ne : nullptr, draw_offset + b0 * draws, sx0 + b0 * dsx, dsx, sz, gz,
-                                srce, d_obs ? d_obs + b0 * ng : nullptr, imloc ? imloc + b0 * ni : nullptr, illum + b0 * ni));
-    }
-    return batch_end(c, nshots, FDW_OK);
+    ShotExtras x;
+    x.illum = illum;
+    return shot_batch_in_parts(c, "fdw_shot_batch_illum", nshots, v2_all, draw_offset, sx0, dsx, sz, gz, srce, d_obs, imloc, x, 12, 0);
 }
 
 // fdw_shot_batch whose forward loop also records every shot's modelled gather (and, with illum, accumulates its illumination in the same
@@ -3082,20 +3100,12 @@ extern "C" int fdw_shot_batch_residual(fdw_ctx* c, int nshots, const float* v2_a
                                        const float* srce, const float* d_obs, float* imloc, float* illum, float* resid)
 {
     if (!c) return fail(FDW_EINVAL, "ctx is NULL");
-    FDW_TRY(check_residual_ctx(c, "fdw_shot_batch_residual"));
+    FDW_TRY(check_single_shot_ctx(c, "residual migration", "fdw_shot_batch_residual"));
     FDW_TRY(check_record_depth(c, gz));
     if (nshots < 1) return fail(FDW_EINVAL, "nshots=%d", nshots);
-    const size_t ni = (size_t)c->nx * c->nz, ne = (size_t)c->prm.nxe * c->prm.nze, ng = (size_t)c->nx * c->prm.nt;
-    const int part = batch_part(c, nshots, illum ? 12 : 11, 1);
-    const unsigned long long draws = (unsigned long long)fdw_border_draws(c->nx, c->nz, c->prm.nxb, c->prm.nzb);
-    batch_begin(c);
-    for (int b0 = 0; b0 < nshots; b0 += part) {
-        const int nb = std::min(part, nshots - b0);
-        FDW_TRY(shot_batch_impl(c, "fdw_shot_batch_residual", nb, v2_all ? v2_all + b0 * ne : nullptr, draw_offset + b0 * draws, sx0 + b0 * dsx, dsx, sz,
-                                gz, srce, d_obs ? d_obs + b0 * ng : nullptr, imloc ? imloc + b0 * ni : nullptr, illum ? illum + b0 * ni : nullptr, true,
-                                resid ? resid + b0 * ng : nullptr));
-    }
-    return batch_end(c, nshots, FDW_OK);
+    ShotExtras x;
+    x.illum = illum; x.residual = true; x.resid = resid;
+    return shot_batch_in_parts(c, "fdw_shot_batch_residual", nshots, v2_all, draw_offset, sx0, dsx, sz, gz, srce, d_obs, imloc, x, illum ? 12 : 11, 1);
 }
 
 // ---- batches of line-source shots (definitions in fdwave.h) ----
@@ -3106,20 +3116,12 @@ static int shot_line_batch(fdw_ctx* c, const char* who, int nshots, const float*
                            const float* wav_all, const float* d_obs, float* imloc, float* illum, bool residual, float* resid)
 {
     if (!c || !wav_all) return fail(FDW_EINVAL, "NULL argument");
-    FDW_TRY(check_line_ctx(c, who));
+    FDW_TRY(check_single_shot_ctx(c, "line sources", who));
     FDW_TRY(check_line_args(c, who, sz, gz, residual, illum != nullptr, true));
     if (nshots < 1) return fail(FDW_EINVAL, "nshots=%d", nshots);
-    const size_t ni = (size_t)c->nx * c->nz, ne = (size_t)c->prm.nxe * c->prm.nze, ng = (size_t)c->nx * c->prm.nt;
-    const int part = batch_part(c, nshots, illum ? 12 : 11, residual ? 2 : 1);
-    const unsigned long long draws = (unsigned long long)fdw_border_draws(c->nx, c->nz, c->prm.nxb, c->prm.nzb);
-    batch_begin(c);
-    for (int b0 = 0; b0 < nshots; b0 += part) {
-        const int nb = std::min(part, nshots - b0);
-        FDW_TRY(shot_batch_impl(c, who, nb, v2_all ? v2_all + b0 * ne : nullptr, draw_offset + b0 * draws, 0, 0, sz, gz, nullptr,
-                                d_obs ? d_obs + b0 * ng : nullptr, imloc ? imloc + b0 * ni : nullptr, illum ? illum + b0 * ni : nullptr, residual,
-                                resid ? resid + b0 * ng : nullptr, wav_all + b0 * ng));
-    }
-    return batch_end(c, nshots, FDW_OK);
+    ShotExtras x;
+    x.line = true; x.illum = illum; x.residual = residual; x.resid = resid;
+    return shot_batch_in_parts(c, who, nshots, v2_all, draw_offset, -1, 0, sz, gz, wav_all, d_obs, imloc, x, illum ? 12 : 11, residual ? 2 : 1);
 }
 
 extern "C" int fdw_shot_line_batch(fdw_ctx* c, int nshots, const float* v2_all, unsigned long long draw_offset, int sz, int gz, const float* wav_all,
@@ -3136,12 +3138,11 @@ extern "C" int fdw_shot_line_batch_residual(fdw_ctx* c, int nshots, const float*
 
 // `nshots` recorded gathers (fdw_record_shot) through one launch per time step for the whole batch where batch_ok holds, one shot after the
 // other otherwise; models as fdw_shot_batch takes them.  data [nshots][nx][nt].
-// wav_all (fdw_record_shot_line_batch): NULL, or the shots' line-source gathers [nshots][nx][nt] in place of (sx0, dsx, srce)
+// line (fdw_record_shot_line_batch): `samples` holds the shots' line-source gathers [nshots][nx][nt] in place of the wavelet and (sx0, dsx)
 static int record_batch_impl(fdw_ctx* c, int nshots, const float* v2_all, unsigned long long draw_offset, int sx0, int dsx, int sz, int gz,
-                             const float* srce, float* data, const float* wav_all = nullptr)
+                             const float* samples, float* data, bool line)
 {
-    if (!c || (!srce && !wav_all) || !data) return fail(FDW_EINVAL, "NULL argument");
-    const bool line = wav_all != nullptr;
+    if (!c || !samples || !data) return fail(FDW_EINVAL, "NULL argument");
     if (nshots < 1) return fail(FDW_EINVAL, "nshots=%d", nshots);
     FDW_TRY(check_record_depth(c, gz));
     if (!is_full_grid(c)) return fail(FDW_EINVAL, "fdw_record_shot_batch needs a full-grid context");
@@ -3149,16 +3150,13 @@ static int record_batch_impl(fdw_ctx* c, int nshots, const float* v2_all, unsign
     if (!v2_all && !c->model_resident) return fail(FDW_ESTATE, "no model: pass v2_all or call fdw_model_resident first");
     const int nt = c->prm.nt;
     const size_t ne = (size_t)c->prm.nxe * c->prm.nze, ng = (size_t)c->nx * nt, fe = field_elems(c);
-    const int sx_last = sx0 + (nshots - 1) * dsx;
-    if (!line && (std::min(sx0, sx_last) < 0 || std::max(sx0, sx_last) >= c->prm.nxe || std::max(sx0, sx_last) >= c->upd_x1))
-        return fail(FDW_EINVAL, "source rows %d..%d leave the rows the reference time-steps (< %d)", sx0, sx_last, c->upd_x1);
+    if (!line) FDW_TRY(check_batch_source_rows(c, nshots, sx0, dsx));
     HIP_TRY(hipSetDevice(c->device));
     const long long draws = fdw_border_draws(c->nx, c->nz, c->prm.nxb, c->prm.nzb);
     auto one_by_one = [&] {
         for (int b = 0; b < nshots; b++) {
             if (!v2_all) FDW_TRY(fdw_dev_extendvel_linear(c, draw_offset + (unsigned long long)b * draws, nullptr));
-            FDW_TRY(record_impl(c, v2_all ? v2_all + b * ne : nullptr, line ? -1 : sx0 + b * dsx, sz, gz, srce, data + b * ng, nullptr, nullptr,
-                                line ? wav_all + b * ng : nullptr));
+            FDW_TRY(record_impl(c, v2_all ? v2_all + b * ne : nullptr, sx0 + b * dsx, sz, gz, line ? samples + b * ng : samples, data + b * ng, nullptr, nullptr, line));
         }
         return (int)FDW_OK;
     };
@@ -3168,15 +3166,15 @@ static int record_batch_impl(fdw_ctx* c, int nshots, const float* v2_all, unsign
     if ((rc = ensure_batch_buffers(c, nshots, true)) == FDW_ENOMEM) return one_by_one();
     if (!rc && line && (rc = ensure_cap(&c->b_wav, &c->b_wav_cap, ng * nshots)) == FDW_ENOMEM) return one_by_one();
     if (!rc) batch_part_ran(c, true);      // no part loop here: the whole batch or, above, the shots one by one (fdw_batch_parts 1 or 0)
-    if (rc || (rc = line ? gathers_to_device(c, wav_all, c->b_wav, nshots) : upload_source(c, srce, nt)) || (rc = batch_models(c, nshots, v2_all, draw_offset)))
+    if (rc || (rc = line ? gathers_to_device(c, samples, c->b_wav, nshots) : upload_source(c, samples, nt)) || (rc = batch_models(c, nshots, v2_all, draw_offset)))
         return rc;
     hipStream_t s = c->stream;
     for (int i = 0; i < 2; i++) HIP_TRY(hipMemsetAsync(c->bfld[i], 0, fe * nshots * sizeof(float), s));    // R:496-497
     {
-        BatchScope scope(c, nshots, line ? 0 : dsx);
+        BatchScope scope(c, nshots, dsx, false);
         int ip = 0, ipp = 1;
-        // d_dobs: the batch's [shot][nt][nx]
-        if ((rc = steps_loop(c, c->fld, c->d_v2, line ? c->b_wav : c->d_srce, line ? -1 : sx0, sz, gz, c->d_dobs, 0, nt, 0, &ip, &ipp, s, nullptr, line))) return rc;
+        const Forward f = device_source(c, line, sx0, sz, c->b_wav).recording(c->d_dobs, gz);      // d_dobs: the batch's [shot][nt][nx]
+        if ((rc = steps_loop(c, c->fld, c->d_v2, f, 0, nt, 0, &ip, &ipp, s))) return rc;
     }
     if ((rc = gathers_to_host(c, c->b_dobs, nshots, data))) return rc;
     HIP_TRY(hipStreamSynchronize(s));
@@ -3187,16 +3185,16 @@ extern "C" int fdw_record_shot_batch(fdw_ctx* c, int nshots, const float* v2_all
                                      const float* srce, float* data)
 {
     if (!srce) return fail(FDW_EINVAL, "NULL argument");
-    return record_batch_impl(c, nshots, v2_all, draw_offset, sx0, dsx, sz, gz, srce, data);
+    return record_batch_impl(c, nshots, v2_all, draw_offset, sx0, dsx, sz, gz, srce, data, false);
 }
 
 extern "C" int fdw_record_shot_line_batch(fdw_ctx* c, int nshots, const float* v2_all, unsigned long long draw_offset, int sz, int gz, const float* wav_all,
                                           float* data)
 {
     if (!c || !wav_all) return fail(FDW_EINVAL, "NULL argument");
-    FDW_TRY(check_line_ctx(c, "fdw_record_shot_line_batch"));
+    FDW_TRY(check_single_shot_ctx(c, "line sources", "fdw_record_shot_line_batch"));
     FDW_TRY(check_line_args(c, "fdw_record_shot_line_batch", sz, gz, true, false));
-    return record_batch_impl(c, nshots, v2_all, draw_offset, 0, 0, sz, gz, nullptr, data, wav_all);
+    return record_batch_impl(c, nshots, v2_all, draw_offset, -1, 0, sz, gz, wav_all, data, true);
 }
 
 // mod_main's shot loop (M:140-174) for `nshots` consecutive shots on its one velocity model, one launch per time step for all of them
