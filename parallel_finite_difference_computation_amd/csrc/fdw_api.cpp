@@ -876,17 +876,14 @@ struct StepnBack {      // the passes of the backward loop (Step2Args: lvl0, lvl
     float *rout1 = nullptr, *rout2 = nullptr;
 };
 // cls[L] of every tile of a FWD / PLAIN launch of fdw_stepn_kernel, in the tile order L = chunk row * nstrip + strip: 0 = it runs the lean body,
-// 1 = the full body, by the predicate the kernel picks the body with (pipe_tile_lean, fdw_kernels.h)
+// 1 = the full body, by the placement the kernels expand and the predicate they pick the body with (FDW_PIPE_TILE_ROWS, pipe_tile_lean: fdw_kernels.h)
 static void tile_classes(const Step2Args& a, const FwdVariant& v, std::vector<unsigned char>& cls)
 {
     constexpr int H = kMaxFastHalfOrder, NS = kPipeSteps;
     cls.resize((size_t)a.nblk);
     for (int L = 0; L < a.nblk; L++) {
-        const int zb = L % a.nstrip, xb = L / a.nstrip;
-        const bool second = xb >= a.chunks_a;
-        const int xa = second ? a.r0b + (xb - a.chunks_a) * a.xchunk : a.r0 + xb * a.xchunk;
-        const int xe = std::min(xa + a.xchunk, second ? a.r1b : a.r1);
-        const int cs = zb * (64 - 2 * NS) - NS;
+        FDW_PIPE_TILE_ROWS(a, L, zb, xa, xe)
+        const int cs = FDW_PIPE_TILE_CELL(zb, NS);
         const bool lean = v.kmode == FDW_MODE_PLAIN ? pipe_tile_lean<H, NS, false, 0>(a, cs, xa, xe)
                           : (v.line && v.rec)       ? pipe_tile_lean<H, NS, true, 2, false, true>(a, cs, xa, xe)
                           : v.line                  ? pipe_tile_lean<H, NS, true, 2>(a, cs, xa, xe)

@@ -156,6 +156,18 @@ __host__ __device__ __forceinline__ bool pipe_tile_lean(const Step2Args& a, int 
     return ok;
 }
 
+// Which tile of a pipeline pass is logical block L (L = chunk row * nstrip + strip)?  Declares the strip `zb` and the rows [`xa`, `xe`) of the
+// chunk (and `xb`, `second`): chunks from chunks_a on walk the second row range of the launch (the two boundary strips of a slab).  A macro
+// because the kernels expand it (FDW_PIPE_TILE, fdw_stepn.hip, where the reason is written down) and the host must agree with them tile for
+// tile (tile_classes, fdw_api.cpp).  FDW_PIPE_TILE_CELL: the first cell of strip zb's wave, NS halo lanes before the 64 - 2 NS cells it owns.
+#define FDW_PIPE_TILE_ROWS(a, L, zb, xa, xe)                                             \
+    const int zb = (L) % a.nstrip;                                                       \
+    const int xb = (L) / a.nstrip;                                                       \
+    const bool second = xb >= a.chunks_a;                                                \
+    const int xa = second ? a.r0b + (xb - a.chunks_a) * a.xchunk : a.r0 + xb * a.xchunk; \
+    const int xe = min(xa + a.xchunk, second ? a.r1b : a.r1);
+#define FDW_PIPE_TILE_CELL(zb, NS) ((zb) * (64 - 2 * (NS)) - (NS))
+
 hipError_t launch_step_fast(const StepArgs& a, int half_order, int mode, int prefetch, hipStream_t s);
 hipError_t launch_step_generic(const StepArgs& a, int half_order, int mode, hipStream_t s);
 hipError_t launch_taper_finalize(float* f, const float* taperz, const float* txfac, int pitch, int nxl, int ztap,

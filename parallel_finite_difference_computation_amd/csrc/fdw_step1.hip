@@ -411,236 +411,101 @@ __device__ __forceinline__ void march(const StepArgs& a, const ShotView& sv, con
         static_for<R>([&](auto UU) { row_step(rb, UU, std::true_type{}); });
 }
 
+// Tile placement of the one-step kernels: the shot a block works on and the strip and rows of each of its four waves.  Declares the ShotView
+// `sv` of shot blockIdx.y (a batch of independent shots of one geometry fills the chip where one small grid cannot), `lane`, the first column
+// `zs` of the wave's strip and its rows [`xa`, `xe`), and leaves the kernel where the wave has no tile (no barrier follows).
+// XCD-aware block remap: blocks b and b + 8 share an XCD (round-robin dispatch), so each XCD gets a contiguous run of logical blocks = a
+// contiguous band of x rows whose chunk halos it re-reads from its own L2.  Placement only changes speed, never results.  a.wz = waves of a
+// block laid along z (1, 2 or 4); the others take consecutive chunks.  A macro for the reason written down at FDW_PIPE_TILE (fdw_stepn.hip).
+#define FDW_STEP_TILE(a, sv, lane, zs, xa, xe)                                                                           \
+    const int shot = blockIdx.y;                                                                                         \
+    const long long o = shot * a.bstride;                                                                                \
+    const ShotView sv{a.p + o, a.pp + o, (a.out ? a.out : a.pp) + o, a.v2 + shot * a.v2_bstride, a.psrc + o, a.fpp + o,  \
+                      a.img + o, a.inj + shot * a.inj_bstride, a.inj_x + shot * a.inj_dx, a.rec + shot * a.rec_bstride}; \
+    const int lane = threadIdx.x & 63;                                                                                   \
+    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);                                                      \
+    const int bid = blockIdx.x;                                                                                          \
+    const int L = (bid & 7) * a.nper + (bid >> 3);                                                                       \
+    if (L >= a.nblk) return;                                                                                             \
+    const int zb = L % a.nzblk;                                                                                          \
+    const int xb = L / a.nzblk;                                                                                          \
+    const int wz = a.wz;                                                                                                 \
+    const int strip = zb * wz + (w & (wz - 1));                                                                          \
+    const int chunk = xb * (4 / wz) + (w / wz);                                                                          \
+    const int zs = strip * 256;                                                                                          \
+    if (zs >= a.pitch) return;                                                                                           \
+    const int xa = a.r0 + chunk * a.xchunk;                                                                              \
+    const int xe = min(xa + a.xchunk, a.r1);                                                                             \
+    if (xa >= xe) return;
+
 template <int H, bool TAPER, int INJ, bool IMG, bool LAPONLY, int PF, bool DD = false, bool BACK = false, int NUM = 0>
 __global__ __launch_bounds__(256) void fdw_step_kernel(const StepArgs a)
 {
-    // a batch of independent shots of one geometry fills the chip where one small grid cannot: blockIdx.y picks the shot
-    const int shot = blockIdx.y;
-    const long long o = shot * a.bstride;
-    const ShotView sv{a.p + o, a.pp + o, (a.out ? a.out : a.pp) + o, a.v2 + shot * a.v2_bstride, a.psrc + o, a.fpp + o, a.img + o, a.inj + shot * a.inj_bstride,
-                      a.inj_x + shot * a.inj_dx, a.rec + shot * a.rec_bstride};
-    const int lane = threadIdx.x & 63;
-    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-
-    // XCD-aware block remap: blocks b and b+8 share an XCD (round-robin dispatch), so give each XCD
-    // a contiguous run of logical blocks = a contiguous band of x rows whose chunk halos it re-reads
-    // from its own L2.  Placement only changes speed, never results.
-    const int bid = blockIdx.x;
-    const int L = (bid & 7) * a.nper + (bid >> 3);
-    if (L >= a.nblk) return;
-    const int zb = L % a.nzblk;
-    const int xb = L / a.nzblk;
-    const int wz = a.wz;              // waves of a block laid along z: 1, 2 or 4
-    const int strip = zb * wz + (w & (wz - 1));
-    const int chunk = xb * (4 / wz) + (w / wz);
-    const int zs = strip * 256;       // first z of this wave's strip
-    if (zs >= a.pitch) return;
-    const int xa = a.r0 + chunk * a.xchunk;
-    const int xe = min(xa + a.xchunk, a.r1);
-    if (xa >= xe) return;
+    FDW_STEP_TILE(a, sv, lane, zs, xa, xe)
     march<H, TAPER, INJ, IMG, LAPONLY, PF, DD, BACK, NUM>(a, sv, lane, zs, xa, xe);
 }
 
 // the forward step (FDW_MODE_FWD) that also records its trace samples (FDW_MODE_FWD_REC; batched like the others: rec + shot * rec_bstride).
-// Its own copy of fdw_step_kernel's tile placement: routing both kernels through one inlined function changes the register allocation
-// of the existing instantiations.
 template <int H, int PF, int NUM>
 __global__ __launch_bounds__(256) void fdw_step_rec_kernel(const StepArgs a)
 {
-    const int shot = blockIdx.y;
-    const long long o = shot * a.bstride;
-    const ShotView sv{a.p + o, a.pp + o, (a.out ? a.out : a.pp) + o, a.v2 + shot * a.v2_bstride, a.psrc + o, a.fpp + o, a.img + o, a.inj + shot * a.inj_bstride,
-                      a.inj_x + shot * a.inj_dx, a.rec + shot * a.rec_bstride};
-    const int lane = threadIdx.x & 63;
-    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-
-    const int bid = blockIdx.x;
-    const int L = (bid & 7) * a.nper + (bid >> 3);
-    if (L >= a.nblk) return;
-    const int zb = L % a.nzblk;
-    const int xb = L / a.nzblk;
-    const int wz = a.wz;
-    const int strip = zb * wz + (w & (wz - 1));
-    const int chunk = xb * (4 / wz) + (w / wz);
-    const int zs = strip * 256;
-    if (zs >= a.pitch) return;
-    const int xa = a.r0 + chunk * a.xchunk;
-    const int xe = min(xa + a.xchunk, a.r1);
-    if (xa >= xe) return;
+    FDW_STEP_TILE(a, sv, lane, zs, xa, xe)
     march<H, true, 1, false, false, PF, false, false, NUM, true>(a, sv, lane, zs, xa, xe);
 }
 
 // the forward step (FDW_MODE_FWD) that also accumulates the source illumination (FDW_MODE_FWD_ILLUM: a.img is the accumulator, +8 B/point/step).
-// Its own copy of the tile placement, like fdw_step_rec_kernel's.
 template <int H, int PF, int NUM>
 __global__ __launch_bounds__(256) void fdw_step_illum_kernel(const StepArgs a)
 {
-    const int shot = blockIdx.y;
-    const long long o = shot * a.bstride;
-    const ShotView sv{a.p + o, a.pp + o, (a.out ? a.out : a.pp) + o, a.v2 + shot * a.v2_bstride, a.psrc + o, a.fpp + o, a.img + o, a.inj + shot * a.inj_bstride,
-                      a.inj_x + shot * a.inj_dx, a.rec + shot * a.rec_bstride};
-    const int lane = threadIdx.x & 63;
-    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-
-    const int bid = blockIdx.x;
-    const int L = (bid & 7) * a.nper + (bid >> 3);
-    if (L >= a.nblk) return;
-    const int zb = L % a.nzblk;
-    const int xb = L / a.nzblk;
-    const int wz = a.wz;
-    const int strip = zb * wz + (w & (wz - 1));
-    const int chunk = xb * (4 / wz) + (w / wz);
-    const int zs = strip * 256;
-    if (zs >= a.pitch) return;
-    const int xa = a.r0 + chunk * a.xchunk;
-    const int xe = min(xa + a.xchunk, a.r1);
-    if (xa >= xe) return;
+    FDW_STEP_TILE(a, sv, lane, zs, xa, xe)
     march<H, true, 1, false, false, PF, false, false, NUM, false, true>(a, sv, lane, zs, xa, xe);
 }
 
 // the forward step that records its trace samples AND accumulates the source illumination (FDW_MODE_FWD_REC_ILLUM: the forward loop of
 // fdw_shot_residual with an accumulator): the sample is fdw_step_rec_kernel's single 32-bit store, the accumulator row rides the pointwise
-// queue as in fdw_step_illum_kernel.  Its own copy of the tile placement, like theirs.
+// queue as in fdw_step_illum_kernel.
 template <int H, int PF, int NUM>
 __global__ __launch_bounds__(256) void fdw_step_rec_illum_kernel(const StepArgs a)
 {
-    const int shot = blockIdx.y;
-    const long long o = shot * a.bstride;
-    const ShotView sv{a.p + o, a.pp + o, (a.out ? a.out : a.pp) + o, a.v2 + shot * a.v2_bstride, a.psrc + o, a.fpp + o, a.img + o, a.inj + shot * a.inj_bstride,
-                      a.inj_x + shot * a.inj_dx, a.rec + shot * a.rec_bstride};
-    const int lane = threadIdx.x & 63;
-    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-
-    const int bid = blockIdx.x;
-    const int L = (bid & 7) * a.nper + (bid >> 3);
-    if (L >= a.nblk) return;
-    const int zb = L % a.nzblk;
-    const int xb = L / a.nzblk;
-    const int wz = a.wz;
-    const int strip = zb * wz + (w & (wz - 1));
-    const int chunk = xb * (4 / wz) + (w / wz);
-    const int zs = strip * 256;
-    if (zs >= a.pitch) return;
-    const int xa = a.r0 + chunk * a.xchunk;
-    const int xe = min(xa + a.xchunk, a.r1);
-    if (xa >= xe) return;
+    FDW_STEP_TILE(a, sv, lane, zs, xa, xe)
     march<H, true, 1, false, false, PF, false, false, NUM, true, true>(a, sv, lane, zs, xa, xe);
 }
 
 // the forward step driven by a LINE source instead of the point source (FDW_MODE_FWD_LINE*: fdw_dev_line_steps): TAPER + INJ = 2 without imaging,
 // one sample per row of [inj_x, inj_x + inj_n) added on column inj_z after the leap-frog, exactly as the receiver pass adds its trace samples.
-// REC: the trace row of the new field, line sample included; ILL: its square into the accumulator (a.img).  Its own copy of the tile
-// placement, like fdw_step_rec_kernel's.
+// REC: the trace row of the new field, line sample included; ILL: its square into the accumulator (a.img).
 template <int H, int PF, bool REC, bool ILL, int NUM>
 __global__ __launch_bounds__(256) void fdw_step_line_kernel(const StepArgs a)
 {
-    const int shot = blockIdx.y;
-    const long long o = shot * a.bstride;
-    const ShotView sv{a.p + o, a.pp + o, (a.out ? a.out : a.pp) + o, a.v2 + shot * a.v2_bstride, a.psrc + o, a.fpp + o, a.img + o, a.inj + shot * a.inj_bstride,
-                      a.inj_x + shot * a.inj_dx, a.rec + shot * a.rec_bstride};
-    const int lane = threadIdx.x & 63;
-    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-
-    const int bid = blockIdx.x;
-    const int L = (bid & 7) * a.nper + (bid >> 3);
-    if (L >= a.nblk) return;
-    const int zb = L % a.nzblk;
-    const int xb = L / a.nzblk;
-    const int wz = a.wz;
-    const int strip = zb * wz + (w & (wz - 1));
-    const int chunk = xb * (4 / wz) + (w / wz);
-    const int zs = strip * 256;
-    if (zs >= a.pitch) return;
-    const int xa = a.r0 + chunk * a.xchunk;
-    const int xe = min(xa + a.xchunk, a.r1);
-    if (xa >= xe) return;
+    FDW_STEP_TILE(a, sv, lane, zs, xa, xe)
     march<H, true, 2, false, false, PF, false, false, NUM, REC, ILL>(a, sv, lane, zs, xa, xe);
 }
 
 // the line-source step that records its trace samples AND accumulates the source illumination (FDW_MODE_FWD_LINE_REC_ILLUM: the forward loop of
 // fdw_shot_line_residual with an accumulator, fdw_dev_line_record_illum_steps): fdw_step_rec_illum_kernel with INJ = 2 -- sample and square are
-// the stored new field, line sample included.  A kernel of its own name, as the point source's combined kernel is, with its own copy of the
-// tile placement.
+// the stored new field, line sample included.  A kernel of its own name, as the point source's combined kernel is.
 template <int H, int PF, int NUM>
 __global__ __launch_bounds__(256) void fdw_step_line_rec_illum_kernel(const StepArgs a)
 {
-    const int shot = blockIdx.y;
-    const long long o = shot * a.bstride;
-    const ShotView sv{a.p + o, a.pp + o, (a.out ? a.out : a.pp) + o, a.v2 + shot * a.v2_bstride, a.psrc + o, a.fpp + o, a.img + o, a.inj + shot * a.inj_bstride,
-                      a.inj_x + shot * a.inj_dx, a.rec + shot * a.rec_bstride};
-    const int lane = threadIdx.x & 63;
-    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-
-    const int bid = blockIdx.x;
-    const int L = (bid & 7) * a.nper + (bid >> 3);
-    if (L >= a.nblk) return;
-    const int zb = L % a.nzblk;
-    const int xb = L / a.nzblk;
-    const int wz = a.wz;
-    const int strip = zb * wz + (w & (wz - 1));
-    const int chunk = xb * (4 / wz) + (w / wz);
-    const int zs = strip * 256;
-    if (zs >= a.pitch) return;
-    const int xa = a.r0 + chunk * a.xchunk;
-    const int xe = min(xa + a.xchunk, a.r1);
-    if (xa >= xe) return;
+    FDW_STEP_TILE(a, sv, lane, zs, xa, xe)
     march<H, true, 2, false, false, PF, false, false, NUM, true, true>(a, sv, lane, zs, xa, xe);
 }
 
 // the forward step (FDW_MODE_FWD) that also keeps the excitation maps (FDW_MODE_FWD_EXC, fdw_dev_excite_steps): a.img is amp, a.texc the time
 // map, both read and written once per cell, +16 B/point/step.  One shot only (the callers refuse a batch: a.texc carries no shot stride).
-// Its own copy of the tile placement, like fdw_step_rec_kernel's.
 template <int H, int PF, int NUM>
 __global__ __launch_bounds__(256) void fdw_step_exc_kernel(const StepArgs a)
 {
-    const int shot = blockIdx.y;
-    const long long o = shot * a.bstride;
-    const ShotView sv{a.p + o, a.pp + o, (a.out ? a.out : a.pp) + o, a.v2 + shot * a.v2_bstride, a.psrc + o, a.fpp + o, a.img + o, a.inj + shot * a.inj_bstride,
-                      a.inj_x + shot * a.inj_dx, a.rec + shot * a.rec_bstride};
-    const int lane = threadIdx.x & 63;
-    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-
-    const int bid = blockIdx.x;
-    const int L = (bid & 7) * a.nper + (bid >> 3);
-    if (L >= a.nblk) return;
-    const int zb = L % a.nzblk;
-    const int xb = L / a.nzblk;
-    const int wz = a.wz;
-    const int strip = zb * wz + (w & (wz - 1));
-    const int chunk = xb * (4 / wz) + (w / wz);
-    const int zs = strip * 256;
-    if (zs >= a.pitch) return;
-    const int xa = a.r0 + chunk * a.xchunk;
-    const int xe = min(xa + a.xchunk, a.r1);
-    if (xa >= xe) return;
+    FDW_STEP_TILE(a, sv, lane, zs, xa, xe)
     march<H, true, 1, false, false, PF, false, false, NUM, false, false, 1>(a, sv, lane, zs, xa, xe);
 }
 
 // the line-source step that also takes the excitation pick (FDW_MODE_FWD_LINE_PICK, fdw_dev_line_pick_steps): fdw_step_line_kernel's step, then
-// exc = the new field, line sample included, where texc equals a.exc_key.  a.img is exc.  Its own copy of the tile placement.
+// exc = the new field, line sample included, where texc equals a.exc_key.  a.img is exc.
 template <int H, int PF, int NUM>
 __global__ __launch_bounds__(256) void fdw_step_line_pick_kernel(const StepArgs a)
 {
-    const int shot = blockIdx.y;
-    const long long o = shot * a.bstride;
-    const ShotView sv{a.p + o, a.pp + o, (a.out ? a.out : a.pp) + o, a.v2 + shot * a.v2_bstride, a.psrc + o, a.fpp + o, a.img + o, a.inj + shot * a.inj_bstride,
-                      a.inj_x + shot * a.inj_dx, a.rec + shot * a.rec_bstride};
-    const int lane = threadIdx.x & 63;
-    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-
-    const int bid = blockIdx.x;
-    const int L = (bid & 7) * a.nper + (bid >> 3);
-    if (L >= a.nblk) return;
-    const int zb = L % a.nzblk;
-    const int xb = L / a.nzblk;
-    const int wz = a.wz;
-    const int strip = zb * wz + (w & (wz - 1));
-    const int chunk = xb * (4 / wz) + (w / wz);
-    const int zs = strip * 256;
-    if (zs >= a.pitch) return;
-    const int xa = a.r0 + chunk * a.xchunk;
-    const int xe = min(xa + a.xchunk, a.r1);
-    if (xa >= xe) return;
+    FDW_STEP_TILE(a, sv, lane, zs, xa, xe)
     march<H, true, 2, false, false, PF, false, false, NUM, false, false, 2>(a, sv, lane, zs, xa, xe);
 }
 
@@ -848,33 +713,37 @@ __global__ void fdw_selftest_kernel(const float* src, float* out)
 // ------------------------------------------------------------------------------------------------
 // launchers
 // ------------------------------------------------------------------------------------------------
-#if FDW_TU == 0
-hipError_t launch_step_dd(const StepArgs& a, int h, int mode, int pf, hipStream_t s);        // fdw_step1_dd.o
-hipError_t launch_step_fastnum(const StepArgs& a, int h, int mode, hipStream_t s);           // fdw_step1_fast.o
-
-template <int H, int PF>
-static hipError_t launch_fast_hp(const StepArgs& a, int mode, hipStream_t s)
+// the mode table of the RTM dialect: exact arithmetic in FDW_TU 0, FAST numerics in FDW_TU 2 (NUM = 1: prefetch distance 2 only, the tuning knob
+// exists for the exact order-8 kernels)
+#if FDW_TU == 0 || FDW_TU == 2
+template <int H, int PF, int NUM>
+static hipError_t launch_rtm_hp(const StepArgs& a, int mode, hipStream_t s)
 {
     const dim3 grid(8 * a.nper, a.nbatch > 1 ? a.nbatch : 1), block(256);
     switch (mode) {
-    case FDW_MODE_FWD:   hipLaunchKernelGGL((fdw_step_kernel<H, true, 1, false, false, PF>), grid, block, 0, s, a); break;
-    case FDW_MODE_PLAIN: hipLaunchKernelGGL((fdw_step_kernel<H, false, 0, false, false, PF>), grid, block, 0, s, a); break;
-    case FDW_MODE_RECV:  hipLaunchKernelGGL((fdw_step_kernel<H, true, 2, true, false, PF>), grid, block, 0, s, a); break;
-    case FDW_MODE_LAP:   hipLaunchKernelGGL((fdw_step_kernel<H, false, 0, false, true, PF>), grid, block, 0, s, a); break;
-    case FDW_MODE_BACK:  hipLaunchKernelGGL((fdw_step_kernel<H, true, 2, true, false, PF, false, true>), grid, block, 0, s, a); break;
-    case FDW_MODE_FWD_REC: hipLaunchKernelGGL((fdw_step_rec_kernel<H, PF, 0>), grid, block, 0, s, a); break;
-    case FDW_MODE_FWD_ILLUM: hipLaunchKernelGGL((fdw_step_illum_kernel<H, PF, 0>), grid, block, 0, s, a); break;
-    case FDW_MODE_FWD_REC_ILLUM: hipLaunchKernelGGL((fdw_step_rec_illum_kernel<H, PF, 0>), grid, block, 0, s, a); break;
-    case FDW_MODE_FWD_LINE: hipLaunchKernelGGL((fdw_step_line_kernel<H, PF, false, false, 0>), grid, block, 0, s, a); break;
-    case FDW_MODE_FWD_LINE_REC: hipLaunchKernelGGL((fdw_step_line_kernel<H, PF, true, false, 0>), grid, block, 0, s, a); break;
-    case FDW_MODE_FWD_LINE_ILLUM: hipLaunchKernelGGL((fdw_step_line_kernel<H, PF, false, true, 0>), grid, block, 0, s, a); break;
-    case FDW_MODE_FWD_LINE_REC_ILLUM: hipLaunchKernelGGL((fdw_step_line_rec_illum_kernel<H, PF, 0>), grid, block, 0, s, a); break;
-    case FDW_MODE_FWD_EXC: hipLaunchKernelGGL((fdw_step_exc_kernel<H, PF, 0>), grid, block, 0, s, a); break;
-    case FDW_MODE_FWD_LINE_PICK: hipLaunchKernelGGL((fdw_step_line_pick_kernel<H, PF, 0>), grid, block, 0, s, a); break;
+    case FDW_MODE_FWD:   hipLaunchKernelGGL((fdw_step_kernel<H, true, 1, false, false, PF, false, false, NUM>), grid, block, 0, s, a); break;
+    case FDW_MODE_PLAIN: hipLaunchKernelGGL((fdw_step_kernel<H, false, 0, false, false, PF, false, false, NUM>), grid, block, 0, s, a); break;
+    case FDW_MODE_RECV:  hipLaunchKernelGGL((fdw_step_kernel<H, true, 2, true, false, PF, false, false, NUM>), grid, block, 0, s, a); break;
+    case FDW_MODE_LAP:   hipLaunchKernelGGL((fdw_step_kernel<H, false, 0, false, true, PF, false, false, NUM>), grid, block, 0, s, a); break;
+    case FDW_MODE_BACK:  hipLaunchKernelGGL((fdw_step_kernel<H, true, 2, true, false, PF, false, true, NUM>), grid, block, 0, s, a); break;
+    case FDW_MODE_FWD_REC: hipLaunchKernelGGL((fdw_step_rec_kernel<H, PF, NUM>), grid, block, 0, s, a); break;
+    case FDW_MODE_FWD_ILLUM: hipLaunchKernelGGL((fdw_step_illum_kernel<H, PF, NUM>), grid, block, 0, s, a); break;
+    case FDW_MODE_FWD_REC_ILLUM: hipLaunchKernelGGL((fdw_step_rec_illum_kernel<H, PF, NUM>), grid, block, 0, s, a); break;
+    case FDW_MODE_FWD_LINE: hipLaunchKernelGGL((fdw_step_line_kernel<H, PF, false, false, NUM>), grid, block, 0, s, a); break;
+    case FDW_MODE_FWD_LINE_REC: hipLaunchKernelGGL((fdw_step_line_kernel<H, PF, true, false, NUM>), grid, block, 0, s, a); break;
+    case FDW_MODE_FWD_LINE_ILLUM: hipLaunchKernelGGL((fdw_step_line_kernel<H, PF, false, true, NUM>), grid, block, 0, s, a); break;
+    case FDW_MODE_FWD_LINE_REC_ILLUM: hipLaunchKernelGGL((fdw_step_line_rec_illum_kernel<H, PF, NUM>), grid, block, 0, s, a); break;
+    case FDW_MODE_FWD_EXC: hipLaunchKernelGGL((fdw_step_exc_kernel<H, PF, NUM>), grid, block, 0, s, a); break;
+    case FDW_MODE_FWD_LINE_PICK: hipLaunchKernelGGL((fdw_step_line_pick_kernel<H, PF, NUM>), grid, block, 0, s, a); break;
     default: return hipErrorInvalidValue;
     }
     return hipGetLastError();
 }
+#endif
+
+#if FDW_TU == 0
+hipError_t launch_step_dd(const StepArgs& a, int h, int mode, int pf, hipStream_t s);        // fdw_step1_dd.o
+hipError_t launch_step_fastnum(const StepArgs& a, int h, int mode, hipStream_t s);           // fdw_step1_fast.o
 
 hipError_t launch_step_fast(const StepArgs& a, int h, int mode, int pf, hipStream_t s)
 {
@@ -883,40 +752,28 @@ hipError_t launch_step_fast(const StepArgs& a, int h, int mode, int pf, hipStrea
     if (a.numerics) return launch_step_fastnum(a, h, mode, s);
     if (h == 4) {
         switch (pf) {
-        case 1: return launch_fast_hp<4, 1>(a, mode, s);
-        case 3: return launch_fast_hp<4, 3>(a, mode, s);
-        default: return launch_fast_hp<4, 2>(a, mode, s);
+        case 1: return launch_rtm_hp<4, 1, 0>(a, mode, s);
+        case 3: return launch_rtm_hp<4, 3, 0>(a, mode, s);
+        default: return launch_rtm_hp<4, 2, 0>(a, mode, s);
         }
     }
     switch (h) {
-    case 1: return launch_fast_hp<1, 2>(a, mode, s);
-    case 2: return launch_fast_hp<2, 2>(a, mode, s);
-    case 3: return launch_fast_hp<3, 2>(a, mode, s);
+    case 1: return launch_rtm_hp<1, 2, 0>(a, mode, s);
+    case 2: return launch_rtm_hp<2, 2, 0>(a, mode, s);
+    case 3: return launch_rtm_hp<3, 2, 0>(a, mode, s);
     default: return hipErrorInvalidValue;
     }
 }
 #elif FDW_TU == 1
-template <int H, int PF>
+// the sibling's dialects; FAST numerics (NUM = 1, prefetch distance 2): the RTM dialect's symmetric-sum / fma chain on weights that carry their spacing
+template <int H, int PF, int NUM>
 static hipError_t launch_dd_hp(const StepArgs& a, int mode, hipStream_t s)
 {
     const dim3 grid(8 * a.nper, a.nbatch > 1 ? a.nbatch : 1), block(256);
     switch (mode) {
-    case FDW_MODE_MOD:     hipLaunchKernelGGL((fdw_step_kernel<H, true, 3, false, false, PF, true>), grid, block, 0, s, a); break;
-    case FDW_MODE_DD_FWD:  hipLaunchKernelGGL((fdw_step_kernel<H, true, 1, false, false, PF, true>), grid, block, 0, s, a); break;
-    case FDW_MODE_DD_RECV: hipLaunchKernelGGL((fdw_step_kernel<H, true, 2, true, false, PF, true>), grid, block, 0, s, a); break;
-    default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
-}
-// FAST numerics for these dialects (prefetch distance 2): the RTM dialect's symmetric-sum / fma chain on weights that carry their spacing
-template <int H>
-static hipError_t launch_dd_fast_h(const StepArgs& a, int mode, hipStream_t s)
-{
-    const dim3 grid(8 * a.nper, a.nbatch > 1 ? a.nbatch : 1), block(256);
-    switch (mode) {
-    case FDW_MODE_MOD:     hipLaunchKernelGGL((fdw_step_kernel<H, true, 3, false, false, 2, true, false, 1>), grid, block, 0, s, a); break;
-    case FDW_MODE_DD_FWD:  hipLaunchKernelGGL((fdw_step_kernel<H, true, 1, false, false, 2, true, false, 1>), grid, block, 0, s, a); break;
-    case FDW_MODE_DD_RECV: hipLaunchKernelGGL((fdw_step_kernel<H, true, 2, true, false, 2, true, false, 1>), grid, block, 0, s, a); break;
+    case FDW_MODE_MOD:     hipLaunchKernelGGL((fdw_step_kernel<H, true, 3, false, false, PF, true, false, NUM>), grid, block, 0, s, a); break;
+    case FDW_MODE_DD_FWD:  hipLaunchKernelGGL((fdw_step_kernel<H, true, 1, false, false, PF, true, false, NUM>), grid, block, 0, s, a); break;
+    case FDW_MODE_DD_RECV: hipLaunchKernelGGL((fdw_step_kernel<H, true, 2, true, false, PF, true, false, NUM>), grid, block, 0, s, a); break;
     default: return hipErrorInvalidValue;
     }
     return hipGetLastError();
@@ -925,59 +782,35 @@ hipError_t launch_step_dd(const StepArgs& a, int h, int mode, int pf, hipStream_
 {
     if (a.numerics) {
         switch (h) {
-        case 1: return launch_dd_fast_h<1>(a, mode, s);
-        case 2: return launch_dd_fast_h<2>(a, mode, s);
-        case 3: return launch_dd_fast_h<3>(a, mode, s);
-        case 4: return launch_dd_fast_h<4>(a, mode, s);
+        case 1: return launch_dd_hp<1, 2, 1>(a, mode, s);
+        case 2: return launch_dd_hp<2, 2, 1>(a, mode, s);
+        case 3: return launch_dd_hp<3, 2, 1>(a, mode, s);
+        case 4: return launch_dd_hp<4, 2, 1>(a, mode, s);
         default: return hipErrorInvalidValue;
         }
     }
     if (h == 4) {
         switch (pf) {
-        case 1: return launch_dd_hp<4, 1>(a, mode, s);
-        case 3: return launch_dd_hp<4, 3>(a, mode, s);
-        default: return launch_dd_hp<4, 2>(a, mode, s);
+        case 1: return launch_dd_hp<4, 1, 0>(a, mode, s);
+        case 3: return launch_dd_hp<4, 3, 0>(a, mode, s);
+        default: return launch_dd_hp<4, 2, 0>(a, mode, s);
         }
     }
     switch (h) {
-    case 1: return launch_dd_hp<1, 2>(a, mode, s);
-    case 2: return launch_dd_hp<2, 2>(a, mode, s);
-    case 3: return launch_dd_hp<3, 2>(a, mode, s);
+    case 1: return launch_dd_hp<1, 2, 0>(a, mode, s);
+    case 2: return launch_dd_hp<2, 2, 0>(a, mode, s);
+    case 3: return launch_dd_hp<3, 2, 0>(a, mode, s);
     default: return hipErrorInvalidValue;
     }
 }
 #elif FDW_TU == 2
-// FAST numerics: the same kernels with NUM = 1 (prefetch distance 2; the tuning knob only exists for the exact order-8 kernels)
-template <int H>
-static hipError_t launch_fastnum_h(const StepArgs& a, int mode, hipStream_t s)
-{
-    const dim3 grid(8 * a.nper, a.nbatch > 1 ? a.nbatch : 1), block(256);
-    switch (mode) {
-    case FDW_MODE_FWD:   hipLaunchKernelGGL((fdw_step_kernel<H, true, 1, false, false, 2, false, false, 1>), grid, block, 0, s, a); break;
-    case FDW_MODE_PLAIN: hipLaunchKernelGGL((fdw_step_kernel<H, false, 0, false, false, 2, false, false, 1>), grid, block, 0, s, a); break;
-    case FDW_MODE_RECV:  hipLaunchKernelGGL((fdw_step_kernel<H, true, 2, true, false, 2, false, false, 1>), grid, block, 0, s, a); break;
-    case FDW_MODE_LAP:   hipLaunchKernelGGL((fdw_step_kernel<H, false, 0, false, true, 2, false, false, 1>), grid, block, 0, s, a); break;
-    case FDW_MODE_BACK:  hipLaunchKernelGGL((fdw_step_kernel<H, true, 2, true, false, 2, false, true, 1>), grid, block, 0, s, a); break;
-    case FDW_MODE_FWD_REC: hipLaunchKernelGGL((fdw_step_rec_kernel<H, 2, 1>), grid, block, 0, s, a); break;
-    case FDW_MODE_FWD_ILLUM: hipLaunchKernelGGL((fdw_step_illum_kernel<H, 2, 1>), grid, block, 0, s, a); break;
-    case FDW_MODE_FWD_REC_ILLUM: hipLaunchKernelGGL((fdw_step_rec_illum_kernel<H, 2, 1>), grid, block, 0, s, a); break;
-    case FDW_MODE_FWD_LINE: hipLaunchKernelGGL((fdw_step_line_kernel<H, 2, false, false, 1>), grid, block, 0, s, a); break;
-    case FDW_MODE_FWD_LINE_REC: hipLaunchKernelGGL((fdw_step_line_kernel<H, 2, true, false, 1>), grid, block, 0, s, a); break;
-    case FDW_MODE_FWD_LINE_ILLUM: hipLaunchKernelGGL((fdw_step_line_kernel<H, 2, false, true, 1>), grid, block, 0, s, a); break;
-    case FDW_MODE_FWD_LINE_REC_ILLUM: hipLaunchKernelGGL((fdw_step_line_rec_illum_kernel<H, 2, 1>), grid, block, 0, s, a); break;
-    case FDW_MODE_FWD_EXC: hipLaunchKernelGGL((fdw_step_exc_kernel<H, 2, 1>), grid, block, 0, s, a); break;
-    case FDW_MODE_FWD_LINE_PICK: hipLaunchKernelGGL((fdw_step_line_pick_kernel<H, 2, 1>), grid, block, 0, s, a); break;
-    default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
-}
 hipError_t launch_step_fastnum(const StepArgs& a, int h, int mode, hipStream_t s)
 {
     switch (h) {
-    case 1: return launch_fastnum_h<1>(a, mode, s);
-    case 2: return launch_fastnum_h<2>(a, mode, s);
-    case 3: return launch_fastnum_h<3>(a, mode, s);
-    case 4: return launch_fastnum_h<4>(a, mode, s);
+    case 1: return launch_rtm_hp<1, 2, 1>(a, mode, s);
+    case 2: return launch_rtm_hp<2, 2, 1>(a, mode, s);
+    case 3: return launch_rtm_hp<3, 2, 1>(a, mode, s);
+    case 4: return launch_rtm_hp<4, 2, 1>(a, mode, s);
     default: return hipErrorInvalidValue;
     }
 }

@@ -265,21 +265,27 @@ __device__ __forceinline__ void march2(const Step2Args& a, const int lane, const
         static_for<R>([&](auto UU) { row_step(mb, UU); });
 }
 
+// Tile placement of the two-step kernels: a workgroup is four waves on four neighbouring strips of one chunk of rows.  Declares `lane`, the wave
+// index `w`, its `strip` and the rows [`xa`, `xe`) and leaves the kernel where the wave has no tile (no barrier follows: waves return alone).
+// The XCD remap is the pipeline kernels'; a macro for the reason written down there (FDW_PIPE_TILE, fdw_stepn.hip).
+#define FDW_STEP2_TILE(a, lane, w, strip, xa, xe)                   \
+    const int lane = threadIdx.x & 63;                              \
+    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6); \
+    const int bid = blockIdx.x;                                     \
+    const int L = (bid & 7) * a.nper + (bid >> 3);                  \
+    if (L >= a.nblk) return;                                        \
+    const int zb = L % a.nzblk;                                     \
+    const int xb = L / a.nzblk;                                     \
+    const int strip = zb * 4 + w;                                   \
+    if (strip >= a.nstrip) return;                                  \
+    const int xa = a.r0 + xb * a.xchunk;                            \
+    const int xe = min(xa + a.xchunk, a.r1);                        \
+    if (xa >= xe) return;
+
 template <int H, bool TAPER, int INJ, bool IMG, int PF, int NUM, bool REC>
 __device__ __forceinline__ void step2_tile(const Step2Args& a)
 {
-    const int lane = threadIdx.x & 63;
-    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int bid = blockIdx.x;
-    const int L = (bid & 7) * a.nper + (bid >> 3);
-    if (L >= a.nblk) return;
-    const int zb = L % a.nzblk;
-    const int xb = L / a.nzblk;
-    const int strip = zb * 4 + w;
-    if (strip >= a.nstrip) return;
-    const int xa = a.r0 + xb * a.xchunk;
-    const int xe = min(xa + a.xchunk, a.r1);
-    if (xa >= xe) return;
+    FDW_STEP2_TILE(a, lane, w, strip, xa, xe)
     // per-wave LDS slab: 8 rows x 64 lanes x 16 B for the v2 rows waiting between step 1 (row s) and step 2 (row s-H)
     __shared__ f4 v2_stash[4][8 * 64];
     march2<H, TAPER, INJ, IMG, PF, NUM, REC>(a, lane, strip * 60 - 2, xa, xe, v2_stash[w]);
@@ -298,47 +304,25 @@ __global__ __launch_bounds__(256, 4) void fdw_step2_rec_kernel(const Step2Args a
     step2_tile<4, true, 1, false, 2, NUM, true>(a);
 }
 
-// FDW_MODE_FWD_ILLUM: the forward pass that also accumulates the source illumination of both steps.  Its own tile placement (see
-// fdw_stepn_rec_kernel); 64 KiB of LDS per workgroup (the v2 rows and the accumulator rows in waiting), two workgroups per CU.
+// FDW_MODE_FWD_ILLUM: the forward pass that also accumulates the source illumination of both steps.  64 KiB of LDS per workgroup (the v2 rows
+// and the accumulator rows in waiting), two workgroups per CU.
 template <int NUM>
 __global__ __launch_bounds__(256, 2) void fdw_step2_illum_kernel(const Step2Args a)
 {
-    const int lane = threadIdx.x & 63;
-    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int bid = blockIdx.x;
-    const int L = (bid & 7) * a.nper + (bid >> 3);
-    if (L >= a.nblk) return;
-    const int zb = L % a.nzblk;
-    const int xb = L / a.nzblk;
-    const int strip = zb * 4 + w;
-    if (strip >= a.nstrip) return;
-    const int xa = a.r0 + xb * a.xchunk;
-    const int xe = min(xa + a.xchunk, a.r1);
-    if (xa >= xe) return;
+    FDW_STEP2_TILE(a, lane, w, strip, xa, xe)
     __shared__ f4 v2_stash[4][8 * 64];
     __shared__ f4 ill_stash[4][8 * 64];
     march2<4, true, 1, false, 2, NUM, false, true>(a, lane, strip * 60 - 2, xa, xe, v2_stash[w], ill_stash[w]);
 }
 
 // FDW_MODE_FWD_LINE*: the forward pass driven by a line source (INJ = 2 without imaging: inj -> u^{n+1}, inj2 -> u^{n+2}), plain, with the
-// trace samples of both steps or with their illumination.  Its own tile placement (see fdw_stepn_rec_kernel); ILL: the second LDS slab and two
-// workgroups per CU as in fdw_step2_illum_kernel.  Otherwise three workgroups per CU like the receiver pass, not the point source's four: at
-// 128 VGPRs the FAST plain body spills one VGPR to scratch (the per-row sample loads of both steps keep more scalars alive).
+// trace samples of both steps or with their illumination.  ILL: the second LDS slab and two workgroups per CU as in fdw_step2_illum_kernel.
+// Otherwise three workgroups per CU like the receiver pass, not the point source's four: at 128 VGPRs the FAST plain body spills one VGPR to
+// scratch (the per-row sample loads of both steps keep more scalars alive).
 template <bool REC, bool ILL, int NUM>
 __global__ __launch_bounds__(256, ILL ? 2 : 3) void fdw_step2_line_kernel(const Step2Args a)
 {
-    const int lane = threadIdx.x & 63;
-    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int bid = blockIdx.x;
-    const int L = (bid & 7) * a.nper + (bid >> 3);
-    if (L >= a.nblk) return;
-    const int zb = L % a.nzblk;
-    const int xb = L / a.nzblk;
-    const int strip = zb * 4 + w;
-    if (strip >= a.nstrip) return;
-    const int xa = a.r0 + xb * a.xchunk;
-    const int xe = min(xa + a.xchunk, a.r1);
-    if (xa >= xe) return;
+    FDW_STEP2_TILE(a, lane, w, strip, xa, xe)
     __shared__ f4 v2_stash[4][8 * 64];
     if constexpr (ILL) {
         __shared__ f4 ill_stash[4][8 * 64];
@@ -350,60 +334,40 @@ __global__ __launch_bounds__(256, ILL ? 2 : 3) void fdw_step2_line_kernel(const 
 
 // FDW_MODE_FWD_LINE_REC_ILLUM: the line-source pass that records the trace samples of both steps AND accumulates their illumination
 // (fdw_dev_line_record_illum_steps, fdw_shot_line_residual with an accumulator).  The LDS slabs and the two workgroups per CU of
-// fdw_step2_illum_kernel, which leave the body 256 VGPRs; its own tile placement and its own name, as the point source's combined kernels have.
+// fdw_step2_illum_kernel, which leave the body 256 VGPRs; its own name, as the point source's combined kernels have.
 template <int NUM>
 __global__ __launch_bounds__(256, 2) void fdw_step2_line_rec_illum_kernel(const Step2Args a)
 {
-    const int lane = threadIdx.x & 63;
-    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int bid = blockIdx.x;
-    const int L = (bid & 7) * a.nper + (bid >> 3);
-    if (L >= a.nblk) return;
-    const int zb = L % a.nzblk;
-    const int xb = L / a.nzblk;
-    const int strip = zb * 4 + w;
-    if (strip >= a.nstrip) return;
-    const int xa = a.r0 + xb * a.xchunk;
-    const int xe = min(xa + a.xchunk, a.r1);
-    if (xa >= xe) return;
+    FDW_STEP2_TILE(a, lane, w, strip, xa, xe)
     __shared__ f4 v2_stash[4][8 * 64];
     __shared__ f4 ill_stash[4][8 * 64];
     march2<4, true, 2, false, 2, NUM, true, true>(a, lane, strip * 60 - 2, xa, xe, v2_stash[w], ill_stash[w]);
+}
+
+template <int NUM>
+static hipError_t launch_step2_num(const Step2Args& a, int mode, hipStream_t s)
+{
+    const dim3 grid(8 * a.nper), block(256);
+    switch (mode) {
+    case FDW_MODE_FWD:   hipLaunchKernelGGL((fdw_step2_kernel<4, true, 1, false, 2, NUM>), grid, block, 0, s, a); break;
+    case FDW_MODE_PLAIN: hipLaunchKernelGGL((fdw_step2_kernel<4, false, 0, false, 2, NUM>), grid, block, 0, s, a); break;
+    case FDW_MODE_RECV:  hipLaunchKernelGGL((fdw_step2_kernel<4, true, 2, true, 2, NUM>), grid, block, 0, s, a); break;
+    case FDW_MODE_FWD_REC: hipLaunchKernelGGL((fdw_step2_rec_kernel<NUM>), grid, block, 0, s, a); break;
+    case FDW_MODE_FWD_ILLUM: hipLaunchKernelGGL((fdw_step2_illum_kernel<NUM>), grid, block, 0, s, a); break;
+    case FDW_MODE_FWD_LINE: hipLaunchKernelGGL((fdw_step2_line_kernel<false, false, NUM>), grid, block, 0, s, a); break;
+    case FDW_MODE_FWD_LINE_REC: hipLaunchKernelGGL((fdw_step2_line_kernel<true, false, NUM>), grid, block, 0, s, a); break;
+    case FDW_MODE_FWD_LINE_ILLUM: hipLaunchKernelGGL((fdw_step2_line_kernel<false, true, NUM>), grid, block, 0, s, a); break;
+    case FDW_MODE_FWD_LINE_REC_ILLUM: hipLaunchKernelGGL((fdw_step2_line_rec_illum_kernel<NUM>), grid, block, 0, s, a); break;
+    default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
 }
 
 hipError_t launch_step2(const Step2Args& a, int h, int mode, hipStream_t s)
 {
     if (a.nper <= 0) return hipSuccess;
     if (h != 4) return hipErrorInvalidValue;
-    const dim3 grid(8 * a.nper), block(256);
-    if (a.numerics) {      // FAST numerics (fdw_device.h)
-        switch (mode) {
-        case FDW_MODE_FWD:   hipLaunchKernelGGL((fdw_step2_kernel<4, true, 1, false, 2, 1>), grid, block, 0, s, a); break;
-        case FDW_MODE_PLAIN: hipLaunchKernelGGL((fdw_step2_kernel<4, false, 0, false, 2, 1>), grid, block, 0, s, a); break;
-        case FDW_MODE_RECV:  hipLaunchKernelGGL((fdw_step2_kernel<4, true, 2, true, 2, 1>), grid, block, 0, s, a); break;
-        case FDW_MODE_FWD_REC: hipLaunchKernelGGL((fdw_step2_rec_kernel<1>), grid, block, 0, s, a); break;
-        case FDW_MODE_FWD_ILLUM: hipLaunchKernelGGL((fdw_step2_illum_kernel<1>), grid, block, 0, s, a); break;
-        case FDW_MODE_FWD_LINE: hipLaunchKernelGGL((fdw_step2_line_kernel<false, false, 1>), grid, block, 0, s, a); break;
-        case FDW_MODE_FWD_LINE_REC: hipLaunchKernelGGL((fdw_step2_line_kernel<true, false, 1>), grid, block, 0, s, a); break;
-        case FDW_MODE_FWD_LINE_ILLUM: hipLaunchKernelGGL((fdw_step2_line_kernel<false, true, 1>), grid, block, 0, s, a); break;
-        case FDW_MODE_FWD_LINE_REC_ILLUM: hipLaunchKernelGGL((fdw_step2_line_rec_illum_kernel<1>), grid, block, 0, s, a); break;
-        default: return hipErrorInvalidValue;
-        }
-        return hipGetLastError();
-    }
-    switch (mode) {
-    case FDW_MODE_FWD:   hipLaunchKernelGGL((fdw_step2_kernel<4, true, 1, false, 2>), grid, block, 0, s, a); break;
-    case FDW_MODE_PLAIN: hipLaunchKernelGGL((fdw_step2_kernel<4, false, 0, false, 2>), grid, block, 0, s, a); break;
-    case FDW_MODE_RECV:  hipLaunchKernelGGL((fdw_step2_kernel<4, true, 2, true, 2>), grid, block, 0, s, a); break;
-    case FDW_MODE_FWD_REC: hipLaunchKernelGGL((fdw_step2_rec_kernel<0>), grid, block, 0, s, a); break;
-    case FDW_MODE_FWD_ILLUM: hipLaunchKernelGGL((fdw_step2_illum_kernel<0>), grid, block, 0, s, a); break;
-    case FDW_MODE_FWD_LINE: hipLaunchKernelGGL((fdw_step2_line_kernel<false, false, 0>), grid, block, 0, s, a); break;
-    case FDW_MODE_FWD_LINE_REC: hipLaunchKernelGGL((fdw_step2_line_kernel<true, false, 0>), grid, block, 0, s, a); break;
-    case FDW_MODE_FWD_LINE_ILLUM: hipLaunchKernelGGL((fdw_step2_line_kernel<false, true, 0>), grid, block, 0, s, a); break;
-    case FDW_MODE_FWD_LINE_REC_ILLUM: hipLaunchKernelGGL((fdw_step2_line_rec_illum_kernel<0>), grid, block, 0, s, a); break;
-    default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    return a.numerics ? launch_step2_num<1>(a, mode, s) : launch_step2_num<0>(a, mode, s);      // FAST numerics (fdw_device.h)
 }
 
 }  // namespace fdw

@@ -421,29 +421,39 @@ constexpr int kPipeWG = 5;
 constexpr int kDDWG = 4;
 constexpr int kPipePF = 2;      // rows of global look-ahead of wave 0
 
+// Tile placement of the pipeline kernels: which strip and rows a workgroup works on, and which wave of it this is.  Declares `lane`, the wave
+// index `k` (wave-uniform), the first cell `cs` of the strip and the rows [`xa`, `xe`) of the chunk; leaves the kernel where the workgroup
+// has no tile.  Blocks b and b + 8 share an XCD (round-robin dispatch), so XCD x takes the logical blocks [x nper, (x + 1) nper): a contiguous
+// band of chunks whose halo rows it re-reads from its own L2.  Whole workgroups return (L and the tile are workgroup-uniform), so every barrier
+// of the march is reached by all its waves.  From L on the text is the host's too (FDW_PIPE_TILE_ROWS, fdw_kernels.h).
+// A macro and not a function, on evidence: as a __forceinline__ function that returns the six values in a struct, 0 of the 30 kernels of this
+// file (and 2 of 56 of the FAST one-step unit) keep their instruction text -- scalar register numbering and scheduling move; as a function that
+// takes the kernel's body as a lambda, 0 of 4 sampled kernels keep it; expanded as a macro, every kernel is byte-identical to the hand-written
+// copies it replaces (scripts/kernel_diff.py, profiles/r16_resource_report.txt).  The same holds for FDW_STEP_TILE and FDW_STEP2_TILE.
+// For the same reason the pair `if (k == 0) marchn<..., WK 1, ...>(...); else marchn<..., WK 2, ...>(...);` stays written out at its 15 sites:
+// behind one __forceinline__ function template over the remaining arguments, 24 of the 30 kernels change their text (2 their SGPR spills).
+#define FDW_PIPE_TILE(a, NS, lane, k, cs, xa, xe)                                   \
+    const int lane = threadIdx.x & 63;                                              \
+    const int k = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);                 \
+    const int bid = blockIdx.x;                                                     \
+    const int L = (bid & 7) * a.nper + (bid >> 3);                                  \
+    if (L >= a.nblk) return;                                                        \
+    FDW_PIPE_TILE_ROWS(a, L, zb, xa, xe)                                            \
+    if (xa >= xe) return;                                                           \
+    const int cs = FDW_PIPE_TILE_CELL(zb, NS);
+
 template <int H, int NS, bool TAPER, int INJ, int PF, bool DD = false, int BK = 0, int NUM = 0>
 __global__ __launch_bounds__(64 * NS, BK == 2 ? 3 : (DD ? kDDWG : kPipeWG)) void fdw_stepn_kernel(const Step2Args a)
 {
-    const int lane = threadIdx.x & 63;
-    const int k = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int bid = blockIdx.x;
-    const int L = (bid & 7) * a.nper + (bid >> 3);
-    if (L >= a.nblk) return;                    // whole workgroups only: every barrier below is reached by all NS waves
-    const int zb = L % a.nstrip;
-    const int xb = L / a.nstrip;
-    const bool second = xb >= a.chunks_a;       // two row ranges in one launch (the two boundary strips of a slab)
-    const int xa = second ? a.r0b + (xb - a.chunks_a) * a.xchunk : a.r0 + xb * a.xchunk;
-    const int xe = min(xa + a.xchunk, second ? a.r1b : a.r1);
-    if (xa >= xe) return;
+    FDW_PIPE_TILE(a, NS, lane, k, cs, xa, xe)
     __shared__ f4 link[NS][2][2][64];                      // [producer wave][parity][0 new row | 1 row leaving the window][lane]
     __shared__ f4 fifo[pipe_fifo_rows(NS, H)][64];
     if constexpr (BK == 2) {
         __shared__ f4 imf[16][64];                         // image rows on their way from wave to wave (a row is 3 (H + 1) = 15 steps under way)
-        marchn<H, NS, TAPER, INJ, PF, DD, BK, false, 0, NUM>(a, lane, k, zb * (64 - 2 * NS) - NS, xa, xe, link, fifo, imf);
+        marchn<H, NS, TAPER, INJ, PF, DD, BK, false, 0, NUM>(a, lane, k, cs, xa, xe, link, fifo, imf);
     } else if constexpr (BK == 0) {
         // nine workgroups in ten of a large grid touch neither the frame, nor the damped strip, nor the source: they take the lean body,
         // compiled once for wave 0 and once for the other waves (the modelling dialect: one body for all four)
-        const int cs = zb * (64 - 2 * NS) - NS;
         if (pipe_lean<H, NS, TAPER, INJ, DD>(a, cs, xa, xe)) {
             if constexpr (!DD) {
                 if (k == 0) marchn<H, NS, false, 0, PF, DD, 0, true, 1, NUM>(a, lane, k, cs, xa, xe, link, fifo);
@@ -460,32 +470,20 @@ __global__ __launch_bounds__(64 * NS, BK == 2 ? 3 : (DD ? kDDWG : kPipeWG)) void
             else marchn<H, NS, TAPER, INJ, PF, false, 0, false, 2, NUM>(a, lane, k, cs, xa, xe, link, fifo);
         }
     } else {
-        marchn<H, NS, TAPER, INJ, PF, DD, BK, false, 0, NUM>(a, lane, k, zb * (64 - 2 * NS) - NS, xa, xe, link, fifo);
+        marchn<H, NS, TAPER, INJ, PF, DD, BK, false, 0, NUM>(a, lane, k, cs, xa, xe, link, fifo);
     }
 }
 
 // FDW_MODE_FWD_REC: the forward pass that also records the trace samples of its kPipeSteps steps.  The tiles whose owned lanes hold the
-// receiver column run the full body with recording, the others fdw_stepn_kernel's lean bodies.  (Its own copy of the tile placement: routing
-// both kernels through one inlined function changes the register allocation of the existing instantiations.)  Four workgroups per CU, not
+// receiver column run the full body with recording, the others fdw_stepn_kernel's lean bodies.  Four workgroups per CU, not
 // kPipeWG: at 96 VGPRs the recording full body spills one VGPR to scratch (its SGPRs, at the limit of 106, spill into VGPR lanes); DESIGN.md 6f.
 template <int NUM>
 __global__ __launch_bounds__(64 * kPipeSteps, kDDWG) void fdw_stepn_rec_kernel(const Step2Args a)
 {
     constexpr int H = 4, NS = kPipeSteps, PF = kPipePF;
-    const int lane = threadIdx.x & 63;
-    const int k = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int bid = blockIdx.x;
-    const int L = (bid & 7) * a.nper + (bid >> 3);
-    if (L >= a.nblk) return;
-    const int zb = L % a.nstrip;
-    const int xb = L / a.nstrip;
-    const bool second = xb >= a.chunks_a;
-    const int xa = second ? a.r0b + (xb - a.chunks_a) * a.xchunk : a.r0 + xb * a.xchunk;
-    const int xe = min(xa + a.xchunk, second ? a.r1b : a.r1);
-    if (xa >= xe) return;
+    FDW_PIPE_TILE(a, NS, lane, k, cs, xa, xe)
     __shared__ f4 link[NS][2][2][64];
     __shared__ f4 fifo[pipe_fifo_rows(NS, H)][64];
-    const int cs = zb * (64 - 2 * NS) - NS;
     if (pipe_lean<H, NS, true, 1, false, true>(a, cs, xa, xe)) {
         if (k == 0) marchn<H, NS, false, 0, PF, false, 0, true, 1, NUM>(a, lane, k, cs, xa, xe, link, fifo);
         else marchn<H, NS, false, 0, PF, false, 0, true, 2, NUM>(a, lane, k, cs, xa, xe, link, fifo);
@@ -495,27 +493,15 @@ __global__ __launch_bounds__(64 * kPipeSteps, kDDWG) void fdw_stepn_rec_kernel(c
 
 // FDW_MODE_FWD_ILLUM: the forward pass that also accumulates the source illumination of its kPipeSteps steps (a.img).  Every tile carries the
 // accumulator row: the lean tiles add the squares without masks, the tiles on the frame, the damped strip or the source with the update masks
-// of the full body.  16 KiB of LDS more than fdw_stepn_kernel (48 KiB): three workgroups per CU, so up to 168 VGPRs.  Its own tile placement
-// (see fdw_stepn_rec_kernel).
+// of the full body.  16 KiB of LDS more than fdw_stepn_kernel (48 KiB): three workgroups per CU, so up to 168 VGPRs.
 template <int NUM>
 __global__ __launch_bounds__(64 * kPipeSteps, 3) void fdw_stepn_illum_kernel(const Step2Args a)
 {
     constexpr int H = 4, NS = kPipeSteps, PF = kPipePF;
-    const int lane = threadIdx.x & 63;
-    const int k = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int bid = blockIdx.x;
-    const int L = (bid & 7) * a.nper + (bid >> 3);
-    if (L >= a.nblk) return;
-    const int zb = L % a.nstrip;
-    const int xb = L / a.nstrip;
-    const bool second = xb >= a.chunks_a;
-    const int xa = second ? a.r0b + (xb - a.chunks_a) * a.xchunk : a.r0 + xb * a.xchunk;
-    const int xe = min(xa + a.xchunk, second ? a.r1b : a.r1);
-    if (xa >= xe) return;
+    FDW_PIPE_TILE(a, NS, lane, k, cs, xa, xe)
     __shared__ f4 link[NS][2][2][64];
     __shared__ f4 fifo[pipe_fifo_rows(NS, H)][64];
     __shared__ f4 ilf[16][64];                             // accumulator rows on their way from wave to wave (3 (H + 1) = 15 steps under way)
-    const int cs = zb * (64 - 2 * NS) - NS;
     if (pipe_lean<H, NS, true, 1>(a, cs, xa, xe)) {
         if (k == 0) marchn<H, NS, false, 0, PF, false, 0, true, 1, NUM, false, true>(a, lane, k, cs, xa, xe, link, fifo, ilf);
         else marchn<H, NS, false, 0, PF, false, 0, true, 2, NUM, false, true>(a, lane, k, cs, xa, xe, link, fifo, ilf);
@@ -527,26 +513,15 @@ __global__ __launch_bounds__(64 * kPipeSteps, 3) void fdw_stepn_illum_kernel(con
 // (the forward loop of fdw_shot_residual with an accumulator).  Every tile carries the accumulator row through the 16-slot LDS FIFO as in
 // fdw_stepn_illum_kernel (48 KiB of LDS, three workgroups per CU, the square taken before the hand-over); the tiles whose owned lanes hold the
 // receiver column run the full body, in which wave k also records row k of the pass as in fdw_stepn_rec_kernel; all others run
-// fdw_stepn_illum_kernel's bodies, lean where the tile allows.  Its own tile placement (see fdw_stepn_rec_kernel).
+// fdw_stepn_illum_kernel's bodies, lean where the tile allows.
 template <int NUM>
 __global__ __launch_bounds__(64 * kPipeSteps, 3) void fdw_stepn_rec_illum_kernel(const Step2Args a)
 {
     constexpr int H = 4, NS = kPipeSteps, PF = kPipePF;
-    const int lane = threadIdx.x & 63;
-    const int k = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int bid = blockIdx.x;
-    const int L = (bid & 7) * a.nper + (bid >> 3);
-    if (L >= a.nblk) return;
-    const int zb = L % a.nstrip;
-    const int xb = L / a.nstrip;
-    const bool second = xb >= a.chunks_a;
-    const int xa = second ? a.r0b + (xb - a.chunks_a) * a.xchunk : a.r0 + xb * a.xchunk;
-    const int xe = min(xa + a.xchunk, second ? a.r1b : a.r1);
-    if (xa >= xe) return;
+    FDW_PIPE_TILE(a, NS, lane, k, cs, xa, xe)
     __shared__ f4 link[NS][2][2][64];
     __shared__ f4 fifo[pipe_fifo_rows(NS, H)][64];
     __shared__ f4 ilf[16][64];
-    const int cs = zb * (64 - 2 * NS) - NS;
     if (pipe_lean<H, NS, true, 1, false, true>(a, cs, xa, xe)) {
         if (k == 0) marchn<H, NS, false, 0, PF, false, 0, true, 1, NUM, false, true>(a, lane, k, cs, xa, xe, link, fifo, ilf);
         else marchn<H, NS, false, 0, PF, false, 0, true, 2, NUM, false, true>(a, lane, k, cs, xa, xe, link, fifo, ilf);
@@ -559,26 +534,15 @@ __global__ __launch_bounds__(64 * kPipeSteps, 3) void fdw_stepn_rec_illum_kernel
 // tiles of the strip that holds the line (and those on the frame and in the damped strip) run the full body; the others keep the lean bodies
 // of fdw_stepn_kernel (plain, REC) or of fdw_stepn_illum_kernel (ILL).  REC: wave k records row k of the pass after the injection, full body
 // where the owned lanes hold the receiver column; ILL: the accumulator row rides the 16-slot LDS FIFO, the square taken after the injection.
-// Workgroups per CU as the point-source kernels of the same variant.  Its own tile placement (see fdw_stepn_rec_kernel).
+// Workgroups per CU as the point-source kernels of the same variant.
 template <bool REC, bool ILL, int NUM>
 __global__ __launch_bounds__(64 * kPipeSteps, ILL ? 3 : (REC ? kDDWG : kPipeWG)) void fdw_stepn_line_kernel(const Step2Args a)
 {
     static_assert(!(REC && ILL), "recording and illumination together are not built for the line source");
     constexpr int H = 4, NS = kPipeSteps, PF = kPipePF;
-    const int lane = threadIdx.x & 63;
-    const int k = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int bid = blockIdx.x;
-    const int L = (bid & 7) * a.nper + (bid >> 3);
-    if (L >= a.nblk) return;
-    const int zb = L % a.nstrip;
-    const int xb = L / a.nstrip;
-    const bool second = xb >= a.chunks_a;
-    const int xa = second ? a.r0b + (xb - a.chunks_a) * a.xchunk : a.r0 + xb * a.xchunk;
-    const int xe = min(xa + a.xchunk, second ? a.r1b : a.r1);
-    if (xa >= xe) return;
+    FDW_PIPE_TILE(a, NS, lane, k, cs, xa, xe)
     __shared__ f4 link[NS][2][2][64];
     __shared__ f4 fifo[pipe_fifo_rows(NS, H)][64];
-    const int cs = zb * (64 - 2 * NS) - NS;
     const bool lean = pipe_lean<H, NS, true, 2, false, REC>(a, cs, xa, xe);
     if constexpr (ILL) {
         __shared__ f4 ilf[16][64];
@@ -604,26 +568,15 @@ __global__ __launch_bounds__(64 * kPipeSteps, ILL ? 3 : (REC ? kDDWG : kPipeWG))
 // (fdw_dev_line_record_illum_steps, fdw_shot_line_residual with an accumulator): fdw_stepn_rec_illum_kernel with INJ = 2.  The tiles of the
 // strip that holds the line, of the strip whose owned lanes hold the receiver column, on the frame and in the damped strip run the full body,
 // in which wave k injects, records row k of the pass and squares, in that order; all others run fdw_stepn_illum_kernel's lean bodies.  48 KiB
-// of LDS, three workgroups per CU.  Its own tile placement and its own name (see fdw_stepn_rec_kernel).
+// of LDS, three workgroups per CU.  A kernel of its own name, as the point source's combined kernel is.
 template <int NUM>
 __global__ __launch_bounds__(64 * kPipeSteps, 3) void fdw_stepn_line_rec_illum_kernel(const Step2Args a)
 {
     constexpr int H = 4, NS = kPipeSteps, PF = kPipePF;
-    const int lane = threadIdx.x & 63;
-    const int k = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int bid = blockIdx.x;
-    const int L = (bid & 7) * a.nper + (bid >> 3);
-    if (L >= a.nblk) return;
-    const int zb = L % a.nstrip;
-    const int xb = L / a.nstrip;
-    const bool second = xb >= a.chunks_a;
-    const int xa = second ? a.r0b + (xb - a.chunks_a) * a.xchunk : a.r0 + xb * a.xchunk;
-    const int xe = min(xa + a.xchunk, second ? a.r1b : a.r1);
-    if (xa >= xe) return;
+    FDW_PIPE_TILE(a, NS, lane, k, cs, xa, xe)
     __shared__ f4 link[NS][2][2][64];
     __shared__ f4 fifo[pipe_fifo_rows(NS, H)][64];
     __shared__ f4 ilf[16][64];
-    const int cs = zb * (64 - 2 * NS) - NS;
     if (pipe_lean<H, NS, true, 2, false, true>(a, cs, xa, xe)) {
         if (k == 0) marchn<H, NS, false, 0, PF, false, 0, true, 1, NUM, false, true>(a, lane, k, cs, xa, xe, link, fifo, ilf);
         else marchn<H, NS, false, 0, PF, false, 0, true, 2, NUM, false, true>(a, lane, k, cs, xa, xe, link, fifo, ilf);
@@ -634,27 +587,16 @@ __global__ __launch_bounds__(64 * kPipeSteps, 3) void fdw_stepn_line_rec_illum_k
 // FDW_MODE_FWD_EXC: the forward pass that also keeps the excitation maps of its kPipeSteps steps (a.img = amp, a.texc; marchn, EXC 1).  Every
 // tile carries the amp row through the 16-slot LDS FIFO as fdw_stepn_illum_kernel carries its accumulator, and beside it a dword of tags per
 // lane and row: 16 + 16 + 16 + 4 = 52 KiB of LDS, three workgroups per CU (156 of the CU's 160 KiB).  Lean tiles compare without masks, the
-// tiles on the frame, the damped strip or the source with the update masks of the full body.  Its own tile placement (see fdw_stepn_rec_kernel).
+// tiles on the frame, the damped strip or the source with the update masks of the full body.
 template <int NUM>
 __global__ __launch_bounds__(64 * kPipeSteps, 3) void fdw_stepn_exc_kernel(const Step2Args a)
 {
     constexpr int H = 4, NS = kPipeSteps, PF = kPipePF;
-    const int lane = threadIdx.x & 63;
-    const int k = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int bid = blockIdx.x;
-    const int L = (bid & 7) * a.nper + (bid >> 3);
-    if (L >= a.nblk) return;
-    const int zb = L % a.nstrip;
-    const int xb = L / a.nstrip;
-    const bool second = xb >= a.chunks_a;
-    const int xa = second ? a.r0b + (xb - a.chunks_a) * a.xchunk : a.r0 + xb * a.xchunk;
-    const int xe = min(xa + a.xchunk, second ? a.r1b : a.r1);
-    if (xa >= xe) return;
+    FDW_PIPE_TILE(a, NS, lane, k, cs, xa, xe)
     __shared__ f4 link[NS][2][2][64];
     __shared__ f4 fifo[pipe_fifo_rows(NS, H)][64];
     __shared__ f4 amf[16][64];                             // amp rows on their way from wave to wave (3 (H + 1) = 15 steps under way)
     __shared__ unsigned tgf[16][64];                       // ... and their tags
-    const int cs = zb * (64 - 2 * NS) - NS;
     if (pipe_lean<H, NS, true, 1>(a, cs, xa, xe)) {
         if (k == 0) marchn<H, NS, false, 0, PF, false, 0, true, 1, NUM, false, false, 1>(a, lane, k, cs, xa, xe, link, fifo, amf, nullptr, tgf);
         else marchn<H, NS, false, 0, PF, false, 0, true, 2, NUM, false, false, 1>(a, lane, k, cs, xa, xe, link, fifo, amf, nullptr, tgf);
@@ -667,27 +609,16 @@ __global__ __launch_bounds__(64 * kPipeSteps, 3) void fdw_stepn_exc_kernel(const
 
 // FDW_MODE_FWD_LINE_PICK: the line-source pass that also takes the excitation pick of its kPipeSteps steps (a.img = exc, a.texc read only;
 // marchn, EXC 2): fdw_stepn_line_kernel's tiles (full body in the strip that holds the line, on the frame and in the damped strip, lean
-// elsewhere), every tile carrying the exc row and the tags wave 0 formed.  52 KiB of LDS, three workgroups per CU.  Its own tile placement.
+// elsewhere), every tile carrying the exc row and the tags wave 0 formed.  52 KiB of LDS, three workgroups per CU.
 template <int NUM>
 __global__ __launch_bounds__(64 * kPipeSteps, 3) void fdw_stepn_line_pick_kernel(const Step2Args a)
 {
     constexpr int H = 4, NS = kPipeSteps, PF = kPipePF;
-    const int lane = threadIdx.x & 63;
-    const int k = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int bid = blockIdx.x;
-    const int L = (bid & 7) * a.nper + (bid >> 3);
-    if (L >= a.nblk) return;
-    const int zb = L % a.nstrip;
-    const int xb = L / a.nstrip;
-    const bool second = xb >= a.chunks_a;
-    const int xa = second ? a.r0b + (xb - a.chunks_a) * a.xchunk : a.r0 + xb * a.xchunk;
-    const int xe = min(xa + a.xchunk, second ? a.r1b : a.r1);
-    if (xa >= xe) return;
+    FDW_PIPE_TILE(a, NS, lane, k, cs, xa, xe)
     __shared__ f4 link[NS][2][2][64];
     __shared__ f4 fifo[pipe_fifo_rows(NS, H)][64];
     __shared__ f4 exf[16][64];
     __shared__ unsigned tgf[16][64];
-    const int cs = zb * (64 - 2 * NS) - NS;
     if (pipe_lean<H, NS, true, 2>(a, cs, xa, xe)) {
         if (k == 0) marchn<H, NS, false, 0, PF, false, 0, true, 1, NUM, false, false, 2>(a, lane, k, cs, xa, xe, link, fifo, exf, nullptr, tgf);
         else marchn<H, NS, false, 0, PF, false, 0, true, 2, NUM, false, false, 2>(a, lane, k, cs, xa, xe, link, fifo, exf, nullptr, tgf);
@@ -703,22 +634,11 @@ __global__ __launch_bounds__(64 * kPipeSteps, 3) void fdw_stepn_line_pick_kernel
 template <int H, int NS, int PF, int NUM = 0>
 __global__ __launch_bounds__(128 * NS, 2) void fdw_back4_kernel(const Step2Args a)
 {
-    const int lane = threadIdx.x & 63;
-    const int k8 = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int bid = blockIdx.x;
-    const int L = (bid & 7) * a.nper + (bid >> 3);
-    if (L >= a.nblk) return;
-    const int zb = L % a.nstrip;
-    const int xb = L / a.nstrip;
-    const bool second = xb >= a.chunks_a;
-    const int xa = second ? a.r0b + (xb - a.chunks_a) * a.xchunk : a.r0 + xb * a.xchunk;
-    const int xe = min(xa + a.xchunk, second ? a.r1b : a.r1);
-    if (xa >= xe) return;
+    FDW_PIPE_TILE(a, NS, lane, k8, cs, xa, xe)
     __shared__ f4 linkF[NS][2][2][64];
     __shared__ f4 linkR[NS][2][2][64];
     __shared__ f4 fifo[kFusedFifoRows][64];
     __shared__ f4 imf[16][64];
-    const int cs = zb * (64 - 2 * NS) - NS;
     // each role runs the lean body (compiled once for its wave 0 and once for its other waves) where its tile allows
     if (k8 < NS) {
         if (pipe_lean<H, NS, false, 0>(a, cs, xa, xe)) {
@@ -738,51 +658,36 @@ __global__ __launch_bounds__(128 * NS, 2) void fdw_back4_kernel(const Step2Args 
     }
 }
 
+template <int NUM>
+static hipError_t launch_stepn_num(const Step2Args& a, int mode, hipStream_t s)
+{
+    const dim3 grid(8 * a.nper), block(64 * kPipeSteps);
+    switch (mode) {
+    case FDW_MODE_FWD:   hipLaunchKernelGGL((fdw_stepn_kernel<4, kPipeSteps, true, 1, kPipePF, false, 0, NUM>), grid, block, 0, s, a); break;
+    case FDW_MODE_FWD_REC: hipLaunchKernelGGL((fdw_stepn_rec_kernel<NUM>), grid, block, 0, s, a); break;
+    case FDW_MODE_FWD_ILLUM: hipLaunchKernelGGL((fdw_stepn_illum_kernel<NUM>), grid, block, 0, s, a); break;
+    case FDW_MODE_FWD_REC_ILLUM: hipLaunchKernelGGL((fdw_stepn_rec_illum_kernel<NUM>), grid, block, 0, s, a); break;
+    case FDW_MODE_FWD_LINE: hipLaunchKernelGGL((fdw_stepn_line_kernel<false, false, NUM>), grid, block, 0, s, a); break;
+    case FDW_MODE_FWD_LINE_REC: hipLaunchKernelGGL((fdw_stepn_line_kernel<true, false, NUM>), grid, block, 0, s, a); break;
+    case FDW_MODE_FWD_LINE_ILLUM: hipLaunchKernelGGL((fdw_stepn_line_kernel<false, true, NUM>), grid, block, 0, s, a); break;
+    case FDW_MODE_FWD_LINE_REC_ILLUM: hipLaunchKernelGGL((fdw_stepn_line_rec_illum_kernel<NUM>), grid, block, 0, s, a); break;
+    case FDW_MODE_FWD_EXC: hipLaunchKernelGGL((fdw_stepn_exc_kernel<NUM>), grid, block, 0, s, a); break;
+    case FDW_MODE_FWD_LINE_PICK: hipLaunchKernelGGL((fdw_stepn_line_pick_kernel<NUM>), grid, block, 0, s, a); break;
+    case FDW_MODE_PLAIN: hipLaunchKernelGGL((fdw_stepn_kernel<4, kPipeSteps, false, 0, kPipePF, false, 0, NUM>), grid, block, 0, s, a); break;
+    case FDW_MODE_MOD:   hipLaunchKernelGGL((fdw_stepn_kernel<4, kPipeSteps, true, 3, kPipePF, true, 0, NUM>), grid, block, 0, s, a); break;
+    case FDW_MODE_PLAIN_ALL: hipLaunchKernelGGL((fdw_stepn_kernel<4, kPipeSteps, false, 0, kPipePF, false, 1, NUM>), grid, block, 0, s, a); break;
+    case FDW_MODE_RECV:  hipLaunchKernelGGL((fdw_stepn_kernel<4, kPipeSteps, true, 2, kPipePF, false, 2, NUM>), grid, block, 0, s, a); break;
+    case FDW_MODE_BACK4: hipLaunchKernelGGL((fdw_back4_kernel<4, kPipeSteps, kPipePF, NUM>), grid, dim3(128 * kPipeSteps), 0, s, a); break;
+    default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+
 hipError_t launch_stepn(const Step2Args& a, int h, int mode, hipStream_t s)
 {
     if (a.nper <= 0) return hipSuccess;
     if (h != 4) return hipErrorInvalidValue;
-    const dim3 grid(8 * a.nper), block(64 * kPipeSteps);
-    if (a.numerics) {      // FAST numerics (fdw_device.h): the same kernels with NUM = 1
-        switch (mode) {
-        case FDW_MODE_FWD:   hipLaunchKernelGGL((fdw_stepn_kernel<4, kPipeSteps, true, 1, kPipePF, false, 0, 1>), grid, block, 0, s, a); break;
-        case FDW_MODE_FWD_REC: hipLaunchKernelGGL((fdw_stepn_rec_kernel<1>), grid, block, 0, s, a); break;
-        case FDW_MODE_FWD_ILLUM: hipLaunchKernelGGL((fdw_stepn_illum_kernel<1>), grid, block, 0, s, a); break;
-        case FDW_MODE_FWD_REC_ILLUM: hipLaunchKernelGGL((fdw_stepn_rec_illum_kernel<1>), grid, block, 0, s, a); break;
-        case FDW_MODE_FWD_LINE: hipLaunchKernelGGL((fdw_stepn_line_kernel<false, false, 1>), grid, block, 0, s, a); break;
-        case FDW_MODE_FWD_LINE_REC: hipLaunchKernelGGL((fdw_stepn_line_kernel<true, false, 1>), grid, block, 0, s, a); break;
-        case FDW_MODE_FWD_LINE_ILLUM: hipLaunchKernelGGL((fdw_stepn_line_kernel<false, true, 1>), grid, block, 0, s, a); break;
-        case FDW_MODE_FWD_LINE_REC_ILLUM: hipLaunchKernelGGL((fdw_stepn_line_rec_illum_kernel<1>), grid, block, 0, s, a); break;
-        case FDW_MODE_FWD_EXC: hipLaunchKernelGGL((fdw_stepn_exc_kernel<1>), grid, block, 0, s, a); break;
-        case FDW_MODE_FWD_LINE_PICK: hipLaunchKernelGGL((fdw_stepn_line_pick_kernel<1>), grid, block, 0, s, a); break;
-        case FDW_MODE_PLAIN: hipLaunchKernelGGL((fdw_stepn_kernel<4, kPipeSteps, false, 0, kPipePF, false, 0, 1>), grid, block, 0, s, a); break;
-        case FDW_MODE_MOD:   hipLaunchKernelGGL((fdw_stepn_kernel<4, kPipeSteps, true, 3, kPipePF, true, 0, 1>), grid, block, 0, s, a); break;
-        case FDW_MODE_PLAIN_ALL: hipLaunchKernelGGL((fdw_stepn_kernel<4, kPipeSteps, false, 0, kPipePF, false, 1, 1>), grid, block, 0, s, a); break;
-        case FDW_MODE_RECV:  hipLaunchKernelGGL((fdw_stepn_kernel<4, kPipeSteps, true, 2, kPipePF, false, 2, 1>), grid, block, 0, s, a); break;
-        case FDW_MODE_BACK4: hipLaunchKernelGGL((fdw_back4_kernel<4, kPipeSteps, kPipePF, 1>), grid, dim3(128 * kPipeSteps), 0, s, a); break;
-        default: return hipErrorInvalidValue;
-        }
-        return hipGetLastError();
-    }
-    switch (mode) {
-    case FDW_MODE_FWD:   hipLaunchKernelGGL((fdw_stepn_kernel<4, kPipeSteps, true, 1, kPipePF>), grid, block, 0, s, a); break;
-    case FDW_MODE_FWD_REC: hipLaunchKernelGGL((fdw_stepn_rec_kernel<0>), grid, block, 0, s, a); break;
-    case FDW_MODE_FWD_ILLUM: hipLaunchKernelGGL((fdw_stepn_illum_kernel<0>), grid, block, 0, s, a); break;
-    case FDW_MODE_FWD_REC_ILLUM: hipLaunchKernelGGL((fdw_stepn_rec_illum_kernel<0>), grid, block, 0, s, a); break;
-    case FDW_MODE_FWD_LINE: hipLaunchKernelGGL((fdw_stepn_line_kernel<false, false, 0>), grid, block, 0, s, a); break;
-    case FDW_MODE_FWD_LINE_REC: hipLaunchKernelGGL((fdw_stepn_line_kernel<true, false, 0>), grid, block, 0, s, a); break;
-    case FDW_MODE_FWD_LINE_ILLUM: hipLaunchKernelGGL((fdw_stepn_line_kernel<false, true, 0>), grid, block, 0, s, a); break;
-    case FDW_MODE_FWD_LINE_REC_ILLUM: hipLaunchKernelGGL((fdw_stepn_line_rec_illum_kernel<0>), grid, block, 0, s, a); break;
-    case FDW_MODE_FWD_EXC: hipLaunchKernelGGL((fdw_stepn_exc_kernel<0>), grid, block, 0, s, a); break;
-    case FDW_MODE_FWD_LINE_PICK: hipLaunchKernelGGL((fdw_stepn_line_pick_kernel<0>), grid, block, 0, s, a); break;
-    case FDW_MODE_PLAIN: hipLaunchKernelGGL((fdw_stepn_kernel<4, kPipeSteps, false, 0, kPipePF>), grid, block, 0, s, a); break;
-    case FDW_MODE_MOD:   hipLaunchKernelGGL((fdw_stepn_kernel<4, kPipeSteps, true, 3, kPipePF, true>), grid, block, 0, s, a); break;
-    case FDW_MODE_PLAIN_ALL: hipLaunchKernelGGL((fdw_stepn_kernel<4, kPipeSteps, false, 0, kPipePF, false, 1>), grid, block, 0, s, a); break;
-    case FDW_MODE_RECV:  hipLaunchKernelGGL((fdw_stepn_kernel<4, kPipeSteps, true, 2, kPipePF, false, 2>), grid, block, 0, s, a); break;
-    case FDW_MODE_BACK4: hipLaunchKernelGGL((fdw_back4_kernel<4, kPipeSteps, kPipePF>), grid, dim3(128 * kPipeSteps), 0, s, a); break;
-    default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    return a.numerics ? launch_stepn_num<1>(a, mode, s) : launch_stepn_num<0>(a, mode, s);      // FAST numerics (fdw_device.h): the same kernels with NUM = 1
 }
 
 }  // namespace fdw
