@@ -319,7 +319,7 @@ int fdw_download_field(fdw_ctx *ctx, float *h_dst, const float *d_src);
  * fdw_batch_parts           how many batched launch sequences the last batched call on this context went through: 0 = its shots ran one
  *                           by one (nshots == 1, a regime the batched launches do not cover, or no room on the device), 1 = the whole
  *                           batch at once, k = k parts (a last part of a single shot counts).  Written by every batched call.
- * Who splits.  fdw_shot_batch_illum, fdw_shot_batch_residual, fdw_shot_line_batch and fdw_shot_line_batch_residual hold more per shot than
+ * Who splits.  fdw_shot_batch_illum, fdw_shot_batch_residual, fdw_shot_line_batch, fdw_shot_line_batch_residual and fdw_shot_excitation_batch hold more per shot than
  * the eleven fields fdw_shot_batch_max counts and cut a batch that exceeds the budget into parts themselves.  fdw_shot_batch,
  * fdw_record_shot_batch, fdw_record_shot_line_batch and fdw_model_shot_batch have NO part loop: they take `nshots` whole, whatever the
  * budget says (fdw_batch_parts 1 or 0); their callers walk the shots in groups of at most fdw_shot_batch_max.
@@ -657,7 +657,7 @@ int fdw_encode_gathers_multi(int device, int nshots, int nplanes, const int *lag
  * it occurred (the excitation time); the backward loop propagates the receiver field ALONE, and every cell takes one sample of it, at its
  * excitation time, divided by the peak.  No source field is reconstructed, no product is accumulated, and the image is source-normalised as
  * it comes.  The RTM dialect on full-grid contexts, EXACT and FAST numerics alike (FAST changes the Laplacian only).  Slab contexts, the
- * sibling's dialects and a context inside a batch: FDW_ESTATE.  A NULL required pointer, it0 < 0, a depth outside [0, zlim) (as for line
+ * sibling's dialects and (but for fdw_shot_excitation_batch itself) a context inside a batch: FDW_ESTATE.  A NULL required pointer, it0 < 0, a depth outside [0, zlim) (as for line
  * sources), a source row the loop never time-steps: FDW_EINVAL.  Every refusal happens before anything is enqueued.
  *
  * Excitation maps.  Two field-shaped device arrays [nxl][pitch], d_amp (float) and d_texc (int32).  Over every extended-grid cell with
@@ -687,21 +687,59 @@ int fdw_encode_gathers_multi(int device, int nshots, int nplanes, const int *lag
  *   plain loop's.  Traffic: +16 B/point per forward pass (amp and texc, in and out), +12 B/point per pick pass (texc and exc in, exc out).
  *   Measured on one MI355X at 8192^2, order 8 (profiles/excitation.json): the forward loop with the maps 142.5 us
  *   per step against 96.6 plain and 123.1 with illumination (FAST 135.8 / 86.8 / 115.4); the line loop with the pick 129.8 against 97.0
- *   (FAST 123.8 / 86.6).  A whole fdw_shot_excitation of 500 steps takes 266.8 ms against fdw_shot's 187.2 ms (FAST 257.4 / 174.1): the
- *   device loops are 0.85 of fdw_shot's, but three interior arrays come back instead of one and the image is formed on the host, so the
- *   shot is 1.43x SLOWER, not cheaper; on a 415 x 295 deck (nt 1700) the two are level (19.8 against 19.5 ms).
+ *   (FAST 123.8 / 86.6): the two device loops are 0.85 of fdw_shot's.  A whole fdw_shot_excitation of 500 steps with imloc alone takes
+ *   177.8 ms against fdw_shot's 185.6 ms (FAST 173.7 / 169.0; DESIGN.md section 6r, profiles/excitation.json key image_on_device): level with
+ *   the cross-correlation shot since the image is formed on the device and ONE array comes back, where it took 255.4 ms (FAST 252.0) with
+ *   three downloads and the image formed on the host; a caller that asks for exc, amp and texc still pays for those downloads (251.9 ms).
+ *   On a 415 x 295 deck (nt 1700) the shot takes 19.5 ms against fdw_shot's 19.3 (FAST 19.6 / 18.8).
  * fdw_shot_excitation       One shot from rest: the forward loop of fdw_shot for nt steps with the maps; the receiver fields zeroed; nt
  *                           iterations of the pick loop with top = nt, row k of the line gather = d_obs[.][nt-1-k], at depth gz.  Iteration
  *                           k meets the cells whose excitation level is nt - k: sample j pairs with level u^{j+1}, as in the recording
  *                           section.  Receiver rows the loop never time-steps (ix >= nsrc) are NOT injected -- the line-source rule, which
  *                           differs from fd_back on ragged compat grids.  v2 NULL: the resident model.  P / PP: fdw_shot's.  exc, amp,
- *                           texc: the interiors [nx][nz]; imloc is then updated by fdw_image_excitation.  Each of the four may be NULL,
- *                           all four NULL is FDW_EINVAL.  The work arrays are allocated on first use.
+ *                           texc: the interiors [nx][nz]; imloc is updated as fdw_image_excitation would, bit for bit, but on the device
+ *                           (fdw_dev_image_excitation on the context's image accumulator) and comes back as ONE array; exc, amp and texc
+ *                           are downloaded only where asked for.  Each of the four may be NULL, all four NULL is FDW_EINVAL.  The line
+ *                           gather is reversed in time on the device.  The work arrays are allocated on first use.
  * fdw_image_excitation      Pure host C, no device.  m = max_i fabsf(amp[i]) taken from 0.0f with > (a NaN never wins); s = eps * m; for each
  *                           i with fabsf(amp[i]) > s: img[i] = img[i] + exc[i] / amp[i], one fp32 division and one fp32 add.  Every other
  *                           img[i] is left untouched (no + 0.0f: -0.0 survives).  eps not finite or < 0: FDW_EINVAL.  Shots stack by calling
  *                           it per shot into one img.
- * Out of scope: batches, slabs, maps under a line source, a combined recording + maps kernel, a two-step excitation kernel. */
+ * fdw_dev_image_excitation  fdw_image_excitation on device arrays.  d_exc, d_amp, d_img: field-shaped [nxl][pitch].  On the interior cells (rows
+ *                           nxb .. nxb+nx-1, columns nzb .. nzb+nz-1) the result is fdw_image_excitation's on the interiors, bit for bit:
+ *                           m = max |amp| over the INTERIOR only, from 0.0f with > (a NaN never wins; border cells and padding columns do not
+ *                           count, although the maps are written over the whole update extents), s = eps * m (one fp32 product), where
+ *                           fabsf(amp) > s: img = img + exc / amp.  The quotient is formed in double and rounded once, which for fp32
+ *                           operands is the correctly rounded fp32 quotient (fp64 has 53 >= 2 * 24 + 2 significand bits).  Every other word
+ *                           of d_img keeps its bits: unselected interior cells (-0.0 stays -0.0), the border, the padding.  d_exc and d_amp
+ *                           are only read.  Two launches behind a memset of one word: the peak as an unsigned maximum of the words |amp|
+ *                           (order-independent, so deterministic), then the update.  stream == NULL: the context's stream; everything goes
+ *                           on the given stream, nothing is synchronised, nothing is allocated.  The context holds ONE peak word: calls on
+ *                           different streams must not overlap.  eps not finite or < 0, a NULL pointer: FDW_EINVAL; a slab context,
+ *                           another dialect, a context inside a batch: FDW_ESTATE -- before anything is enqueued.
+ * fdw_shot_excitation_batch `nshots` excitation shots stacked into one image.  Shot b: source row sx0 + b dsx, gather d_obs + b nx nt, model
+ *                           v2_all + b nxe nze or (v2_all == NULL) the border model of draws [draw_offset + b T, ...) on the resident model --
+ *                           what fdw_shot_batch takes.  imloc [nx][nz]: the running image, in and out.  stack (may be NULL) [nshots][nx][nz]:
+ *                           the running image after each shot.  exc, amp, texc (each may be NULL) [nshots][nx][nz]: the per-shot interiors.
+ *                           Every output equals, bit for bit, the sequence for b = 0 .. nshots-1: fdw_shot_excitation of shot b, then
+ *                           fdw_image_excitation into the one running image.  On the RTM dialect's full-grid contexts of order <= 8 in the
+ *                           one-step regime (neither the pipeline nor the two-step family pays; no forced generic kernel) the forward loop
+ *                           with the maps and the line loop with the pick are ONE launch per time step for all shots, followed by the peak
+ *                           and the update kernel over all shots in shot order; elsewhere, and where the device has no room, the shots run
+ *                           one by one through fdw_shot_excitation's own code.  Ragged compat grids batch too: the pick loop injects only
+ *                           the receiver rows the loop time-steps, in a batch as alone.  fdw_batch_parts reports as for the other batched
+ *                           calls (0 one by one, 1 the whole batch, k parts).  Memory: the call works in fdw_shot_batch's buffers, so per
+ *                           shot it holds that call's ELEVEN fields (it uses eight: two source fields, two receiver fields, v2, amp, texc and
+ *                           exc, the last of which then takes the running images) and ONE gather [nt][nx]; a batch over the batch budget
+ *                           (fdw_set_batch_budget) is cut by the call itself into parts of budget / (11 fields + 1 gather) shots, run in
+ *                           shot order with the running image carried from part to part; under a budget below ONE shot's share the call
+ *                           takes no batch buffers and runs the shots one by one (fdw_batch_parts 0).  A NULL required pointer (srce, d_obs, imloc),
+ *                           nshots < 1, a source row outside the time-stepped rows, a depth outside [0, zlim), a bad eps: FDW_EINVAL; no
+ *                           model, a slab context, another dialect: FDW_ESTATE -- before anything is enqueued.
+ *   Measured on one MI355X (profiles/excitation_batch.json), 415 x 295 interior, nt 1700, 32 shots: 4.67 ms per shot
+ *   against 18.98 ms one by one (FAST 4.81 / 18.92), beside fdw_shot_batch's 3.99 ms (FAST 3.87).
+ * Out of scope: slabs, maps under a line source, a combined recording + maps kernel, a two-step excitation kernel, batches in the pipeline
+ * and generic-order families. */
 int fdw_dev_excite_steps(fdw_ctx *ctx, float *const *d_buf /* [4] */, const float *d_v2, const float *d_srce, int sx, int sz, float *d_amp,
                          int *d_texc, int it0, int nsteps, int first_pp_twice, int *ip, int *ipp, void *stream);
 int fdw_dev_line_pick_steps(fdw_ctx *ctx, float *const *d_buf /* [4] */, const float *d_v2, const float *d_wav, int sz, const int *d_texc, int top,
@@ -709,6 +747,9 @@ int fdw_dev_line_pick_steps(fdw_ctx *ctx, float *const *d_buf /* [4] */, const f
 int fdw_shot_excitation(fdw_ctx *ctx, const float *v2 /* NULL: the resident model */, int sx, int sz, int gz, const float *srce, const float *d_obs,
                         float eps, float *imloc, float *exc, float *amp, int *texc, float *P, float *PP);
 int fdw_image_excitation(const float *exc, const float *amp, size_t n, float eps, float *img);
+int fdw_dev_image_excitation(fdw_ctx *ctx, const float *d_exc, const float *d_amp, float eps, float *d_img, void *stream);
+int fdw_shot_excitation_batch(fdw_ctx *ctx, int nshots, const float *v2_all, unsigned long long draw_offset, int sx0, int dsx, int sz, int gz,
+                              const float *srce, const float *d_obs, float eps, float *imloc, float *stack, float *exc, float *amp, int *texc);
 
 /* ---- tuning / introspection --------------------------------------------------------------------
  * fdw_set_tuning  xchunk = rows marched per wave (0 = auto), wz = waves of a block laid along z

@@ -158,6 +158,8 @@ SIGNATURES = [
     ("fdw_dev_line_pick_steps", C.c_int, [vp, C.POINTER(vp), vp, vp, C.c_int, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), vp]),
     ("fdw_shot_excitation", C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_float, vp, vp, vp, vp, vp, vp]),
     ("fdw_image_excitation", C.c_int, [vp, vp, C.c_size_t, C.c_float, vp]),
+    ("fdw_dev_image_excitation", C.c_int, [vp, vp, vp, C.c_float, vp, vp]),
+    ("fdw_shot_excitation_batch", C.c_int, [vp, C.c_int, vp, C.c_ulonglong, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_float, vp, vp, vp, vp, vp]),
     ("fdw_two_step_active", C.c_int, [vp]),
     ("fdw_steps_per_pass", C.c_int, [vp]),
     ("fdw_selftest", C.c_int, [vp]),

@@ -520,13 +520,49 @@ class FDWave:
                                             C.byref(b), stream))
         return a.value, b.value
 
-    def shot_excitation(self, v2, sx, sz, gz, srce, d_obs, eps=1e-3, imloc=None, want_fields=False):
+    def dev_image_excitation(self, d_exc, d_amp, eps, d_img, stream=None):
+        """The excitation-amplitude image of one shot on device arrays [nxl][pitch] (fdwave.h, fdw_dev_image_excitation): on the interior,
+        d_img += d_exc / d_amp where |d_amp| > eps * max |d_amp|; every other word of d_img keeps its bits.
+        stream=None: the context's own non-blocking stream, unordered against the caller's streams (the legacy default stream included); a caller's
+        stream: every launch, copy and memset of the call is issued on it and the call does not synchronise (fdwave.h)."""
+        check(lib().fdw_dev_image_excitation(self._h, d_exc, d_amp, eps, d_img, stream))
+
+    def shot_excitation_batch(self, nshots, sx0, dsx, sz, gz, srce, d_obs, eps=1e-3, v2_all=None, draw_offset=0, imloc=None, want_stack=True,
+                              want_maps=True):
+        """`nshots` excitation-amplitude shots stacked into one image in shot order, through one launch per time step where shot_batch()
+        batches (fdwave.h, fdw_shot_excitation_batch).  d_obs[nshots][nx][nt]; models as shot_batch() takes them.  Returns a dict: image
+        [nx][nz] (a copy of imloc, zeros if None, with every shot's image added), and as asked stack [nshots][nx][nz] (the running image after
+        each shot) and exc, amp, texc [nshots][nx][nz]."""
+        inner = (self.nx, self.nz)
+        out = {"image": np.zeros(inner, np.float32) if imloc is None else np.array(_f32(imloc, inner), order="C")}
+        if want_stack:
+            out["stack"] = np.zeros((nshots,) + inner, np.float32)
+        if want_maps:
+            out["exc"], out["amp"], out["texc"] = (np.zeros((nshots,) + inner, t) for t in (np.float32, np.float32, np.int32))
+
+        def ptr(name):
+            return out[name].ctypes.data if name in out else None
+
+        v2p = None if v2_all is None else _f32(v2_all, (nshots, self.nxe, self.nze)).ctypes.data
+        srce = _f32(srce, (self.nt,))
+        d_obs = _f32(d_obs, (nshots, self.nx, self.nt))
+        check(lib().fdw_shot_excitation_batch(self._h, nshots, v2p, int(draw_offset), sx0, dsx, sz, gz, srce.ctypes.data, d_obs.ctypes.data, eps,
+                                              ptr("image"), ptr("stack"), ptr("exc"), ptr("amp"), ptr("texc")))
+        return out
+
+    def shot_excitation(self, v2, sx, sz, gz, srce, d_obs, eps=1e-3, imloc=None, want_fields=False, want_maps=True):
         """One shot under the excitation-amplitude imaging condition (fdwave.h, fdw_shot_excitation); v2=None: the resident model.  Returns
         (imloc, exc, amp, texc), the interiors [nx][nz] (texc int32), and with want_fields also P, PP as shot() returns them.  imloc (a copy of
-        the one passed in, zeros if None) has the shot's image added to it."""
+        the one passed in, zeros if None) has the shot's image added to it.  want_maps=False: only the image comes back (one download);
+        exc, amp and texc are None."""
         shape = (self.nxe, self.nze)
         inner = (self.nx, self.nz)
         imloc = np.zeros(inner, np.float32) if imloc is None else np.array(_f32(imloc, inner), order="C")
+        if not want_maps:
+            srce, d_obs = _f32(srce, (self.nt,)), _f32(d_obs, inner[:1] + (self.nt,))
+            check(lib().fdw_shot_excitation(self._h, None if v2 is None else _f32(v2, shape).ctypes.data, sx, sz, gz, srce.ctypes.data, d_obs.ctypes.data,
+                                            eps, imloc.ctypes.data, None, None, None, None, None))
+            return imloc, None, None, None
         exc, amp, texc = np.zeros(inner, np.float32), np.zeros(inner, np.float32), np.zeros(inner, np.int32)
         P = np.zeros(shape, np.float32) if want_fields else None
         PP = np.zeros(shape, np.float32) if want_fields else None

@@ -18,6 +18,7 @@
 #include <type_traits>
 #include <vector>
 
+#include "fdw_excimg.h"
 #include "fdw_internal.h"
 #include "fdw_kernels.h"
 #include "fdwave.h"
@@ -78,6 +79,8 @@ struct fdw_ctx {
     float* d_amp = nullptr;     // excitation maps and picked samples of one shot on the extended grid (fdw_shot_excitation); allocated on first use
     int* d_texc = nullptr;
     float* d_exc = nullptr;
+    unsigned* d_peak = nullptr;   // max |amp| per shot as a word (fdw_dev_image_excitation, fdw_shot_excitation_batch); one word from creation on
+    int peak_cap = 0;
     float* d_snap[3] = {nullptr, nullptr, nullptr};   // frame stores of fdw_shot_snaps (snaps, snaps_rec, snapr): [nframes][nxs][nzs] each
     size_t snap_cap[3] = {0, 0, 0};
     size_t srce_cap = 0, dobs_cap = 0;
@@ -328,6 +331,8 @@ extern "C" int fdw_create_slab(const fdw_params* prm, const fdw_slab* slab, int 
     CREATE_TRY(hipMemcpy(c->d_txfac, c->txfac.data(), c->nxl * sizeof(float), hipMemcpyHostToDevice));
     CREATE_TRY(hipMemcpy(c->d_gcx, c->cx, (FDW_MAX_ORDER + 1) * sizeof(float), hipMemcpyHostToDevice));
     CREATE_TRY(hipMemcpy(c->d_gcz, c->cz, (FDW_MAX_ORDER + 1) * sizeof(float), hipMemcpyHostToDevice));
+    CREATE_TRY(hipMalloc((void**)&c->d_peak, sizeof(unsigned)));      // so that fdw_dev_image_excitation never allocates
+    c->peak_cap = 1;
 #undef CREATE_TRY
     *out = c;
     return FDW_OK;
@@ -380,7 +385,7 @@ extern "C" void fdw_destroy(fdw_ctx* c)
     float* bufs[] = {c->d_taperz, c->d_txfac, c->d_gcx, c->d_gcz, c->fld[0], c->fld[1], c->fld[2], c->fld[3],
                      c->fld[4], c->fld[5], c->fld[6], c->fld[7], c->fld[8], c->fld[9], c->d_v2, c->d_img, c->d_illum, c->d_srce, c->d_dobs, c->d_rec,
                      c->d_vp, c->d_vpe, (float*)c->d_draws, (float*)c->d_jump, c->bfld[0], c->bfld[1], c->bfld[2], c->bfld[3],
-                     c->bfld[4], c->bfld[5], c->bfld[6], c->bfld[7], c->b_v2, c->b_img, c->b_dobs, c->b_illum, c->b_rec, c->b_wav, c->d_raw, c->d_wav, c->d_snap[0], c->d_snap[1], c->d_snap[2], c->d_amp, (float*)c->d_texc, c->d_exc};
+                     c->bfld[4], c->bfld[5], c->bfld[6], c->bfld[7], c->b_v2, c->b_img, c->b_dobs, c->b_illum, c->b_rec, c->b_wav, c->d_raw, c->d_wav, c->d_snap[0], c->d_snap[1], c->d_snap[2], c->d_amp, (float*)c->d_texc, c->d_exc, (float*)c->d_peak};
     for (float* b : bufs)
         if (b) (void)hipFree(b);
     if (c->stream) (void)hipStreamDestroy(c->stream);
@@ -677,10 +682,11 @@ static int step_impl(fdw_ctx* c, int mode, const float* d_p, float* d_pp, const 
     // (a batch accumulates per shot, illum + shot * field, inside fdw_shot_batch_illum only)
     if (f.illum && (mode != FDW_MODE_FWD || (c->nbatch > 1 && !c->batch_illum)))
         return fail(FDW_EINVAL, "step: illumination belongs to a forward step of one shot");
-    // the maps ride a point-source step, the pick a line-source step; neither is built together with recording or illumination, nor batched
+    // the maps ride a point-source step, the pick a line-source step; neither is built together with recording or illumination.  A batch
+    // (fdw_shot_excitation_batch): the one-step ring kernels only, amp / exc and the time map [shot] fields like the others
     const FwdVariant v = fwd_variant(mode, f);
-    if (f.exc != Exc::none && (v.kmode < 0 || mode != FDW_MODE_FWD || c->nbatch > 1 || !f.exc_arr || !f.texc))
-        return fail(FDW_EINVAL, "step: the excitation maps belong to a plain forward step of one shot, the pick to a plain line-source step");
+    if (f.exc != Exc::none && (v.kmode < 0 || mode != FDW_MODE_FWD || !f.exc_arr || !f.texc || (c->nbatch > 1 && (c->h > kMaxFastHalfOrder || c->use_generic))))
+        return fail(FDW_EINVAL, "step: the excitation maps belong to a plain forward step, the pick to a plain line-source step (a batch: orders <= 8)");
     // the RTM forward step that records its trace row, that accumulates the source illumination, or both
     fill_forward(c, a, v, f);
     a.inj = f.samples + in.shift; a.inj_x = in.x; a.inj_z = f.sz; a.inj_n = in.n;
@@ -1490,6 +1496,34 @@ extern "C" int fdw_dev_line_pick_steps(fdw_ctx* c, float* const* d_buf, const fl
     FDW_TRY(check_line_args(c, "fdw_dev_line_pick_steps", sz, 0, false, false));
     const Forward f = line_source(d_wav, sz).exciting(Exc::pick, d_exc, const_cast<int*>(d_texc), top);      // the pick only reads the map
     return steps_loop(c, d_buf, d_v2, f, it0, nsteps, first_pp_twice, ip, ipp, pick_stream(c, stream));
+}
+
+// The image of `nshots` excitation shots on the device (fdw_excimg.hip), everything on s: the per-shot peak words zeroed, the peaks of |amp|
+// over the interior, then img = img + exc / amp in shot order where |amp| > eps * peak.  d_exc, d_amp (and d_stack, if any): [nshots] fields,
+// d_img one field; c->d_peak holds at least nshots words.
+static int exc_image(fdw_ctx* c, const float* d_exc, const float* d_amp, float eps, float* d_img, float* d_stack, int nshots, hipStream_t s)
+{
+    const ExcImgGeom g{c->pitch, c->prm.nxb, c->nx, c->prm.nzb, c->nz, (long long)field_elems(c)};
+    HIP_TRY(hipMemsetAsync(c->d_peak, 0, (size_t)nshots * sizeof(unsigned), s));
+    hipError_t e = launch_exc_peak(d_amp, c->d_peak, g, nshots, s);
+    if (e == hipSuccess) e = launch_exc_stack(d_exc, d_amp, c->d_peak, eps, d_img, d_stack, g, nshots, s);
+    if (e != hipSuccess) return fail(FDW_EHIP, "excitation image launch failed: %s", hipGetErrorString(e));
+    return FDW_OK;
+}
+
+static int check_exc_eps(const char* who, float eps)
+{
+    if (!(eps >= 0.0f) || std::isinf(eps)) return fail(FDW_EINVAL, "%s: eps must be finite and >= 0", who);
+    return FDW_OK;
+}
+
+extern "C" int fdw_dev_image_excitation(fdw_ctx* c, const float* d_exc, const float* d_amp, float eps, float* d_img, void* stream)
+{
+    if (!c) return fail(FDW_EINVAL, "NULL argument");
+    FDW_TRY(check_single_shot_ctx(c, "excitation-amplitude imaging", "fdw_dev_image_excitation"));
+    if (!d_exc || !d_amp || !d_img) return fail(FDW_EINVAL, "NULL argument");
+    FDW_TRY(check_exc_eps("fdw_dev_image_excitation", eps));
+    return exc_image(c, d_exc, d_amp, eps, d_img, nullptr, 1, pick_stream(c, stream));
 }
 
 // d_out[i] = d_a[i] - d_b[i] (fdw_gather_residual_kernel); d_out may be d_a
@@ -2771,38 +2805,49 @@ extern "C" int fdw_image_excitation(const float* exc, const float* amp, size_t n
     return FDW_OK;
 }
 
-extern "C" int fdw_shot_excitation(fdw_ctx* c, const float* v2, int sx, int sz, int gz, const float* srce, const float* d_obs, float eps, float* imloc,
-                                   float* exc, float* amp, int* texc, float* P, float* PP)
+// the data gathers d_obs [nshots][nx][nt] as the pick loop's line gathers d_dst [nshots][nt][nx]: row k = d_obs[.][nt-1-k], reversed on the device
+static int reversed_gathers_to_device(fdw_ctx* c, const float* d_obs, float* d_dst, int nshots)
 {
-    if (!c) return fail(FDW_EINVAL, "NULL argument");
-    FDW_TRY(check_single_shot_ctx(c, "excitation-amplitude imaging", "fdw_shot_excitation"));
-    if (!srce || !d_obs || (!imloc && !exc && !amp && !texc)) return fail(FDW_EINVAL, "NULL argument");
-    if (!(eps >= 0.0f) || std::isinf(eps)) return fail(FDW_EINVAL, "fdw_shot_excitation: eps must be finite and >= 0");
-    FDW_TRY(has_model(c, v2));
-    if (sx < 0) return fail(FDW_EINVAL, "fdw_shot_excitation: source row %d", sx);
-    FDW_TRY(check_exc_source(c, "fdw_shot_excitation", sx, sz));
-    FDW_TRY(check_line_args(c, "fdw_shot_excitation", gz, 0, false, false));
+    const size_t n = (size_t)c->nx * c->prm.nt * nshots;
+    if (n == 0) return FDW_OK;
+    int rc = ensure_cap(&c->d_raw, &c->raw_cap, n);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(c->d_raw, d_obs, n * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    hipError_t e = launch_gather_transpose_rev(c->d_raw, d_dst, c->nx, c->prm.nt, nshots, c->stream);
+    if (e != hipSuccess) return fail(FDW_EHIP, "gather transposition launch failed: %s", hipGetErrorString(e));
+    return FDW_OK;
+}
+
+// what every excitation shot asks of its arguments beyond the pointers (a batch: of its first and last source row)
+static int check_exc_shot(const fdw_ctx* c, const char* who, int sx, int sz, int gz, float eps)
+{
+    FDW_TRY(check_exc_eps(who, eps));
+    if (sx < 0) return fail(FDW_EINVAL, "%s: source row %d", who, sx);
+    FDW_TRY(check_exc_source(c, who, sx, sz));
+    FDW_TRY(check_line_args(c, who, gz, 0, false, false));
     if (c->nx <= 0 || c->nz <= 0) return fail(FDW_EINVAL, "no interior to image");
-    FDW_RANGE("fdw: excitation-amplitude shot (uploads, forward + maps, receiver loop + pick, downloads)");
+    return FDW_OK;
+}
+
+// fdw_shot_excitation behind its checks.  The image is formed on the device (exc_image, one shot) and comes back as ONE interior array;
+// exc, amp and texc come back only where the caller asked for them.
+static int shot_excitation_impl(fdw_ctx* c, const float* v2, int sx, int sz, int gz, const float* srce, const float* d_obs, float eps, float* imloc,
+                                float* exc, float* amp, int* texc, float* P, float* PP)
+{
+    FDW_RANGE("fdw: excitation-amplitude shot (uploads, forward + maps, receiver loop + pick, image, downloads)");
     HIP_TRY(hipSetDevice(c->device));
     int rc;
     const int nt = c->prm.nt, nx = c->nx;
-    const size_t fe = field_elems(c), ni = (size_t)nx * c->nz;
-    if ((rc = ensure_work_buffers(c, 8, false)) || (rc = alloc_zero(&c->d_amp, fe)) || (rc = alloc_zero((float**)&c->d_texc, fe)) ||
+    const size_t fe = field_elems(c);
+    if ((rc = ensure_work_buffers(c, 8, imloc != nullptr)) || (rc = alloc_zero(&c->d_amp, fe)) || (rc = alloc_zero((float**)&c->d_texc, fe)) ||
         (rc = alloc_zero(&c->d_exc, fe)) || (rc = ensure_cap(&c->d_wav, &c->wav_cap, (size_t)nx * nt)))
         return rc;
-    // row k of the pick loop's line gather: d_obs[.][nt-1-k]
-    std::vector<float> wav((size_t)nx * nt);
-    for (int k = 0; k < nt; k++)
-        for (int ix = 0; ix < nx; ix++) wav[(size_t)k * nx + ix] = d_obs[(size_t)ix * nt + (nt - 1 - k)];
-    std::vector<float> h_exc, h_amp;      // the image needs both, whether the caller wants them or not
-    if (imloc && !exc) { h_exc.resize(ni); exc = h_exc.data(); }
-    if (imloc && !amp) { h_amp.resize(ni); amp = h_amp.data(); }
     float* const maps[3] = {c->d_amp, (float*)c->d_texc, c->d_exc};
     if ((rc = zero_fields(c, c->fld, 2)) || (rc = zero_fields(c, maps, 3))) return rc;
     end_residency(c, v2);
     if ((v2 && (rc = upload_rows(c, c->d_v2, v2, c->stream))) || (rc = upload_source(c, srce, nt))) return rc;
-    if (nt > 0) HIP_TRY(hipMemcpyAsync(c->d_wav, wav.data(), wav.size() * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    if ((rc = reversed_gathers_to_device(c, d_obs, c->d_wav, 1))) return rc;
+    if (imloc && (rc = image_to_device(c, imloc, c->d_img))) return rc;
     int ip = 0, ipp = 1;
     const Forward fwd = point_source(c->d_srce, sx, sz).exciting(Exc::maps, c->d_amp, c->d_texc, 0);
     if ((rc = steps_loop(c, c->fld, c->d_v2, fwd, 0, nt, 0, &ip, &ipp, c->stream))) return rc;
@@ -2813,12 +2858,24 @@ extern "C" int fdw_shot_excitation(fdw_ctx* c, const float* v2, int sx, int sz, 
     int rp = 0, rpp = 1;
     const Forward bwd = line_source(c->d_wav, gz).exciting(Exc::pick, c->d_exc, c->d_texc, nt);
     if ((rc = steps_loop(c, c->fld + 4, c->d_v2, bwd, 0, nt, 0, &rp, &rpp, c->stream))) return rc;
+    if (imloc && ((rc = exc_image(c, c->d_exc, c->d_amp, eps, c->d_img, nullptr, 1, c->stream)) || (rc = image_to_host(c, imloc, c->d_img)))) return rc;
     if (exc && (rc = image_to_host(c, exc, c->d_exc))) return rc;
     if (amp && (rc = image_to_host(c, amp, c->d_amp))) return rc;
     if (texc && (rc = image_to_host(c, (float*)texc, (const float*)c->d_texc))) return rc;
     HIP_TRY(hipStreamSynchronize(c->stream));
-    if (imloc) return fdw_image_excitation(exc, amp, ni, eps, imloc);
     return FDW_OK;
+}
+
+extern "C" int fdw_shot_excitation(fdw_ctx* c, const float* v2, int sx, int sz, int gz, const float* srce, const float* d_obs, float eps, float* imloc,
+                                   float* exc, float* amp, int* texc, float* P, float* PP)
+{
+    if (!c) return fail(FDW_EINVAL, "NULL argument");
+    FDW_TRY(check_single_shot_ctx(c, "excitation-amplitude imaging", "fdw_shot_excitation"));
+    if (!srce || !d_obs || (!imloc && !exc && !amp && !texc)) return fail(FDW_EINVAL, "NULL argument");
+    FDW_TRY(check_exc_eps("fdw_shot_excitation", eps));
+    FDW_TRY(has_model(c, v2));
+    FDW_TRY(check_exc_shot(c, "fdw_shot_excitation", sx, sz, gz, eps));
+    return shot_excitation_impl(c, v2, sx, sz, gz, srce, d_obs, eps, imloc, exc, amp, texc, P, PP);
 }
 
 // ---- residual migration (definitions in fdwave.h) ----
@@ -3072,6 +3129,110 @@ static int shot_batch_in_parts(fdw_ctx* c, const char* who, int nshots, const fl
         FDW_TRY(shot_batch_impl(c, who, nb, v2_all ? v2_all + b0 * ne : nullptr, draw_offset + b0 * draws, sx0 + b0 * dsx, dsx, sz, gz,
                                 x.line && samples ? samples + b0 * ng : samples, d_obs ? d_obs + b0 * ng : nullptr, imloc ? imloc + b0 * ni : nullptr,
                                 x.of_shot(b0, ni, ng)));
+    }
+    return batch_end(c, nshots, FDW_OK);
+}
+
+// ---- a batch of excitation shots (definitions in fdwave.h) ----
+// The regime of its batched launches: fdw_shot_batch's (the one-step ring family: orders <= 8, neither the pipeline nor the two-step regime)
+// without its conditions on the backward loop -- the pick loop is a line-source forward loop, which injects only the receiver rows the loop
+// time-steps, so ragged compat grids batch too.
+static bool excitation_batch_ok(const fdw_ctx* c)
+{
+    return c->prm.dialect == FDW_DIALECT_RTM && c->h <= kMaxFastHalfOrder && !c->use_generic && !two_step_pays(c) && !pipe_pays(c);
+}
+
+static int ensure_peaks(fdw_ctx* c, int n)
+{
+    if (c->peak_cap >= n) return FDW_OK;
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    unsigned* p = nullptr;
+    hipError_t e = hipMalloc((void**)&p, (size_t)n * sizeof(unsigned));
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(FDW_ENOMEM, "hipMalloc failed: %s", hipGetErrorString(e));
+    }
+    (void)hipFree(c->d_peak);
+    c->d_peak = p;
+    c->peak_cap = n;
+    return FDW_OK;
+}
+
+// One part of fdw_shot_excitation_batch: `nshots` shots whose images are added to imloc in shot order.  Batched, it works in
+// fdw_shot_batch's buffers: bfld[0..1] the source fields, bfld[2..3] the receiver fields, bfld[4] amp, bfld[5] texc, bfld[6] exc (which the
+// stack kernel then overwrites with the running images), b_dobs the time-reversed gathers [shot][nt][nx]; the running image is c->d_img.
+static int excitation_batch_part(fdw_ctx* c, int nshots, const float* v2_all, unsigned long long draw_offset, int sx0, int dsx, int sz, int gz,
+                                 const float* srce, const float* d_obs, float eps, float* imloc, float* stack, float* exc, float* amp, int* texc, bool room)
+{
+    const int nt = c->prm.nt;
+    const size_t ni = (size_t)c->nx * c->nz, ne = (size_t)c->prm.nxe * c->prm.nze, ng = (size_t)c->nx * nt, fe = field_elems(c);
+    const long long draws = fdw_border_draws(c->nx, c->nz, c->prm.nxb, c->prm.nzb);
+    auto one_by_one = [&] {
+        for (int b = 0; b < nshots; b++) {
+            if (!v2_all) FDW_TRY(fdw_dev_extendvel_linear(c, draw_offset + (unsigned long long)b * draws, nullptr));
+            FDW_TRY(shot_excitation_impl(c, v2_all ? v2_all + b * ne : nullptr, sx0 + b * dsx, sz, gz, srce, d_obs + b * ng, eps, imloc, exc ? exc + b * ni : nullptr,
+                                         amp ? amp + b * ni : nullptr, texc ? texc + b * ni : nullptr, nullptr, nullptr));
+            if (stack) memcpy(stack + b * ni, imloc, ni * sizeof(float));
+        }
+        return (int)FDW_OK;
+    };
+    auto fallback = [&] { batch_part_ran(c, false); return one_by_one(); };
+    if (!excitation_batch_ok(c) || !room) return fallback();      // a regime the batched launches do not cover, or a budget below one shot
+    if (nshots == 1) { batch_part_ran(c, true); return one_by_one(); }      // nothing to gain
+    int rc;
+    if ((rc = ensure_work_buffers(c, 8, true))) return rc;
+    if ((rc = ensure_batch_buffers(c, nshots, true)) == FDW_ENOMEM) return fallback();      // no room for the batch
+    if (!rc && (rc = ensure_peaks(c, nshots)) == FDW_ENOMEM) return fallback();
+    if (!rc) batch_part_ran(c, true);
+    if (rc || (rc = upload_source(c, srce, nt))) return rc;
+    hipStream_t s = c->stream;
+    if ((rc = reversed_gathers_to_device(c, d_obs, c->b_dobs, nshots))) return rc;
+    if ((rc = batch_models(c, nshots, v2_all, draw_offset))) return rc;
+    for (int i = 0; i < 7; i++) HIP_TRY(hipMemsetAsync(c->bfld[i], 0, fe * nshots * sizeof(float), s));
+    if ((rc = image_to_device(c, imloc, c->d_img))) return rc;
+    {
+        BatchScope scope(c, nshots, dsx, false);
+        int ip = 0, ipp = 1, rp = 0, rpp = 1;
+        // batch_ok: one-step passes only, so each loop stays in the first two of the four buffers it is handed
+        const Forward fwd = point_source(c->d_srce, sx0, sz).exciting(Exc::maps, c->fld[4], (int*)c->fld[5], 0);
+        if ((rc = steps_loop(c, c->fld, c->d_v2, fwd, 0, nt, 0, &ip, &ipp, s))) return rc;
+        const Forward bwd = line_source(c->d_dobs, gz).exciting(Exc::pick, c->fld[6], (int*)c->fld[5], nt);
+        if ((rc = steps_loop(c, c->fld + 2, c->d_v2, bwd, 0, nt, 0, &rp, &rpp, s))) return rc;
+    }
+    if (exc && (rc = batch_interiors_to_host(c, exc, c->bfld[6], nshots))) return rc;      // before the running images take its place
+    if (amp && (rc = batch_interiors_to_host(c, amp, c->bfld[4], nshots))) return rc;
+    if (texc && (rc = batch_interiors_to_host(c, (float*)texc, c->bfld[5], nshots))) return rc;
+    if ((rc = exc_image(c, c->bfld[6], c->bfld[4], eps, c->d_img, stack ? c->bfld[6] : nullptr, nshots, s))) return rc;
+    if (stack && (rc = batch_interiors_to_host(c, stack, c->bfld[6], nshots))) return rc;
+    if ((rc = image_to_host(c, imloc, c->d_img))) return rc;
+    HIP_TRY(hipStreamSynchronize(s));
+    return FDW_OK;
+}
+
+extern "C" int fdw_shot_excitation_batch(fdw_ctx* c, int nshots, const float* v2_all, unsigned long long draw_offset, int sx0, int dsx, int sz, int gz,
+                                         const float* srce, const float* d_obs, float eps, float* imloc, float* stack, float* exc, float* amp, int* texc)
+{
+    if (!c) return fail(FDW_EINVAL, "NULL argument");
+    FDW_TRY(check_single_shot_ctx(c, "excitation-amplitude imaging", "fdw_shot_excitation_batch"));
+    if (!srce || !d_obs || !imloc) return fail(FDW_EINVAL, "NULL argument");
+    if (nshots < 1) return fail(FDW_EINVAL, "nshots=%d", nshots);
+    if (!v2_all && !c->model_resident) return fail(FDW_ESTATE, "no model: pass v2_all or call fdw_model_resident first");
+    FDW_TRY(check_batch_source_rows(c, nshots, sx0, dsx));
+    FDW_TRY(check_exc_shot(c, "fdw_shot_excitation_batch", sx0, sz, gz, eps));
+    HIP_TRY(hipSetDevice(c->device));
+    if (v2_all) c->v2_resident = false;
+    // per shot the batch holds fdw_shot_batch's eleven fields (of which it uses two source and two receiver fields, v2, amp, texc and exc)
+    // and one gather [nt][nx]
+    const size_t ni = (size_t)c->nx * c->nz, ne = (size_t)c->prm.nxe * c->prm.nze, ng = (size_t)c->nx * c->prm.nt;
+    const bool room = batch_budget(c) >= (11 * field_elems(c) + ng) * sizeof(float);      // a budget below ONE shot: no batch buffers at all
+    const int part = room ? batch_part(c, nshots, 11, 1) : nshots;
+    const unsigned long long draws = (unsigned long long)fdw_border_draws(c->nx, c->nz, c->prm.nxb, c->prm.nzb);
+    batch_begin(c);
+    for (int b0 = 0; b0 < nshots; b0 += part) {      // in shot order: imloc is carried from part to part
+        const int nb = std::min(part, nshots - b0);
+        FDW_TRY(excitation_batch_part(c, nb, v2_all ? v2_all + b0 * ne : nullptr, draw_offset + b0 * draws, sx0 + b0 * dsx, dsx, sz, gz, srce, d_obs + b0 * ng, eps,
+                                      imloc, stack ? stack + b0 * ni : nullptr, exc ? exc + b0 * ni : nullptr, amp ? amp + b0 * ni : nullptr,
+                                      texc ? texc + b0 * ni : nullptr, room));
     }
     return batch_end(c, nshots, FDW_OK);
 }

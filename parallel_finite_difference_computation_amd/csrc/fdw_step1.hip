@@ -27,7 +27,7 @@ namespace fdw {
 //   REC     trace recording of the RTM dialect's forward loop: the new field at column rec_z of every receiver row (fdw_step_rec_kernel)
 //   ILL     source illumination of the forward loop: sv.img += new field (*) new field on the updated cells, product and sum rounded
 //           separately (fdw_step_illum_kernel); the row of the accumulator rides the image queue
-//   EXC     excitation-amplitude imaging (fdwave.h, "excitation amplitude"), the RTM dialect's forward loops, one shot (no batch):
+//   EXC     excitation-amplitude imaging (fdwave.h, "excitation amplitude"), the RTM dialect's forward loops; batched like the fields:
 //           1  the excitation maps: where |new field| > |amp| strictly, amp = the new field (signed) and texc = a.exc_key (= it + 1);
 //              the amp row rides the image queue (a.img), the texc row a queue of its own (fdw_step_exc_kernel)
 //           2  the excitation pick: where texc == a.exc_key (= top - it), exc = the new field; texc is only read, the exc row (a.img) is
@@ -145,6 +145,8 @@ __device__ __forceinline__ void march(const StepArgs& a, const ShotView& sv, con
     f4 ring[R];
     f4 qhal[PF], qpp[PF], qv2[PF], qps[PF], qim[PF];
     f4 qtx[EXC ? PF : 1];                                   // EXC: the texc row, as words
+    [[maybe_unused]] float* texc_w = nullptr;               // EXC: the time map of this block's shot (a batch: a.texc + shot * a.bstride)
+    if constexpr (EXC != 0) texc_w = reinterpret_cast<float*>(a.texc) + (long long)blockIdx.y * a.bstride;
     f4 fring[BACK ? R : 1], fqhal[BACK ? PF : 1], fqpp[BACK ? PF : 1];      // the source field's ring and pointwise queues
     constexpr int NV = LOOK > PF ? LOOK : PF;
     static_for<2 * H>([&](auto K) {
@@ -174,7 +176,7 @@ __device__ __forceinline__ void march(const StepArgs& a, const ShotView& sv, con
             if constexpr (ILL) qim[m] = load_plain(sv.img, row);
             if constexpr (EXC != 0) {
                 qim[m] = load_plain(sv.img, row);
-                qtx[m] = load_plain(reinterpret_cast<const float*>(a.texc), row);
+                qtx[m] = load_plain(texc_w, row);
             }
             if constexpr (BACK) {
                 fqhal[m] = load_fhalo(row);
@@ -359,14 +361,14 @@ __device__ __forceinline__ void march(const StepArgs& a, const ShotView& sv, con
                 if constexpr (IMG) f4_store(sv.img + (size_t)r * pitch, voff, imr);
                 if constexpr (ILL) f4_store(sv.img + (size_t)r * pitch, voff, imr);
                 if constexpr (EXC != 0) f4_store(sv.img + (size_t)r * pitch, voff, imr);
-                if constexpr (EXC == 1) f4_store(reinterpret_cast<float*>(a.texc) + (size_t)r * pitch, voff, txr);
+                if constexpr (EXC == 1) f4_store(texc_w + (size_t)r * pitch, voff, txr);
                 if constexpr (BACK) f4_store(sv.fpp + (size_t)r * pitch, voff, fres);
             } else if (act) {
                 f4_store(sv.out + (size_t)r * pitch, voff, res);
                 if constexpr (IMG) f4_store(sv.img + (size_t)r * pitch, voff, imr);
                 if constexpr (ILL) f4_store(sv.img + (size_t)r * pitch, voff, imr);
                 if constexpr (EXC != 0) f4_store(sv.img + (size_t)r * pitch, voff, imr);
-                if constexpr (EXC == 1) f4_store(reinterpret_cast<float*>(a.texc) + (size_t)r * pitch, voff, txr);
+                if constexpr (EXC == 1) f4_store(texc_w + (size_t)r * pitch, voff, txr);
                 if constexpr (BACK) f4_store(sv.fpp + (size_t)r * pitch, voff, fres);
             }
             if constexpr (REC) f1_store_arr(array_rsrc(sv.rec, (unsigned)a.rec_n * 4u), rec_offset(rec_lane, r, a.rec_x0, a.rec_n), f4_pick(res, a.rec_z & 3));
@@ -387,7 +389,7 @@ __device__ __forceinline__ void march(const StepArgs& a, const ShotView& sv, con
                 if constexpr (ILL) qim[Q] = load_plain(sv.img, nr);
                 if constexpr (EXC != 0) {
                     qim[Q] = load_plain(sv.img, nr);
-                    qtx[Q] = load_plain(reinterpret_cast<const float*>(a.texc), nr);
+                    qtx[Q] = load_plain(texc_w, nr);
                 }
                 if constexpr (BACK) {
                     fqhal[Q] = load_fhalo(nr);
@@ -492,7 +494,7 @@ __global__ __launch_bounds__(256) void fdw_step_line_rec_illum_kernel(const Step
 }
 
 // the forward step (FDW_MODE_FWD) that also keeps the excitation maps (FDW_MODE_FWD_EXC, fdw_dev_excite_steps): a.img is amp, a.texc the time
-// map, both read and written once per cell, +16 B/point/step.  One shot only (the callers refuse a batch: a.texc carries no shot stride).
+// map, both read and written once per cell, +16 B/point/step.  A batch: amp travels as sv.img, the map of shot b is a.texc + b * a.bstride.
 template <int H, int PF, int NUM>
 __global__ __launch_bounds__(256) void fdw_step_exc_kernel(const StepArgs a)
 {

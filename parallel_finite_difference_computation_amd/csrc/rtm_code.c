@@ -46,8 +46,8 @@
  * are stacked in the order j into dir.image, image.num has one section per plane wave, illum=1 and image_lap=1 work as for shots.  One
  * plane wave after the other; pw together with slabs > 1, gpus > 1, resid=1 or snap > 0 is refused before anything is opened.
  *
- * Excitation-amplitude imaging (no counterpart in the reference): the deck key `exc=1` (absent or 0: nothing changes) sends every shot, one
- * by one, through fdw_shot_excitation: the forward loop keeps the peak of the source field and its time level per cell, the backward loop
+ * Excitation-amplitude imaging (no counterpart in the reference): the deck key `exc=1` (absent or 0: nothing changes) sends the shots, in
+ * groups of fdw_shot_batch_max, through fdw_shot_excitation_batch (a group of one, or FDW_NO_SHOT_BATCH=1: fdw_shot_excitation): the forward loop keeps the peak of the source field and its time level per cell, the backward loop
  * propagates the receiver field alone and every cell takes its sample at that level.  dir.image is the stack in shot order of exc / amp
  * where |amp| > exc_eps max |amp| (fdw_image_excitation; `exc_eps` defaults to 1e-3), image.num has one section per shot.  exc together
  * with illum=1, resid=1, pw, snap > 0, slabs > 1 or gpus > 1 (deck or environment) is refused before anything is opened. */
@@ -396,8 +396,8 @@ int main(int argc, char **argv)
         }
     }
 
-    /* our extension (absent or 0: nothing changes): the excitation-amplitude imaging condition.  Every shot through fdw_shot_excitation, one
-     * after the other on one context: refused with every key that deals shots out or changes what a shot is, before any file, thread,
+    /* our extension (absent or 0: nothing changes): the excitation-amplitude imaging condition.  The shots in groups through
+     * fdw_shot_excitation_batch / fdw_shot_excitation on one context: refused with every key that deals shots out or changes what a shot is, before any file, thread,
      * communicator or device is touched */
     const int exc = fdw_deck_int(deck, "exc") == 1;
     float exc_eps = fdw_deck_has(deck, "exc_eps") ? fdw_deck_float(deck, "exc_eps") : 1.0e-3f;
@@ -575,46 +575,61 @@ int main(int argc, char **argv)
         goto outputs;
     }
     if (exc) {
-        /* ---- exc=1: every shot through fdw_shot_excitation, one by one on one context; the image of each is added to the stack in shot
-         * order by fdw_image_excitation (img is the running sum the call updates), image.num has one section per shot as always ---- */
+        /* ---- exc=1: the shots in groups of fdw_shot_batch_max on one context.  A group of several shots goes through
+         * fdw_shot_excitation_batch (one launch per time step for all of them; the running image after each shot comes back in `stack`), a
+         * group of one through fdw_shot_excitation; either way the image of each shot is added to img in shot order on the device and
+         * image.num has one section per shot as always.  FDW_NO_SHOT_BATCH=1 keeps one shot per launch sequence. ---- */
         const int dev_models = !vel_ext_flag && !getenv("FDW_HOST_BORDER") && nxb != 1 && nzb != 1 && nzb <= nxe;      /* as dev_border below */
         const long long draws = fdw_border_draws(nx, nz, nxb, nzb);
         fdw_ctx *ctx = NULL;
-        float *v2 = (float *)malloc(ne * sizeof(float));
-        if (!v2) {
-            fprintf(stderr, "out of host memory\n");
-            return EXIT_FAILURE;
-        }
         if (fdw_create(&prm, 0, &ctx) != FDW_OK || (dev_models && fdw_model_resident(ctx, vp) != FDW_OK)) {
             fprintf(stderr, "fdw_create: %s\n", fdw_last_error());
             return EXIT_FAILURE;
         }
+        int bmax = (ns > 1 && !getenv("FDW_NO_SHOT_BATCH")) ? fdw_shot_batch_max(ctx) : 1;
+        if (bmax > ns) bmax = ns;
+        shots_per_launch = bmax;
+        float *v2 = (float *)malloc((size_t)bmax * ne * sizeof(float)), *stack = (float *)malloc((size_t)bmax * ni * sizeof(float));
+        if (!v2 || !stack) {
+            fprintf(stderr, "out of host memory\n");
+            return EXIT_FAILURE;
+        }
         printf("## exc = 1, exc_eps = %g: excitation-amplitude imaging, image += exc / amp per shot \n", (double)exc_eps);
+        printf("## exc: up to %d shots per launch sequence (%s) \n", bmax, bmax > 1 ? "fdw_shot_excitation_batch" : "fdw_shot_excitation, one by one");
         const double t0 = now_s();
-        for (int is = 0; is < ns; is++) {
-            const float *model = NULL;      /* NULL: the squared model drawn in HBM */
+        for (int is0 = 0; is0 < ns; is0 += bmax) {
+            const int nb = is0 + bmax <= ns ? bmax : ns - is0;
             int rc = FDW_OK;
-            if (!dev_models) {
+            for (int b = 0; b < nb && !dev_models; b++) {
                 const float *v = vpe;
-                if (vel_ext_flag) v = vel_ext_rnd + (size_t)is * ne;             /* R:484 */
+                if (vel_ext_flag) v = vel_ext_rnd + (size_t)(is0 + b) * ne;      /* R:484 */
                 else fdw_extendvel_linear(nx, nz, nxb, nzb, vpe);               /* R:486: the next draws of the one stream, in shot order */
-                for (size_t k = 0; k < ne; k++) v2[k] = v[k] * v[k];             /* R:490-494 */
-                model = v2;
-            } else {
-                rc = fdw_dev_extendvel_linear(ctx, (unsigned long long)is * (unsigned long long)draws, NULL);
+                for (size_t k = 0; k < ne; k++) v2[(size_t)b * ne + k] = v[k] * v[k];      /* R:490-494 */
             }
-            if (rc == FDW_OK)
-                rc = fdw_shot_excitation(ctx, model, sx[is], sz, gz, srce, d_obs + (size_t)is * nx * nt, exc_eps, img, NULL, NULL, NULL, NULL, NULL);
+            const unsigned long long draw0 = (unsigned long long)is0 * (unsigned long long)draws;
+            const float *gathers = d_obs + (size_t)is0 * nx * nt;
+            if (nb > 1) {
+                rc = fdw_shot_excitation_batch(ctx, nb, dev_models ? NULL : v2, draw0, sx[is0], ds, sz, gz, srce, gathers, exc_eps, img, stack, NULL, NULL,
+                                               NULL);
+            } else {
+                if (dev_models) rc = fdw_dev_extendvel_linear(ctx, draw0, NULL);      /* the squared model drawn in HBM */
+                if (rc == FDW_OK) rc = fdw_shot_excitation(ctx, dev_models ? NULL : v2, sx[is0], sz, gz, srce, gathers, exc_eps, img, NULL, NULL, NULL, NULL, NULL);
+            }
             if (rc != FDW_OK) {
-                fprintf(stderr, "shot %d: %s\n", is + 1, fdw_last_error());
+                fprintf(stderr, "shots %d..%d: %s\n", is0 + 1, is0 + nb, fdw_last_error());
                 return EXIT_FAILURE;
             }
-            fprintf(stdout, "** source %d, at (%d,%d) \n\n** backward propagation %d, at (%d,%d) \n\n", is + 1, sx[is] - nxb, sz - nzb, is + 1, sx[is] - nxb,
-                    sz - nzb);
-            fprintf(fnum, "======== %i ========\n", is);
-            for (int iz = 0; iz < nz; iz++)
-                for (int ix = 0; ix < nx; ix++) fprintf(fnum, " %f \n", img[(size_t)ix * nz + iz]);
+            for (int b = 0; b < nb; b++) {
+                const int is = is0 + b;
+                const float *run = nb > 1 ? stack + (size_t)b * ni : img;      /* the running image after shot is */
+                fprintf(stdout, "** source %d, at (%d,%d) \n\n** backward propagation %d, at (%d,%d) \n\n", is + 1, sx[is] - nxb, sz - nzb, is + 1, sx[is] - nxb,
+                        sz - nzb);
+                fprintf(fnum, "======== %i ========\n", is);
+                for (int iz = 0; iz < nz; iz++)
+                    for (int ix = 0; ix < nx; ix++) fprintf(fnum, " %f \n", run[(size_t)ix * nz + iz]);
+            }
         }
+        free(stack);
         t_shots = now_s() - t0;
         fdw_destroy(ctx);
         free(v2);
@@ -856,7 +871,7 @@ int main(int argc, char **argv)
 outputs:
     if (timing)
         fprintf(stderr, "[timing] shots per launch sequence: up to %d (%s)\n", shots_per_launch,
-                shots_per_launch > 1 ? (pw > 0 ? "fdw_shot_line_batch" : (resid ? "fdw_shot_batch_residual" : (illum ? "fdw_shot_batch_illum" : "fdw_shot_batch")))
+                shots_per_launch > 1 ? (exc ? "fdw_shot_excitation_batch" : pw > 0 ? "fdw_shot_line_batch" : (resid ? "fdw_shot_batch_residual" : (illum ? "fdw_shot_batch_illum" : "fdw_shot_batch")))
                                      : (resid ? "one by one, fdw_shot_residual" : "one by one"));
     if (timing)
         fprintf(stderr, "[timing] total %.3f s: shots (contexts, border models, propagation) %.3f s, stacking + image.num %.3f s, rest (deck, inputs) %.3f s\n",

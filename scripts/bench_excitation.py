@@ -13,6 +13,15 @@ Per numerics (EXACT, FAST), order 8 on a size^2 grid, one process, nothing else 
      `repeats` windows is reported in us per step, with the bytes per point and step the loop must move at least;
   2. whole shots of `steps` time steps: fdw_shot against fdw_shot_excitation, wall time, alternating, median of `shot-repeats`;
   3. the same shot comparison on the new_mod deck size (415 x 295 extended, nt 1700).
+
+    python3 scripts/bench_excitation.py --image-on-device --parent-root DIR [--size 8192] [--steps 500] [--rounds 3]
+
+The whole shot since the image is formed on the device, against the build of the PARENT commit in the same sitting: DIR
+is a checkout of the parent with its library built.  The check of step 0 runs first; then worker processes alternate, parent build and this
+build, `rounds` times each; a worker warms up, then times fdw_shot, fdw_shot_excitation with all four outputs and (this build)
+fdw_shot_excitation with imloc alone, on size^2 and on the new_mod deck size, EXACT and FAST; the medians over the rounds go under the key
+"image_on_device" of --out, with a breakdown of this build's imloc-only shot at size^2: the two device loops and the image kernels timed
+with events on device arrays, the rest being uploads and the one download.
 Development tool, not part of the suite."""
 import argparse
 import json
@@ -21,7 +30,9 @@ import statistics
 import sys
 import time
 
-sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+# --root DIR (the workers of --image-on-device): the tree whose package and library this process loads
+ROOT = sys.argv[sys.argv.index("--root") + 1] if "--root" in sys.argv else os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
+sys.path.insert(0, ROOT)
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
@@ -136,7 +147,7 @@ def loops(size, steps, warmup, repeats, numerics):
     return out
 
 
-def shots(nxe, nze, nb, nt, repeats, numerics, what):
+def shots(nxe, nze, nb, nt, repeats, numerics, what, image_alone=False):
     rng = np.random.default_rng(3)
     ctx = F.FDWave(8, nxe, nze, nb, nb, nt, 0.75, 10.0, 10.0, 0.001, compat=True, numerics=numerics)
     nx = nxe - 2 * nb
@@ -155,17 +166,110 @@ def shots(nxe, nze, nb, nt, repeats, numerics, what):
 
     def excitation():
         ctx.shot_excitation(v2, sx, sz, gz, srce, d_obs)
-    xcorr(); excitation()                                  # warm-up: allocations, first launches
-    t = {"fdw_shot": [], "fdw_shot_excitation": []}
+
+    def image_only():
+        ctx.shot_excitation(v2, sx, sz, gz, srce, d_obs, want_maps=False)
+    fns = {"fdw_shot": xcorr, "fdw_shot_excitation": excitation}
+    if image_alone:
+        fns["fdw_shot_excitation_imloc_only"] = image_only
+    for fn in fns.values():                                # warm-up: allocations, first launches
+        fn()
+    t = {k: [] for k in fns}
     for _ in range(repeats):
-        t["fdw_shot"].append(timed(xcorr))
-        t["fdw_shot_excitation"].append(timed(excitation))
+        for k, fn in fns.items():
+            t[k].append(timed(fn))
     med = {k: statistics.median(v) for k, v in t.items()}
     out = dict(what=what, numerics="fast" if numerics else "exact", grid=[nxe, nze], nt=nt, steps_per_pass=ctx.steps_per_pass(),
                ms={k: round(v, 2) for k, v in med.items()}, runs_ms={k: [round(x, 2) for x in v] for k, v in t.items()},
                ratio_excitation_over_shot=round(med["fdw_shot_excitation"] / med["fdw_shot"], 4))
     print(json.dumps(out), flush=True)
     return out
+
+
+def breakdown(size, steps, numerics):
+    """This build's imloc-only shot at size^2 in parts: the forward loop with the maps and the line loop with the pick over `steps` steps from
+    rest, and fdw_dev_image_excitation, each timed with events on device arrays (ms)."""
+    dev = torch.device("cuda:0")
+    ctx = F.FDWave(8, size, size, NB, NB, steps, 0.75, 10.0, 10.0, 0.001, compat=True, numerics=numerics)
+    bufs, v2, srce, wav = make_state(ctx, size, steps)
+    amp = torch.zeros((size, ctx.pitch), device=dev)
+    texc = torch.zeros((size, ctx.pitch), device=dev, dtype=torch.int32)
+    exc = torch.zeros((size, ctx.pitch), device=dev)
+    img = torch.zeros((size, ctx.pitch), device=dev)
+    ptrs = [b.data_ptr() for b in bufs]
+    ts = torch.cuda.Stream()
+    s = ts.cuda_stream
+
+    def timed(fn):
+        torch.cuda.synchronize()
+        with torch.cuda.stream(ts):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn()
+            e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1)
+    out = {}
+    for _ in range(2):                                      # the second pass is the one reported
+        out["forward_maps_ms"] = timed(lambda: ctx.dev_excite_steps(ptrs, v2.data_ptr(), srce.data_ptr(), size // 2, NB + 2, amp.data_ptr(), texc.data_ptr(), 0,
+                                                                   steps, stream=s))
+        out["line_pick_ms"] = timed(lambda: ctx.dev_line_pick_steps(ptrs, v2.data_ptr(), wav.data_ptr(), NB + 1, texc.data_ptr(), steps, exc.data_ptr(), 0, steps,
+                                                                   stream=s))
+        out["image_kernels_ms"] = timed(lambda: ctx.dev_image_excitation(exc.data_ptr(), amp.data_ptr(), 1e-3, img.data_ptr(), stream=s))
+    out = dict(what=f"{size}^2 breakdown", numerics="fast" if numerics else "exact", **{k: round(v, 2) for k, v in out.items()})
+    print(json.dumps(out), flush=True)
+    return out
+
+
+def worker(args):
+    """One process of --image-on-device: JSON lines on stdout."""
+    if args.worker == "check":
+        for numerics in (0, 1):
+            print(json.dumps(dict(check=True, numerics=numerics, steps_per_pass_auto=check_paths(args.size, numerics))), flush=True)
+        return
+    this = args.worker == "this"
+    for numerics in (0, 1):
+        shots(args.size, args.size, NB, args.steps, 1, numerics, f"{args.size}^2", image_alone=this)
+        shots(415, 295, 50, 1700, 3, numerics, "new_mod deck size", image_alone=this)
+    if this and args.with_breakdown:
+        for numerics in (0, 1):
+            breakdown(args.size, args.steps, numerics)
+
+
+def image_on_device(args):
+    import subprocess
+    here = os.path.abspath(__file__)
+    this_root = os.path.abspath(os.path.join(os.path.dirname(here), ".."))
+
+    def run(which, root, extra=()):
+        cmd = ["timeout", "-k", "10", "300", sys.executable, here, "--worker", which, "--root", root, "--size", str(args.size), "--steps", str(args.steps)] + list(extra)
+        r = subprocess.run(cmd, capture_output=True, text=True)
+        if r.returncode != 0:
+            raise SystemExit(f"worker {which} ({root}) failed with status {r.returncode}: nothing more is started\n{r.stdout}\n{r.stderr}")
+        return [json.loads(ln) for ln in r.stdout.splitlines() if ln.startswith("{")]
+    checks = run("check", this_root)
+    print(json.dumps(checks), flush=True)
+    rows = {}
+    parts = []
+    for r in range(args.rounds):
+        for which, root in (("parent", os.path.abspath(args.parent_root)), ("this", this_root)):
+            for line in run(which, root, ["--with-breakdown"] if r == args.rounds - 1 else []):
+                if "ms" in line:
+                    for k, v in line["ms"].items():
+                        rows.setdefault((line["what"], line["numerics"], which + ":" + k), []).append(v)
+                else:
+                    parts.append(line)
+    table = {}
+    for (what, numerics, k), v in sorted(rows.items()):
+        table.setdefault(what, {}).setdefault(numerics, {})[k] = dict(median_ms=round(statistics.median(v), 2), runs_ms=v)
+    res = json.load(open(args.out)) if os.path.exists(args.out) else {}
+    res["image_on_device"] = dict(method=f"worker processes alternating between the parent's build and this build, {args.rounds} rounds; median of the rounds; "
+                                         f"{args.steps} steps at {args.size}^2, 1700 steps on the new_mod deck size (a worker's own median of 3 there)",
+                                  checks=checks, ms=table, breakdown_this_build=parts)
+    with open(args.out, "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+    print(json.dumps(res["image_on_device"]["ms"], indent=1), flush=True)
 
 
 def main():
@@ -176,7 +280,19 @@ def main():
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--shot-repeats", type=int, default=3)
     ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "profiles", "excitation.json"))
+    ap.add_argument("--image-on-device", action="store_true", help="the whole shot of this build against the parent's build (see the module docstring)")
+    ap.add_argument("--parent-root", default=None, help="--image-on-device: a checkout of the parent commit with its library built")
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--worker", choices=["check", "parent", "this"], default=None, help=argparse.SUPPRESS)
+    ap.add_argument("--root", default=None, help=argparse.SUPPRESS)
+    ap.add_argument("--with-breakdown", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.worker:
+        return worker(args)
+    if args.image_on_device:
+        if not args.parent_root:
+            ap.error("--image-on-device needs --parent-root")
+        return image_on_device(args)
     res = dict(device=torch.cuda.get_device_name(0), checks=[], loops=[], shots=[])
     for numerics in (0, 1):
         spp = check_paths(args.size, numerics)
