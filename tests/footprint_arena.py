@@ -7,13 +7,15 @@ Layout.  Buffers in the order of the case (inputs, then pure outputs), each star
 between any two and after the last: at least GUARD_ROWS rows x pitch floats next to a "field" buffer (more than the 27-step prologue of the
 wave pipeline plus its 16-row read halo), at least GUARD_FLAT floats next to a "flat" one.  Guards hold the quiet-NaN word 0x7FC0ABCD (the
 pattern of tests/test_snaps.py): a value pulled in from one is a NaN in the answer.  Fields hold their values in [:, :nze] and +0.0 in the
-padding columns [nze, pitch); pure outputs hold the case's sentinel.  Everything a stray access of a few dozen rows could reach is memory of
-this one allocation.
+padding columns [nze, pitch) -- or, where the case names one for the buffer (Case.pad_words: the excitation maps and images, of which
+fdwave.h says "padding columns keep their words", not "are zero"), a sentinel word; pure outputs hold the case's sentinel.  A buffer of
+kind "ifield" is a field of int32 words (d_texc): the case hands it over as an int32 array and it travels as words from there to the
+comparison, never through a float conversion.  Everything a stray access of a few dozen rows could reach is memory of this one allocation.
 
 The four rules (fdwave.h: padding columns are zero and stay zero, `const` arrays are only read, a call on rows [r0, r1) writes only those
 rows, the fused fdw_dev_back4 leaves d_lvl0 / d_lvl1 untouched):
   (a) guards      every guard word is bit-identical;
-  (b) pads        the padding columns of every field buffer are +0.0 bit for bit;
+  (b) pads        every padding word of every field buffer equals the upload bit for bit (+0.0, or the buffer's pad word);
   (c) read-only   a buffer that no label names and that is not on the case's scratch list is bit-identical to what was uploaded;
   (d) rows        where a label carries rows (or the case states written_rows for the buffer), the rows outside hold what was uploaded --
                   damped once where the case itself hands the buffer to fdw_dev_taper_finalize after the call (case.finalized): that pass
@@ -25,6 +27,7 @@ GUARD_WORD = 0x7FC0ABCD
 GUARD_ROWS = 48
 GUARD_FLAT = 1024
 ALIGN = 64                  # words: 256 bytes
+FIELD_KINDS = ("field", "ifield")      # [rows][pitch] on the device; "ifield": int32 words
 MAX_REPORTED = 6            # violations listed per rule and buffer
 
 
@@ -38,7 +41,7 @@ class Buf:
 
     def __init__(self, name, kind, off, shape, nze, pitch):
         self.name, self.kind, self.off = name, kind, off
-        if kind == "field":
+        if kind in FIELD_KINDS:
             self.rows, self.cols, self.nze = shape[0], pitch, nze
             assert shape[1] == nze, (name, shape, nze)
         else:
@@ -52,19 +55,22 @@ class Buf:
         return words[self.off:self.off + self.size].reshape(self.rows, self.cols)
 
     def values(self, words):
-        """What a test compares: float32 [rows][nze] of a field, the dense array of a flat buffer (in the case's shape)."""
+        """What a test compares: float32 [rows][nze] of a field (of an "ifield": its int32 words seen as float32, as the answers of
+        tests/stream_cases.py carry them), the dense array of a flat buffer (in the case's shape)."""
         a = self.view(words).view(np.float32)
-        return np.ascontiguousarray(a[:, :self.nze]) if self.kind == "field" else np.ascontiguousarray(a).reshape(self.shape)
+        return np.ascontiguousarray(a[:, :self.nze]) if self.kind in FIELD_KINDS else np.ascontiguousarray(a).reshape(self.shape)
 
 
 class Arena:
     """The layout of one case and its uploaded image `up` (uint32).  bufs: {name: Buf} in arena order; guard: bool mask of the guard words."""
 
     def __init__(self, case, nze, contents, damp=None):
-        """contents: [(name, kind, float32 array)] in arena order, fields dense [nxl][nze]; damp(dense field) -> the field after one pass of
-        fdw_dev_taper_finalize (needed where the case finalizes a buffer on which rule (d) looks at rows)."""
+        """contents: [(name, kind, float32 array)] in arena order, fields dense [nxl][nze] (an "ifield": the float32 VIEW of its int32 words, see
+        words_of); damp(dense field) -> the field after one pass of fdw_dev_taper_finalize (needed where the case finalizes a buffer on which
+        rule (d) looks at rows)."""
         self.case, self.nze, self.pitch = case, nze, pitch_of(nze)
-        need = [GUARD_ROWS * self.pitch if kind == "field" else GUARD_FLAT for _, kind, _ in contents]
+        pad_words = getattr(case, "pad_words", {})
+        need = [GUARD_ROWS * self.pitch if kind in FIELD_KINDS else GUARD_FLAT for _, kind, _ in contents]
         self.bufs, off = {}, 0
         for k, (name, kind, arr) in enumerate(contents):
             gap = max(need[k], need[k - 1] if k else 0)
@@ -79,8 +85,9 @@ class Arena:
             b = self.bufs[name]
             self.guard[b.off:b.off + b.size] = False
             v = b.view(self.up)
-            v[:] = 0                                                   # +0.0 in the padding columns
-            v[:, :b.nze] = np.ascontiguousarray(arr, np.float32).reshape(b.rows, b.nze).view(np.uint32)
+            v[:] = pad_words.get(name, 0) if kind in FIELD_KINDS else 0      # the padding columns: +0.0, or the case's word for the buffer
+            assert arr.dtype == np.float32, (name, arr.dtype)              # (so that the next line copies words and converts nothing)
+            v[:, :b.nze] = np.ascontiguousarray(arr).reshape(b.rows, b.nze).view(np.uint32)
         self.up.setflags(write=False)
         self.outside = {}      # {buffer: uint32 [rows][nze]} what rule (d) expects outside the written rows where that is not the upload
         for name, kind, arr in contents:
@@ -111,10 +118,19 @@ class Arena:
         return f"guard, {d} floats AFTER the end of {b.name} (row {b.rows + r}, column {c} if it went on)"
 
 
+def words_of(kind, arr):
+    """What a case hands over for a buffer, as the float32 array the arena copies word for word: an "ifield" must BE int32 and is only viewed."""
+    if kind == "ifield":
+        arr = np.ascontiguousarray(arr)
+        assert arr.dtype == np.int32, arr.dtype
+        return arr.view(np.float32)
+    return np.asarray(arr, np.float32)
+
+
 def build(case, inputs, damp=None):
     """The arena of a case for the argument set `inputs` (stream_cases.inputs(deck, v)); damp: see Arena."""
     nze = inputs["d"]["nze"]
-    contents = [(name, kind, np.asarray(arr, np.float32)) for name, (kind, arr) in case.ins(inputs).items()]
+    contents = [(name, kind, words_of(kind, arr)) for name, (kind, arr) in case.ins(inputs).items()]
     contents += [(name, kind, np.full(shape, val, np.float32)) for name, (kind, shape, val) in case.outs.items()]
     return Arena(case, nze, contents, damp)
 
@@ -160,8 +176,11 @@ def check(arena, down, labels, rules="abcd"):
     for b in arena.bufs.values():
         idx = np.arange(b.off, b.off + b.size).reshape(b.rows, b.cols)
         changed = b.view(down) != b.view(up)
-        if "b" in rules and b.kind == "field":
-            report("b", f"a padding column of {b.name} is not +0.0", idx[:, b.nze:][b.view(down)[:, b.nze:] != 0])
+        if "b" in rules and b.kind in FIELD_KINDS:
+            pad = int(getattr(case, "pad_words", {}).get(b.name, 0))
+            assert (b.view(up)[:, b.nze:] == pad).all()
+            report("b", f"a padding column of {b.name} does not hold its word {pad:#010x}" if pad else f"a padding column of {b.name} is not +0.0",
+                   idx[:, b.nze:][changed[:, b.nze:]])
         if "c" in rules and b.name not in named and b.name not in case.scratch:
             report("c", f"{b.name} is only read by this call (or left untouched) and changed", idx[:, :b.nze][changed[:, :b.nze]])
         if "d" in rules and b.name in may_write:

@@ -1,13 +1,14 @@
 """TEST HELPER (not a conftest) of tests/test_stream_contract.py: the stream-taking entry points of fdwave.h as CASES -- for each one the
 device buffers it works on with two valid argument sets (the TRUE inputs and the DECOYS: another model, other fields, another wavelet, another
-gather, another entry image and illumination), the call itself, and the CPU oracle's answer to either set -- and the late-producer machinery
+gather, another entry image and illumination, other excitation maps), the call itself, and the CPU oracle's answer to either set -- and the late-producer machinery
 that runs a case: a delay on the caller's stream, then the true inputs copied over the decoys, then the entry point, then the outputs copied
 out, all on that one stream and with no synchronisation before the end.
 
 The answers come from the restatements the other modules already pin: tests/test_line_source.py's line_restatement (the forward chain with
 a point or a line source, its trace rows and its illumination; with a point source it is Oracle.forward bit for bit, pinned there on the
 CPU), Oracle.slab_step / slab_back_iter (one forward / backward iteration on row ranges), O.mod_steps, tests/context_reuse_cases.py's
-oracle_laplacian, and numpy slicing / fp32 subtraction for the two copy-like kernels."""
+oracle_laplacian, numpy slicing / fp32 subtraction for the two copy-like kernels, and tests/excitation_restatement.py's maps_restatement,
+pick_restatement and image_formula for the excitation entry points (EXC_CASES, EXC_FOOTPRINT_CASES)."""
 import functools
 import os
 import time
@@ -16,6 +17,7 @@ import numpy as np
 
 from conftest import make_deck, random_fields
 from context_reuse_cases import oracle_laplacian
+from excitation_restatement import image_formula, maps_restatement, pick_restatement
 from oracle import oracle as O
 from test_line_source import args_of, extents_of, line_restatement
 
@@ -23,6 +25,13 @@ NT = 9                                    # a four-step pass, a two-step pass an
 SENTINELS = (7.0, -7.0, 9.0)              # what pure outputs hold before the call; no oracle answer holds any of them (checked on the CPU)
 EINVAL = -1
 MOD_FAC = 0.05
+EXC_EPS = 0.05                            # fdw_dev_image_excitation's eps in the image cases (noise peaks: |amp| > 0.05 max |amp| holds for most cells)
+# ... and in the chain cases, whose amp comes from the excite call: the source sample (the wavelet x 1000) puts the peak near 100 on the
+# compat decks while the noise-born amplitudes have a median of 0.38 and a tenth percentile of 0.16 to 0.19 (CPU oracle, all decks), so
+# eps = 0.002 puts the threshold near 0.2: most interior cells are selected, some are not
+EXC_CHAIN_EPS = 0.002
+# what the padding columns of the excitation maps and images hold (fdwave.h: they "keep their words"): 123.5, a quiet NaN, -321.25, a negative quiet NaN
+PAD_WORDS = dict(amp=0x42F70000, texc=0x7FC12345, exc=0xC3A0A000, IMG=0xFFC54321, EXC=0xC3A0A000, AMP=0x42F70000, AMPB=0x42F70000, IMGB=0xFFC54321)
 
 # name: geometry (nxe, nze, nxb, nzb), compat, spacings, (sx, sz, gz), tuning every context on it gets on top of its family
 DECKS = {
@@ -78,7 +87,20 @@ def inputs(deck, v):
     xlim, _, ztap = extents_of(d)
     if D["compat"] and xlim < nxe and ztap > 0:
         planted[xlim, 0], planted[nxe - 1, ztap - 1], planted[min(xlim + 1, nxe - 1), 3] = 1e-30, -4.0, 2.5
-    return _freeze(dict(d=d, v2=d["v2"], p0=p0, pp0=pp0, f1=f1, f0=f0, pr=pr, ppr=ppr, m0=m0, m1=m1, srce=srce,
+    # the excitation maps, from a generator of their own (the arrays above are what they were before these existed).  Every texc word is
+    # positive: as float words the answers are subnormals, not NaNs
+    erng = np.random.default_rng(900 + seed)
+    nxb, nzb = d["nxb"], d["nzb"]
+    amp0 = (0.01 * erng.standard_normal((nxe, nze))).astype(f)
+    exc0 = erng.standard_normal((nxe, nze)).astype(f)
+    texc_maps = erng.integers(100, 1100, (nxe, nze)).astype(np.int32)          # no iteration writes (excite) or meets (pick) any of them
+    texc_pick = erng.integers(1, NT + 4, (nxe, nze)).astype(np.int32)           # uniform in [1, NT + 3]: with top = NT, 9 of 12 values meet an iteration
+    amp_img = erng.standard_normal((nxe, nze)).astype(f)                        # a peak map whose border cells tower over the interior
+    border = np.ones((nxe, nze), bool)
+    border[nxb:nxe - nxb, nzb:nze - nzb] = False
+    amp_img[border] *= f(50.0)
+    exc_maps = dict(amp0=amp0, exc0=exc0, texc_maps=texc_maps, texc_pick=texc_pick, amp_img=amp_img)
+    return _freeze(dict(exc_maps, d=d, v2=d["v2"], p0=p0, pp0=pp0, f1=f1, f0=f0, pr=pr, ppr=ppr, m0=m0, m1=m1, srce=srce,
                         msrce=(1e-2 * rng.standard_normal(NT)).astype(f), w=rng.standard_normal((NT, nx)).astype(f),
                         il0=(0.5 + rng.random((nxe, nze))).astype(f), img0=rng.standard_normal((nxe, nze)).astype(f),
                         samples=rng.standard_normal((4, nx)).astype(f), ga=rng.standard_normal((NT, nx)).astype(f),
@@ -159,7 +181,8 @@ def mod_chain(deck, numerics, v):
 # ---------------------------------------------------------------------------------------------------------------------------------------
 class Case:
     """name; deck; numerics; two_step (None: the context's default); dialect.
-    ins(i) -> {buffer: (kind, array)} for an argument set i; kind "field" = [nxe][pitch] on the device, "flat" = dense.
+    ins(i) -> {buffer: (kind, array)} for an argument set i; kind "field" = [nxe][pitch] on the device, "flat" = dense, "ifield" = a field of
+              int32 words (d_texc): an int32 array, uploaded, downloaded and compared as words (its answer: the words seen as float32).
     outs   -> {buffer: (kind, shape, sentinel)}: pure outputs.
     call(ctx, ptr, stream) -> [(label, buffer, post or None, rows or None)]: makes the call(s) and says where each answer lies.
     want(v) -> {label: array}.
@@ -169,13 +192,17 @@ class Case:
                   interior; fdw_dev_steps_shrink, whose rows between the valid ones hold intermediate values);
     finalized     buffers the case itself hands to fdw_dev_taper_finalize after the call: their rows outside the rows asked for come back
                   damped once (damped_once), not as uploaded;
-    tuning        set_tuning arguments of this case alone, on top of the deck's."""
+    tuning        set_tuning arguments of this case alone, on top of the deck's;
+    pad_words     {buffer: 32-bit word} what the padding columns of a field hold before the call instead of +0.0 (and must hold after it);
+    cells         {label: (rows, columns)} the cells fdwave.h lets the call write in a label's array where that is not the whole array: the
+                  non-vacuity tests count changed / differing cells there."""
 
     def __init__(self, name, deck, numerics, two_step, ins, outs, call, want, dialect=0, env=None, scratch=(), written_rows=None, tuning=None,
-                 finalized=()):
+                 finalized=(), pad_words=None, cells=None):
         self.name, self.deck, self.numerics, self.two_step, self.dialect, self.env = name, deck, numerics, two_step, dialect, env or {}
         self.ins, self.outs, self.call, self.want = ins, outs, call, want
         self.scratch, self.written_rows, self.tuning, self.finalized = tuple(scratch), dict(written_rows or {}), dict(tuning or {}), tuple(finalized)
+        self.pad_words, self.cells = dict(pad_words or {}), dict(cells or {})
 
     def make_ctx(self):
         """The context of the case; self.env holds switches the library reads when a context is created."""
@@ -589,6 +616,179 @@ assert len({c.name for c in CASES + FOOTPRINT_CASES}) == len(CASES) + len(FOOTPR
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------------
+# EXC_CASES (both modules) and EXC_FOOTPRINT_CASES (tests/test_dev_footprint.py): the excitation entry points
+# ---------------------------------------------------------------------------------------------------------------------------------------
+EXC_CASES = []                # fdw_dev_excite_steps, fdw_dev_line_pick_steps, fdw_dev_image_excitation on ragged / stepped / tiles
+EXC_FOOTPRINT_CASES = []      # the same builders on the edge decks
+
+
+def _interior(deck):
+    nxe, nze, nxb, nzb, nx, nz = _dims(deck)
+    return slice(nxb, nxb + nx), slice(nzb, nzb + nz)
+
+
+def _update_extents(deck):
+    xlim, zlim, _ = extents_of(inputs(deck, "true")["d"])
+    return slice(0, xlim), slice(0, zlim)
+
+
+@functools.lru_cache(maxsize=None)
+def excite_answers(deck, numerics, v):
+    """amp, texc (as float words), P (damped once), PP after NT iterations of the forward loop with the maps, from (p0, pp0, amp0, texc_maps).
+    The answer arrays carry the entry words outside the update extents."""
+    i = inputs(deck, v)
+    sx, sz, _ = DECKS[deck]["place"]
+    xlim, zlim, _ = extents_of(i["d"])
+    amp, texc, _, PP = maps_restatement(oracle(deck, numerics), i["v2"], sx, sz, i["srce"], xlim, zlim, i["p0"], i["pp0"], i["amp0"], i["texc_maps"])
+    c = chain(deck, numerics, v, False)
+    assert np.array_equal(PP.view(np.uint32), c["PP"].view(np.uint32)), "the chain of maps_restatement is the forward chain of the loop cases"
+    assert texc.dtype == np.int32 and (texc > 0).all()
+    return _freeze(dict(amp=amp, texc=texc.view(np.float32), itexc=texc, P=c["P"], PP=c["PP"]))
+
+
+@functools.lru_cache(maxsize=None)
+def pick_answers(deck, numerics, v, fields="p", texc_from=None):
+    """exc, P (damped once, as fdw_dev_taper_finalize leaves it), PP after NT iterations of the line loop at depth gz with the pick (top = NT), from noise fields (fields "p":
+    p0, pp0; "r": pr, ppr), exc0 and texc_pick -- or, texc_from = "excite", the map the excite case leaves."""
+    i = inputs(deck, v)
+    gz = DECKS[deck]["place"][2]
+    texc = i["texc_pick"] if texc_from is None else excite_answers(deck, numerics, v)["itexc"]
+    a, b = ("p0", "pp0") if fields == "p" else ("pr", "ppr")
+    r = pick_restatement(oracle(deck, numerics), i["d"], i["v2"], i["w"], gz, texc, NT, i["exc0"], i[a], i[b])
+    return _freeze(dict(exc=r["exc"], P=r["P"], PP=r["PP"], picked=r["picked"]))      # P as line_restatement gives it: damped once already
+
+
+def image_answer(deck, exc, amp, img0, eps=EXC_EPS):
+    """The entry image with image_formula applied to the interiors: every word outside the interior is the entry word."""
+    inner = _interior(deck)
+    out = np.array(img0, np.float32)
+    out[inner] = image_formula(exc[inner], amp[inner], eps, out[inner])
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def chain_answers(deck, numerics, v):
+    e = excite_answers(deck, numerics, v)
+    k = pick_answers(deck, numerics, v, fields="r", texc_from="excite")
+    return _freeze(dict(amp=e["amp"], texc=e["texc"], exc=k["exc"], img=image_answer(deck, k["exc"], e["amp"], inputs(deck, v)["img0"], EXC_CHAIN_EPS)))
+
+
+def _exc_case(kind, deck, numerics, two_step, split=((0, NT),), tuning=None, to=None):
+    """kind = excite | pick: fdw_dev_excite_steps / fdw_dev_line_pick_steps over four rotating buffers, then fdw_dev_taper_finalize as
+    _loop_case does; image: fdw_dev_image_excitation (twice, see there); chain: excite, pick on the excite call's texc (a second quartet of buffers), image of
+    that exc and amp, on one stream with nothing in between.  Every map and image has a sentinel word in its padding columns."""
+    nxe, nze, nxb, nzb, nx, nz = _dims(deck)
+    sx, sz, gz = DECKS[deck]["place"]
+    ext, inner = _update_extents(deck), _interior(deck)
+    field_outs = lambda names: {n: ("field", (nxe, nze), s) for n, s in zip(names, (7.0, -7.0, 9.0, -7.0))}      # noqa: E731
+
+    def loops(ctx, bufs, stream, fn):
+        ip, ipp = 0, 1
+        for k, (it0, n) in enumerate(split):
+            ip, ipp = fn(bufs, it0, n, dict(first_pp_twice=k > 0, ip=ip, ipp=ipp, stream=stream))
+        return ip, ipp
+
+    if kind == "excite":
+        ins = lambda i: dict(b0=("field", i["p0"]), b1=("field", i["pp0"]), v2=("field", i["v2"]), src=("flat", i["srce"]),      # noqa: E731
+                             amp=("field", i["amp0"]), texc=("ifield", i["texc_maps"]))
+        outs, scratch = field_outs(("b2", "b3")), ("b0", "b1", "b2", "b3")
+
+        def call(ctx, p, stream):
+            bufs = [p["b0"], p["b1"], p["b2"], p["b3"]]
+            ip, ipp = loops(ctx, bufs, stream, lambda b, it0, n, a: ctx.dev_excite_steps(b, p["v2"], p["src"], sx, sz, p["amp"], p["texc"], it0, n, **a))
+            ctx.dev_taper_finalize(bufs[ip], stream=stream)
+            return [("PP", f"b{ipp}", None, None), ("P", f"b{ip}", None, None), ("amp", "amp", None, None), ("texc", "texc", None, None)]
+
+        want = lambda v: {k: a for k, a in excite_answers(deck, numerics, v).items() if k != "itexc"}      # noqa: E731
+        cells = dict(amp=ext, texc=ext)
+    elif kind == "pick":      # texc is neither labelled nor scratch: rule (c) checks that the `const int *` comes back as uploaded
+        ins = lambda i: dict(b0=("field", i["p0"]), b1=("field", i["pp0"]), v2=("field", i["v2"]), src=("flat", i["w"]),      # noqa: E731
+                             texc=("ifield", i["texc_pick"]), exc=("field", i["exc0"]))
+        outs, scratch = field_outs(("b2", "b3")), ("b0", "b1", "b2", "b3")
+
+        def call(ctx, p, stream):
+            bufs = [p["b0"], p["b1"], p["b2"], p["b3"]]
+            ip, ipp = loops(ctx, bufs, stream, lambda b, it0, n, a: ctx.dev_line_pick_steps(b, p["v2"], p["src"], gz, p["texc"], NT, p["exc"], it0, n, **a))
+            ctx.dev_taper_finalize(bufs[ip], stream=stream)
+            return [("PP", f"b{ipp}", None, None), ("P", f"b{ip}", None, None), ("exc", "exc", None, None)]
+
+        want = lambda v: {k: a for k, a in pick_answers(deck, numerics, v).items() if k != "picked"}      # noqa: E731
+        cells = dict(exc=ext)
+    elif kind == "image":      # EXC, AMP and AMPB are only read
+        # Two calls in a row on the stream.  The first forms another image (IMGB) from a peak map four times as high (AMPB): the context
+        # holds ONE peak word, cleared by a memset at the start of each call, and a memset issued on another stream runs EARLY (during the
+        # delay) -- harmless for a single call, but before the first call's peak kernel here, so that the second call would meet a
+        # stale peak four times too high and select fewer cells.
+        big = lambda i: (np.float32(4.0) * i["amp_img"]).astype(np.float32)      # noqa: E731
+        ins = lambda i: dict(EXC=("field", i["exc0"]), AMP=("field", i["amp_img"]), IMG=("field", i["img0"]), AMPB=("field", big(i)),      # noqa: E731
+                             IMGB=("field", i["lap_in"]))
+        outs, scratch = {}, ()
+
+        def call(ctx, p, stream):
+            ctx.dev_image_excitation(p["EXC"], p["AMPB"], EXC_EPS, p["IMGB"], stream=stream)
+            ctx.dev_image_excitation(p["EXC"], p["AMP"], EXC_EPS, p["IMG"], stream=stream)
+            return [("img", "IMG", None, None), ("img_first", "IMGB", None, None)]
+
+        want = lambda v: dict(img=image_answer(deck, inputs(deck, v)["exc0"], inputs(deck, v)["amp_img"], inputs(deck, v)["img0"]),      # noqa: E731
+                              img_first=image_answer(deck, inputs(deck, v)["exc0"], big(inputs(deck, v)), inputs(deck, v)["lap_in"]))
+        cells = dict(img=inner, img_first=inner)
+    else:
+        assert kind == "chain"
+        ins = lambda i: dict(a0=("field", i["p0"]), a1=("field", i["pp0"]), c0=("field", i["pr"]), c1=("field", i["ppr"]), v2=("field", i["v2"]),      # noqa: E731
+                             src=("flat", i["srce"]), w=("flat", i["w"]), amp=("field", i["amp0"]), texc=("ifield", i["texc_maps"]),
+                             exc=("field", i["exc0"]), IMG=("field", i["img0"]))
+        outs, scratch = field_outs(("a2", "a3", "c2", "c3")), ("a0", "a1", "a2", "a3", "c0", "c1", "c2", "c3")
+
+        def call(ctx, p, stream):
+            ctx.dev_excite_steps([p[f"a{k}"] for k in range(4)], p["v2"], p["src"], sx, sz, p["amp"], p["texc"], 0, NT, stream=stream)
+            ctx.dev_line_pick_steps([p[f"c{k}"] for k in range(4)], p["v2"], p["w"], gz, p["texc"], NT, p["exc"], 0, NT, stream=stream)
+            ctx.dev_image_excitation(p["exc"], p["amp"], EXC_CHAIN_EPS, p["IMG"], stream=stream)
+            return [("amp", "amp", None, None), ("texc", "texc", None, None), ("exc", "exc", None, None), ("img", "IMG", None, None)]
+
+        want = lambda v: dict(chain_answers(deck, numerics, v))      # noqa: E731
+        cells = dict(amp=ext, texc=ext, exc=ext, img=inner)
+    name = dict(excite="excite", pick="pick", image="exc_image", chain="exc_chain")[kind]
+    name += ("" if len(split) == 1 else "-chained") + ("-generic" if tuning else "")
+    _add(name, deck, numerics, two_step, ins, outs, call, want, to=to, scratch=scratch, tuning=tuning, cells=cells,
+         # the border ROWS of d_img must come back as uploaded
+         written_rows=dict(IMG=inner[0], IMGB=inner[0]) if kind == "image" else dict(IMG=inner[0]) if kind == "chain" else None,
+         pad_words=dict(PAD_WORDS))
+
+
+def _exc_cases():
+    fams = ((-1, "ragged"), (1, "ragged"), (4, "stepped"))
+    for num in (0, 1):
+        for kind in ("excite", "pick"):
+            for fam, deck in fams:
+                _exc_case(kind, deck, num, fam, to=EXC_CASES)
+    for kind in ("excite", "pick"):
+        for fam, deck in fams:      # 5 + 4 steps, the maps carried over, no host synchronisation in between
+            _exc_case(kind, deck, 0, fam, split=((0, 5), (5, 4)), to=EXC_CASES)
+    for kind in ("excite", "pick"):
+        _exc_case(kind, "tiles", 0, 4, to=EXC_CASES)      # lean and full tiles
+    for kind in ("excite", "pick"):      # the generic step followed by the compare-and-select / pick kernel
+        _exc_case(kind, "ragged", 0, -1, tuning=dict(use_generic=True), to=EXC_CASES)
+    _exc_case("image", "ragged", 0, None, to=EXC_CASES)
+    _exc_case("chain", "ragged", 0, -1, to=EXC_CASES)
+    _exc_case("chain", "stepped", 0, 4, to=EXC_CASES)
+    for deck in EDGE_DECKS:
+        for num in (0, 1):
+            for kind in ("excite", "pick"):
+                for fam in (-1, 1, 4):
+                    _exc_case(kind, deck, num, fam, to=EXC_FOOTPRINT_CASES)
+        for kind in ("excite", "pick"):
+            _exc_case(kind, deck, 0, -1, tuning=dict(use_generic=True), to=EXC_FOOTPRINT_CASES)
+        _exc_case("image", deck, 0, None, to=EXC_FOOTPRINT_CASES)
+        _exc_case("chain", deck, 0, 4, to=EXC_FOOTPRINT_CASES)
+
+
+_exc_cases()
+_ALL = CASES + FOOTPRINT_CASES + EXC_CASES + EXC_FOOTPRINT_CASES
+assert len({c.name for c in _ALL}) == len(_ALL)
+EXC_BY_NAME = {c.name: c for c in EXC_CASES}
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------
 # the late producer
 # ---------------------------------------------------------------------------------------------------------------------------------------
 class Delay:
@@ -642,8 +842,8 @@ class Run:
         true, decoy = case.ins(inputs(case.deck, "true")), case.ins(inputs(case.deck, "decoy"))
         self.dev, self.stage = {}, {}
         for name, (kind, arr) in decoy.items():
-            self.dev[name] = self._up(kind, arr)
-            self.stage[name] = self._up(kind, true[name][1])
+            self.dev[name] = self._up(kind, arr, name)
+            self.stage[name] = self._up(kind, true[name][1], name)
         self.kinds = {name: kind for name, (kind, _) in decoy.items()}
         for name, (kind, shape, val) in case.outs.items():
             self.dev[name] = self._up(kind, np.full(shape, val, np.float32))
@@ -656,14 +856,17 @@ class Run:
         for name, t in self.dev.items():
             t.copy_(self.first[name])
 
-    def _up(self, kind, arr):
+    def _up(self, kind, arr, name=None):
         torch = self.torch
-        a = torch.from_numpy(np.array(arr, np.float32, order="C")).to("cuda:0")
         if kind == "flat":
-            return a
-        t = torch.zeros((a.shape[0], self.ctx.pitch), device="cuda:0")      # padding columns [nze, pitch) stay zero
-        t[:, :a.shape[1]] = a
-        return t
+            return torch.from_numpy(np.array(arr, np.float32, order="C")).to("cuda:0")
+        # a field: built on the host as words, so that an int32 map and a NaN pad word arrive bit for bit
+        dt = np.int32 if kind == "ifield" else np.float32
+        arr = np.ascontiguousarray(arr)
+        assert kind == "field" or arr.dtype == np.int32, (name, arr.dtype)
+        h = np.full((arr.shape[0], self.ctx.pitch), self.case.pad_words.get(name, 0), np.uint32)      # padding columns [nze, pitch): +0.0 or the case's word
+        h[:, :arr.shape[1]] = np.asarray(arr, dt).view(np.uint32)
+        return torch.from_numpy(h.view(dt)).to("cuda:0")
 
     def enqueue(self, S, delay, ms, entry=None, collect=True):
         """entry: the stream handed to the entry point (default S, the producer's own)."""
@@ -690,8 +893,8 @@ class Run:
         out = {}
         for label, name, post, rows in self.labels:
             a = self.res[name].cpu().numpy()
-            if self.kinds[name] == "field":
-                a = np.ascontiguousarray(a[:, :self.nze])
+            if self.kinds[name] in ("field", "ifield"):
+                a = np.ascontiguousarray(a[:, :self.nze]).view(np.float32)
             if post is not None:
                 a = post(a)
             out[label] = a if rows is None else a[rows]

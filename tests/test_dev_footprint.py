@@ -2,22 +2,26 @@
 of the stream contract, the same builders on three edge decks, and calls on row ranges -- runs once with ALL its buffers carved from one
 guarded arena (tests/footprint_arena.py).  Afterwards the answers must equal the CPU oracle's bit for bit (a value pulled in from a guard
 is a NaN) and the footprint must be what fdwave.h says: guard words untouched, padding columns +0.0, `const` and untouched buffers as
-uploaded, rows outside the rows asked for as uploaded.
+uploaded, rows outside the rows asked for as uploaded.  The excitation entry points (stream_cases.EXC_CASES and, on
+the edge decks, EXC_FOOTPRINT_CASES) run the same way; their maps and images carry a sentinel word in the padding columns, which must
+come back, and d_texc travels as int32 words.
 
 Unmarked tests: the checker sees a planted word in each place it guards (and passes a clean arena); the cases of the edge decks are not
 vacuous; the decks have the properties they were chosen for; the catalogue of tests/test_stream_contract.py is unchanged.
 
-Measured on one MI355X: see DESIGN.md section 6o for the case count, the wall time and what the module found."""
+Measured on one MI355X: see DESIGN.md sections 6o and 6s for the case counts, the wall times and what the module found."""
 import numpy as np
 import pytest
 
 import footprint_arena as FA
 import stream_cases as SC
 from conftest import assert_bit_equal
+from excitation_restatement import image_selection
 
 gpu = pytest.mark.gpu
-ALL_CASES = SC.CASES + SC.FOOTPRINT_CASES
-FP = {c.name: c for c in SC.FOOTPRINT_CASES}
+EXC_ALL = SC.EXC_CASES + SC.EXC_FOOTPRINT_CASES
+ALL_CASES = SC.CASES + SC.FOOTPRINT_CASES + EXC_ALL
+FP = {c.name: c for c in SC.FOOTPRINT_CASES + EXC_ALL}
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------------
@@ -84,12 +88,14 @@ def test_the_edge_decks_have_their_properties(deck):
         assert nxe < 43 and nxe - 27 < 16 and pitch - nze == 3
 
 
-@pytest.mark.parametrize("case", SC.FOOTPRINT_CASES, ids=repr)
+@pytest.mark.parametrize("case", SC.FOOTPRINT_CASES + EXC_ALL, ids=repr)
 def test_the_footprint_cases_are_not_vacuous(case):
     """No oracle answer holds a sentinel or a NaN, and each differs from what its buffer held before the call in more than half of its
     cells (a field that fdw_dev_taper_finalize alone touches, the `const` d_p of fdw_dev_step included: of the cells that pass damps at all
     -- rows below xlim of the damped strip; the rest it must hand back).  A loop's fields end in two of its four rotating buffers, and which
-    two only the real call says (the stand-in context knows no rotation): their answers are held against what EVERY one of b0..b3 held."""
+    two only the real call says (the stand-in context knows no rotation): their answers are held against what EVERY one of b0..b3 held.
+    The excitation maps and images are counted over the cells fdwave.h lets the call write (Case.cells: the update extents, the interior);
+    for those cases the oracle's answer to the decoys also differs from the true one in more than half of those cells."""
     i = SC.inputs(case.deck, "true")
     arena = _arena(case)
     labels = case.call(_NullCtx(), {name: 0 for name in arena.bufs}, None)
@@ -102,6 +108,11 @@ def test_the_footprint_cases_are_not_vacuous(case):
         others = [arena.bufs[n].values(arena.up) for n in sorted(rotating)] if where[label] in rotating else []
         for b in [before[label]] + others:
             _differs(case, i, label, a, b)
+    if case in EXC_ALL:
+        decoy = case.want("decoy")
+        for label, a in want.items():
+            share = (a.view(np.uint32) != decoy[label].view(np.uint32))[case.cells.get(label, (slice(None),) * a.ndim)].mean()
+            assert share > 0.5, f"{case.name}: {label} of the decoys equals the true answer in {1 - share:.0%} of the cells"
 
 
 def _differs(case, i, label, a, b):
@@ -110,6 +121,8 @@ def _differs(case, i, label, a, b):
     for s in SC.SENTINELS:
         assert not (a == s).any(), f"{case.name}: {label} holds the sentinel {s}"
     diff = a.view(np.uint32) != b.view(np.uint32)
+    if label in case.cells:
+        diff = diff[case.cells[label]]
     if case.name.startswith("taper_finalize") or (case.name.startswith("step_fwd-") and label == "P"):      # a damping pass is all the call owes it
         xlim, _, ztap = SC.extents_of(i["d"])
         diff = diff[:xlim, :ztap]
@@ -137,7 +150,7 @@ def _answered(arena, labels, want):
     for label, name, post, rows in labels:
         if post is None:
             b = arena.bufs[name]
-            v = b.view(down)[:, :b.nze] if b.kind == "field" else b.view(down)
+            v = b.view(down)[:, :b.nze] if b.kind in FA.FIELD_KINDS else b.view(down)
             v[slice(None) if rows is None else rows] = np.asarray(want[label], np.float32).reshape(v[slice(None) if rows is None else rows].shape).view(np.uint32)
     return down
 
@@ -161,6 +174,10 @@ PLANTS = [
     ("step_recv-rows17-30-narrow", "d", ("IMG", (16, 60)), "IMG[16][60]"),
     ("steps_shrink-flush", "d", ("A", (3, 0)), "A[3][0]"),
     ("back4-flush", "c", ("L0", (33, 100)), "L0[33][100]"),
+    # the excitation cases: a sentinel pad word, the `const int *d_texc` of a pick, the float before it
+    ("excite-onecol-one-step", "b", ("amp", (5, 449)), "amp[5][449] (a padding column)"),
+    ("pick-flush-pipeline", "c", ("texc", (63, 319)), "texc[63][319]"),
+    ("pick-narrow-pipeline-fast", "a", ("texc", -1), "1 floats BEFORE texc"),
 ]
 
 
@@ -182,6 +199,82 @@ def test_control_a_planted_word_is_reported_at_its_place(name, rule, where, says
     bad = FA.check(arena, down, labels)
     assert len(bad) == 1, bad
     assert f"rule ({rule})" in bad[0] and says in bad[0] and case.name in bad[0] and f"arena word {w}:" in bad[0], bad[0]
+
+
+def test_control_a_changed_border_word_of_the_image_fails_the_answer():
+    """A border word of d_img in an interior ROW: rule (d) speaks of rows and is silent; the whole-array answer is what catches it."""
+    case, arena, labels, down = _control("exc_image-narrow")
+    _assert_answers(case, arena, down, labels)
+    nxb = SC.DECKS["narrow"]["geom"][2]
+    b = arena.bufs["IMG"]
+    down[b.off + (nxb + 1) * b.cols + 2] ^= 0x00400000
+    assert FA.check(arena, down, labels) == []
+    with pytest.raises(AssertionError, match="img, exc_image-narrow: 1 of"):
+        _assert_answers(case, arena, down, labels)
+    down[b.off + 1 * b.cols + 2] ^= 0x00400000      # and one in a border row: rule (d) names it
+    bad = FA.check(arena, down, labels)
+    assert len(bad) == 1 and "rule (d)" in bad[0] and "IMG[1][2]" in bad[0], bad
+
+
+def test_the_pad_words_and_texc_reach_the_arena_as_words():
+    """d_texc is int32: the arena holds exactly the int32 words of the map (no float conversion on the way), the answers carry them back as
+    words, and the padding columns of the maps hold their sentinel words, everything else's +0.0."""
+    for name in ("excite-onecol-one-step", "pick-narrow-pipeline-fast", "exc_chain-flush-pipeline", "exc_image-onecol"):
+        case = FP[name]
+        i = SC.inputs(case.deck, "true")
+        arena = _arena(case)
+        ins = case.ins(i)
+        for bname, b in arena.bufs.items():
+            pad = b.view(arena.up)[:, b.nze:]
+            if b.kind in FA.FIELD_KINDS:
+                assert (pad == case.pad_words.get(bname, 0)).all() and (bname in case.pad_words) == (bname in SC.PAD_WORDS), (name, bname)
+            if b.kind == "ifield":
+                src = ins[bname][1]
+                assert src.dtype == np.int32 and (src > 0).all()
+                assert np.array_equal(b.view(arena.up)[:, :b.nze].view(np.int32), src), (name, bname)
+                assert np.array_equal(b.values(arena.up).view(np.int32), src), (name, bname)
+        assert any(b.kind == "ifield" for b in arena.bufs.values()) or name.startswith("exc_image")
+    want = FP["excite-onecol-one-step"].want("true")["texc"]
+    assert want.dtype == np.float32 and 1 <= want.view(np.int32).min() and np.isfinite(want).all()
+
+
+@pytest.mark.parametrize("deck", ["ragged"] + list(SC.EDGE_DECKS))
+def test_the_image_peak_is_the_interiors(deck):
+    """The image cases' peak map: border cells 50 times the noise.  With the peak taken over the whole array no cell would be selected at
+    eps = 0.05; over the interior (fdwave.h) most are -- and the answer changes most of the interior."""
+    i = SC.inputs(deck, "true")
+    inner = SC._interior(deck)
+    whole = image_selection(i["amp_img"], SC.EXC_EPS).reshape(i["amp_img"].shape)
+    own = image_selection(i["amp_img"][inner], SC.EXC_EPS)
+    print(f"{deck}: the whole-array peak selects {int(whole[inner].sum())} interior cells, the interior peak {own.mean():.1%} of them")
+    assert whole[inner].sum() == 0 and own.mean() > 0.75
+    # ... and a peak word left four times too high by the case's first call (a memset on the wrong stream) would change the selection
+    a32 = np.abs(i["amp_img"][inner]).ravel()
+    stale = a32 > np.float32(SC.EXC_EPS) * (np.float32(4.0) * a32.max())
+    assert (stale != own).mean() > 0.25
+    case = FP[f"exc_image-{deck}"]
+    want = case.want("true")["img"]
+    assert (want[inner].view(np.uint32) != i["img0"][inner].view(np.uint32)).mean() > 0.75
+    outside = np.ones(want.shape, bool)
+    outside[inner] = False
+    assert np.array_equal(want[outside].view(np.uint32), i["img0"][outside].view(np.uint32))
+
+
+def test_the_excitation_answers_keep_the_entry_words_outside_the_extents():
+    """What the whole-array comparison of amp, texc and exc stands on: outside [:xlim, :zlim] the answers ARE the entry words (on the decks
+    that have such cells), inside most cells changed; a pick never changes texc."""
+    for name in ("excite-flush-one-step", "excite-narrow-pipeline", "pick-flush-two-step", "pick-narrow-one-step"):
+        case = FP[name]
+        i = SC.inputs(case.deck, "true")
+        rows, cols = SC._update_extents(case.deck)
+        outside = np.ones(i["amp0"].shape, bool)
+        outside[rows, cols] = False
+        assert outside.any()
+        want = case.want("true")
+        entry = dict(amp=i["amp0"], texc=i["texc_maps"].view(np.float32), exc=i["exc0"])
+        for label in set(want) & set(entry):
+            assert np.array_equal(want[label][outside].view(np.uint32), entry[label][outside].view(np.uint32)), (name, label)
+            assert (want[label][rows, cols].view(np.uint32) != entry[label][rows, cols].view(np.uint32)).mean() > 0.5, (name, label)
 
 
 def test_control_the_fused_back4_labels_leave_the_levels_out():

@@ -7,7 +7,7 @@ decoys, the entry point with stream = S, copies of every output.  Right after th
 did not synchronise, and the delay still held the inputs back when everything had been issued); after S.synchronize() the outputs must
 equal the CPU oracle's answer to the TRUE inputs bit for bit.  A launch, copy or memset that lands on any other stream runs during the
 delay: it reads decoys, or writes before the producer does, and the comparison fails.  The cases and their oracle answers are in
-tests/stream_cases.py; the unmarked test below shows on the CPU that the decoys matter (the oracle's two answers differ in more than half
+tests/stream_cases.py (CASES, the catalogue of 100, and EXC_CASES, the excitation entry points: DESIGN.md section 6s); the unmarked test below shows on the CPU that the decoys matter (the oracle's two answers differ in more than half
 of the cells of every output, and no answer holds a sentinel).
 
 The delay: torch.cuda._sleep, calibrated per module with two events.  Measured on one MI355X on the parent commit: the longest host wall
@@ -36,22 +36,29 @@ gpu = pytest.mark.gpu
 # ---------------------------------------------------------------------------------------------------------------------------------------
 # CPU: the decoys matter
 # ---------------------------------------------------------------------------------------------------------------------------------------
-def _adequate(true, decoy, what):
+def _adequate(true, decoy, what, cells=None):
+    """cells: {label: (rows, columns)} where a call may write only part of a label's array (Case.cells): the share is counted there."""
     assert sorted(true) == sorted(decoy), what
     for label, a in true.items():
         b = decoy[label]
         assert a.shape == b.shape and a.size > 0, (what, label)
         assert np.isfinite(a).all() and np.isfinite(b).all(), (what, label)
-        share = float((a.view(np.uint32) != b.view(np.uint32)).mean())
+        where = (cells or {}).get(label, (slice(None),) * a.ndim)
+        share = float((a.view(np.uint32) != b.view(np.uint32))[where].mean())
         assert share > 0.5, f"{what}: {label} of the decoys equals the true answer in {1 - share:.0%} of the cells"
         for s in SC.SENTINELS:
             assert not (a == s).any(), f"{what}: {label} holds the sentinel {s}"
 
 
-@pytest.mark.parametrize("case", SC.CASES, ids=repr)
+ALL_CASES = SC.CASES + SC.EXC_CASES      # the 100 cases of the catalogue, then the excitation entry points (DESIGN.md section 6s)
+
+
+@pytest.mark.parametrize("case", ALL_CASES, ids=repr)
 def test_the_decoys_matter(case):
-    """A call that read decoys, or an output still holding its sentinel, cannot pass for the answer to the true inputs."""
-    _adequate(case.want("true"), case.want("decoy"), case.name)
+    """A call that read decoys, or an output still holding its sentinel, cannot pass for the answer to the true inputs.  Where a call may
+    write only part of an array (the excitation maps: the update extents; the image: the interior) the answers differ in more than half of
+    THOSE cells -- the rest holds entry words, which differ between the two sets anyway."""
+    _adequate(case.want("true"), case.want("decoy"), case.name, case.cells)
 
 
 def test_the_check_field_plant_is_three_cells():
@@ -82,7 +89,7 @@ def _check(run, what):
 
 
 @gpu
-@pytest.mark.parametrize("case", SC.CASES, ids=repr)
+@pytest.mark.parametrize("case", ALL_CASES, ids=repr)
 def test_late_producer(case, torch_delay):
     torch, delay = torch_delay
     run = SC.Run(case, torch)
@@ -145,21 +152,27 @@ def test_two_contexts_on_two_streams(torch_delay):
 @gpu
 @pytest.mark.parametrize("name", ["steps2-ragged-one-step", "steps2-ragged-two-step", "steps2-stepped-pipeline"])
 def test_control_a_call_on_another_stream_is_caught(name, torch_delay):
+    """Which hardware queue serves a stream is the runtime's choice, and it depends on what the tests before this one created: with the
+    excitation cases in front of it the first pair this test draws came to share a queue (T's work finished the moment S's delay ended),
+    while the pairs drawn next did not.  So up to three pairs are tried, each with a fresh context and buffers, before the test skips."""
     torch, delay = torch_delay
-    run = SC.Run(SC.BY_NAME[name], torch)
-    S, T = torch.cuda.Stream(), torch.cuda.Stream()
-    torch.cuda.synchronize()
-    run.enqueue(S, delay, DELAY_MS, entry=T, collect=False)
-    t0 = time.perf_counter()
-    while not T.query() and time.perf_counter() - t0 < 0.5e-3 * DELAY_MS:
-        pass
-    overlapped = T.query() and not S.query()
-    S.wait_stream(T)
-    run.collect(S)
-    S.synchronize()
-    T.synchronize()
-    if not overlapped:
+    for attempt in range(3):
+        run = SC.Run(SC.BY_NAME[name], torch)
+        S, T = torch.cuda.Stream(), torch.cuda.Stream()
+        torch.cuda.synchronize()
+        run.enqueue(S, delay, DELAY_MS, entry=T, collect=False)
+        t0 = time.perf_counter()
+        while not T.query() and time.perf_counter() - t0 < 0.5e-3 * DELAY_MS:
+            pass
+        overlapped = T.query() and not S.query()
+        S.wait_stream(T)
+        run.collect(S)
+        S.synchronize()
+        T.synchronize()
+        if overlapped:
+            break
         run.close()
+    if not overlapped:
         pytest.skip("the two streams share a hardware queue: T did not run while the delay held S")
     want, got = run.case.want("true"), run.results()
     for label in want:
