@@ -751,6 +751,58 @@ int fdw_dev_image_excitation(fdw_ctx *ctx, const float *d_exc, const float *d_am
 int fdw_shot_excitation_batch(fdw_ctx *ctx, int nshots, const float *v2_all, unsigned long long draw_offset, int sx0, int dsx, int sz, int gz,
                               const float *srce, const float *d_obs, float eps, float *imloc, float *stack, float *exc, float *amp, int *texc);
 
+/* ---- Born modelling: scattered-field gathers from a reflectivity model -------------------------------------------------------------
+ * The other direction of migration: a reflectivity model goes back to data (demigration), the second half of least-squares migration and
+ * of any linearised inversion.  The RTM dialect on full-grid contexts, EXACT and FAST numerics alike (FAST changes the Laplacian only).
+ *
+ * Two field pairs, the background pair (u_p, u_pp) and the scattered pair (du_p, du_pp), caller-owned, [nxl][pitch], each rotated as
+ * fdw_dev_steps rotates its two buffers (swap first, then the new field is written over pp).  One squared-velocity model d_v2 and one
+ * reflectivity d_m, field-shaped [nxl][pitch], of which only the words on the cell set C below are ever used: its border and padding words
+ * influence no output.  Iteration it = it0 .. it0+nsteps-1 runs, in this order:
+ *   1. Background step: iteration it of fd_forward's loop (R:259-267) as fdw_dev_steps runs it -- swap, taper, Laplacian, leap-frog,
+ *      kernel_src with srce[it] at (sx, sz).  U: the stored new field, raw, source sample included (the level recording, illumination,
+ *      snapshots and the excitation maps sample).  A, B: the words the two background buffers held on entry to the iteration (levels it, it-1).
+ *   2. Scattered step: the same iteration without a source on (du_p, du_pp), same d_v2, taper and extents.  D: its stored new field.
+ *   3. Scatter, on C = { (x, z) : nxb <= x < min(nxb+nx, xlim), nzb <= z < min(nzb+nz, zlim) } (fdw_get_extents):
+ *          D = D (+) ( m (*) q )        product and sum rounded separately in fp32, round to nearest, nothing fused, in both numerics
+ *        kind FDW_BORN_FIELD (0): q = U.  The transpose of the cross-correlation imaging condition as this library pairs levels (sample j
+ *                                 meets u^{j+1}).
+ *        kind FDW_BORN_DTT (1):   q = (U (-) A) (-) (A (-) B), three fp32 subtractions: the second time difference, the linearisation of
+ *                                 the modelling in v2 -> v2 (1 + m).
+ *      No cell of C is ever damped (z >= nzb >= ztap), so A and B are the raw words.  Cells outside C receive nothing (no + 0.0f: -0.0
+ *      survives).
+ *   4. Record: d_rec[it][ix] = D[nxb+ix][gz] for ix < nx (after the scatter); rows >= xlim, which no loop time-steps, follow the rule of
+ *      fdw_dev_record_steps applied to the scattered pair.  d_rec0[it][ix] = U[nxb+ix][gz]: fdw_dev_record_steps' gather of the
+ *      background, bit for bit.  Either pointer may be NULL.
+ * Consequences: the background pair equals fdw_dev_steps on it bit for bit; m all zero words, from rest, gives du and d_rec all zero words;
+ * d_rec0 equals fdw_record_shot.
+ *
+ * fdw_dev_born_steps  the loop above on device arrays.  Everything goes on the given stream (NULL: the context's), nothing is synchronised.
+ *                     first_pp_twice applies to both pairs; after an odd or even nsteps the newest fields sit where fdw_dev_steps leaves
+ *                     them.  FDW_EINVAL before anything is enqueued: gz or sz outside [0, zlim), a source row outside the time-stepped
+ *                     rows [0, xlim), a NULL required pointer (the four fields, d_v2, d_m, d_srce), it0 < 0, nsteps < 0, kind outside
+ *                     {0, 1}.  FDW_ESTATE: slab contexts, the sibling's dialects, a context inside a batch.
+ *   Kernels: the one-step register-ring family (orders 2-8, prefetch 1 / 2 / 3 at order 8, EXACT and FAST) has a fused kernel,
+ *   fdw_step_born_kernel: the scattered field rides a second register ring, v2 is read once for both fields, the m row is streamed, and the
+ *   scatter and the trace samples happen in registers before the two stores: 36 B/point/step (six reads, two writes) against 32 for two
+ *   plain steps.  Orders above 8 and the forced generic kernel (and FDW_NO_BORN_FUSED=1 in the environment at fdw_create, for benchmarks and
+ *   tests) run the existing step on each pair and a small scatter kernel behind them; for FDW_BORN_DTT that arrangement keeps (A - B) in a
+ *   context-owned scratch field, allocated by the first call that needs it (the one allocation this entry point can make).  There is no Born
+ *   kernel in the two-step and four-step families: contexts whose plain loop runs them run Born with one-step launches, as fdw_dev_steps does.
+ *   Measured on one MI355X (profiles/born.json; order 8, FDW_BORN_DTT, us per step): 8192^2 fused 413.2, unfused 880.9,
+ *   two plain one-step loops on the parent's build 372.2 (ratio 1.110; FAST 426.7 / 887.0 / 370.3, 1.152); 2048^2 35.0 / 61.2 / 29.9 (1.170;
+ *   FAST 31.7 / 60.7 / 29.6, 1.072).  Order 8, prefetch 2: 208 VGPRs, two waves per SIMD, no scratch.
+ * fdw_born_shot       one shot from rest for the context's nt: m [nx][nz] is embedded into a zeroed field, the gathers are recorded on the
+ *                     device and downloaded transposed to [nx][nt] as fdw_record_shot does (data: scattered; data0, may be NULL: background).
+ *                     v2 NULL: the resident model (FDW_ESTATE without one).  Work arrays are allocated on first use, freed by fdw_destroy.
+ * Out of scope: Born kernels in the two-step and four-step families, batches of Born shots, line-source Born, slabs and several GPUs, the
+ * DTT-adjoint imaging condition. */
+enum { FDW_BORN_FIELD = 0, FDW_BORN_DTT = 1 };
+int fdw_dev_born_steps(fdw_ctx *ctx, float *d_u_p, float *d_u_pp, float *d_du_p, float *d_du_pp, const float *d_v2, const float *d_m, int kind,
+                       const float *d_srce, int sx, int sz, int gz, float *d_rec, float *d_rec0, int it0, int nsteps, int first_pp_twice, void *stream);
+int fdw_born_shot(fdw_ctx *ctx, const float *v2 /* NULL: the resident model */, const float *m /* [nx][nz] */, int kind, int sx, int sz, int gz,
+                  const float *srce, float *data /* [nx][nt] scattered */, float *data0 /* NULL ok: [nx][nt] background */);
+
 /* ---- tuning / introspection --------------------------------------------------------------------
  * fdw_set_tuning  xchunk = rows marched per wave (0 = auto), wz = waves of a block laid along z
  *                 (1,2,4; 0 = auto), use_generic = force the generic-order kernel (tests),

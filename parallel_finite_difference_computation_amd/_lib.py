@@ -12,6 +12,7 @@ vp = C.c_void_p
 
 FDW_OK, FDW_EINVAL, FDW_ENODEVICE, FDW_EHIP, FDW_ENOMEM, FDW_ESTATE = 0, -1, -2, -3, -4, -5
 MODE_FWD, MODE_PLAIN, MODE_RECV = 0, 1, 2
+BORN_FIELD, BORN_DTT = 0, 1      # fdwave.h, "Born modelling": the kind of the scatter
 
 
 class FdwError(RuntimeError):
@@ -160,6 +161,8 @@ SIGNATURES = [
     ("fdw_image_excitation", C.c_int, [vp, vp, C.c_size_t, C.c_float, vp]),
     ("fdw_dev_image_excitation", C.c_int, [vp, vp, vp, C.c_float, vp, vp]),
     ("fdw_shot_excitation_batch", C.c_int, [vp, C.c_int, vp, C.c_ulonglong, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_float, vp, vp, vp, vp, vp]),
+    ("fdw_dev_born_steps", C.c_int, [vp, vp, vp, vp, vp, vp, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, vp]),
+    ("fdw_born_shot", C.c_int, [vp, vp, f32p, C.c_int, C.c_int, C.c_int, C.c_int, f32p, f32p, vp]),
     ("fdw_two_step_active", C.c_int, [vp]),
     ("fdw_steps_per_pass", C.c_int, [vp]),
     ("fdw_selftest", C.c_int, [vp]),

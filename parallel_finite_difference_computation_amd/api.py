@@ -450,6 +450,26 @@ class FDWave:
                                     P.ctypes.data if want_fields else None, PP.ctypes.data if want_fields else None))
         return (data, P, PP) if want_fields else data
 
+    # ---- Born modelling (fdwave.h: scattered-field gathers from a reflectivity model) ----
+    def born_shot(self, v2, m, sx, sz, gz, srce, kind=_lib.BORN_DTT, want_background=False):
+        """One Born shot from rest (fdwave.h, fdw_born_shot): the scattered gather data[nx][nt] of the reflectivity m[nx][nz] in the background
+        v2 (None: the resident model); kind: BORN_FIELD or BORN_DTT.  want_background: also the background gather, which is record_shot()'s."""
+        data = np.zeros((self.nx, self.nt), np.float32)
+        data0 = np.zeros((self.nx, self.nt), np.float32) if want_background else None
+        check(lib().fdw_born_shot(self._h, None if v2 is None else _f32(v2, (self.nxe, self.nze)).ctypes.data, _f32(m, (self.nx, self.nz)), int(kind),
+                                  sx, sz, gz, _f32(srce, (self.nt,)), data, data0.ctypes.data if want_background else None))
+        return (data, data0) if want_background else data
+
+    def dev_born_steps(self, d_u_p, d_u_pp, d_du_p, d_du_pp, d_v2, d_m, kind, d_srce, sx, sz, gz, d_rec, d_rec0, it0, nsteps, first_pp_twice=False,
+                       stream=None):
+        """nsteps Born iterations on the background pair (d_u_p, d_u_pp) and the scattered pair (d_du_p, d_du_pp), each rotated as dev_steps rotates
+        its two buffers; d_m: the reflectivity, field-shaped; d_rec / d_rec0 (device [it][nx], either may be None): the scattered and the
+        background gather (fdwave.h, fdw_dev_born_steps).  stream=None: the context's own non-blocking stream, unordered against the caller's
+        streams (the legacy default stream included); a caller's stream: every launch of the call is issued on it and the call does not
+        synchronise (fdwave.h)."""
+        check(lib().fdw_dev_born_steps(self._h, d_u_p, d_u_pp, d_du_p, d_du_pp, d_v2, d_m, int(kind), d_srce, sx, sz, gz, d_rec, d_rec0, it0, nsteps,
+                                       int(first_pp_twice), stream))
+
     # ---- line sources (fdwave.h: plane-wave and encoded-shot migration) ----
     def shot_line(self, v2, sz, gz, wav, d_obs, imloc=None, want_fields=False, want_illum=False, illum=None):
         """shot() (v2=None: shot_resident()) whose forward loop is driven by the line source wav[nx][nt] at depth sz instead of a point source

@@ -18,6 +18,7 @@
 #include <type_traits>
 #include <vector>
 
+#include "fdw_born.h"
 #include "fdw_excimg.h"
 #include "fdw_internal.h"
 #include "fdw_kernels.h"
@@ -113,6 +114,11 @@ struct fdw_ctx {
     int no_fused_back = 0;   // experiments / tests: backward iterations as two launches (source step, receiver step) -- FDW_NO_FUSED_BACK=1
     int no_back_pipe = 0;    // experiments / tests: no wave-pipeline passes in the backward loop -- FDW_NO_BACK_PIPE=1
     int no_back_fused = 0;   // experiments / tests: the backward pipeline as two passes (source field, receiver field) instead of the fused kernel -- FDW_NO_BACK_FUSED=1
+    int no_born_fused = 0;   // benchmarks / tests: Born modelling as two step launches and a scatter kernel at orders <= 8 too -- FDW_NO_BORN_FUSED=1
+    float* d_born_m = nullptr;     // fdw_born_shot: the reflectivity embedded into a zeroed field; allocated on first use
+    float* d_born_rec0 = nullptr;  // ... the background gather [nt][nx] beside d_rec
+    size_t born_rec0_cap = 0;
+    float* d_born_w = nullptr;     // Born modelling without the fused kernel, FDW_BORN_DTT: (A - B) of the background on the interior cells
     size_t store_budget = 0; // fdw_rtm_stored_shot: bytes the stored source fields may take (0: whatever the device grants); fdw_set_store_budget
     int store_segments = 0;  // ... segments the last such shot was cut into (1: every field kept)
     size_t batch_budget = 0; // bytes a batch of shots may take (0: FDW_BATCH_BUDGET_BYTES, else 6 GiB); written by fdw_set_batch_budget alone
@@ -230,6 +236,7 @@ extern "C" int fdw_create_slab(const fdw_params* prm, const fdw_slab* slab, int 
     c->pitch = ((prm->nze + 63) / 64) * 64;  // 256-B aligned rows: every lane's float4 is aligned
     if (const char* nf = getenv("FDW_NO_FUSED_BACK")) c->no_fused_back = atoi(nf);
     if (const char* nf = getenv("FDW_NO_BACK_PIPE")) c->no_back_pipe = atoi(nf);
+    if (const char* nf = getenv("FDW_NO_BORN_FUSED")) c->no_born_fused = atoi(nf);
     if (const char* nf = getenv("FDW_NO_BACK_FUSED")) c->no_back_fused = atoi(nf);
     if (const char* pad = getenv("FDW_PITCH_PAD")) {   // experiment knob: extra floats per row (multiple of 4)
         const int extra = atoi(pad);
@@ -385,7 +392,8 @@ extern "C" void fdw_destroy(fdw_ctx* c)
     float* bufs[] = {c->d_taperz, c->d_txfac, c->d_gcx, c->d_gcz, c->fld[0], c->fld[1], c->fld[2], c->fld[3],
                      c->fld[4], c->fld[5], c->fld[6], c->fld[7], c->fld[8], c->fld[9], c->d_v2, c->d_img, c->d_illum, c->d_srce, c->d_dobs, c->d_rec,
                      c->d_vp, c->d_vpe, (float*)c->d_draws, (float*)c->d_jump, c->bfld[0], c->bfld[1], c->bfld[2], c->bfld[3],
-                     c->bfld[4], c->bfld[5], c->bfld[6], c->bfld[7], c->b_v2, c->b_img, c->b_dobs, c->b_illum, c->b_rec, c->b_wav, c->d_raw, c->d_wav, c->d_snap[0], c->d_snap[1], c->d_snap[2], c->d_amp, (float*)c->d_texc, c->d_exc, (float*)c->d_peak};
+                     c->bfld[4], c->bfld[5], c->bfld[6], c->bfld[7], c->b_v2, c->b_img, c->b_dobs, c->b_illum, c->b_rec, c->b_wav, c->d_raw, c->d_wav, c->d_snap[0], c->d_snap[1], c->d_snap[2], c->d_amp, (float*)c->d_texc, c->d_exc, (float*)c->d_peak,
+                     c->d_born_m, c->d_born_rec0, c->d_born_w};
     for (float* b : bufs)
         if (b) (void)hipFree(b);
     if (c->stream) (void)hipStreamDestroy(c->stream);
@@ -2070,6 +2078,132 @@ extern "C" int fdw_record_shot(fdw_ctx* c, const float* v2, int sx, int sz, int 
     if (!v2) return fail(FDW_EINVAL, "NULL argument");
     if (c) c->v2_resident = false;
     return record_impl(c, v2, sx, sz, gz, srce, data, P, PP, false);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Born modelling (definitions in fdwave.h)
+// ------------------------------------------------------------------------------------------------
+static bool born_fused(const fdw_ctx* c) { return c->h <= kMaxFastHalfOrder && !c->use_generic && !c->no_born_fused; }
+
+// the cell set C of the scatter on a full-grid context: rows [x0, x1), columns [z0, z1)
+struct BornCells {
+    int x0, x1, z0, z1;
+};
+static BornCells born_cells(const fdw_ctx* c)
+{
+    return BornCells{c->prm.nxb, std::min(c->prm.nxb + c->nx, c->xlim), c->prm.nzb, std::min(c->prm.nzb + c->nz, c->zlim)};
+}
+
+// what fdw_dev_born_steps and fdw_born_shot ask of their arguments beyond the pointers
+static int check_born_args(const fdw_ctx* c, const char* who, int kind, int sx, int sz, int gz)
+{
+    if (kind != FDW_BORN_FIELD && kind != FDW_BORN_DTT) return fail(FDW_EINVAL, "%s: kind=%d is neither FDW_BORN_FIELD nor FDW_BORN_DTT", who, kind);
+    if (sz < 0 || sz >= c->zlim) return fail(FDW_EINVAL, "%s: source depth %d outside the time-stepped columns [0,%d)", who, sz, c->zlim);
+    if (sx < 0 || sx >= c->upd_x1) return fail(FDW_EINVAL, "%s: source row %d outside the time-stepped rows [0,%d)", who, sx, c->upd_x1);
+    if (gz < 0 || gz >= c->zlim) return fail(FDW_EINVAL, "%s: receiver depth %d outside the time-stepped columns [0,%d)", who, gz, c->zlim);
+    return FDW_OK;
+}
+
+// One iteration in ONE launch of the register-ring family (FDW_MODE_BORN): the pairs as the swap left them, f the source's view at this
+// iteration, rec / rec0 this iteration's trace rows (either may be NULL).
+static int born_step_fused(fdw_ctx* c, const float* d_u_p, float* d_u_pp, const float* d_du_p, float* d_du_pp, const float* d_v2, const float* d_m, int kind,
+                           const FwdView& f, int gz, float* rec, float* rec0, int pp_twice, hipStream_t s)
+{
+    StepArgs a{};
+    fill_common(c, a, d_u_p, d_u_pp, d_v2, pp_twice);
+    a.psrc = d_du_p; a.fpp = d_du_pp;
+    a.img = const_cast<float*>(d_m);      // only read
+    a.r0 = 0;
+    a.r1 = std::min(c->nxl, c->upd_x1);
+    Injection in;
+    FDW_TRY(place_source(c, "fdw_dev_born_steps", false, f.samples, f.sx, f.sz, &in));
+    a.inj = f.samples + in.shift; a.inj_x = in.x; a.inj_z = f.sz; a.inj_n = in.n;
+    fill_rec(c, a, rec, gz);
+    a.texc = reinterpret_cast<int*>(rec0);      // the background's trace row travels where the excitation modes carry their map
+    const BornCells C = born_cells(c);
+    a.img_z1 = C.z1; a.exc_key = born_key(kind, C.z0);      // the rows of C: the receiver rows the launch covers
+    if (a.r1 <= a.r0) return FDW_OK;
+    fill_geometry(c, a, a.r1 - a.r0);
+    hipError_t e = launch_step_fast(a, c->h, FDW_MODE_BORN, effective_prefetch(c), s);
+    if (e != hipSuccess) return fail(FDW_EHIP, "kernel launch failed: %s", hipGetErrorString(e));
+    return FDW_OK;
+}
+
+// The loop of fdw_dev_born_steps behind its checks.  Without the fused kernel: the scattered pair's step, (A - B) of the background into
+// the scratch field (FDW_BORN_DTT: the background step overwrites B), the background step, the scatter kernel with the trace samples.
+static int born_loop(fdw_ctx* c, float* d_u_p, float* d_u_pp, float* d_du_p, float* d_du_pp, const float* d_v2, const float* d_m, int kind,
+                     const float* d_srce, int sx, int sz, int gz, float* d_rec, float* d_rec0, int it0, int nsteps, int first_pp_twice, hipStream_t s)
+{
+    const bool fused = born_fused(c);
+    if (!fused && kind == FDW_BORN_DTT && !c->d_born_w) {      // every word read is written first: no memset, nothing to wait for
+        hipError_t e = hipMalloc((void**)&c->d_born_w, field_elems(c) * sizeof(float));
+        if (e != hipSuccess) return fail(FDW_ENOMEM, "hipMalloc(%zu bytes) failed: %s", field_elems(c) * sizeof(float), hipGetErrorString(e));
+    }
+    if (d_rec) FDW_TRY(record_static(c, d_du_p, d_du_pp, gz, d_rec, it0, nsteps, s));
+    if (d_rec0) FDW_TRY(record_static(c, d_u_p, d_u_pp, gz, d_rec0, it0, nsteps, s));
+    const Forward src = point_source(d_srce, sx, sz);
+    const BornCells C = born_cells(c);
+    const size_t nx = (size_t)c->nx;
+    for (int k = 0; k < nsteps; k++) {
+        std::swap(d_u_p, d_u_pp);      // R:260-262, both pairs
+        std::swap(d_du_p, d_du_pp);
+        const int twice = (k > 0) || first_pp_twice;
+        const FwdView f = view_at(src, it0 + k, c->nx);
+        float* rec = d_rec ? d_rec + (size_t)(it0 + k) * nx : nullptr;
+        float* rec0 = d_rec0 ? d_rec0 + (size_t)(it0 + k) * nx : nullptr;
+        if (fused) {
+            FDW_TRY(born_step_fused(c, d_u_p, d_u_pp, d_du_p, d_du_pp, d_v2, d_m, kind, f, gz, rec, rec0, twice, s));
+            continue;
+        }
+        FDW_TRY(step_impl(c, FDW_MODE_FWD, d_du_p, d_du_pp, d_v2, 0, c->nxl, twice, view_at(point_source(nullptr, -1, sz), 0, c->nx), BackExtra{}, s));
+        hipError_t e = hipSuccess;
+        if (kind == FDW_BORN_DTT) e = launch_born_diff(d_u_p, d_u_pp, c->d_born_w, c->pitch, C.x0, C.x1, C.z0, C.z1, s);
+        if (e != hipSuccess) return fail(FDW_EHIP, "Born difference launch failed: %s", hipGetErrorString(e));
+        FDW_TRY(step_impl(c, FDW_MODE_FWD, d_u_p, d_u_pp, d_v2, 0, c->nxl, twice, f, BackExtra{}, s));
+        e = launch_born_scatter(d_u_pp, d_u_p, c->d_born_w, d_m, d_du_pp, kind, c->pitch, C.x0, C.x1, C.z0, C.z1, c->upd_z1, gz, rec, rec0, s);
+        if (e != hipSuccess) return fail(FDW_EHIP, "Born scatter launch failed: %s", hipGetErrorString(e));
+    }
+    return FDW_OK;
+}
+
+extern "C" int fdw_dev_born_steps(fdw_ctx* c, float* d_u_p, float* d_u_pp, float* d_du_p, float* d_du_pp, const float* d_v2, const float* d_m, int kind,
+                                  const float* d_srce, int sx, int sz, int gz, float* d_rec, float* d_rec0, int it0, int nsteps, int first_pp_twice,
+                                  void* stream)
+{
+    if (!c) return fail(FDW_EINVAL, "ctx is NULL");
+    FDW_TRY(check_single_shot_ctx(c, "Born modelling", "fdw_dev_born_steps"));
+    if (!d_u_p || !d_u_pp || !d_du_p || !d_du_pp || !d_v2 || !d_m || !d_srce) return fail(FDW_EINVAL, "fdw_dev_born_steps: NULL argument");
+    if (it0 < 0 || nsteps < 0) return fail(FDW_EINVAL, "fdw_dev_born_steps: it0=%d nsteps=%d", it0, nsteps);
+    FDW_TRY(check_born_args(c, "fdw_dev_born_steps", kind, sx, sz, gz));
+    return born_loop(c, d_u_p, d_u_pp, d_du_p, d_du_pp, d_v2, d_m, kind, d_srce, sx, sz, gz, d_rec, d_rec0, it0, nsteps, first_pp_twice,
+                     pick_stream(c, stream));
+}
+
+extern "C" int fdw_born_shot(fdw_ctx* c, const float* v2, const float* m, int kind, int sx, int sz, int gz, const float* srce, float* data, float* data0)
+{
+    if (!c) return fail(FDW_EINVAL, "ctx is NULL");
+    FDW_TRY(check_single_shot_ctx(c, "Born modelling", "fdw_born_shot"));
+    if (!m || !srce || !data) return fail(FDW_EINVAL, "fdw_born_shot: NULL argument");
+    FDW_TRY(has_model(c, v2));
+    FDW_TRY(check_born_args(c, "fdw_born_shot", kind, sx, sz, gz));
+    if (c->nx <= 0 || c->nz <= 0) return fail(FDW_EINVAL, "fdw_born_shot: no interior");
+    HIP_TRY(hipSetDevice(c->device));
+    const int nt = c->prm.nt;
+    FDW_TRY(ensure_work_buffers(c, 4, false));
+    FDW_TRY(alloc_zero(&c->d_born_m, field_elems(c)));
+    FDW_TRY(ensure_cap(&c->d_rec, &c->rec_cap, (size_t)c->nx * nt));
+    if (data0) FDW_TRY(ensure_cap(&c->d_born_rec0, &c->born_rec0_cap, (size_t)c->nx * nt));
+    FDW_TRY(zero_fields(c, c->fld, 4));
+    end_residency(c, v2);
+    if (v2) FDW_TRY(upload_rows(c, c->d_v2, v2, c->stream));
+    FDW_TRY(upload_source(c, srce, nt));
+    FDW_TRY(image_to_device(c, m, c->d_born_m));
+    FDW_TRY(born_loop(c, c->fld[0], c->fld[1], c->fld[2], c->fld[3], c->d_v2, c->d_born_m, kind, c->d_srce, sx, sz, gz, c->d_rec,
+                      data0 ? c->d_born_rec0 : nullptr, 0, nt, 0, c->stream));
+    FDW_TRY(gathers_to_host(c, c->d_rec, 1, data));
+    if (data0) FDW_TRY(gathers_to_host(c, c->d_born_rec0, 1, data0));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return FDW_OK;
 }
 
 // ---- shots driven by a line source (definitions in fdwave.h) ----

@@ -6,6 +6,7 @@
 //   FDW_TU 1 (fdw_step1_dd.o)    the dialects of the CPU-serial sibling (MOD, DD_FWD, DD_RECV)
 //   FDW_TU 2 (fdw_step1_fast.o)  the RTM dialect with FAST numerics (fdw_device.h)
 #include "fdw_device.h"
+#include "fdw_born.h"
 
 #pragma clang fp contract(off)
 
@@ -33,6 +34,10 @@ namespace fdw {
 //           2  the excitation pick: where texc == a.exc_key (= top - it), exc = the new field; texc is only read, the exc row (a.img) is
 //              stored back whole, unpicked words with the bits they came with (fdw_step_line_pick_kernel)
 //           Compares and selects only: texc travels as 32-bit words in float registers and meets no arithmetic.
+//   BORN    Born modelling (fdwave.h, "Born modelling"; fdw_step_born_kernel): the second register ring of BACK carries the SCATTERED field
+//           (sv.psrc = du_p read only, sv.fpp = du_pp overwritten), which gets the damping and no injection; the row of the reflectivity m
+//           (a.img, only read) rides the pointwise queue; on the interior cells du_new = du_new (+) m (*) q, with q the background's new
+//           value (kind 0, fdw_born.h) or its second time difference (1) from the registers the leap-frog just used; then the trace samples
 // block = 256 threads = 4 independent waves (no LDS, no barrier).
 //
 // ONE code path for every tile.  Every global load of the march is unconditional (addresses are
@@ -58,7 +63,7 @@ struct ShotView {
 };
 
 template <int H, bool TAPER, int INJ, bool IMG, bool LAPONLY, int PF, bool DD = false, bool BACK = false, int NUM = 0, bool REC = false, bool ILL = false,
-          int EXC = 0>
+          int EXC = 0, bool BORN = false>
 __device__ __forceinline__ void march(const StepArgs& a, const ShotView& sv, const int lane, const int zs, const int xa, const int xe)
 {
     // BACK: one whole backward iteration of fd_back (R:317-329) in a single pass: the source field is reconstructed in a second
@@ -92,10 +97,13 @@ __device__ __forceinline__ void march(const StepArgs& a, const ShotView& sv, con
     const CoefPairs<H> cpk = coef_pairs<H>(a.cx, a.cz);
     const v2f c0p = v2f{a.c0, a.c0};                          // FAST numerics: weight of the centre point
     // REC: the lane whose float4 holds column rec_z records element rec_z & 3 of its new row (strips do not overlap: one lane in the grid)
-    const bool rec_lane = REC && (z0 >> 2) == (a.rec_z >> 2);
+    const bool rec_lane = (REC || BORN) && (z0 >> 2) == (a.rec_z >> 2);
+    constexpr bool TWO = BACK || BORN;                      // a second field is stepped side by side in a ring of its own
+    const bool born_here = BORN && (zs < a.img_z1) && (zs + 256 > born_key_z0(a.exc_key));      // wave-uniform: the strip holds interior columns
 
     // per-lane column masks and damping factors
     bool mlap[4], mupd[4], znc[4], znh[4], ihit[4];
+    [[maybe_unused]] bool mborn[4];                         // BORN: the interior columns (the scatter's)
     float tzc[4], tzh[4];
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
@@ -103,6 +111,7 @@ __device__ __forceinline__ void march(const StepArgs& a, const ShotView& sv, con
         mlap[e] = (z >= a.lap_z0) && (z < a.lap_z1);
         mupd[e] = z < a.upd_z1;
         ihit[e] = (z == a.inj_z);
+        if constexpr (BORN) mborn[e] = (z >= born_key_z0(a.exc_key)) && (z < a.img_z1);
         znc[e] = znh[e] = false;
         tzc[e] = tzh[e] = 1.0f;
     }
@@ -147,19 +156,20 @@ __device__ __forceinline__ void march(const StepArgs& a, const ShotView& sv, con
     f4 qtx[EXC ? PF : 1];                                   // EXC: the texc row, as words
     [[maybe_unused]] float* texc_w = nullptr;               // EXC: the time map of this block's shot (a batch: a.texc + shot * a.bstride)
     if constexpr (EXC != 0) texc_w = reinterpret_cast<float*>(a.texc) + (long long)blockIdx.y * a.bstride;
-    f4 fring[BACK ? R : 1], fqhal[BACK ? PF : 1], fqpp[BACK ? PF : 1];      // the source field's ring and pointwise queues
+    f4 fring[TWO ? R : 1], fqhal[TWO ? PF : 1], fqpp[TWO ? PF : 1];      // the source field's (BORN: the scattered field's) ring and pointwise queues
+    f4 qm[BORN ? PF : 1];                                   // BORN: the reflectivity row
     constexpr int NV = LOOK > PF ? LOOK : PF;
     static_for<2 * H>([&](auto K) {
         constexpr int k = decltype(K)::value;
         ring[k] = load_p(xa - H + k);
-        if constexpr (BACK) fring[k] = load_f(xa - H + k);
+        if constexpr (TWO) fring[k] = load_f(xa - H + k);
         __builtin_amdgcn_sched_barrier(0);
     });
     static_for<NV>([&](auto JJ) {
         constexpr int j = decltype(JJ)::value - NV;   // virtual step -NV .. -1
         if constexpr (j >= -LOOK) {
             ring[j + 2 * H + LOOK] = load_p(xa + j + H + LOOK);
-            if constexpr (BACK) fring[j + 2 * H + LOOK] = load_f(xa + j + H + LOOK);
+            if constexpr (TWO) fring[j + 2 * H + LOOK] = load_f(xa + j + H + LOOK);
         }
         if constexpr (j >= -PF) {
             constexpr int m = j + PF;
@@ -178,10 +188,11 @@ __device__ __forceinline__ void march(const StepArgs& a, const ShotView& sv, con
                 qim[m] = load_plain(sv.img, row);
                 qtx[m] = load_plain(texc_w, row);
             }
-            if constexpr (BACK) {
+            if constexpr (TWO) {
                 fqhal[m] = load_fhalo(row);
                 fqpp[m] = load_plain(sv.fpp, row);
             }
+            if constexpr (BORN) qm[m] = load_plain(sv.img, row);
         }
         __builtin_amdgcn_sched_barrier(0);
     });
@@ -189,6 +200,7 @@ __device__ __forceinline__ void march(const StepArgs& a, const ShotView& sv, con
         static_for<2 * H>([&](auto K) {
             constexpr int k = decltype(K)::value;
             taper_row(ring[k], tzc, znc, xa - H + k);
+            if constexpr (BORN) taper_row(fring[k], tzc, znc, xa - H + k);
         });
     }
 
@@ -321,10 +333,19 @@ __device__ __forceinline__ void march(const StepArgs& a, const ShotView& sv, con
                 }
             }
             f4 fres;
-            if constexpr (BACK) {
+            if constexpr (TWO) {
                 // ---- the source field's own step on the same row: kernel_lap + kernel_time, no damping, no injection (R:317-318) ----
+                // BORN: the scattered field's, with the damping of the forward step (what enters the computation this step) and no injection
+                f4 fhal = fqhal[Q];
+                if constexpr (BORN) {
+                    if (wave_tap) {
+                        taper_row(fring[(U + 2 * H) % R], tzc, znc, r + H);
+                        taper_row(fhal, tzh, znh, r);
+                        taper_row(fqpp[Q], tzc, znc, r);
+                        if (a.pp_twice) taper_row(fqpp[Q], tzc, znc, r);
+                    }
+                }
                 const f4 fc = fring[(U + H) % R];
-                const f4 fhal = fqhal[Q];
                 f4 flft, frgt;
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
@@ -346,6 +367,19 @@ __device__ __forceinline__ void march(const StepArgs& a, const ShotView& sv, con
                     }
                 });
             }
+            if constexpr (BORN) {
+                // ---- the scatter on the interior cells: no cell of them is damped (z >= nzb >= ztap), so c and ppt are the words the two
+                // background buffers held; product and sum rounded separately; every other cell keeps its word (a select, no + 0.0f) ----
+                if (born_here && (unsigned)(r - a.rec_x0) < (unsigned)a.rec_n) {
+                    const bool born_kind = born_key_kind(a.exc_key) != 0;
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        const float q = born_kind ? (res.v[e] - c.v[e]) - (c.v[e] - ppt.v[e]) : res.v[e];
+                        const float sc = fres.v[e] + qm[Q].v[e] * q;
+                        fres.v[e] = mborn[e] ? sc : fres.v[e];
+                    }
+                }
+            }
             if constexpr (IMG) {
                 // kernel_img (R:133-144) correlates with the NEW receiver field; the sibling's rtm_main stores the CURRENT one
                 // (rwf[it] = P, rtm_main.cpp:211-215), an interior point of which carries damping factors of exactly 1.0f
@@ -362,14 +396,18 @@ __device__ __forceinline__ void march(const StepArgs& a, const ShotView& sv, con
                 if constexpr (ILL) f4_store(sv.img + (size_t)r * pitch, voff, imr);
                 if constexpr (EXC != 0) f4_store(sv.img + (size_t)r * pitch, voff, imr);
                 if constexpr (EXC == 1) f4_store(texc_w + (size_t)r * pitch, voff, txr);
-                if constexpr (BACK) f4_store(sv.fpp + (size_t)r * pitch, voff, fres);
+                if constexpr (TWO) f4_store(sv.fpp + (size_t)r * pitch, voff, fres);
             } else if (act) {
                 f4_store(sv.out + (size_t)r * pitch, voff, res);
                 if constexpr (IMG) f4_store(sv.img + (size_t)r * pitch, voff, imr);
                 if constexpr (ILL) f4_store(sv.img + (size_t)r * pitch, voff, imr);
                 if constexpr (EXC != 0) f4_store(sv.img + (size_t)r * pitch, voff, imr);
                 if constexpr (EXC == 1) f4_store(texc_w + (size_t)r * pitch, voff, txr);
-                if constexpr (BACK) f4_store(sv.fpp + (size_t)r * pitch, voff, fres);
+                if constexpr (TWO) f4_store(sv.fpp + (size_t)r * pitch, voff, fres);
+            }
+            if constexpr (BORN) {      // the trace samples of both new fields (either gather may be absent: wave-uniform)
+                if (a.rec) f1_store_arr(array_rsrc(a.rec, (unsigned)a.rec_n * 4u), rec_offset(rec_lane, r, a.rec_x0, a.rec_n), f4_pick(fres, a.rec_z & 3));
+                if (a.texc) f1_store_arr(array_rsrc(reinterpret_cast<const float*>(a.texc), (unsigned)a.rec_n * 4u), rec_offset(rec_lane, r, a.rec_x0, a.rec_n), f4_pick(res, a.rec_z & 3));
             }
             if constexpr (REC) f1_store_arr(array_rsrc(sv.rec, (unsigned)a.rec_n * 4u), rec_offset(rec_lane, r, a.rec_x0, a.rec_n), f4_pick(res, a.rec_z & 3));
 
@@ -391,12 +429,13 @@ __device__ __forceinline__ void march(const StepArgs& a, const ShotView& sv, con
                     qim[Q] = load_plain(sv.img, nr);
                     qtx[Q] = load_plain(texc_w, nr);
                 }
-                if constexpr (BACK) {
+                if constexpr (TWO) {
                     fqhal[Q] = load_fhalo(nr);
                     fqpp[Q] = load_plain(sv.fpp, nr);
                 }
+                if constexpr (BORN) qm[Q] = load_plain(sv.img, nr);
             }
-            if constexpr (BACK) fring[U] = load_f(r - H + R);
+            if constexpr (TWO) fring[U] = load_f(r - H + R);
         }
         // keep the look-ahead loads where they were issued: without this the machine scheduler
         // sinks each load to one row before its first use to save registers, which turns the
@@ -511,6 +550,17 @@ __global__ __launch_bounds__(256) void fdw_step_line_pick_kernel(const StepArgs 
     march<H, true, 2, false, false, PF, false, false, NUM, false, false, 2>(a, sv, lane, zs, xa, xe);
 }
 
+// Born modelling (FDW_MODE_BORN, fdw_dev_born_steps): the forward step on the background pair, the same step without a source on the scattered
+// pair in a second register ring, v2 read once for both, and the scatter and the trace samples in registers before the two stores.  Six reads
+// (p, pp, du_p, du_pp, v2, m) and two writes: 36 B/point/step against the 32 of two plain steps.  The kind is a launch argument (fdw_born.h): the second
+// difference costs three subtractions on registers the leap-frog already holds.
+template <int H, int PF, int NUM>
+__global__ __launch_bounds__(256) void fdw_step_born_kernel(const StepArgs a)
+{
+    FDW_STEP_TILE(a, sv, lane, zs, xa, xe)
+    march<H, true, 1, false, false, PF, false, false, NUM, false, false, 0, true>(a, sv, lane, zs, xa, xe);
+}
+
 #if FDW_TU == 0
 // ------------------------------------------------------------------------------------------------
 // generic-order kernel: any even order up to FDW_MAX_ORDER, one thread per point, every tap from
@@ -616,6 +666,40 @@ __global__ __launch_bounds__(256) void fdw_exc_pick_kernel(const float* f, const
     if (z >= z1) return;
     const size_t k = (size_t)(r0 + blockIdx.y) * pitch + z;
     if (texc[k] == key) reinterpret_cast<unsigned*>(exc)[k] = reinterpret_cast<const unsigned*>(f)[k];
+}
+
+// Born modelling behind step kernels that do not scatter themselves (orders above 8, forced generic, FDW_NO_BORN_FUSED=1).  The background
+// step overwrites B (the older level) with U, so the second difference needs (A - B) kept: w = a (-) b on the interior cells, before that step.
+__global__ __launch_bounds__(256) void fdw_born_diff_kernel(const float* a, const float* b, float* w, int pitch, int x0, int z0, int z1)
+{
+    const int z = z0 + blockIdx.x * 256 + threadIdx.x;
+    if (z >= z1) return;
+    const size_t k = (size_t)(x0 + blockIdx.y) * pitch + z;
+    w[k] = a[k] - b[k];
+}
+
+// ... and after both steps: d = d (+) m (*) q on the interior cells [z0, z1) of rows x0 + blockIdx.y, q = u (kind 0) or (u (-) a) (-) w (kind 1),
+// product and sum rounded separately, every other cell left alone; then this step's trace samples of the row at column gz (rec: the scattered
+// field after the scatter, rec0: the background; either may be NULL).  Threads cover columns [0, zcols) because gz may lie outside [z0, z1).
+__global__ __launch_bounds__(256) void fdw_born_scatter_kernel(const float* u, const float* a, const float* w, const float* m, float* d, int kind, int pitch,
+                                                               int x0, int z0, int z1, int zcols, int gz, float* rec, float* rec0)
+{
+    const int z = blockIdx.x * 256 + threadIdx.x;
+    if (z >= zcols) return;
+    const size_t k = (size_t)(x0 + blockIdx.y) * pitch + z;
+    const bool in = (z >= z0) && (z < z1);
+    if (!in && z != gz) return;
+    const float uv = u[k];
+    float dv = d[k];
+    if (in) {
+        const float q = kind ? (uv - a[k]) - w[k] : uv;
+        dv = dv + m[k] * q;
+        d[k] = dv;
+    }
+    if (z == gz) {
+        if (rec) rec[blockIdx.y] = dv;
+        if (rec0) rec0[blockIdx.y] = uv;
+    }
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -737,6 +821,7 @@ static hipError_t launch_rtm_hp(const StepArgs& a, int mode, hipStream_t s)
     case FDW_MODE_FWD_LINE_REC_ILLUM: hipLaunchKernelGGL((fdw_step_line_rec_illum_kernel<H, PF, NUM>), grid, block, 0, s, a); break;
     case FDW_MODE_FWD_EXC: hipLaunchKernelGGL((fdw_step_exc_kernel<H, PF, NUM>), grid, block, 0, s, a); break;
     case FDW_MODE_FWD_LINE_PICK: hipLaunchKernelGGL((fdw_step_line_pick_kernel<H, PF, NUM>), grid, block, 0, s, a); break;
+    case FDW_MODE_BORN: hipLaunchKernelGGL((fdw_step_born_kernel<H, PF, NUM>), grid, block, 0, s, a); break;
     default: return hipErrorInvalidValue;
     }
     return hipGetLastError();
@@ -855,6 +940,22 @@ hipError_t launch_exc_pick(const float* f, const int* texc, float* exc, int pitc
     const int zc = z1 < pitch ? z1 : pitch;
     if (r1 <= r0 || zc <= 0) return hipSuccess;
     hipLaunchKernelGGL(fdw_exc_pick_kernel, dim3((zc + 255) / 256, r1 - r0), dim3(256), 0, s, f, texc, exc, pitch, r0, zc, key);
+    return hipGetLastError();
+}
+
+hipError_t launch_born_diff(const float* a, const float* b, float* w, int pitch, int x0, int x1, int z0, int z1, hipStream_t s)
+{
+    if (x1 <= x0 || z1 <= z0) return hipSuccess;
+    hipLaunchKernelGGL(fdw_born_diff_kernel, dim3((z1 - z0 + 255) / 256, x1 - x0), dim3(256), 0, s, a, b, w, pitch, x0, z0, z1);
+    return hipGetLastError();
+}
+
+hipError_t launch_born_scatter(const float* u, const float* a, const float* w, const float* m, float* d, int kind, int pitch, int x0, int x1, int z0,
+                               int z1, int zcols, int gz, float* rec, float* rec0, hipStream_t s)
+{
+    if (x1 <= x0 || zcols <= 0) return hipSuccess;
+    hipLaunchKernelGGL(fdw_born_scatter_kernel, dim3((zcols + 255) / 256, x1 - x0), dim3(256), 0, s, u, a, w, m, d, kind, pitch, x0, z0, z1, zcols, gz, rec,
+                       rec0);
     return hipGetLastError();
 }
 

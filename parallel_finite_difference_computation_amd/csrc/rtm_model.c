@@ -14,7 +14,13 @@
  * gathers of its shots at their offsets in the temporary file.  `slabs=N` (FDW_SLABS=N) models
  * every shot on N GPUs through fdw_slabs_record_shot, one host thread per rank (FDW_SLABS_LOCAL=1: all ranks on GPU 0); the ranks share
  * one host-built model per shot (the border drawn by the host's extendvel_linear in shot order, the same values the device draws), each
- * writes its own receiver rows of the shot's gather.  In every mode the datfile is byte for byte the one-GPU program's. */
+ * writes its own receiver rows of the shot's gather.  In every mode the datfile is byte for byte the one-GPU program's.
+ *
+ * Born modelling (fdwave.h, "Born modelling"): with `bornfile=<path>` (fp32 [nx][nz] reflectivity; `born_kind=0|1`, default 1 = the second
+ * time difference) the datfile holds the SCATTERED gathers [ns][nx][nt] of fdw_born_shot in the models and border draws the program uses
+ * without the key, shot by shot on one GPU; `born_bg=<path>` also writes the background gathers, which are the plain program's datfile.
+ * bornfile together with slabs / gpus (deck key or environment), a born_kind outside {0, 1} and a short or missing reflectivity file are
+ * refused before any file, thread or device is touched. */
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -208,6 +214,32 @@ int main(int argc, char **argv)
         fprintf(stderr, "slabs / gpus: at most 64\n");
         return EXIT_FAILURE;
     }
+    /* Born modelling: one GPU, shot by shot; everything that cannot run is refused here */
+    const char *bornfile = fdw_deck_str(deck, "bornfile"), *born_bg = fdw_deck_str(deck, "born_bg");
+    int born_kind = fdw_deck_int(deck, "born_kind");
+    if (born_kind == -1) born_kind = FDW_BORN_DTT;
+    if (!bornfile && born_bg) {
+        fprintf(stderr, "born_bg needs bornfile\n");
+        return EXIT_FAILURE;
+    }
+    if (bornfile) {
+        if (slabs > 1 || gpus > 1) {
+            fprintf(stderr, "bornfile: Born modelling runs on one GPU, shot by shot: %s is refused\n", slabs > 1 ? "slabs" : "gpus");
+            return EXIT_FAILURE;
+        }
+        if (born_kind != FDW_BORN_FIELD && born_kind != FDW_BORN_DTT) {
+            fprintf(stderr, "bornfile: born_kind = %d is neither 0 (the field) nor 1 (its second time difference)\n", born_kind);
+            return EXIT_FAILURE;
+        }
+        FILE *bf = fopen(bornfile, "rb");
+        long have = -1;
+        if (bf && fseek(bf, 0, SEEK_END) == 0) have = ftell(bf);
+        if (bf) fclose(bf);
+        if (have < 0 || (size_t)have < (size_t)nx * (size_t)nz * sizeof(float)) {
+            fprintf(stderr, "bornfile '%s' is missing or holds fewer than nx * nz = %zu floats\n", bornfile, (size_t)nx * (size_t)nz);
+            return EXIT_FAILURE;
+        }
+    }
     const int slabs_local = getenv("FDW_SLABS_LOCAL") != NULL;
     if (slabs > 1) {
         const int ndev = fdw_device_count();
@@ -326,6 +358,62 @@ int main(int argc, char **argv)
             if (sj.failed) ok = 0;
         }
         free(v2); free(data);
+    } else if (bornfile) {
+        /* ---- Born modelling: one GPU, one shot after the other, each in the model the plain program gives it ---- */
+        fdw_ctx *ctx = NULL;
+        float *m = read_floats(bornfile, ni, "bornfile");
+        float *data = (float *)malloc(ng * sizeof(float)), *data0 = born_bg ? (float *)malloc(ng * sizeof(float)) : NULL;
+        float *v2 = dev_border ? NULL : (float *)malloc(ne * sizeof(float));
+        char *tmpbg = born_bg ? (char *)malloc(strlen(born_bg) + 16) : NULL;
+        FILE *bg = NULL;
+        if (!m || !data || (born_bg && (!data0 || !tmpbg)) || (!dev_border && !v2)) {
+            fprintf(stderr, "out of host memory\n");
+            ok = 0;
+        }
+        if (ok && born_bg) {
+            sprintf(tmpbg, "%s.XXXXXX", born_bg);
+            const int fdb = mkstemp(tmpbg);
+            bg = fdb >= 0 ? fdopen(fdb, "wb") : NULL;
+            if (!bg) {
+                fprintf(stderr, "cannot create a temporary file beside '%s'\n", born_bg);
+                ok = 0;
+            }
+        }
+        if (ok && fdw_create(&prm, 0, &ctx) != FDW_OK) {
+            fprintf(stderr, "fdw_create: %s\n", fdw_last_error());
+            ok = 0;
+        }
+        if (ok && dev_border && fdw_model_resident(ctx, vp) != FDW_OK) {
+            fprintf(stderr, "fdw_model_resident: %s\n", fdw_last_error());
+            ok = 0;
+        }
+        for (int is = 0; is < ns && ok; is++) {
+            if (dev_border) {
+                if (fdw_dev_extendvel_linear(ctx, (unsigned long long)is * draws, NULL) != FDW_OK) ok = 0;
+            } else {
+                HOST_MODEL(is, v2);
+            }
+            if (!ok || fdw_born_shot(ctx, dev_border ? NULL : v2, m, born_kind, sx0 + is * ds, sz, gz, srce, data, data0) != FDW_OK) {
+                fprintf(stderr, "shot %d: %s\n", is, fdw_last_error());
+                ok = 0;
+                break;
+            }
+            if (fwrite(data, sizeof(float), ng, out) != ng || (bg && fwrite(data0, sizeof(float), ng, bg) != ng)) {
+                fprintf(stderr, "write failed\n");
+                ok = 0;
+                break;
+            }
+            printf("** shot %d, source at (%d,%d): %d receivers at depth %d, %d samples (scattered field, kind %d)\n", is + 1, fsx + is * ds, sz - nzb, nx,
+                   gz - nzb, nt, born_kind);
+        }
+        if (ctx) fdw_destroy(ctx);
+        if (bg && fclose(bg) != 0) ok = 0;
+        if (bg && ok && rename(tmpbg, born_bg) != 0) {
+            fprintf(stderr, "cannot rename '%s' to '%s'\n", tmpbg, born_bg);
+            ok = 0;
+        }
+        if (bg && !ok) unlink(tmpbg);
+        free(m); free(data); free(data0); free(v2); free(tmpbg);
     } else if (nworkers > 1) {
         /* ---- whole shots dealt to worker threads / GPUs ---- */
         model_job job;
