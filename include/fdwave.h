@@ -323,6 +323,9 @@ int fdw_download_field(fdw_ctx *ctx, float *h_dst, const float *d_src);
  * the eleven fields fdw_shot_batch_max counts and cut a batch that exceeds the budget into parts themselves.  fdw_shot_batch,
  * fdw_record_shot_batch, fdw_record_shot_line_batch and fdw_model_shot_batch have NO part loop: they take `nshots` whole, whatever the
  * budget says (fdw_batch_parts 1 or 0); their callers walk the shots in groups of at most fdw_shot_batch_max.
+ * fdw_born_shot_batch and fdw_born_shot_line_batch split too: per shot they hold the eleven fields and 1 + [data0 != NULL] + [line]
+ * gathers [nt][nx] (the scattered traces, the background traces, the line gathers); see "Born modelling driven by a line source, and
+ * batches of Born shots".
  */
 long long fdw_border_draws(int nx, int nz, int nxb, int nzb);
 int fdw_shot_batch(fdw_ctx *ctx, int nshots, const float *v2_all, unsigned long long draw_offset, int sx0, int dsx, int sz, int gz,
@@ -795,13 +798,62 @@ int fdw_shot_excitation_batch(fdw_ctx *ctx, int nshots, const float *v2_all, uns
  * fdw_born_shot       one shot from rest for the context's nt: m [nx][nz] is embedded into a zeroed field, the gathers are recorded on the
  *                     device and downloaded transposed to [nx][nt] as fdw_record_shot does (data: scattered; data0, may be NULL: background).
  *                     v2 NULL: the resident model (FDW_ESTATE without one).  Work arrays are allocated on first use, freed by fdw_destroy.
- * Out of scope: Born kernels in the two-step and four-step families, batches of Born shots, line-source Born, slabs and several GPUs, the
- * DTT-adjoint imaging condition. */
+ * Out of scope: Born kernels in the two-step and four-step families, slabs and several GPUs, the DTT-adjoint imaging condition. */
 enum { FDW_BORN_FIELD = 0, FDW_BORN_DTT = 1 };
 int fdw_dev_born_steps(fdw_ctx *ctx, float *d_u_p, float *d_u_pp, float *d_du_p, float *d_du_pp, const float *d_v2, const float *d_m, int kind,
                        const float *d_srce, int sx, int sz, int gz, float *d_rec, float *d_rec0, int it0, int nsteps, int first_pp_twice, void *stream);
 int fdw_born_shot(fdw_ctx *ctx, const float *v2 /* NULL: the resident model */, const float *m /* [nx][nz] */, int kind, int sx, int sz, int gz,
                   const float *srce, float *data /* [nx][nt] scattered */, float *data0 /* NULL ok: [nx][nt] background */);
+
+/* ---- Born modelling driven by a line source, and batches of Born shots -------------------------------------------------------------------
+ * The two further forms every migration path here has: a line source (the forward operator of plane-wave and encoded-shot least-squares
+ * migration, whose gradient is fdw_shot_line_residual) and batches of small shots through one launch per time step.  Same dialect, contexts
+ * and numerics as above; C, the kinds and the rounding as defined above.
+ *
+ * Line source.  Iteration it of fdw_dev_born_steps with step 1 replaced by the line-source iteration of fdw_dev_line_steps: after the
+ * leap-frog, for ix < nsrc = min(nx, xlim - nxb): U[nxb+ix][sz] = U[nxb+ix][sz] (+) w[it][ix] (d_wav [>= it0+nsteps][nx]; samples of rows
+ * ix >= nsrc are ignored).  Steps 2-4 are unchanged: the scattered pair takes no injection.  U, line samples included, is what q and d_rec0
+ * see; A and B are the entry words of the background buffers.
+ * Consequences: the background pair and d_rec0 equal fdw_dev_line_steps with d_rec, bit for bit; fdw_born_shot_line's data0 equals
+ * fdw_record_shot_line; an all-zero m from rest gives all-zero words.
+ * fdw_dev_born_line_steps  the loop on device arrays, on the given stream (NULL: the context's), nothing synchronised.  FDW_EINVAL before
+ *                     anything is enqueued: sz or gz outside [0, zlim), a NULL required pointer (the four fields, d_v2, d_m, d_wav), it0 < 0,
+ *                     nsteps < 0, kind outside {0, 1}.  FDW_ESTATE: slab contexts, the sibling's dialects, a context inside a batch.
+ *   Kernels: fdw_step_line_born_kernel, the fused kernel above with the line injection of fdw_step_line_kernel (one sample load per row
+ *   more), instantiated wherever fdw_step_born_kernel is; no scratch (DESIGN.md section 6u has the registers).  Orders above 8, the forced
+ *   generic kernel and FDW_NO_BORN_FUSED=1 run the existing steps with the line source on the background pair and the scatter kernel.
+ * fdw_born_shot_line  fdw_born_shot with the gather wav [nx][nt] (uploaded and transposed as fdw_record_shot_line does) in place of the
+ *                     wavelet and its source row.
+ *
+ * Batches.  Shot b of fdw_born_shot_batch is fdw_born_shot with source row sx0 + b dsx, shot b of fdw_born_shot_line_batch is
+ * fdw_born_shot_line with wav_all[b]; the model is v2_all[b] or, with v2_all == NULL, the border model of draws draw_offset + b T on the
+ * resident model: shots and models as fdw_shot_batch takes them.  ONE reflectivity m [nx][nz] for all shots.  data (and data0, may be NULL)
+ * [nshots][nx][nt].  Every output equals the single-shot calls bit for bit; data0 equals fdw_record_shot_batch / fdw_record_shot_line_batch.
+ * Where fdw_record_shot_batch batches and the fused Born kernel runs, the whole batch is one launch per time step (gridDim.y = nshots);
+ * elsewhere (orders above 8, forced generic, FDW_NO_BORN_FUSED=1, static receiver rows, the two-step and pipeline regimes), and without
+ * room on the device, the shots run one by one through the single-shot code and produce the same bytes.
+ * Who splits.  Both calls work in fdw_shot_batch's batch buffers (of its eleven fields per shot they use two pairs and v2; its gather buffer
+ * takes the scattered traces), plus a background-gather buffer of their own when data0 is asked for, plus the line gathers of a line batch;
+ * one device copy of m.  The per-shot share is therefore 11 fields + (1 + [data0 != NULL] + [line]) gathers [nt][nx], and a batch over the
+ * budget (fdw_set_batch_budget) is cut into parts of what that share allows by the call itself: the shots are independent, nothing is
+ * carried between parts.  Under a budget below one shot's share the shots run one by one.  fdw_batch_parts: 0 / 1 / k as for the other
+ * batched calls.
+ * Refusals, before anything is enqueued: those of fdw_born_shot (for the line form: of fdw_born_shot_line) plus nshots < 1 and source rows
+ * outside the time-stepped rows (FDW_EINVAL); no model -- v2_all == NULL without fdw_model_resident -- is FDW_ESTATE.
+ * Measured on one MI355X (profiles/born_batch.json; 415 x 295 interior, nt 1700, order 8, FDW_BORN_DTT, 32 shots, ms
+ * per shot): fdw_born_shot_batch 2.857 against fdw_born_shot one by one on the parent's build 12.477 (4.37 x; FAST 2.667 / 11.426, 4.28 x);
+ * the yardstick in the same run, fdw_record_shot_batch 1.410 against fdw_record_shot one by one 8.405 (5.96 x; FAST 1.345 / 8.358, 6.21 x).
+ * The line loop against the parent's point-source loop, us per step: 8192^2 418.70 / 418.21 (windows spread 2.07), 2048^2 33.71 / 34.51
+ * (spread 0.26). */
+int fdw_dev_born_line_steps(fdw_ctx *ctx, float *d_u_p, float *d_u_pp, float *d_du_p, float *d_du_pp, const float *d_v2, const float *d_m, int kind,
+                            const float *d_wav /* [>= it0+nsteps][nx] */, int sz, int gz, float *d_rec, float *d_rec0, int it0, int nsteps,
+                            int first_pp_twice, void *stream);
+int fdw_born_shot_line(fdw_ctx *ctx, const float *v2 /* NULL: resident */, const float *m, int kind, int sz, int gz, const float *wav /* [nx][nt] */,
+                       float *data, float *data0 /* NULL ok */);
+int fdw_born_shot_batch(fdw_ctx *ctx, int nshots, const float *v2_all, unsigned long long draw_offset, const float *m /* [nx][nz], ONE for all shots */,
+                        int kind, int sx0, int dsx, int sz, int gz, const float *srce, float *data /* [nshots][nx][nt] */, float *data0 /* NULL ok */);
+int fdw_born_shot_line_batch(fdw_ctx *ctx, int nshots, const float *v2_all, unsigned long long draw_offset, const float *m, int kind, int sz, int gz,
+                             const float *wav_all /* [nshots][nx][nt] */, float *data, float *data0);
 
 /* ---- tuning / introspection --------------------------------------------------------------------
  * fdw_set_tuning  xchunk = rows marched per wave (0 = auto), wz = waves of a block laid along z

@@ -163,6 +163,10 @@ SIGNATURES = [
     ("fdw_shot_excitation_batch", C.c_int, [vp, C.c_int, vp, C.c_ulonglong, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_float, vp, vp, vp, vp, vp]),
     ("fdw_dev_born_steps", C.c_int, [vp, vp, vp, vp, vp, vp, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, vp]),
     ("fdw_born_shot", C.c_int, [vp, vp, f32p, C.c_int, C.c_int, C.c_int, C.c_int, f32p, f32p, vp]),
+    ("fdw_dev_born_line_steps", C.c_int, [vp, vp, vp, vp, vp, vp, vp, C.c_int, vp, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, vp]),
+    ("fdw_born_shot_line", C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
+    ("fdw_born_shot_batch", C.c_int, [vp, C.c_int, vp, C.c_ulonglong, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
+    ("fdw_born_shot_line_batch", C.c_int, [vp, C.c_int, vp, C.c_ulonglong, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
     ("fdw_two_step_active", C.c_int, [vp]),
     ("fdw_steps_per_pass", C.c_int, [vp]),
     ("fdw_selftest", C.c_int, [vp]),

@@ -470,6 +470,44 @@ class FDWave:
         check(lib().fdw_dev_born_steps(self._h, d_u_p, d_u_pp, d_du_p, d_du_pp, d_v2, d_m, int(kind), d_srce, sx, sz, gz, d_rec, d_rec0, it0, nsteps,
                                        int(first_pp_twice), stream))
 
+    def dev_born_line_steps(self, d_u_p, d_u_pp, d_du_p, d_du_pp, d_v2, d_m, kind, d_wav, sz, gz, d_rec, d_rec0, it0, nsteps, first_pp_twice=False,
+                            stream=None):
+        """dev_born_steps whose background pair is driven by the line source d_wav (device [>= it0+nsteps][nx]) on column sz instead of a point
+        source (fdwave.h, fdw_dev_born_line_steps).  stream as dev_born_steps takes it."""
+        check(lib().fdw_dev_born_line_steps(self._h, d_u_p, d_u_pp, d_du_p, d_du_pp, d_v2, d_m, int(kind), d_wav, sz, gz, d_rec, d_rec0, it0, nsteps,
+                                            int(first_pp_twice), stream))
+
+    def born_shot_line(self, v2, m, sz, gz, wav, kind=_lib.BORN_DTT, want_background=False):
+        """born_shot() driven by the line source wav[nx][nt] at depth sz (fdwave.h, fdw_born_shot_line); the background gather is
+        record_shot_line()'s."""
+        data = np.zeros((self.nx, self.nt), np.float32)
+        data0 = np.zeros((self.nx, self.nt), np.float32) if want_background else None
+        v2, m, wav = None if v2 is None else _f32(v2, (self.nxe, self.nze)), _f32(m, (self.nx, self.nz)), _f32(wav, (self.nx, self.nt))
+        check(lib().fdw_born_shot_line(self._h, None if v2 is None else v2.ctypes.data, m.ctypes.data, int(kind), sz, gz, wav.ctypes.data, data.ctypes.data,
+                                       data0.ctypes.data if want_background else None))
+        return (data, data0) if want_background else data
+
+    def born_shot_batch(self, nshots, m, sx0, dsx, sz, gz, srce, kind=_lib.BORN_DTT, v2_all=None, draw_offset=0, want_background=False):
+        """`nshots` Born shots of ONE reflectivity m[nx][nz], source rows sx0 + b dsx, models as shot_batch takes them (fdwave.h,
+        fdw_born_shot_batch): data[nshots][nx][nt], with want_background (data, data0).  One launch per time step where record_shot_batch
+        batches and the fused Born kernel runs; batch_parts() says how the call went."""
+        data = np.zeros((nshots, self.nx, self.nt), np.float32)
+        data0 = np.zeros((nshots, self.nx, self.nt), np.float32) if want_background else None
+        v2_all, m, srce = None if v2_all is None else _f32(v2_all, (nshots, self.nxe, self.nze)), _f32(m, (self.nx, self.nz)), _f32(srce, (self.nt,))
+        check(lib().fdw_born_shot_batch(self._h, nshots, None if v2_all is None else v2_all.ctypes.data, int(draw_offset), m.ctypes.data, int(kind), sx0, dsx,
+                                        sz, gz, srce.ctypes.data, data.ctypes.data, data0.ctypes.data if want_background else None))
+        return (data, data0) if want_background else data
+
+    def born_shot_line_batch(self, nshots, m, sz, gz, wav_all, kind=_lib.BORN_DTT, v2_all=None, draw_offset=0, want_background=False):
+        """born_shot_batch() with the shots' line sources wav_all[nshots][nx][nt] at depth sz (fdwave.h, fdw_born_shot_line_batch)."""
+        data = np.zeros((nshots, self.nx, self.nt), np.float32)
+        data0 = np.zeros((nshots, self.nx, self.nt), np.float32) if want_background else None
+        v2_all, m = None if v2_all is None else _f32(v2_all, (nshots, self.nxe, self.nze)), _f32(m, (self.nx, self.nz))
+        wav_all = _f32(wav_all, (nshots, self.nx, self.nt))
+        check(lib().fdw_born_shot_line_batch(self._h, nshots, None if v2_all is None else v2_all.ctypes.data, int(draw_offset), m.ctypes.data, int(kind), sz, gz,
+                                             wav_all.ctypes.data, data.ctypes.data, data0.ctypes.data if want_background else None))
+        return (data, data0) if want_background else data
+
     # ---- line sources (fdwave.h: plane-wave and encoded-shot migration) ----
     def shot_line(self, v2, sz, gz, wav, d_obs, imloc=None, want_fields=False, want_illum=False, illum=None):
         """shot() (v2=None: shot_resident()) whose forward loop is driven by the line source wav[nx][nt] at depth sz instead of a point source

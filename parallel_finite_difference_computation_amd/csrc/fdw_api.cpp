@@ -119,6 +119,8 @@ struct fdw_ctx {
     float* d_born_rec0 = nullptr;  // ... the background gather [nt][nx] beside d_rec
     size_t born_rec0_cap = 0;
     float* d_born_w = nullptr;     // Born modelling without the fused kernel, FDW_BORN_DTT: (A - B) of the background on the interior cells
+    float* b_born_rec0 = nullptr;  // fdw_born_shot_batch with data0: the shots' background gathers [shots][nt][nx]; allocated on first use
+    size_t b_born_rec0_cap = 0;
     size_t store_budget = 0; // fdw_rtm_stored_shot: bytes the stored source fields may take (0: whatever the device grants); fdw_set_store_budget
     int store_segments = 0;  // ... segments the last such shot was cut into (1: every field kept)
     size_t batch_budget = 0; // bytes a batch of shots may take (0: FDW_BATCH_BUDGET_BYTES, else 6 GiB); written by fdw_set_batch_budget alone
@@ -393,7 +395,7 @@ extern "C" void fdw_destroy(fdw_ctx* c)
                      c->fld[4], c->fld[5], c->fld[6], c->fld[7], c->fld[8], c->fld[9], c->d_v2, c->d_img, c->d_illum, c->d_srce, c->d_dobs, c->d_rec,
                      c->d_vp, c->d_vpe, (float*)c->d_draws, (float*)c->d_jump, c->bfld[0], c->bfld[1], c->bfld[2], c->bfld[3],
                      c->bfld[4], c->bfld[5], c->bfld[6], c->bfld[7], c->b_v2, c->b_img, c->b_dobs, c->b_illum, c->b_rec, c->b_wav, c->d_raw, c->d_wav, c->d_snap[0], c->d_snap[1], c->d_snap[2], c->d_amp, (float*)c->d_texc, c->d_exc, (float*)c->d_peak,
-                     c->d_born_m, c->d_born_rec0, c->d_born_w};
+                     c->d_born_m, c->d_born_rec0, c->d_born_w, c->b_born_rec0};
     for (float* b : bufs)
         if (b) (void)hipFree(b);
     if (c->stream) (void)hipStreamDestroy(c->stream);
@@ -2104,8 +2106,9 @@ static int check_born_args(const fdw_ctx* c, const char* who, int kind, int sx, 
     return FDW_OK;
 }
 
-// One iteration in ONE launch of the register-ring family (FDW_MODE_BORN): the pairs as the swap left them, f the source's view at this
-// iteration, rec / rec0 this iteration's trace rows (either may be NULL).
+// One iteration in ONE launch of the register-ring family (FDW_MODE_BORN; a line source: FDW_MODE_BORN_LINE): the pairs as the swap left
+// them, f the source's view at this iteration, rec / rec0 this iteration's trace rows (either may be NULL).  Inside a batch the launch covers
+// every shot: fields, models, sources and trace rows strided as step_impl strides them, the reflectivity shared.
 static int born_step_fused(fdw_ctx* c, const float* d_u_p, float* d_u_pp, const float* d_du_p, float* d_du_pp, const float* d_v2, const float* d_m, int kind,
                            const FwdView& f, int gz, float* rec, float* rec0, int pp_twice, hipStream_t s)
 {
@@ -2116,24 +2119,33 @@ static int born_step_fused(fdw_ctx* c, const float* d_u_p, float* d_u_pp, const 
     a.r0 = 0;
     a.r1 = std::min(c->nxl, c->upd_x1);
     Injection in;
-    FDW_TRY(place_source(c, "fdw_dev_born_steps", false, f.samples, f.sx, f.sz, &in));
+    FDW_TRY(place_injection(c, "Born modelling", FDW_MODE_FWD, f, &in));
     a.inj = f.samples + in.shift; a.inj_x = in.x; a.inj_z = f.sz; a.inj_n = in.n;
     fill_rec(c, a, rec, gz);
     a.texc = reinterpret_cast<int*>(rec0);      // the background's trace row travels where the excitation modes carry their map
     const BornCells C = born_cells(c);
     a.img_z1 = C.z1; a.exc_key = born_key(kind, C.z0);      // the rows of C: the receiver rows the launch covers
     if (a.r1 <= a.r0) return FDW_OK;
-    fill_geometry(c, a, a.r1 - a.r0);
-    hipError_t e = launch_step_fast(a, c->h, FDW_MODE_BORN, effective_prefetch(c), s);
+    if (c->nbatch > 1) {      // fdw_born_shot_batch / fdw_born_shot_line_batch: step_impl's strides; both trace rows advance by rec_bstride
+        a.nbatch = c->nbatch;
+        a.bstride = a.v2_bstride = (long long)field_elems(c);
+        a.inj_bstride = f.line ? (long long)c->nx * c->batch_nt : 0;
+        a.inj_dx = f.line ? 0 : c->batch_dsx;
+        a.rec_bstride = (long long)c->nx * c->batch_nt;
+    }
+    fill_geometry(c, a, a.r1 - a.r0, std::max(c->nbatch, 1));
+    hipError_t e = launch_step_fast(a, c->h, f.line ? FDW_MODE_BORN_LINE : FDW_MODE_BORN, effective_prefetch(c), s);
     if (e != hipSuccess) return fail(FDW_EHIP, "kernel launch failed: %s", hipGetErrorString(e));
     return FDW_OK;
 }
 
-// The loop of fdw_dev_born_steps behind its checks.  Without the fused kernel: the scattered pair's step, (A - B) of the background into
-// the scratch field (FDW_BORN_DTT: the background step overwrites B), the background step, the scatter kernel with the trace samples.
+// The loop of fdw_dev_born_steps / fdw_dev_born_line_steps behind its checks; src: the point or the line source of the background pair.
+// Without the fused kernel: the scattered pair's step, (A - B) of the background into the scratch field (FDW_BORN_DTT: the background step
+// overwrites B), the background step, the scatter kernel with the trace samples.
 static int born_loop(fdw_ctx* c, float* d_u_p, float* d_u_pp, float* d_du_p, float* d_du_pp, const float* d_v2, const float* d_m, int kind,
-                     const float* d_srce, int sx, int sz, int gz, float* d_rec, float* d_rec0, int it0, int nsteps, int first_pp_twice, hipStream_t s)
+                     const Forward& src, int gz, float* d_rec, float* d_rec0, int it0, int nsteps, int first_pp_twice, hipStream_t s)
 {
+    const int sz = src.sz;
     const bool fused = born_fused(c);
     if (!fused && kind == FDW_BORN_DTT && !c->d_born_w) {      // every word read is written first: no memset, nothing to wait for
         hipError_t e = hipMalloc((void**)&c->d_born_w, field_elems(c) * sizeof(float));
@@ -2141,7 +2153,6 @@ static int born_loop(fdw_ctx* c, float* d_u_p, float* d_u_pp, float* d_du_p, flo
     }
     if (d_rec) FDW_TRY(record_static(c, d_du_p, d_du_pp, gz, d_rec, it0, nsteps, s));
     if (d_rec0) FDW_TRY(record_static(c, d_u_p, d_u_pp, gz, d_rec0, it0, nsteps, s));
-    const Forward src = point_source(d_srce, sx, sz);
     const BornCells C = born_cells(c);
     const size_t nx = (size_t)c->nx;
     for (int k = 0; k < nsteps; k++) {
@@ -2175,18 +2186,32 @@ extern "C" int fdw_dev_born_steps(fdw_ctx* c, float* d_u_p, float* d_u_pp, float
     if (!d_u_p || !d_u_pp || !d_du_p || !d_du_pp || !d_v2 || !d_m || !d_srce) return fail(FDW_EINVAL, "fdw_dev_born_steps: NULL argument");
     if (it0 < 0 || nsteps < 0) return fail(FDW_EINVAL, "fdw_dev_born_steps: it0=%d nsteps=%d", it0, nsteps);
     FDW_TRY(check_born_args(c, "fdw_dev_born_steps", kind, sx, sz, gz));
-    return born_loop(c, d_u_p, d_u_pp, d_du_p, d_du_pp, d_v2, d_m, kind, d_srce, sx, sz, gz, d_rec, d_rec0, it0, nsteps, first_pp_twice,
+    return born_loop(c, d_u_p, d_u_pp, d_du_p, d_du_pp, d_v2, d_m, kind, point_source(d_srce, sx, sz), gz, d_rec, d_rec0, it0, nsteps, first_pp_twice,
                      pick_stream(c, stream));
 }
 
-extern "C" int fdw_born_shot(fdw_ctx* c, const float* v2, const float* m, int kind, int sx, int sz, int gz, const float* srce, float* data, float* data0)
+extern "C" int fdw_dev_born_line_steps(fdw_ctx* c, float* d_u_p, float* d_u_pp, float* d_du_p, float* d_du_pp, const float* d_v2, const float* d_m, int kind,
+                                       const float* d_wav, int sz, int gz, float* d_rec, float* d_rec0, int it0, int nsteps, int first_pp_twice, void* stream)
 {
     if (!c) return fail(FDW_EINVAL, "ctx is NULL");
-    FDW_TRY(check_single_shot_ctx(c, "Born modelling", "fdw_born_shot"));
-    if (!m || !srce || !data) return fail(FDW_EINVAL, "fdw_born_shot: NULL argument");
+    FDW_TRY(check_single_shot_ctx(c, "Born modelling", "fdw_dev_born_line_steps"));
+    if (!d_u_p || !d_u_pp || !d_du_p || !d_du_pp || !d_v2 || !d_m || !d_wav) return fail(FDW_EINVAL, "fdw_dev_born_line_steps: NULL argument");
+    if (it0 < 0 || nsteps < 0) return fail(FDW_EINVAL, "fdw_dev_born_line_steps: it0=%d nsteps=%d", it0, nsteps);
+    FDW_TRY(check_born_args(c, "fdw_dev_born_line_steps", kind, 0, sz, gz));      // a line has no source row
+    return born_loop(c, d_u_p, d_u_pp, d_du_p, d_du_pp, d_v2, d_m, kind, line_source(d_wav, sz), gz, d_rec, d_rec0, it0, nsteps, first_pp_twice,
+                     pick_stream(c, stream));
+}
+
+// fdw_born_shot (samples: the wavelet [nt]) / fdw_born_shot_line (line: the gather [nx][nt], sx unused)
+static int born_shot_impl(fdw_ctx* c, const char* who, const float* v2, const float* m, int kind, int sx, int sz, int gz, const float* samples, float* data,
+                          float* data0, bool line)
+{
+    if (!c) return fail(FDW_EINVAL, "ctx is NULL");
+    FDW_TRY(check_single_shot_ctx(c, "Born modelling", who));
+    if (!m || !samples || !data) return fail(FDW_EINVAL, "%s: NULL argument", who);
     FDW_TRY(has_model(c, v2));
-    FDW_TRY(check_born_args(c, "fdw_born_shot", kind, sx, sz, gz));
-    if (c->nx <= 0 || c->nz <= 0) return fail(FDW_EINVAL, "fdw_born_shot: no interior");
+    FDW_TRY(check_born_args(c, who, kind, line ? 0 : sx, sz, gz));
+    if (c->nx <= 0 || c->nz <= 0) return fail(FDW_EINVAL, "%s: no interior", who);
     HIP_TRY(hipSetDevice(c->device));
     const int nt = c->prm.nt;
     FDW_TRY(ensure_work_buffers(c, 4, false));
@@ -2196,14 +2221,24 @@ extern "C" int fdw_born_shot(fdw_ctx* c, const float* v2, const float* m, int ki
     FDW_TRY(zero_fields(c, c->fld, 4));
     end_residency(c, v2);
     if (v2) FDW_TRY(upload_rows(c, c->d_v2, v2, c->stream));
-    FDW_TRY(upload_source(c, srce, nt));
+    FDW_TRY(line ? upload_line_source(c, samples) : upload_source(c, samples, nt));
     FDW_TRY(image_to_device(c, m, c->d_born_m));
-    FDW_TRY(born_loop(c, c->fld[0], c->fld[1], c->fld[2], c->fld[3], c->d_v2, c->d_born_m, kind, c->d_srce, sx, sz, gz, c->d_rec,
+    FDW_TRY(born_loop(c, c->fld[0], c->fld[1], c->fld[2], c->fld[3], c->d_v2, c->d_born_m, kind, device_source(c, line, sx, sz, c->d_wav), gz, c->d_rec,
                       data0 ? c->d_born_rec0 : nullptr, 0, nt, 0, c->stream));
     FDW_TRY(gathers_to_host(c, c->d_rec, 1, data));
     if (data0) FDW_TRY(gathers_to_host(c, c->d_born_rec0, 1, data0));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return FDW_OK;
+}
+
+extern "C" int fdw_born_shot(fdw_ctx* c, const float* v2, const float* m, int kind, int sx, int sz, int gz, const float* srce, float* data, float* data0)
+{
+    return born_shot_impl(c, "fdw_born_shot", v2, m, kind, sx, sz, gz, srce, data, data0, false);
+}
+
+extern "C" int fdw_born_shot_line(fdw_ctx* c, const float* v2, const float* m, int kind, int sz, int gz, const float* wav, float* data, float* data0)
+{
+    return born_shot_impl(c, "fdw_born_shot_line", v2, m, kind, -1, sz, gz, wav, data, data0, true);
 }
 
 // ---- shots driven by a line source (definitions in fdwave.h) ----
@@ -3487,6 +3522,95 @@ extern "C" int fdw_record_shot_line_batch(fdw_ctx* c, int nshots, const float* v
     FDW_TRY(check_single_shot_ctx(c, "line sources", "fdw_record_shot_line_batch"));
     FDW_TRY(check_line_args(c, "fdw_record_shot_line_batch", sz, gz, true, false));
     return record_batch_impl(c, nshots, v2_all, draw_offset, -1, 0, sz, gz, wav_all, data, true);
+}
+
+// ---- batches of Born shots (definitions in fdwave.h) ----
+// The regime of the batched launches: fdw_record_shot_batch's, where the fused Born kernel runs
+static bool born_batch_ok(const fdw_ctx* c) { return batch_ok(c) && born_fused(c); }
+
+// One part of fdw_born_shot_batch / fdw_born_shot_line_batch: `nshots` independent shots.  Batched, it works in fdw_shot_batch's buffers:
+// bfld[0..1] the background pairs, bfld[2..3] the scattered pairs, b_v2 the models, b_dobs the scattered trace rows [shot][nt][nx], b_wav the
+// line gathers; b_born_rec0 the background trace rows when data0 is asked for; ONE reflectivity, c->d_born_m, for all shots.
+static int born_batch_part(fdw_ctx* c, const char* who, int nshots, const float* v2_all, unsigned long long draw_offset, const float* m, int kind, int sx0,
+                           int dsx, int sz, int gz, const float* samples, float* data, float* data0, bool line, bool room)
+{
+    const int nt = c->prm.nt;
+    const size_t ne = (size_t)c->prm.nxe * c->prm.nze, ng = (size_t)c->nx * nt, fe = field_elems(c);
+    const long long draws = fdw_border_draws(c->nx, c->nz, c->prm.nxb, c->prm.nzb);
+    auto one_by_one = [&] {
+        for (int b = 0; b < nshots; b++) {
+            if (!v2_all) FDW_TRY(fdw_dev_extendvel_linear(c, draw_offset + (unsigned long long)b * draws, nullptr));
+            FDW_TRY(born_shot_impl(c, who, v2_all ? v2_all + b * ne : nullptr, m, kind, sx0 + b * dsx, sz, gz, line ? samples + b * ng : samples, data + b * ng,
+                                   data0 ? data0 + b * ng : nullptr, line));
+        }
+        return (int)FDW_OK;
+    };
+    auto fallback = [&] { batch_part_ran(c, false); return one_by_one(); };
+    if (!born_batch_ok(c) || !room) return fallback();      // a regime the batched launches do not cover, or a budget below one shot
+    if (nshots == 1) { batch_part_ran(c, true); return one_by_one(); }      // nothing to gain
+    int rc;
+    if ((rc = alloc_zero(&c->d_born_m, fe))) return rc;
+    if ((rc = ensure_batch_buffers(c, nshots, true)) == FDW_ENOMEM) return fallback();      // no room for the batch
+    if (!rc && data0 && (rc = ensure_cap(&c->b_born_rec0, &c->b_born_rec0_cap, ng * nshots)) == FDW_ENOMEM) return fallback();      // ... or its background gathers
+    if (!rc && line && (rc = ensure_cap(&c->b_wav, &c->b_wav_cap, ng * nshots)) == FDW_ENOMEM) return fallback();      // ... or its line-source gathers
+    if (!rc) batch_part_ran(c, true);
+    if (rc || (rc = line ? gathers_to_device(c, samples, c->b_wav, nshots) : upload_source(c, samples, nt)) || (rc = batch_models(c, nshots, v2_all, draw_offset)))
+        return rc;
+    hipStream_t s = c->stream;
+    for (int i = 0; i < 4; i++) HIP_TRY(hipMemsetAsync(c->bfld[i], 0, fe * nshots * sizeof(float), s));
+    if ((rc = image_to_device(c, m, c->d_born_m))) return rc;
+    {
+        BatchScope scope(c, nshots, dsx, false);
+        // d_dobs: the batch's [shot][nt][nx]
+        if ((rc = born_loop(c, c->fld[0], c->fld[1], c->fld[2], c->fld[3], c->d_v2, c->d_born_m, kind, device_source(c, line, sx0, sz, c->b_wav), gz, c->d_dobs,
+                            data0 ? c->b_born_rec0 : nullptr, 0, nt, 0, s)))
+            return rc;
+    }
+    if ((rc = gathers_to_host(c, c->b_dobs, nshots, data))) return rc;
+    if (data0 && (rc = gathers_to_host(c, c->b_born_rec0, nshots, data0))) return rc;
+    HIP_TRY(hipStreamSynchronize(s));
+    return FDW_OK;
+}
+
+// the checks of both batched Born calls, then the parts.  Per shot the batch holds fdw_shot_batch's eleven fields (of which it uses the two
+// pairs and v2) and the scattered gather [nt][nx], with data0 the background gather, of a line batch the line gather: parts by batch_part.
+static int born_batch_impl(fdw_ctx* c, const char* who, int nshots, const float* v2_all, unsigned long long draw_offset, const float* m, int kind, int sx0,
+                           int dsx, int sz, int gz, const float* samples, float* data, float* data0, bool line)
+{
+    if (!c) return fail(FDW_EINVAL, "ctx is NULL");
+    FDW_TRY(check_single_shot_ctx(c, "Born modelling", who));
+    if (!m || !samples || !data) return fail(FDW_EINVAL, "%s: NULL argument", who);
+    if (nshots < 1) return fail(FDW_EINVAL, "%s: nshots=%d", who, nshots);
+    if (!v2_all && !c->model_resident) return fail(FDW_ESTATE, "%s: no model: pass v2_all or call fdw_model_resident first", who);
+    FDW_TRY(check_born_args(c, who, kind, line ? 0 : sx0, sz, gz));
+    if (!line) FDW_TRY(check_batch_source_rows(c, nshots, sx0, dsx));
+    if (c->nx <= 0 || c->nz <= 0) return fail(FDW_EINVAL, "%s: no interior", who);
+    HIP_TRY(hipSetDevice(c->device));
+    if (v2_all) c->v2_resident = false;
+    const size_t ne = (size_t)c->prm.nxe * c->prm.nze, ng = (size_t)c->nx * c->prm.nt;
+    const int gathers = 1 + (data0 ? 1 : 0) + (line ? 1 : 0);
+    const bool room = batch_budget(c) >= (11 * field_elems(c) + (size_t)gathers * ng) * sizeof(float);      // a budget below ONE shot: no batch buffers at all
+    const int part = room ? batch_part(c, nshots, 11, gathers) : nshots;
+    const unsigned long long draws = (unsigned long long)fdw_border_draws(c->nx, c->nz, c->prm.nxb, c->prm.nzb);
+    batch_begin(c);
+    for (int b0 = 0; b0 < nshots; b0 += part) {      // independent shots: nothing is carried from part to part
+        const int nb = std::min(part, nshots - b0);
+        FDW_TRY(born_batch_part(c, who, nb, v2_all ? v2_all + b0 * ne : nullptr, draw_offset + b0 * draws, m, kind, sx0 + b0 * dsx, dsx, sz, gz,
+                                line ? samples + b0 * ng : samples, data + b0 * ng, data0 ? data0 + b0 * ng : nullptr, line, room));
+    }
+    return batch_end(c, nshots, FDW_OK);
+}
+
+extern "C" int fdw_born_shot_batch(fdw_ctx* c, int nshots, const float* v2_all, unsigned long long draw_offset, const float* m, int kind, int sx0, int dsx,
+                                   int sz, int gz, const float* srce, float* data, float* data0)
+{
+    return born_batch_impl(c, "fdw_born_shot_batch", nshots, v2_all, draw_offset, m, kind, sx0, dsx, sz, gz, srce, data, data0, false);
+}
+
+extern "C" int fdw_born_shot_line_batch(fdw_ctx* c, int nshots, const float* v2_all, unsigned long long draw_offset, const float* m, int kind, int sz, int gz,
+                                        const float* wav_all, float* data, float* data0)
+{
+    return born_batch_impl(c, "fdw_born_shot_line_batch", nshots, v2_all, draw_offset, m, kind, -1, 0, sz, gz, wav_all, data, data0, true);
 }
 
 // mod_main's shot loop (M:140-174) for `nshots` consecutive shots on its one velocity model, one launch per time step for all of them

@@ -158,6 +158,8 @@ __device__ __forceinline__ void march(const StepArgs& a, const ShotView& sv, con
     if constexpr (EXC != 0) texc_w = reinterpret_cast<float*>(a.texc) + (long long)blockIdx.y * a.bstride;
     f4 fring[TWO ? R : 1], fqhal[TWO ? PF : 1], fqpp[TWO ? PF : 1];      // the source field's (BORN: the scattered field's) ring and pointwise queues
     f4 qm[BORN ? PF : 1];                                   // BORN: the reflectivity row
+    [[maybe_unused]] const float* rec0_w = nullptr;         // BORN: this step's background trace row of this block's shot (a.texc + shot * a.rec_bstride)
+    if constexpr (BORN) rec0_w = reinterpret_cast<const float*>(a.texc) + (long long)blockIdx.y * a.rec_bstride;
     constexpr int NV = LOOK > PF ? LOOK : PF;
     static_for<2 * H>([&](auto K) {
         constexpr int k = decltype(K)::value;
@@ -192,7 +194,7 @@ __device__ __forceinline__ void march(const StepArgs& a, const ShotView& sv, con
                 fqhal[m] = load_fhalo(row);
                 fqpp[m] = load_plain(sv.fpp, row);
             }
-            if constexpr (BORN) qm[m] = load_plain(sv.img, row);
+            if constexpr (BORN) qm[m] = load_plain(a.img, row);
         }
         __builtin_amdgcn_sched_barrier(0);
     });
@@ -406,8 +408,8 @@ __device__ __forceinline__ void march(const StepArgs& a, const ShotView& sv, con
                 if constexpr (TWO) f4_store(sv.fpp + (size_t)r * pitch, voff, fres);
             }
             if constexpr (BORN) {      // the trace samples of both new fields (either gather may be absent: wave-uniform)
-                if (a.rec) f1_store_arr(array_rsrc(a.rec, (unsigned)a.rec_n * 4u), rec_offset(rec_lane, r, a.rec_x0, a.rec_n), f4_pick(fres, a.rec_z & 3));
-                if (a.texc) f1_store_arr(array_rsrc(reinterpret_cast<const float*>(a.texc), (unsigned)a.rec_n * 4u), rec_offset(rec_lane, r, a.rec_x0, a.rec_n), f4_pick(res, a.rec_z & 3));
+                if (a.rec) f1_store_arr(array_rsrc(sv.rec, (unsigned)a.rec_n * 4u), rec_offset(rec_lane, r, a.rec_x0, a.rec_n), f4_pick(fres, a.rec_z & 3));
+                if (a.texc) f1_store_arr(array_rsrc(rec0_w, (unsigned)a.rec_n * 4u), rec_offset(rec_lane, r, a.rec_x0, a.rec_n), f4_pick(res, a.rec_z & 3));
             }
             if constexpr (REC) f1_store_arr(array_rsrc(sv.rec, (unsigned)a.rec_n * 4u), rec_offset(rec_lane, r, a.rec_x0, a.rec_n), f4_pick(res, a.rec_z & 3));
 
@@ -433,7 +435,7 @@ __device__ __forceinline__ void march(const StepArgs& a, const ShotView& sv, con
                     fqhal[Q] = load_fhalo(nr);
                     fqpp[Q] = load_plain(sv.fpp, nr);
                 }
-                if constexpr (BORN) qm[Q] = load_plain(sv.img, nr);
+                if constexpr (BORN) qm[Q] = load_plain(a.img, nr);
             }
             if constexpr (TWO) fring[U] = load_f(r - H + R);
         }
@@ -559,6 +561,16 @@ __global__ __launch_bounds__(256) void fdw_step_born_kernel(const StepArgs a)
 {
     FDW_STEP_TILE(a, sv, lane, zs, xa, xe)
     march<H, true, 1, false, false, PF, false, false, NUM, false, false, 0, true>(a, sv, lane, zs, xa, xe);
+}
+
+// Born modelling driven by a LINE source (FDW_MODE_BORN_LINE, fdw_dev_born_line_steps): fdw_step_born_kernel with INJ = 2 -- the background's new
+// field takes one sample per row of [inj_x, inj_x + inj_n) on column inj_z after the leap-frog, and that field, line samples included, is what
+// the scatter and the background trace row see.  The scattered pair takes no injection.  One sample load per row more than the point source.
+template <int H, int PF, int NUM>
+__global__ __launch_bounds__(256) void fdw_step_line_born_kernel(const StepArgs a)
+{
+    FDW_STEP_TILE(a, sv, lane, zs, xa, xe)
+    march<H, true, 2, false, false, PF, false, false, NUM, false, false, 0, true>(a, sv, lane, zs, xa, xe);
 }
 
 #if FDW_TU == 0
@@ -822,6 +834,7 @@ static hipError_t launch_rtm_hp(const StepArgs& a, int mode, hipStream_t s)
     case FDW_MODE_FWD_EXC: hipLaunchKernelGGL((fdw_step_exc_kernel<H, PF, NUM>), grid, block, 0, s, a); break;
     case FDW_MODE_FWD_LINE_PICK: hipLaunchKernelGGL((fdw_step_line_pick_kernel<H, PF, NUM>), grid, block, 0, s, a); break;
     case FDW_MODE_BORN: hipLaunchKernelGGL((fdw_step_born_kernel<H, PF, NUM>), grid, block, 0, s, a); break;
+    case FDW_MODE_BORN_LINE: hipLaunchKernelGGL((fdw_step_line_born_kernel<H, PF, NUM>), grid, block, 0, s, a); break;
     default: return hipErrorInvalidValue;
     }
     return hipGetLastError();

@@ -18,7 +18,9 @@
  *
  * Born modelling (fdwave.h, "Born modelling"): with `bornfile=<path>` (fp32 [nx][nz] reflectivity; `born_kind=0|1`, default 1 = the second
  * time difference) the datfile holds the SCATTERED gathers [ns][nx][nt] of fdw_born_shot in the models and border draws the program uses
- * without the key, shot by shot on one GPU; `born_bg=<path>` also writes the background gathers, which are the plain program's datfile.
+ * without the key, on one GPU, in groups of fdw_shot_batch_max shots through fdw_born_shot_batch (one launch per time step for the group where
+ * the library batches; FDW_NO_SHOT_BATCH=1 keeps one shot after the other; the files are byte for byte the same either way);
+ * `born_bg=<path>` also writes the background gathers, which are the plain program's datfile.
  * bornfile together with slabs / gpus (deck key or environment), a born_kind outside {0, 1} and a short or missing reflectivity file are
  * refused before any file, thread or device is touched. */
 #include <stdio.h>
@@ -359,14 +361,13 @@ int main(int argc, char **argv)
         }
         free(v2); free(data);
     } else if (bornfile) {
-        /* ---- Born modelling: one GPU, one shot after the other, each in the model the plain program gives it ---- */
+        /* ---- Born modelling: one GPU, groups of fdw_shot_batch_max shots through fdw_born_shot_batch, each shot in the model the plain
+         * program gives it.  FDW_NO_SHOT_BATCH=1: groups of one, which the library runs as fdw_born_shot. ---- */
         fdw_ctx *ctx = NULL;
         float *m = read_floats(bornfile, ni, "bornfile");
-        float *data = (float *)malloc(ng * sizeof(float)), *data0 = born_bg ? (float *)malloc(ng * sizeof(float)) : NULL;
-        float *v2 = dev_border ? NULL : (float *)malloc(ne * sizeof(float));
         char *tmpbg = born_bg ? (char *)malloc(strlen(born_bg) + 16) : NULL;
         FILE *bg = NULL;
-        if (!m || !data || (born_bg && (!data0 || !tmpbg)) || (!dev_border && !v2)) {
+        if (!m || (born_bg && !tmpbg)) {
             fprintf(stderr, "out of host memory\n");
             ok = 0;
         }
@@ -387,24 +388,33 @@ int main(int argc, char **argv)
             fprintf(stderr, "fdw_model_resident: %s\n", fdw_last_error());
             ok = 0;
         }
-        for (int is = 0; is < ns && ok; is++) {
-            if (dev_border) {
-                if (fdw_dev_extendvel_linear(ctx, (unsigned long long)is * draws, NULL) != FDW_OK) ok = 0;
-            } else {
-                HOST_MODEL(is, v2);
-            }
-            if (!ok || fdw_born_shot(ctx, dev_border ? NULL : v2, m, born_kind, sx0 + is * ds, sz, gz, srce, data, data0) != FDW_OK) {
-                fprintf(stderr, "shot %d: %s\n", is, fdw_last_error());
+        int batch = (ok && ns > 1 && !getenv("FDW_NO_SHOT_BATCH")) ? fdw_shot_batch_max(ctx) : 1;
+        if (batch > ns) batch = ns;
+        if (batch < 1) batch = 1;
+        float *data = (float *)malloc((size_t)batch * ng * sizeof(float)), *data0 = born_bg ? (float *)malloc((size_t)batch * ng * sizeof(float)) : NULL;
+        float *v2 = dev_border ? NULL : (float *)malloc((size_t)batch * ne * sizeof(float));
+        if (ok && (!data || (born_bg && !data0) || (!dev_border && !v2))) {
+            fprintf(stderr, "out of host memory\n");
+            ok = 0;
+        }
+        for (int is0 = 0; is0 < ns && ok; is0 += batch) {
+            const int nb = is0 + batch <= ns ? batch : ns - is0;
+            for (int b = 0; b < nb && !dev_border; b++) HOST_MODEL(is0 + b, v2 + (size_t)b * ne);
+            if (fdw_born_shot_batch(ctx, nb, v2, (unsigned long long)is0 * draws, m, born_kind, sx0 + is0 * ds, ds, sz, gz, srce, data, data0) != FDW_OK) {
+                fprintf(stderr, "shots %d..%d: %s\n", is0, is0 + nb - 1, fdw_last_error());
                 ok = 0;
                 break;
             }
-            if (fwrite(data, sizeof(float), ng, out) != ng || (bg && fwrite(data0, sizeof(float), ng, bg) != ng)) {
+            if (is0 == 0 && getenv("FDW_TIMING"))      /* which path the first group took (a group of one, or a regime the library does not batch: one by one) */
+                fprintf(stderr, "[timing] shots per launch sequence: up to %d (%s)\n", batch, fdw_batch_parts(ctx) > 0 ? "fdw_born_shot_batch" : "one by one");
+            if (fwrite(data, sizeof(float), (size_t)nb * ng, out) != (size_t)nb * ng || (bg && fwrite(data0, sizeof(float), (size_t)nb * ng, bg) != (size_t)nb * ng)) {
                 fprintf(stderr, "write failed\n");
                 ok = 0;
                 break;
             }
-            printf("** shot %d, source at (%d,%d): %d receivers at depth %d, %d samples (scattered field, kind %d)\n", is + 1, fsx + is * ds, sz - nzb, nx,
-                   gz - nzb, nt, born_kind);
+            for (int b = 0; b < nb; b++)
+                printf("** shot %d, source at (%d,%d): %d receivers at depth %d, %d samples (scattered field, kind %d)\n", is0 + b + 1, fsx + (is0 + b) * ds,
+                       sz - nzb, nx, gz - nzb, nt, born_kind);
         }
         if (ctx) fdw_destroy(ctx);
         if (bg && fclose(bg) != 0) ok = 0;
