@@ -798,7 +798,8 @@ int fdw_shot_excitation_batch(fdw_ctx *ctx, int nshots, const float *v2_all, uns
  * fdw_born_shot       one shot from rest for the context's nt: m [nx][nz] is embedded into a zeroed field, the gathers are recorded on the
  *                     device and downloaded transposed to [nx][nt] as fdw_record_shot does (data: scattered; data0, may be NULL: background).
  *                     v2 NULL: the resident model (FDW_ESTATE without one).  Work arrays are allocated on first use, freed by fdw_destroy.
- * Out of scope: Born kernels in the two-step and four-step families, slabs and several GPUs, the DTT-adjoint imaging condition. */
+ * Out of scope: Born kernels in the two-step and four-step families, slabs and several GPUs (the DTT-adjoint imaging condition: "DTT
+ * imaging" below). */
 enum { FDW_BORN_FIELD = 0, FDW_BORN_DTT = 1 };
 int fdw_dev_born_steps(fdw_ctx *ctx, float *d_u_p, float *d_u_pp, float *d_du_p, float *d_du_pp, const float *d_v2, const float *d_m, int kind,
                        const float *d_srce, int sx, int sz, int gz, float *d_rec, float *d_rec0, int it0, int nsteps, int first_pp_twice, void *stream);
@@ -854,6 +855,77 @@ int fdw_born_shot_batch(fdw_ctx *ctx, int nshots, const float *v2_all, unsigned 
                         int kind, int sx0, int dsx, int sz, int gz, const float *srce, float *data /* [nshots][nx][nt] */, float *data0 /* NULL ok */);
 int fdw_born_shot_line_batch(fdw_ctx *ctx, int nshots, const float *v2_all, unsigned long long draw_offset, const float *m, int kind, int sz, int gz,
                              const float *wav_all /* [nshots][nx][nt] */, float *data, float *data0);
+
+/* ---- DTT imaging: the second-time-difference imaging condition, the adjoint of FDW_BORN_DTT --------------------------------------------
+ * fdw_shot and every form built on it image with the cross-correlation img += F_k (*) r^{k+1}: the transpose of FDW_BORN_FIELD.  This is the
+ * matching transpose of FDW_BORN_DTT, the piece a linearised inversion loop (Born, residual, gradient) needs for the gradient of its own
+ * misfit.  The RTM dialect on full-grid contexts, EXACT and FAST numerics alike (FAST changes the Laplacian only).
+ *
+ * C is the cell set of the Born section.  F_k is the source field iteration k of fd_back images and r^{k+1} the receiver field that
+ * iteration stores, raw, injected sample included, both as fdw_dev_back_iter defines them today.  For k = 0 .. nsteps-1
+ *          q_k = (F_k (-) F_{k+1}) (-) (F_{k+1} (-) F_{k+2})        three fp32 subtractions, round to nearest, nothing fused
+ * -- the Born section's q with U = F_k, A = F_{k+1}, B = F_{k+2}: the levels u^{j+1}, u^j, u^{j-1} FDW_BORN_DTT used at forward iteration
+ * j = nt-1-k -- and on C, for k ascending,
+ *          img = img (+) ( q_k (*) r^{k+1} )                        product and sum rounded separately
+ * Every other word of d_img keeps its bits: border, padding columns, cells outside the extents, and the border cells inside the launch
+ * extents that the cross-correlation epilogue does touch.  No cell of C is ever damped: every operand is the raw word the buffers hold.
+ *
+ * The lag.  q_k needs F_{k+1} and F_{k+2}, which the backward loop reconstructs one and two iterations later, so the loop runs two behind:
+ *   iterations 0, 1   the source fields are the two snapshots; the receiver step and its injection exactly as
+ *                     fdw_dev_back_iter(step_source = 0) runs them; d_img is not touched.
+ *   iteration i >= 2  fdw_dev_back_iter(step_source = 1) with the term k = i-2, q_{i-2} (*) r^{i-1}, in place of the cross-correlation:
+ *                     F_{i-2} = the entry words of d_f0, F_{i-1} = d_f1, F_i = the new source field, r^{i-1} = the entry words of d_ppr.
+ *   tail              after the last iteration two source-only reconstructions F_nsteps, F_{nsteps+1} (the plain leap-frog of R:317-318,
+ *                     mode 1, no receiver step) supply the terms k = nsteps-2 and k = nsteps-1, paired with r^{nsteps-1} and r^{nsteps},
+ *                     added in that order.  nsteps < 2: the same rule with fewer terms.
+ * Consequences: the source pair and the receiver pair (static receiver rows of ragged compat grids included) equal fdw_dev_back_iter's bit
+ * for bit, only the image differs; an all-zero gather leaves every word of the image as it came.
+ *
+ * Exact adjointness.  The backward loop steps with T = 2 + V K (V = diag(v2 dt2), K the Laplacian), which is not the transpose of the
+ * forward T, but V^-1 T V = T^T.  Hence
+ *          < Born_DTT(m), w > = < m, (1/v2) (.) Image_DTT( v2_rec (.) w ) >,    v2_rec[ix] = v2[nxb+ix][gz], 1/v2 per image cell,
+ * up to fp32 rounding, provided that no field reaches a damped column, that the source is silent on the levels the image uses (fd_back
+ * reconstructs without a source: the reference's convention, kept) and that m vanishes where the reconstruction is therefore wrong.  With a
+ * constant v2 the two weights cancel.  The two weights, one fp32 operation per word, pure host code (no device), out may be the input:
+ *   fdw_gather_scale_v2    out[ix][it] = g[ix][it] (*) v2[nxb+ix][gz]
+ *   fdw_image_unscale_v2   out[ix][iz] = img[ix][iz] (/) v2[nxb+ix][nzb+iz]
+ *
+ * fdw_dev_back_iter_dtt  one iteration as defined above on caller-owned device arrays, rows [r0, r1) = [0, nxl) (the whole grid; anything
+ *                     else is FDW_EINVAL).  step_source = 0: iterations 0 and 1 (d_f0 may be NULL, d_img is not touched).  Everything goes
+ *                     on the given stream (NULL: the context's), nothing is synchronised.  FDW_EINVAL before anything is enqueued: a NULL
+ *                     buffer, aliased arrays, gz outside the grid.  FDW_ESTATE: slab contexts, the sibling's dialects, a context inside a batch.
+ * fdw_dev_dtt_image   one term on C: d_img = d_img (+) ((d_fa (-) d_fb) (-) (d_fb (-) d_fc)) (*) d_r.  A device caller's tail is
+ *                     fdw_dev_step(mode 1) into a copy of the older level, then this.  Same stream contract and refusals.
+ *   Kernels: the one-step register-ring family (orders 2-8, prefetch 1 / 2 / 3 at order 8, EXACT and FAST) has fdw_step_back_dtt_kernel,
+ *   the fused backward iteration with one more value of its imaging epilogue: every operand is already in registers, so it adds three
+ *   subtractions and one live mask and no memory traffic (36 B/point, as the cross-correlation iteration); no scratch.  Iterations 0 and 1
+ *   run the receiver step as the line-source step on the receiver rows (fdw_step_line_kernel: the same damping, leap-frog and injection,
+ *   no image).  Orders above 8, the forced generic kernel and FDW_NO_FUSED_BACK=1 run four launches: F_{i-2} (-) F_{i-1} on C into a
+ *   context-owned scratch field (allocated by the first call that needs it), the plain source step, fdw_dtt_image_kernel while d_ppr still
+ *   holds r^{i-1}, the receiver step without imaging.  The two-step and four-step families have no DTT kernel: a DTT backward loop runs
+ *   one-step iterations on every context, as Born does; the forward loop keeps its family.
+ *
+ * Shots.  fdw_shot_dtt / fdw_shot_line_dtt are fdw_shot / fdw_shot_line with this backward loop (single iterations, then the tail into the
+ * two spare source buffers); illum (NULL ok) as fdw_shot_illum, residual = 1 as fdw_shot_residual (resid NULL ok; resid with residual = 0
+ * is FDW_EINVAL), v2 NULL: the resident model.  Every output other than imloc equals the cross-correlation call's bit for bit.
+ * residual = 1 makes imloc the gradient of the DTT Born misfit (up to the two weights above).  The batches are fdw_shot_batch_residual's
+ * and fdw_shot_line_batch_residual's: the same parts under the same budget, fdw_batch_parts 0 / 1 / k as there, batched imloc equal to the
+ * single-shot calls bit for bit.  Snapshots (fdw_shot_snaps), slab contexts, the sibling's dialects and excitation imaging do not combine
+ * with DTT imaging: FDW_ESTATE where a context of that kind is handed in; there is no DTT form of fdw_shot_snaps or fdw_shot_excitation.
+ * Out of scope: DTT kernels in the two-step and pipeline backward families, slabs and several GPUs, snapshots, a conjugate-gradient driver. */
+int fdw_dev_back_iter_dtt(fdw_ctx *ctx, int step_source, const float *d_f1, float *d_f0, const float *d_pr, float *d_ppr, const float *d_v2, int r0,
+                          int r1, int pp_twice, const float *d_samples, int gz, float *d_img, void *stream);
+int fdw_dev_dtt_image(fdw_ctx *ctx, const float *d_fa, const float *d_fb, const float *d_fc, const float *d_r, float *d_img, void *stream);
+int fdw_gather_scale_v2(const float *v2, int nxe, int nze, int nxb, int gz, int nx, int nt, const float *g /* [nx][nt] */, float *out);
+int fdw_image_unscale_v2(const float *v2, int nxe, int nze, int nxb, int nzb, int nx, int nz, const float *img /* [nx][nz] */, float *out);
+int fdw_shot_dtt(fdw_ctx *ctx, const float *v2 /* NULL: resident */, int sx, int sz, int gz, const float *srce, const float *d_obs, float *imloc,
+                 float *illum /* NULL ok */, int residual /* 0 | 1 */, float *resid /* NULL ok */, float *P, float *PP);
+int fdw_shot_line_dtt(fdw_ctx *ctx, const float *v2, int sz, int gz, const float *wav, const float *d_obs, float *imloc, float *illum, int residual,
+                      float *resid, float *P, float *PP);
+int fdw_shot_batch_dtt(fdw_ctx *ctx, int nshots, const float *v2_all, unsigned long long draw_offset, int sx0, int dsx, int sz, int gz,
+                       const float *srce, const float *d_obs, float *imloc, float *illum, int residual, float *resid);
+int fdw_shot_line_batch_dtt(fdw_ctx *ctx, int nshots, const float *v2_all, unsigned long long draw_offset, int sz, int gz, const float *wav_all,
+                            const float *d_obs, float *imloc, float *illum, int residual, float *resid);
 
 /* ---- tuning / introspection --------------------------------------------------------------------
  * fdw_set_tuning  xchunk = rows marched per wave (0 = auto), wz = waves of a block laid along z

@@ -13,6 +13,7 @@ vp = C.c_void_p
 FDW_OK, FDW_EINVAL, FDW_ENODEVICE, FDW_EHIP, FDW_ENOMEM, FDW_ESTATE = 0, -1, -2, -3, -4, -5
 MODE_FWD, MODE_PLAIN, MODE_RECV = 0, 1, 2
 BORN_FIELD, BORN_DTT = 0, 1      # fdwave.h, "Born modelling": the kind of the scatter
+IMAGE_XCORR, IMAGE_DTT = 0, 1    # the imaging condition of a shot: the cross-correlation, or the second time difference (fdwave.h, "DTT imaging")
 
 
 class FdwError(RuntimeError):
@@ -167,6 +168,14 @@ SIGNATURES = [
     ("fdw_born_shot_line", C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
     ("fdw_born_shot_batch", C.c_int, [vp, C.c_int, vp, C.c_ulonglong, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
     ("fdw_born_shot_line_batch", C.c_int, [vp, C.c_int, vp, C.c_ulonglong, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
+    ("fdw_dev_back_iter_dtt", C.c_int, [vp, C.c_int, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, vp]),
+    ("fdw_dev_dtt_image", C.c_int, [vp, vp, vp, vp, vp, vp, vp]),
+    ("fdw_gather_scale_v2", C.c_int, [f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, f32p, f32p]),
+    ("fdw_image_unscale_v2", C.c_int, [f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, f32p, f32p]),
+    ("fdw_shot_dtt", C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, f32p, f32p, f32p, vp, C.c_int, vp, vp, vp]),
+    ("fdw_shot_line_dtt", C.c_int, [vp, vp, C.c_int, C.c_int, f32p, f32p, f32p, vp, C.c_int, vp, vp, vp]),
+    ("fdw_shot_batch_dtt", C.c_int, [vp, C.c_int, vp, C.c_ulonglong, C.c_int, C.c_int, C.c_int, C.c_int, f32p, f32p, f32p, vp, C.c_int, vp]),
+    ("fdw_shot_line_batch_dtt", C.c_int, [vp, C.c_int, vp, C.c_ulonglong, C.c_int, C.c_int, f32p, f32p, f32p, vp, C.c_int, vp]),
     ("fdw_two_step_active", C.c_int, [vp]),
     ("fdw_steps_per_pass", C.c_int, [vp]),
     ("fdw_selftest", C.c_int, [vp]),

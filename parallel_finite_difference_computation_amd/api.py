@@ -127,6 +127,23 @@ def gather_misfit(resid):
     return m.value
 
 
+def gather_scale_v2(v2, nxb, gz, g):
+    """fdw_gather_scale_v2: out[ix][it] = g[ix][it] * v2[nxb+ix][gz], the data-side weight of the exact adjoint of BORN_DTT (fdwave.h, "DTT
+    imaging").  One fp32 product per word.  No device."""
+    v2, g = np.ascontiguousarray(v2, np.float32), np.ascontiguousarray(g, np.float32)
+    out = np.empty_like(g)
+    check(lib().fdw_gather_scale_v2(v2, v2.shape[0], v2.shape[1], int(nxb), int(gz), g.shape[0], g.shape[1], g, out))
+    return out
+
+
+def image_unscale_v2(v2, nxb, nzb, img):
+    """fdw_image_unscale_v2: out = img / v2 on the interior, the model-side weight of the exact adjoint of BORN_DTT.  No device."""
+    v2, img = np.ascontiguousarray(v2, np.float32), np.ascontiguousarray(img, np.float32)
+    out = np.empty_like(img)
+    check(lib().fdw_image_unscale_v2(v2, v2.shape[0], v2.shape[1], int(nxb), int(nzb), img.shape[0], img.shape[1], img, out))
+    return out
+
+
 def snap_dims(nx, nz, nt, every, dec=1):
     """fdw_snap_dims: (nframes, nxs, nzs) = (nt // every, ceil(nx / dec), ceil(nz / dec)); every < 1 or dec < 1 is refused.  No device."""
     a, b, c = C.c_int(), C.c_int(), C.c_int()
@@ -507,6 +524,63 @@ class FDWave:
         check(lib().fdw_born_shot_line_batch(self._h, nshots, None if v2_all is None else v2_all.ctypes.data, int(draw_offset), m.ctypes.data, int(kind), sz, gz,
                                              wav_all.ctypes.data, data.ctypes.data, data0.ctypes.data if want_background else None))
         return (data, data0) if want_background else data
+
+    # ---- DTT imaging (fdwave.h: the second-time-difference imaging condition, the adjoint of BORN_DTT) ----
+    def _dtt_out(self, lead, imloc, residual, want_resid, want_fields, want_illum, illum):
+        out = {"image": np.zeros(lead + (self.nx, self.nz), np.float32) if imloc is None else np.array(imloc, np.float32, order="C")}
+        if residual and want_resid:
+            out["resid"] = np.zeros(lead + (self.nx, self.nt), np.float32)
+        if want_fields:
+            out["P"], out["PP"] = np.zeros((self.nxe, self.nze), np.float32), np.zeros((self.nxe, self.nze), np.float32)
+        if want_illum:
+            shape = lead + (self.nx, self.nz)
+            out["illum"] = np.zeros(shape, np.float32) if illum is None else np.array(_f32(illum, shape), order="C")
+        return out, (lambda name: out[name].ctypes.data if name in out else None)
+
+    def shot_dtt(self, v2, sx, sz, gz, srce, d_obs, imloc=None, residual=False, want_resid=True, want_fields=False, want_illum=False, illum=None):
+        """shot() (v2=None: the resident model) whose backward loop images with the second time difference of the source field (fdwave.h,
+        fdw_shot_dtt); residual: migrate d_obs - d_mod as shot_residual() does -- the image is then the gradient of the BORN_DTT misfit.
+        Returns a dict: image, and resid / illum / P, PP as asked; all but the image equal the cross-correlation calls' bit for bit."""
+        out, ptr = self._dtt_out((), imloc, residual, want_resid, want_fields, want_illum, illum)
+        check(lib().fdw_shot_dtt(self._h, None if v2 is None else _f32(v2, (self.nxe, self.nze)).ctypes.data, sx, sz, gz, _f32(srce, (self.nt,)),
+                                 _f32(d_obs, (self.nx, self.nt)), out["image"], ptr("illum"), int(bool(residual)), ptr("resid"), ptr("P"), ptr("PP")))
+        return out
+
+    def shot_line_dtt(self, v2, sz, gz, wav, d_obs, imloc=None, residual=False, want_resid=True, want_fields=False, want_illum=False, illum=None):
+        """shot_dtt() driven by the line source wav[nx][nt] at depth sz (fdwave.h, fdw_shot_line_dtt)."""
+        out, ptr = self._dtt_out((), imloc, residual, want_resid, want_fields, want_illum, illum)
+        check(lib().fdw_shot_line_dtt(self._h, None if v2 is None else _f32(v2, (self.nxe, self.nze)).ctypes.data, sz, gz, _f32(wav, (self.nx, self.nt)),
+                                      _f32(d_obs, (self.nx, self.nt)), out["image"], ptr("illum"), int(bool(residual)), ptr("resid"), ptr("P"), ptr("PP")))
+        return out
+
+    def shot_batch_dtt(self, nshots, sx0, dsx, sz, gz, srce, d_obs, v2_all=None, draw_offset=0, imloc=None, residual=False, want_resid=True,
+                       want_illum=False, illum=None):
+        """`nshots` shot_dtt() shots, shots and models as shot_batch takes them (fdwave.h, fdw_shot_batch_dtt); batch_parts() says how the call
+        went.  Returns a dict: image [nshots][nx][nz], and resid / illum as asked."""
+        out, ptr = self._dtt_out((nshots,), imloc, residual, want_resid, False, want_illum, illum)
+        v2p = None if v2_all is None else _f32(v2_all, (nshots, self.nxe, self.nze)).ctypes.data
+        check(lib().fdw_shot_batch_dtt(self._h, nshots, v2p, int(draw_offset), sx0, dsx, sz, gz, _f32(srce, (self.nt,)),
+                                       _f32(d_obs, (nshots, self.nx, self.nt)), out["image"], ptr("illum"), int(bool(residual)), ptr("resid")))
+        return out
+
+    def shot_line_batch_dtt(self, nshots, sz, gz, wav_all, d_obs, v2_all=None, draw_offset=0, imloc=None, residual=False, want_resid=True,
+                            want_illum=False, illum=None):
+        """shot_batch_dtt() with the shots' line sources wav_all[nshots][nx][nt] at depth sz (fdwave.h, fdw_shot_line_batch_dtt)."""
+        out, ptr = self._dtt_out((nshots,), imloc, residual, want_resid, False, want_illum, illum)
+        v2p = None if v2_all is None else _f32(v2_all, (nshots, self.nxe, self.nze)).ctypes.data
+        check(lib().fdw_shot_line_batch_dtt(self._h, nshots, v2p, int(draw_offset), sz, gz, _f32(wav_all, (nshots, self.nx, self.nt)),
+                                            _f32(d_obs, (nshots, self.nx, self.nt)), out["image"], ptr("illum"), int(bool(residual)), ptr("resid")))
+        return out
+
+    def dev_back_iter_dtt(self, step_source, d_f1, d_f0, d_pr, d_ppr, d_v2, r0, r1, pp_twice, d_samples, gz, d_img, stream=None):
+        """dev_back_iter() with the DTT image term in place of the cross-correlation; step_source=0 (iterations 0 and 1) leaves d_img alone
+        (fdwave.h, fdw_dev_back_iter_dtt).  stream as dev_back_iter takes it."""
+        check(lib().fdw_dev_back_iter_dtt(self._h, int(step_source), d_f1, d_f0, d_pr, d_ppr, d_v2, r0, r1, int(pp_twice), d_samples, gz, d_img, stream))
+
+    def dev_dtt_image(self, d_fa, d_fb, d_fc, d_r, d_img, stream=None):
+        """One DTT image term on the interior cells: d_img += ((d_fa - d_fb) - (d_fb - d_fc)) * d_r (fdwave.h, fdw_dev_dtt_image): the tail of
+        a device caller's loop, behind dev_step(MODE_PLAIN).  stream as dev_back_iter takes it."""
+        check(lib().fdw_dev_dtt_image(self._h, d_fa, d_fb, d_fc, d_r, d_img, stream))
 
     # ---- line sources (fdwave.h: plane-wave and encoded-shot migration) ----
     def shot_line(self, v2, sz, gz, wav, d_obs, imloc=None, want_fields=False, want_illum=False, illum=None):

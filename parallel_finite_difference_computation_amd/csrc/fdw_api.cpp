@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "fdw_born.h"
+#include "fdw_dtt.h"
 #include "fdw_excimg.h"
 #include "fdw_internal.h"
 #include "fdw_kernels.h"
@@ -118,6 +119,7 @@ struct fdw_ctx {
     float* d_born_m = nullptr;     // fdw_born_shot: the reflectivity embedded into a zeroed field; allocated on first use
     float* d_born_rec0 = nullptr;  // ... the background gather [nt][nx] beside d_rec
     size_t born_rec0_cap = 0;
+    float* d_dtt_w = nullptr;      // DTT imaging without the fused kernel: F_{i-2} (-) F_{i-1} on C, taken before the source step overwrites F_{i-2}
     float* d_born_w = nullptr;     // Born modelling without the fused kernel, FDW_BORN_DTT: (A - B) of the background on the interior cells
     float* b_born_rec0 = nullptr;  // fdw_born_shot_batch with data0: the shots' background gathers [shots][nt][nx]; allocated on first use
     size_t b_born_rec0_cap = 0;
@@ -395,7 +397,7 @@ extern "C" void fdw_destroy(fdw_ctx* c)
                      c->fld[4], c->fld[5], c->fld[6], c->fld[7], c->fld[8], c->fld[9], c->d_v2, c->d_img, c->d_illum, c->d_srce, c->d_dobs, c->d_rec,
                      c->d_vp, c->d_vpe, (float*)c->d_draws, (float*)c->d_jump, c->bfld[0], c->bfld[1], c->bfld[2], c->bfld[3],
                      c->bfld[4], c->bfld[5], c->bfld[6], c->bfld[7], c->b_v2, c->b_img, c->b_dobs, c->b_illum, c->b_rec, c->b_wav, c->d_raw, c->d_wav, c->d_snap[0], c->d_snap[1], c->d_snap[2], c->d_amp, (float*)c->d_texc, c->d_exc, (float*)c->d_peak,
-                     c->d_born_m, c->d_born_rec0, c->d_born_w, c->b_born_rec0};
+                     c->d_born_m, c->d_born_rec0, c->d_born_w, c->b_born_rec0, c->d_dtt_w};
     for (float* b : bufs)
         if (b) (void)hipFree(b);
     if (c->stream) (void)hipStreamDestroy(c->stream);
@@ -646,12 +648,24 @@ static int static_receiver_rows(fdw_ctx* c, int x, int n, int r1, float* field, 
     return FDW_OK;
 }
 
+// the cell set C of the Born scatter and of DTT imaging on a full-grid context: rows [x0, x1), columns [z0, z1)
+struct BornCells {
+    int x0, x1, z0, z1;
+};
+static BornCells born_cells(const fdw_ctx* c)
+{
+    return BornCells{c->prm.nxb, std::min(c->prm.nxb + c->nx, c->xlim), c->prm.nzb, std::min(c->prm.nzb + c->nz, c->zlim)};
+}
+
 struct BackExtra {           // what the receiver / imaging variants of the one-step and two-step kernels need on top of the forward ones
     const float* inj2 = nullptr;      // two-step: the receiver samples of iteration it+1
     const float* psrc_a = nullptr;    // the source field the new receiver field is imaged against (two-step: iteration it's)
     const float* psrc_b = nullptr;    // two-step: iteration it+1's
     float* img = nullptr;
     float* fpp = nullptr;             // BACK: the older source field, stepped in place by the same launch
+    // second-time-difference imaging (fdwave.h, "DTT imaging"):
+    bool no_img = false;              // RECV: the receiver step and its injection alone -- the image is neither read nor written
+    bool dtt = false;                 // BACK: the DTT value of the imaging epilogue (FDW_MODE_BACK_DTT)
 };
 
 // One launch of the one-step kernels on rows [r0, r1).  f (a view): the source, trace row and accumulators of a FWD / DD_FWD / MOD step, the
@@ -662,7 +676,10 @@ static int step_impl(fdw_ctx* c, int mode, const float* d_p, float* d_pp, const 
     const bool lap = (mode == FDW_MODE_LAP);
     if (!d_p || !d_pp) return fail(FDW_EINVAL, "step: field pointer is NULL");
     if (!lap && !d_v2) return fail(FDW_EINVAL, "step: v2 is NULL");
-    if ((mode == FDW_MODE_RECV || mode == FDW_MODE_DD_RECV || mode == FDW_MODE_BACK) && (!bk.psrc_a || !bk.img || !f.samples)) return fail(FDW_EINVAL, "step: RECV needs d_inj, d_psrc and d_img");
+    if ((mode == FDW_MODE_RECV || mode == FDW_MODE_DD_RECV || mode == FDW_MODE_BACK) && !(bk.no_img && mode == FDW_MODE_RECV) && (!bk.psrc_a || !bk.img || !f.samples))
+        return fail(FDW_EINVAL, "step: RECV needs d_inj, d_psrc and d_img");
+    if (bk.no_img && (mode != FDW_MODE_RECV || !f.samples)) return fail(FDW_EINVAL, "step: the receiver step without imaging is a RECV step with d_inj");
+    if (bk.dtt && mode != FDW_MODE_BACK) return fail(FDW_EINVAL, "step: the DTT epilogue belongs to a BACK step");
     if (mode == FDW_MODE_BACK && (!bk.fpp || bk.fpp == d_pp || bk.fpp == d_p || bk.psrc_a == d_pp || c->h > kMaxFastHalfOrder || c->use_generic))
         return fail(FDW_EINVAL, "step: BACK needs the older source field as a fourth, distinct buffer and an order <= 8");
     if (mode < FDW_MODE_FWD || mode > FDW_MODE_BACK) return fail(FDW_EINVAL, "step: unknown mode %d", mode);
@@ -711,15 +728,23 @@ static int step_impl(fdw_ctx* c, int mode, const float* d_p, float* d_pp, const 
         a.v2_bstride = mode == FDW_MODE_MOD ? 0 : a.bstride;                       // mod_main models every shot on one velocity model (M:140-174)
         a.rec_bstride = (long long)c->nx * c->batch_nt;
     }
+    // DTT imaging: a receiver step that leaves the image alone is the line-source step on the receiver rows (damping, leap-frog, one sample
+    // per row after it: the same instantiation, the same bytes in pp); the fused iteration has a mode of its own, which images on C only
+    const int kmode = bk.no_img ? FDW_MODE_FWD_LINE : (bk.dtt ? FDW_MODE_BACK_DTT : v.kmode);
+    if (bk.dtt) {
+        const BornCells C = born_cells(c);
+        a.rec_x0 = C.x0; a.rec_n = std::max(0, C.x1 - C.x0);
+        a.img_z1 = C.z1; a.exc_key = born_key(0, C.z0);
+    }
     hipError_t e;
     if (c->h <= kMaxFastHalfOrder && !c->use_generic) {
         fill_geometry(c, a, a.r1 - a.r0, std::max(c->nbatch, 1));
-        e = launch_step_fast(a, c->h, v.kmode, effective_prefetch(c), s);
+        e = launch_step_fast(a, c->h, kmode, effective_prefetch(c), s);
     } else {
         if (mode >= FDW_MODE_MOD) return fail(FDW_EINVAL, "step: mode %d has no generic-order kernel", mode);
         // no generic-order illumination kernel: the plain step, then illum += pp (*) pp over the cells it updated
         // (recording too: the generic recording step, then the same add)
-        e = launch_step_generic(a, c->h, v.generic, s);
+        e = launch_step_generic(a, c->h, bk.no_img ? FDW_MODE_FWD_LINE : v.generic, s);
         if (e == hipSuccess && v.illum) e = launch_illum_add(d_pp, f.illum, c->pitch, a.r0, a.r1, c->upd_z1, s);
         // no generic-order excitation kernel either: the plain step, then the compare-and-select / the pick over the cells it updated
         if (e == hipSuccess && f.exc != Exc::none)
@@ -727,9 +752,9 @@ static int step_impl(fdw_ctx* c, int mode, const float* d_p, float* d_pp, const 
                                    : launch_exc_select(d_pp, f.exc_arr, f.texc, c->pitch, a.r0, a.r1, c->upd_z1, f.exc_key, s);
     }
     if (e != hipSuccess) return fail(FDW_EHIP, "kernel launch failed: %s", hipGetErrorString(e));
-    if ((mode == FDW_MODE_RECV || mode == FDW_MODE_BACK) && r1 > c->upd_x1)
-        return static_receiver_rows(c, a.inj_x, a.inj_n, std::min(r1, c->nxl), d_pp, a.inj, mode == FDW_MODE_BACK ? bk.fpp : bk.psrc_a, bk.img, f.sz, a.img_z1,
-                                    s);
+    if ((mode == FDW_MODE_RECV || mode == FDW_MODE_BACK) && r1 > c->upd_x1)      // (DTT imaging: no static row lies in C -- the injection alone, an empty column range)
+        return static_receiver_rows(c, a.inj_x, a.inj_n, std::min(r1, c->nxl), d_pp, a.inj, mode == FDW_MODE_BACK ? bk.fpp : bk.psrc_a, bk.img, f.sz,
+                                    (bk.no_img || bk.dtt) ? c->prm.nzb : a.img_z1, s);
     return FDW_OK;
 }
 
@@ -772,6 +797,87 @@ extern "C" int fdw_dev_back_iter(fdw_ctx* c, int step_source, const float* d_f1,
     if (c->prm.dialect != FDW_DIALECT_RTM) return fail(FDW_ESTATE, "fdw_dev_back_iter belongs to the RTM dialect");
     if (!d_f1 || !d_pr || !d_ppr || !d_v2 || !d_samples || !d_img || (step_source && !d_f0)) return fail(FDW_EINVAL, "back_iter: NULL buffer");
     return back_iter(c, step_source, d_f1, d_f0, d_pr, d_ppr, d_v2, r0, r1, pp_twice, d_samples, gz, d_img, pick_stream(c, stream));
+}
+
+// ---- second-time-difference imaging (definitions in fdwave.h, "DTT imaging") ----
+static bool dtt_fused(const fdw_ctx* c) { return c->h <= kMaxFastHalfOrder && !c->use_generic && !c->no_fused_back; }
+
+// one term on C: img = img (+) ((a (-) b) (-) (b (-) c)) (*) r; pre: a holds a (-) b already.  Inside a batch: every shot.
+static int dtt_image(fdw_ctx* c, const float* d_a, const float* d_b, const float* d_c, const float* d_r, float* d_img, int pre, hipStream_t s)
+{
+    const BornCells C = born_cells(c);
+    hipError_t e = launch_dtt_image(d_a, d_b, d_c, d_r, d_img, pre, c->pitch, C.x0, C.x1, C.z0, C.z1, c->nbatch, (long long)field_elems(c), s);
+    if (e != hipSuccess) return fail(FDW_EHIP, "DTT image launch failed: %s", hipGetErrorString(e));
+    return FDW_OK;
+}
+
+// the scratch field of the unfused arrangement: every word read is written first (no memset, nothing to wait for)
+static int ensure_dtt_scratch(fdw_ctx* c)
+{
+    if (dtt_fused(c) || c->d_dtt_w) return FDW_OK;
+    hipError_t e = hipMalloc((void**)&c->d_dtt_w, field_elems(c) * sizeof(float));
+    if (e != hipSuccess) return fail(FDW_ENOMEM, "hipMalloc(%zu bytes) failed: %s", field_elems(c) * sizeof(float), hipGetErrorString(e));
+    return FDW_OK;
+}
+
+// One iteration of the DTT backward loop: back_iter's fields, the image term q_{i-2} (*) r^{i-1} in place of the cross-correlation
+// (step_source != 0), no image at all in iterations 0 and 1.
+static int back_iter_dtt(fdw_ctx* c, int step_source, const float* d_f1, float* d_f0, const float* d_pr, float* d_ppr, const float* d_v2, int r0, int r1,
+                         int pp_twice, const float* d_samples, int gz, float* d_img, hipStream_t s)
+{
+    const FwdView rs = receiver_samples(d_samples, gz);
+    BackExtra bk;
+    if (!step_source) {
+        bk.no_img = true;
+        return step_impl(c, FDW_MODE_RECV, d_pr, d_ppr, d_v2, r0, r1, pp_twice, rs, bk, s);
+    }
+    if (dtt_fused(c)) {
+        bk.psrc_a = d_f1; bk.img = d_img; bk.fpp = d_f0; bk.dtt = true;
+        return step_impl(c, FDW_MODE_BACK, d_pr, d_ppr, d_v2, r0, r1, pp_twice, rs, bk, s);
+    }
+    // in four launches: the first difference while F_{i-2} still stands, the source step over it, the term while d_ppr still holds r^{i-1},
+    // the receiver step
+    FDW_TRY(ensure_dtt_scratch(c));
+    const BornCells C = born_cells(c);
+    hipError_t e = launch_born_diff(d_f0, d_f1, c->d_dtt_w, c->pitch, C.x0, C.x1, C.z0, C.z1, s);
+    if (e != hipSuccess) return fail(FDW_EHIP, "DTT difference launch failed: %s", hipGetErrorString(e));
+    FDW_TRY(step_impl(c, FDW_MODE_PLAIN, d_f1, d_f0, d_v2, r0, r1, 0, FwdView{}, BackExtra{}, s));
+    FDW_TRY(dtt_image(c, c->d_dtt_w, d_f1, d_f0, d_ppr, d_img, 1, s));
+    bk.no_img = true;
+    return step_impl(c, FDW_MODE_RECV, d_pr, d_ppr, d_v2, r0, r1, pp_twice, rs, bk, s);
+}
+
+// what the two device entry points refuse before anything is enqueued
+static int check_dtt_ctx(const fdw_ctx* c, const char* who)
+{
+    if (c->prm.dialect != FDW_DIALECT_RTM) return fail(FDW_ESTATE, "%s: DTT imaging belongs to the RTM dialect (the sibling's dialects do not combine with it)", who);
+    if (!is_full_grid(c)) return fail(FDW_ESTATE, "%s: DTT imaging: full-grid contexts only (slab contexts do not combine with it)", who);
+    if (c->nbatch > 1) return fail(FDW_ESTATE, "%s: not inside a batch of shots", who);
+    return FDW_OK;
+}
+
+extern "C" int fdw_dev_back_iter_dtt(fdw_ctx* c, int step_source, const float* d_f1, float* d_f0, const float* d_pr, float* d_ppr, const float* d_v2,
+                                     int r0, int r1, int pp_twice, const float* d_samples, int gz, float* d_img, void* stream)
+{
+    if (!c) return fail(FDW_EINVAL, "ctx is NULL");
+    FDW_TRY(check_dtt_ctx(c, "fdw_dev_back_iter_dtt"));
+    if (!d_f1 || !d_pr || !d_ppr || !d_v2 || !d_samples || !d_img || (step_source && !d_f0)) return fail(FDW_EINVAL, "fdw_dev_back_iter_dtt: NULL buffer");
+    if (step_source && (d_f0 == d_f1 || d_f0 == d_pr || d_f0 == d_ppr || d_f1 == d_ppr || d_img == d_f0 || d_img == d_ppr))
+        return fail(FDW_EINVAL, "fdw_dev_back_iter_dtt: the source pair, the receiver pair and the image are distinct arrays");
+    if (r0 != 0 || r1 != c->nxl) return fail(FDW_EINVAL, "fdw_dev_back_iter_dtt: rows [%d,%d) are not the whole grid [0,%d)", r0, r1, c->nxl);
+    if (gz < 0 || gz >= c->prm.nze) return fail(FDW_EINVAL, "fdw_dev_back_iter_dtt: receiver depth %d outside the grid", gz);
+    HIP_TRY(hipSetDevice(c->device));
+    if (step_source) FDW_TRY(ensure_dtt_scratch(c));
+    return back_iter_dtt(c, step_source, d_f1, d_f0, d_pr, d_ppr, d_v2, r0, r1, pp_twice, d_samples, gz, d_img, pick_stream(c, stream));
+}
+
+extern "C" int fdw_dev_dtt_image(fdw_ctx* c, const float* d_fa, const float* d_fb, const float* d_fc, const float* d_r, float* d_img, void* stream)
+{
+    if (!c) return fail(FDW_EINVAL, "ctx is NULL");
+    FDW_TRY(check_dtt_ctx(c, "fdw_dev_dtt_image"));
+    if (!d_fa || !d_fb || !d_fc || !d_r || !d_img) return fail(FDW_EINVAL, "fdw_dev_dtt_image: NULL buffer");
+    HIP_TRY(hipSetDevice(c->device));
+    return dtt_image(c, d_fa, d_fb, d_fc, d_r, d_img, 0, pick_stream(c, stream));
 }
 
 extern "C" int fdw_dev_laplacian(fdw_ctx* c, const float* d_p, float* d_lap, void* stream)
@@ -1795,7 +1901,9 @@ static int image_to_host(fdw_ctx* c, float* imloc, const float* d_src)
 // sn (fdw_shot_snaps; SnapPlan{}: none): iterations k = nt - L of the snapshot levels L are STOPS: no pass of several iterations reaches across one (the
 // family is chosen by the iterations left until the next stop; every family equals the one-step iteration bit for bit, so the image
 // does not change), and after iteration k the frames of F_k and r^{k+1} go into the frame stores at index L / every - 1.
-static int back_loop(fdw_ctx* c, float* const src[4], float* const rcv[4], int gz, int nsteps, const SnapPlan& sn)
+// dtt (fdw_shot_dtt and its kin): single iterations of back_iter_dtt -- no pairs, no pipeline -- and the tail of two source-only
+// reconstructions into the spare source buffers with their two image terms (fdwave.h, "DTT imaging").
+static int back_loop(fdw_ctx* c, float* const src[4], float* const rcv[4], int gz, int nsteps, const SnapPlan& sn, bool dtt = false)
 {
     FDW_RANGE("fdw: backward loop + imaging (fd_back)");
     const int nt = c->prm.nt;
@@ -1804,8 +1912,9 @@ static int back_loop(fdw_ctx* c, float* const src[4], float* const rcv[4], int g
     int f1 = 0, f0 = 1;          // indices into src of F_{k-1} (newer) and F_{k-2}: before iteration 2 these are snap0, snap1
     int rn = 0, ro = 1;          // indices into rcv of r^k (d_pr) and r^{k-1} (d_ppr)
     int it = 0;
-    const bool pairs = two_step_pays(c);
-    const bool pipe = fdw_back_pipe_active(c) && c->nbatch <= 1;
+    const bool pairs = two_step_pays(c) && !dtt;
+    const bool pipe = fdw_back_pipe_active(c) && c->nbatch <= 1 && !dtt;
+    if (dtt) FDW_TRY(ensure_dtt_scratch(c));
     std::vector<int> stops;      // ascending iterations after which frames are taken
     if (sn.store[1] || sn.store[2])
         for (int j = sn.nframes - 1; j >= 0; j--)
@@ -1847,8 +1956,8 @@ static int back_loop(fdw_ctx* c, float* const src[4], float* const rcv[4], int g
             it += 2;
         } else {
             // iteration 0 images u^nt, iteration 1 u^{nt-1}; from iteration 2 on F_k overwrites F_{k-2}
-            FDW_TRY(back_iter(c, it >= 2, it == 0 ? src[f0] : src[f1], src[f0], rcv[rn], rcv[ro], c->d_v2, 0, c->nxl, it > 0, samples(it), gz,
-                              c->d_img, c->stream));
+            FDW_TRY((dtt ? back_iter_dtt : back_iter)(c, it >= 2, it == 0 ? src[f0] : src[f1], src[f0], rcv[rn], rcv[ro], c->d_v2, 0, c->nxl, it > 0, samples(it), gz,
+                                                      c->d_img, c->stream));
             if (it >= 2) std::swap(f1, f0);
             std::swap(rn, ro);
             it += 1;
@@ -1859,6 +1968,22 @@ static int back_loop(fdw_ctx* c, float* const src[4], float* const rcv[4], int g
             const size_t off = (size_t)((nt - k) / sn.every - 1) * sn.frame_elems();
             if (sn.store[1]) FDW_TRY(snapshot(c, k == 0 ? src[1] : src[f1], sn.dec, sn.store[1] + off, c->stream));
             if (sn.store[2]) FDW_TRY(snapshot(c, rcv[rn], sn.dec, sn.store[2] + off, c->stream));
+        }
+    }
+    if (dtt && nsteps >= 1) {
+        // the tail: terms k = nsteps-2 (with r^{nsteps-1}) and k = nsteps-1 (with r^{nsteps}), in that order; nsteps = 1: term 0 alone.  Each
+        // needs one more level of the source field: the plain leap-frog (R:317-318) into a spare buffer, the three levels kept side by side.
+        int o[2];
+        spare_pair(f1, f0, &o[0], &o[1]);
+        const size_t bytes = field_elems(c) * (size_t)std::max(c->nbatch, 1) * sizeof(float);
+        const float* lvl[4] = {src[f0], src[f1], nullptr, nullptr};      // F_{nsteps-2}, F_{nsteps-1} (nsteps = 1: the snapshots F_0, F_1)
+        const float* r[2] = {rcv[ro], rcv[rn]};
+        const int nterms = nsteps >= 2 ? 2 : 1;
+        for (int t = 0; t < nterms; t++) {
+            HIP_TRY(hipMemcpyAsync(src[o[t]], lvl[t], bytes, hipMemcpyDeviceToDevice, c->stream));
+            FDW_TRY(step_impl(c, FDW_MODE_PLAIN, lvl[t + 1], src[o[t]], c->d_v2, 0, c->nxl, 0, FwdView{}, BackExtra{}, c->stream));
+            lvl[t + 2] = src[o[t]];
+            FDW_TRY(dtt_image(c, lvl[t], lvl[t + 1], lvl[t + 2], r[nterms == 2 ? t : 1], c->d_img, 0, c->stream));
         }
     }
     return FDW_OK;
@@ -1912,6 +2037,7 @@ struct ShotExtras {      // what a shot does beyond fdw_shot's; of a batch every
     SnapPlan snaps;            // one shot: the snapshot plan of fdw_shot_snaps (frame stores already allocated)
     bool residual = false;     // fdw_shot_residual: the forward loop records the modelled gather (c->d_rec; a batch: b_rec [shot][nt][nx]), which turns
     float* resid = nullptr;    // the data gather into d_obs - d_mod in place before the backward loop reads it; resid: NULL, or [nx][nt] that difference
+    bool dtt = false;          // fdw_shot_dtt and its kin: the backward loop images with the second time difference of the source field (back_loop)
     ShotExtras of_shot(size_t b, size_t ni, size_t ng) const { ShotExtras x = *this; if (illum) x.illum += b * ni; if (resid) x.resid += b * ng; return x; }
 };
 // the uploaded source as the forward loop takes it: the wavelet in c->d_srce, or (line) the gathers transposed to [shot][nt][nx] in d_wav
@@ -1950,7 +2076,7 @@ static int shot_impl(fdw_ctx* c, const float* v2, int sx, int sz, int gz, const 
     float* src[4];
     source_buffers(c, ip, ipp, src);
     if ((rc = zero_fields(c, c->fld + 4, 2))) return rc;
-    if ((rc = back_loop(c, src, c->fld + 4, gz, nt, x.snaps))) return rc;
+    if ((rc = back_loop(c, src, c->fld + 4, gz, nt, x.snaps, x.dtt))) return rc;
     if ((rc = image_to_host(c, imloc, c->d_img))) return rc;
     HIP_TRY(hipStreamSynchronize(c->stream));
     return FDW_OK;
@@ -2086,15 +2212,6 @@ extern "C" int fdw_record_shot(fdw_ctx* c, const float* v2, int sx, int sz, int 
 // Born modelling (definitions in fdwave.h)
 // ------------------------------------------------------------------------------------------------
 static bool born_fused(const fdw_ctx* c) { return c->h <= kMaxFastHalfOrder && !c->use_generic && !c->no_born_fused; }
-
-// the cell set C of the scatter on a full-grid context: rows [x0, x1), columns [z0, z1)
-struct BornCells {
-    int x0, x1, z0, z1;
-};
-static BornCells born_cells(const fdw_ctx* c)
-{
-    return BornCells{c->prm.nxb, std::min(c->prm.nxb + c->nx, c->xlim), c->prm.nzb, std::min(c->prm.nzb + c->nz, c->zlim)};
-}
 
 // what fdw_dev_born_steps and fdw_born_shot ask of their arguments beyond the pointers
 static int check_born_args(const fdw_ctx* c, const char* who, int kind, int sx, int sz, int gz)
@@ -3260,7 +3377,7 @@ static int shot_batch_impl(fdw_ctx* c, const char* who, int nshots, const float*
             if ((rc = fdw_dev_taper_finalize(c, c->fld[ip] + b * fe, s))) return rc;
         float* src[4];
         source_buffers(c, ip, ipp, src);
-        if ((rc = back_loop(c, src, c->fld + 4, gz, nt, SnapPlan{}))) return rc;
+        if ((rc = back_loop(c, src, c->fld + 4, gz, nt, SnapPlan{}, x.dtt))) return rc;
     }
     if (x.resid && (rc = gathers_to_host(c, c->b_dobs, nshots, x.resid))) return rc;
     if (x.illum && (rc = batch_interiors_to_host(c, x.illum, c->b_illum, nshots))) return rc;
@@ -3652,4 +3769,70 @@ extern "C" int fdw_model_shot_batch(fdw_ctx* c, int nshots, const float* vel2, i
     HIP_TRY(hipMemcpyAsync(data, c->d_raw, ng * nshots * sizeof(float), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     return FDW_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// shots that image with the second time difference of the source field (definitions in fdwave.h, "DTT imaging")
+// ------------------------------------------------------------------------------------------------
+// what every DTT shot entry point refuses before anything is enqueued; the ShotExtras of the call
+static int dtt_shot_extras(fdw_ctx* c, const char* who, float* illum, int residual, float* resid, int gz, ShotExtras* x)
+{
+    FDW_TRY(check_dtt_ctx(c, who));
+    if (residual != 0 && residual != 1) return fail(FDW_EINVAL, "%s: residual=%d is neither 0 nor 1", who, residual);
+    if (resid && !residual) return fail(FDW_EINVAL, "%s: resid is the output of residual=1", who);
+    if (residual) FDW_TRY(check_record_depth(c, gz));
+    x->dtt = true; x->illum = illum; x->residual = residual != 0; x->resid = resid;
+    return FDW_OK;
+}
+
+extern "C" int fdw_shot_dtt(fdw_ctx* c, const float* v2, int sx, int sz, int gz, const float* srce, const float* d_obs, float* imloc, float* illum,
+                            int residual, float* resid, float* P, float* PP)
+{
+    if (!c) return fail(FDW_EINVAL, "ctx is NULL");
+    ShotExtras x;
+    FDW_TRY(dtt_shot_extras(c, "fdw_shot_dtt", illum, residual, resid, gz, &x));
+    FDW_TRY(has_model(c, v2));
+    if (!srce || !d_obs || !imloc) return fail(FDW_EINVAL, "fdw_shot_dtt: NULL argument");
+    end_residency(c, v2);
+    return shot_impl(c, v2, sx, sz, gz, srce, d_obs, imloc, P, PP, x);
+}
+
+extern "C" int fdw_shot_line_dtt(fdw_ctx* c, const float* v2, int sz, int gz, const float* wav, const float* d_obs, float* imloc, float* illum, int residual,
+                                 float* resid, float* P, float* PP)
+{
+    if (!c) return fail(FDW_EINVAL, "ctx is NULL");
+    ShotExtras x;
+    FDW_TRY(dtt_shot_extras(c, "fdw_shot_line_dtt", illum, residual, resid, gz, &x));
+    FDW_TRY(has_model(c, v2));
+    if (!wav || !d_obs || !imloc) return fail(FDW_EINVAL, "fdw_shot_line_dtt: NULL argument");
+    FDW_TRY(check_line_args(c, "fdw_shot_line_dtt", sz, gz, residual != 0, illum != nullptr, residual != 0));
+    end_residency(c, v2);
+    x.line = true;
+    return shot_impl(c, v2, -1, sz, gz, wav, d_obs, imloc, P, PP, x);
+}
+
+// the batches: fdw_shot_batch_residual's parts (eleven fields per shot, one more with illum; one gather more with residual, one more for a line)
+extern "C" int fdw_shot_batch_dtt(fdw_ctx* c, int nshots, const float* v2_all, unsigned long long draw_offset, int sx0, int dsx, int sz, int gz,
+                                  const float* srce, const float* d_obs, float* imloc, float* illum, int residual, float* resid)
+{
+    if (!c) return fail(FDW_EINVAL, "ctx is NULL");
+    ShotExtras x;
+    FDW_TRY(dtt_shot_extras(c, "fdw_shot_batch_dtt", illum, residual, resid, gz, &x));
+    if (!srce || !d_obs || !imloc) return fail(FDW_EINVAL, "fdw_shot_batch_dtt: NULL argument");
+    if (nshots < 1) return fail(FDW_EINVAL, "nshots=%d", nshots);
+    return shot_batch_in_parts(c, "fdw_shot_batch_dtt", nshots, v2_all, draw_offset, sx0, dsx, sz, gz, srce, d_obs, imloc, x, illum ? 12 : 11, residual ? 1 : 0);
+}
+
+extern "C" int fdw_shot_line_batch_dtt(fdw_ctx* c, int nshots, const float* v2_all, unsigned long long draw_offset, int sz, int gz, const float* wav_all,
+                                       const float* d_obs, float* imloc, float* illum, int residual, float* resid)
+{
+    if (!c) return fail(FDW_EINVAL, "ctx is NULL");
+    ShotExtras x;
+    FDW_TRY(dtt_shot_extras(c, "fdw_shot_line_batch_dtt", illum, residual, resid, gz, &x));
+    if (!wav_all || !d_obs || !imloc) return fail(FDW_EINVAL, "fdw_shot_line_batch_dtt: NULL argument");
+    FDW_TRY(check_line_args(c, "fdw_shot_line_batch_dtt", sz, gz, residual != 0, illum != nullptr, true));
+    if (nshots < 1) return fail(FDW_EINVAL, "nshots=%d", nshots);
+    x.line = true;
+    return shot_batch_in_parts(c, "fdw_shot_line_batch_dtt", nshots, v2_all, draw_offset, -1, 0, sz, gz, wav_all, d_obs, imloc, x, illum ? 12 : 11,
+                               residual ? 2 : 1);
 }

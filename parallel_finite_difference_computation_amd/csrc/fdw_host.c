@@ -288,3 +288,25 @@ int fdw_encode_line_source(int nshots, const int *src_ix, const int *lag, const 
     }
     return FDW_OK;
 }
+
+/* The weights of the exact adjoint of DTT Born modelling (fdwave.h, "DTT imaging"): one fp32 operation per word, out may be the input.
+ * out[ix][it] = g[ix][it] * v2[nxb+ix][gz] */
+int fdw_gather_scale_v2(const float *v2, int nxe, int nze, int nxb, int gz, int nx, int nt, const float *g, float *out)
+{
+    if (!v2 || !g || !out || nx < 0 || nt < 0 || nxb < 0 || nze < 1 || gz < 0 || gz >= nze || nxb + nx > nxe) return FDW_EINVAL;
+    for (int ix = 0; ix < nx; ix++) {
+        const float w = v2[(size_t)(nxb + ix) * (size_t)nze + (size_t)gz];
+        for (int it = 0; it < nt; it++) out[(size_t)ix * (size_t)nt + (size_t)it] = g[(size_t)ix * (size_t)nt + (size_t)it] * w;
+    }
+    return FDW_OK;
+}
+
+/* out[ix][iz] = img[ix][iz] / v2[nxb+ix][nzb+iz] */
+int fdw_image_unscale_v2(const float *v2, int nxe, int nze, int nxb, int nzb, int nx, int nz, const float *img, float *out)
+{
+    if (!v2 || !img || !out || nx < 0 || nz < 0 || nxb < 0 || nzb < 0 || nxb + nx > nxe || nzb + nz > nze) return FDW_EINVAL;
+    for (int ix = 0; ix < nx; ix++)
+        for (int iz = 0; iz < nz; iz++)
+            out[(size_t)ix * (size_t)nz + (size_t)iz] = img[(size_t)ix * (size_t)nz + (size_t)iz] / v2[(size_t)(nxb + ix) * (size_t)nze + (size_t)(nzb + iz)];
+    return FDW_OK;
+}

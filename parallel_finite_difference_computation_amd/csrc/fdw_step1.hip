@@ -7,6 +7,7 @@
 //   FDW_TU 2 (fdw_step1_fast.o)  the RTM dialect with FAST numerics (fdw_device.h)
 #include "fdw_device.h"
 #include "fdw_born.h"
+#include "fdw_dtt.h"
 
 #pragma clang fp contract(off)
 
@@ -38,6 +39,9 @@ namespace fdw {
 //           (sv.psrc = du_p read only, sv.fpp = du_pp overwritten), which gets the damping and no injection; the row of the reflectivity m
 //           (a.img, only read) rides the pointwise queue; on the interior cells du_new = du_new (+) m (*) q, with q the background's new
 //           value (kind 0, fdw_born.h) or its second time difference (1) from the registers the leap-frog just used; then the trace samples
+//   DTT     second-time-difference imaging (fdwave.h, "DTT imaging"; fdw_step_back_dtt_kernel), a value of the IMG epilogue of BACK: on the
+//           cells C img += ((F_old (-) F_cur) (-) (F_cur (-) F_new)) (*) the receiver field the launch OVERWRITES (its entry words), from
+//           registers the two leap-frogs already hold; every other word of the image row is stored back with the bits it came with
 // block = 256 threads = 4 independent waves (no LDS, no barrier).
 //
 // ONE code path for every tile.  Every global load of the march is unconditional (addresses are
@@ -63,7 +67,7 @@ struct ShotView {
 };
 
 template <int H, bool TAPER, int INJ, bool IMG, bool LAPONLY, int PF, bool DD = false, bool BACK = false, int NUM = 0, bool REC = false, bool ILL = false,
-          int EXC = 0, bool BORN = false>
+          int EXC = 0, bool BORN = false, bool DTT = false>
 __device__ __forceinline__ void march(const StepArgs& a, const ShotView& sv, const int lane, const int zs, const int xa, const int xe)
 {
     // BACK: one whole backward iteration of fd_back (R:317-329) in a single pass: the source field is reconstructed in a second
@@ -99,11 +103,11 @@ __device__ __forceinline__ void march(const StepArgs& a, const ShotView& sv, con
     // REC: the lane whose float4 holds column rec_z records element rec_z & 3 of its new row (strips do not overlap: one lane in the grid)
     const bool rec_lane = (REC || BORN) && (z0 >> 2) == (a.rec_z >> 2);
     constexpr bool TWO = BACK || BORN;                      // a second field is stepped side by side in a ring of its own
-    const bool born_here = BORN && (zs < a.img_z1) && (zs + 256 > born_key_z0(a.exc_key));      // wave-uniform: the strip holds interior columns
+    const bool born_here = (BORN || DTT) && (zs < a.img_z1) && (zs + 256 > born_key_z0(a.exc_key));      // wave-uniform: the strip holds interior columns
 
     // per-lane column masks and damping factors
     bool mlap[4], mupd[4], znc[4], znh[4], ihit[4];
-    [[maybe_unused]] bool mborn[4];                         // BORN: the interior columns (the scatter's)
+    [[maybe_unused]] bool mborn[4];                         // BORN: the interior columns (the scatter's); DTT: the imaged columns
     float tzc[4], tzh[4];
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
@@ -111,7 +115,7 @@ __device__ __forceinline__ void march(const StepArgs& a, const ShotView& sv, con
         mlap[e] = (z >= a.lap_z0) && (z < a.lap_z1);
         mupd[e] = z < a.upd_z1;
         ihit[e] = (z == a.inj_z);
-        if constexpr (BORN) mborn[e] = (z >= born_key_z0(a.exc_key)) && (z < a.img_z1);
+        if constexpr (BORN || DTT) mborn[e] = (z >= born_key_z0(a.exc_key)) && (z < a.img_z1);
         znc[e] = znh[e] = false;
         tzc[e] = tzh[e] = 1.0f;
     }
@@ -335,6 +339,7 @@ __device__ __forceinline__ void march(const StepArgs& a, const ShotView& sv, con
                 }
             }
             f4 fres;
+            [[maybe_unused]] f4 fc_dtt;                             // DTT: the centre row of the source ring (F_{k+1})
             if constexpr (TWO) {
                 // ---- the source field's own step on the same row: kernel_lap + kernel_time, no damping, no injection (R:317-318) ----
                 // BORN: the scattered field's, with the damping of the forward step (what enters the computation this step) and no injection
@@ -348,6 +353,7 @@ __device__ __forceinline__ void march(const StepArgs& a, const ShotView& sv, con
                     }
                 }
                 const f4 fc = fring[(U + H) % R];
+                if constexpr (DTT) fc_dtt = fc;
                 f4 flft, frgt;
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
@@ -382,7 +388,18 @@ __device__ __forceinline__ void march(const StepArgs& a, const ShotView& sv, con
                     }
                 }
             }
-            if constexpr (IMG) {
+            if constexpr (IMG && DTT) {
+                // the second time difference of the source field meets r^{k+1}, the word this launch overwrites: no cell of C is damped, so
+                // ppt is that word (a damping factor there is exactly 1.0f); three subtractions, product and sum rounded one by one; a select
+                // elsewhere, so that the border cells of the launch extents keep their bits
+                const bool dtt_row = born_here && (unsigned)(r - a.rec_x0) < (unsigned)a.rec_n;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const float q = (fqpp[Q].v[e] - fc_dtt.v[e]) - (fc_dtt.v[e] - fres.v[e]);
+                    const float im = qim[Q].v[e] + q * ppt.v[e];
+                    imr.v[e] = (dtt_row && mborn[e]) ? im : qim[Q].v[e];
+                }
+            } else if constexpr (IMG) {
                 // kernel_img (R:133-144) correlates with the NEW receiver field; the sibling's rtm_main stores the CURRENT one
                 // (rwf[it] = P, rtm_main.cpp:211-215), an interior point of which carries damping factors of exactly 1.0f
 #pragma unroll
@@ -573,6 +590,15 @@ __global__ __launch_bounds__(256) void fdw_step_line_born_kernel(const StepArgs 
     march<H, true, 2, false, false, PF, false, false, NUM, false, false, 0, true>(a, sv, lane, zs, xa, xe);
 }
 
+// Second-time-difference imaging (FDW_MODE_BACK_DTT, fdw_dev_back_iter_dtt): the fused backward iteration (BACK) with the DTT value of its
+// imaging epilogue.  The loads and stores are BACK's, 36 B/point; three subtractions and one more live mask on top of it.
+template <int H, int PF, int NUM>
+__global__ __launch_bounds__(256) void fdw_step_back_dtt_kernel(const StepArgs a)
+{
+    FDW_STEP_TILE(a, sv, lane, zs, xa, xe)
+    march<H, true, 2, true, false, PF, false, true, NUM, false, false, 0, false, true>(a, sv, lane, zs, xa, xe);
+}
+
 #if FDW_TU == 0
 // ------------------------------------------------------------------------------------------------
 // generic-order kernel: any even order up to FDW_MAX_ORDER, one thread per point, every tap from
@@ -714,6 +740,23 @@ __global__ __launch_bounds__(256) void fdw_born_scatter_kernel(const float* u, c
     }
 }
 
+// One term of second-time-difference imaging on the cells C = rows [x0, x0 + gridDim.y) x columns [z0, z1) (fdwave.h, "DTT imaging"):
+// img = img (+) ((a (-) b) (-) (b (-) c)) (*) r, every operation rounded on its own; pre: a already holds the first difference (a (-) b taken
+// by fdw_born_diff_kernel before the step that overwrote its operand).  blockIdx.z = shot of a batch (every array bstride words further on).
+// Behind the tail of the DTT backward loop and behind step kernels without the fused epilogue (orders above 8, forced generic,
+// FDW_NO_FUSED_BACK=1).
+__global__ __launch_bounds__(256) void fdw_dtt_image_kernel(const float* a, const float* b, const float* c, const float* r, float* img, int pre, int pitch,
+                                                            int x0, int z0, int z1, long long bstride)
+{
+    const int z = z0 + blockIdx.x * 256 + threadIdx.x;
+    if (z >= z1) return;
+    const size_t k = (size_t)((long long)blockIdx.z * bstride) + (size_t)(x0 + blockIdx.y) * pitch + z;
+    const float bv = b[k];
+    const float d1 = pre ? a[k] : a[k] - bv;
+    const float q = d1 - (bv - c[k]);
+    img[k] = img[k] + q * r[k];
+}
+
 // ------------------------------------------------------------------------------------------------
 // the one T() the lazy scheme owes d_p before it leaves the device (fd_forward's D2H of d_p, R:285)
 // ------------------------------------------------------------------------------------------------
@@ -835,6 +878,7 @@ static hipError_t launch_rtm_hp(const StepArgs& a, int mode, hipStream_t s)
     case FDW_MODE_FWD_LINE_PICK: hipLaunchKernelGGL((fdw_step_line_pick_kernel<H, PF, NUM>), grid, block, 0, s, a); break;
     case FDW_MODE_BORN: hipLaunchKernelGGL((fdw_step_born_kernel<H, PF, NUM>), grid, block, 0, s, a); break;
     case FDW_MODE_BORN_LINE: hipLaunchKernelGGL((fdw_step_line_born_kernel<H, PF, NUM>), grid, block, 0, s, a); break;
+    case FDW_MODE_BACK_DTT: hipLaunchKernelGGL((fdw_step_back_dtt_kernel<H, PF, NUM>), grid, block, 0, s, a); break;
     default: return hipErrorInvalidValue;
     }
     return hipGetLastError();
@@ -969,6 +1013,15 @@ hipError_t launch_born_scatter(const float* u, const float* a, const float* w, c
     if (x1 <= x0 || zcols <= 0) return hipSuccess;
     hipLaunchKernelGGL(fdw_born_scatter_kernel, dim3((zcols + 255) / 256, x1 - x0), dim3(256), 0, s, u, a, w, m, d, kind, pitch, x0, z0, z1, zcols, gz, rec,
                        rec0);
+    return hipGetLastError();
+}
+
+hipError_t launch_dtt_image(const float* a, const float* b, const float* c, const float* r, float* img, int pre, int pitch, int x0, int x1, int z0, int z1,
+                            int nbatch, long long bstride, hipStream_t s)
+{
+    if (x1 <= x0 || z1 <= z0) return hipSuccess;
+    hipLaunchKernelGGL(fdw_dtt_image_kernel, dim3((z1 - z0 + 255) / 256, x1 - x0, nbatch > 1 ? nbatch : 1), dim3(256), 0, s, a, b, c, r, img, pre, pitch, x0,
+                       z0, z1, bstride);
     return hipGetLastError();
 }
 

@@ -50,7 +50,13 @@
  * groups of fdw_shot_batch_max, through fdw_shot_excitation_batch (a group of one, or FDW_NO_SHOT_BATCH=1: fdw_shot_excitation): the forward loop keeps the peak of the source field and its time level per cell, the backward loop
  * propagates the receiver field alone and every cell takes its sample at that level.  dir.image is the stack in shot order of exc / amp
  * where |amp| > exc_eps max |amp| (fdw_image_excitation; `exc_eps` defaults to 1e-3), image.num has one section per shot.  exc together
- * with illum=1, resid=1, pw, snap > 0, slabs > 1 or gpus > 1 (deck or environment) is refused before anything is opened. */
+ * with illum=1, resid=1, pw, snap > 0, slabs > 1 or gpus > 1 (deck or environment) is refused before anything is opened.
+ *
+ * DTT imaging (no counterpart in the reference): the deck key `dtt=1` (absent or 0: nothing changes) images every shot with the second time
+ * difference of the source field instead of the cross-correlation (fdwave.h, "DTT imaging": fdw_shot_dtt, fdw_shot_batch_dtt, with pw
+ * fdw_shot_line_dtt / fdw_shot_line_batch_dtt).  It composes with resid=1 (dir.image is then the gradient of the DTT Born misfit, up to the
+ * two v2 weights of fdwave.h), illum=1, pw=NP, batching and gpus=N; every output other than the images keeps its bytes.  dtt=1 together
+ * with exc=1, snap > 0 or slabs > 1 (deck or environment) is refused before anything is opened. */
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -95,6 +101,7 @@ typedef struct {
     float *imloc_all;
     float *illoc_all;     /* illum=1: the shots' source illumination [nb][nx][nz], else NULL */
     int resid;            /* resid=1: every shot through fdw_shot_residual */
+    int dtt;              /* dtt=1: every shot through fdw_shot_dtt (with resid: its residual form) */
     float *resloc_all;    /* ... the shots' residual gathers [nb][nx][nt] */
     int snap_is;          /* snap=K: the shot whose wavefield frames are taken, else -1 */
     const fdw_snaps *snaps;
@@ -127,7 +134,12 @@ static void *shot_worker(void *p)
         float *imloc = j->imloc_all + (size_t)b * j->ni;
         float *illoc = j->illoc_all ? j->illoc_all + (size_t)b * j->ni : NULL;
         int rc;
-        if (j->resid) {              /* d_obs minus the gather the forward loop models (illoc may be NULL; never together with snap) */
+        if (j->dtt) {                /* the DTT imaging condition (illoc may be NULL; with resid the residual gather comes back too; never with snap) */
+            rc = j->dev_border ? fdw_dev_extendvel_linear(ctx, (unsigned long long)is * (unsigned long long)j->draws, NULL) : FDW_OK;
+            if (rc == FDW_OK)
+                rc = fdw_shot_dtt(ctx, j->dev_border ? NULL : j->vel2_all + (size_t)b * j->ne, j->sx[is], j->sz, j->gz, j->srce, d_obs, imloc, illoc, j->resid,
+                                  j->resid ? j->resloc_all + (size_t)b * j->nx * j->nt : NULL, NULL, NULL);
+        } else if (j->resid) {       /* d_obs minus the gather the forward loop models (illoc may be NULL; never together with snap) */
             rc = j->dev_border ? fdw_dev_extendvel_linear(ctx, (unsigned long long)is * (unsigned long long)j->draws, NULL) : FDW_OK;
             if (rc == FDW_OK)
                 rc = fdw_shot_residual(ctx, j->dev_border ? NULL : j->vel2_all + (size_t)b * j->ne, j->sx[is], j->sz, j->gz, j->srce, d_obs, imloc, illoc,
@@ -416,6 +428,20 @@ int main(int argc, char **argv)
         }
     }
 
+    /* our extension (absent or 0: nothing changes): the DTT imaging condition.  The snapshot shot, the excitation shot and slab-decomposed
+     * shots have no DTT form: refused before any file, thread, communicator or device is touched */
+    const int dtt = fdw_deck_int(deck, "dtt") == 1;
+    if (dtt) {
+        int sl = fdw_deck_int(deck, "slabs");
+        if (getenv("FDW_SLABS")) sl = atoi(getenv("FDW_SLABS"));
+        const char *with = exc ? "exc=1" : (snap > 0 ? "snap" : (sl > 1 ? "slabs" : NULL));
+        if (with) {
+            fprintf(stderr, "dtt=1 cannot be combined with %s: DTT imaging is built for point- and line-source shots on one full-grid context, without snapshots\n",
+                    with);
+            return EXIT_FAILURE;
+        }
+    }
+
     printf("## vp = %s, d_obs = %s, vel_ext_file = %s, vel_ext_flag = %d \n", vpfile, datfile, vel_ext_file, vel_ext_flag);
     printf("## nz = %d, nx = %d, nt = %d \n", nz, nx, nt);
     printf("## dz = %f, dx = %f, dt = %f \n", dz, dx, dt);
@@ -427,6 +453,7 @@ int main(int argc, char **argv)
         printf("## snap = %d, snap_dec = %d, iss = %d: %d frames of %d x %d in dir.snaps, dir.snaps_rec, dir.snapr \n", snap, snap_dec, iss, snap_nf,
                snap_nxs, snap_nzs);
     }
+    if (dtt) printf("## dtt = 1: the image is formed with the second time difference of the source field (the adjoint of DTT Born modelling) \n");
     if (resid) printf("## resid = 1: every shot migrates d_obs minus the gather modelled in the migration model; dir.resid, dir.misfit \n");
     if (nz <= 0 || nx <= 0 || nt <= 0 || !tmpdir || !vpfile || !datfile) {
         fprintf(stderr, "input deck is missing one of tmpdir/vpfile/datfile/nz/nx/nt\n");
@@ -547,7 +574,9 @@ int main(int argc, char **argv)
                 rc = fdw_dev_extendvel_linear(ctx, (unsigned long long)j * (unsigned long long)draws, NULL);      /* R:486: the next draw of the stream */
             memset(imloc, 0, ni * sizeof(float));                                /* R:515 */
             if (illum) memset(illoc, 0, ni * sizeof(float));
-            if (rc == FDW_OK) rc = fdw_shot_line(ctx, model, sz, gz, wav, enc, imloc, illoc, NULL, NULL);
+            if (rc == FDW_OK)
+                rc = dtt ? fdw_shot_line_dtt(ctx, model, sz, gz, wav, enc, imloc, illoc, 0, NULL, NULL, NULL)
+                         : fdw_shot_line(ctx, model, sz, gz, wav, enc, imloc, illoc, NULL, NULL);
             if (rc != FDW_OK) {
                 fprintf(stderr, "plane wave %d: %s\n", j + 1, fdw_last_error());
                 return EXIT_FAILURE;
@@ -558,8 +587,11 @@ int main(int argc, char **argv)
             int rc = fdw_encode_gathers_multi(0, ns, pw, lag, weight, d_obs, nx, nt, enc);
             for (int j0 = 0; rc == FDW_OK && j0 < pw; j0 += pw_bmax) {
                 const int n = pw - j0 < pw_bmax ? pw - j0 : pw_bmax;
-                rc = fdw_shot_line_batch(ctx, n, dev_models ? NULL : v2 + (size_t)j0 * ne, (unsigned long long)j0 * (unsigned long long)draws, sz, gz,
-                                         wav + (size_t)j0 * ng, enc + (size_t)j0 * ng, imloc + (size_t)j0 * ni, illum ? illoc + (size_t)j0 * ni : NULL);
+                const float *models = dev_models ? NULL : v2 + (size_t)j0 * ne;
+                const unsigned long long draw0 = (unsigned long long)j0 * (unsigned long long)draws;
+                float *il = illum ? illoc + (size_t)j0 * ni : NULL;
+                rc = dtt ? fdw_shot_line_batch_dtt(ctx, n, models, draw0, sz, gz, wav + (size_t)j0 * ng, enc + (size_t)j0 * ng, imloc + (size_t)j0 * ni, il, 0, NULL)
+                         : fdw_shot_line_batch(ctx, n, models, draw0, sz, gz, wav + (size_t)j0 * ng, enc + (size_t)j0 * ng, imloc + (size_t)j0 * ni, il);
             }
             if (rc != FDW_OK) {
                 fprintf(stderr, "fdw_shot_line_batch: %s\n", fdw_last_error());
@@ -731,7 +763,7 @@ int main(int argc, char **argv)
     shot_job job;
     job.prm = &prm; job.ns = ns; job.nworkers = nworkers; job.sx = sx; job.sz = sz; job.gz = gz; job.srce = srce; job.d_obs = d_obs;
     job.nx = nx; job.nt = nt; job.ne = ne; job.ni = ni; job.vel2_all = vel2_all; job.imloc_all = imloc_all; job.illoc_all = illoc_all; job.failed = 0;
-    job.resid = resid; job.resloc_all = resloc_all;
+    job.resid = resid; job.resloc_all = resloc_all; job.dtt = dtt;
     job.vp = vp; job.draws = fdw_border_draws(nx, nz, nxb, nzb); job.dev_border = dev_border; job.gpus = gpus;
     if (gpus > 1) {      /* more GPUs asked for than visible: the workers share the visible ones, as in rtm_model (the bytes do not depend on where a shot runs) */
         const int ndev = fdw_device_count();
@@ -783,7 +815,9 @@ int main(int argc, char **argv)
                 const float *models = dev_border ? NULL : vel2_all + (size_t)b0 * ne, *gathers = d_obs + (size_t)isb * nx * nt;
                 float *im = imloc_all + (size_t)b0 * ni, *il = illum ? illoc_all + (size_t)b0 * ni : NULL;
                 int rc;
-                if (resid) {
+                if (dtt) {
+                    rc = fdw_shot_batch_dtt(bctx, n, models, draw0, sx[isb], ds, sz, gz, srce, gathers, im, il, resid, resid ? resloc_all + (size_t)b0 * ng : NULL);
+                } else if (resid) {
                     rc = fdw_shot_batch_residual(bctx, n, models, draw0, sx[isb], ds, sz, gz, srce, gathers, im, il, resloc_all + (size_t)b0 * ng);
                 } else if (isb == job.snap_is) {
                     rc = dev_border ? fdw_dev_extendvel_linear(bctx, draw0, NULL) : FDW_OK;

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Census of the compiled kernels: which GPU test module launches which kernel of libfdwave.so, and how often.
 
-    python3 scripts/kernel_census.py [--out DIR] [--modules a,b,...] [--assemble-only] [--csv FILE]
+    python3 scripts/kernel_census.py [--out DIR] [--modules a,b,...] [--assemble-only] [--keep] [--csv FILE]
 
 The kernel list comes from the BUILT library: the `.kd` symbols of the embedded gfx950 code objects (extracted as the `isa` fixture of
 tests/test_stepn_isa_budget.py extracts them), demangled by the ROCm LLVM demangler (`llvm-readelf --demangle`; the ROCm install ships no
@@ -45,7 +45,7 @@ MODULES = collections.OrderedDict([
     ("test_gpu_parity", 600), ("test_value_domain", 180), ("test_illum", 180), ("test_record", 180), ("test_backward_pins", 180),
     ("test_slabs_gpu", 180), ("test_fast_numerics", 180), ("test_programs", 600), ("test_kernel_census", 180), ("test_snaps", 180),
     ("test_residual", 180), ("test_residual_batch", 180), ("test_line_source", 180), ("test_line_batch", 180), ("test_excitation", 300),
-    ("test_excitation_batch", 180), ("test_born", 180), ("test_born_batch", 300),
+    ("test_excitation_batch", 180), ("test_born", 180), ("test_born_batch", 300), ("test_dtt", 180),
 ])
 # modules whose GPU tests compare device output with the oracle or a restatement of it (test_programs runs the programs end to end)
 PARITY_MODULES = tuple(m for m in MODULES if m != "test_programs")
@@ -156,12 +156,19 @@ def read_census(path=CSV):
     return modules, {r[0]: (r[1], dict(zip(modules, map(int, r[2:])))) for r in rows[1:]}
 
 
-def assemble(out, modules, path):
+def assemble(out, modules, path, keep=False):
+    """keep: a module without counts under `out` keeps its column of the CSV as it stands (a kernel the CSV does not know yet: 0 launches) --
+    for a change that adds kernels and a module without touching what the other modules launch."""
     kernels = library_kernels()
     per = {}
+    old_modules, old = read_census(path) if keep and os.path.exists(path) else ([], {})
     for m in modules:
         f = os.path.join(out, m, "counts.json")
         if not os.path.exists(f):
+            if keep and m in old_modules:
+                per[m] = collections.Counter({s: old[s][1][m] for s in kernels if s in old})
+                print(f"[kernel_census] {m}: column kept from {os.path.relpath(path, ROOT)}")
+                continue
             sys.exit(f"[kernel_census] no counts for {m} under {out}: run it first (--modules {m})")
         per[m] = join(collections.Counter(json.load(open(f))["calls"]), kernels)
     with open(path, "w", newline="") as fo:
@@ -183,6 +190,7 @@ def main():
     ap.add_argument("--columns", default=None, help="modules of the CSV (default: all; they must have been run)")
     ap.add_argument("--assemble-only", action="store_true", help="run nothing: write the CSV from the counts under --out")
     ap.add_argument("--no-assemble", action="store_true", help="run the modules and stop (a census taken in several sittings)")
+    ap.add_argument("--keep", action="store_true", help="assembling: modules without counts under --out keep their column of the CSV")
     ap.add_argument("--csv", default=CSV)
     args = ap.parse_args()
     todo = [m for m in args.modules.split(",") if m]
@@ -197,7 +205,7 @@ def main():
                 sys.exit(f"[kernel_census] {m} failed (rc {rc}): see {os.path.join(args.out, m, 'run.log')}; the census stops here")
         print(f"[kernel_census] traced {len(todo)} modules in {time.time() - t0:.0f} s", flush=True)
     if not args.no_assemble:
-        assemble(args.out, args.columns.split(",") if args.columns else list(MODULES), args.csv)
+        assemble(args.out, args.columns.split(",") if args.columns else list(MODULES), args.csv, keep=args.keep)
 
 
 if __name__ == "__main__":
