@@ -143,7 +143,7 @@ int fdw_shot(fdw_ctx *ctx, const float *v2, int sx, int sz, int gz, const float 
  *                   has not run yet included -- and work queued on the stream after it sees its results.  Nothing is issued on the context's
  *                   own stream, and no other stream or event is involved.  Chained calls on one stream need no host synchronisation in between.
  *                   The ONE exception is fdw_dev_check_field, which issues its check on the stream and then synchronises it to return the count.
- *                   ONE amendment: fdw_dev_steps2 with a pass-band depth above 1 (fdw_set_pass_bands, below) forks part of its passes onto side
+ *                   ONE amendment: fdw_dev_steps2 with a pass-band depth above 1 or the moving cut (fdw_set_pass_bands, fdw_set_pass_cut, below) forks part of its passes onto side
  *                   streams of the context behind an event of the caller's stream and joins them into it before it returns; towards the
  *                   caller the ordering above holds unchanged.
  *   Host arguments (pointers to ip / ipp, role[], scalars) are read and written before the call returns.
@@ -981,7 +981,8 @@ int fdw_trace_active(void);
  *
  * Where the schedule is used: fdw_dev_steps2 only (not inside a batch), for the passes of the four-step kernel; the steps left over
  * (nsteps mod 4) and every other entry point -- the recording, illumination and line-source loops, fdw_forward and the shots, the slab
- * drivers -- run as before.  Automatic policy, from the measurement on one MI355X: 3 bands, depth 2
+ * drivers -- run as before.  Automatic policy (where the moving cut below does not apply: 12288^2 and larger since round 21), from the
+ * measurement on one MI355X: 3 bands, depth 2
  * where a pass has at least 1776 tiles (8192^2 and larger: +3.2 % at 8192^2, +3.1 % at 12288^2, +1.7 % at 16384^2 in EXACT numerics,
  * +7.6 % at 8192^2 and +4.2 % at 16384^2 in FAST) and the call holds at least 8 passes; one band otherwise (4096^2: -16 %; 6144^2: not
  * separable from one band; a call of one pass only pays for the cut).  THE GAIN NEEDS A HARDWARE QUEUE FOR THE SIDE STREAM: a process has four, and where more streams than that are alive two
@@ -994,7 +995,7 @@ int fdw_trace_active(void);
  * given: what is queued behind it sees its results.  At most FDW_PASS_DEPTH_MAX = 3 streams, the caller's included. */
 #define FDW_PASS_DEPTH_MAX 3
 typedef struct fdw_band_unit {
-    int pass, band;     /* n, g */
+    int pass, band;     /* n, g (fdw_plan_pass_cut: 0 lower, 1 upper, 2 the middle of a turn) */
     int r0, r1;         /* rows the unit produces (r1 = nxl for the last band: its launch ends at upd_x1 and copies the static rows) */
     int stream;         /* i mod D */
     int nwait;          /* 0 .. FDW_PASS_DEPTH_MAX - 1 */
@@ -1004,6 +1005,50 @@ int fdw_plan_pass_bands(int nxl, int upd_x1, int xchunk, int bands, int depth, i
                         fdw_band_unit *units, int cap);
 int fdw_set_pass_bands(fdw_ctx *ctx, int bands, int depth);
 int fdw_pass_bands(const fdw_ctx *ctx, int *bands, int *depth);
+
+/* ---- two bands with a moving cut ---------------------------------------------------------------------
+ * Fixed bands need three of them to run two deep (G >= D+1).  Two suffice when the cut between them MOVES by one chunk row per pass:
+ * pass n is cut at chunk row c_n into a lower unit [0, c_n * xchunk) and an upper unit [c_n * xchunk, nxl).  While the cut moves down,
+ * the lower unit of pass n+1 reads only rows the lower unit of pass n produced (xchunk >= 16 = the reach of a pass), so it may overlap
+ * the upper unit of pass n; moving up, the same holds for the upper units.  The cut bounces between cut_lo and cut_hi.  Same tiles, same
+ * results bit for bit, two launches per pass instead of three and two larger units resident.
+ *
+ * fdw_plan_pass_cut   the schedule; pure host C, no context, no device.  nxl, upd_x1, xchunk, npasses as for fdw_plan_pass_bands; the cut
+ *                     of pass 0 is chunk row cut_hi and moves down; at cut_lo it turns and moves up, at cut_hi it turns again.  Two units
+ *                     per pass, band 0 = lower, band 1 = upper (ends at nxl, owns the static rows); a pass whose cut moved down (and pass
+ *                     0) issues the lower unit first, one whose cut moved up the upper unit first.  Unit i runs on stream i mod 2 and
+ *                     waits for unit i-3; with stream order (i-2) everything up to i-2 is complete, so unit i can overlap unit i-1 only.
+ *                     THE TURN.  A range at least four chunk rows wide turns through a pass of THREE units, none of which needs the
+ *                     unit before it: after the pass cut at cut_lo+1, the lower unit [0, cut_lo X), the upper unit [(cut_lo+2) X, nxl)
+ *                     and last the middle (band 2) between them; the next pass is cut at cut_lo+3 and issues its upper unit first.  At
+ *                     the top the mirror image: after the pass cut at cut_hi-1, the upper unit [cut_hi X, nxl), the lower unit
+ *                     [0, (cut_hi-2) X), the middle; the next pass is cut at cut_hi-3.  A narrower range turns on the spot (cut_lo,
+ *                     cut_lo+1, ...), and there -- nowhere else -- the first unit of the pass after the turn touches rows of the unit
+ *                     before it and waits for i-1 as well (wait[] descending: i-1, i-3).  Measured: a wait
+ *                     for i-1 starts both streams' units at the same moment, and units in step run a quarter slower for several passes.
+ *                     Thin requests come back as ONE unit
+ *                     per pass ([0, nxl), stream 0, no waits: the plain loop) with *lo_out = *hi_out = 0: xchunk below 16, fewer than
+ *                     three chunk rows, cut_lo = cut_hi, or a unit that can hold fewer than 16 time-stepped rows (cut_lo = 0;
+ *                     upd_x1 - cut_hi * xchunk < 16).  Otherwise *lo_out / *hi_out = cut_lo / cut_hi.  units (may be NULL) receives
+ *                     min(cap, count) entries.  Returns the unit count (2 per pass plus 1 per three-unit turn); FDW_EINVAL for
+ *                     nxl < 1, upd_x1 outside [0, nxl], xchunk < 1, cut_lo < 0, cut_hi < cut_lo, npasses < 1 or cap < 0.
+ * fdw_set_pass_cut    the policy of fdw_dev_steps2 on this context: 0, 0 automatic (below); -1, -1 off (the band policy alone decides);
+ *                     1 <= lo <= hi: that cut range (a thin one runs the plain loop).  Anything else: FDW_EINVAL.  While it is automatic
+ *                     the environment variable FDW_PASS_CUT="lo,hi" (read at every call; experiments) takes its place.  An explicit
+ *                     fdw_set_pass_bands (anything but 0, 0) and FDW_PASS_BANDS take precedence over all of this.
+ *                     Automatic, from the measurement on one MI355X: the moving cut over the middle
+ *                     third of the chunk rows, [nch/3, nch - nch/3], where a pass has 60 000 to 500 000 strip rows (rows x strips of 56
+ *                     columns of 4 cells: 4096^2 to 8192^2; +5.9 % at 4096^2, +10.6 % at 6144^2, +2.2 % at 8192^2 with 213-row chunks
+ *                     instead of 173, EXACT numerics) and the call holds at least 8 passes; elsewhere the band policy above decides.
+ * fdw_pass_cut        what the last fdw_dev_steps2 call used: the cut range and the number of turns (passes of three units, or units that
+ *                     waited for the unit just before them); -1, -1, 0 when the moving cut did not run.  fdw_pass_bands reports 2, 2
+ *                     when it did.
+ *
+ * Streams: the caller's and the one side stream of the band schedule, forked and joined in the same way (STREAMS above). */
+int fdw_plan_pass_cut(int nxl, int upd_x1, int xchunk, int cut_lo, int cut_hi, int npasses, int *lo_out, int *hi_out, fdw_band_unit *units,
+                      int cap);
+int fdw_set_pass_cut(fdw_ctx *ctx, int lo, int hi);
+int fdw_pass_cut(const fdw_ctx *ctx, int *lo, int *hi, int *turns);
 
 /* ---- host formulas of libsource.a restated (pure C, usable without a device) --------------------
  * fdw_calc_coefs        calc_coefs + makeo2, F:113-192 / S:137-216 (cxx selects the float variant)

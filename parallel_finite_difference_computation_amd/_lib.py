@@ -183,6 +183,9 @@ SIGNATURES = [
     ("fdw_plan_pass_bands", C.c_int, [C.c_int] * 6 + [C.POINTER(C.c_int)] * 2 + [vp, C.c_int]),
     ("fdw_set_pass_bands", C.c_int, [vp, C.c_int, C.c_int]),
     ("fdw_pass_bands", C.c_int, [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    ("fdw_plan_pass_cut", C.c_int, [C.c_int] * 6 + [C.POINTER(C.c_int)] * 2 + [vp, C.c_int]),
+    ("fdw_set_pass_cut", C.c_int, [vp, C.c_int, C.c_int]),
+    ("fdw_pass_cut", C.c_int, [vp] + [C.POINTER(C.c_int)] * 3),
     ("fdw_calc_coefs", C.c_int, [C.c_int, C.c_int, f32p]),
     ("fdw_ricker_wavelet", None, [C.c_int, C.c_float, C.c_float, f32p]),
     ("fdw_taper_tables", None, [C.c_int, C.c_int, C.c_float, vp, vp]),

@@ -167,6 +167,18 @@ def plan_pass_bands(nxl, upd_x1, xchunk, bands, depth, npasses):
                               for u in units]
 
 
+def plan_pass_cut(nxl, upd_x1, xchunk, cut_lo, cut_hi, npasses):
+    """fdw_plan_pass_cut (fdwave.h): (lo, hi, units) of the two-band schedule whose cut moves between chunk rows cut_lo and cut_hi; units as
+    plan_pass_bands gives them (band 0: lower, 1: upper).  A thin request comes back as one unit per pass with lo = hi = 0.  No device."""
+    lo, hi = C.c_int(), C.c_int()
+    n = lib().fdw_plan_pass_cut(nxl, upd_x1, xchunk, cut_lo, cut_hi, npasses, C.byref(lo), C.byref(hi), None, 0)
+    check(min(n, 0))
+    units = (_lib.BandUnit * n)()
+    check(min(lib().fdw_plan_pass_cut(nxl, upd_x1, xchunk, cut_lo, cut_hi, npasses, C.byref(lo), C.byref(hi), units, n), 0))
+    return lo.value, hi.value, [dict(pass_=u.pass_, band=u.band, r0=u.r0, r1=u.r1, stream=u.stream, wait=[u.wait[k] for k in range(u.nwait)])
+                                for u in units]
+
+
 def planewave_lags(src_ix, dx, dt, p):
     """fdw_planewave_lags (fdwave.h): lag[s] = lround(p (src_ix[s] - src_ix[0]) dx / dt) - the smallest of them, in double; p in s/m."""
     src_ix = _i32(src_ix)
@@ -285,6 +297,17 @@ class FDWave:
         a, b = C.c_int(), C.c_int()
         check(lib().fdw_pass_bands(self._h, C.byref(a), C.byref(b)))
         return a.value, b.value
+
+    def set_pass_cut(self, lo=0, hi=0):
+        """dev_steps2's passes as two row bands whose cut moves between chunk rows lo and hi (fdwave.h: fdw_set_pass_cut).  0, 0: automatic;
+        -1, -1: off.  An explicit set_pass_bands takes precedence.  Results never depend on it."""
+        check(lib().fdw_set_pass_cut(self._h, int(lo), int(hi)))
+
+    def pass_cut(self):
+        """(lo, hi, turns) of the moving cut in the last dev_steps2 call; (-1, -1, 0) when it did not run."""
+        a, b, t = C.c_int(), C.c_int(), C.c_int()
+        check(lib().fdw_pass_cut(self._h, C.byref(a), C.byref(b), C.byref(t)))
+        return a.value, b.value, t.value
 
     def selftest(self):
         check(lib().fdw_selftest(self._h))

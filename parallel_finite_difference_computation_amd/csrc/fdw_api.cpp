@@ -48,8 +48,8 @@ extern "C" int fdw_version(void) { return FDW_VERSION; }
 // ------------------------------------------------------------------------------------------------
 // context
 // ------------------------------------------------------------------------------------------------
-// events of the launch units of band_passes: unit i records slot i % kBandRing, and the last unit that waits for it (i + 2D - 1) is
-// issued before unit i + kBandRing records the slot again
+// events of the launch units of unit_passes: unit i records slot i % kBandRing, and the last unit that waits for it (i + 2D - 1 in the band
+// plan, i + 3 in the cut plan) is issued before unit i + kBandRing records the slot again
 constexpr int kBandRing = 8;
 static_assert(kBandRing >= 2 * FDW_PASS_DEPTH_MAX, "a slot must not be recorded again before its last waiter is issued");
 
@@ -131,6 +131,8 @@ struct fdw_ctx {
     // consecutive four-step forward passes as row bands on side streams (fdw_set_pass_bands; band_passes)
     int pb_bands = 0, pb_depth = 0;             // the policy; 0, 0: automatic
     int pb_used_bands = 0, pb_used_depth = 0;   // what the last forward loop used (fdw_pass_bands)
+    int pc_lo = 0, pc_hi = 0;                   // two bands with a moving cut (fdw_set_pass_cut): the policy; 0, 0: automatic, -1, -1: off
+    int pc_used_lo = -1, pc_used_hi = -1, pc_used_turns = 0;      // what the last forward loop used (fdw_pass_cut)
     hipStream_t pb_side[FDW_PASS_DEPTH_MAX - 1] = {};      // created on first use
     hipEvent_t pb_fork = nullptr, pb_join[FDW_PASS_DEPTH_MAX - 1] = {}, pb_ring[kBandRing] = {};
 };
@@ -1021,9 +1023,18 @@ static int pipe_strips(const fdw_ctx* c)
     const int ncells = c->pitch / 4, own = 64 - 2 * kPipeSteps;
     return (ncells + own - 1) / own;
 }
-static int pipe_fwd_xchunk(const fdw_ctx* c, long strip_rows)
+// `moving_cut`: the passes run as two bands with a moving cut (steps_loop).  Its two resident units together are one whole pass, so the
+// 8192^2 class need not keep its pass above the 1280 workgroup slots and takes a longer chunk, 213 rows for 27 rows of run-in (8192^2,
+// Gpoints/s, profiles/r21_ab_bench.txt, session 3: 173 rows 737 - 747, 213 rows 751 - 755, 253 rows 750 - 752; session 4, FAST: 213 rows
+// 877 - 879, 253 rows 853 - 857); the classes below it keep their chunk lengths (4096^2 and 6144^2 were measured at those; 6144^2 at 173
+// rows 698 - 699 against 706 - 709 at 143).
+static int pipe_fwd_xchunk(const fdw_ctx* c, long strip_rows, bool moving_cut = false)
 {
     const bool fastnum = c->prm.numerics == FDW_NUMERICS_FAST;
+    if (c->xchunk2 <= 0) {
+        if (const char* e = getenv("FDW_FWD_XCHUNK")) if (atoi(e) > 0) return atoi(e);      // experiments
+        if (moving_cut && strip_rows >= 250000 && strip_rows < 1000000) return 213;
+    }
     return c->xchunk2 > 0 ? c->xchunk2 : (strip_rows >= 1000000 ? 253 : (strip_rows >= 250000 ? 173 : (strip_rows >= 120000 ? (fastnum ? 173 : 143) : (strip_rows >= 60000 ? 83 : 43))));
 }
 
@@ -1292,6 +1303,101 @@ extern "C" int fdw_pass_bands(const fdw_ctx* c, int* bands, int* depth)
     return FDW_OK;
 }
 
+// ---- two bands with a moving cut (fdwave.h: fdw_plan_pass_cut) -----------------------------------------------------------------------
+// The schedule.  Pure host arithmetic: no context, no HIP call.
+extern "C" int fdw_plan_pass_cut(int nxl, int upd_x1, int xchunk, int cut_lo, int cut_hi, int npasses, int* lo_out, int* hi_out,
+                                 fdw_band_unit* units, int cap)
+{
+    if (nxl <= 0 || upd_x1 < 0 || upd_x1 > nxl || xchunk <= 0 || cut_lo < 0 || cut_hi < cut_lo || npasses < 1 || (units && cap < 0))
+        return fail(FDW_EINVAL, "pass cut: nxl=%d upd_x1=%d xchunk=%d cut=[%d,%d] npasses=%d", nxl, upd_x1, xchunk, cut_lo, cut_hi, npasses);
+    constexpr int reach = kPipeSteps * kMaxFastHalfOrder;      // rows beyond its own that a pass reads on either side
+    const int nchunks = (upd_x1 + xchunk - 1) / xchunk;
+    // the lower unit is thinnest at cut_lo, the upper one at cut_hi; a cut that moves by one chunk row moves by at least the reach
+    const bool safe = xchunk >= reach && nchunks >= 3 && cut_lo < cut_hi && cut_lo >= 1 && cut_hi < nchunks && upd_x1 - (long)cut_hi * xchunk >= reach;
+    if (npasses > INT_MAX / 3) return fail(FDW_EINVAL, "pass cut: %d passes", npasses);
+    if (lo_out) *lo_out = safe ? cut_lo : 0;
+    if (hi_out) *hi_out = safe ? cut_hi : 0;
+    auto clear_waits = [](fdw_band_unit& u) {
+        u.nwait = 0;
+        for (int k = 0; k < FDW_PASS_DEPTH_MAX - 1; k++) u.wait[k] = -1;
+    };
+    if (!safe) {
+        for (int i = 0; units && i < std::min(cap, npasses); i++) {
+            fdw_band_unit& u = units[i];
+            u.pass = i; u.band = 0; u.r0 = 0; u.r1 = nxl; u.stream = 0;
+            clear_waits(u);
+        }
+        return npasses;
+    }
+    auto meet = [](int a0, int a1, int b0, int b1) { return a0 < b1 && b0 < a1; };      // rows [a0, a1) against rows [b0, b1)
+    int total = 0;
+    fdw_band_unit prev{};
+    auto emit = [&](int pass, int band, int r0, int r1) {
+        const int i = total++;
+        fdw_band_unit u{};
+        u.pass = pass; u.band = band; u.r0 = r0; u.r1 = r1;
+        u.stream = i % 2;
+        clear_waits(u);
+        if (i >= 1 && prev.pass != pass) {
+            // the unit before belongs to the pass before: it wrote the buffers this unit reads and read the buffers this unit writes
+            const int rd0 = std::max(r0 - reach, 0), rd1 = std::min(r1 + reach, nxl);
+            const int prd0 = std::max(prev.r0 - reach, 0), prd1 = std::min(prev.r1 + reach, nxl);
+            if (meet(prev.r0, prev.r1, rd0, rd1) || meet(r0, r1, prd0, prd1)) u.wait[u.nwait++] = i - 1;
+        }
+        if (i >= 3) u.wait[u.nwait++] = i - 3;
+        if (units && i < cap) units[i] = u;
+        prev = u;
+    };
+    // a range at least four chunk rows wide turns through a pass of three units, which needs no wait for the unit before; a narrower
+    // one turns on the spot and its first unit after the turn waits
+    const bool three = cut_hi - cut_lo >= 4;
+    const int X = xchunk;
+    int cut = cut_hi, dir = -1;      // the cut of the pass and the way it moved to get there
+    for (int n = 0; n < npasses; n++) {
+        if (n > 0 && three && dir < 0 && cut == cut_lo + 1) {
+            // the lower unit needs the lower unit before it alone, the upper unit the upper one alone; the middle comes last, so that the
+            // upper unit of the next pass, [(cut_lo + 3) X, nxl), shares no row with the unit before it
+            emit(n, 0, 0, cut_lo * X);
+            emit(n, 1, (cut_lo + 2) * X, nxl);
+            emit(n, 2, cut_lo * X, (cut_lo + 2) * X);
+            cut = cut_lo + 2; dir = 1;
+            continue;
+        }
+        if (n > 0 && three && dir > 0 && cut == cut_hi - 1) {
+            emit(n, 1, cut_hi * X, nxl);
+            emit(n, 0, 0, (cut_hi - 2) * X);
+            emit(n, 2, (cut_hi - 2) * X, cut_hi * X);
+            cut = cut_hi - 2; dir = -1;
+            continue;
+        }
+        if (n > 0) {
+            if (!three && (cut + dir < cut_lo || cut + dir > cut_hi)) dir = -dir;
+            cut += dir;
+        }
+        for (int k = 0; k < 2; k++) {
+            if ((k == 0) == (dir < 0)) emit(n, 0, 0, cut * X);      // the cut moved down: lower unit first; up: upper unit first
+            else emit(n, 1, cut * X, nxl);
+        }
+    }
+    return total;
+}
+
+extern "C" int fdw_set_pass_cut(fdw_ctx* c, int lo, int hi)
+{
+    if (!c) return fail(FDW_EINVAL, "ctx is NULL");
+    if (!((lo == 0 && hi == 0) || (lo == -1 && hi == -1) || (lo >= 1 && hi >= lo)))
+        return fail(FDW_EINVAL, "pass cut: lo=%d hi=%d (0, 0 = automatic; -1, -1 = off; else 1 <= lo <= hi)", lo, hi);
+    c->pc_lo = lo; c->pc_hi = hi;
+    return FDW_OK;
+}
+
+extern "C" int fdw_pass_cut(const fdw_ctx* c, int* lo, int* hi, int* turns)
+{
+    if (!c || !lo || !hi || !turns) return fail(FDW_EINVAL, "NULL argument");
+    *lo = c->pc_used_lo; *hi = c->pc_used_hi; *turns = c->pc_used_turns;
+    return FDW_OK;
+}
+
 // The wanted bands / depth of the forward loop's pipeline passes of `tiles` tiles each: the knob, else FDW_PASS_BANDS="G,D" (experiments),
 // else the automatic policy, which is the measurement on one MI355X and nothing else (DESIGN.md section 3c, round 13;
 // profiles/r13_band_probe.txt, python bench.py against the parent commit, Gpoints/s):
@@ -1324,6 +1430,35 @@ static void wanted_pass_bands(const fdw_ctx* c, long tiles, int npasses, int* ba
     }
 }
 
+// Whether the forward loop's passes run as two bands with a moving cut, asked only while the band policy above is automatic: the knob, else
+// FDW_PASS_CUT="lo,hi" (experiments; anything unreadable: off), else the automatic policy.  `nchunks`: chunk rows of a pass at the chunk
+// length this schedule would use.
+// Automatic, from the measurement on one MI355X (profiles/r21_ab_bench.txt; python bench.py, the moving
+// cut over the middle third of the chunk rows against what the tree did before, Gpoints/s):
+//   strip rows   grid       before                  moving cut
+//     78 k       4096^2     one band, 83 rows       +5.9 % (FAST +2.0 %)
+//    172 k       6144^2     one band, 143 rows      +10.6 % (FAST, 173 rows, +1.5 %)
+//    303 k       8192^2     3/2, 173 rows           173 rows +0.7 %; 213 rows +2.2 % (FAST +2.2 %); 253 rows +1.0 %
+//    676 k       12288^2    3/2, 173 rows           173 rows -1.7 %, 253 rows +0.5 .. 1.3 %: stays with the three bands
+//   1212 k       16384^2    3/2, 253 rows           -1.4 %: stays with the three bands
+// Narrower ranges lose (8192^2, 213 rows: [16,23] -0.6 %, [17,22] -2.2 % against [13,26]): every turn costs a small launch that holds its
+// queue for a tile's time; so do wide ones ([2,37] -6 %): a small unit beside a large one leaves the large one's start and end uncovered.
+constexpr long kCutAutoMinStripRows = 60000, kCutAutoMaxStripRows = 500000;
+static bool wanted_pass_cut(const fdw_ctx* c, long strip_rows, int nchunks, int npasses, int* lo, int* hi)
+{
+    if (c->pc_lo >= 1) { *lo = c->pc_lo; *hi = c->pc_hi; return true; }
+    if (c->pc_lo < 0) return false;
+    if (const char* e = getenv("FDW_PASS_CUT")) {
+        int a = 0, b = 0;
+        if (sscanf(e, "%d,%d", &a, &b) != 2 || a < 1 || b < a) return false;
+        *lo = a; *hi = b;
+        return true;
+    }
+    if (strip_rows < kCutAutoMinStripRows || strip_rows >= kCutAutoMaxStripRows || npasses < kBandAutoPasses) return false;
+    *lo = nchunks / 3; *hi = nchunks - nchunks / 3;      // the middle third: both units stay above a third of the pass
+    return true;
+}
+
 static int ensure_band_streams(fdw_ctx* c, int depth)
 {
     if (!c->pb_fork) HIP_TRY(hipEventCreateWithFlags(&c->pb_fork, hipEventDisableTiming));
@@ -1336,18 +1471,23 @@ static int ensure_band_streams(fdw_ctx* c, int depth)
     return FDW_OK;
 }
 
-// `npasses` plain forward passes of the pipeline kernel (what steps_loop's first branch issues one after the other on s) as the launch units
-// of fdw_plan_pass_bands: unit i on stream i mod D behind the events of the units the plan names.  Fork: every side stream starts behind
-// an event recorded on s here.  Join: s waits for the last unit of every side stream, whatever happened in between.  *ip, *ipp advance
-// over the passes issued.
-static int band_passes(fdw_ctx* c, float* const* buf, const float* d_v2, const Forward& f, int it0, int npasses, int first_pp_twice, int* ip, int* ipp,
-                       hipStream_t s, int G, int D, int xchunk)
+// Plain forward passes of the pipeline kernel (what steps_loop's first branch issues one after the other on s) as the launch units of
+// fdw_plan_pass_bands or fdw_plan_pass_cut, whole passes one after the other: every unit on the stream its plan names (D of them) behind the
+// events of the units the plan names.  Fork: every side stream starts behind an event recorded on s here.  Join: s waits for the last unit of every
+// side stream, whatever happened in between.  *ip, *ipp advance over the passes issued.
+static int unit_passes(fdw_ctx* c, float* const* buf, const float* d_v2, const Forward& f, int it0, int first_pp_twice, int* ip, int* ipp, hipStream_t s,
+                       const std::vector<fdw_band_unit>& units, int D, int xchunk)
 {
-    std::vector<fdw_band_unit> units((size_t)G * npasses);
-    int g_ = 0, d_ = 0;
-    const int total = fdw_plan_pass_bands(c->nxl, c->upd_x1, xchunk, G, D, npasses, &g_, &d_, units.data(), (int)units.size());
-    if (total < 0) return total;
-    if (g_ != G || d_ != D || total != (int)units.size()) return fail(FDW_ESTATE, "pass bands: the plan changed between two calls");
+    const int total = (int)units.size();
+    std::vector<char> awaited((size_t)total, 0);      // units whose event someone waits for
+    for (int i = 0; i < total; i++) {
+        const fdw_band_unit& u = units[(size_t)i];
+        if (u.stream < 0 || u.stream >= D || u.nwait < 0 || u.nwait > FDW_PASS_DEPTH_MAX - 1) return fail(FDW_ESTATE, "pass units: unit %d is malformed", i);
+        for (int w = 0; w < u.nwait; w++) {
+            if (u.wait[w] < 0 || u.wait[w] >= i || i - u.wait[w] >= kBandRing) return fail(FDW_ESTATE, "pass units: unit %d waits for unit %d", i, u.wait[w]);
+            awaited[(size_t)u.wait[w]] = 1;
+        }
+    }
     hipStream_t st[FDW_PASS_DEPTH_MAX] = {s};
     if (D > 1) {
         FDW_TRY(ensure_band_streams(c, D));
@@ -1361,13 +1501,13 @@ static int band_passes(fdw_ctx* c, float* const* buf, const float* d_v2, const F
         int o1 = 0, o2 = 0;
         for (int i = 0; i < total; i++) {
             const fdw_band_unit& u = units[(size_t)i];
-            if (u.band == 0) spare_pair(*ip, *ipp, &o1, &o2);
+            if (i == 0 || units[(size_t)i - 1].pass != u.pass) spare_pair(*ip, *ipp, &o1, &o2);      // the first unit of its pass
             const int k = u.pass * kPipeSteps;
             for (int w = 0; w < u.nwait; w++) HIP_TRY(hipStreamWaitEvent(st[u.stream], c->pb_ring[u.wait[w] % kBandRing], 0));
             FDW_TRY(stepn_impl(c, FDW_MODE_FWD, buf[*ipp], buf[*ip], d_v2, buf[o1], buf[o2], (k > 0) || first_pp_twice, view_at(f, it0 + k, c->nx), StepnBack{},
                                 RowRanges{u.r0, u.r1, 0, 0, xchunk}, st[u.stream]));
-            if (D > 1 && i + D + 1 < total) HIP_TRY(hipEventRecord(c->pb_ring[i % kBandRing], st[u.stream]));      // someone will wait for it
-            if (u.band == G - 1) { *ip = o1; *ipp = o2; }      // d_p = u^{n+kPipeSteps-1}, d_pp = u^{n+kPipeSteps}
+            if (D > 1 && awaited[(size_t)i]) HIP_TRY(hipEventRecord(c->pb_ring[i % kBandRing], st[u.stream]));
+            if (i + 1 == total || units[(size_t)i + 1].pass != u.pass) { *ip = o1; *ipp = o2; }      // the last: d_p = u^{n+kPipeSteps-1}, d_pp = u^{n+kPipeSteps}
         }
         return FDW_OK;
     };
@@ -1382,6 +1522,34 @@ static int band_passes(fdw_ctx* c, float* const* buf, const float* d_v2, const F
     }
     if (rc != FDW_OK) memcpy(g_err, msg, sizeof msg);      // the first error is the one to report
     return rc != FDW_OK ? rc : jrc;
+}
+
+// `npasses` passes as G fixed bands D deep
+static int band_passes(fdw_ctx* c, float* const* buf, const float* d_v2, const Forward& f, int it0, int npasses, int first_pp_twice, int* ip, int* ipp,
+                       hipStream_t s, int G, int D, int xchunk)
+{
+    std::vector<fdw_band_unit> units((size_t)G * npasses);
+    int g_ = 0, d_ = 0;
+    const int total = fdw_plan_pass_bands(c->nxl, c->upd_x1, xchunk, G, D, npasses, &g_, &d_, units.data(), (int)units.size());
+    if (total < 0) return total;
+    if (g_ != G || d_ != D || total != (int)units.size()) return fail(FDW_ESTATE, "pass bands: the plan changed between two calls");
+    return unit_passes(c, buf, d_v2, f, it0, first_pp_twice, ip, ipp, s, units, D, xchunk);
+}
+
+// `npasses` passes as two bands whose cut moves between chunk rows lo and hi; *turns: the passes of three units and the units that wait for the
+// unit just before them
+static int cut_passes(fdw_ctx* c, float* const* buf, const float* d_v2, const Forward& f, int it0, int npasses, int first_pp_twice, int* ip, int* ipp,
+                      hipStream_t s, int lo, int hi, int xchunk, int* turns)
+{
+    int lo_ = 0, hi_ = 0;
+    const int total = fdw_plan_pass_cut(c->nxl, c->upd_x1, xchunk, lo, hi, npasses, &lo_, &hi_, nullptr, 0);
+    if (total < 0) return total;
+    std::vector<fdw_band_unit> units((size_t)total);
+    if (lo_ != lo || hi_ != hi || fdw_plan_pass_cut(c->nxl, c->upd_x1, xchunk, lo, hi, npasses, &lo_, &hi_, units.data(), total) != total)
+        return fail(FDW_ESTATE, "pass cut: the plan changed between two calls");
+    *turns = 0;
+    for (int i = 1; i < total; i++) *turns += units[(size_t)i].band == 2 || (units[(size_t)i].nwait > 0 && units[(size_t)i].wait[0] == i - 1);
+    return unit_passes(c, buf, d_v2, f, it0, first_pp_twice, ip, ipp, s, units, 2, xchunk);
 }
 
 // A pass of m steps whose family has no kernel for the loop's extras (the two-step family: point-source recording + illumination, the
@@ -1418,12 +1586,27 @@ static int steps_loop(fdw_ctx* c, float* const* buf, const float* d_v2, const Fo
     if (f.rec) FDW_TRY(record_static(c, buf[*ip], buf[*ipp], f.gz, f.rec, it0, nsteps, s));
     int k = 0;
     c->pb_used_bands = c->pb_used_depth = 1;
+    c->pc_used_lo = c->pc_used_hi = -1; c->pc_used_turns = 0;
     if (f.may_band && var.kmode == FDW_MODE_FWD && c->nbatch <= 1 && nsteps >= kPipeSteps && pipe_pays(c)) {
         // fdw_dev_steps2, the plain forward loop on caller-owned buffers: its pipeline passes may run as row bands (whole chunk rows of the pass's own chunk length: the same tiles)
-        const int nstrip = pipe_strips(c), xchunk = pipe_fwd_xchunk(c, (long)c->upd_x1 * nstrip), npasses = nsteps / kPipeSteps;
-        int G, D;
-        wanted_pass_bands(c, (long)nstrip * ((c->upd_x1 + xchunk - 1) / xchunk), npasses, &G, &D);
-        if (G > 1 && fdw_plan_pass_bands(c->nxl, c->upd_x1, xchunk, G, D, npasses, &G, &D, nullptr, 0) < 0) return FDW_EINVAL;
+        const int nstrip = pipe_strips(c), npasses = nsteps / kPipeSteps;
+        const long strip_rows = (long)c->upd_x1 * nstrip;
+        const int xchunk = pipe_fwd_xchunk(c, strip_rows), xcut = pipe_fwd_xchunk(c, strip_rows, true);
+        int G = 1, D = 1, lo = 0, hi = 0;
+        // a band policy that is set, by the knob or the environment, is kept; else the moving cut where it is wanted; else the automatic bands
+        const bool bands_set = c->pb_bands > 0 || getenv("FDW_PASS_BANDS");
+        if (!bands_set && wanted_pass_cut(c, strip_rows, (c->upd_x1 + xcut - 1) / xcut, npasses, &lo, &hi)) {
+            if (fdw_plan_pass_cut(c->nxl, c->upd_x1, xcut, lo, hi, npasses, &lo, &hi, nullptr, 0) < 0) return FDW_EINVAL;
+            if (lo > 0) {      // else too thin: the plain loop below
+                c->pb_used_bands = c->pb_used_depth = 2;
+                c->pc_used_lo = lo; c->pc_used_hi = hi;
+                FDW_TRY(cut_passes(c, buf, d_v2, f, it0, npasses, first_pp_twice, ip, ipp, s, lo, hi, xcut, &c->pc_used_turns));
+                k = npasses * kPipeSteps;
+            }
+        } else {
+            wanted_pass_bands(c, (long)nstrip * ((c->upd_x1 + xchunk - 1) / xchunk), npasses, &G, &D);
+            if (G > 1 && fdw_plan_pass_bands(c->nxl, c->upd_x1, xchunk, G, D, npasses, &G, &D, nullptr, 0) < 0) return FDW_EINVAL;
+        }
         if (G > 1) {
             c->pb_used_bands = G; c->pb_used_depth = D;
             FDW_TRY(band_passes(c, buf, d_v2, f, it0, npasses, first_pp_twice, ip, ipp, s, G, D, xchunk));
