@@ -799,7 +799,7 @@ int fdw_shot_excitation_batch(fdw_ctx *ctx, int nshots, const float *v2_all, uns
  *                     device and downloaded transposed to [nx][nt] as fdw_record_shot does (data: scattered; data0, may be NULL: background).
  *                     v2 NULL: the resident model (FDW_ESTATE without one).  Work arrays are allocated on first use, freed by fdw_destroy.
  * Out of scope: Born kernels in the two-step and four-step families, slabs and several GPUs (the DTT-adjoint imaging condition: "DTT
- * imaging" below). */
+ * imaging" below; the solver that iterates on the two: "Least-squares migration"). */
 enum { FDW_BORN_FIELD = 0, FDW_BORN_DTT = 1 };
 int fdw_dev_born_steps(fdw_ctx *ctx, float *d_u_p, float *d_u_pp, float *d_du_p, float *d_du_pp, const float *d_v2, const float *d_m, int kind,
                        const float *d_srce, int sx, int sz, int gz, float *d_rec, float *d_rec0, int it0, int nsteps, int first_pp_twice, void *stream);
@@ -912,7 +912,8 @@ int fdw_born_shot_line_batch(fdw_ctx *ctx, int nshots, const float *v2_all, unsi
  * and fdw_shot_line_batch_residual's: the same parts under the same budget, fdw_batch_parts 0 / 1 / k as there, batched imloc equal to the
  * single-shot calls bit for bit.  Snapshots (fdw_shot_snaps), slab contexts, the sibling's dialects and excitation imaging do not combine
  * with DTT imaging: FDW_ESTATE where a context of that kind is handed in; there is no DTT form of fdw_shot_snaps or fdw_shot_excitation.
- * Out of scope: DTT kernels in the two-step and pipeline backward families, slabs and several GPUs, snapshots, a conjugate-gradient driver. */
+ * Out of scope: DTT kernels in the two-step and pipeline backward families, slabs and several GPUs, snapshots (the conjugate-gradient
+ * driver on Born modelling and this imaging condition: "Least-squares migration" below). */
 int fdw_dev_back_iter_dtt(fdw_ctx *ctx, int step_source, const float *d_f1, float *d_f0, const float *d_pr, float *d_ppr, const float *d_v2, int r0,
                           int r1, int pp_twice, const float *d_samples, int gz, float *d_img, void *stream);
 int fdw_dev_dtt_image(fdw_ctx *ctx, const float *d_fa, const float *d_fb, const float *d_fc, const float *d_r, float *d_img, void *stream);
@@ -926,6 +927,93 @@ int fdw_shot_batch_dtt(fdw_ctx *ctx, int nshots, const float *v2_all, unsigned l
                        const float *srce, const float *d_obs, float *imloc, float *illum, int residual, float *resid);
 int fdw_shot_line_batch_dtt(fdw_ctx *ctx, int nshots, const float *v2_all, unsigned long long draw_offset, int sz, int gz, const float *wav_all,
                             const float *d_obs, float *imloc, float *illum, int residual, float *resid);
+
+/* ---- Least-squares migration: conjugate gradients on Born modelling and DTT imaging ---------------------------------------------------
+ * The layer that iterates: a device-resident conjugate-gradient solver for min_m 1/2 sum_s |L_s m - d_s|^2, L_s = FDW_BORN_DTT modelling of
+ * shot s, L_s^T = DTT imaging with the two v2 weights.  Same dialect, contexts and numerics as the Born section (RTM dialect, full-grid
+ * contexts, EXACT and FAST: FAST changes the Laplacian only).  C is the Born cell set.  Model-space vectors are field-shaped device arrays
+ * [nxl][pitch] of which only the words on C are ever read or written: every other word keeps its bits.
+ *
+ * Sum order S(x_0 .. x_{n-1}) of doubles: 64 partials s_l = x_l + x_{l+64} + ..., each ascending onto +0.0; then for d = 32, 16, .., 1:
+ * s_l = s_l + s_{l+d} for l < d; the result is s_0 (n = 0: +0.0).  A dot product over C: the terms of row x are (double)a * (double)b (exact
+ * for two floats) in column order, the row sum is S of the row's terms, the total S of the row sums in row order.  A gather [nt][nx]: the
+ * same with the time rows as rows.  Totals of several shots are added in shot order onto +0.0.  No number depends on launch geometry or
+ * tuning: one wave of 64 lanes performs S as it stands, nothing is added atomically.
+ *
+ * Visit of shot s with direction p, V_s(p, d_obs):
+ *   1. the Born loop of fdw_born_shot (kind FDW_BORN_DTT) from rest with m = p; q [nt][nx] = its scattered gather, on the device;
+ *   2. w = q when d_obs == NULL, else w = d_obs (-) q; n2 = <w, w> in the order above (before the weight);
+ *   3. ws[it][ix] = w[it][ix] (*) v2[nxb+ix][gz]: fdw_gather_scale_v2 on the device layout;
+ *   4. the DTT backward loop of fdw_shot_dtt (single iterations and the tail) onto a zeroed image with ws as the receiver data; its two
+ *      snapshots are the background pair the Born loop just left (the older one damped once, fdw_dev_taper_finalize, as fdw_shot's forward
+ *      loop leaves it): no second forward loop runs, and the image is the one fdw_shot_dtt(residual = 0, d_obs = ws) forms, bit for bit;
+ *   5. on C: h = h (+) mask (*) (img (/) v2), quotient, product and sum rounded separately; mask == NULL: h = h (+) (img (/) v2).
+ * Solve.  All scalars are doubles that live on the device; every fp32 update is a separately rounded product and sum in both numerics.
+ *   start   g = 0; for each shot in order V_s(m, d_s) stacks into g.  misfit_0 = 1/2 sum_s n2_s, gamma = <g, g>, p = g.
+ *   k = 0 .. niter-1:  h = 0; the visits V_s(p, NULL) stack into h.  delta = sum_s n2_s, alpha = gamma / delta (0 when delta == 0),
+ *           af = (float)alpha.  m = m (+) af (*) p, g = g (-) af (*) h.  gamma' = <g, g>, beta = gamma' / gamma (0 when gamma == 0),
+ *           p = g (+) (float)beta (*) p.  misfit_{k+1} = misfit_k - 1/2 (alpha gamma), gamma = gamma'.
+ *   verify  one more pass of visits V_s(m, d_s) into a scratch image: the recomputed misfit 1/2 sum_s n2_s and the residual gathers w.
+ *
+ * Device arrays; everything goes on the given stream (NULL: the context's), nothing is synchronised or allocated.  d_rows receives the
+ * row sums, d_sum / d_n2 / d_gg (one double) their S:
+ *   fdw_dev_dot_cells    <a, b> over C; d_rows [x1 - x0] (the rows of C, fdw_get_extents).
+ *   fdw_dev_dot_gather   <a, b> of two gathers [nt][nx]; d_rows [nt].
+ *   fdw_dev_lsm_gather   steps 2 and 3 in one pass over [nt][nx]: d_w (NULL ok; may be d_q) = w, d_ws (may be d_obs, or d_q) = ws, d_rows
+ *                        [nt], d_n2.  Every word is read before it is written, by the one thread that writes it.
+ *   fdw_dev_lsm_stack    step 5.
+ *   fdw_dev_lsm_update   m = m (+) af (*) p, g = g (-) af (*) h on C with af = (float)*d_alpha read on the device; d_rows [x1 - x0] and
+ *                        d_gg = <g, g> of the new g, formed in the same pass.
+ *   fdw_dev_lsm_direction  p = g (+) (float)*d_beta (*) p on C.
+ *   FDW_EINVAL before anything is enqueued: a NULL required pointer, gz outside [0, zlim).  FDW_ESTATE: slab contexts, the sibling's
+ *   dialects, a context inside a batch.
+ *   Kernels (csrc/fdw_lsm.hip): fdw_lsm_dot_rows_kernel, fdw_lsm_gather_kernel and fdw_lsm_update_kernel run one wave per row (coalesced
+ *   along z, or along ix of a gather), fdw_lsm_finish_kernel one wave over the row sums, fdw_lsm_stack_kernel and fdw_lsm_direction_kernel
+ *   are pointwise, fdw_lsm_scalar_kernel is one wave that turns gamma, delta, gamma' into alpha, beta and the misfit history in device
+ *   memory.  The fp32 quotient of step 5 is the fp64 quotient of the two floats rounded once more (53 >= 2 * 24 + 2 bits: correctly rounded).
+ *
+ * fdw_lsm_visit   one visit on host arrays: p, mask (NULL ok), h (in/out) [nx][nz]; d_obs (NULL ok), data (NULL ok: receives w) [nx][nt];
+ *                 *n2 = <w, w>.  v2 NULL: the resident model (FDW_ESTATE without one).  Synchronous.
+ * fdw_lsm_visit_batch  the visits V_b(p, d_obs[b]) of nshots shots on ONE direction p, stacked into h in shot order; shots and models as
+ *                 fdw_born_shot_batch takes them (v2_all / draw_offset, sx0, dsx); d_obs (NULL ok) and data (NULL ok) [nshots][nx][nt],
+ *                 n2 [nshots].  Groups, parts and fdw_batch_parts as fdw_lsm_solve's passes (below); the bytes are those of fdw_lsm_visit
+ *                 on each shot.  Synchronous.
+ * fdw_lsm_solve   the solve above; shots and models as fdw_shot_batch takes them (v2_all [nshots][nxe][nze], or NULL: the border models of
+ *                 draws draw_offset + b T on the resident model; source rows sx0 + b dsx), d_obs [nshots][nx][nt], mask [nx][nz] (NULL
+ *                 ok), m [nx][nz] in/out.  misfit receives niter + 1 doubles, one more (the recomputed misfit) with verify = 1; resid
+ *                 (NULL ok, verify = 1 only) [nshots][nx][nt] the residual gathers of the verify pass.  m, g, p, h, the mask and every
+ *                 gather stay on the device for the whole solve; the host reads no scalar back per iteration, the history comes down
+ *                 once at the end.  Where fdw_born_shot_batch and fdw_shot_batch_dtt both batch, the visits of a pass run one launch per
+ *                 time step in both loops inside fdw_shot_batch's buffers (the scattered pairs become the spare source buffers; no new
+ *                 field buffers), in groups of what the budget (fdw_set_batch_budget) holds of eleven fields and one gather per shot;
+ *                 the gather pass and the stack run shot by shot in shot order.  Elsewhere, under a budget below one shot's share and
+ *                 without room on the device the shots run one by one.  The same bytes come out either way.  fdw_batch_parts: the
+ *                 groups of one pass, 0 / 1 / k as for the other batched calls.  Synchronous; work arrays are allocated on first use
+ *                 and freed by fdw_destroy.
+ *   Refusals, before anything is enqueued: those of fdw_born_shot / fdw_born_shot_batch (FDW_EINVAL: a NULL required pointer, nshots < 1,
+ *   sz, gz or a source row outside the time-stepped cells; FDW_ESTATE: no model), niter < 0, verify outside {0, 1}, resid without verify
+ *   (FDW_EINVAL); slab contexts, the sibling's dialects and a context inside a batch: FDW_ESTATE.
+ * Measured on one MI355X (profiles/lsm.json; order 8, seconds per shot and iteration): 8192^2, nt 500: 0.4523 against
+ * 0.5364 for fdw_born_shot followed by fdw_shot_dtt on the parent's build (ratio 0.843; FAST 0.4461 / 0.5239, 0.851); 415 x 295 interior,
+ * nt 1700, 32 shots batched: 0.005030 against 0.006378 for fdw_born_shot_batch followed by fdw_shot_batch_dtt (0.789; FAST 0.796).
+ * rtm_code: the deck key lsm=N (with lsm_mute=K) runs fdw_lsm_solve on the deck's shots (csrc/rtm_code.c).
+ * Out of scope: line-source, plane-wave and encoded forms, slabs and several GPUs, illumination or Hessian preconditioning,
+ * regularisation. */
+int fdw_dev_dot_cells(fdw_ctx *ctx, const float *d_a, const float *d_b, double *d_rows, double *d_sum, void *stream);
+int fdw_dev_dot_gather(fdw_ctx *ctx, const float *d_a, const float *d_b, double *d_rows /* [nt] */, double *d_sum, void *stream);
+int fdw_dev_lsm_gather(fdw_ctx *ctx, const float *d_q, const float *d_obs /* NULL ok */, const float *d_v2, int gz, float *d_w /* NULL ok */, float *d_ws,
+                       double *d_rows /* [nt] */, double *d_n2, void *stream);
+int fdw_dev_lsm_stack(fdw_ctx *ctx, float *d_h, const float *d_img, const float *d_v2, const float *d_mask /* NULL ok */, void *stream);
+int fdw_dev_lsm_update(fdw_ctx *ctx, float *d_m, float *d_g, const float *d_p, const float *d_h, const double *d_alpha, double *d_rows, double *d_gg,
+                       void *stream);
+int fdw_dev_lsm_direction(fdw_ctx *ctx, float *d_p, const float *d_g, const double *d_beta, void *stream);
+int fdw_lsm_visit(fdw_ctx *ctx, const float *v2 /* NULL: resident */, const float *p, int sx, int sz, int gz, const float *srce,
+                  const float *d_obs /* NULL ok */, const float *mask /* NULL ok */, float *h, double *n2, float *data /* NULL ok */);
+int fdw_lsm_visit_batch(fdw_ctx *ctx, int nshots, const float *v2_all, unsigned long long draw_offset, const float *p /* ONE for all shots */, int sx0,
+                        int dsx, int sz, int gz, const float *srce, const float *d_obs /* NULL ok */, const float *mask /* NULL ok */, float *h,
+                        double *n2 /* [nshots] */, float *data /* NULL ok */);
+int fdw_lsm_solve(fdw_ctx *ctx, int nshots, const float *v2_all, unsigned long long draw_offset, int sx0, int dsx, int sz, int gz, const float *srce,
+                  const float *d_obs, const float *mask /* NULL ok */, int niter, float *m, double *misfit, int verify, float *resid /* NULL ok */);
 
 /* ---- tuning / introspection --------------------------------------------------------------------
  * fdw_set_tuning  xchunk = rows marched per wave (0 = auto), wz = waves of a block laid along z

@@ -176,6 +176,15 @@ SIGNATURES = [
     ("fdw_shot_line_dtt", C.c_int, [vp, vp, C.c_int, C.c_int, f32p, f32p, f32p, vp, C.c_int, vp, vp, vp]),
     ("fdw_shot_batch_dtt", C.c_int, [vp, C.c_int, vp, C.c_ulonglong, C.c_int, C.c_int, C.c_int, C.c_int, f32p, f32p, f32p, vp, C.c_int, vp]),
     ("fdw_shot_line_batch_dtt", C.c_int, [vp, C.c_int, vp, C.c_ulonglong, C.c_int, C.c_int, f32p, f32p, f32p, vp, C.c_int, vp]),
+    ("fdw_dev_dot_cells", C.c_int, [vp] * 6),
+    ("fdw_dev_dot_gather", C.c_int, [vp] * 6),
+    ("fdw_dev_lsm_gather", C.c_int, [vp, vp, vp, vp, C.c_int, vp, vp, vp, vp, vp]),
+    ("fdw_dev_lsm_stack", C.c_int, [vp] * 6),
+    ("fdw_dev_lsm_update", C.c_int, [vp] * 9),
+    ("fdw_dev_lsm_direction", C.c_int, [vp] * 5),
+    ("fdw_lsm_visit", C.c_int, [vp, vp, f32p, C.c_int, C.c_int, C.c_int, f32p, vp, vp, f32p, C.POINTER(C.c_double), vp]),
+    ("fdw_lsm_visit_batch", C.c_int, [vp, C.c_int, vp, C.c_ulonglong, f32p, C.c_int, C.c_int, C.c_int, C.c_int, f32p, vp, vp, f32p, vp, vp]),
+    ("fdw_lsm_solve", C.c_int, [vp, C.c_int, vp, C.c_ulonglong, C.c_int, C.c_int, C.c_int, C.c_int, f32p, f32p, vp, C.c_int, f32p, vp, C.c_int, vp]),
     ("fdw_two_step_active", C.c_int, [vp]),
     ("fdw_steps_per_pass", C.c_int, [vp]),
     ("fdw_selftest", C.c_int, [vp]),

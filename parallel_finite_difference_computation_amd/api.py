@@ -605,6 +605,82 @@ class FDWave:
         a device caller's loop, behind dev_step(MODE_PLAIN).  stream as dev_back_iter takes it."""
         check(lib().fdw_dev_dtt_image(self._h, d_fa, d_fb, d_fc, d_r, d_img, stream))
 
+    # ---- least-squares migration (fdwave.h: conjugate gradients on BORN_DTT modelling and DTT imaging) ----
+    def dev_dot_cells(self, d_a, d_b, d_rows, d_sum, stream=None):
+        """<a, b> over the Born cell set of two field-shaped device arrays, in the sum order of fdwave.h: d_rows (device doubles, one per
+        row of the cell set) the row sums, d_sum (one device double) the total (fdw_dev_dot_cells).  stream as dev_born_steps takes it."""
+        check(lib().fdw_dev_dot_cells(self._h, d_a, d_b, d_rows, d_sum, stream))
+
+    def dev_dot_gather(self, d_a, d_b, d_rows, d_sum, stream=None):
+        """<a, b> of two device gathers [nt][nx]; d_rows [nt] device doubles, d_sum one (fdw_dev_dot_gather)."""
+        check(lib().fdw_dev_dot_gather(self._h, d_a, d_b, d_rows, d_sum, stream))
+
+    def dev_lsm_gather(self, d_q, d_obs, d_v2, gz, d_w, d_ws, d_rows, d_n2, stream=None):
+        """One pass over a device gather [nt][nx]: w = d_obs - q (d_obs None: q), d_n2 = <w, w>, d_w (None ok) = w, d_ws = w * v2[nxb+ix][gz]
+        (fdw_dev_lsm_gather)."""
+        check(lib().fdw_dev_lsm_gather(self._h, d_q, d_obs, d_v2, gz, d_w, d_ws, d_rows, d_n2, stream))
+
+    def dev_lsm_stack(self, d_h, d_img, d_v2, d_mask, stream=None):
+        """h = h + mask * (img / v2) on the Born cell set, d_mask None: h = h + img / v2 (fdw_dev_lsm_stack)."""
+        check(lib().fdw_dev_lsm_stack(self._h, d_h, d_img, d_v2, d_mask, stream))
+
+    def dev_lsm_update(self, d_m, d_g, d_p, d_h, d_alpha, d_rows, d_gg, stream=None):
+        """m = m + af * p, g = g - af * h on the Born cell set with af = float32 of the device double d_alpha; d_gg = <g, g> of the new g
+        (fdw_dev_lsm_update)."""
+        check(lib().fdw_dev_lsm_update(self._h, d_m, d_g, d_p, d_h, d_alpha, d_rows, d_gg, stream))
+
+    def dev_lsm_direction(self, d_p, d_g, d_beta, stream=None):
+        """p = g + float32(beta) * p on the Born cell set, beta a device double (fdw_dev_lsm_direction)."""
+        check(lib().fdw_dev_lsm_direction(self._h, d_p, d_g, d_beta, stream))
+
+    def lsm_visit(self, v2, p, sx, sz, gz, srce, d_obs=None, mask=None, h=None, want_data=False):
+        """One visit of a least-squares migration (fdwave.h, fdw_lsm_visit): Born modelling of the direction p[nx][nz], the residual d_obs - q
+        (d_obs None: q), its weighted DTT image stacked onto h (None: zeros) through the mask (None: none).  v2 None: the resident model.
+        Returns a dict: h, n2 = <w, w>, and data = w [nx][nt] with want_data."""
+        out = {"h": np.zeros((self.nx, self.nz), np.float32) if h is None else np.array(_f32(h, (self.nx, self.nz)), order="C")}
+        if want_data:
+            out["data"] = np.zeros((self.nx, self.nt), np.float32)
+        n2 = C.c_double(0.0)
+        d_obs = None if d_obs is None else _f32(d_obs, (self.nx, self.nt))
+        mask = None if mask is None else _f32(mask, (self.nx, self.nz))
+        check(lib().fdw_lsm_visit(self._h, None if v2 is None else _f32(v2, (self.nxe, self.nze)).ctypes.data, _f32(p, (self.nx, self.nz)), sx, sz, gz,
+                                  _f32(srce, (self.nt,)), None if d_obs is None else d_obs.ctypes.data, None if mask is None else mask.ctypes.data,
+                                  out["h"], C.byref(n2), out["data"].ctypes.data if want_data else None))
+        out["n2"] = n2.value
+        return out
+
+    def lsm_visit_batch(self, nshots, p, sx0, dsx, sz, gz, srce, d_obs=None, mask=None, h=None, v2_all=None, draw_offset=0, want_data=False):
+        """The visits of `nshots` shots on ONE direction p, stacked into h in shot order (fdwave.h, fdw_lsm_visit_batch); shots and models as
+        born_shot_batch takes them, d_obs[nshots][nx][nt] or None.  One launch per time step in both loops where born_shot_batch and
+        shot_batch_dtt batch; batch_parts() says how the call went.  Returns a dict: h, n2[nshots], and data[nshots][nx][nt] with want_data."""
+        out = {"h": np.zeros((self.nx, self.nz), np.float32) if h is None else np.array(_f32(h, (self.nx, self.nz)), order="C"),
+               "n2": np.zeros(max(nshots, 1), np.float64)}
+        if want_data:
+            out["data"] = np.zeros((nshots, self.nx, self.nt), np.float32)
+        v2_all = None if v2_all is None else _f32(v2_all, (nshots, self.nxe, self.nze))
+        d_obs = None if d_obs is None else _f32(d_obs, (nshots, self.nx, self.nt))
+        mask = None if mask is None else _f32(mask, (self.nx, self.nz))
+        check(lib().fdw_lsm_visit_batch(self._h, nshots, None if v2_all is None else v2_all.ctypes.data, int(draw_offset), _f32(p, (self.nx, self.nz)), sx0, dsx,
+                                        sz, gz, _f32(srce, (self.nt,)), None if d_obs is None else d_obs.ctypes.data,
+                                        None if mask is None else mask.ctypes.data, out["h"], out["n2"].ctypes.data,
+                                        out["data"].ctypes.data if want_data else None))
+        return out
+
+    def lsm_solve(self, nshots, sx0, dsx, sz, gz, srce, d_obs, niter, m=None, mask=None, v2_all=None, draw_offset=0, verify=False, want_resid=False):
+        """`niter` conjugate-gradient iterations on min_m 1/2 sum_s |Born_DTT_s m - d_s|^2 (fdwave.h, fdw_lsm_solve); shots and models as
+        shot_batch takes them, d_obs[nshots][nx][nt], m the start model (None: zeros), mask[nx][nz] or None.  Returns a dict: m, misfit
+        (niter + 1 float64 values, one more -- the recomputed misfit -- with verify) and, with verify and want_resid, resid[nshots][nx][nt]."""
+        out = {"m": np.zeros((self.nx, self.nz), np.float32) if m is None else np.array(_f32(m, (self.nx, self.nz)), order="C"),
+               "misfit": np.zeros(niter + 1 + int(bool(verify)) if niter >= 0 else 1, np.float64)}
+        if want_resid:
+            out["resid"] = np.zeros((nshots, self.nx, self.nt), np.float32)
+        v2_all = None if v2_all is None else _f32(v2_all, (nshots, self.nxe, self.nze))
+        mask = None if mask is None else _f32(mask, (self.nx, self.nz))
+        check(lib().fdw_lsm_solve(self._h, nshots, None if v2_all is None else v2_all.ctypes.data, int(draw_offset), sx0, dsx, sz, gz, _f32(srce, (self.nt,)),
+                                  _f32(d_obs, (nshots, self.nx, self.nt)), None if mask is None else mask.ctypes.data, niter, out["m"],
+                                  out["misfit"].ctypes.data, int(bool(verify)), out["resid"].ctypes.data if want_resid else None))
+        return out
+
     # ---- line sources (fdwave.h: plane-wave and encoded-shot migration) ----
     def shot_line(self, v2, sz, gz, wav, d_obs, imloc=None, want_fields=False, want_illum=False, illum=None):
         """shot() (v2=None: shot_resident()) whose forward loop is driven by the line source wav[nx][nt] at depth sz instead of a point source

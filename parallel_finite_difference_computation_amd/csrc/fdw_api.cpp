@@ -20,6 +20,7 @@
 
 #include "fdw_born.h"
 #include "fdw_dtt.h"
+#include "fdw_lsm.h"
 #include "fdw_excimg.h"
 #include "fdw_internal.h"
 #include "fdw_kernels.h"
@@ -123,6 +124,12 @@ struct fdw_ctx {
     float* d_born_w = nullptr;     // Born modelling without the fused kernel, FDW_BORN_DTT: (A - B) of the background on the interior cells
     float* b_born_rec0 = nullptr;  // fdw_born_shot_batch with data0: the shots' background gathers [shots][nt][nx]; allocated on first use
     size_t b_born_rec0_cap = 0;
+    // least-squares migration (fdw_lsm_visit, fdw_lsm_solve); allocated on first use
+    float* d_lsm_f[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};      // m, g, p, h, the mask, the verify pass's scratch image
+    float* d_lsm_dobs = nullptr;   // the shots' data gathers [shots][nt][nx]
+    float* d_lsm_res = nullptr;    // the verify pass's residual gathers [shots][nt][nx]
+    float* d_lsm_d = nullptr;      // doubles: row sums, the solver's scalars, the shots' n2, the misfit history (LsmDoubles)
+    size_t lsm_dobs_cap = 0, lsm_res_cap = 0, lsm_d_cap = 0;
     size_t store_budget = 0; // fdw_rtm_stored_shot: bytes the stored source fields may take (0: whatever the device grants); fdw_set_store_budget
     int store_segments = 0;  // ... segments the last such shot was cut into (1: every field kept)
     size_t batch_budget = 0; // bytes a batch of shots may take (0: FDW_BATCH_BUDGET_BYTES, else 6 GiB); written by fdw_set_batch_budget alone
@@ -399,7 +406,8 @@ extern "C" void fdw_destroy(fdw_ctx* c)
                      c->fld[4], c->fld[5], c->fld[6], c->fld[7], c->fld[8], c->fld[9], c->d_v2, c->d_img, c->d_illum, c->d_srce, c->d_dobs, c->d_rec,
                      c->d_vp, c->d_vpe, (float*)c->d_draws, (float*)c->d_jump, c->bfld[0], c->bfld[1], c->bfld[2], c->bfld[3],
                      c->bfld[4], c->bfld[5], c->bfld[6], c->bfld[7], c->b_v2, c->b_img, c->b_dobs, c->b_illum, c->b_rec, c->b_wav, c->d_raw, c->d_wav, c->d_snap[0], c->d_snap[1], c->d_snap[2], c->d_amp, (float*)c->d_texc, c->d_exc, (float*)c->d_peak,
-                     c->d_born_m, c->d_born_rec0, c->d_born_w, c->b_born_rec0, c->d_dtt_w};
+                     c->d_born_m, c->d_born_rec0, c->d_born_w, c->b_born_rec0, c->d_dtt_w,
+                     c->d_lsm_f[0], c->d_lsm_f[1], c->d_lsm_f[2], c->d_lsm_f[3], c->d_lsm_f[4], c->d_lsm_f[5], c->d_lsm_dobs, c->d_lsm_res, c->d_lsm_d};
     for (float* b : bufs)
         if (b) (void)hipFree(b);
     if (c->stream) (void)hipStreamDestroy(c->stream);
@@ -4018,4 +4026,351 @@ extern "C" int fdw_shot_line_batch_dtt(fdw_ctx* c, int nshots, const float* v2_a
     x.line = true;
     return shot_batch_in_parts(c, "fdw_shot_line_batch_dtt", nshots, v2_all, draw_offset, -1, 0, sz, gz, wav_all, d_obs, imloc, x, illum ? 12 : 11,
                                residual ? 2 : 1);
+}
+
+// ------------------------------------------------------------------------------------------------
+// least-squares migration: conjugate gradients on Born modelling and DTT imaging (definitions in fdwave.h, "Least-squares migration")
+// ------------------------------------------------------------------------------------------------
+static int check_lsm_ctx(const fdw_ctx* c, const char* who)
+{
+    FDW_TRY(check_dtt_ctx(c, who));
+    if (c->nbatch > 1) return fail(FDW_ESTATE, "%s: not inside a batch of shots", who);
+    return FDW_OK;
+}
+
+static int lsm_launched(hipError_t e, const char* what)
+{
+    return e == hipSuccess ? (int)FDW_OK : fail(FDW_EHIP, "least-squares migration: %s launch failed: %s", what, hipGetErrorString(e));
+}
+
+extern "C" int fdw_dev_dot_cells(fdw_ctx* c, const float* d_a, const float* d_b, double* d_rows, double* d_sum, void* stream)
+{
+    if (!c) return fail(FDW_EINVAL, "ctx is NULL");
+    FDW_TRY(check_lsm_ctx(c, "fdw_dev_dot_cells"));
+    if (!d_a || !d_b || !d_rows || !d_sum) return fail(FDW_EINVAL, "fdw_dev_dot_cells: NULL buffer");
+    const BornCells C = born_cells(c);
+    const int rows = std::max(C.x1 - C.x0, 0);
+    hipStream_t s = pick_stream(c, stream);
+    FDW_TRY(lsm_launched(launch_lsm_dot_rows(d_a, d_b, d_rows, c->pitch, C.x0, rows, C.z0, C.z1, s), "row sums"));
+    return lsm_launched(launch_lsm_finish(d_rows, rows, d_sum, s), "total");
+}
+
+extern "C" int fdw_dev_dot_gather(fdw_ctx* c, const float* d_a, const float* d_b, double* d_rows, double* d_sum, void* stream)
+{
+    if (!c) return fail(FDW_EINVAL, "ctx is NULL");
+    FDW_TRY(check_lsm_ctx(c, "fdw_dev_dot_gather"));
+    if (!d_a || !d_b || !d_rows || !d_sum) return fail(FDW_EINVAL, "fdw_dev_dot_gather: NULL buffer");
+    hipStream_t s = pick_stream(c, stream);
+    FDW_TRY(lsm_launched(launch_lsm_dot_rows(d_a, d_b, d_rows, c->nx, 0, c->prm.nt, 0, c->nx, s), "row sums"));
+    return lsm_launched(launch_lsm_finish(d_rows, c->prm.nt, d_sum, s), "total");
+}
+
+// steps 2 and 3 of a visit behind their checks
+static int lsm_gather(fdw_ctx* c, const float* d_q, const float* d_obs, const float* d_v2, int gz, float* d_w, float* d_ws, double* d_rows, double* d_n2,
+                      hipStream_t s)
+{
+    FDW_TRY(lsm_launched(launch_lsm_gather(d_q, d_obs, d_v2, d_w, d_ws, d_rows, c->prm.nt, c->nx, c->pitch, c->prm.nxb, gz, s), "gather"));
+    return lsm_launched(launch_lsm_finish(d_rows, c->prm.nt, d_n2, s), "total");
+}
+
+extern "C" int fdw_dev_lsm_gather(fdw_ctx* c, const float* d_q, const float* d_obs, const float* d_v2, int gz, float* d_w, float* d_ws, double* d_rows,
+                                  double* d_n2, void* stream)
+{
+    if (!c) return fail(FDW_EINVAL, "ctx is NULL");
+    FDW_TRY(check_lsm_ctx(c, "fdw_dev_lsm_gather"));
+    if (!d_q || !d_v2 || !d_ws || !d_rows || !d_n2) return fail(FDW_EINVAL, "fdw_dev_lsm_gather: NULL buffer");
+    if (gz < 0 || gz >= c->zlim) return fail(FDW_EINVAL, "fdw_dev_lsm_gather: receiver depth %d outside the time-stepped columns [0,%d)", gz, c->zlim);
+    return lsm_gather(c, d_q, d_obs, d_v2, gz, d_w, d_ws, d_rows, d_n2, pick_stream(c, stream));
+}
+
+extern "C" int fdw_dev_lsm_stack(fdw_ctx* c, float* d_h, const float* d_img, const float* d_v2, const float* d_mask, void* stream)
+{
+    if (!c) return fail(FDW_EINVAL, "ctx is NULL");
+    FDW_TRY(check_lsm_ctx(c, "fdw_dev_lsm_stack"));
+    if (!d_h || !d_img || !d_v2) return fail(FDW_EINVAL, "fdw_dev_lsm_stack: NULL buffer");
+    const BornCells C = born_cells(c);
+    return lsm_launched(launch_lsm_stack(d_h, d_img, d_v2, d_mask, c->pitch, C.x0, C.x1, C.z0, C.z1, pick_stream(c, stream)), "stack");
+}
+
+extern "C" int fdw_dev_lsm_update(fdw_ctx* c, float* d_m, float* d_g, const float* d_p, const float* d_h, const double* d_alpha, double* d_rows, double* d_gg,
+                                  void* stream)
+{
+    if (!c) return fail(FDW_EINVAL, "ctx is NULL");
+    FDW_TRY(check_lsm_ctx(c, "fdw_dev_lsm_update"));
+    if (!d_m || !d_g || !d_p || !d_h || !d_alpha || !d_rows || !d_gg) return fail(FDW_EINVAL, "fdw_dev_lsm_update: NULL buffer");
+    const BornCells C = born_cells(c);
+    hipStream_t s = pick_stream(c, stream);
+    FDW_TRY(lsm_launched(launch_lsm_update(d_m, d_g, d_p, d_h, d_alpha, d_rows, c->pitch, C.x0, C.x1, C.z0, C.z1, s), "update"));
+    return lsm_launched(launch_lsm_finish(d_rows, std::max(C.x1 - C.x0, 0), d_gg, s), "total");
+}
+
+extern "C" int fdw_dev_lsm_direction(fdw_ctx* c, float* d_p, const float* d_g, const double* d_beta, void* stream)
+{
+    if (!c) return fail(FDW_EINVAL, "ctx is NULL");
+    FDW_TRY(check_lsm_ctx(c, "fdw_dev_lsm_direction"));
+    if (!d_p || !d_g || !d_beta) return fail(FDW_EINVAL, "fdw_dev_lsm_direction: NULL buffer");
+    const BornCells C = born_cells(c);
+    return lsm_launched(launch_lsm_direction(d_p, d_g, d_beta, c->pitch, C.x0, C.x1, C.z0, C.z1, pick_stream(c, stream)), "direction");
+}
+
+// the doubles of a visit or a solve inside c->d_lsm_d
+struct LsmDoubles {
+    double *rows, *sc, *n2, *hist;
+};
+static int lsm_doubles(fdw_ctx* c, int nshots, int nhist, LsmDoubles* d)
+{
+    const size_t nrows = (size_t)std::max(c->prm.nt, c->nxl);
+    FDW_TRY(ensure_cap(&c->d_lsm_d, &c->lsm_d_cap, 2 * (nrows + LSM_NSCALARS + (size_t)nshots + (size_t)nhist)));
+    d->rows = reinterpret_cast<double*>(c->d_lsm_d);
+    d->sc = d->rows + nrows;
+    d->n2 = d->sc + LSM_NSCALARS;
+    d->hist = d->n2 + nshots;
+    return FDW_OK;
+}
+
+// the buffers every visit works in: the Born loop's four fields and the backward loop's receiver pair, v2, the image, both gathers
+static int lsm_work_buffers(fdw_ctx* c)
+{
+    FDW_TRY(ensure_work_buffers(c, 8, true));
+    FDW_TRY(ensure_cap(&c->d_rec, &c->rec_cap, (size_t)c->nx * c->prm.nt));
+    return ensure_cap(&c->d_dobs, &c->dobs_cap, (size_t)c->nx * c->prm.nt);
+}
+
+// One visit on the context's stream with the model in c->d_v2 and the wavelet in c->d_srce: d_p the direction, d_obs NULL or the shot's data
+// [nt][nx] (may be c->d_dobs), d_mask NULL or the mask, d_h the stack, d_w NULL or where w goes (may be c->d_rec).  The Born loop leaves the
+// background pair in fld[0..1], the newest level where an odd or even nt puts it; the scattered pair fld[2..3] becomes the two spare
+// source buffers of the backward loop.
+static int lsm_visit_dev(fdw_ctx* c, const float* d_p, int sx, int sz, int gz, const float* d_obs, const float* d_mask, float* d_h, double* d_rows,
+                         double* d_n2, float* d_w)
+{
+    const int nt = c->prm.nt;
+    hipStream_t s = c->stream;
+    FDW_TRY(zero_fields(c, c->fld, 4));
+    FDW_TRY(born_loop(c, c->fld[0], c->fld[1], c->fld[2], c->fld[3], c->d_v2, d_p, FDW_BORN_DTT, point_source(c->d_srce, sx, sz), gz, c->d_rec, nullptr, 0, nt,
+                      0, s));
+    const int inew = nt % 2 ? 0 : 1, iold = 1 - inew;
+    if (nt > 0) FDW_TRY(fdw_dev_taper_finalize(c, c->fld[iold], s));      // as fdw_shot's forward loop leaves d_p
+    FDW_TRY(lsm_gather(c, c->d_rec, d_obs, c->d_v2, gz, d_w, c->d_dobs, d_rows, d_n2, s));
+    float* src[4] = {c->fld[iold], c->fld[inew], c->fld[2], c->fld[3]};
+    FDW_TRY(zero_fields(c, c->fld + 4, 2));
+    HIP_TRY(hipMemsetAsync(c->d_img, 0, field_elems(c) * sizeof(float), s));
+    FDW_TRY(back_loop(c, src, c->fld + 4, gz, nt, SnapPlan{}, true));
+    const BornCells C = born_cells(c);
+    return lsm_launched(launch_lsm_stack(d_h, c->d_img, c->d_v2, d_mask, c->pitch, C.x0, C.x1, C.z0, C.z1, s), "stack");
+}
+
+// The visits of `nb` consecutive shots (source rows sx0 + b dsx) through ONE launch per time step in both loops, inside fdw_shot_batch's
+// buffers: bfld[0..1] the background pairs, bfld[2..3] the scattered pairs and then the spare source buffers, bfld[4..5] the receiver pairs,
+// b_v2 the models, b_img the images, b_dobs the scattered gathers and, in place, the weighted receiver data.  ONE direction d_p for all
+// shots.  d_obs NULL or [nb][nt][nx], d_w NULL or [nb][nt][nx], d_n2 [nb].  The gather pass and the stack run shot by shot, in shot order:
+// the bytes are those of lsm_visit_dev on each shot.
+static int lsm_visit_group(fdw_ctx* c, int nb, const float* v2_part, unsigned long long draw_offset, const float* d_p, int sx0, int dsx, int sz, int gz,
+                           const float* d_obs, const float* d_mask, float* d_h, double* d_rows, double* d_n2, float* d_w)
+{
+    const int nt = c->prm.nt;
+    const size_t fe = field_elems(c), ng = (size_t)c->nx * nt;
+    hipStream_t s = c->stream;
+    FDW_TRY(batch_models(c, nb, v2_part, draw_offset));
+    for (int i = 0; i < 6; i++) HIP_TRY(hipMemsetAsync(c->bfld[i], 0, fe * nb * sizeof(float), s));
+    HIP_TRY(hipMemsetAsync(c->b_img, 0, fe * nb * sizeof(float), s));
+    BatchScope scope(c, nb, dsx, false);
+    FDW_TRY(born_loop(c, c->fld[0], c->fld[1], c->fld[2], c->fld[3], c->d_v2, d_p, FDW_BORN_DTT, point_source(c->d_srce, sx0, sz), gz, c->d_dobs, nullptr, 0,
+                      nt, 0, s));
+    const int inew = nt % 2 ? 0 : 1, iold = 1 - inew;
+    for (int b = 0; b < nb && nt > 0; b++) FDW_TRY(fdw_dev_taper_finalize(c, c->fld[iold] + b * fe, s));
+    for (int b = 0; b < nb; b++)
+        FDW_TRY(lsm_gather(c, c->d_dobs + b * ng, d_obs ? d_obs + b * ng : nullptr, c->d_v2 + b * fe, gz, d_w ? d_w + b * ng : nullptr, c->d_dobs + b * ng,
+                           d_rows, d_n2 + b, s));
+    float* src[4] = {c->fld[iold], c->fld[inew], c->fld[2], c->fld[3]};
+    FDW_TRY(back_loop(c, src, c->fld + 4, gz, nt, SnapPlan{}, true));
+    const BornCells C = born_cells(c);
+    for (int b = 0; b < nb; b++)
+        FDW_TRY(lsm_launched(launch_lsm_stack(d_h, c->d_img + b * fe, c->d_v2 + b * fe, d_mask, c->pitch, C.x0, C.x1, C.z0, C.z1, s), "stack"));
+    return FDW_OK;
+}
+
+extern "C" int fdw_lsm_visit(fdw_ctx* c, const float* v2, const float* p, int sx, int sz, int gz, const float* srce, const float* d_obs, const float* mask,
+                             float* h, double* n2, float* data)
+{
+    if (!c) return fail(FDW_EINVAL, "ctx is NULL");
+    FDW_TRY(check_lsm_ctx(c, "fdw_lsm_visit"));
+    if (!p || !srce || !h || !n2) return fail(FDW_EINVAL, "fdw_lsm_visit: NULL argument");
+    FDW_TRY(has_model(c, v2));
+    FDW_TRY(check_born_args(c, "fdw_lsm_visit", FDW_BORN_DTT, sx, sz, gz));
+    if (c->nx <= 0 || c->nz <= 0) return fail(FDW_EINVAL, "fdw_lsm_visit: no interior");
+    HIP_TRY(hipSetDevice(c->device));
+    FDW_TRY(lsm_work_buffers(c));
+    FDW_TRY(alloc_zero(&c->d_born_m, field_elems(c)));
+    FDW_TRY(alloc_zero(&c->d_lsm_f[3], field_elems(c)));
+    if (mask) FDW_TRY(alloc_zero(&c->d_lsm_f[4], field_elems(c)));
+    LsmDoubles d;
+    FDW_TRY(lsm_doubles(c, 1, 0, &d));
+    end_residency(c, v2);
+    if (v2) FDW_TRY(upload_rows(c, c->d_v2, v2, c->stream));
+    FDW_TRY(upload_source(c, srce, c->prm.nt));
+    FDW_TRY(image_to_device(c, p, c->d_born_m));
+    FDW_TRY(image_to_device(c, h, c->d_lsm_f[3]));
+    if (mask) FDW_TRY(image_to_device(c, mask, c->d_lsm_f[4]));
+    if (d_obs) FDW_TRY(gathers_to_device(c, d_obs, c->d_dobs, 1));
+    FDW_TRY(lsm_visit_dev(c, c->d_born_m, sx, sz, gz, d_obs ? c->d_dobs : nullptr, mask ? c->d_lsm_f[4] : nullptr, c->d_lsm_f[3], d.rows, d.n2,
+                          data ? c->d_rec : nullptr));
+    FDW_TRY(image_to_host(c, h, c->d_lsm_f[3]));
+    HIP_TRY(hipMemcpyAsync(n2, d.n2, sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (data) FDW_TRY(gathers_to_host(c, c->d_rec, 1, data));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return FDW_OK;
+}
+
+// The shots of a pass of visits and how they go through: where fdw_born_shot_batch and fdw_shot_batch_dtt both batch, in groups of what the
+// budget holds of eleven fields and one gather per shot (the caller's own arrays are not the batch's); elsewhere, under a budget below one
+// shot's share and without room on the device, one by one (part = 1).
+struct LsmShots {
+    int nshots;
+    const float* v2_all;
+    unsigned long long draw_offset;
+    int sx0, dsx, sz, gz;
+    int part = 1;
+    bool model_set = false;      // one shot: its model stays where the first visit put it
+};
+// decides the groups, allocates their buffers and sets fdw_batch_parts: the groups of ONE pass (every pass runs the same groups)
+static int lsm_plan(fdw_ctx* c, LsmShots* S)
+{
+    const size_t ng = (size_t)c->nx * c->prm.nt;
+    const bool room = batch_budget(c) >= (11 * field_elems(c) + ng) * sizeof(float);
+    bool batched = S->nshots > 1 && born_batch_ok(c) && room;
+    S->part = batched ? batch_part(c, S->nshots, 11, 1) : 1;
+    if (S->part > 1) {
+        const int rc = ensure_batch_buffers(c, S->part, true);
+        if (rc == FDW_ENOMEM) { S->part = 1; batched = false; }      // no room on the device: one by one
+        else if (rc) return rc;
+    }
+    batch_begin(c);
+    for (int b0 = 0; b0 < S->nshots; b0 += S->part) batch_part_ran(c, batched);
+    (void)batch_end(c, S->nshots, FDW_OK);
+    if (S->v2_all) c->v2_resident = false;
+    return FDW_OK;
+}
+// One pass: V_b(d_dir, d_obs ? d_obs[b] : NULL) for every shot in order, stacked into d_stack; the shots' n2 into d.n2, w into d_w (NULL ok).
+// d_obs, d_w: device [nshots][nt][nx].  A group of one shot runs the single-shot code.
+static int lsm_pass(fdw_ctx* c, LsmShots* S, const float* d_dir, const float* d_obs, const float* d_mask, float* d_stack, const LsmDoubles& d, float* d_w)
+{
+    const size_t ne = (size_t)c->prm.nxe * c->prm.nze, ng = (size_t)c->nx * c->prm.nt;
+    const unsigned long long draws = (unsigned long long)fdw_border_draws(c->nx, c->nz, c->prm.nxb, c->prm.nzb);
+    for (int b0 = 0; b0 < S->nshots; b0 += S->part) {
+        const int nb = std::min(S->part, S->nshots - b0);
+        const float* obs = d_obs ? d_obs + b0 * ng : nullptr;
+        float* w = d_w ? d_w + b0 * ng : nullptr;
+        const unsigned long long draw0 = S->draw_offset + (unsigned long long)b0 * draws;
+        if (nb > 1) {
+            FDW_TRY(lsm_visit_group(c, nb, S->v2_all ? S->v2_all + b0 * ne : nullptr, draw0, d_dir, S->sx0 + b0 * S->dsx, S->dsx, S->sz, S->gz, obs, d_mask,
+                                    d_stack, d.rows, d.n2 + b0, w));
+            continue;
+        }
+        if (S->nshots > 1 || !S->model_set)
+            FDW_TRY(S->v2_all ? upload_rows(c, c->d_v2, S->v2_all + b0 * ne, c->stream) : fdw_dev_extendvel_linear(c, draw0, nullptr));
+        S->model_set = true;
+        FDW_TRY(lsm_visit_dev(c, d_dir, S->sx0 + b0 * S->dsx, S->sz, S->gz, obs, d_mask, d_stack, d.rows, d.n2 + b0, w));
+    }
+    return FDW_OK;
+}
+
+// what fdw_lsm_visit_batch and fdw_lsm_solve refuse of their shots and models
+static int check_lsm_shots(fdw_ctx* c, const char* who, int nshots, const float* v2_all, int sx0, int dsx, int sz, int gz)
+{
+    if (nshots < 1) return fail(FDW_EINVAL, "%s: nshots=%d", who, nshots);
+    if (!v2_all && !c->model_resident) return fail(FDW_ESTATE, "%s: no model: pass v2_all or call fdw_model_resident first", who);
+    FDW_TRY(check_born_args(c, who, FDW_BORN_DTT, sx0, sz, gz));
+    FDW_TRY(check_batch_source_rows(c, nshots, sx0, dsx));
+    if (c->nx <= 0 || c->nz <= 0) return fail(FDW_EINVAL, "%s: no interior", who);
+    return FDW_OK;
+}
+
+extern "C" int fdw_lsm_visit_batch(fdw_ctx* c, int nshots, const float* v2_all, unsigned long long draw_offset, const float* p, int sx0, int dsx, int sz, int gz,
+                                   const float* srce, const float* d_obs, const float* mask, float* h, double* n2, float* data)
+{
+    if (!c) return fail(FDW_EINVAL, "ctx is NULL");
+    FDW_TRY(check_lsm_ctx(c, "fdw_lsm_visit_batch"));
+    if (!p || !srce || !h || !n2) return fail(FDW_EINVAL, "fdw_lsm_visit_batch: NULL argument");
+    FDW_TRY(check_lsm_shots(c, "fdw_lsm_visit_batch", nshots, v2_all, sx0, dsx, sz, gz));
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t ng = (size_t)c->nx * c->prm.nt;
+    FDW_TRY(lsm_work_buffers(c));
+    FDW_TRY(alloc_zero(&c->d_born_m, field_elems(c)));
+    FDW_TRY(alloc_zero(&c->d_lsm_f[3], field_elems(c)));
+    if (mask) FDW_TRY(alloc_zero(&c->d_lsm_f[4], field_elems(c)));
+    if (d_obs) FDW_TRY(ensure_cap(&c->d_lsm_dobs, &c->lsm_dobs_cap, ng * nshots));
+    if (data) FDW_TRY(ensure_cap(&c->d_lsm_res, &c->lsm_res_cap, ng * nshots));
+    LsmDoubles d;
+    FDW_TRY(lsm_doubles(c, nshots, 0, &d));
+    LsmShots S{nshots, v2_all, draw_offset, sx0, dsx, sz, gz};
+    FDW_TRY(lsm_plan(c, &S));
+    FDW_TRY(upload_source(c, srce, c->prm.nt));
+    FDW_TRY(image_to_device(c, p, c->d_born_m));
+    FDW_TRY(image_to_device(c, h, c->d_lsm_f[3]));
+    if (mask) FDW_TRY(image_to_device(c, mask, c->d_lsm_f[4]));
+    if (d_obs) FDW_TRY(gathers_to_device(c, d_obs, c->d_lsm_dobs, nshots));
+    FDW_TRY(lsm_pass(c, &S, c->d_born_m, d_obs ? c->d_lsm_dobs : nullptr, mask ? c->d_lsm_f[4] : nullptr, c->d_lsm_f[3], d, data ? c->d_lsm_res : nullptr));
+    FDW_TRY(image_to_host(c, h, c->d_lsm_f[3]));
+    HIP_TRY(hipMemcpyAsync(n2, d.n2, (size_t)nshots * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (data) FDW_TRY(gathers_to_host(c, c->d_lsm_res, nshots, data));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return FDW_OK;
+}
+
+extern "C" int fdw_lsm_solve(fdw_ctx* c, int nshots, const float* v2_all, unsigned long long draw_offset, int sx0, int dsx, int sz, int gz, const float* srce,
+                             const float* d_obs, const float* mask, int niter, float* m, double* misfit, int verify, float* resid)
+{
+    if (!c) return fail(FDW_EINVAL, "ctx is NULL");
+    FDW_TRY(check_lsm_ctx(c, "fdw_lsm_solve"));
+    if (!srce || !d_obs || !m || !misfit) return fail(FDW_EINVAL, "fdw_lsm_solve: NULL argument");
+    if (niter < 0) return fail(FDW_EINVAL, "fdw_lsm_solve: niter=%d", niter);
+    if (verify != 0 && verify != 1) return fail(FDW_EINVAL, "fdw_lsm_solve: verify=%d is neither 0 nor 1", verify);
+    if (resid && !verify) return fail(FDW_EINVAL, "fdw_lsm_solve: resid is the output of verify=1");
+    FDW_TRY(check_lsm_shots(c, "fdw_lsm_solve", nshots, v2_all, sx0, dsx, sz, gz));
+    HIP_TRY(hipSetDevice(c->device));
+    const int nt = c->prm.nt;
+    const size_t ng = (size_t)c->nx * nt, fbytes = field_elems(c) * sizeof(float);
+    FDW_TRY(lsm_work_buffers(c));
+    for (int i = 0; i < 6; i++)
+        if (i != 4 || mask) FDW_TRY(alloc_zero(&c->d_lsm_f[i], field_elems(c)));
+    FDW_TRY(ensure_cap(&c->d_lsm_dobs, &c->lsm_dobs_cap, ng * nshots));
+    if (resid) FDW_TRY(ensure_cap(&c->d_lsm_res, &c->lsm_res_cap, ng * nshots));
+    LsmDoubles d;
+    FDW_TRY(lsm_doubles(c, nshots, niter + 2, &d));
+    LsmShots S{nshots, v2_all, draw_offset, sx0, dsx, sz, gz};
+    FDW_TRY(lsm_plan(c, &S));
+    float *d_m = c->d_lsm_f[0], *d_g = c->d_lsm_f[1], *d_p = c->d_lsm_f[2], *d_h = c->d_lsm_f[3], *d_mask = mask ? c->d_lsm_f[4] : nullptr, *d_scr = c->d_lsm_f[5];
+    hipStream_t s = c->stream;
+    const BornCells C = born_cells(c);
+    const int crows = std::max(C.x1 - C.x0, 0);
+    FDW_TRY(upload_source(c, srce, nt));
+    FDW_TRY(image_to_device(c, m, d_m));
+    if (mask) FDW_TRY(image_to_device(c, mask, d_mask));
+    FDW_TRY(gathers_to_device(c, d_obs, c->d_lsm_dobs, nshots));
+    auto pass = [&](const float* d_dir, bool data, float* d_stack, float* d_w) { return lsm_pass(c, &S, d_dir, data ? c->d_lsm_dobs : nullptr, d_mask, d_stack, d, d_w); };
+    HIP_TRY(hipMemsetAsync(d_g, 0, fbytes, s));
+    FDW_TRY(pass(d_m, true, d_g, nullptr));
+    FDW_TRY(lsm_launched(launch_lsm_dot_rows(d_g, d_g, d.rows, c->pitch, C.x0, crows, C.z0, C.z1, s), "row sums"));
+    FDW_TRY(lsm_launched(launch_lsm_finish(d.rows, crows, d.sc + LSM_GG, s), "total"));
+    FDW_TRY(lsm_launched(launch_lsm_scalars(d.sc, d.n2, nshots, d.hist, 0, LSM_START, s), "scalars"));
+    HIP_TRY(hipMemcpyAsync(d_p, d_g, fbytes, hipMemcpyDeviceToDevice, s));
+    for (int k = 0; k < niter; k++) {
+        HIP_TRY(hipMemsetAsync(d_h, 0, fbytes, s));
+        FDW_TRY(pass(d_p, false, d_h, nullptr));
+        FDW_TRY(lsm_launched(launch_lsm_scalars(d.sc, d.n2, nshots, d.hist, k, LSM_STEP, s), "scalars"));
+        FDW_TRY(lsm_launched(launch_lsm_update(d_m, d_g, d_p, d_h, d.sc + LSM_ALPHA, d.rows, c->pitch, C.x0, C.x1, C.z0, C.z1, s), "update"));
+        FDW_TRY(lsm_launched(launch_lsm_finish(d.rows, crows, d.sc + LSM_GG, s), "total"));
+        FDW_TRY(lsm_launched(launch_lsm_scalars(d.sc, d.n2, nshots, d.hist, k, LSM_TURN, s), "scalars"));
+        FDW_TRY(lsm_launched(launch_lsm_direction(d_p, d_g, d.sc + LSM_BETA, c->pitch, C.x0, C.x1, C.z0, C.z1, s), "direction"));
+    }
+    if (verify) {
+        HIP_TRY(hipMemsetAsync(d_scr, 0, fbytes, s));
+        FDW_TRY(pass(d_m, true, d_scr, resid ? c->d_lsm_res : nullptr));
+        FDW_TRY(lsm_launched(launch_lsm_scalars(d.sc, d.n2, nshots, d.hist, niter + 1, LSM_VERIFY, s), "scalars"));
+        if (resid) FDW_TRY(gathers_to_host(c, c->d_lsm_res, nshots, resid));
+    }
+    FDW_TRY(image_to_host(c, m, d_m));
+    HIP_TRY(hipMemcpyAsync(misfit, d.hist, (size_t)(niter + 1 + verify) * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return FDW_OK;
 }

@@ -52,6 +52,11 @@
  * where |amp| > exc_eps max |amp| (fdw_image_excitation; `exc_eps` defaults to 1e-3), image.num has one section per shot.  exc together
  * with illum=1, resid=1, pw, snap > 0, slabs > 1 or gpus > 1 (deck or environment) is refused before anything is opened.
  *
+ * Least-squares migration (no counterpart in the reference): the deck key `lsm=N` (absent or 0: nothing changes) makes dir.image the model
+ * after N conjugate-gradient iterations of fdw_lsm_solve on the deck's shots, from zero; `lsm_mute=K` (default 0) zeroes the mask on the
+ * interior columns iz < K.  <tmpdir>/dir.lsm_misfit holds N + 2 doubles: the misfit history and last the recomputed misfit; the history is
+ * printed.  lsm together with exc, snap, slabs, pw, gpus, illum, resid or dtt is refused before anything is opened.
+ *
  * DTT imaging (no counterpart in the reference): the deck key `dtt=1` (absent or 0: nothing changes) images every shot with the second time
  * difference of the source field instead of the cross-correlation (fdwave.h, "DTT imaging": fdw_shot_dtt, fdw_shot_batch_dtt, with pw
  * fdw_shot_line_dtt / fdw_shot_line_batch_dtt).  It composes with resid=1 (dir.image is then the gradient of the DTT Born misfit, up to the
@@ -442,6 +447,28 @@ int main(int argc, char **argv)
         }
     }
 
+    /* our extension (absent or 0: nothing changes): least-squares migration, lsm=N conjugate-gradient iterations of fdw_lsm_solve on the
+     * deck's shots (fdwave.h, "Least-squares migration").  The solve is one call on one full-grid context with point sources: refused with
+     * every key that deals shots out, changes what a shot is or asks for another image, before any file, thread, communicator or device is
+     * touched */
+    const int lsm = fdw_deck_int(deck, "lsm") > 0 ? fdw_deck_int(deck, "lsm") : 0;
+    const int lsm_mute = fdw_deck_has(deck, "lsm_mute") ? fdw_deck_int(deck, "lsm_mute") : 0;
+    if (lsm > 0) {
+        int sl = fdw_deck_int(deck, "slabs"), gp = fdw_deck_int(deck, "gpus");
+        if (getenv("FDW_SLABS")) sl = atoi(getenv("FDW_SLABS"));
+        if (getenv("FDW_GPUS")) gp = atoi(getenv("FDW_GPUS"));
+        const char *with = exc ? "exc=1" : (snap > 0 ? "snap" : (sl > 1 ? "slabs" : (pw > 0 ? "pw" : (gp > 1 ? "gpus" : (illum ? "illum=1" : (resid ? "resid=1" : (dtt ? "dtt=1" : NULL)))))));
+        if (with) {
+            fprintf(stderr, "lsm=%d cannot be combined with %s: the least-squares solve runs point-source shots on one full-grid context and forms its own residuals and "
+                            "DTT images; it has no snapshots, illumination, excitation image or slab / multi-GPU form\n", lsm, with);
+            return EXIT_FAILURE;
+        }
+        if (lsm_mute < 0) {
+            fprintf(stderr, "lsm_mute=%d: the number of muted interior columns must be >= 0\n", lsm_mute);
+            return EXIT_FAILURE;
+        }
+    }
+
     printf("## vp = %s, d_obs = %s, vel_ext_file = %s, vel_ext_flag = %d \n", vpfile, datfile, vel_ext_file, vel_ext_flag);
     printf("## nz = %d, nx = %d, nt = %d \n", nz, nx, nt);
     printf("## dz = %f, dx = %f, dt = %f \n", dz, dx, dt);
@@ -604,6 +631,52 @@ int main(int argc, char **argv)
         fdw_destroy(ctx);
         if (illum && write_illum_outputs(tmpdir, img, ill, ni, illum_eps) != 0) return EXIT_FAILURE;
         free(src_ix); free(lag); free(weight); free(wav); free(enc); free(v2); free(imloc); free(illoc); free(ill);
+        goto outputs;
+    }
+    if (lsm > 0) {
+        /* ---- lsm=N: dir.image = the model after N conjugate-gradient iterations from zero (fdw_lsm_solve with the verify pass); the mask is
+         * zero on the interior columns iz < lsm_mute.  <tmpdir>/dir.lsm_misfit: N + 2 doubles, the misfit history and last the recomputed
+         * misfit.  Border models as everywhere: drawn on the device per shot, or built here in shot order. ---- */
+        const int dev_models = !vel_ext_flag && !getenv("FDW_HOST_BORDER") && nxb != 1 && nzb != 1 && nzb <= nxe;      /* as dev_border below */
+        fdw_ctx *ctx = NULL;
+        if (fdw_create(&prm, 0, &ctx) != FDW_OK || (dev_models && fdw_model_resident(ctx, vp) != FDW_OK)) {
+            fprintf(stderr, "fdw_create: %s\n", fdw_last_error());
+            return EXIT_FAILURE;
+        }
+        float *v2 = dev_models ? NULL : (float *)malloc((size_t)ns * ne * sizeof(float)), *mask = lsm_mute > 0 ? (float *)malloc(ni * sizeof(float)) : NULL;
+        double *hist = (double *)calloc((size_t)lsm + 2, sizeof(double));
+        FILE *fh = open_out(tmpdir, "dir.lsm_misfit");
+        if ((!dev_models && !v2) || (lsm_mute > 0 && !mask) || !hist || !fh) {
+            fprintf(stderr, "out of host memory, or cannot open dir.lsm_misfit\n");
+            return EXIT_FAILURE;
+        }
+        for (int is = 0; is < ns && !dev_models; is++) {
+            const float *v = vpe;
+            if (vel_ext_flag) v = vel_ext_rnd + (size_t)is * ne;      /* R:484 */
+            else fdw_extendvel_linear(nx, nz, nxb, nzb, vpe);        /* R:486: the next draws of the one stream, in shot order */
+            for (size_t k = 0; k < ne; k++) v2[(size_t)is * ne + k] = v[k] * v[k];      /* R:490-494 */
+        }
+        for (int ix = 0; ix < nx && mask; ix++)
+            for (int iz = 0; iz < nz; iz++) mask[(size_t)ix * nz + iz] = iz < lsm_mute ? 0.0f : 1.0f;
+        printf("## lsm = %d, lsm_mute = %d: least-squares migration, conjugate gradients on DTT Born modelling and DTT imaging; dir.lsm_misfit \n", lsm, lsm_mute);
+        const double t0 = now_s();
+        if (fdw_lsm_solve(ctx, ns, v2, 0, sx[0], ds, sz, gz, srce, d_obs, mask, lsm, img, hist, 1, NULL) != FDW_OK) {
+            fprintf(stderr, "fdw_lsm_solve: %s\n", fdw_last_error());
+            return EXIT_FAILURE;
+        }
+        t_shots = now_s() - t0;
+        shots_per_launch = fdw_batch_parts(ctx) > 0 ? (ns + fdw_batch_parts(ctx) - 1) / fdw_batch_parts(ctx) : 1;
+        for (int k = 0; k <= lsm; k++) printf("## lsm: misfit after %d iterations = %.9e \n", k, hist[k]);
+        printf("## lsm: recomputed misfit = %.9e \n", hist[lsm + 1]);
+        fprintf(fnum, "======== %i ========\n", 0);
+        for (int iz = 0; iz < nz; iz++)
+            for (int ix = 0; ix < nx; ix++) fprintf(fnum, " %f \n", img[(size_t)ix * nz + iz]);
+        if (fwrite(hist, sizeof(double), (size_t)lsm + 2, fh) != (size_t)lsm + 2 || fclose(fh) != 0) {
+            fprintf(stderr, "cannot write dir.lsm_misfit\n");
+            return EXIT_FAILURE;
+        }
+        fdw_destroy(ctx);
+        free(v2); free(mask); free(hist);
         goto outputs;
     }
     if (exc) {
@@ -905,7 +978,7 @@ int main(int argc, char **argv)
 outputs:
     if (timing)
         fprintf(stderr, "[timing] shots per launch sequence: up to %d (%s)\n", shots_per_launch,
-                shots_per_launch > 1 ? (exc ? "fdw_shot_excitation_batch" : pw > 0 ? "fdw_shot_line_batch" : (resid ? "fdw_shot_batch_residual" : (illum ? "fdw_shot_batch_illum" : "fdw_shot_batch")))
+                shots_per_launch > 1 ? (lsm > 0 ? "fdw_lsm_solve" : exc ? "fdw_shot_excitation_batch" : pw > 0 ? "fdw_shot_line_batch" : (resid ? "fdw_shot_batch_residual" : (illum ? "fdw_shot_batch_illum" : "fdw_shot_batch")))
                                      : (resid ? "one by one, fdw_shot_residual" : "one by one"));
     if (timing)
         fprintf(stderr, "[timing] total %.3f s: shots (contexts, border models, propagation) %.3f s, stacking + image.num %.3f s, rest (deck, inputs) %.3f s\n",
