@@ -257,19 +257,20 @@ class Device:
         return self.f[self.names.get(role, role)].cpu().numpy()
 
 
-def check_image(dv, c, what):
-    """Every word of the device image: C against the restatement, the rest as it came, the sentinels in the padding columns."""
+def check_image(dv, c, what, same=assert_bit_equal):
+    """Every word of the device image: C against the restatement, the rest as it came (bit for bit), the sentinels in the padding columns.
+    same: the comparison with the restatement (value_classes.assert_same_nonfinite where the deck holds NaNs)."""
     d, F1, F0, img0, samples, want = c
     got = dv.whole("img")
     assert (got[:, d["nze"]:].view(np.uint32) == PAD).all(), "padding columns of the image, " + what
-    assert_bit_equal(got[:, :d["nze"]], want["img"], "image, " + what)
+    same(got[:, :d["nze"]], want["img"], "image, " + what)
     x0, x1, z0, z1 = born_cells(d)
     out = np.ones(img0.shape, bool)
     out[x0:x1, z0:z1] = False
     assert_bit_equal(got[:, :d["nze"]][out], img0[out], "image outside C, " + what)
 
 
-def run_and_check(make_ctx, c, what, restart=None, nsteps=NIT):
+def run_and_check(make_ctx, c, what, restart=None, nsteps=NIT, same=assert_bit_equal):
     """nsteps iterations and the tail (restart: a fresh context and fresh buffers holding the same words after that many iterations) against the
     restatement; both field pairs against fdw_dev_back_iter on copies."""
     d, F1, F0, img0, samples, want = c
@@ -286,12 +287,12 @@ def run_and_check(make_ctx, c, what, restart=None, nsteps=NIT):
         tw.iterate(k, dtt=False)
     dv.torch.cuda.synchronize()
     for role in ("f1", "f0", "pr", "ppr", "v2"):
-        assert_bit_equal(dv.whole(role), tw.whole(role), f"{role} vs fdw_dev_back_iter, " + what)
+        same(dv.whole(role), tw.whole(role), f"{role} vs fdw_dev_back_iter, " + what)
     assert (tw.whole("img") != dv.whole("img")).any()
     dv.tail(nsteps)
-    check_image(dv, c, what)
+    check_image(dv, c, what, same)
     for role in ("f1", "f0", "pr", "ppr", "v2"):
-        assert_bit_equal(dv.whole(role), tw.whole(role), f"{role} after the tail, " + what)
+        same(dv.whole(role), tw.whole(role), f"{role} after the tail, " + what)
     return dv
 
 
