@@ -928,6 +928,63 @@ int fdw_shot_batch_dtt(fdw_ctx *ctx, int nshots, const float *v2_all, unsigned l
 int fdw_shot_line_batch_dtt(fdw_ctx *ctx, int nshots, const float *v2_all, unsigned long long draw_offset, int sz, int gz, const float *wav_all,
                             const float *d_obs, float *imloc, float *illum, int residual, float *resid);
 
+/* ---- Extended imaging: subsurface-offset image gathers ------------------------------------------------------------------------------
+ * Every imaging condition above needs a migration velocity that is already right.  The extended image over subsurface offset says whether it
+ * is:   I(x, z, h) = sum_t F(x - h, z, t) (*) R(x + h, z, t).   With the right velocity the energy sits at h = 0, a velocity error spreads it
+ * over h.  The RTM dialect on full-grid contexts, EXACT and FAST numerics alike (FAST changes the Laplacian only).  C is the Born cell set,
+ * rows [x0, x1) x columns [z0, z1).
+ *
+ * For a half-width H, 0 <= H <= FDW_EXT_HMAX, the extended image is 2H+1 field-shaped planes, plane j = h + H; on the device they are
+ * contiguous, one fdw_field_bytes apart.  One term, for two fields f and r: for every h = -H .. H and every cell of C whose rows x - h and
+ * x + h both lie in [x0, x1)
+ *          E[h+H][x][z] = E[h+H][x][z] (+) ( f[x-h][z] (*) r[x+h][z] )          product and sum rounded separately in fp32, round to
+ * nearest, nothing fused, in both numerics.  Every other word of every plane keeps its bits: border, padding columns, cells outside the
+ * extents, and the |h| rows at either end of C.  No + 0.0f is applied, so a -0.0 survives.  No cell of C is ever damped: every operand is
+ * the raw word the buffers hold.
+ *
+ * The loop: the backward loop of fdw_shot, run as single fdw_dev_back_iter iterations on every context (as DTT imaging does; the forward
+ * loop keeps its family).  After iteration k = 0 .. nt-1 the term is added with f = F_k, the source field that iteration images (k < 2: the
+ * two snapshots), and r = r^{k+1}, the receiver field it stores, injected sample included; terms in ascending k.  Consequences: the plane
+ * h = 0 equals fdw_shot's imloc on the interior cells of C; imloc, P and PP equal fdw_shot's; all-zero data leave every plane as it came;
+ * swapping f and r mirrors the planes (the fp32 product commutes): E_{f,r}[h] == E_{r,f}[-h] bit for bit from equal entry planes.
+ *
+ * fdw_plan_ext_image  the row plan of one term; pure host code, no context, no device.  Rows [x0, x1) of nz columns in chunks of xchunk rows
+ *                     (0: automatic -- about 8192 waves of 256 columns where the grid has them, never below max(H, 2) nor above 64 rows;
+ *                     the length used goes to *xchunk_out).  Returns the number of chunks and fills chunks[0 .. n) (NULL: counts only; cap
+ *                     < n: FDW_EINVAL).  Per chunk: [c0, c1) the rows whose cells it accumulates into, [rd0, rd1) the rows of f and r it
+ *                     loads ([c0 - H, c1 + H) cut to [x0, x1): 2H run-in rows), and per plane j the rows it writes, [w0[j], w1[j]) (none:
+ *                     0, 0).  The launcher and the kernel form their rows with the same two inline functions (csrc/fdw_extimg.h): a
+ *                     shifted row index is the one way this kernel can read outside its arrays, and it is settled here, on the CPU.
+ * fdw_dev_ext_image   one term on caller-owned device arrays: d_f, d_r fields, d_eimg 2H+1 planes.  Everything goes on the given stream
+ *                     (NULL: the context's), nothing is synchronised, nothing is allocated.  FDW_EINVAL before anything is enqueued: a NULL
+ *                     pointer, H outside [0, FDW_EXT_HMAX], d_eimg overlapping an input (d_f may be d_r).  FDW_ESTATE: slab contexts, the
+ *                     sibling's dialects, a context inside a batch.  The chunk length follows fdw_set_tuning's xchunk when non-zero.
+ * fdw_shot_ext        one shot as defined above.  eimg [2H+1][nx][nz] is accumulated into, as imloc is (imloc NULL: not wanted), so a caller
+ *                     stacks shots by passing the same array.  The planes live on the device for the whole shot: allocated on first use,
+ *                     sized for the largest H seen, freed by fdw_destroy; without room the call fails with FDW_ENOMEM before the forward
+ *                     loop starts.  v2 NULL: the resident model.
+ *   Kernels (csrc/fdw_extimg.hip): fdw_ext_image_kernel<H, V, 0>, one instantiation per H and per lane width V (4 words where the arrays are
+ *   16-byte aligned, else 1).  Lanes run along z; a wave marches a chunk of rows along x with the last 2H+1 rows of f and of r in two
+ *   register rings with static indices, so every f and r word is read once per chunk and every plane row read and written once:
+ *   (2 + 2(2H+1)) * 4 B per point.  No LDS, no scratch, no atomics.  FDW_EXT_POINTWISE=1 (read when a context is created; benchmarks and
+ *   tests) runs the obvious alternative, one thread per cell reading its 2(2H+1) operands through the caches; the same bytes in every plane.
+ *   Measured on one MI355X (profiles/ext_image.json), 8192^2, H = 0 / 1 / 4 / 8: 224 / 436 / 1223 / 2132 us per term
+ *   (4.8 / 4.9 / 4.4 / 4.5 TB/s of the byte model; the one-step backward iteration reaches 5.3 TB/s there), the pointwise form 1.16 to
+ *   1.27 times that; 2048^2: 10 / 25 / 59 / 107 us.  fdw_shot_ext at 8192^2, nt 500, H = 4: 1.20 s (fdw_shot_dtt: 0.32 s).
+ * Out of scope: fusing the term into the backward kernels; the two-step and pipeline backward families; batched, line-source, residual and
+ * DTT forms; slabs and several GPUs; time-shift gathers; the offset-to-angle transform; an extended Born operator. */
+#define FDW_EXT_HMAX 8
+typedef struct fdw_ext_chunk {
+    int c0, c1;                          /* rows accumulated into */
+    int rd0, rd1;                        /* rows of f and r loaded */
+    int w0[2 * FDW_EXT_HMAX + 1];        /* plane j = h + H: rows written, [w0[j], w1[j]) */
+    int w1[2 * FDW_EXT_HMAX + 1];
+} fdw_ext_chunk;
+int fdw_plan_ext_image(int x0, int x1, int nz, int H, int xchunk, int *xchunk_out, fdw_ext_chunk *chunks, int cap);
+int fdw_dev_ext_image(fdw_ctx *ctx, const float *d_f, const float *d_r, int H, float *d_eimg, void *stream);
+int fdw_shot_ext(fdw_ctx *ctx, const float *v2 /* NULL: resident */, int sx, int sz, int gz, const float *srce, const float *d_obs, int H,
+                 float *imloc /* NULL ok */, float *eimg /* [2H+1][nx][nz], in/out */, float *P, float *PP);
+
 /* ---- Least-squares migration: conjugate gradients on Born modelling and DTT imaging ---------------------------------------------------
  * The layer that iterates: a device-resident conjugate-gradient solver for min_m 1/2 sum_s |L_s m - d_s|^2, L_s = FDW_BORN_DTT modelling of
  * shot s, L_s^T = DTT imaging with the two v2 weights.  Same dialect, contexts and numerics as the Born section (RTM dialect, full-grid

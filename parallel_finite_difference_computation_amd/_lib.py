@@ -47,6 +47,14 @@ class BandUnit(C.Structure):
                 ("wait", C.c_int * (PASS_DEPTH_MAX - 1))]
 
 
+EXT_HMAX = 8
+
+
+class ExtChunk(C.Structure):
+    """struct fdw_ext_chunk (fdwave.h): one chunk of fdw_plan_ext_image."""
+    _fields_ = [("c0", C.c_int), ("c1", C.c_int), ("rd0", C.c_int), ("rd1", C.c_int), ("w0", C.c_int * (2 * EXT_HMAX + 1)), ("w1", C.c_int * (2 * EXT_HMAX + 1))]
+
+
 # every symbol fdwave.h declares: (name, restype, argtypes)
 SIGNATURES = [
     ("fdw_last_error", C.c_char_p, []),
@@ -176,6 +184,9 @@ SIGNATURES = [
     ("fdw_shot_line_dtt", C.c_int, [vp, vp, C.c_int, C.c_int, f32p, f32p, f32p, vp, C.c_int, vp, vp, vp]),
     ("fdw_shot_batch_dtt", C.c_int, [vp, C.c_int, vp, C.c_ulonglong, C.c_int, C.c_int, C.c_int, C.c_int, f32p, f32p, f32p, vp, C.c_int, vp]),
     ("fdw_shot_line_batch_dtt", C.c_int, [vp, C.c_int, vp, C.c_ulonglong, C.c_int, C.c_int, f32p, f32p, f32p, vp, C.c_int, vp]),
+    ("fdw_plan_ext_image", C.c_int, [C.c_int] * 5 + [C.POINTER(C.c_int), vp, C.c_int]),
+    ("fdw_dev_ext_image", C.c_int, [vp, vp, vp, C.c_int, vp, vp]),
+    ("fdw_shot_ext", C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, f32p, f32p, C.c_int, vp, vp, vp, vp]),
     ("fdw_dev_dot_cells", C.c_int, [vp] * 6),
     ("fdw_dev_dot_gather", C.c_int, [vp] * 6),
     ("fdw_dev_lsm_gather", C.c_int, [vp, vp, vp, vp, C.c_int, vp, vp, vp, vp, vp]),

@@ -179,6 +179,17 @@ def plan_pass_cut(nxl, upd_x1, xchunk, cut_lo, cut_hi, npasses):
                                 for u in units]
 
 
+def plan_ext_image(x0, x1, nz, H, xchunk=0):
+    """fdw_plan_ext_image (fdwave.h): (xchunk used, chunks) of one extended-image term on rows [x0, x1) of nz columns; chunks[i] =
+    dict(c0, c1, rd0, rd1, writes) with writes[j] = (w0, w1), the rows of plane j = h + H that chunk writes (w0 == w1: none).  No device."""
+    used = C.c_int()
+    n = lib().fdw_plan_ext_image(x0, x1, nz, H, xchunk, C.byref(used), None, 0)
+    check(min(n, 0))
+    chunks = (_lib.ExtChunk * max(n, 1))()
+    check(min(lib().fdw_plan_ext_image(x0, x1, nz, H, xchunk, C.byref(used), chunks, n), 0))
+    return used.value, [dict(c0=k.c0, c1=k.c1, rd0=k.rd0, rd1=k.rd1, writes=[(k.w0[j], k.w1[j]) for j in range(2 * H + 1)]) for k in chunks[:n]]
+
+
 def planewave_lags(src_ix, dx, dt, p):
     """fdw_planewave_lags (fdwave.h): lag[s] = lround(p (src_ix[s] - src_ix[0]) dx / dt) - the smallest of them, in double; p in s/m."""
     src_ix = _i32(src_ix)
@@ -604,6 +615,27 @@ class FDWave:
         """One DTT image term on the interior cells: d_img += ((d_fa - d_fb) - (d_fb - d_fc)) * d_r (fdwave.h, fdw_dev_dtt_image): the tail of
         a device caller's loop, behind dev_step(MODE_PLAIN).  stream as dev_back_iter takes it."""
         check(lib().fdw_dev_dtt_image(self._h, d_fa, d_fb, d_fc, d_r, d_img, stream))
+
+    # ---- subsurface-offset image gathers (fdwave.h: "Extended imaging") ----
+    def dev_ext_image(self, d_f, d_r, H, d_eimg, stream=None):
+        """One term of the extended image on the Born cell set: plane h + H of d_eimg (2H+1 field-shaped planes, one field apart) +=
+        d_f[x-h] * d_r[x+h] wherever both rows lie in the cell set (fdwave.h, fdw_dev_ext_image).  stream as dev_back_iter takes it."""
+        check(lib().fdw_dev_ext_image(self._h, d_f, d_r, int(H), d_eimg, stream))
+
+    def shot_ext(self, v2, sx, sz, gz, srce, d_obs, H, eimg=None, imloc=None, want_image=True, want_fields=False):
+        """shot() (v2=None: the resident model) whose backward loop also accumulates the subsurface-offset extended image eimg[2H+1][nx][nz]
+        (from zero, or into `eimg`; fdwave.h, fdw_shot_ext).  Returns a dict: eimg, image (want_image) and P, PP (want_fields); image, P and PP
+        equal shot()'s bit for bit, and plane H of eimg equals the image on the interior cells of the Born cell set."""
+        shape = (2 * max(int(H), 0) + 1, self.nx, self.nz)      # (a negative H is the library's to refuse)
+        out = dict(eimg=np.zeros(shape, np.float32) if eimg is None else np.array(_f32(eimg, shape), order="C"))
+        if want_image:
+            out["image"] = np.zeros((self.nx, self.nz), np.float32) if imloc is None else np.array(_f32(imloc, (self.nx, self.nz)), order="C")
+        if want_fields:
+            out["P"], out["PP"] = np.zeros((self.nxe, self.nze), np.float32), np.zeros((self.nxe, self.nze), np.float32)
+        ptr = lambda k: out[k].ctypes.data if k in out else None      # noqa: E731
+        check(lib().fdw_shot_ext(self._h, None if v2 is None else _f32(v2, (self.nxe, self.nze)).ctypes.data, sx, sz, gz, _f32(srce, (self.nt,)),
+                                 _f32(d_obs, (self.nx, self.nt)), int(H), ptr("image"), ptr("eimg"), ptr("P"), ptr("PP")))
+        return out
 
     # ---- least-squares migration (fdwave.h: conjugate gradients on BORN_DTT modelling and DTT imaging) ----
     def dev_dot_cells(self, d_a, d_b, d_rows, d_sum, stream=None):

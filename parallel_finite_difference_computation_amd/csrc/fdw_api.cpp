@@ -20,6 +20,7 @@
 
 #include "fdw_born.h"
 #include "fdw_dtt.h"
+#include "fdw_extimg.h"
 #include "fdw_lsm.h"
 #include "fdw_excimg.h"
 #include "fdw_internal.h"
@@ -122,6 +123,9 @@ struct fdw_ctx {
     size_t born_rec0_cap = 0;
     float* d_dtt_w = nullptr;      // DTT imaging without the fused kernel: F_{i-2} (-) F_{i-1} on C, taken before the source step overwrites F_{i-2}
     float* d_born_w = nullptr;     // Born modelling without the fused kernel, FDW_BORN_DTT: (A - B) of the background on the interior cells
+    float* d_eimg = nullptr;       // fdw_shot_ext: the planes of the extended image, eimg_planes fields; allocated on first use, sized for the largest H seen
+    int eimg_planes = 0;
+    int ext_pointwise = 0;         // benchmarks / tests: the extended-image term one thread per cell instead of the march -- FDW_EXT_POINTWISE=1
     float* b_born_rec0 = nullptr;  // fdw_born_shot_batch with data0: the shots' background gathers [shots][nt][nx]; allocated on first use
     size_t b_born_rec0_cap = 0;
     // least-squares migration (fdw_lsm_visit, fdw_lsm_solve); allocated on first use
@@ -251,6 +255,7 @@ extern "C" int fdw_create_slab(const fdw_params* prm, const fdw_slab* slab, int 
     if (const char* nf = getenv("FDW_NO_BACK_PIPE")) c->no_back_pipe = atoi(nf);
     if (const char* nf = getenv("FDW_NO_BORN_FUSED")) c->no_born_fused = atoi(nf);
     if (const char* nf = getenv("FDW_NO_BACK_FUSED")) c->no_back_fused = atoi(nf);
+    if (const char* nf = getenv("FDW_EXT_POINTWISE")) c->ext_pointwise = atoi(nf);
     if (const char* pad = getenv("FDW_PITCH_PAD")) {   // experiment knob: extra floats per row (multiple of 4)
         const int extra = atoi(pad);
         if (extra > 0 && extra % 4 == 0) c->pitch += extra;
@@ -406,7 +411,7 @@ extern "C" void fdw_destroy(fdw_ctx* c)
                      c->fld[4], c->fld[5], c->fld[6], c->fld[7], c->fld[8], c->fld[9], c->d_v2, c->d_img, c->d_illum, c->d_srce, c->d_dobs, c->d_rec,
                      c->d_vp, c->d_vpe, (float*)c->d_draws, (float*)c->d_jump, c->bfld[0], c->bfld[1], c->bfld[2], c->bfld[3],
                      c->bfld[4], c->bfld[5], c->bfld[6], c->bfld[7], c->b_v2, c->b_img, c->b_dobs, c->b_illum, c->b_rec, c->b_wav, c->d_raw, c->d_wav, c->d_snap[0], c->d_snap[1], c->d_snap[2], c->d_amp, (float*)c->d_texc, c->d_exc, (float*)c->d_peak,
-                     c->d_born_m, c->d_born_rec0, c->d_born_w, c->b_born_rec0, c->d_dtt_w,
+                     c->d_born_m, c->d_born_rec0, c->d_born_w, c->b_born_rec0, c->d_dtt_w, c->d_eimg,
                      c->d_lsm_f[0], c->d_lsm_f[1], c->d_lsm_f[2], c->d_lsm_f[3], c->d_lsm_f[4], c->d_lsm_f[5], c->d_lsm_dobs, c->d_lsm_res, c->d_lsm_d};
     for (float* b : bufs)
         if (b) (void)hipFree(b);
@@ -888,6 +893,37 @@ extern "C" int fdw_dev_dtt_image(fdw_ctx* c, const float* d_fa, const float* d_f
     if (!d_fa || !d_fb || !d_fc || !d_r || !d_img) return fail(FDW_EINVAL, "fdw_dev_dtt_image: NULL buffer");
     HIP_TRY(hipSetDevice(c->device));
     return dtt_image(c, d_fa, d_fb, d_fc, d_r, d_img, 0, pick_stream(c, stream));
+}
+
+// ---- subsurface-offset image gathers (definitions in fdwave.h, "Extended imaging") ----
+// one term on C: plane h + H of d_eimg += f[x-h] (*) r[x+h], h = -H .. H
+static int ext_image(fdw_ctx* c, const float* d_f, const float* d_r, int H, float* d_eimg, hipStream_t s)
+{
+    const BornCells C = born_cells(c);
+    hipError_t e = launch_ext_image(d_f, d_r, d_eimg, H, c->pitch, field_elems(c), C.x0, C.x1, C.z0, C.z1, c->xchunk, c->ext_pointwise != 0, s);
+    if (e != hipSuccess) return fail(FDW_EHIP, "extended image launch failed: %s", hipGetErrorString(e));
+    return FDW_OK;
+}
+
+static int check_ext_ctx(const fdw_ctx* c, const char* who, int H)
+{
+    if (c->prm.dialect != FDW_DIALECT_RTM) return fail(FDW_ESTATE, "%s: extended imaging belongs to the RTM dialect (the sibling's dialects do not combine with it)", who);
+    if (!is_full_grid(c)) return fail(FDW_ESTATE, "%s: extended imaging: full-grid contexts only (slab contexts do not combine with it)", who);
+    if (c->nbatch > 1) return fail(FDW_ESTATE, "%s: not inside a batch of shots", who);
+    if (H < 0 || H > FDW_EXT_HMAX) return fail(FDW_EINVAL, "%s: H=%d outside [0,%d]", who, H, FDW_EXT_HMAX);
+    return FDW_OK;
+}
+
+extern "C" int fdw_dev_ext_image(fdw_ctx* c, const float* d_f, const float* d_r, int H, float* d_eimg, void* stream)
+{
+    if (!c) return fail(FDW_EINVAL, "ctx is NULL");
+    FDW_TRY(check_ext_ctx(c, "fdw_dev_ext_image", H));
+    if (!d_f || !d_r || !d_eimg) return fail(FDW_EINVAL, "fdw_dev_ext_image: NULL buffer");
+    const uintptr_t fb = fdw_field_bytes(c), e0 = (uintptr_t)d_eimg, e1 = e0 + (uintptr_t)(2 * H + 1) * fb;
+    for (const float* in : {d_f, d_r})
+        if ((uintptr_t)in < e1 && (uintptr_t)in + fb > e0) return fail(FDW_EINVAL, "fdw_dev_ext_image: the planes of d_eimg overlap an input field");
+    HIP_TRY(hipSetDevice(c->device));
+    return ext_image(c, d_f, d_r, H, d_eimg, pick_stream(c, stream));
 }
 
 extern "C" int fdw_dev_laplacian(fdw_ctx* c, const float* d_p, float* d_lap, void* stream)
@@ -2094,7 +2130,10 @@ static int image_to_host(fdw_ctx* c, float* imloc, const float* d_src)
 // does not change), and after iteration k the frames of F_k and r^{k+1} go into the frame stores at index L / every - 1.
 // dtt (fdw_shot_dtt and its kin): single iterations of back_iter_dtt -- no pairs, no pipeline -- and the tail of two source-only
 // reconstructions into the spare source buffers with their two image terms (fdwave.h, "DTT imaging").
-static int back_loop(fdw_ctx* c, float* const src[4], float* const rcv[4], int gz, int nsteps, const SnapPlan& sn, bool dtt = false)
+// ext_H >= 0 (fdw_shot_ext): single iterations of back_iter too, and after iteration k the term F_k, r^{k+1} of the extended image into the
+// planes d_eimg (fdwave.h, "Extended imaging").
+static int back_loop(fdw_ctx* c, float* const src[4], float* const rcv[4], int gz, int nsteps, const SnapPlan& sn, bool dtt = false, int ext_H = -1,
+                     float* d_eimg = nullptr)
 {
     FDW_RANGE("fdw: backward loop + imaging (fd_back)");
     const int nt = c->prm.nt;
@@ -2103,8 +2142,9 @@ static int back_loop(fdw_ctx* c, float* const src[4], float* const rcv[4], int g
     int f1 = 0, f0 = 1;          // indices into src of F_{k-1} (newer) and F_{k-2}: before iteration 2 these are snap0, snap1
     int rn = 0, ro = 1;          // indices into rcv of r^k (d_pr) and r^{k-1} (d_ppr)
     int it = 0;
-    const bool pairs = two_step_pays(c) && !dtt;
-    const bool pipe = fdw_back_pipe_active(c) && c->nbatch <= 1 && !dtt;
+    const bool single = dtt || ext_H >= 0;
+    const bool pairs = two_step_pays(c) && !single;
+    const bool pipe = fdw_back_pipe_active(c) && c->nbatch <= 1 && !single;
     if (dtt) FDW_TRY(ensure_dtt_scratch(c));
     std::vector<int> stops;      // ascending iterations after which frames are taken
     if (sn.store[1] || sn.store[2])
@@ -2151,6 +2191,8 @@ static int back_loop(fdw_ctx* c, float* const src[4], float* const rcv[4], int g
                                                       c->d_img, c->stream));
             if (it >= 2) std::swap(f1, f0);
             std::swap(rn, ro);
+            // F_k: u^nt (src[1]) at k = 0, then the newer of the source pair; r^{k+1}: the newer receiver field
+            if (ext_H >= 0) FDW_TRY(ext_image(c, it == 0 ? src[1] : src[f1], rcv[rn], ext_H, d_eimg, c->stream));
             it += 1;
         }
         if (next < stops.size() && it == stops[next] + 1) {
@@ -2229,6 +2271,7 @@ struct ShotExtras {      // what a shot does beyond fdw_shot's; of a batch every
     bool residual = false;     // fdw_shot_residual: the forward loop records the modelled gather (c->d_rec; a batch: b_rec [shot][nt][nx]), which turns
     float* resid = nullptr;    // the data gather into d_obs - d_mod in place before the backward loop reads it; resid: NULL, or [nx][nt] that difference
     bool dtt = false;          // fdw_shot_dtt and its kin: the backward loop images with the second time difference of the source field (back_loop)
+    int ext_H = -1;            // fdw_shot_ext: >= 0, the half-width of the extended image the backward loop accumulates into c->d_eimg; imloc may be NULL
     ShotExtras of_shot(size_t b, size_t ni, size_t ng) const { ShotExtras x = *this; if (illum) x.illum += b * ni; if (resid) x.resid += b * ng; return x; }
 };
 // the uploaded source as the forward loop takes it: the wavelet in c->d_srce, or (line) the gathers transposed to [shot][nt][nx] in d_wav
@@ -2238,7 +2281,7 @@ static Forward device_source(const fdw_ctx* c, bool line, int sx, int sz, const 
 static int shot_impl(fdw_ctx* c, const float* v2, int sx, int sz, int gz, const float* samples, const float* d_obs, float* imloc, float* P, float* PP,
                      const ShotExtras& x)
 {
-    if (!c || !samples || !d_obs || !imloc) return fail(FDW_EINVAL, "NULL argument");
+    if (!c || !samples || !d_obs || (!imloc && x.ext_H < 0)) return fail(FDW_EINVAL, "NULL argument");
     if (x.residual) FDW_TRY(check_record_depth(c, gz));
     FDW_RANGE("fdw: shot (uploads, forward, backward, image download)");
     if (!is_full_grid(c)) return fail(FDW_EINVAL, "fdw_shot needs a full-grid context");
@@ -2251,7 +2294,7 @@ static int shot_impl(fdw_ctx* c, const float* v2, int sx, int sz, int gz, const 
     HIP_TRY(hipMemsetAsync(c->fld[0], 0, field_elems(c) * sizeof(float), c->stream));    // R:496-497
     HIP_TRY(hipMemsetAsync(c->fld[1], 0, field_elems(c) * sizeof(float), c->stream));
     if ((v2 && (rc = upload_rows(c, c->d_v2, v2, c->stream))) || (rc = x.line ? upload_line_source(c, samples) : upload_source(c, samples, nt)) ||
-        (rc = upload_gather(c, d_obs)) || (rc = image_to_device(c, imloc, c->d_img)))
+        (rc = upload_gather(c, d_obs)) || (rc = imloc ? image_to_device(c, imloc, c->d_img) : zero_fields(c, &c->d_img, 1)))
         return rc;
     if (x.illum && ((rc = alloc_zero(&c->d_illum, field_elems(c))) || (rc = image_to_device(c, x.illum, c->d_illum)))) return rc;
     if (x.residual && (rc = ensure_cap(&c->d_rec, &c->rec_cap, (size_t)c->nx * nt))) return rc;
@@ -2267,8 +2310,8 @@ static int shot_impl(fdw_ctx* c, const float* v2, int sx, int sz, int gz, const 
     float* src[4];
     source_buffers(c, ip, ipp, src);
     if ((rc = zero_fields(c, c->fld + 4, 2))) return rc;
-    if ((rc = back_loop(c, src, c->fld + 4, gz, nt, x.snaps, x.dtt))) return rc;
-    if ((rc = image_to_host(c, imloc, c->d_img))) return rc;
+    if ((rc = back_loop(c, src, c->fld + 4, gz, nt, x.snaps, x.dtt, x.ext_H, c->d_eimg))) return rc;
+    if (imloc && (rc = image_to_host(c, imloc, c->d_img))) return rc;
     HIP_TRY(hipStreamSynchronize(c->stream));
     return FDW_OK;
 }
@@ -4026,6 +4069,47 @@ extern "C" int fdw_shot_line_batch_dtt(fdw_ctx* c, int nshots, const float* v2_a
     x.line = true;
     return shot_batch_in_parts(c, "fdw_shot_line_batch_dtt", nshots, v2_all, draw_offset, -1, 0, sz, gz, wav_all, d_obs, imloc, x, illum ? 12 : 11,
                                residual ? 2 : 1);
+}
+
+// ------------------------------------------------------------------------------------------------
+// the shot that accumulates the subsurface-offset extended image (definitions in fdwave.h, "Extended imaging")
+// ------------------------------------------------------------------------------------------------
+extern "C" int fdw_shot_ext(fdw_ctx* c, const float* v2, int sx, int sz, int gz, const float* srce, const float* d_obs, int H, float* imloc, float* eimg,
+                            float* P, float* PP)
+{
+    if (!c) return fail(FDW_EINVAL, "ctx is NULL");
+    FDW_TRY(check_ext_ctx(c, "fdw_shot_ext", H));
+    FDW_TRY(has_model(c, v2));
+    if (!srce || !d_obs || !eimg) return fail(FDW_EINVAL, "fdw_shot_ext: NULL argument");
+    if (c->nx <= 0 || c->nz <= 0) return fail(FDW_EINVAL, "no interior to image");
+    HIP_TRY(hipSetDevice(c->device));
+    const int planes = 2 * H + 1;
+    const size_t fe = field_elems(c);
+    if (c->eimg_planes < planes) {      // the planes of the largest H seen, before anything is enqueued
+        if (c->d_eimg) (void)hipFree(c->d_eimg);
+        c->d_eimg = nullptr;
+        c->eimg_planes = 0;
+        hipError_t e = hipMalloc((void**)&c->d_eimg, (size_t)planes * fe * sizeof(float));
+        if (e != hipSuccess) {
+            c->d_eimg = nullptr;
+            size_t free_b = 0, total_b = 0;
+            (void)hipMemGetInfo(&free_b, &total_b);
+            return fail(FDW_ENOMEM, "fdw_shot_ext: the planes do not fit: %d planes x %zu bytes = %zu bytes, %zu bytes free on the device", planes,
+                        fe * sizeof(float), (size_t)planes * fe * sizeof(float), free_b);
+        }
+        c->eimg_planes = planes;
+    }
+    FDW_TRY(ensure_work_buffers(c, 8, true));
+    end_residency(c, v2);
+    const size_t ni = (size_t)c->nx * c->nz;
+    for (int j = 0; j < planes; j++) FDW_TRY(image_to_device(c, eimg + j * ni, c->d_eimg + j * fe));
+    ShotExtras x;
+    x.ext_H = H;
+    FDW_TRY(shot_impl(c, v2, sx, sz, gz, srce, d_obs, imloc, P, PP, x));
+    // (shot_impl has synchronised: the copies below are the only work left on the stream)
+    for (int j = 0; j < planes; j++) FDW_TRY(image_to_host(c, eimg + j * ni, c->d_eimg + j * fe));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return FDW_OK;
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -61,7 +61,13 @@
  * difference of the source field instead of the cross-correlation (fdwave.h, "DTT imaging": fdw_shot_dtt, fdw_shot_batch_dtt, with pw
  * fdw_shot_line_dtt / fdw_shot_line_batch_dtt).  It composes with resid=1 (dir.image is then the gradient of the DTT Born misfit, up to the
  * two v2 weights of fdwave.h), illum=1, pw=NP, batching and gpus=N; every output other than the images keeps its bytes.  dtt=1 together
- * with exc=1, snap > 0 or slabs > 1 (deck or environment) is refused before anything is opened. */
+ * with exc=1, snap > 0 or slabs > 1 (deck or environment) is refused before anything is opened.
+ *
+ * Extended imaging (no counterpart in the reference): the deck key `ext=H`, 1 <= H <= 8 (absent or 0: nothing changes), also writes
+ * <tmpdir>/dir.image_ext, the subsurface-offset extended image [2H+1][nx][nz] stacked in shot order (fdwave.h, "Extended imaging":
+ * fdw_shot_ext, the shots one by one on one context, all into the same planes).  dir.image, dir.image_lap and image.num are byte for byte
+ * what the run without the key writes.  ext together with exc, dtt, lsm, pw, slabs, gpus, snap, resid or illum is refused before anything
+ * is opened. */
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -469,6 +475,26 @@ int main(int argc, char **argv)
         }
     }
 
+    /* our extension (absent or 0: nothing changes): ext=H, the subsurface-offset extended image of half-width H (fdwave.h, "Extended
+     * imaging").  The shots go one by one through fdw_shot_ext on one full-grid context: refused with every key that deals shots out,
+     * changes what a shot is or asks for another image, before any file, thread, communicator or device is touched */
+    const int ext = fdw_deck_int(deck, "ext") > 0 ? fdw_deck_int(deck, "ext") : 0;
+    if (ext > 0) {
+        int sl = fdw_deck_int(deck, "slabs"), gp = fdw_deck_int(deck, "gpus");
+        if (getenv("FDW_SLABS")) sl = atoi(getenv("FDW_SLABS"));
+        if (getenv("FDW_GPUS")) gp = atoi(getenv("FDW_GPUS"));
+        const char *with = exc ? "exc=1" : (dtt ? "dtt=1" : (lsm > 0 ? "lsm" : (pw > 0 ? "pw" : (sl > 1 ? "slabs" : (gp > 1 ? "gpus" : (snap > 0 ? "snap" : (resid ? "resid=1" : (illum ? "illum=1" : NULL))))))));
+        if (with) {
+            fprintf(stderr, "ext=%d cannot be combined with %s: the extended image is accumulated by single point-source cross-correlation shots on one full-grid "
+                            "context; it has no batched, line-source, residual, DTT, excitation, snapshot, illumination or slab / multi-GPU form\n", ext, with);
+            return EXIT_FAILURE;
+        }
+        if (ext > FDW_EXT_HMAX) {
+            fprintf(stderr, "ext=%d: the half-width must lie in [0, %d]\n", ext, FDW_EXT_HMAX);
+            return EXIT_FAILURE;
+        }
+    }
+
     printf("## vp = %s, d_obs = %s, vel_ext_file = %s, vel_ext_flag = %d \n", vpfile, datfile, vel_ext_file, vel_ext_flag);
     printf("## nz = %d, nx = %d, nt = %d \n", nz, nx, nt);
     printf("## dz = %f, dx = %f, dt = %f \n", dz, dx, dt);
@@ -677,6 +703,63 @@ int main(int argc, char **argv)
         }
         fdw_destroy(ctx);
         free(v2); free(mask); free(hist);
+        goto outputs;
+    }
+    if (ext > 0) {
+        /* ---- ext=H: the shots one by one through fdw_shot_ext on one context, every shot accumulating into the same 2H+1 planes;
+         * <tmpdir>/dir.image_ext is [2H+1][nx][nz], the shots stacked in shot order.  dir.image, dir.image_lap and image.num are what the
+         * run without the key writes: each shot's image from zero, added to the running sum on the host.  Border models as everywhere. ---- */
+        const int dev_models = !vel_ext_flag && !getenv("FDW_HOST_BORDER") && nxb != 1 && nzb != 1 && nzb <= nxe;      /* as dev_border below */
+        const long long draws = fdw_border_draws(nx, nz, nxb, nzb);
+        const size_t np = (size_t)(2 * ext + 1) * ni;
+        fdw_ctx *ctx = NULL;
+        if (fdw_create(&prm, 0, &ctx) != FDW_OK || (dev_models && fdw_model_resident(ctx, vp) != FDW_OK)) {
+            fprintf(stderr, "fdw_create: %s\n", fdw_last_error());
+            return EXIT_FAILURE;
+        }
+        float *v2 = dev_models ? NULL : (float *)malloc(ne * sizeof(float)), *imloc = (float *)malloc(ni * sizeof(float));
+        float *eimg = (float *)calloc(np, sizeof(float));
+        FILE *fext = open_out(tmpdir, "dir.image_ext");
+        if ((!dev_models && !v2) || !imloc || !eimg || !fext) {
+            fprintf(stderr, "out of host memory, or cannot open dir.image_ext\n");
+            return EXIT_FAILURE;
+        }
+        printf("## ext = %d: subsurface-offset extended image, %d planes of %d x %d in dir.image_ext \n", ext, 2 * ext + 1, nx, nz);
+        const double t0 = now_s();
+        for (int is = 0; is < ns; is++) {
+            int rc = FDW_OK;
+            if (dev_models) {
+                rc = fdw_dev_extendvel_linear(ctx, (unsigned long long)is * (unsigned long long)draws, NULL);      /* R:486: the next draw of the stream */
+            } else {
+                const float *v = vpe;
+                if (vel_ext_flag) v = vel_ext_rnd + (size_t)is * ne;      /* R:484 */
+                else fdw_extendvel_linear(nx, nz, nxb, nzb, vpe);        /* R:486: the next draws of the one stream, in shot order */
+                for (size_t k = 0; k < ne; k++) v2[k] = v[k] * v[k];      /* R:490-494 */
+            }
+            memset(imloc, 0, ni * sizeof(float));                        /* R:515 */
+            if (rc == FDW_OK) rc = fdw_shot_ext(ctx, v2, sx[is], sz, gz, srce, d_obs + (size_t)is * nx * nt, ext, imloc, eimg, NULL, NULL);
+            if (rc != FDW_OK) {
+                fprintf(stderr, "shot %d: %s\n", is + 1, fdw_last_error());
+                return EXIT_FAILURE;
+            }
+            fprintf(stdout, "** source %d, at (%d,%d) \n", is + 1, sx[is] - nxb, sz - nzb);
+            fprintf(stdout, "\n");
+            fprintf(stdout, "** backward propagation %d, at (%d,%d) \n", is + 1, sx[is] - nxb, sz - nzb);
+            fprintf(stdout, "\n");
+            fprintf(fnum, "======== %i ========\n", is); /* R:522-528: iz outer, ix inner, running sum */
+            for (int iz = 0; iz < nz; iz++)
+                for (int ix = 0; ix < nx; ix++) {
+                    img[(size_t)ix * nz + iz] += imloc[(size_t)ix * nz + iz];
+                    fprintf(fnum, " %f \n", img[(size_t)ix * nz + iz]);
+                }
+        }
+        t_shots = now_s() - t0;
+        if (fwrite(eimg, sizeof(float), np, fext) != np || fclose(fext) != 0) {
+            fprintf(stderr, "cannot write dir.image_ext\n");
+            return EXIT_FAILURE;
+        }
+        fdw_destroy(ctx);
+        free(v2); free(imloc); free(eimg);
         goto outputs;
     }
     if (exc) {

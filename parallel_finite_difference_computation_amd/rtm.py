@@ -46,7 +46,7 @@ def read_deck(path):
         d = dict(tmpdir=s("tmpdir"), vpfile=s("vpfile"), datfile=s("datfile"), vel_ext_file=s("vel_ext_file"),
                  nz=i("nz"), nx=i("nx"), nt=i("nt"), ns=i("ns"), sz=i("sz"), fsx=i("fsx"), ds=i("ds"), gz=i("gz"),
                  order=i("order"), nzb=i("nzb"), nxb=i("nxb"), dz=f("dz"), dx=f("dx"), dt=f("dt"), fpeak=f("fpeak"), fac=f("fac"),
-                 numerics=i("numerics"), illum=i("illum"), snap=i("snap"), resid=i("resid"), pw=i("pw"), exc=i("exc"), dtt=i("dtt"), lsm=i("lsm"))
+                 numerics=i("numerics"), illum=i("illum"), snap=i("snap"), resid=i("resid"), pw=i("pw"), exc=i("exc"), dtt=i("dtt"), lsm=i("lsm"), ext=i("ext"))
     finally:
         L.fdw_deck_free(h)
     if d["illum"] == 1:      # rtm_code's key: this driver would silently write neither dir.illum nor dir.image_illum
@@ -63,6 +63,8 @@ def read_deck(path):
         raise ValueError("the deck sets dtt=1: the shot-parallel Python driver has no DTT imaging; run bin/rtm_code")
     if d["lsm"] > 0:        # rtm_code's key: this driver would silently write a migration image instead of the least-squares one
         raise ValueError(f"the deck sets lsm={d['lsm']}: the shot-parallel Python driver has no least-squares migration; run bin/rtm_code")
+    if d["ext"] > 0:        # rtm_code's key: this driver would silently leave dir.image_ext unwritten
+        raise ValueError(f"the deck sets ext={d['ext']}: the shot-parallel Python driver forms no extended image; run bin/rtm_code")
     for key, default in (("ns", 1), ("sz", 0), ("fsx", 0), ("ds", 1), ("gz", 0), ("order", 8), ("nzb", 40), ("nxb", 40)):
         if d[key] == -1:
             d[key] = default

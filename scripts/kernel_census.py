@@ -46,7 +46,7 @@ MODULES = collections.OrderedDict([
     ("test_slabs_gpu", 180), ("test_fast_numerics", 180), ("test_programs", 600), ("test_kernel_census", 180), ("test_snaps", 180),
     ("test_residual", 180), ("test_residual_batch", 180), ("test_line_source", 180), ("test_line_batch", 180), ("test_excitation", 300),
     ("test_excitation_batch", 180), ("test_born", 180), ("test_born_batch", 300), ("test_dtt", 180),
-    ("test_lsm", 180), ("test_value_domain_inverse", 180),
+    ("test_lsm", 180), ("test_value_domain_inverse", 180), ("test_ext_image", 180),
 ])
 # modules whose GPU tests compare device output with the oracle or a restatement of it (test_programs runs the programs end to end)
 PARITY_MODULES = tuple(m for m in MODULES if m != "test_programs")
